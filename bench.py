@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- images/sec of the fake-quant training path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line; "roofline", "extras" and "cpu_baseline"
+(below) are measured with --full only.  --dump-outputs DIR writes what the last timed step computed, as a caller of the
+path receives it: DIR/out.npy (a fixed seeded sample of 2^22 of the forward output's elements, float32) and DIR/ds.npy
+(the learned-scale gradient; dP is dy itself and not an output).  Inputs are generated from fixed seeds, so two builds
+given the same arguments can be compared output for output.
 
 Workload: synthetic conv-activation batch
 256 x 3 x 224 x 224 fp32 per GPU (x ~ U[0,255), dy ~ N(0,1e-3), seed 42), per-channel scales
@@ -18,7 +24,7 @@ With N > 1 ranks (one process per GPU, torch.distributed "nccl" = RCCL over xGMI
 processes its own 256-image shard (weak scaling) and the learned-scale gradient is all-reduced
 each step -- the only exchange this path has.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) including
+Prints ONE JSON line on rank 0 (contract in the task statement); with --full it also holds
   "roofline":     K1, K2 and K4 each timed live with HIP events on the launch stream in a dedicated region right after
                   the timed loop: a FIXED number of isolated launches per kernel (independent of --steps), the
                   events stamped by the kernel dispatch itself (lq_profile_events -> hipExtLaunchKernelGGL), so
@@ -83,7 +89,26 @@ def parse():
                          "one-rank communicator; the fallback when the capture fails, and the default on other backends) or async "
                          "(eager, RCCL side stream + events: ~27 us/step)")
     ap.add_argument("--force-dist", action="store_true", help="initialise torch.distributed even with one rank (exercises the RCCL path)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also measure the roofline leg, the extras and the CPU baseline after the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (rank 0) as DIR/out.npy (fixed seeded sample) and DIR/ds.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_SAMPLE = 1 << 22                           # elements of `out` written by --dump-outputs (16 MB of float32)
+
+
+def dump_outputs(path: str, out: torch.Tensor, ds: torch.Tensor) -> None:
+    """`out` is 154 MB: a fixed seeded sample of its elements (sorted indices, the same in every run) stands for it."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    idx = np.sort(np.random.default_rng(0).integers(0, out.numel(), DUMP_SAMPLE))
+    sample = out.reshape(-1)[torch.from_numpy(idx).to(out.device)]
+    np.save(os.path.join(path, "out.npy"), sample.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, "ds.npy"), ds.cpu().numpy().astype(np.float32))
 
 
 def cpu_baseline(lam: float, budget_s: float):
@@ -358,86 +383,118 @@ def main():
         exchange_form = "sync"
 
     def run_steps(n):
-        """n steps of the path: eager launches, or replays of the S-step graph plus one remainder graph."""
+        """n steps of the path: eager launches, or replays of the S-step graph plus one remainder graph.  Returns the
+        (buffer set, gradient buffer) the last of them wrote."""
         if graphs is None:
             for i in range(n):
                 step(i)
-            return
+            return (n - 1) % nsets, (n - 1) & 1
         S = max(graphs)
         for _ in range(n // S):
             graphs[S].replay()
         if n % S:
             graphs[n % S].replay()
+        j = (n % S or S) - 1                               # the last step's index inside the graph that ran last (capture())
+        return j % nsets, (j if use_dist and args.graph_edges == "fork_only" else j & 1)
 
     run_steps(args.warmup)
     fence()
     t0 = time.perf_counter()
-    run_steps(args.steps)
+    last_k, last_b = run_steps(args.steps)
     fence()
     elapsed = time.perf_counter() - t0
     if use_dist:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outs[last_k], dss[last_b])     # before the --full legs reuse the buffers
+    step_bytes = BYTES_FWD + BYTES_BWD if args.variant == "split" else BYTES_FUSED
 
-    # ---- roofline leg: every kernel of the path, ROOF_SAMPLES launches each, independent of --steps.  The kernels are
-    # launched through the ABI with lq_profile_events(start, stop): hipExtLaunchKernelGGL stamps the two events with the
-    # kernel's own begin and end (the duration rocprofv3 reports) -- no event-record cost inside the interval, the finalize
-    # launch of the two-launch calls outside it, and no marker packets between the launches: the stream sees the same
-    # back-to-back kernel sequence as in the timed loop.
-    ROOF_SAMPLES = 64
-    Ev = lambda: torch.cuda.Event(enable_timing=True)          # noqa: E731
+    roofline = None
+    if args.full:
+        # ---- roofline leg: every kernel of the path, ROOF_SAMPLES launches each, independent of --steps.  The kernels are
+        # launched through the ABI with lq_profile_events(start, stop): hipExtLaunchKernelGGL stamps the two events with the
+        # kernel's own begin and end (the duration rocprofv3 reports) -- no event-record cost inside the interval, the finalize
+        # launch of the two-launch calls outside it, and no marker packets between the launches: the stream sees the same
+        # back-to-back kernel sequence as in the timed loop.
+        ROOF_SAMPLES = 64
+        Ev = lambda: torch.cuda.Event(enable_timing=True)          # noqa: E731
 
-    def stamped(n):
-        evs = [(Ev(), Ev()) for _ in range(n)]
-        for a, b in evs:                                       # torch creates the hipEvent_t lazily, at the first record
-            a.record(stream)
-            b.record(stream)
-        return evs
+        def stamped(n):
+            evs = [(Ev(), Ev()) for _ in range(n)]
+            for a, b in evs:                                       # torch creates the hipEvent_t lazily, at the first record
+                a.record(stream)
+                b.record(stream)
+            return evs
 
-    nroof = ROOF_SAMPLES + 4                                   # the first four warm the path and are dropped
-    e1, e2, e4 = stamped(nroof), stamped(nroof), stamped(nroof)
-    torch.cuda.synchronize(dev)
-    rc = 0
-    for j in range(nroof):                                     # the split step as in the timed loop, back to back: K1, K2 (+K3), ...
-        k = j % nsets
-        lib.lq_profile_events(e1[j][0].cuda_event, e1[j][1].cuda_event)
-        rc |= fwd(px[k], ps, pout[k], None, 0, outer, G, inner, sp)
-        lib.lq_profile_events(e2[j][0].cuda_event, e2[j][1].cuda_event)
-        rc |= bwd(px[k], ps, pdy[k], lam, pds, None, pws, ws_bytes, outer, G, inner, sp)
-    for j in range(nroof):                                     # the fused single-pass step, back to back
-        k = j % nsets
-        lib.lq_profile_events(e4[j][0].cuda_event, e4[j][1].cuda_event)
-        rc |= fused(px[k], ps, pdy[k], lam, pout[k], pds, pws, ws_bytes, outer, G, inner, sp)
-    lib.lq_profile_events(None, None)
-    if rc:
-        _hip.check(rc, "roofline leg")
-    torch.cuda.synchronize(dev)
-    mean_us = lambda prs: sum(a.elapsed_time(b) for a, b in prs[4:]) / len(prs[4:]) * 1e3      # noqa: E731
-    t_k1, t_k2, t_k4 = mean_us(e1), mean_us(e2), mean_us(e4)
-    kernels = {}
-    for name, t_us, nbytes in (("K1 k_flat_fwd<OP_FWD> (lq_fq_forward)", t_k1, BYTES_FWD),
-                               ("K2 k_row_stream<OP_BWD> (lq_fq_scale_grad, traversal)", t_k2, BYTES_BWD),
-                               ("K4 k_row_stream<OP_FUSED> (lq_fq_fwd_bwd_fused, traversal)", t_k4, BYTES_FUSED)):
-        gbs = nbytes / (t_us * 1e-6) / 1e9
-        kernels[name] = {"avg_launch_us": t_us, "algorithmic_bytes_per_launch": nbytes, "achieved_GBs": gbs, "frac": gbs / HBM_PEAK_GBS}
-    if args.variant == "split":
-        # the step runs K1, K2, K3: the dominant kernel is the one with the largest total per step
-        kname = max(list(kernels)[:2], key=lambda k: kernels[k]["avg_launch_us"])
-        step_bytes = BYTES_FWD + BYTES_BWD
-    else:
-        kname = list(kernels)[2]
-        step_bytes = BYTES_FUSED
-    kt = kernels[kname]["avg_launch_us"] * 1e-6
-    kbytes = kernels[kname]["algorithmic_bytes_per_launch"]
-    extra = {"kernels": kernels, "event_samples_per_kernel": ROOF_SAMPLES,
-             "method": "mean over back-to-back launches of hipEventElapsedTime(start, stop) with the events stamped by the kernel "
-                       "dispatch itself (hipExtLaunchKernelGGL through lq_profile_events); region placed after the timed loop, "
-                       "independent of --steps"}
+        nroof = ROOF_SAMPLES + 4                                   # the first four warm the path and are dropped
+        e1, e2, e4 = stamped(nroof), stamped(nroof), stamped(nroof)
+        torch.cuda.synchronize(dev)
+        rc = 0
+        for j in range(nroof):                                     # the split step as in the timed loop, back to back: K1, K2 (+K3), ...
+            k = j % nsets
+            lib.lq_profile_events(e1[j][0].cuda_event, e1[j][1].cuda_event)
+            rc |= fwd(px[k], ps, pout[k], None, 0, outer, G, inner, sp)
+            lib.lq_profile_events(e2[j][0].cuda_event, e2[j][1].cuda_event)
+            rc |= bwd(px[k], ps, pdy[k], lam, pds, None, pws, ws_bytes, outer, G, inner, sp)
+        for j in range(nroof):                                     # the fused single-pass step, back to back
+            k = j % nsets
+            lib.lq_profile_events(e4[j][0].cuda_event, e4[j][1].cuda_event)
+            rc |= fused(px[k], ps, pdy[k], lam, pout[k], pds, pws, ws_bytes, outer, G, inner, sp)
+        lib.lq_profile_events(None, None)
+        if rc:
+            _hip.check(rc, "roofline leg")
+        torch.cuda.synchronize(dev)
+        mean_us = lambda prs: sum(a.elapsed_time(b) for a, b in prs[4:]) / len(prs[4:]) * 1e3      # noqa: E731
+        t_k1, t_k2, t_k4 = mean_us(e1), mean_us(e2), mean_us(e4)
+        kernels = {}
+        for name, t_us, nbytes in (("K1 k_flat_fwd<OP_FWD> (lq_fq_forward)", t_k1, BYTES_FWD),
+                                   ("K2 k_row_stream<OP_BWD> (lq_fq_scale_grad, traversal)", t_k2, BYTES_BWD),
+                                   ("K4 k_row_stream<OP_FUSED> (lq_fq_fwd_bwd_fused, traversal)", t_k4, BYTES_FUSED)):
+            gbs = nbytes / (t_us * 1e-6) / 1e9
+            kernels[name] = {"avg_launch_us": t_us, "algorithmic_bytes_per_launch": nbytes, "achieved_GBs": gbs, "frac": gbs / HBM_PEAK_GBS}
+        if args.variant == "split":
+            # the step runs K1, K2, K3: the dominant kernel is the one with the largest total per step
+            kname = max(list(kernels)[:2], key=lambda k: kernels[k]["avg_launch_us"])
+        else:
+            kname = list(kernels)[2]
+        kt = kernels[kname]["avg_launch_us"] * 1e-6
+        kbytes = kernels[kname]["algorithmic_bytes_per_launch"]
+        extra = {"kernels": kernels, "event_samples_per_kernel": ROOF_SAMPLES,
+                 "method": "mean over back-to-back launches of hipEventElapsedTime(start, stop) with the events stamped by the kernel "
+                           "dispatch itself (hipExtLaunchKernelGGL through lq_profile_events); region placed after the timed loop, "
+                           "independent of --steps"}
+
+        # HBM bytes per launch of the dominant kernel from the committed PMC passes -- only while the kernel sources still are
+        # the ones that were profiled (tools/prof_pmc.sh stores their hash next to the numbers)
+        traffic, traffic_note = None, "profiles/traffic.json absent"
+        tpath = os.path.join(ROOT, "profiles", "traffic.json")
+        if os.path.exists(tpath):
+            try:
+                with open(tpath) as f:
+                    tj = json.load(f)
+                if tj.get("csrc_sha") != csrc_sha():
+                    traffic_note = f"profiles/traffic.json was collected on other kernel sources (csrc_sha {tj.get('csrc_sha')} != {csrc_sha()}): not reported"
+                else:
+                    key = "K1" if kname.startswith("K1") else ("K2" if kname.startswith("K2") else "K4")
+                    traffic = tj.get("hbm_bytes_per_launch", {}).get(key)
+                    traffic_note = f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of {tj.get('collected_with', 'tools/prof_pmc.sh')}, csrc_sha {tj.get('csrc_sha')}"
+            except Exception as e:
+                traffic, traffic_note = None, f"profiles/traffic.json unreadable: {e!r}"
+        achieved = kbytes / kt / 1e9
+        roofline = {"bound": "hbm", "kernel": kname, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_note,
+                    "algorithmic_bytes_per_launch": kbytes, "avg_launch_us": kt * 1e6, **extra,
+                    # math-free kernels of the same shape on this device class (tools/membench, re-measured in round 3:
+                    # 512 threads, nontemporal): what a streaming kernel can reach of the 8 TB/s spec peak.  Box to box the
+                    # figures move by 2-3 % (round 1: 6579 / 6808 / 6507)
+                    "stream_ceiling_GBs": {"read1_write1": 6637, "read2": 6689, "read2_write1": 6385,
+                                           "source": "profiles/r03/membench.txt"}}
 
     # ---- informational extras (not part of `value`): other variants of the same step, 100 steps each, no events
     extras = {}
-    if world == 1 and not args.no_extras and graphs is None:
+    if args.full and world == 1 and not args.no_extras and graphs is None:
         def timed(fn, n=100):
             for i in range(10):
                 fn(i)
@@ -538,27 +595,9 @@ def main():
         except Exception as e:      # informational only
             extras["weight_set_step"] = {"error": repr(e)[:200]}
 
-    # HBM bytes per launch of the dominant kernel from the committed PMC passes -- only while the kernel sources still are
-    # the ones that were profiled (tools/prof_pmc.sh stores their hash next to the numbers)
-    traffic, traffic_note = None, "profiles/traffic.json absent"
-    tpath = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tpath):
-        try:
-            with open(tpath) as f:
-                tj = json.load(f)
-            if tj.get("csrc_sha") != csrc_sha():
-                traffic_note = f"profiles/traffic.json was collected on other kernel sources (csrc_sha {tj.get('csrc_sha')} != {csrc_sha()}): not reported"
-            else:
-                key = "K1" if kname.startswith("K1") else ("K2" if kname.startswith("K2") else "K4")
-                traffic = tj.get("hbm_bytes_per_launch", {}).get(key)
-                traffic_note = f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of {tj.get('collected_with', 'tools/prof_pmc.sh')}, csrc_sha {tj.get('csrc_sha')}"
-        except Exception as e:
-            traffic, traffic_note = None, f"profiles/traffic.json unreadable: {e!r}"
-
     if rank == 0:
         ms = elapsed / args.steps * 1e3
         value = world * BATCH * args.steps / elapsed
-        achieved = kbytes / kt / 1e9
         line = {
             "metric": "images/sec training with fake-quant layer, CIFAR-10 bs=256, 1/2/4/8 MI355X",
             "value": value,
@@ -582,18 +621,11 @@ def main():
                                      "async": "eager all-reduce of ds on RCCL's stream"}.get(exchange_form) if use_dist else None),
                        **({"note": graph_note} if graph_note else {}),
                        "step_GBs": step_bytes / (elapsed / args.steps) / 1e9},
-            "roofline": {"bound": "hbm", "kernel": kname, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_note,
-                         "algorithmic_bytes_per_launch": kbytes, "avg_launch_us": kt * 1e6, **extra,
-                         # math-free kernels of the same shape on this device class (tools/membench, re-measured in round 3:
-                         # 512 threads, nontemporal): what a streaming kernel can reach of the 8 TB/s spec peak.  Box to box the
-                         # figures move by 2-3 % (round 1: 6579 / 6808 / 6507)
-                         "stream_ceiling_GBs": {"read1_write1": 6637, "read2": 6689, "read2_write1": 6385,
-                                                "source": "profiles/r03/membench.txt"}},
+            "roofline": roofline,
         }
-        if world == 1 and not args.no_extras and graphs is None:
+        if args.full and world == 1 and not args.no_extras and graphs is None:
             line["extras"] = extras
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(lam, args.cpu_seconds)
         else:
             line["cpu_baseline"] = None

@@ -213,7 +213,7 @@ def test_one_rank_rccl_all_reduce_captured_inside_the_step_graph():
 def test_bench_force_dist_one_rank_rccl():
     """bench.py with torch.distributed initialised on RCCL (one rank): the scale-gradient all-reduce (ReduceOp.AVG) runs every step."""
     import json
-    out = _run_script([os.path.join(ROOT, "bench.py"), "--force-dist", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-extras"])
+    out = _run_script([os.path.join(ROOT, "bench.py"), "--force-dist", "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-extras"])
     line = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["value"] > 1e5 and line["roofline"]["frac"] > 0.5
 
@@ -270,7 +270,7 @@ def test_bench_two_ranks_through_the_driver_launcher():
     import json
     out = _run_script(["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                        "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",
-                       "--backend", "gloo", "--share-gpu", "--no-cpu-baseline", "--no-extras"])
+                       "--backend", "gloo", "--share-gpu", "--full", "--no-cpu-baseline", "--no-extras"])
     lines = [l for l in out.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out[-2000:]
     line = json.loads(lines[0])
@@ -278,3 +278,43 @@ def test_bench_two_ranks_through_the_driver_launcher():
     assert line["config"]["global_batch"] == 512 and line["config"]["parallelism"] == "dp2"
     assert abs(line["value"] - 512 / (line["ms_per_step"] * 1e-3)) < 1e-3 * line["value"]
     assert line["cpu_baseline"] is None                      # timed on rank 0 at N = 1 only
+
+
+@pytest.mark.parametrize("extra,steps", [([], 7), (["--graph", "--graph-steps", "6"], 9)])
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path, extra, steps):
+    """`bench.py --dump-outputs DIR` writes what the LAST of the --steps timed steps computed -- eager (step 6: buffer set 2), and
+    from one replay of a 6-step graph plus a 3-step remainder graph (its step 2: buffer set 2 of the graph's own rotation, where
+    the eager count would give set 0) -- recomputed here on the regenerated inputs through the same C ABI, bit for bit.  A plain
+    run (no --full) reports neither roofline, extras nor CPU baseline."""
+    import json
+    sys.path.insert(0, ROOT)
+    import bench
+    from learned_quantization_amd import _hip
+    out = _run_script([os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "3", "--dump-outputs", str(tmp_path / "bench")] + extra)
+    line = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == steps and line["roofline"] is None and line["cpu_baseline"] is None and "extras" not in line
+    assert abs(line["value"] - 256 / (line["ms_per_step"] * 1e-3)) < 1e-3 * line["value"]
+
+    dev = torch.device("cuda:0")
+    shape, (outer, G, inner) = (bench.BATCH, bench.CH, bench.H, bench.W), (bench.BATCH, bench.CH, bench.H * bench.W)
+    g = torch.Generator(device=dev).manual_seed(42)                   # bench.py's inputs: 4 buffer sets of x, then of dy
+    xs = [torch.rand(shape, device=dev, generator=g) * 255.0 for _ in range(4)]
+    dys = [torch.randn(shape, device=dev, generator=g) * 1e-3 for _ in range(4)]
+    s = torch.tensor([0.5, 1.0, 2.0], device=dev).view(1, 3, 1, 1)
+    o, ds = torch.empty(shape, device=dev), torch.zeros_like(s)
+    lib = _hip.load()
+    wsb = lib.lq_workspace_bytes(outer, G, inner)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    sp = _hip.stream_ptr(dev)
+    x, dy = xs[2], dys[2]
+    _hip.check(lib.lq_fq_forward(x.data_ptr(), s.data_ptr(), o.data_ptr(), None, 0, outer, G, inner, sp), "forward")
+    _hip.check(lib.lq_fq_scale_grad(x.data_ptr(), s.data_ptr(), dy.data_ptr(), 1e-11, ds.data_ptr(), None, ws.data_ptr(), wsb,
+                                    outer, G, inner, sp), "scale grad")
+    torch.cuda.synchronize()
+    bench.dump_outputs(str(tmp_path / "ref"), o, ds)
+    for name in ("out", "ds"):
+        got, ref = np.load(tmp_path / "bench" / f"{name}.npy"), np.load(tmp_path / "ref" / f"{name}.npy")
+        assert got.dtype == np.float32 and got.shape == ref.shape
+        np.testing.assert_array_equal(got, ref, err_msg=name)
+    assert np.load(tmp_path / "bench" / "out.npy").size == bench.DUMP_SAMPLE and np.all(np.load(tmp_path / "bench" / "ds.npy") != 0)
+    assert sum(f.stat().st_size for f in (tmp_path / "bench").iterdir()) <= 64 << 20

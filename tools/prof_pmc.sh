@@ -7,7 +7,7 @@ out=$1; shift
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for c in FETCH_SIZE WRITE_SIZE; do
   mkdir -p $out/$c
-  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $out/$c -- python3 bench.py --no-cpu-baseline --no-extras --steps 30 --warmup 6 "$@" > $out/$c/bench.json 2> $out/$c/err.log || exit 1
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $out/$c -- python3 bench.py --full --no-cpu-baseline --no-extras --steps 30 --warmup 6 "$@" > $out/$c/bench.json 2> $out/$c/err.log || exit 1
 done
 python3 - $out "$@" <<'PY'
 import collections, csv, glob, json, os, sys

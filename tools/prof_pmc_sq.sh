@@ -3,7 +3,7 @@
 out=$1; shift
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 mkdir -p $out
-timeout -k 10 300 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAVES --output-format csv -d $out -- python3 bench.py --no-cpu-baseline --no-extras --steps 40 --warmup 8 --event-every 0 "$@" > $out/bench.json 2> $out/err.log
+timeout -k 10 300 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAVES --output-format csv -d $out -- python3 bench.py --full --no-cpu-baseline --no-extras --steps 40 --warmup 8 --event-every 0 "$@" > $out/bench.json 2> $out/err.log
 python3 - $out <<'PY'
 import csv,glob,sys,collections,json
 out=sys.argv[1]

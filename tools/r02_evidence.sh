@@ -6,11 +6,11 @@ out=$1; part=${2:-all}
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 if [ $part = all ] || [ $part = bench ]; then
-  timeout -k 10 400 python3 bench.py > $out/bench_default.json 2> $out/bench_default.err || exit 1
-  timeout -k 10 200 python3 bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $out/bench_steps20.json 2>> $out/bench_default.err || exit 1
-  timeout -k 10 200 python3 bench.py --steps 300 --warmup 30 --no-extras --no-cpu-baseline > $out/bench_steps300.json 2>> $out/bench_default.err || exit 1
-  timeout -k 10 200 python3 bench.py --variant fused --no-extras --no-cpu-baseline > $out/bench_fused.json 2>> $out/bench_default.err || exit 1
-  timeout -k 10 200 python3 bench.py --force-dist --no-extras --no-cpu-baseline > $out/bench_force_dist_rccl_1rank.json 2>> $out/bench_default.err || exit 1
+  timeout -k 10 400 python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err || exit 1
+  timeout -k 10 200 python3 bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $out/bench_steps20.json 2>> $out/bench_default.err || exit 1
+  timeout -k 10 200 python3 bench.py --full --steps 300 --warmup 30 --no-extras --no-cpu-baseline > $out/bench_steps300.json 2>> $out/bench_default.err || exit 1
+  timeout -k 10 200 python3 bench.py --full --variant fused --no-extras --no-cpu-baseline > $out/bench_fused.json 2>> $out/bench_default.err || exit 1
+  timeout -k 10 200 python3 bench.py --full --force-dist --no-extras --no-cpu-baseline > $out/bench_force_dist_rccl_1rank.json 2>> $out/bench_default.err || exit 1
   mkdir -p $out/prof_default_cmd
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_default_cmd -- python3 bench.py > $out/prof_default_cmd/bench.json 2> $out/prof_default_cmd/err.log || exit 1
   bash tools/prof_pmc.sh $out/pmc > $out/pmc.log 2>&1 || exit 1

@@ -159,7 +159,7 @@ sweeps_companion)
   timeout -k 10 300 python3 tools/bench_weights.py --abi-only --companion-only > $out/r03_weight_sweeps_companion_only.jsonl 2>> $out/sweeps.err || exit 1
   cat $out/r03_weight_sweeps_companion_only.jsonl ;;
 bench)
-  timeout -k 10 400 python3 bench.py > $out/bench_default.json 2> $out/bench_default.err || exit 1
+  timeout -k 10 400 python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err || exit 1
   cat $out/bench_default.json ;;
 esac
 done

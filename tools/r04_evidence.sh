@@ -74,7 +74,7 @@ for l in open(sys.argv[1]):
 PY
   ;;
 bench)
-  timeout -k 10 400 python3 bench.py > $out/bench_default.json 2> $out/bench_default.err || exit 1
+  timeout -k 10 400 python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err || exit 1
   tail -c 1500 $out/bench_default.json ;;
 esac
 done

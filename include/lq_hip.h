@@ -245,6 +245,24 @@ int lq_q_minmax(const float* P, const float* s, int32_t* minmax_dev, int64_t out
 int lq_q_histogram(const float* P, const float* s, int32_t qmin, int64_t nbins, uint32_t* bins_dev,
                    int64_t outer, int64_t G, int64_t inner, void* stream);
 
+/* ---- bit-packed integer view: lossless export and exact restore -----------------------------------------
+ * The reference's export casts floor(P/s) to int8 (CIFAR-10/nested_quantization_layer/utils/log_scripts.py:61-97,
+ * lossy once |q| > 127); these store q = floor(P/s) (custom_layers.py:55-60, K1's division) without loss.
+ * Stream format: code c_i = q_i - qmin of `bits` (0..32) bits, element i at stream bits [i*bits, i*bits + bits),
+ * stream bit j = bit (j mod 32) of words[j/32], ceil(numel*bits/32) little-endian uint32 words, pad bits 0.
+ * Elements in the contiguous order of P; at most 2^31 of them.  bits = 0: no words (`words` may be NULL).
+ * lq_q_pack: writes the words; ADDS to *bad_dev (uint64 on the device, zeroed by the caller) the number of elements
+ *   whose quotient is NaN, +-Inf, outside what lq_q_minmax counts or outside [qmin, qmin + 2^bits - 1] (stored as 0).
+ *   P must be 16-byte aligned.
+ * lq_q_unpack: any of out (float, = lq_fq_forward's out bit for bit except that -0 comes back as +0), q (int32) and
+ *   p_restore (float whose K1 quotient floors to q: (q + 1/2) * s) may be NULL, not all three; each 16-byte aligned.
+ *   With p_restore, every value is divided back with K1's division and the misses are ADDED to *bad_dev (required then;
+ *   0 for |q| < 2^22, the caller must refuse the restore otherwise).                                            */
+int lq_q_pack(const float* P, const float* s, int32_t qmin, int bits, uint32_t* words, uint64_t* bad_dev,
+              int64_t outer, int64_t G, int64_t inner, void* stream);
+int lq_q_unpack(const uint32_t* words, int32_t qmin, int bits, const float* s, float* out, int32_t* q, float* p_restore,
+                uint64_t* bad_dev, int64_t outer, int64_t G, int64_t inner, void* stream);
+
 /* ---- device self-test -------------------------------------------------------------------
  * Compares the kernels' in-window ratio division (rcp + Newton + fma chain, see lq_kernels.hip window_div)
  * with the IEEE `/` on blocks*256*pairs_per_thread pseudo-random operand pairs in [2^-40, 2^40]; ADDS the

@@ -11,13 +11,13 @@ from .layers import (default_kernel_storage, CustomConv2DLayer, CustomConv2DLaye
                      reset_layer_names)
 from .losses import SCCEDifference, SCCEInverse, SCCEMaxBin, sparse_categorical_crossentropy
 from .ops import (difference_term, fq_forward, fq_fwd_bwd_fused, fq_scale_grad, inverse_term, maxbin_term,
-                  my_custom_gradient, q_absmax_over_axis, q_unique, quantized_integers)
+                  my_custom_gradient, q_absmax_over_axis, q_minmax, q_pack, q_unique, q_unpack, quantized_integers)
 from .optim import KerasAdam, ScaleAdam, apply_constraints, non_scale_parameters, scale_parameters
 from .ddp import DataParallel, GradBucket
 from .batch import BatchedScaleAdam, FakeQuantBatch
 from .models import CIFARCNN, MNISTDense, ResNet18Like, ResNet50Like, build_model
 from .data import augment_image, preprocess_for_validation
-from .export import save_compress_parameters
+from .export import load_packed_parameters, save_compress_parameters, save_packed_parameters
 from .tracking import AccuracyLossTrackingCallBack, NestedScaleTrackingCallback
 
 __version__ = "0.1.0"

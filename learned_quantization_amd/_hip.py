@@ -96,6 +96,8 @@ SIGNATURES.update({
     "lq_q_minmax": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p]),
     "lq_q_histogram": (_c_int, [_c_p, _c_p, ctypes.c_int32, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_p]),
     "lq_profile_events": (_c_int, [_c_p, _c_p]),
+    "lq_q_pack": (_c_int, [_c_p, _c_p, ctypes.c_int32, _c_int, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p]),
+    "lq_q_unpack": (_c_int, [_c_p, ctypes.c_int32, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p]),
 })
 
 _lock = threading.RLock()

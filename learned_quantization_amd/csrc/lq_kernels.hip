@@ -9,6 +9,7 @@
 //   lq_stream2.hpp      streaming-size forms of the column and tiny-row modes (round 2): flat K1, pipelined column tile, ...
 //   lq_aux_kernels.hpp  scale-sized kernels (K5c, K6), integer statistics, device self-test
 //   lq_batch.hpp        device side of the multi-tensor batch
+//   lq_pack.hpp         bit-packed integer view: lossless export and exact restore
 //   this file           host side: traversal plan, launchers, the extern "C" entry points
 //
 // The path is elementwise + per-group reductions: HBM-bound, no MFMA.  Design rules
@@ -47,6 +48,7 @@
 
 #include "lq_batch.hpp"
 #include "lq_stream2.hpp"
+#include "lq_pack.hpp"
 
 namespace lq {
 
@@ -2094,6 +2096,51 @@ int lq_q_histogram(const float* P, const float* s, int32_t qmin, int64_t nbins, 
     if (n < 2147483648ll) hipLaunchKernelGGL(k_q_histogram<uint32_t>, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, P, s, qmin, nbins, bins_dev, n, G, inner);
     else hipLaunchKernelGGL(k_q_histogram<int64_t>, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, P, s, qmin, nbins, bins_dev, n, G, inner);
     return check_hip("q histogram launch");
+}
+
+static int check_pack(const char* fn, int bits, int64_t outer, int64_t G, int64_t inner) {
+    int rc = check_desc(outer, G, inner);
+    if (rc) return rc;
+    if (bits < 0 || bits > 32) return fail(LQ_EINVAL, "%s: bits must be in 0..32, got %d", fn, bits);
+    if (outer * G * inner > 2147483648ll) return fail(LQ_EINVAL, "%s: at most 2^31 elements (32-bit element indices)", fn);
+    return LQ_OK;
+}
+
+static dim3 pack_grid(int64_t n) { return dim3((unsigned)ceil_div(n, (int64_t)kPackWaves * kPackElems)); }
+
+int lq_q_pack(const float* P, const float* s, int32_t qmin, int bits, uint32_t* words, uint64_t* bad_dev, int64_t outer, int64_t G,
+              int64_t inner, void* stream) {
+    int rc = check_pack("lq_q_pack", bits, outer, G, inner);
+    if (rc) return rc;
+    LQ_REQUIRE_PTR(P);
+    LQ_REQUIRE_PTR(s);
+    if (!aligned(P, 16)) return fail(LQ_EALIGN, "lq_q_pack: P must be 16-byte aligned (float4 loads)");
+    if (bits > 0) LQ_REQUIRE_PTR(words);
+    if (!bad_dev) return fail(LQ_EINVAL, "lq_q_pack: argument 'bad_dev' is NULL");
+    if (!aligned(bad_dev, 8)) return fail(LQ_EALIGN, "lq_q_pack: bad_dev must be 8-byte aligned");
+    const int64_t n = outer * G * inner;
+    hipLaunchKernelGGL(k_q_pack, pack_grid(n), dim3(kPackWaves * 64), 0, (hipStream_t)stream, P, s, qmin, bits, words,
+                       reinterpret_cast<unsigned long long*>(bad_dev), (uint32_t)n, (uint64_t)((n * bits + 31) / 32),
+                       make_fastdiv((uint32_t)inner), make_fastdiv((uint32_t)G));
+    return check_hip("q pack launch");
+}
+
+int lq_q_unpack(const uint32_t* words, int32_t qmin, int bits, const float* s, float* out, int32_t* q, float* p_restore,
+                uint64_t* bad_dev, int64_t outer, int64_t G, int64_t inner, void* stream) {
+    int rc = check_pack("lq_q_unpack", bits, outer, G, inner);
+    if (rc) return rc;
+    if (bits > 0) LQ_REQUIRE_PTR(words);
+    LQ_REQUIRE_PTR(s);
+    if (!out && !q && !p_restore) return fail(LQ_EINVAL, "lq_q_unpack: out, q and p_restore are all NULL");
+    if ((out && !aligned(out, 16)) || (q && !aligned(q, 16)) || (p_restore && !aligned(p_restore, 16)))
+        return fail(LQ_EALIGN, "lq_q_unpack: out, q and p_restore must be 16-byte aligned (16-byte stores)");
+    if (p_restore && !bad_dev) return fail(LQ_EINVAL, "lq_q_unpack: p_restore needs bad_dev (the check of every restored value)");
+    if (bad_dev && !aligned(bad_dev, 8)) return fail(LQ_EALIGN, "lq_q_unpack: bad_dev must be 8-byte aligned");
+    const int64_t n = outer * G * inner;
+    hipLaunchKernelGGL(k_q_unpack, pack_grid(n), dim3(kPackWaves * 64), 0, (hipStream_t)stream, words, qmin, bits, s, out,
+                       q, p_restore, reinterpret_cast<unsigned long long*>(bad_dev), (uint32_t)n,
+                       (uint64_t)((n * bits + 31) / 32), make_fastdiv((uint32_t)inner), make_fastdiv((uint32_t)G));
+    return check_hip("q unpack launch");
 }
 
 int lq_selftest_uniform_division(uint64_t seed, uint32_t blocks, uint32_t pairs_per_thread, uint64_t* mismatches_dev, void* stream) {

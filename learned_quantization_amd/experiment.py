@@ -9,7 +9,7 @@ Flags ``--seed --orientation --training [--custom_loss]`` and the log tree
 /root/reference/CIFAR-10/custom_loss_terms/experiment.py:289-302; the run does what the reference's ``main`` does
 around ``model.fit``: structure log (utils/log_scripts.py:10-58), one tracking callback per custom layer + the
 accuracy/loss callback (experiment.py:61-81), per-epoch validation, the Imagenette LR schedule
-(IMAGENETTE/.../experiment.py:67-78), the integer export at the end (utils/log_scripts.py:61-97).
+(IMAGENETTE/.../experiment.py:67-78), the integer export at the end (utils/log_scripts.py:61-97); ``--export-packed`` adds the lossless packed container (export.py).
 ``post_training`` needs ``--baseline-weights file.npz`` (arrays W1,b1,W2,b2 for ``--config mnist``): the reference's
 PTQ entry (MNIST/.../experiment.py:70-118) with the weights of its shipped ``baseline_model.keras``.
 No dataset is reachable offline: images are U[0,255), labels uniform (so accuracies are chance level).
@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import layers as L
-from .export import save_compress_parameters
+from .export import save_compress_parameters, save_packed_parameters
 from .tracking import AccuracyLossTrackingCallBack, NestedScaleTrackingCallback
 from .train import Trainer, synthetic_batch
 
@@ -121,6 +121,8 @@ def main(argv=None):
     ap.add_argument("--baseline-weights", default=None)
     ap.add_argument("--log-root", default="logs")
     ap.add_argument("--batched", action="store_true")
+    ap.add_argument("--export-packed", action="store_true",
+                    help="also write the lossless bit-packed export (weights_packed.npz/.zip, packed_sizes.log; not in the reference)")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("needs an MI355X (no CPU fallback)")
@@ -150,10 +152,14 @@ def main(argv=None):
     history = fit(tr, args.epochs, args.steps_per_epoch, args.batch, callbacks, args.lr,
                   use_scheduler=(args.config == "imagenette"), seed=args.seed)
     sizes = save_compress_parameters(tr.model, log_dir)
+    packed = save_packed_parameters(tr.model, log_dir) if args.export_packed else None
     stats = callbacks[0].stats()
-    print(json.dumps({"log_dir": log_dir, "epochs": args.epochs, "seconds": time.perf_counter() - t0,
-                      "final": history[-1], "export": sizes,
-                      "first_layer_unique_integers": stats["unique_k"], "first_layer_max_abs_q": float(stats["max_k"].max())}))
+    line = {"log_dir": log_dir, "epochs": args.epochs, "seconds": time.perf_counter() - t0,
+            "final": history[-1], "export": sizes,
+            "first_layer_unique_integers": stats["unique_k"], "first_layer_max_abs_q": float(stats["max_k"].max())}
+    if packed is not None:
+        line["packed"] = packed
+    print(json.dumps(line))
 
 
 if __name__ == "__main__":

@@ -16,15 +16,17 @@ The reference does not store the scales (thesis chapter4.tex:328-330 notes they 
 """
 from __future__ import annotations
 
+import json
+import math
 import os
 import zipfile
-from typing import Dict
+from typing import Dict, List, Tuple
 
 import numpy as np
 import torch
 
 from . import ops
-from .layers import CustomDenseLayer, _ConvBase
+from .layers import CustomDenseLayer, CustomQuantizedScaleLayer, _ConvBase
 
 
 def _host(t: torch.Tensor) -> np.ndarray:
@@ -34,20 +36,24 @@ def _host(t: torch.Tensor) -> np.ndarray:
     return np.ascontiguousarray(t.detach().cpu().numpy())
 
 
-def quantized_state(model: torch.nn.Module) -> Dict[str, np.ndarray]:
-    weights: Dict[str, np.ndarray] = {}
-
-    def q(param, nested):
-        return _host(ops.quantized_integers(param.data, nested.scale.data, torch.int8))
+def quantized_tensors(model: torch.nn.Module) -> List[Tuple[str, torch.nn.Parameter, CustomQuantizedScaleLayer]]:
+    """(reference name, parameter, nested scale layer) of every quantized tensor -- kernel/W and bias of every custom layer,
+    in module order.  The one walk both exports use: the int8 file (log_scripts.py:74-79) and the packed container."""
+    out = []
     for layer in model.modules():
         if isinstance(layer, _ConvBase):
-            weights[layer.name + "/W"] = q(layer.kernel, layer.nested_q_k_layer)
+            out.append((layer.name + "/W", layer.kernel, layer.nested_q_k_layer))
             if layer._has_bias:
-                weights[layer.name + "/b"] = q(layer.b, layer.nested_q_b_layer)
+                out.append((layer.name + "/b", layer.b, layer.nested_q_b_layer))
         elif isinstance(layer, CustomDenseLayer):
-            weights[layer.name + "/W"] = q(layer.W, layer.nested_q_w_layer)
-            weights[layer.name + "/b"] = q(layer.b, layer.nested_q_b_layer)
-    return weights
+            out.append((layer.name + "/W", layer.W, layer.nested_q_w_layer))
+            out.append((layer.name + "/b", layer.b, layer.nested_q_b_layer))
+    return out
+
+
+def quantized_state(model: torch.nn.Module) -> Dict[str, np.ndarray]:
+    return {name: _host(ops.quantized_integers(param.data, nested.scale.data, torch.int8))
+            for name, param, nested in quantized_tensors(model)}
 
 
 def scale_state(model: torch.nn.Module) -> Dict[str, np.ndarray]:
@@ -81,3 +87,169 @@ def save_compress_parameters(model: torch.nn.Module, log_dir: str) -> Dict[str, 
         log_file.write(f"Weights size: {size:.4f} MB\n")
         log_file.write(f"Compressed weights size: {zip_size:.4f} MB\n")
     return {"weights_mb": size, "zip_mb": zip_size}
+
+
+# ------------------------------------------------------------------------------------------------ lossless packed export
+# The int8 file above reproduces the reference's artefact and its limits: |q| > 127 wraps, the scales sit in a side file,
+# BatchNorm statistics and loss-term buffers are nowhere, and nothing reads it back.  The packed container stores every
+# q = floor(P/s) of K1 exactly (bit-packed by lq_q_pack, include/lq_hip.h), the scales, and the rest of the state_dict.
+PACKED_FORMAT = "lq-packed"
+PACKED_VERSION = 1
+PACKED_FILES = ("weights_packed.npz", "weights_packed.zip", "packed_sizes.log")
+
+
+def _manifest_bytes(manifest: dict) -> np.ndarray:
+    return np.frombuffer(json.dumps(manifest).encode("utf-8"), dtype=np.uint8)
+
+
+def _plain_state_keys(model: torch.nn.Module, tensors) -> List[str]:
+    """state_dict keys of everything that is not a quantized parameter or its scale, in state_dict order."""
+    skip = {id(p) for _, p, _ in tensors} | {id(nested.scale) for _, _, nested in tensors}
+    owned = {key for key, p in model.named_parameters() if id(p) in skip}
+    return [k for k in model.state_dict().keys() if k not in owned]
+
+
+def save_packed_parameters(model: torch.nn.Module, log_dir: str) -> Dict[str, float]:
+    """Writes weights_packed.npz (manifest, codes, scales, state), weights_packed.zip and packed_sizes.log next to the
+    reference export (which it does not touch); returns {"packed_mb", "zip_mb", "bits_per_weight"}.  Raises ValueError naming
+    the tensor when an integer cannot be stored exactly (NaN, Inf, |q| beyond int32); then no file is written."""
+    tensors = quantized_tensors(model)
+    if not tensors:
+        raise ValueError("the model has no quantized tensor to pack")
+    dev = tensors[0][1].device
+    ranges = torch.empty((len(tensors), 2), dtype=torch.int32, device=dev)
+    for k, (_, param, nested) in enumerate(tensors):
+        ops.q_minmax(param.data, nested.scale.data, out=ranges[k])
+    lohi = ranges.tolist()                                      # every range in one device->host copy
+    entries = []
+    for (name, param, nested), (lo, hi) in zip(tensors, lohi):
+        if lo > hi:
+            raise ValueError(f"{name}: floor(P/s) has no finite integer (NaN/Inf or beyond int32): cannot pack it")
+        entries.append({"name": name, "shape": list(param.shape), "scale_shape": list(nested.scale.shape),
+                        "orientation": nested.orientation, "qmin": int(lo), "bits": int(hi - lo).bit_length(),
+                        "numel": int(param.numel())})
+    bad = torch.zeros(len(tensors), dtype=torch.int64, device=dev)
+    words = [ops.q_pack(param.data, nested.scale.data, qmin=e["qmin"], bits=e["bits"], bad=bad[k:k + 1])[0]
+             for k, ((_, param, nested), e) in enumerate(zip(tensors, entries))]
+    for e, nbad in zip(entries, bad.tolist()):
+        if nbad:
+            raise ValueError(f"{e['name']}: {nbad} elements of floor(P/s) are NaN, Inf or beyond int32: cannot pack it")
+    state_keys = _plain_state_keys(model, tensors)
+    sd = model.state_dict()
+    manifest = {"format": PACKED_FORMAT, "version": PACKED_VERSION, "tensors": entries, "state": state_keys}
+    arrays = {"manifest": _manifest_bytes(manifest)}
+    for (name, _, nested), e, w in zip(tensors, entries, words):
+        arrays[name + ".codes"] = w.cpu().numpy().view(np.uint32)
+        arrays[name + ".scale"] = _host(nested.scale)
+    for key in state_keys:
+        arrays["state/" + key] = np.array(sd[key].detach().cpu().numpy(), order="C")   # keeps 0-d counters 0-d
+
+    os.makedirs(log_dir, exist_ok=True)
+    final = [os.path.join(log_dir, f) for f in PACKED_FILES]
+    tmp = [os.path.join(log_dir, "." + f + ".tmp") for f in PACKED_FILES]
+    try:
+        with open(tmp[0], "wb") as fh:
+            np.savez(fh, **arrays)
+        with zipfile.ZipFile(tmp[1], "w", compression=zipfile.ZIP_DEFLATED) as zipf:
+            zipf.write(tmp[0], arcname=PACKED_FILES[0])
+        size = os.path.getsize(tmp[0]) / (1024 * 1024)
+        zip_size = os.path.getsize(tmp[1]) / (1024 * 1024)
+        n_total = sum(e["numel"] for e in entries)
+        bpw = sum(e["numel"] * e["bits"] for e in entries) / n_total
+        with open(tmp[2], "w") as log_file:
+            log_file.write(f"Packed weights size: {size:.4f} MB\n")
+            log_file.write(f"Compressed packed weights size: {zip_size:.4f} MB\n")
+            log_file.write(f"Bits per quantised weight: {bpw:.4f}\n")
+        for t, f in zip(tmp, final):
+            os.replace(t, f)
+    finally:
+        for t in tmp:
+            if os.path.exists(t):
+                os.remove(t)
+    return {"packed_mb": size, "zip_mb": zip_size, "bits_per_weight": bpw}
+
+
+def read_packed_manifest(z) -> dict:
+    manifest = json.loads(bytes(np.asarray(z["manifest"], dtype=np.uint8)).decode("utf-8"))
+    if not isinstance(manifest, dict) or manifest.get("format") != PACKED_FORMAT or manifest.get("version") != PACKED_VERSION:
+        raise ValueError(f"not an {PACKED_FORMAT} version {PACKED_VERSION} container: format={manifest.get('format')!r} "
+                         f"version={manifest.get('version')!r}" if isinstance(manifest, dict) else "manifest is not an object")
+    return manifest
+
+
+def _check_packed(model: torch.nn.Module, manifest: dict, z, tensors, state_keys) -> None:
+    """Every mismatch between the container and the model raises ValueError before anything is changed."""
+    entries = manifest.get("tensors", [])
+    names = [e.get("name") for e in entries]
+    have = [name for name, _, _ in tensors]
+    if names != have:
+        missing = sorted(set(have) - set(names))
+        extra = sorted(set(names) - set(have))
+        raise ValueError(f"quantized tensors differ: missing from the container {missing}, not in the model {extra}"
+                         + ("" if missing or extra else " (order differs)"))
+    for (name, param, nested), e in zip(tensors, entries):
+        if list(e.get("shape", [])) != list(param.shape):
+            raise ValueError(f"{name}: shape {e.get('shape')} in the container, {list(param.shape)} in the model")
+        if list(e.get("scale_shape", [])) != list(nested.scale.shape):
+            raise ValueError(f"{name}: scale shape {e.get('scale_shape')} in the container, {list(nested.scale.shape)} in the model")
+        if e.get("orientation") != nested.orientation:
+            raise ValueError(f"{name}: orientation {e.get('orientation')!r} in the container, {nested.orientation!r} in the model")
+        bits, numel = e.get("bits"), e.get("numel")
+        if not isinstance(bits, int) or not 0 <= bits <= 32 or numel != param.numel():
+            raise ValueError(f"{name}: bad bits/numel {bits}/{numel}")
+        qmin = e.get("qmin")
+        if not isinstance(qmin, int) or qmin < -(2 ** 31) or qmin + (1 << bits) - 1 > 2 ** 31 - 1 and bits < 32:
+            raise ValueError(f"{name}: qmin {qmin} with {bits} bits leaves int32")
+        codes = z[name + ".codes"] if name + ".codes" in z.files else None
+        if codes is None or codes.dtype != np.uint32 or codes.shape != (ops.packed_words(numel, bits),):
+            raise ValueError(f"{name}: codes missing or not {ops.packed_words(numel, bits)} uint32 words")
+        sc = z[name + ".scale"] if name + ".scale" in z.files else None
+        if sc is None or sc.dtype != np.float32 or list(sc.shape) != list(nested.scale.shape):
+            raise ValueError(f"{name}: scale missing or not float32 {list(nested.scale.shape)}")
+    if list(manifest.get("state", [])) != state_keys:
+        missing = sorted(set(state_keys) - set(manifest.get("state", [])))
+        extra = sorted(set(manifest.get("state", [])) - set(state_keys))
+        raise ValueError(f"state entries differ: missing from the container {missing}, not in the model {extra}")
+    sd = model.state_dict()
+    for key in state_keys:
+        a = z["state/" + key] if "state/" + key in z.files else None
+        if a is None or tuple(a.shape) != tuple(sd[key].shape):
+            raise ValueError(f"state entry {key}: missing or shape {None if a is None else a.shape} != {tuple(sd[key].shape)}")
+
+
+def load_packed_parameters(model: torch.nn.Module, path: str) -> dict:
+    """Restores a weights_packed.npz (or the directory holding it) into ``model`` -- built by build_model with the same
+    config, either kernel_storage: each quantized P becomes a value whose floor(P/s) is the stored integer, each scale and every
+    state entry the stored one, copied into the existing tensors.  Format, version, names, shapes and orientations are
+    checked first: on a mismatch ValueError is raised and the model is left untouched.  Returns the manifest."""
+    if os.path.isdir(path):
+        path = os.path.join(path, PACKED_FILES[0])
+    tensors = quantized_tensors(model)
+    with np.load(path, allow_pickle=False) as z:
+        manifest = read_packed_manifest(z)
+        state_keys = _plain_state_keys(model, tensors)
+        _check_packed(model, manifest, z, tensors, state_keys)
+        codes = {e["name"]: z[e["name"] + ".codes"] for e in manifest["tensors"]}
+        scales = {e["name"]: z[e["name"] + ".scale"] for e in manifest["tensors"]}
+        state = {key: z["state/" + key] for key in state_keys}
+    if not tensors:
+        return manifest
+    dev = tensors[0][1].device
+    bad = torch.zeros(1, dtype=torch.int64, device=dev)
+    restored = []
+    for (name, param, nested), e in zip(tensors, manifest["tensors"]):
+        s = torch.from_numpy(scales[name]).to(dev)
+        w = torch.from_numpy(codes[name].view(np.int32)).to(dev)
+        _, _, pr = ops.q_unpack(w, e["qmin"], e["bits"], s, param.shape, want_out=False, want_q=False, bad=bad)
+        restored.append((param, nested, s, pr))
+    nbad = int(bad.item())
+    if nbad:
+        raise ValueError(f"{nbad} restored values do not floor back to their stored integer (|q| >= 2^22): model left untouched")
+    with torch.no_grad():
+        for param, nested, s, pr in restored:
+            param.data.copy_(pr)                               # into the parameter's own storage (HWIO or OIHW order)
+            nested.scale.data.copy_(s)
+        sd = model.state_dict()
+        for key, a in state.items():
+            sd[key].copy_(torch.from_numpy(np.array(a, order="C")))
+    return manifest

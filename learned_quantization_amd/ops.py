@@ -150,6 +150,100 @@ def q_unique(parameter: torch.Tensor, scale: torch.Tensor):
     return (nz + lo).to(torch.int32), bins[nz].to(torch.int64)
 
 
+def q_minmax(parameter: torch.Tensor, scale: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(min, max) of floor(P/s) as a 2-element int32 device tensor, without a device->host read; ``out`` (a contiguous
+    2-element int32 device tensor) lets a caller gather many ranges into one buffer.  NaN/Inf/beyond-int32 quotients are
+    skipped: an all-skipped tensor gives min > max."""
+    lib = _hip.load()
+    p = _hip.require_device_f32(parameter, "parameter")
+    s = _hip.require_device_f32(scale, "scale")
+    outer, G, inner = _desc(p, s)
+    if out is None:
+        out = torch.empty(2, dtype=torch.int32, device=p.device)
+    elif out.dtype != torch.int32 or out.numel() != 2 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous 2-element int32 tensor")
+    out[0], out[1] = 2 ** 31 - 1, -(2 ** 31)
+    _hip.check(lib.lq_q_minmax(_hip.ptr(p), _hip.ptr(s), _hip.ptr(out), outer, G, inner, _hip.stream_ptr(p.device)),
+               "lq_q_minmax")
+    return out
+
+
+def packed_words(numel: int, bits: int) -> int:
+    """Number of uint32 words of the packed stream: ceil(numel * bits / 32)."""
+    return (int(numel) * int(bits) + 31) // 32
+
+
+def _aligned16(t: torch.Tensor) -> torch.Tensor:
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def q_pack(parameter: torch.Tensor, scale: torch.Tensor, qmin: Optional[int] = None, bits: Optional[int] = None,
+           bad: Optional[torch.Tensor] = None):
+    """Bit-packs q = floor(P/s) (K1's division, custom_layers.py:55-60) losslessly: returns ``(words, qmin, bits)`` with
+    ``words`` an int32 device tensor holding the uint32 stream of include/lq_hip.h (codes q - qmin, LSB-first), in the
+    parameter's LOGICAL C order whatever its memory order.  Without ``qmin``/``bits`` the range is read from the device
+    (lq_q_minmax, one sync).  Without ``bad`` the call checks the element count the kernel rejected and raises ValueError;
+    with ``bad`` (a 1-element int64 device tensor) that count is added to it and checking it is the caller's business."""
+    lib = _hip.load()
+    p = _aligned16(_hip.require_device_f32(parameter, "parameter"))
+    s = _hip.require_device_f32(scale, "scale")
+    outer, G, inner = _desc(p, s)
+    if qmin is None or bits is None:
+        lo, hi = (int(v) for v in q_minmax(p, s).tolist())
+        if lo > hi:
+            raise ValueError("no finite integer in floor(P/s): nothing to pack")
+        qmin, bits = lo, (hi - lo).bit_length()
+    if not 0 <= int(bits) <= 32:
+        raise ValueError(f"bits must be in 0..32, got {bits}")
+    check_here = bad is None
+    if bad is None:
+        bad = torch.zeros(1, dtype=torch.int64, device=p.device)
+    elif bad.dtype != torch.int64 or bad.numel() != 1 or not bad.is_cuda:
+        raise TypeError("bad must be a 1-element int64 device tensor")
+    words = torch.empty(packed_words(p.numel(), bits), dtype=torch.int32, device=p.device)
+    _hip.check(lib.lq_q_pack(_hip.ptr(p), _hip.ptr(s), int(qmin), int(bits), _hip.ptr(words) if words.numel() else None,
+                             _hip.ptr(bad), outer, G, inner, _hip.stream_ptr(p.device)), "lq_q_pack")
+    if check_here and int(bad.item()):
+        raise ValueError(f"{int(bad.item())} elements of floor(P/s) are NaN, Inf, beyond int32 or outside "
+                         f"[{qmin}, {qmin} + 2^{bits} - 1]")
+    return words, int(qmin), int(bits)
+
+
+def q_unpack(words: torch.Tensor, qmin: int, bits: int, scale: torch.Tensor, shape, want_out: bool = True,
+             want_q: bool = True, want_restore: bool = True, bad: Optional[torch.Tensor] = None):
+    """Inverse of ``q_pack``: returns ``(out, q, p_restore)`` of ``shape`` (contiguous; None where not wanted).
+    out = q * s bit for bit as K1's out (a -0 of P comes back +0), q int32, p_restore a float whose floor(P/s) is q.  Every
+    p_restore is divided back on the device; without ``bad`` a miss raises ValueError (|q| >= 2^22 can miss), with ``bad``
+    the misses are added to it."""
+    lib = _hip.load()
+    s = _hip.require_device_f32(scale, "scale")
+    shape = tuple(int(d) for d in shape)
+    outer, G, inner = group_descriptor(shape, tuple(s.shape))
+    n = outer * G * inner
+    if not 0 <= int(bits) <= 32:
+        raise ValueError(f"bits must be in 0..32, got {bits}")
+    if int(bits) and (words.dtype != torch.int32 or not words.is_cuda or not words.is_contiguous()
+                      or words.numel() != packed_words(n, bits)):
+        raise ValueError(f"words must be a contiguous int32 device tensor of {packed_words(n, bits)} elements")
+    if not (want_out or want_q or want_restore):
+        raise ValueError("nothing to compute")
+    out = torch.empty(shape, dtype=torch.float32, device=s.device) if want_out else None
+    q = torch.empty(shape, dtype=torch.int32, device=s.device) if want_q else None
+    pr = torch.empty(shape, dtype=torch.float32, device=s.device) if want_restore else None
+    check_here = want_restore and bad is None
+    if check_here:
+        bad = torch.zeros(1, dtype=torch.int64, device=s.device)
+    elif bad is not None and (bad.dtype != torch.int64 or bad.numel() != 1 or not bad.is_cuda):
+        raise TypeError("bad must be a 1-element int64 device tensor")
+    _hip.check(lib.lq_q_unpack(_hip.ptr(words) if int(bits) else None, int(qmin), int(bits), _hip.ptr(s), _hip.ptr(out),
+                               _hip.ptr(q), _hip.ptr(pr), _hip.ptr(bad), outer, G, inner, _hip.stream_ptr(s.device)),
+               "lq_q_unpack")
+    if check_here and int(bad.item()):
+        raise ValueError(f"{int(bad.item())} restored values do not floor back to their integer (|q| too large for an exact "
+                         "float restore)")
+    return out, q, pr
+
+
 def min_value_project_(w: torch.Tensor, min_value: float) -> torch.Tensor:
     """In-place MinValueConstraint: w <- max(w, min_value)  (custom_layers.py:42-43)."""
     lib = _hip.load()

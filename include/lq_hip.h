@@ -221,6 +221,39 @@ typedef enum lq_penalty_kind { LQ_PENALTY_MAXBIN = 0, LQ_PENALTY_DIFFERENCE = 1,
 int lq_batch_penalty_grads(const lq_batch* batch, int kind, const float* coeff, float* const* grad,
                            void* ws, size_t ws_bytes, void* stream);
 
+/* VALUE of the custom-loss-term penalty for the whole batch (compute_{maxbin,difference,inverse}_penalty,
+ *   custom_loss_functions.py:75-116, 161-195, 240-275), the number compute_total_loss adds to the cross-entropy (:47-58).
+ * Per-tensor term t_i as in lq_penalty_{maxbin,difference,inverse}_fwd; the model penalty in the reference's order (:102-116):
+ *   per layer  t_k * dim_k (+ t_b * dim_b),  running fp32 sum over the layers in descriptor order,  / sum(dims).
+ * dims: host float[n], the element counts (:102-108); layer_start: host uint8[n], 1 where tensor i opens a new layer (kernel and
+ * bias of one layer are paired as the reference pairs them).  terms_dev: device float[n]; penalty_dev: one device float.
+ * lq_batch_penalty_values: values only -- MaxBin 4 launches, Difference 4 (a forward traversal of the batch, its finalize, terms,
+ *   combine), Inverse 2 (the two small ones: terms, combine).
+ * lq_batch_penalty_grads_values: lq_batch_penalty_grads (same arguments, LQ_PENALTY_ACCUMULATE_DS included; bit-identical
+ *   gradient outputs) and the values, without reading any parameter more often than lq_batch_penalty_grads does.  MaxBin and
+ *   Inverse reduce what the gradient launches left behind (mb[g], s[g]) in the two small launches.  Difference: the backward
+ *   traversal carries sum |P - P/s| in a second accumulator next to the scale-gradient sum (the same f64 accumulation and merge
+ *   order for ds: the same bits), one finalize launch emits ds and the groups' mean |u|, then the two small launches -- 4
+ *   launches instead of lq_batch_penalty_grads' 2.
+ * All reductions are two-stage and ordered (no float atomics): run-to-run bit-stable.  ws as for lq_batch_penalty_grads
+ * (lq_batch_workspace_bytes, which covers the second partial slice; not needed for LQ_PENALTY_INVERSE).  Nothing allocates;
+ * the calls only enqueue.                                                                                                */
+int lq_batch_penalty_values(const lq_batch* batch, int kind, const float* dims, const uint8_t* layer_start,
+                            float* terms_dev, float* penalty_dev, void* ws, size_t ws_bytes, void* stream);
+int lq_batch_penalty_grads_values(const lq_batch* batch, int kind, const float* coeff, float* const* grad,
+                                  const float* dims, const uint8_t* layer_start, float* terms_dev, float* penalty_dev,
+                                  void* ws, size_t ws_bytes, void* stream);
+
+/* One row of the reference's per-step logs custom_losses/{total,scce,<term>}_loss.log (custom_loss_functions.py:58-71),
+ * appended ON THE DEVICE in one tiny launch: no device->host synchronisation per step, and -- the cursor lives in device
+ * memory -- the launch can be captured into a hipGraph once and replayed.
+ *   row = { scce + rate * penalty, scce, rate * penalty }   (fp32, in this order of operations, :58)
+ * is written to rows_dev[3 * cursor_dev[0]] and cursor_dev[0] (int64) is incremented; when cursor_dev[0] == capacity nothing
+ * is written to rows_dev and cursor_dev[1] (dropped rows) is incremented instead.  cursor_dev: two int64, 8-byte aligned.
+ * last_dev (optional, device float[3]): always receives the row, whether it was logged or dropped.                      */
+int lq_loss_log_append(const float* scce_dev, const float* penalty_dev, float rate, float* rows_dev, int64_t capacity,
+                       int64_t* cursor_dev, float* last_dev, void* stream);
+
 /* ---- multi-tensor Adam for the ordinary parameters (SURVEY f-4) -------------------------------------------
  * The reference trains everything with Keras 2.11 Adam(learning_rate=1e-4)
  *   CIFAR-10/nested_quantization_layer/experiment.py:435-443.

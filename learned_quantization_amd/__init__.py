@@ -9,7 +9,7 @@ from .descriptor import ORIENTATIONS, group_descriptor, memory_descriptor, memor
 from .layers import (default_kernel_storage, CustomConv2DLayer, CustomConv2DLayerNoBias, CustomDenseLayer, CustomQuantizedScaleLayer,
                      L2, MinValueConstraint, RandomNormal, SCALE_INIT, custom_layers_of, eps_float32, l2,
                      reset_layer_names)
-from .losses import SCCEDifference, SCCEInverse, SCCEMaxBin, sparse_categorical_crossentropy
+from .losses import LossLog, SCCEDifference, SCCEInverse, SCCEMaxBin, sparse_categorical_crossentropy
 from .ops import (difference_term, fq_forward, fq_fwd_bwd_fused, fq_scale_grad, inverse_term, maxbin_term,
                   my_custom_gradient, q_absmax_over_axis, q_minmax, q_pack, q_unique, q_unpack, quantized_integers)
 from .optim import KerasAdam, ScaleAdam, apply_constraints, non_scale_parameters, scale_parameters

@@ -87,6 +87,10 @@ SIGNATURES.update({
     "lq_fq_scale_grad_oihw": (_c_int, [_c_p, _c_p, _c_p, _c_f, _c_p, _c_p, _c_p, _c_sz, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_p]),
     "lq_batch_scale_adam": (_c_int, [_c_p, _c_d, _c_d, _c_d, _c_d, _c_i64, _c_p, _c_int, _c_p]),
     "lq_batch_penalty_grads": (_c_int, [_c_p, _c_int, ctypes.POINTER(_c_f), ctypes.POINTER(_c_p), _c_p, _c_sz, _c_p]),
+    "lq_batch_penalty_values": (_c_int, [_c_p, _c_int, ctypes.POINTER(_c_f), ctypes.POINTER(ctypes.c_uint8), _c_p, _c_p, _c_p, _c_sz, _c_p]),
+    "lq_batch_penalty_grads_values": (_c_int, [_c_p, _c_int, ctypes.POINTER(_c_f), ctypes.POINTER(_c_p), ctypes.POINTER(_c_f),
+                                               ctypes.POINTER(ctypes.c_uint8), _c_p, _c_p, _c_p, _c_sz, _c_p]),
+    "lq_loss_log_append": (_c_int, [_c_p, _c_p, _c_f, _c_p, _c_i64, _c_p, _c_p, _c_p]),
     "lq_adam_set_create": (_c_int, [ctypes.POINTER(_c_p), ctypes.POINTER(_c_p), ctypes.POINTER(_c_p), ctypes.POINTER(_c_i64),
                                     ctypes.POINTER(_c_f), _c_int, ctypes.POINTER(_c_p)]),
     "lq_adam_set_destroy": (_c_int, [_c_p]),

@@ -369,14 +369,43 @@ class FakeQuantBatch:
     # ------------------------------------------------------------------ custom loss terms
     _KINDS = {"maxbin": 0, "difference": 1, "inverse": 2}
 
-    def inject_penalty_grads(self, kind: str, penalty_rate: float, accumulate_ds: bool = False):
+    def _value_buffers(self):
+        """Host constants and persistent device outputs of the penalty value (built once: a captured graph keeps pointing at
+        ``terms`` / ``penalty``): element counts and, per tensor, whether it opens a new layer (CL-F:102-116 pairs a layer's
+        kernel with its bias)."""
+        vb = getattr(self, "_values", None)
+        if vb is None:
+            n = len(self.entries)
+            dims = (ctypes.c_float * n)(*[float(e.param.numel()) for e in self.entries])
+            start = (ctypes.c_uint8 * n)(*[1 if e.slot == 0 else 0 for e in self.entries])
+            terms = torch.zeros(n, dtype=torch.float32, device=self.device)
+            penalty = torch.zeros((), dtype=torch.float32, device=self.device)
+            vb = self._values = (dims, start, terms, penalty)
+        return vb
+
+    def penalty_values(self, kind: str):
+        """``(terms, penalty)``: the per-tensor terms (one float per entry) and the model penalty of the reference's
+        ``compute_{maxbin,difference,inverse}_penalty`` (custom_loss_functions.py:75-116, 161-195, 240-275) for the current
+        parameters and scales, without a backward pass (lq_batch_penalty_values).  Both are persistent device tensors that
+        the next call rewrites in place."""
+        self._check_pointers()
+        dims, start, terms, penalty = self._value_buffers()
+        _hip.check(_hip.load().lq_batch_penalty_values(self._handle, self._KINDS[kind], dims, start, terms.data_ptr(), penalty.data_ptr(),
+                                                       _hip.ptr(self.ws), self.ws.numel(), _hip.stream_ptr(self.device)),
+                   "lq_batch_penalty_values")
+        return terms, penalty
+
+    def inject_penalty_grads(self, kind: str, penalty_rate: float, accumulate_ds: bool = False, values: bool = False):
         """Adds d(penalty_rate * penalty)/dP to every ``P.grad`` and writes d(...)/ds to every ``scale.grad`` in 2-4
         launches.  Call after ``loss.backward()`` of the task loss alone: the reference's objective is
         ``mean(SCCE) + penalty_rate * penalty`` (custom_loss_functions.py:58), so the coefficient of tensor i's term
         ``mean(...)_i`` is the constant ``penalty_rate * numel_i / sum(numel)`` (:110-116) and no autograd node per tensor
         is needed.  Equivalent to differentiating ``SCCE*.compute_total_loss`` (tests/test_gpu_batch.py).
         ``accumulate_ds``: add the penalty's scale gradient to what the ds buffers already hold (nested-quantization layers
-        trained with a loss term: LQ_PENALTY_ACCUMULATE_DS)."""
+        trained with a loss term: LQ_PENALTY_ACCUMULATE_DS).
+        ``values``: also evaluate the penalty (lq_batch_penalty_grads_values: the same gradient launches, then the value
+        launches) and return it as a 0-dim device tensor -- a persistent buffer, rewritten in place by every call; the
+        per-tensor terms are in ``self._values[2]``.  Default: returns ``None`` and issues the gradient launches only."""
         lib = _hip.load()
         n = len(self.entries)
         normalizer = float(sum(e.param.numel() for e in self.entries))
@@ -391,10 +420,18 @@ class FakeQuantBatch:
                     g = e.param.grad = torch.empty_like(e.param.data).copy_(g)
                 grads[i] = g.data_ptr()
         kind_flag = self._KINDS[kind] | (_hip.LQ_PENALTY_ACCUMULATE_DS if accumulate_ds else 0)
-        _hip.check(lib.lq_batch_penalty_grads(self._handle, kind_flag, coeff, grads, _hip.ptr(self.ws), self.ws.numel(),
-                                              _hip.stream_ptr(self.device)), "lq_batch_penalty_grads")
+        penalty = None
+        if values:
+            dims, start, terms, penalty = self._value_buffers()
+            _hip.check(lib.lq_batch_penalty_grads_values(self._handle, kind_flag, coeff, grads, dims, start, terms.data_ptr(),
+                                                         penalty.data_ptr(), _hip.ptr(self.ws), self.ws.numel(),
+                                                         _hip.stream_ptr(self.device)), "lq_batch_penalty_grads_values")
+        else:
+            _hip.check(lib.lq_batch_penalty_grads(self._handle, kind_flag, coeff, grads, _hip.ptr(self.ws), self.ws.numel(),
+                                                  _hip.stream_ptr(self.device)), "lq_batch_penalty_grads")
         for e in self.entries:
             e.nested.scale.grad = e.ds
+        return penalty
 
     # ------------------------------------------------------------------ optimizer
     def scale_adam_step(self, step: Optional[int] = None, step_dev: Optional[torch.Tensor] = None):

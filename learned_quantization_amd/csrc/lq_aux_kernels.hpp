@@ -9,8 +9,9 @@ namespace lq {
 //  Small vector kernels (scale-sized data).
 // ------------------------------------------------------------------------------------------
 // mode 0: out = mean(v[0..n))      mode 1: out = mean(1 / where(v==0, eps, v))
+// the mean by one block of kBlock threads, valid in thread 0 (shared by k_vec_mean and the batch's k_batch_penalty_terms)
 template <int MODE>
-__global__ __launch_bounds__(kBlock) void k_vec_mean(const float* v, int64_t n, float* out) {
+__device__ __forceinline__ float block_vec_mean(const float* v, int64_t n) {
     double acc = 0.0;
     for (int64_t i = threadIdx.x; i < n; i += kBlock) {
         float x = v[i];
@@ -24,11 +25,14 @@ __global__ __launch_bounds__(kBlock) void k_vec_mean(const float* v, int64_t n, 
     __shared__ double lds[kWavesPerBlock];
     if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = acc;
     __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = lds[0];
-        for (int w = 1; w < kWavesPerBlock; ++w) t += lds[w];
-        out[0] = (float)(t / (double)n);
-    }
+    double t = lds[0];
+    for (int w = 1; w < kWavesPerBlock; ++w) t += lds[w];
+    return (float)(t / (double)n);
+}
+template <int MODE>
+__global__ __launch_bounds__(kBlock) void k_vec_mean(const float* v, int64_t n, float* out) {
+    const float m = block_vec_mean<MODE>(v, n);
+    if (threadIdx.x == 0) out[0] = m;
 }
 
 __global__ void k_maxbin_ds(const float* s, const float* mb, const float* c_dev, float c_scale, float* ds, int64_t G) {

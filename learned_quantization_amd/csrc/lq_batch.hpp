@@ -169,13 +169,14 @@ __global__ __launch_bounds__(kBlock) void k_batch_traverse(const Task* __restric
 #endif
 }
 
-template <int OP, int BS = 64>     // BS = 256 when some group of the batch has more than 256 partials (host decides)
-__global__ __launch_bounds__(BS) void k_batch_finalize(const Task* __restrict__ tasks, const uint32_t* __restrict__ gprefix, int ntasks,
-                                                       uint32_t* ws, int accum = 0) {
-    const int ti = find_task(gprefix, ntasks, blockIdx.x);
+// SECOND: the slice of an op's second accumulator (write_partial_second), 4 * np_pad words behind the first
+template <int OP, int BS, bool SECOND>
+__device__ __forceinline__ void batch_finalize_body(const Task* __restrict__ tasks, const uint32_t* __restrict__ gprefix, int ntasks,
+                                                    uint32_t* ws, int accum, uint32_t gb) {      // gb: group of the batch
+    const int ti = find_task(gprefix, ntasks, gb);
     const Task& t = tasks[ti];
     Params p = t.p;
-    p.pa = ws + t.ws_off;
+    p.pa = ws + t.ws_off + (SECOND ? 4 * t.np_pad : 0);
     p.pb = p.pa + t.np_pad;
     p.pc = reinterpret_cast<double*>(p.pb + t.np_pad);
     FinGeom f;
@@ -185,11 +186,25 @@ __global__ __launch_bounds__(BS) void k_batch_finalize(const Task* __restrict__ 
     f.stride1 = t.stride1;
     f.n2 = t.n2;
     f.count = t.count;
-    f.o0 = (OP == OP_MAXBIN_FWD) ? t.mb : t.ds;
+    f.o0 = (OP == OP_MAXBIN_FWD || OP == OP_DIFF_FWD) ? t.mb : t.ds;     // OP_DIFF_FWD: the group's mean |P - P/s| (penalty value)
     f.o1 = nullptr;
     f.o2 = (OP == OP_MAXBIN_FWD) ? t.ties : nullptr;
     f.accum = accum;
-    finalize_block_body<OP, BS>(p, f, (int64_t)(blockIdx.x - t.first_group), (int)threadIdx.x);
+    finalize_block_body<OP, BS>(p, f, (int64_t)(gb - t.first_group), (int)threadIdx.x);
+}
+
+template <int OP, int BS = 64>     // BS = 256 when some group of the batch has more than 256 partials (host decides)
+__global__ __launch_bounds__(BS) void k_batch_finalize(const Task* __restrict__ tasks, const uint32_t* __restrict__ gprefix, int ntasks,
+                                                       uint32_t* ws, int accum = 0) {
+    batch_finalize_body<OP, BS, false>(tasks, gprefix, ntasks, ws, accum, blockIdx.x);
+}
+// Finalize of k_batch_traverse<OP_DIFF_BWD_V> in ONE launch of 2 * groups one-wave blocks: the first `groups` blocks are
+// k_batch_finalize<OP_DIFF_BWD> (ds, the same body: the same bits), the others finalize the sums |P - P/s| of the second slice like
+// OP_DIFF_FWD's: mb[g] = the group's mean |u|.
+__global__ __launch_bounds__(64) void k_batch_finalize_diff_v(const Task* __restrict__ tasks, const uint32_t* __restrict__ gprefix, int ntasks,
+                                                              uint32_t* ws, int accum, uint32_t groups) {
+    if (blockIdx.x < groups) batch_finalize_body<OP_DIFF_BWD, 64, false>(tasks, gprefix, ntasks, ws, accum, blockIdx.x);
+    else batch_finalize_body<OP_DIFF_FWD, 64, true>(tasks, gprefix, ntasks, ws, 0, blockIdx.x - groups);
 }
 
 // Scale gradients of the MaxBin (kind 0) and Inverse (kind 2) penalty terms for every group of every tensor:
@@ -205,6 +220,80 @@ __global__ __launch_bounds__(kBlock) void k_batch_penalty_ds(const Task* __restr
     const float up = cf.c[ti], sg = t.p.s[g], G = (float)t.p.G;
     const float v = (kind == 0) ? -((up / G) * t.mb[g]) / sg : ((sg == 0.0f) ? 0.0f : -((up / G) / sg) / sg);
     t.ds[g] = accum ? t.ds[g] + v : v;
+}
+
+// VALUE of the penalty (custom_loss_functions.py:75-116, 161-195, 240-275).  After the gradient launches every tensor's term is a
+// mean over its groups of something that already sits in memory: mb[g] (MaxBin: max|P|/s of the group; Difference: the group's
+// mean |P - P/s|, left there by k_batch_finalize<OP_DIFF_FWD> -- all groups of a tensor have the same element count, so the mean
+// of the group means is the tensor's mean) or 1/s[g] (Inverse).  Block per tensor, the summation of k_vec_mean (block_vec_mean: f64, fixed order):
+// MaxBin and Inverse terms are the single-tensor entry points' bit for bit.
+struct TermPack {           // table position -> descriptor index (tasks are ordered by work per block)
+    uint16_t index[kBatchMax];
+};
+__global__ __launch_bounds__(kBlock) void k_batch_penalty_terms(const Task* __restrict__ tasks, int kind, TermPack tp, float* __restrict__ terms) {
+    const Task& t = tasks[blockIdx.x];
+    float m;
+    if (kind == 2) m = block_vec_mean<1>(t.p.s, t.p.G);     // the body of k_vec_mean: one code, the same bits
+    else m = block_vec_mean<0>(t.mb, t.p.G);
+    if (threadIdx.x == 0) terms[tp.index[blockIdx.x]] = m;
+}
+
+// terms -> penalty in the reference's order (custom_loss_functions.py:102-116): per layer  t_k * dim_k (+ t_b * dim_b),
+// running fp32 sum over the layers in descriptor order, divided by the normalizer.  Every operation rounds on its own
+// (TensorFlow and torch run them as separate fp32 ops: no fused multiply-add).
+struct CombinePack {
+    float dim[kBatchMax];
+    uint8_t start[kBatchMax];     // 1: this tensor opens a new layer
+};
+__global__ __launch_bounds__(kBatchMax) void k_batch_penalty_combine(const float* __restrict__ terms, int n, CombinePack cp, float normalizer,
+                                                                     float* __restrict__ penalty) {
+    // the products in parallel (one load per thread), the ordered sum by one thread out of LDS: a single thread walking terms[] in
+    // global memory pays a dependent trip per tensor (13 us for the 108 tensors of the ResNet-50-like set)
+    __shared__ float prod[kBatchMax];
+    if ((int)threadIdx.x < n) prod[threadIdx.x] = __fmul_rn(terms[threadIdx.x], cp.dim[threadIdx.x]);
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    float total = 0.f, layer = 0.f;
+    bool have_total = false;
+#pragma unroll 8
+    for (int i = 0; i < n; ++i) {
+        const float pr = prod[i];
+        if (i == 0 || cp.start[i]) {
+            if (i > 0) {
+                total = have_total ? __fadd_rn(total, layer) : layer;       // :112
+                have_total = true;
+            }
+            layer = pr;
+        } else {
+            layer = __fadd_rn(layer, pr);                                   // :110
+        }
+    }
+    total = have_total ? __fadd_rn(total, layer) : layer;
+    penalty[0] = __fdiv_rn(total, normalizer);                              // :116
+}
+
+// One row of the reference's three per-step logs (custom_loss_functions.py:58-71) appended on the device: the cursor lives in
+// device memory, so the launch can be captured once and replayed.  cursor[0] = rows written, cursor[1] = rows dropped.
+__global__ void k_loss_log_append(const float* __restrict__ scce, const float* __restrict__ penalty, float rate, float* __restrict__ rows,
+                                  int64_t capacity, int64_t* __restrict__ cursor, float* __restrict__ last) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const float sc = scce[0];
+    const float rp = __fmul_rn(rate, penalty[0]);
+    const float total = __fadd_rn(sc, rp);                                  // :58
+    if (last) {
+        last[0] = total;
+        last[1] = sc;
+        last[2] = rp;
+    }
+    const int64_t c = cursor[0];
+    if (c >= 0 && c < capacity) {
+        rows[3 * c + 0] = total;
+        rows[3 * c + 1] = sc;
+        rows[3 * c + 2] = rp;
+        cursor[0] = c + 1;
+    } else {
+        cursor[1] = cursor[1] + 1;
+    }
 }
 
 // K6 for every scale of the batch in one launch: block per tensor.

@@ -1648,7 +1648,7 @@ static int fill_task(Task& t, const lq_tensor_desc& d, bool bwd, bool allow_tile
 }
 
 // Orders the table by decreasing work per block (tiles first), assigns block / group prefixes and workspace slices, uploads.
-static int finish_table(lq_task_table& tb, bool bwd) {
+static int finish_table(lq_task_table& tb, bool bwd, int slices = 1) {     // slices: partial slices per task (2: an op with a second accumulator)
     const size_t n = tb.h.size();
     if (!n) return LQ_OK;
     std::vector<size_t> order(n);
@@ -1676,7 +1676,7 @@ static int finish_table(lq_task_table& tb, bool bwd) {
         gp += ng;
         if (bwd) {
             t.ws_off = words;
-            words += 4 * t.np_pad;
+            words += 4 * t.np_pad * slices;
         }
         h2[k] = t;
         idx2[k] = tb.index[order[k]];
@@ -1853,7 +1853,7 @@ int lq_batch_create(const lq_tensor_desc* descs, int n, lq_batch** out) {
     if (!rc) rc = finish_table(b->fwd, false);
     if (!rc) rc = finish_table(b->bwd, true);
     if (!rc) rc = finish_table(b->bwd_o, true);
-    if (!rc) rc = finish_table(b->pen, true);
+    if (!rc) rc = finish_table(b->pen, true, 2);      // OP_DIFF_BWD_V writes a second partial per work unit
     if (!rc && !b->pen.h.empty()) {
         hipError_t e = hipMalloc(&b->mb_d, (size_t)b->pen.groups * sizeof(float));
         if (e == hipSuccess) e = hipMalloc(&b->ties_d, (size_t)b->pen.groups * sizeof(uint32_t));
@@ -1999,17 +1999,79 @@ static int batch_scale_grad(const lq_batch* b, const float* const* dy, void* ws,
     return check_hip("batch finalize launch");
 }
 
-extern "C" {
+// Value outputs of the penalty entry points (lq_hip.h: lq_batch_penalty_values, lq_batch_penalty_grads_values).
+struct PenaltyValueArgs {
+    const float* dims;
+    const uint8_t* layer_start;
+    float* terms;
+    float* penalty;
+};
 
-int lq_batch_penalty_grads(const lq_batch* b, int kind, const float* coeff, float* const* grad, void* ws, size_t ws_bytes,
-                           void* stream) {
-    if (!b) return fail(LQ_EINVAL, "lq_batch_penalty_grads: NULL batch");
+// everything that can be said about the arguments without the batch: kind first, then the outputs
+static int check_penalty_value_args(const char* fn, int kind, const PenaltyValueArgs& va) {
+    if (kind < LQ_PENALTY_MAXBIN || kind > LQ_PENALTY_INVERSE) return fail(LQ_EINVAL, "%s: bad kind %d", fn, kind);
+    if (!va.terms) return fail(LQ_EINVAL, "%s: terms_dev is NULL", fn);
+    if (!va.penalty) return fail(LQ_EINVAL, "%s: penalty_dev is NULL", fn);
+    if (!aligned(va.terms, 4) || !aligned(va.penalty, 4)) return fail(LQ_EALIGN, "%s: terms_dev / penalty_dev must be 4-byte aligned", fn);
+    if (!va.dims) return fail(LQ_EINVAL, "%s: dims is NULL", fn);
+    if (!va.layer_start) return fail(LQ_EINVAL, "%s: layer_start is NULL", fn);
+    return LQ_OK;
+}
+
+static int check_penalty_workspace(const char* fn, const lq_batch* b, const void* ws, size_t ws_bytes) {
+    if (!ws) return fail(LQ_EWORKSPACE, "%s: workspace is NULL (need %zu bytes)", fn, b->ws_bytes);
+    if (!aligned(ws, 16)) return fail(LQ_EALIGN, "%s: workspace must be 16-byte aligned", fn);
+    if (ws_bytes < b->ws_bytes) return fail(LQ_EWORKSPACE, "%s: workspace too small: %zu < %zu bytes", fn, ws_bytes, b->ws_bytes);
+    return LQ_OK;
+}
+
+// The value launches.  `have_mb`: the gradient launches of this call have just left, for every group, mb[g] (MaxBin) or the mean
+// |P - P/s| (Difference, co-emitted by OP_DIFF_BWD_V) in the batch's buffer.  Without them (values only) a forward traversal of
+// the batch and its finalize produce the same numbers first.
+static int launch_penalty_values(const char* fn, const lq_batch* b, int kind, const PenaltyValueArgs& va, void* ws, bool have_mb, hipStream_t st) {
+    const lq_task_table& tb = b->pen;
+    const int nt = (int)tb.h.size();
+    const uint32_t* gpre = tb.prefix_d + nt;
+    CoefPack cf;
+    PtrPack none;
+    memset(&cf, 0, sizeof(cf));
+    memset(&none, 0, sizeof(none));
+    if (kind == LQ_PENALTY_MAXBIN && !have_mb) {
+        hipLaunchKernelGGL((k_batch_traverse<OP_MAXBIN_FWD>), dim3(tb.blocks), dim3(kBlock), 0, st, tb.d, tb.block_task_d, nt, (uint32_t*)ws, none, 0, cf);
+        hipLaunchKernelGGL((k_batch_finalize<OP_MAXBIN_FWD>), dim3(tb.groups), dim3(64), 0, st, tb.d, gpre, nt, (uint32_t*)ws, 0);
+    } else if (kind == LQ_PENALTY_DIFFERENCE && !have_mb) {
+        hipLaunchKernelGGL((k_batch_traverse<OP_DIFF_FWD>), dim3(tb.blocks), dim3(kBlock), 0, st, tb.d, tb.block_task_d, nt, (uint32_t*)ws, none, 0, cf);
+        hipLaunchKernelGGL((k_batch_finalize<OP_DIFF_FWD>), dim3(tb.groups), dim3(64), 0, st, tb.d, gpre, nt, (uint32_t*)ws, 0);
+    }
+    TermPack tp;
+    CombinePack cp;
+    memset(&tp, 0, sizeof(tp));
+    memset(&cp, 0, sizeof(cp));
+    double normalizer = 0.0;                                    // custom_loss_functions.py:114, a Python float
+    for (int i = 0; i < nt; ++i) {
+        tp.index[i] = (uint16_t)tb.index[i];
+        cp.dim[i] = va.dims[i];
+        cp.start[i] = va.layer_start[i] ? 1 : 0;
+        normalizer += (double)va.dims[i];
+    }
+    hipLaunchKernelGGL(k_batch_penalty_terms, dim3(nt), dim3(kBlock), 0, st, tb.d, kind, tp, va.terms);
+    hipLaunchKernelGGL(k_batch_penalty_combine, dim3(1), dim3(kBatchMax), 0, st, va.terms, nt, cp, (float)normalizer, va.penalty);
+    return check_hip(fn);
+}
+
+static int batch_penalty_grads(const char* fn, const lq_batch* b, int kind, const float* coeff, float* const* grad, void* ws, size_t ws_bytes,
+                               void* stream, const PenaltyValueArgs* va) {
+    if (va) {
+        const int rc = check_penalty_value_args(fn, kind & ~LQ_PENALTY_ACCUMULATE_DS, *va);
+        if (rc) return rc;
+    }
+    if (!b) return fail(LQ_EINVAL, "%s: NULL batch", fn);
     const int accum = (kind & LQ_PENALTY_ACCUMULATE_DS) ? 1 : 0;
     kind &= ~LQ_PENALTY_ACCUMULATE_DS;
-    if (kind < LQ_PENALTY_MAXBIN || kind > LQ_PENALTY_INVERSE) return fail(LQ_EINVAL, "lq_batch_penalty_grads: bad kind %d", kind);
-    if (!coeff) return fail(LQ_EINVAL, "lq_batch_penalty_grads: coeff is NULL");
+    if (kind < LQ_PENALTY_MAXBIN || kind > LQ_PENALTY_INVERSE) return fail(LQ_EINVAL, "%s: bad kind %d", fn, kind);
+    if (!coeff) return fail(LQ_EINVAL, "%s: coeff is NULL", fn);
     const lq_task_table& tb = b->pen;
-    if (tb.h.size() != (size_t)b->n) return fail(LQ_EINVAL, "lq_batch_penalty_grads: every tensor of the batch needs a ds buffer");
+    if (tb.h.size() != (size_t)b->n) return fail(LQ_EINVAL, "%s: every tensor of the batch needs a ds buffer", fn);
     CoefPack cf;
     PtrPack pk;
     memset(&pk, 0, sizeof(pk));
@@ -2018,16 +2080,16 @@ int lq_batch_penalty_grads(const lq_batch* b, int kind, const float* coeff, floa
     for (int i = 0; i < nt; ++i) cf.c[i] = coeff[tb.index[i]];
     hipStream_t st = (hipStream_t)stream;
     if (kind != LQ_PENALTY_INVERSE) {
-        if (!grad) return fail(LQ_EINVAL, "lq_batch_penalty_grads: grad pointers are NULL");
-        if (!ws) return fail(LQ_EWORKSPACE, "lq_batch_penalty_grads: workspace is NULL (need %zu bytes)", b->ws_bytes);
-        if (!aligned(ws, 16)) return fail(LQ_EALIGN, "lq_batch_penalty_grads: workspace must be 16-byte aligned");
-        if (ws_bytes < b->ws_bytes) return fail(LQ_EWORKSPACE, "lq_batch_penalty_grads: workspace too small: %zu < %zu bytes", ws_bytes, b->ws_bytes);
+        if (!grad) return fail(LQ_EINVAL, "%s: grad pointers are NULL", fn);
+        if (!ws) return fail(LQ_EWORKSPACE, "%s: workspace is NULL (need %zu bytes)", fn, b->ws_bytes);
+        if (!aligned(ws, 16)) return fail(LQ_EALIGN, "%s: workspace must be 16-byte aligned", fn);
+        if (ws_bytes < b->ws_bytes) return fail(LQ_EWORKSPACE, "%s: workspace too small: %zu < %zu bytes", fn, ws_bytes, b->ws_bytes);
         for (int i = 0; i < nt; ++i) {
             float* gi = grad[tb.index[i]];
-            if (!gi || !aligned(gi, 4)) return fail(LQ_EINVAL, "lq_batch_penalty_grads: gradient buffer of tensor %d missing", tb.index[i]);
+            if (!gi || !aligned(gi, 4)) return fail(LQ_EINVAL, "%s: gradient buffer of tensor %d missing", fn, tb.index[i]);
             const Task& t = tb.h[i];
             const bool wants16 = (t.mode != MODE_COL && t.vec) || (t.mode == MODE_COL && t.col_variant >= 4);
-            if (wants16 && !aligned(gi, 16)) return fail(LQ_EALIGN, "lq_batch_penalty_grads: gradient buffer of tensor %d is not 16-byte aligned", tb.index[i]);
+            if (wants16 && !aligned(gi, 16)) return fail(LQ_EALIGN, "%s: gradient buffer of tensor %d is not 16-byte aligned", fn, tb.index[i]);
             pk.dy[i] = gi;
         }
     }
@@ -2040,12 +2102,62 @@ int lq_batch_penalty_grads(const lq_batch* b, int kind, const float* coeff, floa
         hipLaunchKernelGGL((k_batch_traverse<OP_MAXBIN_BWD>), dim3(tb.blocks), dim3(kBlock), 0, st, tb.d, tb.block_task_d, nt, (uint32_t*)ws, pk, 2, cf);
         hipLaunchKernelGGL(k_batch_penalty_ds, dim3((unsigned)ceil_div(tb.groups, kBlock)), dim3(kBlock), 0, st, tb.d, gpre, nt, tb.groups, 0, cf, accum);
     } else if (kind == LQ_PENALTY_DIFFERENCE) {
-        hipLaunchKernelGGL((k_batch_traverse<OP_DIFF_BWD>), dim3(tb.blocks), dim3(kBlock), 0, st, tb.d, tb.block_task_d, nt, (uint32_t*)ws, pk, 2, cf);
-        hipLaunchKernelGGL((k_batch_finalize<OP_DIFF_BWD>), dim3(tb.groups), dim3(64), 0, st, tb.d, gpre, nt, (uint32_t*)ws, accum);
+        if (va) {
+            // the same traversal with a second accumulator (sum |u| next to sum gi * (P/s) / s: OP_DIFF_BWD_V, lq_ops.hpp); its
+            // partials go to the second slice of every task; one finalize launch emits ds and, into the mb buffer, the groups' mean |u|
+            if (tb.groups > 0x3fffffffu) return fail(LQ_EINVAL, "%s: too many groups for the two-slice finalize (%u)", fn, tb.groups);
+            hipLaunchKernelGGL((k_batch_traverse<OP_DIFF_BWD_V>), dim3(tb.blocks), dim3(kBlock), 0, st, tb.d, tb.block_task_d, nt, (uint32_t*)ws, pk, 2, cf);
+            hipLaunchKernelGGL(k_batch_finalize_diff_v, dim3(2 * tb.groups), dim3(64), 0, st, tb.d, gpre, nt, (uint32_t*)ws, accum, tb.groups);
+        } else {
+            hipLaunchKernelGGL((k_batch_traverse<OP_DIFF_BWD>), dim3(tb.blocks), dim3(kBlock), 0, st, tb.d, tb.block_task_d, nt, (uint32_t*)ws, pk, 2, cf);
+            hipLaunchKernelGGL((k_batch_finalize<OP_DIFF_BWD>), dim3(tb.groups), dim3(64), 0, st, tb.d, gpre, nt, (uint32_t*)ws, accum);
+        }
     } else {
         hipLaunchKernelGGL(k_batch_penalty_ds, dim3((unsigned)ceil_div(tb.groups, kBlock)), dim3(kBlock), 0, st, tb.d, gpre, nt, tb.groups, 2, cf, accum);
     }
-    return check_hip("batch penalty launch");
+    int rc = check_hip("batch penalty launch");
+    if (rc || !va) return rc;
+    return launch_penalty_values(fn, b, kind, *va, ws, kind != LQ_PENALTY_INVERSE, st);
+}
+
+extern "C" {
+
+int lq_batch_penalty_grads(const lq_batch* b, int kind, const float* coeff, float* const* grad, void* ws, size_t ws_bytes,
+                           void* stream) {
+    return batch_penalty_grads("lq_batch_penalty_grads", b, kind, coeff, grad, ws, ws_bytes, stream, nullptr);
+}
+
+int lq_batch_penalty_grads_values(const lq_batch* b, int kind, const float* coeff, float* const* grad, const float* dims,
+                                  const uint8_t* layer_start, float* terms_dev, float* penalty_dev, void* ws, size_t ws_bytes,
+                                  void* stream) {
+    const PenaltyValueArgs va = {dims, layer_start, terms_dev, penalty_dev};
+    return batch_penalty_grads("lq_batch_penalty_grads_values", b, kind, coeff, grad, ws, ws_bytes, stream, &va);
+}
+
+int lq_batch_penalty_values(const lq_batch* b, int kind, const float* dims, const uint8_t* layer_start, float* terms_dev,
+                            float* penalty_dev, void* ws, size_t ws_bytes, void* stream) {
+    const char* fn = "lq_batch_penalty_values";
+    const PenaltyValueArgs va = {dims, layer_start, terms_dev, penalty_dev};
+    int rc = check_penalty_value_args(fn, kind, va);
+    if (rc) return rc;
+    if (!b) return fail(LQ_EINVAL, "%s: NULL batch", fn);
+    if (b->pen.h.size() != (size_t)b->n) return fail(LQ_EINVAL, "%s: every tensor of the batch needs a ds buffer", fn);
+    if (kind != LQ_PENALTY_INVERSE && (rc = check_penalty_workspace(fn, b, ws, ws_bytes))) return rc;
+    return launch_penalty_values(fn, b, kind, va, ws, false, (hipStream_t)stream);
+}
+
+int lq_loss_log_append(const float* scce_dev, const float* penalty_dev, float rate, float* rows_dev, int64_t capacity,
+                       int64_t* cursor_dev, float* last_dev, void* stream) {
+    if (!scce_dev || !penalty_dev) return fail(LQ_EINVAL, "lq_loss_log_append: scce_dev / penalty_dev is NULL");
+    if (!rows_dev) return fail(LQ_EINVAL, "lq_loss_log_append: rows_dev is NULL");
+    if (!cursor_dev) return fail(LQ_EINVAL, "lq_loss_log_append: cursor_dev is NULL");
+    if (capacity <= 0) return fail(LQ_EINVAL, "lq_loss_log_append: capacity must be positive");
+    if (!aligned(scce_dev, 4) || !aligned(penalty_dev, 4) || !aligned(rows_dev, 4) || !aligned(last_dev, 4))
+        return fail(LQ_EALIGN, "lq_loss_log_append: scce_dev, penalty_dev, rows_dev and last_dev must be 4-byte aligned");
+    if (!aligned(cursor_dev, 8)) return fail(LQ_EALIGN, "lq_loss_log_append: cursor_dev must be 8-byte aligned (two int64)");
+    hipLaunchKernelGGL(k_loss_log_append, dim3(1), dim3(64), 0, (hipStream_t)stream, scce_dev, penalty_dev, rate, rows_dev, capacity, cursor_dev,
+                       last_dev);
+    return check_hip("lq_loss_log_append");
 }
 
 int lq_batch_scale_adam(const lq_batch* b, double lr, double beta1, double beta2, double eps, int64_t step,

@@ -20,6 +20,7 @@ struct OpBase {
     static constexpr bool kDy = false;
     static constexpr bool kStore = false;
     static constexpr bool kReduce = false;
+    static constexpr bool kSecond = false;    // the op carries a second f64 sum (see OP_DIFF_BWD_V)
     template <typename A>
     __device__ static __forceinline__ A init() {
         A a;
@@ -263,6 +264,38 @@ struct OpT<OP_DIFF_BWD> : OpBase {
         acc.c += (double)((gi * pq) / c.s);
         const float g = gi - gi / c.s;
         return p.accum ? p.out[i] + g : g;
+    }
+};
+
+// K5b backward + value: the OP_DIFF_BWD arithmetic, untouched (same acc.c, same stores: dP and ds are its bits), and next to it
+// sum |u| = sum |P - P/s| of OP_DIFF_FWD for the VALUE of the term -- u is already in a register, so the value costs no second
+// read of the tensor.  The second sum is an f64 like the first; while a thread accumulates, its bits live in the (a, b) pair of
+// the accumulator, which this op does not use otherwise (64 bits, the registers of one double).  Before the traversal reduces,
+// take_second() moves it into the c of a SECOND accumulator of the same type and clears (a, b): both go through the same
+// standard merge one after the other, the first exactly as OP_DIFF_BWD's, the second into a second slice of partials.
+template <>
+struct OpT<OP_DIFF_BWD_V> : OpT<OP_DIFF_BWD> {
+    static constexpr bool kSecond = true;
+    __device__ static __forceinline__ float elem(const Params& p, const Ctx& c, int64_t i, float x, float, Acc& acc) {
+        float pq = x / c.s;
+        float u = x - pq;
+        float sgn = (u > 0.f) ? 1.f : ((u < 0.f) ? -1.f : 0.f);
+        float gi = sgn * c.k0;
+        acc.c += (double)((gi * pq) / c.s);
+        const double v = __hiloint2double((int)acc.b, (int)acc.a) + (double)fabsf(u);      // custom_loss_functions.py:175
+        acc.a = (uint32_t)__double2loint(v);
+        acc.b = (uint32_t)__double2hiint(v);
+        const float g = gi - gi / c.s;
+        return p.accum ? p.out[i] + g : g;
+    }
+    __device__ static __forceinline__ Acc take_second(Acc& acc) {
+        Acc s;
+        s.a = 0u;
+        s.b = 0u;
+        s.c = __hiloint2double((int)acc.b, (int)acc.a);
+        acc.a = 0u;
+        acc.b = 0u;
+        return s;
     }
 };
 

@@ -41,6 +41,15 @@ __device__ __forceinline__ void write_partial(const Params& p, int64_t idx, cons
     p.pc[idx] = acc.c;
 }
 
+// Partial of an op's SECOND accumulator (OpT::kSecond): the slice right behind the first one.  A slice is 4 * np words
+// (u32[np], u32[np], f64[np]) with np = pb - pa; the host sizes the task's workspace for both (lq_batch_create, penalty table).
+__device__ __forceinline__ void write_partial_second(const Params& p, int64_t idx, const Acc& acc) {
+    const int64_t np = p.pb - p.pa;
+    p.pa[4 * np + idx] = acc.a;
+    p.pb[4 * np + idx] = acc.b;
+    p.pc[2 * np + idx] = acc.c;
+}
+
 template <int OP>
 __device__ __forceinline__ void emit_direct(const Params& p, int64_t g, const Acc& acc);     // lq_traverse.hpp (needs FinT)
 

@@ -180,12 +180,19 @@ __device__ __forceinline__ void row_stream_body(const Params& p, int64_t L, int6
         }
     }
     if (O::kReduce) {
+        [[maybe_unused]] Acc acc2;
+        if constexpr (O::kSecond) acc2 = O::take_second(acc);
         if constexpr (O::kStdMerge) {
             block_reduce_dpp<BS>(acc);
         } else {
             block_reduce<O, Acc, BS>(acc);
         }
         if (threadIdx.x == 0) write_partial_t<OP>(p, row * nc + ck, acc);
+        if constexpr (O::kSecond) {
+            __syncthreads();                     // the reduction's LDS words are still being read by wave 0
+            block_reduce_dpp<BS>(acc2);
+            if (threadIdx.x == 0) write_partial_second(p, row * nc + ck, acc2);
+        }
     }
 }
 
@@ -251,12 +258,18 @@ __device__ __forceinline__ void row_small_body(const Params& p, int64_t R, int L
         }
     }
     if (O::kReduce) {
+        [[maybe_unused]] Acc acc2;
+        if constexpr (O::kSecond) {
+            acc2 = O::take_second(acc);
+            wave_reduce<O>(acc2, lpr);
+        }
         wave_reduce<O>(acc, lpr);   // all 64 lanes execute the shuffles; teams never mix (xor < lpr)
         if (valid && lane == 0) {
             // group-major partials (index g*outer + o for row o*G + g): the finalize of group g then reads one contiguous
             // run instead of every G-th word (16 groups x 16384 rows: 29.5 us of strided gathers)
             const int64_t o = row / p.G, g = row - o * p.G;
             write_partial_t<OP>(p, (p.G > 1 ? g * p.outer + o : row), acc);
+            if constexpr (O::kSecond) write_partial_second(p, (p.G > 1 ? g * p.outer + o : row), acc2);
         }
     }
 }
@@ -342,6 +355,11 @@ __device__ __forceinline__ void col_tile_body(const Params& p, int64_t C, int64_
         }
     }
     if (O::kReduce) {
+        [[maybe_unused]] Acc acc2[VW];
+        if constexpr (O::kSecond) {
+#pragma unroll
+            for (int k = 0; k < VW; ++k) acc2[k] = O::take_second(acc[k]);
+        }
 #pragma unroll
         for (int k = 0; k < VW; ++k) lds[w * (64 * VW) + lane * VW + k] = acc[k];
         __syncthreads();
@@ -352,6 +370,21 @@ __device__ __forceinline__ void col_tile_body(const Params& p, int64_t C, int64_
 #pragma unroll
                 for (int ww = 1; ww < 4; ++ww) O::merge(r, lds[ww * (64 * VW) + lane * VW + k]);   // fixed wave order
                 write_partial_t<OP>(p, by * C + col0 + k, r);
+            }
+        }
+        if constexpr (O::kSecond) {              // the second accumulators take the same way through the same LDS
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < VW; ++k) lds[w * (64 * VW) + lane * VW + k] = acc2[k];
+            __syncthreads();
+            if (w == 0 && active) {
+#pragma unroll
+                for (int k = 0; k < VW; ++k) {
+                    Acc r = lds[lane * VW + k];
+#pragma unroll
+                    for (int ww = 1; ww < 4; ++ww) O::merge(r, lds[ww * (64 * VW) + lane * VW + k]);
+                    write_partial_second(p, by * C + col0 + k, r);
+                }
             }
         }
     }
@@ -391,6 +424,8 @@ __device__ __forceinline__ void col_small_body(const Params& p, int C, int64_t R
         }
     }
     if (O::kReduce) {
+        [[maybe_unused]] Acc acc2;
+        if constexpr (O::kSecond) acc2 = O::take_second(acc);
         lds[threadIdx.x] = acc;
         __syncthreads();
         if ((int)threadIdx.x < C) {
@@ -398,6 +433,17 @@ __device__ __forceinline__ void col_small_body(const Params& p, int C, int64_t R
             for (int ww = 0; ww < 4; ++ww)
                 for (int q = 0; q < k; ++q) O::merge(r, lds[ww * 64 + q * C + (int)threadIdx.x]);      // fixed order
             write_partial_t<OP>(p, by * C + threadIdx.x, r);
+        }
+        if constexpr (O::kSecond) {
+            __syncthreads();
+            lds[threadIdx.x] = acc2;
+            __syncthreads();
+            if ((int)threadIdx.x < C) {
+                Acc r = O::template init<Acc>();
+                for (int ww = 0; ww < 4; ++ww)
+                    for (int q = 0; q < k; ++q) O::merge(r, lds[ww * 64 + q * C + (int)threadIdx.x]);
+                write_partial_second(p, by * C + threadIdx.x, r);
+            }
         }
     }
 }
@@ -459,6 +505,7 @@ __device__ __forceinline__ void col_periodic4_body(const Params& p, int C, int64
             }
         }
     }
+    static_assert(!O::kSecond, "the periodic float4 stream carries one accumulator per column (not planned for OP_DIFF_BWD_V)");
     if (O::kReduce) {
         Acc* lds2 = lds + kBlock * 4;
 #pragma unroll
@@ -578,6 +625,8 @@ struct FinT<OP_DIFF_BWD> {
         return 0.f;
     }
 };
+template <>
+struct FinT<OP_DIFF_BWD_V> : FinT<OP_DIFF_BWD> {};
 
 template <int OP>
 __device__ __forceinline__ void emit_direct(const Params& p, int64_t g, const Acc& acc) {

@@ -65,7 +65,7 @@ def log_model_structure(model: torch.nn.Module, folder_name: str, filename: str 
 
 
 def fit(tr: Trainer, epochs: int, steps_per_epoch: int, batch: int, callbacks, lr: float, use_scheduler: bool = False,
-        val_steps: int = 2, seed: int = 42):
+        val_steps: int = 2, seed: int = 42, with_penalty: bool = False):
     """model.fit counterpart: callbacks get Keras-style ``logs`` dicts."""
     g = torch.Generator(device=tr.device).manual_seed(seed)
     val = [synthetic_batch(tr.config, batch, tr.device, g) for _ in range(val_steps)]
@@ -93,7 +93,9 @@ def fit(tr: Trainer, epochs: int, steps_per_epoch: int, batch: int, callbacks, l
             tr.model.eval()
             p = tr.model(x)
             run_acc = float((p.argmax(1) == y).float().mean())
-        vl, va = zip(*(tr.evaluate(vx, vy) for vx, vy in val))
+        vl, va = zip(*(tr.evaluate(vx, vy, with_penalty=with_penalty) for vx, vy in val))
+        if tr.loss_log is not None:
+            tr.flush_loss_log()              # custom_losses/*.log: one line per step of this epoch (CL-F:60-71)
         logs = {"loss": run_loss / steps_per_epoch, "accuracy": run_acc, "val_loss": float(np.mean(vl)),
                 "val_accuracy": float(np.mean(va)), "lr": lr}
         history.append(logs)
@@ -121,9 +123,14 @@ def main(argv=None):
     ap.add_argument("--baseline-weights", default=None)
     ap.add_argument("--log-root", default="logs")
     ap.add_argument("--batched", action="store_true")
+    ap.add_argument("--loss-values", action="store_true",
+                    help="with --custom_loss: loss and val_loss include rate * penalty (what Keras reports for compute_total_loss) "
+                         "and custom_losses/*.log get one line per step, from a device-side log flushed at every epoch end")
     ap.add_argument("--export-packed", action="store_true",
                     help="also write the lossless bit-packed export (weights_packed.npz/.zip, packed_sizes.log; not in the reference)")
     args = ap.parse_args(argv)
+    if args.loss_values and not args.custom_loss:
+        ap.error("--loss-values needs --custom_loss (the nested-quantization variant has no loss term to evaluate)")
     if not torch.cuda.is_available():
         raise SystemExit("needs an MI355X (no CPU fallback)")
     dev = torch.device("cuda", 0)
@@ -134,7 +141,8 @@ def main(argv=None):
     os.makedirs(log_dir, exist_ok=True)
 
     tr = Trainer(args.config, mode, value, args.orientation, args.custom_loss, lr=args.lr, seed=args.seed, device=dev,
-                 log_dir=log_dir, batched=args.batched)
+                 log_dir=log_dir, batched=args.batched, loss_values=args.loss_values,
+                 loss_log_capacity=max(4096, args.steps_per_epoch))
     if args.training == "post_training":
         if args.config != "mnist" or not args.baseline_weights:
             raise SystemExit("post_training needs --config mnist --baseline-weights <npz with W1,b1,W2,b2> "
@@ -150,7 +158,7 @@ def main(argv=None):
     callbacks.append(AccuracyLossTrackingCallBack(log_dir))
     t0 = time.perf_counter()
     history = fit(tr, args.epochs, args.steps_per_epoch, args.batch, callbacks, args.lr,
-                  use_scheduler=(args.config == "imagenette"), seed=args.seed)
+                  use_scheduler=(args.config == "imagenette"), seed=args.seed, with_penalty=args.loss_values)
     sizes = save_compress_parameters(tr.model, log_dir)
     packed = save_packed_parameters(tr.model, log_dir) if args.export_packed else None
     stats = callbacks[0].stats()
@@ -159,6 +167,10 @@ def main(argv=None):
             "first_layer_unique_integers": stats["unique_k"], "first_layer_max_abs_q": float(stats["max_k"].max())}
     if packed is not None:
         line["packed"] = packed
+    if args.loss_values:
+        # rate * penalty of the final parameters: what val_loss holds on top of the cross-entropy (CL-F:58)
+        penalty = tr.batch.penalty_values(tr.loss_kind)[1] if tr.batch is not None else tr.loss_obj._penalty()
+        line["rate_penalty"] = float(tr.penalty_rate * penalty.detach())
     print(json.dumps(line))
 
 

@@ -13,17 +13,19 @@ backward; the per-layer scalar glue ``term * dim``, the sum over layers and ``/ 
 are 0-dim device tensor arithmetic.  The sparse categorical cross-entropy is stock.
 
 The reference writes three ``tf.print`` lines per step into ``<log_dir>/custom_losses/*.log``
-(CL-F:60-71).  That forces a device->host sync per step, so it is opt-in here
-(``log_every_step=True``); the files are always created, as ``setup_logger`` does (CL-F:13-30).
+(CL-F:60-71).  Printed from the host that forces a device->host sync per step (``log_every_step=True``, opt-in);
+``LossLog`` appends the same three numbers to a device buffer instead (one tiny launch per step, capturable into a
+hipGraph) and writes the files when it is flushed.  The files are always created, as ``setup_logger`` does (CL-F:13-30).
 """
 from __future__ import annotations
 
 import os
+import warnings
 from typing import List, Sequence
 
 import torch
 
-from . import ops
+from . import _hip, ops
 
 _EPSILON = 1e-7   # keras.backend.epsilon()
 
@@ -130,6 +132,63 @@ class _SCCEBase:
     def _append(self, name, value):
         with open(os.path.join(self.custom_loss_dir, name), "a") as f:
             f.write(f"{value}\n")
+
+
+class LossLog:
+    """The reference's three per-step logs (CL-F:60-71) without a synchronisation per step.
+
+    ``append(scce, penalty)`` enqueues lq_loss_log_append: the row ``{scce + rate * penalty, scce, rate * penalty}``
+    (float32, CL-F:58) goes to ``rows[cursor]`` on the device and the device-side cursor advances -- so the launch can be
+    recorded into a hipGraph once and replayed; when the buffer is full the row is counted as dropped instead.
+    ``flush()`` is one device->host copy: it appends one value per line to ``total_loss.log``, ``scce_loss.log`` and the
+    term's log (``_SCCEBase._append``'s format), resets the cursor and returns ``(rows_written, rows_dropped)``."""
+
+    def __init__(self, loss_obj: "_SCCEBase", capacity: int = 4096, device=None):
+        if capacity <= 0:
+            raise ValueError("LossLog: capacity must be positive")
+        self.loss_obj = loss_obj
+        self.capacity = int(capacity)
+        self.device = device
+        self.rows = self.cursor = self.last = None
+        if device is not None:
+            self._allocate(device)
+
+    def _allocate(self, device):
+        self.device = device
+        self.rows = torch.zeros(self.capacity, 3, dtype=torch.float32, device=device)
+        self.cursor = torch.zeros(2, dtype=torch.int64, device=device)       # rows written, rows dropped
+        self.last = torch.zeros(3, dtype=torch.float32, device=device)       # the latest row, logged or dropped
+
+    def append(self, scce: torch.Tensor, penalty: torch.Tensor) -> torch.Tensor:
+        """``scce``: mean cross-entropy, ``penalty``: the un-scaled penalty; both 0-dim float32 device tensors.  Returns
+        ``last`` (``[total, scce, rate * penalty]``), a persistent device tensor rewritten by every call."""
+        if self.rows is None:
+            self._allocate(scce.device)
+        scce = _hip.require_device_f32(scce, "scce")
+        penalty = _hip.require_device_f32(penalty, "penalty")
+        _hip.check(_hip.load().lq_loss_log_append(scce.data_ptr(), penalty.data_ptr(), float(self.loss_obj.penalty_rate),
+                                                  self.rows.data_ptr(), self.capacity, self.cursor.data_ptr(),
+                                                  self.last.data_ptr(), _hip.stream_ptr(self.rows.device)), "lq_loss_log_append")
+        return self.last
+
+    def flush(self):
+        if self.rows is None:
+            return 0, 0
+        count, dropped = (int(v) for v in self.cursor.tolist())              # the device->host copy (synchronises)
+        rows = self.rows[:count].tolist() if count else []
+        self.cursor.zero_()
+        return self._write(rows, dropped)
+
+    def _write(self, rows, dropped: int):
+        """Host side of ``flush``: ``rows`` = list of ``[total, scce, rate * penalty]``."""
+        obj = self.loss_obj
+        for col, name in enumerate(("total_loss.log", "scce_loss.log", obj._penalty_log)):
+            with open(os.path.join(obj.custom_loss_dir, name), "a") as f:
+                f.write("".join(f"{r[col]}\n" for r in rows))
+        if dropped:
+            warnings.warn(f"LossLog: {dropped} rows were dropped (capacity {self.capacity}); flush more often or build it larger",
+                          RuntimeWarning, stacklevel=3)
+        return len(rows), dropped
 
 
 class SCCEMaxBin(_SCCEBase):

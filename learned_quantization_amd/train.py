@@ -29,7 +29,7 @@ import torch.distributed as dist
 from . import layers as L
 from . import _hip
 from .ddp import CaptureRefused, DataParallel, capture_with_agreement, control_group
-from .losses import SCCEDifference, SCCEInverse, SCCEMaxBin, sparse_categorical_crossentropy
+from .losses import LossLog, SCCEDifference, SCCEInverse, SCCEMaxBin, sparse_categorical_crossentropy
 from .models import INPUT_SHAPES, build_model
 from .optim import KerasAdam, ScaleAdam, non_scale_parameters, scale_parameters
 
@@ -64,7 +64,17 @@ class Trainer:
     def __init__(self, config="cifar", mode="nq", value=1e-11, orientation="channelwise", loss: Optional[str] = None,
                  lr=1e-4, seed=42, device=None, ddp_mode="A", log_dir="logs", graph=False, batched=False,
                  bucket_mb: float = 25.0, overlap: bool = True, graph_collectives: Optional[bool] = None,
-                 force_collectives: bool = False, kernel_storage: str = "oihw"):
+                 force_collectives: bool = False, kernel_storage: str = "oihw", loss_values: bool = False,
+                 loss_log_capacity: int = 4096):
+        """``loss_values`` (modes with a loss term): the step also EVALUATES the penalty -- batched: as a by-product of the
+        gradient injection (lq_batch_penalty_grads_values); per-tensor path: the loss object's own device scalar -- appends the
+        reference's three per-step numbers (CL-F:58-71) to a device-side ``LossLog`` (no synchronisation, capturable) and
+        ``step()`` / ``step_graphed()`` return ``mean(SCCE) (+ regularisers) + rate * penalty``.  ``loss_terms`` is a
+        persistent device tensor of the trainer, ``[total, scce, rate * penalty]`` of the latest step with the regularisers
+        in ``total`` in both forms (the log's rows never hold them: Keras adds them outside ``compute_total_loss``).  Batched,
+        the returned loss IS ``loss_terms[0]``: one buffer, rewritten by every step -- ``clone()`` it to keep the losses of
+        several steps (the per-tensor path returns the differentiated scalar, a fresh tensor every step).
+        ``flush_loss_log()`` writes the files."""
         self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
         torch.manual_seed(seed)
         L.reset_layer_names()
@@ -118,6 +128,13 @@ class Trainer:
         else:
             self.scale_opt = ScaleAdam(scale_parameters(self.model), lr=lr, capturable=graph)
         self.regularized = [l for l in self.custom_layers if l.regularizer is not None]
+        self.loss_values = bool(loss_values)
+        if self.loss_values and self.loss_obj is None:
+            raise ValueError("loss_values=True needs a loss term (mode 'cl' or 'nqcl')")
+        self.loss_log = LossLog(self.loss_obj, loss_log_capacity, self.device) if self.loss_values else None
+        # [total, scce, rate * penalty] of the latest step, regularisers in the total (persistent: a captured graph rewrites it)
+        self.loss_terms = torch.zeros(3, dtype=torch.float32, device=self.device) if self.loss_values else None
+        self._scce = self._task = None       # this step's mean(SCCE) and mean(SCCE) + regularisers (batched form)
         self.graph = None
         self.graph_update = None
         if graph_collectives is None:          # default: capture the collective where the backend can be captured
@@ -130,10 +147,26 @@ class Trainer:
 
     def loss(self, y, p):
         if self.loss_obj is not None and self.batch is None:
-            per_sample = self.loss_obj.compute_total_loss(y, p)
+            if self.loss_values:
+                # compute_total_loss (CL-F:47-58) with its two ingredients kept: they are the log's row
+                cross_entropy_loss = sparse_categorical_crossentropy(y, p)
+                penalty = self.loss_obj._penalty()
+                per_sample = cross_entropy_loss + self.loss_obj.penalty_rate * penalty
+                self._row = self.loss_log.append(cross_entropy_loss.detach().mean(), penalty.detach())
+            else:
+                per_sample = self.loss_obj.compute_total_loss(y, p)
         else:
             per_sample = sparse_categorical_crossentropy(y, p)
-        return self._with_regularizers(per_sample.mean())
+        total = per_sample.mean()
+        if self.loss_values and self.batch is not None:
+            self._scce = total.detach()
+        total = self._with_regularizers(total)
+        if self.loss_values and self.batch is not None:
+            self._task = total.detach()
+        elif self.loss_values:
+            self.loss_terms.copy_(self._row)
+            self.loss_terms[0].copy_(total.detach())      # the differentiated scalar: regularisers included
+        return total
 
     def _with_regularizers(self, total):
         """Keras adds the regulariser losses to the objective (custom_layers.py:327).  Exact mode B: their VALUE is added here,
@@ -169,7 +202,27 @@ class Trainer:
         # batched custom-loss-terms mode: the task loss went through autograd, the penalty gradients are injected
         # by the batch kernels (identical on every rank, so adding them before the all-reduce changes nothing);
         # "nqcl": the penalty's ds is ADDED to the nested-quantization ds the batch has just written
-        self.batch.inject_penalty_grads(self.loss_kind, self.penalty_rate, accumulate_ds=(self.mode == "nqcl"))
+        penalty = self.batch.inject_penalty_grads(self.loss_kind, self.penalty_rate, accumulate_ds=(self.mode == "nqcl"),
+                                                  values=self.loss_values)
+        if self.loss_values:
+            # the log's row is the reference's three numbers (CL-F:58-71); Keras adds the regularisers outside
+            # compute_total_loss: they are in the returned total, not in the log
+            self.loss_terms.copy_(self.loss_log.append(self._scce, penalty))
+            if self.regularized:
+                self.loss_terms[0].copy_(self._task + self.loss_terms[2])
+
+    def _returned_loss(self, loss):
+        """What ``step()`` hands back: the differentiated scalar, or -- batched with ``loss_values`` -- the total read from
+        ``loss_terms`` (the penalty never went through autograd there)."""
+        if self.loss_values and self.batch is not None:
+            return self.loss_terms[0]
+        return loss
+
+    def flush_loss_log(self):
+        """Writes the rows collected since the last flush to ``custom_losses/*.log``; ``(rows_written, rows_dropped)``."""
+        if self.loss_log is None:
+            raise RuntimeError("flush_loss_log() needs Trainer(loss_values=True)")
+        return self.loss_log.flush()
 
     def _update_phase(self):
         if self.dp is not None:
@@ -187,11 +240,13 @@ class Trainer:
         self.scale_opt.step()
 
     def step(self, x, y):
+        """One training step; returns the loss as a 0-dim device tensor.  With ``loss_values=True`` and ``batched=True`` that is
+        ``loss_terms[0]``, a view of one persistent buffer that the next step overwrites (``clone()`` to keep it)."""
         loss = self._backward_phase(x, y)
         if self.dp is not None:
             self.dp.exchange()
         self._update_phase()
-        return loss
+        return self._returned_loss(loss)
 
     def _capture(self, fn):
         g = torch.cuda.CUDAGraph()
@@ -218,7 +273,7 @@ class Trainer:
             phase[0] = "update"
             self._update_phase()
             phase[0] = "end"                 # what is raised from here on comes from closing the capture
-            return loss
+            return self._returned_loss(loss)
 
         def attempt():
             try:
@@ -274,6 +329,7 @@ class Trainer:
                 self.graph, self._loss = self._capture(lambda: self._backward_phase(self._x, self._y))
                 self.dp.exchange()
                 self.graph_update, _ = self._capture(self._update_phase)
+                self._loss = self._returned_loss(self._loss)      # mode B evaluates the penalty in the update phase
         self._x.copy_(x)
         self._y.copy_(y)
         if self.dp is not None:
@@ -285,10 +341,18 @@ class Trainer:
         return self._loss
 
     @torch.no_grad()
-    def evaluate(self, x, y):
+    def evaluate(self, x, y, with_penalty: bool = False):
+        """``with_penalty``: add ``rate * penalty`` to the validation loss, as Keras' ``val_loss`` of a model compiled with
+        ``loss=obj.compute_total_loss`` does (CL-F:47-58)."""
         self.model.eval()
         p = self.model(x)
-        return float(sparse_categorical_crossentropy(y, p).mean()), float((p.argmax(1) == y).float().mean())
+        loss = sparse_categorical_crossentropy(y, p).mean()
+        if with_penalty:
+            if self.loss_obj is None:
+                raise ValueError("evaluate(with_penalty=True) needs a loss term (mode 'cl' or 'nqcl')")
+            penalty = self.batch.penalty_values(self.loss_kind)[1] if self.batch is not None else self.loss_obj._penalty()
+            loss = loss + self.penalty_rate * penalty
+        return float(loss), float((p.argmax(1) == y).float().mean())
 
 
 def main(argv=None):
@@ -317,6 +381,9 @@ def main(argv=None):
     ap.add_argument("--backend", default="nccl", help="nccl = RCCL over xGMI (default); gloo + --share-gpu rehearses N>1 on one GPU")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal only: every rank uses cuda:0 (needs --backend gloo)")
     ap.add_argument("--batched", action="store_true", help="multi-tensor launches for all fake-quant ops of a step (lq_batch_*)")
+    ap.add_argument("--loss-values", action="store_true",
+                    help="modes cl / nqcl: evaluate the penalty with its gradients, report mean(SCCE) + rate * penalty and keep the "
+                         "reference's per-step loss logs in a device buffer (written at the end)")
     ap.add_argument("--kernel-storage", choices=["oihw", "hwio"], default="oihw",
                     help="memory order of the conv kernels behind their HWIO shape (layers.py)")
     ap.add_argument("--channels-last", action="store_true",
@@ -354,7 +421,8 @@ def main(argv=None):
         value = (args.value_coarse, args.value)
     tr = Trainer(args.config, args.mode, value, args.orientation, args.loss, seed=args.seed, device=dev,
                  ddp_mode=args.ddp_mode, graph=args.graph, batched=args.batched, bucket_mb=args.bucket_mb,
-                 graph_collectives=args.graph_collectives, force_collectives=args.force_dist, kernel_storage=args.kernel_storage)
+                 graph_collectives=args.graph_collectives, force_collectives=args.force_dist, kernel_storage=args.kernel_storage,
+                 loss_values=args.loss_values, loss_log_capacity=max(4096, args.steps + args.warmup + 8))
     do_step = tr.step_graphed if args.graph else tr.step
     g = torch.Generator(device=dev).manual_seed(args.seed + rank)
     batches = [synthetic_batch(args.config, args.batch, dev, g) for _ in range(4)]
@@ -376,6 +444,7 @@ def main(argv=None):
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t)
+    log_rows = tr.flush_loss_log() if args.loss_values and rank == 0 else None     # every rank holds the same rows: one writes
     if rank == 0:
         n_q = sum(p.numel() for l in tr.custom_layers for p in l._regularized())
         print(json.dumps({
@@ -386,7 +455,8 @@ def main(argv=None):
             "hipgraph": bool(args.graph), "graph_collectives": bool(tr.graph_collectives and args.graph and use_dist),
             **({"graph_note": tr.graph_note} if tr.graph_note else {}), "batched": bool(args.batched),
             "backend": (args.backend if use_dist else None),
-            "channels_last": bool(args.channels_last), "kernel_storage": args.kernel_storage}))
+            "channels_last": bool(args.channels_last), "kernel_storage": args.kernel_storage,
+            **({"loss_values": True, "loss_log_rows": log_rows[0], "loss_log_dropped": log_rows[1]} if log_rows else {})}))
         if args.export_dir:
             from .export import save_compress_parameters
             print(json.dumps(save_compress_parameters(tr.model, args.export_dir)))

@@ -16,6 +16,13 @@ constexpr int64_t kPeriodic4Min = 4ll << 20;         // column mode, C <= 64: el
                                                      // (the same 4 M boundary as the 512-thread streaming units: below it single-tensor
                                                      // and batched launches share one geometry and give bit-identical results)
 constexpr int64_t kNtBytes = 64ll << 20;             // tensors at least this large are streamed with nontemporal accesses
+// Infinity Cache reuse between the forward and the scale gradient of one streaming tensor ("Infinity Cache
+// reuse"): K1 loads the LAST kMallKeepBytes of P with the default policy and K2 walks its units backwards, so that it meets those
+// lines first.  A line `d` bytes before the end of P sees about 4 d bytes of other traffic between its two uses (P + out behind it
+// in K1, P + dy ahead of it in K2) and survives while that fits the 256 MiB cache: d <= 64 MiB at best.  Swept on the BENCH
+// tensor (154 MB) in tenths of the tensor: the step is shortest at 0.3 = 46 MB and longer again at 0.4 and 0.5, where K1 pays
+// the default policy for lines that do not last.  Smaller streaming tensors keep all of P that fits.
+constexpr int64_t kMallKeepBytes = 44ll << 20;
 
 // ------------------------------------------------------------------------------------------
 //  Parameters shared by every kernel (passed by value in the kernarg segment).
@@ -62,6 +69,7 @@ __device__ __forceinline__ uint32_t perm_index(const Params& p, int64_t i) {    
 
 struct FlatIdx {          // group of flat element i: (i / inner) % G
     FastDiv inner, G;
+    uint32_t keep_from;   // k_flat_fwd, streaming forward of long aligned rows: first block that loads P with the default cache policy
 };
 
 // Per-group context, loaded once per row / column.

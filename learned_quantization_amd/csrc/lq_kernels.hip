@@ -94,6 +94,23 @@ static int knob_env(const char* name, int dflt) {
 #define LQ_KNOB(var, name, dflt) constexpr int var = (dflt)
 #endif
 
+#ifdef LQ_DEV_KNOBS
+static int g_dev_flags_host = 0;       // the host's copy of lq_dev_set_flags(bits)
+#endif
+// First element of the part of a streaming tensor that K1 loads with the default cache policy and K2 expects in the Infinity
+// Cache (kMallKeepBytes; DESIGN.md section 3 "Infinity Cache reuse").  Development builds: LQ_TUNE_MALL_T or bits 0xf00 of
+// lq_dev_set_flags hold 1 + the fraction of the tensor in tenths (1 = nothing kept), 0 = the shipped rule.
+static int64_t mall_keep_from(int64_t numel) {
+    int64_t keep = kMallKeepBytes / 4;
+    LQ_KNOB(t_env, "LQ_TUNE_MALL_T", 0);
+    int t = t_env;
+#ifdef LQ_DEV_KNOBS
+    if (g_dev_flags_host & 0xf00) t = (g_dev_flags_host >> 8) & 15;
+#endif
+    if (t > 0) keep = (int64_t)((double)numel * (t - 1) / 10.0);
+    return keep >= numel ? 0 : numel - keep;
+}
+
 static bool flat_cols_ok(int64_t C) { return C == 8 || C == 16 || C == 32 || C == 64; }
 static int64_t colx_max_inner() {        // rows shorter than this may run in column mode (see make_plan)
     LQ_KNOB(v, "LQ_TUNE_COLX_INNER", 200);
@@ -348,6 +365,7 @@ static int launch_stream2_impl(Plan& pl, const Params& p, hipStream_t st) {
     FlatIdx fx;              // 32-bit forms only (numel < 2^32); the wide forms divide in 64 bits
     fx.inner = make_fastdiv((uint32_t)(p.inner < 4294967296ll ? p.inner : 1));
     fx.G = make_fastdiv((uint32_t)(p.G < 4294967296ll ? p.G : 1));
+    fx.keep_from = 0xffffffffu;      // no block keeps its lines (set below for the streaming forward of long aligned rows)
     (void)fx;
     if (pl.mode == MODE_ROW_BIG) {
         // long rows off the 16-byte grid: K1 as a line-aligned flat stream (lq_stream2.hpp k_flat_fwd, group mode 6 / 7)
@@ -370,6 +388,7 @@ static int launch_stream2_impl(Plan& pl, const Params& p, hipStream_t st) {
                     // hipExtLaunchKernelGGL: with lq_profile_events() set, the events take the kernel's own begin / end timestamps
 #define LQ_FLATR(NT_, GM_) hipExtLaunchKernelGGL((k_flat_fwd<OP, 512, NT_, GM_>), dim3((unsigned)blocks), dim3(512), 0, st, g_prof_start, g_prof_stop, 0, p, fx, nv, rem)
                     if (pl.L % 4 == 0) {                    // (2^32 elements are 16 GiB: `wide` implies `ntb`)
+                        if (ntb) fx.keep_from = (uint32_t)ceil_div(mall_keep_from(nn), 2048);      // 512 float4 per block
                         if (ntb) { if (wide) LQ_FLATR(1, 2); else LQ_FLATR(1, 0); }
                         else LQ_FLATR(0, 0);
                     } else if (!(off_rb & 512) && (double)pl.L / (double)(pl.nc * pl.CH) >= 0.8) {
@@ -854,10 +873,15 @@ static int launch_traverse(Plan& pl, const Params& p, hipStream_t st) {
         if constexpr (OP == OP_BWD || OP == OP_FUSED) if (u2) {
             const int64_t nc2 = row_chunks(pl.L, (int64_t)pl.bs * 8);
             const dim3 grid2 = grid3d ? dim3((unsigned)nc2, (unsigned)p.G, (unsigned)outer_f) : dim3((unsigned)(pl.R * nc2));
+            // the scale gradient walks these units backwards and expects the end of P in the Infinity Cache (kMallWalk)
+            int64_t keep_from = OP == OP_BWD ? mall_keep_from(pl.R * pl.L) : 0;
+#ifdef LQ_DEV_KNOBS
+            if (g_dev_flags_host & 0x1000) keep_from = -1 - keep_from;      // the forward walk
+#endif
             if (needs_tail((int64_t)pl.bs * 8))
-                hipExtLaunchKernelGGL((k_row_stream<OP, 4, 512, 1, 2, 1>), grid2, dim3(512), 0, st, g_prof_start, g_prof_stop, 0, p, pl.L, nc2, grid3d);
+                hipExtLaunchKernelGGL((k_row_stream<OP, 4, 512, 1, 2, 1>), grid2, dim3(512), 0, st, g_prof_start, g_prof_stop, 0, p, pl.L, nc2, grid3d, keep_from);
             else
-                hipExtLaunchKernelGGL((k_row_stream<OP, 4, 512, 1, 2, 0>), grid2, dim3(512), 0, st, g_prof_start, g_prof_stop, 0, p, pl.L, nc2, grid3d);
+                hipExtLaunchKernelGGL((k_row_stream<OP, 4, 512, 1, 2, 0>), grid2, dim3(512), 0, st, g_prof_start, g_prof_stop, 0, p, pl.L, nc2, grid3d, keep_from);
             // the finalize that follows must walk the partial layout this launch produced
             pl.CH = pl.bs * 8;
             pl.nc = nc2;
@@ -875,8 +899,8 @@ static int launch_traverse(Plan& pl, const Params& p, hipStream_t st) {
 #define LQ_LAUNCH_STREAM(VEC_, BS_, NT_) do { \
         constexpr bool kTail0 = kDevKnobs || (VEC_ == 4 && !(OP == OP_FWD && (BS_ != kBlock || NT_ != 0)) && !(OP == OP_BWD && BS_ == 512 && NT_ == 1)); \
         constexpr bool kTail1 = kDevKnobs || !(OP == OP_BWD && VEC_ == 4 && BS_ == 512 && NT_ == 1); \
-        if (VEC_ == 1 || tail1) { if constexpr (kTail1) hipExtLaunchKernelGGL((k_row_stream<OP, VEC_, BS_, NT_, 1, 1>), grid, dim3(BS_), 0, st, g_prof_start, g_prof_stop, 0, p, pl.L, pl.nc, grid3d); } \
-        else { if constexpr (kTail0) hipExtLaunchKernelGGL((k_row_stream<OP, VEC_, BS_, NT_, 1, 0>), grid, dim3(BS_), 0, st, g_prof_start, g_prof_stop, 0, p, pl.L, pl.nc, grid3d); } } while (0)
+        if (VEC_ == 1 || tail1) { if constexpr (kTail1) hipExtLaunchKernelGGL((k_row_stream<OP, VEC_, BS_, NT_, 1, 1>), grid, dim3(BS_), 0, st, g_prof_start, g_prof_stop, 0, p, pl.L, pl.nc, grid3d, (int64_t)0); } \
+        else { if constexpr (kTail0) hipExtLaunchKernelGGL((k_row_stream<OP, VEC_, BS_, NT_, 1, 0>), grid, dim3(BS_), 0, st, g_prof_start, g_prof_stop, 0, p, pl.L, pl.nc, grid3d, (int64_t)0); } } while (0)
         if constexpr (!kStreamOp<OP>) {
             if (vec) LQ_LAUNCH_STREAM(4, 256, 0);
             else LQ_LAUNCH_STREAM(1, 256, 0);
@@ -1015,6 +1039,7 @@ int lq_dev_set_ablate(int mask) {      // development builds only (see lq_conv_t
 
 #ifdef LQ_DEV_KNOBS
 int lq_dev_set_flags(int bits) {       // development builds only (see lq_stream2.hpp)
+    g_dev_flags_host = bits;
     return hipMemcpyToSymbol(HIP_SYMBOL(lq::g_dev_flags), &bits, sizeof(int)) == hipSuccess ? LQ_OK : LQ_EHIP;
 }
 #endif

@@ -50,6 +50,8 @@ namespace lq {
 //            unless it straddles a row end -- checked from the groups of its first and last element (32-bit / 64-bit)
 #ifdef LQ_DEV_KNOBS
 // development builds: lq_dev_set_flags(bits) -- 1: k_row_win stores with the default cache policy (loads stay nontemporal)
+//   0x70: cache policy of the `out` stores of the streaming forward (store4_policy: 0 as shipped, 1 default, 2 sc1 nt, 3 sc0 sc1 nt, 4 sc1, 5 sc0 sc1, 6 nt)
+//   0xf00 and 0x1000 are read on the host (lq_kernels.hip: mall_keep_from, launch_traverse)
 __device__ int g_dev_flags = 0;
 #endif
 
@@ -67,9 +69,15 @@ template <int OP, int BS, int NT, int GM>
 __global__ __launch_bounds__(BS) void k_flat_fwd(Params p, FlatIdx fx, int64_t nv, int rem) {
     using O = OpT<OP>;
     const int64_t v = (int64_t)blockIdx.x * BS + threadIdx.x;
+    // The streaming forward of long aligned rows keeps the END of P in the Infinity Cache for the scale gradient that follows
+    // (kMallKeepBytes): blocks from fx.keep_from on load P with the default policy, every other one stays nontemporal.  The
+    // choice is block-uniform.
+    constexpr bool kKeep = NT == 1 && (GM == 0 || GM == 2);
     if (v < nv) {
         const int64_t i = v * 4;
-        const float4 x = load4<NT>(p.P + i);
+        float4 x;
+        if (kKeep && blockIdx.x >= fx.keep_from) x = load4_keep(p.P + i);
+        else x = load4<NT>(p.P + i);
         __builtin_amdgcn_sched_barrier(0);      // the load first; index arithmetic and contexts while it is in flight
         Acc none = O::template init<Acc>();
         float4 o;
@@ -182,7 +190,12 @@ __global__ __launch_bounds__(BS) void k_flat_fwd(Params p, FlatIdx fx, int64_t n
             }
             o = O::elem4c(p, ctx, i, x, x, acc);
         }
-        if (O::kStore) store4<NT>(p.out + i, o);
+#ifdef LQ_DEV_KNOBS
+        if (O::kStore && kKeep && (g_dev_flags & 0x70)) store4_policy((g_dev_flags >> 4) & 7, p.out + i, o);
+        else
+#endif
+        if (O::kStore && kKeep) store4_sc1nt(p.out + i, o);
+        else if (O::kStore) store4<NT>(p.out + i, o);
     } else if (v == nv && rem) {                // numel % 4 trailing elements
         Acc none = O::template init<Acc>();
         for (int k = 0; k < rem; ++k) {

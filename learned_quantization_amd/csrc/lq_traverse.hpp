@@ -35,9 +35,41 @@ __device__ __forceinline__ void store4(float* p, const float4& v) {
     }
 }
 
+// `out` of the streaming forward (k_flat_fwd): a nontemporal store at agent scope, `sc1 nt`.  No builtin gives these bits, hence
+// the inline-asm vector store; it is the last access of its thread.  Measured against plain `nt` in the K1, K2, K3 step at six
+// fractions of kept P: 0.5-0.8 us per step less at every one of them (profiles/mall_reuse/sweep.jsonl).
+__device__ __forceinline__ void store4_sc1nt(float* p, const float4& v) {
+    const v4f t = {v.x, v.y, v.z, v.w};
+    asm volatile("global_store_dwordx4 %0, %1, off sc1 nt" : : "v"(p), "v"(t) : "memory");
+}
+#ifdef LQ_DEV_KNOBS
+// development builds: float4 store with an explicit gfx950 cache policy (the store-policy sweep of tools/sweep_mall.py)
+__device__ __forceinline__ void store4_policy(int pol, float* p, const float4& v) {
+    const v4f t = {v.x, v.y, v.z, v.w};
+    if (pol == 1) asm volatile("global_store_dwordx4 %0, %1, off" : : "v"(p), "v"(t) : "memory");
+    else if (pol == 2) asm volatile("global_store_dwordx4 %0, %1, off sc1 nt" : : "v"(p), "v"(t) : "memory");
+    else if (pol == 3) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1 nt" : : "v"(p), "v"(t) : "memory");
+    else if (pol == 4) asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(p), "v"(t) : "memory");
+    else if (pol == 5) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" : : "v"(p), "v"(t) : "memory");
+    else __builtin_nontemporal_store(t, reinterpret_cast<v4f*>(p));      // 6: nt, the compiler's nontemporal store
+}
+#endif
+
 // float4 access at an address that is only 4-byte aligned (one global_load_dwordx4 / global_store_dwordx4: global memory
 // needs dword alignment only; a wave's 1 KB access then touches 9 lines instead of 8)
 typedef float v4f_u __attribute__((ext_vector_type(4), aligned(4)));
+// Default-policy float4 load of a line that is to stay in (or is expected in) the Infinity Cache.  It stands in one arm of a
+// block-uniform branch whose other arm is the nontemporal load of the same address.  Two loads that differ in nothing but the
+// hint are merged into one -- hoisted above the branch or sunk below it -- that keeps only what both have in common (seen:
+// every P load of K2 lost its `nt`).  The two empty asm statements make this arm begin and end with something the other arm
+// does not have, and the 4-byte alignment of the type (still one global_load_dwordx4, see load4x) tells the loads apart.
+__device__ __forceinline__ float4 load4_keep(const float* p) {
+    asm volatile("; default-policy load" : : : );
+    const v4f_u v = *reinterpret_cast<const v4f_u*>(p);
+    asm volatile("; end" : : : );
+    return make_float4(v.x, v.y, v.z, v.w);
+}
+
 template <int NT, int UA>
 __device__ __forceinline__ float4 load4x(const float* p) {
     if (!UA) return load4<NT>(p);
@@ -58,11 +90,19 @@ __device__ __forceinline__ void store4x(float* p, const float4& v) {
 // TAIL = 1: rows whose last chunk carries a folded tail, or whose chunks do not start on a 16-byte line (scalar head / tail
 // elements).  Rows without either (the BENCH shape, rows of 2^k elements, ...) run the TAIL = 0 instantiation, which keeps the
 // registers of the round-1 kernel (the hoisted tail loads cost 7-14 VGPRs).
+// The streaming scale gradient (OP_BWD, two nontemporal float4 per thread) walks its units from the END of the tensor and loads
+// the P of units at or behind element `keep_from` with the default policy: the forward left those lines in the Infinity Cache
+// (kMallKeepBytes).  dy and every other P load stay nontemporal.  The partial of a unit keeps its place (row * nc + ck).
+template <int OP, int VEC, int NT, int U>
+constexpr bool kMallWalk = OP == OP_BWD && VEC == 4 && NT == 1 && U == 2;
+
 template <int OP, int VEC, int BS, int NT, int U = 1, int TAIL = 1>
-__device__ __forceinline__ void row_stream_body(const Params& p, int64_t L, int64_t nc, int64_t row, int64_t ck, int64_t g) {
+__device__ __forceinline__ void row_stream_body(const Params& p, int64_t L, int64_t nc, int64_t row, int64_t ck, int64_t g,
+                                                int64_t keep_from = 0) {
     using O = OpT<OP>;
     constexpr int CH = BS * 4 * U;
     const int64_t base = row * L + ck * (int64_t)CH;
+    [[maybe_unused]] const bool keep = kMallWalk<OP, VEC, NT, U> && base >= keep_from;      // block-uniform
     const int64_t rem = L - ck * (int64_t)CH;
     // The last chunk of a row takes everything that remains: at most CH, or up to CH + CH/8 when the host folded a short
     // tail into it (row_chunks(): a row of 4100 elements is 2 chunks of 2048 + 2052, not 3 with an almost empty block).
@@ -93,7 +133,8 @@ __device__ __forceinline__ void row_stream_body(const Params& p, int64_t L, int6
             const int j = u * BS + (int)threadIdx.x;
             i[u] = vbase + (int64_t)(j < len4 ? j : 0) * 4;
             const int64_t il = len4 > 0 ? i[u] : vbase - 4;
-            x[u] = load4<NT>(p.P + il);
+            if (kMallWalk<OP, VEC, NT, U> && keep) x[u] = load4_keep(p.P + il);
+            else x[u] = load4<NT>(p.P + il);
             d[u] = x[u];
             if (O::kDy) d[u] = load4<NT>(p.dy + il);
         }
@@ -197,19 +238,27 @@ __device__ __forceinline__ void row_stream_body(const Params& p, int64_t L, int6
 }
 
 template <int OP, int VEC, int BS, int NT, int U = 1, int TAIL = 1>
-__global__ __launch_bounds__(BS, (BS == 1024 ? 8 : 0)) void k_row_stream(Params p, int64_t L, int64_t nc, int grid3d) {
+__global__ __launch_bounds__(BS, (BS == 1024 ? 8 : 0)) void k_row_stream(Params p, int64_t L, int64_t nc, int grid3d, int64_t keep_from) {
+    // kMallWalk: from the end -- the block dispatched first (index 0 in every dimension) takes the last chunk of the last row
+    constexpr bool kRev = kMallWalk<OP, VEC, NT, U>;
+#ifdef LQ_DEV_KNOBS
+    const bool rev = kRev && keep_from >= 0;          // development knob 0x1000: the forward walk (keep_from = -1 - value)
+    if (kRev && !rev) keep_from = -1 - keep_from;
+#else
+    constexpr bool rev = kRev;
+#endif
     int64_t row, ck, g;
     if (grid3d) {
-        ck = blockIdx.x;
-        g = blockIdx.y;
-        row = (int64_t)blockIdx.z * p.G + g;
+        ck = rev ? gridDim.x - 1 - blockIdx.x : blockIdx.x;
+        g = rev ? gridDim.y - 1 - blockIdx.y : blockIdx.y;
+        row = (int64_t)(rev ? gridDim.z - 1 - blockIdx.z : blockIdx.z) * p.G + g;
     } else {
-        const int64_t unit = blockIdx.x;
+        const int64_t unit = rev ? gridDim.x - 1 - blockIdx.x : blockIdx.x;
         row = unit / nc;
         ck = unit - row * nc;
         g = row % p.G;
     }
-    row_stream_body<OP, VEC, BS, NT, U, TAIL>(p, L, nc, row, ck, g);
+    row_stream_body<OP, VEC, BS, NT, U, TAIL>(p, L, nc, row, ck, g, keep_from);
 }
 
 // ------------------------------------------------------------------------------------------

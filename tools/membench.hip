@@ -2,8 +2,10 @@
 // read streams and read+write streams sustain on this MI355X with the traversal geometries the
 // library uses?  Build: hipcc -O3 --offload-arch=gfx950 -o membench tools/membench.hip
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 #include <vector>
 
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); exit(1);} } while (0)
@@ -169,10 +171,35 @@ LQ_POL_KERNEL(k_pol_sc0sc1, "sc0 sc1", "sc0 sc1")
 LQ_POL_KERNEL(k_pol_ldnt_stsc, "nt", "sc0 sc1 nt")
 LQ_POL_KERNEL(k_pol_ldsc_stnt, "sc0 sc1 nt", "nt")
 
+// Survival probe: a store-only stream with an explicit policy (vector stores), and the same behind a nontemporal read (K1's mix).
+#define LQ_ST_KERNEL(NAME, STPOL)                                                                                      \
+    __global__ __launch_bounds__(512) void NAME(const float* A, float* C, int rd) {                                   \
+        const int64_t j = (int64_t)blockIdx.x * 512 + threadIdx.x;                                                     \
+        float4* pc = (float4*)C + j;                                                                                   \
+        v4f a = {1.f, 2.f, 3.f, 4.f};                                                                                  \
+        if (rd) a = __builtin_nontemporal_load((const v4f*)A + j);                                                     \
+        asm volatile("global_store_dwordx4 %0, %1, off " STPOL : : "v"(pc), "v"(a) : "memory");                        \
+    }
+LQ_ST_KERNEL(k_st_plain, "")
+LQ_ST_KERNEL(k_st_nt, "nt")
+LQ_ST_KERNEL(k_st_sc1nt, "sc1 nt")
+LQ_ST_KERNEL(k_st_sc0sc1nt, "sc0 sc1 nt")
+LQ_ST_KERNEL(k_st_sc1, "sc1")
+LQ_ST_KERNEL(k_st_sc0sc1, "sc0 sc1")
+
+// the re-read of the probe: the table with the default policy NEXT TO a cold nontemporal stream of the same size, as K2 reads
+// P next to dy -- alone, a 62 MB read runs at the same 5.2 TB/s from the cache and from HBM and tells nothing
+__global__ __launch_bounds__(512) void k_table2(const float* A, const float* B, float* sink) {
+    const int64_t j = (int64_t)blockIdx.x * 512 + threadIdx.x;
+    const float4 a = *((const float4*)A + j);
+    const v4f b = __builtin_nontemporal_load((const v4f*)B + j);
+    if (a.x + a.y + a.z + a.w + b.x + b.y + b.z + b.w == 123.456f) sink[0] = a.x;
+}
+
 int main(int argc, char** argv) {
     const int64_t N = 256ll * 3 * 224 * 224;
     const int SETS = 4;
-    const size_t pad = argc > 1 ? (size_t)atol(argv[1]) : 0;   // extra bytes between buffers (de-alias test)
+    const size_t pad = argc > 1 && strcmp(argv[1], "survive") ? (size_t)atol(argv[1]) : 0;   // extra bytes between buffers (de-alias test)
     std::vector<float*> A(SETS), B(SETS), C(SETS);
     char* pool;
     size_t each = N * 4 + pad;
@@ -194,6 +221,44 @@ int main(int argc, char** argv) {
         CK(hipGetLastError()); report(name, bytes, ms);
     };
     const double b2 = N * 8.0, b3 = N * 12.0;
+    // "survive" rows (`membench survive` prints only these): a 62 MB table (the first 0.4 of A[0]) is read with the default
+    // policy, then 154 MB are stored to C[1] under one store policy, then the table is read again next to a cold 62 MB stream
+    // (k_table2) and THAT kernel is timed.  "hot" re-reads it at once, "cold" after 616 MB of nontemporal read + write on other
+    // buffers.  The second group reads A[1] (nontemporal) in the storing kernel as well, which is K1's mix.
+    {
+        const int nbt = (int)(N * 2 / 5 / 4 / 512), nb = (int)(N / 4 / 512);
+        const double tb = (double)nbt * 512 * 16;
+        auto table = [&] { hipLaunchKernelGGL((k_one<0, 512, 0>), dim3(nbt), dim3(512), 0, 0, A[0], B[0], C[0], sink); };
+        int slice = 0;      // the cold stream walks six 62 MB slices of B[0], B[2], B[3]: far more than the cache between two uses of one
+        auto survive = [&](const char* name, auto between) {
+            float tot = 0.f;
+            const int reps = 20;
+            for (int it = 0; it < reps + 2; ++it) {
+                table();
+                between();
+                const int bi[3] = {0, 2, 3};
+                const float* cold = B[bi[slice / 2 % 3]] + (size_t)(slice % 2) * nbt * 2048;
+                slice = (slice + 1) % 6;
+                hipExtLaunchKernelGGL(k_table2, dim3(nbt), dim3(512), 0, 0, e0, e1, 0, A[0], cold, sink);      // the kernel's own duration
+                CK(hipEventSynchronize(e1)); float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+                if (it >= 2) tot += ms;
+            }
+            CK(hipGetLastError());
+            printf("%-52s %8.1f us  %7.0f GB/s\n", name, tot * 1000.0 / reps, 2 * tb * reps / (tot * 1e-3) / 1e9);
+        };
+        for (int rep = 0; rep < 2; ++rep) {
+            survive("survive 62MB table: hot", [&] {});
+            survive("survive 62MB table: cold (616MB between)", [&] {
+                hipLaunchKernelGGL((k_one<2, 512, 1>), dim3(nb), dim3(512), 0, 0, A[2], B[2], C[2], sink);
+                hipLaunchKernelGGL((k_one<2, 512, 1>), dim3(nb), dim3(512), 0, 0, A[3], B[3], C[3], sink); });
+#define SURV(K, label) \
+            survive("survive 62MB table: 154MB stores " label, [&] { hipLaunchKernelGGL(K, dim3(nb), dim3(512), 0, 0, A[1], C[1], 0); }); \
+            survive("survive 62MB table: nt read + stores " label, [&] { hipLaunchKernelGGL(K, dim3(nb), dim3(512), 0, 0, A[1], C[1], 1); });
+            SURV(k_st_plain, "(none)") SURV(k_st_nt, "nt") SURV(k_st_sc1nt, "sc1 nt") SURV(k_st_sc0sc1nt, "sc0 sc1 nt")
+            SURV(k_st_sc1, "sc1") SURV(k_st_sc0sc1, "sc0 sc1")
+        }
+        if (argc > 1 && !strcmp(argv[1], "survive")) return 0;
+    }
 #define TB(label, MODE, bytes, BS) { char nm[96]; const int nb = (int)(N / 4 / BS); \
         snprintf(nm, 96, "one BS%d %s", BS, label); \
         run(nm, bytes, [&](int k){ hipLaunchKernelGGL((k_one<MODE, BS, 0>), dim3(nb), dim3(BS), 0, 0, A[k], B[k], C[k], sink); }); \

@@ -83,6 +83,25 @@ int lq_fq_scale_grad(const float* P, const float* s, const float* dy, float lamb
                      float* ds, float* parts, void* ws, size_t ws_bytes,
                      int64_t outer, int64_t G, int64_t inner, void* stream);
 
+/* ---- straight-through scale gradient (the step-size gradient of LSQ and relatives, for this floor quantizer) ----
+ * Fills the slot the reference leaves open: CIFAR-10/paper_implementation returns zeros for the scale (a TODO).  Under
+ * the straight-through convention that already gives dP = dy (floor' == 1), d out / d s = floor(P/s) - P/s, in [-1, 0]:
+ *   t_i = P_i / s[g]       IEEE fp32 division: K1's quotient, bit for bit
+ *   q_i = floorf(t_i)
+ *   r_i = q_i - t_i        ONE fp32 subtraction (not always exact: t = -2^-40 gives r = -1)
+ *   ds[g] = RN_f32( (double)grad_scale * sum_{i in g} (double)dy_i * (double)r_i )
+ * dP is `dy` itself (STE) and is therefore not an output.  The fp32 quotient is part of the definition (what a TensorFlow
+ * fp32 graph computes; an f64 quotient moves the sum by ~3e-4 of sum |terms| at the initial scale, |q| ~ 1e4).  The sum is f64
+ * from the first addition, two-stage and ordered (no float atomics): run-to-run bit-stable.  NaN / Inf as fp32 arithmetic gives
+ * them: a NaN or +-Inf quotient makes that group's ds NaN, other groups are unaffected; |t| >= 2^23 contributes exactly 0.
+ * NO bit-identity across traversals: unlike the NQ vote at lambda < 4e-4 the terms have no common quantum, so the single-tensor
+ * call, the batch and different descriptors of the same data may differ in the last bits of the f64 sum (~2^-50 relative, visible
+ * in fp32 only on a rounding boundary); each is within ~2^-23 * sum |dy_i r_i| of the exact value.
+ * Runs the generic traversal bodies at every size (tensors from 4 M elements: correct, slower than K2's streaming forms).  */
+int lq_fq_scale_grad_ste(const float* P, const float* s, const float* dy, float grad_scale,
+                         float* ds, void* ws, size_t ws_bytes,
+                         int64_t outer, int64_t G, int64_t inner, void* stream);
+
 /* ---- K4: forward and NQ backward of one tensor in a single pass (benchmark path) ---
  * Same results as lq_fq_forward followed by lq_fq_scale_grad (out, max|q| and the vote count bit for bit; on
  * streaming-size tensors the vote sum may differ by fp32 summation order, ~1e-7 relative); P is read once.  */
@@ -220,6 +239,14 @@ typedef enum lq_penalty_kind { LQ_PENALTY_MAXBIN = 0, LQ_PENALTY_DIFFERENCE = 1,
 #define LQ_PENALTY_ACCUMULATE_DS 0x100
 int lq_batch_penalty_grads(const lq_batch* batch, int kind, const float* coeff, float* const* grad,
                            void* ws, size_t ws_bytes, void* stream);
+
+/* lq_fq_scale_grad_ste of every tensor of the batch that has a ds buffer, whatever its lambda (NaN included), in TWO launches
+ * (traversal + finalize).  dy: optional host array [n] of device pointers, indexed like the descriptors, in the memory order of
+ * P; overrides the descriptors' dy.  grad_scale: host float[n], or NULL = 1 for every tensor.  Same definition and the same
+ * "no bit-identity across traversals" note as the single-tensor call.  ws as for lq_batch_penalty_grads; only enqueues.
+ * To add a loss term's scale gradient, call lq_batch_penalty_grads[_values] with LQ_PENALTY_ACCUMULATE_DS afterwards.     */
+int lq_batch_scale_grad_ste(const lq_batch* batch, const float* const* dy, const float* grad_scale,
+                            void* ws, size_t ws_bytes, void* stream);
 
 /* VALUE of the custom-loss-term penalty for the whole batch (compute_{maxbin,difference,inverse}_penalty,
  *   custom_loss_functions.py:75-116, 161-195, 240-275), the number compute_total_loss adds to the cross-entropy (:47-58).

@@ -8,7 +8,9 @@ backward for the MNIST / CIFAR-10 / Imagenette models.  None of them depends on 
     layer its quantised tensors;
   * its autograd node receives ALL upstream gradients at the end of the backward pass and computes every scale
     gradient in two launches (traversal + finalize), writing ``scale.grad`` directly (no per-scale
-    accumulate kernels) and passing ``dy`` through unchanged as ``∂P`` (STE, custom_layers.py:118);
+    accumulate kernels) and passing ``dy`` through unchanged as ``∂P`` (STE, custom_layers.py:118) -- the
+    nested-quantization vote (``lq_batch_scale_grad``), or, for a model whose layers all have ``scale_gradient="ste"``,
+    the straight-through scale gradient (``lq_batch_scale_grad_ste``); one batch holds one rule;
   * ``BatchedScaleAdam.step()`` updates every scale (Adam + MinValueConstraint, custom_layers.py:158) in one launch.
 
 Semantics per tensor are those of the single-tensor ops (same device code; results bit-identical).
@@ -53,6 +55,12 @@ class FakeQuantBatch:
         self._fused_opt = None               # BatchedScaleAdam(fused=True): the scale-gradient finalize applies the Adam step itself
         self.defer_scale_grads = False       # exact data-parallel mode: backward skips ds, scale_grads_from_param_grads() follows
         self.entries: List[_Entry] = []
+        nested_layers = [getattr(layer, a) for layer in layers for a in ("nested_q_w_layer", "nested_q_k_layer", "nested_q_b_layer")
+                         if hasattr(layer, a)]
+        rules = {n.scale_gradient for n in nested_layers}
+        if "ste" in rules and len(rules) > 1:
+            raise ValueError('one FakeQuantBatch holds one scale-gradient rule: every layer needs scale_gradient="ste", or none')
+        self.ste = "ste" in rules            # every scale gradient of the batch is the straight-through one
         for layer in layers:
             if isinstance(layer, _ConvBase):
                 pairs = [(0, layer.kernel, layer.nested_q_k_layer)]
@@ -76,7 +84,10 @@ class FakeQuantBatch:
                 e.shape = tuple(param.shape)
                 e.pstride = tuple(param.data.stride())
                 e.pdev = param.device
-                e.nq = nested.penalty_threshold is not None
+                e.nq = nested.penalty_threshold is not None or self.ste      # the op itself gives this scale a gradient
+                if self.ste and isinstance(layer, _ConvBase) and layer.kernel_storage == "hwio":
+                    raise ValueError('a batched scale_gradient="ste" model takes conv kernels in the memory order the convolution '
+                                     'consumes: build it with kernel_storage="oihw"')
                 # write straight into an existing gradient buffer (e.g. a DataParallel bucket view) when there is one
                 g = nested.scale.grad
                 if g is not None and g.is_contiguous():
@@ -118,6 +129,7 @@ class FakeQuantBatch:
         _hip.check(lib.lq_batch_create(arr, n, ctypes.byref(handle)), "lq_batch_create")
         self._handle = handle
         self._ptrs = (ctypes.c_void_p * n)()
+        self._grad_scales = (ctypes.c_float * n)(*[e.nested.grad_scale_value(e.param.numel()) for e in self.entries]) if self.ste else None
         self.ws = torch.empty(lib.lq_batch_workspace_bytes(handle), dtype=torch.uint8, device=self.device)
         self.hyper = dict(lr=lr, betas=betas, eps=eps, mode=mode)
         self._data_ptrs = [(e.param.data_ptr(), e.nested.scale.data_ptr()) for e in self.entries]
@@ -252,6 +264,10 @@ class FakeQuantBatch:
         lib = _hip.load()
         opt = self._fused_opt
         sp = _hip.stream_ptr(self.device)
+        if self.ste:
+            _hip.check(lib.lq_batch_scale_grad_ste(self._handle, self._ptrs, self._grad_scales, _hip.ptr(self.ws), self.ws.numel(), sp),
+                       "lq_batch_scale_grad_ste")
+            return
         if opt is None:
             fn = lib.lq_batch_scale_grad_oihw if oihw else lib.lq_batch_scale_grad
             _hip.check(fn(self._handle, self._ptrs, _hip.ptr(self.ws), self.ws.numel(), sp), "lq_batch_scale_grad")
@@ -350,6 +366,9 @@ class FakeQuantBatch:
         data-parallel all-reduce ``P.grad`` is the global-batch dy (dP == dy, custom_layers.py:118), so this yields the
         single-device large-batch scale gradient, identical on every rank."""
         lib = _hip.load()
+        if self.ste:
+            raise RuntimeError("scale_grads_from_param_grads() is the exact mode of the nested-quantization vote; the straight-through "
+                               "scale gradient is linear in dy: average ds over the ranks (data-parallel mode A)")
         keep = []
         for i, e in enumerate(self.entries):
             g = e.param.grad
@@ -478,6 +497,9 @@ class BatchedScaleAdam:
         self.capturable = capturable
         self._applied = False
         if fused:
+            if batch.ste:
+                raise ValueError("the fused finalize + Adam launch exists for the nested-quantization vote only: "
+                                 'build BatchedScaleAdam(fused=False) for a scale_gradient="ste" model')
             if any(e.nested.penalty_threshold is None for e in batch.entries):
                 raise ValueError("a fused scale update needs nested-quantization layers throughout (every scale gets its gradient "
                                  "from the batch's own scale-gradient pass)")

@@ -172,10 +172,12 @@ __global__ __launch_bounds__(kBlock) void k_batch_traverse(const Task* __restric
 // SECOND: the slice of an op's second accumulator (write_partial_second), 4 * np_pad words behind the first
 template <int OP, int BS, bool SECOND>
 __device__ __forceinline__ void batch_finalize_body(const Task* __restrict__ tasks, const uint32_t* __restrict__ gprefix, int ntasks,
-                                                    uint32_t* ws, int accum, uint32_t gb) {      // gb: group of the batch
+                                                    uint32_t* ws, int accum, uint32_t gb,      // gb: group of the batch
+                                                    const CoefPack* cf = nullptr) {            // cf: per-task Params::c_scale
     const int ti = find_task(gprefix, ntasks, gb);
     const Task& t = tasks[ti];
     Params p = t.p;
+    if (cf) p.c_scale = cf->c[ti];
     p.pa = ws + t.ws_off + (SECOND ? 4 * t.np_pad : 0);
     p.pb = p.pa + t.np_pad;
     p.pc = reinterpret_cast<double*>(p.pb + t.np_pad);
@@ -197,6 +199,11 @@ template <int OP, int BS = 64>     // BS = 256 when some group of the batch has 
 __global__ __launch_bounds__(BS) void k_batch_finalize(const Task* __restrict__ tasks, const uint32_t* __restrict__ gprefix, int ntasks,
                                                        uint32_t* ws, int accum = 0) {
     batch_finalize_body<OP, BS, false>(tasks, gprefix, ntasks, ws, accum, blockIdx.x);
+}
+// Finalize of k_batch_traverse<OP_STE_SCALE>: ds[g] = (float)(k * sum) with the tensor's own factor k = cf.c[task]
+__global__ __launch_bounds__(64) void k_batch_finalize_ste(const Task* __restrict__ tasks, const uint32_t* __restrict__ gprefix, int ntasks,
+                                                           uint32_t* ws, CoefPack cf) {
+    batch_finalize_body<OP_STE_SCALE, 64, false>(tasks, gprefix, ntasks, ws, 0, blockIdx.x, &cf);
 }
 // Finalize of k_batch_traverse<OP_DIFF_BWD_V> in ONE launch of 2 * groups one-wave blocks: the first `groups` blocks are
 // k_batch_finalize<OP_DIFF_BWD> (ds, the same body: the same bits), the others finalize the sums |P - P/s| of the second slice like

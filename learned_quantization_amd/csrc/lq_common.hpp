@@ -115,6 +115,7 @@ enum OpKind {
     OP_FWD_PERM = 8,   // K1 that can also emit the OIHW companion of an HWIO conv kernel
     OP_BWD_PERM = 9,   // K2 that can take dy in OIHW order and write dP in HWIO order
     OP_DIFF_BWD_V = 10, // K5b backward that also carries sum |P - P/s| (the term's VALUE) in a second accumulator
+    OP_STE_SCALE = 11,  // straight-through scale gradient: ds[g] = k * sum dy * (floor(P/s) - P/s)
 };
 
 }  // namespace lq

@@ -3,7 +3,7 @@
 //
 //   lq_common.hpp       constants, kernel parameter block, accumulator types
 //   lq_math.hpp         exact fp32 arithmetic: uniform-divisor division, in-window ratio division, |tanh|, vote
-//   lq_ops.hpp          per-operation traits (K1 fwd, K2 bwd, K4 fused, K5 penalties, integer view)
+//   lq_ops.hpp          per-operation traits (K1 fwd, K2 bwd, K4 fused, K5 penalties, integer view, STE scale gradient)
 //   lq_reduce.hpp       wave/block reductions (DPP for the standard accumulator, shuffles for custom merges)
 //   lq_traverse.hpp     traversal modes (row stream / row small / column) + finalize kernels
 //   lq_stream2.hpp      streaming-size forms of the column and tiny-row modes (round 2): flat K1, pipelined column tile, ...
@@ -1232,6 +1232,33 @@ int lq_fq_scale_grad(const float* P, const float* s, const float* dy, float lamb
     return launch_finalize<OP_BWD>(p, f, (hipStream_t)stream);
 }
 
+int lq_fq_scale_grad_ste(const float* P, const float* s, const float* dy, float grad_scale, float* ds, void* ws, size_t ws_bytes,
+                         int64_t outer, int64_t G, int64_t inner, void* stream) {
+    int rc = check_desc(outer, G, inner);
+    if (rc) return rc;
+    LQ_REQUIRE_PTR(P);
+    LQ_REQUIRE_PTR(s);
+    LQ_REQUIRE_PTR(dy);
+    LQ_REQUIRE_PTR(ds);
+    Plan pl = make_plan(outer, G, inner, kBlock);      // generic traversal bodies: 256-thread units at every size (kStreamOp)
+    Params p = base_params(P, s, outer, G, inner);
+    p.dy = dy;
+    p.c_scale = grad_scale;
+    if ((rc = bind_ws(p, pl, ws, ws_bytes))) return rc;
+    const bool direct = pl.n1 * pl.n2 == 1;      // one partial per group: the traversal emits ds itself, no finalize launch
+    if (direct) {
+        p.direct = 1;
+        p.e0 = ds;
+        p.e1 = nullptr;
+        p.ecount = (double)outer * (double)inner;
+    }
+    if ((rc = launch_traverse<OP_STE_SCALE>(pl, p, (hipStream_t)stream))) return rc;
+    if (direct) return LQ_OK;
+    FinGeom f = group_geom(pl, outer, G, inner);
+    f.o0 = ds;
+    return launch_finalize<OP_STE_SCALE>(p, f, (hipStream_t)stream);
+}
+
 int lq_fq_fwd_bwd_fused(const float* P, const float* s, const float* dy, float lambda, float* out, float* ds, void* ws,
                         size_t ws_bytes, int64_t outer, int64_t G, int64_t inner, void* stream) {
     int rc = check_desc(outer, G, inner);
@@ -2169,6 +2196,36 @@ int lq_batch_penalty_values(const lq_batch* b, int kind, const float* dims, cons
     if (b->pen.h.size() != (size_t)b->n) return fail(LQ_EINVAL, "%s: every tensor of the batch needs a ds buffer", fn);
     if (kind != LQ_PENALTY_INVERSE && (rc = check_penalty_workspace(fn, b, ws, ws_bytes))) return rc;
     return launch_penalty_values(fn, b, kind, va, ws, false, (hipStream_t)stream);
+}
+
+// Runs on the `pen` table: every tensor with a ds buffer, generic traversal bodies and partial layout, whatever its lambda.
+int lq_batch_scale_grad_ste(const lq_batch* b, const float* const* dy, const float* grad_scale, void* ws, size_t ws_bytes, void* stream) {
+    const char* fn = "lq_batch_scale_grad_ste";
+    if (!b) return fail(LQ_EINVAL, "%s: NULL batch", fn);
+    const lq_task_table& tb = b->pen;
+    if (tb.h.empty()) return LQ_OK;
+    int rc = check_penalty_workspace(fn, b, ws, ws_bytes);
+    if (rc) return rc;
+    PtrPack pk;
+    CoefPack cf;
+    memset(&pk, 0, sizeof(pk));
+    memset(&cf, 0, sizeof(cf));
+    const int nt = (int)tb.h.size();
+    for (int i = 0; i < nt; ++i) {
+        const Task& t = tb.h[i];
+        const float* d = dy ? dy[tb.index[i]] : t.p.dy;
+        if (!d) return fail(LQ_EINVAL, "%s: no upstream gradient for tensor %d", fn, tb.index[i]);
+        if (!aligned(d, 4)) return fail(LQ_EALIGN, "%s: dy of tensor %d misaligned", fn, tb.index[i]);
+        const bool wants16 = (t.mode != MODE_COL && t.vec) || (t.mode == MODE_COL && t.col_variant >= 4);
+        if (wants16 && !aligned(d, 16)) return fail(LQ_EALIGN, "%s: dy of the 16-byte aligned tensor %d is not 16-byte aligned", fn, tb.index[i]);
+        pk.dy[i] = d;
+        cf.c[i] = grad_scale ? grad_scale[tb.index[i]] : 1.0f;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL((k_batch_traverse<OP_STE_SCALE>), dim3(tb.blocks), dim3(kBlock), 0, st, tb.d, tb.block_task_d, nt, (uint32_t*)ws, pk, 1, cf);
+    if ((rc = check_hip("batch STE scale-grad launch"))) return rc;
+    hipLaunchKernelGGL(k_batch_finalize_ste, dim3(tb.groups), dim3(64), 0, st, tb.d, tb.prefix_d + nt, nt, (uint32_t*)ws, cf);
+    return check_hip("batch STE finalize launch");
 }
 
 int lq_loss_log_append(const float* scce_dev, const float* penalty_dev, float rate, float* rows_dev, int64_t capacity,

@@ -115,6 +115,26 @@ __device__ __forceinline__ void fq_core4(const float4& x, const Ctx& c, float4& 
     o.x = q.x * c.s; o.y = q.y * c.s; o.z = q.z * c.s; o.w = q.w * c.s;
 }
 
+// The quotient t of fq_core4 itself (same window test, same two divisions: the same bits), for the op that needs t next to
+// floor(t): the straight-through scale gradient.  A form of its own: fq_core4 keeps the code the compiler gives it today.
+__device__ __forceinline__ float4 fq_quot4(const float4& x, const Ctx& c) {
+    const float amax = fmaxf(fmaxf(fabsf(x.x), fabsf(x.y)), fmaxf(fabsf(x.z), fabsf(x.w)));
+    const float amin = fminf(fminf(fabsf(x.x), fabsf(x.y)), fminf(fabsf(x.z), fabsf(x.w)));
+    float4 t;
+    if (__builtin_expect((c.fast != 0) & (amin >= 8.271806125530277e-25f) & (amax < 2.4178516392292583e+24f), 1)) {
+        t.x = fast_div(x.x, c.s, c.r);
+        t.y = fast_div(x.y, c.s, c.r);
+        t.z = fast_div(x.z, c.s, c.r);
+        t.w = fast_div(x.w, c.s, c.r);
+    } else {
+        t.x = x.x / c.s;
+        t.y = x.y / c.s;
+        t.z = x.z / c.s;
+        t.w = x.w / c.s;
+    }
+    return t;
+}
+
 __device__ __forceinline__ void vote_ctx(Ctx& c, float lam) {
     c.lam_hi = lam * 1.000001f;
     const float bmin = fminf(fabsf(c.s), kEpsF32);      // b = |q*s| >= |s| when q != 0, else eps (:63)
@@ -226,6 +246,25 @@ __device__ __forceinline__ void fq_core4c(const float4& x, const Ctx* c, float4&
     }
     q.x = floorf(t.x); q.y = floorf(t.y); q.z = floorf(t.z); q.w = floorf(t.w);
     o.x = q.x * c[0].s; o.y = q.y * c[1].s; o.z = q.z * c[2].s; o.w = q.w * c[3].s;
+}
+
+__device__ __forceinline__ float4 fq_quot4c(const float4& x, const Ctx* c) {      // the quotient of fq_core4c (see fq_quot4)
+    const float amax = fmaxf(fmaxf(fabsf(x.x), fabsf(x.y)), fmaxf(fabsf(x.z), fabsf(x.w)));
+    const float amin = fminf(fminf(fabsf(x.x), fabsf(x.y)), fminf(fabsf(x.z), fabsf(x.w)));
+    const int fast = c[0].fast & c[1].fast & c[2].fast & c[3].fast;
+    float4 t;
+    if (__builtin_expect((fast != 0) & (amin >= 8.271806125530277e-25f) & (amax < 2.4178516392292583e+24f), 1)) {
+        t.x = fast_div(x.x, c[0].s, c[0].r);
+        t.y = fast_div(x.y, c[1].s, c[1].r);
+        t.z = fast_div(x.z, c[2].s, c[2].r);
+        t.w = fast_div(x.w, c[3].s, c[3].r);
+    } else {
+        t.x = x.x / c[0].s;
+        t.y = x.y / c[1].s;
+        t.z = x.z / c[2].s;
+        t.w = x.w / c[3].s;
+    }
+    return t;
 }
 
 template <int TM>

@@ -299,6 +299,54 @@ struct OpT<OP_DIFF_BWD_V> : OpT<OP_DIFF_BWD> {
     }
 };
 
+// Straight-through scale gradient (lq_hip.h: lq_fq_scale_grad_ste): with floor' == 1, d out / d s = floor(P/s) - P/s, so
+//   t = P / s (K1's fp32 quotient, bit for bit)   r = floorf(t) - t (ONE fp32 subtraction, in [-1, 0])   acc.c += dy * r
+// product and sum in f64; the factor k (Params::c_scale) is applied once per group by FinT::emit.  |t| >= 2^23 gives r == 0
+// exactly; a NaN or +-Inf quotient gives a NaN term.  The terms have no common quantum: unlike the vote sums of OP_BWD at
+// lambda < 4e-4 the f64 sum depends on the traversal's order (below 2^-50 relative), so different traversals of one tensor may
+// differ in the last bit of ds -- every one of them is run-to-run bit-stable.
+template <>
+struct OpT<OP_STE_SCALE> : OpBase {
+    static constexpr bool kDy = true;
+    static constexpr bool kReduce = true;
+    __device__ static __forceinline__ Ctx ctx(const Params& p, int64_t g) {
+        Ctx c;
+        c.s = p.s[g];
+        div_ctx(c);
+        c.k0 = 0.f;
+        c.k1 = 0.f;
+        c.lam_hi = 0.f;
+        c.sure_ok = 0;
+        return c;
+    }
+    __device__ static __forceinline__ void term(float t, float dy, Acc& acc) {
+        const float r = floorf(t) - t;
+        acc.c += (double)dy * (double)r;
+    }
+    __device__ static __forceinline__ float elem(const Params&, const Ctx& c, int64_t, float x, float dy, Acc& acc) {
+        term(div_by_uniform(x, c), dy, acc);
+        return 0.f;
+    }
+    static constexpr bool kVec4 = true;
+    __device__ static __forceinline__ float4 elem4(const Params&, const Ctx& c, int64_t, const float4& x, const float4& dy, Acc& acc) {
+        const float4 t = fq_quot4(x, c);
+        term(t.x, dy.x, acc);
+        term(t.y, dy.y, acc);
+        term(t.z, dy.z, acc);
+        term(t.w, dy.w, acc);
+        return t;
+    }
+    static constexpr bool kVec4c = true;
+    __device__ static __forceinline__ float4 elem4c(const Params&, const Ctx* c, int64_t, const float4& x, const float4& dy, Acc* acc) {
+        const float4 t = fq_quot4c(x, c);
+        term(t.x, dy.x, acc[0]);
+        term(t.y, dy.y, acc[1]);
+        term(t.z, dy.z, acc[2]);
+        term(t.w, dy.w, acc[3]);
+        return t;
+    }
+};
+
 }  // namespace lq
 
 #endif

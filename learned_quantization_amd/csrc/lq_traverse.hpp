@@ -677,6 +677,15 @@ struct FinT<OP_DIFF_BWD> {
 template <>
 struct FinT<OP_DIFF_BWD_V> : FinT<OP_DIFF_BWD> {};
 
+template <>
+struct FinT<OP_STE_SCALE> {
+    __device__ static float emit(const Params& p, const FinGeom& f, int64_t g, const AccW& a) {
+        const float ds = (float)((double)p.c_scale * a.c);       // k = grad_scale, once per group
+        f.o0[g] = ds;
+        return ds;
+    }
+};
+
 template <int OP>
 __device__ __forceinline__ void emit_direct(const Params& p, int64_t g, const Acc& acc) {
     FinGeom f;

@@ -116,6 +116,9 @@ def main(argv=None):
     ap.add_argument("--custom_loss", type=str, default=None, choices=["maxbin", "difference", "inverse"],
                     help="custom_loss_terms variant; omitted = nested_quantization_layer variant")
     ap.add_argument("--value", type=float, default=None, help="penalty_threshold (default 1e-11) or penalty_rate (default 1e-7)")
+    ap.add_argument("--scale-gradient", default=None, choices=["ste"],
+                    help="the straight-through scale gradient instead of the nested-quantization vote (with --custom_loss: next to "
+                         "the loss term)")
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--steps-per-epoch", type=int, default=10)
     ap.add_argument("--batch", type=int, default=128)
@@ -134,8 +137,11 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise SystemExit("needs an MI355X (no CPU fallback)")
     dev = torch.device("cuda", 0)
-    mode = "cl" if args.custom_loss else "nq"
-    value = args.value if args.value is not None else (1e-7 if mode == "cl" else 1e-11)
+    if args.scale_gradient == "ste":
+        mode = "stecl" if args.custom_loss else "ste"
+    else:
+        mode = "cl" if args.custom_loss else "nq"
+    value = args.value if args.value is not None else (1e-7 if args.custom_loss else 1e-11)
     scenario_dir = os.path.join(args.log_root, f"{args.orientation}_{args.training}", f"seed_{args.seed}")
     log_dir = os.path.join(scenario_dir, f"{time.strftime('%Y-%m-%d_%H-%M-%S')}_lr_{args.lr}_pr_{value}")
     os.makedirs(log_dir, exist_ok=True)

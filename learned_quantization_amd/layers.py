@@ -126,14 +126,26 @@ class CustomQuantizedScaleLayer(nn.Module):
 
     ``penalty_threshold`` given  -> nested-quantization op (hand-written scale gradient).
     ``penalty_rate`` given instead (CL-L:71) -> STE-only op; the scale learns through a loss term.
+    ``scale_gradient="ste"`` (not in the reference; only without ``penalty_threshold``) -> the scale also receives the
+    straight-through gradient ``grad_scale * sum dy * (floor(P/s) - P/s)`` (ops.fq_scale_grad_ste); ``grad_scale`` is a
+    float or ``"rsqrt_group"`` = 1 / sqrt(elements per group).
     """
 
     _SCALE_NAMES = {"rowwise": "Rowwise-scaler", "columnwise": "Columnwise-scaler",
                     "channelwise": "Columnwise-scaler",      # sic, NQ-L:178
                     "scalar": "Scalar-scaler"}
 
-    def __init__(self, penalty_threshold=None, initializer=None, orientation="scalar", *, penalty_rate=None):
+    def __init__(self, penalty_threshold=None, initializer=None, orientation="scalar", *, penalty_rate=None,
+                 scale_gradient=None, grad_scale=1.0):
         super().__init__()
+        if scale_gradient not in ops.SCALE_GRADIENTS:
+            raise ValueError(f"scale_gradient must be one of {ops.SCALE_GRADIENTS}, got {scale_gradient!r}")
+        if scale_gradient == "ste" and penalty_threshold is not None:
+            raise ValueError('scale_gradient="ste" replaces the nested-quantization vote: it needs penalty_threshold=None')
+        if grad_scale != "rsqrt_group":
+            grad_scale = float(grad_scale)
+        self.scale_gradient = scale_gradient
+        self.grad_scale = grad_scale
         self.initializer = initializer
         self.orientation = orientation
         self.penalty_threshold = penalty_threshold
@@ -156,9 +168,18 @@ class CustomQuantizedScaleLayer(nn.Module):
         self.scale_name = self._SCALE_NAMES[self.orientation]
         self.built = True
 
+    def grad_scale_value(self, parameter_numel: int) -> float:
+        """The factor k of the straight-through scale gradient for a parameter of that many elements."""
+        if self.grad_scale == "rsqrt_group":
+            return 1.0 / math.sqrt(parameter_numel / self.scale.numel())
+        return self.grad_scale
+
     def call(self, inputs):
         if not self.built:
             self.build(tuple(inputs.shape), device=inputs.device)
+        if self.scale_gradient == "ste":
+            return ops.my_custom_gradient(inputs, self.scale, scale_gradient="ste", grad_scale=self.grad_scale_value(inputs.numel()),
+                                          defer_scale_grad=self.defer_scale_grad)
         if self.penalty_threshold is None:
             return ops.my_custom_gradient(inputs, self.scale)                        # CL-L:143-144
         return ops.my_custom_gradient(inputs, self.scale, self.penalty_threshold,   # NQ-L:199-200
@@ -167,12 +188,16 @@ class CustomQuantizedScaleLayer(nn.Module):
     forward = call
 
     def extra_repr(self):
-        return f"orientation={self.orientation!r}, penalty_threshold={self.penalty_threshold}, penalty_rate={self.penalty_rate}"
+        r = f"orientation={self.orientation!r}, penalty_threshold={self.penalty_threshold}, penalty_rate={self.penalty_rate}"
+        if self.scale_gradient is not None:
+            r += f", scale_gradient={self.scale_gradient!r}, grad_scale={self.grad_scale!r}"
+        return r
 
 
-def _nested(penalty_threshold, penalty_rate, orientation):
+def _nested(penalty_threshold, penalty_rate, orientation, scale_gradient=None, grad_scale=1.0):
     return CustomQuantizedScaleLayer(penalty_threshold=penalty_threshold, initializer=None,
-                                     orientation=orientation, penalty_rate=penalty_rate)
+                                     orientation=orientation, penalty_rate=penalty_rate,
+                                     scale_gradient=scale_gradient, grad_scale=grad_scale)
 
 
 def _as_tensor(a, shape, device):
@@ -207,11 +232,11 @@ class CustomDenseLayer(_HostLayer):
 
     def __init__(self, seed=None, units=None, penalty_threshold=None, orientation="scalar", initializer=None,
                  name=None, regularizer=None, trained_weights=None, *, penalty_rate=None, input_shape=None,
-                 device=None, **kwargs):
+                 device=None, scale_gradient=None, grad_scale=1.0, **kwargs):
         super().__init__()
         self.seed = seed
-        self.nested_q_w_layer = _nested(penalty_threshold, penalty_rate, orientation)       # NQ-L:222-224
-        self.nested_q_b_layer = _nested(penalty_threshold, penalty_rate, "scalar")          # NQ-L:225-227
+        self.nested_q_w_layer = _nested(penalty_threshold, penalty_rate, orientation, scale_gradient, grad_scale)   # NQ-L:222-224
+        self.nested_q_b_layer = _nested(penalty_threshold, penalty_rate, "scalar", scale_gradient, grad_scale)      # NQ-L:225-227
         self.units = units
         self.initializer = initializer
         self.regularizer = regularizer
@@ -299,7 +324,7 @@ class _ConvBase(_HostLayer):
     def __init__(self, seed=None, penalty_threshold=None, orientation="scalar", initializer=None, filters=None,
                  kernel_size=(3, 3), strides=(1, 1), padding="same", name=None, regularizer=None,
                  trained_weights=None, *, penalty_rate=None, input_shape=None, data_format="NCHW", device=None,
-                 kernel_storage=None, **kwargs):
+                 kernel_storage=None, scale_gradient=None, grad_scale=1.0, **kwargs):
         super().__init__()
         self.seed = seed
         if kernel_storage is None:
@@ -307,9 +332,9 @@ class _ConvBase(_HostLayer):
         if kernel_storage not in ("oihw", "hwio"):
             raise ValueError("kernel_storage must be 'oihw' or 'hwio'")
         self.kernel_storage = kernel_storage
-        self.nested_q_k_layer = _nested(penalty_threshold, penalty_rate, orientation)      # NQ-L:293-295
+        self.nested_q_k_layer = _nested(penalty_threshold, penalty_rate, orientation, scale_gradient, grad_scale)      # NQ-L:293-295
         if self._has_bias:
-            self.nested_q_b_layer = _nested(penalty_threshold, penalty_rate, "scalar")     # NQ-L:296-298
+            self.nested_q_b_layer = _nested(penalty_threshold, penalty_rate, "scalar", scale_gradient, grad_scale)     # NQ-L:296-298
         self.initializer = initializer
         self.filters = filters
         self.kernel_size = _pair(kernel_size)

@@ -19,7 +19,9 @@ reference's do, so ``compute_total_loss(y_true, y_pred)`` keeps its meaning; lik
 carries its logits (``losses.softmax``), from which the cross-entropy is computed.  Activations are NCHW.
 
 ``mode="nq"``: ``value`` is the penalty_threshold (nested-quantization scale gradient);
-``mode="cl"``: ``value`` is the penalty_rate (STE-only op; scales learn through a custom loss term).
+``mode="cl"``: ``value`` is the penalty_rate (STE-only op; scales learn through a custom loss term);
+``mode="ste"``: the straight-through scale gradient (ops.fq_scale_grad_ste), no loss term, ``value`` is ignored;
+``mode="stecl"``: the same plus a custom loss term, ``value`` is the penalty_rate.
 """
 from __future__ import annotations
 
@@ -44,7 +46,11 @@ def _kw(mode: str, value: float):
         return dict(penalty_threshold=None, penalty_rate=value)
     if mode == "nqcl":      # (penalty_threshold, penalty_rate): nested-quantization op + a loss term (extension, train.py)
         return dict(penalty_threshold=value[0], penalty_rate=value[1])
-    raise ValueError("mode must be 'nq', 'cl' or 'nqcl'")
+    if mode == "ste":       # straight-through scale gradient, no loss term (extension: the reference leaves this slot a TODO)
+        return dict(penalty_threshold=None, scale_gradient="ste")
+    if mode == "stecl":     # the same + a loss term
+        return dict(penalty_threshold=None, penalty_rate=value, scale_gradient="ste")
+    raise ValueError("mode must be 'nq', 'cl', 'nqcl', 'ste' or 'stecl'")
 
 
 def _plain_dense(n_in: int, n_out: int, seed: Optional[int]) -> nn.Linear:
@@ -262,9 +268,17 @@ class ResNet50Like(nn.Module):
         return softmax(self.out(torch.mean(x, dim=(2, 3))), dim=1)
 
 
-def build_model(config: str, kernel_storage: str = None, **kw) -> nn.Module:
+def build_model(config: str, kernel_storage: str = None, grad_scale=None, **kw) -> nn.Module:
     """config: 'mnist' (C1), 'cifar' (C2/C4), 'imagenette' (C3), 'resnet50' (C5, extension).
-    ``kernel_storage``: memory order of the conv kernels, "oihw" (default) or "hwio" (layers.py)."""
+    ``kernel_storage``: memory order of the conv kernels, "oihw" (default) or "hwio" (layers.py).
+    ``grad_scale`` (modes "ste" / "stecl"): factor of every straight-through scale gradient, a float or "rsqrt_group"."""
+    if grad_scale is not None:
+        from .layers import CustomQuantizedScaleLayer
+        model = build_model(config, kernel_storage=kernel_storage, **kw)
+        for m in model.modules():
+            if isinstance(m, CustomQuantizedScaleLayer):
+                m.grad_scale = grad_scale if grad_scale == "rsqrt_group" else float(grad_scale)
+        return model
     if kernel_storage is not None:
         from .layers import default_kernel_storage
         with default_kernel_storage(kernel_storage):

@@ -6,7 +6,7 @@
   * 2-argument form ``(parameter, scale)`` = STE-only op
     /root/reference/CIFAR-10/custom_loss_terms/custom_components/custom_layers.py:49-64
 
-Raw (non-autograd) wrappers ``fq_forward``, ``fq_scale_grad``, ``fq_fwd_bwd_fused``,
+Raw (non-autograd) wrappers ``fq_forward``, ``fq_scale_grad``, ``fq_scale_grad_ste``, ``fq_fwd_bwd_fused``,
 ``quantized_integers`` ... are thin: argument checking + one C-ABI call each.
 Everything runs on the HIP device; there is no CPU fallback.
 """
@@ -82,6 +82,20 @@ def fq_scale_grad(parameter: torch.Tensor, scale: torch.Tensor, dy: torch.Tensor
                                     outer, G, inner, _hip.stream_ptr(p.device)), "lq_fq_scale_grad")
     if return_parts:
         return ds, parts.view(3, G)
+    return ds
+
+
+def fq_scale_grad_ste(parameter: torch.Tensor, scale: torch.Tensor, dy: torch.Tensor, grad_scale: float = 1.0):
+    """The straight-through scale gradient (include/lq_hip.h, lq_fq_scale_grad_ste):
+    ds[g] = grad_scale * sum_{i in g} dy_i * (floor(P_i/s_g) - P_i/s_g), K1's fp32 quotient, f64 sum.  Returns ds (shape of scale)."""
+    lib = _hip.load()
+    p, s, (outer, G, inner) = _param(parameter, scale)
+    d = _hip.require_device_f32(dy, "dy", like=p)
+    ds = torch.empty_like(s)
+    ws = _hip.workspace_for(p.device, outer, G, inner)
+    _hip.check(lib.lq_fq_scale_grad_ste(_hip.ptr(p), _hip.ptr(s), _hip.ptr(d), float(grad_scale), _hip.ptr(ds),
+                                        _hip.ptr(ws), ws.numel(), outer, G, inner, _hip.stream_ptr(p.device)),
+               "lq_fq_scale_grad_ste")
     return ds
 
 
@@ -397,11 +411,43 @@ class _STEQuantFn(torch.autograd.Function):
         return (dy if ctx.needs_input_grad[0] else None), ds
 
 
-def my_custom_gradient(parameter, scale, penalty_threshold=None, *, defer_scale_grad=False):
+class _STEScaleQuantFn(torch.autograd.Function):
+    """Forward K1, backward (dy, straight-through scale gradient): the variant the reference's paper_implementation leaves
+    as a TODO (its scale gradient is zeros)."""
+
+    @staticmethod
+    def forward(ctx, parameter, scale, grad_scale, defer_scale_grad=False):
+        ctx.save_for_backward(parameter, scale)
+        ctx.grad_scale = float(grad_scale)
+        ctx.defer = bool(defer_scale_grad)
+        return fq_forward(parameter, scale)
+
+    @staticmethod
+    def backward(ctx, dy):
+        parameter, scale = ctx.saved_tensors
+        ds = None
+        # defer: the batch computes every scale gradient of the step in two launches (batch.py)
+        if ctx.needs_input_grad[1] and not ctx.defer:
+            ds = fq_scale_grad_ste(parameter, scale, dy, ctx.grad_scale)
+        return (dy if ctx.needs_input_grad[0] else None), ds, None, None
+
+
+SCALE_GRADIENTS = (None, "ste")
+
+
+def my_custom_gradient(parameter, scale, penalty_threshold=None, *, scale_gradient=None, grad_scale=1.0, defer_scale_grad=False):
     """The reference op.  With ``penalty_threshold`` -> nested-quantization variant
     (custom_layers.py:49-120); without -> STE-only variant (CL custom_layers.py:49-64).
+    ``scale_gradient="ste"`` (not in the reference, only without ``penalty_threshold``): the scale receives the
+    straight-through gradient ``grad_scale * sum dy * (floor(P/s) - P/s)`` instead of zeros.
     ``defer_scale_grad`` (not in the reference): backward returns dP only; the caller computes ds later from the
     all-reduced dP (exact data-parallel mode, ddp.py)."""
+    if scale_gradient not in SCALE_GRADIENTS:
+        raise ValueError(f"scale_gradient must be one of {SCALE_GRADIENTS}, got {scale_gradient!r}")
+    if scale_gradient == "ste":
+        if penalty_threshold is not None:
+            raise ValueError('scale_gradient="ste" replaces the nested-quantization vote: it needs penalty_threshold=None')
+        return _STEScaleQuantFn.apply(parameter, scale, float(grad_scale), defer_scale_grad)
     if penalty_threshold is None:
         return _STEQuantFn.apply(parameter, scale)
     if isinstance(penalty_threshold, torch.Tensor):

@@ -50,7 +50,11 @@ class Trainer:
     ``mode``: "nq" (nested quantization: ``value`` = penalty_threshold), "cl" (custom loss terms: ``value`` =
     penalty_rate, ``loss`` names the term), "nqcl" (BASELINE.json configs[3], "nested quantization + custom_loss_terms
     penalty": ``value`` = (penalty_threshold, penalty_rate); the scale gradient is the hand-written NQ gradient PLUS the
-    penalty's -- an extension without a reference call site, the reference never combines the two: CL-L:61-62).
+    penalty's -- an extension without a reference call site, the reference never combines the two: CL-L:61-62),
+    "ste" (the straight-through scale gradient of ops.fq_scale_grad_ste, no loss term, ``value`` ignored) and "stecl" (the
+    same plus a loss term: ``value`` = penalty_rate, ``loss`` names the term); ``grad_scale`` is their factor k, a float
+    or "rsqrt_group".  Both are linear in dy: data-parallel mode "A" (average ds over the ranks) already is the global-batch
+    gradient, mode "B" is refused.
 
     A step is two phases: ``_backward_phase`` (zero the gradients, fake-quantise, forward, loss, backward, penalty
     injection) and ``_update_phase`` (exact-mode scale gradients, both optimizers); between them the data-parallel
@@ -65,7 +69,7 @@ class Trainer:
                  lr=1e-4, seed=42, device=None, ddp_mode="A", log_dir="logs", graph=False, batched=False,
                  bucket_mb: float = 25.0, overlap: bool = True, graph_collectives: Optional[bool] = None,
                  force_collectives: bool = False, kernel_storage: str = "oihw", loss_values: bool = False,
-                 loss_log_capacity: int = 4096):
+                 loss_log_capacity: int = 4096, grad_scale=None):
         """``loss_values`` (modes with a loss term): the step also EVALUATES the penalty -- batched: as a by-product of the
         gradient injection (lq_batch_penalty_grads_values); per-tensor path: the loss object's own device scalar -- appends the
         reference's three per-step numbers (CL-F:58-71) to a device-side ``LossLog`` (no synchronisation, capturable) and
@@ -80,21 +84,27 @@ class Trainer:
         L.reset_layer_names()
         self.config = config
         self.mode = mode
+        ste = mode in ("ste", "stecl")
+        if ste and ddp_mode == "B":
+            raise ValueError(f"mode {mode!r} with ddp_mode 'B': the straight-through scale gradient is linear in dy, so averaging ds "
+                             "over the ranks (ddp_mode 'A') already is the global-batch gradient; there is nothing to recompute")
+        if grad_scale is not None and not ste:
+            raise ValueError("grad_scale belongs to the modes 'ste' and 'stecl'")
         # conv kernels shaped HWIO like the reference's, stored in the order MIOpen consumes (layers.py kernel_storage): the
         # fake-quantised kernel goes to the convolution as written and its weight gradient is dP
         self.model = build_model(config, mode=mode, value=value, seed=seed, orientation=orientation, device=self.device,
-                                 kernel_storage=kernel_storage)
+                                 kernel_storage=kernel_storage, grad_scale=grad_scale)
         self.model.to(self.device)
         self.custom_layers = L.custom_layers_of(self.model)
         self.loss_obj = None
         self.loss_kind = loss
         self.penalty_rate = value[1] if mode == "nqcl" else value
-        if mode in ("cl", "nqcl"):
+        if mode in ("cl", "nqcl", "stecl"):
             if loss not in LOSSES:
                 raise ValueError(f"mode {mode!r} needs --loss maxbin|difference|inverse")
             self.loss_obj = LOSSES[loss](self.custom_layers, self.penalty_rate, log_dir)   # custom_loss_terms/experiment.py:436-455
         elif loss is not None:
-            raise ValueError("a loss term needs mode 'cl' or 'nqcl'")
+            raise ValueError("a loss term needs mode 'cl', 'nqcl' or 'stecl'")
         self.world = dist.get_world_size() if dist.is_initialized() else 1
         use_dp = self.world > 1 or (force_collectives and dist.is_initialized())
         # Exact mode B reads the all-reduced P.grad as the global-batch dy (custom_layers.py:118): everything else that has a
@@ -121,7 +131,8 @@ class Trainer:
             self.batch = FakeQuantBatch(self.model, lr=lr, hwio_out=False, autograd=False)
             # nothing touches ds between its computation and the scales' update when there is no loss term and ds is not
             # exchanged (one process, or exact mode B): the finalize then applies the Adam step itself (one launch fewer)
-            fused = self.loss_obj is None and (self.dp is None or ddp_mode == "B")
+            # (the fused finalize + Adam is the nested-quantization pass's: not for the straight-through modes)
+            fused = self.loss_obj is None and (self.dp is None or ddp_mode == "B") and not ste
             self.scale_opt = BatchedScaleAdam(self.batch, capturable=graph, fused=fused)
             if self.dp is not None:
                 self.dp.attach_batch(self.batch)
@@ -201,8 +212,8 @@ class Trainer:
     def _inject_penalty(self):
         # batched custom-loss-terms mode: the task loss went through autograd, the penalty gradients are injected
         # by the batch kernels (identical on every rank, so adding them before the all-reduce changes nothing);
-        # "nqcl": the penalty's ds is ADDED to the nested-quantization ds the batch has just written
-        penalty = self.batch.inject_penalty_grads(self.loss_kind, self.penalty_rate, accumulate_ds=(self.mode == "nqcl"),
+        # "nqcl" / "stecl": the penalty's ds is ADDED to the op's own ds the batch has just written
+        penalty = self.batch.inject_penalty_grads(self.loss_kind, self.penalty_rate, accumulate_ds=(self.mode in ("nqcl", "stecl")),
                                                   values=self.loss_values)
         if self.loss_values:
             # the log's row is the reference's three numbers (CL-F:58-71); Keras adds the regularisers outside
@@ -358,8 +369,10 @@ class Trainer:
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", choices=list(INPUT_SHAPES), default="cifar")
-    ap.add_argument("--mode", choices=["nq", "cl", "nqcl"], default="nq")
-    ap.add_argument("--value", type=float, default=1e-11, help="penalty_threshold (nq, nqcl) or penalty_rate (cl)")
+    ap.add_argument("--mode", choices=["nq", "cl", "nqcl", "ste", "stecl"], default="nq")
+    ap.add_argument("--value", type=float, default=1e-11, help="penalty_threshold (nq, nqcl) or penalty_rate (cl, stecl); ignored by ste")
+    ap.add_argument("--grad-scale", default=None,
+                    help="modes ste / stecl: factor of the straight-through scale gradient, a float or 'rsqrt_group' (default 1)")
     ap.add_argument("--rate", type=float, default=1e-7, help="penalty_rate of the loss term in mode nqcl")
     ap.add_argument("--value-coarse", type=float, default=None,
                     help="resnet50 only: threshold of the 3x3 kernels ('mixed' quantisation intensity); --value is the rest")
@@ -422,7 +435,9 @@ def main(argv=None):
     tr = Trainer(args.config, args.mode, value, args.orientation, args.loss, seed=args.seed, device=dev,
                  ddp_mode=args.ddp_mode, graph=args.graph, batched=args.batched, bucket_mb=args.bucket_mb,
                  graph_collectives=args.graph_collectives, force_collectives=args.force_dist, kernel_storage=args.kernel_storage,
-                 loss_values=args.loss_values, loss_log_capacity=max(4096, args.steps + args.warmup + 8))
+                 loss_values=args.loss_values, loss_log_capacity=max(4096, args.steps + args.warmup + 8),
+                 grad_scale=(None if args.grad_scale is None else
+                             (args.grad_scale if args.grad_scale == "rsqrt_group" else float(args.grad_scale))))
     do_step = tr.step_graphed if args.graph else tr.step
     g = torch.Generator(device=dev).manual_seed(args.seed + rank)
     batches = [synthetic_batch(args.config, args.batch, dev, g) for _ in range(4)]

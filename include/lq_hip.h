@@ -102,6 +102,34 @@ int lq_fq_scale_grad_ste(const float* P, const float* s, const float* dy, float 
                          float* ds, void* ws, size_t ws_bytes,
                          int64_t outer, int64_t G, int64_t inner, void* stream);
 
+/* ---- clipped b-bit fake-quant with LSQ gradients (the integer range is chosen, not an outcome of training) ----
+ * Integers qmin <= qmax with -2^24 <= qmin, qmax <= 2^24 (exact in fp32); lo = (float)qmin, hi = (float)qmax.  For element i
+ * of group g:
+ *   t  = P_i / s[g]                              IEEE fp32 division: K1's quotient, bit for bit
+ *   q0 = floorf(t)
+ *   q  = q0 < lo ? lo : (q0 > hi ? hi : q0)      comparisons, not fmin/fmax: a NaN q0 stays NaN, +-Inf saturates
+ *   out_i = q * s[g]                             one fp32 product, as K1
+ *   inside_i = (q0 >= lo) && (q0 <= hi)          false for NaN
+ *   dP_i  = inside_i ? dy_i : +0.0f
+ *   r_i   = inside_i ? (q0 - t)  [ONE fp32 subtraction, as lq_fq_scale_grad_ste]  :  q   [lo or hi; NaN if q0 is NaN]
+ *   ds[g] = RN_f32( (double)grad_scale * sum_{i in g} (double)dy_i * (double)r_i )
+ *   clipped[g] = #{ i in g : !inside_i }         exact, uint32 (saturates at 2^32 - 1)
+ * Clipped elements pass no gradient to P and pull the scale towards covering them.  The sum is f64 from the first addition,
+ * two-stage and ordered (no float atomics): run-to-run bit-stable.  As for lq_fq_scale_grad_ste the terms have no common
+ * quantum, so different traversals of the same data need not give bit-identical ds.  With qmin = -2^24, qmax = 2^24 and
+ * |t| < 2^24: out has lq_fq_forward's bits, dP == dy, ds is lq_fq_scale_grad_ste's up to the summation order.
+ * lq_fq_forward_clip: `out` is required; q / q_dtype optionally give the CLAMPED integers (as lq_fq_forward's integer view).
+ * lq_fq_backward_clip: dP is required (same memory order as P); ds == NULL means "mask only" (the loss-term-only rule: the
+ * same kernel runs and the sum is dropped when the outputs are written); clipped may be NULL.  ws: lq_workspace_bytes() of the
+ * descriptor, required in every case.  A NULL required pointer, qmin > qmax, a bound outside +-2^24, a workspace that is
+ * missing or too small and a bad descriptor return LQ_EINVAL before any launch.  Both calls only enqueue (capturable).
+ * Run the generic traversal bodies at every size, as lq_fq_scale_grad_ste.  */
+int lq_fq_forward_clip(const float* P, const float* s, float* out, void* q, int q_dtype,
+                       int32_t qmin, int32_t qmax, int64_t outer, int64_t G, int64_t inner, void* stream);
+int lq_fq_backward_clip(const float* P, const float* s, const float* dy, int32_t qmin, int32_t qmax, float grad_scale,
+                        float* dP, float* ds /* may be NULL */, uint32_t* clipped /* may be NULL */,
+                        void* ws, size_t ws_bytes, int64_t outer, int64_t G, int64_t inner, void* stream);
+
 /* ---- K4: forward and NQ backward of one tensor in a single pass (benchmark path) ---
  * Same results as lq_fq_forward followed by lq_fq_scale_grad (out, max|q| and the vote count bit for bit; on
  * streaming-size tensors the vote sum may differ by fp32 summation order, ~1e-7 relative); P is read once.  */

@@ -10,8 +10,9 @@ from .layers import (default_kernel_storage, CustomConv2DLayer, CustomConv2DLaye
                      L2, MinValueConstraint, RandomNormal, SCALE_INIT, custom_layers_of, eps_float32, l2,
                      reset_layer_names)
 from .losses import LossLog, SCCEDifference, SCCEInverse, SCCEMaxBin, sparse_categorical_crossentropy
-from .ops import (difference_term, fq_forward, fq_fwd_bwd_fused, fq_scale_grad, fq_scale_grad_ste, inverse_term, maxbin_term,
-                  my_custom_gradient, q_absmax_over_axis, q_minmax, q_pack, q_unique, q_unpack, quantized_integers)
+from .ops import (difference_term, fq_backward_clip, fq_forward, fq_forward_clip, fq_fwd_bwd_fused, fq_scale_grad, fq_scale_grad_ste,
+                  inverse_term, maxbin_term,
+                  my_custom_gradient, q_absmax_over_axis, q_minmax, q_pack, q_range_of, q_unique, q_unpack, quantized_integers)
 from .optim import KerasAdam, ScaleAdam, apply_constraints, non_scale_parameters, scale_parameters
 from .ddp import DataParallel, GradBucket
 from .batch import BatchedScaleAdam, FakeQuantBatch

@@ -42,6 +42,7 @@ _c_d = ctypes.c_double
 _c_p = ctypes.c_void_p
 _c_sz = ctypes.c_size_t
 _c_int = ctypes.c_int
+_c_i32 = ctypes.c_int32
 
 #: name -> (restype, argtypes); one entry per symbol declared in include/lq_hip.h
 SIGNATURES = {
@@ -52,6 +53,8 @@ SIGNATURES = {
     "lq_fq_forward": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_i64, _c_i64, _c_i64, _c_p]),
     "lq_fq_scale_grad": (_c_int, [_c_p, _c_p, _c_p, _c_f, _c_p, _c_p, _c_p, _c_sz, _c_i64, _c_i64, _c_i64, _c_p]),
     "lq_fq_scale_grad_ste": (_c_int, [_c_p, _c_p, _c_p, _c_f, _c_p, _c_p, _c_sz, _c_i64, _c_i64, _c_i64, _c_p]),
+    "lq_fq_forward_clip": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_i32, _c_i32, _c_i64, _c_i64, _c_i64, _c_p]),
+    "lq_fq_backward_clip": (_c_int, [_c_p, _c_p, _c_p, _c_i32, _c_i32, _c_f, _c_p, _c_p, _c_p, _c_p, _c_sz, _c_i64, _c_i64, _c_i64, _c_p]),
     "lq_fq_fwd_bwd_fused": (_c_int, [_c_p, _c_p, _c_p, _c_f, _c_p, _c_p, _c_p, _c_sz, _c_i64, _c_i64, _c_i64, _c_p]),
     "lq_penalty_maxbin_fwd": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_sz, _c_i64, _c_i64, _c_i64, _c_p]),
     "lq_penalty_maxbin_bwd": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_f, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p]),

@@ -57,6 +57,9 @@ class FakeQuantBatch:
         self.entries: List[_Entry] = []
         nested_layers = [getattr(layer, a) for layer in layers for a in ("nested_q_w_layer", "nested_q_k_layer", "nested_q_b_layer")
                          if hasattr(layer, a)]
+        if any(getattr(n, "q_range", None) is not None for n in nested_layers):
+            raise ValueError("FakeQuantBatch over a clipped layer (bits / q_range): the multi-tensor backward hands dy on as dP, "
+                             "but a clipped layer's dP is a masked copy of dy; run such a model on the per-tensor path (batched=False)")
         rules = {n.scale_gradient for n in nested_layers}
         if "ste" in rules and len(rules) > 1:
             raise ValueError('one FakeQuantBatch holds one scale-gradient rule: every layer needs scale_gradient="ste", or none')

@@ -36,6 +36,8 @@ struct Params {
     int q_dtype;
     float lam;
     int tmode;           // 0: lambda < 4e-4 (tanh(d) == d), 1: lambda <= 0.25 (polynomial), 2: general (ocml tanhf)
+    float clip_lo;       // OP_CLIP_FWD / OP_CLIP_BWD: (float)qmin (this word and clip_hi below sit where alignment padding was: no
+                         // other field moves and the struct keeps its size, so the other kernels' argument offsets stay)
     const float* mb;     // per-group max(|P|/s)      (maxbin backward)
     const uint32_t* ties;
     const float* c_dev;  // upstream gradient, device scalar
@@ -48,6 +50,7 @@ struct Params {
     // direct emit (scale-gradient ops whose groups have exactly one partial: biases, row-wise Dense, one row per group):
     // the traversal writes the op's outputs itself and the finalize launch is skipped
     int direct;
+    float clip_hi;       // OP_CLIP_FWD / OP_CLIP_BWD: (float)qmax
     float* e0;           // ds[G]
     float* e1;           // optional parts[3*G]
     double ecount;       // elements per group
@@ -59,6 +62,8 @@ struct Params {
     float* dp_out;         // K2: dP in HWIO order, written when dy_perm is set
     uint32_t perm_hw, perm_ci, perm_co;
 };
+
+static_assert(sizeof(Params) == 208, "Params: clip_lo / clip_hi must stay inside the former padding");
 
 __device__ __forceinline__ uint32_t perm_index(const Params& p, int64_t i) {      // conv kernels are far below 2^32 elements
     const uint32_t iu = (uint32_t)i;
@@ -116,6 +121,8 @@ enum OpKind {
     OP_BWD_PERM = 9,   // K2 that can take dy in OIHW order and write dP in HWIO order
     OP_DIFF_BWD_V = 10, // K5b backward that also carries sum |P - P/s| (the term's VALUE) in a second accumulator
     OP_STE_SCALE = 11,  // straight-through scale gradient: ds[g] = k * sum dy * (floor(P/s) - P/s)
+    OP_CLIP_FWD = 12,   // clipped forward: out = clamp(floor(P/s), qmin, qmax) * s
+    OP_CLIP_BWD = 13,   // clipped backward: dP = inside ? dy : 0, ds[g] = k * sum dy * r, clipped[g] = #{!inside}
 };
 
 }  // namespace lq

@@ -3,7 +3,7 @@
 //
 //   lq_common.hpp       constants, kernel parameter block, accumulator types
 //   lq_math.hpp         exact fp32 arithmetic: uniform-divisor division, in-window ratio division, |tanh|, vote
-//   lq_ops.hpp          per-operation traits (K1 fwd, K2 bwd, K4 fused, K5 penalties, integer view, STE scale gradient)
+//   lq_ops.hpp          per-operation traits (K1 fwd, K2 bwd, K4 fused, K5 penalties, integer view, STE scale gradient, clipped pair)
 //   lq_reduce.hpp       wave/block reductions (DPP for the standard accumulator, shuffles for custom merges)
 //   lq_traverse.hpp     traversal modes (row stream / row small / column) + finalize kernels
 //   lq_stream2.hpp      streaming-size forms of the column and tiny-row modes (round 2): flat K1, pipelined column tile, ...
@@ -1257,6 +1257,70 @@ int lq_fq_scale_grad_ste(const float* P, const float* s, const float* dy, float 
     FinGeom f = group_geom(pl, outer, G, inner);
     f.o0 = ds;
     return launch_finalize<OP_STE_SCALE>(p, f, (hipStream_t)stream);
+}
+
+static int check_clip_range(const char* fn, int32_t qmin, int32_t qmax) {
+    constexpr int32_t kLim = 1 << 24;      // integers up to 2^24 in magnitude are exact in fp32
+    if (qmin > qmax) return fail(LQ_EINVAL, "%s: qmin %d > qmax %d", fn, (int)qmin, (int)qmax);
+    if (qmin < -kLim || qmax > kLim) return fail(LQ_EINVAL, "%s: range [%d, %d] is outside +-2^24", fn, (int)qmin, (int)qmax);
+    return LQ_OK;
+}
+
+int lq_fq_forward_clip(const float* P, const float* s, float* out, void* q, int q_dtype, int32_t qmin, int32_t qmax, int64_t outer,
+                       int64_t G, int64_t inner, void* stream) {
+    int rc = check_desc(outer, G, inner);
+    if (rc) return rc;
+    LQ_REQUIRE_PTR(P);
+    LQ_REQUIRE_PTR(s);
+    LQ_REQUIRE_PTR(out);
+    if ((rc = check_clip_range(__func__, qmin, qmax))) return rc;
+    if (q_dtype < LQ_Q_NONE || q_dtype > LQ_Q_I8) return fail(LQ_EINVAL, "lq_fq_forward_clip: bad q_dtype %d", q_dtype);
+    if ((q != nullptr) != (q_dtype != LQ_Q_NONE)) return fail(LQ_EINVAL, "lq_fq_forward_clip: q and q_dtype disagree");
+    Plan pl = make_plan(outer, G, inner, kBlock);      // generic traversal bodies: 256-thread units at every size (kStreamOp)
+    Params p = base_params(P, s, outer, G, inner);
+    p.out = out;
+    p.q = q;
+    p.q_dtype = q_dtype;
+    p.clip_lo = (float)qmin;
+    p.clip_hi = (float)qmax;
+    return launch_traverse<OP_CLIP_FWD>(pl, p, (hipStream_t)stream);
+}
+
+int lq_fq_backward_clip(const float* P, const float* s, const float* dy, int32_t qmin, int32_t qmax, float grad_scale, float* dP,
+                        float* ds, uint32_t* clipped, void* ws, size_t ws_bytes, int64_t outer, int64_t G, int64_t inner, void* stream) {
+    int rc = check_desc(outer, G, inner);
+    if (rc) return rc;
+    LQ_REQUIRE_PTR(P);
+    LQ_REQUIRE_PTR(s);
+    LQ_REQUIRE_PTR(dy);
+    LQ_REQUIRE_PTR(dP);
+    if (ds && !aligned(ds, 4)) return fail(LQ_EALIGN, "lq_fq_backward_clip: ds is not 4-byte aligned");
+    if (clipped && !aligned(clipped, 4)) return fail(LQ_EALIGN, "lq_fq_backward_clip: clipped is not 4-byte aligned");
+    if ((rc = check_clip_range(__func__, qmin, qmax))) return rc;
+    Plan pl = make_plan(outer, G, inner, kBlock);      // generic traversal bodies, as lq_fq_scale_grad_ste
+    Params p = base_params(P, s, outer, G, inner);
+    p.dy = dy;
+    p.out = dP;
+    p.c_scale = grad_scale;
+    p.clip_lo = (float)qmin;
+    p.clip_hi = (float)qmax;
+    // the workspace is required, and checked, also for "mask only" calls: one kernel serves both, the sum is dropped at the emit
+    if (!ws || ws_bytes < ws_bytes_for(pl)) return fail(LQ_EINVAL, "lq_fq_backward_clip: workspace %s (%zu bytes given, %zu needed)",
+                                                        ws ? "too small" : "is NULL", ws ? ws_bytes : (size_t)0, ws_bytes_for(pl));
+    if ((rc = bind_ws(p, pl, ws, ws_bytes))) return rc;
+    const bool direct = pl.n1 * pl.n2 == 1;      // one partial per group: the traversal emits ds and the count itself
+    if (direct) {
+        p.direct = 1;
+        p.e0 = ds;
+        p.e1 = reinterpret_cast<float*>(clipped);      // emit_direct<OP_CLIP_BWD> hands it on as FinGeom::o2
+        p.ecount = (double)outer * (double)inner;
+    }
+    if ((rc = launch_traverse<OP_CLIP_BWD>(pl, p, (hipStream_t)stream))) return rc;
+    if (direct || (!ds && !clipped)) return LQ_OK;
+    FinGeom f = group_geom(pl, outer, G, inner);
+    f.o0 = ds;
+    f.o2 = clipped;
+    return launch_finalize<OP_CLIP_BWD>(p, f, (hipStream_t)stream);
 }
 
 int lq_fq_fwd_bwd_fused(const float* P, const float* s, const float* dy, float lambda, float* out, float* ds, void* ws,

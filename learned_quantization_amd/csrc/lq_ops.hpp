@@ -347,6 +347,104 @@ struct OpT<OP_STE_SCALE> : OpBase {
     }
 };
 
+// Clipped b-bit fake-quant (lq_hip.h: lq_fq_forward_clip / lq_fq_backward_clip).  lo = (float)qmin and hi = (float)qmax travel in
+// Ctx::k0 / k1 (Params::clip_lo / clip_hi).  The quotient is K1's (div_by_uniform, fq_quot4, fq_quot4c); the clamp is two
+// comparisons and two selects, not fmin / fmax: a NaN floor stays NaN, +-Inf saturates.
+struct ClipBase : OpBase {
+    __device__ static __forceinline__ Ctx ctx(const Params& p, int64_t g) {
+        Ctx c;
+        c.s = p.s[g];
+        div_ctx(c);
+        c.k0 = p.clip_lo;
+        c.k1 = p.clip_hi;
+        c.lam_hi = 0.f;
+        c.sure_ok = 0;
+        return c;
+    }
+    __device__ static __forceinline__ float clampq(float q0, float lo, float hi) { return q0 < lo ? lo : (q0 > hi ? hi : q0); }
+};
+
+template <>
+struct OpT<OP_CLIP_FWD> : ClipBase {
+    static constexpr bool kStore = true;
+    __device__ static __forceinline__ void side4(const Params& p, int64_t i, const float4& q) {      // one test per float4, as FwdOp
+        if (p.q) {
+            store_q(p.q, p.q_dtype, i + 0, q.x);
+            store_q(p.q, p.q_dtype, i + 1, q.y);
+            store_q(p.q, p.q_dtype, i + 2, q.z);
+            store_q(p.q, p.q_dtype, i + 3, q.w);
+        }
+    }
+    __device__ static __forceinline__ float elem(const Params& p, const Ctx& c, int64_t i, float x, float, Acc&) {
+        const float q = clampq(floorf(div_by_uniform(x, c)), c.k0, c.k1);
+        if (p.q) store_q(p.q, p.q_dtype, i, q);
+        return q * c.s;
+    }
+    static constexpr bool kVec4 = true;
+    __device__ static __forceinline__ float4 elem4(const Params& p, const Ctx& c, int64_t i, const float4& x, const float4&, Acc&) {
+        const float4 t = fq_quot4(x, c);
+        float4 q, o;
+        q.x = clampq(floorf(t.x), c.k0, c.k1); q.y = clampq(floorf(t.y), c.k0, c.k1);
+        q.z = clampq(floorf(t.z), c.k0, c.k1); q.w = clampq(floorf(t.w), c.k0, c.k1);
+        o.x = q.x * c.s; o.y = q.y * c.s; o.z = q.z * c.s; o.w = q.w * c.s;
+        side4(p, i, q);
+        return o;
+    }
+    static constexpr bool kVec4c = true;
+    __device__ static __forceinline__ float4 elem4c(const Params& p, const Ctx* c, int64_t i, const float4& x, const float4&, Acc*) {
+        const float4 t = fq_quot4c(x, c);
+        float4 q, o;
+        q.x = clampq(floorf(t.x), c[0].k0, c[0].k1); q.y = clampq(floorf(t.y), c[1].k0, c[1].k1);
+        q.z = clampq(floorf(t.z), c[2].k0, c[2].k1); q.w = clampq(floorf(t.w), c[3].k0, c[3].k1);
+        o.x = q.x * c[0].s; o.y = q.y * c[1].s; o.z = q.z * c[2].s; o.w = q.w * c[3].s;
+        side4(p, i, q);
+        return o;
+    }
+};
+
+// Backward: the value returned (stored by the traversal in the primary dense output) is dP.  acc.c carries sum dy * r in f64
+// from the first addition (r = floor(t) - t inside the range, ONE fp32 subtraction as OP_STE_SCALE; the bound lo or hi
+// outside; NaN for a NaN floor), acc.b the number of elements outside the range (a NaN floor counts); the standard merge adds
+// both.  The factor k (Params::c_scale) is applied once per group by FinT::emit.  As for OP_STE_SCALE the terms have no
+// common quantum: different traversals may differ in the last bit of ds, each one is run-to-run bit-stable.
+template <>
+struct OpT<OP_CLIP_BWD> : ClipBase {
+    static constexpr bool kDy = true;
+    static constexpr bool kStore = true;
+    static constexpr bool kReduce = true;
+    __device__ static __forceinline__ float one(float t, float dy, float lo, float hi, Acc& acc) {
+        const float q0 = floorf(t);
+        const bool inside = (q0 >= lo) & (q0 <= hi);           // false for NaN
+        const float r = inside ? q0 - t : clampq(q0, lo, hi);
+        acc.c += (double)dy * (double)r;
+        acc.b += inside ? 0u : 1u;
+        return inside ? dy : 0.f;
+    }
+    __device__ static __forceinline__ float elem(const Params&, const Ctx& c, int64_t, float x, float dy, Acc& acc) {
+        return one(div_by_uniform(x, c), dy, c.k0, c.k1, acc);
+    }
+    static constexpr bool kVec4 = true;
+    __device__ static __forceinline__ float4 elem4(const Params&, const Ctx& c, int64_t, const float4& x, const float4& dy, Acc& acc) {
+        const float4 t = fq_quot4(x, c);
+        float4 o;
+        o.x = one(t.x, dy.x, c.k0, c.k1, acc);
+        o.y = one(t.y, dy.y, c.k0, c.k1, acc);
+        o.z = one(t.z, dy.z, c.k0, c.k1, acc);
+        o.w = one(t.w, dy.w, c.k0, c.k1, acc);
+        return o;
+    }
+    static constexpr bool kVec4c = true;
+    __device__ static __forceinline__ float4 elem4c(const Params&, const Ctx* c, int64_t, const float4& x, const float4& dy, Acc* acc) {
+        const float4 t = fq_quot4c(x, c);
+        float4 o;
+        o.x = one(t.x, dy.x, c[0].k0, c[0].k1, acc[0]);
+        o.y = one(t.y, dy.y, c[1].k0, c[1].k1, acc[1]);
+        o.z = one(t.z, dy.z, c[2].k0, c[2].k1, acc[2]);
+        o.w = one(t.w, dy.w, c[3].k0, c[3].k1, acc[3]);
+        return o;
+    }
+};
+
 }  // namespace lq
 
 #endif

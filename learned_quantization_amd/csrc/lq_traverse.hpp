@@ -686,6 +686,17 @@ struct FinT<OP_STE_SCALE> {
     }
 };
 
+// ds[g] = (float)(k * sum) and the exact clip count; either output may be absent ("mask only": the sum is dropped here)
+template <>
+struct FinT<OP_CLIP_BWD> {
+    __device__ static float emit(const Params& p, const FinGeom& f, int64_t g, const AccW& a) {
+        const float ds = (float)((double)p.c_scale * a.c);
+        if (f.o0) f.o0[g] = ds;
+        if (f.o2) f.o2[g] = (uint32_t)(a.b > 4294967295.0 ? 4294967295.0 : a.b);
+        return ds;
+    }
+};
+
 template <int OP>
 __device__ __forceinline__ void emit_direct(const Params& p, int64_t g, const Acc& acc) {
     FinGeom f;
@@ -695,6 +706,7 @@ __device__ __forceinline__ void emit_direct(const Params& p, int64_t g, const Ac
     f.o0 = p.e0;
     f.o1 = p.e1;
     f.o2 = nullptr;
+    if constexpr (OP == OP_CLIP_BWD) f.o2 = reinterpret_cast<uint32_t*>(p.e1);      // clipped[G] travels in the e1 slot
     f.accum = 0;
     AccW w;
     w.a = acc.a;

@@ -215,6 +215,9 @@ class DataParallel:
                  overlap: bool = True, force_collectives: bool = False):
         if mode not in ("A", "B"):
             raise ValueError("mode must be 'A' or 'B'")
+        if mode == "B" and any(getattr(m, "q_range", None) is not None for m in module.modules()):
+            raise ValueError("mode 'B' over a clipped layer (bits / q_range): it recomputes ds from the all-reduced dP, which no longer "
+                             "holds the dy of the clipped elements; use mode 'A' (the gradients are ordinary tensors)")
         self.module = module
         self.mode = mode
         self.group = group

@@ -119,6 +119,9 @@ def main(argv=None):
     ap.add_argument("--scale-gradient", default=None, choices=["ste"],
                     help="the straight-through scale gradient instead of the nested-quantization vote (with --custom_loss: next to "
                          "the loss term)")
+    ap.add_argument("--bits", type=int, default=None,
+                    help="clipped b-bit quantizer (signed, integers in [-2^(b-1), 2^(b-1) - 1]); needs --scale-gradient ste or "
+                         "--custom_loss")
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--steps-per-epoch", type=int, default=10)
     ap.add_argument("--batch", type=int, default=128)
@@ -148,7 +151,7 @@ def main(argv=None):
 
     tr = Trainer(args.config, mode, value, args.orientation, args.custom_loss, lr=args.lr, seed=args.seed, device=dev,
                  log_dir=log_dir, batched=args.batched, loss_values=args.loss_values,
-                 loss_log_capacity=max(4096, args.steps_per_epoch))
+                 loss_log_capacity=max(4096, args.steps_per_epoch), bits=args.bits)
     if args.training == "post_training":
         if args.config != "mnist" or not args.baseline_weights:
             raise SystemExit("post_training needs --config mnist --baseline-weights <npz with W1,b1,W2,b2> "

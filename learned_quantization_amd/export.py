@@ -52,8 +52,19 @@ def quantized_tensors(model: torch.nn.Module) -> List[Tuple[str, torch.nn.Parame
 
 
 def quantized_state(model: torch.nn.Module) -> Dict[str, np.ndarray]:
-    return {name: _host(ops.quantized_integers(param.data, nested.scale.data, torch.int8))
+    # a layer with an integer range exports the CLAMPED integers (nested.quantized_integers): inside the range whatever
+    # floor(P/s) is, so int8 cannot wrap for bits <= 8; a layer without one exports floor(P/s) as before
+    return {name: _host(nested.quantized_integers(param.data, torch.int8))
             for name, param, nested in quantized_tensors(model)}
+
+
+def _pack_source(param: torch.nn.Parameter, nested: CustomQuantizedScaleLayer):
+    """(P, s) whose floor(P/s) is the integer the layer's quantizer produces.  Without a range: the parameter and its scale.  With
+    one: the clamped integers themselves as floats over a unit scale (floor(q / 1) == q exactly, |q| <= 2^24), so that the range
+    scan and the packer see no integer outside the range even where floor(P/s) lies outside."""
+    if getattr(nested, "q_range", None) is None:
+        return param.data, nested.scale.data
+    return nested.quantized_integers(param.data, torch.float32), torch.ones_like(nested.scale.data)
 
 
 def scale_state(model: torch.nn.Module) -> Dict[str, np.ndarray]:
@@ -118,8 +129,9 @@ def save_packed_parameters(model: torch.nn.Module, log_dir: str) -> Dict[str, fl
         raise ValueError("the model has no quantized tensor to pack")
     dev = tensors[0][1].device
     ranges = torch.empty((len(tensors), 2), dtype=torch.int32, device=dev)
-    for k, (_, param, nested) in enumerate(tensors):
-        ops.q_minmax(param.data, nested.scale.data, out=ranges[k])
+    sources = [_pack_source(param, nested) for _, param, nested in tensors]
+    for k, (src, unit) in enumerate(sources):
+        ops.q_minmax(src, unit, out=ranges[k])
     lohi = ranges.tolist()                                      # every range in one device->host copy
     entries = []
     for (name, param, nested), (lo, hi) in zip(tensors, lohi):
@@ -129,8 +141,8 @@ def save_packed_parameters(model: torch.nn.Module, log_dir: str) -> Dict[str, fl
                         "orientation": nested.orientation, "qmin": int(lo), "bits": int(hi - lo).bit_length(),
                         "numel": int(param.numel())})
     bad = torch.zeros(len(tensors), dtype=torch.int64, device=dev)
-    words = [ops.q_pack(param.data, nested.scale.data, qmin=e["qmin"], bits=e["bits"], bad=bad[k:k + 1])[0]
-             for k, ((_, param, nested), e) in enumerate(zip(tensors, entries))]
+    words = [ops.q_pack(src, unit, qmin=e["qmin"], bits=e["bits"], bad=bad[k:k + 1])[0]
+             for k, ((src, unit), e) in enumerate(zip(sources, entries))]
     for e, nbad in zip(entries, bad.tolist()):
         if nbad:
             raise ValueError(f"{e['name']}: {nbad} elements of floor(P/s) are NaN, Inf or beyond int32: cannot pack it")

@@ -129,6 +129,9 @@ class CustomQuantizedScaleLayer(nn.Module):
     ``scale_gradient="ste"`` (not in the reference; only without ``penalty_threshold``) -> the scale also receives the
     straight-through gradient ``grad_scale * sum dy * (floor(P/s) - P/s)`` (ops.fq_scale_grad_ste); ``grad_scale`` is a
     float or ``"rsqrt_group"`` = 1 / sqrt(elements per group).
+    ``bits`` / ``signed`` or ``q_range=(qmin, qmax)`` (not in the reference; only without ``penalty_threshold``) -> the clipped
+    quantizer (ops.fq_forward_clip / fq_backward_clip): integers saturate at [-2^(b-1), 2^(b-1) - 1] (signed) or [0, 2^b - 1],
+    clipped elements pass no gradient to the parameter and, with ``scale_gradient="ste"``, pull the scale towards covering them.
     """
 
     _SCALE_NAMES = {"rowwise": "Rowwise-scaler", "columnwise": "Columnwise-scaler",
@@ -136,8 +139,12 @@ class CustomQuantizedScaleLayer(nn.Module):
                     "scalar": "Scalar-scaler"}
 
     def __init__(self, penalty_threshold=None, initializer=None, orientation="scalar", *, penalty_rate=None,
-                 scale_gradient=None, grad_scale=1.0):
+                 scale_gradient=None, grad_scale=1.0, bits=None, signed=True, q_range=None):
         super().__init__()
+        self.q_range = ops.q_range_of(bits, signed, q_range)
+        if self.q_range is not None and penalty_threshold is not None:
+            raise ValueError("a clipped layer (bits / q_range) needs penalty_threshold=None: the nested-quantization vote is "
+                             "defined on the unclipped quantizer")
         if scale_gradient not in ops.SCALE_GRADIENTS:
             raise ValueError(f"scale_gradient must be one of {ops.SCALE_GRADIENTS}, got {scale_gradient!r}")
         if scale_gradient == "ste" and penalty_threshold is not None:
@@ -177,6 +184,10 @@ class CustomQuantizedScaleLayer(nn.Module):
     def call(self, inputs):
         if not self.built:
             self.build(tuple(inputs.shape), device=inputs.device)
+        if self.q_range is not None:
+            return ops.my_custom_gradient(inputs, self.scale, self.penalty_threshold, scale_gradient=self.scale_gradient,
+                                          grad_scale=self.grad_scale_value(inputs.numel()) if self.scale_gradient == "ste" else 1.0,
+                                          defer_scale_grad=self.defer_scale_grad, q_range=self.q_range)
         if self.scale_gradient == "ste":
             return ops.my_custom_gradient(inputs, self.scale, scale_gradient="ste", grad_scale=self.grad_scale_value(inputs.numel()),
                                           defer_scale_grad=self.defer_scale_grad)
@@ -191,13 +202,21 @@ class CustomQuantizedScaleLayer(nn.Module):
         r = f"orientation={self.orientation!r}, penalty_threshold={self.penalty_threshold}, penalty_rate={self.penalty_rate}"
         if self.scale_gradient is not None:
             r += f", scale_gradient={self.scale_gradient!r}, grad_scale={self.grad_scale!r}"
+        if self.q_range is not None:
+            r += f", q_range={self.q_range!r}"
         return r
 
+    def quantized_integers(self, parameter, dtype=torch.float32):
+        """The integer view of ``parameter`` under this layer's quantizer: floor(P/s), clamped when the layer has a range."""
+        if self.q_range is None:
+            return ops.quantized_integers(parameter, self.scale.data, dtype)
+        return ops.fq_forward_clip(parameter, self.scale.data, *self.q_range, q_dtype=dtype)[1]
 
-def _nested(penalty_threshold, penalty_rate, orientation, scale_gradient=None, grad_scale=1.0):
+
+def _nested(penalty_threshold, penalty_rate, orientation, scale_gradient=None, grad_scale=1.0, q_range=None):
     return CustomQuantizedScaleLayer(penalty_threshold=penalty_threshold, initializer=None,
                                      orientation=orientation, penalty_rate=penalty_rate,
-                                     scale_gradient=scale_gradient, grad_scale=grad_scale)
+                                     scale_gradient=scale_gradient, grad_scale=grad_scale, q_range=q_range)
 
 
 def _as_tensor(a, shape, device):
@@ -208,6 +227,11 @@ def _as_tensor(a, shape, device):
 
 
 class _HostLayer(nn.Module):
+    q_range = None
+
+    def extra_repr(self):
+        return f"q_range={self.q_range!r}" if self.q_range is not None else ""
+
     def _init_value(self, initializer, shape, device):
         if initializer is None:
             raise ValueError("initializer is required when trained_weights is not given")
@@ -232,11 +256,12 @@ class CustomDenseLayer(_HostLayer):
 
     def __init__(self, seed=None, units=None, penalty_threshold=None, orientation="scalar", initializer=None,
                  name=None, regularizer=None, trained_weights=None, *, penalty_rate=None, input_shape=None,
-                 device=None, scale_gradient=None, grad_scale=1.0, **kwargs):
+                 device=None, scale_gradient=None, grad_scale=1.0, bits=None, signed=True, q_range=None, **kwargs):
         super().__init__()
         self.seed = seed
-        self.nested_q_w_layer = _nested(penalty_threshold, penalty_rate, orientation, scale_gradient, grad_scale)   # NQ-L:222-224
-        self.nested_q_b_layer = _nested(penalty_threshold, penalty_rate, "scalar", scale_gradient, grad_scale)      # NQ-L:225-227
+        self.q_range = ops.q_range_of(bits, signed, q_range)      # None: the reference's unbounded quantizer
+        self.nested_q_w_layer = _nested(penalty_threshold, penalty_rate, orientation, scale_gradient, grad_scale, self.q_range)   # NQ-L:222-224
+        self.nested_q_b_layer = _nested(penalty_threshold, penalty_rate, "scalar", scale_gradient, grad_scale, self.q_range)      # NQ-L:225-227
         self.units = units
         self.initializer = initializer
         self.regularizer = regularizer
@@ -324,17 +349,18 @@ class _ConvBase(_HostLayer):
     def __init__(self, seed=None, penalty_threshold=None, orientation="scalar", initializer=None, filters=None,
                  kernel_size=(3, 3), strides=(1, 1), padding="same", name=None, regularizer=None,
                  trained_weights=None, *, penalty_rate=None, input_shape=None, data_format="NCHW", device=None,
-                 kernel_storage=None, scale_gradient=None, grad_scale=1.0, **kwargs):
+                 kernel_storage=None, scale_gradient=None, grad_scale=1.0, bits=None, signed=True, q_range=None, **kwargs):
         super().__init__()
         self.seed = seed
+        self.q_range = ops.q_range_of(bits, signed, q_range)      # None: the reference's unbounded quantizer
         if kernel_storage is None:
             kernel_storage = _KERNEL_STORAGE[-1]
         if kernel_storage not in ("oihw", "hwio"):
             raise ValueError("kernel_storage must be 'oihw' or 'hwio'")
         self.kernel_storage = kernel_storage
-        self.nested_q_k_layer = _nested(penalty_threshold, penalty_rate, orientation, scale_gradient, grad_scale)      # NQ-L:293-295
+        self.nested_q_k_layer = _nested(penalty_threshold, penalty_rate, orientation, scale_gradient, grad_scale, self.q_range)      # NQ-L:293-295
         if self._has_bias:
-            self.nested_q_b_layer = _nested(penalty_threshold, penalty_rate, "scalar", scale_gradient, grad_scale)     # NQ-L:296-298
+            self.nested_q_b_layer = _nested(penalty_threshold, penalty_rate, "scalar", scale_gradient, grad_scale, self.q_range)     # NQ-L:296-298
         self.initializer = initializer
         self.filters = filters
         self.kernel_size = _pair(kernel_size)

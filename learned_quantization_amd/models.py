@@ -22,6 +22,8 @@ carries its logits (``losses.softmax``), from which the cross-entropy is compute
 ``mode="cl"``: ``value`` is the penalty_rate (STE-only op; scales learn through a custom loss term);
 ``mode="ste"``: the straight-through scale gradient (ops.fq_scale_grad_ste), no loss term, ``value`` is ignored;
 ``mode="stecl"``: the same plus a custom loss term, ``value`` is the penalty_rate.
+``bits`` / ``signed`` / ``q_range`` (``build_model``; modes "cl", "ste", "stecl"): every quantised tensor uses the clipped
+quantizer with that integer range (layers.py).
 """
 from __future__ import annotations
 
@@ -268,10 +270,32 @@ class ResNet50Like(nn.Module):
         return softmax(self.out(torch.mean(x, dim=(2, 3))), dim=1)
 
 
-def build_model(config: str, kernel_storage: str = None, grad_scale=None, **kw) -> nn.Module:
+CLIP_MODES = ("cl", "ste", "stecl")
+
+
+def check_clip_mode(mode: str) -> None:
+    """A model with an integer range needs a mode without the nested-quantization vote."""
+    if mode not in CLIP_MODES:
+        raise ValueError(f"bits / q_range with mode {mode!r}: the nested-quantization vote is defined on the unclipped quantizer; "
+                         f"a clipped model needs one of the modes {CLIP_MODES}")
+
+
+def build_model(config: str, kernel_storage: str = None, grad_scale=None, bits=None, signed=True, q_range=None, **kw) -> nn.Module:
     """config: 'mnist' (C1), 'cifar' (C2/C4), 'imagenette' (C3), 'resnet50' (C5, extension).
     ``kernel_storage``: memory order of the conv kernels, "oihw" (default) or "hwio" (layers.py).
-    ``grad_scale`` (modes "ste" / "stecl"): factor of every straight-through scale gradient, a float or "rsqrt_group"."""
+    ``grad_scale`` (modes "ste" / "stecl"): factor of every straight-through scale gradient, a float or "rsqrt_group".
+    ``bits`` (1..24) with ``signed``, or ``q_range=(qmin, qmax)`` (modes "cl" / "ste" / "stecl"): the integer range of every
+    quantised tensor, carried by the host layers and both of their nested layers."""
+    if bits is not None or q_range is not None:
+        from .layers import CustomQuantizedScaleLayer, _HostLayer
+        from .ops import q_range_of
+        rng = q_range_of(bits, signed, q_range)
+        check_clip_mode(kw.get("mode", "nq"))
+        model = build_model(config, kernel_storage=kernel_storage, grad_scale=grad_scale, **kw)
+        for m in model.modules():
+            if isinstance(m, (CustomQuantizedScaleLayer, _HostLayer)):
+                m.q_range = rng
+        return model
     if grad_scale is not None:
         from .layers import CustomQuantizedScaleLayer
         model = build_model(config, kernel_storage=kernel_storage, **kw)

@@ -6,8 +6,8 @@
   * 2-argument form ``(parameter, scale)`` = STE-only op
     /root/reference/CIFAR-10/custom_loss_terms/custom_components/custom_layers.py:49-64
 
-Raw (non-autograd) wrappers ``fq_forward``, ``fq_scale_grad``, ``fq_scale_grad_ste``, ``fq_fwd_bwd_fused``,
-``quantized_integers`` ... are thin: argument checking + one C-ABI call each.
+Raw (non-autograd) wrappers ``fq_forward``, ``fq_scale_grad``, ``fq_scale_grad_ste``, ``fq_forward_clip``,
+``fq_backward_clip``, ``fq_fwd_bwd_fused``, ``quantized_integers`` ... are thin: argument checking + one C-ABI call each.
 Everything runs on the HIP device; there is no CPU fallback.
 """
 from __future__ import annotations
@@ -97,6 +97,76 @@ def fq_scale_grad_ste(parameter: torch.Tensor, scale: torch.Tensor, dy: torch.Te
                                         _hip.ptr(ws), ws.numel(), outer, G, inner, _hip.stream_ptr(p.device)),
                "lq_fq_scale_grad_ste")
     return ds
+
+
+Q_LIMIT = 1 << 24      # integers up to 2^24 in magnitude are exact in fp32
+
+
+def check_q_range(qmin, qmax) -> Tuple[int, int]:
+    """(qmin, qmax) as ints, or ValueError: qmin <= qmax, both inside +-2^24 (include/lq_hip.h, clipped fake-quant)."""
+    if int(qmin) != qmin or int(qmax) != qmax:
+        raise ValueError(f"q_range must be two integers, got ({qmin!r}, {qmax!r})")
+    qmin, qmax = int(qmin), int(qmax)
+    if qmin > qmax:
+        raise ValueError(f"q_range needs qmin <= qmax, got ({qmin}, {qmax})")
+    if qmin < -Q_LIMIT or qmax > Q_LIMIT:
+        raise ValueError(f"q_range ({qmin}, {qmax}) is outside +-2^24, the integers fp32 holds exactly")
+    return qmin, qmax
+
+
+def q_range_of(bits=None, signed=True, q_range=None) -> Optional[Tuple[int, int]]:
+    """The integer range of a layer: ``bits`` = b gives [-2^(b-1), 2^(b-1) - 1] (signed) or [0, 2^b - 1] (unsigned), 1 <= b <= 24;
+    ``q_range`` = (qmin, qmax) gives it directly; neither gives None (the unbounded quantizer).  Both together are an error."""
+    if bits is not None and q_range is not None:
+        raise ValueError("give bits or q_range, not both")
+    if q_range is not None:
+        if len(tuple(q_range)) != 2:
+            raise ValueError(f"q_range must be (qmin, qmax), got {q_range!r}")
+        return check_q_range(*q_range)
+    if bits is None:
+        return None
+    if int(bits) != bits or not 1 <= int(bits) <= 24:
+        raise ValueError(f"bits must be an integer in 1..24, got {bits!r}")
+    b = int(bits)
+    return (-(1 << (b - 1)), (1 << (b - 1)) - 1) if signed else (0, (1 << b) - 1)
+
+
+def fq_forward_clip(parameter: torch.Tensor, scale: torch.Tensor, qmin: int, qmax: int, q_dtype: Optional[torch.dtype] = None):
+    """Clipped forward (include/lq_hip.h, lq_fq_forward_clip): out = clamp(floor(P/s), qmin, qmax) * s.  Returns ``out``, or
+    ``(out, q)`` with the clamped integers when ``q_dtype`` is given."""
+    qmin, qmax = check_q_range(qmin, qmax)
+    lib = _hip.load()
+    p, s, (outer, G, inner) = _param(parameter, scale)
+    out = torch.empty_like(p)
+    q = None
+    qd = _hip.LQ_Q_NONE
+    if q_dtype is not None:
+        if q_dtype not in _QDTYPES:
+            raise TypeError(f"q_dtype must be one of {list(_QDTYPES)}, got {q_dtype}")
+        q = torch.empty_like(p, dtype=q_dtype)
+        qd = _QDTYPES[q_dtype]
+    _hip.check(lib.lq_fq_forward_clip(_hip.ptr(p), _hip.ptr(s), _hip.ptr(out), _hip.ptr(q), qd, qmin, qmax,
+                                      outer, G, inner, _hip.stream_ptr(p.device)), "lq_fq_forward_clip")
+    return out if q is None else (out, q)
+
+
+def fq_backward_clip(parameter: torch.Tensor, scale: torch.Tensor, dy: torch.Tensor, qmin: int, qmax: int,
+                     grad_scale: float = 1.0, want_ds: bool = True, want_clipped: bool = False):
+    """Clipped backward (include/lq_hip.h, lq_fq_backward_clip).  Returns ``(dP, ds, clipped)``: dP = dy inside the range and +0
+    outside, with the parameter's strides; ds (shape of scale; None unless ``want_ds``) = grad_scale * sum dy * r; clipped
+    (int32 tensor holding the uint32 counts per group, shape of scale; None unless ``want_clipped``)."""
+    qmin, qmax = check_q_range(qmin, qmax)
+    lib = _hip.load()
+    p, s, (outer, G, inner) = _param(parameter, scale)
+    d = _hip.require_device_f32(dy, "dy", like=p)
+    dP = torch.empty_like(p)
+    ds = torch.empty_like(s) if want_ds else None
+    clipped = torch.empty_like(s, dtype=torch.int32) if want_clipped else None
+    ws = _hip.workspace_for(p.device, outer, G, inner)
+    _hip.check(lib.lq_fq_backward_clip(_hip.ptr(p), _hip.ptr(s), _hip.ptr(d), qmin, qmax, float(grad_scale), _hip.ptr(dP),
+                                       _hip.ptr(ds), _hip.ptr(clipped), _hip.ptr(ws), ws.numel(), outer, G, inner,
+                                       _hip.stream_ptr(p.device)), "lq_fq_backward_clip")
+    return dP, ds, clipped
 
 
 def fq_fwd_bwd_fused(parameter: torch.Tensor, scale: torch.Tensor, dy: torch.Tensor, penalty_threshold: float,
@@ -432,18 +502,54 @@ class _STEScaleQuantFn(torch.autograd.Function):
         return (dy if ctx.needs_input_grad[0] else None), ds, None, None
 
 
+class _ClipQuantFn(torch.autograd.Function):
+    """The clipped pair: forward lq_fq_forward_clip, backward lq_fq_backward_clip.  ``want_ds``: the scale receives the LSQ
+    gradient (scale_gradient="ste"); otherwise zeros like the STE-only op (the loss-term-only rule) and the kernel's sum is
+    dropped."""
+
+    @staticmethod
+    def forward(ctx, parameter, scale, qmin, qmax, grad_scale, want_ds):
+        ctx.save_for_backward(parameter, scale)
+        ctx.q_range = (int(qmin), int(qmax))
+        ctx.grad_scale = float(grad_scale)
+        ctx.want_ds = bool(want_ds)
+        return fq_forward_clip(parameter, scale, qmin, qmax)
+
+    @staticmethod
+    def backward(ctx, dy):
+        parameter, scale = ctx.saved_tensors
+        want_ds = ctx.want_ds and ctx.needs_input_grad[1]
+        dP, ds, _ = fq_backward_clip(parameter, scale, dy, *ctx.q_range, grad_scale=ctx.grad_scale, want_ds=want_ds)
+        if ds is None and ctx.needs_input_grad[1]:
+            ds = torch.zeros_like(scale)
+        return (dP if ctx.needs_input_grad[0] else None), ds, None, None, None, None
+
+
 SCALE_GRADIENTS = (None, "ste")
 
 
-def my_custom_gradient(parameter, scale, penalty_threshold=None, *, scale_gradient=None, grad_scale=1.0, defer_scale_grad=False):
+def my_custom_gradient(parameter, scale, penalty_threshold=None, *, scale_gradient=None, grad_scale=1.0, defer_scale_grad=False,
+                       q_range=None):
     """The reference op.  With ``penalty_threshold`` -> nested-quantization variant
     (custom_layers.py:49-120); without -> STE-only variant (CL custom_layers.py:49-64).
     ``scale_gradient="ste"`` (not in the reference, only without ``penalty_threshold``): the scale receives the
     straight-through gradient ``grad_scale * sum dy * (floor(P/s) - P/s)`` instead of zeros.
     ``defer_scale_grad`` (not in the reference): backward returns dP only; the caller computes ds later from the
-    all-reduced dP (exact data-parallel mode, ddp.py)."""
+    all-reduced dP (exact data-parallel mode, ddp.py).
+    ``q_range=(qmin, qmax)`` (not in the reference, only without ``penalty_threshold``): the clipped quantizer -- integers
+    saturate at the range, clipped elements pass no gradient to ``parameter``; with ``scale_gradient="ste"`` the scale gets the
+    LSQ gradient (clipped elements pull it by ``dy * qmin`` / ``dy * qmax``), with ``None`` it gets zeros."""
     if scale_gradient not in SCALE_GRADIENTS:
         raise ValueError(f"scale_gradient must be one of {SCALE_GRADIENTS}, got {scale_gradient!r}")
+    if q_range is not None:
+        if penalty_threshold is not None:
+            raise ValueError("q_range with a penalty_threshold: the nested-quantization vote is defined on the unclipped "
+                             "quantizer; a clipped layer needs penalty_threshold=None")
+        if defer_scale_grad:
+            raise ValueError("q_range with defer_scale_grad: the all-reduced dP of a clipped layer no longer holds the dy of its "
+                             "clipped elements, so ds cannot be recomputed from it")
+        qmin, qmax = check_q_range(*q_range)
+        return _ClipQuantFn.apply(parameter, scale, qmin, qmax, float(grad_scale), scale_gradient == "ste")
     if scale_gradient == "ste":
         if penalty_threshold is not None:
             raise ValueError('scale_gradient="ste" replaces the nested-quantization vote: it needs penalty_threshold=None')

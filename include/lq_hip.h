@@ -130,6 +130,20 @@ int lq_fq_backward_clip(const float* P, const float* s, const float* dy, int32_t
                         float* dP, float* ds /* may be NULL */, uint32_t* clipped /* may be NULL */,
                         void* ws, size_t ws_bytes, int64_t outer, int64_t G, int64_t inner, void* stream);
 
+/* ---- the clipped pair with a choice of rounding ----
+ * `rounding` replaces the floorf of q0 above: LQ_ROUND_FLOOR runs exactly what lq_fq_forward_clip / lq_fq_backward_clip run (those
+ * two forward here); LQ_ROUND_NEAREST_EVEN takes q0 = rintf(t), round half to even (|t| >= 2^23 gives q0 == t).  Everything else in
+ * the definition reads the same with that q0: r = q0 - t is then in [-1/2, 1/2]; t = qmax + 1/2 rounds to qmax + 1 when qmax is
+ * odd and is clipped, t = qmin - 1/2 rounds to qmin when qmin is even and is inside; P in [-s/2, 0) gives q0 = -0.0, out keeps
+ * the sign (-0.0 * s) and the integer outputs store 0.  The nearest pair has kernels of its own (the rounding is a compile-time
+ * parameter of the op trait).  Any other `rounding` returns LQ_EINVAL before any launch; every other rule is the floor pair's. */
+typedef enum lq_rounding { LQ_ROUND_FLOOR = 0, LQ_ROUND_NEAREST_EVEN = 1 } lq_rounding;
+int lq_fq_forward_clip_r(const float* P, const float* s, float* out, void* q, int q_dtype,
+                         int32_t qmin, int32_t qmax, int rounding, int64_t outer, int64_t G, int64_t inner, void* stream);
+int lq_fq_backward_clip_r(const float* P, const float* s, const float* dy, int32_t qmin, int32_t qmax, int rounding, float grad_scale,
+                          float* dP, float* ds /* may be NULL */, uint32_t* clipped /* may be NULL */,
+                          void* ws, size_t ws_bytes, int64_t outer, int64_t G, int64_t inner, void* stream);
+
 /* ---- K4: forward and NQ backward of one tensor in a single pass (benchmark path) ---
  * Same results as lq_fq_forward followed by lq_fq_scale_grad (out, max|q| and the vote count bit for bit; on
  * streaming-size tensors the vote sum may differ by fp32 summation order, ~1e-7 relative); P is read once.  */

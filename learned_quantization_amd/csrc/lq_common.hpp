@@ -36,7 +36,7 @@ struct Params {
     int q_dtype;
     float lam;
     int tmode;           // 0: lambda < 4e-4 (tanh(d) == d), 1: lambda <= 0.25 (polynomial), 2: general (ocml tanhf)
-    float clip_lo;       // OP_CLIP_FWD / OP_CLIP_BWD: (float)qmin (this word and clip_hi below sit where alignment padding was: no
+    float clip_lo;       // OP_CLIP_* (floor and nearest pair): (float)qmin (this word and clip_hi below sit where alignment padding was: no
                          // other field moves and the struct keeps its size, so the other kernels' argument offsets stay)
     const float* mb;     // per-group max(|P|/s)      (maxbin backward)
     const uint32_t* ties;
@@ -50,7 +50,7 @@ struct Params {
     // direct emit (scale-gradient ops whose groups have exactly one partial: biases, row-wise Dense, one row per group):
     // the traversal writes the op's outputs itself and the finalize launch is skipped
     int direct;
-    float clip_hi;       // OP_CLIP_FWD / OP_CLIP_BWD: (float)qmax
+    float clip_hi;       // OP_CLIP_*: (float)qmax
     float* e0;           // ds[G]
     float* e1;           // optional parts[3*G]
     double ecount;       // elements per group
@@ -123,6 +123,8 @@ enum OpKind {
     OP_STE_SCALE = 11,  // straight-through scale gradient: ds[g] = k * sum dy * (floor(P/s) - P/s)
     OP_CLIP_FWD = 12,   // clipped forward: out = clamp(floor(P/s), qmin, qmax) * s
     OP_CLIP_BWD = 13,   // clipped backward: dP = inside ? dy : 0, ds[g] = k * sum dy * r, clipped[g] = #{!inside}
+    OP_CLIP_FWD_RNE = 14,   // OP_CLIP_FWD with rintf (round half to even) in place of floorf, a compile-time parameter of the trait
+    OP_CLIP_BWD_RNE = 15,   // OP_CLIP_BWD with rintf: r = rint(t) - t in [-1/2, 1/2]
 };
 
 }  // namespace lq

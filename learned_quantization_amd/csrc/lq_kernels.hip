@@ -3,7 +3,7 @@
 //
 //   lq_common.hpp       constants, kernel parameter block, accumulator types
 //   lq_math.hpp         exact fp32 arithmetic: uniform-divisor division, in-window ratio division, |tanh|, vote
-//   lq_ops.hpp          per-operation traits (K1 fwd, K2 bwd, K4 fused, K5 penalties, integer view, STE scale gradient, clipped pair)
+//   lq_ops.hpp          per-operation traits (K1 fwd, K2 bwd, K4 fused, K5 penalties, integer view, STE scale gradient, clipped pairs: floor / nearest)
 //   lq_reduce.hpp       wave/block reductions (DPP for the standard accumulator, shuffles for custom merges)
 //   lq_traverse.hpp     traversal modes (row stream / row small / column) + finalize kernels
 //   lq_stream2.hpp      streaming-size forms of the column and tiny-row modes (round 2): flat K1, pipelined column tile, ...
@@ -1013,6 +1013,18 @@ static Params base_params(const float* P, const float* s, int64_t outer, int64_t
     return p;
 }
 
+// traversal and, unless the traversal emitted the outputs itself or none is wanted, finalize of a clipped backward (OP_CLIP_BWD[_RNE])
+template <int OP>
+static int clip_backward_launch(Plan& pl, const Params& p, bool direct, float* ds, uint32_t* clipped, int64_t outer, int64_t G,
+                                int64_t inner, hipStream_t st) {
+    if (int rc = launch_traverse<OP>(pl, p, st)) return rc;
+    if (direct || (!ds && !clipped)) return LQ_OK;
+    FinGeom f = group_geom(pl, outer, G, inner);
+    f.o0 = ds;
+    f.o2 = clipped;
+    return launch_finalize<OP>(p, f, st);
+}
+
 static bool make_conv_tile(ConvTile& ct, int64_t hw, int64_t ci, int64_t co, int64_t outer, int64_t G, int64_t inner);
 static int64_t conv_tile_partials(const ConvTile& ct, int64_t G);
 static void conv_tile_fin(const ConvTile& ct, int64_t G, int64_t& gstride, int64_t& n1, int64_t& stride1, int64_t& n2);
@@ -1021,11 +1033,13 @@ static void conv_tile_fin(const ConvTile& ct, int64_t G, int64_t& gstride, int64
 
 using namespace lq;
 
-#define LQ_REQUIRE_PTR(x)                                                      \
+// fn: the entry point's name as the caller spelled it (it opens every message); bodies shared by two entry points pass it on
+#define LQ_REQUIRE_PTR_FN(fn, x)                                               \
     do {                                                                       \
-        if (!(x)) return fail(LQ_EINVAL, "%s: argument '%s' is NULL", __func__, #x); \
-        if (!aligned((x), 4)) return fail(LQ_EALIGN, "%s: argument '%s' is not 4-byte aligned", __func__, #x); \
+        if (!(x)) return fail(LQ_EINVAL, "%s: argument '%s' is NULL", fn, #x); \
+        if (!aligned((x), 4)) return fail(LQ_EALIGN, "%s: argument '%s' is not 4-byte aligned", fn, #x); \
     } while (0)
+#define LQ_REQUIRE_PTR(x) LQ_REQUIRE_PTR_FN(__func__, x)
 
 extern "C" {
 
@@ -1266,16 +1280,23 @@ static int check_clip_range(const char* fn, int32_t qmin, int32_t qmax) {
     return LQ_OK;
 }
 
-int lq_fq_forward_clip(const float* P, const float* s, float* out, void* q, int q_dtype, int32_t qmin, int32_t qmax, int64_t outer,
-                       int64_t G, int64_t inner, void* stream) {
+static int check_rounding(const char* fn, int rounding) {
+    if (rounding != LQ_ROUND_FLOOR && rounding != LQ_ROUND_NEAREST_EVEN) return fail(LQ_EINVAL, "%s: bad rounding %d", fn, rounding);
+    return LQ_OK;
+}
+
+// One body per direction behind both spellings of the entry point; `fn` is the name the caller used.
+static int clip_forward(const char* fn, const float* P, const float* s, float* out, void* q, int q_dtype, int32_t qmin, int32_t qmax,
+                        int rounding, int64_t outer, int64_t G, int64_t inner, void* stream) {
     int rc = check_desc(outer, G, inner);
     if (rc) return rc;
-    LQ_REQUIRE_PTR(P);
-    LQ_REQUIRE_PTR(s);
-    LQ_REQUIRE_PTR(out);
-    if ((rc = check_clip_range(__func__, qmin, qmax))) return rc;
-    if (q_dtype < LQ_Q_NONE || q_dtype > LQ_Q_I8) return fail(LQ_EINVAL, "lq_fq_forward_clip: bad q_dtype %d", q_dtype);
-    if ((q != nullptr) != (q_dtype != LQ_Q_NONE)) return fail(LQ_EINVAL, "lq_fq_forward_clip: q and q_dtype disagree");
+    LQ_REQUIRE_PTR_FN(fn, P);
+    LQ_REQUIRE_PTR_FN(fn, s);
+    LQ_REQUIRE_PTR_FN(fn, out);
+    if ((rc = check_clip_range(fn, qmin, qmax))) return rc;
+    if ((rc = check_rounding(fn, rounding))) return rc;
+    if (q_dtype < LQ_Q_NONE || q_dtype > LQ_Q_I8) return fail(LQ_EINVAL, "%s: bad q_dtype %d", fn, q_dtype);
+    if ((q != nullptr) != (q_dtype != LQ_Q_NONE)) return fail(LQ_EINVAL, "%s: q and q_dtype disagree", fn);
     Plan pl = make_plan(outer, G, inner, kBlock);      // generic traversal bodies: 256-thread units at every size (kStreamOp)
     Params p = base_params(P, s, outer, G, inner);
     p.out = out;
@@ -1283,20 +1304,34 @@ int lq_fq_forward_clip(const float* P, const float* s, float* out, void* q, int 
     p.q_dtype = q_dtype;
     p.clip_lo = (float)qmin;
     p.clip_hi = (float)qmax;
+    // the rounding is a template parameter of the op trait: each pair has its own kernels, none tests a flag
+    if (rounding == LQ_ROUND_NEAREST_EVEN) return launch_traverse<OP_CLIP_FWD_RNE>(pl, p, (hipStream_t)stream);
     return launch_traverse<OP_CLIP_FWD>(pl, p, (hipStream_t)stream);
 }
 
-int lq_fq_backward_clip(const float* P, const float* s, const float* dy, int32_t qmin, int32_t qmax, float grad_scale, float* dP,
-                        float* ds, uint32_t* clipped, void* ws, size_t ws_bytes, int64_t outer, int64_t G, int64_t inner, void* stream) {
+int lq_fq_forward_clip_r(const float* P, const float* s, float* out, void* q, int q_dtype, int32_t qmin, int32_t qmax, int rounding,
+                         int64_t outer, int64_t G, int64_t inner, void* stream) {
+    return clip_forward(__func__, P, s, out, q, q_dtype, qmin, qmax, rounding, outer, G, inner, stream);
+}
+
+int lq_fq_forward_clip(const float* P, const float* s, float* out, void* q, int q_dtype, int32_t qmin, int32_t qmax, int64_t outer,
+                       int64_t G, int64_t inner, void* stream) {
+    return clip_forward(__func__, P, s, out, q, q_dtype, qmin, qmax, LQ_ROUND_FLOOR, outer, G, inner, stream);
+}
+
+static int clip_backward(const char* fn, const float* P, const float* s, const float* dy, int32_t qmin, int32_t qmax, int rounding,
+                         float grad_scale, float* dP, float* ds, uint32_t* clipped, void* ws, size_t ws_bytes, int64_t outer, int64_t G,
+                         int64_t inner, void* stream) {
     int rc = check_desc(outer, G, inner);
     if (rc) return rc;
-    LQ_REQUIRE_PTR(P);
-    LQ_REQUIRE_PTR(s);
-    LQ_REQUIRE_PTR(dy);
-    LQ_REQUIRE_PTR(dP);
-    if (ds && !aligned(ds, 4)) return fail(LQ_EALIGN, "lq_fq_backward_clip: ds is not 4-byte aligned");
-    if (clipped && !aligned(clipped, 4)) return fail(LQ_EALIGN, "lq_fq_backward_clip: clipped is not 4-byte aligned");
-    if ((rc = check_clip_range(__func__, qmin, qmax))) return rc;
+    LQ_REQUIRE_PTR_FN(fn, P);
+    LQ_REQUIRE_PTR_FN(fn, s);
+    LQ_REQUIRE_PTR_FN(fn, dy);
+    LQ_REQUIRE_PTR_FN(fn, dP);
+    if (ds && !aligned(ds, 4)) return fail(LQ_EALIGN, "%s: ds is not 4-byte aligned", fn);
+    if (clipped && !aligned(clipped, 4)) return fail(LQ_EALIGN, "%s: clipped is not 4-byte aligned", fn);
+    if ((rc = check_clip_range(fn, qmin, qmax))) return rc;
+    if ((rc = check_rounding(fn, rounding))) return rc;
     Plan pl = make_plan(outer, G, inner, kBlock);      // generic traversal bodies, as lq_fq_scale_grad_ste
     Params p = base_params(P, s, outer, G, inner);
     p.dy = dy;
@@ -1305,22 +1340,31 @@ int lq_fq_backward_clip(const float* P, const float* s, const float* dy, int32_t
     p.clip_lo = (float)qmin;
     p.clip_hi = (float)qmax;
     // the workspace is required, and checked, also for "mask only" calls: one kernel serves both, the sum is dropped at the emit
-    if (!ws || ws_bytes < ws_bytes_for(pl)) return fail(LQ_EINVAL, "lq_fq_backward_clip: workspace %s (%zu bytes given, %zu needed)",
+    if (!ws || ws_bytes < ws_bytes_for(pl)) return fail(LQ_EINVAL, "%s: workspace %s (%zu bytes given, %zu needed)", fn,
                                                         ws ? "too small" : "is NULL", ws ? ws_bytes : (size_t)0, ws_bytes_for(pl));
     if ((rc = bind_ws(p, pl, ws, ws_bytes))) return rc;
     const bool direct = pl.n1 * pl.n2 == 1;      // one partial per group: the traversal emits ds and the count itself
     if (direct) {
         p.direct = 1;
         p.e0 = ds;
-        p.e1 = reinterpret_cast<float*>(clipped);      // emit_direct<OP_CLIP_BWD> hands it on as FinGeom::o2
+        p.e1 = reinterpret_cast<float*>(clipped);      // emit_direct<OP_CLIP_BWD[_RNE]> hands it on as FinGeom::o2
         p.ecount = (double)outer * (double)inner;
     }
-    if ((rc = launch_traverse<OP_CLIP_BWD>(pl, p, (hipStream_t)stream))) return rc;
-    if (direct || (!ds && !clipped)) return LQ_OK;
-    FinGeom f = group_geom(pl, outer, G, inner);
-    f.o0 = ds;
-    f.o2 = clipped;
-    return launch_finalize<OP_CLIP_BWD>(p, f, (hipStream_t)stream);
+    // the rounding is a template parameter of the op trait: each pair has its own kernels, none tests a flag
+    if (rounding == LQ_ROUND_NEAREST_EVEN)
+        return clip_backward_launch<OP_CLIP_BWD_RNE>(pl, p, direct, ds, clipped, outer, G, inner, (hipStream_t)stream);
+    return clip_backward_launch<OP_CLIP_BWD>(pl, p, direct, ds, clipped, outer, G, inner, (hipStream_t)stream);
+}
+
+int lq_fq_backward_clip_r(const float* P, const float* s, const float* dy, int32_t qmin, int32_t qmax, int rounding, float grad_scale,
+                          float* dP, float* ds, uint32_t* clipped, void* ws, size_t ws_bytes, int64_t outer, int64_t G, int64_t inner,
+                          void* stream) {
+    return clip_backward(__func__, P, s, dy, qmin, qmax, rounding, grad_scale, dP, ds, clipped, ws, ws_bytes, outer, G, inner, stream);
+}
+
+int lq_fq_backward_clip(const float* P, const float* s, const float* dy, int32_t qmin, int32_t qmax, float grad_scale, float* dP,
+                        float* ds, uint32_t* clipped, void* ws, size_t ws_bytes, int64_t outer, int64_t G, int64_t inner, void* stream) {
+    return clip_backward(__func__, P, s, dy, qmin, qmax, LQ_ROUND_FLOOR, grad_scale, dP, ds, clipped, ws, ws_bytes, outer, G, inner, stream);
 }
 
 int lq_fq_fwd_bwd_fused(const float* P, const float* s, const float* dy, float lambda, float* out, float* ds, void* ws,

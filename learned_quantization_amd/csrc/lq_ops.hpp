@@ -350,7 +350,15 @@ struct OpT<OP_STE_SCALE> : OpBase {
 // Clipped b-bit fake-quant (lq_hip.h: lq_fq_forward_clip / lq_fq_backward_clip).  lo = (float)qmin and hi = (float)qmax travel in
 // Ctx::k0 / k1 (Params::clip_lo / clip_hi).  The quotient is K1's (div_by_uniform, fq_quot4, fq_quot4c); the clamp is two
 // comparisons and two selects, not fmin / fmax: a NaN floor stays NaN, +-Inf saturates.
+// RNE (compile time, never a runtime flag) picks the rounding of the quotient: false = floorf (OP_CLIP_FWD / OP_CLIP_BWD), true =
+// rintf, round half to even (OP_CLIP_FWD_RNE / OP_CLIP_BWD_RNE: lq_fq_forward_clip_r / lq_fq_backward_clip_r with
+// LQ_ROUND_NEAREST_EVEN).  Either is one instruction (v_floor_f32 / v_rndne_f32); |t| >= 2^23 comes back unchanged from both.
+template <bool RNE>
 struct ClipBase : OpBase {
+    __device__ static __forceinline__ float rnd(float t) {
+        if constexpr (RNE) return rintf(t);
+        else return floorf(t);
+    }
     __device__ static __forceinline__ Ctx ctx(const Params& p, int64_t g) {
         Ctx c;
         c.s = p.s[g];
@@ -364,8 +372,10 @@ struct ClipBase : OpBase {
     __device__ static __forceinline__ float clampq(float q0, float lo, float hi) { return q0 < lo ? lo : (q0 > hi ? hi : q0); }
 };
 
-template <>
-struct OpT<OP_CLIP_FWD> : ClipBase {
+template <bool RNE>
+struct ClipFwdOp : ClipBase<RNE> {
+    using ClipBase<RNE>::rnd;
+    using ClipBase<RNE>::clampq;
     static constexpr bool kStore = true;
     __device__ static __forceinline__ void side4(const Params& p, int64_t i, const float4& q) {      // one test per float4, as FwdOp
         if (p.q) {
@@ -376,7 +386,7 @@ struct OpT<OP_CLIP_FWD> : ClipBase {
         }
     }
     __device__ static __forceinline__ float elem(const Params& p, const Ctx& c, int64_t i, float x, float, Acc&) {
-        const float q = clampq(floorf(div_by_uniform(x, c)), c.k0, c.k1);
+        const float q = clampq(rnd(div_by_uniform(x, c)), c.k0, c.k1);
         if (p.q) store_q(p.q, p.q_dtype, i, q);
         return q * c.s;
     }
@@ -384,8 +394,8 @@ struct OpT<OP_CLIP_FWD> : ClipBase {
     __device__ static __forceinline__ float4 elem4(const Params& p, const Ctx& c, int64_t i, const float4& x, const float4&, Acc&) {
         const float4 t = fq_quot4(x, c);
         float4 q, o;
-        q.x = clampq(floorf(t.x), c.k0, c.k1); q.y = clampq(floorf(t.y), c.k0, c.k1);
-        q.z = clampq(floorf(t.z), c.k0, c.k1); q.w = clampq(floorf(t.w), c.k0, c.k1);
+        q.x = clampq(rnd(t.x), c.k0, c.k1); q.y = clampq(rnd(t.y), c.k0, c.k1);
+        q.z = clampq(rnd(t.z), c.k0, c.k1); q.w = clampq(rnd(t.w), c.k0, c.k1);
         o.x = q.x * c.s; o.y = q.y * c.s; o.z = q.z * c.s; o.w = q.w * c.s;
         side4(p, i, q);
         return o;
@@ -394,26 +404,32 @@ struct OpT<OP_CLIP_FWD> : ClipBase {
     __device__ static __forceinline__ float4 elem4c(const Params& p, const Ctx* c, int64_t i, const float4& x, const float4&, Acc*) {
         const float4 t = fq_quot4c(x, c);
         float4 q, o;
-        q.x = clampq(floorf(t.x), c[0].k0, c[0].k1); q.y = clampq(floorf(t.y), c[1].k0, c[1].k1);
-        q.z = clampq(floorf(t.z), c[2].k0, c[2].k1); q.w = clampq(floorf(t.w), c[3].k0, c[3].k1);
+        q.x = clampq(rnd(t.x), c[0].k0, c[0].k1); q.y = clampq(rnd(t.y), c[1].k0, c[1].k1);
+        q.z = clampq(rnd(t.z), c[2].k0, c[2].k1); q.w = clampq(rnd(t.w), c[3].k0, c[3].k1);
         o.x = q.x * c[0].s; o.y = q.y * c[1].s; o.z = q.z * c[2].s; o.w = q.w * c[3].s;
         side4(p, i, q);
         return o;
     }
 };
+template <>
+struct OpT<OP_CLIP_FWD> : ClipFwdOp<false> {};
+template <>
+struct OpT<OP_CLIP_FWD_RNE> : ClipFwdOp<true> {};
 
 // Backward: the value returned (stored by the traversal in the primary dense output) is dP.  acc.c carries sum dy * r in f64
-// from the first addition (r = floor(t) - t inside the range, ONE fp32 subtraction as OP_STE_SCALE; the bound lo or hi
-// outside; NaN for a NaN floor), acc.b the number of elements outside the range (a NaN floor counts); the standard merge adds
-// both.  The factor k (Params::c_scale) is applied once per group by FinT::emit.  As for OP_STE_SCALE the terms have no
+// from the first addition (r = rnd(t) - t inside the range, ONE fp32 subtraction as OP_STE_SCALE, in [-1, 0] for floor and in
+// [-1/2, 1/2] for nearest; the bound lo or hi outside; NaN for a NaN q0), acc.b the number of elements outside the range (a NaN
+// q0 counts); the standard merge adds both.  The factor k (Params::c_scale) is applied once per group by FinT::emit.  As for OP_STE_SCALE the terms have no
 // common quantum: different traversals may differ in the last bit of ds, each one is run-to-run bit-stable.
-template <>
-struct OpT<OP_CLIP_BWD> : ClipBase {
+template <bool RNE>
+struct ClipBwdOp : ClipBase<RNE> {
+    using ClipBase<RNE>::rnd;
+    using ClipBase<RNE>::clampq;
     static constexpr bool kDy = true;
     static constexpr bool kStore = true;
     static constexpr bool kReduce = true;
     __device__ static __forceinline__ float one(float t, float dy, float lo, float hi, Acc& acc) {
-        const float q0 = floorf(t);
+        const float q0 = rnd(t);
         const bool inside = (q0 >= lo) & (q0 <= hi);           // false for NaN
         const float r = inside ? q0 - t : clampq(q0, lo, hi);
         acc.c += (double)dy * (double)r;
@@ -444,6 +460,10 @@ struct OpT<OP_CLIP_BWD> : ClipBase {
         return o;
     }
 };
+template <>
+struct OpT<OP_CLIP_BWD> : ClipBwdOp<false> {};
+template <>
+struct OpT<OP_CLIP_BWD_RNE> : ClipBwdOp<true> {};
 
 }  // namespace lq
 

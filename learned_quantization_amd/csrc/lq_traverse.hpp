@@ -696,6 +696,8 @@ struct FinT<OP_CLIP_BWD> {
         return ds;
     }
 };
+template <>
+struct FinT<OP_CLIP_BWD_RNE> : FinT<OP_CLIP_BWD> {};      // the rounding lives in the traversal's trait; the emit is the same
 
 template <int OP>
 __device__ __forceinline__ void emit_direct(const Params& p, int64_t g, const Acc& acc) {
@@ -706,7 +708,7 @@ __device__ __forceinline__ void emit_direct(const Params& p, int64_t g, const Ac
     f.o0 = p.e0;
     f.o1 = p.e1;
     f.o2 = nullptr;
-    if constexpr (OP == OP_CLIP_BWD) f.o2 = reinterpret_cast<uint32_t*>(p.e1);      // clipped[G] travels in the e1 slot
+    if constexpr (OP == OP_CLIP_BWD || OP == OP_CLIP_BWD_RNE) f.o2 = reinterpret_cast<uint32_t*>(p.e1);      // clipped[G] travels in the e1 slot
     f.accum = 0;
     AccW w;
     w.a = acc.a;

@@ -122,6 +122,8 @@ def main(argv=None):
     ap.add_argument("--bits", type=int, default=None,
                     help="clipped b-bit quantizer (signed, integers in [-2^(b-1), 2^(b-1) - 1]); needs --scale-gradient ste or "
                          "--custom_loss")
+    ap.add_argument("--rounding", default="floor", choices=["floor", "nearest"],
+                    help="with --bits: round P/s down (the reference's floor) or to nearest, ties to even")
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--steps-per-epoch", type=int, default=10)
     ap.add_argument("--batch", type=int, default=128)
@@ -151,7 +153,7 @@ def main(argv=None):
 
     tr = Trainer(args.config, mode, value, args.orientation, args.custom_loss, lr=args.lr, seed=args.seed, device=dev,
                  log_dir=log_dir, batched=args.batched, loss_values=args.loss_values,
-                 loss_log_capacity=max(4096, args.steps_per_epoch), bits=args.bits)
+                 loss_log_capacity=max(4096, args.steps_per_epoch), bits=args.bits, rounding=args.rounding)
     if args.training == "post_training":
         if args.config != "mnist" or not args.baseline_weights:
             raise SystemExit("post_training needs --config mnist --baseline-weights <npz with W1,b1,W2,b2> "

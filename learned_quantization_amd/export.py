@@ -53,7 +53,8 @@ def quantized_tensors(model: torch.nn.Module) -> List[Tuple[str, torch.nn.Parame
 
 def quantized_state(model: torch.nn.Module) -> Dict[str, np.ndarray]:
     # a layer with an integer range exports the CLAMPED integers (nested.quantized_integers): inside the range whatever
-    # floor(P/s) is, so int8 cannot wrap for bits <= 8; a layer without one exports floor(P/s) as before
+    # floor(P/s) is, so int8 cannot wrap for bits <= 8 (rint(P/s) for a rounding="nearest" layer: the view is the layer's own); a
+    # layer without one exports floor(P/s) as before
     return {name: _host(nested.quantized_integers(param.data, torch.int8))
             for name, param, nested in quantized_tensors(model)}
 
@@ -140,6 +141,8 @@ def save_packed_parameters(model: torch.nn.Module, log_dir: str) -> Dict[str, fl
         entries.append({"name": name, "shape": list(param.shape), "scale_shape": list(nested.scale.shape),
                         "orientation": nested.orientation, "qmin": int(lo), "bits": int(hi - lo).bit_length(),
                         "numel": int(param.numel())})
+        if getattr(nested, "rounding", "floor") != "floor":      # floor layers get no key: their container is unchanged
+            entries[-1]["rounding"] = nested.rounding
     bad = torch.zeros(len(tensors), dtype=torch.int64, device=dev)
     words = [ops.q_pack(src, unit, qmin=e["qmin"], bits=e["bits"], bad=bad[k:k + 1])[0]
              for k, ((src, unit), e) in enumerate(zip(sources, entries))]
@@ -206,6 +209,9 @@ def _check_packed(model: torch.nn.Module, manifest: dict, z, tensors, state_keys
             raise ValueError(f"{name}: scale shape {e.get('scale_shape')} in the container, {list(nested.scale.shape)} in the model")
         if e.get("orientation") != nested.orientation:
             raise ValueError(f"{name}: orientation {e.get('orientation')!r} in the container, {nested.orientation!r} in the model")
+        if e.get("rounding", "floor") != getattr(nested, "rounding", "floor"):      # a missing key means floor
+            raise ValueError(f"{name}: rounding {e.get('rounding', 'floor')!r} in the container, "
+                             f"{getattr(nested, 'rounding', 'floor')!r} in the model")
         bits, numel = e.get("bits"), e.get("numel")
         if not isinstance(bits, int) or not 0 <= bits <= 32 or numel != param.numel():
             raise ValueError(f"{name}: bad bits/numel {bits}/{numel}")
@@ -232,8 +238,10 @@ def _check_packed(model: torch.nn.Module, manifest: dict, z, tensors, state_keys
 def load_packed_parameters(model: torch.nn.Module, path: str) -> dict:
     """Restores a weights_packed.npz (or the directory holding it) into ``model`` -- built by build_model with the same
     config, either kernel_storage: each quantized P becomes a value whose floor(P/s) is the stored integer, each scale and every
-    state entry the stored one, copied into the existing tensors.  Format, version, names, shapes and orientations are
-    checked first: on a mismatch ValueError is raised and the model is left untouched.  Returns the manifest."""
+    state entry the stored one, copied into the existing tensors.  A rounding="nearest" layer takes another pre-image: (q + 1/2) * s
+    is a tie under rint, so its P becomes q * s, and the layer's own integer view of that P is compared with q on the device.
+    Format, version, names, shapes, orientations and roundings are checked first: on a mismatch, or a restored value that does
+    not round back, ValueError is raised and the model is left untouched.  Returns the manifest."""
     if os.path.isdir(path):
         path = os.path.join(path, PACKED_FILES[0])
     tensors = quantized_tensors(model)
@@ -248,15 +256,27 @@ def load_packed_parameters(model: torch.nn.Module, path: str) -> dict:
         return manifest
     dev = tensors[0][1].device
     bad = torch.zeros(1, dtype=torch.int64, device=dev)
+    outside = torch.zeros(1, dtype=torch.int64, device=dev)      # nearest layers: stored integers beyond the model layer's range
     restored = []
     for (name, param, nested), e in zip(tensors, manifest["tensors"]):
         s = torch.from_numpy(scales[name]).to(dev)
         w = torch.from_numpy(codes[name].view(np.int32)).to(dev)
-        _, _, pr = ops.q_unpack(w, e["qmin"], e["bits"], s, param.shape, want_out=False, want_q=False, bad=bad)
+        if e.get("rounding", "floor") == "nearest":
+            # rint(fl(fl(q * s) / s)) == q holds for |q| < 2^22 and can miss beyond: counted with the stored scale, like the floor misses
+            pr, q, _ = ops.q_unpack(w, e["qmin"], e["bits"], s, param.shape, want_restore=False)
+            view = ops.fq_forward_clip(pr, s, *nested.q_range, q_dtype=torch.int32, rounding="nearest")[1]
+            beyond = (q < nested.q_range[0]) | (q > nested.q_range[1])      # the layer would clamp these: not a rounding miss
+            outside += beyond.sum()
+            bad += ((view != q) & ~beyond).sum()
+        else:
+            _, _, pr = ops.q_unpack(w, e["qmin"], e["bits"], s, param.shape, want_out=False, want_q=False, bad=bad)
         restored.append((param, nested, s, pr))
-    nbad = int(bad.item())
+    nbad, noutside = int(bad.item()), int(outside.item())
+    if noutside:
+        raise ValueError(f"{noutside} stored integers lie outside the integer range of their layer in the model (the container was "
+                         "written by a model with a wider range): model left untouched")
     if nbad:
-        raise ValueError(f"{nbad} restored values do not floor back to their stored integer (|q| >= 2^22): model left untouched")
+        raise ValueError(f"{nbad} restored values do not round back to their stored integer (|q| >= 2^22): model left untouched")
     with torch.no_grad():
         for param, nested, s, pr in restored:
             param.data.copy_(pr)                               # into the parameter's own storage (HWIO or OIHW order)

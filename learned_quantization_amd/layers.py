@@ -132,6 +132,8 @@ class CustomQuantizedScaleLayer(nn.Module):
     ``bits`` / ``signed`` or ``q_range=(qmin, qmax)`` (not in the reference; only without ``penalty_threshold``) -> the clipped
     quantizer (ops.fq_forward_clip / fq_backward_clip): integers saturate at [-2^(b-1), 2^(b-1) - 1] (signed) or [0, 2^b - 1],
     clipped elements pass no gradient to the parameter and, with ``scale_gradient="ste"``, pull the scale towards covering them.
+    ``rounding="nearest"`` (not in the reference; only with a range) -> the integers are rint(P/s), round half to even, instead of
+    floor(P/s); the LSQ residual is then centred on zero.
     """
 
     _SCALE_NAMES = {"rowwise": "Rowwise-scaler", "columnwise": "Columnwise-scaler",
@@ -139,9 +141,11 @@ class CustomQuantizedScaleLayer(nn.Module):
                     "scalar": "Scalar-scaler"}
 
     def __init__(self, penalty_threshold=None, initializer=None, orientation="scalar", *, penalty_rate=None,
-                 scale_gradient=None, grad_scale=1.0, bits=None, signed=True, q_range=None):
+                 scale_gradient=None, grad_scale=1.0, bits=None, signed=True, q_range=None, rounding="floor"):
         super().__init__()
         self.q_range = ops.q_range_of(bits, signed, q_range)
+        ops.check_rounding(rounding, self.q_range is not None)
+        self.rounding = rounding
         if self.q_range is not None and penalty_threshold is not None:
             raise ValueError("a clipped layer (bits / q_range) needs penalty_threshold=None: the nested-quantization vote is "
                              "defined on the unclipped quantizer")
@@ -187,7 +191,7 @@ class CustomQuantizedScaleLayer(nn.Module):
         if self.q_range is not None:
             return ops.my_custom_gradient(inputs, self.scale, self.penalty_threshold, scale_gradient=self.scale_gradient,
                                           grad_scale=self.grad_scale_value(inputs.numel()) if self.scale_gradient == "ste" else 1.0,
-                                          defer_scale_grad=self.defer_scale_grad, q_range=self.q_range)
+                                          defer_scale_grad=self.defer_scale_grad, q_range=self.q_range, rounding=self.rounding)
         if self.scale_gradient == "ste":
             return ops.my_custom_gradient(inputs, self.scale, scale_gradient="ste", grad_scale=self.grad_scale_value(inputs.numel()),
                                           defer_scale_grad=self.defer_scale_grad)
@@ -204,19 +208,23 @@ class CustomQuantizedScaleLayer(nn.Module):
             r += f", scale_gradient={self.scale_gradient!r}, grad_scale={self.grad_scale!r}"
         if self.q_range is not None:
             r += f", q_range={self.q_range!r}"
+        if self.rounding != "floor":
+            r += f", rounding={self.rounding!r}"
         return r
 
     def quantized_integers(self, parameter, dtype=torch.float32):
-        """The integer view of ``parameter`` under this layer's quantizer: floor(P/s), clamped when the layer has a range."""
+        """The integer view of ``parameter`` under this layer's quantizer: floor(P/s), clamped when the layer has a range (then
+        rint(P/s) for ``rounding="nearest"``)."""
         if self.q_range is None:
             return ops.quantized_integers(parameter, self.scale.data, dtype)
-        return ops.fq_forward_clip(parameter, self.scale.data, *self.q_range, q_dtype=dtype)[1]
+        return ops.fq_forward_clip(parameter, self.scale.data, *self.q_range, q_dtype=dtype, rounding=self.rounding)[1]
 
 
-def _nested(penalty_threshold, penalty_rate, orientation, scale_gradient=None, grad_scale=1.0, q_range=None):
+def _nested(penalty_threshold, penalty_rate, orientation, scale_gradient=None, grad_scale=1.0, q_range=None, rounding="floor"):
     return CustomQuantizedScaleLayer(penalty_threshold=penalty_threshold, initializer=None,
                                      orientation=orientation, penalty_rate=penalty_rate,
-                                     scale_gradient=scale_gradient, grad_scale=grad_scale, q_range=q_range)
+                                     scale_gradient=scale_gradient, grad_scale=grad_scale, q_range=q_range,
+                                     rounding=rounding)
 
 
 def _as_tensor(a, shape, device):
@@ -228,9 +236,13 @@ def _as_tensor(a, shape, device):
 
 class _HostLayer(nn.Module):
     q_range = None
+    rounding = "floor"
 
     def extra_repr(self):
-        return f"q_range={self.q_range!r}" if self.q_range is not None else ""
+        r = f"q_range={self.q_range!r}" if self.q_range is not None else ""
+        if self.rounding != "floor":
+            r += f", rounding={self.rounding!r}"
+        return r
 
     def _init_value(self, initializer, shape, device):
         if initializer is None:
@@ -256,12 +268,14 @@ class CustomDenseLayer(_HostLayer):
 
     def __init__(self, seed=None, units=None, penalty_threshold=None, orientation="scalar", initializer=None,
                  name=None, regularizer=None, trained_weights=None, *, penalty_rate=None, input_shape=None,
-                 device=None, scale_gradient=None, grad_scale=1.0, bits=None, signed=True, q_range=None, **kwargs):
+                 device=None, scale_gradient=None, grad_scale=1.0, bits=None, signed=True, q_range=None, rounding="floor", **kwargs):
         super().__init__()
         self.seed = seed
         self.q_range = ops.q_range_of(bits, signed, q_range)      # None: the reference's unbounded quantizer
-        self.nested_q_w_layer = _nested(penalty_threshold, penalty_rate, orientation, scale_gradient, grad_scale, self.q_range)   # NQ-L:222-224
-        self.nested_q_b_layer = _nested(penalty_threshold, penalty_rate, "scalar", scale_gradient, grad_scale, self.q_range)      # NQ-L:225-227
+        ops.check_rounding(rounding, self.q_range is not None)
+        self.rounding = rounding
+        self.nested_q_w_layer = _nested(penalty_threshold, penalty_rate, orientation, scale_gradient, grad_scale, self.q_range, rounding)   # NQ-L:222-224
+        self.nested_q_b_layer = _nested(penalty_threshold, penalty_rate, "scalar", scale_gradient, grad_scale, self.q_range, rounding)      # NQ-L:225-227
         self.units = units
         self.initializer = initializer
         self.regularizer = regularizer
@@ -349,18 +363,20 @@ class _ConvBase(_HostLayer):
     def __init__(self, seed=None, penalty_threshold=None, orientation="scalar", initializer=None, filters=None,
                  kernel_size=(3, 3), strides=(1, 1), padding="same", name=None, regularizer=None,
                  trained_weights=None, *, penalty_rate=None, input_shape=None, data_format="NCHW", device=None,
-                 kernel_storage=None, scale_gradient=None, grad_scale=1.0, bits=None, signed=True, q_range=None, **kwargs):
+                 kernel_storage=None, scale_gradient=None, grad_scale=1.0, bits=None, signed=True, q_range=None, rounding="floor", **kwargs):
         super().__init__()
         self.seed = seed
         self.q_range = ops.q_range_of(bits, signed, q_range)      # None: the reference's unbounded quantizer
+        ops.check_rounding(rounding, self.q_range is not None)
+        self.rounding = rounding
         if kernel_storage is None:
             kernel_storage = _KERNEL_STORAGE[-1]
         if kernel_storage not in ("oihw", "hwio"):
             raise ValueError("kernel_storage must be 'oihw' or 'hwio'")
         self.kernel_storage = kernel_storage
-        self.nested_q_k_layer = _nested(penalty_threshold, penalty_rate, orientation, scale_gradient, grad_scale, self.q_range)      # NQ-L:293-295
+        self.nested_q_k_layer = _nested(penalty_threshold, penalty_rate, orientation, scale_gradient, grad_scale, self.q_range, rounding)      # NQ-L:293-295
         if self._has_bias:
-            self.nested_q_b_layer = _nested(penalty_threshold, penalty_rate, "scalar", scale_gradient, grad_scale, self.q_range)     # NQ-L:296-298
+            self.nested_q_b_layer = _nested(penalty_threshold, penalty_rate, "scalar", scale_gradient, grad_scale, self.q_range, rounding)     # NQ-L:296-298
         self.initializer = initializer
         self.filters = filters
         self.kernel_size = _pair(kernel_size)

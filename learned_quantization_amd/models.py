@@ -23,7 +23,7 @@ carries its logits (``losses.softmax``), from which the cross-entropy is compute
 ``mode="ste"``: the straight-through scale gradient (ops.fq_scale_grad_ste), no loss term, ``value`` is ignored;
 ``mode="stecl"``: the same plus a custom loss term, ``value`` is the penalty_rate.
 ``bits`` / ``signed`` / ``q_range`` (``build_model``; modes "cl", "ste", "stecl"): every quantised tensor uses the clipped
-quantizer with that integer range (layers.py).
+quantizer with that integer range (layers.py); ``rounding="nearest"`` makes it round to nearest (ties to even), not down.
 """
 from __future__ import annotations
 
@@ -280,12 +280,16 @@ def check_clip_mode(mode: str) -> None:
                          f"a clipped model needs one of the modes {CLIP_MODES}")
 
 
-def build_model(config: str, kernel_storage: str = None, grad_scale=None, bits=None, signed=True, q_range=None, **kw) -> nn.Module:
+def build_model(config: str, kernel_storage: str = None, grad_scale=None, bits=None, signed=True, q_range=None, rounding="floor",
+                **kw) -> nn.Module:
     """config: 'mnist' (C1), 'cifar' (C2/C4), 'imagenette' (C3), 'resnet50' (C5, extension).
     ``kernel_storage``: memory order of the conv kernels, "oihw" (default) or "hwio" (layers.py).
     ``grad_scale`` (modes "ste" / "stecl"): factor of every straight-through scale gradient, a float or "rsqrt_group".
     ``bits`` (1..24) with ``signed``, or ``q_range=(qmin, qmax)`` (modes "cl" / "ste" / "stecl"): the integer range of every
-    quantised tensor, carried by the host layers and both of their nested layers."""
+    quantised tensor, carried by the host layers and both of their nested layers.
+    ``rounding`` ("floor" / "nearest"; "nearest" only with a range): how that quantizer rounds P/s, carried the same way."""
+    from .ops import check_rounding
+    check_rounding(rounding, bits is not None or q_range is not None)
     if bits is not None or q_range is not None:
         from .layers import CustomQuantizedScaleLayer, _HostLayer
         from .ops import q_range_of
@@ -295,6 +299,7 @@ def build_model(config: str, kernel_storage: str = None, grad_scale=None, bits=N
         for m in model.modules():
             if isinstance(m, (CustomQuantizedScaleLayer, _HostLayer)):
                 m.q_range = rng
+                m.rounding = rounding
         return model
     if grad_scale is not None:
         from .layers import CustomQuantizedScaleLayer

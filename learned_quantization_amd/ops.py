@@ -131,10 +131,25 @@ def q_range_of(bits=None, signed=True, q_range=None) -> Optional[Tuple[int, int]
     return (-(1 << (b - 1)), (1 << (b - 1)) - 1) if signed else (0, (1 << b) - 1)
 
 
-def fq_forward_clip(parameter: torch.Tensor, scale: torch.Tensor, qmin: int, qmax: int, q_dtype: Optional[torch.dtype] = None):
-    """Clipped forward (include/lq_hip.h, lq_fq_forward_clip): out = clamp(floor(P/s), qmin, qmax) * s.  Returns ``out``, or
-    ``(out, q)`` with the clamped integers when ``q_dtype`` is given."""
+ROUNDINGS = ("floor", "nearest")      # include/lq_hip.h: LQ_ROUND_FLOOR, LQ_ROUND_NEAREST_EVEN
+
+
+def check_rounding(rounding, has_range: bool = True) -> int:
+    """The C ABI's value of ``rounding``, or ValueError: one of ROUNDINGS, and "nearest" only for a quantizer with a range."""
+    if rounding not in ROUNDINGS:
+        raise ValueError(f"rounding must be one of {ROUNDINGS}, got {rounding!r}")
+    if rounding == "nearest" and not has_range:
+        raise ValueError("rounding='nearest' needs bits or q_range (the unbounded nearest quantizer is q_range=(-2**24, 2**24))")
+    return ROUNDINGS.index(rounding)
+
+
+def fq_forward_clip(parameter: torch.Tensor, scale: torch.Tensor, qmin: int, qmax: int, q_dtype: Optional[torch.dtype] = None,
+                    *, rounding: str = "floor"):
+    """Clipped forward (include/lq_hip.h, lq_fq_forward_clip_r): out = clamp(rnd(P/s), qmin, qmax) * s with rnd = floor, or rint
+    (round half to even) for ``rounding="nearest"``.  Returns ``out``, or ``(out, q)`` with the clamped integers when ``q_dtype``
+    is given."""
     qmin, qmax = check_q_range(qmin, qmax)
+    rnd = check_rounding(rounding)
     lib = _hip.load()
     p, s, (outer, G, inner) = _param(parameter, scale)
     out = torch.empty_like(p)
@@ -145,17 +160,19 @@ def fq_forward_clip(parameter: torch.Tensor, scale: torch.Tensor, qmin: int, qma
             raise TypeError(f"q_dtype must be one of {list(_QDTYPES)}, got {q_dtype}")
         q = torch.empty_like(p, dtype=q_dtype)
         qd = _QDTYPES[q_dtype]
-    _hip.check(lib.lq_fq_forward_clip(_hip.ptr(p), _hip.ptr(s), _hip.ptr(out), _hip.ptr(q), qd, qmin, qmax,
-                                      outer, G, inner, _hip.stream_ptr(p.device)), "lq_fq_forward_clip")
+    _hip.check(lib.lq_fq_forward_clip_r(_hip.ptr(p), _hip.ptr(s), _hip.ptr(out), _hip.ptr(q), qd, qmin, qmax, rnd,
+                                        outer, G, inner, _hip.stream_ptr(p.device)), "lq_fq_forward_clip_r")
     return out if q is None else (out, q)
 
 
 def fq_backward_clip(parameter: torch.Tensor, scale: torch.Tensor, dy: torch.Tensor, qmin: int, qmax: int,
-                     grad_scale: float = 1.0, want_ds: bool = True, want_clipped: bool = False):
-    """Clipped backward (include/lq_hip.h, lq_fq_backward_clip).  Returns ``(dP, ds, clipped)``: dP = dy inside the range and +0
-    outside, with the parameter's strides; ds (shape of scale; None unless ``want_ds``) = grad_scale * sum dy * r; clipped
-    (int32 tensor holding the uint32 counts per group, shape of scale; None unless ``want_clipped``)."""
+                     grad_scale: float = 1.0, want_ds: bool = True, want_clipped: bool = False, *, rounding: str = "floor"):
+    """Clipped backward (include/lq_hip.h, lq_fq_backward_clip_r; ``rounding`` as fq_forward_clip).  Returns
+    ``(dP, ds, clipped)``: dP = dy inside the range and +0 outside, with the parameter's strides; ds (shape of scale; None unless
+    ``want_ds``) = grad_scale * sum dy * r; clipped (int32 tensor holding the uint32 counts per group, shape of scale; None
+    unless ``want_clipped``)."""
     qmin, qmax = check_q_range(qmin, qmax)
+    rnd = check_rounding(rounding)
     lib = _hip.load()
     p, s, (outer, G, inner) = _param(parameter, scale)
     d = _hip.require_device_f32(dy, "dy", like=p)
@@ -163,9 +180,9 @@ def fq_backward_clip(parameter: torch.Tensor, scale: torch.Tensor, dy: torch.Ten
     ds = torch.empty_like(s) if want_ds else None
     clipped = torch.empty_like(s, dtype=torch.int32) if want_clipped else None
     ws = _hip.workspace_for(p.device, outer, G, inner)
-    _hip.check(lib.lq_fq_backward_clip(_hip.ptr(p), _hip.ptr(s), _hip.ptr(d), qmin, qmax, float(grad_scale), _hip.ptr(dP),
-                                       _hip.ptr(ds), _hip.ptr(clipped), _hip.ptr(ws), ws.numel(), outer, G, inner,
-                                       _hip.stream_ptr(p.device)), "lq_fq_backward_clip")
+    _hip.check(lib.lq_fq_backward_clip_r(_hip.ptr(p), _hip.ptr(s), _hip.ptr(d), qmin, qmax, rnd, float(grad_scale), _hip.ptr(dP),
+                                         _hip.ptr(ds), _hip.ptr(clipped), _hip.ptr(ws), ws.numel(), outer, G, inner,
+                                         _hip.stream_ptr(p.device)), "lq_fq_backward_clip_r")
     return dP, ds, clipped
 
 
@@ -503,33 +520,35 @@ class _STEScaleQuantFn(torch.autograd.Function):
 
 
 class _ClipQuantFn(torch.autograd.Function):
-    """The clipped pair: forward lq_fq_forward_clip, backward lq_fq_backward_clip.  ``want_ds``: the scale receives the LSQ
-    gradient (scale_gradient="ste"); otherwise zeros like the STE-only op (the loss-term-only rule) and the kernel's sum is
-    dropped."""
+    """The clipped pair: forward lq_fq_forward_clip_r, backward lq_fq_backward_clip_r (``rounding``: floor or nearest).
+    ``want_ds``: the scale receives the LSQ gradient (scale_gradient="ste"); otherwise zeros like the STE-only op (the
+    loss-term-only rule) and the kernel's sum is dropped."""
 
     @staticmethod
-    def forward(ctx, parameter, scale, qmin, qmax, grad_scale, want_ds):
+    def forward(ctx, parameter, scale, qmin, qmax, grad_scale, want_ds, rounding="floor"):
         ctx.save_for_backward(parameter, scale)
+        ctx.rounding = rounding
         ctx.q_range = (int(qmin), int(qmax))
         ctx.grad_scale = float(grad_scale)
         ctx.want_ds = bool(want_ds)
-        return fq_forward_clip(parameter, scale, qmin, qmax)
+        return fq_forward_clip(parameter, scale, qmin, qmax, rounding=rounding)
 
     @staticmethod
     def backward(ctx, dy):
         parameter, scale = ctx.saved_tensors
         want_ds = ctx.want_ds and ctx.needs_input_grad[1]
-        dP, ds, _ = fq_backward_clip(parameter, scale, dy, *ctx.q_range, grad_scale=ctx.grad_scale, want_ds=want_ds)
+        dP, ds, _ = fq_backward_clip(parameter, scale, dy, *ctx.q_range, grad_scale=ctx.grad_scale, want_ds=want_ds,
+                                     rounding=ctx.rounding)
         if ds is None and ctx.needs_input_grad[1]:
             ds = torch.zeros_like(scale)
-        return (dP if ctx.needs_input_grad[0] else None), ds, None, None, None, None
+        return (dP if ctx.needs_input_grad[0] else None), ds, None, None, None, None, None
 
 
 SCALE_GRADIENTS = (None, "ste")
 
 
 def my_custom_gradient(parameter, scale, penalty_threshold=None, *, scale_gradient=None, grad_scale=1.0, defer_scale_grad=False,
-                       q_range=None):
+                       q_range=None, rounding="floor"):
     """The reference op.  With ``penalty_threshold`` -> nested-quantization variant
     (custom_layers.py:49-120); without -> STE-only variant (CL custom_layers.py:49-64).
     ``scale_gradient="ste"`` (not in the reference, only without ``penalty_threshold``): the scale receives the
@@ -538,9 +557,12 @@ def my_custom_gradient(parameter, scale, penalty_threshold=None, *, scale_gradie
     all-reduced dP (exact data-parallel mode, ddp.py).
     ``q_range=(qmin, qmax)`` (not in the reference, only without ``penalty_threshold``): the clipped quantizer -- integers
     saturate at the range, clipped elements pass no gradient to ``parameter``; with ``scale_gradient="ste"`` the scale gets the
-    LSQ gradient (clipped elements pull it by ``dy * qmin`` / ``dy * qmax``), with ``None`` it gets zeros."""
+    LSQ gradient (clipped elements pull it by ``dy * qmin`` / ``dy * qmax``), with ``None`` it gets zeros.
+    ``rounding="nearest"`` (not in the reference, only with ``q_range``): the integers are rint(P/s), round half to even, instead
+    of floor(P/s), and the LSQ residual is rint(t) - t in [-1/2, 1/2]."""
     if scale_gradient not in SCALE_GRADIENTS:
         raise ValueError(f"scale_gradient must be one of {SCALE_GRADIENTS}, got {scale_gradient!r}")
+    check_rounding(rounding, q_range is not None)
     if q_range is not None:
         if penalty_threshold is not None:
             raise ValueError("q_range with a penalty_threshold: the nested-quantization vote is defined on the unclipped "
@@ -549,7 +571,7 @@ def my_custom_gradient(parameter, scale, penalty_threshold=None, *, scale_gradie
             raise ValueError("q_range with defer_scale_grad: the all-reduced dP of a clipped layer no longer holds the dy of its "
                              "clipped elements, so ds cannot be recomputed from it")
         qmin, qmax = check_q_range(*q_range)
-        return _ClipQuantFn.apply(parameter, scale, qmin, qmax, float(grad_scale), scale_gradient == "ste")
+        return _ClipQuantFn.apply(parameter, scale, qmin, qmax, float(grad_scale), scale_gradient == "ste", rounding)
     if scale_gradient == "ste":
         if penalty_threshold is not None:
             raise ValueError('scale_gradient="ste" replaces the nested-quantization vote: it needs penalty_threshold=None')

@@ -31,7 +31,7 @@ from . import _hip
 from .ddp import CaptureRefused, DataParallel, capture_with_agreement, control_group
 from .losses import LossLog, SCCEDifference, SCCEInverse, SCCEMaxBin, sparse_categorical_crossentropy
 from .models import INPUT_SHAPES, build_model, check_clip_mode
-from .ops import q_range_of
+from .ops import ROUNDINGS, check_rounding, q_range_of
 from .optim import KerasAdam, ScaleAdam, non_scale_parameters, scale_parameters
 
 LOSSES = {"maxbin": SCCEMaxBin, "difference": SCCEDifference, "inverse": SCCEInverse}
@@ -55,8 +55,9 @@ class Trainer:
     "ste" (the straight-through scale gradient of ops.fq_scale_grad_ste, no loss term, ``value`` ignored) and "stecl" (the
     same plus a loss term: ``value`` = penalty_rate, ``loss`` names the term); ``grad_scale`` is their factor k, a float
     or "rsqrt_group".  ``bits`` (with ``signed``) or ``q_range`` (modes "cl", "ste", "stecl"; eager and graphed, per-tensor
-    path, data-parallel mode "A") gives every quantised tensor the clipped quantizer with that integer range.  Both are linear in dy: data-parallel mode "A" (average ds over the ranks) already is the global-batch
-    gradient, mode "B" is refused.
+    path, data-parallel mode "A") gives every quantised tensor the clipped quantizer with that integer range; with
+    ``rounding="nearest"`` that quantizer rounds P/s to the nearest integer, ties to even, instead of down.  Both rules are linear
+    in dy: data-parallel mode "A" (average ds over the ranks) already is the global-batch gradient, mode "B" is refused.
 
     A step is two phases: ``_backward_phase`` (zero the gradients, fake-quantise, forward, loss, backward, penalty
     injection) and ``_update_phase`` (exact-mode scale gradients, both optimizers); between them the data-parallel
@@ -71,7 +72,7 @@ class Trainer:
                  lr=1e-4, seed=42, device=None, ddp_mode="A", log_dir="logs", graph=False, batched=False,
                  bucket_mb: float = 25.0, overlap: bool = True, graph_collectives: Optional[bool] = None,
                  force_collectives: bool = False, kernel_storage: str = "oihw", loss_values: bool = False,
-                 loss_log_capacity: int = 4096, grad_scale=None, bits=None, signed=True, q_range=None):
+                 loss_log_capacity: int = 4096, grad_scale=None, bits=None, signed=True, q_range=None, rounding="floor"):
         """``loss_values`` (modes with a loss term): the step also EVALUATES the penalty -- batched: as a by-product of the
         gradient injection (lq_batch_penalty_grads_values); per-tensor path: the loss object's own device scalar -- appends the
         reference's three per-step numbers (CL-F:58-71) to a device-side ``LossLog`` (no synchronisation, capturable) and
@@ -94,6 +95,8 @@ class Trainer:
             raise ValueError("grad_scale belongs to the modes 'ste' and 'stecl'")
         # ``bits`` / ``signed`` or ``q_range``: the clipped quantizer for every quantised tensor (layers.py), per-tensor path
         self.q_range = q_range_of(bits, signed, q_range)
+        check_rounding(rounding, self.q_range is not None)
+        self.rounding = rounding
         if self.q_range is not None:
             check_clip_mode(mode)
             if ddp_mode == "B":
@@ -105,7 +108,7 @@ class Trainer:
         # conv kernels shaped HWIO like the reference's, stored in the order MIOpen consumes (layers.py kernel_storage): the
         # fake-quantised kernel goes to the convolution as written and its weight gradient is dP
         self.model = build_model(config, mode=mode, value=value, seed=seed, orientation=orientation, device=self.device,
-                                 kernel_storage=kernel_storage, grad_scale=grad_scale, q_range=self.q_range)
+                                 kernel_storage=kernel_storage, grad_scale=grad_scale, q_range=self.q_range, rounding=rounding)
         self.model.to(self.device)
         self.custom_layers = L.custom_layers_of(self.model)
         self.loss_obj = None
@@ -388,6 +391,8 @@ def main(argv=None):
     ap.add_argument("--bits", type=int, default=None,
                     help="modes cl / ste / stecl: clipped b-bit quantizer, integers in [-2^(b-1), 2^(b-1) - 1] (1 <= b <= 24)")
     ap.add_argument("--unsigned", action="store_true", help="with --bits: integers in [0, 2^b - 1]")
+    ap.add_argument("--rounding", default="floor", choices=list(ROUNDINGS),
+                    help="with --bits: round P/s down (the reference's floor) or to nearest, ties to even")
     ap.add_argument("--rate", type=float, default=1e-7, help="penalty_rate of the loss term in mode nqcl")
     ap.add_argument("--value-coarse", type=float, default=None,
                     help="resnet50 only: threshold of the 3x3 kernels ('mixed' quantisation intensity); --value is the rest")
@@ -453,7 +458,7 @@ def main(argv=None):
                  loss_values=args.loss_values, loss_log_capacity=max(4096, args.steps + args.warmup + 8),
                  grad_scale=(None if args.grad_scale is None else
                              (args.grad_scale if args.grad_scale == "rsqrt_group" else float(args.grad_scale))),
-                 bits=args.bits, signed=not args.unsigned)
+                 bits=args.bits, signed=not args.unsigned, rounding=args.rounding)
     do_step = tr.step_graphed if args.graph else tr.step
     g = torch.Generator(device=dev).manual_seed(args.seed + rank)
     batches = [synthetic_batch(args.config, args.batch, dev, g) for _ in range(4)]
@@ -488,6 +493,7 @@ def main(argv=None):
             "backend": (args.backend if use_dist else None),
             "channels_last": bool(args.channels_last), "kernel_storage": args.kernel_storage,
             **({"q_range": list(tr.q_range)} if tr.q_range else {}),
+            **({"rounding": tr.rounding} if tr.rounding != "floor" else {}),
             **({"loss_values": True, "loss_log_rows": log_rows[0], "loss_log_dropped": log_rows[1]} if log_rows else {})}))
         if args.export_dir:
             from .export import save_compress_parameters

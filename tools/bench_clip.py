@@ -3,13 +3,17 @@
 
   * ``lq_fq_forward_clip`` against ``lq_fq_forward`` (one read, one write);
   * ``lq_fq_backward_clip`` against ``lq_fq_fwd_bwd_fused`` (two reads, one write, a per-group reduction);
+  * the round-to-nearest pair (``lq_fq_forward_clip_r`` / ``lq_fq_backward_clip_r`` with LQ_ROUND_NEAREST_EVEN) against the floor
+    pair, which is its yardstick.  The margin is the floor pair's own spread: the rounds are cut into ``--repeats`` consecutive
+    blocks, each block has its median, and ``*_floor_spread`` is (max - min) / median of the floor kernel's block medians; a
+    ``nearest_*_over_floor`` ratio further from 1 than that spread is outside the margin;
 
 on the BENCH tensor (256, 3, 50176) and on the largest ResNet-18-like weight (3, 3, 512, 512), channel-wise, stored OIHW.
 Raw C-ABI calls into preallocated outputs; every round times each variant once (event-timed run of ``--inner`` back-to-back
 calls, each on the next buffer set), the rounds interleave the variants, the figure is the median over the rounds.  One JSON
 line per tensor.  Run it under ``rocprofv3 --kernel-trace --stats`` for the per-kernel figures.
 
-    python tools/bench_clip.py [--rounds 15] [--inner 10] [--sets 3]
+    python tools/bench_clip.py [--rounds 15] [--inner 10] [--sets 3] [--repeats 3]
 """
 import argparse
 import json
@@ -32,6 +36,7 @@ def main():
     ap.add_argument("--inner", type=int, default=10)
     ap.add_argument("--sets", type=int, default=3)
     ap.add_argument("--bits", type=int, default=4)
+    ap.add_argument("--repeats", type=int, default=3, help="blocks of rounds whose medians give the floor pair's own spread")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     lib = _hip.load()
@@ -73,7 +78,23 @@ def main():
             _hip.check(lib.lq_fq_backward_clip(ptr(P), ptr(s0), ptr(dy), qmin, qmax, 1.0, ptr(out), None, None, ptr(ws),
                                                ws.numel(), outer, G, inner, sp), "bwd_clip_mask")
 
-        variants = {"forward": fwd, "forward_clip": fwd_clip, "fused": fused, "backward_clip": bwd_clip, "backward_clip_mask_only": bwd_clip_mask}
+        nearest = 1      # LQ_ROUND_NEAREST_EVEN
+
+        def fwd_clip_rne(P, dy, out):
+            _hip.check(lib.lq_fq_forward_clip_r(ptr(P), ptr(s0), ptr(out), None, _hip.LQ_Q_NONE, qmin, qmax, nearest, outer, G, inner, sp),
+                       "fwd_clip_rne")
+
+        def bwd_clip_rne(P, dy, out):
+            _hip.check(lib.lq_fq_backward_clip_r(ptr(P), ptr(s0), ptr(dy), qmin, qmax, nearest, 1.0, ptr(out), ptr(ds), ptr(clipped), ptr(ws),
+                                                 ws.numel(), outer, G, inner, sp), "bwd_clip_rne")
+
+        def bwd_clip_rne_mask(P, dy, out):
+            _hip.check(lib.lq_fq_backward_clip_r(ptr(P), ptr(s0), ptr(dy), qmin, qmax, nearest, 1.0, ptr(out), None, None, ptr(ws),
+                                                 ws.numel(), outer, G, inner, sp), "bwd_clip_rne_mask")
+
+        variants = {"forward": fwd, "forward_clip": fwd_clip, "forward_clip_nearest": fwd_clip_rne, "fused": fused,
+                    "backward_clip": bwd_clip, "backward_clip_nearest": bwd_clip_rne, "backward_clip_mask_only": bwd_clip_mask,
+                    "backward_clip_nearest_mask_only": bwd_clip_rne_mask}
         times = {k: [] for k in variants}
         k_set = 0
         for fn in variants.values():
@@ -100,6 +121,23 @@ def main():
         row["tb_per_s_backward_clip"] = 12 * n / row["us_backward_clip"] / 1e6
         row["forward_clip_over_forward"] = row["us_forward_clip"] / row["us_forward"]
         row["backward_clip_over_fused"] = row["us_backward_clip"] / row["us_fused"]
+
+        def block_medians(key):
+            n_blocks = max(1, min(args.repeats, len(times[key])))
+            size = len(times[key]) // n_blocks
+            return [statistics.median(times[key][b * size:(b + 1) * size]) for b in range(n_blocks)]
+
+        for what, floor_key, near_key in (("forward", "forward_clip", "forward_clip_nearest"),
+                                          ("backward", "backward_clip", "backward_clip_nearest"),
+                                          ("backward_mask_only", "backward_clip_mask_only", "backward_clip_nearest_mask_only")):
+            blocks = block_medians(floor_key)
+            row[f"us_{floor_key}_block_medians"] = blocks
+            row[f"us_{near_key}_block_medians"] = block_medians(near_key)
+            spread = (max(blocks) - min(blocks)) / row[f"us_{floor_key}"]
+            ratio = row[f"us_{near_key}"] / row[f"us_{floor_key}"]
+            row[f"{what}_floor_spread"] = spread
+            row[f"nearest_{what}_over_floor"] = ratio
+            row[f"nearest_{what}_within_floor_spread"] = abs(ratio - 1.0) <= spread
         print(json.dumps(row), flush=True)
         del sets
 

@@ -243,7 +243,7 @@ typedef struct lq_tensor_desc {
     float min_value;     /* MinValueConstraint bound used by lq_batch_scale_adam */
     /* conv kernels (HWIO, custom_layers.py:321): optional OIHW companions, see lq_fq_forward_oihw below; conv_co = 0: none */
     float* out_oihw;     /* second forward output in OIHW order, or NULL          */
-    float* dp;           /* dP in HWIO order, written by lq_batch_scale_grad_oihw */
+    float* dp;           /* dP in HWIO order, written by lq_batch_scale_grad_oihw; conv_co = 0: dP of lq_batch_backward_clip, else unused */
     int64_t conv_hw, conv_ci, conv_co;   /* kh*kw, input channels, output channels  */
 } lq_tensor_desc;
 
@@ -289,6 +289,30 @@ int lq_batch_penalty_grads(const lq_batch* batch, int kind, const float* coeff, 
  * To add a loss term's scale gradient, call lq_batch_penalty_grads[_values] with LQ_PENALTY_ACCUMULATE_DS afterwards.     */
 int lq_batch_scale_grad_ste(const lq_batch* batch, const float* const* dy, const float* grad_scale,
                             void* ws, size_t ws_bytes, void* stream);
+
+/* Clipped b-bit tensors in the batch (opt-in): lq_fq_forward_clip_r / lq_fq_backward_clip_r of every tensor, each with its own
+ * integer range, one rounding per batch.
+ * lq_batch_set_clip: HOST call (allocates and uploads: never inside a capture; a repeated call replaces the ranges).  qmin / qmax:
+ *   host int32[n], indexed like the descriptors, each pair under the single-tensor rule (qmin <= qmax, |q| <= 2^24); rounding:
+ *   LQ_ROUND_FLOOR or LQ_ROUND_NEAREST_EVEN; n must be the batch's tensor count.  Every tensor needs conv_co == 0 (no OIHW
+ *   companions: store conv kernels in the order the convolution consumes) and a `dp` buffer of the parameter's size, which
+ *   receives dP.  The clipped pair runs on task tables of its own (generic traversal bodies); a tensor whose traversal uses 16-byte
+ *   accesses and whose `dp` is not 16-byte aligned is refused here with LQ_EALIGN.  lq_batch_workspace_bytes covers the pair
+ *   afterwards (query it after this call).
+ * lq_batch_forward_clip: ONE launch, out_i = clamp(rnd(P_i / s_i), qmin_i, qmax_i) * s_i, bit-identical to the single-tensor call.
+ * lq_batch_backward_clip: TWO launches (traversal + finalize).  dy as for lq_batch_scale_grad_ste (NULL entry: LQ_EINVAL; 4-byte
+ *   alignment; 16-byte alignment where the tensor's traversal needs it: LQ_EALIGN).  Writes dP_i = inside ? dy_i : 0 to `dp`, the
+ *   exact per-group clip counts to batch-owned memory (lq_batch_clip_counts) and -- grad_scale != NULL, host float[n] --
+ *   ds_i[g] = (float)(grad_scale[i] * sum dy * r) to the descriptors' ds (every tensor then needs one).  grad_scale == NULL is
+ *   "mask only": ds is not written at all.  dP and the counts are bit-identical to the single-tensor call; ds carries its "no
+ *   bit-identity across traversals" note.  Moves 12 bytes per element (P, dy, dP).
+ * Both return LQ_EINVAL on a batch without ranges; they only enqueue, never allocate, and can be captured.
+ * lq_batch_clip_counts: device address of tensor `tensor`'s clip counts (uint32[groups], rewritten by every backward).     */
+int lq_batch_set_clip(lq_batch* batch, const int32_t* qmin, const int32_t* qmax, int n, int rounding);
+int lq_batch_forward_clip(const lq_batch* batch, void* stream);
+int lq_batch_backward_clip(const lq_batch* batch, const float* const* dy, const float* grad_scale, void* ws, size_t ws_bytes,
+                           void* stream);
+int lq_batch_clip_counts(const lq_batch* batch, int tensor, const uint32_t** dev, int64_t* groups);
 
 /* VALUE of the custom-loss-term penalty for the whole batch (compute_{maxbin,difference,inverse}_penalty,
  *   custom_loss_functions.py:75-116, 161-195, 240-275), the number compute_total_loss adds to the cross-entropy (:47-58).

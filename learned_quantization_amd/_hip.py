@@ -86,6 +86,10 @@ SIGNATURES.update({
     "lq_batch_forward": (_c_int, [_c_p, _c_p]),
     "lq_batch_scale_grad": (_c_int, [_c_p, ctypes.POINTER(_c_p), _c_p, _c_sz, _c_p]),
     "lq_batch_scale_grad_ste": (_c_int, [_c_p, ctypes.POINTER(_c_p), ctypes.POINTER(_c_f), _c_p, _c_sz, _c_p]),
+    "lq_batch_set_clip": (_c_int, [_c_p, ctypes.POINTER(_c_i32), ctypes.POINTER(_c_i32), _c_int, _c_int]),
+    "lq_batch_forward_clip": (_c_int, [_c_p, _c_p]),
+    "lq_batch_backward_clip": (_c_int, [_c_p, ctypes.POINTER(_c_p), ctypes.POINTER(_c_f), _c_p, _c_sz, _c_p]),
+    "lq_batch_clip_counts": (_c_int, [_c_p, _c_int, ctypes.POINTER(_c_p), ctypes.POINTER(_c_i64)]),
     "lq_batch_scale_grad_step": (_c_int, [_c_p, ctypes.POINTER(_c_p), _c_int, _c_p, _c_sz, _c_d, _c_d, _c_d, _c_d, _c_i64, _c_p, _c_int, _c_p]),
     "lq_batch_scale_grad_oihw": (_c_int, [_c_p, ctypes.POINTER(_c_p), _c_p, _c_sz, _c_p]),
     "lq_conv_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64]),

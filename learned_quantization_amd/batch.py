@@ -27,6 +27,7 @@ import torch
 from . import _hip
 from .descriptor import memory_descriptor
 from .layers import CustomDenseLayer, _ConvBase, custom_layers_of
+from .ops import ROUNDINGS
 
 
 class _Entry:
@@ -34,9 +35,16 @@ class _Entry:
                  "nq")
 
 
+class _DeviceInts:
+    """A window onto int32 device memory the library owns, for ``torch.as_tensor`` (no copy, no ownership)."""
+
+    def __init__(self, address: int, count: int):
+        self.__cuda_array_interface__ = {"shape": (int(count),), "typestr": "<i4", "data": (int(address), False), "version": 2}
+
+
 class FakeQuantBatch:
     def __init__(self, model_or_layers, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-7, mode: str = "keras",
-                 oihw: bool = True, hwio_out: bool = True, autograd: bool = True):
+                 oihw: bool = True, hwio_out: bool = True, autograd: bool = True, clipped: bool = False):
         """``autograd=True``: ``quantize_all()`` is ONE autograd node (2 x tensors inputs, one output per tensor) and everything happens
         inside ``loss.backward()``.  Convenient -- and, for 40 tensors, 0.4-0.6 ms of autograd-engine work per step (an 80-input node,
         40 output wrappers, an AccumulateGrad per parameter that adds into the data-parallel bucket with a launch of its own).
@@ -47,7 +55,13 @@ class FakeQuantBatch:
         ``oihw``: conv kernels of nested-quantization layers get an OIHW companion output (what MIOpen consumes).
         ``hwio_out=False``: where the LDS-tile kernel writes that companion, the HWIO output is not materialised at all -- in a
         training step the convolution is the kernel's only consumer (custom_layers.py:340-348), so the forward moves 8 bytes
-        per element instead of 12; ``quantize_all()`` then returns the HWIO tensor as a permuted VIEW of the companion."""
+        per element instead of 12; ``quantize_all()`` then returns the HWIO tensor as a permuted VIEW of the companion.
+        ``clipped=True`` (opt-in): a batch of clipped b-bit layers (``bits`` / ``q_range``, each tensor its own range, one
+        ``rounding`` and one rule -- ``scale_gradient`` ``None`` or ``"ste"`` -- for all).  ``quantize_all()`` is
+        ``lq_batch_forward_clip``; the backward is ``lq_batch_backward_clip``, which writes the masked ``dP`` of every tensor into a
+        buffer the batch owns (one per tensor, handed to the parameters) and reads 12 bytes per element (P, dy, dP) where the
+        unclipped batch reads 8.  Not combined with ``defer_scale_grads`` / ``scale_grads_from_param_grads`` (a masked dP no
+        longer holds the dy of the clipped elements) nor with ``BatchedScaleAdam(fused=True)``."""
         layers = custom_layers_of(model_or_layers) if isinstance(model_or_layers, torch.nn.Module) else list(model_or_layers)
         self.layers = layers
         self.autograd = bool(autograd)
@@ -57,13 +71,27 @@ class FakeQuantBatch:
         self.entries: List[_Entry] = []
         nested_layers = [getattr(layer, a) for layer in layers for a in ("nested_q_w_layer", "nested_q_k_layer", "nested_q_b_layer")
                          if hasattr(layer, a)]
-        if any(getattr(n, "q_range", None) is not None for n in nested_layers):
+        self.clipped = bool(clipped)
+        if not self.clipped and any(getattr(n, "q_range", None) is not None for n in nested_layers):
             raise ValueError("FakeQuantBatch over a clipped layer (bits / q_range): the multi-tensor backward hands dy on as dP, "
-                             "but a clipped layer's dP is a masked copy of dy; run such a model on the per-tensor path (batched=False)")
+                             "but a clipped layer's dP is a masked copy of dy; run such a model on the per-tensor path (batched=False), "
+                             "or opt in to the clipped batch, which owns a dP buffer per tensor: FakeQuantBatch(..., clipped=True)")
         rules = {n.scale_gradient for n in nested_layers}
         if "ste" in rules and len(rules) > 1:
             raise ValueError('one FakeQuantBatch holds one scale-gradient rule: every layer needs scale_gradient="ste", or none')
         self.ste = "ste" in rules            # every scale gradient of the batch is the straight-through one
+        self.rounding = "floor"
+        if self.clipped:
+            if any(getattr(n, "q_range", None) is None for n in nested_layers):
+                raise ValueError("FakeQuantBatch(clipped=True) over a layer without a range: every quantised tensor of a clipped batch "
+                                 "needs bits / q_range (an unclipped model runs the default batch)")
+            roundings = {n.rounding for n in nested_layers}
+            if len(roundings) > 1:
+                raise ValueError(f"one clipped FakeQuantBatch holds one rounding, got {sorted(roundings)}")
+            self.rounding = next(iter(roundings), "floor")
+            if any(isinstance(layer, _ConvBase) and layer.kernel_storage == "hwio" for layer in layers):
+                raise ValueError('a clipped batch takes conv kernels in the memory order the convolution '
+                                 'consumes: build it with kernel_storage="oihw"')
         for layer in layers:
             if isinstance(layer, _ConvBase):
                 pairs = [(0, layer.kernel, layer.nested_q_k_layer)]
@@ -113,6 +141,8 @@ class FakeQuantBatch:
                     if (not hwio_out and param.data_ptr() % 16 == 0
                             and _hip.load().lq_conv_tile_supported(kh * kw, ci, co, *e.desc) == 1):
                         e.out = None               # the companion is the only forward output of this tensor
+                if self.clipped:
+                    e.dp = torch.empty_like(param.data)            # the masked dP (lq_batch_backward_clip), in the parameter's element order
                 self.entries.append(e)
         if not self.entries:
             raise ValueError("no custom layers")
@@ -131,6 +161,10 @@ class FakeQuantBatch:
         handle = ctypes.c_void_p()
         _hip.check(lib.lq_batch_create(arr, n, ctypes.byref(handle)), "lq_batch_create")
         self._handle = handle
+        if self.clipped:
+            qmin = (ctypes.c_int32 * n)(*[int(e.nested.q_range[0]) for e in self.entries])
+            qmax = (ctypes.c_int32 * n)(*[int(e.nested.q_range[1]) for e in self.entries])
+            _hip.check(lib.lq_batch_set_clip(handle, qmin, qmax, n, ROUNDINGS.index(self.rounding)), "lq_batch_set_clip")
         self._ptrs = (ctypes.c_void_p * n)()
         self._grad_scales = (ctypes.c_float * n)(*[e.nested.grad_scale_value(e.param.numel()) for e in self.entries]) if self.ste else None
         self.ws = torch.empty(lib.lq_batch_workspace_bytes(handle), dtype=torch.uint8, device=self.device)
@@ -188,8 +222,15 @@ class FakeQuantBatch:
                                         outs[self._oihw_pos[ik]] if ik in self._oihw_pos else None)
         return outs[:n]
 
+    def _forward_call(self):
+        lib = _hip.load()
+        if self.clipped:
+            _hip.check(lib.lq_batch_forward_clip(self._handle, _hip.stream_ptr(self.device)), "lq_batch_forward_clip")
+        else:
+            _hip.check(lib.lq_batch_forward(self._handle, _hip.stream_ptr(self.device)), "lq_batch_forward")
+
     def _quantize_all_leaves(self):
-        _hip.check(_hip.load().lq_batch_forward(self._handle, _hip.stream_ptr(self.device)), "lq_batch_forward")
+        self._forward_call()
         self._awaiting_finish = True
         for lf in self._all_leaves:
             lf.grad = None
@@ -214,6 +255,7 @@ class FakeQuantBatch:
             # a second call would add dP to the parameters' gradients (bucket views) once more
             raise RuntimeError("finish_backward() without a quantize_all() since the last call: one backward pass per forward")
         self._awaiting_finish = False
+        self._refuse_deferred_clip()
         if self._static_pre is not None and not self.defer_scale_grads:
             dps = self._leaf_grads_core()
         else:
@@ -224,6 +266,8 @@ class FakeQuantBatch:
             p = e.param
             if p.grad is None:
                 p.grad = dp                                # by reference: no launch (what AccumulateGrad does with a fresh gradient)
+            elif p.grad.data_ptr() == dp.data_ptr():
+                pass                                       # clipped batch: the parameter still holds the batch's dP buffer, just rewritten
             else:
                 add_to.append(p.grad)                      # a data-parallel bucket view, or the gradient a regulariser left there
                 add_from.append(dp)
@@ -259,6 +303,8 @@ class FakeQuantBatch:
         for e in self.entries:
             if e.nq:
                 e.nested.scale.grad = e.ds                 # written in place by the kernel: no accumulate launch
+        if self.clipped:
+            return [e.dp for e in entries]                 # the masked copies of dy the launch has just written
         return dps
 
     def _scale_grad_call(self, oihw: bool):
@@ -267,6 +313,11 @@ class FakeQuantBatch:
         lib = _hip.load()
         opt = self._fused_opt
         sp = _hip.stream_ptr(self.device)
+        if self.clipped:
+            # dP of every tensor into the batch's buffers, the clip counts, and -- rule "ste" -- ds; mask only: no grad_scale, ds untouched
+            _hip.check(lib.lq_batch_backward_clip(self._handle, self._ptrs, self._grad_scales, _hip.ptr(self.ws), self.ws.numel(), sp),
+                       "lq_batch_backward_clip")
+            return
         if self.ste:
             _hip.check(lib.lq_batch_scale_grad_ste(self._handle, self._ptrs, self._grad_scales, _hip.ptr(self.ws), self.ws.numel(), sp),
                        "lq_batch_scale_grad_ste")
@@ -293,6 +344,7 @@ class FakeQuantBatch:
         """``dys``: upstream gradient of every HWIO-shaped output, then of every OIHW companion (``None`` where nothing consumed
         it).  Launches the scale-gradient pass (unless deferred), sets ``scale.grad`` and returns ``dP`` per tensor."""
         batch = self
+        batch._refuse_deferred_clip()
         n = len(batch.entries)
         # a conv kernel with an OIHW companion: its consumer (the convolution) used the companion, so the gradient arrives there,
         # in OIHW order; a consumer that used the HWIO output instead is served by the plain path below
@@ -334,6 +386,8 @@ class FakeQuantBatch:
             for e in batch.entries:
                 if e.nq:
                     e.nested.scale.grad = e.ds                     # written in place by the kernel: no accumulate launch
+            if batch.clipped:
+                return [e.dp for e in batch.entries]               # the masked copies of dy the launch has just written
             return keep
         for i, e in enumerate(batch.entries):
             d = dys[i]
@@ -363,12 +417,34 @@ class FakeQuantBatch:
         assert len(dps) == n
         return dps
 
+    def _refuse_deferred_clip(self):
+        if self.clipped and self.defer_scale_grads:
+            raise ValueError("a clipped FakeQuantBatch cannot defer its scale gradients (data-parallel mode B): the exchanged dP is a "
+                             "masked copy of dy and no longer holds the dy of the clipped elements; use mode A")
+
+    def clip_counts(self):
+        """Clipped batch: per entry, the number of elements the latest backward found outside the range, per group (int32, in
+        the shape of the entry's scale; exact).  Copies of the library's device buffers: no synchronisation."""
+        if not self.clipped:
+            raise RuntimeError("clip_counts() belongs to FakeQuantBatch(clipped=True)")
+        lib = _hip.load()
+        out = []
+        for i, e in enumerate(self.entries):
+            dev, groups = ctypes.c_void_p(), ctypes.c_int64()
+            _hip.check(lib.lq_batch_clip_counts(self._handle, i, ctypes.byref(dev), ctypes.byref(groups)), "lq_batch_clip_counts")
+            view = torch.as_tensor(_DeviceInts(dev.value, groups.value), device=self.device)
+            out.append(view.clone().reshape(e.nested.scale.shape))
+        return out
+
     # ------------------------------------------------------------------ exact data-parallel mode (ddp.py, mode B)
     def scale_grads_from_param_grads(self):
         """ds of every nested-quantization tensor from its parameter's CURRENT gradient, in two launches.  After the
         data-parallel all-reduce ``P.grad`` is the global-batch dy (dP == dy, custom_layers.py:118), so this yields the
         single-device large-batch scale gradient, identical on every rank."""
         lib = _hip.load()
+        if self.clipped:
+            raise ValueError("scale_grads_from_param_grads() reads P.grad as dy; a clipped batch's dP is a masked copy of dy, which "
+                             "no longer holds the dy of the clipped elements: average ds over the ranks (data-parallel mode A)")
         if self.ste:
             raise RuntimeError("scale_grads_from_param_grads() is the exact mode of the nested-quantization vote; the straight-through "
                                "scale gradient is linear in dy: average ds over the ranks (data-parallel mode A)")
@@ -468,8 +544,7 @@ class FakeQuantBatch:
 class _BatchFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, batch: FakeQuantBatch, *tensors):
-        lib = _hip.load()
-        _hip.check(lib.lq_batch_forward(batch._handle, _hip.stream_ptr(batch.device)), "lq_batch_forward")
+        batch._forward_call()
         ctx.batch = batch
         ctx.set_materialize_grads(False)        # an output nobody consumed arrives as None in backward, not as a zero tensor
         # fresh tensor objects over the static buffers: every HWIO output, then the OIHW companions of the conv kernels
@@ -500,6 +575,9 @@ class BatchedScaleAdam:
         self.capturable = capturable
         self._applied = False
         if fused:
+            if batch.clipped:
+                raise ValueError("the fused finalize + Adam launch exists for the nested-quantization vote only: "
+                                 "build BatchedScaleAdam(fused=False) for a clipped batch")
             if batch.ste:
                 raise ValueError("the fused finalize + Adam launch exists for the nested-quantization vote only: "
                                  'build BatchedScaleAdam(fused=False) for a scale_gradient="ste" model')

@@ -22,7 +22,7 @@ struct Task {
     Params p;                 // pa/pb/pc are rebound to the batch workspace inside the kernel
     ConvTile ct;              // mode == MODE_CONV_TILE
     float* ds;                // scale gradient output [G]
-    float* dp;                // dP in HWIO order (conv kernels with an OIHW companion), else NULL
+    float* dp;                // dP in HWIO order (conv kernels with an OIHW companion); clipped tables: dP of the tensor; else NULL
     float* am;                // Adam moments of the scale (fused update in the finalize), or NULL
     float* av;
     float amin;               // MinValueConstraint of the scale
@@ -97,6 +97,10 @@ __global__ __launch_bounds__(kBlock) void k_batch_traverse(const Task* __restric
         p.c_scale = cf.c[ti];
         p.mb = t.mb;
         p.ties = t.ties;
+    }
+    if constexpr (OP == OP_CLIP_BWD || OP == OP_CLIP_BWD_RNE) {      // tables of their own (lq_batch_set_clip): the stored value is dP
+        p.out = t.dp;
+        p.dy = pk.dy[ti];
     }
     p.pa = ws + t.ws_off;
     p.pb = p.pa + t.np_pad;
@@ -173,7 +177,8 @@ __global__ __launch_bounds__(kBlock) void k_batch_traverse(const Task* __restric
 template <int OP, int BS, bool SECOND>
 __device__ __forceinline__ void batch_finalize_body(const Task* __restrict__ tasks, const uint32_t* __restrict__ gprefix, int ntasks,
                                                     uint32_t* ws, int accum, uint32_t gb,      // gb: group of the batch
-                                                    const CoefPack* cf = nullptr) {            // cf: per-task Params::c_scale
+                                                    const CoefPack* cf = nullptr,              // cf: per-task Params::c_scale
+                                                    int mask_only = 0) {                       // OP_CLIP_BWD: ds is not written at all
     const int ti = find_task(gprefix, ntasks, gb);
     const Task& t = tasks[ti];
     Params p = t.p;
@@ -191,6 +196,10 @@ __device__ __forceinline__ void batch_finalize_body(const Task* __restrict__ tas
     f.o0 = (OP == OP_MAXBIN_FWD || OP == OP_DIFF_FWD) ? t.mb : t.ds;     // OP_DIFF_FWD: the group's mean |P - P/s| (penalty value)
     f.o1 = nullptr;
     f.o2 = (OP == OP_MAXBIN_FWD) ? t.ties : nullptr;
+    if constexpr (OP == OP_CLIP_BWD) {       // the clipped tables keep the batch-owned clip counts in the `ties` slot
+        f.o0 = mask_only ? nullptr : t.ds;
+        f.o2 = t.ties;
+    }
     f.accum = accum;
     finalize_block_body<OP, BS>(p, f, (int64_t)(gb - t.first_group), (int)threadIdx.x);
 }
@@ -204,6 +213,12 @@ __global__ __launch_bounds__(BS) void k_batch_finalize(const Task* __restrict__ 
 __global__ __launch_bounds__(64) void k_batch_finalize_ste(const Task* __restrict__ tasks, const uint32_t* __restrict__ gprefix, int ntasks,
                                                            uint32_t* ws, CoefPack cf) {
     batch_finalize_body<OP_STE_SCALE, 64, false>(tasks, gprefix, ntasks, ws, 0, blockIdx.x, &cf);
+}
+// Finalize of k_batch_traverse<OP_CLIP_BWD[_RNE]> (FinT<OP_CLIP_BWD_RNE> is FinT<OP_CLIP_BWD>: one kernel serves both roundings):
+// ds[g] = (float)(k * sum) with k = cf.c[task] unless `mask_only`, and the exact clip count of every group
+__global__ __launch_bounds__(64) void k_batch_finalize_clip(const Task* __restrict__ tasks, const uint32_t* __restrict__ gprefix, int ntasks,
+                                                            uint32_t* ws, CoefPack cf, int mask_only) {
+    batch_finalize_body<OP_CLIP_BWD, 64, false>(tasks, gprefix, ntasks, ws, 0, blockIdx.x, &cf, mask_only);
 }
 // Finalize of k_batch_traverse<OP_DIFF_BWD_V> in ONE launch of 2 * groups one-wave blocks: the first `groups` blocks are
 // k_batch_finalize<OP_DIFF_BWD> (ds, the same body: the same bits), the others finalize the sums |P - P/s| of the second slice like

@@ -1593,6 +1593,13 @@ struct lq_batch {
     lq::AdamTask* adam_d = nullptr;
     size_t ws_bytes = 256;
     bool has_perm = false;               // some conv kernel has an OIHW companion
+    // clipped pair (lq_batch_set_clip): tables of their own, planned for the generic traversal bodies with the stored destination's
+    // alignment taken into account (cfwd: out; cbwd: dp), Params::clip_lo / clip_hi per task
+    std::vector<lq_tensor_desc> descs;   // the descriptors as given to lq_batch_create
+    lq_task_table cfwd, cbwd;
+    uint32_t* clip_d = nullptr;          // per-group clip counts, in the order of cbwd's groups
+    bool has_clip = false;
+    int clip_rounding = 0;
 };
 
 namespace lq {
@@ -1934,6 +1941,7 @@ int lq_batch_create(const lq_tensor_desc* descs, int n, lq_batch** out) {
     lq_batch* b = new (std::nothrow) lq_batch();
     if (!b) return fail(LQ_EHIP, "lq_batch_create: out of host memory");
     b->n = n;
+    b->descs.assign(descs, descs + n);
     int rc = LQ_OK;
     double bwd_elements = 0.0;             // elements the scale-gradient pass traverses: sizes its row blocks (batch_block_elements)
     for (int i = 0; i < n; ++i)
@@ -2052,6 +2060,9 @@ int lq_batch_destroy(lq_batch* b) {
     free_table(b->bwd);
     free_table(b->bwd_o);
     free_table(b->pen);
+    free_table(b->cfwd);
+    free_table(b->cbwd);
+    if (b->clip_d) (void)hipFree(b->clip_d);
     if (b->adam_d) (void)hipFree(b->adam_d);
     if (b->mb_d) (void)hipFree(b->mb_d);
     if (b->ties_d) (void)hipFree(b->ties_d);
@@ -2334,6 +2345,145 @@ int lq_batch_scale_grad_ste(const lq_batch* b, const float* const* dy, const flo
     if ((rc = check_hip("batch STE scale-grad launch"))) return rc;
     hipLaunchKernelGGL(k_batch_finalize_ste, dim3(tb.groups), dim3(64), 0, st, tb.d, tb.prefix_d + nt, nt, (uint32_t*)ws, cf);
     return check_hip("batch STE finalize launch");
+}
+
+// ---- clipped b-bit tensors in the batch (lq_hip.h: lq_batch_set_clip) ----
+// Does the traversal the task was planned for touch its streams with 16-byte accesses?  (the rule of lq_batch_scale_grad_ste)
+static bool task_wants16(const Task& t) { return (t.mode != MODE_COL && t.vec) || (t.mode == MODE_COL && t.col_variant >= 4); }
+
+int lq_batch_set_clip(lq_batch* b, const int32_t* qmin, const int32_t* qmax, int n, int rounding) {
+    const char* fn = "lq_batch_set_clip";
+    if (!b) return fail(LQ_EINVAL, "%s: NULL batch", fn);
+    if (!qmin || !qmax) return fail(LQ_EINVAL, "%s: qmin / qmax is NULL", fn);
+    if (n != b->n) return fail(LQ_EINVAL, "%s: %d ranges for a batch of %d tensors", fn, n, b->n);
+    int rc = check_rounding(fn, rounding);
+    if (rc) return rc;
+    for (int i = 0; i < n; ++i) {
+        const lq_tensor_desc& d = b->descs[i];
+        if ((rc = check_clip_range(fn, qmin[i], qmax[i]))) return rc;
+        if (d.conv_co != 0) return fail(LQ_EINVAL, "%s: tensor %d has an OIHW companion (conv extents); the clipped pair takes conv kernels stored OIHW", fn, i);
+        if (!d.out) return fail(LQ_EINVAL, "%s: tensor %d has no out buffer", fn, i);
+        if (!d.dp) return fail(LQ_EINVAL, "%s: tensor %d has no dp buffer", fn, i);
+        if (!aligned(d.dp, 4)) return fail(LQ_EALIGN, "%s: dp of tensor %d is not 4-byte aligned", fn, i);
+        if (d.ds && !aligned(d.ds, 4)) return fail(LQ_EALIGN, "%s: ds of tensor %d is not 4-byte aligned", fn, i);
+    }
+    // tables of their own, sized per tensor (batch_w = 0: no batch-sized units, no periodic stream, no fragment layout): the forms
+    // of the single-tensor clipped pair.  The forward table's plan looks at `out`; the backward's looks at P only, so the stored
+    // destination is checked here: never a misaligned vector store.
+    lq_task_table cf, cb;
+    uint32_t* counts = nullptr;
+    for (int i = 0; i < n && !rc; ++i) {
+        const lq_tensor_desc& d = b->descs[i];
+        Task t;
+        if ((rc = fill_task(t, d, false, false, cf))) break;
+        t.p.clip_lo = (float)qmin[i];
+        t.p.clip_hi = (float)qmax[i];
+        cf.h.push_back(t);
+        cf.index.push_back(i);
+        if ((rc = fill_task(t, d, true, false, cb))) break;
+        t.p.clip_lo = (float)qmin[i];
+        t.p.clip_hi = (float)qmax[i];
+        t.dp = d.dp;
+        if (task_wants16(t) && !aligned(d.dp, 16)) {
+            rc = fail(LQ_EALIGN, "%s: tensor %d is traversed with 16-byte accesses but its dp is not 16-byte aligned", fn, i);
+            break;
+        }
+        cb.h.push_back(t);
+        cb.index.push_back(i);
+    }
+    if (!rc) rc = finish_table(cf, false);
+    if (!rc) rc = finish_table(cb, true);
+    if (!rc) {
+        if (hipMalloc(&counts, (size_t)cb.groups * sizeof(uint32_t)) != hipSuccess) rc = fail(LQ_EHIP, "%s: out of device memory", fn);
+        else if (hipMemset(counts, 0, (size_t)cb.groups * sizeof(uint32_t)) != hipSuccess) rc = fail(LQ_EHIP, "%s: hipMemset failed", fn);
+    }
+    if (!rc) {
+        for (Task& t : cb.h) t.ties = counts + t.first_group;      // the finalize's count output (batch_finalize_body)
+        rc = upload_table(cf);
+    }
+    if (!rc) rc = upload_table(cb);
+    if (rc) {
+        free_table(cf);
+        free_table(cb);
+        if (counts) (void)hipFree(counts);
+        return rc;
+    }
+    free_table(b->cfwd);            // a repeated call replaces the ranges (hipFree waits for the device)
+    free_table(b->cbwd);
+    if (b->clip_d) (void)hipFree(b->clip_d);
+    b->cfwd = cf;
+    b->cbwd = cb;
+    b->clip_d = counts;
+    b->clip_rounding = rounding;
+    b->has_clip = true;
+    const size_t need = (size_t)cb.ws_words * 4 + 256;
+    if (need > b->ws_bytes) b->ws_bytes = need;
+    return LQ_OK;
+}
+
+int lq_batch_forward_clip(const lq_batch* b, void* stream) {
+    const char* fn = "lq_batch_forward_clip";
+    if (!b) return fail(LQ_EINVAL, "%s: NULL batch", fn);
+    if (!b->has_clip) return fail(LQ_EINVAL, "%s: the batch has no ranges (lq_batch_set_clip)", fn);
+    PtrPack pk;
+    CoefPack cf;
+    memset(&pk, 0, sizeof(pk));
+    memset(&cf, 0, sizeof(cf));
+    const lq_task_table& tb = b->cfwd;
+    const int nt = (int)tb.h.size();
+    hipStream_t st = (hipStream_t)stream;
+    if (b->clip_rounding == LQ_ROUND_NEAREST_EVEN)
+        hipLaunchKernelGGL((k_batch_traverse<OP_CLIP_FWD_RNE>), dim3(tb.blocks), dim3(kBlock), 0, st, tb.d, tb.block_task_d, nt, (uint32_t*)nullptr, pk, 0, cf);
+    else
+        hipLaunchKernelGGL((k_batch_traverse<OP_CLIP_FWD>), dim3(tb.blocks), dim3(kBlock), 0, st, tb.d, tb.block_task_d, nt, (uint32_t*)nullptr, pk, 0, cf);
+    return check_hip("batch clipped forward launch");
+}
+
+int lq_batch_backward_clip(const lq_batch* b, const float* const* dy, const float* grad_scale, void* ws, size_t ws_bytes, void* stream) {
+    const char* fn = "lq_batch_backward_clip";
+    if (!b) return fail(LQ_EINVAL, "%s: NULL batch", fn);
+    if (!b->has_clip) return fail(LQ_EINVAL, "%s: the batch has no ranges (lq_batch_set_clip)", fn);
+    const lq_task_table& tb = b->cbwd;
+    int rc = check_penalty_workspace(fn, b, ws, ws_bytes);
+    if (rc) return rc;
+    PtrPack pk;
+    CoefPack cf;
+    memset(&pk, 0, sizeof(pk));
+    memset(&cf, 0, sizeof(cf));
+    const int nt = (int)tb.h.size();
+    for (int i = 0; i < nt; ++i) {
+        const Task& t = tb.h[i];
+        const float* d = dy ? dy[tb.index[i]] : t.p.dy;
+        if (!d) return fail(LQ_EINVAL, "%s: no upstream gradient for tensor %d", fn, tb.index[i]);
+        if (!aligned(d, 4)) return fail(LQ_EALIGN, "%s: dy of tensor %d misaligned", fn, tb.index[i]);
+        if (task_wants16(t) && !aligned(d, 16)) return fail(LQ_EALIGN, "%s: dy of the 16-byte aligned tensor %d is not 16-byte aligned", fn, tb.index[i]);
+        if (grad_scale && !t.ds) return fail(LQ_EINVAL, "%s: tensor %d has no ds buffer (pass grad_scale = NULL for the mask alone)", fn, tb.index[i]);
+        pk.dy[i] = d;
+        cf.c[i] = grad_scale ? grad_scale[tb.index[i]] : 0.0f;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (b->clip_rounding == LQ_ROUND_NEAREST_EVEN)
+        hipLaunchKernelGGL((k_batch_traverse<OP_CLIP_BWD_RNE>), dim3(tb.blocks), dim3(kBlock), 0, st, tb.d, tb.block_task_d, nt, (uint32_t*)ws, pk, 0, cf);
+    else
+        hipLaunchKernelGGL((k_batch_traverse<OP_CLIP_BWD>), dim3(tb.blocks), dim3(kBlock), 0, st, tb.d, tb.block_task_d, nt, (uint32_t*)ws, pk, 0, cf);
+    if ((rc = check_hip("batch clipped backward launch"))) return rc;
+    hipLaunchKernelGGL(k_batch_finalize_clip, dim3(tb.groups), dim3(64), 0, st, tb.d, tb.prefix_d + nt, nt, (uint32_t*)ws, cf, grad_scale ? 0 : 1);
+    return check_hip("batch clipped finalize launch");
+}
+
+int lq_batch_clip_counts(const lq_batch* b, int tensor, const uint32_t** dev, int64_t* groups) {
+    const char* fn = "lq_batch_clip_counts";
+    if (!b || !dev || !groups) return fail(LQ_EINVAL, "%s: NULL argument", fn);
+    if (!b->has_clip) return fail(LQ_EINVAL, "%s: the batch has no ranges (lq_batch_set_clip)", fn);
+    if (tensor < 0 || tensor >= b->n) return fail(LQ_EINVAL, "%s: tensor %d of %d", fn, tensor, b->n);
+    const lq_task_table& tb = b->cbwd;
+    for (size_t k = 0; k < tb.h.size(); ++k) {
+        if (tb.index[k] != tensor) continue;
+        *dev = tb.h[k].ties;
+        *groups = tb.h[k].p.G;
+        return LQ_OK;
+    }
+    return fail(LQ_EINVAL, "%s: tensor %d is not in the clipped tables", fn, tensor);
 }
 
 int lq_loss_log_append(const float* scce_dev, const float* penalty_dev, float rate, float* rows_dev, int64_t capacity,

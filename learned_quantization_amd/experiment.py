@@ -107,7 +107,7 @@ def fit(tr: Trainer, epochs: int, steps_per_epoch: int, batch: int, callbacks, l
     return history
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description="Train model for one penalty value in this scenario (synthetic data).")
     ap.add_argument("--config", choices=["mnist", "cifar", "imagenette"], default="cifar")
     ap.add_argument("--seed", type=int, required=True, help="Random seed for reproducibility.")
@@ -131,11 +131,18 @@ def main(argv=None):
     ap.add_argument("--baseline-weights", default=None)
     ap.add_argument("--log-root", default="logs")
     ap.add_argument("--batched", action="store_true")
+    ap.add_argument("--clipped-batch", action="store_true",
+                    help="with --batched and --bits: run the clipped layers in the multi-tensor batch (opt-in, see train.py)")
     ap.add_argument("--loss-values", action="store_true",
                     help="with --custom_loss: loss and val_loss include rate * penalty (what Keras reports for compute_total_loss) "
                          "and custom_losses/*.log get one line per step, from a device-side log flushed at every epoch end")
     ap.add_argument("--export-packed", action="store_true",
                     help="also write the lossless bit-packed export (weights_packed.npz/.zip, packed_sizes.log; not in the reference)")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     args = ap.parse_args(argv)
     if args.loss_values and not args.custom_loss:
         ap.error("--loss-values needs --custom_loss (the nested-quantization variant has no loss term to evaluate)")
@@ -153,7 +160,8 @@ def main(argv=None):
 
     tr = Trainer(args.config, mode, value, args.orientation, args.custom_loss, lr=args.lr, seed=args.seed, device=dev,
                  log_dir=log_dir, batched=args.batched, loss_values=args.loss_values,
-                 loss_log_capacity=max(4096, args.steps_per_epoch), bits=args.bits, rounding=args.rounding)
+                 loss_log_capacity=max(4096, args.steps_per_epoch), bits=args.bits, rounding=args.rounding,
+                 clipped_batch=args.clipped_batch)
     if args.training == "post_training":
         if args.config != "mnist" or not args.baseline_weights:
             raise SystemExit("post_training needs --config mnist --baseline-weights <npz with W1,b1,W2,b2> "

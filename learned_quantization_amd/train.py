@@ -72,8 +72,13 @@ class Trainer:
                  lr=1e-4, seed=42, device=None, ddp_mode="A", log_dir="logs", graph=False, batched=False,
                  bucket_mb: float = 25.0, overlap: bool = True, graph_collectives: Optional[bool] = None,
                  force_collectives: bool = False, kernel_storage: str = "oihw", loss_values: bool = False,
-                 loss_log_capacity: int = 4096, grad_scale=None, bits=None, signed=True, q_range=None, rounding="floor"):
-        """``loss_values`` (modes with a loss term): the step also EVALUATES the penalty -- batched: as a by-product of the
+                 loss_log_capacity: int = 4096, grad_scale=None, bits=None, signed=True, q_range=None, rounding="floor",
+                 clipped_batch: bool = False):
+        """``clipped_batch`` (opt-in, with ``batched=True`` and a range): the clipped layers run in the multi-tensor batch
+        (``FakeQuantBatch(clipped=True)``: one forward launch, two backward launches; the batch owns one dP buffer per tensor
+        and its backward moves 12 bytes per element instead of 8).  Everything else about a range stays: modes "cl", "ste",
+        "stecl", data-parallel mode "A".
+        ``loss_values`` (modes with a loss term): the step also EVALUATES the penalty -- batched: as a by-product of the
         gradient injection (lq_batch_penalty_grads_values); per-tensor path: the loss object's own device scalar -- appends the
         reference's three per-step numbers (CL-F:58-71) to a device-side ``LossLog`` (no synchronisation, capturable) and
         ``step()`` / ``step_graphed()`` return ``mean(SCCE) (+ regularisers) + rate * penalty``.  ``loss_terms`` is a
@@ -102,9 +107,15 @@ class Trainer:
             if ddp_mode == "B":
                 raise ValueError("bits / q_range with ddp_mode 'B': it recomputes ds from the all-reduced dP, which no longer holds "
                                  "the dy of the clipped elements; use ddp_mode 'A'")
-            if batched:
+            if batched and not clipped_batch:
                 raise ValueError("bits / q_range with batched=True: the multi-tensor backward hands dy on as dP, but a clipped "
-                                 "layer's dP is a masked copy of dy; use the per-tensor path")
+                                 "layer's dP is a masked copy of dy; use the per-tensor path, or opt in to the clipped batch "
+                                 "(clipped_batch=True / --clipped-batch), which owns a dP buffer per tensor")
+        if clipped_batch and not batched:
+            raise ValueError("clipped_batch=True belongs to batched=True")
+        if clipped_batch and self.q_range is None:
+            raise ValueError("clipped_batch=True needs bits / q_range: an unclipped model runs the default batch")
+        self.clipped_batch = bool(clipped_batch)
         # conv kernels shaped HWIO like the reference's, stored in the order MIOpen consumes (layers.py kernel_storage): the
         # fake-quantised kernel goes to the convolution as written and its weight gradient is dP
         self.model = build_model(config, mode=mode, value=value, seed=seed, orientation=orientation, device=self.device,
@@ -143,11 +154,11 @@ class Trainer:
                 self.dp.zero_grad()          # makes scale.grad the bucket views the batch will write into
             # the convolutions consume the OIHW companions only; autograd=False: the fake-quantised tensors are leaves and
             # _backward_phase calls finish_backward() itself (0.4-0.6 ms less autograd-engine work per eager step for 40 tensors)
-            self.batch = FakeQuantBatch(self.model, lr=lr, hwio_out=False, autograd=False)
+            self.batch = FakeQuantBatch(self.model, lr=lr, hwio_out=False, autograd=False, clipped=self.clipped_batch)
             # nothing touches ds between its computation and the scales' update when there is no loss term and ds is not
             # exchanged (one process, or exact mode B): the finalize then applies the Adam step itself (one launch fewer)
             # (the fused finalize + Adam is the nested-quantization pass's: not for the straight-through modes)
-            fused = self.loss_obj is None and (self.dp is None or ddp_mode == "B") and not ste
+            fused = self.loss_obj is None and (self.dp is None or ddp_mode == "B") and not ste and not self.clipped_batch
             self.scale_opt = BatchedScaleAdam(self.batch, capturable=graph, fused=fused)
             if self.dp is not None:
                 self.dp.attach_batch(self.batch)
@@ -381,7 +392,7 @@ class Trainer:
         return float(loss), float((p.argmax(1) == y).float().mean())
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", choices=list(INPUT_SHAPES), default="cifar")
     ap.add_argument("--mode", choices=["nq", "cl", "nqcl", "ste", "stecl"], default="nq")
@@ -414,6 +425,9 @@ def main(argv=None):
     ap.add_argument("--backend", default="nccl", help="nccl = RCCL over xGMI (default); gloo + --share-gpu rehearses N>1 on one GPU")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal only: every rank uses cuda:0 (needs --backend gloo)")
     ap.add_argument("--batched", action="store_true", help="multi-tensor launches for all fake-quant ops of a step (lq_batch_*)")
+    ap.add_argument("--clipped-batch", action="store_true",
+                    help="with --batched and --bits: run the clipped layers in the multi-tensor batch (opt-in: it owns a dP buffer per "
+                         "tensor and its backward moves 12 bytes per element instead of 8)")
     ap.add_argument("--loss-values", action="store_true",
                     help="modes cl / nqcl: evaluate the penalty with its gradients, report mean(SCCE) + rate * penalty and keep the "
                          "reference's per-step loss logs in a device buffer (written at the end)")
@@ -422,7 +436,11 @@ def main(argv=None):
     ap.add_argument("--channels-last", action="store_true",
                     help="feed NHWC-strided batches (torch.channels_last): MIOpen's fp32 igemm kernels are NHWC; measured "
                          "+17 %% on the ResNet-18-like config, -17 %% on the small CIFAR CNN")
-    args = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
 
     # read by the HSA runtime when it initialises (the first torch.cuda call below): the host driver only supports dmabuf IPC
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -458,7 +476,7 @@ def main(argv=None):
                  loss_values=args.loss_values, loss_log_capacity=max(4096, args.steps + args.warmup + 8),
                  grad_scale=(None if args.grad_scale is None else
                              (args.grad_scale if args.grad_scale == "rsqrt_group" else float(args.grad_scale))),
-                 bits=args.bits, signed=not args.unsigned, rounding=args.rounding)
+                 bits=args.bits, signed=not args.unsigned, rounding=args.rounding, clipped_batch=args.clipped_batch)
     do_step = tr.step_graphed if args.graph else tr.step
     g = torch.Generator(device=dev).manual_seed(args.seed + rank)
     batches = [synthetic_batch(args.config, args.batch, dev, g) for _ in range(4)]
@@ -490,6 +508,7 @@ def main(argv=None):
             "loss_term": args.loss, "quantized_elements": n_q, "final_loss": float(loss.detach()), "ddp_mode": args.ddp_mode,
             "hipgraph": bool(args.graph), "graph_collectives": bool(tr.graph_collectives and args.graph and use_dist),
             **({"graph_note": tr.graph_note} if tr.graph_note else {}), "batched": bool(args.batched),
+            **({"clipped_batch": True} if args.clipped_batch else {}),
             "backend": (args.backend if use_dist else None),
             "channels_last": bool(args.channels_last), "kernel_storage": args.kernel_storage,
             **({"q_range": list(tr.q_range)} if tr.q_range else {}),

@@ -63,6 +63,12 @@ enum Mode { MODE_ROW_BIG = 0, MODE_ROW_SMALL = 1, MODE_COL = 2 };
 constexpr int64_t kColRbFused = 48;
 constexpr int64_t kColRbBwd = 128;
 
+// Where a traversal leaves its partial triples and how the finalize walks them (host only: FinGeom and Task carry copies).
+struct PartialLayout {
+    int64_t np;                             // partial triples the traversal writes
+    int64_t gstride, n1, stride1, n2;       // finalize geometry: group g's partials at g * gstride + i1 * stride1 + i2
+};
+
 struct Plan {
     int mode;
     int64_t R, L;       // row modes
@@ -72,13 +78,28 @@ struct Plan {
     int lpr_log2;
     int64_t C, rps, ysplit;   // column mode
     int per4;           // column mode, C <= 64: geometry admits the float4 grid-stride variant (ysplit % C == 0)
-    int64_t np;         // number of partial triples
-    int64_t np_ws;      // row-big at streaming size: partial count of the smallest chunk the launch may choose (workspace bound)
-    // finalize geometry (per group)
-    int64_t gstride, n1, stride1, n2;
+    PartialLayout lay;  // the partials of the form the plan describes; a launch that runs another form replaces it
+    int64_t np_bound;   // workspace bound: the largest partial count of any form the launch may choose (>= lay.np)
 };
 
 static int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// The three layouts, and the only code that writes one (the batch's group fragments and the conv tile have one each further
+// down: layout_frags, conv_tile_layout).  Partial p of group g, outer index o:
+// one per (row, chunk): row o * G + g, chunk c at (o * G + g) * nc + c
+static PartialLayout layout_row_chunks(int64_t R, int64_t nc, int64_t f_outer, int64_t G) { return {R * nc, nc, f_outer, G * nc, nc}; }
+// one per row, stored group-major: g * f_outer + o
+static PartialLayout layout_rows(int64_t R, int64_t f_outer) { return {R, f_outer, f_outer, 1, 1}; }
+// one per (row block, column): block y, column g * inner + i at y * C + g * inner + i
+static PartialLayout layout_cols(int64_t nby, int64_t C, int64_t inner) { return {nby * C, inner, nby, C, inner}; }
+// a plan that carries nothing but a layout (the conv tile's: its launch has a geometry of its own, ConvTile)
+static Plan plan_of_layout(const PartialLayout& lay) {
+    Plan pl;
+    memset(&pl, 0, sizeof(pl));
+    pl.lay = lay;
+    pl.np_bound = lay.np;
+    return pl;
+}
 
 // Development knobs.  The shipped library reads NO environment variable: the traversal plan, the partial layout and with
 // them the workspace size are pure functions of the descriptor and the pointers' alignment.  `make dev` (-DLQ_DEV_KNOBS,
@@ -199,21 +220,18 @@ static Plan make_plan(int64_t outer, int64_t G, int64_t inner, int force_bs = 0)
                 pl.rps = RB;
                 pl.ysplit = nby;
                 pl.per4 = per4;
-                pl.np = nby * C;
+                pl.lay = layout_cols(nby, C, inner);
+                pl.np_bound = pl.lay.np;
                 // the one-shot flat column kernel (lq_stream2.hpp k_flat_cols: C <= 4 or C = 8, 16, 32, 64 at streaming sizes)
                 // writes one partial per (block of 1024 float4, column): size the workspace for it
                 if (per4 && flat_cols_ok(C)) {
                     const int64_t fb = ceil_div(ceil_div(outer * C, 4) + 1, (int64_t)kFlatColsBlock * 2);
-                    if (fb * C > pl.np) pl.np = fb * C;
+                    if (fb * C > pl.np_bound) pl.np_bound = fb * C;
                 }
                 // 64 < C <= 256 at streaming size may run the periodic form (a column tile narrower than 256 columns leaves
                 // lanes idle): one partial per (block, column) for periodic_blocks(C) blocks
-                if (C > 64 && C <= 256 && (double)outer * (double)C >= (double)kPeriodic4Min && periodic_blocks(C) * C > pl.np)
-                    pl.np = periodic_blocks(C) * C;
-                pl.gstride = inner;
-                pl.n1 = nby;
-                pl.stride1 = C;
-                pl.n2 = inner;
+                if (C > 64 && C <= 256 && (double)outer * (double)C >= (double)kPeriodic4Min && periodic_blocks(C) * C > pl.np_bound)
+                    pl.np_bound = periodic_blocks(C) * C;
             }
         }
     }
@@ -236,7 +254,6 @@ static Plan make_plan(int64_t outer, int64_t G, int64_t inner, int force_bs = 0)
 #endif
             pl.CH = pl.bs * 4;
             pl.nc = row_chunks(L, pl.CH);
-            if (pl.bs == 512) pl.np_ws = R * row_chunks(L, 1024);      // launch_traverse may cut such rows into 1024-element chunks
         } else {
             pl.mode = MODE_ROW_SMALL;
             pl.CH = (int)L;
@@ -249,18 +266,10 @@ static Plan make_plan(int64_t outer, int64_t G, int64_t inner, int force_bs = 0)
             }
             pl.lpr_log2 = lg;
         }
-        pl.np = R * pl.nc;
-        if (pl.mode == MODE_ROW_SMALL) {   // one partial per row, stored group-major: g * outer + o
-            pl.gstride = f_outer;
-            pl.n1 = f_outer;
-            pl.stride1 = 1;
-            pl.n2 = 1;
-        } else {
-            pl.gstride = pl.nc;
-            pl.n1 = f_outer;
-            pl.stride1 = G * pl.nc;
-            pl.n2 = pl.nc;
-        }
+        pl.lay = pl.mode == MODE_ROW_SMALL ? layout_rows(R, f_outer) : layout_row_chunks(R, pl.nc, f_outer, G);
+        pl.np_bound = pl.lay.np;
+        // launch_traverse may cut the rows of 512-thread units into 1024-element chunks
+        if (pl.mode == MODE_ROW_BIG && pl.bs == 512 && R * row_chunks(L, 1024) > pl.np_bound) pl.np_bound = R * row_chunks(L, 1024);
     }
     return pl;
 }
@@ -291,17 +300,14 @@ static int check_desc(int64_t outer, int64_t G, int64_t inner) {
     return LQ_OK;
 }
 
-static size_t ws_bytes_for(const Plan& pl) {
-    size_t np = (size_t)(pl.np_ws > pl.np ? pl.np_ws : pl.np);
-    np = (np + 63) / 64 * 64;
-    return np * 16 + 256;
-}
+static size_t ws_partials(const Plan& pl) { return ((size_t)pl.np_bound + 63) / 64 * 64; }      // per accumulator array
+static size_t ws_bytes_for(const Plan& pl) { return ws_partials(pl) * 16 + 256; }
 
 static int bind_ws(Params& p, const Plan& pl, void* ws, size_t ws_bytes) {
     if (!ws) return fail(LQ_EWORKSPACE, "workspace is NULL (need %zu bytes)", ws_bytes_for(pl));
     if (!aligned(ws, 16)) return fail(LQ_EALIGN, "workspace must be 16-byte aligned");
     if (ws_bytes < ws_bytes_for(pl)) return fail(LQ_EWORKSPACE, "workspace too small: %zu < %zu bytes", ws_bytes, ws_bytes_for(pl));
-    size_t np = ((size_t)(pl.np_ws > pl.np ? pl.np_ws : pl.np) + 63) / 64 * 64;
+    const size_t np = ws_partials(pl);
     p.pa = reinterpret_cast<uint32_t*>(ws);
     p.pb = p.pa + np;
     p.pc = reinterpret_cast<double*>(p.pb + np);
@@ -327,8 +333,8 @@ static void col_variant(const Plan& pl, const void* P, const void* dy, const voi
     if (pl.C <= 64) {
         variant = (allow_periodic4 && pl.per4 && al16) ? (bytes >= (double)kNtBytes ? 7 : 6) : 0;
         nbx = 1;
-    } else if (pl.C % 4 == 0 && aligned(P, 16) && (!dy || aligned(dy, 16)) && (!out || aligned(out, 16))) {
-        variant = ((double)pl.C * (double)pl.ysplit * (double)pl.rps * 4.0 >= (double)kNtBytes) ? 5 : 4;
+    } else if (pl.C % 4 == 0 && al16) {
+        variant = (bytes >= (double)kNtBytes) ? 5 : 4;
         nbx = ceil_div(pl.C, 256);
     } else {
         variant = 1;
@@ -345,19 +351,60 @@ constexpr bool kDevKnobs = true;       // tools/ builds: the LQ_TUNE_* switches 
 constexpr bool kDevKnobs = false;
 #endif
 
+// The streaming geometry of long rows (512-thread units, nontemporal accesses, two float4 per thread) exists for K1, K2 and K4 --
+// the operations that run on activation-sized tensors.  The penalty terms, the integer view and the element-wise OIHW
+// companion work on weight-sized tensors: they keep the 256-thread units at every size (their entry points plan with
+// make_plan(..., kBlock)), which is a third of the row-stream instantiations and none that a parity test could not reach.
+template <int OP>
+constexpr bool kStreamOp = OP == OP_FWD || OP == OP_BWD || OP == OP_FUSED;
+
+template <int NT, int GM>
+static void launch_flat_fwd_as(const Params& p, const FlatIdx& fx, int64_t nv, int rem, int64_t blocks, bool events, hipStream_t st) {
+    // hipExtLaunchKernelGGL: with lq_profile_events() set, the events take the kernel's own begin / end timestamps
+    if (events) hipExtLaunchKernelGGL((k_flat_fwd<OP_FWD, 512, NT, GM>), dim3((unsigned)blocks), dim3(512), 0, st, g_prof_start, g_prof_stop, 0, p, fx, nv, rem);
+    else hipLaunchKernelGGL((k_flat_fwd<OP_FWD, 512, NT, GM>), dim3((unsigned)blocks), dim3(512), 0, st, p, fx, nv, rem);
+}
+
+// K1 as the flat one-shot stream (lq_stream2.hpp k_flat_fwd): the `n` elements as float4, 512 per block, and with `with_rem` a
+// last block for the n % 4 elements that remain.  gm: the kernel's group mode; gm_wide: its 64-bit form for 2^32 or more
+// elements (< 0: there is none and the caller keeps such tensors away; 2^32 elements are 16 GiB, so `wide` implies `nt`).
+// events: the launch lq_profile_events() stamps.  Returns 1 when it launched, < 0 on error, 0 when the grid would be too large.
+static int launch_flat_fwd(const Params& p, const FlatIdx& fx, int64_t n, int gm, int gm_wide, bool with_rem, bool nt, bool events,
+                           hipStream_t st) {
+    const int64_t nv = n >> 2;
+    const int rem = with_rem ? (int)(n & 3) : 0;
+    const int64_t blocks = ceil_div(nv + (rem ? 1 : 0), 512);
+    if (blocks > 2147483647ll) return 0;
+    const bool wide = nt && gm_wide >= 0 && n >= 4294967296ll;
+    switch ((wide ? gm_wide : gm) * 2 + (nt ? 1 : 0)) {      // every (NT, GM) pair that is compiled
+        case 0 * 2 + 0: launch_flat_fwd_as<0, 0>(p, fx, nv, rem, blocks, events, st); break;
+        case 0 * 2 + 1: launch_flat_fwd_as<1, 0>(p, fx, nv, rem, blocks, events, st); break;
+        case 2 * 2 + 1: launch_flat_fwd_as<1, 2>(p, fx, nv, rem, blocks, events, st); break;
+        case 4 * 2 + 0: launch_flat_fwd_as<0, 4>(p, fx, nv, rem, blocks, events, st); break;
+        case 4 * 2 + 1: launch_flat_fwd_as<1, 4>(p, fx, nv, rem, blocks, events, st); break;
+        case 5 * 2 + 1: launch_flat_fwd_as<1, 5>(p, fx, nv, rem, blocks, events, st); break;
+        case 6 * 2 + 0: launch_flat_fwd_as<0, 6>(p, fx, nv, rem, blocks, events, st); break;
+        case 6 * 2 + 1: launch_flat_fwd_as<1, 6>(p, fx, nv, rem, blocks, events, st); break;
+        case 7 * 2 + 1: launch_flat_fwd_as<1, 7>(p, fx, nv, rem, blocks, events, st); break;
+        case 8 * 2 + 0: launch_flat_fwd_as<0, 8>(p, fx, nv, rem, blocks, events, st); break;
+        case 8 * 2 + 1: launch_flat_fwd_as<1, 8>(p, fx, nv, rem, blocks, events, st); break;
+        case 9 * 2 + 1: launch_flat_fwd_as<1, 9>(p, fx, nv, rem, blocks, events, st); break;
+        case 10 * 2 + 0: launch_flat_fwd_as<0, 10>(p, fx, nv, rem, blocks, events, st); break;
+        case 10 * 2 + 1: launch_flat_fwd_as<1, 10>(p, fx, nv, rem, blocks, events, st); break;
+        case 11 * 2 + 0: launch_flat_fwd_as<0, 11>(p, fx, nv, rem, blocks, events, st); break;
+        case 11 * 2 + 1: launch_flat_fwd_as<1, 11>(p, fx, nv, rem, blocks, events, st); break;
+        default: fail(LQ_EINVAL, "internal: flat forward has no group mode %d (nt %d)", wide ? gm_wide : gm, (int)nt); return -1;
+    }
+    return check_hip("flat forward launch") ? -1 : 1;
+}
+
 // Streaming-size (>= 4 M elements) forms of lq_stream2.hpp.  Returns 1 when it launched the traversal, 0 when the
 // round-1 traversal should run, < 0 on error.
 template <int OP>
-static int launch_stream2_impl(Plan& pl, const Params& p, hipStream_t st);
-
-template <int OP>
 static int launch_stream2(Plan& pl, const Params& p, hipStream_t st) {
-    if constexpr (OP == OP_FWD || OP == OP_BWD || OP == OP_FUSED) return launch_stream2_impl<OP>(pl, p, st);
-    else return 0;
-}
-
-template <int OP>
-static int launch_stream2_impl(Plan& pl, const Params& p, hipStream_t st) {
+    if constexpr (!kStreamOp<OP>) {
+        return 0;
+    } else {
     using O = OpT<OP>;
     const double numel = (double)p.outer * (double)p.G * (double)p.inner;
     if (numel < (double)kPeriodic4Min) return 0;
@@ -379,30 +426,20 @@ static int launch_stream2_impl(Plan& pl, const Params& p, hipStream_t st) {
             // knob 32768 restores the row stream for them).  L % 4 != 0: a float4 may straddle a row end (6 / 7), see below.
             const bool poor_fill = (double)pl.L / (double)(pl.nc * pl.CH) < 0.95;
             if (!(off_rb & 256) && (pl.L % 32 != 0 || poor_fill || !(off_rb & 32768)) && aligned(p.P, 16) && aligned(p.out, 16)) {
-                const int64_t nv = nn >> 2;
-                const int rem = (int)(nn & 3);
-                const int64_t blocks = ceil_div(nv + (rem ? 1 : 0), 512);
-                if (blocks <= 2147483647ll) {
-                    const bool ntb = numel * 4.0 >= (double)kNtBytes;
-                    const bool wide = nn >= 4294967296ll;
-                    // hipExtLaunchKernelGGL: with lq_profile_events() set, the events take the kernel's own begin / end timestamps
-#define LQ_FLATR(NT_, GM_) hipExtLaunchKernelGGL((k_flat_fwd<OP, 512, NT_, GM_>), dim3((unsigned)blocks), dim3(512), 0, st, g_prof_start, g_prof_stop, 0, p, fx, nv, rem)
-                    if (pl.L % 4 == 0) {                    // (2^32 elements are 16 GiB: `wide` implies `ntb`)
-                        if (ntb) fx.keep_from = (uint32_t)ceil_div(mall_keep_from(nn), 2048);      // 512 float4 per block
-                        if (ntb) { if (wide) LQ_FLATR(1, 2); else LQ_FLATR(1, 0); }
-                        else LQ_FLATR(0, 0);
-                    } else if (!(off_rb & 512) && (double)pl.L / (double)(pl.nc * pl.CH) >= 0.8) {
-                        // long rows with L % 4 != 0 keep the row stream (TAIL instantiation): K1 5.8-6.0 TB/s on rows of 1025,
-                        // 2047, 4099, 50177 against 5.4-5.9 for the straddling flat form (development knob 512 selects the latter)
-                        // -- unless their chunks are poorly filled (rows of 1225 = 1024 + 201 elements: 4.3 TB/s)
-                        return 0;
-                    } else {
-                        if (ntb) { if (wide) LQ_FLATR(1, 7); else LQ_FLATR(1, 6); }
-                        else LQ_FLATR(0, 6);
-                    }
-#undef LQ_FLATR
-                    return check_hip("flat forward launch") ? -1 : 1;
+                const bool ntb = numel * 4.0 >= (double)kNtBytes;
+                int r;
+                if (pl.L % 4 == 0) {
+                    if (ntb) fx.keep_from = (uint32_t)ceil_div(mall_keep_from(nn), 2048);      // 512 float4 per block
+                    r = launch_flat_fwd(p, fx, nn, 0, 2, true, ntb, true, st);
+                } else if (!(off_rb & 512) && (double)pl.L / (double)(pl.nc * pl.CH) >= 0.8) {
+                    // long rows with L % 4 != 0 keep the row stream (TAIL instantiation): K1 5.8-6.0 TB/s on rows of 1025,
+                    // 2047, 4099, 50177 against 5.4-5.9 for the straddling flat form (development knob 512 selects the latter)
+                    // -- unless their chunks are poorly filled (rows of 1225 = 1024 + 201 elements: 4.3 TB/s)
+                    return 0;
+                } else {
+                    r = launch_flat_fwd(p, fx, nn, 6, 7, true, ntb, true, st);
                 }
+                if (r) return r;
             }
         } else {
             // Rows of 1153..1533 elements are two 1024-chunks, the second one 13-50 % full (35 x 35 planes: 1225 = 1024 + 201) --
@@ -421,13 +458,8 @@ static int launch_stream2_impl(Plan& pl, const Params& p, hipStream_t st) {
                     const int64_t n = p.outer * p.G * p.inner;
                     const bool ntb = numel * 4.0 >= (double)kNtBytes;
                     const FastDiv fG = make_fastdiv((uint32_t)p.G);
-                    const int64_t f_outer = pl.R / p.G;
                     pl.nc = 1;                 // the finalize that follows must walk the partial layout this launch produces:
-                    pl.np = pl.R;              // one partial per row, group-major (g * outer + o), as in the row-small mode
-                    pl.gstride = f_outer;
-                    pl.n1 = f_outer;
-                    pl.stride1 = 1;
-                    pl.n2 = 1;
+                    pl.lay = layout_rows(pl.R, pl.R / p.G);      // one partial per row, as in the row-small mode
 #define LQ_WINB(NT_, V_) hipLaunchKernelGGL((k_row_win<OP, NT_, 6, V_, 1>), dim3((unsigned)blocks), dim3(kBlock), 0, st, p, fG, pl.R, (int)pl.L, n)
                     if (nwin <= 320) { if (ntb) LQ_WINB(1, 5); else LQ_WINB(0, 5); }
                     else if (nwin <= 384) { if (ntb) LQ_WINB(1, 6); else LQ_WINB(0, 6); }
@@ -455,67 +487,18 @@ static int launch_stream2_impl(Plan& pl, const Params& p, hipStream_t st) {
         // rows of 4..1023 elements off the 16-byte grid (row-small mode, L % 4 != 0): a float4 straddles at most one row end
         const bool straddle = pl.mode == MODE_ROW_SMALL && pl.L >= 4 && pl.L % 4 != 0 && !(off & 256);
         if (straddle) {
-            const int64_t nv = n >> 2;
-            const int rem = (int)(n & 3);
-            const int64_t blocks = ceil_div(nv + (rem ? 1 : 0), 512);
-            if (blocks <= 2147483647ll) {
-                const bool wide = n >= 4294967296ll;
-#define LQ_FLATS(NT_, GM_) hipLaunchKernelGGL((k_flat_fwd<OP, 512, NT_, GM_>), dim3((unsigned)blocks), dim3(512), 0, st, p, fx, nv, rem)
-                if (nt) { if (wide) LQ_FLATS(1, 7); else LQ_FLATS(1, 6); }
-                else LQ_FLATS(0, 6);
-#undef LQ_FLATS
-                return check_hip("flat forward launch") ? -1 : 1;
-            }
+            if (const int r = launch_flat_fwd(p, fx, n, 6, 7, true, nt, false, st)) return r;
         }
         if (scale4u && !(off & 1)) {
-            const int64_t nv = n >> 2;
-            const int rem = (int)(n & 3);
-            const int64_t blocks = ceil_div(nv + (rem ? 1 : 0), 512);
-            if (blocks <= 2147483647ll) {
-                const bool wide = n >= 4294967296ll;
-#define LQ_FLATU(NT_, GM_) hipLaunchKernelGGL((k_flat_fwd<OP, 512, NT_, GM_>), dim3((unsigned)blocks), dim3(512), 0, st, p, fx, nv, rem)
-                if (nt) { if (wide) LQ_FLATU(1, 9); else LQ_FLATU(1, 8); }
-                else LQ_FLATU(0, 8);
-#undef LQ_FLATU
-                return check_hip("flat forward launch") ? -1 : 1;
-            }
+            if (const int r = launch_flat_fwd(p, fx, n, 8, 9, true, nt, false, st)) return r;
         }
         // every other column-mode forward (several groups inside a float4: C = 3, 5, 10, 30; inner = 2, 3, 5, 15): gathered scales
         LQ_KNOB(gather_on, "LQ_TUNE_GATHER", 1);
         if (gather_on && !(off & 1) && pl.mode == MODE_COL && !one_group && !scale4 && !scale4u && !cols_pow2 && n < 4294967296ll) {
-            const int64_t nv = n >> 2;
-            const int rem = (int)(n & 3);
-            const int64_t blocks = ceil_div(nv + (rem ? 1 : 0), 512);
-            if (blocks <= 2147483647ll) {
-#define LQ_FLATG(NT_, GM_) hipLaunchKernelGGL((k_flat_fwd<OP, 512, NT_, GM_>), dim3((unsigned)blocks), dim3(512), 0, st, p, fx, nv, rem)
-                if (p.inner == 1) { if (nt) LQ_FLATG(1, 10); else LQ_FLATG(0, 10); }
-                else { if (nt) LQ_FLATG(1, 11); else LQ_FLATG(0, 11); }
-#undef LQ_FLATG
-                return check_hip("flat forward launch") ? -1 : 1;
-            }
+            if (const int r = launch_flat_fwd(p, fx, n, p.inner == 1 ? 10 : 11, -1, true, nt, false, st)) return r;
         }
-        if (!(off & 1) && (one_group || scale4) && !cols_pow2) {
-            const int64_t nv = n >> 2;
-            const int64_t blocks = ceil_div(nv, 512);
-            if (blocks <= 2147483647ll) {
-                const bool wide = n >= 4294967296ll;
-#define LQ_FLAT(NT_, GM_) hipLaunchKernelGGL((k_flat_fwd<OP, 512, NT_, GM_>), dim3((unsigned)blocks), dim3(512), 0, st, p, fx, nv, 0)
-                if (one_group) {
-                    if (nt) {
-                        if (wide) LQ_FLAT(1, 2); else LQ_FLAT(1, 0);
-                    } else {
-                        LQ_FLAT(0, 0);
-                    }
-                } else {
-                    if (nt) {
-                        if (wide) LQ_FLAT(1, 5); else LQ_FLAT(1, 4);
-                    } else {
-                        LQ_FLAT(0, 4);
-                    }
-                }
-#undef LQ_FLAT
-                return check_hip("flat forward launch") ? -1 : 1;
-            }
+        if (!(off & 1) && (one_group || scale4) && !cols_pow2) {      // n % 4 == 0: no remainder block
+            if (const int r = launch_flat_fwd(p, fx, n, one_group ? 0 : 4, one_group ? 2 : 5, false, nt, false, st)) return r;
         }
     }
     if (pl.mode == MODE_COL) {
@@ -533,10 +516,9 @@ static int launch_stream2_impl(Plan& pl, const Params& p, hipStream_t st) {
             if (fc_k2 == 4 && pl.C <= 64 && pl.per4 && flat_cols_ok(pl.C) && nt && !(off & 64)) {
                 const int64_t nv = n >> 2;
                 const int64_t fb = ceil_div(nv, (int64_t)kFlatColsBlock * 4);
-                if (fb <= 2147483647ll && fb * pl.C <= pl.np) {
+                if (fb <= 2147483647ll && fb * pl.C <= pl.np_bound) {
                     pl.ysplit = fb;           // the finalize that follows must walk the partial layout this launch produces
-                    pl.np = fb * pl.C;
-                    pl.n1 = fb;
+                    pl.lay = layout_cols(fb, pl.C, p.inner);
                     hipLaunchKernelGGL((k_flat_cols<OP, 1, 4>), dim3((unsigned)fb), dim3(kFlatColsBlock), 0, st, p, (int)pl.C, nv);
                     return check_hip("flat column launch") ? -1 : 1;
                 }
@@ -547,11 +529,10 @@ static int launch_stream2_impl(Plan& pl, const Params& p, hipStream_t st) {
             const int64_t nv = n >> 2;                        // numel = outer * C is a multiple of 8
             constexpr int kU = 2;
             const int64_t fb = ceil_div(nv, (int64_t)kFlatColsBlock * kU);
-            if (fb <= 2147483647ll && (OP == OP_FWD || fb * pl.C <= pl.np)) {
+            if (fb <= 2147483647ll && (OP == OP_FWD || fb * pl.C <= pl.np_bound)) {
                 if (OP != OP_FWD) {
                     pl.ysplit = fb;           // the finalize that follows must walk the partial layout this launch produces
-                    pl.np = fb * pl.C;
-                    pl.n1 = fb;
+                    pl.lay = layout_cols(fb, pl.C, p.inner);
                 }
                 if (nt) hipLaunchKernelGGL((k_flat_cols<OP, 1, kU>), dim3((unsigned)fb), dim3(kFlatColsBlock), 0, st, p, (int)pl.C, nv);
                 else hipLaunchKernelGGL((k_flat_cols<OP, 0, kU>), dim3((unsigned)fb), dim3(kFlatColsBlock), 0, st, p, (int)pl.C, nv);
@@ -567,8 +548,7 @@ static int launch_stream2_impl(Plan& pl, const Params& p, hipStream_t st) {
                 const int64_t nb2 = ((pl.ysplit / 2) / pl.C) * pl.C;
                 if (nb2 >= pl.C) {
                     pl.ysplit = nb2;
-                    pl.np = nb2 * pl.C;
-                    pl.n1 = nb2;
+                    pl.lay = layout_cols(nb2, pl.C, p.inner);
                     if (per == 12) hipLaunchKernelGGL((k_col_periodic_pipe<OP, 1, 1, 512>), dim3((unsigned)nb2), dim3(512), 0, st, p, (int)pl.C, nb2);
                     else hipLaunchKernelGGL((k_col_periodic_pipe<OP, 1, 2, 512>), dim3((unsigned)nb2), dim3(512), 0, st, p, (int)pl.C, nb2);
                     return check_hip("periodic column launch") ? -1 : 1;
@@ -594,15 +574,14 @@ static int launch_stream2_impl(Plan& pl, const Params& p, hipStream_t st) {
             return check_hip("periodic column launch") ? -1 : 1;
         }
         LQ_KNOB(per_cmax, "LQ_TUNE_PER_CMAX", 256);      // development knob: 0 = always the tile
-        if (pl.C <= per_cmax && pl.C <= 256 && (pl.C < 192 || pl.C % 32 != 0) && periodic_blocks(pl.C) * pl.C <= pl.np) {
+        if (pl.C <= per_cmax && pl.C <= 256 && (pl.C < 192 || pl.C % 32 != 0) && periodic_blocks(pl.C) * pl.C <= pl.np_bound) {
             // 64 < C <= 256: a tile narrower than 256 columns leaves lanes idle and, when C % 32 != 0, starts every row in the
             // middle of a 128-byte line; the periodic form is a flat line-aligned stream for any C.  Measured (K2 / K4 TB/s,
             // tile -> periodic): C = 68: 3.2 / 2.9 -> 5.6 / 5.7; 100: 4.3 / 4.0 -> 5.7 / 5.6; 130: 5.0 / 4.3 -> 5.4 / 5.1;
             // 99 (inner 3): 3.9 / 3.6 -> 5.5 / 5.0; 200, 250: +-3 %; 192 (3 full lines per row): 5.5 / 5.6 -> 5.1 / 5.1, keeps the tile
             const int64_t nb = periodic_blocks(pl.C);
             pl.ysplit = nb;               // the finalize that follows must walk the partial layout this launch produces
-            pl.np = nb * pl.C;
-            pl.n1 = nb;
+            pl.lay = layout_cols(nb, pl.C, p.inner);
             if constexpr (OP == OP_FUSED) {
                 if (nt) hipLaunchKernelGGL((k_col_periodic_pipe<OP, 1, 1>), dim3((unsigned)nb), dim3(kBlock), 0, st, p, (int)pl.C, nb);
                 else hipLaunchKernelGGL((k_col_periodic_pipe<OP, 0, kUp>), dim3((unsigned)nb), dim3(kBlock), 0, st, p, (int)pl.C, nb);
@@ -617,10 +596,9 @@ static int launch_stream2_impl(Plan& pl, const Params& p, hipStream_t st) {
         // size): C = 300: 4.2 / 4.0 -> 5.5 / 5.4; 320: -> 5.6 / 5.5; 450: 4.8 / 4.5 -> 5.4 / 5.4; 500: 5.3 / 4.9 -> 5.5 / 5.6
         if (nt && pl.C > 256 && pl.C <= 512 && pl.C <= per_cmax * 2 && ((double)pl.C / 512.0 < 0.8 || pl.C % 32 != 0)) {
             const int64_t nb = pl.C * ((1024 + pl.C / 2) / pl.C);          // ~1024 blocks of 512 threads, a multiple of C
-            if (nb * pl.C <= pl.np) {
+            if (nb * pl.C <= pl.np_bound) {
                 pl.ysplit = nb;               // the finalize that follows must walk the partial layout this launch produces
-                pl.np = nb * pl.C;
-                pl.n1 = nb;
+                pl.lay = layout_cols(nb, pl.C, p.inner);
                 if constexpr (OP == OP_FUSED) hipLaunchKernelGGL((k_col_periodic_pipe<OP, 1, 1, 512>), dim3((unsigned)nb), dim3(512), 0, st, p, (int)pl.C, nb);
                 else hipLaunchKernelGGL((k_col_periodic_pipe<OP, 1, 2, 512>), dim3((unsigned)nb), dim3(512), 0, st, p, (int)pl.C, nb);
                 return check_hip("periodic column launch") ? -1 : 1;
@@ -639,8 +617,7 @@ static int launch_stream2_impl(Plan& pl, const Params& p, hipStream_t st) {
             const int64_t nby = ceil_div(p.outer, rb);
             pl.rps = rb;                      // the finalize that follows must walk the partial layout this launch produces
             pl.ysplit = nby;
-            pl.np = nby * pl.C;
-            pl.n1 = nby;
+            pl.lay = layout_cols(nby, pl.C, p.inner);
         }
         const int64_t blocks = nbx * pl.ysplit;
         if (blocks > 2147483647ll) return 0;
@@ -808,14 +785,8 @@ static int launch_stream2_impl(Plan& pl, const Params& p, hipStream_t st) {
 #undef LQ_TINY3
         return check_hip("tiny-row launch") ? -1 : 1;
     }
+    }      // kStreamOp<OP>
 }
-
-// The streaming geometry of long rows (512-thread units, nontemporal accesses, two float4 per thread) exists for K1, K2 and K4 --
-// the operations that run on activation-sized tensors.  The penalty terms, the integer view and the element-wise OIHW
-// companion work on weight-sized tensors: they keep the 256-thread units at every size (their entry points plan with
-// make_plan(..., kBlock)), which is a third of the row-stream instantiations and none that a parity test could not reach.
-template <int OP>
-constexpr bool kStreamOp = OP == OP_FWD || OP == OP_BWD || OP == OP_FUSED;
 
 template <int OP>
 static int launch_traverse(Plan& pl, const Params& p, hipStream_t st) {
@@ -836,7 +807,7 @@ static int launch_traverse(Plan& pl, const Params& p, hipStream_t st) {
         // row that is ONE chunk keeps it (2500: 6.8 against 6.3).  The BENCH rows (50176 = 24.5 x 2048) keep 512 threads.
         LQ_KNOB(tune_chunk, "LQ_TUNE_CHUNK", 1);     // development knob: 0 = always the plan's block size
         LQ_KNOB(forced_bs, "LQ_TUNE_BS", 0);
-        if (pl.bs == 512 && vec && tune_chunk && !p.direct && !forced_bs && pl.np_ws >= pl.R * row_chunks(pl.L, 1024)) {
+        if (pl.bs == 512 && vec && tune_chunk && !p.direct && !forced_bs && pl.np_bound >= pl.R * row_chunks(pl.L, 1024)) {
             auto fill = [&](int64_t CH) { return (double)pl.L / (double)(row_chunks(pl.L, CH) * CH); };
             const bool k2_form = (OP == OP_BWD || (OP == OP_FUSED && p.tmode >= 1)) && (double)pl.R * (double)pl.L * 4.0 >= (double)kNtBytes;
             const bool small = k2_form ? (row_chunks(pl.L, 4096) > 1 && fill(1024) > fill(4096) + 0.1) : (fill(1024) > fill(2048) + 0.05);
@@ -844,10 +815,7 @@ static int launch_traverse(Plan& pl, const Params& p, hipStream_t st) {
                 pl.bs = 256;
                 pl.CH = 1024;
                 pl.nc = row_chunks(pl.L, 1024);
-                pl.np = pl.R * pl.nc;              // the finalize that follows must walk the partial layout this launch produces
-                pl.gstride = pl.nc;
-                pl.stride1 = p.G * pl.nc;
-                pl.n2 = pl.nc;
+                pl.lay = layout_row_chunks(pl.R, pl.nc, pl.R / p.G, p.G);      // the finalize that follows must walk the partial layout this launch produces
             }
         }
         const int64_t units = pl.R * pl.nc;
@@ -885,10 +853,7 @@ static int launch_traverse(Plan& pl, const Params& p, hipStream_t st) {
             // the finalize that follows must walk the partial layout this launch produced
             pl.CH = pl.bs * 8;
             pl.nc = nc2;
-            pl.np = pl.R * nc2;
-            pl.gstride = nc2;
-            pl.stride1 = p.G * nc2;
-            pl.n2 = nc2;
+            pl.lay = layout_row_chunks(pl.R, nc2, outer_f, p.G);
             return check_hip("traversal launch");
         }
         // hipExtLaunchKernelGGL with NULL events is a plain launch; with lq_profile_events() set, the events take the kernel's own
@@ -982,10 +947,10 @@ static FinGeom group_geom(const Plan& pl, int64_t outer, int64_t G, int64_t inne
     FinGeom f;
     memset(&f, 0, sizeof(f));
     f.groups = G;
-    f.gstride = pl.gstride;
-    f.n1 = pl.n1;
-    f.stride1 = pl.stride1;
-    f.n2 = pl.n2;
+    f.gstride = pl.lay.gstride;
+    f.n1 = pl.lay.n1;
+    f.stride1 = pl.lay.stride1;
+    f.n2 = pl.lay.n2;
     f.count = (double)outer * (double)inner;
     return f;
 }
@@ -997,7 +962,7 @@ static FinGeom global_geom(const Plan& pl, int64_t outer, int64_t G, int64_t inn
     f.gstride = 0;
     f.n1 = 1;
     f.stride1 = 0;
-    f.n2 = pl.np;
+    f.n2 = pl.lay.np;
     f.count = (double)outer * (double)G * (double)inner;
     return f;
 }
@@ -1013,21 +978,33 @@ static Params base_params(const float* P, const float* s, int64_t outer, int64_t
     return p;
 }
 
-// traversal and, unless the traversal emitted the outputs itself or none is wanted, finalize of a clipped backward (OP_CLIP_BWD[_RNE])
-template <int OP>
-static int clip_backward_launch(Plan& pl, const Params& p, bool direct, float* ds, uint32_t* clipped, int64_t outer, int64_t G,
-                                int64_t inner, hipStream_t st) {
+// The vote's branch of the scale gradient by lambda (lq_ops.hpp).  A NaN lambda fails both comparisons: 2.
+static int tmode_of(float lambda) { return (lambda < 4.0e-4f) ? 0 : ((lambda <= 0.25f) ? 1 : 2); }
+
+// The tail of the per-group reductions: the traversal OP into the bound workspace, then the finalize FIN_OP into o0 / o1 / o2
+// (FinGeom's outputs; NULL = not wanted).  With `allow_direct` and one partial per group the traversal emits the outputs itself
+// and no finalize is launched: o0 and, as the second pointer, o1 or else o2 (emit_direct of the clipped ops hands it on as
+// FinGeom::o2).  No finalize either when no output is wanted (a clipped backward called for dP alone).
+template <int OP, int FIN_OP = OP>
+static int traverse_and_finalize(Plan& pl, Params& p, float* o0, float* o1, uint32_t* o2, bool allow_direct, hipStream_t st) {
+    const bool direct = allow_direct && pl.lay.n1 * pl.lay.n2 == 1;
+    if (direct) {
+        p.direct = 1;
+        p.e0 = o0;
+        p.e1 = o1 ? o1 : reinterpret_cast<float*>(o2);
+        p.ecount = (double)p.outer * (double)p.inner;
+    }
     if (int rc = launch_traverse<OP>(pl, p, st)) return rc;
-    if (direct || (!ds && !clipped)) return LQ_OK;
-    FinGeom f = group_geom(pl, outer, G, inner);
-    f.o0 = ds;
-    f.o2 = clipped;
-    return launch_finalize<OP>(p, f, st);
+    if (direct || (!o0 && !o1 && !o2)) return LQ_OK;
+    FinGeom f = group_geom(pl, p.outer, p.G, p.inner);
+    f.o0 = o0;
+    f.o1 = o1;
+    f.o2 = o2;
+    return launch_finalize<FIN_OP>(p, f, st);
 }
 
 static bool make_conv_tile(ConvTile& ct, int64_t hw, int64_t ci, int64_t co, int64_t outer, int64_t G, int64_t inner);
-static int64_t conv_tile_partials(const ConvTile& ct, int64_t G);
-static void conv_tile_fin(const ConvTile& ct, int64_t G, int64_t& gstride, int64_t& n1, int64_t& stride1, int64_t& n2);
+static PartialLayout conv_tile_layout(const ConvTile& ct, int64_t G);
 
 }  // namespace lq
 
@@ -1156,10 +1133,7 @@ size_t lq_conv_workspace_bytes(int64_t hw, int64_t ci, int64_t co, int64_t outer
     size_t need = ws_bytes_for(make_plan(outer, G, inner));
     ConvTile ct;
     if (hw > 0 && ci > 0 && co > 0 && make_conv_tile(ct, hw, ci, co, outer, G, inner)) {
-        Plan tp;
-        memset(&tp, 0, sizeof(tp));
-        tp.np = conv_tile_partials(ct, G);
-        const size_t t = ws_bytes_for(tp);
+        const size_t t = ws_bytes_for(plan_of_layout(conv_tile_layout(ct, G)));
         if (t > need) need = t;
     }
     return need;
@@ -1185,13 +1159,10 @@ int lq_fq_scale_grad_oihw(const float* P, const float* s, const float* dy_oihw, 
     p.perm_ci = (uint32_t)ci;
     p.perm_co = (uint32_t)co;
     p.lam = lambda;
-    p.tmode = (lambda < 4.0e-4f) ? 0 : ((lambda <= 0.25f) ? 1 : 2);
+    p.tmode = tmode_of(lambda);
     ConvTile ct;
     if (aligned(P, 16) && aligned(dP, 16) && make_conv_tile(ct, hw, ci, co, outer, G, inner)) {       // LDS tiles (lq_conv_tile.hpp)
-        Plan tp;
-        memset(&tp, 0, sizeof(tp));
-        tp.np = conv_tile_partials(ct, G);
-        conv_tile_fin(ct, G, tp.gstride, tp.n1, tp.stride1, tp.n2);
+        const Plan tp = plan_of_layout(conv_tile_layout(ct, G));
         if (ws && ws_bytes < ws_bytes_for(tp))
             return fail(LQ_EWORKSPACE, "lq_fq_scale_grad_oihw: workspace too small: %zu < %zu bytes (size it with lq_conv_workspace_bytes)",
                         ws_bytes, ws_bytes_for(tp));
@@ -1203,18 +1174,7 @@ int lq_fq_scale_grad_oihw(const float* P, const float* s, const float* dy_oihw, 
         return launch_finalize<OP_BWD>(p, f, (hipStream_t)stream);
     }
     if ((rc = bind_ws(p, pl, ws, ws_bytes))) return rc;
-    const bool direct = pl.n1 * pl.n2 == 1;
-    if (direct) {
-        p.direct = 1;
-        p.e0 = ds;
-        p.e1 = nullptr;
-        p.ecount = (double)outer * (double)inner;
-    }
-    if ((rc = launch_traverse<OP_BWD_PERM>(pl, p, (hipStream_t)stream))) return rc;
-    if (direct) return LQ_OK;
-    FinGeom f = group_geom(pl, outer, G, inner);
-    f.o0 = ds;
-    return launch_finalize<OP_BWD>(p, f, (hipStream_t)stream);
+    return traverse_and_finalize<OP_BWD_PERM, OP_BWD>(pl, p, ds, nullptr, nullptr, true, (hipStream_t)stream);
 }
 
 int lq_fq_scale_grad(const float* P, const float* s, const float* dy, float lambda, float* ds, float* parts, void* ws,
@@ -1229,21 +1189,9 @@ int lq_fq_scale_grad(const float* P, const float* s, const float* dy, float lamb
     Params p = base_params(P, s, outer, G, inner);
     p.dy = dy;
     p.lam = lambda;
-    p.tmode = (lambda < 4.0e-4f) ? 0 : ((lambda <= 0.25f) ? 1 : 2);   // NaN lambda -> 2
+    p.tmode = tmode_of(lambda);
     if ((rc = bind_ws(p, pl, ws, ws_bytes))) return rc;
-    const bool direct = pl.n1 * pl.n2 == 1;      // one partial per group: the traversal emits ds itself, no finalize launch
-    if (direct) {
-        p.direct = 1;
-        p.e0 = ds;
-        p.e1 = parts;
-        p.ecount = (double)outer * (double)inner;
-    }
-    if ((rc = launch_traverse<OP_BWD>(pl, p, (hipStream_t)stream))) return rc;
-    if (direct) return LQ_OK;
-    FinGeom f = group_geom(pl, outer, G, inner);
-    f.o0 = ds;
-    f.o1 = parts;
-    return launch_finalize<OP_BWD>(p, f, (hipStream_t)stream);
+    return traverse_and_finalize<OP_BWD>(pl, p, ds, parts, nullptr, true, (hipStream_t)stream);
 }
 
 int lq_fq_scale_grad_ste(const float* P, const float* s, const float* dy, float grad_scale, float* ds, void* ws, size_t ws_bytes,
@@ -1259,18 +1207,7 @@ int lq_fq_scale_grad_ste(const float* P, const float* s, const float* dy, float 
     p.dy = dy;
     p.c_scale = grad_scale;
     if ((rc = bind_ws(p, pl, ws, ws_bytes))) return rc;
-    const bool direct = pl.n1 * pl.n2 == 1;      // one partial per group: the traversal emits ds itself, no finalize launch
-    if (direct) {
-        p.direct = 1;
-        p.e0 = ds;
-        p.e1 = nullptr;
-        p.ecount = (double)outer * (double)inner;
-    }
-    if ((rc = launch_traverse<OP_STE_SCALE>(pl, p, (hipStream_t)stream))) return rc;
-    if (direct) return LQ_OK;
-    FinGeom f = group_geom(pl, outer, G, inner);
-    f.o0 = ds;
-    return launch_finalize<OP_STE_SCALE>(p, f, (hipStream_t)stream);
+    return traverse_and_finalize<OP_STE_SCALE>(pl, p, ds, nullptr, nullptr, true, (hipStream_t)stream);
 }
 
 static int check_clip_range(const char* fn, int32_t qmin, int32_t qmax) {
@@ -1343,17 +1280,9 @@ static int clip_backward(const char* fn, const float* P, const float* s, const f
     if (!ws || ws_bytes < ws_bytes_for(pl)) return fail(LQ_EINVAL, "%s: workspace %s (%zu bytes given, %zu needed)", fn,
                                                         ws ? "too small" : "is NULL", ws ? ws_bytes : (size_t)0, ws_bytes_for(pl));
     if ((rc = bind_ws(p, pl, ws, ws_bytes))) return rc;
-    const bool direct = pl.n1 * pl.n2 == 1;      // one partial per group: the traversal emits ds and the count itself
-    if (direct) {
-        p.direct = 1;
-        p.e0 = ds;
-        p.e1 = reinterpret_cast<float*>(clipped);      // emit_direct<OP_CLIP_BWD[_RNE]> hands it on as FinGeom::o2
-        p.ecount = (double)outer * (double)inner;
-    }
     // the rounding is a template parameter of the op trait: each pair has its own kernels, none tests a flag
-    if (rounding == LQ_ROUND_NEAREST_EVEN)
-        return clip_backward_launch<OP_CLIP_BWD_RNE>(pl, p, direct, ds, clipped, outer, G, inner, (hipStream_t)stream);
-    return clip_backward_launch<OP_CLIP_BWD>(pl, p, direct, ds, clipped, outer, G, inner, (hipStream_t)stream);
+    if (rounding == LQ_ROUND_NEAREST_EVEN) return traverse_and_finalize<OP_CLIP_BWD_RNE>(pl, p, ds, nullptr, clipped, true, (hipStream_t)stream);
+    return traverse_and_finalize<OP_CLIP_BWD>(pl, p, ds, nullptr, clipped, true, (hipStream_t)stream);
 }
 
 int lq_fq_backward_clip_r(const float* P, const float* s, const float* dy, int32_t qmin, int32_t qmax, int rounding, float grad_scale,
@@ -1380,21 +1309,10 @@ int lq_fq_fwd_bwd_fused(const float* P, const float* s, const float* dy, float l
     Params p = base_params(P, s, outer, G, inner);
     p.dy = dy;
     p.lam = lambda;
-    p.tmode = (lambda < 4.0e-4f) ? 0 : ((lambda <= 0.25f) ? 1 : 2);   // NaN lambda -> 2
+    p.tmode = tmode_of(lambda);
     p.out = out;
     if ((rc = bind_ws(p, pl, ws, ws_bytes))) return rc;
-    const bool direct = pl.n1 * pl.n2 == 1;
-    if (direct) {
-        p.direct = 1;
-        p.e0 = ds;
-        p.e1 = nullptr;
-        p.ecount = (double)outer * (double)inner;
-    }
-    if ((rc = launch_traverse<OP_FUSED>(pl, p, (hipStream_t)stream))) return rc;
-    if (direct) return LQ_OK;
-    FinGeom f = group_geom(pl, outer, G, inner);
-    f.o0 = ds;
-    return launch_finalize<OP_FUSED>(p, f, (hipStream_t)stream);
+    return traverse_and_finalize<OP_FUSED>(pl, p, ds, nullptr, nullptr, true, (hipStream_t)stream);
 }
 
 int lq_penalty_maxbin_fwd(const float* P, const float* s, float* mb, uint32_t* ties, float* term, void* ws,
@@ -1472,10 +1390,7 @@ int lq_penalty_difference_bwd(const float* P, const float* s, const float* c_dev
     p.c_scale = c_scale;
     p.out = dP;
     if ((rc = bind_ws(p, pl, ws, ws_bytes))) return rc;
-    if ((rc = launch_traverse<OP_DIFF_BWD>(pl, p, (hipStream_t)stream))) return rc;
-    FinGeom f = group_geom(pl, outer, G, inner);
-    f.o0 = ds;
-    return launch_finalize<OP_DIFF_BWD>(p, f, (hipStream_t)stream);
+    return traverse_and_finalize<OP_DIFF_BWD>(pl, p, ds, nullptr, nullptr, false, (hipStream_t)stream);
 }
 
 int lq_penalty_inverse_fwd(const float* s, float* term, int64_t G, void* stream) {
@@ -1652,18 +1567,15 @@ static bool make_conv_tile(ConvTile& ct, int64_t hw, int64_t ci, int64_t co, int
     return true;
 }
 
-static int64_t conv_tile_partials(const ConvTile& ct, int64_t G) {
-    return ct.kind == 0 ? (int64_t)ct.ci * ct.nto : G * (int64_t)ct.nto * ct.ntc * kWavesPerBlock;
+// the tile's partials (see ct_flush): per group one run of a partial per column tile (kind 0), or per (tile, wave) (kind 1)
+static PartialLayout conv_tile_layout(const ConvTile& ct, int64_t G) {
+    const int64_t per_group = ct.kind == 0 ? (int64_t)ct.nto : (int64_t)ct.nto * ct.ntc * kWavesPerBlock;
+    return {(ct.kind == 0 ? (int64_t)ct.ci : G) * per_group, per_group, 1, 0, per_group};
 }
 
-// finalize geometry of the tile's partials (see ct_flush)
-static void conv_tile_fin(const ConvTile& ct, int64_t G, int64_t& gstride, int64_t& n1, int64_t& stride1, int64_t& n2) {
-    n1 = 1;
-    stride1 = 0;
-    n2 = ct.kind == 0 ? (int64_t)ct.nto : (int64_t)ct.nto * ct.ntc * kWavesPerBlock;
-    gstride = n2;
-    (void)G;
-}
+// the batch's group fragments (lq_batch_cols.hpp): one partial per (row block, fragment); finalize_frag_body walks them through
+// Task::fg, the geometry here is kept consistent for the workspace bound
+static PartialLayout layout_frags(int64_t nby, int64_t F) { return {nby * F, 0, nby, F, 1}; }
 
 // Row blocks of the batch's scale-gradient column tiles are sized by the BATCH, not per tensor: make_plan aims at about 512 blocks
 // per tensor (right for a launch of its own); 40 or 108 tensors in one launch then make 2000-5300 blocks of 2-8 K elements, more than
@@ -1704,11 +1616,16 @@ constexpr double kBatchPeriodicMin = 32768.0;      // elements from which a C <=
 static int fill_task(Task& t, const lq_tensor_desc& d, bool bwd, bool allow_tile, lq_task_table& tb, double batch_w = 0.0) {
     memset(&t, 0, sizeof(t));
     Plan pl = make_plan(d.outer, d.G, d.inner, kBlock);
+    // a task runs one form, chosen here: where that is not the plan's, its partial count is the bound of the task's workspace slice too
+    auto relayout = [&pl](const PartialLayout& lay) {
+        pl.lay = lay;
+        pl.np_bound = lay.np;
+    };
     t.p = base_params(d.P, d.s, d.outer, d.G, d.inner);
     t.p.out = d.out;
     t.p.dy = d.dy;
     t.p.lam = d.lambda;
-    t.p.tmode = (d.lambda < 4.0e-4f) ? 0 : ((d.lambda <= 0.25f) ? 1 : 2);
+    t.p.tmode = tmode_of(d.lambda);
     bool tile = false;
     if (d.conv_co > 0) {
         t.p.out_perm = bwd ? nullptr : d.out_oihw;
@@ -1736,15 +1653,12 @@ static int fill_task(Task& t, const lq_tensor_desc& d, bool bwd, bool allow_tile
             LQ_KNOB(frag, "LQ_TUNE_BATCH_FRAG", 1);    // development: 0 = a partial per column (the generic layout)
             const bool grouped = frag && d.inner > 1 && d.inner <= 64;
             t.fg = make_frag_geom(d.G, d.inner, pl.C, grouped);
-            if (!grouped) t.fg.F = (uint32_t)pl.C;
-            pl.np = pl.ysplit * (int64_t)t.fg.F;
-            pl.n1 = pl.ysplit;
-            if (grouped) {                             // read by finalize_frag_body through t.fg; kept consistent for the workspace bound
-                pl.gstride = 0;
-                pl.stride1 = t.fg.F;
-                pl.n2 = 1;
+            if (grouped) {
+                relayout(layout_frags(pl.ysplit, (int64_t)t.fg.F));
             } else {
+                t.fg.F = (uint32_t)pl.C;
                 t.fg.gpb = 0;
+                relayout(layout_cols(pl.ysplit, pl.C, d.inner));
             }
         } else if (!bwd && batch_w > 0.0 && t.col_variant >= 4) {
             // forward tiles keep make_plan's row blocks (16-32 rows: 1968 blocks for the ResNet-18-like set, all resident at 62 VGPRs)
@@ -1760,8 +1674,7 @@ static int fill_task(Task& t, const lq_tensor_desc& d, bool bwd, bool allow_tile
             pl.ysplit = batch_periodic_blocks(pl.C, (double)d.outer * (double)pl.C, batch_w);
             pl.rps = pl.ysplit;                        // variant 6: the block count travels in `rps`
             t.nbx = 1;
-            pl.np = pl.ysplit * pl.C;                  // one partial per (block, column)
-            pl.n1 = pl.ysplit;
+            relayout(layout_cols(pl.ysplit, pl.C, d.inner));      // one partial per (block, column)
         }
     }
     t.rps = pl.rps;
@@ -1779,10 +1692,7 @@ static int fill_task(Task& t, const lq_tensor_desc& d, bool bwd, bool allow_tile
             if (ru > 1) {
                 t.ru = ru;
                 pl.nc = row_chunks(pl.L, (int64_t)kBlock * 4 * ru);
-                pl.np = pl.R * pl.nc;
-                pl.gstride = pl.nc;                    // partial (row o * G + g, chunk c) at (o * G + g) * nc + c
-                pl.stride1 = d.G * pl.nc;
-                pl.n2 = pl.nc;
+                relayout(layout_row_chunks(pl.R, pl.nc, pl.R / d.G, d.G));
                 t.nc = pl.nc;
             }
         }
@@ -1798,16 +1708,12 @@ static int fill_task(Task& t, const lq_tensor_desc& d, bool bwd, bool allow_tile
     t.first_block = (uint32_t)blocks;            // block COUNT until finish_table() turns it into a prefix
     if (bwd) {
         t.first_group = (uint32_t)d.G;           // likewise
-        int64_t np = pl.np;
-        t.gstride = pl.gstride;
-        t.n1 = pl.n1;
-        t.stride1 = pl.stride1;
-        t.n2 = pl.n2;
-        if (tile) {
-            np = conv_tile_partials(t.ct, d.G);
-            conv_tile_fin(t.ct, d.G, t.gstride, t.n1, t.stride1, t.n2);
-        }
-        t.np_pad = (np + 63) / 64 * 64;
+        if (tile) relayout(conv_tile_layout(t.ct, d.G));
+        t.gstride = pl.lay.gstride;
+        t.n1 = pl.lay.n1;
+        t.stride1 = pl.lay.stride1;
+        t.n2 = pl.lay.n2;
+        t.np_pad = (int64_t)ws_partials(pl);
         t.count = (double)d.outer * (double)d.inner;
     }
     if (tile) tb.has_tile = true;
@@ -2088,9 +1994,43 @@ int lq_batch_forward(const lq_batch* b, void* stream) {
 }
 
 }  // extern "C"
-extern "C" {
 
-static int batch_scale_grad(const lq_batch* b, const float* const* dy, void* ws, size_t ws_bytes, void* stream, bool oihw, const AdamHyper& ah);
+// ---- checks the batch entry points share ----
+// Does the traversal the task was planned for touch its streams with 16-byte accesses?
+static bool task_wants16(const lq::Task& t) {
+    return t.mode == MODE_CONV_TILE || (t.mode != MODE_COL && t.vec) || (t.mode == MODE_COL && t.col_variant >= 4);
+}
+
+static int check_batch_workspace(const char* fn, const lq_batch* b, const void* ws, size_t ws_bytes) {
+    if (!ws) return fail(LQ_EWORKSPACE, "%s: workspace is NULL (need %zu bytes)", fn, b->ws_bytes);
+    if (!aligned(ws, 16)) return fail(LQ_EALIGN, "%s: workspace must be 16-byte aligned", fn);
+    if (ws_bytes < b->ws_bytes) return fail(LQ_EWORKSPACE, "%s: workspace too small: %zu < %zu bytes", fn, ws_bytes, b->ws_bytes);
+    return LQ_OK;
+}
+
+// The upstream gradient of every task of `tb` into pk.dy: the caller's dy[tensor] or else the descriptor's.  oihw: gradients of
+// conv kernels are read through the permutation (LDS tile or element-wise), never with vector loads.  A dy off the 16-byte grid
+// of a task that wants it there fails at that tensor, or with `report16_last` after every dy was looked at, without an index.
+// per_task(i, task): what else the caller checks or collects per task, after the task's dy passed.
+template <class F>
+static int gather_dy(const char* fn, const lq_task_table& tb, const float* const* dy, bool oihw, PtrPack& pk, bool report16_last, F&& per_task) {
+    bool all_aligned = true;
+    for (size_t i = 0; i < tb.h.size(); ++i) {
+        const lq::Task& t = tb.h[i];
+        const float* d = dy ? dy[tb.index[i]] : t.p.dy;
+        if (!d) return fail(LQ_EINVAL, "%s: no upstream gradient for tensor %d", fn, tb.index[i]);
+        if (!aligned(d, 4)) return fail(LQ_EALIGN, "%s: dy of tensor %d misaligned", fn, tb.index[i]);
+        const bool gathered = oihw && t.p.perm_co != 0;
+        if (!gathered && task_wants16(t) && !aligned(d, 16)) {
+            if (!report16_last) return fail(LQ_EALIGN, "%s: dy of the 16-byte aligned tensor %d is not 16-byte aligned", fn, tb.index[i]);
+            all_aligned = false;
+        }
+        if (int rc = per_task(i, t)) return rc;
+        pk.dy[i] = d;
+    }
+    if (!all_aligned) return fail(LQ_EALIGN, "%s: a 16-byte aligned tensor got a dy that is not 16-byte aligned", fn);
+    return LQ_OK;
+}
 
 static AdamHyper adam_hyper(double lr, double beta1, double beta2, double eps, int64_t step, const int64_t* step_dev, int mode, int on) {
     AdamHyper h;
@@ -2110,6 +2050,31 @@ static AdamHyper adam_hyper(double lr, double beta1, double beta2, double eps, i
     h.on = on;
     return h;
 }
+
+static int batch_scale_grad(const lq_batch* b, const float* const* dy, void* ws, size_t ws_bytes, void* stream, bool oihw, const AdamHyper& ah) {
+    const char* fn = "lq_batch_scale_grad";
+    if (!b) return fail(LQ_EINVAL, "%s: NULL batch", fn);
+    const lq_task_table& tb = oihw ? b->bwd_o : b->bwd;
+    if (tb.h.empty()) return LQ_OK;
+    int rc = check_batch_workspace(fn, b, ws, ws_bytes);
+    if (rc) return rc;
+    PtrPack pk;
+    memset(&pk, 0, sizeof(pk));
+    if ((rc = gather_dy(fn, tb, dy, oihw, pk, true, [](size_t, const lq::Task&) { return LQ_OK; }))) return rc;
+    CoefPack cf;
+    const int nt = (int)tb.h.size();
+    if (oihw)
+        hipLaunchKernelGGL((k_batch_traverse<OP_BWD_PERM>), dim3(tb.blocks), dim3(kBlock), 0, (hipStream_t)stream, tb.d, tb.block_task_d, nt,
+                           (uint32_t*)ws, pk, oihw ? 3 : 1, cf);
+    else
+        hipLaunchKernelGGL((k_batch_traverse<OP_BWD>), dim3(tb.blocks), dim3(kBlock), 0, (hipStream_t)stream, tb.d, tb.block_task_d, nt,
+                           (uint32_t*)ws, pk, 1, cf);
+    if ((rc = check_hip("batch scale-grad launch"))) return rc;
+    hipLaunchKernelGGL((k_batch_finalize_t<OP_BWD>), dim3(tb.fin_blocks), dim3(256), 0, (hipStream_t)stream, tb.fin_blocks_d, (uint32_t*)ws, ah);
+    return check_hip("batch finalize launch");
+}
+
+extern "C" {
 
 int lq_batch_scale_grad(const lq_batch* b, const float* const* dy, void* ws, size_t ws_bytes, void* stream) {
     return batch_scale_grad(b, dy, ws, ws_bytes, stream, false, adam_hyper(0, 0, 0, 0, 1, nullptr, LQ_ADAM_KERAS, 0));
@@ -2135,41 +2100,6 @@ int lq_batch_scale_grad_step(const lq_batch* b, const float* const* dy, int dy_o
 
 }  // extern "C"
 
-static int batch_scale_grad(const lq_batch* b, const float* const* dy, void* ws, size_t ws_bytes, void* stream, bool oihw, const AdamHyper& ah) {
-    if (!b) return fail(LQ_EINVAL, "lq_batch_scale_grad: NULL batch");
-    const lq_task_table& tb = oihw ? b->bwd_o : b->bwd;
-    if (tb.h.empty()) return LQ_OK;
-    if (!ws) return fail(LQ_EWORKSPACE, "lq_batch_scale_grad: workspace is NULL (need %zu bytes)", b->ws_bytes);
-    if (!aligned(ws, 16)) return fail(LQ_EALIGN, "lq_batch_scale_grad: workspace must be 16-byte aligned");
-    if (ws_bytes < b->ws_bytes) return fail(LQ_EWORKSPACE, "lq_batch_scale_grad: workspace too small: %zu < %zu bytes", ws_bytes, b->ws_bytes);
-    PtrPack pk;
-    memset(&pk, 0, sizeof(pk));
-    bool all_aligned = true;
-    for (size_t i = 0; i < tb.h.size(); ++i) {
-        const lq::Task& t = tb.h[i];
-        const float* d = dy ? dy[tb.index[i]] : t.p.dy;
-        if (!d) return fail(LQ_EINVAL, "lq_batch_scale_grad: no upstream gradient for tensor %d", tb.index[i]);
-        if (!aligned(d, 4)) return fail(LQ_EALIGN, "lq_batch_scale_grad: dy of tensor %d misaligned", tb.index[i]);
-        const bool gathered = oihw && t.p.perm_co != 0;      // read through the permutation (LDS tile or element-wise): no vector loads
-        const bool wants16 = t.mode == MODE_CONV_TILE || (t.mode != MODE_COL && t.vec) || (t.mode == MODE_COL && t.col_variant >= 4);
-        if (!gathered && wants16 && !aligned(d, 16)) all_aligned = false;
-        pk.dy[i] = d;
-    }
-    if (!all_aligned) return fail(LQ_EALIGN, "lq_batch_scale_grad: a 16-byte aligned tensor got a dy that is not 16-byte aligned");
-    CoefPack cf;
-    const int nt = (int)tb.h.size();
-    if (oihw)
-        hipLaunchKernelGGL((k_batch_traverse<OP_BWD_PERM>), dim3(tb.blocks), dim3(kBlock), 0, (hipStream_t)stream, tb.d, tb.block_task_d, nt,
-                           (uint32_t*)ws, pk, oihw ? 3 : 1, cf);
-    else
-        hipLaunchKernelGGL((k_batch_traverse<OP_BWD>), dim3(tb.blocks), dim3(kBlock), 0, (hipStream_t)stream, tb.d, tb.block_task_d, nt,
-                           (uint32_t*)ws, pk, 1, cf);
-    int rc = check_hip("batch scale-grad launch");
-    if (rc) return rc;
-    hipLaunchKernelGGL((k_batch_finalize_t<OP_BWD>), dim3(tb.fin_blocks), dim3(256), 0, (hipStream_t)stream, tb.fin_blocks_d, (uint32_t*)ws, ah);
-    return check_hip("batch finalize launch");
-}
-
 // Value outputs of the penalty entry points (lq_hip.h: lq_batch_penalty_values, lq_batch_penalty_grads_values).
 struct PenaltyValueArgs {
     const float* dims;
@@ -2186,13 +2116,6 @@ static int check_penalty_value_args(const char* fn, int kind, const PenaltyValue
     if (!aligned(va.terms, 4) || !aligned(va.penalty, 4)) return fail(LQ_EALIGN, "%s: terms_dev / penalty_dev must be 4-byte aligned", fn);
     if (!va.dims) return fail(LQ_EINVAL, "%s: dims is NULL", fn);
     if (!va.layer_start) return fail(LQ_EINVAL, "%s: layer_start is NULL", fn);
-    return LQ_OK;
-}
-
-static int check_penalty_workspace(const char* fn, const lq_batch* b, const void* ws, size_t ws_bytes) {
-    if (!ws) return fail(LQ_EWORKSPACE, "%s: workspace is NULL (need %zu bytes)", fn, b->ws_bytes);
-    if (!aligned(ws, 16)) return fail(LQ_EALIGN, "%s: workspace must be 16-byte aligned", fn);
-    if (ws_bytes < b->ws_bytes) return fail(LQ_EWORKSPACE, "%s: workspace too small: %zu < %zu bytes", fn, ws_bytes, b->ws_bytes);
     return LQ_OK;
 }
 
@@ -2252,15 +2175,11 @@ static int batch_penalty_grads(const char* fn, const lq_batch* b, int kind, cons
     hipStream_t st = (hipStream_t)stream;
     if (kind != LQ_PENALTY_INVERSE) {
         if (!grad) return fail(LQ_EINVAL, "%s: grad pointers are NULL", fn);
-        if (!ws) return fail(LQ_EWORKSPACE, "%s: workspace is NULL (need %zu bytes)", fn, b->ws_bytes);
-        if (!aligned(ws, 16)) return fail(LQ_EALIGN, "%s: workspace must be 16-byte aligned", fn);
-        if (ws_bytes < b->ws_bytes) return fail(LQ_EWORKSPACE, "%s: workspace too small: %zu < %zu bytes", fn, ws_bytes, b->ws_bytes);
+        if (const int rc = check_batch_workspace(fn, b, ws, ws_bytes)) return rc;
         for (int i = 0; i < nt; ++i) {
             float* gi = grad[tb.index[i]];
             if (!gi || !aligned(gi, 4)) return fail(LQ_EINVAL, "%s: gradient buffer of tensor %d missing", fn, tb.index[i]);
-            const Task& t = tb.h[i];
-            const bool wants16 = (t.mode != MODE_COL && t.vec) || (t.mode == MODE_COL && t.col_variant >= 4);
-            if (wants16 && !aligned(gi, 16)) return fail(LQ_EALIGN, "%s: gradient buffer of tensor %d is not 16-byte aligned", fn, tb.index[i]);
+            if (task_wants16(tb.h[i]) && !aligned(gi, 16)) return fail(LQ_EALIGN, "%s: gradient buffer of tensor %d is not 16-byte aligned", fn, tb.index[i]);
             pk.dy[i] = gi;
         }
     }
@@ -2313,7 +2232,7 @@ int lq_batch_penalty_values(const lq_batch* b, int kind, const float* dims, cons
     if (rc) return rc;
     if (!b) return fail(LQ_EINVAL, "%s: NULL batch", fn);
     if (b->pen.h.size() != (size_t)b->n) return fail(LQ_EINVAL, "%s: every tensor of the batch needs a ds buffer", fn);
-    if (kind != LQ_PENALTY_INVERSE && (rc = check_penalty_workspace(fn, b, ws, ws_bytes))) return rc;
+    if (kind != LQ_PENALTY_INVERSE && (rc = check_batch_workspace(fn, b, ws, ws_bytes))) return rc;
     return launch_penalty_values(fn, b, kind, va, ws, false, (hipStream_t)stream);
 }
 
@@ -2323,23 +2242,18 @@ int lq_batch_scale_grad_ste(const lq_batch* b, const float* const* dy, const flo
     if (!b) return fail(LQ_EINVAL, "%s: NULL batch", fn);
     const lq_task_table& tb = b->pen;
     if (tb.h.empty()) return LQ_OK;
-    int rc = check_penalty_workspace(fn, b, ws, ws_bytes);
+    int rc = check_batch_workspace(fn, b, ws, ws_bytes);
     if (rc) return rc;
     PtrPack pk;
     CoefPack cf;
     memset(&pk, 0, sizeof(pk));
     memset(&cf, 0, sizeof(cf));
     const int nt = (int)tb.h.size();
-    for (int i = 0; i < nt; ++i) {
-        const Task& t = tb.h[i];
-        const float* d = dy ? dy[tb.index[i]] : t.p.dy;
-        if (!d) return fail(LQ_EINVAL, "%s: no upstream gradient for tensor %d", fn, tb.index[i]);
-        if (!aligned(d, 4)) return fail(LQ_EALIGN, "%s: dy of tensor %d misaligned", fn, tb.index[i]);
-        const bool wants16 = (t.mode != MODE_COL && t.vec) || (t.mode == MODE_COL && t.col_variant >= 4);
-        if (wants16 && !aligned(d, 16)) return fail(LQ_EALIGN, "%s: dy of the 16-byte aligned tensor %d is not 16-byte aligned", fn, tb.index[i]);
-        pk.dy[i] = d;
+    rc = gather_dy(fn, tb, dy, false, pk, false, [&](size_t i, const Task&) {
         cf.c[i] = grad_scale ? grad_scale[tb.index[i]] : 1.0f;
-    }
+        return LQ_OK;
+    });
+    if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL((k_batch_traverse<OP_STE_SCALE>), dim3(tb.blocks), dim3(kBlock), 0, st, tb.d, tb.block_task_d, nt, (uint32_t*)ws, pk, 1, cf);
     if ((rc = check_hip("batch STE scale-grad launch"))) return rc;
@@ -2348,8 +2262,6 @@ int lq_batch_scale_grad_ste(const lq_batch* b, const float* const* dy, const flo
 }
 
 // ---- clipped b-bit tensors in the batch (lq_hip.h: lq_batch_set_clip) ----
-// Does the traversal the task was planned for touch its streams with 16-byte accesses?  (the rule of lq_batch_scale_grad_ste)
-static bool task_wants16(const Task& t) { return (t.mode != MODE_COL && t.vec) || (t.mode == MODE_COL && t.col_variant >= 4); }
 
 int lq_batch_set_clip(lq_batch* b, const int32_t* qmin, const int32_t* qmax, int n, int rounding) {
     const char* fn = "lq_batch_set_clip";
@@ -2444,23 +2356,19 @@ int lq_batch_backward_clip(const lq_batch* b, const float* const* dy, const floa
     if (!b) return fail(LQ_EINVAL, "%s: NULL batch", fn);
     if (!b->has_clip) return fail(LQ_EINVAL, "%s: the batch has no ranges (lq_batch_set_clip)", fn);
     const lq_task_table& tb = b->cbwd;
-    int rc = check_penalty_workspace(fn, b, ws, ws_bytes);
+    int rc = check_batch_workspace(fn, b, ws, ws_bytes);
     if (rc) return rc;
     PtrPack pk;
     CoefPack cf;
     memset(&pk, 0, sizeof(pk));
     memset(&cf, 0, sizeof(cf));
     const int nt = (int)tb.h.size();
-    for (int i = 0; i < nt; ++i) {
-        const Task& t = tb.h[i];
-        const float* d = dy ? dy[tb.index[i]] : t.p.dy;
-        if (!d) return fail(LQ_EINVAL, "%s: no upstream gradient for tensor %d", fn, tb.index[i]);
-        if (!aligned(d, 4)) return fail(LQ_EALIGN, "%s: dy of tensor %d misaligned", fn, tb.index[i]);
-        if (task_wants16(t) && !aligned(d, 16)) return fail(LQ_EALIGN, "%s: dy of the 16-byte aligned tensor %d is not 16-byte aligned", fn, tb.index[i]);
+    rc = gather_dy(fn, tb, dy, false, pk, false, [&](size_t i, const Task& t) {
         if (grad_scale && !t.ds) return fail(LQ_EINVAL, "%s: tensor %d has no ds buffer (pass grad_scale = NULL for the mask alone)", fn, tb.index[i]);
-        pk.dy[i] = d;
         cf.c[i] = grad_scale ? grad_scale[tb.index[i]] : 0.0f;
-    }
+        return (int)LQ_OK;
+    });
+    if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (b->clip_rounding == LQ_ROUND_NEAREST_EVEN)
         hipLaunchKernelGGL((k_batch_traverse<OP_CLIP_BWD_RNE>), dim3(tb.blocks), dim3(kBlock), 0, st, tb.d, tb.block_task_d, nt, (uint32_t*)ws, pk, 0, cf);

@@ -1,6 +1,7 @@
 """Generates tests/golden/golden_cases.npz and tests/golden/mnist_expected.npz.
 
     python tests/golden/make_golden.py
+    python tests/golden/make_golden.py --workspace-bytes PATH/liblq_hip.so     # writes workspace_bytes.json only
 
 The reference cannot run here (TensorFlow 2.11 not installed, no network) and ships no
 golden vectors, so these fixtures are produced by the float32 restatement oracle/lq_oracle.py,
@@ -128,5 +129,62 @@ def main():
     print("mnist_expected:", len(meta), "entries")
 
 
+# ---- workspace contract ---------------------------------------------------------------
+# lq_workspace_bytes / lq_conv_workspace_bytes are ABI: callers size buffers by them.  The pin is taken from a library built
+# BEFORE a change to the host planning code and reproduced by the library under test (tests/test_host_cpu.py); both functions
+# are pure host code, no device is needed.
+WS_OUTER = (1, 2, 3, 31, 32, 33, 256, 4096, 100003)
+WS_G = (1, 2, 3, 9, 10, 64, 65, 200, 256, 257, 320, 512, 1000, 1024, 4096)
+WS_INNER = (1, 2, 3, 4, 5, 8, 15, 16, 17, 49, 64, 68, 100, 199, 200, 1023, 1024, 1025, 1225, 2047, 2048, 4100, 50176)
+WS_CONV_CONFIGS = ("imagenette", "resnet50")      # the ResNet-18-like and ResNet-50-like sets of tools/bench_weights.py
+WS_ORIENTATIONS = ("rowwise", "columnwise", "channelwise", "scalar")
+
+
+def workspace_conv_cases():
+    """[hw, ci, co, outer, G, inner] of every distinct conv kernel of the two sets, for the four orientations."""
+    import torch
+    import learned_quantization_amd as lq
+    cases = []
+    for config in WS_CONV_CONFIGS:
+        lq.reset_layer_names()
+        model = lq.build_model(config, mode="nq", value=(1e-10, 1e-11) if config == "resnet50" else 1e-11, seed=42,
+                               orientation="rowwise", device=torch.device("cpu"))
+        shapes = sorted({tuple(m.kernel.shape) for m in model.modules() if getattr(m, "kernel", None) is not None and m.kernel.dim() == 4})
+        for kh, kw, ci, co in shapes:
+            for orient in WS_ORIENTATIONS:
+                outer, G, inner = lq.group_descriptor((kh, kw, ci, co), lq.scale_shape((kh, kw, ci, co), orient))
+                c = [kh * kw, ci, co, outer, G, inner]
+                if c not in cases:
+                    cases.append(c)
+    return cases
+
+
+def workspace_bytes(lib_path):
+    """The contract as `lib_path` answers it: {"grid": [...], "conv": [[hw, ci, co, outer, G, inner, bytes], ...]}."""
+    import ctypes
+    lib = ctypes.CDLL(lib_path)
+    for fn, n in ((lib.lq_workspace_bytes, 3), (lib.lq_conv_workspace_bytes, 6)):
+        fn.restype = ctypes.c_size_t
+        fn.argtypes = [ctypes.c_int64] * n
+    grid = [int(lib.lq_workspace_bytes(o, g, i)) for o in WS_OUTER for g in WS_G for i in WS_INNER]
+    conv = [c + [int(lib.lq_conv_workspace_bytes(*c))] for c in workspace_conv_cases()]
+    return {"grid": grid, "conv": conv}
+
+
+def main_workspace(lib_path, commit):
+    doc = {"header": "lq_workspace_bytes over outer x G x inner (outer-major, the WS_* tuples of make_golden.py) and "
+                     "lq_conv_workspace_bytes of the conv kernels of the ResNet-18-like and ResNet-50-like sets; generated from a "
+                     "library built at the PARENT commit " + commit + ", never from the library under test",
+           "outer": list(WS_OUTER), "G": list(WS_G), "inner": list(WS_INNER)}
+    doc.update(workspace_bytes(lib_path))
+    with open(os.path.join(HERE, "workspace_bytes.json"), "w") as f:
+        json.dump(doc, f, separators=(",", ":"))
+        f.write("\n")
+    print("workspace_bytes.json:", len(doc["grid"]), "descriptors,", len(set(doc["grid"])), "distinct values,", len(doc["conv"]), "conv cases")
+
+
 if __name__ == "__main__":
-    main()
+    if len(sys.argv) >= 3 and sys.argv[1] == "--workspace-bytes":
+        main_workspace(os.path.abspath(sys.argv[2]), sys.argv[3] if len(sys.argv) > 3 else "(unnamed)")
+    else:
+        main()

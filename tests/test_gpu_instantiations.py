@@ -3,10 +3,10 @@
 `tools/kernel_coverage.py` compares the kernel names of a rocprofv3 trace of the GPU suite with the device stubs of
 liblq_hip.so; the first such run (profiles/r03/kernel_coverage_before.txt) found 171 of 340 instantiations that no test
 launched.  Those that no descriptor can reach were removed from the dispatch (csrc/lq_kernels.hip: kStreamOp, the constexpr
-branches of launch_stream2_impl); the others are reached here, each case against the oracle like every other parity test
+branches of launch_stream2); the others are reached here, each case against the oracle like every other parity test
 (q, out, max|q| bit-exact; mean and ds within 1e-5: custom_layers.py:55-60, 62-118).
 
-What decides the instantiation (lq_kernels.hip: make_plan, launch_stream2_impl, launch_traverse):
+What decides the instantiation (lq_kernels.hip: make_plan, launch_stream2, launch_traverse):
   * NT: nontemporal accesses from 64 MiB per tensor (16 777 216 elements) -- most cases below are the round-2 streaming shapes
     of test_gpu_parity.py::STREAM2_SHAPES again, at 17 M elements instead of 4-5 M;
   * row length / column count: team width and float4 per lane of k_row_tiny / k_row_win, flat or periodic or tiled columns;

@@ -58,6 +58,30 @@ def test_workspace_is_small_relative_to_tensor(desc):
         assert ws <= n * 4, f"workspace {ws} B for {n} elements"
 
 
+def test_workspace_bytes_reproduce_the_pinned_contract():
+    """lq_workspace_bytes / lq_conv_workspace_bytes are ABI (callers size buffers by them): every value of
+    tests/golden/workspace_bytes.json -- 3105 descriptors that take every branch of the plan, and the conv kernels of the two
+    ResNet-like sets in four orientations, answered by a library built before the last change to the planning code -- is
+    reproduced by the library under test."""
+    import json
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    try:
+        import make_golden
+    finally:
+        sys.path.pop(0)
+    pin = json.load(open(os.path.join(ROOT, "tests", "golden", "workspace_bytes.json")))
+    assert (tuple(pin["outer"]), tuple(pin["G"]), tuple(pin["inner"])) == (make_golden.WS_OUTER, make_golden.WS_G, make_golden.WS_INNER)
+    assert len(pin["grid"]) == 9 * 15 * 23 and len(set(pin["grid"])) > 500
+    lib = _hip.load()
+    now = make_golden.workspace_bytes(lib._name)
+    descs = [(o, g, i) for o in pin["outer"] for g in pin["G"] for i in pin["inner"]]
+    bad = [(d, a, b) for d, a, b in zip(descs, pin["grid"], now["grid"]) if a != b]
+    assert not bad, f"{len(bad)} descriptors changed their workspace size, first (descriptor, pinned, now): {bad[:5]}"
+    assert len(pin["conv"]) >= 60
+    assert now["conv"] == pin["conv"]
+
+
 def test_descriptor_and_scale_shape_agree_with_oracle():
     for shape in [(784, 128), (128, 10), (3, 3, 64, 128), (7, 7, 3, 64), (10,), (256, 3, 224, 224)]:
         for orient in lq.ORIENTATIONS:

@@ -10,6 +10,12 @@ and prints the instantiations no launch was recorded for.
 
 Exit status 1 when an ``lq::`` instantiation was never launched and is not listed (with a reason) in
 ``tools/kernel_coverage_allow.txt``.
+
+    python3 tools/kernel_coverage.py --compare DIR_A DIR_B
+
+Same dispatch, launch by launch: the multiset of (kernel, grid, workgroup) over the ``lq::`` launches of the
+``*_kernel_trace.csv`` files under each directory (two builds, the same seeded single-process tests).  Prints one summary line
+and every triple whose count differs; exit status 1 when one does.
 """
 import csv
 import os
@@ -79,7 +85,36 @@ def launched(paths):
     return names, files
 
 
+def dispatches(path):
+    """{(kernel, grid, workgroup): launches} of the lq:: kernels in the kernel traces under `path`."""
+    count = {}
+    files = [os.path.join(d, f) for d, _, fs in os.walk(path) for f in fs if f.endswith("kernel_trace.csv")]
+    for f in files:
+        with open(f, newline="") as fh:
+            for r in csv.DictReader(fh):
+                k = norm(r["Kernel_Name"])
+                if not k.startswith("lq::"):
+                    continue
+                key = (k, tuple(int(r["Grid_Size_" + a]) for a in "XYZ"), tuple(int(r["Workgroup_Size_" + a]) for a in "XYZ"))
+                count[key] = count.get(key, 0) + 1
+    return count, len(files)
+
+
+def compare(dir_a, dir_b):
+    a, fa = dispatches(dir_a)
+    b, fb = dispatches(dir_b)
+    diff = sorted(k for k in set(a) | set(b) if a.get(k, 0) != b.get(k, 0))
+    print(f"# dispatch compare: A {sum(a.values())} lq:: launches in {fa} trace files, B {sum(b.values())} in {fb}; "
+          f"distinct (kernel, grid, workgroup) A {len(a)}, B {len(b)}, {len({k[0] for k in a})} kernels in A, "
+          f"{len({k[0] for k in b})} in B; triples whose count differs: {len(diff)}")
+    for k in diff:
+        print(f"DIFFERENT {k[0]} grid {k[1]} workgroup {k[2]}: A x{a.get(k, 0)}, B x{b.get(k, 0)}")
+    return 1 if diff or not a else 0
+
+
 def main():
+    if len(sys.argv) == 4 and sys.argv[1] == "--compare":
+        return compare(sys.argv[2], sys.argv[3])
     if len(sys.argv) < 2:
         print(__doc__)
         return 2

@@ -34,6 +34,7 @@ def use_library(path: str) -> None:
 
 LQ_Q_NONE, LQ_Q_F32, LQ_Q_I32, LQ_Q_I8 = 0, 1, 2, 3
 LQ_ADAM_KERAS, LQ_ADAM_TORCH = 0, 1
+_ADAM_MODES = {"keras": LQ_ADAM_KERAS, "torch": LQ_ADAM_TORCH}
 LQ_PENALTY_ACCUMULATE_DS = 0x100
 
 _c_i64 = ctypes.c_int64
@@ -218,6 +219,19 @@ def require_device_f32(t: torch.Tensor, name: str, dense_ok: bool = False, like:
     if t.is_contiguous() or (dense_ok and memory_order(t.shape, t.stride()) is not None):
         return t
     return t.contiguous()
+
+
+def require_like(t: torch.Tensor, name: str, like: torch.Tensor) -> torch.Tensor:
+    """``require_device_f32(t, name, like=like)`` for the loops that run every eager step for every tensor: four attribute
+    comparisons first (autograd's own gradients pass them), the full checks and a relayout only where one fails."""
+    if t.dtype is not torch.float32 or t.shape != like.shape or t.stride() != like.stride() or t.device != like.device:
+        return require_device_f32(t, name, like=like)
+    return t
+
+
+def adam_mode(mode: str) -> int:
+    """The C ABI's value (include/lq_hip.h) of an optimizer's ``mode``; KeyError for a name that is neither."""
+    return _ADAM_MODES[mode]
 
 
 def ptr(t: Optional[torch.Tensor]) -> Optional[int]:

@@ -31,8 +31,7 @@ from .ops import ROUNDINGS
 
 
 class _Entry:
-    __slots__ = ("layer", "slot", "param", "nested", "out", "ds", "m", "v", "desc", "out_oihw", "dp", "conv", "shape", "pstride", "pdev",
-                 "nq")
+    __slots__ = ("layer", "slot", "param", "nested", "scale", "out", "ds", "m", "v", "desc", "out_oihw", "dp", "conv", "nq")
 
 
 class _DeviceInts:
@@ -104,6 +103,7 @@ class FakeQuantBatch:
             for slot, param, nested in pairs:
                 e = _Entry()
                 e.layer, e.slot, e.param, e.nested = layer, slot, param, nested
+                e.scale = nested.scale             # the Parameter itself: nn.Module attribute lookup is the dearest step of a per-step loop
                 _hip.require_device_f32(param.data, "parameter")
                 _hip.require_device_f32(nested.scale.data, "scale")
                 # a dense permutation of the logical axes (conv kernels stored OIHW, layers.py kernel_storage) is described in
@@ -112,9 +112,6 @@ class FakeQuantBatch:
                 if e.desc is None:
                     raise ValueError("parameters must be dense (contiguous, or a permutation of a contiguous array)")
                 e.out = torch.empty_like(param.data)
-                e.shape = tuple(param.shape)
-                e.pstride = tuple(param.data.stride())
-                e.pdev = param.device
                 e.nq = nested.penalty_threshold is not None or self.ste      # the op itself gives this scale a gradient
                 if self.ste and isinstance(layer, _ConvBase) and layer.kernel_storage == "hwio":
                     raise ValueError('a batched scale_gradient="ste" model takes conv kernels in the memory order the convolution '
@@ -185,7 +182,6 @@ class FakeQuantBatch:
             self._leaf = [None if e.out is None else e.out.detach().requires_grad_(True) for e in self.entries]
             self._leaf_o = [None if e.out_oihw is None else e.out_oihw.detach().requires_grad_(True) for e in self.entries]
             self._all_leaves = [t for t in self._leaf + self._leaf_o if t is not None]
-            self._last_ptrs = [0] * n
             # no companions at all (kernels stored OIHW, dense models): what quantize_all() hands to the layers never changes
             self._static_pre = self._static_outs = None
             if not self._oihw_idx and all(lf is not None for lf in self._leaf):
@@ -204,7 +200,7 @@ class FakeQuantBatch:
 
     def _check_pointers(self):
         for e, (pp, sp) in zip(self.entries, self._data_ptrs):
-            if e.param.data_ptr() != pp or e.nested.scale.data_ptr() != sp:
+            if e.param.data_ptr() != pp or e.nested.scale.data_ptr() != sp:      # the module's scale: a replaced Parameter is caught too
                 raise RuntimeError("a parameter or scale was re-allocated after the batch was built "
                                    "(e.g. model.to(device)); rebuild the FakeQuantBatch")
 
@@ -255,12 +251,8 @@ class FakeQuantBatch:
             # a second call would add dP to the parameters' gradients (bucket views) once more
             raise RuntimeError("finish_backward() without a quantize_all() since the last call: one backward pass per forward")
         self._awaiting_finish = False
-        self._refuse_deferred_clip()
-        if self._static_pre is not None and not self.defer_scale_grads:
-            dps = self._leaf_grads_core()
-        else:
-            dys = [None if lf is None else lf.grad for lf in self._leaf] + [self._leaf_o[i].grad for i in self._oihw_idx]
-            dps = self._backward_core(dys)
+        dps = self._backward_core([None if lf is None else lf.grad for lf in self._leaf]
+                                  + [self._leaf_o[i].grad for i in self._oihw_idx])
         add_to, add_from = [], []
         for e, dp in zip(self.entries, dps):
             p = e.param
@@ -273,39 +265,6 @@ class FakeQuantBatch:
                 add_from.append(dp)
         if add_to:
             torch._foreach_add_(add_to, add_from)          # one fused launch for all of them
-
-    def _leaf_grads_core(self):
-        """The backward of every tensor when the upstream gradients are the leaves' own ``.grad`` (no companions): autograd's
-        AccumulateGrad has already made them float32 tensors of the leaf's shape and strides on the leaf's device (its layout
-        contract; assignment to ``.grad`` checks shape, dtype and device too), so of the per-tensor checks of ``_backward_core`` only
-        the element order is looked at; the pointer table is rewritten only where an address changed (the caching allocator hands a steady-state step the same blocks again)."""
-        ptrs, last, entries = self._ptrs, self._last_ptrs, self.entries
-        dps = []
-        for i, lf in enumerate(self._leaf):
-            d = lf.grad
-            if d is None:                                  # nothing consumed this tensor: dP = 0
-                d = torch.zeros_like(entries[i].param.data)
-            elif d.stride() != entries[i].pstride:         # a hand-assigned gradient in another element order (autograd's own obey the leaf's)
-                d = _hip.require_device_f32(d, "dy", like=entries[i].param.data)
-            a = d.data_ptr()
-            if a != last[i]:
-                ptrs[i] = a
-                last[i] = a
-            dps.append(d)
-        ext = self._external_grads
-        for e in self.entries:
-            if e.nq:
-                g = e.nested.scale
-                if g.grad is not None and not ext:
-                    raise RuntimeError("FakeQuantBatch: scale gradients must be None before backward "
-                                       "(gradient accumulation over several backward passes is not supported in batched mode)")
-        self._scale_grad_call(False)
-        for e in self.entries:
-            if e.nq:
-                e.nested.scale.grad = e.ds                 # written in place by the kernel: no accumulate launch
-        if self.clipped:
-            return [e.dp for e in entries]                 # the masked copies of dy the launch has just written
-        return dps
 
     def _scale_grad_call(self, oihw: bool):
         """lq_batch_scale_grad(_oihw), or -- a fused optimizer attached -- lq_batch_scale_grad_step: same launches, the finalize
@@ -333,89 +292,84 @@ class FakeQuantBatch:
                                "step() first, or build BatchedScaleAdam(fused=False) (fused=True excludes gradient accumulation)")
         step, step_dev = opt._advance()
         h = self.hyper
-        md = {"keras": _hip.LQ_ADAM_KERAS, "torch": _hip.LQ_ADAM_TORCH}[h["mode"]]
         _hip.check(lib.lq_batch_scale_grad_step(self._handle, self._ptrs, 1 if oihw else 0, _hip.ptr(self.ws), self.ws.numel(),
                                                 h["lr"], h["betas"][0], h["betas"][1], h["eps"], int(step or 0), _hip.ptr(step_dev),
-                                                md, sp), "lq_batch_scale_grad_step")
+                                                _hip.adam_mode(h["mode"]), sp), "lq_batch_scale_grad_step")
         opt._applied = True
 
     # ------------------------------------------------------------------ backward of every tensor (both modes)
+    def _point_at(self, grads, name: str = "dy", as_it_stands=(), zeros: bool = True):
+        """The one writer of the pointer table the scale-gradient launches read ``dy`` from.  ``grads[i]`` is the upstream
+        gradient of tensor i: ``None`` (nothing consumed the tensor) stands for zeros like the parameter -- or, ``zeros=False``, for
+        a NULL entry where the op reads no dy (a tensor without a vote; the caller has refused every other); an index in
+        ``as_it_stands`` holds the OIHW gradient of a companion, which the launch gathers itself; every other gradient is brought
+        into the parameter's element order (this loop runs every eager step for every tensor: ``_hip.require_like``).  Returns the
+        tensors the table now points at, one per entry: the caller keeps them alive until the launch is enqueued."""
+        ptrs = self._ptrs
+        keep = []
+        for i, e in enumerate(self.entries):
+            d = grads[i]
+            if d is None and not (zeros or e.nq):
+                keep.append(None)
+                ptrs[i] = None
+                continue
+            if d is None:
+                d = torch.zeros_like(e.param.data)
+            elif i in as_it_stands:
+                d = _hip.require_device_f32(d, name)
+            else:
+                d = _hip.require_like(d, name, e.param)
+            keep.append(d)
+            ptrs[i] = d.data_ptr()
+        return keep
+
+    def _launch_and_publish(self, keep, oihw: bool = False, gathered=(), refuse_accumulation: bool = True):
+        """The scale-gradient launches on the table ``_point_at`` has just written, then ``scale.grad`` of every scale the op gives
+        a gradient.  Returns ``dP`` per tensor: the batch's own buffers where the launch writes one (a clipped batch: the masked
+        copies of dy; ``gathered`` companions: dy in HWIO order), the kept dy itself otherwise (custom_layers.py:118)."""
+        if refuse_accumulation and not self._external_grads:
+            for e in self.entries:
+                if e.nq and e.scale.grad is not None:
+                    # the kernel OVERWRITES its gradient buffer: a second backward without zero_grad(set_to_none=True)
+                    # would silently drop the first gradient -- refuse instead (before anything is launched)
+                    raise RuntimeError("FakeQuantBatch: scale gradients must be None before backward "
+                                       "(gradient accumulation over several backward passes is not supported in batched mode)")
+        self._scale_grad_call(oihw)
+        for e in self.entries:
+            if e.nq:
+                e.scale.grad = e.ds                        # written in place by the kernel: no accumulate launch
+            # STE-only: zeros_like(scale) (CL custom_layers.py:62) -- no scale gradient from the op
+        if self.clipped:
+            return [e.dp for e in self.entries]
+        if gathered:
+            return [e.dp if i in gathered else d for i, (e, d) in enumerate(zip(self.entries, keep))]
+        return keep
+
     def _backward_core(self, dys):
         """``dys``: upstream gradient of every HWIO-shaped output, then of every OIHW companion (``None`` where nothing consumed
         it).  Launches the scale-gradient pass (unless deferred), sets ``scale.grad`` and returns ``dP`` per tensor."""
-        batch = self
-        batch._refuse_deferred_clip()
-        n = len(batch.entries)
-        # a conv kernel with an OIHW companion: its consumer (the convolution) used the companion, so the gradient arrives there,
-        # in OIHW order; a consumer that used the HWIO output instead is served by the plain path below
+        self._refuse_deferred_clip()
         dys = list(dys)
-        oihw_used = False
-        for i in batch._oihw_idx:
-            d_o = dys[batch._oihw_pos[i]]
+        # a conv kernel with an OIHW companion: its consumer (the convolution) used the companion, so the gradient arrives there,
+        # in OIHW order; a consumer that used the HWIO output instead is served like every other tensor
+        gathered = set()
+        for i in self._oihw_idx:
+            d_o = dys[self._oihw_pos[i]]
             if d_o is not None:
                 if dys[i] is not None:
                     raise RuntimeError("FakeQuantBatch: both the HWIO and the OIHW output of one conv kernel received a gradient")
-                oihw_used = True
-        if batch.defer_scale_grads:          # dP == dy (custom_layers.py:118); ds follows after the all-reduce
+                gathered.add(i)
+        if self.defer_scale_grads:           # dP == dy (custom_layers.py:118); ds follows after the all-reduce
             dps = []
-            for i, e in enumerate(batch.entries):
-                d = dys[i]
-                if d is None and i in batch._oihw_pos and dys[batch._oihw_pos[i]] is not None:
-                    d = dys[batch._oihw_pos[i]].permute(2, 3, 1, 0)
+            for i, e in enumerate(self.entries):
+                d = dys[self._oihw_pos[i]].permute(2, 3, 1, 0) if i in gathered else dys[i]
                 dps.append(d if d is not None else torch.zeros_like(e.param.data))
             return dps
-        keep = []
-        gathered = set()
-        if not batch._oihw_idx:
-            # no companions (kernels stored OIHW, dense models): the per-step host work is one pass of cheap checks -- this loop runs
-            # every eager step for every tensor (tools/bench_weights.py us_per_step_batched_leaves)
-            ptrs = batch._ptrs
-            f32 = torch.float32
-            for i, e in enumerate(batch.entries):
-                d = dys[i]
-                if d is None:
-                    d = torch.zeros_like(e.param.data)
-                elif d.dtype is not f32 or d.shape != e.shape or d.stride() != e.pstride or d.device != e.pdev:
-                    d = _hip.require_device_f32(d, "dy", like=e.param.data)      # the full checks, a relayout where needed
-                if e.nq and e.nested.scale.grad is not None and not batch._external_grads:
-                    raise RuntimeError("FakeQuantBatch: scale gradients must be None before backward "
-                                       "(gradient accumulation over several backward passes is not supported in batched mode)")
-                keep.append(d)
-                ptrs[i] = d.data_ptr()
-            batch._scale_grad_call(False)
-            for e in batch.entries:
-                if e.nq:
-                    e.nested.scale.grad = e.ds                     # written in place by the kernel: no accumulate launch
-            if batch.clipped:
-                return [e.dp for e in batch.entries]               # the masked copies of dy the launch has just written
-            return keep
-        for i, e in enumerate(batch.entries):
-            d = dys[i]
-            if d is None and i in batch._oihw_pos and dys[batch._oihw_pos[i]] is not None:
-                d = dys[batch._oihw_pos[i]]
-                gathered.add(i)
-            elif d is None:
-                d = torch.zeros_like(e.param.data)
-            elif oihw_used and i in batch._oihw_pos:
-                raise RuntimeError("FakeQuantBatch: conv kernels must all be consumed through the same layout in one step")
-            d = _hip.require_device_f32(d, "dy", like=None if i in gathered else e.param.data)
-            keep.append(d)
-            batch._ptrs[i] = d.data_ptr()
-        for e in batch.entries:
-            if e.nested.penalty_threshold is not None and e.nested.scale.grad is not None and not batch._external_grads:
-                # the kernel OVERWRITES its gradient buffer: a second backward without zero_grad(set_to_none=True)
-                # would silently drop the first gradient -- refuse instead (before anything is launched)
-                raise RuntimeError("FakeQuantBatch: scale gradients must be None before backward "
-                                   "(gradient accumulation over several backward passes is not supported in batched mode)")
-        batch._scale_grad_call(oihw_used)
-        dps = []
-        for i, (e, d) in enumerate(zip(batch.entries, keep)):
-            dps.append(e.dp if i in gathered else d)               # dP is dy itself (custom_layers.py:118), in HWIO order
-            if e.nested.penalty_threshold is not None:
-                e.nested.scale.grad = e.ds                         # written in place by the kernel: no accumulate launch
-            # STE-only: zeros_like(scale) (CL custom_layers.py:62) -- no scale gradient from the op
-        assert len(dps) == n
-        return dps
+        for i in gathered:
+            dys[i] = dys[self._oihw_pos[i]]
+        if gathered and any(dys[i] is not None for i in self._oihw_idx if i not in gathered):
+            raise RuntimeError("FakeQuantBatch: conv kernels must all be consumed through the same layout in one step")
+        return self._launch_and_publish(self._point_at(dys, as_it_stands=gathered), bool(gathered), gathered)
 
     def _refuse_deferred_clip(self):
         if self.clipped and self.defer_scale_grads:
@@ -433,7 +387,7 @@ class FakeQuantBatch:
             dev, groups = ctypes.c_void_p(), ctypes.c_int64()
             _hip.check(lib.lq_batch_clip_counts(self._handle, i, ctypes.byref(dev), ctypes.byref(groups)), "lq_batch_clip_counts")
             view = torch.as_tensor(_DeviceInts(dev.value, groups.value), device=self.device)
-            out.append(view.clone().reshape(e.nested.scale.shape))
+            out.append(view.clone().reshape(e.scale.shape))
         return out
 
     # ------------------------------------------------------------------ exact data-parallel mode (ddp.py, mode B)
@@ -441,28 +395,17 @@ class FakeQuantBatch:
         """ds of every nested-quantization tensor from its parameter's CURRENT gradient, in two launches.  After the
         data-parallel all-reduce ``P.grad`` is the global-batch dy (dP == dy, custom_layers.py:118), so this yields the
         single-device large-batch scale gradient, identical on every rank."""
-        lib = _hip.load()
         if self.clipped:
             raise ValueError("scale_grads_from_param_grads() reads P.grad as dy; a clipped batch's dP is a masked copy of dy, which "
                              "no longer holds the dy of the clipped elements: average ds over the ranks (data-parallel mode A)")
         if self.ste:
             raise RuntimeError("scale_grads_from_param_grads() is the exact mode of the nested-quantization vote; the straight-through "
                                "scale gradient is linear in dy: average ds over the ranks (data-parallel mode A)")
-        keep = []
-        for i, e in enumerate(self.entries):
-            g = e.param.grad
-            if g is None:
-                if e.nested.penalty_threshold is not None:
-                    raise RuntimeError("scale_grads_from_param_grads: a quantised parameter has no gradient")
-                self._ptrs[i] = None
-                continue
-            g = _hip.require_device_f32(g, "parameter gradient", like=e.param.data)
-            keep.append(g)
-            self._ptrs[i] = g.data_ptr()
-        self._scale_grad_call(False)
-        for e in self.entries:
-            if e.nested.penalty_threshold is not None:
-                e.nested.scale.grad = e.ds
+        grads = [e.param.grad for e in self.entries]
+        if any(g is None and e.nq for g, e in zip(grads, self.entries)):
+            raise RuntimeError("scale_grads_from_param_grads: a quantised parameter has no gradient")
+        # no refusal here: ds is recomputed from whatever P.grad holds now, as often as the caller asks
+        self._launch_and_publish(self._point_at(grads, "parameter gradient", zeros=False), refuse_accumulation=False)
 
     # ------------------------------------------------------------------ custom loss terms
     _KINDS = {"maxbin": 0, "difference": 1, "inverse": 2}
@@ -528,16 +471,15 @@ class FakeQuantBatch:
             _hip.check(lib.lq_batch_penalty_grads(self._handle, kind_flag, coeff, grads, _hip.ptr(self.ws), self.ws.numel(),
                                                   _hip.stream_ptr(self.device)), "lq_batch_penalty_grads")
         for e in self.entries:
-            e.nested.scale.grad = e.ds
+            e.scale.grad = e.ds
         return penalty
 
     # ------------------------------------------------------------------ optimizer
     def scale_adam_step(self, step: Optional[int] = None, step_dev: Optional[torch.Tensor] = None):
         lib = _hip.load()
         h = self.hyper
-        md = {"keras": _hip.LQ_ADAM_KERAS, "torch": _hip.LQ_ADAM_TORCH}[h["mode"]]
         _hip.check(lib.lq_batch_scale_adam(self._handle, h["lr"], h["betas"][0], h["betas"][1], h["eps"],
-                                           int(step or 0), _hip.ptr(step_dev), md, _hip.stream_ptr(self.device)),
+                                           int(step or 0), _hip.ptr(step_dev), _hip.adam_mode(h["mode"]), _hip.stream_ptr(self.device)),
                    "lq_batch_scale_adam")
 
 
@@ -593,7 +535,7 @@ class BatchedScaleAdam:
 
     def zero_grad(self, set_to_none: bool = True):
         for e in self.batch.entries:
-            e.nested.scale.grad = None
+            e.scale.grad = None
 
     def _advance(self):
         """(host step, device step tensor) of the update that is about to be applied."""
@@ -613,7 +555,7 @@ class BatchedScaleAdam:
         # only scales that actually received a gradient this step are updated by Adam in the reference too; with the
         # nested-quantization op every scale does.  STE-only scales are updated from the loss-term gradients.
         for e in self.batch.entries:
-            g = e.nested.scale.grad
+            g = e.scale.grad
             if g is None:
                 e.ds.zero_()
             elif g.data_ptr() != e.ds.data_ptr():

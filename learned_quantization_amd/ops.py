@@ -30,6 +30,15 @@ def _desc(parameter: torch.Tensor, scale: torch.Tensor) -> Tuple[int, int, int]:
     return group_descriptor(tuple(parameter.shape), tuple(scale.shape))
 
 
+def _q_buffer(p: torch.Tensor, q_dtype: Optional[torch.dtype]):
+    """(q, the C ABI's name of its type) for the integer side output of a forward: (None, LQ_Q_NONE) without ``q_dtype``."""
+    if q_dtype is None:
+        return None, _hip.LQ_Q_NONE
+    if q_dtype not in _QDTYPES:
+        raise TypeError(f"q_dtype must be one of {list(_QDTYPES)}, got {q_dtype}")
+    return torch.empty_like(p, dtype=q_dtype), _QDTYPES[q_dtype]
+
+
 def _param(parameter: torch.Tensor, scale: torch.Tensor):
     """(P, s, descriptor) as the kernels read them.  A parameter whose memory is a dense permutation of its logical axes -- a
     conv kernel shaped HWIO (custom_layers.py:321) and stored OIHW, layers.py ``kernel_storage`` -- is NOT copied: the groups
@@ -47,13 +56,7 @@ def fq_forward(parameter: torch.Tensor, scale: torch.Tensor, q_dtype: Optional[t
     lib = _hip.load()
     p, s, (outer, G, inner) = _param(parameter, scale)
     out = torch.empty_like(p) if want_out else None
-    q = None
-    qd = _hip.LQ_Q_NONE
-    if q_dtype is not None:
-        if q_dtype not in _QDTYPES:
-            raise TypeError(f"q_dtype must be one of {list(_QDTYPES)}, got {q_dtype}")
-        q = torch.empty_like(p, dtype=q_dtype)
-        qd = _QDTYPES[q_dtype]
+    q, qd = _q_buffer(p, q_dtype)
     if out is None and q is None:
         raise ValueError("nothing to compute: want_out=False and q_dtype=None")
     _hip.check(lib.lq_fq_forward(_hip.ptr(p), _hip.ptr(s), _hip.ptr(out), _hip.ptr(q), qd,
@@ -153,13 +156,7 @@ def fq_forward_clip(parameter: torch.Tensor, scale: torch.Tensor, qmin: int, qma
     lib = _hip.load()
     p, s, (outer, G, inner) = _param(parameter, scale)
     out = torch.empty_like(p)
-    q = None
-    qd = _hip.LQ_Q_NONE
-    if q_dtype is not None:
-        if q_dtype not in _QDTYPES:
-            raise TypeError(f"q_dtype must be one of {list(_QDTYPES)}, got {q_dtype}")
-        q = torch.empty_like(p, dtype=q_dtype)
-        qd = _QDTYPES[q_dtype]
+    q, qd = _q_buffer(p, q_dtype)
     _hip.check(lib.lq_fq_forward_clip_r(_hip.ptr(p), _hip.ptr(s), _hip.ptr(out), _hip.ptr(q), qd, qmin, qmax, rnd,
                                         outer, G, inner, _hip.stream_ptr(p.device)), "lq_fq_forward_clip_r")
     return out if q is None else (out, q)
@@ -356,16 +353,20 @@ def min_value_project_(w: torch.Tensor, min_value: float) -> torch.Tensor:
     return w
 
 
+def _check_adam_args(scale: torch.Tensor, grad: torch.Tensor, m: torch.Tensor, v: torch.Tensor) -> None:
+    for name, t in (("scale", scale), ("grad", grad), ("m", m), ("v", v)):
+        _hip.require_device_f32(t, name)
+        if not t.is_contiguous() or t.numel() != scale.numel():
+            raise ValueError(f"{name} must be contiguous with {scale.numel()} elements")
+
+
 def scale_adam_step_(scale: torch.Tensor, grad: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: int,
                      lr: float = 1e-4, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-7,
                      min_value: float = 0.0, mode: str = "keras") -> None:
     """K6: Adam + MinValueConstraint projection in one launch (custom_layers.py:158; Keras 2.11 Adam)."""
     lib = _hip.load()
-    for name, t in (("scale", scale), ("grad", grad), ("m", m), ("v", v)):
-        _hip.require_device_f32(t, name)
-        if not t.is_contiguous() or t.numel() != scale.numel():
-            raise ValueError(f"{name} must be contiguous with {scale.numel()} elements")
-    md = {"keras": _hip.LQ_ADAM_KERAS, "torch": _hip.LQ_ADAM_TORCH}[mode]
+    _check_adam_args(scale, grad, m, v)
+    md = _hip.adam_mode(mode)
     _hip.check(lib.lq_scale_adam_step(_hip.ptr(scale), _hip.ptr(grad), _hip.ptr(m), _hip.ptr(v), scale.numel(),
                                       lr, beta1, beta2, eps, int(step), float(min_value), md,
                                       _hip.stream_ptr(scale.device)), "lq_scale_adam_step")
@@ -376,13 +377,10 @@ def scale_adam_step_dev_(scale: torch.Tensor, grad: torch.Tensor, m: torch.Tenso
                          min_value: float = 0.0, mode: str = "keras") -> None:
     """K6, hipGraph-capturable form: ``step_dev`` is a 1-element int64 device tensor holding the 1-based step."""
     lib = _hip.load()
-    for name, t in (("scale", scale), ("grad", grad), ("m", m), ("v", v)):
-        _hip.require_device_f32(t, name)
-        if not t.is_contiguous() or t.numel() != scale.numel():
-            raise ValueError(f"{name} must be contiguous with {scale.numel()} elements")
+    _check_adam_args(scale, grad, m, v)
     if step_dev.dtype != torch.int64 or not step_dev.is_cuda or step_dev.numel() != 1:
         raise TypeError("step_dev must be a 1-element int64 device tensor")
-    md = {"keras": _hip.LQ_ADAM_KERAS, "torch": _hip.LQ_ADAM_TORCH}[mode]
+    md = _hip.adam_mode(mode)
     _hip.check(lib.lq_scale_adam_step_dev(_hip.ptr(scale), _hip.ptr(grad), _hip.ptr(m), _hip.ptr(v), scale.numel(),
                                           lr, beta1, beta2, eps, _hip.ptr(step_dev), float(min_value), md,
                                           _hip.stream_ptr(scale.device)), "lq_scale_adam_step_dev")

@@ -154,7 +154,6 @@ class KerasAdam(torch.optim.Optimizer):
         else:
             self._step += 1
         keep = []
-        f32 = torch.float32
         for group, chunk, handle, gptrs, ptrs in self._sets:
             for i, p in enumerate(chunk):
                 d = p.data
@@ -164,16 +163,13 @@ class KerasAdam(torch.optim.Optimizer):
                 if g is None:
                     gptrs[i] = None
                 else:
-                    # this loop runs every eager step for every parameter: the cheap comparisons first (autograd's own gradients
-                    # pass them), the full checks and a relayout only where one fails
-                    if g.dtype is not f32 or g.shape != d.shape or g.stride() != d.stride() or g.device != d.device:
-                        g = _hip.require_device_f32(g, "gradient", like=d)
+                    g = _hip.require_like(g, "gradient", d)
                     keep.append(g)
                     gptrs[i] = g.data_ptr()
             b1, b2 = group["betas"]
-            md = {"keras": _hip.LQ_ADAM_KERAS, "torch": _hip.LQ_ADAM_TORCH}[group["mode"]]
             _hip.check(lib.lq_adam_set_step(handle, gptrs, group["lr"], b1, b2, group["eps"], self._step,
-                                            _hip.ptr(self._step_t), md, _hip.stream_ptr(chunk[0].device)), "lq_adam_set_step")
+                                            _hip.ptr(self._step_t), _hip.adam_mode(group["mode"]), _hip.stream_ptr(chunk[0].device)),
+                       "lq_adam_set_step")
         return loss
 
 

@@ -379,6 +379,121 @@ def test_leaf_mode_equals_the_autograd_node(dev, config, orient, storage):
     assert any(float(t.abs().max()) > 0 for t in res[False][2])
 
 
+def _half_zero_grads(shapes, dev, g):
+    """Per shape: randn * 1e-3 with a random half of the elements exactly 0.  A zero dy is below every threshold, so the vote of
+    a group -- and with it ds -- depends on which elements are zero: with every |dy| / |out| >= lambda the scale gradient is
+    -|tanh(lambda)| * max|q| whatever dy is, and two different gradients could not be told apart."""
+    return [torch.randn(sh, generator=g).mul_(1e-3).masked_fill_(torch.rand(sh, generator=g) < 0.5, 0.0).to(dev) for sh in shapes]
+
+
+@pytest.mark.parametrize("orient", ["rowwise", "columnwise"])
+def test_leaf_pass_after_another_writer_of_the_pointer_table_reads_its_own_gradients(dev, orient):
+    """finish_backward() -> scale_grads_from_param_grads() -> finish_backward() on one leaf-mode batch, the leaves' gradients of the
+    first and the third pass at the SAME addresses (assigned, so the test fixes them and not the allocator): every pass computes
+    ds from the gradients it was given, bit for bit.  A leaf pass that kept the addresses of its previous pass in front of the pointer
+    table skipped the store here and launched on the table the second pass had written: ds of the third pass was that of B."""
+    import learned_quantization_amd as lq
+    m = _model(dev, "mnist", orient, value=1e-4)
+    batch = lq.FakeQuantBatch(m, autograd=False)
+    entries = batch.entries
+    shapes = [tuple(e.param.shape) for e in entries]
+    g = torch.Generator().manual_seed(41)
+
+    def reference(grads):
+        return [lq.fq_scale_grad(e.param.data, e.nested.scale.data, d, e.nested.penalty_threshold) for e, d in zip(entries, grads)]
+
+    A = _half_zero_grads(shapes, dev, g)
+    B = [torch.full_like(e.param.data, 1e-3) for e in entries]          # alive to the end: a stale read is a read of live memory
+    # 1. a leaf pass on A
+    outs = batch.quantize_all()
+    for o, a in zip(outs, A):
+        o.grad = a
+    batch.finish_backward()
+    ds_a = [e.nested.scale.grad.clone() for e in entries]
+    for i, (ds, ref) in enumerate(zip(ds_a, reference(A))):
+        assert torch.equal(ds, ref), f"tensor {i}: first leaf pass"
+    # 2. ds from P.grad = B: the other writer of the table
+    for e, b in zip(entries, B):
+        e.nested.scale.grad = None
+        e.param.grad = b
+    batch.scale_grads_from_param_grads()
+    for i, (e, ref, ds1) in enumerate(zip(entries, reference(B), ds_a)):
+        assert torch.equal(e.nested.scale.grad, ref), f"tensor {i}: ds from P.grad"
+        assert not torch.equal(ref, ds1), f"tensor {i}: A and B give the same ds, the inputs do not discriminate"
+    # 3. a leaf pass again, new values in the storages of A
+    for e in entries:
+        e.nested.scale.grad = None
+        e.param.grad = None
+    outs = batch.quantize_all()
+    for a, fresh in zip(A, _half_zero_grads(shapes, dev, g)):
+        a.copy_(fresh)
+    for o, a in zip(outs, A):
+        o.grad = a
+    batch.finish_backward()
+    for i, (e, a, ref) in enumerate(zip(entries, A, reference(A))):
+        assert e.param.grad is a, f"tensor {i}: dP is dy itself"
+        assert e.nested.scale.grad is e.ds
+        assert torch.equal(e.nested.scale.grad, ref), f"tensor {i}: leaf pass after scale_grads_from_param_grads()"
+
+
+@pytest.mark.parametrize("config,orient,storage", [("mnist", "columnwise", None), ("cifar", "rowwise", "hwio")])
+def test_three_backward_routes_give_one_result_and_toggle_on_one_object(dev, config, orient, storage):
+    """The autograd node, the leaves, and the leaves with deferred scale gradients followed by scale_grads_from_param_grads()
+    give the same dP and ds bit for bit -- ds that of the single-tensor op on the HWIO-ordered gradient -- with and without
+    OIHW companions; and the deferring batch, switched back to ``defer_scale_grads = False``, does a second step like any other."""
+    import learned_quantization_amd as lq
+
+    def step(m, batch, g):
+        """One backward of seeded gradients on what the layers consume; returns (dP, ds, the gradients in HWIO order)."""
+        batch.quantize_all()
+        consumed, dys, hwio = [], [], []
+        for l in lq.custom_layers_of(m):
+            w, qb = l.quantized_parameters()
+            for k, o in enumerate((w, qb)):
+                if o is not None:
+                    d = torch.randn(tuple(o.shape), generator=g).mul_(1e-3).to(dev)
+                    consumed.append(o)
+                    dys.append(d)
+                    hwio.append(d.permute(2, 3, 1, 0).contiguous() if k == 0 and d.dim() == 4 else d)
+        torch.autograd.backward(consumed, dys)
+        if not batch.autograd:
+            batch.finish_backward()
+        if batch.defer_scale_grads:
+            assert all(e.nested.scale.grad is None for e in batch.entries), "deferred: no ds before the recomputation"
+            batch.scale_grads_from_param_grads()
+        assert all(e.nested.scale.grad is e.ds for e in batch.entries)
+        return [e.param.grad.detach().clone() for e in batch.entries], [e.ds.clone() for e in batch.entries], hwio
+
+    def check(m, batch, dP, ds, hwio, what):
+        for i, e in enumerate(batch.entries):
+            assert torch.equal(dP[i], hwio[i]), f"{what} tensor {i}: dP must be dy in HWIO order"
+            ref = lq.fq_scale_grad(e.param.data, e.nested.scale.data, hwio[i], e.nested.penalty_threshold)
+            assert torch.equal(ds[i], ref), f"{what} tensor {i}: ds against the single-tensor op"
+
+    res = {}
+    for route in ("node", "leaves", "deferred"):
+        m = _model(dev, config, orient, value=1e-4, kernel_storage=storage)
+        batch = lq.FakeQuantBatch(m, hwio_out=False, autograd=route == "node")
+        assert bool(batch._oihw_idx) == (storage == "hwio")
+        batch.defer_scale_grads = route == "deferred"
+        dP, ds, hwio = step(m, batch, torch.Generator().manual_seed(77))
+        check(m, batch, dP, ds, hwio, route)
+        res[route] = (dP, ds)
+    for route in ("leaves", "deferred"):
+        for what, a, b in zip(("dP", "ds"), res["node"], res[route]):
+            for i, (ta, tb) in enumerate(zip(a, b)):
+                assert torch.equal(ta, tb), f"{route} tensor {i}: {what}"
+    assert any(float(t.abs().max()) > 0 for t in res["node"][1])
+    # the object of the deferred route, toggled: a second step with fresh gradients, ds now from the leaf pass itself
+    batch.defer_scale_grads = False
+    for e in batch.entries:
+        e.nested.scale.grad = None
+        e.param.grad = None
+    dP, ds, hwio = step(m, batch, torch.Generator().manual_seed(78))
+    check(m, batch, dP, ds, hwio, "toggled")
+    assert not all(torch.equal(a, b) for a, b in zip(ds, res["deferred"][1])), "fresh gradients, another ds"
+
+
 def test_leaf_mode_finish_backward_belongs_to_leaf_mode(dev):
     import learned_quantization_amd as lq
     b = lq.FakeQuantBatch(_model(dev, "mnist", "rowwise"))

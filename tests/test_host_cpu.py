@@ -47,6 +47,18 @@ def test_argument_validation_without_gpu():
     assert lib.lq_workspace_bytes(0, 1, 1) == 0
 
 
+def test_adam_mode_names_map_to_the_abi_values():
+    """_hip.adam_mode: the one place an optimizer's ``mode`` becomes the header's lq_adam_mode; an unknown name is a KeyError."""
+    header = open(os.path.join(ROOT, "include", "lq_hip.h")).read()
+    abi = {name: int(value) for name, value in re.findall(r"\bLQ_ADAM_(KERAS|TORCH)\s*=\s*(\d+)", header)}
+    assert abi == {"KERAS": 0, "TORCH": 1}
+    assert _hip.adam_mode("keras") == abi["KERAS"] == _hip.LQ_ADAM_KERAS
+    assert _hip.adam_mode("torch") == abi["TORCH"] == _hip.LQ_ADAM_TORCH
+    for unknown in ("Keras", "adamw", "", None):
+        with pytest.raises(KeyError):
+            _hip.adam_mode(unknown)
+
+
 @pytest.mark.parametrize("desc", [(256, 3, 50176), (1, 1, 38535168), (1, 784, 128), (784, 128, 1), (9, 64, 128),
                                   (1, 3, 3 * 512 * 512), (1, 1, 10), (1000, 7, 2), (1, 1000000, 10)])
 def test_workspace_is_small_relative_to_tensor(desc):

@@ -16,13 +16,22 @@ constexpr int64_t kPeriodic4Min = 4ll << 20;         // column mode, C <= 64: el
                                                      // (the same 4 M boundary as the 512-thread streaming units: below it single-tensor
                                                      // and batched launches share one geometry and give bit-identical results)
 constexpr int64_t kNtBytes = 64ll << 20;             // tensors at least this large are streamed with nontemporal accesses
-// Infinity Cache reuse between the forward and the scale gradient of one streaming tensor ("Infinity Cache
-// reuse"): K1 loads the LAST kMallKeepBytes of P with the default policy and K2 walks its units backwards, so that it meets those
-// lines first.  A line `d` bytes before the end of P sees about 4 d bytes of other traffic between its two uses (P + out behind it
-// in K1, P + dy ahead of it in K2) and survives while that fits the 256 MiB cache: d <= 64 MiB at best.  Swept on the BENCH
-// tensor (154 MB) in tenths of the tensor: the step is shortest at 0.3 = 46 MB and longer again at 0.4 and 0.5, where K1 pays
-// the default policy for lines that do not last.  Smaller streaming tensors keep all of P that fits.
-constexpr int64_t kMallKeepBytes = 44ll << 20;
+// Cache policy of the two streaming kernels of one tensor, the forward K1 (k_flat_fwd) and the scale gradient K2 (k_row_stream,
+// kMallWalk) -- DESIGN.md section 3, "Infinity Cache reuse" and "Cache-policy mix".  Both stream fastest with PART of their P
+// loads under the default policy and the rest `nt`, and with that part interleaved through the tensor, not in one piece: on
+// math-free kernels of the same shapes 3/8 of K1's blocks in runs of 16 take 2.6 us off its 45.7, a quarter of K2's units 0.5 us
+// off its 44.5 (profiles/policy_mix/membench_mix.txt).  A mix word holds an 8-bit mask for P (bits 0-7), one for dy (bits 8-15,
+// K2 only) and the log2 of a run length (bits 16-20): unit u is picked when bit (u >> log2run) & 7 of its stream's mask is set.
+// The constants are the pair with the shortest K1, K2, K3 step in tools/sweep_policy.py (profiles/policy_mix/sweep.jsonl).
+constexpr uint32_t mix_word(uint32_t mask_p, uint32_t mask_dy, uint32_t log2run) { return mask_p | (mask_dy << 8) | (log2run << 16); }
+constexpr uint32_t kMixK1 = mix_word(0x15, 0x00, 4);      // K1 blocks of 512 float4: 3 of every 8 runs of 16 blocks
+constexpr uint32_t kMixK2 = mix_word(0x11, 0x00, 0);      // K2 units of 4096 elements: every 4th unit's P; dy stays nt
+// Before the mix, K1 loaded the LAST kMallKeepBytes of P with the default policy (44 MiB) and K2, which walks its units backwards
+// and so meets those lines first, did the same: a line `d` bytes before the end of P sees about 4 d bytes of other traffic between
+// its two uses and can survive in the 256 MiB Infinity Cache for d <= 64 MiB.  With the mix in place the same sweep finds no point
+// with such a tail ahead of the ones without: the hits were never measurably faster than HBM (membench_survive.txt), the tail
+// acted as one more, coarser, mix.  The tail stays as a development knob (LQ_TUNE_MALL_T, lq_dev_set_flags 0xf00); shipped: none.
+constexpr int64_t kMallKeepBytes = 0;
 
 // ------------------------------------------------------------------------------------------
 //  Parameters shared by every kernel (passed by value in the kernarg segment).
@@ -75,7 +84,10 @@ __device__ __forceinline__ uint32_t perm_index(const Params& p, int64_t i) {    
 struct FlatIdx {          // group of flat element i: (i / inner) % G
     FastDiv inner, G;
     uint32_t keep_from;   // k_flat_fwd, streaming forward of long aligned rows: first block that loads P with the default cache policy
+    uint32_t keep_mix;    // ... and the mix word of the blocks before it (kMixK1; 0: none).  It sits where the kernel arguments had
+                          // padding: no argument of any k_flat_fwd moves
 };
+static_assert(sizeof(FlatIdx) == 40, "FlatIdx: keep_mix must stay inside the former padding before nv");
 
 // Per-group context, loaded once per row / column.
 struct Ctx {

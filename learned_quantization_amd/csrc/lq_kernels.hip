@@ -118,15 +118,34 @@ static int knob_env(const char* name, int dflt) {
 #ifdef LQ_DEV_KNOBS
 static int g_dev_flags_host = 0;       // the host's copy of lq_dev_set_flags(bits)
 #endif
-// First element of the part of a streaming tensor that K1 loads with the default cache policy and K2 expects in the Infinity
-// Cache (kMallKeepBytes; DESIGN.md section 3 "Infinity Cache reuse").  Development builds: LQ_TUNE_MALL_T or bits 0xf00 of
-// lq_dev_set_flags hold 1 + the fraction of the tensor in tenths (1 = nothing kept), 0 = the shipped rule.
-static int64_t mall_keep_from(int64_t numel) {
+// First element of the tail of a streaming tensor that K1 and K2 load with the default cache policy whatever the mix word says
+// (kMallKeepBytes: none in the shipped build; DESIGN.md section 3 "Infinity Cache reuse", "Cache-policy mix").  Development
+// builds: LQ_TUNE_MALL_T or bits 0xf00 of lq_dev_set_flags hold 1 + the fraction of the tensor in tenths (1 = nothing kept), 0 =
+// the shipped rule.
+#ifdef LQ_DEV_KNOBS
+// lq_dev_set_policy_mix(k1, k2): the mix words of K1 and K2 (mix_word, lq_common.hpp; 0xffffffff = the shipped constant).  Bits
+// 24-27 of k1, when set, hold a tail fraction for K1 ALONE, coded like bits 0xf00 of lq_dev_set_flags (K2 keeps its own).
+static uint32_t g_dev_mix_k1 = 0xffffffffu, g_dev_mix_k2 = 0xffffffffu;
+#endif
+static uint32_t mix_k1() {
+#ifdef LQ_DEV_KNOBS
+    if (g_dev_mix_k1 != 0xffffffffu) return g_dev_mix_k1 & 0x1fffffu;
+#endif
+    return kMixK1;
+}
+static uint32_t mix_k2() {
+#ifdef LQ_DEV_KNOBS
+    if (g_dev_mix_k2 != 0xffffffffu) return g_dev_mix_k2 & 0x1fffffu;
+#endif
+    return kMixK2;
+}
+static int64_t mall_keep_from(int64_t numel, bool k1 = false) {
     int64_t keep = kMallKeepBytes / 4;
     LQ_KNOB(t_env, "LQ_TUNE_MALL_T", 0);
     int t = t_env;
 #ifdef LQ_DEV_KNOBS
     if (g_dev_flags_host & 0xf00) t = (g_dev_flags_host >> 8) & 15;
+    if (k1 && g_dev_mix_k1 != 0xffffffffu && (g_dev_mix_k1 >> 24 & 15)) t = g_dev_mix_k1 >> 24 & 15;
 #endif
     if (t > 0) keep = (int64_t)((double)numel * (t - 1) / 10.0);
     return keep >= numel ? 0 : numel - keep;
@@ -413,6 +432,7 @@ static int launch_stream2(Plan& pl, const Params& p, hipStream_t st) {
     fx.inner = make_fastdiv((uint32_t)(p.inner < 4294967296ll ? p.inner : 1));
     fx.G = make_fastdiv((uint32_t)(p.G < 4294967296ll ? p.G : 1));
     fx.keep_from = 0xffffffffu;      // no block keeps its lines (set below for the streaming forward of long aligned rows)
+    fx.keep_mix = 0;
     (void)fx;
     if (pl.mode == MODE_ROW_BIG) {
         // long rows off the 16-byte grid: K1 as a line-aligned flat stream (lq_stream2.hpp k_flat_fwd, group mode 6 / 7)
@@ -429,7 +449,10 @@ static int launch_stream2(Plan& pl, const Params& p, hipStream_t st) {
                 const bool ntb = numel * 4.0 >= (double)kNtBytes;
                 int r;
                 if (pl.L % 4 == 0) {
-                    if (ntb) fx.keep_from = (uint32_t)ceil_div(mall_keep_from(nn), 2048);      // 512 float4 per block
+                    if (ntb) {
+                        fx.keep_from = (uint32_t)ceil_div(mall_keep_from(nn, true), 2048);      // 512 float4 per block
+                        fx.keep_mix = mix_k1();
+                    }
                     r = launch_flat_fwd(p, fx, nn, 0, 2, true, ntb, true, st);
                 } else if (!(off_rb & 512) && (double)pl.L / (double)(pl.nc * pl.CH) >= 0.8) {
                     // long rows with L % 4 != 0 keep the row stream (TAIL instantiation): K1 5.8-6.0 TB/s on rows of 1025,
@@ -841,15 +864,16 @@ static int launch_traverse(Plan& pl, const Params& p, hipStream_t st) {
         if constexpr (OP == OP_BWD || OP == OP_FUSED) if (u2) {
             const int64_t nc2 = row_chunks(pl.L, (int64_t)pl.bs * 8);
             const dim3 grid2 = grid3d ? dim3((unsigned)nc2, (unsigned)p.G, (unsigned)outer_f) : dim3((unsigned)(pl.R * nc2));
-            // the scale gradient walks these units backwards and expects the end of P in the Infinity Cache (kMallWalk)
+            // the scale gradient walks these units backwards, with the cache-policy mix of kMixK2 (kMallWalk)
             int64_t keep_from = OP == OP_BWD ? mall_keep_from(pl.R * pl.L) : 0;
+            const uint32_t mix = OP == OP_BWD ? mix_k2() : 0u;
 #ifdef LQ_DEV_KNOBS
             if (g_dev_flags_host & 0x1000) keep_from = -1 - keep_from;      // the forward walk
 #endif
             if (needs_tail((int64_t)pl.bs * 8))
-                hipExtLaunchKernelGGL((k_row_stream<OP, 4, 512, 1, 2, 1>), grid2, dim3(512), 0, st, g_prof_start, g_prof_stop, 0, p, pl.L, nc2, grid3d, keep_from);
+                hipExtLaunchKernelGGL((k_row_stream<OP, 4, 512, 1, 2, 1>), grid2, dim3(512), 0, st, g_prof_start, g_prof_stop, 0, p, pl.L, nc2, grid3d, mix, keep_from);
             else
-                hipExtLaunchKernelGGL((k_row_stream<OP, 4, 512, 1, 2, 0>), grid2, dim3(512), 0, st, g_prof_start, g_prof_stop, 0, p, pl.L, nc2, grid3d, keep_from);
+                hipExtLaunchKernelGGL((k_row_stream<OP, 4, 512, 1, 2, 0>), grid2, dim3(512), 0, st, g_prof_start, g_prof_stop, 0, p, pl.L, nc2, grid3d, mix, keep_from);
             // the finalize that follows must walk the partial layout this launch produced
             pl.CH = pl.bs * 8;
             pl.nc = nc2;
@@ -864,8 +888,8 @@ static int launch_traverse(Plan& pl, const Params& p, hipStream_t st) {
 #define LQ_LAUNCH_STREAM(VEC_, BS_, NT_) do { \
         constexpr bool kTail0 = kDevKnobs || (VEC_ == 4 && !(OP == OP_FWD && (BS_ != kBlock || NT_ != 0)) && !(OP == OP_BWD && BS_ == 512 && NT_ == 1)); \
         constexpr bool kTail1 = kDevKnobs || !(OP == OP_BWD && VEC_ == 4 && BS_ == 512 && NT_ == 1); \
-        if (VEC_ == 1 || tail1) { if constexpr (kTail1) hipExtLaunchKernelGGL((k_row_stream<OP, VEC_, BS_, NT_, 1, 1>), grid, dim3(BS_), 0, st, g_prof_start, g_prof_stop, 0, p, pl.L, pl.nc, grid3d, (int64_t)0); } \
-        else { if constexpr (kTail0) hipExtLaunchKernelGGL((k_row_stream<OP, VEC_, BS_, NT_, 1, 0>), grid, dim3(BS_), 0, st, g_prof_start, g_prof_stop, 0, p, pl.L, pl.nc, grid3d, (int64_t)0); } } while (0)
+        if (VEC_ == 1 || tail1) { if constexpr (kTail1) hipExtLaunchKernelGGL((k_row_stream<OP, VEC_, BS_, NT_, 1, 1>), grid, dim3(BS_), 0, st, g_prof_start, g_prof_stop, 0, p, pl.L, pl.nc, grid3d, 0u, (int64_t)0); } \
+        else { if constexpr (kTail0) hipExtLaunchKernelGGL((k_row_stream<OP, VEC_, BS_, NT_, 1, 0>), grid, dim3(BS_), 0, st, g_prof_start, g_prof_stop, 0, p, pl.L, pl.nc, grid3d, 0u, (int64_t)0); } } while (0)
         if constexpr (!kStreamOp<OP>) {
             if (vec) LQ_LAUNCH_STREAM(4, 256, 0);
             else LQ_LAUNCH_STREAM(1, 256, 0);
@@ -1032,6 +1056,14 @@ int lq_dev_set_ablate(int mask) {      // development builds only (see lq_conv_t
 int lq_dev_set_flags(int bits) {       // development builds only (see lq_stream2.hpp)
     g_dev_flags_host = bits;
     return hipMemcpyToSymbol(HIP_SYMBOL(lq::g_dev_flags), &bits, sizeof(int)) == hipSuccess ? LQ_OK : LQ_EHIP;
+}
+#endif
+
+#ifdef LQ_DEV_KNOBS
+int lq_dev_set_policy_mix(unsigned k1, unsigned k2) {      // development builds only (see mix_k1 / mix_k2 above)
+    g_dev_mix_k1 = k1;
+    g_dev_mix_k2 = k2;
+    return LQ_OK;
 }
 #endif
 

@@ -69,14 +69,14 @@ template <int OP, int BS, int NT, int GM>
 __global__ __launch_bounds__(BS) void k_flat_fwd(Params p, FlatIdx fx, int64_t nv, int rem) {
     using O = OpT<OP>;
     const int64_t v = (int64_t)blockIdx.x * BS + threadIdx.x;
-    // The streaming forward of long aligned rows keeps the END of P in the Infinity Cache for the scale gradient that follows
-    // (kMallKeepBytes): blocks from fx.keep_from on load P with the default policy, every other one stays nontemporal.  The
-    // choice is block-uniform.
+    // The streaming forward of long aligned rows loads P with a mix of cache policies (lq_common.hpp, "Cache-policy mix"): the
+    // blocks that the mix word fx.keep_mix picks, and those from fx.keep_from on (a development knob; shipped: none), load with
+    // the default policy, every other one stays nontemporal.  The choice is block-uniform.
     constexpr bool kKeep = NT == 1 && (GM == 0 || GM == 2);
     if (v < nv) {
         const int64_t i = v * 4;
         float4 x;
-        if (kKeep && blockIdx.x >= fx.keep_from) x = load4_keep(p.P + i);
+        if (kKeep && (blockIdx.x >= fx.keep_from || mix_picks(fx.keep_mix, blockIdx.x, 0))) x = load4_keep(p.P + i);
         else x = load4<NT>(p.P + i);
         __builtin_amdgcn_sched_barrier(0);      // the load first; index arithmetic and contexts while it is in flight
         Acc none = O::template init<Acc>();

@@ -58,7 +58,7 @@ __device__ __forceinline__ void store4_policy(int pol, float* p, const float4& v
 // float4 access at an address that is only 4-byte aligned (one global_load_dwordx4 / global_store_dwordx4: global memory
 // needs dword alignment only; a wave's 1 KB access then touches 9 lines instead of 8)
 typedef float v4f_u __attribute__((ext_vector_type(4), aligned(4)));
-// Default-policy float4 load of a line that is to stay in (or is expected in) the Infinity Cache.  It stands in one arm of a
+// Default-policy float4 load of the blocks that the cache-policy mix picks.  It stands in one arm of a
 // block-uniform branch whose other arm is the nontemporal load of the same address.  Two loads that differ in nothing but the
 // hint are merged into one -- hoisted above the branch or sunk below it -- that keeps only what both have in common (seen:
 // every P load of K2 lost its `nt`).  The two empty asm statements make this arm begin and end with something the other arm
@@ -68,6 +68,10 @@ __device__ __forceinline__ float4 load4_keep(const float* p) {
     const v4f_u v = *reinterpret_cast<const v4f_u*>(p);
     asm volatile("; end" : : : );
     return make_float4(v.x, v.y, v.z, v.w);
+}
+// Block-uniform pick of the cache-policy mix (mix_word, lq_common.hpp): stream 0 = P, 1 = dy
+__device__ __forceinline__ bool mix_picks(uint32_t mix, uint32_t unit, int stream) {
+    return (mix >> ((((unit >> ((mix >> 16) & 31u)) & 7u)) + 8u * stream)) & 1u;
 }
 
 template <int NT, int UA>
@@ -90,19 +94,26 @@ __device__ __forceinline__ void store4x(float* p, const float4& v) {
 // TAIL = 1: rows whose last chunk carries a folded tail, or whose chunks do not start on a 16-byte line (scalar head / tail
 // elements).  Rows without either (the BENCH shape, rows of 2^k elements, ...) run the TAIL = 0 instantiation, which keeps the
 // registers of the round-1 kernel (the hoisted tail loads cost 7-14 VGPRs).
-// The streaming scale gradient (OP_BWD, two nontemporal float4 per thread) walks its units from the END of the tensor and loads
-// the P of units at or behind element `keep_from` with the default policy: the forward left those lines in the Infinity Cache
-// (kMallKeepBytes).  dy and every other P load stay nontemporal.  The partial of a unit keeps its place (row * nc + ck).
+// The streaming scale gradient (OP_BWD, two float4 per thread) walks its units from the END of the tensor and loads with a mix
+// of cache policies (lq_common.hpp, "Cache-policy mix"): the P, and the dy, of the units that the mix word picks for that stream
+// -- by the unit's place in memory, row * nc + ck -- and the P of units at or behind element `keep_from` (a development knob;
+// shipped: none) load with the default policy, every other load stays nontemporal.  The partial of a unit keeps its place
+// (row * nc + ck).
 template <int OP, int VEC, int NT, int U>
 constexpr bool kMallWalk = OP == OP_BWD && VEC == 4 && NT == 1 && U == 2;
 
 template <int OP, int VEC, int BS, int NT, int U = 1, int TAIL = 1>
 __device__ __forceinline__ void row_stream_body(const Params& p, int64_t L, int64_t nc, int64_t row, int64_t ck, int64_t g,
-                                                int64_t keep_from = 0) {
+                                                int64_t keep_from = 0, uint32_t mix = 0) {
     using O = OpT<OP>;
     constexpr int CH = BS * 4 * U;
     const int64_t base = row * L + ck * (int64_t)CH;
-    [[maybe_unused]] const bool keep = kMallWalk<OP, VEC, NT, U> && base >= keep_from;      // block-uniform
+    [[maybe_unused]] bool keep = false, keep_dy = false;      // block-uniform
+    if constexpr (kMallWalk<OP, VEC, NT, U>) {
+        const uint32_t unit = (uint32_t)(row * nc + ck);
+        keep = base >= keep_from || mix_picks(mix, unit, 0);
+        keep_dy = mix_picks(mix, unit, 1);
+    }
     const int64_t rem = L - ck * (int64_t)CH;
     // The last chunk of a row takes everything that remains: at most CH, or up to CH + CH/8 when the host folded a short
     // tail into it (row_chunks(): a row of 4100 elements is 2 chunks of 2048 + 2052, not 3 with an almost empty block).
@@ -136,7 +147,8 @@ __device__ __forceinline__ void row_stream_body(const Params& p, int64_t L, int6
             if (kMallWalk<OP, VEC, NT, U> && keep) x[u] = load4_keep(p.P + il);
             else x[u] = load4<NT>(p.P + il);
             d[u] = x[u];
-            if (O::kDy) d[u] = load4<NT>(p.dy + il);
+            if (kMallWalk<OP, VEC, NT, U> && O::kDy && keep_dy) d[u] = load4_keep(p.dy + il);
+            else if (O::kDy) d[u] = load4<NT>(p.dy + il);
         }
         // The folded tail (one more float4 for a few threads of a row's last chunk) and the scalar head / tail elements of rows
         // that do not start on a 16-byte line are loaded HERE, together with the main loads: as a second and third dependent
@@ -238,7 +250,8 @@ __device__ __forceinline__ void row_stream_body(const Params& p, int64_t L, int6
 }
 
 template <int OP, int VEC, int BS, int NT, int U = 1, int TAIL = 1>
-__global__ __launch_bounds__(BS, (BS == 1024 ? 8 : 0)) void k_row_stream(Params p, int64_t L, int64_t nc, int grid3d, int64_t keep_from) {
+__global__ __launch_bounds__(BS, (BS == 1024 ? 8 : 0)) void k_row_stream(Params p, int64_t L, int64_t nc, int grid3d, uint32_t mix, int64_t keep_from) {
+    // (`mix` sits where the arguments had padding: no argument of any instantiation moves)
     // kMallWalk: from the end -- the block dispatched first (index 0 in every dimension) takes the last chunk of the last row
     constexpr bool kRev = kMallWalk<OP, VEC, NT, U>;
 #ifdef LQ_DEV_KNOBS
@@ -258,7 +271,7 @@ __global__ __launch_bounds__(BS, (BS == 1024 ? 8 : 0)) void k_row_stream(Params 
         ck = unit - row * nc;
         g = row % p.G;
     }
-    row_stream_body<OP, VEC, BS, NT, U, TAIL>(p, L, nc, row, ck, g, keep_from);
+    row_stream_body<OP, VEC, BS, NT, U, TAIL>(p, L, nc, row, ck, g, keep_from, mix);
 }
 
 // ------------------------------------------------------------------------------------------

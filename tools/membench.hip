@@ -196,10 +196,50 @@ __global__ __launch_bounds__(512) void k_table2(const float* A, const float* B, 
     if (a.x + a.y + a.z + a.w + b.x + b.y + b.z + b.w == 123.456f) sink[0] = a.x;
 }
 
+// Cache-policy MIX rows (`membench mix`; DESIGN.md section 3 "Cache-policy mix"): the two BENCH access shapes with a
+// block-uniform predicate per stream that picks the stream's policy -- loads: default (picked) or nt; stores: nt (picked) or
+// sc1 nt.  A predicate picks the blocks from `from` on (a contiguous tail) or those whose bit is set in an 8-bit mask indexed
+// by (block >> shift) & 7 (interleaved: shift 0 = single blocks, which also pins the picked blocks to fixed XCDs of the
+// round-robin dispatch; shift 3 = runs of 8 consecutive blocks, spread over every XCD).
+struct Pick { int from; unsigned mask; int shift; };
+__device__ __forceinline__ bool picked(const Pick q, int b) { return b >= q.from || ((q.mask >> ((b >> q.shift) & 7)) & 1u); }
+#define LQ_MIX_LD(DST, PTR, KEEP)                                                                                      \
+    if (KEEP) asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(DST) : "v"(PTR) : "memory");                      \
+    else asm volatile("global_load_dwordx4 %0, %1, off nt" : "=&v"(DST) : "v"(PTR) : "memory");
+// read + write: 512 threads, one float4 per thread (K1's shape)
+__global__ __launch_bounds__(512) void k_mix_rw(const float* A, float* C, float* sink, Pick ld, Pick stp) {
+    const int b = blockIdx.x;
+    const int64_t j = (int64_t)b * 512 + threadIdx.x;
+    const float4* pa = (const float4*)A + j;
+    float4* pc = (float4*)C + j;
+    const bool keep = picked(ld, b), snt = picked(stp, b);
+    v4f a;
+    LQ_MIX_LD(a, pa, keep)
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(a));
+    a.x += 1.0f;
+    if (snt) asm volatile("global_store_dwordx4 %0, %1, off nt" : : "v"(pc), "v"(a) : "memory");
+    else asm volatile("global_store_dwordx4 %0, %1, off sc1 nt" : : "v"(pc), "v"(a) : "memory");
+}
+// two reads: 512 threads, two float4 per thread and stream (K2's unit of 4096 elements)
+__global__ __launch_bounds__(512) void k_mix_r2(const float* A, const float* B, float* sink, Pick pa_, Pick pb_) {
+    const int b = blockIdx.x;
+    const int64_t j = (int64_t)b * 1024 + threadIdx.x;
+    const float4 *pa0 = (const float4*)A + j, *pa1 = pa0 + 512, *pb0 = (const float4*)B + j, *pb1 = pb0 + 512;
+    const bool ka = picked(pa_, b), kb = picked(pb_, b);
+    v4f a0, a1, b0, b1;
+    LQ_MIX_LD(a0, pa0, ka)
+    LQ_MIX_LD(b0, pb0, kb)
+    LQ_MIX_LD(a1, pa1, ka)
+    LQ_MIX_LD(b1, pb1, kb)
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(a0), "+v"(a1), "+v"(b0), "+v"(b1));
+    const v4f t = a0 + a1 + b0 + b1;
+    if (t.x + t.y + t.z + t.w == 123.456f) sink[0] = t.x;
+}
+
 int main(int argc, char** argv) {
     const int64_t N = 256ll * 3 * 224 * 224;
     const int SETS = 4;
-    const size_t pad = argc > 1 && strcmp(argv[1], "survive") ? (size_t)atol(argv[1]) : 0;   // extra bytes between buffers (de-alias test)
+    const size_t pad = argc > 1 && strcmp(argv[1], "survive") && strcmp(argv[1], "mix") ? (size_t)atol(argv[1]) : 0;   // extra bytes between buffers (de-alias test)
     std::vector<float*> A(SETS), B(SETS), C(SETS);
     char* pool;
     size_t each = N * 4 + pad;
@@ -221,6 +261,65 @@ int main(int argc, char** argv) {
         CK(hipGetLastError()); report(name, bytes, ms);
     };
     const double b2 = N * 8.0, b3 = N * 12.0;
+    // "mix" rows (`membench mix` prints only these): every point in turn, three rounds, so that drift hits all points alike
+    if (argc > 1 && !strcmp(argv[1], "mix")) {
+        struct Pt { char name[80]; int r2; Pick p, q; };
+        std::vector<Pt> pts;
+        const int nb1 = (int)(N / 4 / 512), nb2 = (int)(N / 4 / 1024), never = 0x7fffffff;
+        const int keep1 = (int)((44ll << 20) / 8192), keep2 = keep1 / 2;      // the shipped 44 MiB tail, in blocks of each shape
+        const Pick none = {never, 0u, 0}, all = {0, 0u, 0};
+        const char* fn[4] = {"1/8", "1/4", "3/8", "1/2"};
+        const unsigned fm[4] = {0x01u, 0x11u, 0x15u, 0x55u};                 // every 8th, 4th, (3 of 8), 2nd
+        const char* pn[3] = {"tail", "every-kth-block", "every-kth-run-of-8"};
+        auto pick = [&](int pat, int f, int nb) { return pat == 0 ? Pick{nb - nb * (f + 1) / 8, 0u, 0} : Pick{never, fm[f], pat == 1 ? 0 : 3}; };
+        auto add = [&](int r2, Pick p, Pick q, const char* fmt, const char* a, const char* b) {
+            Pt t; t.r2 = r2; t.p = p; t.q = q; snprintf(t.name, 80, fmt, a, b); pts.push_back(t); };
+        // read + write; p = loads with the default policy, q = stores with plain nt (else sc1 nt)
+        add(0, Pick{nb1 - keep1, 0u, 0}, none, "rw PARENT  ld tail 44MiB, st sc1nt%s%s", "", "");
+        add(0, none, none, "rw ld f=0 (all nt), st sc1nt%s%s", "", "");
+        add(0, all, none, "rw ld f=1 (all default), st sc1nt%s%s", "", "");
+        for (int pat = 0; pat < 3; ++pat) for (int f = 0; f < 4; ++f) add(0, pick(pat, f, nb1), none, "rw ld %s f=%s, st sc1nt", pn[pat], fn[f]);
+        add(0, Pick{nb1 - keep1, 0u, 0}, all, "rw ld tail 44MiB, st f=1 (all nt)%s%s", "", "");
+        for (int pat = 0; pat < 2; ++pat) for (int f = 1; f < 4; f += 2) add(0, Pick{nb1 - keep1, 0u, 0}, pick(pat, f, nb1), "rw ld tail 44MiB, st nt %s f=%s", pn[pat], fn[f]);
+        // two reads; p = stream A (P) default, q = stream B (dy) default
+        add(1, Pick{nb2 - keep2, 0u, 0}, none, "r2 PARENT  A tail 44MiB, B nt%s%s", "", "");
+        add(1, none, none, "r2 f=0 (all nt)%s%s", "", "");
+        add(1, all, none, "r2 A f=1%s%s", "", "");
+        add(1, none, all, "r2 B f=1%s%s", "", "");
+        add(1, all, all, "r2 A+B f=1%s%s", "", "");
+        for (int pat = 0; pat < 3; ++pat) for (int f = 0; f < 4; ++f) {
+            add(1, pick(pat, f, nb2), none, "r2 A %s f=%s", pn[pat], fn[f]);
+            add(1, none, pick(pat, f, nb2), "r2 B %s f=%s", pn[pat], fn[f]);
+            add(1, pick(pat, f, nb2), pick(pat, f, nb2), "r2 A+B %s f=%s", pn[pat], fn[f]);
+        }
+        // beyond the issue's grid: other run lengths of the interleave (2^shift blocks), and the shipped tail kept next to it
+        for (int sh = 1; sh <= 6; ++sh) for (int f = 1; f < 3; ++f) {
+            if (sh == 3) continue;
+            char rl[24]; snprintf(rl, 24, "every-kth-run-of-%d", 1 << sh);
+            add(0, Pick{never, fm[f], sh}, none, "rw ld %s f=%s, st sc1nt", rl, fn[f]);
+            if (sh <= 4) add(1, Pick{never, fm[f], sh}, none, "r2 A %s f=%s", rl, fn[f]);
+        }
+        for (int f = 0; f < 2; ++f) {
+            add(0, Pick{nb1 - keep1, fm[f], 3}, none, "rw ld tail 44MiB + %s f=%s, st sc1nt", pn[2], fn[f]);
+            add(1, Pick{nb2 - keep2, fm[f], 0}, none, "r2 A tail 44MiB + %s f=%s, B nt", pn[1], fn[f]);
+        }
+        for (int f = 0; f < 3; ++f) add(1, Pick{nb2 - keep2, 0u, 0}, Pick{never, fm[f], 0}, "r2 A tail 44MiB, B %s f=%s", pn[1], fn[f]);
+        const int mi = 100;
+        for (int rnd = 0; rnd < 3; ++rnd)
+            for (const Pt& t : pts) {
+                auto launch = [&](int k) {
+                    if (t.r2) hipLaunchKernelGGL(k_mix_r2, dim3(nb2), dim3(512), 0, 0, A[k], B[k], sink, t.p, t.q);
+                    else hipLaunchKernelGGL(k_mix_rw, dim3(nb1), dim3(512), 0, 0, A[k], C[k], sink, t.p, t.q);
+                };
+                for (int w = 0; w < 8; ++w) launch(w % SETS);
+                CK(hipEventRecord(e0));
+                for (int it = 0; it < mi; ++it) launch(it % SETS);
+                CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1)); float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+                CK(hipGetLastError());
+                printf("round %d  %-52s %8.2f us  %7.0f GB/s\n", rnd, t.name, ms * 1000.0 / mi, b2 * mi / (ms * 1e-3) / 1e9);
+            }
+        return 0;
+    }
     // "survive" rows (`membench survive` prints only these): a 62 MB table (the first 0.4 of A[0]) is read with the default
     // policy, then 154 MB are stored to C[1] under one store policy, then the table is read again next to a cold 62 MB stream
     // (k_table2) and THAT kernel is timed.  "hot" re-reads it at once, "cold" after 616 MB of nontemporal read + write on other

@@ -18,6 +18,8 @@
  *   - `ws` is caller-owned DEVICE scratch of at least lq_workspace_bytes(outer,G,inner)
  *     bytes, 16-byte aligned; it carries deterministic two-stage reduction partials
  *     (no float atomics: results are run-to-run bit-stable);
+ *   - memory contract: the contents of `ws` on entry are irrelevant.  No call writes outside the stated extent of its outputs
+ *     and of [ws, ws + lq_workspace_bytes), and no byte outside the stated extents of its inputs influences any result;
  *   - return value: LQ_OK (0) or a negative lq_status; lq_last_error() returns a
  *     thread-local message for the last failing call on this thread.
  */

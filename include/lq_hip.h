@@ -146,6 +146,36 @@ int lq_fq_backward_clip_r(const float* P, const float* s, const float* dy, int32
                           float* dP, float* ds /* may be NULL */, uint32_t* clipped /* may be NULL */,
                           void* ws, size_t ws_bytes, int64_t outer, int64_t G, int64_t inner, void* stream);
 
+/* ---- group-wise (block) scales of the clipped pair ----
+ * The parameter is seen in MEMORY order as a matrix [R][C], C contiguous, R * C < 2^31.  axis = 0: groups run along R (strided: the
+ * `in` dimension of a Dense kernel stored (in, out)); axis = 1: groups run along C (contiguous: the (ci, kh, kw) run of one output
+ * channel of an OIHW conv kernel).  gs >= 1 is the group size and nb = ceil(len / gs) with len = R for axis 0 and C for axis 1: the
+ * last group of a line may be short, gs >= len gives one group per line.  The scale matrix is dense fp32, [nb][C] for axis 0 and
+ * [R][nb] for axis 1: element (r, c) uses s[r / gs][c] for axis 0 and s[r][c / gs] for axis 1.
+ * Per element and per group the definition is exactly the one of lq_fq_forward_clip_r / lq_fq_backward_clip_r above:
+ *   t = P / s (IEEE fp32 division), q0 = floorf(t) or rintf(t) by `rounding`, q = q0 < lo ? lo : (q0 > hi ? hi : q0) (comparisons),
+ *   out = q * s; inside = (q0 >= lo) && (q0 <= hi); dP = inside ? dy : +0.0f; r = inside ? q0 - t : q;
+ *   ds[g] = RN_f32( (double)grad_scale * sum_{i in g} (double)dy_i * (double)r_i ); clipped[g] = #{ i in g : !inside_i }, exact, uint32.
+ * ds and clipped have the scale's shape.  NaN and Inf behave as there and spoil only their own group.  The sums are f64 from the first
+ * addition and taken in one fixed order (no float atomics): run-to-run bit-stable; the note "no bit-identity of ds across traversals"
+ * carries over (the same data under the per-axis descriptor of lq_fq_backward_clip_r may differ in the last bits of the f64 sum).
+ * Any 4-byte aligned base works (16-byte aligned bases with C % 4 == 0 -- and gs % 4 == 0 on axis 1 -- take 16-byte accesses); a
+ * worse alignment returns LQ_EALIGN.  Dispatch is a pure function of the arguments; the library reads no environment.
+ * lq_group_workspace_bytes: scratch the backward needs for this shape.  Every shipped form emits ds and clipped from the launch
+ * that computes them, so it is 0 for every shape and `ws` may be NULL; a caller that sizes `ws` with it stays correct if a
+ * two-stage form is added (memory contract as above: the contents of `ws` on entry are irrelevant, no call writes outside the
+ * stated extents of its outputs and of [ws, ws + lq_group_workspace_bytes)).
+ * lq_fq_forward_group: `out` is required; q / q_dtype optionally give the CLAMPED integers.  lq_fq_backward_group: dP is required;
+ * ds == NULL means "mask only", clipped may be NULL.  A NULL required pointer, qmin > qmax, a bound outside +-2^24, a bad `rounding`,
+ * axis not in {0, 1}, gs < 1, a non-positive extent and R * C >= 2^31 return LQ_EINVAL before any launch.  Both calls only enqueue
+ * (capturable), ONE launch each.  */
+size_t lq_group_workspace_bytes(int64_t R, int64_t C, int axis, int64_t gs);
+int lq_fq_forward_group(const float* P, const float* s, float* out, void* q, int q_dtype, int32_t qmin, int32_t qmax, int rounding,
+                        int64_t R, int64_t C, int axis, int64_t gs, void* stream);
+int lq_fq_backward_group(const float* P, const float* s, const float* dy, int32_t qmin, int32_t qmax, int rounding, float grad_scale,
+                         float* dP, float* ds /* may be NULL: mask only */, uint32_t* clipped /* may be NULL */,
+                         void* ws, size_t ws_bytes, int64_t R, int64_t C, int axis, int64_t gs, void* stream);
+
 /* ---- K4: forward and NQ backward of one tensor in a single pass (benchmark path) ---
  * Same results as lq_fq_forward followed by lq_fq_scale_grad (out, max|q| and the vote count bit for bit; on
  * streaming-size tensors the vote sum may differ by fp32 summation order, ~1e-7 relative); P is read once.  */

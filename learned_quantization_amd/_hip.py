@@ -58,6 +58,10 @@ SIGNATURES = {
     "lq_fq_backward_clip": (_c_int, [_c_p, _c_p, _c_p, _c_i32, _c_i32, _c_f, _c_p, _c_p, _c_p, _c_p, _c_sz, _c_i64, _c_i64, _c_i64, _c_p]),
     "lq_fq_forward_clip_r": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_i32, _c_i32, _c_int, _c_i64, _c_i64, _c_i64, _c_p]),
     "lq_fq_backward_clip_r": (_c_int, [_c_p, _c_p, _c_p, _c_i32, _c_i32, _c_int, _c_f, _c_p, _c_p, _c_p, _c_p, _c_sz, _c_i64, _c_i64, _c_i64, _c_p]),
+    "lq_group_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_int, _c_i64]),
+    "lq_fq_forward_group": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_i32, _c_i32, _c_int, _c_i64, _c_i64, _c_int, _c_i64, _c_p]),
+    "lq_fq_backward_group": (_c_int, [_c_p, _c_p, _c_p, _c_i32, _c_i32, _c_int, _c_f, _c_p, _c_p, _c_p, _c_p, _c_sz, _c_i64, _c_i64, _c_int,
+                                      _c_i64, _c_p]),
     "lq_fq_fwd_bwd_fused": (_c_int, [_c_p, _c_p, _c_p, _c_f, _c_p, _c_p, _c_p, _c_sz, _c_i64, _c_i64, _c_i64, _c_p]),
     "lq_penalty_maxbin_fwd": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_sz, _c_i64, _c_i64, _c_i64, _c_p]),
     "lq_penalty_maxbin_bwd": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_f, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p]),

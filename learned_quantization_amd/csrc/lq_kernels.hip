@@ -49,6 +49,7 @@
 #include "lq_batch.hpp"
 #include "lq_stream2.hpp"
 #include "lq_pack.hpp"
+#include "lq_group.hpp"
 
 namespace lq {
 
@@ -1326,6 +1327,112 @@ int lq_fq_backward_clip_r(const float* P, const float* s, const float* dy, int32
 int lq_fq_backward_clip(const float* P, const float* s, const float* dy, int32_t qmin, int32_t qmax, float grad_scale, float* dP,
                         float* ds, uint32_t* clipped, void* ws, size_t ws_bytes, int64_t outer, int64_t G, int64_t inner, void* stream) {
     return clip_backward(__func__, P, s, dy, qmin, qmax, LQ_ROUND_FLOOR, grad_scale, dP, ds, clipped, ws, ws_bytes, outer, G, inner, stream);
+}
+
+// ---- group-wise (block) scales of the clipped pair (lq_group.hpp) ----
+// Dispatch is a pure function of the arguments: axis picks the traversal, V = 4 (float4) needs C % 4 == 0 (and gs % 4 == 0 on
+// axis 1) and every dense base 16-byte aligned, anything else that is 4-byte aligned runs the scalar form.  Neither form has a
+// second stage: the workspace size is 0 for every shape.
+static int check_group(const char* fn, int64_t R, int64_t C, int axis, int64_t gs) {
+    if (R <= 0 || C <= 0) return fail(LQ_EINVAL, "%s: extents must be positive (R=%lld C=%lld)", fn, (long long)R, (long long)C);
+    if ((double)R * (double)C >= 2147483648.0) return fail(LQ_EINVAL, "%s: R * C = %lld * %lld is not below 2^31", fn, (long long)R, (long long)C);
+    if (axis != 0 && axis != 1) return fail(LQ_EINVAL, "%s: bad axis %d (0: groups along R, 1: groups along C)", fn, axis);
+    if (gs < 1) return fail(LQ_EINVAL, "%s: group size %lld < 1", fn, (long long)gs);
+    return LQ_OK;
+}
+
+static GroupParams group_params(const float* P, const float* s, int32_t qmin, int32_t qmax, int64_t R, int64_t C, int axis, int64_t gs) {
+    GroupParams p{};
+    const int64_t len = axis == 0 ? R : C;
+    if (gs > len) gs = len;      // gs >= len: one group per line
+    p.P = P;
+    p.s = s;
+    p.lo = (float)qmin;
+    p.hi = (float)qmax;
+    p.k = 1.0f;
+    p.R = (int32_t)R;
+    p.C = (int32_t)C;
+    p.gs = (int32_t)gs;
+    p.nb = (int32_t)((len + gs - 1) / gs);
+    return p;
+}
+
+extern "C++" {      // a template inside the C-linkage block
+template <bool RNE, bool BWD>
+static int launch_group(const GroupParams& p, int axis, bool vec, hipStream_t st) {
+    if (axis == 0) {
+        const int cols = vec ? kGroupColsLanes4 * 4 : kGroupColsLanes1;
+        dim3 grid((unsigned)((p.C + cols - 1) / cols), (unsigned)std::min<int32_t>(p.nb, 32768));
+        if (!BWD) {      // a block per (column tile, group) leaves the chip half empty on weight-sized tensors: split the rows of a group
+            const int slots = kBlock / (vec ? kGroupColsLanes4 : kGroupColsLanes1);
+            while (grid.z < 4 && (int64_t)grid.x * grid.y * grid.z < 2048 && (int64_t)slots * grid.z * 4 <= p.gs) grid.z *= 2;
+        }
+        if (vec) hipLaunchKernelGGL((k_group_cols<RNE, BWD, 4, kGroupColsLanes4>), grid, dim3(kBlock), 0, st, p);
+        else hipLaunchKernelGGL((k_group_cols<RNE, BWD, 1, kGroupColsLanes1>), grid, dim3(kBlock), 0, st, p);
+        return check_hip("group-wise column launch");
+    }
+    const int64_t items = (p.gs + (vec ? 3 : 0)) / (vec ? 4 : 1);      // accesses per group; about four per lane
+    int log_team = 0;
+    while (log_team < 6 && ((int64_t)4 << log_team) < items) ++log_team;
+    const int64_t pairs = (int64_t)p.R * p.nb, per_block = kBlock >> log_team;
+    const dim3 grid((unsigned)((pairs + per_block - 1) / per_block));
+    if (vec) hipLaunchKernelGGL((k_group_rows<RNE, BWD, 4>), grid, dim3(kBlock), 0, st, p, log_team);
+    else hipLaunchKernelGGL((k_group_rows<RNE, BWD, 1>), grid, dim3(kBlock), 0, st, p, log_team);
+    return check_hip("group-wise row launch");
+}
+}  // extern "C++"
+
+size_t lq_group_workspace_bytes(int64_t R, int64_t C, int axis, int64_t gs) {
+    (void)R; (void)C; (void)axis; (void)gs;
+    return 0;      // every form is single-stage (lq_group.hpp)
+}
+
+int lq_fq_forward_group(const float* P, const float* s, float* out, void* q, int q_dtype, int32_t qmin, int32_t qmax, int rounding,
+                        int64_t R, int64_t C, int axis, int64_t gs, void* stream) {
+    const char* fn = __func__;
+    int rc = check_group(fn, R, C, axis, gs);
+    if (rc) return rc;
+    LQ_REQUIRE_PTR_FN(fn, P);
+    LQ_REQUIRE_PTR_FN(fn, s);
+    LQ_REQUIRE_PTR_FN(fn, out);
+    if ((rc = check_clip_range(fn, qmin, qmax))) return rc;
+    if ((rc = check_rounding(fn, rounding))) return rc;
+    if (q_dtype < LQ_Q_NONE || q_dtype > LQ_Q_I8) return fail(LQ_EINVAL, "%s: bad q_dtype %d", fn, q_dtype);
+    if ((q != nullptr) != (q_dtype != LQ_Q_NONE)) return fail(LQ_EINVAL, "%s: q and q_dtype disagree", fn);
+    if (q && q_dtype != LQ_Q_I8 && !aligned(q, 4)) return fail(LQ_EALIGN, "%s: q is not 4-byte aligned", fn);
+    GroupParams p = group_params(P, s, qmin, qmax, R, C, axis, gs);
+    p.out = out;
+    p.q = q;
+    p.q_dtype = q_dtype;
+    const bool vec = C % 4 == 0 && (axis == 0 || p.gs % 4 == 0) && aligned(P, 16) && aligned(out, 16);
+    if (rounding == LQ_ROUND_NEAREST_EVEN) return launch_group<true, false>(p, axis, vec, (hipStream_t)stream);
+    return launch_group<false, false>(p, axis, vec, (hipStream_t)stream);
+}
+
+int lq_fq_backward_group(const float* P, const float* s, const float* dy, int32_t qmin, int32_t qmax, int rounding, float grad_scale,
+                         float* dP, float* ds, uint32_t* clipped, void* ws, size_t ws_bytes, int64_t R, int64_t C, int axis,
+                         int64_t gs, void* stream) {
+    const char* fn = __func__;
+    (void)ws; (void)ws_bytes;      // lq_group_workspace_bytes() == 0: ws may be NULL and is never touched
+    int rc = check_group(fn, R, C, axis, gs);
+    if (rc) return rc;
+    LQ_REQUIRE_PTR_FN(fn, P);
+    LQ_REQUIRE_PTR_FN(fn, s);
+    LQ_REQUIRE_PTR_FN(fn, dy);
+    LQ_REQUIRE_PTR_FN(fn, dP);
+    if (ds && !aligned(ds, 4)) return fail(LQ_EALIGN, "%s: ds is not 4-byte aligned", fn);
+    if (clipped && !aligned(clipped, 4)) return fail(LQ_EALIGN, "%s: clipped is not 4-byte aligned", fn);
+    if ((rc = check_clip_range(fn, qmin, qmax))) return rc;
+    if ((rc = check_rounding(fn, rounding))) return rc;
+    GroupParams p = group_params(P, s, qmin, qmax, R, C, axis, gs);
+    p.dy = dy;
+    p.out = dP;
+    p.k = grad_scale;
+    p.ds = ds;
+    p.clipped = clipped;
+    const bool vec = C % 4 == 0 && (axis == 0 || p.gs % 4 == 0) && aligned(P, 16) && aligned(dy, 16) && aligned(dP, 16);
+    if (rounding == LQ_ROUND_NEAREST_EVEN) return launch_group<true, true>(p, axis, vec, (hipStream_t)stream);
+    return launch_group<false, true>(p, axis, vec, (hipStream_t)stream);
 }
 
 int lq_fq_fwd_bwd_fused(const float* P, const float* s, const float* dy, float lambda, float* out, float* ds, void* ws,

@@ -12,6 +12,10 @@ include/lq_hip.h: element ``i`` of the contiguous parameter uses scale element
 ``memory_order`` / ``memory_descriptor`` do the same for a parameter whose MEMORY is a permutation of its logical axes
 (a conv kernel presented HWIO like the reference's, custom_layers.py:321, but stored in the OIHW order the convolution
 library consumes): the descriptor then speaks about the element order in memory, which is all the kernels see.
+
+``groupwise_scale_shape`` / ``group_geometry`` are the second descriptor, for group-wise (block) scales (include/lq_hip.h,
+lq_fq_forward_group): the parameter's memory seen as a matrix [R][C] with groups of ``group_size`` along one of the two axes,
+which the flat rule above cannot express (groups along the strided axis, ragged lines).
 """
 from __future__ import annotations
 
@@ -90,3 +94,54 @@ def memory_descriptor(shape: Sequence[int], strides: Sequence[int], scale_shape_
     if len(scale_shape_) != len(shape):
         return group_descriptor(shape, scale_shape_)          # raises with the usual message
     return group_descriptor(tuple(shape[a] for a in order), tuple(scale_shape_[a] for a in order))
+
+
+def _check_group_size(group_size) -> int:
+    if isinstance(group_size, bool) or int(group_size) != group_size or int(group_size) < 1:
+        raise ValueError(f"group_size must be an integer >= 1, got {group_size!r}")
+    return int(group_size)
+
+
+def groupwise_scale_shape(param_shape: Sequence[int], group_size: int) -> Tuple[int, int]:
+    """Scale shape of ``orientation="groupwise"``: one scale per group of ``group_size`` consecutive inputs of each output unit.
+    The LAST logical axis holds the output units (Dense ``(in, out)``, conv HWIO ``(kh, kw, ci, co)``) and the others are its
+    inputs, ``fan_in`` of them; ``nb = ceil(fan_in / group_size)`` (the last group may be short).  A 2-D parameter gets
+    ``(nb, out)`` -- its memory is ``(in, out)``, the groups run along the strided axis -- and a parameter of more axes gets
+    ``(out, nb)``: its groups run along the contiguous (ci, kh, kw) run of each output channel of an OIHW-stored kernel."""
+    param_shape = tuple(int(d) for d in param_shape)
+    gs = _check_group_size(group_size)
+    if len(param_shape) < 2 or min(param_shape) <= 0:
+        raise ValueError(f"group-wise scales need a parameter of at least two non-empty axes (inputs..., outputs), got shape {param_shape}")
+    out = param_shape[-1]
+    nb = -(-math.prod(param_shape[:-1]) // gs)
+    return (nb, out) if len(param_shape) == 2 else (out, nb)
+
+
+def group_geometry(shape: Sequence[int], strides: Sequence[int], scale_shape_: Sequence[int], group_size: int) -> Tuple[int, int, int]:
+    """(R, C, axis) of include/lq_hip.h's group-wise entry points for a parameter of ``shape`` / ``strides`` and a 2-D scale:
+    the parameter's axes IN MEMORY ORDER split into a slow part of R and a contiguous part of C elements such that the scale is
+    ``(R, ceil(C / group_size))`` (axis 1, groups along the contiguous axis) or ``(ceil(R / group_size), C)`` (axis 0, groups
+    along the strided axis).  Raises ValueError when the memory is not a dense permutation of the logical axes or no split fits
+    -- the groups are defined in memory order, so a scale built for another storage order does not fit."""
+    shape = tuple(int(d) for d in shape)
+    scale_shape_ = tuple(int(d) for d in scale_shape_)
+    gs = _check_group_size(group_size)
+    order = memory_order(shape, strides)
+    if order is None:
+        raise ValueError(f"group-wise scales need a dense parameter (a permutation of a contiguous array), got shape {shape} "
+                         f"with strides {tuple(int(d) for d in strides)}")
+    if len(scale_shape_) != 2:
+        raise ValueError(f"a group-wise scale is a matrix, got shape {scale_shape_}")
+    dims = [shape[a] for a in order]
+    if not dims or math.prod(dims) <= 0:
+        raise ValueError(f"parameter must be non-empty, got shape {shape}")
+    if math.prod(dims) >= 1 << 31:
+        raise ValueError(f"group-wise scales take parameters below 2^31 elements, got {math.prod(dims)}")
+    for k in range(1, len(dims)):
+        R, C = math.prod(dims[:k]), math.prod(dims[k:])
+        if scale_shape_ == (R, -(-C // gs)):
+            return R, C, 1
+        if scale_shape_ == (-(-R // gs), C):
+            return R, C, 0
+    raise ValueError(f"scale shape {scale_shape_} fits no split of the parameter's memory-order extents {tuple(dims)} into [R][C] "
+                     f"with groups of {gs} along one axis (the groups are defined in memory order)")

@@ -124,6 +124,9 @@ def build_parser():
                          "--custom_loss")
     ap.add_argument("--rounding", default="floor", choices=["floor", "nearest"],
                     help="with --bits: round P/s down (the reference's floor) or to nearest, ties to even")
+    ap.add_argument("--group-size", type=int, default=None,
+                    help="with --bits and --scale-gradient ste (no --custom_loss): group-wise scales, one per N consecutive inputs of "
+                         "each output unit (replaces --orientation)")
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--steps-per-epoch", type=int, default=10)
     ap.add_argument("--batch", type=int, default=128)
@@ -161,7 +164,7 @@ def main(argv=None):
     tr = Trainer(args.config, mode, value, args.orientation, args.custom_loss, lr=args.lr, seed=args.seed, device=dev,
                  log_dir=log_dir, batched=args.batched, loss_values=args.loss_values,
                  loss_log_capacity=max(4096, args.steps_per_epoch), bits=args.bits, rounding=args.rounding,
-                 clipped_batch=args.clipped_batch)
+                 clipped_batch=args.clipped_batch, group_size=args.group_size)
     if args.training == "post_training":
         if args.config != "mnist" or not args.baseline_weights:
             raise SystemExit("post_training needs --config mnist --baseline-weights <npz with W1,b1,W2,b2> "
@@ -173,17 +176,21 @@ def main(argv=None):
             tr.model.dense_2.W.copy_(torch.from_numpy(w["W2"]))
             tr.model.dense_2.b.copy_(torch.from_numpy(w["b2"]))
     log_model_structure(tr.model, log_dir)
-    callbacks = [NestedScaleTrackingCallback(layer, log_dir) for layer in tr.custom_layers]
+    # the scale-tracking callback reads the unclipped integer view under one-axis scales: not attached to group-wise layers
+    callbacks = [NestedScaleTrackingCallback(layer, log_dir) for layer in tr.custom_layers if layer.group_size is None]
     callbacks.append(AccuracyLossTrackingCallBack(log_dir))
     t0 = time.perf_counter()
     history = fit(tr, args.epochs, args.steps_per_epoch, args.batch, callbacks, args.lr,
                   use_scheduler=(args.config == "imagenette"), seed=args.seed, with_penalty=args.loss_values)
     sizes = save_compress_parameters(tr.model, log_dir)
     packed = save_packed_parameters(tr.model, log_dir) if args.export_packed else None
-    stats = callbacks[0].stats()
     line = {"log_dir": log_dir, "epochs": args.epochs, "seconds": time.perf_counter() - t0,
-            "final": history[-1], "export": sizes,
-            "first_layer_unique_integers": stats["unique_k"], "first_layer_max_abs_q": float(stats["max_k"].max())}
+            "final": history[-1], "export": sizes}
+    if isinstance(callbacks[0], NestedScaleTrackingCallback):
+        stats = callbacks[0].stats()
+        line.update({"first_layer_unique_integers": stats["unique_k"], "first_layer_max_abs_q": float(stats["max_k"].max())})
+    else:
+        line["group_size"] = args.group_size
     if packed is not None:
         line["packed"] = packed
     if args.loss_values:

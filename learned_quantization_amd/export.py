@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .descriptor import group_geometry
 from .layers import CustomDenseLayer, CustomQuantizedScaleLayer, _ConvBase
 
 
@@ -65,6 +66,8 @@ def _pack_source(param: torch.nn.Parameter, nested: CustomQuantizedScaleLayer):
     scan and the packer see no integer outside the range even where floor(P/s) lies outside."""
     if getattr(nested, "q_range", None) is None:
         return param.data, nested.scale.data
+    if getattr(nested, "group_size", None) is not None:      # group-wise scales: the clamped integers over ONE unit scale
+        return nested.quantized_integers(param.data, torch.float32), torch.ones(1, dtype=torch.float32, device=param.device)
     return nested.quantized_integers(param.data, torch.float32), torch.ones_like(nested.scale.data)
 
 
@@ -143,6 +146,8 @@ def save_packed_parameters(model: torch.nn.Module, log_dir: str) -> Dict[str, fl
                         "numel": int(param.numel())})
         if getattr(nested, "rounding", "floor") != "floor":      # floor layers get no key: their container is unchanged
             entries[-1]["rounding"] = nested.rounding
+        if getattr(nested, "group_size", None) is not None:      # layers without group-wise scales get no key either
+            entries[-1]["group_size"] = int(nested.group_size)
     bad = torch.zeros(len(tensors), dtype=torch.int64, device=dev)
     words = [ops.q_pack(src, unit, qmin=e["qmin"], bits=e["bits"], bad=bad[k:k + 1])[0]
              for k, ((src, unit), e) in enumerate(zip(sources, entries))]
@@ -205,6 +210,9 @@ def _check_packed(model: torch.nn.Module, manifest: dict, z, tensors, state_keys
     for (name, param, nested), e in zip(tensors, entries):
         if list(e.get("shape", [])) != list(param.shape):
             raise ValueError(f"{name}: shape {e.get('shape')} in the container, {list(param.shape)} in the model")
+        if e.get("group_size") != getattr(nested, "group_size", None):      # a missing key means no group-wise scales
+            raise ValueError(f"{name}: group_size {e.get('group_size')} in the container, {getattr(nested, 'group_size', None)} in "
+                             "the model")
         if list(e.get("scale_shape", [])) != list(nested.scale.shape):
             raise ValueError(f"{name}: scale shape {e.get('scale_shape')} in the container, {list(nested.scale.shape)} in the model")
         if e.get("orientation") != nested.orientation:
@@ -235,11 +243,25 @@ def _check_packed(model: torch.nn.Module, manifest: dict, z, tensors, state_keys
             raise ValueError(f"state entry {key}: missing or shape {None if a is None else a.shape} != {tuple(sd[key].shape)}")
 
 
+def _restore_groupwise(param: torch.Tensor, q: torch.Tensor, s: torch.Tensor, group_size: int, rounding: str):
+    """(P, q) with the parameter's strides for the stored integers ``q`` (int32, logical order) of a group-wise layer:
+    P = (q + 1/2) * s for floor, q * s for nearest, s broadcast by the index rule of include/lq_hip.h (lq_fq_forward_group)."""
+    R, C, axis = group_geometry(tuple(param.shape), param.data.stride(), tuple(s.shape), group_size)
+    qs = torch.empty_like(param.data, dtype=torch.int32).copy_(q)
+    pr = torch.empty_like(param.data)
+    gs = min(int(group_size), R if axis == 0 else C)
+    sx = s.repeat_interleave(gs, dim=axis)[:R, :C]
+    qm = torch.as_strided(qs, (R, C), (C, 1)).to(torch.float32)      # the memory-order matrix of include/lq_hip.h
+    torch.as_strided(pr, (R, C), (C, 1)).copy_((qm if rounding == "nearest" else qm + 0.5) * sx)
+    return pr, qs
+
+
 def load_packed_parameters(model: torch.nn.Module, path: str) -> dict:
     """Restores a weights_packed.npz (or the directory holding it) into ``model`` -- built by build_model with the same
     config, either kernel_storage: each quantized P becomes a value whose floor(P/s) is the stored integer, each scale and every
     state entry the stored one, copied into the existing tensors.  A rounding="nearest" layer takes another pre-image: (q + 1/2) * s
     is a tie under rint, so its P becomes q * s, and the layer's own integer view of that P is compared with q on the device.
+    A group-wise layer is restored the same way with its scale broadcast over the groups, and always verified through its own view.
     Format, version, names, shapes, orientations and roundings are checked first: on a mismatch, or a restored value that does
     not round back, ValueError is raised and the model is left untouched.  Returns the manifest."""
     if os.path.isdir(path):
@@ -261,7 +283,17 @@ def load_packed_parameters(model: torch.nn.Module, path: str) -> dict:
     for (name, param, nested), e in zip(tensors, manifest["tensors"]):
         s = torch.from_numpy(scales[name]).to(dev)
         w = torch.from_numpy(codes[name].view(np.int32)).to(dev)
-        if e.get("rounding", "floor") == "nearest":
+        if e.get("group_size") is not None:
+            # P = (q + 1/2) * s (floor) or q * s (nearest) with the scale broadcast over its groups in the parameter's memory
+            # order; the layer's own group-wise integer view of that P is compared with q on the device
+            unit = torch.ones(1, dtype=torch.float32, device=dev)
+            _, q, _ = ops.q_unpack(w, e["qmin"], e["bits"], unit, param.shape, want_out=False, want_restore=False)
+            pr, qs = _restore_groupwise(param, q, s, e["group_size"], e.get("rounding", "floor"))
+            view = ops.fq_forward_group(pr, s, *nested.q_range, e["group_size"], q_dtype=torch.int32, rounding=nested.rounding)[1]
+            beyond = (qs < nested.q_range[0]) | (qs > nested.q_range[1])
+            outside += beyond.sum()
+            bad += ((view != qs) & ~beyond).sum()
+        elif e.get("rounding", "floor") == "nearest":
             # rint(fl(fl(q * s) / s)) == q holds for |q| < 2^22 and can miss beyond: counted with the stored scale, like the floor misses
             pr, q, _ = ops.q_unpack(w, e["qmin"], e["bits"], s, param.shape, want_restore=False)
             view = ops.fq_forward_clip(pr, s, *nested.q_range, q_dtype=torch.int32, rounding="nearest")[1]

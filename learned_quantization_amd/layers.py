@@ -50,7 +50,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .descriptor import scale_shape
+from .descriptor import groupwise_scale_shape, scale_shape
 
 eps_float32 = float(np.finfo(np.float32).eps)            # NQ-L:11
 SCALE_INIT = float(np.float32(eps_float32 * 100))        # NQ-L:156
@@ -134,18 +134,23 @@ class CustomQuantizedScaleLayer(nn.Module):
     clipped elements pass no gradient to the parameter and, with ``scale_gradient="ste"``, pull the scale towards covering them.
     ``rounding="nearest"`` (not in the reference; only with a range) -> the integers are rint(P/s), round half to even, instead of
     floor(P/s); the LSQ residual is then centred on zero.
+    ``orientation="groupwise", group_size=gs`` (not in the reference; only with a range and without a loss term) -> one scale per
+    ``gs`` consecutive inputs of each output unit (descriptor.groupwise_scale_shape; ops.fq_forward_group / fq_backward_group).
+    The groups are defined in the parameter's memory order: a Dense kernel ``(in, out)`` gets scales ``(nb, out)``, a conv kernel
+    stored OIHW gets ``(co, nb)`` over the (ci, kh, kw) run of each output channel.
     """
 
     _SCALE_NAMES = {"rowwise": "Rowwise-scaler", "columnwise": "Columnwise-scaler",
                     "channelwise": "Columnwise-scaler",      # sic, NQ-L:178
-                    "scalar": "Scalar-scaler"}
+                    "scalar": "Scalar-scaler", "groupwise": "Groupwise-scaler"}
 
     def __init__(self, penalty_threshold=None, initializer=None, orientation="scalar", *, penalty_rate=None,
-                 scale_gradient=None, grad_scale=1.0, bits=None, signed=True, q_range=None, rounding="floor"):
+                 scale_gradient=None, grad_scale=1.0, bits=None, signed=True, q_range=None, rounding="floor", group_size=None):
         super().__init__()
         self.q_range = ops.q_range_of(bits, signed, q_range)
         ops.check_rounding(rounding, self.q_range is not None)
         self.rounding = rounding
+        self.group_size = check_groupwise(orientation, group_size, self.q_range, penalty_threshold, penalty_rate)
         if self.q_range is not None and penalty_threshold is not None:
             raise ValueError("a clipped layer (bits / q_range) needs penalty_threshold=None: the nested-quantization vote is "
                              "defined on the unclipped quantizer")
@@ -168,7 +173,10 @@ class CustomQuantizedScaleLayer(nn.Module):
         self.defer_scale_grad = False          # set by DataParallel(mode="B"): ds is recomputed after the all-reduce
 
     def build(self, input_shape, device=None):
-        shape = scale_shape(tuple(input_shape), self.orientation)  # raises ValueError like NQ-L:194-197
+        if self.group_size is not None:
+            shape = groupwise_scale_shape(tuple(input_shape), self.group_size)
+        else:
+            shape = scale_shape(tuple(input_shape), self.orientation)  # raises ValueError like NQ-L:194-197
         self.scale = nn.Parameter(torch.full(shape, SCALE_INIT, dtype=torch.float32, device=device))  # NQ-L:156
         self.scale.lq_constraint = self.constraint                 # found by optim.apply_constraints
         self.scale.lq_is_scale = True
@@ -191,7 +199,8 @@ class CustomQuantizedScaleLayer(nn.Module):
         if self.q_range is not None:
             return ops.my_custom_gradient(inputs, self.scale, self.penalty_threshold, scale_gradient=self.scale_gradient,
                                           grad_scale=self.grad_scale_value(inputs.numel()) if self.scale_gradient == "ste" else 1.0,
-                                          defer_scale_grad=self.defer_scale_grad, q_range=self.q_range, rounding=self.rounding)
+                                          defer_scale_grad=self.defer_scale_grad, q_range=self.q_range, rounding=self.rounding,
+                                          group_size=self.group_size)
         if self.scale_gradient == "ste":
             return ops.my_custom_gradient(inputs, self.scale, scale_gradient="ste", grad_scale=self.grad_scale_value(inputs.numel()),
                                           defer_scale_grad=self.defer_scale_grad)
@@ -210,6 +219,8 @@ class CustomQuantizedScaleLayer(nn.Module):
             r += f", q_range={self.q_range!r}"
         if self.rounding != "floor":
             r += f", rounding={self.rounding!r}"
+        if self.group_size is not None:
+            r += f", group_size={self.group_size}"
         return r
 
     def quantized_integers(self, parameter, dtype=torch.float32):
@@ -217,14 +228,38 @@ class CustomQuantizedScaleLayer(nn.Module):
         rint(P/s) for ``rounding="nearest"``)."""
         if self.q_range is None:
             return ops.quantized_integers(parameter, self.scale.data, dtype)
+        if self.group_size is not None:
+            return ops.fq_forward_group(parameter, self.scale.data, *self.q_range, self.group_size, q_dtype=dtype,
+                                        rounding=self.rounding)[1]
         return ops.fq_forward_clip(parameter, self.scale.data, *self.q_range, q_dtype=dtype, rounding=self.rounding)[1]
 
 
-def _nested(penalty_threshold, penalty_rate, orientation, scale_gradient=None, grad_scale=1.0, q_range=None, rounding="floor"):
+def check_groupwise(orientation, group_size, q_range, penalty_threshold=None, penalty_rate=None):
+    """The ``group_size`` of a layer as an int (None for the reference's orientations), or ValueError naming the reason."""
+    if orientation != "groupwise":
+        if group_size is not None:
+            raise ValueError(f'group_size needs orientation="groupwise", got orientation={orientation!r}')
+        return None
+    if group_size is None:
+        raise ValueError('orientation="groupwise" needs group_size (elements per scale)')
+    if isinstance(group_size, bool) or int(group_size) != group_size or int(group_size) < 1:
+        raise ValueError(f"group_size must be an integer >= 1, got {group_size!r}")
+    if q_range is None:
+        raise ValueError('orientation="groupwise" needs bits or q_range: group-wise scales exist for the clipped quantizer only')
+    if penalty_threshold is not None:
+        raise ValueError('orientation="groupwise" with a penalty_threshold: the nested-quantization vote is defined on the '
+                         "unclipped quantizer with one-axis scales")
+    if penalty_rate is not None:
+        raise ValueError('orientation="groupwise" with a loss term (penalty_rate): the penalty kernels broadcast one-axis scales')
+    return int(group_size)
+
+
+def _nested(penalty_threshold, penalty_rate, orientation, scale_gradient=None, grad_scale=1.0, q_range=None, rounding="floor",
+            group_size=None):
     return CustomQuantizedScaleLayer(penalty_threshold=penalty_threshold, initializer=None,
                                      orientation=orientation, penalty_rate=penalty_rate,
                                      scale_gradient=scale_gradient, grad_scale=grad_scale, q_range=q_range,
-                                     rounding=rounding)
+                                     rounding=rounding, group_size=group_size)
 
 
 def _as_tensor(a, shape, device):
@@ -237,12 +272,30 @@ def _as_tensor(a, shape, device):
 class _HostLayer(nn.Module):
     q_range = None
     rounding = "floor"
+    group_size = None
 
     def extra_repr(self):
         r = f"q_range={self.q_range!r}" if self.q_range is not None else ""
         if self.rounding != "floor":
             r += f", rounding={self.rounding!r}"
+        if self.group_size is not None:
+            r += f", group_size={self.group_size}"
         return r
+
+    def make_groupwise(self, group_size):
+        """Switches the weight quantizer of a constructed layer to ``orientation="groupwise"`` with this ``group_size`` and
+        rebuilds its scale (models.build_model applies ranges and group sizes after construction); the bias stays scalar."""
+        conv = hasattr(self, "nested_q_k_layer")
+        nested = self.nested_q_k_layer if conv else self.nested_q_w_layer
+        gs = check_groupwise("groupwise", group_size, self.q_range, nested.penalty_threshold, nested.penalty_rate)
+        if conv and self.kernel_storage != "oihw":
+            raise ValueError('orientation="groupwise" with kernel_storage="hwio": the groups are defined in the convolution\'s memory '
+                             'order (the contiguous (ci, kh, kw) run of an output channel); store the kernel "oihw"')
+        self.group_size = nested.group_size = gs
+        nested.orientation = "groupwise"
+        if nested.built:
+            param = self.kernel if conv else self.W
+            nested.build(tuple(param.shape), device=param.device)
 
     def _init_value(self, initializer, shape, device):
         if initializer is None:
@@ -268,13 +321,17 @@ class CustomDenseLayer(_HostLayer):
 
     def __init__(self, seed=None, units=None, penalty_threshold=None, orientation="scalar", initializer=None,
                  name=None, regularizer=None, trained_weights=None, *, penalty_rate=None, input_shape=None,
-                 device=None, scale_gradient=None, grad_scale=1.0, bits=None, signed=True, q_range=None, rounding="floor", **kwargs):
+                 device=None, scale_gradient=None, grad_scale=1.0, bits=None, signed=True, q_range=None, rounding="floor",
+                 group_size=None, **kwargs):
         super().__init__()
         self.seed = seed
         self.q_range = ops.q_range_of(bits, signed, q_range)      # None: the reference's unbounded quantizer
         ops.check_rounding(rounding, self.q_range is not None)
         self.rounding = rounding
-        self.nested_q_w_layer = _nested(penalty_threshold, penalty_rate, orientation, scale_gradient, grad_scale, self.q_range, rounding)   # NQ-L:222-224
+        # groupwise: groups along `in` for every output column, scale (nb, out); the bias keeps its scalar scale
+        self.group_size = check_groupwise(orientation, group_size, self.q_range, penalty_threshold, penalty_rate)
+        self.nested_q_w_layer = _nested(penalty_threshold, penalty_rate, orientation, scale_gradient, grad_scale, self.q_range, rounding,
+                                        self.group_size)   # NQ-L:222-224
         self.nested_q_b_layer = _nested(penalty_threshold, penalty_rate, "scalar", scale_gradient, grad_scale, self.q_range, rounding)      # NQ-L:225-227
         self.units = units
         self.initializer = initializer
@@ -363,7 +420,8 @@ class _ConvBase(_HostLayer):
     def __init__(self, seed=None, penalty_threshold=None, orientation="scalar", initializer=None, filters=None,
                  kernel_size=(3, 3), strides=(1, 1), padding="same", name=None, regularizer=None,
                  trained_weights=None, *, penalty_rate=None, input_shape=None, data_format="NCHW", device=None,
-                 kernel_storage=None, scale_gradient=None, grad_scale=1.0, bits=None, signed=True, q_range=None, rounding="floor", **kwargs):
+                 kernel_storage=None, scale_gradient=None, grad_scale=1.0, bits=None, signed=True, q_range=None, rounding="floor",
+                 group_size=None, **kwargs):
         super().__init__()
         self.seed = seed
         self.q_range = ops.q_range_of(bits, signed, q_range)      # None: the reference's unbounded quantizer
@@ -374,7 +432,13 @@ class _ConvBase(_HostLayer):
         if kernel_storage not in ("oihw", "hwio"):
             raise ValueError("kernel_storage must be 'oihw' or 'hwio'")
         self.kernel_storage = kernel_storage
-        self.nested_q_k_layer = _nested(penalty_threshold, penalty_rate, orientation, scale_gradient, grad_scale, self.q_range, rounding)      # NQ-L:293-295
+        # groupwise: groups along the (ci, kh, kw) memory run of every output channel, scale (co, nb); the bias stays scalar
+        self.group_size = check_groupwise(orientation, group_size, self.q_range, penalty_threshold, penalty_rate)
+        if self.group_size is not None and kernel_storage != "oihw":
+            raise ValueError('orientation="groupwise" with kernel_storage="hwio": the groups are defined in the convolution\'s memory '
+                             'order (the contiguous (ci, kh, kw) run of an output channel); store the kernel "oihw"')
+        self.nested_q_k_layer = _nested(penalty_threshold, penalty_rate, orientation, scale_gradient, grad_scale, self.q_range, rounding,
+                                        self.group_size)      # NQ-L:293-295
         if self._has_bias:
             self.nested_q_b_layer = _nested(penalty_threshold, penalty_rate, "scalar", scale_gradient, grad_scale, self.q_range, rounding)     # NQ-L:296-298
         self.initializer = initializer

@@ -280,16 +280,41 @@ def check_clip_mode(mode: str) -> None:
                          f"a clipped model needs one of the modes {CLIP_MODES}")
 
 
+GROUP_MODES = ("ste",)
+
+
+def check_group_mode(mode: str, has_range: bool) -> None:
+    """Group-wise scales need the clipped quantizer and a mode whose scale gradient is "ste" without a loss term."""
+    if not has_range:
+        raise ValueError("group_size needs bits / q_range: group-wise scales exist for the clipped quantizer only")
+    if mode in ("cl", "stecl", "nqcl"):
+        raise ValueError(f"group_size with mode {mode!r}: the loss-term penalty kernels broadcast one-axis scales; group-wise scales "
+                         f"train with one of the modes {GROUP_MODES}")
+    if mode not in GROUP_MODES:
+        raise ValueError(f"group_size with mode {mode!r}: group-wise scales train with one of the modes {GROUP_MODES}")
+
+
 def build_model(config: str, kernel_storage: str = None, grad_scale=None, bits=None, signed=True, q_range=None, rounding="floor",
-                **kw) -> nn.Module:
+                group_size=None, **kw) -> nn.Module:
     """config: 'mnist' (C1), 'cifar' (C2/C4), 'imagenette' (C3), 'resnet50' (C5, extension).
     ``kernel_storage``: memory order of the conv kernels, "oihw" (default) or "hwio" (layers.py).
     ``grad_scale`` (modes "ste" / "stecl"): factor of every straight-through scale gradient, a float or "rsqrt_group".
     ``bits`` (1..24) with ``signed``, or ``q_range=(qmin, qmax)`` (modes "cl" / "ste" / "stecl"): the integer range of every
     quantised tensor, carried by the host layers and both of their nested layers.
-    ``rounding`` ("floor" / "nearest"; "nearest" only with a range): how that quantizer rounds P/s, carried the same way."""
+    ``rounding`` ("floor" / "nearest"; "nearest" only with a range): how that quantizer rounds P/s, carried the same way.
+    ``group_size`` (with a range, mode "ste"): every quantised kernel gets group-wise scales, one per ``group_size`` consecutive
+    inputs of each output unit (layers.py ``orientation="groupwise"``; it replaces ``orientation``); biases keep a scalar scale."""
     from .ops import check_rounding
     check_rounding(rounding, bits is not None or q_range is not None)
+    if group_size is not None:
+        from .layers import _HostLayer
+        check_group_mode(kw.get("mode", "nq"), bits is not None or q_range is not None)
+        model = build_model(config, kernel_storage=kernel_storage, grad_scale=grad_scale, bits=bits, signed=signed, q_range=q_range,
+                            rounding=rounding, **{**kw, "orientation": "scalar"})
+        for m in model.modules():
+            if isinstance(m, _HostLayer):
+                m.make_groupwise(group_size)
+        return model
     if bits is not None or q_range is not None:
         from .layers import CustomQuantizedScaleLayer, _HostLayer
         from .ops import q_range_of

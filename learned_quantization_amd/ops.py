@@ -7,7 +7,7 @@
     /root/reference/CIFAR-10/custom_loss_terms/custom_components/custom_layers.py:49-64
 
 Raw (non-autograd) wrappers ``fq_forward``, ``fq_scale_grad``, ``fq_scale_grad_ste``, ``fq_forward_clip``,
-``fq_backward_clip``, ``fq_fwd_bwd_fused``, ``quantized_integers`` ... are thin: argument checking + one C-ABI call each.
+``fq_backward_clip``, ``fq_forward_group``, ``fq_backward_group``, ``fq_fwd_bwd_fused``, ``quantized_integers`` ... are thin: argument checking + one C-ABI call each.
 Everything runs on the HIP device; there is no CPU fallback.
 """
 from __future__ import annotations
@@ -17,7 +17,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _hip
-from .descriptor import group_descriptor, memory_descriptor
+from .descriptor import group_descriptor, group_geometry, memory_descriptor
 
 _QDTYPES = {
     torch.float32: _hip.LQ_Q_F32,
@@ -180,6 +180,50 @@ def fq_backward_clip(parameter: torch.Tensor, scale: torch.Tensor, dy: torch.Ten
     _hip.check(lib.lq_fq_backward_clip_r(_hip.ptr(p), _hip.ptr(s), _hip.ptr(d), qmin, qmax, rnd, float(grad_scale), _hip.ptr(dP),
                                          _hip.ptr(ds), _hip.ptr(clipped), _hip.ptr(ws), ws.numel(), outer, G, inner,
                                          _hip.stream_ptr(p.device)), "lq_fq_backward_clip_r")
+    return dP, ds, clipped
+
+
+def _group_param(parameter: torch.Tensor, scale: torch.Tensor, group_size: int):
+    """(P, s, (R, C, axis)) as the group-wise kernels read them: the parameter in its own memory order (descriptor.group_geometry)."""
+    p = _hip.require_device_f32(parameter, "parameter", dense_ok=True)
+    s = _hip.require_device_f32(scale, "scale")
+    return p, s, group_geometry(tuple(p.shape), p.stride(), tuple(s.shape), group_size)
+
+
+def fq_forward_group(parameter: torch.Tensor, scale: torch.Tensor, qmin: int, qmax: int, group_size: int,
+                     q_dtype: Optional[torch.dtype] = None, *, rounding: str = "floor"):
+    """Clipped forward with group-wise scales (include/lq_hip.h, lq_fq_forward_group): ``scale`` is the matrix of
+    descriptor.groupwise_scale_shape, one scale per ``group_size`` elements along one axis of the parameter's memory.  Returns
+    ``out`` (the parameter's strides), or ``(out, q)`` with the clamped integers when ``q_dtype`` is given."""
+    qmin, qmax = check_q_range(qmin, qmax)
+    rnd = check_rounding(rounding)
+    lib = _hip.load()
+    p, s, (R, C, axis) = _group_param(parameter, scale, group_size)
+    out = torch.empty_like(p)
+    q, qd = _q_buffer(p, q_dtype)
+    _hip.check(lib.lq_fq_forward_group(_hip.ptr(p), _hip.ptr(s), _hip.ptr(out), _hip.ptr(q), qd, qmin, qmax, rnd,
+                                       R, C, axis, int(group_size), _hip.stream_ptr(p.device)), "lq_fq_forward_group")
+    return out if q is None else (out, q)
+
+
+def fq_backward_group(parameter: torch.Tensor, scale: torch.Tensor, dy: torch.Tensor, qmin: int, qmax: int, group_size: int,
+                      grad_scale: float = 1.0, want_ds: bool = True, want_clipped: bool = False, *, rounding: str = "floor"):
+    """Clipped backward with group-wise scales (include/lq_hip.h, lq_fq_backward_group).  Returns ``(dP, ds, clipped)`` as
+    ``fq_backward_clip`` does: dP with the parameter's strides, ds and clipped (int32 tensor holding the uint32 counts) in the
+    shape of ``scale``, None where not wanted."""
+    qmin, qmax = check_q_range(qmin, qmax)
+    rnd = check_rounding(rounding)
+    lib = _hip.load()
+    p, s, (R, C, axis) = _group_param(parameter, scale, group_size)
+    d = _hip.require_device_f32(dy, "dy", like=p)
+    dP = torch.empty_like(p)
+    ds = torch.empty_like(s) if want_ds else None
+    clipped = torch.empty_like(s, dtype=torch.int32) if want_clipped else None
+    need = lib.lq_group_workspace_bytes(R, C, axis, int(group_size))
+    ws = _hip.workspace(p.device, need) if need else None
+    _hip.check(lib.lq_fq_backward_group(_hip.ptr(p), _hip.ptr(s), _hip.ptr(d), qmin, qmax, rnd, float(grad_scale), _hip.ptr(dP),
+                                        _hip.ptr(ds), _hip.ptr(clipped), _hip.ptr(ws), ws.numel() if ws is not None else 0,
+                                        R, C, axis, int(group_size), _hip.stream_ptr(p.device)), "lq_fq_backward_group")
     return dP, ds, clipped
 
 
@@ -542,11 +586,35 @@ class _ClipQuantFn(torch.autograd.Function):
         return (dP if ctx.needs_input_grad[0] else None), ds, None, None, None, None, None
 
 
+class _GroupQuantFn(torch.autograd.Function):
+    """``_ClipQuantFn`` with group-wise scales: forward lq_fq_forward_group, backward lq_fq_backward_group."""
+
+    @staticmethod
+    def forward(ctx, parameter, scale, qmin, qmax, group_size, grad_scale, want_ds, rounding="floor"):
+        ctx.save_for_backward(parameter, scale)
+        ctx.rounding = rounding
+        ctx.q_range = (int(qmin), int(qmax))
+        ctx.group_size = int(group_size)
+        ctx.grad_scale = float(grad_scale)
+        ctx.want_ds = bool(want_ds)
+        return fq_forward_group(parameter, scale, qmin, qmax, group_size, rounding=rounding)
+
+    @staticmethod
+    def backward(ctx, dy):
+        parameter, scale = ctx.saved_tensors
+        want_ds = ctx.want_ds and ctx.needs_input_grad[1]
+        dP, ds, _ = fq_backward_group(parameter, scale, dy, *ctx.q_range, ctx.group_size, grad_scale=ctx.grad_scale,
+                                      want_ds=want_ds, rounding=ctx.rounding)
+        if ds is None and ctx.needs_input_grad[1]:
+            ds = torch.zeros_like(scale)
+        return (dP if ctx.needs_input_grad[0] else None), ds, None, None, None, None, None, None
+
+
 SCALE_GRADIENTS = (None, "ste")
 
 
 def my_custom_gradient(parameter, scale, penalty_threshold=None, *, scale_gradient=None, grad_scale=1.0, defer_scale_grad=False,
-                       q_range=None, rounding="floor"):
+                       q_range=None, rounding="floor", group_size=None):
     """The reference op.  With ``penalty_threshold`` -> nested-quantization variant
     (custom_layers.py:49-120); without -> STE-only variant (CL custom_layers.py:49-64).
     ``scale_gradient="ste"`` (not in the reference, only without ``penalty_threshold``): the scale receives the
@@ -557,7 +625,19 @@ def my_custom_gradient(parameter, scale, penalty_threshold=None, *, scale_gradie
     saturate at the range, clipped elements pass no gradient to ``parameter``; with ``scale_gradient="ste"`` the scale gets the
     LSQ gradient (clipped elements pull it by ``dy * qmin`` / ``dy * qmax``), with ``None`` it gets zeros.
     ``rounding="nearest"`` (not in the reference, only with ``q_range``): the integers are rint(P/s), round half to even, instead
-    of floor(P/s), and the LSQ residual is rint(t) - t in [-1/2, 1/2]."""
+    of floor(P/s), and the LSQ residual is rint(t) - t in [-1/2, 1/2].
+    ``group_size=gs`` (not in the reference, only with ``q_range``): ``scale`` is a group-wise scale matrix
+    (descriptor.groupwise_scale_shape): one scale per ``gs`` elements along one axis of the parameter's memory."""
+    if group_size is not None:
+        if q_range is None:
+            raise ValueError("group_size needs a q_range: group-wise scales exist for the clipped quantizer only (the unclipped "
+                             "ops broadcast one-axis scales)")
+        if penalty_threshold is not None:
+            raise ValueError("group_size with a penalty_threshold: the nested-quantization vote is defined on the unclipped "
+                             "quantizer with one-axis scales")
+        if defer_scale_grad:
+            raise ValueError("group_size with defer_scale_grad: the all-reduced dP of a clipped layer no longer holds the dy of "
+                             "its clipped elements, so ds cannot be recomputed from it")
     if scale_gradient not in SCALE_GRADIENTS:
         raise ValueError(f"scale_gradient must be one of {SCALE_GRADIENTS}, got {scale_gradient!r}")
     check_rounding(rounding, q_range is not None)
@@ -569,6 +649,9 @@ def my_custom_gradient(parameter, scale, penalty_threshold=None, *, scale_gradie
             raise ValueError("q_range with defer_scale_grad: the all-reduced dP of a clipped layer no longer holds the dy of its "
                              "clipped elements, so ds cannot be recomputed from it")
         qmin, qmax = check_q_range(*q_range)
+        if group_size is not None:
+            return _GroupQuantFn.apply(parameter, scale, qmin, qmax, int(group_size), float(grad_scale), scale_gradient == "ste",
+                                       rounding)
         return _ClipQuantFn.apply(parameter, scale, qmin, qmax, float(grad_scale), scale_gradient == "ste", rounding)
     if scale_gradient == "ste":
         if penalty_threshold is not None:

@@ -30,7 +30,7 @@ from . import layers as L
 from . import _hip
 from .ddp import CaptureRefused, DataParallel, capture_with_agreement, control_group
 from .losses import LossLog, SCCEDifference, SCCEInverse, SCCEMaxBin, sparse_categorical_crossentropy
-from .models import INPUT_SHAPES, build_model, check_clip_mode
+from .models import INPUT_SHAPES, build_model, check_clip_mode, check_group_mode
 from .ops import ROUNDINGS, check_rounding, q_range_of
 from .optim import KerasAdam, ScaleAdam, non_scale_parameters, scale_parameters
 
@@ -73,8 +73,10 @@ class Trainer:
                  bucket_mb: float = 25.0, overlap: bool = True, graph_collectives: Optional[bool] = None,
                  force_collectives: bool = False, kernel_storage: str = "oihw", loss_values: bool = False,
                  loss_log_capacity: int = 4096, grad_scale=None, bits=None, signed=True, q_range=None, rounding="floor",
-                 clipped_batch: bool = False):
-        """``clipped_batch`` (opt-in, with ``batched=True`` and a range): the clipped layers run in the multi-tensor batch
+                 clipped_batch: bool = False, group_size=None):
+        """``group_size`` (with ``bits`` / ``q_range`` and mode "ste"; eager, graphed and data-parallel mode "A"): group-wise scales
+        for every quantised kernel (models.build_model); it replaces ``orientation``.
+        ``clipped_batch`` (opt-in, with ``batched=True`` and a range): the clipped layers run in the multi-tensor batch
         (``FakeQuantBatch(clipped=True)``: one forward launch, two backward launches; the batch owns one dP buffer per tensor
         and its backward moves 12 bytes per element instead of 8).  Everything else about a range stays: modes "cl", "ste",
         "stecl", data-parallel mode "A".
@@ -93,6 +95,15 @@ class Trainer:
         self.config = config
         self.mode = mode
         ste = mode in ("ste", "stecl")
+        self.group_size = group_size
+        if group_size is not None:
+            check_group_mode(mode, bits is not None or q_range is not None)
+            if batched:
+                raise ValueError("group_size with batched=True: the multi-tensor batch describes every tensor by one-axis "
+                                 "(outer, G, inner) scales; group-wise scales run on the per-tensor path")
+            if ddp_mode == "B":
+                raise ValueError("group_size with ddp_mode 'B': it recomputes ds from the all-reduced dP, which no longer holds the "
+                                 "dy of the clipped elements; use ddp_mode 'A'")
         if ste and ddp_mode == "B":
             raise ValueError(f"mode {mode!r} with ddp_mode 'B': the straight-through scale gradient is linear in dy, so averaging ds "
                              "over the ranks (ddp_mode 'A') already is the global-batch gradient; there is nothing to recompute")
@@ -119,7 +130,8 @@ class Trainer:
         # conv kernels shaped HWIO like the reference's, stored in the order MIOpen consumes (layers.py kernel_storage): the
         # fake-quantised kernel goes to the convolution as written and its weight gradient is dP
         self.model = build_model(config, mode=mode, value=value, seed=seed, orientation=orientation, device=self.device,
-                                 kernel_storage=kernel_storage, grad_scale=grad_scale, q_range=self.q_range, rounding=rounding)
+                                 kernel_storage=kernel_storage, grad_scale=grad_scale, q_range=self.q_range, rounding=rounding,
+                                 group_size=group_size)
         self.model.to(self.device)
         self.custom_layers = L.custom_layers_of(self.model)
         self.loss_obj = None
@@ -404,6 +416,9 @@ def build_parser():
     ap.add_argument("--unsigned", action="store_true", help="with --bits: integers in [0, 2^b - 1]")
     ap.add_argument("--rounding", default="floor", choices=list(ROUNDINGS),
                     help="with --bits: round P/s down (the reference's floor) or to nearest, ties to even")
+    ap.add_argument("--group-size", type=int, default=None,
+                    help="with --bits and mode ste: group-wise scales, one per N consecutive inputs of each output unit (replaces "
+                         "--orientation; biases keep a scalar scale)")
     ap.add_argument("--rate", type=float, default=1e-7, help="penalty_rate of the loss term in mode nqcl")
     ap.add_argument("--value-coarse", type=float, default=None,
                     help="resnet50 only: threshold of the 3x3 kernels ('mixed' quantisation intensity); --value is the rest")
@@ -476,7 +491,8 @@ def main(argv=None):
                  loss_values=args.loss_values, loss_log_capacity=max(4096, args.steps + args.warmup + 8),
                  grad_scale=(None if args.grad_scale is None else
                              (args.grad_scale if args.grad_scale == "rsqrt_group" else float(args.grad_scale))),
-                 bits=args.bits, signed=not args.unsigned, rounding=args.rounding, clipped_batch=args.clipped_batch)
+                 bits=args.bits, signed=not args.unsigned, rounding=args.rounding, clipped_batch=args.clipped_batch,
+                 group_size=args.group_size)
     do_step = tr.step_graphed if args.graph else tr.step
     g = torch.Generator(device=dev).manual_seed(args.seed + rank)
     batches = [synthetic_batch(args.config, args.batch, dev, g) for _ in range(4)]
@@ -504,7 +520,8 @@ def main(argv=None):
         print(json.dumps({
             "metric": "images/sec end-to-end training step (synthetic data)", "config": args.config, "mode": args.mode,
             "value": world * args.batch * args.steps / dt, "unit": "images/s", "n_gpus": world,
-            "ms_per_step": dt / args.steps * 1e3, "per_gpu_batch": args.batch, "orientation": args.orientation,
+            "ms_per_step": dt / args.steps * 1e3, "per_gpu_batch": args.batch,
+            "orientation": ("groupwise" if args.group_size is not None else args.orientation),
             "loss_term": args.loss, "quantized_elements": n_q, "final_loss": float(loss.detach()), "ddp_mode": args.ddp_mode,
             "hipgraph": bool(args.graph), "graph_collectives": bool(tr.graph_collectives and args.graph and use_dist),
             **({"graph_note": tr.graph_note} if tr.graph_note else {}), "batched": bool(args.batched),
@@ -513,6 +530,7 @@ def main(argv=None):
             "channels_last": bool(args.channels_last), "kernel_storage": args.kernel_storage,
             **({"q_range": list(tr.q_range)} if tr.q_range else {}),
             **({"rounding": tr.rounding} if tr.rounding != "floor" else {}),
+            **({"group_size": tr.group_size} if tr.group_size is not None else {}),
             **({"loss_values": True, "loss_log_rows": log_rows[0], "loss_log_dropped": log_rows[1]} if log_rows else {})}))
         if args.export_dir:
             from .export import save_compress_parameters

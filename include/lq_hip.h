@@ -346,6 +346,44 @@ int lq_batch_backward_clip(const lq_batch* batch, const float* const* dy, const 
                            void* stream);
 int lq_batch_clip_counts(const lq_batch* batch, int tensor, const uint32_t** dev, int64_t* groups);
 
+/* ---- group-wise tensors in a batch: ONE launch per pass ----
+ * lq_fq_forward_group / lq_fq_backward_group of up to 256 tensors.  Per tensor the definition is exactly the one stated at
+ * lq_fq_forward_group above; each tensor has its own range and geometry, the batch has one rounding.  A 1-D parameter with a
+ * scalar scale (a bias) is the geometry R = 1, C = numel, axis = 1, gs = numel: one group.
+ * lq_group_batch_create / _destroy: HOST calls (allocate and upload: never inside a capture).  create validates every descriptor
+ *   before its first HIP call: n outside 1 .. 256, a NULL P / s / out / dp, a bad axis, gs < 1, a non-positive extent,
+ *   R * C >= 2^31, qmin > qmax, a bound outside +-2^24 and a bad rounding return LQ_EINVAL, a base that is not 4-byte aligned
+ *   returns LQ_EALIGN; the message names the tensor.  Each tensor takes the form (axis, 16-byte or 4-byte accesses, lanes per
+ *   group) that the single-tensor call takes for the same geometry and alignment: the forward by P and out, the backward by P and dp.
+ * lq_group_batch_forward: ONE launch; out_i is bit-identical to lq_fq_forward_group on the same buffers.
+ * lq_group_batch_backward: ONE launch.  dy: host array [n] of device pointers, indexed like the descriptors (a NULL entry:
+ *   LQ_EINVAL; an entry off the 16-byte grid for a tensor whose backward uses 16-byte accesses: LQ_EALIGN, before any launch).
+ *   grad_scale: host float[n], or NULL for "mask only": then no ds is written at all; when given, every tensor needs a ds.
+ *   dp_i is written for every tensor, and the exact uint32 clip counts, in the scale's shape, go to batch-owned memory that every
+ *   backward rewrites (lq_group_batch_clip_counts gives the address and the element count).  dP, the counts AND ds are
+ *   bit-identical to lq_fq_backward_group on the same buffers with the same grad_scale: a block of the batch runs the same code
+ *   on the same unit of work, so every sum has the single-tensor call's order.
+ * lq_group_batch_workspace_bytes: scratch the backward needs; 0 for every shipped form, and `ws` may then be NULL.  The memory
+ *   contract of lq_group_workspace_bytes applies.
+ * Both passes only enqueue, never allocate, and can be captured.  The library reads no environment.  */
+typedef struct lq_group_desc {
+    const float* P;      /* parameter in MEMORY order, matrix [R][C], C contiguous           */
+    const float* s;      /* scale, [nb][C] (axis 0) or [R][nb] (axis 1), as lq_fq_*_group    */
+    float* out;          /* forward output, required                                         */
+    float* dp;           /* masked dP of the backward, required                              */
+    float* ds;           /* scale gradient in the scale's shape; may be NULL (mask only)     */
+    int64_t R, C, gs;
+    int32_t axis, qmin, qmax;
+} lq_group_desc;
+typedef struct lq_group_batch lq_group_batch;
+int lq_group_batch_create(const lq_group_desc* descs, int n, int rounding, lq_group_batch** out);
+int lq_group_batch_destroy(lq_group_batch* b);
+size_t lq_group_batch_workspace_bytes(const lq_group_batch* b);
+int lq_group_batch_forward(const lq_group_batch* b, void* stream);
+int lq_group_batch_backward(const lq_group_batch* b, const float* const* dy, const float* grad_scale,
+                            void* ws, size_t ws_bytes, void* stream);
+int lq_group_batch_clip_counts(const lq_group_batch* b, int tensor, const uint32_t** dev, int64_t* groups);
+
 /* VALUE of the custom-loss-term penalty for the whole batch (compute_{maxbin,difference,inverse}_penalty,
  *   custom_loss_functions.py:75-116, 161-195, 240-275), the number compute_total_loss adds to the cross-entropy (:47-58).
  * Per-tensor term t_i as in lq_penalty_{maxbin,difference,inverse}_fwd; the model penalty in the reference's order (:102-116):

@@ -120,6 +120,23 @@ SIGNATURES.update({
     "lq_q_unpack": (_c_int, [_c_p, ctypes.c_int32, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p]),
 })
 
+
+
+class GroupDesc(ctypes.Structure):
+    """lq_group_desc of include/lq_hip.h."""
+    _fields_ = [("P", _c_p), ("s", _c_p), ("out", _c_p), ("dp", _c_p), ("ds", _c_p),
+                ("R", _c_i64), ("C", _c_i64), ("gs", _c_i64), ("axis", _c_i32), ("qmin", _c_i32), ("qmax", _c_i32)]
+
+
+SIGNATURES.update({
+    "lq_group_batch_create": (_c_int, [ctypes.POINTER(GroupDesc), _c_int, _c_int, ctypes.POINTER(_c_p)]),
+    "lq_group_batch_destroy": (_c_int, [_c_p]),
+    "lq_group_batch_workspace_bytes": (_c_sz, [_c_p]),
+    "lq_group_batch_forward": (_c_int, [_c_p, _c_p]),
+    "lq_group_batch_backward": (_c_int, [_c_p, ctypes.POINTER(_c_p), ctypes.POINTER(_c_f), _c_p, _c_sz, _c_p]),
+    "lq_group_batch_clip_counts": (_c_int, [_c_p, _c_int, ctypes.POINTER(_c_p), ctypes.POINTER(_c_i64)]),
+})
+
 _lock = threading.RLock()
 
 

@@ -25,7 +25,7 @@ from typing import List, Optional
 import torch
 
 from . import _hip
-from .descriptor import memory_descriptor
+from .descriptor import group_geometry, memory_descriptor
 from .layers import CustomDenseLayer, _ConvBase, custom_layers_of
 from .ops import ROUNDINGS
 
@@ -43,7 +43,8 @@ class _DeviceInts:
 
 class FakeQuantBatch:
     def __init__(self, model_or_layers, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-7, mode: str = "keras",
-                 oihw: bool = True, hwio_out: bool = True, autograd: bool = True, clipped: bool = False):
+                 oihw: bool = True, hwio_out: bool = True, autograd: bool = True, clipped: bool = False,
+                 group_batch: bool = False):
         """``autograd=True``: ``quantize_all()`` is ONE autograd node (2 x tensors inputs, one output per tensor) and everything happens
         inside ``loss.backward()``.  Convenient -- and, for 40 tensors, 0.4-0.6 ms of autograd-engine work per step (an 80-input node,
         40 output wrappers, an AccumulateGrad per parameter that adds into the data-parallel bucket with a launch of its own).
@@ -60,7 +61,13 @@ class FakeQuantBatch:
         ``lq_batch_forward_clip``; the backward is ``lq_batch_backward_clip``, which writes the masked ``dP`` of every tensor into a
         buffer the batch owns (one per tensor, handed to the parameters) and reads 12 bytes per element (P, dy, dP) where the
         unclipped batch reads 8.  Not combined with ``defer_scale_grads`` / ``scale_grads_from_param_grads`` (a masked dP no
-        longer holds the dy of the clipped elements) nor with ``BatchedScaleAdam(fused=True)``."""
+        longer holds the dy of the clipped elements) nor with ``BatchedScaleAdam(fused=True)``.
+        ``group_batch=True`` (opt-in, not together with ``clipped``): a batch of group-wise layers (``orientation="groupwise"``) and
+        their scalar-scale biases on ``lq_group_batch_*``: ``quantize_all()`` is ONE launch and the whole backward -- the masked
+        ``dP`` of every tensor into a buffer the batch owns, ds, the clip counts -- ONE more.  Per tensor the results are the
+        per-tensor group-wise ops' bit for bit, ds included.  A bias is the one-group line ``R = 1, C = numel, axis = 1``; any
+        other one-axis scale belongs to the clipped batch.  One rounding and one rule for all; no loss term, no HWIO storage, no
+        ``defer_scale_grads`` / ``scale_grads_from_param_grads``, no ``BatchedScaleAdam(fused=True)``."""
         layers = custom_layers_of(model_or_layers) if isinstance(model_or_layers, torch.nn.Module) else list(model_or_layers)
         self.layers = layers
         self.autograd = bool(autograd)
@@ -71,6 +78,18 @@ class FakeQuantBatch:
         nested_layers = [getattr(layer, a) for layer in layers for a in ("nested_q_w_layer", "nested_q_k_layer", "nested_q_b_layer")
                          if hasattr(layer, a)]
         self.clipped = bool(clipped)
+        self.group_batch = bool(group_batch)
+        self._ghandle = None
+        if self.group_batch and self.clipped:
+            raise ValueError("group_batch=True together with clipped=True: a batch is either the group batch (group-wise layers and "
+                             "their biases) or the clipped batch (one-axis scales), not both")
+        if not self.group_batch and any(getattr(n, "group_size", None) is not None for n in nested_layers):
+            raise ValueError("FakeQuantBatch over a group-wise layer (group_size): its scale has two non-unit axes, which the "
+                             "(outer, G, inner) descriptor of the default and the clipped batch cannot express; run such a model on "
+                             "the per-tensor path, or opt in to the group batch: FakeQuantBatch(..., group_batch=True)")
+        if self.group_batch:
+            self._init_group_batch(layers, nested_layers, lr, betas, eps, mode)
+            return
         if not self.clipped and any(getattr(n, "q_range", None) is not None for n in nested_layers):
             raise ValueError("FakeQuantBatch over a clipped layer (bits / q_range): the multi-tensor backward hands dy on as dP, "
                              "but a clipped layer's dP is a masked copy of dy; run such a model on the per-tensor path (batched=False), "
@@ -189,7 +208,125 @@ class FakeQuantBatch:
                 self._static_pre = [(layer.__dict__, (None if ik is None else self._leaf[ik], None if ib is None else self._leaf[ib], None))
                                     for layer, ik, ib in self._layer_slots]
 
+    def _init_group_batch(self, layers, nested_layers, lr, betas, eps, mode):
+        """The group batch: entries, buffers and the ``lq_group_batch`` handle (one descriptor per kernel and bias)."""
+        if any(getattr(n, "q_range", None) is None for n in nested_layers):
+            raise ValueError("FakeQuantBatch(group_batch=True) over a layer without a range: group-wise scales exist for the clipped "
+                             "quantizer only, every quantised tensor needs bits / q_range")
+        rules = {n.scale_gradient for n in nested_layers}
+        if len(rules) > 1:
+            raise ValueError(f"one FakeQuantBatch holds one scale-gradient rule, got {sorted(map(str, rules))}")
+        self.ste = "ste" in rules
+        roundings = {n.rounding for n in nested_layers}
+        if len(roundings) > 1:
+            raise ValueError(f"one group FakeQuantBatch holds one rounding, got {sorted(roundings)}")
+        self.rounding = next(iter(roundings), "floor")
+        if any(n.penalty_threshold is not None or n.penalty_rate is not None for n in nested_layers):
+            raise ValueError("FakeQuantBatch(group_batch=True) with a loss term / penalty_threshold: the penalty kernels broadcast "
+                             "one-axis scales; group-wise scales have no loss term")
+        if any(isinstance(layer, _ConvBase) and layer.kernel_storage == "hwio" for layer in layers):
+            raise ValueError('FakeQuantBatch(group_batch=True) with kernel_storage="hwio": the groups are defined in the memory order '
+                             'the convolution consumes; build the model with kernel_storage="oihw"')
+        found = []
+        for layer in layers:
+            if isinstance(layer, _ConvBase):
+                pairs = [(0, layer.kernel, layer.nested_q_k_layer)]
+                if layer._has_bias:
+                    pairs.append((1, layer.b, layer.nested_q_b_layer))
+            elif isinstance(layer, CustomDenseLayer):
+                pairs = [(0, layer.W, layer.nested_q_w_layer), (1, layer.b, layer.nested_q_b_layer)]
+            else:
+                raise TypeError(f"not a custom layer: {type(layer).__name__}")
+            for slot, param, nested in pairs:
+                # geometry first: a tensor the group batch cannot describe is refused before anything touches the device
+                if nested.group_size is not None:
+                    R, C, axis = group_geometry(tuple(param.shape), param.data.stride(), tuple(nested.scale.shape), nested.group_size)
+                    desc = (R, C, axis, int(nested.group_size))
+                elif param.dim() == 1 and param.data.is_contiguous() and nested.scale.numel() == 1:
+                    desc = (1, param.numel(), 1, param.numel())        # a bias with its scalar scale: one line, one group
+                else:
+                    raise ValueError(f"FakeQuantBatch(group_batch=True): a parameter of shape {tuple(param.shape)} with a one-axis scale "
+                                     f"of shape {tuple(nested.scale.shape)} is neither group-wise nor a 1-D parameter with a scalar "
+                                     "scale; one-axis orientations belong to the clipped batch (clipped=True)")
+                found.append((layer, slot, param, nested, desc))
+        for layer, slot, param, nested, desc in found:
+            e = _Entry()
+            e.layer, e.slot, e.param, e.nested, e.desc = layer, slot, param, nested, desc
+            e.scale = nested.scale
+            _hip.require_device_f32(param.data, "parameter")
+            _hip.require_device_f32(nested.scale.data, "scale")
+            e.out = torch.empty_like(param.data)
+            e.dp = torch.empty_like(param.data)                    # the masked dP, in the parameter's element order
+            e.nq = self.ste
+            g = nested.scale.grad
+            if g is not None and g.is_contiguous():
+                e.ds = g                                           # external buffer (bucket view)
+                self._external_grads = True
+            else:
+                e.ds = torch.zeros_like(nested.scale.data)
+            e.m = torch.zeros_like(nested.scale.data)
+            e.v = torch.zeros_like(nested.scale.data)
+            e.out_oihw = e.conv = None
+            self.entries.append(e)
+        if not self.entries:
+            raise ValueError("no custom layers")
+        self.device = self.entries[0].param.device
+        lib = _hip.load()
+        n = len(self.entries)
+        arr = (_hip.GroupDesc * n)()
+        for i, e in enumerate(self.entries):
+            R, C, axis, gs = e.desc
+            arr[i] = _hip.GroupDesc(e.param.data_ptr(), e.scale.data_ptr(), e.out.data_ptr(), e.dp.data_ptr(), e.ds.data_ptr(),
+                                    R, C, gs, axis, int(e.nested.q_range[0]), int(e.nested.q_range[1]))
+        handle = ctypes.c_void_p()
+        _hip.check(lib.lq_group_batch_create(arr, n, ROUNDINGS.index(self.rounding), ctypes.byref(handle)), "lq_group_batch_create")
+        self._ghandle = handle
+        self._handle = None
+        self._ptrs = (ctypes.c_void_p * n)()
+        self._grad_scales = (ctypes.c_float * n)(*[e.nested.grad_scale_value(e.param.numel()) for e in self.entries]) if self.ste else None
+        self.ws = torch.empty(max(1, lib.lq_group_batch_workspace_bytes(handle)), dtype=torch.uint8, device=self.device)
+        self._ws_bytes = lib.lq_group_batch_workspace_bytes(handle)
+        self.hyper = dict(lr=lr, betas=betas, eps=eps, mode=mode)
+        self._data_ptrs = [(e.param.data_ptr(), e.nested.scale.data_ptr()) for e in self.entries]
+        self._flat = [t for e in self.entries for t in (e.param, e.nested.scale)]
+        slots = {}
+        for i, e in enumerate(self.entries):
+            slots.setdefault(id(e.layer), [e.layer, None, None])[1 + e.slot] = i
+        self._layer_slots = list(slots.values())
+        self._oihw_idx, self._oihw_pos = [], {}
+        # the scales' Adam step: one launch over all of them (lq_adam_set_step; the gradients are the batch's ds buffers)
+        cnt = (ctypes.c_int64 * n)(*[e.scale.numel() for e in self.entries])
+        mv = (ctypes.c_float * n)(*[float(c.min_value) if (c := getattr(e.scale, "lq_constraint", None)) is not None else float("-inf")
+                                    for e in self.entries])
+        w = (ctypes.c_void_p * n)(*[e.scale.data_ptr() for e in self.entries])
+        m = (ctypes.c_void_p * n)(*[e.m.data_ptr() for e in self.entries])
+        v = (ctypes.c_void_p * n)(*[e.v.data_ptr() for e in self.entries])
+        adam = ctypes.c_void_p()
+        _hip.check(lib.lq_adam_set_create(w, m, v, cnt, mv, n, ctypes.byref(adam)), "lq_adam_set_create")
+        self._adam_set = adam
+        self._adam_grads = (ctypes.c_void_p * n)(*[e.ds.data_ptr() for e in self.entries])
+        if not self.autograd:
+            self._leaf = [e.out.detach().requires_grad_(True) for e in self.entries]
+            self._leaf_o = [None] * n
+            self._all_leaves = list(self._leaf)
+            self._static_outs = list(self._leaf)
+            self._static_pre = [(layer.__dict__, (None if ik is None else self._leaf[ik], None if ib is None else self._leaf[ib], None))
+                                for layer, ik, ib in self._layer_slots]
+
+    def _refuse_group(self, what: str):
+        if self.group_batch:
+            raise ValueError(f"{what} is not available on FakeQuantBatch(group_batch=True): group-wise scales have no loss term and "
+                             "their dP is a masked copy of dy (no exact data-parallel mode B)")
+
     def __del__(self):
+        for name, destroy in (("_ghandle", "lq_group_batch_destroy"), ("_adam_set", "lq_adam_set_destroy")):
+            h = getattr(self, name, None)
+            if h:
+                try:
+                    getattr(_hip.load(), destroy)(h)
+                except Exception:
+                    pass
+                setattr(self, name, None)
         h = getattr(self, "_handle", None)
         if h:
             try:
@@ -220,7 +357,9 @@ class FakeQuantBatch:
 
     def _forward_call(self):
         lib = _hip.load()
-        if self.clipped:
+        if self.group_batch:
+            _hip.check(lib.lq_group_batch_forward(self._ghandle, _hip.stream_ptr(self.device)), "lq_group_batch_forward")
+        elif self.clipped:
             _hip.check(lib.lq_batch_forward_clip(self._handle, _hip.stream_ptr(self.device)), "lq_batch_forward_clip")
         else:
             _hip.check(lib.lq_batch_forward(self._handle, _hip.stream_ptr(self.device)), "lq_batch_forward")
@@ -272,6 +411,12 @@ class FakeQuantBatch:
         lib = _hip.load()
         opt = self._fused_opt
         sp = _hip.stream_ptr(self.device)
+        if self.group_batch:
+            # ONE launch: dP of every tensor into the batch's buffers, the clip counts, and -- rule "ste" -- ds; mask only otherwise
+            _hip.check(lib.lq_group_batch_backward(self._ghandle, self._ptrs, self._grad_scales,
+                                                   _hip.ptr(self.ws) if self._ws_bytes else None, self._ws_bytes, sp),
+                       "lq_group_batch_backward")
+            return
         if self.clipped:
             # dP of every tensor into the batch's buffers, the clip counts, and -- rule "ste" -- ds; mask only: no grad_scale, ds untouched
             _hip.check(lib.lq_batch_backward_clip(self._handle, self._ptrs, self._grad_scales, _hip.ptr(self.ws), self.ws.numel(), sp),
@@ -339,7 +484,7 @@ class FakeQuantBatch:
             if e.nq:
                 e.scale.grad = e.ds                        # written in place by the kernel: no accumulate launch
             # STE-only: zeros_like(scale) (CL custom_layers.py:62) -- no scale gradient from the op
-        if self.clipped:
+        if self.clipped or self.group_batch:
             return [e.dp for e in self.entries]
         if gathered:
             return [e.dp if i in gathered else d for i, (e, d) in enumerate(zip(self.entries, keep))]
@@ -372,6 +517,8 @@ class FakeQuantBatch:
         return self._launch_and_publish(self._point_at(dys, as_it_stands=gathered), bool(gathered), gathered)
 
     def _refuse_deferred_clip(self):
+        if self.group_batch and self.defer_scale_grads:
+            self._refuse_group("defer_scale_grads")
         if self.clipped and self.defer_scale_grads:
             raise ValueError("a clipped FakeQuantBatch cannot defer its scale gradients (data-parallel mode B): the exchanged dP is a "
                              "masked copy of dy and no longer holds the dy of the clipped elements; use mode A")
@@ -379,13 +526,17 @@ class FakeQuantBatch:
     def clip_counts(self):
         """Clipped batch: per entry, the number of elements the latest backward found outside the range, per group (int32, in
         the shape of the entry's scale; exact).  Copies of the library's device buffers: no synchronisation."""
-        if not self.clipped:
-            raise RuntimeError("clip_counts() belongs to FakeQuantBatch(clipped=True)")
+        if not (self.clipped or self.group_batch):
+            raise RuntimeError("clip_counts() belongs to FakeQuantBatch(clipped=True) and FakeQuantBatch(group_batch=True)")
         lib = _hip.load()
         out = []
         for i, e in enumerate(self.entries):
             dev, groups = ctypes.c_void_p(), ctypes.c_int64()
-            _hip.check(lib.lq_batch_clip_counts(self._handle, i, ctypes.byref(dev), ctypes.byref(groups)), "lq_batch_clip_counts")
+            if self.group_batch:
+                _hip.check(lib.lq_group_batch_clip_counts(self._ghandle, i, ctypes.byref(dev), ctypes.byref(groups)),
+                           "lq_group_batch_clip_counts")
+            else:
+                _hip.check(lib.lq_batch_clip_counts(self._handle, i, ctypes.byref(dev), ctypes.byref(groups)), "lq_batch_clip_counts")
             view = torch.as_tensor(_DeviceInts(dev.value, groups.value), device=self.device)
             out.append(view.clone().reshape(e.scale.shape))
         return out
@@ -395,6 +546,7 @@ class FakeQuantBatch:
         """ds of every nested-quantization tensor from its parameter's CURRENT gradient, in two launches.  After the
         data-parallel all-reduce ``P.grad`` is the global-batch dy (dP == dy, custom_layers.py:118), so this yields the
         single-device large-batch scale gradient, identical on every rank."""
+        self._refuse_group("scale_grads_from_param_grads()")
         if self.clipped:
             raise ValueError("scale_grads_from_param_grads() reads P.grad as dy; a clipped batch's dP is a masked copy of dy, which "
                              "no longer holds the dy of the clipped elements: average ds over the ranks (data-parallel mode A)")
@@ -429,6 +581,7 @@ class FakeQuantBatch:
         ``compute_{maxbin,difference,inverse}_penalty`` (custom_loss_functions.py:75-116, 161-195, 240-275) for the current
         parameters and scales, without a backward pass (lq_batch_penalty_values).  Both are persistent device tensors that
         the next call rewrites in place."""
+        self._refuse_group("penalty_values()")
         self._check_pointers()
         dims, start, terms, penalty = self._value_buffers()
         _hip.check(_hip.load().lq_batch_penalty_values(self._handle, self._KINDS[kind], dims, start, terms.data_ptr(), penalty.data_ptr(),
@@ -447,6 +600,7 @@ class FakeQuantBatch:
         ``values``: also evaluate the penalty (lq_batch_penalty_grads_values: the same gradient launches, then the value
         launches) and return it as a 0-dim device tensor -- a persistent buffer, rewritten in place by every call; the
         per-tensor terms are in ``self._values[2]``.  Default: returns ``None`` and issues the gradient launches only."""
+        self._refuse_group("inject_penalty_grads()")
         lib = _hip.load()
         n = len(self.entries)
         normalizer = float(sum(e.param.numel() for e in self.entries))
@@ -478,6 +632,11 @@ class FakeQuantBatch:
     def scale_adam_step(self, step: Optional[int] = None, step_dev: Optional[torch.Tensor] = None):
         lib = _hip.load()
         h = self.hyper
+        if self.group_batch:
+            _hip.check(lib.lq_adam_set_step(self._adam_set, self._adam_grads, h["lr"], h["betas"][0], h["betas"][1], h["eps"],
+                                            int(step or 0), _hip.ptr(step_dev), _hip.adam_mode(h["mode"]), _hip.stream_ptr(self.device)),
+                       "lq_adam_set_step")
+            return
         _hip.check(lib.lq_batch_scale_adam(self._handle, h["lr"], h["betas"][0], h["betas"][1], h["eps"],
                                            int(step or 0), _hip.ptr(step_dev), _hip.adam_mode(h["mode"]), _hip.stream_ptr(self.device)),
                    "lq_batch_scale_adam")
@@ -517,6 +676,9 @@ class BatchedScaleAdam:
         self.capturable = capturable
         self._applied = False
         if fused:
+            if batch.group_batch:
+                raise ValueError("the fused finalize + Adam launch exists for the nested-quantization vote only: "
+                                 "build BatchedScaleAdam(fused=False) for a group batch")
             if batch.clipped:
                 raise ValueError("the fused finalize + Adam launch exists for the nested-quantization vote only: "
                                  "build BatchedScaleAdam(fused=False) for a clipped batch")

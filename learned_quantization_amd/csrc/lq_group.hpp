@@ -17,6 +17,8 @@
 //
 // Every sum has one fixed order (lane's own rows or elements in ascending order, then slots 0 .. or the butterfly): run-to-run
 // bit-stable, no atomics, no second stage and therefore no workspace.  The forward is the same traversal without dy and sums.
+// The work of one block is a __device__ function of the block's coordinates (group_cols_body, group_rows_body): the kernels here and
+// the multi-tensor k_group_batch (lq_group_batch.hpp) both call it.
 #ifndef LQ_GROUP_HPP_
 #define LQ_GROUP_HPP_
 #include "lq_ops.hpp"
@@ -64,83 +66,96 @@ __device__ __forceinline__ float group_elem(const GroupParams& p, const Ctx& c, 
 constexpr int kGroupColsLanes4 = 16;      // V = 4: 16 lanes x float4 = 64 columns (256 bytes of a row), 16 row slots
 constexpr int kGroupColsLanes1 = 64;      // V = 1: 64 lanes = 64 columns, 4 row slots (one wave each)
 
+// The work of one block of k_group_cols on group g of column tile bx: the single-tensor kernel below and the multi-tensor batch
+// (lq_group_batch.hpp) both run this body, so a tensor's bits do not depend on which launch carried it.  zi / nz: this block's
+// share of the group's rows (forward only: nothing to merge).  sh_sum / sh_cnt: [256 / TX][TX * V] in LDS (backward only).
+// Every thread of the block must call it (two barriers when `reduce`).
 template <bool RNE, bool BWD, int V, int TX>
-__global__ __launch_bounds__(kBlock) void k_group_cols(const GroupParams p) {
+__device__ __forceinline__ void group_cols_body(const GroupParams& p, const int64_t bx, const int64_t g, const int zi, const int nz,
+                                                const bool reduce, double* sh_sum, uint32_t* sh_cnt) {
     constexpr int SLOTS = kBlock / TX;
     constexpr int COLS = TX * V;
-    __shared__ double sh_sum[BWD ? SLOTS : 1][BWD ? COLS : 1];
-    __shared__ uint32_t sh_cnt[BWD ? SLOTS : 1][BWD ? COLS : 1];
     const int lx = (int)threadIdx.x % TX, slot = (int)threadIdx.x / TX;
-    const int64_t c0 = ((int64_t)blockIdx.x * TX + lx) * V;
+    const int64_t c0 = (bx * TX + lx) * V;
     const bool live = c0 < p.C;      // V = 4 runs only with C % 4 == 0: the lane's four columns are inside together
-    const bool reduce = BWD && (p.ds != nullptr || p.clipped != nullptr);
-    for (int64_t g = blockIdx.y; g < p.nb; g += gridDim.y) {
-        Acc acc[V];
+    Acc acc[V];
 #pragma unroll
-        for (int k = 0; k < V; ++k) acc[k] = Acc{0u, 0u, 0.0};
-        if (live) {
-            const int64_t r0 = g * p.gs;
-            const int64_t r1 = (r0 + p.gs < p.R) ? r0 + p.gs : p.R;
-            Ctx c[V];
+    for (int k = 0; k < V; ++k) acc[k] = Acc{0u, 0u, 0.0};
+    if (live) {
+        const int64_t r0 = g * p.gs;
+        const int64_t r1 = (r0 + p.gs < p.R) ? r0 + p.gs : p.R;
+        Ctx c[V];
 #pragma unroll
-            for (int k = 0; k < V; ++k) c[k] = group_ctx<RNE>(p, p.s[g * p.C + c0 + k]);
+        for (int k = 0; k < V; ++k) c[k] = group_ctx<RNE>(p, p.s[g * p.C + c0 + k]);
 #pragma unroll 2
-            // gridDim.z > 1 (forward only: nothing to merge) spreads the rows of a group over that many blocks
-            for (int64_t r = r0 + blockIdx.z * SLOTS + slot; r < r1; r += (int64_t)SLOTS * gridDim.z) {
-                const int64_t i = r * p.C + c0;
-                if constexpr (V == 4) {
-                    const float4 x = *reinterpret_cast<const float4*>(p.P + i);
-                    float4 dy = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if constexpr (BWD) dy = *reinterpret_cast<const float4*>(p.dy + i);
-                    const float4 t = fq_quot4c(x, c);
-                    float4 o;
-                    o.x = group_elem<RNE, BWD>(p, c[0], i + 0, t.x, dy.x, acc[0]);
-                    o.y = group_elem<RNE, BWD>(p, c[1], i + 1, t.y, dy.y, acc[1]);
-                    o.z = group_elem<RNE, BWD>(p, c[2], i + 2, t.z, dy.z, acc[2]);
-                    o.w = group_elem<RNE, BWD>(p, c[3], i + 3, t.w, dy.w, acc[3]);
-                    *reinterpret_cast<float4*>(p.out + i) = o;
-                } else {
-                    const float x = p.P[i];
-                    float dy = 0.f;
-                    if constexpr (BWD) dy = p.dy[i];
-                    p.out[i] = group_elem<RNE, BWD>(p, c[0], i, div_by_uniform(x, c[0]), dy, acc[0]);
-                }
+        // nz > 1 (forward only: nothing to merge) spreads the rows of a group over that many blocks
+        for (int64_t r = r0 + zi * SLOTS + slot; r < r1; r += (int64_t)SLOTS * nz) {
+            const int64_t i = r * p.C + c0;
+            if constexpr (V == 4) {
+                const float4 x = *reinterpret_cast<const float4*>(p.P + i);
+                float4 dy = make_float4(0.f, 0.f, 0.f, 0.f);
+                if constexpr (BWD) dy = *reinterpret_cast<const float4*>(p.dy + i);
+                const float4 t = fq_quot4c(x, c);
+                float4 o;
+                o.x = group_elem<RNE, BWD>(p, c[0], i + 0, t.x, dy.x, acc[0]);
+                o.y = group_elem<RNE, BWD>(p, c[1], i + 1, t.y, dy.y, acc[1]);
+                o.z = group_elem<RNE, BWD>(p, c[2], i + 2, t.z, dy.z, acc[2]);
+                o.w = group_elem<RNE, BWD>(p, c[3], i + 3, t.w, dy.w, acc[3]);
+                *reinterpret_cast<float4*>(p.out + i) = o;
+            } else {
+                const float x = p.P[i];
+                float dy = 0.f;
+                if constexpr (BWD) dy = p.dy[i];
+                p.out[i] = group_elem<RNE, BWD>(p, c[0], i, div_by_uniform(x, c[0]), dy, acc[0]);
             }
         }
-        if constexpr (BWD) {
-            if (reduce) {      // kernel-uniform; the trip count of the group loop is block-uniform: every thread meets the barriers
+    }
+    if constexpr (BWD) {
+        if (reduce) {      // block-uniform: every thread meets the barriers
+#pragma unroll
+            for (int k = 0; k < V; ++k) {
+                sh_sum[slot * COLS + lx * V + k] = acc[k].c;
+                sh_cnt[slot * COLS + lx * V + k] = acc[k].b;
+            }
+            __syncthreads();
+            if (slot == 0 && live) {
 #pragma unroll
                 for (int k = 0; k < V; ++k) {
-                    sh_sum[slot][lx * V + k] = acc[k].c;
-                    sh_cnt[slot][lx * V + k] = acc[k].b;
-                }
-                __syncthreads();
-                if (slot == 0 && live) {
-#pragma unroll
-                    for (int k = 0; k < V; ++k) {
-                        double sum = sh_sum[0][lx * V + k];
-                        uint32_t cnt = sh_cnt[0][lx * V + k];
-                        for (int w = 1; w < SLOTS; ++w) {      // fixed order: slot 0, 1, 2, ...
-                            sum += sh_sum[w][lx * V + k];
-                            cnt += sh_cnt[w][lx * V + k];
-                        }
-                        const int64_t j = g * p.C + c0 + k;
-                        if (p.ds) p.ds[j] = (float)((double)p.k * sum);
-                        if (p.clipped) p.clipped[j] = cnt;
+                    double sum = sh_sum[lx * V + k];
+                    uint32_t cnt = sh_cnt[lx * V + k];
+                    for (int w = 1; w < SLOTS; ++w) {      // fixed order: slot 0, 1, 2, ...
+                        sum += sh_sum[w * COLS + lx * V + k];
+                        cnt += sh_cnt[w * COLS + lx * V + k];
                     }
+                    const int64_t j = g * p.C + c0 + k;
+                    if (p.ds) p.ds[j] = (float)((double)p.k * sum);
+                    if (p.clipped) p.clipped[j] = cnt;
                 }
-                __syncthreads();
             }
+            __syncthreads();
         }
     }
 }
 
+template <bool RNE, bool BWD, int V, int TX>
+__global__ __launch_bounds__(kBlock) void k_group_cols(const GroupParams p) {
+    constexpr int SLOTS = kBlock / TX;
+    constexpr int COLS = TX * V;
+    __shared__ double sh_sum[BWD ? SLOTS * COLS : 1];
+    __shared__ uint32_t sh_cnt[BWD ? SLOTS * COLS : 1];
+    const bool reduce = BWD && (p.ds != nullptr || p.clipped != nullptr);      // kernel-uniform
+    // the trip count of the group loop is block-uniform
+    for (int64_t g = blockIdx.y; g < p.nb; g += gridDim.y)
+        group_cols_body<RNE, BWD, V, TX>(p, (int64_t)blockIdx.x, g, (int)blockIdx.z, (int)gridDim.z, reduce, sh_sum, sh_cnt);
+}
+
+// The work of block `blk` of k_group_rows: kBlock >> log_team (row, group) pairs, a team of 1 << log_team lanes each.  No barrier.
 template <bool RNE, bool BWD, int V>
-__global__ __launch_bounds__(kBlock) void k_group_rows(const GroupParams p, const int log_team) {
+__device__ __forceinline__ void group_rows_body(const GroupParams& p, const int log_team, const uint32_t blk) {
     const int T = 1 << log_team;
     const int lt = (int)threadIdx.x & (T - 1);
     const uint32_t pairs = (uint32_t)p.R * (uint32_t)p.nb;      // <= R * C < 2^31
-    const uint32_t pair = blockIdx.x * (uint32_t)(kBlock >> log_team) + (threadIdx.x >> log_team);
+    const uint32_t pair = blk * (uint32_t)(kBlock >> log_team) + (threadIdx.x >> log_team);
     const bool live = pair < pairs;
     Acc acc = Acc{0u, 0u, 0.0};
     if (live) {
@@ -171,7 +186,7 @@ __global__ __launch_bounds__(kBlock) void k_group_rows(const GroupParams p, cons
         }
     }
     if constexpr (BWD) {
-        if (p.ds != nullptr || p.clipped != nullptr) {      // kernel-uniform
+        if (p.ds != nullptr || p.clipped != nullptr) {      // block-uniform
             double sum = acc.c;
             uint32_t cnt = acc.b;
             for (int off = T >> 1; off > 0; off >>= 1) {      // fixed butterfly inside the aligned team; every lane of the wave takes part
@@ -184,6 +199,11 @@ __global__ __launch_bounds__(kBlock) void k_group_rows(const GroupParams p, cons
             }
         }
     }
+}
+
+template <bool RNE, bool BWD, int V>
+__global__ __launch_bounds__(kBlock) void k_group_rows(const GroupParams p, const int log_team) {
+    group_rows_body<RNE, BWD, V>(p, log_team, blockIdx.x);
 }
 
 }  // namespace lq

@@ -50,6 +50,7 @@
 #include "lq_stream2.hpp"
 #include "lq_pack.hpp"
 #include "lq_group.hpp"
+#include "lq_group_batch.hpp"
 
 namespace lq {
 
@@ -1357,23 +1358,40 @@ static GroupParams group_params(const float* P, const float* s, int32_t qmin, in
     return p;
 }
 
+// The launch shape of a group-wise tensor; the single-tensor launch and the batch's task table (lq_group_batch_create) both ask here,
+// which keeps a tensor's form and team width the same on either path.
+// Column forms: blocks that share the rows of a group in the forward.  A block per (column tile, group) leaves the chip half empty
+// on weight-sized tensors; `groups_y` is the group extent of the grid.
+static int group_cols_row_split(const GroupParams& p, bool vec, int64_t tiles_x, int64_t groups_y) {
+    const int slots = kBlock / (vec ? kGroupColsLanes4 : kGroupColsLanes1);
+    int nz = 1;
+    while (nz < 4 && tiles_x * groups_y * nz < 2048 && (int64_t)slots * nz * 4 <= p.gs) nz *= 2;
+    return nz;
+}
+static int64_t group_cols_tiles(const GroupParams& p, bool vec) {
+    const int cols = vec ? kGroupColsLanes4 * 4 : kGroupColsLanes1;
+    return (p.C + cols - 1) / cols;
+}
+// Row forms: log2 of the lanes per (row, group) pair: about four accesses per lane
+static int group_rows_log_team(const GroupParams& p, bool vec) {
+    const int64_t items = (p.gs + (vec ? 3 : 0)) / (vec ? 4 : 1);
+    int log_team = 0;
+    while (log_team < 6 && ((int64_t)4 << log_team) < items) ++log_team;
+    return log_team;
+}
+static bool group_vec_ok(const GroupParams& p, int axis) { return p.C % 4 == 0 && (axis == 0 || p.gs % 4 == 0); }
+
 extern "C++" {      // a template inside the C-linkage block
 template <bool RNE, bool BWD>
 static int launch_group(const GroupParams& p, int axis, bool vec, hipStream_t st) {
     if (axis == 0) {
-        const int cols = vec ? kGroupColsLanes4 * 4 : kGroupColsLanes1;
-        dim3 grid((unsigned)((p.C + cols - 1) / cols), (unsigned)std::min<int32_t>(p.nb, 32768));
-        if (!BWD) {      // a block per (column tile, group) leaves the chip half empty on weight-sized tensors: split the rows of a group
-            const int slots = kBlock / (vec ? kGroupColsLanes4 : kGroupColsLanes1);
-            while (grid.z < 4 && (int64_t)grid.x * grid.y * grid.z < 2048 && (int64_t)slots * grid.z * 4 <= p.gs) grid.z *= 2;
-        }
+        dim3 grid((unsigned)group_cols_tiles(p, vec), (unsigned)std::min<int32_t>(p.nb, 32768));
+        if (!BWD) grid.z = (unsigned)group_cols_row_split(p, vec, grid.x, grid.y);
         if (vec) hipLaunchKernelGGL((k_group_cols<RNE, BWD, 4, kGroupColsLanes4>), grid, dim3(kBlock), 0, st, p);
         else hipLaunchKernelGGL((k_group_cols<RNE, BWD, 1, kGroupColsLanes1>), grid, dim3(kBlock), 0, st, p);
         return check_hip("group-wise column launch");
     }
-    const int64_t items = (p.gs + (vec ? 3 : 0)) / (vec ? 4 : 1);      // accesses per group; about four per lane
-    int log_team = 0;
-    while (log_team < 6 && ((int64_t)4 << log_team) < items) ++log_team;
+    const int log_team = group_rows_log_team(p, vec);
     const int64_t pairs = (int64_t)p.R * p.nb, per_block = kBlock >> log_team;
     const dim3 grid((unsigned)((pairs + per_block - 1) / per_block));
     if (vec) hipLaunchKernelGGL((k_group_rows<RNE, BWD, 4>), grid, dim3(kBlock), 0, st, p, log_team);
@@ -1404,7 +1422,7 @@ int lq_fq_forward_group(const float* P, const float* s, float* out, void* q, int
     p.out = out;
     p.q = q;
     p.q_dtype = q_dtype;
-    const bool vec = C % 4 == 0 && (axis == 0 || p.gs % 4 == 0) && aligned(P, 16) && aligned(out, 16);
+    const bool vec = group_vec_ok(p, axis) && aligned(P, 16) && aligned(out, 16);
     if (rounding == LQ_ROUND_NEAREST_EVEN) return launch_group<true, false>(p, axis, vec, (hipStream_t)stream);
     return launch_group<false, false>(p, axis, vec, (hipStream_t)stream);
 }
@@ -1430,7 +1448,7 @@ int lq_fq_backward_group(const float* P, const float* s, const float* dy, int32_
     p.k = grad_scale;
     p.ds = ds;
     p.clipped = clipped;
-    const bool vec = C % 4 == 0 && (axis == 0 || p.gs % 4 == 0) && aligned(P, 16) && aligned(dy, 16) && aligned(dP, 16);
+    const bool vec = group_vec_ok(p, axis) && aligned(P, 16) && aligned(dy, 16) && aligned(dP, 16);
     if (rounding == LQ_ROUND_NEAREST_EVEN) return launch_group<true, true>(p, axis, vec, (hipStream_t)stream);
     return launch_group<false, true>(p, axis, vec, (hipStream_t)stream);
 }
@@ -2531,6 +2549,229 @@ int lq_batch_clip_counts(const lq_batch* b, int tensor, const uint32_t** dev, in
         return LQ_OK;
     }
     return fail(LQ_EINVAL, "%s: tensor %d is not in the clipped tables", fn, tensor);
+}
+
+// ------------------------------------------------------------------------------------------
+//  lq_group_batch: group-wise tensors, one launch per pass (lq_group_batch.hpp)
+// ------------------------------------------------------------------------------------------
+}  // extern "C"
+
+struct lq_group_table {
+    std::vector<lq::GroupTask> h;
+    std::vector<int> index;               // table position -> descriptor index (tasks are ordered by work per block)
+    lq::GroupTask* d = nullptr;
+    uint32_t* block_task_d = nullptr;     // [blocks] task of every block
+    uint32_t blocks = 0;
+};
+
+struct lq_group_batch {
+    int n = 0;
+    int rounding = 0;
+    lq_group_table fwd, bwd;
+    std::vector<const uint32_t*> counts;  // per descriptor: its slice of counts_d
+    std::vector<int64_t> groups;          // per descriptor: scale elements
+    uint32_t* counts_d = nullptr;
+};
+
+namespace lq {
+
+// One task: the form lq_fq_*_group picks for this geometry and alignment, and its blocks (left in first_block until the table is ordered)
+static void fill_group_task(GroupTask& t, const GroupParams& p, int axis, bool vec, bool bwd) {
+    memset(&t, 0, sizeof(t));
+    t.p = p;
+    t.nbx = 1;
+    t.nz = 1;
+    if (axis == 0) {
+        t.form = vec ? GROUP_COLS4 : GROUP_COLS1;
+        t.nbx = (uint32_t)group_cols_tiles(p, vec);
+        if (!bwd) t.nz = (uint32_t)group_cols_row_split(p, vec, t.nbx, p.nb);
+        t.first_block = t.nbx * (uint32_t)p.nb * t.nz;      // tiles * groups <= R * C < 2^31 elements, nz <= 4 only below 2048 blocks
+    } else {
+        t.form = vec ? GROUP_ROWS4 : GROUP_ROWS1;
+        t.log_team = group_rows_log_team(p, vec);
+        const int64_t pairs = (int64_t)p.R * p.nb, per_block = kBlock >> t.log_team;
+        t.first_block = (uint32_t)((pairs + per_block - 1) / per_block);
+    }
+}
+
+// Orders the table so that the heaviest units start first (as finish_table), assigns the block prefix and uploads it
+static int finish_group_table(lq_group_table& tb) {
+    const size_t n = tb.h.size();
+    std::vector<size_t> order(n);
+    for (size_t i = 0; i < n; ++i) order[i] = i;
+    auto weight = [&](size_t i) { return (double)tb.h[i].p.R * (double)tb.h[i].p.C / (double)tb.h[i].first_block; };      // elements per block
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return weight(a) > weight(b); });
+    std::vector<GroupTask> h2(n);
+    std::vector<int> idx2(n);
+    uint64_t bp = 0;
+    for (size_t k = 0; k < n; ++k) {
+        h2[k] = tb.h[order[k]];
+        idx2[k] = tb.index[order[k]];
+        const uint32_t nb = h2[k].first_block;
+        h2[k].first_block = (uint32_t)bp;
+        bp += nb;
+        if (bp > 0x7fffffffull) return fail(LQ_EINVAL, "lq_group_batch_create: too many blocks");
+    }
+    tb.h.swap(h2);
+    tb.index.swap(idx2);
+    tb.blocks = (uint32_t)bp;
+    std::vector<uint32_t> bt((size_t)bp);
+    for (size_t k = 0; k < n; ++k) {
+        const uint64_t end = k + 1 < n ? tb.h[k + 1].first_block : bp;
+        for (uint64_t b = tb.h[k].first_block; b < end; ++b) bt[b] = (uint32_t)k;
+    }
+    hipError_t e = hipMalloc(&tb.block_task_d, bt.size() * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemcpy(tb.block_task_d, bt.data(), bt.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc(&tb.d, n * sizeof(GroupTask));
+    if (e != hipSuccess) return fail(LQ_EHIP, "lq_group_batch_create: %s", hipGetErrorString(e));
+    return LQ_OK;
+}
+
+static void free_group_table(lq_group_table& tb) {
+    if (tb.d) (void)hipFree(tb.d);
+    if (tb.block_task_d) (void)hipFree(tb.block_task_d);
+    tb.d = nullptr;
+    tb.block_task_d = nullptr;
+}
+
+}  // namespace lq
+
+extern "C" {
+
+int lq_group_batch_create(const lq_group_desc* descs, int n, int rounding, lq_group_batch** out) {
+    const char* fn = "lq_group_batch_create";
+    if (!out) return fail(LQ_EINVAL, "%s: out is NULL", fn);
+    *out = nullptr;
+    if (!descs) return fail(LQ_EINVAL, "%s: descs is NULL", fn);
+    if (n < 1 || n > kBatchMax) return fail(LQ_EINVAL, "%s: %d tensors (1 .. %d)", fn, n, kBatchMax);
+    int rc = check_rounding(fn, rounding);
+    if (rc) return rc;
+    // everything is validated before the first HIP call
+    for (int i = 0; i < n; ++i) {
+        const lq_group_desc& d = descs[i];
+        char who[64];
+        snprintf(who, sizeof(who), "%s: tensor %d", fn, i);
+        if (!d.P || !d.s || !d.out || !d.dp)
+            return fail(LQ_EINVAL, "%s: %s is NULL", who, !d.P ? "P" : (!d.s ? "s" : (!d.out ? "out" : "dp")));
+        if (!aligned(d.P, 4) || !aligned(d.s, 4) || !aligned(d.out, 4) || !aligned(d.dp, 4) || (d.ds && !aligned(d.ds, 4)))
+            return fail(LQ_EALIGN, "%s: P, s, out, dp and ds must be 4-byte aligned", who);
+        if ((rc = check_group(who, d.R, d.C, d.axis, d.gs))) return rc;
+        if ((rc = check_clip_range(who, d.qmin, d.qmax))) return rc;
+    }
+    lq_group_batch* b = new (std::nothrow) lq_group_batch();
+    if (!b) return fail(LQ_EHIP, "%s: out of host memory", fn);
+    b->n = n;
+    b->rounding = rounding;
+    b->counts.resize(n);
+    b->groups.resize(n);
+    int64_t total = 0;
+    std::vector<int64_t> first(n);
+    for (int i = 0; i < n; ++i) {
+        const lq_group_desc& d = descs[i];
+        const GroupParams p = group_params(d.P, d.s, d.qmin, d.qmax, d.R, d.C, d.axis, d.gs);
+        first[i] = total;
+        b->groups[i] = d.axis == 0 ? (int64_t)p.nb * p.C : (int64_t)p.R * p.nb;
+        total += b->groups[i];
+    }
+    if (hipMalloc(&b->counts_d, (size_t)total * sizeof(uint32_t)) != hipSuccess) rc = fail(LQ_EHIP, "%s: out of device memory", fn);
+    else if (hipMemset(b->counts_d, 0, (size_t)total * sizeof(uint32_t)) != hipSuccess) rc = fail(LQ_EHIP, "%s: hipMemset failed", fn);
+    for (int i = 0; i < n && !rc; ++i) {
+        const lq_group_desc& d = descs[i];
+        b->counts[i] = b->counts_d + first[i];
+        GroupParams p = group_params(d.P, d.s, d.qmin, d.qmax, d.R, d.C, d.axis, d.gs);
+        GroupTask t;
+        p.out = d.out;
+        fill_group_task(t, p, d.axis, group_vec_ok(p, d.axis) && aligned(d.P, 16) && aligned(d.out, 16), false);
+        b->fwd.h.push_back(t);
+        b->fwd.index.push_back(i);
+        p.out = d.dp;            // dy and grad_scale arrive with the call
+        p.ds = d.ds;
+        p.clipped = b->counts_d + first[i];
+        fill_group_task(t, p, d.axis, group_vec_ok(p, d.axis) && aligned(d.P, 16) && aligned(d.dp, 16), true);
+        b->bwd.h.push_back(t);
+        b->bwd.index.push_back(i);
+    }
+    for (lq_group_table* tb : {&b->fwd, &b->bwd}) {
+        if (!rc) rc = finish_group_table(*tb);
+        if (!rc && hipMemcpy(tb->d, tb->h.data(), tb->h.size() * sizeof(GroupTask), hipMemcpyHostToDevice) != hipSuccess)
+            rc = fail(LQ_EHIP, "%s: table upload failed", fn);
+    }
+    if (rc) {
+        (void)lq_group_batch_destroy(b);
+        return rc;
+    }
+    *out = b;
+    return LQ_OK;
+}
+
+int lq_group_batch_destroy(lq_group_batch* b) {
+    if (!b) return fail(LQ_EINVAL, "lq_group_batch_destroy: NULL batch");
+    free_group_table(b->fwd);
+    free_group_table(b->bwd);
+    if (b->counts_d) (void)hipFree(b->counts_d);
+    delete b;
+    return LQ_OK;
+}
+
+size_t lq_group_batch_workspace_bytes(const lq_group_batch* b) {
+    (void)b;
+    return 0;      // every form is single-stage (lq_group.hpp)
+}
+
+int lq_group_batch_forward(const lq_group_batch* b, void* stream) {
+    if (!b) return fail(LQ_EINVAL, "lq_group_batch_forward: NULL batch");
+    PtrPack pk;
+    CoefPack cf;
+    memset(&pk, 0, sizeof(pk));
+    memset(&cf, 0, sizeof(cf));
+    const lq_group_table& tb = b->fwd;
+    hipStream_t st = (hipStream_t)stream;
+    if (b->rounding == LQ_ROUND_NEAREST_EVEN)
+        hipLaunchKernelGGL((k_group_batch<true, false>), dim3(tb.blocks), dim3(kBlock), 0, st, tb.d, tb.block_task_d, pk, cf, 0);
+    else
+        hipLaunchKernelGGL((k_group_batch<false, false>), dim3(tb.blocks), dim3(kBlock), 0, st, tb.d, tb.block_task_d, pk, cf, 0);
+    return check_hip("group batch forward launch");
+}
+
+int lq_group_batch_backward(const lq_group_batch* b, const float* const* dy, const float* grad_scale, void* ws, size_t ws_bytes,
+                            void* stream) {
+    const char* fn = "lq_group_batch_backward";
+    (void)ws; (void)ws_bytes;      // lq_group_batch_workspace_bytes() == 0: ws may be NULL and is never touched
+    if (!b) return fail(LQ_EINVAL, "%s: NULL batch", fn);
+    if (!dy) return fail(LQ_EINVAL, "%s: dy is NULL", fn);
+    PtrPack pk;
+    CoefPack cf;
+    memset(&pk, 0, sizeof(pk));
+    memset(&cf, 0, sizeof(cf));
+    const lq_group_table& tb = b->bwd;
+    for (size_t k = 0; k < tb.h.size(); ++k) {
+        const GroupTask& t = tb.h[k];
+        const int i = tb.index[k];
+        const float* d = dy[i];
+        if (!d) return fail(LQ_EINVAL, "%s: no upstream gradient for tensor %d", fn, i);
+        if (!aligned(d, 4)) return fail(LQ_EALIGN, "%s: dy of tensor %d is not 4-byte aligned", fn, i);
+        if ((t.form == GROUP_COLS4 || t.form == GROUP_ROWS4) && !aligned(d, 16))
+            return fail(LQ_EALIGN, "%s: tensor %d is traversed with 16-byte accesses but its dy is not 16-byte aligned", fn, i);
+        if (grad_scale && !t.p.ds) return fail(LQ_EINVAL, "%s: tensor %d has no ds buffer (pass grad_scale = NULL for the mask alone)", fn, i);
+        pk.dy[k] = d;
+        cf.c[k] = grad_scale ? grad_scale[i] : 0.0f;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int mask_only = grad_scale ? 0 : 1;
+    if (b->rounding == LQ_ROUND_NEAREST_EVEN)
+        hipLaunchKernelGGL((k_group_batch<true, true>), dim3(tb.blocks), dim3(kBlock), 0, st, tb.d, tb.block_task_d, pk, cf, mask_only);
+    else
+        hipLaunchKernelGGL((k_group_batch<false, true>), dim3(tb.blocks), dim3(kBlock), 0, st, tb.d, tb.block_task_d, pk, cf, mask_only);
+    return check_hip("group batch backward launch");
+}
+
+int lq_group_batch_clip_counts(const lq_group_batch* b, int tensor, const uint32_t** dev, int64_t* groups) {
+    const char* fn = "lq_group_batch_clip_counts";
+    if (!b || !dev || !groups) return fail(LQ_EINVAL, "%s: NULL argument", fn);
+    if (tensor < 0 || tensor >= b->n) return fail(LQ_EINVAL, "%s: tensor %d of %d", fn, tensor, b->n);
+    *dev = b->counts[tensor];
+    *groups = b->groups[tensor];
+    return LQ_OK;
 }
 
 int lq_loss_log_append(const float* scce_dev, const float* penalty_dev, float rate, float* rows_dev, int64_t capacity,

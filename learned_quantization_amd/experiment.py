@@ -136,6 +136,8 @@ def build_parser():
     ap.add_argument("--batched", action="store_true")
     ap.add_argument("--clipped-batch", action="store_true",
                     help="with --batched and --bits: run the clipped layers in the multi-tensor batch (opt-in, see train.py)")
+    ap.add_argument("--group-batch", action="store_true",
+                    help="with --batched, --bits and --group-size: run the group-wise layers in the group batch (opt-in, see train.py)")
     ap.add_argument("--loss-values", action="store_true",
                     help="with --custom_loss: loss and val_loss include rate * penalty (what Keras reports for compute_total_loss) "
                          "and custom_losses/*.log get one line per step, from a device-side log flushed at every epoch end")
@@ -164,7 +166,8 @@ def main(argv=None):
     tr = Trainer(args.config, mode, value, args.orientation, args.custom_loss, lr=args.lr, seed=args.seed, device=dev,
                  log_dir=log_dir, batched=args.batched, loss_values=args.loss_values,
                  loss_log_capacity=max(4096, args.steps_per_epoch), bits=args.bits, rounding=args.rounding,
-                 clipped_batch=args.clipped_batch, group_size=args.group_size)
+                 clipped_batch=args.clipped_batch, group_size=args.group_size,
+                 group_batch=args.group_batch)
     if args.training == "post_training":
         if args.config != "mnist" or not args.baseline_weights:
             raise SystemExit("post_training needs --config mnist --baseline-weights <npz with W1,b1,W2,b2> "

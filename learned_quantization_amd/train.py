@@ -73,9 +73,12 @@ class Trainer:
                  bucket_mb: float = 25.0, overlap: bool = True, graph_collectives: Optional[bool] = None,
                  force_collectives: bool = False, kernel_storage: str = "oihw", loss_values: bool = False,
                  loss_log_capacity: int = 4096, grad_scale=None, bits=None, signed=True, q_range=None, rounding="floor",
-                 clipped_batch: bool = False, group_size=None):
+                 clipped_batch: bool = False, group_size=None, group_batch: bool = False):
         """``group_size`` (with ``bits`` / ``q_range`` and mode "ste"; eager, graphed and data-parallel mode "A"): group-wise scales
         for every quantised kernel (models.build_model); it replaces ``orientation``.
+        ``group_batch`` (opt-in, with ``batched=True`` and ``group_size``; mode "ste", eager, graphed, data-parallel mode "A"): the
+        group-wise kernels and their biases run in the group batch (``FakeQuantBatch(group_batch=True)``: one forward launch and
+        one backward launch for the whole model, results those of the per-tensor path bit for bit for the kernels).
         ``clipped_batch`` (opt-in, with ``batched=True`` and a range): the clipped layers run in the multi-tensor batch
         (``FakeQuantBatch(clipped=True)``: one forward launch, two backward launches; the batch owns one dP buffer per tensor
         and its backward moves 12 bytes per element instead of 8).  Everything else about a range stays: modes "cl", "ste",
@@ -98,9 +101,10 @@ class Trainer:
         self.group_size = group_size
         if group_size is not None:
             check_group_mode(mode, bits is not None or q_range is not None)
-            if batched:
+            if batched and (not group_batch or clipped_batch):
                 raise ValueError("group_size with batched=True: the multi-tensor batch describes every tensor by one-axis "
-                                 "(outer, G, inner) scales; group-wise scales run on the per-tensor path")
+                                 "(outer, G, inner) scales; group-wise scales run on the per-tensor path, or opt in to the group "
+                                 "batch (group_batch=True / --group-batch, without clipped_batch)")
             if ddp_mode == "B":
                 raise ValueError("group_size with ddp_mode 'B': it recomputes ds from the all-reduced dP, which no longer holds the "
                                  "dy of the clipped elements; use ddp_mode 'A'")
@@ -118,7 +122,7 @@ class Trainer:
             if ddp_mode == "B":
                 raise ValueError("bits / q_range with ddp_mode 'B': it recomputes ds from the all-reduced dP, which no longer holds "
                                  "the dy of the clipped elements; use ddp_mode 'A'")
-            if batched and not clipped_batch:
+            if batched and not clipped_batch and not group_batch:
                 raise ValueError("bits / q_range with batched=True: the multi-tensor backward hands dy on as dP, but a clipped "
                                  "layer's dP is a masked copy of dy; use the per-tensor path, or opt in to the clipped batch "
                                  "(clipped_batch=True / --clipped-batch), which owns a dP buffer per tensor")
@@ -126,7 +130,12 @@ class Trainer:
             raise ValueError("clipped_batch=True belongs to batched=True")
         if clipped_batch and self.q_range is None:
             raise ValueError("clipped_batch=True needs bits / q_range: an unclipped model runs the default batch")
+        if group_batch and not batched:
+            raise ValueError("group_batch=True belongs to batched=True")
+        if group_batch and group_size is None:
+            raise ValueError("group_batch=True needs group_size: a model of one-axis scales runs the default or the clipped batch")
         self.clipped_batch = bool(clipped_batch)
+        self.group_batch = bool(group_batch)
         # conv kernels shaped HWIO like the reference's, stored in the order MIOpen consumes (layers.py kernel_storage): the
         # fake-quantised kernel goes to the convolution as written and its weight gradient is dP
         self.model = build_model(config, mode=mode, value=value, seed=seed, orientation=orientation, device=self.device,
@@ -166,11 +175,12 @@ class Trainer:
                 self.dp.zero_grad()          # makes scale.grad the bucket views the batch will write into
             # the convolutions consume the OIHW companions only; autograd=False: the fake-quantised tensors are leaves and
             # _backward_phase calls finish_backward() itself (0.4-0.6 ms less autograd-engine work per eager step for 40 tensors)
-            self.batch = FakeQuantBatch(self.model, lr=lr, hwio_out=False, autograd=False, clipped=self.clipped_batch)
+            self.batch = FakeQuantBatch(self.model, lr=lr, hwio_out=False, autograd=False, clipped=self.clipped_batch,
+                                        group_batch=self.group_batch)
             # nothing touches ds between its computation and the scales' update when there is no loss term and ds is not
             # exchanged (one process, or exact mode B): the finalize then applies the Adam step itself (one launch fewer)
             # (the fused finalize + Adam is the nested-quantization pass's: not for the straight-through modes)
-            fused = self.loss_obj is None and (self.dp is None or ddp_mode == "B") and not ste and not self.clipped_batch
+            fused = self.loss_obj is None and (self.dp is None or ddp_mode == "B") and not ste and not self.clipped_batch and not self.group_batch
             self.scale_opt = BatchedScaleAdam(self.batch, capturable=graph, fused=fused)
             if self.dp is not None:
                 self.dp.attach_batch(self.batch)
@@ -443,6 +453,9 @@ def build_parser():
     ap.add_argument("--clipped-batch", action="store_true",
                     help="with --batched and --bits: run the clipped layers in the multi-tensor batch (opt-in: it owns a dP buffer per "
                          "tensor and its backward moves 12 bytes per element instead of 8)")
+    ap.add_argument("--group-batch", action="store_true",
+                    help="with --batched, --bits and --group-size: run the group-wise layers and their biases in the group batch "
+                         "(opt-in: one forward and one backward launch for the whole model)")
     ap.add_argument("--loss-values", action="store_true",
                     help="modes cl / nqcl: evaluate the penalty with its gradients, report mean(SCCE) + rate * penalty and keep the "
                          "reference's per-step loss logs in a device buffer (written at the end)")
@@ -492,7 +505,7 @@ def main(argv=None):
                  grad_scale=(None if args.grad_scale is None else
                              (args.grad_scale if args.grad_scale == "rsqrt_group" else float(args.grad_scale))),
                  bits=args.bits, signed=not args.unsigned, rounding=args.rounding, clipped_batch=args.clipped_batch,
-                 group_size=args.group_size)
+                 group_size=args.group_size, group_batch=args.group_batch)
     do_step = tr.step_graphed if args.graph else tr.step
     g = torch.Generator(device=dev).manual_seed(args.seed + rank)
     batches = [synthetic_batch(args.config, args.batch, dev, g) for _ in range(4)]
@@ -526,6 +539,7 @@ def main(argv=None):
             "hipgraph": bool(args.graph), "graph_collectives": bool(tr.graph_collectives and args.graph and use_dist),
             **({"graph_note": tr.graph_note} if tr.graph_note else {}), "batched": bool(args.batched),
             **({"clipped_batch": True} if args.clipped_batch else {}),
+            **({"group_batch": True} if args.group_batch else {}),
             "backend": (args.backend if use_dist else None),
             "channels_last": bool(args.channels_last), "kernel_storage": args.kernel_storage,
             **({"q_range": list(tr.q_range)} if tr.q_range else {}),

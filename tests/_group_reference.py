@@ -74,6 +74,23 @@ def mixed_share(ref, R, C, axis, gs):
     return float(np.mean((n_in > 0) & (ref["clipped"] > 0)))
 
 
+def check_condition(ref, R, C, axis, gs, what):
+    """On the REFERENCE, before any kernel runs: the case clips a sizeable share and leaves a sizeable share inside, group by group."""
+    length = R if axis == 0 else C
+    n = ref["inside"].size
+    clipped, inside = int(ref["clipped"].sum()), int(ref["inside"].sum())
+    assert clipped + inside == n
+    assert clipped >= 0.1 * n and inside >= 0.1 * n, f"{what}: {clipped} clipped, {inside} inside of {n}"
+    if min(gs, length) >= 8:
+        sizes = np.minimum(gs, length - np.arange(ref["clipped"].shape[axis]) * min(gs, length))
+        big = np.broadcast_to(sizes.reshape((-1, 1) if axis == 0 else (1, -1)) >= 8, ref["clipped"].shape)
+        n_in = sizes.reshape((-1, 1) if axis == 0 else (1, -1)) - ref["clipped"]
+        mixed = (ref["clipped"] > 0) & (n_in > 0)
+        share = float(mixed[big].mean())
+        assert share >= 0.9, f"{what}: only {share:.3f} of the groups of >= 8 elements hold both clipped and inside elements"
+        assert abs(mixed_share(ref, R, C, axis, gs) - float(mixed.mean())) < 1e-12
+
+
 def make_case(seed, R, C, axis, gs):
     """The inputs of the GPU tests: per-group s = 2^U(-9, -5), P = N(0, 1) * 8 s, dy = N(0, 1)."""
     rng = np.random.default_rng(seed)

@@ -25,7 +25,8 @@ sys.path.insert(0, os.path.dirname(__file__))
 from _arena import Arena                                                                  # noqa: E402
 from _bounds import assert_within_terms, stable_seed                                      # noqa: E402
 from _clip_reference import bits_equal, edge_table                                        # noqa: E402
-from _group_reference import expand_scale, group_reference, make_case, mixed_share, scale_shape      # noqa: E402
+from _group_reference import check_condition as _check_condition                          # noqa: E402
+from _group_reference import expand_scale, group_reference, make_case, scale_shape        # noqa: E402
 
 pytestmark = pytest.mark.gpu
 LIM = 1 << 24
@@ -57,23 +58,6 @@ def _case(R, C, axis, gs, qmin=-8, qmax=7, rounding="floor", k=1.0):
         _check_condition(ref, R, C, axis, gs, f"{key}")
         _CASES[key] = (P, s, dy, ref)
     return _CASES[key]
-
-
-def _check_condition(ref, R, C, axis, gs, what):
-    """On the REFERENCE, before any kernel runs: the case clips a sizeable share and leaves a sizeable share inside, group by group."""
-    length = R if axis == 0 else C
-    n = ref["inside"].size
-    clipped, inside = int(ref["clipped"].sum()), int(ref["inside"].sum())
-    assert clipped + inside == n
-    assert clipped >= 0.1 * n and inside >= 0.1 * n, f"{what}: {clipped} clipped, {inside} inside of {n}"
-    if min(gs, length) >= 8:
-        sizes = np.minimum(gs, length - np.arange(ref["clipped"].shape[axis]) * min(gs, length))
-        big = np.broadcast_to(sizes.reshape((-1, 1) if axis == 0 else (1, -1)) >= 8, ref["clipped"].shape)
-        n_in = sizes.reshape((-1, 1) if axis == 0 else (1, -1)) - ref["clipped"]
-        mixed = (ref["clipped"] > 0) & (n_in > 0)
-        share = float(mixed[big].mean())
-        assert share >= 0.9, f"{what}: only {share:.3f} of the groups of >= 8 elements hold both clipped and inside elements"
-        assert abs(mixed_share(ref, R, C, axis, gs) - float(mixed.mean())) < 1e-12
 
 
 def _ratio(got, ref, terms):

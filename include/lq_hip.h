@@ -176,6 +176,37 @@ int lq_fq_backward_group(const float* P, const float* s, const float* dy, int32_
                          float* dP, float* ds /* may be NULL: mask only */, uint32_t* clipped /* may be NULL */,
                          void* ws, size_t ws_bytes, int64_t R, int64_t C, int axis, int64_t gs, void* stream);
 
+/* ---- scale initialisation: the group-wise scales of the clipped pair from the weights themselves ----
+ * At the library's initial scale (1.19e-5) a range clips every weight of an ordinary layer: dP is masked to zero and only the scale
+ * moves.  This call writes a starting scale per group that covers the weights.  Geometry: lq_fq_forward_group's ([R][C] in memory
+ * order, axis, gs clamped to the line length, nb = ceil(len / gs), the last group may be short); s is the OUTPUT, [nb][C] or [R][nb].
+ * A 1-D parameter with a scalar scale (a bias) is R = 1, C = numel, axis = 1, gs = numel.
+ * n: the element count of a group (its own when short); lo = (float)qmin, hi = (float)qmax.  Every group's result is
+ * fmaxf(s_raw, min_value), min_value > 0 and finite.
+ *   LQ_INIT_ABSMAX  ap = max(max_i P_i, 0), an = max(max_i -P_i, 0)                                   (exact)
+ *                   a  = max(qmax > 0 ? RN_f32(ap / hi) : 0, qmin < 0 ? RN_f32(an / -lo) : 0)         (IEEE fp32 quotients)
+ *                   s_raw = RN_f32(a * (1 + 2^-22))
+ *                   RN(x/d) >= (x/d)(1 - 2^-24), and two such roundings against the factor 1 + 2^-22 leave s_raw strictly above the
+ *                   real quotient: |P_i| / s <= bound in the reals, so the ROUNDED quotient of every element stays inside the range
+ *                   for floor and for nearest -- no element on a side with a nonzero bound is clipped.
+ *   LQ_INIT_LSQ     qp = qmax > 0 ? qmax : -qmin;  s_raw = RN_f32( 2 * sum_i (double)|P_i| / ((double)n * sqrt((double)qp)) ),
+ *                   the LSQ paper's 2 <|w|> / sqrt(Qp); the sum is f64 in one fixed order.  (The range [0, 0] has qp = 0: the
+ *                   quotient is then +Inf, or NaN -> min_value for a group of zeros, as IEEE arithmetic gives it.)
+ *   LQ_INIT_MSE     s0 = the group's LQ_INIT_ABSMAX s_raw.  Candidates k = 0 .. 27: s_k = fmaxf(RN_f32(s0 * c_k), min_value) with
+ *                   c_k = (32 - k) / 32 (exact in fp32, 1 down to 5/32).  E_k = sum_i ((double)P_i - (double)out_i)^2 with out_i the
+ *                   fp32 fake-quantised value of the clipped quantizer above under s_k (IEEE P_i / s_k, floorf or rintf by
+ *                   `rounding`, clamp by comparisons, one fp32 product); d * d and the addition round separately, the sum is f64 in
+ *                   one fixed order per candidate.  The result is the s_k of the smallest E_k; on equal E_k the smallest k wins.
+ * A group that holds a NaN or +-Inf gets s = NaN under every method, other groups are unaffected; a group of zeros gets min_value.
+ * `rounding` is validated for every method and used by LQ_INIT_MSE only.  Two runs give the same bits (no atomics); there is no
+ * workspace.  A NULL pointer, qmin > qmax, a bound outside +-2^24, an unknown `rounding` or `method`, min_value not finite or <= 0,
+ * gs < 1, axis not in {0, 1}, a non-positive extent and R * C >= 2^31 return LQ_EINVAL before any launch; a base off the 4-byte grid
+ * returns LQ_EALIGN (16-byte aligned P with C % 4 == 0 -- and gs % 4 == 0 on axis 1 -- takes 16-byte loads).  The call only enqueues
+ * ONE launch, allocates nothing, reads P's extent and writes s's extent and nothing else.  */
+typedef enum lq_scale_init_method { LQ_INIT_ABSMAX = 0, LQ_INIT_LSQ = 1, LQ_INIT_MSE = 2 } lq_scale_init_method;
+int lq_scale_init_group(const float* P, float* s, int32_t qmin, int32_t qmax, int rounding, int method, float min_value,
+                        int64_t R, int64_t C, int axis, int64_t gs, void* stream);
+
 /* ---- K4: forward and NQ backward of one tensor in a single pass (benchmark path) ---
  * Same results as lq_fq_forward followed by lq_fq_scale_grad (out, max|q| and the vote count bit for bit; on
  * streaming-size tensors the vote sum may differ by fp32 summation order, ~1e-7 relative); P is read once.  */

@@ -5,15 +5,15 @@ custom loss terms and the scale update of anuunchin/learned-quantization, behind
 reference's own Python layer surface, executed by hand-written HIP kernels through the C ABI of
 ``include/lq_hip.h``.  See DESIGN.md / INTEGRATION.md.
 """
-from .descriptor import (ORIENTATIONS, group_descriptor, group_geometry, groupwise_scale_shape, memory_descriptor, memory_order,
+from .descriptor import (ORIENTATIONS, group_descriptor, group_geometry, groupwise_scale_shape, init_geometry, memory_descriptor, memory_order,
                          scale_shape)
 from .layers import (default_kernel_storage, CustomConv2DLayer, CustomConv2DLayerNoBias, CustomDenseLayer, CustomQuantizedScaleLayer,
-                     L2, MinValueConstraint, RandomNormal, SCALE_INIT, custom_layers_of, eps_float32, l2,
+                     L2, MinValueConstraint, RandomNormal, SCALE_INIT, custom_layers_of, eps_float32, init_scales, l2,
                      reset_layer_names)
 from .losses import LossLog, SCCEDifference, SCCEInverse, SCCEMaxBin, sparse_categorical_crossentropy
 from .ops import (difference_term, fq_backward_clip, fq_backward_group, fq_forward, fq_forward_clip, fq_forward_group, fq_fwd_bwd_fused, fq_scale_grad, fq_scale_grad_ste,
                   inverse_term, maxbin_term,
-                  my_custom_gradient, q_absmax_over_axis, q_minmax, q_pack, q_range_of, q_unique, q_unpack, quantized_integers)
+                  my_custom_gradient, q_absmax_over_axis, q_minmax, q_pack, q_range_of, q_unique, q_unpack, quantized_integers, SCALE_INITS, scale_init_group)
 from .optim import KerasAdam, ScaleAdam, apply_constraints, non_scale_parameters, scale_parameters
 from .ddp import DataParallel, GradBucket
 from .batch import BatchedScaleAdam, FakeQuantBatch

@@ -51,6 +51,7 @@
 #include "lq_pack.hpp"
 #include "lq_group.hpp"
 #include "lq_group_batch.hpp"
+#include "lq_scale_init.hpp"
 
 namespace lq {
 
@@ -1451,6 +1452,58 @@ int lq_fq_backward_group(const float* P, const float* s, const float* dy, int32_
     const bool vec = group_vec_ok(p, axis) && aligned(P, 16) && aligned(dy, 16) && aligned(dP, 16);
     if (rounding == LQ_ROUND_NEAREST_EVEN) return launch_group<true, true>(p, axis, vec, (hipStream_t)stream);
     return launch_group<false, true>(p, axis, vec, (hipStream_t)stream);
+}
+
+// ---- scale initialisation (lq_scale_init.hpp) ----
+// The launch shape is the group-wise BACKWARD's: the same host rule picks V, TX, the team width and the grid (no row split: a block
+// owns whole groups), so alignment handling and dead lanes / teams are the code that pair already runs.
+extern "C++" {
+template <int M, bool RNE>
+static int launch_scale_init(const InitParams& ip, const GroupParams& gp, int axis, bool vec, hipStream_t st) {
+    if (axis == 0) {
+        const dim3 grid((unsigned)group_cols_tiles(gp, vec), (unsigned)std::min<int32_t>(gp.nb, 32768));
+        if (vec) hipLaunchKernelGGL((k_init_cols<M, RNE, 4, kGroupColsLanes4>), grid, dim3(kBlock), 0, st, ip);
+        else hipLaunchKernelGGL((k_init_cols<M, RNE, 1, kGroupColsLanes1>), grid, dim3(kBlock), 0, st, ip);
+        return check_hip("scale-init column launch");
+    }
+    const int log_team = group_rows_log_team(gp, vec);
+    const int64_t pairs = (int64_t)gp.R * gp.nb, per_block = kBlock >> log_team;
+    const dim3 grid((unsigned)((pairs + per_block - 1) / per_block));
+    if (vec) hipLaunchKernelGGL((k_init_rows<M, RNE, 4>), grid, dim3(kBlock), 0, st, ip, log_team);
+    else hipLaunchKernelGGL((k_init_rows<M, RNE, 1>), grid, dim3(kBlock), 0, st, ip, log_team);
+    return check_hip("scale-init row launch");
+}
+}  // extern "C++"
+
+int lq_scale_init_group(const float* P, float* s, int32_t qmin, int32_t qmax, int rounding, int method, float min_value,
+                        int64_t R, int64_t C, int axis, int64_t gs, void* stream) {
+    const char* fn = __func__;
+    int rc = check_group(fn, R, C, axis, gs);
+    if (rc) return rc;
+    LQ_REQUIRE_PTR_FN(fn, P);
+    LQ_REQUIRE_PTR_FN(fn, s);
+    if ((rc = check_clip_range(fn, qmin, qmax))) return rc;
+    if ((rc = check_rounding(fn, rounding))) return rc;
+    if (method != LQ_INIT_ABSMAX && method != LQ_INIT_LSQ && method != LQ_INIT_MSE) return fail(LQ_EINVAL, "%s: bad method %d", fn, method);
+    if (!(min_value > 0.0f) || !(min_value <= 3.4028234663852886e+38f)) return fail(LQ_EINVAL, "%s: min_value %g is not a positive finite number", fn, (double)min_value);
+    const GroupParams gp = group_params(P, s, qmin, qmax, R, C, axis, gs);
+    InitParams ip{};
+    ip.P = P;
+    ip.s = s;
+    ip.lo = gp.lo;
+    ip.hi = gp.hi;
+    ip.min_value = min_value;
+    ip.sqrt_qp = sqrt((double)(qmax > 0 ? qmax : -(int64_t)qmin));
+    ip.R = gp.R;
+    ip.C = gp.C;
+    ip.gs = gp.gs;
+    ip.nb = gp.nb;
+    const bool vec = group_vec_ok(gp, axis) && aligned(P, 16);
+    hipStream_t st = (hipStream_t)stream;
+    if (method == LQ_INIT_ABSMAX) return launch_scale_init<LQ_INIT_ABSMAX, false>(ip, gp, axis, vec, st);
+    if (method == LQ_INIT_LSQ) return launch_scale_init<LQ_INIT_LSQ, false>(ip, gp, axis, vec, st);
+    if (rounding == LQ_ROUND_NEAREST_EVEN) return launch_scale_init<LQ_INIT_MSE, true>(ip, gp, axis, vec, st);
+    return launch_scale_init<LQ_INIT_MSE, false>(ip, gp, axis, vec, st);
 }
 
 int lq_fq_fwd_bwd_fused(const float* P, const float* s, const float* dy, float lambda, float* out, float* ds, void* ws,

@@ -16,6 +16,9 @@ library consumes): the descriptor then speaks about the element order in memory,
 ``groupwise_scale_shape`` / ``group_geometry`` are the second descriptor, for group-wise (block) scales (include/lq_hip.h,
 lq_fq_forward_group): the parameter's memory seen as a matrix [R][C] with groups of ``group_size`` along one of the two axes,
 which the flat rule above cannot express (groups along the strided axis, ragged lines).
+
+``init_geometry`` maps ANY scale of a clipped layer -- group-wise, one-axis or scalar -- to that matrix form for scale
+initialisation (lq_scale_init_group), or says that its groups are not lines of a matrix.
 """
 from __future__ import annotations
 
@@ -145,3 +148,37 @@ def group_geometry(shape: Sequence[int], strides: Sequence[int], scale_shape_: S
             return R, C, 0
     raise ValueError(f"scale shape {scale_shape_} fits no split of the parameter's memory-order extents {tuple(dims)} into [R][C] "
                      f"with groups of {gs} along one axis (the groups are defined in memory order)")
+
+
+def init_geometry(shape: Sequence[int], strides: Sequence[int], scale_shape_: Sequence[int],
+                  group_size: Optional[int] = None) -> Tuple[int, int, int, int]:
+    """(R, C, axis, gs) of include/lq_hip.h's lq_scale_init_group for ANY scale of a clipped layer.  A group-wise scale
+    (``group_size`` given) goes through ``group_geometry``.  A one-axis or scalar scale goes through its ``memory_descriptor``
+    (outer, G, inner), whose groups are lines of a matrix in three cases: G == 1 -> (1, numel, 1, numel), one group (a bias, a
+    scalar scale); outer == 1 -> (G, inner, 1, inner), every row is a group; inner == 1 -> (outer, G, 0, outer), every column is
+    a group.  That covers every Dense orientation, biases, scalar scales and channel-wise conv kernels stored OIHW.  With
+    outer > 1, G > 1 and inner > 1 a group is a set of separate runs (the reference's row- / column-wise scales of a 4-D conv
+    kernel, channel-wise on HWIO storage): ValueError."""
+    shape = tuple(int(d) for d in shape)
+    scale_shape_ = tuple(int(d) for d in scale_shape_)
+    if group_size is not None:
+        R, C, axis = group_geometry(shape, strides, scale_shape_, group_size)
+        return R, C, axis, _check_group_size(group_size)
+    desc = memory_descriptor(shape, strides, scale_shape_)
+    if desc is None:
+        raise ValueError(f"scale initialisation needs a dense parameter (a permutation of a contiguous array), got shape {shape} "
+                         f"with strides {tuple(int(d) for d in strides)}")
+    outer, G, inner = desc
+    numel = outer * G * inner
+    if numel >= 1 << 31:
+        raise ValueError(f"scale initialisation takes parameters below 2^31 elements, got {numel}")
+    if G == 1:
+        return 1, numel, 1, numel
+    if outer == 1:
+        return G, inner, 1, inner
+    if inner == 1:
+        return outer, G, 0, outer
+    raise ValueError(f"scale shape {scale_shape_} on a parameter of shape {shape}: in memory order the groups are "
+                     f"(outer, G, inner) = {desc}, {outer} separate runs of {inner} elements each -- the groups are not lines of a "
+                     "matrix, which scale initialisation needs; use a scalar, channel-wise (OIHW storage) or group-wise scale, "
+                     "or set the scales directly")

@@ -127,6 +127,9 @@ def build_parser():
     ap.add_argument("--group-size", type=int, default=None,
                     help="with --bits and --scale-gradient ste (no --custom_loss): group-wise scales, one per N consecutive inputs of "
                          "each output unit (replaces --orientation)")
+    ap.add_argument("--scale-init", default=None, choices=["absmax", "lsq", "mse"],
+                    help="with --bits: start every scale from its weights (after --baseline-weights are loaded) instead of the "
+                         "library's initial value, which clips every weight")
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--steps-per-epoch", type=int, default=10)
     ap.add_argument("--batch", type=int, default=128)
@@ -167,7 +170,7 @@ def main(argv=None):
                  log_dir=log_dir, batched=args.batched, loss_values=args.loss_values,
                  loss_log_capacity=max(4096, args.steps_per_epoch), bits=args.bits, rounding=args.rounding,
                  clipped_batch=args.clipped_batch, group_size=args.group_size,
-                 group_batch=args.group_batch)
+                 group_batch=args.group_batch, scale_init=args.scale_init)
     if args.training == "post_training":
         if args.config != "mnist" or not args.baseline_weights:
             raise SystemExit("post_training needs --config mnist --baseline-weights <npz with W1,b1,W2,b2> "
@@ -178,6 +181,10 @@ def main(argv=None):
             tr.model.dense_1.b.copy_(torch.from_numpy(w["b1"]))
             tr.model.dense_2.W.copy_(torch.from_numpy(w["W2"]))
             tr.model.dense_2.b.copy_(torch.from_numpy(w["b2"]))
+        if args.scale_init is not None:
+            # the trainer initialised the scales from the random weights: again, in place, from the ones just loaded (no step
+            # has run: the scale optimizer's moments are still zero)
+            L.init_scales(tr.model, args.scale_init)
     log_model_structure(tr.model, log_dir)
     # the scale-tracking callback reads the unclipped integer view under one-axis scales: not attached to group-wise layers
     callbacks = [NestedScaleTrackingCallback(layer, log_dir) for layer in tr.custom_layers if layer.group_size is None]

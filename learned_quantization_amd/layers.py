@@ -223,6 +223,21 @@ class CustomQuantizedScaleLayer(nn.Module):
             r += f", group_size={self.group_size}"
         return r
 
+    def init_scale(self, parameter, method):
+        """Writes this layer's scale IN PLACE from ``parameter`` (ops.scale_init_group; ``method`` one of ops.SCALE_INITS) with
+        the layer's range, rounding and group size and the ``min_value`` of its constraint.  The unbounded quantizer has nothing
+        to cover: ValueError without a range.  One launch, no synchronisation."""
+        ops.check_scale_init(method)
+        if self.q_range is None:
+            raise ValueError("scale initialisation needs bits or q_range: the unbounded quantizer clips nothing, there is no range "
+                             "for the scale to cover")
+        if not self.built:
+            self.build(tuple(parameter.shape), device=parameter.device)
+        with torch.no_grad():
+            ops.scale_init_group(parameter.detach(), self.scale.data, *self.q_range, self.group_size, method,
+                                 rounding=self.rounding, min_value=self.constraint.min_value)
+        return self.scale
+
     def quantized_integers(self, parameter, dtype=torch.float32):
         """The integer view of ``parameter`` under this layer's quantizer: floor(P/s), clamped when the layer has a range (then
         rint(P/s) for ``rounding="nearest"``)."""
@@ -296,6 +311,22 @@ class _HostLayer(nn.Module):
         if nested.built:
             param = self.kernel if conv else self.W
             nested.build(tuple(param.shape), device=param.device)
+
+    def scale_pairs(self):
+        """[(what, nested layer, parameter)] of this layer's quantised tensors."""
+        conv = hasattr(self, "nested_q_k_layer")
+        pairs = [("kernel", self.nested_q_k_layer, self.kernel)] if conv else [("W", self.nested_q_w_layer, self.W)]
+        if hasattr(self, "nested_q_b_layer"):
+            pairs.append(("b", self.nested_q_b_layer, self.b))
+        return pairs
+
+    def init_scales(self, method):
+        """``CustomQuantizedScaleLayer.init_scale`` for the kernel / ``W`` and the bias of a built layer."""
+        ops.check_scale_init(method)
+        if not self.built:
+            raise ValueError(f"{self.name}: scale initialisation reads the weights; build the layer first")
+        for _, nested, param in self.scale_pairs():
+            nested.init_scale(param, method)
 
     def _init_value(self, initializer, shape, device):
         if initializer is None:
@@ -543,3 +574,23 @@ def custom_layers_of(model: nn.Module):
     """The reference selects layers by name substring (experiment.py:73, custom_loss_terms/experiment.py:446)."""
     return [m for m in model.modules()
             if isinstance(m, (CustomDenseLayer, _ConvBase))]
+
+
+def init_scales(model: nn.Module, method) -> nn.Module:
+    """Initialises every scale of every custom layer of ``model`` from its weights (``_HostLayer.init_scales``; ``method`` one of
+    ops.SCALE_INITS), then checks all scales with ONE ``isfinite`` reduction -- one synchronisation: this is a host call made
+    once, before the optimizer and any graph exist, never inside a capture.  A NaN scale (a weight tensor that holds a NaN or
+    an Inf) raises ValueError with the layer's name.  The scales are written in place: pointers taken before stay valid."""
+    ops.check_scale_init(method)
+    layers = custom_layers_of(model)
+    entries = []
+    for layer in layers:
+        layer.init_scales(method)
+        entries += [(layer, what, nested) for what, nested, _ in layer.scale_pairs()]
+    if entries:
+        ok = torch.stack([torch.isfinite(nested.scale.detach()).all() for _, _, nested in entries]).cpu().numpy()
+        for (layer, what, nested), fine in zip(entries, ok):
+            if not fine:
+                raise ValueError(f"scale initialisation ({method}) of layer {layer.name!r}: the scale of {what!r} is not finite -- "
+                                 "the weights hold a NaN or an Inf")
+    return model

@@ -295,7 +295,7 @@ def check_group_mode(mode: str, has_range: bool) -> None:
 
 
 def build_model(config: str, kernel_storage: str = None, grad_scale=None, bits=None, signed=True, q_range=None, rounding="floor",
-                group_size=None, **kw) -> nn.Module:
+                group_size=None, scale_init=None, **kw) -> nn.Module:
     """config: 'mnist' (C1), 'cifar' (C2/C4), 'imagenette' (C3), 'resnet50' (C5, extension).
     ``kernel_storage``: memory order of the conv kernels, "oihw" (default) or "hwio" (layers.py).
     ``grad_scale`` (modes "ste" / "stecl"): factor of every straight-through scale gradient, a float or "rsqrt_group".
@@ -303,9 +303,20 @@ def build_model(config: str, kernel_storage: str = None, grad_scale=None, bits=N
     quantised tensor, carried by the host layers and both of their nested layers.
     ``rounding`` ("floor" / "nearest"; "nearest" only with a range): how that quantizer rounds P/s, carried the same way.
     ``group_size`` (with a range, mode "ste"): every quantised kernel gets group-wise scales, one per ``group_size`` consecutive
-    inputs of each output unit (layers.py ``orientation="groupwise"``; it replaces ``orientation``); biases keep a scalar scale."""
+    inputs of each output unit (layers.py ``orientation="groupwise"``; it replaces ``orientation``); biases keep a scalar scale.
+    ``scale_init`` ("absmax" / "lsq" / "mse"; needs a range and ``device``): every scale starts from its weights
+    (layers.init_scales) instead of the library's initial value, applied after the ranges and group sizes are in place."""
     from .ops import check_rounding
     check_rounding(rounding, bits is not None or q_range is not None)
+    if scale_init is not None:
+        from .layers import init_scales
+        from .ops import check_scale_init
+        check_scale_init(scale_init)
+        if bits is None and q_range is None:
+            raise ValueError("scale_init needs bits / q_range: the unbounded quantizer clips nothing, there is no range to cover")
+        model = build_model(config, kernel_storage=kernel_storage, grad_scale=grad_scale, bits=bits, signed=signed, q_range=q_range,
+                            rounding=rounding, group_size=group_size, **kw)
+        return init_scales(model, scale_init)
     if group_size is not None:
         from .layers import _HostLayer
         check_group_mode(kw.get("mode", "nq"), bits is not None or q_range is not None)

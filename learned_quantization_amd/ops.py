@@ -7,17 +7,19 @@
     /root/reference/CIFAR-10/custom_loss_terms/custom_components/custom_layers.py:49-64
 
 Raw (non-autograd) wrappers ``fq_forward``, ``fq_scale_grad``, ``fq_scale_grad_ste``, ``fq_forward_clip``,
-``fq_backward_clip``, ``fq_forward_group``, ``fq_backward_group``, ``fq_fwd_bwd_fused``, ``quantized_integers`` ... are thin: argument checking + one C-ABI call each.
+``fq_backward_clip``, ``fq_forward_group``, ``fq_backward_group``, ``scale_init_group``, ``fq_fwd_bwd_fused``, ``quantized_integers`` ... are thin: argument checking + one C-ABI call each.
 Everything runs on the HIP device; there is no CPU fallback.
 """
 from __future__ import annotations
 
+import math
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _hip
-from .descriptor import group_descriptor, group_geometry, memory_descriptor
+from .descriptor import group_descriptor, group_geometry, init_geometry, memory_descriptor
 
 _QDTYPES = {
     torch.float32: _hip.LQ_Q_F32,
@@ -225,6 +227,44 @@ def fq_backward_group(parameter: torch.Tensor, scale: torch.Tensor, dy: torch.Te
                                         _hip.ptr(ds), _hip.ptr(clipped), _hip.ptr(ws), ws.numel() if ws is not None else 0,
                                         R, C, axis, int(group_size), _hip.stream_ptr(p.device)), "lq_fq_backward_group")
     return dP, ds, clipped
+
+
+SCALE_INITS = ("absmax", "lsq", "mse")      # include/lq_hip.h: LQ_INIT_ABSMAX, LQ_INIT_LSQ, LQ_INIT_MSE
+SCALE_INIT = float(np.float32(float(np.finfo(np.float32).eps) * 100))      # the library's initial scale and minimum (layers.SCALE_INIT)
+
+
+def check_scale_init(method) -> int:
+    """The C ABI's value of a scale-initialisation ``method``, or ValueError: one of SCALE_INITS."""
+    if method not in SCALE_INITS:
+        raise ValueError(f"scale_init must be one of {SCALE_INITS}, got {method!r}")
+    return SCALE_INITS.index(method)
+
+
+def scale_init_group(parameter: torch.Tensor, scale: torch.Tensor, qmin: int, qmax: int, group_size: Optional[int], method: str,
+                     rounding: str = "floor", min_value: float = SCALE_INIT) -> torch.Tensor:
+    """Writes ``scale`` IN PLACE from ``parameter`` (include/lq_hip.h, lq_scale_init_group): per group "absmax" (the smallest
+    scale, up to a 2^-22 margin, under which no element is clipped), "lsq" (2 mean|P| / sqrt(Qp)) or "mse" (the candidate
+    below absmax with the smallest squared error of this quantizer; ``rounding`` matters here only), never below ``min_value``.
+    ``scale`` is a group-wise matrix with its ``group_size`` (descriptor.group_geometry), or, with ``group_size=None``, any
+    one-axis or scalar scale whose groups are lines of the parameter's memory (descriptor.init_geometry).  A group that holds a
+    NaN or an Inf gets NaN.  One launch, no synchronisation.  Returns ``scale``."""
+    qmin, qmax = check_q_range(qmin, qmax)
+    rnd = check_rounding(rounding)
+    m = check_scale_init(method)
+    if method == "lsq" and qmin == 0 and qmax == 0:
+        raise ValueError('scale_init "lsq" divides by sqrt(Qp): the range [0, 0] has no bound to scale by')
+    min_value = float(min_value)
+    if not (min_value > 0.0 and math.isfinite(min_value)):
+        raise ValueError(f"min_value must be a positive finite number, got {min_value!r}")
+    p = _hip.require_device_f32(parameter, "parameter", dense_ok=True)
+    s = _hip.require_device_f32(scale, "scale")
+    if s is not scale:
+        raise ValueError("scale must be contiguous: it is written in place")
+    R, C, axis, gs = init_geometry(tuple(p.shape), p.stride(), tuple(s.shape), group_size)
+    lib = _hip.load()
+    _hip.check(lib.lq_scale_init_group(_hip.ptr(p), _hip.ptr(s), qmin, qmax, rnd, m, min_value, R, C, axis, gs,
+                                       _hip.stream_ptr(p.device)), "lq_scale_init_group")
+    return scale
 
 
 def fq_fwd_bwd_fused(parameter: torch.Tensor, scale: torch.Tensor, dy: torch.Tensor, penalty_threshold: float,

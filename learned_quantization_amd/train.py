@@ -31,7 +31,7 @@ from . import _hip
 from .ddp import CaptureRefused, DataParallel, capture_with_agreement, control_group
 from .losses import LossLog, SCCEDifference, SCCEInverse, SCCEMaxBin, sparse_categorical_crossentropy
 from .models import INPUT_SHAPES, build_model, check_clip_mode, check_group_mode
-from .ops import ROUNDINGS, check_rounding, q_range_of
+from .ops import ROUNDINGS, SCALE_INITS, check_rounding, q_range_of
 from .optim import KerasAdam, ScaleAdam, non_scale_parameters, scale_parameters
 
 LOSSES = {"maxbin": SCCEMaxBin, "difference": SCCEDifference, "inverse": SCCEInverse}
@@ -73,8 +73,12 @@ class Trainer:
                  bucket_mb: float = 25.0, overlap: bool = True, graph_collectives: Optional[bool] = None,
                  force_collectives: bool = False, kernel_storage: str = "oihw", loss_values: bool = False,
                  loss_log_capacity: int = 4096, grad_scale=None, bits=None, signed=True, q_range=None, rounding="floor",
-                 clipped_batch: bool = False, group_size=None, group_batch: bool = False):
-        """``group_size`` (with ``bits`` / ``q_range`` and mode "ste"; eager, graphed and data-parallel mode "A"): group-wise scales
+                 clipped_batch: bool = False, group_size=None, group_batch: bool = False, scale_init=None):
+        """``scale_init`` ("absmax" / "lsq" / "mse"; with ``bits`` / ``q_range``): every scale starts from its layer's weights
+        (layers.init_scales) instead of the library's initial value, at which a range clips every weight.  It runs once, on the
+        device, after the weights are in place and before the optimizers, the batch, the graph and the data-parallel wrapper are
+        built: the scales are written in place, and the wrapper's initial broadcast carries them to every rank.
+        ``group_size`` (with ``bits`` / ``q_range`` and mode "ste"; eager, graphed and data-parallel mode "A"): group-wise scales
         for every quantised kernel (models.build_model); it replaces ``orientation``.
         ``group_batch`` (opt-in, with ``batched=True`` and ``group_size``; mode "ste", eager, graphed, data-parallel mode "A"): the
         group-wise kernels and their biases run in the group batch (``FakeQuantBatch(group_batch=True)``: one forward launch and
@@ -142,6 +146,11 @@ class Trainer:
                                  kernel_storage=kernel_storage, grad_scale=grad_scale, q_range=self.q_range, rounding=rounding,
                                  group_size=group_size)
         self.model.to(self.device)
+        self.scale_init = scale_init
+        if scale_init is not None:
+            if self.q_range is None:
+                raise ValueError("scale_init needs bits / q_range: the unbounded quantizer clips nothing, there is no range to cover")
+            L.init_scales(self.model, scale_init)
         self.custom_layers = L.custom_layers_of(self.model)
         self.loss_obj = None
         self.loss_kind = loss
@@ -429,6 +438,9 @@ def build_parser():
     ap.add_argument("--group-size", type=int, default=None,
                     help="with --bits and mode ste: group-wise scales, one per N consecutive inputs of each output unit (replaces "
                          "--orientation; biases keep a scalar scale)")
+    ap.add_argument("--scale-init", default=None, choices=list(SCALE_INITS),
+                    help="with --bits: start every scale from its weights (absmax: nothing clipped; lsq: 2 mean|w| / sqrt(Qp); mse: "
+                         "least squared error below absmax) instead of the library's initial value, which clips every weight")
     ap.add_argument("--rate", type=float, default=1e-7, help="penalty_rate of the loss term in mode nqcl")
     ap.add_argument("--value-coarse", type=float, default=None,
                     help="resnet50 only: threshold of the 3x3 kernels ('mixed' quantisation intensity); --value is the rest")
@@ -505,7 +517,7 @@ def main(argv=None):
                  grad_scale=(None if args.grad_scale is None else
                              (args.grad_scale if args.grad_scale == "rsqrt_group" else float(args.grad_scale))),
                  bits=args.bits, signed=not args.unsigned, rounding=args.rounding, clipped_batch=args.clipped_batch,
-                 group_size=args.group_size, group_batch=args.group_batch)
+                 group_size=args.group_size, group_batch=args.group_batch, scale_init=args.scale_init)
     do_step = tr.step_graphed if args.graph else tr.step
     g = torch.Generator(device=dev).manual_seed(args.seed + rank)
     batches = [synthetic_batch(args.config, args.batch, dev, g) for _ in range(4)]
@@ -545,6 +557,7 @@ def main(argv=None):
             **({"q_range": list(tr.q_range)} if tr.q_range else {}),
             **({"rounding": tr.rounding} if tr.rounding != "floor" else {}),
             **({"group_size": tr.group_size} if tr.group_size is not None else {}),
+            **({"scale_init": tr.scale_init} if tr.scale_init is not None else {}),
             **({"loss_values": True, "loss_log_rows": log_rows[0], "loss_log_dropped": log_rows[1]} if log_rows else {})}))
         if args.export_dir:
             from .export import save_compress_parameters

@@ -207,6 +207,62 @@ typedef enum lq_scale_init_method { LQ_INIT_ABSMAX = 0, LQ_INIT_LSQ = 1, LQ_INIT
 int lq_scale_init_group(const float* P, float* s, int32_t qmin, int32_t qmax, int rounding, int method, float min_value,
                         int64_t R, int64_t C, int axis, int64_t gs, void* stream);
 
+/* ---- asymmetric group-wise scales: a learned offset per group ----
+ * Geometry is exactly lq_fq_forward_group's: matrix [R][C] in memory order, axis, gs, nb = ceil(len / gs), ragged last group.  The
+ * offset b is a dense fp32 matrix of the scale's shape and indexed like it.  lo = (float)qmin, hi = (float)qmax.  All operations
+ * are fp32 unless stated otherwise, and every operation rounds on its own (the library is built without contraction: no fma
+ * fuses q * s + b).
+ *   u  = P - b                      (one subtraction)
+ *   t  = u / s                      (IEEE division: K1's division on u)
+ *   q0 = floorf(t) | rintf(t)       by `rounding`
+ *   q  = q0 < lo ? lo : (q0 > hi ? hi : q0)
+ *   out = (q * s) + b               (product rounds, then the sum rounds)
+ *   inside = (q0 >= lo) && (q0 <= hi)
+ *   dP = inside ? dy : +0.0f
+ *   r  = inside ? q0 - t : q
+ *   ds[g] = RN_f32( (double)grad_scale        * sum_{i in g} (double)dy_i * (double)r_i )
+ *   db[g] = RN_f32( (double)offset_grad_scale * sum_{i in g, !inside_i} (double)dy_i )
+ *   clipped[g] = #{ i in g : !inside_i }      exact, uint32
+ * db is LSQ+'s offset gradient: under the straight-through rule d out / d b is 0 inside the range and 1 outside.
+ * The sums are f64 from the first addition.  They are taken in the one fixed order the symmetric backward uses for the same
+ * geometry and alignment, with no float atomics and no workspace: lq_group_workspace_bytes covers this pair too and stays 0.
+ * NaN or Inf in P, s or b spoils only its own group, as for the symmetric pair.  With b == +0.0f everywhere, dP, ds and clipped
+ * are bit-identical to lq_fq_backward_group on the same buffers; out is equal as a value, only -0.0 comes back as +0.0; the
+ * integer view is identical.  The kernels take the symmetric pair's form, vector width, team width, row split and grid.
+ * lq_fq_forward_group_affine: `out` is required; q / q_dtype optionally give the CLAMPED integers q.
+ * lq_fq_backward_group_affine: dP is required; ds, db and clipped may each be NULL; both gradient pointers NULL means mask only.
+ * A NULL required pointer, qmin > qmax, a bound outside +-2^24, a bad `rounding`, axis not in {0, 1}, gs < 1, a non-positive
+ * extent and R * C >= 2^31 return LQ_EINVAL before any launch; a base off the 4-byte grid returns LQ_EALIGN; 16-byte accesses are
+ * used under the symmetric rule (16-byte aligned dense bases, C % 4 == 0, and gs % 4 == 0 on axis 1).  Both calls only enqueue
+ * (capturable), ONE launch each.
+ *
+ * lq_scale_init_group_minmax writes s AND b per group ("minmax").  n below is the range width, not an element count.
+ *   mn = min_i P_i, mx = max_i P_i (exact);  n = (float)(qmax - qmin)
+ *   s  = fmaxf( RN(RN(RN(mx - mn) / n) * (1 + 2^-22)), min_value )
+ *   mid = RN(0.5f*mn + 0.5f*mx)
+ *   c   = (qmin + qmax)/2 + (floor ? 1/2 : 0)      (formed in double on the host, exact as a float)
+ *   b   = RN(mid - RN(c * s))
+ * The data lands on t in [lo + 1/2, hi + 1/2] for floor and [lo, hi] for nearest: half a step of slack on both sides.
+ * When nothing is clipped (a sufficient condition).  Let M = max_i |P_i| and let no intermediate overflow or be subnormal.  Three
+ * roundings against the factor 1 + 2^-22 leave s >= (mx - mn) / n in the reals, so the exact quotient t* = (P_i - (mn + mx)/2) / s + c
+ * lies in [c - n/2, c + n/2].  The computed t differs from t* by the roundings of mid, c * s, b, u and t, each at most 2^-24 of
+ * its result: |t - t*| <= 2^-24 * (2 M / s + 4 |c| + n) up to second order.  Both roundings keep the element inside while
+ * |t - t*| < 1/2, so NO element of the group is clipped whenever  2 M / s + 4 |c| + n <= 2^22.  For b-bit ranges (n, |c| <= 2^16)
+ * that is M <= ~2^20 * s: the group's distance from zero may be up to a million steps.  Beyond it the offset's own rounding
+ * exceeds the slack and an extreme element may be clipped by one code.
+ * qmax > qmin and both bounds within +-2^22 are required, otherwise LQ_EINVAL (as is a bad rounding, min_value not finite or <= 0
+ * and the geometry checks above); LQ_EALIGN as above.  A group holding NaN or +-Inf gets s = b = NaN.  A group of equal values
+ * gets s = min_value and b by the formula (where its minimum is a zero of either sign and c == 0, the sign of b's zero is that
+ * of the zero fminf kept).  ONE launch, only enqueues, no workspace, two runs give the same bits.  */
+int lq_fq_forward_group_affine(const float* P, const float* s, const float* b, float* out, void* q, int q_dtype, int32_t qmin,
+                               int32_t qmax, int rounding, int64_t R, int64_t C, int axis, int64_t gs, void* stream);
+int lq_fq_backward_group_affine(const float* P, const float* s, const float* b, const float* dy, int32_t qmin, int32_t qmax,
+                                int rounding, float grad_scale, float offset_grad_scale, float* dP, float* ds /* may be NULL */,
+                                float* db /* may be NULL */, uint32_t* clipped /* may be NULL */, void* ws, size_t ws_bytes,
+                                int64_t R, int64_t C, int axis, int64_t gs, void* stream);
+int lq_scale_init_group_minmax(const float* P, float* s, float* b, int32_t qmin, int32_t qmax, int rounding, float min_value,
+                               int64_t R, int64_t C, int axis, int64_t gs, void* stream);
+
 /* ---- K4: forward and NQ backward of one tensor in a single pass (benchmark path) ---
  * Same results as lq_fq_forward followed by lq_fq_scale_grad (out, max|q| and the vote count bit for bit; on
  * streaming-size tensors the vote sum may differ by fp32 summation order, ~1e-7 relative); P is read once.  */

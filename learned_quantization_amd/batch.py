@@ -83,6 +83,9 @@ class FakeQuantBatch:
         if self.group_batch and self.clipped:
             raise ValueError("group_batch=True together with clipped=True: a batch is either the group batch (group-wise layers and "
                              "their biases) or the clipped batch (one-axis scales), not both")
+        if any(getattr(n, "asymmetric", False) for n in nested_layers):
+            raise ValueError("FakeQuantBatch over an asymmetric layer (asymmetric=True): neither the clipped batch nor the group batch "
+                             "carries an offset per group or its gradient; run such a model on the per-tensor path (batched=False)")
         if not self.group_batch and any(getattr(n, "group_size", None) is not None for n in nested_layers):
             raise ValueError("FakeQuantBatch over a group-wise layer (group_size): its scale has two non-unit axes, which the "
                              "(outer, G, inner) descriptor of the default and the clipped batch cannot express; run such a model on "

@@ -52,6 +52,7 @@
 #include "lq_group.hpp"
 #include "lq_group_batch.hpp"
 #include "lq_scale_init.hpp"
+#include "lq_group_affine.hpp"
 
 namespace lq {
 
@@ -1504,6 +1505,128 @@ int lq_scale_init_group(const float* P, float* s, int32_t qmin, int32_t qmax, in
     if (method == LQ_INIT_LSQ) return launch_scale_init<LQ_INIT_LSQ, false>(ip, gp, axis, vec, st);
     if (rounding == LQ_ROUND_NEAREST_EVEN) return launch_scale_init<LQ_INIT_MSE, true>(ip, gp, axis, vec, st);
     return launch_scale_init<LQ_INIT_MSE, false>(ip, gp, axis, vec, st);
+}
+
+// ---- asymmetric group-wise scales (lq_group_affine.hpp) ----
+// The launch shape is the symmetric pair's for the same geometry and alignment: the same helpers pick V, TX, the team width, the
+// forward's row split and the grid.  The offset and db are read and written one element at a time, like s and ds.
+extern "C++" {
+template <bool RNE, bool BWD>
+static int launch_group_affine(const GroupAffineParams& ap, int axis, bool vec, hipStream_t st) {
+    const GroupParams& p = ap.g;
+    if (axis == 0) {
+        dim3 grid((unsigned)group_cols_tiles(p, vec), (unsigned)std::min<int32_t>(p.nb, 32768));
+        if (!BWD) grid.z = (unsigned)group_cols_row_split(p, vec, grid.x, grid.y);
+        if (vec) hipLaunchKernelGGL((k_group_affine_cols<RNE, BWD, 4, kGroupColsLanes4>), grid, dim3(kBlock), 0, st, ap);
+        else hipLaunchKernelGGL((k_group_affine_cols<RNE, BWD, 1, kGroupColsLanes1>), grid, dim3(kBlock), 0, st, ap);
+        return check_hip("affine group-wise column launch");
+    }
+    const int log_team = group_rows_log_team(p, vec);
+    const int64_t pairs = (int64_t)p.R * p.nb, per_block = kBlock >> log_team;
+    const dim3 grid((unsigned)((pairs + per_block - 1) / per_block));
+    if (vec) hipLaunchKernelGGL((k_group_affine_rows<RNE, BWD, 4>), grid, dim3(kBlock), 0, st, ap, log_team);
+    else hipLaunchKernelGGL((k_group_affine_rows<RNE, BWD, 1>), grid, dim3(kBlock), 0, st, ap, log_team);
+    return check_hip("affine group-wise row launch");
+}
+}  // extern "C++"
+
+int lq_fq_forward_group_affine(const float* P, const float* s, const float* b, float* out, void* q, int q_dtype, int32_t qmin,
+                               int32_t qmax, int rounding, int64_t R, int64_t C, int axis, int64_t gs, void* stream) {
+    const char* fn = __func__;
+    int rc = check_group(fn, R, C, axis, gs);
+    if (rc) return rc;
+    LQ_REQUIRE_PTR_FN(fn, P);
+    LQ_REQUIRE_PTR_FN(fn, s);
+    LQ_REQUIRE_PTR_FN(fn, b);
+    LQ_REQUIRE_PTR_FN(fn, out);
+    if ((rc = check_clip_range(fn, qmin, qmax))) return rc;
+    if ((rc = check_rounding(fn, rounding))) return rc;
+    if (q_dtype < LQ_Q_NONE || q_dtype > LQ_Q_I8) return fail(LQ_EINVAL, "%s: bad q_dtype %d", fn, q_dtype);
+    if ((q != nullptr) != (q_dtype != LQ_Q_NONE)) return fail(LQ_EINVAL, "%s: q and q_dtype disagree", fn);
+    if (q && q_dtype != LQ_Q_I8 && !aligned(q, 4)) return fail(LQ_EALIGN, "%s: q is not 4-byte aligned", fn);
+    GroupAffineParams ap{};
+    ap.g = group_params(P, s, qmin, qmax, R, C, axis, gs);
+    ap.g.out = out;
+    ap.g.q = q;
+    ap.g.q_dtype = q_dtype;
+    ap.b = b;
+    const bool vec = group_vec_ok(ap.g, axis) && aligned(P, 16) && aligned(out, 16);
+    if (rounding == LQ_ROUND_NEAREST_EVEN) return launch_group_affine<true, false>(ap, axis, vec, (hipStream_t)stream);
+    return launch_group_affine<false, false>(ap, axis, vec, (hipStream_t)stream);
+}
+
+int lq_fq_backward_group_affine(const float* P, const float* s, const float* b, const float* dy, int32_t qmin, int32_t qmax,
+                                int rounding, float grad_scale, float offset_grad_scale, float* dP, float* ds, float* db,
+                                uint32_t* clipped, void* ws, size_t ws_bytes, int64_t R, int64_t C, int axis, int64_t gs,
+                                void* stream) {
+    const char* fn = __func__;
+    (void)ws; (void)ws_bytes;      // lq_group_workspace_bytes() == 0: ws may be NULL and is never touched
+    int rc = check_group(fn, R, C, axis, gs);
+    if (rc) return rc;
+    LQ_REQUIRE_PTR_FN(fn, P);
+    LQ_REQUIRE_PTR_FN(fn, s);
+    LQ_REQUIRE_PTR_FN(fn, b);
+    LQ_REQUIRE_PTR_FN(fn, dy);
+    LQ_REQUIRE_PTR_FN(fn, dP);
+    if (ds && !aligned(ds, 4)) return fail(LQ_EALIGN, "%s: ds is not 4-byte aligned", fn);
+    if (db && !aligned(db, 4)) return fail(LQ_EALIGN, "%s: db is not 4-byte aligned", fn);
+    if (clipped && !aligned(clipped, 4)) return fail(LQ_EALIGN, "%s: clipped is not 4-byte aligned", fn);
+    if ((rc = check_clip_range(fn, qmin, qmax))) return rc;
+    if ((rc = check_rounding(fn, rounding))) return rc;
+    GroupAffineParams ap{};
+    ap.g = group_params(P, s, qmin, qmax, R, C, axis, gs);
+    ap.g.dy = dy;
+    ap.g.out = dP;
+    ap.g.k = grad_scale;
+    ap.g.ds = ds;
+    ap.g.clipped = clipped;
+    ap.b = b;
+    ap.db = db;
+    ap.kb = offset_grad_scale;
+    const bool vec = group_vec_ok(ap.g, axis) && aligned(P, 16) && aligned(dy, 16) && aligned(dP, 16);
+    if (rounding == LQ_ROUND_NEAREST_EVEN) return launch_group_affine<true, true>(ap, axis, vec, (hipStream_t)stream);
+    return launch_group_affine<false, true>(ap, axis, vec, (hipStream_t)stream);
+}
+
+int lq_scale_init_group_minmax(const float* P, float* s, float* b, int32_t qmin, int32_t qmax, int rounding, float min_value,
+                               int64_t R, int64_t C, int axis, int64_t gs, void* stream) {
+    const char* fn = __func__;
+    int rc = check_group(fn, R, C, axis, gs);
+    if (rc) return rc;
+    LQ_REQUIRE_PTR_FN(fn, P);
+    LQ_REQUIRE_PTR_FN(fn, s);
+    LQ_REQUIRE_PTR_FN(fn, b);
+    constexpr int32_t kLim = 1 << 22;      // c = (qmin + qmax) / 2 (+ 1/2) and n = qmax - qmin are exact floats
+    if (qmin >= qmax) return fail(LQ_EINVAL, "%s: min-max needs qmax > qmin (got [%d, %d])", fn, (int)qmin, (int)qmax);
+    if (qmin < -kLim || qmax > kLim) return fail(LQ_EINVAL, "%s: range [%d, %d] is outside +-2^22", fn, (int)qmin, (int)qmax);
+    if ((rc = check_rounding(fn, rounding))) return rc;
+    if (!(min_value > 0.0f) || !(min_value <= 3.4028234663852886e+38f)) return fail(LQ_EINVAL, "%s: min_value %g is not a positive finite number", fn, (double)min_value);
+    const GroupParams gp = group_params(P, s, qmin, qmax, R, C, axis, gs);
+    MinMaxParams mp{};
+    mp.P = P;
+    mp.s = s;
+    mp.b = b;
+    mp.n = (float)((int64_t)qmax - (int64_t)qmin);
+    mp.c = (float)(((double)qmin + (double)qmax) * 0.5 + (rounding == LQ_ROUND_FLOOR ? 0.5 : 0.0));
+    mp.min_value = min_value;
+    mp.R = gp.R;
+    mp.C = gp.C;
+    mp.gs = gp.gs;
+    mp.nb = gp.nb;
+    const bool vec = group_vec_ok(gp, axis) && aligned(P, 16);
+    hipStream_t st = (hipStream_t)stream;
+    if (axis == 0) {
+        const dim3 grid((unsigned)group_cols_tiles(gp, vec), (unsigned)std::min<int32_t>(gp.nb, 32768));
+        if (vec) hipLaunchKernelGGL((k_minmax_cols<4, kGroupColsLanes4>), grid, dim3(kBlock), 0, st, mp);
+        else hipLaunchKernelGGL((k_minmax_cols<1, kGroupColsLanes1>), grid, dim3(kBlock), 0, st, mp);
+        return check_hip("min-max column launch");
+    }
+    const int log_team = group_rows_log_team(gp, vec);
+    const int64_t pairs = (int64_t)gp.R * gp.nb, per_block = kBlock >> log_team;
+    const dim3 grid((unsigned)((pairs + per_block - 1) / per_block));
+    if (vec) hipLaunchKernelGGL((k_minmax_rows<4>), grid, dim3(kBlock), 0, st, mp, log_team);
+    else hipLaunchKernelGGL((k_minmax_rows<1>), grid, dim3(kBlock), 0, st, mp, log_team);
+    return check_hip("min-max row launch");
 }
 
 int lq_fq_fwd_bwd_fused(const float* P, const float* s, const float* dy, float lambda, float* out, float* ds, void* ws,

@@ -27,7 +27,7 @@ import torch
 from . import layers as L
 from .export import save_compress_parameters, save_packed_parameters
 from .tracking import AccuracyLossTrackingCallBack, NestedScaleTrackingCallback
-from .train import Trainer, synthetic_batch
+from .train import DriverParser, Trainer, synthetic_batch
 
 
 def scheduler(epoch: int, lr: float) -> float:
@@ -108,7 +108,7 @@ def fit(tr: Trainer, epochs: int, steps_per_epoch: int, batch: int, callbacks, l
 
 
 def build_parser():
-    ap = argparse.ArgumentParser(description="Train model for one penalty value in this scenario (synthetic data).")
+    ap = DriverParser(description="Train model for one penalty value in this scenario (synthetic data).")
     ap.add_argument("--config", choices=["mnist", "cifar", "imagenette"], default="cifar")
     ap.add_argument("--seed", type=int, required=True, help="Random seed for reproducibility.")
     ap.add_argument("--orientation", type=str, required=True, choices=["rowwise", "columnwise", "channelwise", "scalar"])
@@ -127,9 +127,12 @@ def build_parser():
     ap.add_argument("--group-size", type=int, default=None,
                     help="with --bits and --scale-gradient ste (no --custom_loss): group-wise scales, one per N consecutive inputs of "
                          "each output unit (replaces --orientation)")
-    ap.add_argument("--scale-init", default=None, choices=["absmax", "lsq", "mse"],
+    ap.add_argument("--asymmetric", action="store_true",
+                    help="with --bits, --group-size and --scale-gradient ste: every group-wise kernel also learns an offset per group")
+    ap.add_argument("--scale-init", default=None, choices=["absmax", "lsq", "mse", "minmax"],
                     help="with --bits: start every scale from its weights (after --baseline-weights are loaded) instead of the "
-                         "library's initial value, which clips every weight")
+                         "library's initial value, which clips every weight; minmax (scale and offset from each group's minimum and "
+                         "maximum) with --asymmetric only")
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--steps-per-epoch", type=int, default=10)
     ap.add_argument("--batch", type=int, default=128)
@@ -170,7 +173,7 @@ def main(argv=None):
                  log_dir=log_dir, batched=args.batched, loss_values=args.loss_values,
                  loss_log_capacity=max(4096, args.steps_per_epoch), bits=args.bits, rounding=args.rounding,
                  clipped_batch=args.clipped_batch, group_size=args.group_size,
-                 group_batch=args.group_batch, scale_init=args.scale_init)
+                 group_batch=args.group_batch, scale_init=args.scale_init, asymmetric=args.asymmetric)
     if args.training == "post_training":
         if args.config != "mnist" or not args.baseline_weights:
             raise SystemExit("post_training needs --config mnist --baseline-weights <npz with W1,b1,W2,b2> "

@@ -78,6 +78,8 @@ def scale_state(model: torch.nn.Module) -> Dict[str, np.ndarray]:
             nested = getattr(layer, attr, None)
             if nested is not None and getattr(nested, "scale", None) is not None and hasattr(layer, "name"):
                 out[layer.name + tag] = _host(nested.scale)
+                if getattr(nested, "offset", None) is not None:      # asymmetric layers only: other models' files are unchanged
+                    out[layer.name + tag.replace("_scale", "_offset")] = _host(nested.offset)
     return out
 
 
@@ -120,6 +122,7 @@ def _manifest_bytes(manifest: dict) -> np.ndarray:
 def _plain_state_keys(model: torch.nn.Module, tensors) -> List[str]:
     """state_dict keys of everything that is not a quantized parameter or its scale, in state_dict order."""
     skip = {id(p) for _, p, _ in tensors} | {id(nested.scale) for _, _, nested in tensors}
+    skip |= {id(nested.offset) for _, _, nested in tensors if getattr(nested, "offset", None) is not None}
     owned = {key for key, p in model.named_parameters() if id(p) in skip}
     return [k for k in model.state_dict().keys() if k not in owned]
 
@@ -148,6 +151,8 @@ def save_packed_parameters(model: torch.nn.Module, log_dir: str) -> Dict[str, fl
             entries[-1]["rounding"] = nested.rounding
         if getattr(nested, "group_size", None) is not None:      # layers without group-wise scales get no key either
             entries[-1]["group_size"] = int(nested.group_size)
+        if getattr(nested, "asymmetric", False):                 # nor symmetric layers: the offset array sits behind the scale
+            entries[-1]["asymmetric"] = True
     bad = torch.zeros(len(tensors), dtype=torch.int64, device=dev)
     words = [ops.q_pack(src, unit, qmin=e["qmin"], bits=e["bits"], bad=bad[k:k + 1])[0]
              for k, ((src, unit), e) in enumerate(zip(sources, entries))]
@@ -161,6 +166,8 @@ def save_packed_parameters(model: torch.nn.Module, log_dir: str) -> Dict[str, fl
     for (name, _, nested), e, w in zip(tensors, entries, words):
         arrays[name + ".codes"] = w.cpu().numpy().view(np.uint32)
         arrays[name + ".scale"] = _host(nested.scale)
+        if e.get("asymmetric"):
+            arrays[name + ".offset"] = _host(nested.offset)
     for key in state_keys:
         arrays["state/" + key] = np.array(sd[key].detach().cpu().numpy(), order="C")   # keeps 0-d counters 0-d
 
@@ -213,6 +220,9 @@ def _check_packed(model: torch.nn.Module, manifest: dict, z, tensors, state_keys
         if e.get("group_size") != getattr(nested, "group_size", None):      # a missing key means no group-wise scales
             raise ValueError(f"{name}: group_size {e.get('group_size')} in the container, {getattr(nested, 'group_size', None)} in "
                              "the model")
+        if bool(e.get("asymmetric", False)) != bool(getattr(nested, "asymmetric", False)):      # a missing key means symmetric
+            raise ValueError(f"{name}: asymmetric {bool(e.get('asymmetric', False))} in the container, "
+                             f"{bool(getattr(nested, 'asymmetric', False))} in the model")
         if list(e.get("scale_shape", [])) != list(nested.scale.shape):
             raise ValueError(f"{name}: scale shape {e.get('scale_shape')} in the container, {list(nested.scale.shape)} in the model")
         if e.get("orientation") != nested.orientation:
@@ -232,6 +242,10 @@ def _check_packed(model: torch.nn.Module, manifest: dict, z, tensors, state_keys
         sc = z[name + ".scale"] if name + ".scale" in z.files else None
         if sc is None or sc.dtype != np.float32 or list(sc.shape) != list(nested.scale.shape):
             raise ValueError(f"{name}: scale missing or not float32 {list(nested.scale.shape)}")
+        if e.get("asymmetric"):
+            off = z[name + ".offset"] if name + ".offset" in z.files else None
+            if off is None or off.dtype != np.float32 or list(off.shape) != list(nested.scale.shape):
+                raise ValueError(f"{name}: offset missing or not float32 {list(nested.scale.shape)}")
     if list(manifest.get("state", [])) != state_keys:
         missing = sorted(set(state_keys) - set(manifest.get("state", [])))
         extra = sorted(set(manifest.get("state", [])) - set(state_keys))
@@ -243,16 +257,20 @@ def _check_packed(model: torch.nn.Module, manifest: dict, z, tensors, state_keys
             raise ValueError(f"state entry {key}: missing or shape {None if a is None else a.shape} != {tuple(sd[key].shape)}")
 
 
-def _restore_groupwise(param: torch.Tensor, q: torch.Tensor, s: torch.Tensor, group_size: int, rounding: str):
+def _restore_groupwise(param: torch.Tensor, q: torch.Tensor, s: torch.Tensor, group_size: int, rounding: str, b=None):
     """(P, q) with the parameter's strides for the stored integers ``q`` (int32, logical order) of a group-wise layer:
-    P = (q + 1/2) * s for floor, q * s for nearest, s broadcast by the index rule of include/lq_hip.h (lq_fq_forward_group)."""
+    P = (q + 1/2) * s for floor, q * s for nearest, s broadcast by the index rule of include/lq_hip.h (lq_fq_forward_group);
+    an asymmetric layer's offset ``b`` is broadcast the same way and added."""
     R, C, axis = group_geometry(tuple(param.shape), param.data.stride(), tuple(s.shape), group_size)
     qs = torch.empty_like(param.data, dtype=torch.int32).copy_(q)
     pr = torch.empty_like(param.data)
     gs = min(int(group_size), R if axis == 0 else C)
     sx = s.repeat_interleave(gs, dim=axis)[:R, :C]
     qm = torch.as_strided(qs, (R, C), (C, 1)).to(torch.float32)      # the memory-order matrix of include/lq_hip.h
-    torch.as_strided(pr, (R, C), (C, 1)).copy_((qm if rounding == "nearest" else qm + 0.5) * sx)
+    pm = (qm if rounding == "nearest" else qm + 0.5) * sx
+    if b is not None:
+        pm = pm + b.repeat_interleave(gs, dim=axis)[:R, :C]
+    torch.as_strided(pr, (R, C), (C, 1)).copy_(pm)
     return pr, qs
 
 
@@ -262,6 +280,8 @@ def load_packed_parameters(model: torch.nn.Module, path: str) -> dict:
     state entry the stored one, copied into the existing tensors.  A rounding="nearest" layer takes another pre-image: (q + 1/2) * s
     is a tie under rint, so its P becomes q * s, and the layer's own integer view of that P is compared with q on the device.
     A group-wise layer is restored the same way with its scale broadcast over the groups, and always verified through its own view.
+    An asymmetric layer takes P = (q + 1/2) * s + b (floor) or q * s + b (nearest) and is verified through the affine forward; a
+    container and a model that disagree on ``asymmetric`` raise.
     Format, version, names, shapes, orientations and roundings are checked first: on a mismatch, or a restored value that does
     not round back, ValueError is raised and the model is left untouched.  Returns the manifest."""
     if os.path.isdir(path):
@@ -273,6 +293,7 @@ def load_packed_parameters(model: torch.nn.Module, path: str) -> dict:
         _check_packed(model, manifest, z, tensors, state_keys)
         codes = {e["name"]: z[e["name"] + ".codes"] for e in manifest["tensors"]}
         scales = {e["name"]: z[e["name"] + ".scale"] for e in manifest["tensors"]}
+        offsets = {e["name"]: z[e["name"] + ".offset"] for e in manifest["tensors"] if e.get("asymmetric")}
         state = {key: z["state/" + key] for key in state_keys}
     if not tensors:
         return manifest
@@ -288,8 +309,13 @@ def load_packed_parameters(model: torch.nn.Module, path: str) -> dict:
             # order; the layer's own group-wise integer view of that P is compared with q on the device
             unit = torch.ones(1, dtype=torch.float32, device=dev)
             _, q, _ = ops.q_unpack(w, e["qmin"], e["bits"], unit, param.shape, want_out=False, want_restore=False)
-            pr, qs = _restore_groupwise(param, q, s, e["group_size"], e.get("rounding", "floor"))
-            view = ops.fq_forward_group(pr, s, *nested.q_range, e["group_size"], q_dtype=torch.int32, rounding=nested.rounding)[1]
+            b = torch.from_numpy(offsets[name]).to(dev) if e.get("asymmetric") else None
+            pr, qs = _restore_groupwise(param, q, s, e["group_size"], e.get("rounding", "floor"), b)
+            if b is not None:
+                view = ops.fq_forward_group_affine(pr, s, b, *nested.q_range, e["group_size"], q_dtype=torch.int32,
+                                                   rounding=nested.rounding)[1]
+            else:
+                view = ops.fq_forward_group(pr, s, *nested.q_range, e["group_size"], q_dtype=torch.int32, rounding=nested.rounding)[1]
             beyond = (qs < nested.q_range[0]) | (qs > nested.q_range[1])
             outside += beyond.sum()
             bad += ((view != qs) & ~beyond).sum()
@@ -302,7 +328,7 @@ def load_packed_parameters(model: torch.nn.Module, path: str) -> dict:
             bad += ((view != q) & ~beyond).sum()
         else:
             _, _, pr = ops.q_unpack(w, e["qmin"], e["bits"], s, param.shape, want_out=False, want_q=False, bad=bad)
-        restored.append((param, nested, s, pr))
+        restored.append((param, nested, s, pr, offsets.get(name)))
     nbad, noutside = int(bad.item()), int(outside.item())
     if noutside:
         raise ValueError(f"{noutside} stored integers lie outside the integer range of their layer in the model (the container was "
@@ -310,9 +336,11 @@ def load_packed_parameters(model: torch.nn.Module, path: str) -> dict:
     if nbad:
         raise ValueError(f"{nbad} restored values do not round back to their stored integer (|q| >= 2^22): model left untouched")
     with torch.no_grad():
-        for param, nested, s, pr in restored:
+        for param, nested, s, pr, off in restored:
             param.data.copy_(pr)                               # into the parameter's own storage (HWIO or OIHW order)
             nested.scale.data.copy_(s)
+            if off is not None:
+                nested.offset.data.copy_(torch.from_numpy(off))
         sd = model.state_dict()
         for key, a in state.items():
             sd[key].copy_(torch.from_numpy(np.array(a, order="C")))

@@ -138,6 +138,10 @@ class CustomQuantizedScaleLayer(nn.Module):
     ``gs`` consecutive inputs of each output unit (descriptor.groupwise_scale_shape; ops.fq_forward_group / fq_backward_group).
     The groups are defined in the parameter's memory order: a Dense kernel ``(in, out)`` gets scales ``(nb, out)``, a conv kernel
     stored OIHW gets ``(co, nb)`` over the (ci, kh, kw) run of each output channel.
+    ``asymmetric=True`` (not in the reference; only with ``orientation="groupwise"``, a range and ``scale_gradient="ste"``) -> the
+    layer also owns ``offset``, a Parameter of the scale's shape (zeros), and quantises ``clamp(rnd((P - b) / s)) * s + b``
+    (ops.fq_forward_group_affine / fq_backward_group_affine): a group's grid need not be centred on zero.  The offset is stepped
+    like a scale (``lq_is_scale``) but has no lower bound (no ``lq_constraint``); ``lq_is_offset`` tells it apart.
     """
 
     _SCALE_NAMES = {"rowwise": "Rowwise-scaler", "columnwise": "Columnwise-scaler",
@@ -145,11 +149,13 @@ class CustomQuantizedScaleLayer(nn.Module):
                     "scalar": "Scalar-scaler", "groupwise": "Groupwise-scaler"}
 
     def __init__(self, penalty_threshold=None, initializer=None, orientation="scalar", *, penalty_rate=None,
-                 scale_gradient=None, grad_scale=1.0, bits=None, signed=True, q_range=None, rounding="floor", group_size=None):
+                 scale_gradient=None, grad_scale=1.0, bits=None, signed=True, q_range=None, rounding="floor", group_size=None,
+                 asymmetric=False):
         super().__init__()
         self.q_range = ops.q_range_of(bits, signed, q_range)
         ops.check_rounding(rounding, self.q_range is not None)
         self.rounding = rounding
+        self.asymmetric = check_asymmetric(asymmetric, orientation, self.q_range, penalty_threshold, penalty_rate, scale_gradient)
         self.group_size = check_groupwise(orientation, group_size, self.q_range, penalty_threshold, penalty_rate)
         if self.q_range is not None and penalty_threshold is not None:
             raise ValueError("a clipped layer (bits / q_range) needs penalty_threshold=None: the nested-quantization vote is "
@@ -168,6 +174,7 @@ class CustomQuantizedScaleLayer(nn.Module):
         self.penalty_rate = penalty_rate
         self.constraint = MinValueConstraint(SCALE_INIT)          # NQ-L:158
         self.scale: Optional[nn.Parameter] = None
+        self.offset: Optional[nn.Parameter] = None      # asymmetric layers only
         self.scale_name: Optional[str] = None
         self.built = False
         self.defer_scale_grad = False          # set by DataParallel(mode="B"): ds is recomputed after the all-reduce
@@ -180,6 +187,10 @@ class CustomQuantizedScaleLayer(nn.Module):
         self.scale = nn.Parameter(torch.full(shape, SCALE_INIT, dtype=torch.float32, device=device))  # NQ-L:156
         self.scale.lq_constraint = self.constraint                 # found by optim.apply_constraints
         self.scale.lq_is_scale = True
+        if self.asymmetric:
+            self.offset = nn.Parameter(torch.zeros(shape, dtype=torch.float32, device=device))
+            self.offset.lq_is_scale = True       # stepped by ScaleAdam; no lq_constraint: an offset has no lower bound
+            self.offset.lq_is_offset = True
         if self.penalty_rate is not None and not hasattr(self, "penalty_rate_weight"):
             # the MNIST loss-term variant keeps the rate as a NON-trainable weight of the nested layer
             # (MNIST/custom_loss_terms/custom_components/custom_layers.py:97-102): a buffer here, saved with the model
@@ -196,6 +207,12 @@ class CustomQuantizedScaleLayer(nn.Module):
     def call(self, inputs):
         if not self.built:
             self.build(tuple(inputs.shape), device=inputs.device)
+        if self.asymmetric:
+            if self.defer_scale_grad:
+                raise ValueError("an asymmetric layer with defer_scale_grad (data-parallel mode B): the all-reduced dP of a clipped "
+                                 "layer no longer holds the dy of its clipped elements, so neither ds nor db can be recomputed from it")
+            return ops.my_custom_gradient(inputs, self.scale, scale_gradient="ste", grad_scale=self.grad_scale_value(inputs.numel()),
+                                          q_range=self.q_range, rounding=self.rounding, group_size=self.group_size, offset=self.offset)
         if self.q_range is not None:
             return ops.my_custom_gradient(inputs, self.scale, self.penalty_threshold, scale_gradient=self.scale_gradient,
                                           grad_scale=self.grad_scale_value(inputs.numel()) if self.scale_gradient == "ste" else 1.0,
@@ -221,13 +238,28 @@ class CustomQuantizedScaleLayer(nn.Module):
             r += f", rounding={self.rounding!r}"
         if self.group_size is not None:
             r += f", group_size={self.group_size}"
+        if self.asymmetric:
+            r += ", asymmetric=True"
         return r
 
     def init_scale(self, parameter, method):
         """Writes this layer's scale IN PLACE from ``parameter`` (ops.scale_init_group; ``method`` one of ops.SCALE_INITS) with
         the layer's range, rounding and group size and the ``min_value`` of its constraint.  The unbounded quantizer has nothing
-        to cover: ValueError without a range.  One launch, no synchronisation."""
-        ops.check_scale_init(method)
+        to cover: ValueError without a range.  One launch, no synchronisation.
+        An asymmetric layer also takes "minmax" (ops.scale_init_group_minmax: scale and offset from each group's minimum and
+        maximum); under the other methods its scale is written as a symmetric layer's and its offset is set to zero."""
+        ops.check_layer_scale_init(method)
+        if method == "minmax":
+            if not self.asymmetric:
+                raise ValueError('scale_init "minmax" on a symmetric layer: it places each group\'s range over [min, max] through an '
+                                 "offset, which only an asymmetric=True layer has")
+            ops.check_minmax_range(*self.q_range)
+            if not self.built:
+                self.build(tuple(parameter.shape), device=parameter.device)
+            with torch.no_grad():
+                ops.scale_init_group_minmax(parameter.detach(), self.scale.data, self.offset.data, *self.q_range, self.group_size,
+                                            rounding=self.rounding, min_value=self.constraint.min_value)
+            return self.scale
         if self.q_range is None:
             raise ValueError("scale initialisation needs bits or q_range: the unbounded quantizer clips nothing, there is no range "
                              "for the scale to cover")
@@ -236,6 +268,8 @@ class CustomQuantizedScaleLayer(nn.Module):
         with torch.no_grad():
             ops.scale_init_group(parameter.detach(), self.scale.data, *self.q_range, self.group_size, method,
                                  rounding=self.rounding, min_value=self.constraint.min_value)
+            if self.asymmetric:
+                self.offset.data.zero_()
         return self.scale
 
     def quantized_integers(self, parameter, dtype=torch.float32):
@@ -243,10 +277,33 @@ class CustomQuantizedScaleLayer(nn.Module):
         rint(P/s) for ``rounding="nearest"``)."""
         if self.q_range is None:
             return ops.quantized_integers(parameter, self.scale.data, dtype)
+        if self.asymmetric:
+            return ops.fq_forward_group_affine(parameter, self.scale.data, self.offset.data, *self.q_range, self.group_size,
+                                               q_dtype=dtype, rounding=self.rounding)[1]
         if self.group_size is not None:
             return ops.fq_forward_group(parameter, self.scale.data, *self.q_range, self.group_size, q_dtype=dtype,
                                         rounding=self.rounding)[1]
         return ops.fq_forward_clip(parameter, self.scale.data, *self.q_range, q_dtype=dtype, rounding=self.rounding)[1]
+
+
+def check_asymmetric(asymmetric, orientation, q_range, penalty_threshold=None, penalty_rate=None, scale_gradient="ste") -> bool:
+    """``asymmetric`` as a bool, or ValueError naming the reason it cannot be had."""
+    if not asymmetric:
+        return False
+    if orientation != "groupwise":
+        raise ValueError(f'asymmetric=True needs orientation="groupwise", got orientation={orientation!r}: offsets exist per group; a '
+                         "group_size of the line length or more gives per-channel offsets")
+    if q_range is None:
+        raise ValueError("asymmetric=True needs bits or q_range: the offset places a chosen integer range over each group")
+    if penalty_threshold is not None:
+        raise ValueError("asymmetric=True with a penalty_threshold: the nested-quantization vote is defined on the unclipped "
+                         "symmetric quantizer")
+    if penalty_rate is not None:
+        raise ValueError("asymmetric=True with a loss term (penalty_rate): the penalty kernels know scales only, an offset would "
+                         "get no gradient from them")
+    if scale_gradient != "ste":
+        raise ValueError('asymmetric=True needs scale_gradient="ste": the loss-term-only rule has no gradient for an offset')
+    return True
 
 
 def check_groupwise(orientation, group_size, q_range, penalty_threshold=None, penalty_rate=None):
@@ -270,11 +327,11 @@ def check_groupwise(orientation, group_size, q_range, penalty_threshold=None, pe
 
 
 def _nested(penalty_threshold, penalty_rate, orientation, scale_gradient=None, grad_scale=1.0, q_range=None, rounding="floor",
-            group_size=None):
+            group_size=None, asymmetric=False):
     return CustomQuantizedScaleLayer(penalty_threshold=penalty_threshold, initializer=None,
                                      orientation=orientation, penalty_rate=penalty_rate,
                                      scale_gradient=scale_gradient, grad_scale=grad_scale, q_range=q_range,
-                                     rounding=rounding, group_size=group_size)
+                                     rounding=rounding, group_size=group_size, asymmetric=asymmetric)
 
 
 def _as_tensor(a, shape, device):
@@ -288,6 +345,7 @@ class _HostLayer(nn.Module):
     q_range = None
     rounding = "floor"
     group_size = None
+    asymmetric = False
 
     def extra_repr(self):
         r = f"q_range={self.q_range!r}" if self.q_range is not None else ""
@@ -295,7 +353,23 @@ class _HostLayer(nn.Module):
             r += f", rounding={self.rounding!r}"
         if self.group_size is not None:
             r += f", group_size={self.group_size}"
+        if self.asymmetric:
+            r += ", asymmetric=True"
         return r
+
+    def weight_nested(self):
+        """The nested layer of the kernel / ``W`` (the one that may be group-wise and asymmetric; the bias never is)."""
+        return self.nested_q_k_layer if hasattr(self, "nested_q_k_layer") else self.nested_q_w_layer
+
+    def make_asymmetric(self):
+        """Gives the weight quantizer of a constructed group-wise layer an offset per group (models.build_model applies it after
+        ``make_groupwise``); the bias stays symmetric and scalar."""
+        nested = self.weight_nested()
+        check_asymmetric(True, nested.orientation, self.q_range, nested.penalty_threshold, nested.penalty_rate, nested.scale_gradient)
+        self.asymmetric = nested.asymmetric = True
+        if nested.built:
+            param = self.kernel if hasattr(self, "nested_q_k_layer") else self.W
+            nested.build(tuple(param.shape), device=param.device)
 
     def make_groupwise(self, group_size):
         """Switches the weight quantizer of a constructed layer to ``orientation="groupwise"`` with this ``group_size`` and
@@ -322,11 +396,17 @@ class _HostLayer(nn.Module):
 
     def init_scales(self, method):
         """``CustomQuantizedScaleLayer.init_scale`` for the kernel / ``W`` and the bias of a built layer."""
-        ops.check_scale_init(method)
+        ops.check_layer_scale_init(method)
+        if method == "minmax" and not self.asymmetric:
+            raise ValueError(f'{self.name}: scale_init "minmax" on a symmetric layer: it places each group\'s range over [min, max] '
+                             "through an offset, which only an asymmetric=True layer has")
+        if method == "minmax":
+            ops.check_minmax_range(*self.q_range)
         if not self.built:
             raise ValueError(f"{self.name}: scale initialisation reads the weights; build the layer first")
         for _, nested, param in self.scale_pairs():
-            nested.init_scale(param, method)
+            # the bias of an asymmetric layer is symmetric and scalar: "absmax" covers it under "minmax"
+            nested.init_scale(param, "absmax" if method == "minmax" and not nested.asymmetric else method)
 
     def _init_value(self, initializer, shape, device):
         if initializer is None:
@@ -353,16 +433,17 @@ class CustomDenseLayer(_HostLayer):
     def __init__(self, seed=None, units=None, penalty_threshold=None, orientation="scalar", initializer=None,
                  name=None, regularizer=None, trained_weights=None, *, penalty_rate=None, input_shape=None,
                  device=None, scale_gradient=None, grad_scale=1.0, bits=None, signed=True, q_range=None, rounding="floor",
-                 group_size=None, **kwargs):
+                 group_size=None, asymmetric=False, **kwargs):
         super().__init__()
         self.seed = seed
         self.q_range = ops.q_range_of(bits, signed, q_range)      # None: the reference's unbounded quantizer
         ops.check_rounding(rounding, self.q_range is not None)
         self.rounding = rounding
+        self.asymmetric = check_asymmetric(asymmetric, orientation, self.q_range, penalty_threshold, penalty_rate, scale_gradient)
         # groupwise: groups along `in` for every output column, scale (nb, out); the bias keeps its scalar scale
         self.group_size = check_groupwise(orientation, group_size, self.q_range, penalty_threshold, penalty_rate)
         self.nested_q_w_layer = _nested(penalty_threshold, penalty_rate, orientation, scale_gradient, grad_scale, self.q_range, rounding,
-                                        self.group_size)   # NQ-L:222-224
+                                        self.group_size, self.asymmetric)   # NQ-L:222-224
         self.nested_q_b_layer = _nested(penalty_threshold, penalty_rate, "scalar", scale_gradient, grad_scale, self.q_range, rounding)      # NQ-L:225-227
         self.units = units
         self.initializer = initializer
@@ -452,12 +533,13 @@ class _ConvBase(_HostLayer):
                  kernel_size=(3, 3), strides=(1, 1), padding="same", name=None, regularizer=None,
                  trained_weights=None, *, penalty_rate=None, input_shape=None, data_format="NCHW", device=None,
                  kernel_storage=None, scale_gradient=None, grad_scale=1.0, bits=None, signed=True, q_range=None, rounding="floor",
-                 group_size=None, **kwargs):
+                 group_size=None, asymmetric=False, **kwargs):
         super().__init__()
         self.seed = seed
         self.q_range = ops.q_range_of(bits, signed, q_range)      # None: the reference's unbounded quantizer
         ops.check_rounding(rounding, self.q_range is not None)
         self.rounding = rounding
+        self.asymmetric = check_asymmetric(asymmetric, orientation, self.q_range, penalty_threshold, penalty_rate, scale_gradient)
         if kernel_storage is None:
             kernel_storage = _KERNEL_STORAGE[-1]
         if kernel_storage not in ("oihw", "hwio"):
@@ -469,7 +551,7 @@ class _ConvBase(_HostLayer):
             raise ValueError('orientation="groupwise" with kernel_storage="hwio": the groups are defined in the convolution\'s memory '
                              'order (the contiguous (ci, kh, kw) run of an output channel); store the kernel "oihw"')
         self.nested_q_k_layer = _nested(penalty_threshold, penalty_rate, orientation, scale_gradient, grad_scale, self.q_range, rounding,
-                                        self.group_size)      # NQ-L:293-295
+                                        self.group_size, self.asymmetric)      # NQ-L:293-295
         if self._has_bias:
             self.nested_q_b_layer = _nested(penalty_threshold, penalty_rate, "scalar", scale_gradient, grad_scale, self.q_range, rounding)     # NQ-L:296-298
         self.initializer = initializer
@@ -581,14 +663,22 @@ def init_scales(model: nn.Module, method) -> nn.Module:
     ops.SCALE_INITS), then checks all scales with ONE ``isfinite`` reduction -- one synchronisation: this is a host call made
     once, before the optimizer and any graph exist, never inside a capture.  A NaN scale (a weight tensor that holds a NaN or
     an Inf) raises ValueError with the layer's name.  The scales are written in place: pointers taken before stay valid."""
-    ops.check_scale_init(method)
+    ops.check_layer_scale_init(method)
     layers = custom_layers_of(model)
+    if method == "minmax":      # before any launch: every layer must be able to take it
+        for layer in layers:
+            if not layer.asymmetric:
+                raise ValueError(f'scale_init "minmax" on a symmetric layer ({layer.name!r}): it places each group\'s range over '
+                                 "[min, max] through an offset, which only an asymmetric=True layer has")
+            ops.check_minmax_range(*layer.q_range)
     entries = []
     for layer in layers:
         layer.init_scales(method)
         entries += [(layer, what, nested) for what, nested, _ in layer.scale_pairs()]
     if entries:
-        ok = torch.stack([torch.isfinite(nested.scale.detach()).all() for _, _, nested in entries]).cpu().numpy()
+        ok = torch.stack([torch.isfinite(nested.scale.detach()).all() if nested.offset is None else
+                          torch.isfinite(nested.scale.detach()).all() & torch.isfinite(nested.offset.detach()).all()
+                          for _, _, nested in entries]).cpu().numpy()
         for (layer, what, nested), fine in zip(entries, ok):
             if not fine:
                 raise ValueError(f"scale initialisation ({method}) of layer {layer.name!r}: the scale of {what!r} is not finite -- "

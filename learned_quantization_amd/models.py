@@ -294,8 +294,28 @@ def check_group_mode(mode: str, has_range: bool) -> None:
         raise ValueError(f"group_size with mode {mode!r}: group-wise scales train with one of the modes {GROUP_MODES}")
 
 
+def check_asymmetric_model(mode: str, has_range: bool, group_size, kernel_storage=None) -> None:
+    """An asymmetric model needs group-wise scales, a range, mode "ste" and conv kernels in the convolution's memory order."""
+    if group_size is None:
+        raise ValueError("asymmetric=True needs group_size (orientation=\"groupwise\"): offsets exist per group; a group_size of the "
+                         "line length or more gives per-channel offsets")
+    if not has_range:
+        raise ValueError("asymmetric=True needs bits / q_range: the offset places a chosen integer range over each group")
+    if mode in ("cl", "stecl", "nqcl"):
+        raise ValueError(f"asymmetric=True with mode {mode!r}: the loss-term penalty kernels know scales only, an offset would get no "
+                         f"gradient from them; asymmetric layers train with one of the modes {GROUP_MODES}")
+    if mode in ("nq",):
+        raise ValueError(f"asymmetric=True with mode {mode!r}: the nested-quantization vote is defined on the unclipped symmetric "
+                         f"quantizer; asymmetric layers train with one of the modes {GROUP_MODES}")
+    if mode not in GROUP_MODES:
+        raise ValueError(f"asymmetric=True with mode {mode!r}: asymmetric layers train with one of the modes {GROUP_MODES}")
+    if kernel_storage == "hwio":
+        raise ValueError('asymmetric=True with kernel_storage="hwio": the groups and their offsets are defined in the convolution\'s '
+                         'memory order; store the kernel "oihw"')
+
+
 def build_model(config: str, kernel_storage: str = None, grad_scale=None, bits=None, signed=True, q_range=None, rounding="floor",
-                group_size=None, scale_init=None, **kw) -> nn.Module:
+                group_size=None, scale_init=None, asymmetric=False, **kw) -> nn.Module:
     """config: 'mnist' (C1), 'cifar' (C2/C4), 'imagenette' (C3), 'resnet50' (C5, extension).
     ``kernel_storage``: memory order of the conv kernels, "oihw" (default) or "hwio" (layers.py).
     ``grad_scale`` (modes "ste" / "stecl"): factor of every straight-through scale gradient, a float or "rsqrt_group".
@@ -305,18 +325,36 @@ def build_model(config: str, kernel_storage: str = None, grad_scale=None, bits=N
     ``group_size`` (with a range, mode "ste"): every quantised kernel gets group-wise scales, one per ``group_size`` consecutive
     inputs of each output unit (layers.py ``orientation="groupwise"``; it replaces ``orientation``); biases keep a scalar scale.
     ``scale_init`` ("absmax" / "lsq" / "mse"; needs a range and ``device``): every scale starts from its weights
-    (layers.init_scales) instead of the library's initial value, applied after the ranges and group sizes are in place."""
+    (layers.init_scales) instead of the library's initial value, applied after the ranges and group sizes are in place.
+    ``asymmetric`` (with ``group_size``, mode "ste"): every group-wise kernel also learns an offset per group (layers.py
+    ``asymmetric=True``); biases stay symmetric.  ``scale_init="minmax"`` exists for such models only: scale and offset of every
+    group from its minimum and maximum, biases by "absmax"."""
     from .ops import check_rounding
     check_rounding(rounding, bits is not None or q_range is not None)
+    if asymmetric:
+        check_asymmetric_model(kw.get("mode", "nq"), bits is not None or q_range is not None, group_size, kernel_storage)
     if scale_init is not None:
         from .layers import init_scales
-        from .ops import check_scale_init
-        check_scale_init(scale_init)
+        from .ops import check_layer_scale_init, check_minmax_range, q_range_of
+        check_layer_scale_init(scale_init)
         if bits is None and q_range is None:
             raise ValueError("scale_init needs bits / q_range: the unbounded quantizer clips nothing, there is no range to cover")
+        if scale_init == "minmax":
+            if not asymmetric:
+                raise ValueError('scale_init "minmax" on a symmetric model: it places each group\'s range over [min, max] through an '
+                                 "offset, which only asymmetric=True layers have")
+            check_minmax_range(*q_range_of(bits, signed, q_range))
+        model = build_model(config, kernel_storage=kernel_storage, grad_scale=grad_scale, bits=bits, signed=signed, q_range=q_range,
+                            rounding=rounding, group_size=group_size, asymmetric=asymmetric, **kw)
+        return init_scales(model, scale_init)
+    if asymmetric:
+        from .layers import _HostLayer
         model = build_model(config, kernel_storage=kernel_storage, grad_scale=grad_scale, bits=bits, signed=signed, q_range=q_range,
                             rounding=rounding, group_size=group_size, **kw)
-        return init_scales(model, scale_init)
+        for m in model.modules():
+            if isinstance(m, _HostLayer):
+                m.make_asymmetric()
+        return model
     if group_size is not None:
         from .layers import _HostLayer
         check_group_mode(kw.get("mode", "nq"), bits is not None or q_range is not None)

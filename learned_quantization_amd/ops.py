@@ -7,7 +7,8 @@
     /root/reference/CIFAR-10/custom_loss_terms/custom_components/custom_layers.py:49-64
 
 Raw (non-autograd) wrappers ``fq_forward``, ``fq_scale_grad``, ``fq_scale_grad_ste``, ``fq_forward_clip``,
-``fq_backward_clip``, ``fq_forward_group``, ``fq_backward_group``, ``scale_init_group``, ``fq_fwd_bwd_fused``, ``quantized_integers`` ... are thin: argument checking + one C-ABI call each.
+``fq_backward_clip``, ``fq_forward_group``, ``fq_backward_group``, ``fq_forward_group_affine``, ``fq_backward_group_affine``,
+``scale_init_group``, ``scale_init_group_minmax``, ``fq_fwd_bwd_fused``, ``quantized_integers`` ... are thin: argument checking + one C-ABI call each.
 Everything runs on the HIP device; there is no CPU fallback.
 """
 from __future__ import annotations
@@ -240,6 +241,17 @@ def check_scale_init(method) -> int:
     return SCALE_INITS.index(method)
 
 
+LAYER_SCALE_INITS = SCALE_INITS + ("minmax",)      # what layers, models and drivers accept; "minmax" writes scale AND offset
+
+
+def check_layer_scale_init(method) -> str:
+    """``method`` if a layer can be initialised with it (LAYER_SCALE_INITS; "minmax" only where the layer is asymmetric: the
+    layer checks that), or ValueError."""
+    if method not in LAYER_SCALE_INITS:
+        raise ValueError(f"scale_init must be one of {LAYER_SCALE_INITS}, got {method!r}")
+    return method
+
+
 def scale_init_group(parameter: torch.Tensor, scale: torch.Tensor, qmin: int, qmax: int, group_size: Optional[int], method: str,
                      rounding: str = "floor", min_value: float = SCALE_INIT) -> torch.Tensor:
     """Writes ``scale`` IN PLACE from ``parameter`` (include/lq_hip.h, lq_scale_init_group): per group "absmax" (the smallest
@@ -265,6 +277,86 @@ def scale_init_group(parameter: torch.Tensor, scale: torch.Tensor, qmin: int, qm
     _hip.check(lib.lq_scale_init_group(_hip.ptr(p), _hip.ptr(s), qmin, qmax, rnd, m, min_value, R, C, axis, gs,
                                        _hip.stream_ptr(p.device)), "lq_scale_init_group")
     return scale
+
+
+def _offset_like(offset: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
+    b = _hip.require_device_f32(offset, "offset")
+    if b.shape != s.shape:
+        raise ValueError(f"offset shape {tuple(b.shape)} != scale shape {tuple(s.shape)}: one offset per group")
+    return b
+
+
+def fq_forward_group_affine(parameter: torch.Tensor, scale: torch.Tensor, offset: torch.Tensor, qmin: int, qmax: int,
+                            group_size: int, q_dtype: Optional[torch.dtype] = None, *, rounding: str = "floor"):
+    """Asymmetric group-wise forward (include/lq_hip.h, lq_fq_forward_group_affine): ``out = clamp(rnd((P - b) / s)) * s + b``
+    with ``offset`` (b) a matrix of the scale's shape.  Returns ``out``, or ``(out, q)`` with the clamped integers."""
+    qmin, qmax = check_q_range(qmin, qmax)
+    rnd = check_rounding(rounding)
+    lib = _hip.load()
+    p, s, (R, C, axis) = _group_param(parameter, scale, group_size)
+    b = _offset_like(offset, s)
+    out = torch.empty_like(p)
+    q, qd = _q_buffer(p, q_dtype)
+    _hip.check(lib.lq_fq_forward_group_affine(_hip.ptr(p), _hip.ptr(s), _hip.ptr(b), _hip.ptr(out), _hip.ptr(q), qd, qmin, qmax, rnd,
+                                              R, C, axis, int(group_size), _hip.stream_ptr(p.device)), "lq_fq_forward_group_affine")
+    return out if q is None else (out, q)
+
+
+def fq_backward_group_affine(parameter: torch.Tensor, scale: torch.Tensor, offset: torch.Tensor, dy: torch.Tensor, qmin: int,
+                             qmax: int, group_size: int, grad_scale: float = 1.0, offset_grad_scale: Optional[float] = None,
+                             want_ds: bool = True, want_db: bool = True, want_clipped: bool = False, *, rounding: str = "floor"):
+    """Asymmetric group-wise backward (include/lq_hip.h, lq_fq_backward_group_affine).  Returns ``(dP, ds, db, clipped)``: dP
+    with the parameter's strides; ds, db (``offset_grad_scale`` times the sum of dy over the group's clipped elements; the
+    factor defaults to ``grad_scale``, as LSQ+) and clipped (int32 tensor holding the uint32 counts) in the shape of ``scale``,
+    None where not wanted."""
+    qmin, qmax = check_q_range(qmin, qmax)
+    rnd = check_rounding(rounding)
+    lib = _hip.load()
+    p, s, (R, C, axis) = _group_param(parameter, scale, group_size)
+    b = _offset_like(offset, s)
+    d = _hip.require_device_f32(dy, "dy", like=p)
+    dP = torch.empty_like(p)
+    ds = torch.empty_like(s) if want_ds else None
+    db = torch.empty_like(s) if want_db else None
+    clipped = torch.empty_like(s, dtype=torch.int32) if want_clipped else None
+    kb = float(grad_scale if offset_grad_scale is None else offset_grad_scale)
+    need = lib.lq_group_workspace_bytes(R, C, axis, int(group_size))
+    ws = _hip.workspace(p.device, need) if need else None
+    _hip.check(lib.lq_fq_backward_group_affine(_hip.ptr(p), _hip.ptr(s), _hip.ptr(b), _hip.ptr(d), qmin, qmax, rnd, float(grad_scale),
+                                               kb, _hip.ptr(dP), _hip.ptr(ds), _hip.ptr(db), _hip.ptr(clipped), _hip.ptr(ws),
+                                               ws.numel() if ws is not None else 0, R, C, axis, int(group_size),
+                                               _hip.stream_ptr(p.device)), "lq_fq_backward_group_affine")
+    return dP, ds, db, clipped
+
+
+def check_minmax_range(qmin: int, qmax: int) -> None:
+    """"minmax" spreads a group's values over the range: it needs two codes at least and bounds within +-2^22."""
+    if qmin >= qmax:
+        raise ValueError(f'scale_init "minmax" needs a range of two codes at least: [{qmin}, {qmax}] has one, there is no width '
+                         "to spread the group's values over")
+    if qmin < -(1 << 22) or qmax > (1 << 22):
+        raise ValueError(f'scale_init "minmax": range [{qmin}, {qmax}] is outside +-2^22')
+
+
+def scale_init_group_minmax(parameter: torch.Tensor, scale: torch.Tensor, offset: torch.Tensor, qmin: int, qmax: int,
+                            group_size: int, rounding: str = "floor", min_value: float = SCALE_INIT):
+    """Writes ``scale`` and ``offset`` IN PLACE from ``parameter`` (include/lq_hip.h, lq_scale_init_group_minmax): per group the
+    step that spreads [min, max] over the range and the offset that centres it, so that no element is clipped (the header states
+    when).  A group that holds a NaN or an Inf gets NaN in both.  One launch, no synchronisation.  Returns ``(scale, offset)``."""
+    qmin, qmax = check_q_range(qmin, qmax)
+    check_minmax_range(qmin, qmax)
+    rnd = check_rounding(rounding)
+    min_value = float(min_value)
+    if not (min_value > 0.0 and math.isfinite(min_value)):
+        raise ValueError(f"min_value must be a positive finite number, got {min_value!r}")
+    p, s, (R, C, axis) = _group_param(parameter, scale, group_size)
+    b = _offset_like(offset, s)
+    if s is not scale or b is not offset:
+        raise ValueError("scale and offset must be contiguous: they are written in place")
+    lib = _hip.load()
+    _hip.check(lib.lq_scale_init_group_minmax(_hip.ptr(p), _hip.ptr(s), _hip.ptr(b), qmin, qmax, rnd, min_value, R, C, axis,
+                                              int(group_size), _hip.stream_ptr(p.device)), "lq_scale_init_group_minmax")
+    return scale, offset
 
 
 def fq_fwd_bwd_fused(parameter: torch.Tensor, scale: torch.Tensor, dy: torch.Tensor, penalty_threshold: float,
@@ -650,11 +742,33 @@ class _GroupQuantFn(torch.autograd.Function):
         return (dP if ctx.needs_input_grad[0] else None), ds, None, None, None, None, None, None
 
 
+class _GroupAffineQuantFn(torch.autograd.Function):
+    """``_GroupQuantFn`` with an offset per group: forward lq_fq_forward_group_affine, backward lq_fq_backward_group_affine.
+    The offset's gradient is scaled like the scale's (LSQ+)."""
+
+    @staticmethod
+    def forward(ctx, parameter, scale, offset, qmin, qmax, group_size, grad_scale, rounding="floor"):
+        ctx.save_for_backward(parameter, scale, offset)
+        ctx.rounding = rounding
+        ctx.q_range = (int(qmin), int(qmax))
+        ctx.group_size = int(group_size)
+        ctx.grad_scale = float(grad_scale)
+        return fq_forward_group_affine(parameter, scale, offset, qmin, qmax, group_size, rounding=rounding)
+
+    @staticmethod
+    def backward(ctx, dy):
+        parameter, scale, offset = ctx.saved_tensors
+        dP, ds, db, _ = fq_backward_group_affine(parameter, scale, offset, dy, *ctx.q_range, ctx.group_size,
+                                                 grad_scale=ctx.grad_scale, want_ds=ctx.needs_input_grad[1],
+                                                 want_db=ctx.needs_input_grad[2], rounding=ctx.rounding)
+        return (dP if ctx.needs_input_grad[0] else None), ds, db, None, None, None, None, None
+
+
 SCALE_GRADIENTS = (None, "ste")
 
 
 def my_custom_gradient(parameter, scale, penalty_threshold=None, *, scale_gradient=None, grad_scale=1.0, defer_scale_grad=False,
-                       q_range=None, rounding="floor", group_size=None):
+                       q_range=None, rounding="floor", group_size=None, offset=None):
     """The reference op.  With ``penalty_threshold`` -> nested-quantization variant
     (custom_layers.py:49-120); without -> STE-only variant (CL custom_layers.py:49-64).
     ``scale_gradient="ste"`` (not in the reference, only without ``penalty_threshold``): the scale receives the
@@ -667,7 +781,21 @@ def my_custom_gradient(parameter, scale, penalty_threshold=None, *, scale_gradie
     ``rounding="nearest"`` (not in the reference, only with ``q_range``): the integers are rint(P/s), round half to even, instead
     of floor(P/s), and the LSQ residual is rint(t) - t in [-1/2, 1/2].
     ``group_size=gs`` (not in the reference, only with ``q_range``): ``scale`` is a group-wise scale matrix
-    (descriptor.groupwise_scale_shape): one scale per ``gs`` elements along one axis of the parameter's memory."""
+    (descriptor.groupwise_scale_shape): one scale per ``gs`` elements along one axis of the parameter's memory.
+    ``offset=b`` (not in the reference, only with ``group_size`` and ``scale_gradient="ste"``): the asymmetric quantizer
+    ``clamp(rnd((P - b) / s)) * s + b`` with one learned offset per group (``b`` has the scale's shape); gradients go to the
+    parameter, the scale and the offset (LSQ+: the sum of dy over the group's clipped elements, times ``grad_scale``)."""
+    if offset is not None:
+        if group_size is None:
+            raise ValueError("offset needs a group_size: the asymmetric quantizer exists for group-wise scales only (a group_size "
+                             "of the line length or more gives per-channel offsets)")
+        if q_range is None:
+            raise ValueError("offset needs a q_range: the asymmetric quantizer places a chosen integer range over each group")
+        if penalty_threshold is not None:
+            raise ValueError("offset with a penalty_threshold: the nested-quantization vote is defined on the unclipped "
+                             "symmetric quantizer")
+        if scale_gradient != "ste":
+            raise ValueError('offset needs scale_gradient="ste": the loss-term-only rule has no gradient for an offset')
     if group_size is not None:
         if q_range is None:
             raise ValueError("group_size needs a q_range: group-wise scales exist for the clipped quantizer only (the unclipped "
@@ -689,6 +817,8 @@ def my_custom_gradient(parameter, scale, penalty_threshold=None, *, scale_gradie
             raise ValueError("q_range with defer_scale_grad: the all-reduced dP of a clipped layer no longer holds the dy of its "
                              "clipped elements, so ds cannot be recomputed from it")
         qmin, qmax = check_q_range(*q_range)
+        if offset is not None:
+            return _GroupAffineQuantFn.apply(parameter, scale, offset, qmin, qmax, int(group_size), float(grad_scale), rounding)
         if group_size is not None:
             return _GroupQuantFn.apply(parameter, scale, qmin, qmax, int(group_size), float(grad_scale), scale_gradient == "ste",
                                        rounding)

@@ -30,8 +30,8 @@ from . import layers as L
 from . import _hip
 from .ddp import CaptureRefused, DataParallel, capture_with_agreement, control_group
 from .losses import LossLog, SCCEDifference, SCCEInverse, SCCEMaxBin, sparse_categorical_crossentropy
-from .models import INPUT_SHAPES, build_model, check_clip_mode, check_group_mode
-from .ops import ROUNDINGS, SCALE_INITS, check_rounding, q_range_of
+from .models import INPUT_SHAPES, build_model, check_asymmetric_model, check_clip_mode, check_group_mode
+from .ops import LAYER_SCALE_INITS, ROUNDINGS, check_minmax_range, check_rounding, q_range_of
 from .optim import KerasAdam, ScaleAdam, non_scale_parameters, scale_parameters
 
 LOSSES = {"maxbin": SCCEMaxBin, "difference": SCCEDifference, "inverse": SCCEInverse}
@@ -73,8 +73,11 @@ class Trainer:
                  bucket_mb: float = 25.0, overlap: bool = True, graph_collectives: Optional[bool] = None,
                  force_collectives: bool = False, kernel_storage: str = "oihw", loss_values: bool = False,
                  loss_log_capacity: int = 4096, grad_scale=None, bits=None, signed=True, q_range=None, rounding="floor",
-                 clipped_batch: bool = False, group_size=None, group_batch: bool = False, scale_init=None):
-        """``scale_init`` ("absmax" / "lsq" / "mse"; with ``bits`` / ``q_range``): every scale starts from its layer's weights
+                 clipped_batch: bool = False, group_size=None, group_batch: bool = False, scale_init=None, asymmetric: bool = False):
+        """``asymmetric`` (with ``group_size``, a range and mode "ste"; eager, graphed and data-parallel mode "A", per-tensor path
+        only): every group-wise kernel also learns an offset per group (models.build_model); the offsets are stepped by the
+        scales' optimizer, without a lower bound.  ``scale_init="minmax"`` exists for such models only.
+        ``scale_init`` ("absmax" / "lsq" / "mse"; with ``bits`` / ``q_range``): every scale starts from its layer's weights
         (layers.init_scales) instead of the library's initial value, at which a range clips every weight.  It runs once, on the
         device, after the weights are in place and before the optimizers, the batch, the graph and the data-parallel wrapper are
         built: the scales are written in place, and the wrapper's initial broadcast carries them to every rank.
@@ -103,6 +106,20 @@ class Trainer:
         self.mode = mode
         ste = mode in ("ste", "stecl")
         self.group_size = group_size
+        self.asymmetric = bool(asymmetric)
+        if asymmetric:
+            check_asymmetric_model(mode, bits is not None or q_range is not None, group_size, kernel_storage)
+            if batched:
+                raise ValueError("asymmetric=True with batched=True: neither multi-tensor batch (clipped_batch, group_batch) carries "
+                                 "an offset per group; asymmetric layers run on the per-tensor path")
+            if ddp_mode == "B":
+                raise ValueError("asymmetric=True with ddp_mode 'B': it recomputes ds from the all-reduced dP, which no longer holds "
+                                 "the dy of the clipped elements -- the very elements the offset's gradient sums; use ddp_mode 'A'")
+        if scale_init == "minmax":
+            if not asymmetric:
+                raise ValueError('scale_init "minmax" on a symmetric model: it places each group\'s range over [min, max] through an '
+                                 "offset, which only asymmetric=True layers have")
+            check_minmax_range(*q_range_of(bits, signed, q_range))
         if group_size is not None:
             check_group_mode(mode, bits is not None or q_range is not None)
             if batched and (not group_batch or clipped_batch):
@@ -144,7 +161,7 @@ class Trainer:
         # fake-quantised kernel goes to the convolution as written and its weight gradient is dP
         self.model = build_model(config, mode=mode, value=value, seed=seed, orientation=orientation, device=self.device,
                                  kernel_storage=kernel_storage, grad_scale=grad_scale, q_range=self.q_range, rounding=rounding,
-                                 group_size=group_size)
+                                 group_size=group_size, asymmetric=self.asymmetric)
         self.model.to(self.device)
         self.scale_init = scale_init
         if scale_init is not None:
@@ -423,8 +440,23 @@ class Trainer:
         return float(loss), float((p.argmax(1) == y).float().mean())
 
 
+class DriverParser(argparse.ArgumentParser):
+    """Argument parser of both drivers: what the flags refuse in combination is refused here, as a usage error, before any device
+    is touched -- ``--scale-init minmax`` belongs to ``--asymmetric``, which belongs to ``--group-size``."""
+
+    def parse_args(self, args=None, namespace=None):
+        ns = super().parse_args(args, namespace)
+        if getattr(ns, "asymmetric", False) and getattr(ns, "group_size", None) is None:
+            self.error("--asymmetric needs --group-size: offsets exist per group (a group size of the line length or more gives "
+                       "per-channel offsets)")
+        if getattr(ns, "scale_init", None) == "minmax" and not getattr(ns, "asymmetric", False):
+            self.error("--scale-init minmax needs --asymmetric: it places each group's range over [min, max] through an offset, "
+                       "which a symmetric layer does not have")
+        return ns
+
+
 def build_parser():
-    ap = argparse.ArgumentParser()
+    ap = DriverParser()
     ap.add_argument("--config", choices=list(INPUT_SHAPES), default="cifar")
     ap.add_argument("--mode", choices=["nq", "cl", "nqcl", "ste", "stecl"], default="nq")
     ap.add_argument("--value", type=float, default=1e-11, help="penalty_threshold (nq, nqcl) or penalty_rate (cl, stecl); ignored by ste")
@@ -438,9 +470,13 @@ def build_parser():
     ap.add_argument("--group-size", type=int, default=None,
                     help="with --bits and mode ste: group-wise scales, one per N consecutive inputs of each output unit (replaces "
                          "--orientation; biases keep a scalar scale)")
-    ap.add_argument("--scale-init", default=None, choices=list(SCALE_INITS),
+    ap.add_argument("--asymmetric", action="store_true",
+                    help="with --bits, --group-size and mode ste: every group-wise kernel also learns an offset per group (per-tensor "
+                         "path; biases stay symmetric)")
+    ap.add_argument("--scale-init", default=None, choices=list(LAYER_SCALE_INITS),
                     help="with --bits: start every scale from its weights (absmax: nothing clipped; lsq: 2 mean|w| / sqrt(Qp); mse: "
-                         "least squared error below absmax) instead of the library's initial value, which clips every weight")
+                         "least squared error below absmax; minmax, with --asymmetric only: scale and offset from each group's "
+                         "minimum and maximum) instead of the library's initial value, which clips every weight")
     ap.add_argument("--rate", type=float, default=1e-7, help="penalty_rate of the loss term in mode nqcl")
     ap.add_argument("--value-coarse", type=float, default=None,
                     help="resnet50 only: threshold of the 3x3 kernels ('mixed' quantisation intensity); --value is the rest")
@@ -517,7 +553,8 @@ def main(argv=None):
                  grad_scale=(None if args.grad_scale is None else
                              (args.grad_scale if args.grad_scale == "rsqrt_group" else float(args.grad_scale))),
                  bits=args.bits, signed=not args.unsigned, rounding=args.rounding, clipped_batch=args.clipped_batch,
-                 group_size=args.group_size, group_batch=args.group_batch, scale_init=args.scale_init)
+                 group_size=args.group_size, group_batch=args.group_batch, scale_init=args.scale_init,
+                 asymmetric=args.asymmetric)
     do_step = tr.step_graphed if args.graph else tr.step
     g = torch.Generator(device=dev).manual_seed(args.seed + rank)
     batches = [synthetic_batch(args.config, args.batch, dev, g) for _ in range(4)]
@@ -557,6 +594,7 @@ def main(argv=None):
             **({"q_range": list(tr.q_range)} if tr.q_range else {}),
             **({"rounding": tr.rounding} if tr.rounding != "floor" else {}),
             **({"group_size": tr.group_size} if tr.group_size is not None else {}),
+            **({"asymmetric": True} if tr.asymmetric else {}),
             **({"scale_init": tr.scale_init} if tr.scale_init is not None else {}),
             **({"loss_values": True, "loss_log_rows": log_rows[0], "loss_log_dropped": log_rows[1]} if log_rows else {})}))
         if args.export_dir:

@@ -8,7 +8,7 @@
 //
 //   column forms (axis 0)   one unit per (column tile, group); the forward keeps the single-tensor row split (nz blocks per group),
 //                           the backward is one block per group: the LDS merge in slot order needs the whole group in one block
-//   row forms (axis 1)      one unit per kBlock >> log_team (row, group) pairs, log_team by launch_group's rule
+//   row forms (axis 1)      one unit per kBlock >> log_team (row, group) pairs, log_team by group_launch's rule
 //
 // No partials, no finalize, no workspace: the whole backward of a model (masked dP, ds, clip counts) is ONE launch.
 // Upstream gradients and grad_scale travel by value in the kernel arguments (PtrPack 2 KB + CoefPack 1 KB + three words: below
@@ -53,8 +53,8 @@ __global__ __launch_bounds__(kBlock) void k_group_batch(const GroupTask* __restr
     if (t.form <= GROUP_COLS1) {       // block-uniform
         const uint32_t bx = b % t.nbx, rest = b / t.nbx;
         const uint32_t g = rest % (uint32_t)p.nb, z = rest / (uint32_t)p.nb;      // backward: nz == 1, z == 0
-        if (t.form == GROUP_COLS4) group_cols_body<RNE, BWD, 4, kGroupColsLanes4>(p, (int64_t)bx, (int64_t)g, (int)z, (int)t.nz, BWD, sh_sum, sh_cnt);
-        else group_cols_body<RNE, BWD, 1, kGroupColsLanes1>(p, (int64_t)bx, (int64_t)g, (int)z, (int)t.nz, BWD, sh_sum, sh_cnt);
+        if (t.form == GROUP_COLS4) group_cols_body<RNE, BWD, 4, kGroupColsLanes4>(p, (int64_t)bx, (int64_t)g, (int)z, (int)t.nz, BWD, sh_sum, nullptr, sh_cnt);
+        else group_cols_body<RNE, BWD, 1, kGroupColsLanes1>(p, (int64_t)bx, (int64_t)g, (int)z, (int)t.nz, BWD, sh_sum, nullptr, sh_cnt);
     } else if (t.form == GROUP_ROWS4) {
         group_rows_body<RNE, BWD, 4>(p, t.log_team, b);
     } else {

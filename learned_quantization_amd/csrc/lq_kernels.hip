@@ -10,6 +10,9 @@
 //   lq_aux_kernels.hpp  scale-sized kernels (K5c, K6), integer statistics, device self-test
 //   lq_batch.hpp        device side of the multi-tensor batch
 //   lq_pack.hpp         bit-packed integer view: lossless export and exact restore
+//   lq_group.hpp        group-wise (block) scales, symmetric and with an offset: one traversal body per axis
+//   lq_group_batch.hpp  group-wise tensors in one launch per pass
+//   lq_scale_init.hpp   scales and offsets from the weights: absmax / LSQ / MSE / min-max on the group-wise unit shapes
 //   this file           host side: traversal plan, launchers, the extern "C" entry points
 //
 // The path is elementwise + per-group reductions: HBM-bound, no MFMA.  Design rules
@@ -52,7 +55,6 @@
 #include "lq_group.hpp"
 #include "lq_group_batch.hpp"
 #include "lq_scale_init.hpp"
-#include "lq_group_affine.hpp"
 
 namespace lq {
 
@@ -315,6 +317,13 @@ static int check_hip(const char* what) {
 }
 
 static bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
+
+// the optional integer view of a forward: q and q_dtype come together or not at all
+static int check_q_view(const char* fn, const void* q, int q_dtype) {
+    if (q_dtype < LQ_Q_NONE || q_dtype > LQ_Q_I8) return fail(LQ_EINVAL, "%s: bad q_dtype %d", fn, q_dtype);
+    if ((q != nullptr) != (q_dtype != LQ_Q_NONE)) return fail(LQ_EINVAL, "%s: q and q_dtype disagree", fn);
+    return LQ_OK;
+}
 
 static int check_desc(int64_t outer, int64_t G, int64_t inner) {
     if (outer <= 0 || G <= 0 || inner <= 0) return fail(LQ_EINVAL, "descriptor extents must be positive (outer=%lld G=%lld inner=%lld)", (long long)outer, (long long)G, (long long)inner);
@@ -1109,8 +1118,7 @@ int lq_fq_forward(const float* P, const float* s, float* out, void* q, int q_dty
     LQ_REQUIRE_PTR(P);
     LQ_REQUIRE_PTR(s);
     if (!out && !q) return fail(LQ_EINVAL, "lq_fq_forward: both out and q are NULL");
-    if (q_dtype < LQ_Q_NONE || q_dtype > LQ_Q_I8) return fail(LQ_EINVAL, "lq_fq_forward: bad q_dtype %d", q_dtype);
-    if ((q != nullptr) != (q_dtype != LQ_Q_NONE)) return fail(LQ_EINVAL, "lq_fq_forward: q and q_dtype disagree");
+    if ((rc = check_q_view(__func__, q, q_dtype))) return rc;
     Plan pl = make_plan(outer, G, inner);
     Params p = base_params(P, s, outer, G, inner);
     p.q = q;
@@ -1268,8 +1276,7 @@ static int clip_forward(const char* fn, const float* P, const float* s, float* o
     LQ_REQUIRE_PTR_FN(fn, out);
     if ((rc = check_clip_range(fn, qmin, qmax))) return rc;
     if ((rc = check_rounding(fn, rounding))) return rc;
-    if (q_dtype < LQ_Q_NONE || q_dtype > LQ_Q_I8) return fail(LQ_EINVAL, "%s: bad q_dtype %d", fn, q_dtype);
-    if ((q != nullptr) != (q_dtype != LQ_Q_NONE)) return fail(LQ_EINVAL, "%s: q and q_dtype disagree", fn);
+    if ((rc = check_q_view(fn, q, q_dtype))) return rc;
     Plan pl = make_plan(outer, G, inner, kBlock);      // generic traversal bodies: 256-thread units at every size (kStreamOp)
     Params p = base_params(P, s, outer, G, inner);
     p.out = out;
@@ -1332,10 +1339,11 @@ int lq_fq_backward_clip(const float* P, const float* s, const float* dy, int32_t
     return clip_backward(__func__, P, s, dy, qmin, qmax, LQ_ROUND_FLOOR, grad_scale, dP, ds, clipped, ws, ws_bytes, outer, G, inner, stream);
 }
 
-// ---- group-wise (block) scales of the clipped pair (lq_group.hpp) ----
+// ---- group-wise (block) scales of the clipped pair, symmetric and with an offset, and their initialisation ----
+// (lq_group.hpp, lq_scale_init.hpp)
 // Dispatch is a pure function of the arguments: axis picks the traversal, V = 4 (float4) needs C % 4 == 0 (and gs % 4 == 0 on
 // axis 1) and every dense base 16-byte aligned, anything else that is 4-byte aligned runs the scalar form.  Neither form has a
-// second stage: the workspace size is 0 for every shape.
+// second stage: the workspace size is 0 for every shape.  Scale, offset, ds and db are read and written one element at a time.
 static int check_group(const char* fn, int64_t R, int64_t C, int axis, int64_t gs) {
     if (R <= 0 || C <= 0) return fail(LQ_EINVAL, "%s: extents must be positive (R=%lld C=%lld)", fn, (long long)R, (long long)C);
     if ((double)R * (double)C >= 2147483648.0) return fail(LQ_EINVAL, "%s: R * C = %lld * %lld is not below 2^31", fn, (long long)R, (long long)C);
@@ -1360,47 +1368,136 @@ static GroupParams group_params(const float* P, const float* s, int32_t qmin, in
     return p;
 }
 
-// The launch shape of a group-wise tensor; the single-tensor launch and the batch's task table (lq_group_batch_create) both ask here,
-// which keeps a tensor's form and team width the same on either path.
-// Column forms: blocks that share the rows of a group in the forward.  A block per (column tile, group) leaves the chip half empty
-// on weight-sized tensors; `groups_y` is the group extent of the grid.
-static int group_cols_row_split(const GroupParams& p, bool vec, int64_t tiles_x, int64_t groups_y) {
-    const int slots = kBlock / (vec ? kGroupColsLanes4 : kGroupColsLanes1);
-    int nz = 1;
-    while (nz < 4 && tiles_x * groups_y * nz < 2048 && (int64_t)slots * nz * 4 <= p.gs) nz *= 2;
-    return nz;
-}
-static int64_t group_cols_tiles(const GroupParams& p, bool vec) {
-    const int cols = vec ? kGroupColsLanes4 * 4 : kGroupColsLanes1;
-    return (p.C + cols - 1) / cols;
-}
-// Row forms: log2 of the lanes per (row, group) pair: about four accesses per lane
-static int group_rows_log_team(const GroupParams& p, bool vec) {
-    const int64_t items = (p.gs + (vec ? 3 : 0)) / (vec ? 4 : 1);
-    int log_team = 0;
-    while (log_team < 6 && ((int64_t)4 << log_team) < items) ++log_team;
-    return log_team;
-}
 static bool group_vec_ok(const GroupParams& p, int axis) { return p.C % 4 == 0 && (axis == 0 || p.gs % 4 == 0); }
 
-extern "C++" {      // a template inside the C-linkage block
-template <bool RNE, bool BWD>
-static int launch_group(const GroupParams& p, int axis, bool vec, hipStream_t st) {
+// The launch shape of a group-wise tensor.  This is the ONE statement of the rule: the forward and backward pairs (symmetric and
+// with an offset), both scale initialisations and the batch's task table (fill_group_task) all ask here, which keeps a tensor's
+// form, team width and row split the same on every path.
+struct GroupLaunch {
+    int32_t form;         // GROUP_* of lq_group_batch.hpp: axis picks columns / rows, `vec` V = 4 / V = 1
+    dim3 grid;
+    int log_team;         // row forms: log2 of the lanes per (row, group) pair
+    uint32_t nbx, nz;     // column forms: column tiles (grid.x) and blocks that share the rows of a group (grid.z)
+    uint32_t blocks;      // of the grid
+};
+// `max_groups_y`, the group extent of a column grid.  A single-tensor kernel strides over the groups from kGroupGridY on; the batch
+// has one block per (tile, group, z) and passes kGroupEveryGroup.  The two differ only above 32768 groups, where the row split
+// (the one thing that reads the extent) is past its 2048-block cap on either path.
+constexpr int64_t kGroupGridY = 32768;
+constexpr int64_t kGroupEveryGroup = INT32_MAX;
+
+// row_split: the forward of the column forms, which has nothing to merge, may share the rows of a group among up to 4 blocks (a
+// block per (column tile, group) leaves the chip half empty on weight-sized tensors); whoever needs a whole group in one block
+// (backward, scale initialisation) passes false.
+static GroupLaunch group_launch(const GroupParams& p, int axis, bool vec, bool row_split, int64_t max_groups_y) {
+    GroupLaunch L{};
+    L.nbx = L.nz = 1;
     if (axis == 0) {
-        dim3 grid((unsigned)group_cols_tiles(p, vec), (unsigned)std::min<int32_t>(p.nb, 32768));
-        if (!BWD) grid.z = (unsigned)group_cols_row_split(p, vec, grid.x, grid.y);
-        if (vec) hipLaunchKernelGGL((k_group_cols<RNE, BWD, 4, kGroupColsLanes4>), grid, dim3(kBlock), 0, st, p);
-        else hipLaunchKernelGGL((k_group_cols<RNE, BWD, 1, kGroupColsLanes1>), grid, dim3(kBlock), 0, st, p);
-        return check_hip("group-wise column launch");
+        const int lanes = vec ? kGroupColsLanes4 : kGroupColsLanes1, cols = lanes * (vec ? 4 : 1), slots = kBlock / lanes;
+        const int64_t groups_y = std::min<int64_t>(p.nb, max_groups_y);
+        L.form = vec ? GROUP_COLS4 : GROUP_COLS1;
+        L.nbx = (uint32_t)((p.C + cols - 1) / cols);
+        while (row_split && L.nz < 4 && (int64_t)L.nbx * groups_y * L.nz < 2048 && (int64_t)slots * L.nz * 4 <= p.gs) L.nz *= 2;
+        L.grid = dim3(L.nbx, (unsigned)groups_y, L.nz);
+    } else {
+        const int64_t items = (p.gs + (vec ? 3 : 0)) / (vec ? 4 : 1);      // about four accesses per lane
+        while (L.log_team < 6 && ((int64_t)4 << L.log_team) < items) ++L.log_team;
+        const int64_t pairs = (int64_t)p.R * p.nb, per_block = kBlock >> L.log_team;
+        L.form = vec ? GROUP_ROWS4 : GROUP_ROWS1;
+        L.grid = dim3((unsigned)((pairs + per_block - 1) / per_block));
     }
-    const int log_team = group_rows_log_team(p, vec);
-    const int64_t pairs = (int64_t)p.R * p.nb, per_block = kBlock >> log_team;
-    const dim3 grid((unsigned)((pairs + per_block - 1) / per_block));
-    if (vec) hipLaunchKernelGGL((k_group_rows<RNE, BWD, 4>), grid, dim3(kBlock), 0, st, p, log_team);
-    else hipLaunchKernelGGL((k_group_rows<RNE, BWD, 1>), grid, dim3(kBlock), 0, st, p, log_team);
-    return check_hip("group-wise row launch");
+    L.blocks = L.grid.x * L.grid.y * L.grid.z;
+    return L;
+}
+
+extern "C++" {      // templates inside the C-linkage block
+// The four instantiations of a kernel family, in launch_group_form's order: columns V = 4, V = 1, rows V = 4, V = 1
+#define LQ_GROUP_FAMILY(COLS, ROWS, ...) \
+    COLS<__VA_ARGS__, 4, kGroupColsLanes4>, COLS<__VA_ARGS__, 1, kGroupColsLanes1>, ROWS<__VA_ARGS__, 4>, ROWS<__VA_ARGS__, 1>
+
+// Launches the member of a family that the form names; `family` opens the message of a failed launch
+template <class Args>
+static int launch_group_form(const GroupLaunch& L, void (*cols4)(Args), void (*cols1)(Args), void (*rows4)(Args, int),
+                             void (*rows1)(Args, int), const Args& a, const char* family, hipStream_t st) {
+    const bool cols = L.form <= GROUP_COLS1;
+    if (cols) hipLaunchKernelGGL(L.form == GROUP_COLS4 ? cols4 : cols1, L.grid, dim3(kBlock), 0, st, a);
+    else hipLaunchKernelGGL(L.form == GROUP_ROWS4 ? rows4 : rows1, L.grid, dim3(kBlock), 0, st, a, L.log_team);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(LQ_EHIP, "%s %s launch: %s", family, cols ? "column" : "row", hipGetErrorString(e));
+    return LQ_OK;
+}
+
+// PT: GroupParams or GroupAffineParams.  The rounding is a template parameter of the kernels: none tests a flag
+template <bool BWD, class PT>
+static int launch_group(const PT& pp, int axis, bool vec, int rounding, void* stream) {
+    const GroupLaunch L = group_launch(group_base(pp), axis, vec, !BWD, kGroupGridY);
+    const bool rne = rounding == LQ_ROUND_NEAREST_EVEN;
+    hipStream_t st = (hipStream_t)stream;
+    if constexpr (kGroupHasOffset<PT>) {
+        if (rne) return launch_group_form(L, LQ_GROUP_FAMILY(k_group_affine_cols, k_group_affine_rows, true, BWD), pp, "affine group-wise", st);
+        return launch_group_form(L, LQ_GROUP_FAMILY(k_group_affine_cols, k_group_affine_rows, false, BWD), pp, "affine group-wise", st);
+    } else {
+        if (rne) return launch_group_form(L, LQ_GROUP_FAMILY(k_group_cols, k_group_rows, true, BWD), pp, "group-wise", st);
+        return launch_group_form(L, LQ_GROUP_FAMILY(k_group_cols, k_group_rows, false, BWD), pp, "group-wise", st);
+    }
+}
+
+// Scale initialisation takes the group-wise BACKWARD's shape (no row split: a block owns whole groups), so alignment handling and
+// dead lanes / teams are the code that pair already runs.
+template <int M, bool RNE>
+static int launch_scale_init(const InitParams& ip, const GroupParams& gp, int axis, bool vec, const char* family, void* stream) {
+    return launch_group_form(group_launch(gp, axis, vec, false, kGroupGridY), LQ_GROUP_FAMILY(k_init_cols, k_init_rows, M, RNE), ip,
+                             family, (hipStream_t)stream);
 }
 }  // extern "C++"
+
+// What the group forward entry points check and fill in common; affine: the offset b is an argument
+static int group_forward_setup(const char* fn, const float* P, const float* s, bool affine, const float* b, float* out, void* q,
+                               int q_dtype, int32_t qmin, int32_t qmax, int rounding, int64_t R, int64_t C, int axis, int64_t gs,
+                               GroupParams& p, bool& vec) {
+    int rc = check_group(fn, R, C, axis, gs);
+    if (rc) return rc;
+    LQ_REQUIRE_PTR_FN(fn, P);
+    LQ_REQUIRE_PTR_FN(fn, s);
+    if (affine) LQ_REQUIRE_PTR_FN(fn, b);
+    LQ_REQUIRE_PTR_FN(fn, out);
+    if ((rc = check_clip_range(fn, qmin, qmax))) return rc;
+    if ((rc = check_rounding(fn, rounding))) return rc;
+    if ((rc = check_q_view(fn, q, q_dtype))) return rc;
+    if (q && q_dtype != LQ_Q_I8 && !aligned(q, 4)) return fail(LQ_EALIGN, "%s: q is not 4-byte aligned", fn);
+    p = group_params(P, s, qmin, qmax, R, C, axis, gs);
+    p.out = out;
+    p.q = q;
+    p.q_dtype = q_dtype;
+    vec = group_vec_ok(p, axis) && aligned(P, 16) && aligned(out, 16);
+    return LQ_OK;
+}
+
+// The same for the backward entry points; affine: b and the optional db are arguments
+static int group_backward_setup(const char* fn, const float* P, const float* s, bool affine, const float* b, const float* dy,
+                                int32_t qmin, int32_t qmax, int rounding, float grad_scale, float* dP, float* ds, float* db,
+                                uint32_t* clipped, int64_t R, int64_t C, int axis, int64_t gs, GroupParams& p, bool& vec) {
+    int rc = check_group(fn, R, C, axis, gs);
+    if (rc) return rc;
+    LQ_REQUIRE_PTR_FN(fn, P);
+    LQ_REQUIRE_PTR_FN(fn, s);
+    if (affine) LQ_REQUIRE_PTR_FN(fn, b);
+    LQ_REQUIRE_PTR_FN(fn, dy);
+    LQ_REQUIRE_PTR_FN(fn, dP);
+    if (ds && !aligned(ds, 4)) return fail(LQ_EALIGN, "%s: ds is not 4-byte aligned", fn);
+    if (affine && db && !aligned(db, 4)) return fail(LQ_EALIGN, "%s: db is not 4-byte aligned", fn);
+    if (clipped && !aligned(clipped, 4)) return fail(LQ_EALIGN, "%s: clipped is not 4-byte aligned", fn);
+    if ((rc = check_clip_range(fn, qmin, qmax))) return rc;
+    if ((rc = check_rounding(fn, rounding))) return rc;
+    p = group_params(P, s, qmin, qmax, R, C, axis, gs);
+    p.dy = dy;
+    p.out = dP;
+    p.k = grad_scale;
+    p.ds = ds;
+    p.clipped = clipped;
+    vec = group_vec_ok(p, axis) && aligned(P, 16) && aligned(dy, 16) && aligned(dP, 16);
+    return LQ_OK;
+}
 
 size_t lq_group_workspace_bytes(int64_t R, int64_t C, int axis, int64_t gs) {
     (void)R; (void)C; (void)axis; (void)gs;
@@ -1409,72 +1506,65 @@ size_t lq_group_workspace_bytes(int64_t R, int64_t C, int axis, int64_t gs) {
 
 int lq_fq_forward_group(const float* P, const float* s, float* out, void* q, int q_dtype, int32_t qmin, int32_t qmax, int rounding,
                         int64_t R, int64_t C, int axis, int64_t gs, void* stream) {
-    const char* fn = __func__;
-    int rc = check_group(fn, R, C, axis, gs);
-    if (rc) return rc;
-    LQ_REQUIRE_PTR_FN(fn, P);
-    LQ_REQUIRE_PTR_FN(fn, s);
-    LQ_REQUIRE_PTR_FN(fn, out);
-    if ((rc = check_clip_range(fn, qmin, qmax))) return rc;
-    if ((rc = check_rounding(fn, rounding))) return rc;
-    if (q_dtype < LQ_Q_NONE || q_dtype > LQ_Q_I8) return fail(LQ_EINVAL, "%s: bad q_dtype %d", fn, q_dtype);
-    if ((q != nullptr) != (q_dtype != LQ_Q_NONE)) return fail(LQ_EINVAL, "%s: q and q_dtype disagree", fn);
-    if (q && q_dtype != LQ_Q_I8 && !aligned(q, 4)) return fail(LQ_EALIGN, "%s: q is not 4-byte aligned", fn);
-    GroupParams p = group_params(P, s, qmin, qmax, R, C, axis, gs);
-    p.out = out;
-    p.q = q;
-    p.q_dtype = q_dtype;
-    const bool vec = group_vec_ok(p, axis) && aligned(P, 16) && aligned(out, 16);
-    if (rounding == LQ_ROUND_NEAREST_EVEN) return launch_group<true, false>(p, axis, vec, (hipStream_t)stream);
-    return launch_group<false, false>(p, axis, vec, (hipStream_t)stream);
+    GroupParams p;
+    bool vec;
+    const int rc = group_forward_setup(__func__, P, s, false, nullptr, out, q, q_dtype, qmin, qmax, rounding, R, C, axis, gs, p, vec);
+    return rc ? rc : launch_group<false>(p, axis, vec, rounding, stream);
 }
 
 int lq_fq_backward_group(const float* P, const float* s, const float* dy, int32_t qmin, int32_t qmax, int rounding, float grad_scale,
                          float* dP, float* ds, uint32_t* clipped, void* ws, size_t ws_bytes, int64_t R, int64_t C, int axis,
                          int64_t gs, void* stream) {
-    const char* fn = __func__;
     (void)ws; (void)ws_bytes;      // lq_group_workspace_bytes() == 0: ws may be NULL and is never touched
-    int rc = check_group(fn, R, C, axis, gs);
-    if (rc) return rc;
-    LQ_REQUIRE_PTR_FN(fn, P);
-    LQ_REQUIRE_PTR_FN(fn, s);
-    LQ_REQUIRE_PTR_FN(fn, dy);
-    LQ_REQUIRE_PTR_FN(fn, dP);
-    if (ds && !aligned(ds, 4)) return fail(LQ_EALIGN, "%s: ds is not 4-byte aligned", fn);
-    if (clipped && !aligned(clipped, 4)) return fail(LQ_EALIGN, "%s: clipped is not 4-byte aligned", fn);
-    if ((rc = check_clip_range(fn, qmin, qmax))) return rc;
-    if ((rc = check_rounding(fn, rounding))) return rc;
-    GroupParams p = group_params(P, s, qmin, qmax, R, C, axis, gs);
-    p.dy = dy;
-    p.out = dP;
-    p.k = grad_scale;
-    p.ds = ds;
-    p.clipped = clipped;
-    const bool vec = group_vec_ok(p, axis) && aligned(P, 16) && aligned(dy, 16) && aligned(dP, 16);
-    if (rounding == LQ_ROUND_NEAREST_EVEN) return launch_group<true, true>(p, axis, vec, (hipStream_t)stream);
-    return launch_group<false, true>(p, axis, vec, (hipStream_t)stream);
+    GroupParams p;
+    bool vec;
+    const int rc = group_backward_setup(__func__, P, s, false, nullptr, dy, qmin, qmax, rounding, grad_scale, dP, ds, nullptr, clipped,
+                                        R, C, axis, gs, p, vec);
+    return rc ? rc : launch_group<true>(p, axis, vec, rounding, stream);
+}
+
+int lq_fq_forward_group_affine(const float* P, const float* s, const float* b, float* out, void* q, int q_dtype, int32_t qmin,
+                               int32_t qmax, int rounding, int64_t R, int64_t C, int axis, int64_t gs, void* stream) {
+    GroupAffineParams ap{};
+    bool vec;
+    const int rc = group_forward_setup(__func__, P, s, true, b, out, q, q_dtype, qmin, qmax, rounding, R, C, axis, gs, ap.g, vec);
+    ap.b = b;
+    return rc ? rc : launch_group<false>(ap, axis, vec, rounding, stream);
+}
+
+int lq_fq_backward_group_affine(const float* P, const float* s, const float* b, const float* dy, int32_t qmin, int32_t qmax,
+                                int rounding, float grad_scale, float offset_grad_scale, float* dP, float* ds, float* db,
+                                uint32_t* clipped, void* ws, size_t ws_bytes, int64_t R, int64_t C, int axis, int64_t gs,
+                                void* stream) {
+    (void)ws; (void)ws_bytes;      // lq_group_workspace_bytes() == 0: ws may be NULL and is never touched
+    GroupAffineParams ap{};
+    bool vec;
+    const int rc = group_backward_setup(__func__, P, s, true, b, dy, qmin, qmax, rounding, grad_scale, dP, ds, db, clipped, R, C, axis,
+                                        gs, ap.g, vec);
+    ap.b = b;
+    ap.db = db;
+    ap.kb = offset_grad_scale;
+    return rc ? rc : launch_group<true>(ap, axis, vec, rounding, stream);
 }
 
 // ---- scale initialisation (lq_scale_init.hpp) ----
-// The launch shape is the group-wise BACKWARD's: the same host rule picks V, TX, the team width and the grid (no row split: a block
-// owns whole groups), so alignment handling and dead lanes / teams are the code that pair already runs.
-extern "C++" {
-template <int M, bool RNE>
-static int launch_scale_init(const InitParams& ip, const GroupParams& gp, int axis, bool vec, hipStream_t st) {
-    if (axis == 0) {
-        const dim3 grid((unsigned)group_cols_tiles(gp, vec), (unsigned)std::min<int32_t>(gp.nb, 32768));
-        if (vec) hipLaunchKernelGGL((k_init_cols<M, RNE, 4, kGroupColsLanes4>), grid, dim3(kBlock), 0, st, ip);
-        else hipLaunchKernelGGL((k_init_cols<M, RNE, 1, kGroupColsLanes1>), grid, dim3(kBlock), 0, st, ip);
-        return check_hip("scale-init column launch");
-    }
-    const int log_team = group_rows_log_team(gp, vec);
-    const int64_t pairs = (int64_t)gp.R * gp.nb, per_block = kBlock >> log_team;
-    const dim3 grid((unsigned)((pairs + per_block - 1) / per_block));
-    if (vec) hipLaunchKernelGGL((k_init_rows<M, RNE, 4>), grid, dim3(kBlock), 0, st, ip, log_team);
-    else hipLaunchKernelGGL((k_init_rows<M, RNE, 1>), grid, dim3(kBlock), 0, st, ip, log_team);
-    return check_hip("scale-init row launch");
+static int check_init_min_value(const char* fn, float min_value) {
+    if (!(min_value > 0.0f) || !(min_value <= 3.4028234663852886e+38f)) return fail(LQ_EINVAL, "%s: min_value %g is not a positive finite number", fn, (double)min_value);
+    return LQ_OK;
 }
-}  // extern "C++"
+
+// the fields every method reads; lo / hi / sqrt_qp or n / c / b are the caller's
+static InitParams init_params(const GroupParams& gp, float* s, float min_value) {
+    InitParams ip{};
+    ip.P = gp.P;
+    ip.s = s;
+    ip.min_value = min_value;
+    ip.R = gp.R;
+    ip.C = gp.C;
+    ip.gs = gp.gs;
+    ip.nb = gp.nb;
+    return ip;
+}
 
 int lq_scale_init_group(const float* P, float* s, int32_t qmin, int32_t qmax, int rounding, int method, float min_value,
                         int64_t R, int64_t C, int axis, int64_t gs, void* stream) {
@@ -1486,106 +1576,17 @@ int lq_scale_init_group(const float* P, float* s, int32_t qmin, int32_t qmax, in
     if ((rc = check_clip_range(fn, qmin, qmax))) return rc;
     if ((rc = check_rounding(fn, rounding))) return rc;
     if (method != LQ_INIT_ABSMAX && method != LQ_INIT_LSQ && method != LQ_INIT_MSE) return fail(LQ_EINVAL, "%s: bad method %d", fn, method);
-    if (!(min_value > 0.0f) || !(min_value <= 3.4028234663852886e+38f)) return fail(LQ_EINVAL, "%s: min_value %g is not a positive finite number", fn, (double)min_value);
+    if ((rc = check_init_min_value(fn, min_value))) return rc;
     const GroupParams gp = group_params(P, s, qmin, qmax, R, C, axis, gs);
-    InitParams ip{};
-    ip.P = P;
-    ip.s = s;
+    InitParams ip = init_params(gp, s, min_value);
     ip.lo = gp.lo;
     ip.hi = gp.hi;
-    ip.min_value = min_value;
     ip.sqrt_qp = sqrt((double)(qmax > 0 ? qmax : -(int64_t)qmin));
-    ip.R = gp.R;
-    ip.C = gp.C;
-    ip.gs = gp.gs;
-    ip.nb = gp.nb;
     const bool vec = group_vec_ok(gp, axis) && aligned(P, 16);
-    hipStream_t st = (hipStream_t)stream;
-    if (method == LQ_INIT_ABSMAX) return launch_scale_init<LQ_INIT_ABSMAX, false>(ip, gp, axis, vec, st);
-    if (method == LQ_INIT_LSQ) return launch_scale_init<LQ_INIT_LSQ, false>(ip, gp, axis, vec, st);
-    if (rounding == LQ_ROUND_NEAREST_EVEN) return launch_scale_init<LQ_INIT_MSE, true>(ip, gp, axis, vec, st);
-    return launch_scale_init<LQ_INIT_MSE, false>(ip, gp, axis, vec, st);
-}
-
-// ---- asymmetric group-wise scales (lq_group_affine.hpp) ----
-// The launch shape is the symmetric pair's for the same geometry and alignment: the same helpers pick V, TX, the team width, the
-// forward's row split and the grid.  The offset and db are read and written one element at a time, like s and ds.
-extern "C++" {
-template <bool RNE, bool BWD>
-static int launch_group_affine(const GroupAffineParams& ap, int axis, bool vec, hipStream_t st) {
-    const GroupParams& p = ap.g;
-    if (axis == 0) {
-        dim3 grid((unsigned)group_cols_tiles(p, vec), (unsigned)std::min<int32_t>(p.nb, 32768));
-        if (!BWD) grid.z = (unsigned)group_cols_row_split(p, vec, grid.x, grid.y);
-        if (vec) hipLaunchKernelGGL((k_group_affine_cols<RNE, BWD, 4, kGroupColsLanes4>), grid, dim3(kBlock), 0, st, ap);
-        else hipLaunchKernelGGL((k_group_affine_cols<RNE, BWD, 1, kGroupColsLanes1>), grid, dim3(kBlock), 0, st, ap);
-        return check_hip("affine group-wise column launch");
-    }
-    const int log_team = group_rows_log_team(p, vec);
-    const int64_t pairs = (int64_t)p.R * p.nb, per_block = kBlock >> log_team;
-    const dim3 grid((unsigned)((pairs + per_block - 1) / per_block));
-    if (vec) hipLaunchKernelGGL((k_group_affine_rows<RNE, BWD, 4>), grid, dim3(kBlock), 0, st, ap, log_team);
-    else hipLaunchKernelGGL((k_group_affine_rows<RNE, BWD, 1>), grid, dim3(kBlock), 0, st, ap, log_team);
-    return check_hip("affine group-wise row launch");
-}
-}  // extern "C++"
-
-int lq_fq_forward_group_affine(const float* P, const float* s, const float* b, float* out, void* q, int q_dtype, int32_t qmin,
-                               int32_t qmax, int rounding, int64_t R, int64_t C, int axis, int64_t gs, void* stream) {
-    const char* fn = __func__;
-    int rc = check_group(fn, R, C, axis, gs);
-    if (rc) return rc;
-    LQ_REQUIRE_PTR_FN(fn, P);
-    LQ_REQUIRE_PTR_FN(fn, s);
-    LQ_REQUIRE_PTR_FN(fn, b);
-    LQ_REQUIRE_PTR_FN(fn, out);
-    if ((rc = check_clip_range(fn, qmin, qmax))) return rc;
-    if ((rc = check_rounding(fn, rounding))) return rc;
-    if (q_dtype < LQ_Q_NONE || q_dtype > LQ_Q_I8) return fail(LQ_EINVAL, "%s: bad q_dtype %d", fn, q_dtype);
-    if ((q != nullptr) != (q_dtype != LQ_Q_NONE)) return fail(LQ_EINVAL, "%s: q and q_dtype disagree", fn);
-    if (q && q_dtype != LQ_Q_I8 && !aligned(q, 4)) return fail(LQ_EALIGN, "%s: q is not 4-byte aligned", fn);
-    GroupAffineParams ap{};
-    ap.g = group_params(P, s, qmin, qmax, R, C, axis, gs);
-    ap.g.out = out;
-    ap.g.q = q;
-    ap.g.q_dtype = q_dtype;
-    ap.b = b;
-    const bool vec = group_vec_ok(ap.g, axis) && aligned(P, 16) && aligned(out, 16);
-    if (rounding == LQ_ROUND_NEAREST_EVEN) return launch_group_affine<true, false>(ap, axis, vec, (hipStream_t)stream);
-    return launch_group_affine<false, false>(ap, axis, vec, (hipStream_t)stream);
-}
-
-int lq_fq_backward_group_affine(const float* P, const float* s, const float* b, const float* dy, int32_t qmin, int32_t qmax,
-                                int rounding, float grad_scale, float offset_grad_scale, float* dP, float* ds, float* db,
-                                uint32_t* clipped, void* ws, size_t ws_bytes, int64_t R, int64_t C, int axis, int64_t gs,
-                                void* stream) {
-    const char* fn = __func__;
-    (void)ws; (void)ws_bytes;      // lq_group_workspace_bytes() == 0: ws may be NULL and is never touched
-    int rc = check_group(fn, R, C, axis, gs);
-    if (rc) return rc;
-    LQ_REQUIRE_PTR_FN(fn, P);
-    LQ_REQUIRE_PTR_FN(fn, s);
-    LQ_REQUIRE_PTR_FN(fn, b);
-    LQ_REQUIRE_PTR_FN(fn, dy);
-    LQ_REQUIRE_PTR_FN(fn, dP);
-    if (ds && !aligned(ds, 4)) return fail(LQ_EALIGN, "%s: ds is not 4-byte aligned", fn);
-    if (db && !aligned(db, 4)) return fail(LQ_EALIGN, "%s: db is not 4-byte aligned", fn);
-    if (clipped && !aligned(clipped, 4)) return fail(LQ_EALIGN, "%s: clipped is not 4-byte aligned", fn);
-    if ((rc = check_clip_range(fn, qmin, qmax))) return rc;
-    if ((rc = check_rounding(fn, rounding))) return rc;
-    GroupAffineParams ap{};
-    ap.g = group_params(P, s, qmin, qmax, R, C, axis, gs);
-    ap.g.dy = dy;
-    ap.g.out = dP;
-    ap.g.k = grad_scale;
-    ap.g.ds = ds;
-    ap.g.clipped = clipped;
-    ap.b = b;
-    ap.db = db;
-    ap.kb = offset_grad_scale;
-    const bool vec = group_vec_ok(ap.g, axis) && aligned(P, 16) && aligned(dy, 16) && aligned(dP, 16);
-    if (rounding == LQ_ROUND_NEAREST_EVEN) return launch_group_affine<true, true>(ap, axis, vec, (hipStream_t)stream);
-    return launch_group_affine<false, true>(ap, axis, vec, (hipStream_t)stream);
+    if (method == LQ_INIT_ABSMAX) return launch_scale_init<LQ_INIT_ABSMAX, false>(ip, gp, axis, vec, "scale-init", stream);
+    if (method == LQ_INIT_LSQ) return launch_scale_init<LQ_INIT_LSQ, false>(ip, gp, axis, vec, "scale-init", stream);
+    if (rounding == LQ_ROUND_NEAREST_EVEN) return launch_scale_init<LQ_INIT_MSE, true>(ip, gp, axis, vec, "scale-init", stream);
+    return launch_scale_init<LQ_INIT_MSE, false>(ip, gp, axis, vec, "scale-init", stream);
 }
 
 int lq_scale_init_group_minmax(const float* P, float* s, float* b, int32_t qmin, int32_t qmax, int rounding, float min_value,
@@ -1600,33 +1601,14 @@ int lq_scale_init_group_minmax(const float* P, float* s, float* b, int32_t qmin,
     if (qmin >= qmax) return fail(LQ_EINVAL, "%s: min-max needs qmax > qmin (got [%d, %d])", fn, (int)qmin, (int)qmax);
     if (qmin < -kLim || qmax > kLim) return fail(LQ_EINVAL, "%s: range [%d, %d] is outside +-2^22", fn, (int)qmin, (int)qmax);
     if ((rc = check_rounding(fn, rounding))) return rc;
-    if (!(min_value > 0.0f) || !(min_value <= 3.4028234663852886e+38f)) return fail(LQ_EINVAL, "%s: min_value %g is not a positive finite number", fn, (double)min_value);
+    if ((rc = check_init_min_value(fn, min_value))) return rc;
     const GroupParams gp = group_params(P, s, qmin, qmax, R, C, axis, gs);
-    MinMaxParams mp{};
-    mp.P = P;
-    mp.s = s;
-    mp.b = b;
-    mp.n = (float)((int64_t)qmax - (int64_t)qmin);
-    mp.c = (float)(((double)qmin + (double)qmax) * 0.5 + (rounding == LQ_ROUND_FLOOR ? 0.5 : 0.0));
-    mp.min_value = min_value;
-    mp.R = gp.R;
-    mp.C = gp.C;
-    mp.gs = gp.gs;
-    mp.nb = gp.nb;
+    InitParams ip = init_params(gp, s, min_value);
+    ip.n = (float)((int64_t)qmax - (int64_t)qmin);
+    ip.c = (float)(((double)qmin + (double)qmax) * 0.5 + (rounding == LQ_ROUND_FLOOR ? 0.5 : 0.0));
+    ip.b = b;
     const bool vec = group_vec_ok(gp, axis) && aligned(P, 16);
-    hipStream_t st = (hipStream_t)stream;
-    if (axis == 0) {
-        const dim3 grid((unsigned)group_cols_tiles(gp, vec), (unsigned)std::min<int32_t>(gp.nb, 32768));
-        if (vec) hipLaunchKernelGGL((k_minmax_cols<4, kGroupColsLanes4>), grid, dim3(kBlock), 0, st, mp);
-        else hipLaunchKernelGGL((k_minmax_cols<1, kGroupColsLanes1>), grid, dim3(kBlock), 0, st, mp);
-        return check_hip("min-max column launch");
-    }
-    const int log_team = group_rows_log_team(gp, vec);
-    const int64_t pairs = (int64_t)gp.R * gp.nb, per_block = kBlock >> log_team;
-    const dim3 grid((unsigned)((pairs + per_block - 1) / per_block));
-    if (vec) hipLaunchKernelGGL((k_minmax_rows<4>), grid, dim3(kBlock), 0, st, mp, log_team);
-    else hipLaunchKernelGGL((k_minmax_rows<1>), grid, dim3(kBlock), 0, st, mp, log_team);
-    return check_hip("min-max row launch");
+    return launch_scale_init<kInitMinMax, false>(ip, gp, axis, vec, "min-max", stream);
 }
 
 int lq_fq_fwd_bwd_fused(const float* P, const float* s, const float* dy, float lambda, float* out, float* ds, void* ws,
@@ -2751,23 +2733,17 @@ struct lq_group_batch {
 
 namespace lq {
 
-// One task: the form lq_fq_*_group picks for this geometry and alignment, and its blocks (left in first_block until the table is ordered)
+// One task: the form lq_fq_*_group picks for this geometry and alignment (group_launch), and its blocks (left in first_block until
+// the table is ordered): tiles * groups <= R * C < 2^31 elements, nz <= 4 only below 2048 blocks
 static void fill_group_task(GroupTask& t, const GroupParams& p, int axis, bool vec, bool bwd) {
+    const GroupLaunch L = group_launch(p, axis, vec, !bwd, kGroupEveryGroup);
     memset(&t, 0, sizeof(t));
     t.p = p;
-    t.nbx = 1;
-    t.nz = 1;
-    if (axis == 0) {
-        t.form = vec ? GROUP_COLS4 : GROUP_COLS1;
-        t.nbx = (uint32_t)group_cols_tiles(p, vec);
-        if (!bwd) t.nz = (uint32_t)group_cols_row_split(p, vec, t.nbx, p.nb);
-        t.first_block = t.nbx * (uint32_t)p.nb * t.nz;      // tiles * groups <= R * C < 2^31 elements, nz <= 4 only below 2048 blocks
-    } else {
-        t.form = vec ? GROUP_ROWS4 : GROUP_ROWS1;
-        t.log_team = group_rows_log_team(p, vec);
-        const int64_t pairs = (int64_t)p.R * p.nb, per_block = kBlock >> t.log_team;
-        t.first_block = (uint32_t)((pairs + per_block - 1) / per_block);
-    }
+    t.form = L.form;
+    t.log_team = L.log_team;
+    t.nbx = L.nbx;
+    t.nz = L.nz;
+    t.first_block = L.blocks;
 }
 
 // Orders the table so that the heaviest units start first (as finish_table), assigns the block prefix and uploads it

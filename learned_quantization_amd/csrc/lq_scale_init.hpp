@@ -1,4 +1,5 @@
-// lq_scale_init.hpp -- scales of the clipped b-bit quantizer from the weights themselves (lq_hip.h: lq_scale_init_group)
+// lq_scale_init.hpp -- scales (and offsets) of the clipped b-bit quantizer from the weights themselves
+// (lq_hip.h: lq_scale_init_group / lq_scale_init_group_minmax)
 //
 // Geometry and unit shapes are those of lq_group.hpp's BACKWARD, the ones in which a whole group meets in one place:
 //
@@ -7,9 +8,11 @@
 //                          grid-stride).  The slots' partials meet in LDS and are merged in slot order; slot 0 emits.
 //   k_init_rows  (axis 1)  a team of T = 2^k <= 64 lanes per (row, group), a fixed xor butterfly, lane 0 of the team emits.
 //
-// The method is a compile-time parameter: LQ_INIT_ABSMAX carries two fp32 maxima (exact, order-free), LQ_INIT_LSQ one f64 sum of
-// |P|, LQ_INIT_MSE runs the absmax reduction (phase 1: every lane of the group reads the result back), then walks the group's
-// elements again and adds up, per candidate scale, the f64 squared error of the project's own clipped quantizer (phase 2), and the
+// The method is a compile-time parameter.  What a lane starts from and carries, how two partials merge and what the emitting lane
+// writes are the method's init_start / init_take / init_merge / init_raw / init_final (and init_offset) below; the two kernels are
+// the traversal around them.  LQ_INIT_ABSMAX carries two fp32 maxima; kInitMinMax (min-max: s and the offset b of the asymmetric
+// quantizer) the minimum and the maximum (fminf / fmaxf: exact, order-free); LQ_INIT_LSQ one f64 sum of |P|; LQ_INIT_MSE runs the
+// absmax reduction (phase 1: every lane of the group reads the result back), then walks the group's elements again and adds up, per candidate scale, the f64 squared error of the project's own clipped quantizer (phase 2), and the
 // emitting lane takes the first smallest.  The row form holds all 28 error sums of its one scale (56 VGPRs); the column form with
 // four columns per lane walks the candidates 7 at a time and re-reads the group per chunk.  Its partials pass through the same
 // 12 KB of LDS the backward uses (one f64 and one 32-bit word per slot and column), one candidate at a time.
@@ -22,12 +25,22 @@
 
 namespace lq {
 
+constexpr int kInitMinMax = 3;      // internal: lq_scale_init_group_minmax.  The public methods are lq_scale_init_method's
+static_assert(kInitMinMax != LQ_INIT_ABSMAX && kInitMinMax != LQ_INIT_LSQ && kInitMinMax != LQ_INIT_MSE, "method constants collide");
+
+// One layout for every method.  Min-max's n, c and b lie in unions on the fields it does not read (the host writes only the members
+// of the method it launches): three more plain fields would grow the kernel argument, move log_team behind it and so change the
+// argument loads and descriptors of the three methods that shipped before it.
 struct InitParams {
     const float* P;
     float* s;
-    float lo, hi;         // (float)qmin, (float)qmax
+    union { float lo; float n; };      // (float)qmin | min-max: (float)(qmax - qmin), >= 1
+    union { float hi; float c; };      // (float)qmax | min-max: (qmin + qmax) / 2 (+ 1/2 for floor), exact
     float min_value;      // > 0, finite
-    double sqrt_qp;       // LQ_INIT_LSQ: sqrt((double)qp), taken on the host
+    union {
+        double sqrt_qp;   // LQ_INIT_LSQ: sqrt((double)qp), taken on the host
+        float* b;         // min-max: the offset, the scale's shape
+    };
     int32_t R, C, gs, nb; // as GroupParams
 };
 
@@ -36,20 +49,44 @@ constexpr float kAbsmaxMargin = 1.0000002384185791015625f;   // 1 + 2^-22
 
 // what one lane carries through phase 1
 struct InitAcc {
-    float ap, an;      // max(P, 0), max(-P, 0): absmax and mse
+    float f0, f1;      // absmax and mse: max(P, 0), max(-P, 0); min-max: min P, max P
     double sum;        // sum |P|: lsq
     uint32_t bad;      // the group holds a NaN or an Inf
 };
+
+// a lane starts from InitAcc{0, 0, 0.0, 0}, and min-max's extremes from +-Inf
+template <int M>
+__device__ __forceinline__ void init_start(InitAcc& a) {
+    if constexpr (M == kInitMinMax) {
+        a.f0 = __builtin_inff();
+        a.f1 = -__builtin_inff();
+    }
+}
 
 template <int M>
 __device__ __forceinline__ void init_take(float x, InitAcc& a) {
     a.bad |= (fabsf(x) < __builtin_inff()) ? 0u : 1u;      // false for NaN and +-Inf
     if constexpr (M == LQ_INIT_LSQ) {
         a.sum += (double)fabsf(x);
+    } else if constexpr (M == kInitMinMax) {
+        a.f0 = fminf(a.f0, x);       // fminf / fmaxf skip a NaN operand; `bad` has it
+        a.f1 = fmaxf(a.f1, x);
     } else {
-        a.ap = fmaxf(a.ap, x);       // fmaxf skips a NaN operand; `bad` has it
-        a.an = fmaxf(a.an, -x);
+        a.f0 = fmaxf(a.f0, x);
+        a.f1 = fmaxf(a.f1, -x);
     }
+}
+
+// a += another lane's or slot's partial
+template <int M>
+__device__ __forceinline__ void init_merge(InitAcc& a, float f0, float f1, double sum, uint32_t bad) {
+    if constexpr (M == LQ_INIT_LSQ) {
+        a.sum += sum;
+    } else {
+        a.f0 = (M == kInitMinMax) ? fminf(a.f0, f0) : fmaxf(a.f0, f0);
+        a.f1 = fmaxf(a.f1, f1);
+    }
+    a.bad |= bad;
 }
 
 // s_raw of a group of n elements from its merged accumulator
@@ -57,15 +94,24 @@ template <int M>
 __device__ __forceinline__ float init_raw(const InitParams& p, const InitAcc& a, int64_t n) {
     if constexpr (M == LQ_INIT_LSQ) {
         return (float)(2.0 * a.sum / ((double)n * p.sqrt_qp));
+    } else if constexpr (M == kInitMinMax) {
+        return (a.f1 - a.f0) / p.n * kAbsmaxMargin;      // three roundings
     } else {
-        const float qa = p.hi > 0.f ? a.ap / p.hi : 0.f;
-        const float qb = p.lo < 0.f ? a.an / -p.lo : 0.f;
+        const float qa = p.hi > 0.f ? a.f0 / p.hi : 0.f;
+        const float qb = p.lo < 0.f ? a.f1 / -p.lo : 0.f;
         return fmaxf(qa, qb) * kAbsmaxMargin;
     }
 }
 
 __device__ __forceinline__ float init_final(const InitParams& p, float raw, uint32_t bad) {
     return bad ? __uint_as_float(0x7fc00000u) : fmaxf(raw, p.min_value);
+}
+
+// min-max: the offset b = (min / 2 + max / 2) - c * s of a group next to its s = init_final(raw), one rounding per operation
+__device__ __forceinline__ float init_offset(const InitParams& p, const InitAcc& a, float raw) {
+    const float mid = 0.5f * a.f0 + 0.5f * a.f1;
+    const float b = mid - p.c * fmaxf(raw, p.min_value);
+    return a.bad ? __uint_as_float(0x7fc00000u) : b;
 }
 
 __device__ __forceinline__ float init_candidate(const InitParams& p, float s0, int k) {
@@ -93,7 +139,7 @@ __global__ __launch_bounds__(kBlock) void k_init_cols(const InitParams p) {
     constexpr int COLS = TX * V;
     constexpr int CH = kInitCandidates / V;      // V = 4: 7 candidates per walk (28 f64 sums per lane); V = 1: all 28
     static_assert(CH * V == kInitCandidates, "the chunks must tile the candidates");
-    __shared__ double sh_d[SLOTS * COLS];        // lsq: the sums; mse phase 2: one candidate's sums; else ap | an as floats
+    __shared__ double sh_d[SLOTS * COLS];        // lsq: the sums; mse phase 2: one candidate's sums; else f0 | f1 as floats
     __shared__ uint32_t sh_u[SLOTS * COLS];
     float* const sh_f = reinterpret_cast<float*>(sh_d);
     const int lx = (int)threadIdx.x % TX, slot = (int)threadIdx.x / TX;
@@ -105,7 +151,10 @@ __global__ __launch_bounds__(kBlock) void k_init_cols(const InitParams p) {
         const int64_t r1 = (r0 + p.gs < p.R) ? r0 + p.gs : p.R;
         InitAcc a[V];
 #pragma unroll
-        for (int k = 0; k < V; ++k) a[k] = InitAcc{0.f, 0.f, 0.0, 0u};
+        for (int k = 0; k < V; ++k) {
+            a[k] = InitAcc{0.f, 0.f, 0.0, 0u};
+            init_start<M>(a[k]);
+        }
         if (live) {
 #pragma unroll 4
             for (int64_t r = r0 + slot; r < r1; r += SLOTS) {
@@ -127,36 +176,39 @@ __global__ __launch_bounds__(kBlock) void k_init_cols(const InitParams p) {
             if constexpr (M == LQ_INIT_LSQ) {
                 sh_d[j] = a[k].sum;
             } else {
-                sh_f[j] = a[k].ap;
-                sh_f[SLOTS * COLS + j] = a[k].an;
+                sh_f[j] = a[k].f0;
+                sh_f[SLOTS * COLS + j] = a[k].f1;
             }
             sh_u[j] = a[k].bad;
         }
         __syncthreads();
-        // mse: every lane merges (phase 2 needs s0 in all slots); otherwise slot 0 alone
+        // mse: every lane merges (phase 2 needs s0 in all slots); otherwise slot 0 alone.  Min-max's live lanes of slot 0 also store
+        // where they merge: with the two output addresses formed here, not ahead of the row loop, that loop keeps four loads in flight
+        // (66 VGPRs) instead of three and one (64).  The older methods store below, in the form they shipped with.
+        constexpr bool STORE_HERE = M == kInitMinMax;
         float raw[V];
         uint32_t bad[V];
-        if (M == LQ_INIT_MSE || slot == 0) {
+        if ((M == LQ_INIT_MSE || slot == 0) && (!STORE_HERE || live)) {
 #pragma unroll
             for (int k = 0; k < V; ++k) {
                 InitAcc t = InitAcc{0.f, 0.f, 0.0, 0u};
+                init_start<M>(t);
 #pragma unroll 2
                 for (int w = 0; w < SLOTS; ++w) {      // fixed order: slot 0, 1, 2, ...
                     const int j = w * COLS + lx * V + k;
-                    if constexpr (M == LQ_INIT_LSQ) {
-                        t.sum += sh_d[j];
-                    } else {
-                        t.ap = fmaxf(t.ap, sh_f[j]);
-                        t.an = fmaxf(t.an, sh_f[SLOTS * COLS + j]);
-                    }
-                    t.bad |= sh_u[j];
+                    if constexpr (M == LQ_INIT_LSQ) init_merge<M>(t, 0.f, 0.f, sh_d[j], sh_u[j]);
+                    else init_merge<M>(t, sh_f[j], sh_f[SLOTS * COLS + j], 0.0, sh_u[j]);
                 }
                 raw[k] = init_raw<M>(p, t, r1 - r0);
                 bad[k] = t.bad;
+                if constexpr (STORE_HERE) {
+                    p.s[g * p.C + c0 + k] = init_final(p, raw[k], bad[k]);
+                    p.b[g * p.C + c0 + k] = init_offset(p, t, raw[k]);
+                }
             }
         }
         if constexpr (M != LQ_INIT_MSE) {
-            if (slot == 0 && live) {
+            if (!STORE_HERE && slot == 0 && live) {
 #pragma unroll
                 for (int k = 0; k < V; ++k) p.s[g * p.C + c0 + k] = init_final(p, raw[k], bad[k]);
             }
@@ -228,6 +280,7 @@ __global__ __launch_bounds__(kBlock) void k_init_rows(const InitParams p, const 
     const bool live = pair < pairs;
     int64_t base = 0, c0 = 0, c1 = 0;
     InitAcc a = InitAcc{0.f, 0.f, 0.0, 0u};
+    init_start<M>(a);
     if (live) {
         const uint32_t r = pair / (uint32_t)p.nb, g = pair - r * (uint32_t)p.nb;
         base = (int64_t)r * p.C;
@@ -246,17 +299,15 @@ __global__ __launch_bounds__(kBlock) void k_init_rows(const InitParams p, const 
         }
     }
     for (int off = T >> 1; off > 0; off >>= 1) {      // fixed butterfly inside the aligned team: every lane ends with the total
-        if constexpr (M == LQ_INIT_LSQ) {
-            a.sum += __shfl_xor(a.sum, off);
-        } else {
-            a.ap = fmaxf(a.ap, __shfl_xor(a.ap, off));
-            a.an = fmaxf(a.an, __shfl_xor(a.an, off));
-        }
-        a.bad |= __shfl_xor(a.bad, off);
+        if constexpr (M == LQ_INIT_LSQ) init_merge<M>(a, 0.f, 0.f, __shfl_xor(a.sum, off), __shfl_xor(a.bad, off));
+        else init_merge<M>(a, __shfl_xor(a.f0, off), __shfl_xor(a.f1, off), 0.0, __shfl_xor(a.bad, off));
     }
     const float raw = init_raw<M>(p, a, live ? c1 - c0 : 1);
     if constexpr (M != LQ_INIT_MSE) {
-        if (live && lt == 0) p.s[pair] = init_final(p, raw, a.bad);
+        if (live && lt == 0) {
+            p.s[pair] = init_final(p, raw, a.bad);
+            if constexpr (M == kInitMinMax) p.b[pair] = init_offset(p, a, raw);
+        }
     } else {
         double E[kInitCandidates];
 #pragma unroll

@@ -1,7 +1,7 @@
 """The launch rule of the group-wise kernels restated in Python, and the case table that reaches every run-time branch of it.
 
-``launch_shape`` restates launch_group, group_cols_tiles, group_cols_row_split, group_rows_log_team and group_vec_ok of
-csrc/lq_kernels.hip (fill_group_task asks the same functions, with the group extent nb instead of min(nb, 32768) -- the two agree
+``launch_shape`` restates group_launch and group_vec_ok of csrc/lq_kernels.hip (the single-tensor launchers and fill_group_task
+all ask group_launch; fill_group_task passes the group extent nb instead of min(nb, 32768) as max_groups_y -- the two agree
 wherever the row split can exceed 1, see ``launch_shape``).  It exists ONLY so that tests/test_group_forms_cpu.py can prove that
 ``FORMS`` (with AXIS0 / AXIS1 of tests/test_gpu_groupwise.py) takes every branch; profiles/group_forms/kernel_coverage.txt holds
 the kernel names and grids of a traced run next to what it predicts.  It is never used to compute an expected output: those come

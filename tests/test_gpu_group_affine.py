@@ -1,4 +1,4 @@
-"""GPU tests of the asymmetric group-wise quantizer (csrc/lq_group_affine.hpp; include/lq_hip.h: lq_fq_forward_group_affine /
+"""GPU tests of the asymmetric group-wise quantizer (csrc/lq_group.hpp; include/lq_hip.h: lq_fq_forward_group_affine /
 lq_fq_backward_group_affine / lq_scale_init_group_minmax) and of everything built on it: the ops, the layers, the Trainer and both
 exports.
 

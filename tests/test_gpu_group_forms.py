@@ -7,8 +7,8 @@ tests/_bounds.py::assert_within_terms, |got - ref| <= 1e-5 * sum|dy_i r_i| (floo
 gives the bits of the single-tensor call, ds included.  Conditions on the inputs are asserted on the reference before a kernel runs
 (and, without a device, by tests/test_group_forms_cpu.py).
 
-``FORMS`` (tests/_group_forms.py) is the case table: one row per run-time branch of launch_group / group_rows_log_team /
-group_cols_row_split / fill_group_task that the lists of tests/test_gpu_groupwise.py and test_gpu_group_batch.py do not reach --
+``FORMS`` (tests/_group_forms.py) is the case table: one row per run-time branch of group_launch (the host's one launch rule:
+form, team width, forward row split, grid; launch_group and fill_group_task ask it) that the lists of tests/test_gpu_groupwise.py and test_gpu_group_batch.py do not reach --
 team widths 2 to 64 of both row forms, a second trip of the column forms' grid-stride group loop (nb > 32768), the forward row split
 decided by the 2048-block cap.  The integer view q of a NaN quotient is not defined by the reference (NumPy's cast of NaN to an integer
 is not); the int32 view is therefore compared only where the reference q is finite, the float32 view everywhere."""

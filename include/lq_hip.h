@@ -471,6 +471,32 @@ int lq_group_batch_backward(const lq_group_batch* b, const float* const* dy, con
                             void* ws, size_t ws_bytes, void* stream);
 int lq_group_batch_clip_counts(const lq_group_batch* b, int tensor, const uint32_t** dev, int64_t* groups);
 
+/* ---- group-wise tensors with a learned offset in the batch ----
+ * lq_group_batch_create_affine builds the same kind of batch from the same descriptors plus, per tensor, an optional offset:
+ * a tensor with b != NULL is lq_fq_forward_group_affine / lq_fq_backward_group_affine (the definition stated in "asymmetric
+ * group-wise scales" above), a tensor with b == NULL is lq_fq_forward_group / lq_fq_backward_group as in a batch without offsets
+ * (a bias of an asymmetric model: it keeps the symmetric bits, the sign of -0.0 included).  The handle is an lq_group_batch:
+ * _forward, _backward, _clip_counts, _workspace_bytes (still 0: no workspace is used) and _destroy serve it unchanged, ONE launch
+ * per pass.  offs == NULL, or no tensor with a b, is exactly lq_group_batch_create: the same tables and the same kernels.
+ * out, dP, the clip counts, ds AND db of every tensor are bit-identical to the single-tensor call of its kind on the same buffers
+ * with the same grad_scale and offset_grad_scale: a block runs the same code on the same unit of work.
+ * offset_grad_scale (kb of the definition) is FIXED at create time and lives in the device-resident task table: the kernel's
+ * argument block already carries one pointer and one coefficient per tensor for dy and grad_scale, and a second coefficient
+ * array would pass its 4 KB limit.  A layer's kb is a function of its geometry and range, so nothing is lost.
+ * Backward: grad_scale == NULL stays "mask only": neither ds nor db is written.  With grad_scale every tensor needs a ds, and db
+ * is written where it was given.
+ * Refused before the first HIP call, in addition to everything lq_group_batch_create refuses: a db without a b and an
+ * offset_grad_scale that is not finite on a tensor with a b (LQ_EINVAL); b or db off the 4-byte grid (LQ_EALIGN; they need no
+ * more, as in the single-tensor call).  The message names the tensor.
+ * create is a HOST call (allocates and uploads: never inside a capture); both passes only enqueue and can be captured.  */
+typedef struct lq_group_offset {
+    const float* b;            /* offset, the scale's shape; NULL: this tensor is symmetric          */
+    float* db;                 /* offset gradient, the scale's shape; may be NULL (not written)      */
+    float offset_grad_scale;   /* kb of lq_fq_backward_group_affine, fixed for the batch's life      */
+} lq_group_offset;
+int lq_group_batch_create_affine(const lq_group_desc* descs, const lq_group_offset* offs /* [n] or NULL */,
+                                 int n, int rounding, lq_group_batch** out);
+
 /* VALUE of the custom-loss-term penalty for the whole batch (compute_{maxbin,difference,inverse}_penalty,
  *   custom_loss_functions.py:75-116, 161-195, 240-275), the number compute_total_loss adds to the cross-entropy (:47-58).
  * Per-tensor term t_i as in lq_penalty_{maxbin,difference,inverse}_fwd; the model penalty in the reference's order (:102-116):

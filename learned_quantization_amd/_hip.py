@@ -134,7 +134,14 @@ class GroupDesc(ctypes.Structure):
                 ("R", _c_i64), ("C", _c_i64), ("gs", _c_i64), ("axis", _c_i32), ("qmin", _c_i32), ("qmax", _c_i32)]
 
 
+class GroupOffset(ctypes.Structure):
+    """lq_group_offset of include/lq_hip.h."""
+    _fields_ = [("b", _c_p), ("db", _c_p), ("offset_grad_scale", _c_f)]
+
+
 SIGNATURES.update({
+    "lq_group_batch_create_affine": (_c_int, [ctypes.POINTER(GroupDesc), ctypes.POINTER(GroupOffset), _c_int, _c_int,
+                                              ctypes.POINTER(_c_p)]),
     "lq_group_batch_create": (_c_int, [ctypes.POINTER(GroupDesc), _c_int, _c_int, ctypes.POINTER(_c_p)]),
     "lq_group_batch_destroy": (_c_int, [_c_p]),
     "lq_group_batch_workspace_bytes": (_c_sz, [_c_p]),

@@ -31,7 +31,8 @@ from .ops import ROUNDINGS
 
 
 class _Entry:
-    __slots__ = ("layer", "slot", "param", "nested", "scale", "out", "ds", "m", "v", "desc", "out_oihw", "dp", "conv", "nq")
+    __slots__ = ("layer", "slot", "param", "nested", "scale", "out", "ds", "m", "v", "desc", "out_oihw", "dp", "conv", "nq",
+                 "offset", "db", "mb", "vb")      # asymmetric group batch: the layer's offset, its gradient and its Adam moments
 
 
 class _DeviceInts:
@@ -44,7 +45,7 @@ class _DeviceInts:
 class FakeQuantBatch:
     def __init__(self, model_or_layers, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-7, mode: str = "keras",
                  oihw: bool = True, hwio_out: bool = True, autograd: bool = True, clipped: bool = False,
-                 group_batch: bool = False):
+                 group_batch: bool = False, asymmetric: bool = False):
         """``autograd=True``: ``quantize_all()`` is ONE autograd node (2 x tensors inputs, one output per tensor) and everything happens
         inside ``loss.backward()``.  Convenient -- and, for 40 tensors, 0.4-0.6 ms of autograd-engine work per step (an 80-input node,
         40 output wrappers, an AccumulateGrad per parameter that adds into the data-parallel bucket with a launch of its own).
@@ -67,7 +68,16 @@ class FakeQuantBatch:
         ``dP`` of every tensor into a buffer the batch owns, ds, the clip counts -- ONE more.  Per tensor the results are the
         per-tensor group-wise ops' bit for bit, ds included.  A bias is the one-group line ``R = 1, C = numel, axis = 1``; any
         other one-axis scale belongs to the clipped batch.  One rounding and one rule for all; no loss term, no HWIO storage, no
-        ``defer_scale_grads`` / ``scale_grads_from_param_grads``, no ``BatchedScaleAdam(fused=True)``."""
+        ``defer_scale_grads`` / ``scale_grads_from_param_grads``, no ``BatchedScaleAdam(fused=True)``.
+        ``asymmetric=True`` (opt-in, with ``group_batch=True`` only): the group batch also carries the offsets of asymmetric layers
+        (``lq_group_batch_create_affine``): still ONE launch per pass, which also writes every offset's gradient; ``out``, ``dP``,
+        ds and db are the per-tensor asymmetric ops' bit for bit, and the biases (symmetric, scalar) keep the symmetric batch's
+        bits.  An offset's gradient factor is its layer's ``grad_scale_value`` (what the per-tensor path passes), fixed when the
+        batch is built.  The offsets join the scales' Adam set without a lower bound: scales and offsets are stepped by ONE
+        launch.  That set holds 256 tensors at most (scales + offsets; the ResNet-50-like model has 108 + 54 = 162): a larger model is
+        refused at construction, never split silently.  Over a model without an asymmetric layer this is the plain group batch.
+        Everything the group batch refuses stays refused (``clipped``, a loss term, HWIO storage, ``defer_scale_grads``,
+        ``BatchedScaleAdam(fused=True)``)."""
         layers = custom_layers_of(model_or_layers) if isinstance(model_or_layers, torch.nn.Module) else list(model_or_layers)
         self.layers = layers
         self.autograd = bool(autograd)
@@ -79,13 +89,21 @@ class FakeQuantBatch:
                          if hasattr(layer, a)]
         self.clipped = bool(clipped)
         self.group_batch = bool(group_batch)
+        self.asymmetric = bool(asymmetric)
         self._ghandle = None
+        if self.asymmetric and self.clipped:
+            raise ValueError("asymmetric=True together with clipped=True: the clipped one-axis batch carries no offset per group; "
+                             "offsets travel in the group batch only (group_batch=True, asymmetric=True)")
+        if self.asymmetric and not self.group_batch:
+            raise ValueError("asymmetric=True belongs to group_batch=True: only the group batch carries an offset per group and its "
+                             "gradient")
         if self.group_batch and self.clipped:
             raise ValueError("group_batch=True together with clipped=True: a batch is either the group batch (group-wise layers and "
                              "their biases) or the clipped batch (one-axis scales), not both")
-        if any(getattr(n, "asymmetric", False) for n in nested_layers):
-            raise ValueError("FakeQuantBatch over an asymmetric layer (asymmetric=True): neither the clipped batch nor the group batch "
-                             "carries an offset per group or its gradient; run such a model on the per-tensor path (batched=False)")
+        if not self.asymmetric and any(getattr(n, "asymmetric", False) for n in nested_layers):
+            raise ValueError("FakeQuantBatch over an asymmetric layer: the offsets and their gradients travel only in the group "
+                             "batch that was asked to carry them; opt in with FakeQuantBatch(..., group_batch=True, asymmetric=True), "
+                             "or run such a model on the per-tensor path (batched=False)")
         if not self.group_batch and any(getattr(n, "group_size", None) is not None for n in nested_layers):
             raise ValueError("FakeQuantBatch over a group-wise layer (group_size): its scale has two non-unit axes, which the "
                              "(outer, G, inner) descriptor of the default and the clipped batch cannot express; run such a model on "
@@ -134,6 +152,7 @@ class FakeQuantBatch:
                 if e.desc is None:
                     raise ValueError("parameters must be dense (contiguous, or a permutation of a contiguous array)")
                 e.out = torch.empty_like(param.data)
+                e.offset = e.db = e.mb = e.vb = None
                 e.nq = nested.penalty_threshold is not None or self.ste      # the op itself gives this scale a gradient
                 if self.ste and isinstance(layer, _ConvBase) and layer.kernel_storage == "hwio":
                     raise ValueError('a batched scale_gradient="ste" model takes conv kernels in the memory order the convolution '
@@ -270,9 +289,25 @@ class FakeQuantBatch:
             e.m = torch.zeros_like(nested.scale.data)
             e.v = torch.zeros_like(nested.scale.data)
             e.out_oihw = e.conv = None
+            e.offset = e.db = e.mb = e.vb = None
+            if getattr(nested, "asymmetric", False):               # only where the batch was asked to carry offsets (__init__)
+                e.offset = nested.offset
+                _hip.require_device_f32(e.offset.data, "offset")
+                g = e.offset.grad
+                if g is not None and g.is_contiguous():
+                    e.db = g                                       # external buffer (bucket view), as ds
+                    self._external_grads = True
+                else:
+                    e.db = torch.zeros_like(e.offset.data)
+                e.mb = torch.zeros_like(e.offset.data)
+                e.vb = torch.zeros_like(e.offset.data)
             self.entries.append(e)
         if not self.entries:
             raise ValueError("no custom layers")
+        affine = [e for e in self.entries if e.offset is not None]
+        if len(self.entries) + len(affine) > self.ADAM_SET_MAX:
+            raise ValueError(f"FakeQuantBatch(group_batch=True): {len(self.entries)} scales + {len(affine)} offsets are more than the "
+                             f"{self.ADAM_SET_MAX} tensors one lq_adam_set steps in its single launch")
         self.device = self.entries[0].param.device
         lib = _hip.load()
         n = len(self.entries)
@@ -282,7 +317,16 @@ class FakeQuantBatch:
             arr[i] = _hip.GroupDesc(e.param.data_ptr(), e.scale.data_ptr(), e.out.data_ptr(), e.dp.data_ptr(), e.ds.data_ptr(),
                                     R, C, gs, axis, int(e.nested.q_range[0]), int(e.nested.q_range[1]))
         handle = ctypes.c_void_p()
-        _hip.check(lib.lq_group_batch_create(arr, n, ROUNDINGS.index(self.rounding), ctypes.byref(handle)), "lq_group_batch_create")
+        if affine:
+            # kb is the layer's factor (ops.fq_backward_group_affine: the offset's defaults to the scale's), fixed for the batch's life
+            offs = (_hip.GroupOffset * n)()
+            for i, e in enumerate(self.entries):
+                if e.offset is not None:
+                    offs[i] = _hip.GroupOffset(e.offset.data_ptr(), e.db.data_ptr(), float(e.nested.grad_scale_value(e.param.numel())))
+            _hip.check(lib.lq_group_batch_create_affine(arr, offs, n, ROUNDINGS.index(self.rounding), ctypes.byref(handle)),
+                       "lq_group_batch_create_affine")
+        else:
+            _hip.check(lib.lq_group_batch_create(arr, n, ROUNDINGS.index(self.rounding), ctypes.byref(handle)), "lq_group_batch_create")
         self._ghandle = handle
         self._handle = None
         self._ptrs = (ctypes.c_void_p * n)()
@@ -291,23 +335,27 @@ class FakeQuantBatch:
         self._ws_bytes = lib.lq_group_batch_workspace_bytes(handle)
         self.hyper = dict(lr=lr, betas=betas, eps=eps, mode=mode)
         self._data_ptrs = [(e.param.data_ptr(), e.nested.scale.data_ptr()) for e in self.entries]
+        self._offset_ptrs = [(e, e.offset.data_ptr()) for e in affine]
         self._flat = [t for e in self.entries for t in (e.param, e.nested.scale)]
         slots = {}
         for i, e in enumerate(self.entries):
             slots.setdefault(id(e.layer), [e.layer, None, None])[1 + e.slot] = i
         self._layer_slots = list(slots.values())
         self._oihw_idx, self._oihw_pos = [], {}
-        # the scales' Adam step: one launch over all of them (lq_adam_set_step; the gradients are the batch's ds buffers)
-        cnt = (ctypes.c_int64 * n)(*[e.scale.numel() for e in self.entries])
-        mv = (ctypes.c_float * n)(*[float(c.min_value) if (c := getattr(e.scale, "lq_constraint", None)) is not None else float("-inf")
-                                    for e in self.entries])
-        w = (ctypes.c_void_p * n)(*[e.scale.data_ptr() for e in self.entries])
-        m = (ctypes.c_void_p * n)(*[e.m.data_ptr() for e in self.entries])
-        v = (ctypes.c_void_p * n)(*[e.v.data_ptr() for e in self.entries])
+        # the Adam step of the scales, then of the offsets (no lower bound): one launch over all of them (lq_adam_set_step; the
+        # gradients are the batch's ds and db buffers)
+        stepped = [(e.scale, e.m, e.v, e.ds) for e in self.entries] + [(e.offset, e.mb, e.vb, e.db) for e in affine]
+        na = len(stepped)
+        cnt = (ctypes.c_int64 * na)(*[w.numel() for w, _, _, _ in stepped])
+        mv = (ctypes.c_float * na)(*[float(c.min_value) if (c := getattr(w, "lq_constraint", None)) is not None else float("-inf")
+                                     for w, _, _, _ in stepped])
+        w = (ctypes.c_void_p * na)(*[t[0].data_ptr() for t in stepped])
+        m = (ctypes.c_void_p * na)(*[t[1].data_ptr() for t in stepped])
+        v = (ctypes.c_void_p * na)(*[t[2].data_ptr() for t in stepped])
         adam = ctypes.c_void_p()
-        _hip.check(lib.lq_adam_set_create(w, m, v, cnt, mv, n, ctypes.byref(adam)), "lq_adam_set_create")
+        _hip.check(lib.lq_adam_set_create(w, m, v, cnt, mv, na, ctypes.byref(adam)), "lq_adam_set_create")
         self._adam_set = adam
-        self._adam_grads = (ctypes.c_void_p * n)(*[e.ds.data_ptr() for e in self.entries])
+        self._adam_grads = (ctypes.c_void_p * na)(*[t[3].data_ptr() for t in stepped])
         if not self.autograd:
             self._leaf = [e.out.detach().requires_grad_(True) for e in self.entries]
             self._leaf_o = [None] * n
@@ -315,6 +363,9 @@ class FakeQuantBatch:
             self._static_outs = list(self._leaf)
             self._static_pre = [(layer.__dict__, (None if ik is None else self._leaf[ik], None if ib is None else self._leaf[ib], None))
                                 for layer, ik, ib in self._layer_slots]
+
+    #: tensors one lq_adam_set steps in its single launch (scales + offsets of a group batch)
+    ADAM_SET_MAX = 256
 
     def _refuse_group(self, what: str):
         if self.group_batch:
@@ -343,6 +394,10 @@ class FakeQuantBatch:
             if e.param.data_ptr() != pp or e.nested.scale.data_ptr() != sp:      # the module's scale: a replaced Parameter is caught too
                 raise RuntimeError("a parameter or scale was re-allocated after the batch was built "
                                    "(e.g. model.to(device)); rebuild the FakeQuantBatch")
+        for e, bp in getattr(self, "_offset_ptrs", ()):
+            if e.nested.offset.data_ptr() != bp:
+                raise RuntimeError("an offset was re-allocated after the batch was built (e.g. model.to(device)); rebuild the "
+                                   "FakeQuantBatch")
 
     # ------------------------------------------------------------------ forward
     def quantize_all(self):
@@ -477,15 +532,17 @@ class FakeQuantBatch:
         copies of dy; ``gathered`` companions: dy in HWIO order), the kept dy itself otherwise (custom_layers.py:118)."""
         if refuse_accumulation and not self._external_grads:
             for e in self.entries:
-                if e.nq and e.scale.grad is not None:
+                if e.nq and (e.scale.grad is not None or (e.offset is not None and e.offset.grad is not None)):
                     # the kernel OVERWRITES its gradient buffer: a second backward without zero_grad(set_to_none=True)
                     # would silently drop the first gradient -- refuse instead (before anything is launched)
-                    raise RuntimeError("FakeQuantBatch: scale gradients must be None before backward "
+                    raise RuntimeError("FakeQuantBatch: scale (and offset) gradients must be None before backward "
                                        "(gradient accumulation over several backward passes is not supported in batched mode)")
         self._scale_grad_call(oihw)
         for e in self.entries:
             if e.nq:
                 e.scale.grad = e.ds                        # written in place by the kernel: no accumulate launch
+                if e.offset is not None:
+                    e.offset.grad = e.db                   # and so is the offset's, by the same launch
             # STE-only: zeros_like(scale) (CL custom_layers.py:62) -- no scale gradient from the op
         if self.clipped or self.group_batch:
             return [e.dp for e in self.entries]
@@ -681,7 +738,8 @@ class BatchedScaleAdam:
         if fused:
             if batch.group_batch:
                 raise ValueError("the fused finalize + Adam launch exists for the nested-quantization vote only: "
-                                 "build BatchedScaleAdam(fused=False) for a group batch")
+                                 "build BatchedScaleAdam(fused=False) for a group batch (with or without asymmetric=True: "
+                                 "the offsets step with the scales in the Adam set's one launch)")
             if batch.clipped:
                 raise ValueError("the fused finalize + Adam launch exists for the nested-quantization vote only: "
                                  "build BatchedScaleAdam(fused=False) for a clipped batch")
@@ -696,11 +754,14 @@ class BatchedScaleAdam:
             batch._fused_opt = self
         self._step = 0
         self._step_t = torch.zeros(1, dtype=torch.int64, device=batch.device) if capturable else None
-        self.param_groups = [{"params": [e.nested.scale for e in batch.entries]}]
+        self.param_groups = [{"params": [e.nested.scale for e in batch.entries]
+                              + [e.offset for e in batch.entries if e.offset is not None]}]
 
     def zero_grad(self, set_to_none: bool = True):
         for e in self.batch.entries:
             e.scale.grad = None
+            if e.offset is not None:
+                e.offset.grad = None
 
     def _advance(self):
         """(host step, device step tensor) of the update that is about to be applied."""
@@ -725,5 +786,11 @@ class BatchedScaleAdam:
                 e.ds.zero_()
             elif g.data_ptr() != e.ds.data_ptr():
                 e.ds.copy_(g)                                      # loss-term gradients arrive in autograd-owned tensors
+            if e.offset is not None:                               # an asymmetric group batch: the offsets step in the same launch
+                g = e.offset.grad
+                if g is None:
+                    e.db.zero_()
+                elif g.data_ptr() != e.db.data_ptr():
+                    e.db.copy_(g)
         step, step_dev = self._advance()
         self.batch.scale_adam_step(step=step, step_dev=step_dev)

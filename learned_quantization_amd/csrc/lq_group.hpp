@@ -61,8 +61,8 @@ struct GroupAffineParams {
     float kb;             // offset_grad_scale
 };
 
-template <class PT>
-constexpr bool kGroupHasOffset = std::is_same_v<PT, GroupAffineParams>;
+template <class PT>      // GroupAffineParams, or a struct derived from it (the batch's: lq_group_batch.hpp)
+constexpr bool kGroupHasOffset = std::is_base_of_v<GroupAffineParams, PT>;
 __host__ __device__ __forceinline__ const GroupParams& group_base(const GroupParams& p) { return p; }
 __host__ __device__ __forceinline__ const GroupParams& group_base(const GroupAffineParams& ap) { return ap.g; }
 

@@ -15,6 +15,19 @@
 // the 4 KB limit of the argument block).  The form branch is block-uniform; only the backward column forms have barriers and every
 // thread of such a block reaches both.  The backward's static LDS is the float4 column form's 12 KB for every form: 13 blocks per
 // CU by LDS, above the 8 blocks of 256 threads a CU holds, so it never bounds occupancy.  The forward uses no LDS.
+//
+// Tensors with a learned offset per group (lq_group_batch_create_affine) run k_group_batch_affine on a table of GroupAffineTask:
+// a GroupTask followed by the offset b, its gradient db and the gradient's factor kb.  kb lives in the table, fixed at create
+// time, because the argument block has no room for a second 1 KB coefficient pack.  A task with b == NULL (a bias of an asymmetric
+// model) calls the bodies with GroupParams, literally what k_group_batch does, so it keeps the symmetric bits, -0.0 included; a
+// task with b calls them with GroupAffineParams, as k_group_affine_cols / k_group_affine_rows do.  That branch is block-uniform
+// too.  k_group_batch and the GroupTask table of a batch without offsets are untouched.
+// Resources of k_group_batch_affine on gfx950 (compiler's report, profiles/group_affine_batch/kernel_resources.txt):
+//   forward   44 VGPRs, 68 SGPRs, no LDS, no scratch, 8 waves per SIMD      (k_group_batch: 39 VGPRs, 8 waves)
+//   backward  72 VGPRs, 94 SGPRs, 20480 bytes of LDS, no scratch, 7 waves per SIMD      (k_group_batch: 66 VGPRs, 12288 bytes, 7 waves)
+// The backward's static LDS is 8 KB sh_sum + 8 KB sh_sumb + 4 KB sh_cnt = 20 KB for every form: 8 blocks x 20 KB are the CU's
+// 160 KB, exactly the 8 blocks of 256 threads a CU holds, so the 72 registers bound occupancy (7 waves) before LDS does.  The
+// float4 column body keeps its one row in flight (lq_group.hpp, unroll(1) with an offset in the backward).
 #ifndef LQ_GROUP_BATCH_HPP_
 #define LQ_GROUP_BATCH_HPP_
 #include "lq_group.hpp"
@@ -60,6 +73,67 @@ __global__ __launch_bounds__(kBlock) void k_group_batch(const GroupTask* __restr
     } else {
         group_rows_body<RNE, BWD, 1>(p, t.log_team, b);
     }
+}
+
+// A GroupTask that may carry an offset: the affine table's entry.  b == NULL: a symmetric tensor, db and kb unused.
+struct GroupAffineTask {
+    GroupTask t;
+    const float* b;           // offset, the scale's shape, or NULL
+    float* db;                // backward table: offset gradient or NULL; forward table: NULL
+    float kb;                 // offset_grad_scale, fixed at create time
+    uint32_t pad;
+};
+
+// The batch's own name for GroupAffineParams (kGroupHasOffset holds for it): the bodies are instantiated apart from the
+// single-tensor kernels' copies.  With the shared instantiation the compiler built k_group_affine_cols<*, true, *, *> differently
+// once it had a second caller (float4 form: 170 VGPRs and 2 waves per SIMD instead of 76 and 6); with a type of its own every
+// kernel the library had keeps its instruction stream (tools/asm_compare.py) and the source of the bodies is still one.
+struct GroupBatchAffineParams : GroupAffineParams {};
+
+// The work of one block on its task's unit: the form branch of k_group_batch for either parameter struct
+template <bool RNE, bool BWD, class PT>
+__device__ __forceinline__ void group_batch_unit(const PT& pp, const GroupTask& t, const uint32_t b, double* sh_sum, double* sh_sumb,
+                                                 uint32_t* sh_cnt) {
+    const GroupParams& p = group_base(pp);
+    if (t.form <= GROUP_COLS1) {       // block-uniform
+        const uint32_t bx = b % t.nbx, rest = b / t.nbx;
+        const uint32_t g = rest % (uint32_t)p.nb, z = rest / (uint32_t)p.nb;      // backward: nz == 1, z == 0
+        if (t.form == GROUP_COLS4) group_cols_body<RNE, BWD, 4, kGroupColsLanes4>(pp, (int64_t)bx, (int64_t)g, (int)z, (int)t.nz, BWD, sh_sum, sh_sumb, sh_cnt);
+        else group_cols_body<RNE, BWD, 1, kGroupColsLanes1>(pp, (int64_t)bx, (int64_t)g, (int)z, (int)t.nz, BWD, sh_sum, sh_sumb, sh_cnt);
+    } else if (t.form == GROUP_ROWS4) {
+        group_rows_body<RNE, BWD, 4>(pp, t.log_team, b);
+    } else {
+        group_rows_body<RNE, BWD, 1>(pp, t.log_team, b);
+    }
+}
+
+template <bool RNE, bool BWD>
+__global__ __launch_bounds__(kBlock) void k_group_batch_affine(const GroupAffineTask* __restrict__ tasks, const uint32_t* __restrict__ block_task,
+                                                               PtrPack pk, CoefPack cf, int mask_only) {
+    __shared__ double sh_sum[BWD ? kGroupBatchLdsSum : 1];
+    __shared__ double sh_sumb[BWD ? kGroupBatchLdsSum : 1];
+    __shared__ uint32_t sh_cnt[BWD ? kGroupBatchLdsSum : 1];
+    const int ti = (int)block_task[blockIdx.x];
+    const GroupAffineTask& at = tasks[ti];
+    const GroupTask& t = at.t;
+    GroupBatchAffineParams ap;
+    ap.g = t.p;
+    ap.b = at.b;
+    ap.db = nullptr;
+    ap.kb = at.kb;
+    if constexpr (BWD) {
+        ap.g.dy = pk.dy[ti];
+        ap.g.k = cf.c[ti];
+        ap.db = at.db;
+        if (mask_only) {
+            ap.g.ds = nullptr;
+            ap.db = nullptr;
+        }
+    }
+    const uint32_t b = blockIdx.x - t.first_block;
+    // block-uniform: every thread of a block takes the same side, and a column form's two barriers with it
+    if (ap.b != nullptr) group_batch_unit<RNE, BWD>(ap, t, b, sh_sum, sh_sumb, sh_cnt);
+    else group_batch_unit<RNE, BWD>(ap.g, t, b, sh_sum, nullptr, sh_cnt);
 }
 
 }  // namespace lq

@@ -2717,7 +2717,8 @@ int lq_batch_clip_counts(const lq_batch* b, int tensor, const uint32_t** dev, in
 struct lq_group_table {
     std::vector<lq::GroupTask> h;
     std::vector<int> index;               // table position -> descriptor index (tasks are ordered by work per block)
-    lq::GroupTask* d = nullptr;
+    lq::GroupTask* d = nullptr;           // a batch without offsets
+    lq::GroupAffineTask* da = nullptr;    // a batch with offsets: the same tasks, each with its b, db and kb
     uint32_t* block_task_d = nullptr;     // [blocks] task of every block
     uint32_t blocks = 0;
 };
@@ -2725,6 +2726,8 @@ struct lq_group_table {
 struct lq_group_batch {
     int n = 0;
     int rounding = 0;
+    bool affine = false;                  // some tensor has an offset: the tables are GroupAffineTask, the kernel k_group_batch_affine
+    std::vector<lq_group_offset> offs;    // per descriptor; empty without offsets
     lq_group_table fwd, bwd;
     std::vector<const uint32_t*> counts;  // per descriptor: its slice of counts_d
     std::vector<int64_t> groups;          // per descriptor: scale elements
@@ -2746,8 +2749,9 @@ static void fill_group_task(GroupTask& t, const GroupParams& p, int axis, bool v
     t.first_block = L.blocks;
 }
 
-// Orders the table so that the heaviest units start first (as finish_table), assigns the block prefix and uploads it
-static int finish_group_table(lq_group_table& tb) {
+// Orders the table so that the heaviest units start first (as finish_table), assigns the block prefix, uploads the block table and
+// allocates the task table; affine: its entries are GroupAffineTask (a batch with offsets), else GroupTask
+static int finish_group_table(lq_group_table& tb, bool affine) {
     const size_t n = tb.h.size();
     std::vector<size_t> order(n);
     for (size_t i = 0; i < n; ++i) order[i] = i;
@@ -2774,15 +2778,17 @@ static int finish_group_table(lq_group_table& tb) {
     }
     hipError_t e = hipMalloc(&tb.block_task_d, bt.size() * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMemcpy(tb.block_task_d, bt.data(), bt.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(&tb.d, n * sizeof(GroupTask));
+    if (e == hipSuccess) e = affine ? hipMalloc(&tb.da, n * sizeof(GroupAffineTask)) : hipMalloc(&tb.d, n * sizeof(GroupTask));
     if (e != hipSuccess) return fail(LQ_EHIP, "lq_group_batch_create: %s", hipGetErrorString(e));
     return LQ_OK;
 }
 
 static void free_group_table(lq_group_table& tb) {
     if (tb.d) (void)hipFree(tb.d);
+    if (tb.da) (void)hipFree(tb.da);
     if (tb.block_task_d) (void)hipFree(tb.block_task_d);
     tb.d = nullptr;
+    tb.da = nullptr;
     tb.block_task_d = nullptr;
 }
 
@@ -2790,8 +2796,10 @@ static void free_group_table(lq_group_table& tb) {
 
 extern "C" {
 
-int lq_group_batch_create(const lq_group_desc* descs, int n, int rounding, lq_group_batch** out) {
-    const char* fn = "lq_group_batch_create";
+// lq_group_batch_create and lq_group_batch_create_affine.  offs == NULL, or no tensor with a b: the tables and the kernel of a
+// batch without offsets
+static int group_batch_create(const char* fn, const lq_group_desc* descs, const lq_group_offset* offs, int n, int rounding,
+                              lq_group_batch** out) {
     if (!out) return fail(LQ_EINVAL, "%s: out is NULL", fn);
     *out = nullptr;
     if (!descs) return fail(LQ_EINVAL, "%s: descs is NULL", fn);
@@ -2810,10 +2818,22 @@ int lq_group_batch_create(const lq_group_desc* descs, int n, int rounding, lq_gr
         if ((rc = check_group(who, d.R, d.C, d.axis, d.gs))) return rc;
         if ((rc = check_clip_range(who, d.qmin, d.qmax))) return rc;
     }
+    bool affine = false;
+    for (int i = 0; offs && i < n; ++i) {
+        const lq_group_offset& o = offs[i];
+        if (o.db && !o.b) return fail(LQ_EINVAL, "%s: tensor %d has a db but no offset b", fn, i);
+        if (o.b && !std::isfinite(o.offset_grad_scale))
+            return fail(LQ_EINVAL, "%s: tensor %d: offset_grad_scale %g is not finite", fn, i, (double)o.offset_grad_scale);
+        if ((o.b && !aligned(o.b, 4)) || (o.db && !aligned(o.db, 4)))
+            return fail(LQ_EALIGN, "%s: tensor %d: b and db must be 4-byte aligned", fn, i);
+        affine = affine || o.b != nullptr;
+    }
     lq_group_batch* b = new (std::nothrow) lq_group_batch();
     if (!b) return fail(LQ_EHIP, "%s: out of host memory", fn);
     b->n = n;
     b->rounding = rounding;
+    b->affine = affine;
+    if (affine) b->offs.assign(offs, offs + n);
     b->counts.resize(n);
     b->groups.resize(n);
     int64_t total = 0;
@@ -2844,9 +2864,24 @@ int lq_group_batch_create(const lq_group_desc* descs, int n, int rounding, lq_gr
         b->bwd.index.push_back(i);
     }
     for (lq_group_table* tb : {&b->fwd, &b->bwd}) {
-        if (!rc) rc = finish_group_table(*tb);
-        if (!rc && hipMemcpy(tb->d, tb->h.data(), tb->h.size() * sizeof(GroupTask), hipMemcpyHostToDevice) != hipSuccess)
-            rc = fail(LQ_EHIP, "%s: table upload failed", fn);
+        if (!rc) rc = finish_group_table(*tb, affine);
+        if (rc) break;
+        hipError_t e;
+        if (affine) {      // the ordered tasks, each with its descriptor's offset; db only where the backward writes it
+            std::vector<GroupAffineTask> ha(tb->h.size());
+            for (size_t k = 0; k < ha.size(); ++k) {
+                const lq_group_offset& o = b->offs[tb->index[k]];
+                memset(&ha[k], 0, sizeof(GroupAffineTask));
+                ha[k].t = tb->h[k];
+                ha[k].b = o.b;
+                ha[k].db = tb == &b->bwd ? o.db : nullptr;
+                ha[k].kb = o.b ? o.offset_grad_scale : 0.0f;
+            }
+            e = hipMemcpy(tb->da, ha.data(), ha.size() * sizeof(GroupAffineTask), hipMemcpyHostToDevice);
+        } else {
+            e = hipMemcpy(tb->d, tb->h.data(), tb->h.size() * sizeof(GroupTask), hipMemcpyHostToDevice);
+        }
+        if (e != hipSuccess) rc = fail(LQ_EHIP, "%s: table upload failed", fn);
     }
     if (rc) {
         (void)lq_group_batch_destroy(b);
@@ -2854,6 +2889,14 @@ int lq_group_batch_create(const lq_group_desc* descs, int n, int rounding, lq_gr
     }
     *out = b;
     return LQ_OK;
+}
+
+int lq_group_batch_create(const lq_group_desc* descs, int n, int rounding, lq_group_batch** out) {
+    return group_batch_create("lq_group_batch_create", descs, nullptr, n, rounding, out);
+}
+
+int lq_group_batch_create_affine(const lq_group_desc* descs, const lq_group_offset* offs, int n, int rounding, lq_group_batch** out) {
+    return group_batch_create("lq_group_batch_create_affine", descs, offs, n, rounding, out);
 }
 
 int lq_group_batch_destroy(lq_group_batch* b) {
@@ -2878,7 +2921,11 @@ int lq_group_batch_forward(const lq_group_batch* b, void* stream) {
     memset(&cf, 0, sizeof(cf));
     const lq_group_table& tb = b->fwd;
     hipStream_t st = (hipStream_t)stream;
-    if (b->rounding == LQ_ROUND_NEAREST_EVEN)
+    const bool rne = b->rounding == LQ_ROUND_NEAREST_EVEN;
+    if (b->affine) {
+        if (rne) hipLaunchKernelGGL((k_group_batch_affine<true, false>), dim3(tb.blocks), dim3(kBlock), 0, st, tb.da, tb.block_task_d, pk, cf, 0);
+        else hipLaunchKernelGGL((k_group_batch_affine<false, false>), dim3(tb.blocks), dim3(kBlock), 0, st, tb.da, tb.block_task_d, pk, cf, 0);
+    } else if (rne)
         hipLaunchKernelGGL((k_group_batch<true, false>), dim3(tb.blocks), dim3(kBlock), 0, st, tb.d, tb.block_task_d, pk, cf, 0);
     else
         hipLaunchKernelGGL((k_group_batch<false, false>), dim3(tb.blocks), dim3(kBlock), 0, st, tb.d, tb.block_task_d, pk, cf, 0);
@@ -2910,7 +2957,11 @@ int lq_group_batch_backward(const lq_group_batch* b, const float* const* dy, con
     }
     hipStream_t st = (hipStream_t)stream;
     const int mask_only = grad_scale ? 0 : 1;
-    if (b->rounding == LQ_ROUND_NEAREST_EVEN)
+    const bool rne = b->rounding == LQ_ROUND_NEAREST_EVEN;
+    if (b->affine) {
+        if (rne) hipLaunchKernelGGL((k_group_batch_affine<true, true>), dim3(tb.blocks), dim3(kBlock), 0, st, tb.da, tb.block_task_d, pk, cf, mask_only);
+        else hipLaunchKernelGGL((k_group_batch_affine<false, true>), dim3(tb.blocks), dim3(kBlock), 0, st, tb.da, tb.block_task_d, pk, cf, mask_only);
+    } else if (rne)
         hipLaunchKernelGGL((k_group_batch<true, true>), dim3(tb.blocks), dim3(kBlock), 0, st, tb.d, tb.block_task_d, pk, cf, mask_only);
     else
         hipLaunchKernelGGL((k_group_batch<false, true>), dim3(tb.blocks), dim3(kBlock), 0, st, tb.d, tb.block_task_d, pk, cf, mask_only);

@@ -144,6 +144,8 @@ def build_parser():
                     help="with --batched and --bits: run the clipped layers in the multi-tensor batch (opt-in, see train.py)")
     ap.add_argument("--group-batch", action="store_true",
                     help="with --batched, --bits and --group-size: run the group-wise layers in the group batch (opt-in, see train.py)")
+    ap.add_argument("--asymmetric-batch", action="store_true",
+                    help="with --asymmetric, --batched and --group-batch: the group batch also carries the offsets (opt-in, see train.py)")
     ap.add_argument("--loss-values", action="store_true",
                     help="with --custom_loss: loss and val_loss include rate * penalty (what Keras reports for compute_total_loss) "
                          "and custom_losses/*.log get one line per step, from a device-side log flushed at every epoch end")
@@ -173,7 +175,8 @@ def main(argv=None):
                  log_dir=log_dir, batched=args.batched, loss_values=args.loss_values,
                  loss_log_capacity=max(4096, args.steps_per_epoch), bits=args.bits, rounding=args.rounding,
                  clipped_batch=args.clipped_batch, group_size=args.group_size,
-                 group_batch=args.group_batch, scale_init=args.scale_init, asymmetric=args.asymmetric)
+                 group_batch=args.group_batch, scale_init=args.scale_init, asymmetric=args.asymmetric,
+                 asymmetric_batch=args.asymmetric_batch)
     if args.training == "post_training":
         if args.config != "mnist" or not args.baseline_weights:
             raise SystemExit("post_training needs --config mnist --baseline-weights <npz with W1,b1,W2,b2> "

@@ -73,10 +73,15 @@ class Trainer:
                  bucket_mb: float = 25.0, overlap: bool = True, graph_collectives: Optional[bool] = None,
                  force_collectives: bool = False, kernel_storage: str = "oihw", loss_values: bool = False,
                  loss_log_capacity: int = 4096, grad_scale=None, bits=None, signed=True, q_range=None, rounding="floor",
-                 clipped_batch: bool = False, group_size=None, group_batch: bool = False, scale_init=None, asymmetric: bool = False):
-        """``asymmetric`` (with ``group_size``, a range and mode "ste"; eager, graphed and data-parallel mode "A", per-tensor path
-        only): every group-wise kernel also learns an offset per group (models.build_model); the offsets are stepped by the
-        scales' optimizer, without a lower bound.  ``scale_init="minmax"`` exists for such models only.
+                 clipped_batch: bool = False, group_size=None, group_batch: bool = False, scale_init=None, asymmetric: bool = False,
+                 asymmetric_batch: bool = False):
+        """``asymmetric`` (with ``group_size``, a range and mode "ste"; eager, graphed and data-parallel mode "A"; per-tensor path
+        unless ``asymmetric_batch``): every group-wise kernel also learns an offset per group (models.build_model); the offsets
+        are stepped by the scales' optimizer, without a lower bound.  ``scale_init="minmax"`` exists for such models only.
+        ``asymmetric_batch`` (opt-in, with ``asymmetric``, ``group_batch`` and ``batched``; eager, graphed, data-parallel mode
+        "A"): the group batch also carries the offsets (``FakeQuantBatch(group_batch=True, asymmetric=True)``): still one forward
+        and one backward launch for the whole model, the backward writes every offset's gradient too (into the data-parallel
+        bucket's views where there is one), and scales and offsets are stepped by one launch.
         ``scale_init`` ("absmax" / "lsq" / "mse"; with ``bits`` / ``q_range``): every scale starts from its layer's weights
         (layers.init_scales) instead of the library's initial value, at which a range clips every weight.  It runs once, on the
         device, after the weights are in place and before the optimizers, the batch, the graph and the data-parallel wrapper are
@@ -109,12 +114,17 @@ class Trainer:
         self.asymmetric = bool(asymmetric)
         if asymmetric:
             check_asymmetric_model(mode, bits is not None or q_range is not None, group_size, kernel_storage)
-            if batched:
-                raise ValueError("asymmetric=True with batched=True: neither multi-tensor batch (clipped_batch, group_batch) carries "
-                                 "an offset per group; asymmetric layers run on the per-tensor path")
+            if batched and not asymmetric_batch:
+                raise ValueError("asymmetric=True with batched=True: the multi-tensor batches carry no offset per group unless asked "
+                                 "to; asymmetric layers run on the per-tensor path, or opt in to offsets in the group batch "
+                                 "(group_batch=True, asymmetric_batch=True / --group-batch --asymmetric-batch)")
             if ddp_mode == "B":
                 raise ValueError("asymmetric=True with ddp_mode 'B': it recomputes ds from the all-reduced dP, which no longer holds "
                                  "the dy of the clipped elements -- the very elements the offset's gradient sums; use ddp_mode 'A'")
+        if asymmetric_batch and not (asymmetric and group_batch and batched):
+            raise ValueError("asymmetric_batch=True belongs to asymmetric=True, group_batch=True and batched=True: it lets the group "
+                             "batch carry the offsets of an asymmetric model")
+        self.asymmetric_batch = bool(asymmetric_batch)
         if scale_init == "minmax":
             if not asymmetric:
                 raise ValueError('scale_init "minmax" on a symmetric model: it places each group\'s range over [min, max] through an '
@@ -202,7 +212,7 @@ class Trainer:
             # the convolutions consume the OIHW companions only; autograd=False: the fake-quantised tensors are leaves and
             # _backward_phase calls finish_backward() itself (0.4-0.6 ms less autograd-engine work per eager step for 40 tensors)
             self.batch = FakeQuantBatch(self.model, lr=lr, hwio_out=False, autograd=False, clipped=self.clipped_batch,
-                                        group_batch=self.group_batch)
+                                        group_batch=self.group_batch, asymmetric=self.asymmetric_batch)
             # nothing touches ds between its computation and the scales' update when there is no loss term and ds is not
             # exchanged (one process, or exact mode B): the finalize then applies the Adam step itself (one launch fewer)
             # (the fused finalize + Adam is the nested-quantization pass's: not for the straight-through modes)
@@ -442,13 +452,18 @@ class Trainer:
 
 class DriverParser(argparse.ArgumentParser):
     """Argument parser of both drivers: what the flags refuse in combination is refused here, as a usage error, before any device
-    is touched -- ``--scale-init minmax`` belongs to ``--asymmetric``, which belongs to ``--group-size``."""
+    is touched -- ``--scale-init minmax`` belongs to ``--asymmetric``, which belongs to ``--group-size``; ``--asymmetric-batch``
+    belongs to ``--asymmetric``, ``--group-batch`` and ``--batched``."""
 
     def parse_args(self, args=None, namespace=None):
         ns = super().parse_args(args, namespace)
         if getattr(ns, "asymmetric", False) and getattr(ns, "group_size", None) is None:
             self.error("--asymmetric needs --group-size: offsets exist per group (a group size of the line length or more gives "
                        "per-channel offsets)")
+        if getattr(ns, "asymmetric_batch", False) and not (getattr(ns, "asymmetric", False) and getattr(ns, "group_batch", False)
+                                                           and getattr(ns, "batched", False)):
+            self.error("--asymmetric-batch needs --asymmetric, --group-batch and --batched: it lets the group batch carry the "
+                       "offsets of an asymmetric model")
         if getattr(ns, "scale_init", None) == "minmax" and not getattr(ns, "asymmetric", False):
             self.error("--scale-init minmax needs --asymmetric: it places each group's range over [min, max] through an offset, "
                        "which a symmetric layer does not have")
@@ -472,7 +487,7 @@ def build_parser():
                          "--orientation; biases keep a scalar scale)")
     ap.add_argument("--asymmetric", action="store_true",
                     help="with --bits, --group-size and mode ste: every group-wise kernel also learns an offset per group (per-tensor "
-                         "path; biases stay symmetric)")
+                         "path unless --asymmetric-batch; biases stay symmetric)")
     ap.add_argument("--scale-init", default=None, choices=list(LAYER_SCALE_INITS),
                     help="with --bits: start every scale from its weights (absmax: nothing clipped; lsq: 2 mean|w| / sqrt(Qp); mse: "
                          "least squared error below absmax; minmax, with --asymmetric only: scale and offset from each group's "
@@ -504,6 +519,9 @@ def build_parser():
     ap.add_argument("--group-batch", action="store_true",
                     help="with --batched, --bits and --group-size: run the group-wise layers and their biases in the group batch "
                          "(opt-in: one forward and one backward launch for the whole model)")
+    ap.add_argument("--asymmetric-batch", action="store_true",
+                    help="with --asymmetric, --batched and --group-batch: the group batch also carries the offsets (opt-in: still one "
+                         "forward and one backward launch, which writes the offsets' gradients too)")
     ap.add_argument("--loss-values", action="store_true",
                     help="modes cl / nqcl: evaluate the penalty with its gradients, report mean(SCCE) + rate * penalty and keep the "
                          "reference's per-step loss logs in a device buffer (written at the end)")
@@ -554,7 +572,7 @@ def main(argv=None):
                              (args.grad_scale if args.grad_scale == "rsqrt_group" else float(args.grad_scale))),
                  bits=args.bits, signed=not args.unsigned, rounding=args.rounding, clipped_batch=args.clipped_batch,
                  group_size=args.group_size, group_batch=args.group_batch, scale_init=args.scale_init,
-                 asymmetric=args.asymmetric)
+                 asymmetric=args.asymmetric, asymmetric_batch=args.asymmetric_batch)
     do_step = tr.step_graphed if args.graph else tr.step
     g = torch.Generator(device=dev).manual_seed(args.seed + rank)
     batches = [synthetic_batch(args.config, args.batch, dev, g) for _ in range(4)]
@@ -589,6 +607,7 @@ def main(argv=None):
             **({"graph_note": tr.graph_note} if tr.graph_note else {}), "batched": bool(args.batched),
             **({"clipped_batch": True} if args.clipped_batch else {}),
             **({"group_batch": True} if args.group_batch else {}),
+            **({"asymmetric_batch": True} if args.asymmetric_batch else {}),
             "backend": (args.backend if use_dist else None),
             "channels_last": bool(args.channels_last), "kernel_storage": args.kernel_storage,
             **({"q_range": list(tr.q_range)} if tr.q_range else {}),

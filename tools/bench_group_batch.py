@@ -15,7 +15,14 @@ the whole weight set), the rounds interleave the variants, the figure is the med
 whole comparison is repeated ``--repeats`` times in the process, so the yardstick's own run-to-run spread is visible.  One JSON
 line per set and repeat.
 
+``--asymmetric``: the same three weight sets with a learned offset per group on every kernel (the biases stay symmetric and
+scalar, as in an asymmetric model).  Yardstick: ``lq_fq_forward_group_affine`` + ``lq_fq_backward_group_affine`` per kernel plus the
+three launches per bias.  Candidate: the batch of ``lq_group_batch_create_affine`` (two launches).  A third pair of variants, timed in
+the same rounds, is the SYMMETRIC batch over the same buffers (it ignores the offsets): what the offsets cost inside the batch.
+Before anything is timed the tool asserts that out, dP, ds and db of the affine batch equal the per-tensor calls' bit for bit.
+
     python tools/bench_group_batch.py [--configs cifar imagenette resnet50] [--rounds 15] [--inner 10] [--sets 4] [--repeats 3] [--out FILE]
+                                      [--asymmetric]
 """
 import argparse
 import ctypes
@@ -58,6 +65,7 @@ def main():
     ap.add_argument("--bits", type=int, default=4)
     ap.add_argument("--group-size", type=int, default=128)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--asymmetric", action="store_true", help="kernels with an offset per group: the affine batch against the affine per-tensor calls")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file as well")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -79,7 +87,10 @@ def main():
                 else:
                     geom = (1, numel, 1, numel)
                 s = torch.exp2(torch.empty(sshape, device=dev).uniform_(-9.0, -5.0, generator=g))
+                affine = args.asymmetric and gs is not None
                 tensors.append(dict(geom=geom, group=gs is not None, numel=numel, qmin=qmin, qmax=qmax, s=s, ds=torch.empty_like(s),
+                                    b=torch.empty_like(s).uniform_(-6.0, 6.0, generator=g) * s if affine else None,
+                                    db=torch.empty_like(s) if affine else None,
                                     cl=torch.empty_like(s, dtype=torch.int32),
                                     ws=None if gs is not None else _hip.workspace_for(dev, 1, 1, numel).clone()))
             n = len(tensors)
@@ -93,11 +104,16 @@ def main():
                 arr = (_hip.GroupDesc * n)(*[_hip.GroupDesc(P.data_ptr(), t["s"].data_ptr(), out.data_ptr(), dp.data_ptr(), t["ds"].data_ptr(),
                                                             t["geom"][0], t["geom"][1], t["geom"][3], t["geom"][2], t["qmin"], t["qmax"])
                                              for t, (P, dy, out, dp) in zip(tensors, bufs)])
-                h = ctypes.c_void_p()
-                _hip.check(lib.lq_group_batch_create(arr, n, 0, ctypes.byref(h)), "lq_group_batch_create")
+                h, hs = ctypes.c_void_p(), ctypes.c_void_p()
+                if args.asymmetric:
+                    offs = (_hip.GroupOffset * n)(*[_hip.GroupOffset(_hip.ptr(t["b"]), _hip.ptr(t["db"]), 1.0) for t in tensors])
+                    _hip.check(lib.lq_group_batch_create_affine(arr, offs, n, 0, ctypes.byref(h)), "lq_group_batch_create_affine")
+                    _hip.check(lib.lq_group_batch_create(arr, n, 0, ctypes.byref(hs)), "lq_group_batch_create")
+                else:
+                    _hip.check(lib.lq_group_batch_create(arr, n, 0, ctypes.byref(h)), "lq_group_batch_create")
                 dys = (ctypes.c_void_p * n)(*[dy.data_ptr() for _, dy, _, _ in bufs])
                 sets.append(bufs)
-                handles.append((h, dys))
+                handles.append((h, dys, hs))
             ks = (ctypes.c_float * n)(*([1.0] * n))
             need = lib.lq_group_batch_workspace_bytes(handles[0][0])
             bws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
@@ -106,7 +122,10 @@ def main():
                 rc = 0
                 for t, (P, dy, out, dp) in zip(tensors, sets[k]):
                     R, C, axis, gs = t["geom"]
-                    if t["group"]:
+                    if t["b"] is not None:
+                        rc |= lib.lq_fq_forward_group_affine(P.data_ptr(), t["s"].data_ptr(), t["b"].data_ptr(), out.data_ptr(), None,
+                                                             _hip.LQ_Q_NONE, t["qmin"], t["qmax"], 0, R, C, axis, gs, sp)
+                    elif t["group"]:
                         rc |= lib.lq_fq_forward_group(P.data_ptr(), t["s"].data_ptr(), out.data_ptr(), None, _hip.LQ_Q_NONE, t["qmin"], t["qmax"], 0,
                                                 R, C, axis, gs, sp)
                     else:
@@ -118,7 +137,11 @@ def main():
                 rc = 0
                 for t, (P, dy, out, dp) in zip(tensors, sets[k]):
                     R, C, axis, gs = t["geom"]
-                    if t["group"]:
+                    if t["b"] is not None:
+                        rc |= lib.lq_fq_backward_group_affine(P.data_ptr(), t["s"].data_ptr(), t["b"].data_ptr(), dy.data_ptr(), t["qmin"],
+                                                              t["qmax"], 0, 1.0, 1.0, dp.data_ptr(), t["ds"].data_ptr(), t["db"].data_ptr(),
+                                                              t["cl"].data_ptr(), None, 0, R, C, axis, gs, sp)
+                    elif t["group"]:
                         rc |= lib.lq_fq_backward_group(P.data_ptr(), t["s"].data_ptr(), dy.data_ptr(), t["qmin"], t["qmax"], 0, 1.0, dp.data_ptr(),
                                                  t["ds"].data_ptr(), t["cl"].data_ptr(), None, 0, R, C, axis, gs, sp)
                     else:
@@ -134,6 +157,28 @@ def main():
 
             variants = {"forward_per_tensor": fwd_per_tensor, "forward_batch": fwd_batch, "backward_per_tensor": bwd_per_tensor,
                         "backward_batch": bwd_batch}
+            if args.asymmetric:
+                variants["forward_symmetric_batch"] = lambda k: lib.lq_group_batch_forward(handles[k][2], sp)
+                variants["backward_symmetric_batch"] = lambda k: lib.lq_group_batch_backward(handles[k][2], handles[k][1], ks, None, 0, sp)
+
+            def outputs():
+                torch.cuda.synchronize(dev)
+                return ([(out.clone(), dp.clone()) for _, _, out, dp in sets[0]], [t["ds"].clone() for t in tensors],
+                        [t["db"].clone() for t in tensors if t["db"] is not None])
+
+            if args.asymmetric:      # before anything is timed: the candidate computes what the yardstick computes, bit for bit
+                _hip.check(fwd_per_tensor(0) | bwd_per_tensor(0), "per-tensor pass")
+                w_out, w_ds, w_db = outputs()
+                for t in tensors:
+                    t["ds"].fill_(float("nan"))
+                    if t["db"] is not None:
+                        t["db"].fill_(float("nan"))
+                _hip.check(fwd_batch(0) | bwd_batch(0), "batch pass")
+                g_out, g_ds, g_db = outputs()
+                assert all(torch.equal(a, c) and torch.equal(b, d) for (a, b), (c, d) in zip(g_out, w_out)), "out / dP differ"
+                assert all(torch.equal(a, b) for a, b, t in zip(g_ds, w_ds, tensors) if t["group"]), "ds of a kernel differs"
+                assert len(g_db) == sum(t["group"] for t in tensors) and all(torch.equal(a, b) for a, b in zip(g_db, w_db)), "db differs"
+                assert all(bool((d != 0).any()) for d in g_db), "an offset gradient is zero everywhere: nothing clips"
             times = {k: [] for k in variants}
             for key, fn in variants.items():
                 for k in range(args.sets):
@@ -163,17 +208,25 @@ def main():
                    "bits": args.bits, "group_size": args.group_size, "repeat": repeat, "rounds": args.rounds, "inner": args.inner,
                    "buffer_sets": args.sets, "launches_per_tensor_path": sum(2 if t["group"] else 3 for t in tensors),
                    "launches_batch": 2, "out_dp_bit_identical": bool(same), "kernel_ds_bit_identical": bool(same_ds)}
+            if args.asymmetric:
+                row["asymmetric"] = True
+                row["kernel_ds_db_bit_identical_before_timing"] = True      # asserted above
             for key in variants:
                 row[f"us_{key}"] = statistics.median(times[key])
                 row[f"us_{key}_min_max"] = [min(times[key]), max(times[key])]
             row["us_sum_per_tensor"] = row["us_forward_per_tensor"] + row["us_backward_per_tensor"]
             row["us_sum_batch"] = row["us_forward_batch"] + row["us_backward_batch"]
             row["batch_over_per_tensor"] = row["us_sum_batch"] / row["us_sum_per_tensor"]
+            if args.asymmetric:
+                row["us_sum_symmetric_batch"] = row["us_forward_symmetric_batch"] + row["us_backward_symmetric_batch"]
+                row["affine_batch_over_symmetric_batch"] = row["us_sum_batch"] / row["us_sum_symmetric_batch"]
             line = json.dumps(row)
             print(line, flush=True)
             lines.append(line)
-            for h, _ in handles:
+            for h, _, hs in handles:
                 lib.lq_group_batch_destroy(h)
+                if hs:
+                    lib.lq_group_batch_destroy(hs)
             del sets, handles, tensors
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -26,7 +26,7 @@ import torch
 
 from . import _hip
 from .descriptor import group_geometry, memory_descriptor
-from .layers import CustomDenseLayer, _ConvBase, custom_layers_of
+from .layers import _ConvBase, _HostLayer, custom_layers_of
 from .ops import ROUNDINGS
 
 
@@ -40,6 +40,318 @@ class _DeviceInts:
 
     def __init__(self, address: int, count: int):
         self.__cuda_array_interface__ = {"shape": (int(count),), "typestr": "<i4", "data": (int(address), False), "version": 2}
+
+
+class _Kind:
+    """What one kind of batch owns: its refusals (``check``, ``describe``: before any device call), what an entry holds beyond the
+    common buffers (``own``), the library handle or handles with their workspace (``create`` / ``destroy``), the four per-step
+    calls (``forward``, ``backward``, ``clip_counts``, ``adam_step``: bound once by ``FakeQuantBatch.__init__``) and the
+    capabilities below.  A kind never refers to its batch: it keeps the arrays its calls pass on (``_bind``)."""
+    owns_dp = False        # the backward writes a masked dP of every tensor into a buffer of the batch (else dP is dy itself)
+    loss_terms = True      # penalty_values() / inject_penalty_grads()
+    defers = True          # defer_scale_grads / scale_grads_from_param_grads(): exact data-parallel mode B
+    fuses = True           # BatchedScaleAdam(fused=True); where False, ``name`` says what to build fused=False for
+    handle = None          # the lq_batch handle (FakeQuantBatch._handle): penalty calls, bench.py and the tools pass it on
+    fused_opt = None       # BatchedScaleAdam(fused=True): the scale-gradient finalize applies the Adam step itself
+
+    @staticmethod
+    def _destroy(handle, destroy: str):
+        """Destroys a library handle, if there is one.  Never raises: it runs from ``FakeQuantBatch.__del__``."""
+        if handle:
+            try:
+                getattr(_hip.load(), destroy)(handle)
+            except Exception:
+                pass
+
+    def _bind(self, batch):
+        self.entries, self.device, self.hyper = batch.entries, batch.device, batch.hyper
+        self.ptrs, self.grad_scales = batch._ptrs, batch._grad_scales
+
+    def _counts(self, fn, handle, what: str):
+        out = []
+        for i, e in enumerate(self.entries):
+            dev, groups = ctypes.c_void_p(), ctypes.c_int64()
+            _hip.check(fn(handle, i, ctypes.byref(dev), ctypes.byref(groups)), what)
+            view = torch.as_tensor(_DeviceInts(dev.value, groups.value), device=self.device)
+            out.append(view.clone().reshape(e.scale.shape))
+        return out
+
+
+class _DefaultKind(_Kind):
+    """The default batch on ``lq_batch_*``: the vote, ``"ste"`` or STE-only scale rule; ``dP`` is ``dy`` itself."""
+
+    def check(self, layers, nested_layers):
+        if any(getattr(n, "q_range", None) is not None for n in nested_layers):
+            raise ValueError("FakeQuantBatch over a clipped layer (bits / q_range): the multi-tensor backward hands dy on as dP, "
+                             "but a clipped layer's dP is a masked copy of dy; run such a model on the per-tensor path (batched=False), "
+                             "or opt in to the clipped batch, which owns a dP buffer per tensor: FakeQuantBatch(..., clipped=True)")
+        self._one_rule(nested_layers)
+        self.rounding = "floor"
+
+    def _one_rule(self, nested_layers):
+        rules = {n.scale_gradient for n in nested_layers}
+        if "ste" in rules and len(rules) > 1:
+            raise ValueError('one FakeQuantBatch holds one scale-gradient rule: every layer needs scale_gradient="ste", or none')
+        self.ste = "ste" in rules
+
+    def describe(self, layer, param, nested):
+        # a dense permutation of the logical axes (conv kernels stored OIHW, layers.py kernel_storage) is described in
+        # memory order; outputs and gradients carry the parameter's strides
+        desc = memory_descriptor(tuple(param.shape), param.data.stride(), tuple(nested.scale.shape))
+        if desc is None:
+            raise ValueError("parameters must be dense (contiguous, or a permutation of a contiguous array)")
+        if self.ste and isinstance(layer, _ConvBase) and layer.kernel_storage == "hwio":
+            raise ValueError('a batched scale_gradient="ste" model takes conv kernels in the memory order the convolution '
+                             'consumes: build it with kernel_storage="oihw"')
+        return desc
+
+    def own(self, batch, e, oihw: bool, hwio_out: bool):
+        # conv kernels of nested-quantization layers: the forward launch also emits the OIHW tensor MIOpen consumes and
+        # the scale-gradient launch reads MIOpen's OIHW weight gradient, writing dP back in HWIO order (lq_hip.h:
+        # lq_fq_forward_oihw) -- no transposition launches around the convolutions
+        param = e.param
+        if (oihw and e.slot == 0 and isinstance(e.layer, _ConvBase) and e.nested.penalty_threshold is not None
+                and param.data.is_contiguous()):          # HWIO-stored kernels only: an OIHW-stored one needs no companion
+            kh, kw, ci, co = (int(d) for d in param.shape)
+            e.conv = (kh * kw, ci, co)
+            e.out_oihw = torch.empty((co, ci, kh, kw), dtype=torch.float32, device=param.device)
+            e.dp = torch.empty_like(param.data)
+            if (not hwio_out and param.data_ptr() % 16 == 0
+                    and _hip.load().lq_conv_tile_supported(kh * kw, ci, co, *e.desc) == 1):
+                e.out = None               # the companion is the only forward output of this tensor
+
+    def create(self, batch):
+        self._bind(batch)
+        lib = _hip.load()
+        n = len(self.entries)
+        arr = (_hip.TensorDesc * n)()
+        for i, e in enumerate(self.entries):
+            lam = e.nested.penalty_threshold
+            c = getattr(e.nested.scale, "lq_constraint", None)
+            arr[i] = _hip.TensorDesc(e.param.data_ptr(), e.nested.scale.data_ptr(), None, _hip.ptr(e.out), e.ds.data_ptr(),
+                                     e.m.data_ptr(), e.v.data_ptr(), e.desc[0], e.desc[1], e.desc[2],
+                                     float("nan") if lam is None else float(lam),
+                                     float(c.min_value) if c is not None else float("-inf"),
+                                     _hip.ptr(e.out_oihw), _hip.ptr(e.dp), *(e.conv or (0, 0, 0)))
+        handle = ctypes.c_void_p()
+        _hip.check(lib.lq_batch_create(arr, n, ctypes.byref(handle)), "lq_batch_create")
+        self.handle = handle
+        self._set_up(lib, n)
+        self.ws = torch.empty(lib.lq_batch_workspace_bytes(handle), dtype=torch.uint8, device=self.device)
+
+    def _set_up(self, lib, n: int):
+        pass
+
+    def destroy(self):
+        self._destroy(self.handle, "lq_batch_destroy")
+        self.handle = None
+
+    def forward(self):
+        _hip.check(_hip.load().lq_batch_forward(self.handle, _hip.stream_ptr(self.device)), "lq_batch_forward")
+
+    def backward(self, oihw: bool):
+        """lq_batch_scale_grad(_oihw), or -- a fused optimizer attached -- lq_batch_scale_grad_step: same launches, the finalize
+        also applies the scales' Adam step."""
+        lib = _hip.load()
+        opt = self.fused_opt
+        sp = _hip.stream_ptr(self.device)
+        if self.ste:
+            _hip.check(lib.lq_batch_scale_grad_ste(self.handle, self.ptrs, self.grad_scales, _hip.ptr(self.ws), self.ws.numel(), sp),
+                       "lq_batch_scale_grad_ste")
+            return
+        if opt is None:
+            fn = lib.lq_batch_scale_grad_oihw if oihw else lib.lq_batch_scale_grad
+            _hip.check(fn(self.handle, self.ptrs, _hip.ptr(self.ws), self.ws.numel(), sp), "lq_batch_scale_grad")
+            return
+        if opt._applied:
+            # the finalize of a scale-gradient pass applies Adam: a second pass before step() (gradient accumulation, a retried
+            # backward) would update the scales twice and the weights once
+            raise RuntimeError("FakeQuantBatch: the fused scale update of this step has already been applied; call the optimizer's "
+                               "step() first, or build BatchedScaleAdam(fused=False) (fused=True excludes gradient accumulation)")
+        step, step_dev = opt._advance()
+        h = self.hyper
+        _hip.check(lib.lq_batch_scale_grad_step(self.handle, self.ptrs, 1 if oihw else 0, _hip.ptr(self.ws), self.ws.numel(),
+                                                h["lr"], h["betas"][0], h["betas"][1], h["eps"], int(step or 0), _hip.ptr(step_dev),
+                                                _hip.adam_mode(h["mode"]), sp), "lq_batch_scale_grad_step")
+        opt._applied = True
+
+    def clip_counts(self):
+        raise RuntimeError("clip_counts() belongs to FakeQuantBatch(clipped=True) and FakeQuantBatch(group_batch=True)")
+
+    def adam_step(self, step: Optional[int] = None, step_dev: Optional[torch.Tensor] = None):
+        h = self.hyper
+        _hip.check(_hip.load().lq_batch_scale_adam(self.handle, h["lr"], h["betas"][0], h["betas"][1], h["eps"],
+                                                   int(step or 0), _hip.ptr(step_dev), _hip.adam_mode(h["mode"]), _hip.stream_ptr(self.device)),
+                   "lq_batch_scale_adam")
+
+
+class _ClippedKind(_DefaultKind):
+    """The clipped batch: ``lq_batch_*`` plus ``lq_batch_set_clip``; the backward writes the masked ``dP`` of every tensor."""
+    owns_dp = True
+    defers = False
+    fuses = False
+    name = "a clipped batch"
+    _REFUSALS = {
+        "defer_scale_grads": "a clipped FakeQuantBatch cannot defer its scale gradients (data-parallel mode B): the exchanged dP is a "
+                             "masked copy of dy and no longer holds the dy of the clipped elements; use mode A",
+        "scale_grads_from_param_grads()": "scale_grads_from_param_grads() reads P.grad as dy; a clipped batch's dP is a masked copy of "
+                                          "dy, which no longer holds the dy of the clipped elements: average ds over the ranks "
+                                          "(data-parallel mode A)"}
+
+    def refuse(self, what: str):
+        raise ValueError(self._REFUSALS[what])
+
+    def check(self, layers, nested_layers):
+        self._one_rule(nested_layers)
+        if any(getattr(n, "q_range", None) is None for n in nested_layers):
+            raise ValueError("FakeQuantBatch(clipped=True) over a layer without a range: every quantised tensor of a clipped batch "
+                             "needs bits / q_range (an unclipped model runs the default batch)")
+        roundings = {n.rounding for n in nested_layers}
+        if len(roundings) > 1:
+            raise ValueError(f"one clipped FakeQuantBatch holds one rounding, got {sorted(roundings)}")
+        self.rounding = next(iter(roundings), "floor")
+        if any(isinstance(layer, _ConvBase) and layer.kernel_storage == "hwio" for layer in layers):
+            raise ValueError('a clipped batch takes conv kernels in the memory order the convolution '
+                             'consumes: build it with kernel_storage="oihw"')
+
+    def own(self, batch, e, oihw: bool, hwio_out: bool):
+        super().own(batch, e, oihw, hwio_out)
+        e.dp = torch.empty_like(e.param.data)            # the masked dP (lq_batch_backward_clip), in the parameter's element order
+
+    def _set_up(self, lib, n: int):
+        qmin = (ctypes.c_int32 * n)(*[int(e.nested.q_range[0]) for e in self.entries])
+        qmax = (ctypes.c_int32 * n)(*[int(e.nested.q_range[1]) for e in self.entries])
+        _hip.check(lib.lq_batch_set_clip(self.handle, qmin, qmax, n, ROUNDINGS.index(self.rounding)), "lq_batch_set_clip")
+
+    def forward(self):
+        _hip.check(_hip.load().lq_batch_forward_clip(self.handle, _hip.stream_ptr(self.device)), "lq_batch_forward_clip")
+
+    def backward(self, oihw: bool):
+        # dP of every tensor into the batch's buffers, the clip counts, and -- rule "ste" -- ds; mask only: no grad_scale, ds untouched
+        _hip.check(_hip.load().lq_batch_backward_clip(self.handle, self.ptrs, self.grad_scales, _hip.ptr(self.ws), self.ws.numel(),
+                                                      _hip.stream_ptr(self.device)), "lq_batch_backward_clip")
+
+    def clip_counts(self):
+        return self._counts(_hip.load().lq_batch_clip_counts, self.handle, "lq_batch_clip_counts")
+
+
+class _GroupKind(_Kind):
+    """The group batch on ``lq_group_batch_*``, with the offsets of asymmetric layers where there are any: entries, buffers and
+    the ``lq_group_batch`` handle (one descriptor per kernel and bias), and an Adam set of its own."""
+    owns_dp = True
+    loss_terms = False
+    defers = False
+    fuses = False
+    name = "a group batch (with or without asymmetric=True: the offsets step with the scales in the Adam set's one launch)"
+    group = None           # the lq_group_batch handle
+    adam_set = None
+
+    def refuse(self, what: str):
+        raise ValueError(f"{what} is not available on FakeQuantBatch(group_batch=True): group-wise scales have no loss term and "
+                         "their dP is a masked copy of dy (no exact data-parallel mode B)")
+
+    def check(self, layers, nested_layers):
+        if any(getattr(n, "q_range", None) is None for n in nested_layers):
+            raise ValueError("FakeQuantBatch(group_batch=True) over a layer without a range: group-wise scales exist for the clipped "
+                             "quantizer only, every quantised tensor needs bits / q_range")
+        rules = {n.scale_gradient for n in nested_layers}
+        if len(rules) > 1:
+            raise ValueError(f"one FakeQuantBatch holds one scale-gradient rule, got {sorted(map(str, rules))}")
+        self.ste = "ste" in rules
+        roundings = {n.rounding for n in nested_layers}
+        if len(roundings) > 1:
+            raise ValueError(f"one group FakeQuantBatch holds one rounding, got {sorted(roundings)}")
+        self.rounding = next(iter(roundings), "floor")
+        if any(n.penalty_threshold is not None or n.penalty_rate is not None for n in nested_layers):
+            raise ValueError("FakeQuantBatch(group_batch=True) with a loss term / penalty_threshold: the penalty kernels broadcast "
+                             "one-axis scales; group-wise scales have no loss term")
+        if any(isinstance(layer, _ConvBase) and layer.kernel_storage == "hwio" for layer in layers):
+            raise ValueError('FakeQuantBatch(group_batch=True) with kernel_storage="hwio": the groups are defined in the memory order '
+                             'the convolution consumes; build the model with kernel_storage="oihw"')
+
+    def describe(self, layer, param, nested):
+        if nested.group_size is not None:
+            R, C, axis = group_geometry(tuple(param.shape), param.data.stride(), tuple(nested.scale.shape), nested.group_size)
+            return R, C, axis, int(nested.group_size)
+        if param.dim() == 1 and param.data.is_contiguous() and nested.scale.numel() == 1:
+            return 1, param.numel(), 1, param.numel()        # a bias with its scalar scale: one line, one group
+        raise ValueError(f"FakeQuantBatch(group_batch=True): a parameter of shape {tuple(param.shape)} with a one-axis scale "
+                         f"of shape {tuple(nested.scale.shape)} is neither group-wise nor a 1-D parameter with a scalar "
+                         "scale; one-axis orientations belong to the clipped batch (clipped=True)")
+
+    def own(self, batch, e, oihw: bool, hwio_out: bool):
+        e.dp = torch.empty_like(e.param.data)                    # the masked dP, in the parameter's element order
+        if getattr(e.nested, "asymmetric", False):               # only where the batch was asked to carry offsets (__init__)
+            e.offset = e.nested.offset
+            _hip.require_device_f32(e.offset.data, "offset")
+            e.db = batch._grad_buffer(e.offset)
+            e.mb = torch.zeros_like(e.offset.data)
+            e.vb = torch.zeros_like(e.offset.data)
+
+    def create(self, batch):
+        self._bind(batch)
+        affine = [e for e in self.entries if e.offset is not None]
+        if len(self.entries) + len(affine) > batch.ADAM_SET_MAX:
+            raise ValueError(f"FakeQuantBatch(group_batch=True): {len(self.entries)} scales + {len(affine)} offsets are more than the "
+                             f"{batch.ADAM_SET_MAX} tensors one lq_adam_set steps in its single launch")
+        lib = _hip.load()
+        n = len(self.entries)
+        arr = (_hip.GroupDesc * n)()
+        for i, e in enumerate(self.entries):
+            R, C, axis, gs = e.desc
+            arr[i] = _hip.GroupDesc(e.param.data_ptr(), e.scale.data_ptr(), e.out.data_ptr(), e.dp.data_ptr(), e.ds.data_ptr(),
+                                    R, C, gs, axis, int(e.nested.q_range[0]), int(e.nested.q_range[1]))
+        handle = ctypes.c_void_p()
+        if affine:
+            # kb is the layer's factor (ops.fq_backward_group_affine: the offset's defaults to the scale's), fixed for the batch's life
+            offs = (_hip.GroupOffset * n)()
+            for i, e in enumerate(self.entries):
+                if e.offset is not None:
+                    offs[i] = _hip.GroupOffset(e.offset.data_ptr(), e.db.data_ptr(), float(e.nested.grad_scale_value(e.param.numel())))
+            _hip.check(lib.lq_group_batch_create_affine(arr, offs, n, ROUNDINGS.index(self.rounding), ctypes.byref(handle)),
+                       "lq_group_batch_create_affine")
+        else:
+            _hip.check(lib.lq_group_batch_create(arr, n, ROUNDINGS.index(self.rounding), ctypes.byref(handle)), "lq_group_batch_create")
+        self.group = handle
+        self.ws_bytes = lib.lq_group_batch_workspace_bytes(handle)
+        self.ws = torch.empty(max(1, self.ws_bytes), dtype=torch.uint8, device=self.device)
+        # the Adam step of the scales, then of the offsets (no lower bound): one launch over all of them (lq_adam_set_step; the
+        # gradients are the batch's ds and db buffers)
+        stepped = [(e.scale, e.m, e.v, e.ds) for e in self.entries] + [(e.offset, e.mb, e.vb, e.db) for e in affine]
+        na = len(stepped)
+        cnt = (ctypes.c_int64 * na)(*[w.numel() for w, _, _, _ in stepped])
+        mv = (ctypes.c_float * na)(*[float(c.min_value) if (c := getattr(w, "lq_constraint", None)) is not None else float("-inf")
+                                     for w, _, _, _ in stepped])
+        w = (ctypes.c_void_p * na)(*[t[0].data_ptr() for t in stepped])
+        m = (ctypes.c_void_p * na)(*[t[1].data_ptr() for t in stepped])
+        v = (ctypes.c_void_p * na)(*[t[2].data_ptr() for t in stepped])
+        adam = ctypes.c_void_p()
+        _hip.check(lib.lq_adam_set_create(w, m, v, cnt, mv, na, ctypes.byref(adam)), "lq_adam_set_create")
+        self.adam_set = adam
+        self.adam_grads = (ctypes.c_void_p * na)(*[t[3].data_ptr() for t in stepped])
+
+    def destroy(self):
+        self._destroy(self.group, "lq_group_batch_destroy")
+        self._destroy(self.adam_set, "lq_adam_set_destroy")
+        self.group = self.adam_set = None
+
+    def forward(self):
+        _hip.check(_hip.load().lq_group_batch_forward(self.group, _hip.stream_ptr(self.device)), "lq_group_batch_forward")
+
+    def backward(self, oihw: bool):
+        # ONE launch: dP of every tensor into the batch's buffers, the clip counts, and -- rule "ste" -- ds; mask only otherwise
+        _hip.check(_hip.load().lq_group_batch_backward(self.group, self.ptrs, self.grad_scales,
+                                                       _hip.ptr(self.ws) if self.ws_bytes else None, self.ws_bytes,
+                                                       _hip.stream_ptr(self.device)), "lq_group_batch_backward")
+
+    def clip_counts(self):
+        return self._counts(_hip.load().lq_group_batch_clip_counts, self.group, "lq_group_batch_clip_counts")
+
+    def adam_step(self, step: Optional[int] = None, step_dev: Optional[torch.Tensor] = None):
+        h = self.hyper
+        _hip.check(_hip.load().lq_adam_set_step(self.adam_set, self.adam_grads, h["lr"], h["betas"][0], h["betas"][1], h["eps"],
+                                                int(step or 0), _hip.ptr(step_dev), _hip.adam_mode(h["mode"]), _hip.stream_ptr(self.device)),
+                   "lq_adam_set_step")
 
 
 class FakeQuantBatch:
@@ -82,132 +394,40 @@ class FakeQuantBatch:
         self.layers = layers
         self.autograd = bool(autograd)
         self._external_grads = False
-        self._fused_opt = None               # BatchedScaleAdam(fused=True): the scale-gradient finalize applies the Adam step itself
         self.defer_scale_grads = False       # exact data-parallel mode: backward skips ds, scale_grads_from_param_grads() follows
         self.entries: List[_Entry] = []
         nested_layers = [getattr(layer, a) for layer in layers for a in ("nested_q_w_layer", "nested_q_k_layer", "nested_q_b_layer")
                          if hasattr(layer, a)]
-        self.clipped = bool(clipped)
-        self.group_batch = bool(group_batch)
-        self.asymmetric = bool(asymmetric)
-        self._ghandle = None
-        if self.asymmetric and self.clipped:
-            raise ValueError("asymmetric=True together with clipped=True: the clipped one-axis batch carries no offset per group; "
-                             "offsets travel in the group batch only (group_batch=True, asymmetric=True)")
-        if self.asymmetric and not self.group_batch:
-            raise ValueError("asymmetric=True belongs to group_batch=True: only the group batch carries an offset per group and its "
-                             "gradient")
-        if self.group_batch and self.clipped:
-            raise ValueError("group_batch=True together with clipped=True: a batch is either the group batch (group-wise layers and "
-                             "their biases) or the clipped batch (one-axis scales), not both")
-        if not self.asymmetric and any(getattr(n, "asymmetric", False) for n in nested_layers):
+        kind = self._set_kind(clipped, group_batch, asymmetric)
+        if not asymmetric and any(getattr(n, "asymmetric", False) for n in nested_layers):
             raise ValueError("FakeQuantBatch over an asymmetric layer: the offsets and their gradients travel only in the group "
                              "batch that was asked to carry them; opt in with FakeQuantBatch(..., group_batch=True, asymmetric=True), "
                              "or run such a model on the per-tensor path (batched=False)")
-        if not self.group_batch and any(getattr(n, "group_size", None) is not None for n in nested_layers):
+        if not group_batch and any(getattr(n, "group_size", None) is not None for n in nested_layers):
             raise ValueError("FakeQuantBatch over a group-wise layer (group_size): its scale has two non-unit axes, which the "
                              "(outer, G, inner) descriptor of the default and the clipped batch cannot express; run such a model on "
                              "the per-tensor path, or opt in to the group batch: FakeQuantBatch(..., group_batch=True)")
-        if self.group_batch:
-            self._init_group_batch(layers, nested_layers, lr, betas, eps, mode)
-            return
-        if not self.clipped and any(getattr(n, "q_range", None) is not None for n in nested_layers):
-            raise ValueError("FakeQuantBatch over a clipped layer (bits / q_range): the multi-tensor backward hands dy on as dP, "
-                             "but a clipped layer's dP is a masked copy of dy; run such a model on the per-tensor path (batched=False), "
-                             "or opt in to the clipped batch, which owns a dP buffer per tensor: FakeQuantBatch(..., clipped=True)")
-        rules = {n.scale_gradient for n in nested_layers}
-        if "ste" in rules and len(rules) > 1:
-            raise ValueError('one FakeQuantBatch holds one scale-gradient rule: every layer needs scale_gradient="ste", or none')
-        self.ste = "ste" in rules            # every scale gradient of the batch is the straight-through one
-        self.rounding = "floor"
-        if self.clipped:
-            if any(getattr(n, "q_range", None) is None for n in nested_layers):
-                raise ValueError("FakeQuantBatch(clipped=True) over a layer without a range: every quantised tensor of a clipped batch "
-                                 "needs bits / q_range (an unclipped model runs the default batch)")
-            roundings = {n.rounding for n in nested_layers}
-            if len(roundings) > 1:
-                raise ValueError(f"one clipped FakeQuantBatch holds one rounding, got {sorted(roundings)}")
-            self.rounding = next(iter(roundings), "floor")
-            if any(isinstance(layer, _ConvBase) and layer.kernel_storage == "hwio" for layer in layers):
-                raise ValueError('a clipped batch takes conv kernels in the memory order the convolution '
-                                 'consumes: build it with kernel_storage="oihw"')
-        for layer in layers:
-            if isinstance(layer, _ConvBase):
-                pairs = [(0, layer.kernel, layer.nested_q_k_layer)]
-                if layer._has_bias:
-                    pairs.append((1, layer.b, layer.nested_q_b_layer))
-            elif isinstance(layer, CustomDenseLayer):
-                pairs = [(0, layer.W, layer.nested_q_w_layer), (1, layer.b, layer.nested_q_b_layer)]
-            else:
-                raise TypeError(f"not a custom layer: {type(layer).__name__}")
-            for slot, param, nested in pairs:
-                e = _Entry()
-                e.layer, e.slot, e.param, e.nested = layer, slot, param, nested
-                e.scale = nested.scale             # the Parameter itself: nn.Module attribute lookup is the dearest step of a per-step loop
-                _hip.require_device_f32(param.data, "parameter")
-                _hip.require_device_f32(nested.scale.data, "scale")
-                # a dense permutation of the logical axes (conv kernels stored OIHW, layers.py kernel_storage) is described in
-                # memory order; outputs and gradients carry the parameter's strides
-                e.desc = memory_descriptor(tuple(param.shape), param.data.stride(), tuple(nested.scale.shape))
-                if e.desc is None:
-                    raise ValueError("parameters must be dense (contiguous, or a permutation of a contiguous array)")
-                e.out = torch.empty_like(param.data)
-                e.offset = e.db = e.mb = e.vb = None
-                e.nq = nested.penalty_threshold is not None or self.ste      # the op itself gives this scale a gradient
-                if self.ste and isinstance(layer, _ConvBase) and layer.kernel_storage == "hwio":
-                    raise ValueError('a batched scale_gradient="ste" model takes conv kernels in the memory order the convolution '
-                                     'consumes: build it with kernel_storage="oihw"')
-                # write straight into an existing gradient buffer (e.g. a DataParallel bucket view) when there is one
-                g = nested.scale.grad
-                if g is not None and g.is_contiguous():
-                    e.ds = g                       # external buffer (bucket view): zeroed by its owner, never set to None
-                    self._external_grads = True
-                else:
-                    e.ds = torch.zeros_like(nested.scale.data)
-                e.m = torch.zeros_like(nested.scale.data)
-                e.v = torch.zeros_like(nested.scale.data)
-                # conv kernels of nested-quantization layers: the forward launch also emits the OIHW tensor MIOpen consumes and
-                # the scale-gradient launch reads MIOpen's OIHW weight gradient, writing dP back in HWIO order (lq_hip.h:
-                # lq_fq_forward_oihw) -- no transposition launches around the convolutions
-                e.out_oihw = e.dp = e.conv = None
-                if (oihw and slot == 0 and isinstance(layer, _ConvBase) and nested.penalty_threshold is not None
-                        and param.data.is_contiguous()):          # HWIO-stored kernels only: an OIHW-stored one needs no companion
-                    kh, kw, ci, co = (int(d) for d in param.shape)
-                    e.conv = (kh * kw, ci, co)
-                    e.out_oihw = torch.empty((co, ci, kh, kw), dtype=torch.float32, device=param.device)
-                    e.dp = torch.empty_like(param.data)
-                    if (not hwio_out and param.data_ptr() % 16 == 0
-                            and _hip.load().lq_conv_tile_supported(kh * kw, ci, co, *e.desc) == 1):
-                        e.out = None               # the companion is the only forward output of this tensor
-                if self.clipped:
-                    e.dp = torch.empty_like(param.data)            # the masked dP (lq_batch_backward_clip), in the parameter's element order
-                self.entries.append(e)
-        if not self.entries:
-            raise ValueError("no custom layers")
+        kind.check(layers, nested_layers)
+        self.ste = kind.ste                  # every scale gradient of the batch is the straight-through one
+        self.rounding = kind.rounding
+        self._build_entries(layers, oihw, hwio_out)
         self.device = self.entries[0].param.device
-        lib = _hip.load()
         n = len(self.entries)
-        arr = (_hip.TensorDesc * n)()
-        for i, e in enumerate(self.entries):
-            lam = e.nested.penalty_threshold
-            c = getattr(e.nested.scale, "lq_constraint", None)
-            arr[i] = _hip.TensorDesc(e.param.data_ptr(), e.nested.scale.data_ptr(), None, _hip.ptr(e.out), e.ds.data_ptr(),
-                                     e.m.data_ptr(), e.v.data_ptr(), e.desc[0], e.desc[1], e.desc[2],
-                                     float("nan") if lam is None else float(lam),
-                                     float(c.min_value) if c is not None else float("-inf"),
-                                     _hip.ptr(e.out_oihw), _hip.ptr(e.dp), *(e.conv or (0, 0, 0)))
-        handle = ctypes.c_void_p()
-        _hip.check(lib.lq_batch_create(arr, n, ctypes.byref(handle)), "lq_batch_create")
-        self._handle = handle
-        if self.clipped:
-            qmin = (ctypes.c_int32 * n)(*[int(e.nested.q_range[0]) for e in self.entries])
-            qmax = (ctypes.c_int32 * n)(*[int(e.nested.q_range[1]) for e in self.entries])
-            _hip.check(lib.lq_batch_set_clip(handle, qmin, qmax, n, ROUNDINGS.index(self.rounding)), "lq_batch_set_clip")
         self._ptrs = (ctypes.c_void_p * n)()
         self._grad_scales = (ctypes.c_float * n)(*[e.nested.grad_scale_value(e.param.numel()) for e in self.entries]) if self.ste else None
-        self.ws = torch.empty(lib.lq_batch_workspace_bytes(handle), dtype=torch.uint8, device=self.device)
         self.hyper = dict(lr=lr, betas=betas, eps=eps, mode=mode)
+        # what the backward publishes and the optimizer steps, as (parameter, gradient buffer, the op gives it a gradient): the
+        # scales, then the offsets of asymmetric entries
+        self._stepped = ([(e.scale, e.ds, e.nq) for e in self.entries]
+                         + [(e.offset, e.db, e.nq) for e in self.entries if e.offset is not None])
+        kind.create(self)
+        self._handle = kind.handle
+        self.ws = kind.ws
+        self._forward_call = kind.forward
+        self._scale_grad_call = kind.backward
+        self.scale_adam_step = kind.adam_step
         self._data_ptrs = [(e.param.data_ptr(), e.nested.scale.data_ptr()) for e in self.entries]
+        self._offset_ptrs = [(e, e.offset.data_ptr()) for e in self.entries if e.offset is not None]
         # per-step host work is kept to list lookups: the flat (param, scale, ...) argument list of the autograd node and,
         # per layer, which outputs are its kernel and its bias
         self._flat = [t for e in self.entries for t in (e.param, e.nested.scale)]
@@ -230,163 +450,67 @@ class FakeQuantBatch:
                 self._static_pre = [(layer.__dict__, (None if ik is None else self._leaf[ik], None if ib is None else self._leaf[ib], None))
                                     for layer, ik, ib in self._layer_slots]
 
-    def _init_group_batch(self, layers, nested_layers, lr, betas, eps, mode):
-        """The group batch: entries, buffers and the ``lq_group_batch`` handle (one descriptor per kernel and bias)."""
-        if any(getattr(n, "q_range", None) is None for n in nested_layers):
-            raise ValueError("FakeQuantBatch(group_batch=True) over a layer without a range: group-wise scales exist for the clipped "
-                             "quantizer only, every quantised tensor needs bits / q_range")
-        rules = {n.scale_gradient for n in nested_layers}
-        if len(rules) > 1:
-            raise ValueError(f"one FakeQuantBatch holds one scale-gradient rule, got {sorted(map(str, rules))}")
-        self.ste = "ste" in rules
-        roundings = {n.rounding for n in nested_layers}
-        if len(roundings) > 1:
-            raise ValueError(f"one group FakeQuantBatch holds one rounding, got {sorted(roundings)}")
-        self.rounding = next(iter(roundings), "floor")
-        if any(n.penalty_threshold is not None or n.penalty_rate is not None for n in nested_layers):
-            raise ValueError("FakeQuantBatch(group_batch=True) with a loss term / penalty_threshold: the penalty kernels broadcast "
-                             "one-axis scales; group-wise scales have no loss term")
-        if any(isinstance(layer, _ConvBase) and layer.kernel_storage == "hwio" for layer in layers):
-            raise ValueError('FakeQuantBatch(group_batch=True) with kernel_storage="hwio": the groups are defined in the memory order '
-                             'the convolution consumes; build the model with kernel_storage="oihw"')
+    def _set_kind(self, clipped: bool, group_batch: bool, asymmetric: bool):
+        """The three opt-ins as read-only facts and the kind they resolve to -- the only place that reads them.  No device call."""
+        self.clipped = bool(clipped)
+        self.group_batch = bool(group_batch)
+        self.asymmetric = bool(asymmetric)
+        if asymmetric and clipped:
+            raise ValueError("asymmetric=True together with clipped=True: the clipped one-axis batch carries no offset per group; "
+                             "offsets travel in the group batch only (group_batch=True, asymmetric=True)")
+        if asymmetric and not group_batch:
+            raise ValueError("asymmetric=True belongs to group_batch=True: only the group batch carries an offset per group and its "
+                             "gradient")
+        if group_batch and clipped:
+            raise ValueError("group_batch=True together with clipped=True: a batch is either the group batch (group-wise layers and "
+                             "their biases) or the clipped batch (one-axis scales), not both")
+        self._kind = _GroupKind() if group_batch else _ClippedKind() if clipped else _DefaultKind()
+        return self._kind
+
+    def _grad_buffer(self, t):
+        """The gradient buffer of a learned tensor (scale or offset): an existing contiguous ``.grad`` (e.g. a DataParallel bucket
+        view) is written straight into; otherwise zeros of the batch's own."""
+        g = t.grad
+        if g is not None and g.is_contiguous():
+            self._external_grads = True          # external buffer (bucket view): zeroed by its owner, never set to None
+            return g
+        return torch.zeros_like(t.data)
+
+    def _build_entries(self, layers, oihw: bool, hwio_out: bool):
+        """One entry per kernel / ``W`` (slot 0) and bias (slot 1) of every layer, for every kind."""
+        kind = self._kind
         found = []
         for layer in layers:
-            if isinstance(layer, _ConvBase):
-                pairs = [(0, layer.kernel, layer.nested_q_k_layer)]
-                if layer._has_bias:
-                    pairs.append((1, layer.b, layer.nested_q_b_layer))
-            elif isinstance(layer, CustomDenseLayer):
-                pairs = [(0, layer.W, layer.nested_q_w_layer), (1, layer.b, layer.nested_q_b_layer)]
-            else:
+            if not isinstance(layer, _HostLayer):
                 raise TypeError(f"not a custom layer: {type(layer).__name__}")
-            for slot, param, nested in pairs:
-                # geometry first: a tensor the group batch cannot describe is refused before anything touches the device
-                if nested.group_size is not None:
-                    R, C, axis = group_geometry(tuple(param.shape), param.data.stride(), tuple(nested.scale.shape), nested.group_size)
-                    desc = (R, C, axis, int(nested.group_size))
-                elif param.dim() == 1 and param.data.is_contiguous() and nested.scale.numel() == 1:
-                    desc = (1, param.numel(), 1, param.numel())        # a bias with its scalar scale: one line, one group
-                else:
-                    raise ValueError(f"FakeQuantBatch(group_batch=True): a parameter of shape {tuple(param.shape)} with a one-axis scale "
-                                     f"of shape {tuple(nested.scale.shape)} is neither group-wise nor a 1-D parameter with a scalar "
-                                     "scale; one-axis orientations belong to the clipped batch (clipped=True)")
-                found.append((layer, slot, param, nested, desc))
+            for slot, (_, nested, param) in enumerate(layer.scale_pairs()):
+                # geometry first: a tensor the kind cannot describe is refused before anything touches the device
+                found.append((layer, slot, param, nested, kind.describe(layer, param, nested)))
         for layer, slot, param, nested, desc in found:
             e = _Entry()
             e.layer, e.slot, e.param, e.nested, e.desc = layer, slot, param, nested, desc
-            e.scale = nested.scale
+            e.scale = nested.scale             # the Parameter itself: nn.Module attribute lookup is the dearest step of a per-step loop
             _hip.require_device_f32(param.data, "parameter")
             _hip.require_device_f32(nested.scale.data, "scale")
             e.out = torch.empty_like(param.data)
-            e.dp = torch.empty_like(param.data)                    # the masked dP, in the parameter's element order
-            e.nq = self.ste
-            g = nested.scale.grad
-            if g is not None and g.is_contiguous():
-                e.ds = g                                           # external buffer (bucket view)
-                self._external_grads = True
-            else:
-                e.ds = torch.zeros_like(nested.scale.data)
+            e.nq = nested.penalty_threshold is not None or self.ste      # the op itself gives this scale a gradient
+            e.ds = self._grad_buffer(nested.scale)
             e.m = torch.zeros_like(nested.scale.data)
             e.v = torch.zeros_like(nested.scale.data)
-            e.out_oihw = e.conv = None
+            e.out_oihw = e.dp = e.conv = None
             e.offset = e.db = e.mb = e.vb = None
-            if getattr(nested, "asymmetric", False):               # only where the batch was asked to carry offsets (__init__)
-                e.offset = nested.offset
-                _hip.require_device_f32(e.offset.data, "offset")
-                g = e.offset.grad
-                if g is not None and g.is_contiguous():
-                    e.db = g                                       # external buffer (bucket view), as ds
-                    self._external_grads = True
-                else:
-                    e.db = torch.zeros_like(e.offset.data)
-                e.mb = torch.zeros_like(e.offset.data)
-                e.vb = torch.zeros_like(e.offset.data)
+            kind.own(self, e, oihw, hwio_out)
             self.entries.append(e)
         if not self.entries:
             raise ValueError("no custom layers")
-        affine = [e for e in self.entries if e.offset is not None]
-        if len(self.entries) + len(affine) > self.ADAM_SET_MAX:
-            raise ValueError(f"FakeQuantBatch(group_batch=True): {len(self.entries)} scales + {len(affine)} offsets are more than the "
-                             f"{self.ADAM_SET_MAX} tensors one lq_adam_set steps in its single launch")
-        self.device = self.entries[0].param.device
-        lib = _hip.load()
-        n = len(self.entries)
-        arr = (_hip.GroupDesc * n)()
-        for i, e in enumerate(self.entries):
-            R, C, axis, gs = e.desc
-            arr[i] = _hip.GroupDesc(e.param.data_ptr(), e.scale.data_ptr(), e.out.data_ptr(), e.dp.data_ptr(), e.ds.data_ptr(),
-                                    R, C, gs, axis, int(e.nested.q_range[0]), int(e.nested.q_range[1]))
-        handle = ctypes.c_void_p()
-        if affine:
-            # kb is the layer's factor (ops.fq_backward_group_affine: the offset's defaults to the scale's), fixed for the batch's life
-            offs = (_hip.GroupOffset * n)()
-            for i, e in enumerate(self.entries):
-                if e.offset is not None:
-                    offs[i] = _hip.GroupOffset(e.offset.data_ptr(), e.db.data_ptr(), float(e.nested.grad_scale_value(e.param.numel())))
-            _hip.check(lib.lq_group_batch_create_affine(arr, offs, n, ROUNDINGS.index(self.rounding), ctypes.byref(handle)),
-                       "lq_group_batch_create_affine")
-        else:
-            _hip.check(lib.lq_group_batch_create(arr, n, ROUNDINGS.index(self.rounding), ctypes.byref(handle)), "lq_group_batch_create")
-        self._ghandle = handle
-        self._handle = None
-        self._ptrs = (ctypes.c_void_p * n)()
-        self._grad_scales = (ctypes.c_float * n)(*[e.nested.grad_scale_value(e.param.numel()) for e in self.entries]) if self.ste else None
-        self.ws = torch.empty(max(1, lib.lq_group_batch_workspace_bytes(handle)), dtype=torch.uint8, device=self.device)
-        self._ws_bytes = lib.lq_group_batch_workspace_bytes(handle)
-        self.hyper = dict(lr=lr, betas=betas, eps=eps, mode=mode)
-        self._data_ptrs = [(e.param.data_ptr(), e.nested.scale.data_ptr()) for e in self.entries]
-        self._offset_ptrs = [(e, e.offset.data_ptr()) for e in affine]
-        self._flat = [t for e in self.entries for t in (e.param, e.nested.scale)]
-        slots = {}
-        for i, e in enumerate(self.entries):
-            slots.setdefault(id(e.layer), [e.layer, None, None])[1 + e.slot] = i
-        self._layer_slots = list(slots.values())
-        self._oihw_idx, self._oihw_pos = [], {}
-        # the Adam step of the scales, then of the offsets (no lower bound): one launch over all of them (lq_adam_set_step; the
-        # gradients are the batch's ds and db buffers)
-        stepped = [(e.scale, e.m, e.v, e.ds) for e in self.entries] + [(e.offset, e.mb, e.vb, e.db) for e in affine]
-        na = len(stepped)
-        cnt = (ctypes.c_int64 * na)(*[w.numel() for w, _, _, _ in stepped])
-        mv = (ctypes.c_float * na)(*[float(c.min_value) if (c := getattr(w, "lq_constraint", None)) is not None else float("-inf")
-                                     for w, _, _, _ in stepped])
-        w = (ctypes.c_void_p * na)(*[t[0].data_ptr() for t in stepped])
-        m = (ctypes.c_void_p * na)(*[t[1].data_ptr() for t in stepped])
-        v = (ctypes.c_void_p * na)(*[t[2].data_ptr() for t in stepped])
-        adam = ctypes.c_void_p()
-        _hip.check(lib.lq_adam_set_create(w, m, v, cnt, mv, na, ctypes.byref(adam)), "lq_adam_set_create")
-        self._adam_set = adam
-        self._adam_grads = (ctypes.c_void_p * na)(*[t[3].data_ptr() for t in stepped])
-        if not self.autograd:
-            self._leaf = [e.out.detach().requires_grad_(True) for e in self.entries]
-            self._leaf_o = [None] * n
-            self._all_leaves = list(self._leaf)
-            self._static_outs = list(self._leaf)
-            self._static_pre = [(layer.__dict__, (None if ik is None else self._leaf[ik], None if ib is None else self._leaf[ib], None))
-                                for layer, ik, ib in self._layer_slots]
 
     #: tensors one lq_adam_set steps in its single launch (scales + offsets of a group batch)
     ADAM_SET_MAX = 256
 
-    def _refuse_group(self, what: str):
-        if self.group_batch:
-            raise ValueError(f"{what} is not available on FakeQuantBatch(group_batch=True): group-wise scales have no loss term and "
-                             "their dP is a masked copy of dy (no exact data-parallel mode B)")
-
     def __del__(self):
-        for name, destroy in (("_ghandle", "lq_group_batch_destroy"), ("_adam_set", "lq_adam_set_destroy")):
-            h = getattr(self, name, None)
-            if h:
-                try:
-                    getattr(_hip.load(), destroy)(h)
-                except Exception:
-                    pass
-                setattr(self, name, None)
-        h = getattr(self, "_handle", None)
-        if h:
-            try:
-                _hip.load().lq_batch_destroy(h)
-            except Exception:
-                pass
+        kind = getattr(self, "_kind", None)      # absent where the constructor raised before the kind was resolved
+        if kind is not None:
+            kind.destroy()
             self._handle = None
 
     def _check_pointers(self):
@@ -394,7 +518,7 @@ class FakeQuantBatch:
             if e.param.data_ptr() != pp or e.nested.scale.data_ptr() != sp:      # the module's scale: a replaced Parameter is caught too
                 raise RuntimeError("a parameter or scale was re-allocated after the batch was built "
                                    "(e.g. model.to(device)); rebuild the FakeQuantBatch")
-        for e, bp in getattr(self, "_offset_ptrs", ()):
+        for e, bp in self._offset_ptrs:
             if e.nested.offset.data_ptr() != bp:
                 raise RuntimeError("an offset was re-allocated after the batch was built (e.g. model.to(device)); rebuild the "
                                    "FakeQuantBatch")
@@ -412,15 +536,6 @@ class FakeQuantBatch:
             layer.__dict__["_q_pre"] = (None if ik is None else outs[ik], None if ib is None else outs[ib],
                                         outs[self._oihw_pos[ik]] if ik in self._oihw_pos else None)
         return outs[:n]
-
-    def _forward_call(self):
-        lib = _hip.load()
-        if self.group_batch:
-            _hip.check(lib.lq_group_batch_forward(self._ghandle, _hip.stream_ptr(self.device)), "lq_group_batch_forward")
-        elif self.clipped:
-            _hip.check(lib.lq_batch_forward_clip(self._handle, _hip.stream_ptr(self.device)), "lq_batch_forward_clip")
-        else:
-            _hip.check(lib.lq_batch_forward(self._handle, _hip.stream_ptr(self.device)), "lq_batch_forward")
 
     def _quantize_all_leaves(self):
         self._forward_call()
@@ -463,43 +578,6 @@ class FakeQuantBatch:
         if add_to:
             torch._foreach_add_(add_to, add_from)          # one fused launch for all of them
 
-    def _scale_grad_call(self, oihw: bool):
-        """lq_batch_scale_grad(_oihw), or -- a fused optimizer attached -- lq_batch_scale_grad_step: same launches, the finalize
-        also applies the scales' Adam step."""
-        lib = _hip.load()
-        opt = self._fused_opt
-        sp = _hip.stream_ptr(self.device)
-        if self.group_batch:
-            # ONE launch: dP of every tensor into the batch's buffers, the clip counts, and -- rule "ste" -- ds; mask only otherwise
-            _hip.check(lib.lq_group_batch_backward(self._ghandle, self._ptrs, self._grad_scales,
-                                                   _hip.ptr(self.ws) if self._ws_bytes else None, self._ws_bytes, sp),
-                       "lq_group_batch_backward")
-            return
-        if self.clipped:
-            # dP of every tensor into the batch's buffers, the clip counts, and -- rule "ste" -- ds; mask only: no grad_scale, ds untouched
-            _hip.check(lib.lq_batch_backward_clip(self._handle, self._ptrs, self._grad_scales, _hip.ptr(self.ws), self.ws.numel(), sp),
-                       "lq_batch_backward_clip")
-            return
-        if self.ste:
-            _hip.check(lib.lq_batch_scale_grad_ste(self._handle, self._ptrs, self._grad_scales, _hip.ptr(self.ws), self.ws.numel(), sp),
-                       "lq_batch_scale_grad_ste")
-            return
-        if opt is None:
-            fn = lib.lq_batch_scale_grad_oihw if oihw else lib.lq_batch_scale_grad
-            _hip.check(fn(self._handle, self._ptrs, _hip.ptr(self.ws), self.ws.numel(), sp), "lq_batch_scale_grad")
-            return
-        if opt._applied:
-            # the finalize of a scale-gradient pass applies Adam: a second pass before step() (gradient accumulation, a retried
-            # backward) would update the scales twice and the weights once
-            raise RuntimeError("FakeQuantBatch: the fused scale update of this step has already been applied; call the optimizer's "
-                               "step() first, or build BatchedScaleAdam(fused=False) (fused=True excludes gradient accumulation)")
-        step, step_dev = opt._advance()
-        h = self.hyper
-        _hip.check(lib.lq_batch_scale_grad_step(self._handle, self._ptrs, 1 if oihw else 0, _hip.ptr(self.ws), self.ws.numel(),
-                                                h["lr"], h["betas"][0], h["betas"][1], h["eps"], int(step or 0), _hip.ptr(step_dev),
-                                                _hip.adam_mode(h["mode"]), sp), "lq_batch_scale_grad_step")
-        opt._applied = True
-
     # ------------------------------------------------------------------ backward of every tensor (both modes)
     def _point_at(self, grads, name: str = "dy", as_it_stands=(), zeros: bool = True):
         """The one writer of the pointer table the scale-gradient launches read ``dy`` from.  ``grads[i]`` is the upstream
@@ -531,20 +609,18 @@ class FakeQuantBatch:
         a gradient.  Returns ``dP`` per tensor: the batch's own buffers where the launch writes one (a clipped batch: the masked
         copies of dy; ``gathered`` companions: dy in HWIO order), the kept dy itself otherwise (custom_layers.py:118)."""
         if refuse_accumulation and not self._external_grads:
-            for e in self.entries:
-                if e.nq and (e.scale.grad is not None or (e.offset is not None and e.offset.grad is not None)):
+            for p, _, nq in self._stepped:
+                if nq and p.grad is not None:
                     # the kernel OVERWRITES its gradient buffer: a second backward without zero_grad(set_to_none=True)
                     # would silently drop the first gradient -- refuse instead (before anything is launched)
                     raise RuntimeError("FakeQuantBatch: scale (and offset) gradients must be None before backward "
                                        "(gradient accumulation over several backward passes is not supported in batched mode)")
         self._scale_grad_call(oihw)
-        for e in self.entries:
-            if e.nq:
-                e.scale.grad = e.ds                        # written in place by the kernel: no accumulate launch
-                if e.offset is not None:
-                    e.offset.grad = e.db                   # and so is the offset's, by the same launch
+        for p, g, nq in self._stepped:
+            if nq:
+                p.grad = g                                 # written in place by the kernel: no accumulate launch (an offset's by the same launch)
             # STE-only: zeros_like(scale) (CL custom_layers.py:62) -- no scale gradient from the op
-        if self.clipped or self.group_batch:
+        if self._kind.owns_dp:
             return [e.dp for e in self.entries]
         if gathered:
             return [e.dp if i in gathered else d for i, (e, d) in enumerate(zip(self.entries, keep))]
@@ -553,7 +629,8 @@ class FakeQuantBatch:
     def _backward_core(self, dys):
         """``dys``: upstream gradient of every HWIO-shaped output, then of every OIHW companion (``None`` where nothing consumed
         it).  Launches the scale-gradient pass (unless deferred), sets ``scale.grad`` and returns ``dP`` per tensor."""
-        self._refuse_deferred_clip()
+        if self.defer_scale_grads and not self._kind.defers:
+            self._kind.refuse("defer_scale_grads")
         dys = list(dys)
         # a conv kernel with an OIHW companion: its consumer (the convolution) used the companion, so the gradient arrives there,
         # in OIHW order; a consumer that used the HWIO output instead is served like every other tensor
@@ -576,40 +653,18 @@ class FakeQuantBatch:
             raise RuntimeError("FakeQuantBatch: conv kernels must all be consumed through the same layout in one step")
         return self._launch_and_publish(self._point_at(dys, as_it_stands=gathered), bool(gathered), gathered)
 
-    def _refuse_deferred_clip(self):
-        if self.group_batch and self.defer_scale_grads:
-            self._refuse_group("defer_scale_grads")
-        if self.clipped and self.defer_scale_grads:
-            raise ValueError("a clipped FakeQuantBatch cannot defer its scale gradients (data-parallel mode B): the exchanged dP is a "
-                             "masked copy of dy and no longer holds the dy of the clipped elements; use mode A")
-
     def clip_counts(self):
         """Clipped batch: per entry, the number of elements the latest backward found outside the range, per group (int32, in
         the shape of the entry's scale; exact).  Copies of the library's device buffers: no synchronisation."""
-        if not (self.clipped or self.group_batch):
-            raise RuntimeError("clip_counts() belongs to FakeQuantBatch(clipped=True) and FakeQuantBatch(group_batch=True)")
-        lib = _hip.load()
-        out = []
-        for i, e in enumerate(self.entries):
-            dev, groups = ctypes.c_void_p(), ctypes.c_int64()
-            if self.group_batch:
-                _hip.check(lib.lq_group_batch_clip_counts(self._ghandle, i, ctypes.byref(dev), ctypes.byref(groups)),
-                           "lq_group_batch_clip_counts")
-            else:
-                _hip.check(lib.lq_batch_clip_counts(self._handle, i, ctypes.byref(dev), ctypes.byref(groups)), "lq_batch_clip_counts")
-            view = torch.as_tensor(_DeviceInts(dev.value, groups.value), device=self.device)
-            out.append(view.clone().reshape(e.scale.shape))
-        return out
+        return self._kind.clip_counts()
 
     # ------------------------------------------------------------------ exact data-parallel mode (ddp.py, mode B)
     def scale_grads_from_param_grads(self):
         """ds of every nested-quantization tensor from its parameter's CURRENT gradient, in two launches.  After the
         data-parallel all-reduce ``P.grad`` is the global-batch dy (dP == dy, custom_layers.py:118), so this yields the
         single-device large-batch scale gradient, identical on every rank."""
-        self._refuse_group("scale_grads_from_param_grads()")
-        if self.clipped:
-            raise ValueError("scale_grads_from_param_grads() reads P.grad as dy; a clipped batch's dP is a masked copy of dy, which "
-                             "no longer holds the dy of the clipped elements: average ds over the ranks (data-parallel mode A)")
+        if not self._kind.defers:
+            self._kind.refuse("scale_grads_from_param_grads()")
         if self.ste:
             raise RuntimeError("scale_grads_from_param_grads() is the exact mode of the nested-quantization vote; the straight-through "
                                "scale gradient is linear in dy: average ds over the ranks (data-parallel mode A)")
@@ -641,7 +696,8 @@ class FakeQuantBatch:
         ``compute_{maxbin,difference,inverse}_penalty`` (custom_loss_functions.py:75-116, 161-195, 240-275) for the current
         parameters and scales, without a backward pass (lq_batch_penalty_values).  Both are persistent device tensors that
         the next call rewrites in place."""
-        self._refuse_group("penalty_values()")
+        if not self._kind.loss_terms:
+            self._kind.refuse("penalty_values()")
         self._check_pointers()
         dims, start, terms, penalty = self._value_buffers()
         _hip.check(_hip.load().lq_batch_penalty_values(self._handle, self._KINDS[kind], dims, start, terms.data_ptr(), penalty.data_ptr(),
@@ -660,7 +716,8 @@ class FakeQuantBatch:
         ``values``: also evaluate the penalty (lq_batch_penalty_grads_values: the same gradient launches, then the value
         launches) and return it as a 0-dim device tensor -- a persistent buffer, rewritten in place by every call; the
         per-tensor terms are in ``self._values[2]``.  Default: returns ``None`` and issues the gradient launches only."""
-        self._refuse_group("inject_penalty_grads()")
+        if not self._kind.loss_terms:
+            self._kind.refuse("inject_penalty_grads()")
         lib = _hip.load()
         n = len(self.entries)
         normalizer = float(sum(e.param.numel() for e in self.entries))
@@ -687,19 +744,6 @@ class FakeQuantBatch:
         for e in self.entries:
             e.scale.grad = e.ds
         return penalty
-
-    # ------------------------------------------------------------------ optimizer
-    def scale_adam_step(self, step: Optional[int] = None, step_dev: Optional[torch.Tensor] = None):
-        lib = _hip.load()
-        h = self.hyper
-        if self.group_batch:
-            _hip.check(lib.lq_adam_set_step(self._adam_set, self._adam_grads, h["lr"], h["betas"][0], h["betas"][1], h["eps"],
-                                            int(step or 0), _hip.ptr(step_dev), _hip.adam_mode(h["mode"]), _hip.stream_ptr(self.device)),
-                       "lq_adam_set_step")
-            return
-        _hip.check(lib.lq_batch_scale_adam(self._handle, h["lr"], h["betas"][0], h["betas"][1], h["eps"],
-                                           int(step or 0), _hip.ptr(step_dev), _hip.adam_mode(h["mode"]), _hip.stream_ptr(self.device)),
-                   "lq_batch_scale_adam")
 
 
 class _BatchFn(torch.autograd.Function):
@@ -736,13 +780,9 @@ class BatchedScaleAdam:
         self.capturable = capturable
         self._applied = False
         if fused:
-            if batch.group_batch:
+            if not batch._kind.fuses:
                 raise ValueError("the fused finalize + Adam launch exists for the nested-quantization vote only: "
-                                 "build BatchedScaleAdam(fused=False) for a group batch (with or without asymmetric=True: "
-                                 "the offsets step with the scales in the Adam set's one launch)")
-            if batch.clipped:
-                raise ValueError("the fused finalize + Adam launch exists for the nested-quantization vote only: "
-                                 "build BatchedScaleAdam(fused=False) for a clipped batch")
+                                 f"build BatchedScaleAdam(fused=False) for {batch._kind.name}")
             if batch.ste:
                 raise ValueError("the fused finalize + Adam launch exists for the nested-quantization vote only: "
                                  'build BatchedScaleAdam(fused=False) for a scale_gradient="ste" model')
@@ -751,17 +791,14 @@ class BatchedScaleAdam:
                                  "from the batch's own scale-gradient pass)")
             if batch._external_grads:
                 raise ValueError("a fused scale update cannot be combined with gradient buffers that are exchanged (bucket views)")
-            batch._fused_opt = self
+            batch._kind.fused_opt = self
         self._step = 0
         self._step_t = torch.zeros(1, dtype=torch.int64, device=batch.device) if capturable else None
-        self.param_groups = [{"params": [e.nested.scale for e in batch.entries]
-                              + [e.offset for e in batch.entries if e.offset is not None]}]
+        self.param_groups = [{"params": [p for p, _, _ in batch._stepped]}]
 
     def zero_grad(self, set_to_none: bool = True):
-        for e in self.batch.entries:
-            e.scale.grad = None
-            if e.offset is not None:
-                e.offset.grad = None
+        for p, _, _ in self.batch._stepped:
+            p.grad = None
 
     def _advance(self):
         """(host step, device step tensor) of the update that is about to be applied."""
@@ -773,24 +810,18 @@ class BatchedScaleAdam:
 
     @torch.no_grad()
     def step(self):
-        if self.batch._fused_opt is self:
+        if self.batch._kind.fused_opt is self:
             if not self._applied:
                 raise RuntimeError("BatchedScaleAdam(fused=True).step() without a backward pass of the batch since the last step")
             self._applied = False            # the finalize of this step's scale-gradient pass has already updated the scales
             return
         # only scales that actually received a gradient this step are updated by Adam in the reference too; with the
         # nested-quantization op every scale does.  STE-only scales are updated from the loss-term gradients.
-        for e in self.batch.entries:
-            g = e.scale.grad
+        for p, buf, _ in self.batch._stepped:                      # an asymmetric group batch: the offsets step in the same launch
+            g = p.grad
             if g is None:
-                e.ds.zero_()
-            elif g.data_ptr() != e.ds.data_ptr():
-                e.ds.copy_(g)                                      # loss-term gradients arrive in autograd-owned tensors
-            if e.offset is not None:                               # an asymmetric group batch: the offsets step in the same launch
-                g = e.offset.grad
-                if g is None:
-                    e.db.zero_()
-                elif g.data_ptr() != e.db.data_ptr():
-                    e.db.copy_(g)
+                buf.zero_()
+            elif g.data_ptr() != buf.data_ptr():
+                buf.copy_(g)                                       # loss-term gradients arrive in autograd-owned tensors
         step, step_dev = self._advance()
         self.batch.scale_adam_step(step=step, step_dev=step_dev)

@@ -285,8 +285,8 @@ class DataParallel:
             # FakeQuantBatch(autograd=False) hands dP to its parameters in finish_backward(), after loss.backward() has returned: a
             # sub-bucket that holds one of them must not be exchanged from a hook -- a regularised kernel's hook fires for the
             # regulariser's gradient alone -- but by exchange(), which the step calls after finish_backward()
-            managed = {id(e.param) for e in batch.entries} | {id(e.nested.scale) for e in batch.entries}
-            managed |= {id(e.offset) for e in batch.entries if e.offset is not None}      # an asymmetric group batch writes db too
+            # (the scales, and the offsets of an asymmetric group batch, which writes db too: batch._stepped)
+            managed = {id(e.param) for e in batch.entries} | {id(p) for p, _, _ in batch._stepped}
             self._hold = {self._param_bucket[i] for i, p in enumerate(self.bucket.params) if id(p) in managed}
 
     def no_sync(self):

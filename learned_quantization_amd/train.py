@@ -215,8 +215,9 @@ class Trainer:
                                         group_batch=self.group_batch, asymmetric=self.asymmetric_batch)
             # nothing touches ds between its computation and the scales' update when there is no loss term and ds is not
             # exchanged (one process, or exact mode B): the finalize then applies the Adam step itself (one launch fewer)
-            # (the fused finalize + Adam is the nested-quantization pass's: not for the straight-through modes)
-            fused = self.loss_obj is None and (self.dp is None or ddp_mode == "B") and not ste and not self.clipped_batch and not self.group_batch
+            # (the fused finalize + Adam is the nested-quantization pass's: not for the straight-through modes, nor for a kind of
+            # batch that cannot fuse)
+            fused = self.loss_obj is None and (self.dp is None or ddp_mode == "B") and not ste and self.batch._kind.fuses
             self.scale_opt = BatchedScaleAdam(self.batch, capturable=graph, fused=fused)
             if self.dp is not None:
                 self.dp.attach_batch(self.batch)

@@ -153,7 +153,8 @@ def test_batch_refusals_with_the_opt_in():
 def test_what_a_built_asymmetric_batch_refuses():
     """Mode B, the loss term and the fused Adam step on an object that skipped the device-side construction."""
     b = FakeQuantBatch.__new__(FakeQuantBatch)
-    b.group_batch, b.asymmetric, b.clipped, b.ste, b.defer_scale_grads, b.entries = True, True, False, True, True, []
+    b._set_kind(clipped=False, group_batch=True, asymmetric=True)
+    b.ste, b.defer_scale_grads, b.entries = True, True, []
     with pytest.raises(ValueError, match="mode B"):
         b._backward_core([])                                            # defer_scale_grads is set
     with pytest.raises(ValueError, match="mode B"):

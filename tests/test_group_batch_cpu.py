@@ -123,7 +123,8 @@ def test_group_batch_refusals():
 def test_what_a_built_group_batch_refuses():
     """The refusals of an existing batch, on an object that skipped the device-side construction."""
     b = FakeQuantBatch.__new__(FakeQuantBatch)
-    b.group_batch, b.clipped, b.ste, b.defer_scale_grads, b.entries = True, False, True, True, []
+    b._set_kind(clipped=False, group_batch=True, asymmetric=False)
+    b.ste, b.defer_scale_grads, b.entries = True, True, []
     with pytest.raises(ValueError, match="group_batch=True"):
         b.scale_grads_from_param_grads()
     with pytest.raises(ValueError, match="group_batch=True"):

@@ -263,6 +263,40 @@ int lq_fq_backward_group_affine(const float* P, const float* s, const float* b, 
 int lq_scale_init_group_minmax(const float* P, float* s, float* b, int32_t qmin, int32_t qmax, int rounding, float min_value,
                                int64_t R, int64_t C, int axis, int64_t gs, void* stream);
 
+/* ---- quantization statistics of the clipped pair: per group and per tensor, read only ----
+ * What the quantizer does to P under the scales (and offsets) it has NOW: how much each group loses on either side of the range,
+ * the squared error and the squared signal of each group, and the histogram of the codes of the tensor.
+ * Geometry is exactly lq_fq_forward_group's: matrix [R][C] in memory order, axis, gs clamped to the line length, nb = ceil(len / gs),
+ * ragged last group; s (and b) are [nb][C] or [R][nb].  A bias with a scalar scale is R = 1, C = numel, axis = 1, gs = numel.
+ * b == NULL: the symmetric pair; otherwise the offset of the asymmetric pair, the scale's shape.  lo = (float)qmin, hi = (float)qmax.
+ * Per element, in fp32, every operation rounding on its own (the library is built without contraction):
+ *   u  = P - b                      (with an offset only; otherwise u is P)
+ *   t  = u / s                      (IEEE division: the forward's quotient bit for bit)
+ *   q0 = floorf(t) | rintf(t)       by `rounding`
+ *   q  = q0 < lo ? lo : (q0 > hi ? hi : q0)
+ *   out = q * s                     (with an offset: (q * s) + b, product and sum round separately)
+ * Per group g, in the scale's shape:
+ *   below[g] = #{ i in g : q0_i < lo }        exact, uint32
+ *   above[g] = #{ i in g : q0_i > hi }        exact, uint32      (below + above is lq_fq_backward_group's clipped)
+ *   err2[g]  = sum_{i in g} e_i * e_i  with e_i = (double)P_i - (double)out_i;  the product and the addition round separately
+ *   sig2[g]  = sum_{i in g} (double)P_i * (double)P_i
+ * The group's SQNR is 10 log10 of sig2 / err2.  The sums are f64 from the first addition and taken in one fixed order (no float
+ * atomics, no workspace): two runs give the same bits.  All four are written for every group.
+ * Per tensor, when hist != NULL: hist[q - qmin] += 1 for every element whose q is a number; qmax - qmin + 1 uint32 bins that the
+ * caller has zeroed (counts are ADDED, as by lq_q_histogram).  The bins are summed with integer atomics, which are exact in
+ * any order.  hist != NULL needs qmax - qmin + 1 <= 4096, otherwise LQ_EINVAL.
+ * Non-finite values: a NaN q0 counts on neither side and is not binned, and its group's err2 is NaN by IEEE arithmetic; +-Inf t
+ * counts on its side and q saturates at the bound.  Other groups are unaffected.
+ * A NULL P, s, below, above, err2 or sig2, qmin > qmax, a bound outside +-2^24, a bad `rounding`, axis not in {0, 1}, gs < 1, a
+ * non-positive extent and R * C >= 2^31 return LQ_EINVAL before any launch.  P, s, b, below, above or hist off the 4-byte grid and
+ * err2 or sig2 off the 8-byte grid return LQ_EALIGN; 16-byte loads of P are used under the group rule (16-byte aligned P,
+ * C % 4 == 0, and gs % 4 == 0 on axis 1).  The kernels take the group-wise backward's form, team width and grid.  The call only
+ * enqueues ONE launch (capturable), allocates nothing, reads the extents of P, s and b and writes the extents of its five
+ * outputs and nothing else.  */
+int lq_group_stats(const float* P, const float* s, const float* b /* NULL: symmetric */, int32_t qmin, int32_t qmax, int rounding,
+                   uint32_t* below, uint32_t* above, double* err2, double* sig2, uint32_t* hist /* may be NULL */,
+                   int64_t R, int64_t C, int axis, int64_t gs, void* stream);
+
 /* ---- K4: forward and NQ backward of one tensor in a single pass (benchmark path) ---
  * Same results as lq_fq_forward followed by lq_fq_scale_grad (out, max|q| and the vote count bit for bit; on
  * streaming-size tensors the vote sum may differ by fp32 summation order, ~1e-7 relative); P is read once.  */

@@ -55,6 +55,7 @@
 #include "lq_group.hpp"
 #include "lq_group_batch.hpp"
 #include "lq_scale_init.hpp"
+#include "lq_group_stats.hpp"
 
 namespace lq {
 
@@ -1609,6 +1610,69 @@ int lq_scale_init_group_minmax(const float* P, float* s, float* b, int32_t qmin,
     ip.b = b;
     const bool vec = group_vec_ok(gp, axis) && aligned(P, 16);
     return launch_scale_init<kInitMinMax, false>(ip, gp, axis, vec, "min-max", stream);
+}
+
+// ---- per-group statistics (lq_group_stats.hpp) ----
+extern "C++" {
+// The backward's launch shape (group_launch without a row split) with the block's histogram in dynamic LDS
+template <bool RNE, bool AFF>
+static int launch_group_stats(const GroupLaunch& L, const StatsParams& sp, hipStream_t st) {
+    const size_t lds = sp.hist ? (size_t)sp.nbins * sizeof(uint32_t) : 0;
+    switch (L.form) {
+        case GROUP_COLS4: hipLaunchKernelGGL((k_stats_cols<RNE, AFF, 4, kGroupColsLanes4>), L.grid, dim3(kBlock), lds, st, sp); break;
+        case GROUP_COLS1: hipLaunchKernelGGL((k_stats_cols<RNE, AFF, 1, kGroupColsLanes1>), L.grid, dim3(kBlock), lds, st, sp); break;
+        case GROUP_ROWS4: hipLaunchKernelGGL((k_stats_rows<RNE, AFF, 4>), L.grid, dim3(kBlock), lds, st, sp, L.log_team); break;
+        default: hipLaunchKernelGGL((k_stats_rows<RNE, AFF, 1>), L.grid, dim3(kBlock), lds, st, sp, L.log_team); break;
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(LQ_EHIP, "group statistics %s launch: %s", L.form <= GROUP_COLS1 ? "column" : "row", hipGetErrorString(e));
+    return LQ_OK;
+}
+}  // extern "C++"
+
+int lq_group_stats(const float* P, const float* s, const float* b, int32_t qmin, int32_t qmax, int rounding, uint32_t* below,
+                   uint32_t* above, double* err2, double* sig2, uint32_t* hist, int64_t R, int64_t C, int axis, int64_t gs,
+                   void* stream) {
+    const char* fn = __func__;
+    int rc = check_group(fn, R, C, axis, gs);
+    if (rc) return rc;
+    LQ_REQUIRE_PTR_FN(fn, P);
+    LQ_REQUIRE_PTR_FN(fn, s);
+    if (b && !aligned(b, 4)) return fail(LQ_EALIGN, "%s: b is not 4-byte aligned", fn);
+    LQ_REQUIRE_PTR_FN(fn, below);
+    LQ_REQUIRE_PTR_FN(fn, above);
+    if (!err2 || !sig2) return fail(LQ_EINVAL, "%s: argument '%s' is NULL", fn, err2 ? "sig2" : "err2");
+    if (!aligned(err2, 8) || !aligned(sig2, 8)) return fail(LQ_EALIGN, "%s: err2 and sig2 must be 8-byte aligned", fn);
+    if (hist && !aligned(hist, 4)) return fail(LQ_EALIGN, "%s: hist is not 4-byte aligned", fn);
+    if ((rc = check_clip_range(fn, qmin, qmax))) return rc;
+    if ((rc = check_rounding(fn, rounding))) return rc;
+    const int64_t codes = (int64_t)qmax - (int64_t)qmin + 1;
+    if (hist && codes > kStatsMaxBins)
+        return fail(LQ_EINVAL, "%s: a histogram of %lld codes exceeds the limit of %d (pass hist = NULL)", fn, (long long)codes, kStatsMaxBins);
+    const GroupParams gp = group_params(P, s, qmin, qmax, R, C, axis, gs);
+    StatsParams sp{};
+    sp.P = P;
+    sp.s = s;
+    sp.b = b;
+    sp.lo = gp.lo;
+    sp.hi = gp.hi;
+    sp.qmin = qmin;
+    sp.nbins = hist ? (int32_t)codes : 0;
+    sp.below = below;
+    sp.above = above;
+    sp.err2 = err2;
+    sp.sig2 = sig2;
+    sp.hist = hist;
+    sp.R = gp.R;
+    sp.C = gp.C;
+    sp.gs = gp.gs;
+    sp.nb = gp.nb;
+    const bool vec = group_vec_ok(gp, axis) && aligned(P, 16);
+    const GroupLaunch L = group_launch(gp, axis, vec, false, kGroupGridY);
+    hipStream_t st = (hipStream_t)stream;
+    const bool rne = rounding == LQ_ROUND_NEAREST_EVEN;
+    if (b) return rne ? launch_group_stats<true, true>(L, sp, st) : launch_group_stats<false, true>(L, sp, st);
+    return rne ? launch_group_stats<true, false>(L, sp, st) : launch_group_stats<false, false>(L, sp, st);
 }
 
 int lq_fq_fwd_bwd_fused(const float* P, const float* s, const float* dy, float lambda, float* out, float* ds, void* ws,

@@ -26,7 +26,7 @@ import torch
 
 from . import layers as L
 from .export import save_compress_parameters, save_packed_parameters
-from .tracking import AccuracyLossTrackingCallBack, NestedScaleTrackingCallback
+from .tracking import AccuracyLossTrackingCallBack, GroupQuantTrackingCallback, NestedScaleTrackingCallback
 from .train import DriverParser, Trainer, synthetic_batch
 
 
@@ -192,8 +192,11 @@ def main(argv=None):
             # has run: the scale optimizer's moments are still zero)
             L.init_scales(tr.model, args.scale_init)
     log_model_structure(tr.model, log_dir)
-    # the scale-tracking callback reads the unclipped integer view under one-axis scales: not attached to group-wise layers
+    # the scale-tracking callback reads the unclipped integer view under one-axis scales: group-wise layers get the clipped
+    # quantizer's own statistics instead (clipped shares, SQNR, codes in use), after the callbacks that were attached before
     callbacks = [NestedScaleTrackingCallback(layer, log_dir) for layer in tr.custom_layers if layer.group_size is None]
+    group_callbacks = [GroupQuantTrackingCallback(layer, log_dir) for layer in tr.custom_layers if layer.group_size is not None]
+    callbacks += group_callbacks
     callbacks.append(AccuracyLossTrackingCallBack(log_dir))
     t0 = time.perf_counter()
     history = fit(tr, args.epochs, args.steps_per_epoch, args.batch, callbacks, args.lr,
@@ -207,6 +210,10 @@ def main(argv=None):
         line.update({"first_layer_unique_integers": stats["unique_k"], "first_layer_max_abs_q": float(stats["max_k"].max())})
     else:
         line["group_size"] = args.group_size
+        if group_callbacks:
+            stats = group_callbacks[0].stats()["kernel"]
+            line.update({"first_layer_sqnr_db": stats["sqnr_db"], "first_layer_clip_low": stats["clip_low"],
+                         "first_layer_clip_high": stats["clip_high"]})
     if packed is not None:
         line["packed"] = packed
     if args.loss_values:

@@ -20,14 +20,14 @@ import json
 import math
 import os
 import zipfile
-from typing import Dict, List, Tuple
+from typing import Dict, List
 
 import numpy as np
 import torch
 
 from . import ops
 from .descriptor import group_geometry
-from .layers import CustomDenseLayer, CustomQuantizedScaleLayer, _ConvBase
+from .layers import CustomQuantizedScaleLayer, quantized_tensors      # the one walk both exports use
 
 
 def _host(t: torch.Tensor) -> np.ndarray:
@@ -35,21 +35,6 @@ def _host(t: torch.Tensor) -> np.ndarray:
     back from ``.cpu().numpy()`` with permuted strides -- a 1x1 kernel even F-contiguous, which numpy pickles in Fortran byte order:
     the bytes of weights.npy (and the compressed size in file_sizes.log) would then depend on the storage."""
     return np.ascontiguousarray(t.detach().cpu().numpy())
-
-
-def quantized_tensors(model: torch.nn.Module) -> List[Tuple[str, torch.nn.Parameter, CustomQuantizedScaleLayer]]:
-    """(reference name, parameter, nested scale layer) of every quantized tensor -- kernel/W and bias of every custom layer,
-    in module order.  The one walk both exports use: the int8 file (log_scripts.py:74-79) and the packed container."""
-    out = []
-    for layer in model.modules():
-        if isinstance(layer, _ConvBase):
-            out.append((layer.name + "/W", layer.kernel, layer.nested_q_k_layer))
-            if layer._has_bias:
-                out.append((layer.name + "/b", layer.b, layer.nested_q_b_layer))
-        elif isinstance(layer, CustomDenseLayer):
-            out.append((layer.name + "/W", layer.W, layer.nested_q_w_layer))
-            out.append((layer.name + "/b", layer.b, layer.nested_q_b_layer))
-    return out
 
 
 def quantized_state(model: torch.nn.Module) -> Dict[str, np.ndarray]:

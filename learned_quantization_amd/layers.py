@@ -272,6 +272,22 @@ class CustomQuantizedScaleLayer(nn.Module):
                 self.offset.data.zero_()
         return self.scale
 
+    def quant_stats(self, parameter, want_hist=True):
+        """Statistics of this layer's quantizer on ``parameter`` as the scale (and offset) stand now (ops.group_stats, with the
+        layer's own range, rounding, group size and offset): an ops.GroupStats record of device tensors, to be read with
+        ops.summarize_stats.  One launch, no synchronisation.  A layer without a range clips nothing and has no fixed set of
+        codes: ValueError; its statistics are ops.q_minmax, ops.q_unique and ops.q_absmax_over_axis
+        (tracking.NestedScaleTrackingCallback)."""
+        if self.q_range is None:
+            raise ValueError("quant_stats needs bits or q_range: the unbounded quantizer clips nothing and has no fixed set of codes; "
+                             "its statistics are ops.q_minmax / ops.q_unique / ops.q_absmax_over_axis "
+                             "(tracking.NestedScaleTrackingCallback)")
+        if not self.built:
+            raise ValueError("quant_stats before the layer is built: there is no scale yet")
+        with torch.no_grad():
+            return ops.group_stats(parameter.detach(), self.scale.data, *self.q_range, self.group_size,
+                                   offset=self.offset.data if self.asymmetric else None, rounding=self.rounding, want_hist=want_hist)
+
     def quantized_integers(self, parameter, dtype=torch.float32):
         """The integer view of ``parameter`` under this layer's quantizer: floor(P/s), clamped when the layer has a range (then
         rint(P/s) for ``rounding="nearest"``)."""
@@ -656,6 +672,39 @@ def custom_layers_of(model: nn.Module):
     """The reference selects layers by name substring (experiment.py:73, custom_loss_terms/experiment.py:446)."""
     return [m for m in model.modules()
             if isinstance(m, (CustomDenseLayer, _ConvBase))]
+
+
+def quantized_tensors(model: nn.Module):
+    """(reference name, parameter, nested scale layer) of every quantized tensor -- kernel/W and bias of every custom layer,
+    in module order.  The one walk the int8 file (log_scripts.py:74-79), the packed container (export.py) and ``quant_stats``
+    use."""
+    out = []
+    for layer in model.modules():
+        if isinstance(layer, _ConvBase):
+            out.append((layer.name + "/W", layer.kernel, layer.nested_q_k_layer))
+            if layer._has_bias:
+                out.append((layer.name + "/b", layer.b, layer.nested_q_b_layer))
+        elif isinstance(layer, CustomDenseLayer):
+            out.append((layer.name + "/W", layer.W, layer.nested_q_w_layer))
+            out.append((layer.name + "/b", layer.b, layer.nested_q_b_layer))
+    return out
+
+
+def quant_stats(model: nn.Module, want_hist=True) -> dict:
+    """{reference name: summary} of every quantized tensor of ``model`` (``quantized_tensors``' walk): the
+    ops.summarize_stats dict of the tensor's ``CustomQuantizedScaleLayer.quant_stats``.  One launch per tensor, then all records
+    go to the host together in one copy (one synchronisation: call it between steps, never inside a capture).  Every layer
+    needs a range: ValueError otherwise."""
+    tensors = quantized_tensors(model)
+    for name, _, nested in tensors:      # before any launch
+        if nested.q_range is None:
+            raise ValueError(f"quant_stats: the quantizer of {name!r} has no range (bits / q_range); the unbounded quantizer's "
+                             "statistics are tracking.NestedScaleTrackingCallback's")
+    # a range of more than ops.STATS_MAX_BINS codes has no histogram: its summary holds None for the two code statistics
+    records = [nested.quant_stats(param.data, want_hist and nested.q_range[1] - nested.q_range[0] < ops.STATS_MAX_BINS)
+               for _, param, nested in tensors]
+    summaries = ops.summarize_stats_many(records, [param.numel() for _, param, _ in tensors])
+    return {name: summary for (name, _, _), summary in zip(tensors, summaries)}
 
 
 def init_scales(model: nn.Module, method) -> nn.Module:

@@ -8,13 +8,13 @@
 
 Raw (non-autograd) wrappers ``fq_forward``, ``fq_scale_grad``, ``fq_scale_grad_ste``, ``fq_forward_clip``,
 ``fq_backward_clip``, ``fq_forward_group``, ``fq_backward_group``, ``fq_forward_group_affine``, ``fq_backward_group_affine``,
-``scale_init_group``, ``scale_init_group_minmax``, ``fq_fwd_bwd_fused``, ``quantized_integers`` ... are thin: argument checking + one C-ABI call each.
+``scale_init_group``, ``scale_init_group_minmax``, ``group_stats``, ``fq_fwd_bwd_fused``, ``quantized_integers`` ... are thin: argument checking + one C-ABI call each.
 Everything runs on the HIP device; there is no CPU fallback.
 """
 from __future__ import annotations
 
 import math
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -357,6 +357,131 @@ def scale_init_group_minmax(parameter: torch.Tensor, scale: torch.Tensor, offset
     _hip.check(lib.lq_scale_init_group_minmax(_hip.ptr(p), _hip.ptr(s), _hip.ptr(b), qmin, qmax, rnd, min_value, R, C, axis,
                                               int(group_size), _hip.stream_ptr(p.device)), "lq_scale_init_group_minmax")
     return scale, offset
+
+
+STATS_MAX_BINS = 4096      # include/lq_hip.h, lq_group_stats: the widest range whose codes it bins
+
+
+class GroupStats(NamedTuple):
+    """What ``group_stats`` returns, all on the device: ``below`` / ``above`` (int32 tensors holding the uint32 counts) and
+    ``err2`` / ``sig2`` (float64) in the scale's shape, ``hist`` (int32, qmax - qmin + 1 bins) or None."""
+    below: torch.Tensor
+    above: torch.Tensor
+    err2: torch.Tensor
+    sig2: torch.Tensor
+    hist: Optional[torch.Tensor]
+
+
+def group_stats(parameter: torch.Tensor, scale: torch.Tensor, qmin: int, qmax: int, group_size: Optional[int], *,
+                offset: Optional[torch.Tensor] = None, rounding: str = "floor", want_hist: bool = True) -> GroupStats:
+    """Statistics of the clipped quantizer on ``parameter`` under ``scale`` (and ``offset``) as they are now (include/lq_hip.h,
+    lq_group_stats): per group the elements clipped below and above the range and the f64 sums of squared error and squared
+    signal, per tensor the histogram of the codes.  ``scale`` is a group-wise matrix with its ``group_size``, or, with
+    ``group_size=None``, any scale descriptor.init_geometry accepts (as ``scale_init_group``).  Ranges of more than
+    STATS_MAX_BINS codes have no histogram: pass ``want_hist=False``.  One launch, read only, no synchronisation."""
+    qmin, qmax = check_q_range(qmin, qmax)
+    rnd = check_rounding(rounding)
+    if want_hist and qmax - qmin + 1 > STATS_MAX_BINS:
+        raise ValueError(f"the range [{qmin}, {qmax}] has {qmax - qmin + 1} codes, the histogram at most {STATS_MAX_BINS}: "
+                         "pass want_hist=False")
+    p = _hip.require_device_f32(parameter, "parameter", dense_ok=True)
+    s = _hip.require_device_f32(scale, "scale")
+    b = None if offset is None else _offset_like(offset, s)
+    R, C, axis, gs = init_geometry(tuple(p.shape), p.stride(), tuple(s.shape), group_size)
+    below = torch.empty_like(s, dtype=torch.int32)
+    above = torch.empty_like(s, dtype=torch.int32)
+    err2 = torch.empty_like(s, dtype=torch.float64)
+    sig2 = torch.empty_like(s, dtype=torch.float64)
+    hist = torch.zeros(qmax - qmin + 1, dtype=torch.int32, device=p.device) if want_hist else None
+    lib = _hip.load()
+    _hip.check(lib.lq_group_stats(_hip.ptr(p), _hip.ptr(s), _hip.ptr(b), qmin, qmax, rnd, _hip.ptr(below), _hip.ptr(above),
+                                  _hip.ptr(err2), _hip.ptr(sig2), _hip.ptr(hist), R, C, axis, gs, _hip.stream_ptr(p.device)),
+               "lq_group_stats")
+    return GroupStats(below, above, err2, sig2, hist)
+
+
+def _sqnr_db(sig2: float, err2: float) -> float:
+    """10 log10(sig2 / err2) in float64: inf for zero error, -inf for zero signal under an error, NaN where either sum is NaN
+    or both are infinite."""
+    if math.isnan(sig2) or math.isnan(err2) or (math.isinf(sig2) and math.isinf(err2)):
+        return math.nan
+    if err2 == 0.0 or math.isinf(sig2):
+        return math.inf
+    if sig2 == 0.0 or math.isinf(err2):
+        return -math.inf
+    ratio = sig2 / err2
+    if 0.0 < ratio < math.inf:
+        return 10.0 * math.log10(ratio)
+    return 10.0 * (math.log10(sig2) - math.log10(err2))      # the quotient itself left the float64 range
+
+
+def _stats_to_host(records):
+    """The records' tensors in ONE device->host copy, as records of NumPy arrays: float64 sums, int64 counts and bins (the
+    uint32 values behind the int32 tensors, which float64 carries exactly)."""
+    def f64(t):
+        t = t.reshape(-1)
+        if t.dtype == torch.int32:
+            return (t.to(torch.int64) & 0xFFFFFFFF).to(torch.float64)
+        return t.to(torch.float64)
+
+    parts = [f64(t) for rec in records for t in rec if t is not None]
+    if not parts:
+        return []
+    flat = torch.cat(parts).cpu().numpy()
+    host, at = [], 0
+    for rec in records:
+        fields = []
+        for t in rec:
+            if t is None:
+                fields.append(None)
+                continue
+            a = flat[at:at + t.numel()].reshape(tuple(t.shape))
+            at += t.numel()
+            fields.append(a if t.dtype.is_floating_point else a.astype(np.int64))
+        host.append(GroupStats(*fields))
+    return host
+
+
+def _summarize_host(rec: GroupStats, numel: int) -> dict:
+    n = float(numel)
+    err2 = np.asarray(rec.err2, dtype=np.float64).reshape(-1)
+    sig2 = np.asarray(rec.sig2, dtype=np.float64).reshape(-1)
+    out = {
+        "clip_low": float(np.asarray(rec.below, dtype=np.float64).sum() / n),
+        "clip_high": float(np.asarray(rec.above, dtype=np.float64).sum() / n),
+        "sqnr_db": _sqnr_db(float(sig2.sum()), float(err2.sum())),
+        "worst_group_sqnr_db": min((_sqnr_db(float(a), float(e)) for a, e in zip(sig2, err2)),
+                                   key=lambda v: -math.inf if math.isnan(v) else v),
+        "used_levels": None,
+        "entropy_bits": None,
+    }
+    if rec.hist is not None:
+        h = np.asarray(rec.hist, dtype=np.float64).reshape(-1)
+        used, total = h[h > 0], float(h.sum())
+        out["used_levels"] = int(used.size)
+        pr = used / total if total > 0 else used
+        out["entropy_bits"] = float(max(0.0, -(pr * np.log2(pr)).sum())) if used.size else 0.0
+    return out
+
+
+def summarize_stats(record: GroupStats, numel: int) -> dict:
+    """Host floats of one ``group_stats`` record of a tensor of ``numel`` elements, computed in float64 on the host after ONE
+    device->host copy: ``clip_low`` / ``clip_high`` (shares of the elements clipped below / above), ``sqnr_db`` = 10 log10(sum
+    sig2 / sum err2) (inf for zero error), ``worst_group_sqnr_db`` (the smallest group's; NaN if a group's is NaN),
+    ``used_levels`` (codes that occur) and ``entropy_bits`` (Shannon entropy of the code distribution; both None without a
+    histogram).  The record's fields may be device tensors, host tensors or NumPy arrays."""
+    numel = int(numel)
+    if numel < 1:
+        raise ValueError(f"numel must be positive, got {numel}")
+    if any(isinstance(t, torch.Tensor) for t in record):
+        record = _stats_to_host([GroupStats(*(t if t is None or isinstance(t, torch.Tensor) else torch.as_tensor(t) for t in record))])[0]
+    return _summarize_host(record, numel)
+
+
+def summarize_stats_many(records, numels) -> list:
+    """``summarize_stats`` of several records with all of them copied to the host together (one device->host copy)."""
+    host = _stats_to_host(list(records))
+    return [_summarize_host(rec, int(n)) for rec, n in zip(host, numels)]
 
 
 def fq_fwd_bwd_fused(parameter: torch.Tensor, scale: torch.Tensor, dy: torch.Tensor, penalty_threshold: float,

@@ -11,14 +11,20 @@ The statistics that define the Pareto axes are computed on the GPU -- ``floor(P/
 (LDS-privatised integer histogram) -- and only the
 results cross PCIe.  The reference's per-epoch dump of every raw kernel value (:52-66) is opt-in
 (``dump_values=True``): it is tens of MB of text per epoch and not needed by the Pareto plots.
+
+``GroupQuantTrackingCallback`` (not in the reference) logs the clipped b-bit quantizer in the same format: per group the
+clipped shares on either side and the SQNR, per tensor the SQNR, the codes in use and their entropy, from one
+``lq_group_stats`` launch per tensor.
 """
 from __future__ import annotations
 
 import os
 
+import numpy as np
 import torch
 
 from . import ops
+from .descriptor import init_geometry
 
 
 def _shape(t) -> str:
@@ -111,6 +117,115 @@ class NestedScaleTrackingCallback:
     def on_train_begin(self, logs=None):
         self._dump_quantized(self.log_file_path_qk_initial, self.log_file_path_qb_initial,
                              self.log_file_path_qk_initial_unique, self.log_file_path_qb_initial_unique)
+
+
+def group_sizes(param, scale, group_size) -> np.ndarray:
+    """Elements per group of ``scale`` on ``param`` (int64, the scale's shape): the last group of a line may be short."""
+    R, C, axis, gs = init_geometry(tuple(param.shape), param.stride(), tuple(scale.shape), group_size)
+    length, lines = (R, C) if axis == 0 else (C, R)
+    gs = min(gs, length)
+    per_line = np.minimum(gs, length - gs * np.arange(-(-length // gs), dtype=np.int64))
+    n = np.repeat(per_line[:, None], lines, axis=1) if axis == 0 else np.repeat(per_line[None, :], lines, axis=0)
+    return n.reshape(tuple(scale.shape))
+
+
+class GroupQuantTrackingCallback:
+    """Per-epoch logs of a layer whose quantizer has a range (``bits`` / ``q_range``), with any scale ops.group_stats takes:
+    group-wise (symmetric or with offsets), scalar, a Dense orientation, channel-wise on OIHW storage.  Same directory layout
+    and ``Epoch N`` + one-value-per-line format as ``NestedScaleTrackingCallback``.  For the kernel and the bias, per epoch end
+    (group values in the scale's memory order):
+
+      <name>_<shape>_<scale name>_<scale shape>.log    the scales          <name>_<shape>_Offset_<scale shape>.log   the offsets
+      Clip_low_<name>_<shape>.log / Clip_high_...      share of each group's elements clipped below / above the range
+      SQNR_dB_<name>_<shape>.log                       10 log10(sig2 / err2) of each group
+      SQNR_dB_tensor_<name>_<shape>.log                the same of the whole tensor (one value per epoch)
+      Used_levels_<name>_<shape>.log                   codes of the range that occur
+      Code_entropy_bits_<name>_<shape>.log             Shannon entropy of the code distribution
+
+    and on train begin / train end the code histogram as ``value, count`` lines (``Unique_initial_quantized_...`` /
+    ``Unique_quantized_...``).  One lq_group_stats launch per tensor and one device->host copy per call."""
+
+    def __init__(self, layer, log_dir):
+        self.layer = layer
+        if hasattr(layer, "kernel"):
+            param, nested, kernel_name = layer.kernel, layer.nested_q_k_layer, f"Kernel_{layer.name}"
+        else:
+            param, nested, kernel_name = layer.W, layer.nested_q_w_layer, "Weights"
+        bias_name = f"Bias_{layer.name}" if hasattr(layer, "kernel") else "Bias"
+        self.tensors = [("kernel", kernel_name, param, nested)]
+        if getattr(layer, "b", None) is not None and getattr(layer, "nested_q_b_layer", None) is not None:
+            self.tensors.append(("bias", bias_name, layer.b, layer.nested_q_b_layer))
+        e, t, b0 = (os.path.join(log_dir, d) for d in ("on_epoch_end", "on_train_end", "on_train_begin"))
+        for d in (e, t, b0):
+            os.makedirs(d, exist_ok=True)
+        self.paths, self.sizes = {}, {}
+        for what, name, p, q in self.tensors:
+            if q.q_range is None:
+                raise ValueError(f"GroupQuantTrackingCallback: the quantizer of {name} has no range; use NestedScaleTrackingCallback")
+            self.sizes[what] = group_sizes(p, q.scale, q.group_size)      # ValueError where the groups are not lines of a matrix
+            psh, ssh = _shape(p), _shape(q.scale)
+            self.paths[what] = {
+                "scale": f"{e}/{name}_{psh}_{q.scale_name}_{ssh}.log",
+                "offset": f"{e}/{name}_{psh}_Offset_{ssh}.log" if q.asymmetric else None,
+                "clip_low": f"{e}/Clip_low_{name}_{psh}.log",
+                "clip_high": f"{e}/Clip_high_{name}_{psh}.log",
+                "sqnr": f"{e}/SQNR_dB_{name}_{psh}.log",
+                "sqnr_tensor": f"{e}/SQNR_dB_tensor_{name}_{psh}.log",
+                "used": f"{e}/Used_levels_{name}_{psh}.log",
+                "entropy": f"{e}/Code_entropy_bits_{name}_{psh}.log",
+                "hist_begin": f"{b0}/Unique_initial_quantized_{name}_{psh}_{q.scale_name}_{ssh}.log",
+                "hist_end": f"{t}/Unique_quantized_{name}_{psh}_{q.scale_name}_{ssh}.log",
+            }
+
+    def epoch_files(self):
+        """Every file ``on_epoch_end`` appends to."""
+        keys = ("scale", "offset", "clip_low", "clip_high", "sqnr", "sqnr_tensor", "used", "entropy")
+        return [self.paths[what][k] for what, *_ in self.tensors for k in keys if self.paths[what][k] is not None]
+
+    def _records(self):
+        """The host copies of every tensor's statistics, taken together."""
+        return ops._stats_to_host([q.quant_stats(p.data, want_hist=q.q_range[1] - q.q_range[0] < ops.STATS_MAX_BINS)
+                                   for _, _, p, q in self.tensors])
+
+    def stats(self):
+        """{"kernel": summary, "bias": summary}: ops.summarize_stats of the tensors as they are now."""
+        return {what: ops._summarize_host(rec, p.numel()) for (what, _, p, _), rec in zip(self.tensors, self._records())}
+
+    _append = staticmethod(NestedScaleTrackingCallback._append)
+
+    def on_epoch_end(self, epoch, logs=None):
+        hdr = f"Epoch {epoch}\n"
+        out = {}
+        for (what, _, p, q), rec in zip(self.tensors, self._records()):
+            paths, n = self.paths[what], self.sizes[what].reshape(-1).astype(np.float64)
+            st = ops._summarize_host(rec, p.numel())
+            self._append(paths["scale"], hdr, q.scale.detach().flatten().cpu().numpy())
+            if paths["offset"] is not None:
+                self._append(paths["offset"], hdr, q.offset.detach().flatten().cpu().numpy())
+            self._append(paths["clip_low"], hdr, rec.below.reshape(-1) / n)
+            self._append(paths["clip_high"], hdr, rec.above.reshape(-1) / n)
+            self._append(paths["sqnr"], hdr, [ops._sqnr_db(float(a), float(b)) for a, b in zip(rec.sig2.reshape(-1), rec.err2.reshape(-1))])
+            self._append(paths["sqnr_tensor"], hdr, [st["sqnr_db"]])
+            if rec.hist is not None:      # a range of more than ops.STATS_MAX_BINS codes has no histogram
+                self._append(paths["used"], hdr, [st["used_levels"]])
+                self._append(paths["entropy"], hdr, [st["entropy_bits"]])
+            out[what] = st
+        return out
+
+    def _dump_hist(self, key):
+        for (what, _, _, q), rec in zip(self.tensors, self._records()):
+            if rec.hist is None:
+                continue
+            with open(self.paths[what][key], "a") as f:
+                for code, count in enumerate(rec.hist):
+                    if count:
+                        f.write(f"{np.float32(q.q_range[0] + code)}, {int(count)}\n")
+
+    def on_train_end(self, logs=None):
+        self._dump_hist("hist_end")
+
+    def on_train_begin(self, logs=None):
+        self._dump_hist("hist_begin")
 
 
 class AccuracyLossTrackingCallBack:

@@ -531,11 +531,17 @@ def build_parser():
     ap.add_argument("--channels-last", action="store_true",
                     help="feed NHWC-strided batches (torch.channels_last): MIOpen's fp32 igemm kernels are NHWC; measured "
                          "+17 %% on the ResNet-18-like config, -17 %% on the small CIFAR CNN")
+    ap.add_argument("--quant-stats", action="store_true",
+                    help="with --bits: add layers.quant_stats of the final parameters to the result line (per tensor: clipped "
+                         "shares, SQNR in dB, codes in use, code entropy); taken after the timed steps")
     return ap
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if args.quant_stats and args.bits is None:
+        ap.error("--quant-stats needs --bits: the statistics are those of a quantizer with a range")
 
     # read by the HSA runtime when it initialises (the first torch.cuda call below): the host driver only supports dmabuf IPC
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -596,6 +602,7 @@ def main(argv=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t)
     log_rows = tr.flush_loss_log() if args.loss_values and rank == 0 else None     # every rank holds the same rows: one writes
+    quant_stats = L.quant_stats(tr.model) if args.quant_stats and rank == 0 else None      # after the clock has stopped
     if rank == 0:
         n_q = sum(p.numel() for l in tr.custom_layers for p in l._regularized())
         print(json.dumps({
@@ -616,7 +623,8 @@ def main(argv=None):
             **({"group_size": tr.group_size} if tr.group_size is not None else {}),
             **({"asymmetric": True} if tr.asymmetric else {}),
             **({"scale_init": tr.scale_init} if tr.scale_init is not None else {}),
-            **({"loss_values": True, "loss_log_rows": log_rows[0], "loss_log_dropped": log_rows[1]} if log_rows else {})}))
+            **({"loss_values": True, "loss_log_rows": log_rows[0], "loss_log_dropped": log_rows[1]} if log_rows else {}),
+            **({"quant_stats": quant_stats} if quant_stats is not None else {})}))
         if args.export_dir:
             from .export import save_compress_parameters
             print(json.dumps(save_compress_parameters(tr.model, args.export_dir)))

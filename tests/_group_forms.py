@@ -184,12 +184,10 @@ def plant_specials(P, rng, rounds=6):
     return at
 
 
-def window_group_case(seed, R, C, axis, gs):
-    """(P, s, dy, bad): ordinary inputs (make_case) with scales of BAD_SCALES interleaved -- axis 0: exactly one of every four
-    columns of a float4 (its lane moves with the group and the float4), axis 1: every other group of a row, shifted by the row --
-    and special values planted in P.  ``bad``: bool, in the shape of s."""
-    P, s, dy = make_case(seed, R, C, axis, gs)
-    rng = np.random.default_rng(seed + 1)
+def interleave_bad_scales(s, C, axis):
+    """(s, bad): the scales ``s`` with the values of BAD_SCALES interleaved -- axis 0: exactly one of every four columns of a
+    float4 (its lane moves with the group and the float4), axis 1: every other group of a row, shifted by the row.  ``bad``: bool,
+    in the shape of s; every value of BAD_SCALES is reached."""
     a, b = np.indices(s.shape)
     if axis == 0:                      # s[g][c]
         bad = (b % 4) == ((a + b // 4) % 4)
@@ -199,6 +197,15 @@ def window_group_case(seed, R, C, axis, gs):
         which = ((a * s.shape[1] + b) // 2) % BAD_SCALES.size
     s = np.where(bad, BAD_SCALES[which], s).astype(np.float32)
     assert set(which[bad].tolist()) == set(range(BAD_SCALES.size)), "a scale value is not reached"
+    return s, bad
+
+
+def window_group_case(seed, R, C, axis, gs):
+    """(P, s, dy, bad): ordinary inputs (make_case) with scales of BAD_SCALES interleaved (interleave_bad_scales) and special
+    values planted in P.  ``bad``: bool, in the shape of s."""
+    P, s, dy = make_case(seed, R, C, axis, gs)
+    rng = np.random.default_rng(seed + 1)
+    s, bad = interleave_bad_scales(s, C, axis)
     plant_specials(P, rng)
     return P, s, dy, bad
 

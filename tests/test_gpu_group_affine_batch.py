@@ -122,6 +122,7 @@ class Buf:
         Pn = Pn if P is None else P
         bn = None if b is False else (bn if b is None else b)
         self.i, self.geom, self.range = i, SET[i], RANGES[i % 3]
+        self.k, self.kb = _k(i), _kb(i)                               # grad_scale and offset_grad_scale of this tensor
         self.s = _t(sn, dev)
         self.b = None if bn is None else _t(bn, dev)
         self.P, self.dy = self._at(Pn, dev, offset), self._at(dyn, dev, offset)
@@ -150,7 +151,7 @@ class Buf:
     def off(self, _hip):
         if self.b is None:
             return _hip.GroupOffset(None, None, 0.0)
-        return _hip.GroupOffset(self.b.data_ptr(), self.db.data_ptr() if self.pass_db else None, _kb(self.i))
+        return _hip.GroupOffset(self.b.data_ptr(), self.db.data_ptr() if self.pass_db else None, self.kb)
 
     def untouched(self, *names):
         return all(bool((getattr(self, n).view(torch.int32) == SENTINEL).all()) for n in names)
@@ -190,7 +191,7 @@ class Batch:
     def backward_rc(self, dys=None, mask_only=False):
         n = len(self.bufs)
         ptrs = (ctypes.c_void_p * n)(*[(b.dy if dys is None else dys[j]).data_ptr() for j, b in enumerate(self.bufs)])
-        gs = None if mask_only else (ctypes.c_float * n)(*[_k(b.i) for b in self.bufs])
+        gs = None if mask_only else (ctypes.c_float * n)(*[b.k for b in self.bufs])
         return self.lib.lq_group_batch_backward(self.handle, ptrs, gs, None, 0, self._hip.stream_ptr(self.dev))
 
     def backward(self, **kw):
@@ -223,14 +224,14 @@ def _single(b, rounding):
     if b.b is None:
         db = None
         _hip.check(lib.lq_fq_forward_group(b.P.data_ptr(), b.s.data_ptr(), out.data_ptr(), None, 0, *b.range, rnd, R, C, axis, gs, st), "fwd")
-        _hip.check(lib.lq_fq_backward_group(b.P.data_ptr(), b.s.data_ptr(), b.dy.data_ptr(), *b.range, rnd, _k(b.i), dP.data_ptr(),
+        _hip.check(lib.lq_fq_backward_group(b.P.data_ptr(), b.s.data_ptr(), b.dy.data_ptr(), *b.range, rnd, b.k, dP.data_ptr(),
                                             ds.data_ptr(), cnt.data_ptr(), None, 0, R, C, axis, gs, st), "bwd")
     else:
         db = torch.empty_like(b.s)
         _hip.check(lib.lq_fq_forward_group_affine(b.P.data_ptr(), b.s.data_ptr(), b.b.data_ptr(), out.data_ptr(), None, 0, *b.range, rnd,
                                                   R, C, axis, gs, st), "affine fwd")
         _hip.check(lib.lq_fq_backward_group_affine(b.P.data_ptr(), b.s.data_ptr(), b.b.data_ptr(), b.dy.data_ptr(), *b.range, rnd,
-                                                   _k(b.i), _kb(b.i), dP.data_ptr(), ds.data_ptr(), db.data_ptr(), cnt.data_ptr(),
+                                                   b.k, b.kb, dP.data_ptr(), ds.data_ptr(), db.data_ptr(), cnt.data_ptr(),
                                                    None, 0, R, C, axis, gs, st), "affine bwd")
     return (out.cpu().numpy(), dP.cpu().numpy(), ds.cpu().numpy(), None if db is None else db.cpu().numpy(),
             cnt.cpu().numpy().view(np.uint32).astype(np.int64))

@@ -263,6 +263,73 @@ int lq_fq_backward_group_affine(const float* P, const float* s, const float* b, 
 int lq_scale_init_group_minmax(const float* P, float* s, float* b, int32_t qmin, int32_t qmax, int rounding, float min_value,
                                int64_t R, int64_t C, int axis, int64_t gs, void* stream);
 
+/* ---- OCP microscaling (MX) element formats: a minifloat grid under one scale per group ----
+ * Geometry is exactly lq_fq_forward_group's: matrix [R][C] in memory order, axis, gs clamped to the line length, nb = ceil(len / gs),
+ * ragged last group; the scale is [nb][C] or [R][nb].  (An MX block is gs = 32.)
+ *
+ * Element formats (lq_elem_format)      id  bits  E  M  emin  emax  max
+ *   LQ_ELEM_FP4_E2M1                     0    4   2  1     0     2  6
+ *   LQ_ELEM_FP6_E2M3                     1    6   2  3     0     2  7.5
+ *   LQ_ELEM_FP6_E3M2                     2    6   3  2    -2     4  28
+ *   LQ_ELEM_FP8_E4M3 (OCP e4m3fn)        3    8   4  3    -6     8  448
+ *   LQ_ELEM_FP8_E5M2 (OCP e5m2)          4    8   5  2   -14    15  57344
+ * Neither fp8 format is an FNUZ variant.
+ *
+ * Effective scale s_eff of a stored scale s, by `scale_format` (bits(s): the fp32 pattern of s):
+ *   LQ_SCALE_E8M0  s is valid iff 0x00800000 <= bits(s) < 0x7F800000 (positive, normal, finite).
+ *                  nb = (bits(s) + 0x004AFB0D) & 0x7F800000: the nearest power of two in the log domain; the mantissa threshold is
+ *                  sqrt(2) (fraction bits 0x3504F3) and rounds up.  s_eff = the float with pattern nb if s is valid and
+ *                  nb < 0x7F800000, otherwise NaN.  So s_eff is in [2^-126, 2^127]; a zero, negative, subnormal, non-finite or too
+ *                  large scale spoils its own group and no other.
+ *   LQ_SCALE_FP32  s_eff = s, used as the group-wise pair uses it.
+ *
+ * Per element, in fp32, every operation rounding on its own; mx is the format's max:
+ *   t  = P / s_eff                              IEEE division
+ *   a  = |t|;  e = max(unbiased exponent field of a, emin)      (zero / fp32-subnormal a: the field is -127, so e = emin)
+ *   u  = 2^(e - M)
+ *   q0 = copysign(rintf(a / u) * u, t)          ties to even; a / u and the product are exact; a non-finite t passes through
+ *   inside = |q0| <= mx                         false for NaN
+ *   q  = q0 < -mx ? -mx : (q0 > mx ? mx : q0)   comparisons: NaN stays NaN, +-Inf saturates
+ *   out = q * s_eff
+ *   dP = inside ? dy : +0.0f
+ *   r  = inside ? q0 - t : q
+ *   ds[g]      = RN_f32( (double)grad_scale * sum_{i in g} (double)dy_i * (double)r_i )      f64 from the first addition
+ *   clipped[g] = #{ i in g : !inside_i }        exact, uint32
+ * ds is the straight-through gradient with respect to the STORED s: the power-of-two rounding passes it unchanged.  With E8M0, t,
+ * q0 - t and out are exact barring under/overflow; only the order of the f64 sum is left open, and it is the group-wise backward's
+ * for the same geometry and alignment: no atomics, no workspace, run-to-run bit-stable.
+ *
+ * Code view.  The optional integer output of the forward (`code` / `code_dtype`, the q / q_dtype mechanism of the other forwards)
+ * holds the element's ENCODING, the bits a packed MX operand carries:
+ *   sign = signbit(q), a = |q|;  a < 2^emin: mag = a * 2^(M - emin);  otherwise, with e the exponent of a,
+ *   mag = (e - emin + 1) * 2^M + (a * 2^(M - e) - 2^M);  code = sign * 2^(E+M) + mag, in [0, 2^bits); -0.0 keeps its sign bit.
+ *   A NaN q gets code 2^(E+M) - 1: all ones below the sign bit, sign bit clear (the sign of a NaN is not defined by the arithmetic
+ *   that made it).
+ *
+ * lq_fq_forward_mx: `out` is required.  lq_fq_backward_mx: dP is required, ds == NULL means mask only, clipped may be NULL.
+ * LQ_EINVAL and LQ_EALIGN under exactly the conditions of the group-wise pair (range and rounding aside: there are none); an
+ * unknown `format`, `scale_format` or `method` returns LQ_EINVAL too.  The kernels take the group-wise pair's form, vector width,
+ * team width, row split and grid.  Each call only enqueues (capturable) ONE launch, needs no workspace and reads no environment.
+ *
+ * lq_scale_init_mx writes a power-of-two starting scale per group (s is the OUTPUT).  A = max_i |P_i| (exact) = m * 2^e with m in
+ * [1, 2), a subnormal A normalised; mx = mm * 2^emax with mm = 1.5, 1.875, 1.75, 1.75, 1.75 in table order.
+ *   LQ_MX_INIT_OCP    p = 2^(e - emax): the OCP MX rule; elements up to 2^(emax+1) steps may saturate.
+ *   LQ_MX_INIT_COVER  p = m <= mm ? 2^(e - emax) : 2^(e - emax + 1): the smallest power of two under which nothing saturates.
+ * p is raised to 2^-126 if below it; the result is fmaxf(p, min_value) (min_value > 0 and finite, else LQ_EINVAL).  A group of
+ * zeros gets min_value, a group holding NaN or +-Inf gets NaN.  Integer exponent arithmetic: no rounding is involved.  */
+typedef enum lq_elem_format {
+    LQ_ELEM_FP4_E2M1 = 0, LQ_ELEM_FP6_E2M3 = 1, LQ_ELEM_FP6_E3M2 = 2, LQ_ELEM_FP8_E4M3 = 3, LQ_ELEM_FP8_E5M2 = 4
+} lq_elem_format;
+typedef enum lq_scale_format { LQ_SCALE_E8M0 = 0, LQ_SCALE_FP32 = 1 } lq_scale_format;
+typedef enum lq_mx_init_method { LQ_MX_INIT_OCP = 0, LQ_MX_INIT_COVER = 1 } lq_mx_init_method;
+int lq_fq_forward_mx(const float* P, const float* s, float* out, void* code, int code_dtype, int format, int scale_format,
+                     int64_t R, int64_t C, int axis, int64_t gs, void* stream);
+int lq_fq_backward_mx(const float* P, const float* s, const float* dy, int format, int scale_format, float grad_scale, float* dP,
+                      float* ds /* may be NULL: mask only */, uint32_t* clipped /* may be NULL */, int64_t R, int64_t C, int axis,
+                      int64_t gs, void* stream);
+int lq_scale_init_mx(const float* P, float* s /* out */, int format, int method, float min_value, int64_t R, int64_t C, int axis,
+                     int64_t gs, void* stream);
+
 /* ---- quantization statistics of the clipped pair: per group and per tensor, read only ----
  * What the quantizer does to P under the scales (and offsets) it has NOW: how much each group loses on either side of the range,
  * the squared error and the squared signal of each group, and the histogram of the codes of the tensor.

@@ -14,6 +14,7 @@ from .losses import LossLog, SCCEDifference, SCCEInverse, SCCEMaxBin, sparse_cat
 from .ops import (difference_term, fq_backward_clip, fq_backward_group, fq_forward, fq_forward_clip, fq_forward_group, fq_fwd_bwd_fused, fq_scale_grad, fq_scale_grad_ste,
                   inverse_term, maxbin_term,
                   fq_backward_group_affine, fq_forward_group_affine, scale_init_group_minmax, GroupStats, group_stats, summarize_stats,
+                  ELEMENT_FORMATS, check_element_format, fq_backward_mx, fq_forward_mx, scale_init_mx,
                   my_custom_gradient, q_absmax_over_axis, q_minmax, q_pack, q_range_of, q_unique, q_unpack, quantized_integers, SCALE_INITS, scale_init_group)
 from .optim import KerasAdam, ScaleAdam, apply_constraints, non_scale_parameters, scale_parameters
 from .ddp import DataParallel, GradBucket

@@ -68,6 +68,9 @@ SIGNATURES = {
     "lq_fq_backward_group_affine": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i32, _c_i32, _c_int, _c_f, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p,
                                              _c_sz, _c_i64, _c_i64, _c_int, _c_i64, _c_p]),
     "lq_scale_init_group_minmax": (_c_int, [_c_p, _c_p, _c_p, _c_i32, _c_i32, _c_int, _c_f, _c_i64, _c_i64, _c_int, _c_i64, _c_p]),
+    "lq_fq_forward_mx": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_i64, _c_i64, _c_int, _c_i64, _c_p]),
+    "lq_fq_backward_mx": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_f, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_int, _c_i64, _c_p]),
+    "lq_scale_init_mx": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_f, _c_i64, _c_i64, _c_int, _c_i64, _c_p]),
     "lq_group_stats": (_c_int, [_c_p, _c_p, _c_p, _c_i32, _c_i32, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_int, _c_i64,
                                 _c_p]),
     "lq_fq_fwd_bwd_fused": (_c_int, [_c_p, _c_p, _c_p, _c_f, _c_p, _c_p, _c_p, _c_sz, _c_i64, _c_i64, _c_i64, _c_p]),

@@ -398,6 +398,11 @@ class FakeQuantBatch:
         self.entries: List[_Entry] = []
         nested_layers = [getattr(layer, a) for layer in layers for a in ("nested_q_w_layer", "nested_q_k_layer", "nested_q_b_layer")
                          if hasattr(layer, a)]
+        mx = [n for n in nested_layers if getattr(n, "element_format", None) is not None]
+        if mx:
+            raise ValueError(f"FakeQuantBatch over a layer with an element format ({mx[0].element_format!r}): none of the multi-tensor "
+                             "batches (default, clipped, group) carries a minifloat grid; run such a model on the per-tensor path "
+                             "(batched=False)")
         kind = self._set_kind(clipped, group_batch, asymmetric)
         if not asymmetric and any(getattr(n, "asymmetric", False) for n in nested_layers):
             raise ValueError("FakeQuantBatch over an asymmetric layer: the offsets and their gradients travel only in the group "

@@ -30,6 +30,9 @@
 //
 // Every sum has one fixed order (lane's own rows or elements in ascending order, then slots 0 .. or the butterfly): run-to-run
 // bit-stable, no atomics, no second stage and therefore no workspace.  The forward is the same traversal without dy and sums.
+// What depends on the element grid -- the context of a group from its stored scale, the clamped grid value of a quotient, what the
+// integer view holds, the backward's term -- the bodies ask of GroupStep<RNE, PT>: the integer grid here, the minifloat grids of
+// the microscaling formats in lq_mx.hpp (k_group_mx_cols / k_group_mx_rows).
 // The kernels are wrappers that own the LDS and hand the body its block's coordinates: k_group_cols / k_group_rows and
 // k_group_affine_cols / k_group_affine_rows here (blockIdx.y strides over the groups, blockIdx.z shares a group's rows in the
 // forward) and the multi-tensor k_group_batch (lq_group_batch.hpp), so a tensor's bits do not depend on which launch carried it.
@@ -91,15 +94,29 @@ __device__ __forceinline__ float affine_bwd_one(float t, float dy, float lo, flo
     return ClipBwdOp<RNE>::one(t, dy, lo, hi, acc);
 }
 
+// The element step of a parameter struct: the context of a group from its stored scale, the clamped grid value of a quotient, what
+// the integer view holds for it, and the backward's term.  This one is the integer grid (GroupParams, GroupAffineParams and what
+// derives from them); lq_mx.hpp specialises it for the minifloat grids under a power-of-two scale.
+template <bool RNE, class PT>
+struct GroupStep {
+    __device__ static __forceinline__ Ctx ctx(const PT& pp, float s) { return group_ctx<RNE>(group_base(pp), s); }
+    __device__ static __forceinline__ float quant(const PT&, const Ctx& c, float t) { return ClipBase<RNE>::clampq(ClipBase<RNE>::rnd(t), c.k0, c.k1); }
+    __device__ static __forceinline__ float view(const PT&, float q) { return q; }
+    __device__ static __forceinline__ float bwd(const PT&, const Ctx& c, float t, float dy, Acc& acc) { return ClipBwdOp<RNE>::one(t, dy, c.k0, c.k1, acc); }
+};
+
 // one element: forward returns out and hands q to the integer view; backward returns dP and accumulates.  b, accb: AFF only
-template <bool RNE, bool BWD, bool AFF>
-__device__ __forceinline__ float group_elem(const GroupParams& p, const Ctx& c, float b, int64_t i, float t, float dy, Acc& acc, double& accb) {
+template <bool RNE, bool BWD, class PT>
+__device__ __forceinline__ float group_elem(const PT& pp, const Ctx& c, float b, int64_t i, float t, float dy, Acc& acc, double& accb) {
+    constexpr bool AFF = kGroupHasOffset<PT>;
+    using Step = GroupStep<RNE, PT>;
+    const GroupParams& p = group_base(pp);
     if constexpr (BWD) {
         if constexpr (AFF) return affine_bwd_one<RNE>(t, dy, c.k0, c.k1, acc, accb);
-        else return ClipBwdOp<RNE>::one(t, dy, c.k0, c.k1, acc);
+        else return Step::bwd(pp, c, t, dy, acc);
     } else {
-        const float q = ClipBase<RNE>::clampq(ClipBase<RNE>::rnd(t), c.k0, c.k1);
-        if (p.q) store_q(p.q, p.q_dtype, i, q);
+        const float q = Step::quant(pp, c, t);
+        if (p.q) store_q(p.q, p.q_dtype, i, Step::view(pp, q));
         const float m = q * c.s;
         if constexpr (AFF) return m + b;
         else return m;
@@ -137,14 +154,15 @@ __device__ __forceinline__ void group_cols_body(const PT& pp, const int64_t bx, 
         float b[V];
 #pragma unroll
         for (int k = 0; k < V; ++k) {
-            c[k] = group_ctx<RNE>(p, p.s[g * p.C + c0 + k]);
+            c[k] = GroupStep<RNE, PT>::ctx(pp, p.s[g * p.C + c0 + k]);
             if constexpr (AFF) b[k] = pp.b[g * p.C + c0 + k];
             else b[k] = 0.f;
         }
         // Two rows in flight, except in the backward with an offset: there they cost 106 VGPRs with the second f64 accumulator, 4
         // waves per SIMD instead of 6, and a second round of blocks on weight-sized tensors.
         // nz > 1 (forward only: nothing to merge) spreads the rows of a group over that many blocks
-#pragma unroll(AFF && BWD ? 1 : 2)
+        constexpr int kRowsInFlight = AFF && BWD ? 1 : 2;
+#pragma unroll kRowsInFlight
         for (int64_t r = r0 + zi * SLOTS + slot; r < r1; r += (int64_t)SLOTS * nz) {
             const int64_t i = r * p.C + c0;
             if constexpr (V == 4) {
@@ -155,17 +173,17 @@ __device__ __forceinline__ void group_cols_body(const PT& pp, const int64_t bx, 
                 if constexpr (AFF) t = fq_quot4c(make_float4(x.x - b[0], x.y - b[1], x.z - b[2], x.w - b[3]), c);
                 else t = fq_quot4c(x, c);
                 float4 o;
-                o.x = group_elem<RNE, BWD, AFF>(p, c[0], b[0], i + 0, t.x, dy.x, acc[0], accb[0]);
-                o.y = group_elem<RNE, BWD, AFF>(p, c[1], b[1], i + 1, t.y, dy.y, acc[1], accb[1]);
-                o.z = group_elem<RNE, BWD, AFF>(p, c[2], b[2], i + 2, t.z, dy.z, acc[2], accb[2]);
-                o.w = group_elem<RNE, BWD, AFF>(p, c[3], b[3], i + 3, t.w, dy.w, acc[3], accb[3]);
+                o.x = group_elem<RNE, BWD>(pp, c[0], b[0], i + 0, t.x, dy.x, acc[0], accb[0]);
+                o.y = group_elem<RNE, BWD>(pp, c[1], b[1], i + 1, t.y, dy.y, acc[1], accb[1]);
+                o.z = group_elem<RNE, BWD>(pp, c[2], b[2], i + 2, t.z, dy.z, acc[2], accb[2]);
+                o.w = group_elem<RNE, BWD>(pp, c[3], b[3], i + 3, t.w, dy.w, acc[3], accb[3]);
                 *reinterpret_cast<float4*>(p.out + i) = o;
             } else {
                 float u = p.P[i];
                 float dy = 0.f;
                 if constexpr (BWD) dy = p.dy[i];
                 if constexpr (AFF) u = u - b[0];
-                p.out[i] = group_elem<RNE, BWD, AFF>(p, c[0], b[0], i, div_by_uniform(u, c[0]), dy, acc[0], accb[0]);
+                p.out[i] = group_elem<RNE, BWD>(pp, c[0], b[0], i, div_by_uniform(u, c[0]), dy, acc[0], accb[0]);
             }
         }
     }
@@ -249,7 +267,7 @@ __device__ __forceinline__ void group_rows_body(const PT& pp, const int log_team
         const int64_t base = (int64_t)r * p.C;
         const int64_t c0 = (int64_t)g * p.gs;
         const int64_t c1 = (c0 + p.gs < p.C) ? c0 + p.gs : p.C;
-        const Ctx c = group_ctx<RNE>(p, p.s[pair]);
+        const Ctx c = GroupStep<RNE, PT>::ctx(pp, p.s[pair]);
         float b = 0.f;
         if constexpr (AFF) b = pp.b[pair];
         for (int64_t col = c0 + (int64_t)lt * V; col < c1; col += (int64_t)T * V) {      // V = 4: gs % 4 == 0 and C % 4 == 0
@@ -262,17 +280,17 @@ __device__ __forceinline__ void group_rows_body(const PT& pp, const int log_team
                 if constexpr (AFF) t = fq_quot4(make_float4(x.x - b, x.y - b, x.z - b, x.w - b), c);
                 else t = fq_quot4(x, c);
                 float4 o;
-                o.x = group_elem<RNE, BWD, AFF>(p, c, b, i + 0, t.x, dy.x, acc, accb);
-                o.y = group_elem<RNE, BWD, AFF>(p, c, b, i + 1, t.y, dy.y, acc, accb);
-                o.z = group_elem<RNE, BWD, AFF>(p, c, b, i + 2, t.z, dy.z, acc, accb);
-                o.w = group_elem<RNE, BWD, AFF>(p, c, b, i + 3, t.w, dy.w, acc, accb);
+                o.x = group_elem<RNE, BWD>(pp, c, b, i + 0, t.x, dy.x, acc, accb);
+                o.y = group_elem<RNE, BWD>(pp, c, b, i + 1, t.y, dy.y, acc, accb);
+                o.z = group_elem<RNE, BWD>(pp, c, b, i + 2, t.z, dy.z, acc, accb);
+                o.w = group_elem<RNE, BWD>(pp, c, b, i + 3, t.w, dy.w, acc, accb);
                 *reinterpret_cast<float4*>(p.out + i) = o;
             } else {
                 float u = p.P[i];
                 float dy = 0.f;
                 if constexpr (BWD) dy = p.dy[i];
                 if constexpr (AFF) u = u - b;
-                p.out[i] = group_elem<RNE, BWD, AFF>(p, c, b, i, div_by_uniform(u, c), dy, acc, accb);
+                p.out[i] = group_elem<RNE, BWD>(pp, c, b, i, div_by_uniform(u, c), dy, acc, accb);
             }
         }
     }

@@ -13,6 +13,7 @@
 //   lq_group.hpp        group-wise (block) scales, symmetric and with an offset: one traversal body per axis
 //   lq_group_batch.hpp  group-wise tensors in one launch per pass
 //   lq_scale_init.hpp   scales and offsets from the weights: absmax / LSQ / MSE / min-max on the group-wise unit shapes
+//   lq_mx.hpp           OCP microscaling element formats: the group-wise traversal bodies with a minifloat element step
 //   this file           host side: traversal plan, launchers, the extern "C" entry points
 //
 // The path is elementwise + per-group reductions: HBM-bound, no MFMA.  Design rules
@@ -55,6 +56,7 @@
 #include "lq_group.hpp"
 #include "lq_group_batch.hpp"
 #include "lq_scale_init.hpp"
+#include "lq_mx.hpp"
 #include "lq_group_stats.hpp"
 
 namespace lq {
@@ -1428,13 +1430,16 @@ static int launch_group_form(const GroupLaunch& L, void (*cols4)(Args), void (*c
     return LQ_OK;
 }
 
-// PT: GroupParams or GroupAffineParams.  The rounding is a template parameter of the kernels: none tests a flag
+// PT: GroupParams, GroupAffineParams or GroupMxParams.  The rounding is a template parameter of the kernels: none tests a flag
+// (a minifloat grid has one rounding: `rounding` is not read for GroupMxParams)
 template <bool BWD, class PT>
 static int launch_group(const PT& pp, int axis, bool vec, int rounding, void* stream) {
     const GroupLaunch L = group_launch(group_base(pp), axis, vec, !BWD, kGroupGridY);
     const bool rne = rounding == LQ_ROUND_NEAREST_EVEN;
     hipStream_t st = (hipStream_t)stream;
-    if constexpr (kGroupHasOffset<PT>) {
+    if constexpr (std::is_same_v<PT, GroupMxParams>) {
+        return launch_group_form(L, LQ_GROUP_FAMILY(k_group_mx_cols, k_group_mx_rows, BWD), pp, "microscaling", st);
+    } else if constexpr (kGroupHasOffset<PT>) {
         if (rne) return launch_group_form(L, LQ_GROUP_FAMILY(k_group_affine_cols, k_group_affine_rows, true, BWD), pp, "affine group-wise", st);
         return launch_group_form(L, LQ_GROUP_FAMILY(k_group_affine_cols, k_group_affine_rows, false, BWD), pp, "affine group-wise", st);
     } else {
@@ -1610,6 +1615,76 @@ int lq_scale_init_group_minmax(const float* P, float* s, float* b, int32_t qmin,
     ip.b = b;
     const bool vec = group_vec_ok(gp, axis) && aligned(P, 16);
     return launch_scale_init<kInitMinMax, false>(ip, gp, axis, vec, "min-max", stream);
+}
+
+// ---- OCP microscaling element formats under a power-of-two (or fp32) scale per group (lq_mx.hpp) ----
+struct MxFormat {
+    int32_t bits, M, emin, emax;
+    float mx;
+    uint32_t mm_frac;      // fraction bits of mx / 2^emax
+};
+static const MxFormat kMxFormats[] = {
+    {4, 1, 0, 2, 6.0f, 0x400000u},            // LQ_ELEM_FP4_E2M1
+    {6, 3, 0, 2, 7.5f, 0x700000u},            // LQ_ELEM_FP6_E2M3
+    {6, 2, -2, 4, 28.0f, 0x600000u},          // LQ_ELEM_FP6_E3M2
+    {8, 3, -6, 8, 448.0f, 0x600000u},         // LQ_ELEM_FP8_E4M3
+    {8, 2, -14, 15, 57344.0f, 0x600000u},     // LQ_ELEM_FP8_E5M2
+};
+
+static int check_mx(const char* fn, int format, int scale_format) {
+    if (format < LQ_ELEM_FP4_E2M1 || format > LQ_ELEM_FP8_E5M2) return fail(LQ_EINVAL, "%s: bad element format %d", fn, format);
+    if (scale_format != LQ_SCALE_E8M0 && scale_format != LQ_SCALE_FP32) return fail(LQ_EINVAL, "%s: bad scale format %d", fn, scale_format);
+    return LQ_OK;
+}
+
+static void mx_fill(GroupMxParams& mp, int format, int scale_format) {
+    const MxFormat& f = kMxFormats[format];
+    mp.g.lo = -f.mx;
+    mp.g.hi = f.mx;
+    mp.M = f.M;
+    mp.emin = f.emin;
+    mp.bits = f.bits;
+    mp.e8m0_mask = scale_format == LQ_SCALE_E8M0 ? ~0u : 0u;
+}
+
+int lq_fq_forward_mx(const float* P, const float* s, float* out, void* code, int code_dtype, int format, int scale_format,
+                     int64_t R, int64_t C, int axis, int64_t gs, void* stream) {
+    GroupMxParams mp{};
+    bool vec;
+    int rc = group_forward_setup(__func__, P, s, false, nullptr, out, code, code_dtype, 0, 0, LQ_ROUND_NEAREST_EVEN, R, C, axis, gs, mp.g, vec);
+    if (rc || (rc = check_mx(__func__, format, scale_format))) return rc;
+    mx_fill(mp, format, scale_format);
+    return launch_group<false>(mp, axis, vec, LQ_ROUND_NEAREST_EVEN, stream);
+}
+
+int lq_fq_backward_mx(const float* P, const float* s, const float* dy, int format, int scale_format, float grad_scale, float* dP,
+                      float* ds, uint32_t* clipped, int64_t R, int64_t C, int axis, int64_t gs, void* stream) {
+    GroupMxParams mp{};
+    bool vec;
+    int rc = group_backward_setup(__func__, P, s, false, nullptr, dy, 0, 0, LQ_ROUND_NEAREST_EVEN, grad_scale, dP, ds, nullptr, clipped,
+                                  R, C, axis, gs, mp.g, vec);
+    if (rc || (rc = check_mx(__func__, format, scale_format))) return rc;
+    mx_fill(mp, format, scale_format);
+    return launch_group<true>(mp, axis, vec, LQ_ROUND_NEAREST_EVEN, stream);
+}
+
+int lq_scale_init_mx(const float* P, float* s, int format, int method, float min_value, int64_t R, int64_t C, int axis, int64_t gs,
+                     void* stream) {
+    const char* fn = __func__;
+    int rc = check_group(fn, R, C, axis, gs);
+    if (rc) return rc;
+    LQ_REQUIRE_PTR_FN(fn, P);
+    LQ_REQUIRE_PTR_FN(fn, s);
+    if ((rc = check_mx(fn, format, LQ_SCALE_E8M0))) return rc;
+    if (method != LQ_MX_INIT_OCP && method != LQ_MX_INIT_COVER) return fail(LQ_EINVAL, "%s: bad method %d", fn, method);
+    if ((rc = check_init_min_value(fn, min_value))) return rc;
+    const GroupParams gp = group_params(P, s, 0, 0, R, C, axis, gs);
+    InitParams ip = init_params(gp, s, min_value);
+    ip.emax = kMxFormats[format].emax;
+    ip.mm_frac = kMxFormats[format].mm_frac;
+    const bool vec = group_vec_ok(gp, axis) && aligned(P, 16);
+    if (method == LQ_MX_INIT_OCP) return launch_scale_init<kInitMxOcp, false>(ip, gp, axis, vec, "microscaling scale-init", stream);
+    return launch_scale_init<kInitMxCover, false>(ip, gp, axis, vec, "microscaling scale-init", stream);
 }
 
 // ---- per-group statistics (lq_group_stats.hpp) ----

@@ -27,6 +27,9 @@ namespace lq {
 
 constexpr int kInitMinMax = 3;      // internal: lq_scale_init_group_minmax.  The public methods are lq_scale_init_method's
 static_assert(kInitMinMax != LQ_INIT_ABSMAX && kInitMinMax != LQ_INIT_LSQ && kInitMinMax != LQ_INIT_MSE, "method constants collide");
+// internal: lq_scale_init_mx's two rules (LQ_MX_INIT_OCP / LQ_MX_INIT_COVER).  They carry the absmax pair and differ in init_raw only
+constexpr int kInitMxOcp = 4;
+constexpr int kInitMxCover = 5;
 
 // One layout for every method.  Min-max's n, c and b lie in unions on the fields it does not read (the host writes only the members
 // of the method it launches): three more plain fields would grow the kernel argument, move log_team behind it and so change the
@@ -34,8 +37,8 @@ static_assert(kInitMinMax != LQ_INIT_ABSMAX && kInitMinMax != LQ_INIT_LSQ && kIn
 struct InitParams {
     const float* P;
     float* s;
-    union { float lo; float n; };      // (float)qmin | min-max: (float)(qmax - qmin), >= 1
-    union { float hi; float c; };      // (float)qmax | min-max: (qmin + qmax) / 2 (+ 1/2 for floor), exact
+    union { float lo; float n; int32_t emax; };          // (float)qmin | min-max: (float)(qmax - qmin), >= 1 | MX: the format's emax
+    union { float hi; float c; uint32_t mm_frac; };      // (float)qmax | min-max: (qmin + qmax) / 2 (+ 1/2 for floor), exact | MX: fraction bits of mx / 2^emax
     float min_value;      // > 0, finite
     union {
         double sqrt_qp;   // LQ_INIT_LSQ: sqrt((double)qp), taken on the host
@@ -96,6 +99,24 @@ __device__ __forceinline__ float init_raw(const InitParams& p, const InitAcc& a,
         return (float)(2.0 * a.sum / ((double)n * p.sqrt_qp));
     } else if constexpr (M == kInitMinMax) {
         return (a.f1 - a.f0) / p.n * kAbsmaxMargin;      // three roundings
+    } else if constexpr (M == kInitMxOcp || M == kInitMxCover) {
+        // A = m * 2^e, m in [1, 2): p = 2^(e - emax), one binade up under COVER when m exceeds the format's largest mantissa.
+        // Integer exponent arithmetic throughout; a subnormal A is normalised first
+        const uint32_t ab = __float_as_uint(fmaxf(a.f0, a.f1));
+        if (ab == 0u) return 0.f;                        // a group of zeros: init_final raises it to min_value
+        int e;
+        uint32_t frac;
+        if (ab < 0x00800000u) {
+            const int top = 31 - __clz((int)ab);         // 0 .. 22
+            e = top - 149;
+            frac = (ab << (23 - top)) & 0x7fffffu;
+        } else {
+            e = (int)(ab >> 23) - 127;
+            frac = ab & 0x7fffffu;
+        }
+        int pe = e - p.emax + ((M == kInitMxCover && frac > p.mm_frac) ? 1 : 0);
+        pe = max(pe, -126);                              // at most 127 - 2 + 1: every format has emax >= 2
+        return __uint_as_float((uint32_t)(pe + 127) << 23);
     } else {
         const float qa = p.hi > 0.f ? a.f0 / p.hi : 0.f;
         const float qb = p.lo < 0.f ? a.f1 / -p.lo : 0.f;

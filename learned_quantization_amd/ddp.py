@@ -218,6 +218,9 @@ class DataParallel:
         if mode == "B" and any(getattr(m, "q_range", None) is not None for m in module.modules()):
             raise ValueError("mode 'B' over a clipped layer (bits / q_range): it recomputes ds from the all-reduced dP, which no longer "
                              "holds the dy of the clipped elements; use mode 'A' (the gradients are ordinary tensors)")
+        if mode == "B" and any(getattr(m, "element_format", None) is not None for m in module.modules()):
+            raise ValueError("mode 'B' over a layer with an element format: it recomputes ds from the all-reduced dP, which no longer "
+                             "holds the dy of the saturated elements; use mode 'A' (the gradients are ordinary tensors)")
         self.module = module
         self.mode = mode
         self.group = group

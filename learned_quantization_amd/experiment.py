@@ -129,10 +129,15 @@ def build_parser():
                          "each output unit (replaces --orientation)")
     ap.add_argument("--asymmetric", action="store_true",
                     help="with --bits, --group-size and --scale-gradient ste: every group-wise kernel also learns an offset per group")
-    ap.add_argument("--scale-init", default=None, choices=["absmax", "lsq", "mse", "minmax"],
+    ap.add_argument("--element-format", default=None, choices=["fp4_e2m1", "fp6_e2m3", "fp6_e3m2", "fp8_e4m3", "fp8_e5m2"],
+                    help="with --scale-gradient ste (no --custom_loss, --bits, --rounding or --batched): OCP microscaling quantizer, "
+                         "elements on this minifloat grid under one scale per block of --group-size elements (default 32)")
+    ap.add_argument("--scale-format", default=None, choices=["e8m0", "fp32"],
+                    help="with --element-format: e8m0 (default; the scale is rounded to a power of two) or fp32")
+    ap.add_argument("--scale-init", default=None, choices=["absmax", "lsq", "mse", "minmax", "mx", "cover"],
                     help="with --bits: start every scale from its weights (after --baseline-weights are loaded) instead of the "
                          "library's initial value, which clips every weight; minmax (scale and offset from each group's minimum and "
-                         "maximum) with --asymmetric only")
+                         "maximum) with --asymmetric only; mx (the OCP rule) and cover (nothing saturates) with --element-format only")
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--steps-per-epoch", type=int, default=10)
     ap.add_argument("--batch", type=int, default=128)
@@ -176,7 +181,8 @@ def main(argv=None):
                  loss_log_capacity=max(4096, args.steps_per_epoch), bits=args.bits, rounding=args.rounding,
                  clipped_batch=args.clipped_batch, group_size=args.group_size,
                  group_batch=args.group_batch, scale_init=args.scale_init, asymmetric=args.asymmetric,
-                 asymmetric_batch=args.asymmetric_batch)
+                 asymmetric_batch=args.asymmetric_batch, element_format=args.element_format,
+                 scale_format=args.scale_format or "e8m0")
     if args.training == "post_training":
         if args.config != "mnist" or not args.baseline_weights:
             raise SystemExit("post_training needs --config mnist --baseline-weights <npz with W1,b1,W2,b2> "
@@ -194,8 +200,12 @@ def main(argv=None):
     log_model_structure(tr.model, log_dir)
     # the scale-tracking callback reads the unclipped integer view under one-axis scales: group-wise layers get the clipped
     # quantizer's own statistics instead (clipped shares, SQNR, codes in use), after the callbacks that were attached before
-    callbacks = [NestedScaleTrackingCallback(layer, log_dir) for layer in tr.custom_layers if layer.group_size is None]
-    group_callbacks = [GroupQuantTrackingCallback(layer, log_dir) for layer in tr.custom_layers if layer.group_size is not None]
+    # layers with an element format have neither: both callbacks read an integer view, and the statistics kernel bins the codes of
+    # an integer range.  Such a run keeps the accuracy / loss log and the exports
+    callbacks = [NestedScaleTrackingCallback(layer, log_dir) for layer in tr.custom_layers
+                 if layer.group_size is None and layer.element_format is None]
+    group_callbacks = [GroupQuantTrackingCallback(layer, log_dir) for layer in tr.custom_layers
+                       if layer.group_size is not None and layer.element_format is None]
     callbacks += group_callbacks
     callbacks.append(AccuracyLossTrackingCallBack(log_dir))
     t0 = time.perf_counter()
@@ -209,7 +219,9 @@ def main(argv=None):
         stats = callbacks[0].stats()
         line.update({"first_layer_unique_integers": stats["unique_k"], "first_layer_max_abs_q": float(stats["max_k"].max())})
     else:
-        line["group_size"] = args.group_size
+        line["group_size"] = tr.custom_layers[0].group_size
+        if tr.element_format is not None:
+            line.update({"element_format": tr.element_format, "scale_format": tr.scale_format})
         if group_callbacks:
             stats = group_callbacks[0].stats()["kernel"]
             line.update({"first_layer_sqnr_db": stats["sqnr_db"], "first_layer_clip_low": stats["clip_low"],

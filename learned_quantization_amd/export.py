@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .descriptor import group_geometry
+from .descriptor import group_geometry, init_geometry
 from .layers import CustomQuantizedScaleLayer, quantized_tensors      # the one walk both exports use
 
 
@@ -48,7 +48,10 @@ def quantized_state(model: torch.nn.Module) -> Dict[str, np.ndarray]:
 def _pack_source(param: torch.nn.Parameter, nested: CustomQuantizedScaleLayer):
     """(P, s) whose floor(P/s) is the integer the layer's quantizer produces.  Without a range: the parameter and its scale.  With
     one: the clamped integers themselves as floats over a unit scale (floor(q / 1) == q exactly, |q| <= 2^24), so that the range
-    scan and the packer see no integer outside the range even where floor(P/s) lies outside."""
+    scan and the packer see no integer outside the range even where floor(P/s) lies outside.  With an element format: the
+    elements' encodings, taken the same way over one unit scale."""
+    if getattr(nested, "element_format", None) is not None:
+        return nested.quantized_integers(param.data, torch.float32), torch.ones(1, dtype=torch.float32, device=param.device)
     if getattr(nested, "q_range", None) is None:
         return param.data, nested.scale.data
     if getattr(nested, "group_size", None) is not None:      # group-wise scales: the clamped integers over ONE unit scale
@@ -112,14 +115,56 @@ def _plain_state_keys(model: torch.nn.Module, tensors) -> List[str]:
     return [k for k in model.state_dict().keys() if k not in owned]
 
 
+def _mx_scales_to_store(tensors) -> Dict[str, np.ndarray]:
+    """{name: array} for the tensors with an element format: what the container holds as their scale -- under "e8m0" ONE uint8 per
+    group, the exponent of s_eff plus 127 (the E8M0 byte of an MX block); under "fp32" the scale itself.  ValueError naming the
+    tensor when a group has no valid scale or an element has no finite value (its code would stand for another value)."""
+    out, checks = {}, []
+    for name, param, nested in tensors:
+        if getattr(nested, "element_format", None) is None:
+            continue
+        s = _host(nested.scale)
+        eff = ops.mx_effective_scale(s, nested.scale_format)
+        if not (np.isfinite(eff) & (eff > 0)).all():
+            raise ValueError(f"{name}: {int((~(np.isfinite(eff) & (eff > 0))).sum())} groups have no valid {nested.scale_format} scale "
+                             "(not positive and finite, subnormal or beyond 2^127): cannot pack it")
+        out[name] = (eff.view(np.uint32) >> 23).astype(np.uint8) if nested.scale_format == "e8m0" else s
+        fq = ops.fq_forward_mx(param.data, nested.scale.data, nested.element_format, nested.group_size, nested.scale_format)
+        checks.append((name, (~torch.isfinite(fq)).sum()))
+    if checks:
+        for (name, _), n in zip(checks, torch.stack([c for _, c in checks]).tolist()):      # one device->host copy
+            if n:
+                raise ValueError(f"{name}: {n} elements have no finite value on the element grid (NaN or Inf in the parameter): their "
+                                 "NaN code cannot be told from a value's; cannot pack it")
+    return out
+
+
+def _mx_decode(param: torch.Tensor, q: torch.Tensor, s_eff: torch.Tensor, element_format: str, group_size):
+    """(P, codes) with the parameter's strides for the stored encodings ``q`` (int32, logical order) of a layer with an element
+    format: P = value(code) * s_eff, the value from the format's 2^bits-entry table, s_eff broadcast over its groups in the
+    parameter's memory order (a bias: one group)."""
+    R, C, axis, gs = init_geometry(tuple(param.shape), param.data.stride(), tuple(s_eff.shape), group_size)
+    qs = torch.empty_like(param.data, dtype=torch.int32).copy_(q)
+    pr = torch.empty_like(param.data)
+    gs = min(gs, R if axis == 0 else C)
+    nb = -(-(R if axis == 0 else C) // gs)
+    sx = s_eff.reshape((nb, C) if axis == 0 else (R, nb)).repeat_interleave(gs, dim=axis)[:R, :C]
+    table = torch.from_numpy(ops.mx_decode_table(element_format)).to(param.device)
+    torch.as_strided(pr, (R, C), (C, 1)).copy_(table[torch.as_strided(qs, (R, C), (C, 1)).long()] * sx)
+    return pr, qs
+
+
 def save_packed_parameters(model: torch.nn.Module, log_dir: str) -> Dict[str, float]:
     """Writes weights_packed.npz (manifest, codes, scales, state), weights_packed.zip and packed_sizes.log next to the
     reference export (which it does not touch); returns {"packed_mb", "zip_mb", "bits_per_weight"}.  Raises ValueError naming
-    the tensor when an integer cannot be stored exactly (NaN, Inf, |q| beyond int32); then no file is written."""
+    the tensor when an integer cannot be stored exactly (NaN, Inf, |q| beyond int32); then no file is written.
+    A tensor with an element format is stored as its encodings, packed at the format's 4 / 6 / 8 bits, with ``element_format``,
+    ``scale_format`` and ``group_size`` in its manifest entry and its scales as ``_mx_scales_to_store`` gives them."""
     tensors = quantized_tensors(model)
     if not tensors:
         raise ValueError("the model has no quantized tensor to pack")
     dev = tensors[0][1].device
+    mx_scales = _mx_scales_to_store(tensors)
     ranges = torch.empty((len(tensors), 2), dtype=torch.int32, device=dev)
     sources = [_pack_source(param, nested) for _, param, nested in tensors]
     for k, (src, unit) in enumerate(sources):
@@ -127,6 +172,8 @@ def save_packed_parameters(model: torch.nn.Module, log_dir: str) -> Dict[str, fl
     lohi = ranges.tolist()                                      # every range in one device->host copy
     entries = []
     for (name, param, nested), (lo, hi) in zip(tensors, lohi):
+        if name in mx_scales:      # every code of the format has its place: 0 .. 2^bits - 1
+            lo, hi = 0, (1 << ops.check_element_format(nested.element_format).bits) - 1
         if lo > hi:
             raise ValueError(f"{name}: floor(P/s) has no finite integer (NaN/Inf or beyond int32): cannot pack it")
         entries.append({"name": name, "shape": list(param.shape), "scale_shape": list(nested.scale.shape),
@@ -138,6 +185,8 @@ def save_packed_parameters(model: torch.nn.Module, log_dir: str) -> Dict[str, fl
             entries[-1]["group_size"] = int(nested.group_size)
         if getattr(nested, "asymmetric", False):                 # nor symmetric layers: the offset array sits behind the scale
             entries[-1]["asymmetric"] = True
+        if name in mx_scales:                                    # nor layers without an element format
+            entries[-1].update({"element_format": nested.element_format, "scale_format": nested.scale_format})
     bad = torch.zeros(len(tensors), dtype=torch.int64, device=dev)
     words = [ops.q_pack(src, unit, qmin=e["qmin"], bits=e["bits"], bad=bad[k:k + 1])[0]
              for k, ((src, unit), e) in enumerate(zip(sources, entries))]
@@ -150,7 +199,7 @@ def save_packed_parameters(model: torch.nn.Module, log_dir: str) -> Dict[str, fl
     arrays = {"manifest": _manifest_bytes(manifest)}
     for (name, _, nested), e, w in zip(tensors, entries, words):
         arrays[name + ".codes"] = w.cpu().numpy().view(np.uint32)
-        arrays[name + ".scale"] = _host(nested.scale)
+        arrays[name + ".scale"] = mx_scales[name] if name in mx_scales else _host(nested.scale)
         if e.get("asymmetric"):
             arrays[name + ".offset"] = _host(nested.offset)
     for key in state_keys:
@@ -208,6 +257,9 @@ def _check_packed(model: torch.nn.Module, manifest: dict, z, tensors, state_keys
         if bool(e.get("asymmetric", False)) != bool(getattr(nested, "asymmetric", False)):      # a missing key means symmetric
             raise ValueError(f"{name}: asymmetric {bool(e.get('asymmetric', False))} in the container, "
                              f"{bool(getattr(nested, 'asymmetric', False))} in the model")
+        for key in ("element_format", "scale_format"):      # a missing key means an integer layer
+            if e.get(key) != getattr(nested, key, None):
+                raise ValueError(f"{name}: {key} {e.get(key)!r} in the container, {getattr(nested, key, None)!r} in the model")
         if list(e.get("scale_shape", [])) != list(nested.scale.shape):
             raise ValueError(f"{name}: scale shape {e.get('scale_shape')} in the container, {list(nested.scale.shape)} in the model")
         if e.get("orientation") != nested.orientation:
@@ -225,8 +277,12 @@ def _check_packed(model: torch.nn.Module, manifest: dict, z, tensors, state_keys
         if codes is None or codes.dtype != np.uint32 or codes.shape != (ops.packed_words(numel, bits),):
             raise ValueError(f"{name}: codes missing or not {ops.packed_words(numel, bits)} uint32 words")
         sc = z[name + ".scale"] if name + ".scale" in z.files else None
-        if sc is None or sc.dtype != np.float32 or list(sc.shape) != list(nested.scale.shape):
-            raise ValueError(f"{name}: scale missing or not float32 {list(nested.scale.shape)}")
+        sc_dtype = np.uint8 if e.get("scale_format") == "e8m0" else np.float32
+        if sc is None or sc.dtype != sc_dtype or list(sc.shape) != list(nested.scale.shape):
+            raise ValueError(f"{name}: scale missing or not {np.dtype(sc_dtype).name} {list(nested.scale.shape)}")
+        if e.get("element_format") is not None and (bits != ops.check_element_format(e["element_format"]).bits or qmin != 0):
+            raise ValueError(f"{name}: {e['element_format']} codes are stored at {ops.check_element_format(e['element_format']).bits} "
+                             f"bits from 0, the container says {bits} bits from {qmin}")
         if e.get("asymmetric"):
             off = z[name + ".offset"] if name + ".offset" in z.files else None
             if off is None or off.dtype != np.float32 or list(off.shape) != list(nested.scale.shape):
@@ -267,6 +323,9 @@ def load_packed_parameters(model: torch.nn.Module, path: str) -> dict:
     A group-wise layer is restored the same way with its scale broadcast over the groups, and always verified through its own view.
     An asymmetric layer takes P = (q + 1/2) * s + b (floor) or q * s + b (nearest) and is verified through the affine forward; a
     container and a model that disagree on ``asymmetric`` raise.
+    A layer with an element format takes P = value(code) * s_eff (the value from the format's decode table) and s = s_eff, and its
+    own code view of that P is compared with the stored codes on the device; a container and a model that disagree on the element
+    format, the scale format or the group size raise.
     Format, version, names, shapes, orientations and roundings are checked first: on a mismatch, or a restored value that does
     not round back, ValueError is raised and the model is left untouched.  Returns the manifest."""
     if os.path.isdir(path):
@@ -287,8 +346,18 @@ def load_packed_parameters(model: torch.nn.Module, path: str) -> dict:
     outside = torch.zeros(1, dtype=torch.int64, device=dev)      # nearest layers: stored integers beyond the model layer's range
     restored = []
     for (name, param, nested), e in zip(tensors, manifest["tensors"]):
-        s = torch.from_numpy(scales[name]).to(dev)
         w = torch.from_numpy(codes[name].view(np.int32)).to(dev)
+        if e.get("element_format") is not None:
+            sc = scales[name]
+            s = torch.from_numpy((sc.astype(np.uint32) << 23).view(np.float32) if sc.dtype == np.uint8 else sc).to(dev)
+            unit = torch.ones(1, dtype=torch.float32, device=dev)
+            _, q, _ = ops.q_unpack(w, 0, e["bits"], unit, param.shape, want_out=False, want_restore=False)
+            pr, qs = _mx_decode(param, q, s, e["element_format"], e.get("group_size"))
+            view = ops.fq_forward_mx(pr, s, e["element_format"], e.get("group_size"), e["scale_format"], q_dtype=torch.int32)[1]
+            bad += (view != qs).sum()
+            restored.append((param, nested, s, pr, None))
+            continue
+        s = torch.from_numpy(scales[name]).to(dev)
         if e.get("group_size") is not None:
             # P = (q + 1/2) * s (floor) or q * s (nearest) with the scale broadcast over its groups in the parameter's memory
             # order; the layer's own group-wise integer view of that P is compared with q on the device
@@ -319,7 +388,7 @@ def load_packed_parameters(model: torch.nn.Module, path: str) -> dict:
         raise ValueError(f"{noutside} stored integers lie outside the integer range of their layer in the model (the container was "
                          "written by a model with a wider range): model left untouched")
     if nbad:
-        raise ValueError(f"{nbad} restored values do not round back to their stored integer (|q| >= 2^22): model left untouched")
+        raise ValueError(f"{nbad} restored values do not round back to their stored integer (|q| >= 2^22) or code: model left untouched")
     with torch.no_grad():
         for param, nested, s, pr, off in restored:
             param.data.copy_(pr)                               # into the parameter's own storage (HWIO or OIHW order)

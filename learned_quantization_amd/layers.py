@@ -142,6 +142,13 @@ class CustomQuantizedScaleLayer(nn.Module):
     layer also owns ``offset``, a Parameter of the scale's shape (zeros), and quantises ``clamp(rnd((P - b) / s)) * s + b``
     (ops.fq_forward_group_affine / fq_backward_group_affine): a group's grid need not be centred on zero.  The offset is stepped
     like a scale (``lq_is_scale``) but has no lower bound (no ``lq_constraint``); ``lq_is_offset`` tells it apart.
+    ``element_format="fp4_e2m1" | ...`` (one of ops.ELEMENT_FORMATS; not in the reference) -> the OCP microscaling quantizer
+    (ops.fq_forward_mx / fq_backward_mx): the elements lie on that minifloat grid under one scale per group, with
+    ``scale_format="e8m0"`` (the default) the stored scale rounded to a power of two, with "fp32" the scale as it is.  It needs
+    ``orientation="groupwise"`` (``group_size`` defaults to 32, the MX block) -- or "scalar", the one-group form the host layers
+    give their biases -- and takes neither a range, a rounding, an offset nor a loss term; the gradients are the straight-through
+    ones (``scale_gradient`` is "ste").  ``init_scale`` takes "mx" / "cover" (ops.scale_init_mx), ``quantized_integers`` returns
+    the elements' encodings, ``quant_stats`` is not available.
     """
 
     _SCALE_NAMES = {"rowwise": "Rowwise-scaler", "columnwise": "Columnwise-scaler",
@@ -150,13 +157,19 @@ class CustomQuantizedScaleLayer(nn.Module):
 
     def __init__(self, penalty_threshold=None, initializer=None, orientation="scalar", *, penalty_rate=None,
                  scale_gradient=None, grad_scale=1.0, bits=None, signed=True, q_range=None, rounding="floor", group_size=None,
-                 asymmetric=False):
+                 asymmetric=False, element_format=None, scale_format="e8m0"):
         super().__init__()
+        self.element_format = self.scale_format = None
+        if element_format is not None:
+            group_size = check_element_layer(element_format, scale_format, orientation, group_size, bits, signed, q_range, rounding,
+                                             asymmetric, penalty_threshold, penalty_rate, scale_gradient, bias=orientation == "scalar")
+            self.element_format, self.scale_format, scale_gradient = element_format, scale_format, "ste"
         self.q_range = ops.q_range_of(bits, signed, q_range)
         ops.check_rounding(rounding, self.q_range is not None)
         self.rounding = rounding
         self.asymmetric = check_asymmetric(asymmetric, orientation, self.q_range, penalty_threshold, penalty_rate, scale_gradient)
-        self.group_size = check_groupwise(orientation, group_size, self.q_range, penalty_threshold, penalty_rate)
+        self.group_size = group_size if element_format is not None else \
+            check_groupwise(orientation, group_size, self.q_range, penalty_threshold, penalty_rate)
         if self.q_range is not None and penalty_threshold is not None:
             raise ValueError("a clipped layer (bits / q_range) needs penalty_threshold=None: the nested-quantization vote is "
                              "defined on the unclipped quantizer")
@@ -207,6 +220,12 @@ class CustomQuantizedScaleLayer(nn.Module):
     def call(self, inputs):
         if not self.built:
             self.build(tuple(inputs.shape), device=inputs.device)
+        if self.element_format is not None:
+            if self.defer_scale_grad:
+                raise ValueError("a layer with an element format with defer_scale_grad (data-parallel mode B): the all-reduced dP no "
+                                 "longer holds the dy of its saturated elements, so ds cannot be recomputed from it")
+            return ops.my_custom_gradient(inputs, self.scale, grad_scale=self.grad_scale_value(inputs.numel()),
+                                          group_size=self.group_size, element_format=self.element_format, scale_format=self.scale_format)
         if self.asymmetric:
             if self.defer_scale_grad:
                 raise ValueError("an asymmetric layer with defer_scale_grad (data-parallel mode B): the all-reduced dP of a clipped "
@@ -240,6 +259,8 @@ class CustomQuantizedScaleLayer(nn.Module):
             r += f", group_size={self.group_size}"
         if self.asymmetric:
             r += ", asymmetric=True"
+        if self.element_format is not None:
+            r += f", element_format={self.element_format!r}, scale_format={self.scale_format!r}"
         return r
 
     def init_scale(self, parameter, method):
@@ -247,7 +268,19 @@ class CustomQuantizedScaleLayer(nn.Module):
         the layer's range, rounding and group size and the ``min_value`` of its constraint.  The unbounded quantizer has nothing
         to cover: ValueError without a range.  One launch, no synchronisation.
         An asymmetric layer also takes "minmax" (ops.scale_init_group_minmax: scale and offset from each group's minimum and
-        maximum); under the other methods its scale is written as a symmetric layer's and its offset is set to zero."""
+        maximum); under the other methods its scale is written as a symmetric layer's and its offset is set to zero.
+        A layer with an element format takes "mx" (the OCP rule) and "cover" (nothing saturates) instead: ops.scale_init_mx."""
+        if self.element_format is not None:
+            ops.check_mx_scale_init(method)
+            if not self.built:
+                self.build(tuple(parameter.shape), device=parameter.device)
+            with torch.no_grad():
+                ops.scale_init_mx(parameter.detach(), self.scale.data, self.element_format, self.group_size, method,
+                                  min_value=self.constraint.min_value)
+            return self.scale
+        if method in ops.MX_SCALE_INITS:
+            raise ValueError(f"scale_init {method!r} on a layer without an element format: it writes the power-of-two scale of a "
+                             f"microscaling block; an integer layer takes one of {ops.LAYER_SCALE_INITS}")
         ops.check_layer_scale_init(method)
         if method == "minmax":
             if not self.asymmetric:
@@ -278,6 +311,9 @@ class CustomQuantizedScaleLayer(nn.Module):
         ops.summarize_stats.  One launch, no synchronisation.  A layer without a range clips nothing and has no fixed set of
         codes: ValueError; its statistics are ops.q_minmax, ops.q_unique and ops.q_absmax_over_axis
         (tracking.NestedScaleTrackingCallback)."""
+        if self.element_format is not None:
+            raise ValueError("quant_stats on a layer with an element format: the statistics kernel bins the codes of an integer range; "
+                             "a microscaling layer has none (its saturation counts are ops.fq_backward_mx's `clipped`)")
         if self.q_range is None:
             raise ValueError("quant_stats needs bits or q_range: the unbounded quantizer clips nothing and has no fixed set of codes; "
                              "its statistics are ops.q_minmax / ops.q_unique / ops.q_absmax_over_axis "
@@ -290,7 +326,10 @@ class CustomQuantizedScaleLayer(nn.Module):
 
     def quantized_integers(self, parameter, dtype=torch.float32):
         """The integer view of ``parameter`` under this layer's quantizer: floor(P/s), clamped when the layer has a range (then
-        rint(P/s) for ``rounding="nearest"``)."""
+        rint(P/s) for ``rounding="nearest"``).  With an element format: the elements' encodings (the code view)."""
+        if self.element_format is not None:
+            return ops.fq_forward_mx(parameter, self.scale.data, self.element_format, self.group_size, self.scale_format,
+                                     q_dtype=dtype)[1]
         if self.q_range is None:
             return ops.quantized_integers(parameter, self.scale.data, dtype)
         if self.asymmetric:
@@ -322,6 +361,43 @@ def check_asymmetric(asymmetric, orientation, q_range, penalty_threshold=None, p
     return True
 
 
+def check_element_layer(element_format, scale_format, orientation, group_size, bits=None, signed=True, q_range=None, rounding="floor",
+                        asymmetric=False, penalty_threshold=None, penalty_rate=None, scale_gradient="ste", bias=False):
+    """The group size of a layer with an ``element_format`` (None for ``bias``, the scalar one-group form), or ValueError naming
+    what does not go with a microscaling format."""
+    ops.check_element_format(element_format)
+    ops.check_scale_format(scale_format)
+    if bits is not None or q_range is not None or not signed:
+        raise ValueError(f"element_format={element_format!r} with bits / q_range / signed: an element format brings its own grid, "
+                         "range and sign")
+    if rounding != "floor":
+        raise ValueError(f"element_format={element_format!r} with rounding={rounding!r}: a minifloat grid rounds to nearest, ties to "
+                         "even, and nothing else; leave rounding at its default")
+    if asymmetric:
+        raise ValueError(f"element_format={element_format!r} with asymmetric=True: the microscaling formats are symmetric, a block "
+                         "has a scale and no offset")
+    if penalty_threshold is not None:
+        raise ValueError(f"element_format={element_format!r} with a penalty_threshold: the nested-quantization vote is defined on "
+                         "the unclipped integer quantizer")
+    if penalty_rate is not None:
+        raise ValueError(f"element_format={element_format!r} with a loss term (penalty_rate): the penalty kernels know the integer "
+                         "quantizer with one-axis scales only")
+    if scale_gradient not in (None, "ste"):
+        raise ValueError(f'element_format={element_format!r} needs scale_gradient="ste", got {scale_gradient!r}')
+    if bias:
+        if orientation != "scalar" or group_size is not None:
+            raise ValueError("the bias of a layer with an element format is one group under a scalar scale")
+        return None
+    if orientation != "groupwise":
+        raise ValueError(f'element_format={element_format!r} needs orientation="groupwise", got orientation={orientation!r}: a '
+                         "microscaling scale belongs to a block of consecutive elements")
+    if group_size is None:
+        return ops.MX_GROUP_SIZE
+    if isinstance(group_size, bool) or int(group_size) != group_size or int(group_size) < 1:
+        raise ValueError(f"group_size must be an integer >= 1, got {group_size!r}")
+    return int(group_size)
+
+
 def check_groupwise(orientation, group_size, q_range, penalty_threshold=None, penalty_rate=None):
     """The ``group_size`` of a layer as an int (None for the reference's orientations), or ValueError naming the reason."""
     if orientation != "groupwise":
@@ -343,11 +419,12 @@ def check_groupwise(orientation, group_size, q_range, penalty_threshold=None, pe
 
 
 def _nested(penalty_threshold, penalty_rate, orientation, scale_gradient=None, grad_scale=1.0, q_range=None, rounding="floor",
-            group_size=None, asymmetric=False):
+            group_size=None, asymmetric=False, element_format=None, scale_format="e8m0"):
     return CustomQuantizedScaleLayer(penalty_threshold=penalty_threshold, initializer=None,
                                      orientation=orientation, penalty_rate=penalty_rate,
                                      scale_gradient=scale_gradient, grad_scale=grad_scale, q_range=q_range,
-                                     rounding=rounding, group_size=group_size, asymmetric=asymmetric)
+                                     rounding=rounding, group_size=group_size, asymmetric=asymmetric,
+                                     element_format=element_format, scale_format=scale_format)
 
 
 def _as_tensor(a, shape, device):
@@ -362,9 +439,46 @@ class _HostLayer(nn.Module):
     rounding = "floor"
     group_size = None
     asymmetric = False
+    element_format = None
+    scale_format = None
+
+    def _element_args(self, element_format, scale_format, orientation, group_size, bits, signed, q_range, rounding, asymmetric,
+                      penalty_threshold, penalty_rate, scale_gradient):
+        """Constructor half of ``element_format``: checks it against everything else and returns the group size (unchanged without
+        a format)."""
+        if element_format is None:
+            return group_size
+        gs = check_element_layer(element_format, scale_format, orientation, group_size, bits, signed, q_range, rounding, asymmetric,
+                                 penalty_threshold, penalty_rate, scale_gradient)
+        self.element_format, self.scale_format = element_format, scale_format
+        return gs
+
+    def _nested_quantizers(self):
+        return [getattr(self, n) for n in ("nested_q_k_layer", "nested_q_w_layer", "nested_q_b_layer") if hasattr(self, n)]
+
+    def make_mx(self, element_format, scale_format="e8m0", group_size=None):
+        """Switches both quantizers of a constructed layer to the microscaling ``element_format``: the kernel / ``W`` group-wise
+        with ``group_size`` (32 by default), the bias as one group under its scalar scale; rebuilds the weight's scale
+        (models.build_model applies it after construction)."""
+        conv = hasattr(self, "nested_q_k_layer")
+        nested = self.weight_nested()
+        gs = check_element_layer(element_format, scale_format, "groupwise", group_size, None, True, self.q_range, self.rounding,
+                                 self.asymmetric, nested.penalty_threshold, nested.penalty_rate, nested.scale_gradient)
+        if conv and self.kernel_storage != "oihw":
+            raise ValueError(f'element_format={element_format!r} with kernel_storage="hwio": the blocks are defined in the '
+                             'convolution\'s memory order (the contiguous (ci, kh, kw) run of an output channel); store the kernel "oihw"')
+        self.element_format, self.scale_format, self.group_size = element_format, scale_format, gs
+        for n in self._nested_quantizers():
+            n.element_format, n.scale_format, n.scale_gradient = element_format, scale_format, "ste"
+        nested.group_size, nested.orientation = gs, "groupwise"
+        if nested.built:
+            param = self.kernel if conv else self.W
+            nested.build(tuple(param.shape), device=param.device)
 
     def extra_repr(self):
         r = f"q_range={self.q_range!r}" if self.q_range is not None else ""
+        if self.element_format is not None:
+            r += f"element_format={self.element_format!r}, scale_format={self.scale_format!r}"
         if self.rounding != "floor":
             r += f", rounding={self.rounding!r}"
         if self.group_size is not None:
@@ -412,6 +526,16 @@ class _HostLayer(nn.Module):
 
     def init_scales(self, method):
         """``CustomQuantizedScaleLayer.init_scale`` for the kernel / ``W`` and the bias of a built layer."""
+        if self.element_format is not None:
+            ops.check_mx_scale_init(method)
+            if not self.built:
+                raise ValueError(f"{self.name}: scale initialisation reads the weights; build the layer first")
+            for _, nested, param in self.scale_pairs():
+                nested.init_scale(param, method)
+            return
+        if method in ops.MX_SCALE_INITS:
+            raise ValueError(f"{self.name}: scale_init {method!r} on a layer without an element format: it writes the power-of-two "
+                             f"scale of a microscaling block; an integer layer takes one of {ops.LAYER_SCALE_INITS}")
         ops.check_layer_scale_init(method)
         if method == "minmax" and not self.asymmetric:
             raise ValueError(f'{self.name}: scale_init "minmax" on a symmetric layer: it places each group\'s range over [min, max] '
@@ -449,18 +573,22 @@ class CustomDenseLayer(_HostLayer):
     def __init__(self, seed=None, units=None, penalty_threshold=None, orientation="scalar", initializer=None,
                  name=None, regularizer=None, trained_weights=None, *, penalty_rate=None, input_shape=None,
                  device=None, scale_gradient=None, grad_scale=1.0, bits=None, signed=True, q_range=None, rounding="floor",
-                 group_size=None, asymmetric=False, **kwargs):
+                 group_size=None, asymmetric=False, element_format=None, scale_format="e8m0", **kwargs):
         super().__init__()
         self.seed = seed
+        group_size = self._element_args(element_format, scale_format, orientation, group_size, bits, signed, q_range, rounding,
+                                        asymmetric, penalty_threshold, penalty_rate, scale_gradient)
         self.q_range = ops.q_range_of(bits, signed, q_range)      # None: the reference's unbounded quantizer
         ops.check_rounding(rounding, self.q_range is not None)
         self.rounding = rounding
         self.asymmetric = check_asymmetric(asymmetric, orientation, self.q_range, penalty_threshold, penalty_rate, scale_gradient)
         # groupwise: groups along `in` for every output column, scale (nb, out); the bias keeps its scalar scale
-        self.group_size = check_groupwise(orientation, group_size, self.q_range, penalty_threshold, penalty_rate)
+        self.group_size = group_size if element_format is not None else \
+            check_groupwise(orientation, group_size, self.q_range, penalty_threshold, penalty_rate)
         self.nested_q_w_layer = _nested(penalty_threshold, penalty_rate, orientation, scale_gradient, grad_scale, self.q_range, rounding,
-                                        self.group_size, self.asymmetric)   # NQ-L:222-224
-        self.nested_q_b_layer = _nested(penalty_threshold, penalty_rate, "scalar", scale_gradient, grad_scale, self.q_range, rounding)      # NQ-L:225-227
+                                        self.group_size, self.asymmetric, element_format, scale_format)   # NQ-L:222-224
+        self.nested_q_b_layer = _nested(penalty_threshold, penalty_rate, "scalar", scale_gradient, grad_scale, self.q_range, rounding,
+                                        element_format=element_format, scale_format=scale_format)      # NQ-L:225-227
         self.units = units
         self.initializer = initializer
         self.regularizer = regularizer
@@ -549,9 +677,11 @@ class _ConvBase(_HostLayer):
                  kernel_size=(3, 3), strides=(1, 1), padding="same", name=None, regularizer=None,
                  trained_weights=None, *, penalty_rate=None, input_shape=None, data_format="NCHW", device=None,
                  kernel_storage=None, scale_gradient=None, grad_scale=1.0, bits=None, signed=True, q_range=None, rounding="floor",
-                 group_size=None, asymmetric=False, **kwargs):
+                 group_size=None, asymmetric=False, element_format=None, scale_format="e8m0", **kwargs):
         super().__init__()
         self.seed = seed
+        group_size = self._element_args(element_format, scale_format, orientation, group_size, bits, signed, q_range, rounding,
+                                        asymmetric, penalty_threshold, penalty_rate, scale_gradient)
         self.q_range = ops.q_range_of(bits, signed, q_range)      # None: the reference's unbounded quantizer
         ops.check_rounding(rounding, self.q_range is not None)
         self.rounding = rounding
@@ -562,14 +692,16 @@ class _ConvBase(_HostLayer):
             raise ValueError("kernel_storage must be 'oihw' or 'hwio'")
         self.kernel_storage = kernel_storage
         # groupwise: groups along the (ci, kh, kw) memory run of every output channel, scale (co, nb); the bias stays scalar
-        self.group_size = check_groupwise(orientation, group_size, self.q_range, penalty_threshold, penalty_rate)
+        self.group_size = group_size if element_format is not None else \
+            check_groupwise(orientation, group_size, self.q_range, penalty_threshold, penalty_rate)
         if self.group_size is not None and kernel_storage != "oihw":
             raise ValueError('orientation="groupwise" with kernel_storage="hwio": the groups are defined in the convolution\'s memory '
                              'order (the contiguous (ci, kh, kw) run of an output channel); store the kernel "oihw"')
         self.nested_q_k_layer = _nested(penalty_threshold, penalty_rate, orientation, scale_gradient, grad_scale, self.q_range, rounding,
-                                        self.group_size, self.asymmetric)      # NQ-L:293-295
+                                        self.group_size, self.asymmetric, element_format, scale_format)      # NQ-L:293-295
         if self._has_bias:
-            self.nested_q_b_layer = _nested(penalty_threshold, penalty_rate, "scalar", scale_gradient, grad_scale, self.q_range, rounding)     # NQ-L:296-298
+            self.nested_q_b_layer = _nested(penalty_threshold, penalty_rate, "scalar", scale_gradient, grad_scale, self.q_range, rounding,
+                                            element_format=element_format, scale_format=scale_format)     # NQ-L:296-298
         self.initializer = initializer
         self.filters = filters
         self.kernel_size = _pair(kernel_size)
@@ -694,8 +826,9 @@ def quant_stats(model: nn.Module, want_hist=True) -> dict:
     """{reference name: summary} of every quantized tensor of ``model`` (``quantized_tensors``' walk): the
     ops.summarize_stats dict of the tensor's ``CustomQuantizedScaleLayer.quant_stats``.  One launch per tensor, then all records
     go to the host together in one copy (one synchronisation: call it between steps, never inside a capture).  Every layer
-    needs a range: ValueError otherwise."""
-    tensors = quantized_tensors(model)
+    needs a range: ValueError otherwise.  Tensors of layers with an element format are skipped: the statistics kernel bins the
+    codes of an integer range."""
+    tensors = [t for t in quantized_tensors(model) if t[2].element_format is None]
     for name, _, nested in tensors:      # before any launch
         if nested.q_range is None:
             raise ValueError(f"quant_stats: the quantizer of {name!r} has no range (bits / q_range); the unbounded quantizer's "
@@ -711,9 +844,20 @@ def init_scales(model: nn.Module, method) -> nn.Module:
     """Initialises every scale of every custom layer of ``model`` from its weights (``_HostLayer.init_scales``; ``method`` one of
     ops.SCALE_INITS), then checks all scales with ONE ``isfinite`` reduction -- one synchronisation: this is a host call made
     once, before the optimizer and any graph exist, never inside a capture.  A NaN scale (a weight tensor that holds a NaN or
-    an Inf) raises ValueError with the layer's name.  The scales are written in place: pointers taken before stay valid."""
-    ops.check_layer_scale_init(method)
+    an Inf) raises ValueError with the layer's name.  The scales are written in place: pointers taken before stay valid.
+    A model of layers with an element format takes "mx" / "cover" (ops.MX_SCALE_INITS) and none of the others; a model without
+    them takes none of these two."""
     layers = custom_layers_of(model)
+    mx = [layer for layer in layers if layer.element_format is not None]
+    if mx:
+        if method not in ops.MX_SCALE_INITS:
+            raise ValueError(f"scale_init {method!r} on a model with element formats ({mx[0].name!r}: {mx[0].element_format!r}): a "
+                             f"microscaling scale is a power of two, written by one of {ops.MX_SCALE_INITS}")
+    elif method in ops.MX_SCALE_INITS:
+        raise ValueError(f"scale_init {method!r} on a model without element formats: it writes the power-of-two scale of a "
+                         f"microscaling block; an integer model takes one of {ops.LAYER_SCALE_INITS}")
+    else:
+        ops.check_layer_scale_init(method)
     if method == "minmax":      # before any launch: every layer must be able to take it
         for layer in layers:
             if not layer.asymmetric:

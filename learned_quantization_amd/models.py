@@ -314,8 +314,39 @@ def check_asymmetric_model(mode: str, has_range: bool, group_size, kernel_storag
                          'memory order; store the kernel "oihw"')
 
 
+MX_MODES = ("ste",)
+
+
+def check_mx_model(mode: str, bits=None, signed=True, q_range=None, rounding="floor", asymmetric=False, kernel_storage=None,
+                   scale_init=None) -> None:
+    """A model with an element format trains in mode "ste", on conv kernels in the convolution's memory order, and takes neither an
+    integer range, a rounding, offsets nor an integer scale initialisation."""
+    from .ops import MX_SCALE_INITS
+    if bits is not None or q_range is not None or not signed:
+        raise ValueError("element_format with bits / q_range / signed: an element format brings its own grid, range and sign")
+    if rounding != "floor":
+        raise ValueError(f"element_format with rounding={rounding!r}: a minifloat grid rounds to nearest, ties to even, and nothing "
+                         "else; leave rounding at its default")
+    if asymmetric:
+        raise ValueError("element_format with asymmetric=True: the microscaling formats are symmetric, a block has a scale and no offset")
+    if mode in ("cl", "stecl", "nqcl"):
+        raise ValueError(f"element_format with mode {mode!r}: the loss-term penalty kernels know the integer quantizer with one-axis "
+                         f"scales only; a model with an element format trains with one of the modes {MX_MODES}")
+    if mode == "nq":
+        raise ValueError(f"element_format with mode {mode!r}: the nested-quantization vote is defined on the unclipped integer "
+                         f"quantizer; a model with an element format trains with one of the modes {MX_MODES}")
+    if mode not in MX_MODES:
+        raise ValueError(f"element_format with mode {mode!r}: a model with an element format trains with one of the modes {MX_MODES}")
+    if kernel_storage == "hwio":
+        raise ValueError('element_format with kernel_storage="hwio": the blocks are defined in the convolution\'s memory order; store '
+                         'the kernel "oihw"')
+    if scale_init is not None and scale_init not in MX_SCALE_INITS:
+        raise ValueError(f"scale_init {scale_init!r} on a model with an element format: a microscaling scale is a power of two, "
+                         f"written by one of {MX_SCALE_INITS}")
+
+
 def build_model(config: str, kernel_storage: str = None, grad_scale=None, bits=None, signed=True, q_range=None, rounding="floor",
-                group_size=None, scale_init=None, asymmetric=False, **kw) -> nn.Module:
+                group_size=None, scale_init=None, asymmetric=False, element_format=None, scale_format="e8m0", **kw) -> nn.Module:
     """config: 'mnist' (C1), 'cifar' (C2/C4), 'imagenette' (C3), 'resnet50' (C5, extension).
     ``kernel_storage``: memory order of the conv kernels, "oihw" (default) or "hwio" (layers.py).
     ``grad_scale`` (modes "ste" / "stecl"): factor of every straight-through scale gradient, a float or "rsqrt_group".
@@ -328,8 +359,25 @@ def build_model(config: str, kernel_storage: str = None, grad_scale=None, bits=N
     (layers.init_scales) instead of the library's initial value, applied after the ranges and group sizes are in place.
     ``asymmetric`` (with ``group_size``, mode "ste"): every group-wise kernel also learns an offset per group (layers.py
     ``asymmetric=True``); biases stay symmetric.  ``scale_init="minmax"`` exists for such models only: scale and offset of every
-    group from its minimum and maximum, biases by "absmax"."""
+    group from its minimum and maximum, biases by "absmax".
+    ``element_format`` (one of ops.ELEMENT_FORMATS; mode "ste") with ``scale_format`` ("e8m0" / "fp32"): the OCP microscaling
+    quantizer for every quantised tensor (layers.py ``element_format=``): kernels in blocks of ``group_size`` (32 by default),
+    biases as one group.  It replaces ``orientation`` and takes no range, rounding or offsets; ``scale_init`` is "mx" or "cover"."""
     from .ops import check_rounding
+    if element_format is not None:
+        from .layers import _HostLayer, init_scales
+        from .ops import check_element_format, check_scale_format
+        check_element_format(element_format)
+        check_scale_format(scale_format)
+        check_mx_model(kw.get("mode", "nq"), bits, signed, q_range, rounding, asymmetric, kernel_storage, scale_init)
+        model = build_model(config, kernel_storage=kernel_storage, grad_scale=grad_scale, **{**kw, "orientation": "scalar"})
+        for m in model.modules():
+            if isinstance(m, _HostLayer):
+                m.make_mx(element_format, scale_format, group_size)
+        return model if scale_init is None else init_scales(model, scale_init)
+    if scale_init in ("mx", "cover"):
+        raise ValueError(f"scale_init {scale_init!r} on a model without an element format: it writes the power-of-two scale of a "
+                         "microscaling block")
     check_rounding(rounding, bits is not None or q_range is not None)
     if asymmetric:
         check_asymmetric_model(kw.get("mode", "nq"), bits is not None or q_range is not None, group_size, kernel_storage)

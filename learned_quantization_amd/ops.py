@@ -359,7 +359,144 @@ def scale_init_group_minmax(parameter: torch.Tensor, scale: torch.Tensor, offset
     return scale, offset
 
 
-STATS_MAX_BINS = 4096      # include/lq_hip.h, lq_group_stats: the widest range whose codes it bins
+# --------------------------------------------------------------------------- OCP microscaling element formats
+class ElementFormat(NamedTuple):
+    """One row of include/lq_hip.h's lq_elem_format table."""
+    id: int
+    bits: int
+    E: int
+    M: int
+    emin: int
+    emax: int
+    max: float
+
+
+ELEMENT_FORMATS = {
+    "fp4_e2m1": ElementFormat(0, 4, 2, 1, 0, 2, 6.0),
+    "fp6_e2m3": ElementFormat(1, 6, 2, 3, 0, 2, 7.5),
+    "fp6_e3m2": ElementFormat(2, 6, 3, 2, -2, 4, 28.0),
+    "fp8_e4m3": ElementFormat(3, 8, 4, 3, -6, 8, 448.0),       # OCP e4m3fn
+    "fp8_e5m2": ElementFormat(4, 8, 5, 2, -14, 15, 57344.0),   # OCP e5m2
+}
+SCALE_FORMATS = ("e8m0", "fp32")       # include/lq_hip.h: LQ_SCALE_E8M0, LQ_SCALE_FP32
+MX_SCALE_INITS = ("mx", "cover")       # include/lq_hip.h: LQ_MX_INIT_OCP, LQ_MX_INIT_COVER
+MX_GROUP_SIZE = 32                     # the block of the OCP MX formats: the default group size of a layer with an element format
+
+
+def check_element_format(element_format) -> ElementFormat:
+    """The table row of ``element_format``, or ValueError: one of ELEMENT_FORMATS."""
+    if not isinstance(element_format, str) or element_format not in ELEMENT_FORMATS:
+        raise ValueError(f"element_format must be one of {tuple(ELEMENT_FORMATS)}, got {element_format!r}")
+    return ELEMENT_FORMATS[element_format]
+
+
+def check_scale_format(scale_format) -> int:
+    """The C ABI's value of ``scale_format``, or ValueError: one of SCALE_FORMATS."""
+    if scale_format not in SCALE_FORMATS:
+        raise ValueError(f"scale_format must be one of {SCALE_FORMATS}, got {scale_format!r}")
+    return SCALE_FORMATS.index(scale_format)
+
+
+def check_mx_scale_init(method) -> int:
+    """The C ABI's value of a microscaling scale-initialisation ``method``, or ValueError: one of MX_SCALE_INITS."""
+    if method not in MX_SCALE_INITS:
+        raise ValueError(f"scale_init of a layer with an element format must be one of {MX_SCALE_INITS}, got {method!r}")
+    return MX_SCALE_INITS.index(method)
+
+
+def mx_decode_table(element_format) -> np.ndarray:
+    """float32 [2^bits]: the value of every code of ``element_format`` (include/lq_hip.h, "Code view"); the fp8 formats hold NaN
+    (fp8_e4m3: S.1111.111) and +-Inf / NaN (fp8_e5m2: the top exponent) where OCP defines them."""
+    f = check_element_format(element_format)
+    codes = np.arange(1 << f.bits)
+    mag = codes & ((1 << (f.bits - 1)) - 1)
+    ef, mf = mag >> f.M, mag & ((1 << f.M) - 1)
+    val = np.where(ef == 0, mf * 2.0 ** (f.emin - f.M), (1.0 + mf / 2.0 ** f.M) * np.exp2((ef - 1 + f.emin).astype(np.float64)))
+    if element_format == "fp8_e4m3":
+        val = np.where(mag == 127, np.nan, val)
+    if element_format == "fp8_e5m2":
+        val = np.where(ef == 31, np.where(mf == 0, np.inf, np.nan), val)
+    return (np.where(codes >> (f.bits - 1), -1.0, 1.0) * val).astype(np.float32)
+
+
+def mx_effective_scale(scale: np.ndarray, scale_format) -> np.ndarray:
+    """Host restatement of s_eff (include/lq_hip.h): float32 in the shape of ``scale``; NaN marks an E8M0 scale that is not
+    positive, normal and finite or that rounds past 2^127.  For the exports, which read the scales on the host anyway."""
+    check_scale_format(scale_format)
+    s = np.ascontiguousarray(scale, np.float32)
+    if scale_format == "fp32":
+        return s
+    b = s.view(np.uint32).astype(np.uint64)
+    nb = (b + 0x004AFB0D) & 0x7F800000
+    ok = (b >= 0x00800000) & (b < 0x7F800000) & (nb < 0x7F800000)
+    return np.where(ok, nb.astype(np.uint32).view(np.float32), np.float32(np.nan)).astype(np.float32)
+
+
+def _mx_param(parameter: torch.Tensor, scale: torch.Tensor, group_size: Optional[int]):
+    """(P, s, (R, C, axis, gs)): a group-wise scale matrix with its ``group_size``, or (``group_size=None``) a one-axis or scalar
+    scale whose groups are lines of the parameter's memory -- a bias is one group (descriptor.init_geometry)."""
+    p = _hip.require_device_f32(parameter, "parameter", dense_ok=True)
+    s = _hip.require_device_f32(scale, "scale")
+    return p, s, init_geometry(tuple(p.shape), p.stride(), tuple(s.shape), group_size)
+
+
+def fq_forward_mx(parameter: torch.Tensor, scale: torch.Tensor, element_format: str, group_size: Optional[int] = MX_GROUP_SIZE,
+                  scale_format: str = "e8m0", q_dtype: Optional[torch.dtype] = None):
+    """Microscaling forward (include/lq_hip.h, lq_fq_forward_mx): every element rounded to the ``element_format`` minifloat grid
+    (ties to even, saturating at the format's max) under its group's scale -- rounded to a power of two for
+    ``scale_format="e8m0"``, as it is for "fp32".  Returns ``out`` (the parameter's strides), or ``(out, code)`` with the
+    elements' encodings when ``q_dtype`` is given."""
+    fmt = check_element_format(element_format)
+    sf = check_scale_format(scale_format)
+    lib = _hip.load()
+    p, s, (R, C, axis, gs) = _mx_param(parameter, scale, group_size)
+    out = torch.empty_like(p)
+    q, qd = _q_buffer(p, q_dtype)
+    _hip.check(lib.lq_fq_forward_mx(_hip.ptr(p), _hip.ptr(s), _hip.ptr(out), _hip.ptr(q), qd, fmt.id, sf, R, C, axis, gs,
+                                    _hip.stream_ptr(p.device)), "lq_fq_forward_mx")
+    return out if q is None else (out, q)
+
+
+def fq_backward_mx(parameter: torch.Tensor, scale: torch.Tensor, dy: torch.Tensor, element_format: str,
+                   group_size: Optional[int] = MX_GROUP_SIZE, scale_format: str = "e8m0", grad_scale: float = 1.0,
+                   want_ds: bool = True, want_clipped: bool = False):
+    """Microscaling backward (include/lq_hip.h, lq_fq_backward_mx).  Returns ``(dP, ds, clipped)`` as ``fq_backward_group`` does:
+    dP = dy where the element is inside the format's range and +0 where it saturates; ds (shape of scale) the straight-through
+    gradient of the stored scale; clipped the count of saturated elements per group (int32 tensor holding the uint32 counts)."""
+    fmt = check_element_format(element_format)
+    sf = check_scale_format(scale_format)
+    lib = _hip.load()
+    p, s, (R, C, axis, gs) = _mx_param(parameter, scale, group_size)
+    d = _hip.require_device_f32(dy, "dy", like=p)
+    dP = torch.empty_like(p)
+    ds = torch.empty_like(s) if want_ds else None
+    clipped = torch.empty_like(s, dtype=torch.int32) if want_clipped else None
+    _hip.check(lib.lq_fq_backward_mx(_hip.ptr(p), _hip.ptr(s), _hip.ptr(d), fmt.id, sf, float(grad_scale), _hip.ptr(dP),
+                                     _hip.ptr(ds), _hip.ptr(clipped), R, C, axis, gs, _hip.stream_ptr(p.device)),
+               "lq_fq_backward_mx")
+    return dP, ds, clipped
+
+
+def scale_init_mx(parameter: torch.Tensor, scale: torch.Tensor, element_format: str, group_size: Optional[int] = MX_GROUP_SIZE,
+                  method: str = "mx", min_value: float = SCALE_INIT) -> torch.Tensor:
+    """Writes ``scale`` IN PLACE from ``parameter`` (include/lq_hip.h, lq_scale_init_mx): per group a power of two, "mx" the OCP
+    rule 2^(floor(log2 absmax) - emax) (the largest elements may saturate), "cover" the smallest power of two under which none
+    does; never below ``min_value``.  A group that holds a NaN or an Inf gets NaN.  One launch.  Returns ``scale``."""
+    fmt = check_element_format(element_format)
+    m = check_mx_scale_init(method)
+    min_value = float(min_value)
+    if not (min_value > 0.0 and math.isfinite(min_value)):
+        raise ValueError(f"min_value must be a positive finite number, got {min_value!r}")
+    p, s, (R, C, axis, gs) = _mx_param(parameter, scale, group_size)
+    if s is not scale:
+        raise ValueError("scale must be contiguous: it is written in place")
+    lib = _hip.load()
+    _hip.check(lib.lq_scale_init_mx(_hip.ptr(p), _hip.ptr(s), fmt.id, m, min_value, R, C, axis, gs, _hip.stream_ptr(p.device)),
+               "lq_scale_init_mx")
+    return scale
+
+
+STATS_MAX_BINS = 4096     # include/lq_hip.h, lq_group_stats: the widest range whose codes it bins
 
 
 class GroupStats(NamedTuple):
@@ -889,11 +1026,29 @@ class _GroupAffineQuantFn(torch.autograd.Function):
         return (dP if ctx.needs_input_grad[0] else None), ds, db, None, None, None, None, None
 
 
+class _MxQuantFn(torch.autograd.Function):
+    """``_GroupQuantFn`` on a microscaling element grid: forward lq_fq_forward_mx, backward lq_fq_backward_mx.  ``group_size`` None:
+    a one-axis or scalar scale (a bias: one group)."""
+
+    @staticmethod
+    def forward(ctx, parameter, scale, element_format, scale_format, group_size, grad_scale):
+        ctx.save_for_backward(parameter, scale)
+        ctx.mx = (element_format, group_size, scale_format)
+        ctx.grad_scale = float(grad_scale)
+        return fq_forward_mx(parameter, scale, element_format, group_size, scale_format)
+
+    @staticmethod
+    def backward(ctx, dy):
+        parameter, scale = ctx.saved_tensors
+        dP, ds, _ = fq_backward_mx(parameter, scale, dy, *ctx.mx, grad_scale=ctx.grad_scale, want_ds=ctx.needs_input_grad[1])
+        return (dP if ctx.needs_input_grad[0] else None), ds, None, None, None, None
+
+
 SCALE_GRADIENTS = (None, "ste")
 
 
 def my_custom_gradient(parameter, scale, penalty_threshold=None, *, scale_gradient=None, grad_scale=1.0, defer_scale_grad=False,
-                       q_range=None, rounding="floor", group_size=None, offset=None):
+                       q_range=None, rounding="floor", group_size=None, offset=None, element_format=None, scale_format="e8m0"):
     """The reference op.  With ``penalty_threshold`` -> nested-quantization variant
     (custom_layers.py:49-120); without -> STE-only variant (CL custom_layers.py:49-64).
     ``scale_gradient="ste"`` (not in the reference, only without ``penalty_threshold``): the scale receives the
@@ -909,7 +1064,30 @@ def my_custom_gradient(parameter, scale, penalty_threshold=None, *, scale_gradie
     (descriptor.groupwise_scale_shape): one scale per ``gs`` elements along one axis of the parameter's memory.
     ``offset=b`` (not in the reference, only with ``group_size`` and ``scale_gradient="ste"``): the asymmetric quantizer
     ``clamp(rnd((P - b) / s)) * s + b`` with one learned offset per group (``b`` has the scale's shape); gradients go to the
-    parameter, the scale and the offset (LSQ+: the sum of dy over the group's clipped elements, times ``grad_scale``)."""
+    parameter, the scale and the offset (LSQ+: the sum of dy over the group's clipped elements, times ``grad_scale``).
+    ``element_format=F`` (not in the reference; one of ops.ELEMENT_FORMATS): the OCP microscaling quantizer -- elements on the
+    minifloat grid of ``F`` under one scale per group, a power of two for ``scale_format="e8m0"`` (the default) or the scale as it
+    is for "fp32".  ``scale`` is a group-wise matrix with its ``group_size``, or with ``group_size=None`` a scalar or one-axis
+    scale (a bias: one group).  Gradients are the straight-through ones (``scale_gradient`` may be left out or "ste")."""
+    if element_format is not None:
+        check_element_format(element_format)
+        check_scale_format(scale_format)
+        if penalty_threshold is not None:
+            raise ValueError("element_format with a penalty_threshold: the nested-quantization vote is defined on the unclipped "
+                             "integer quantizer")
+        if q_range is not None:
+            raise ValueError("element_format with a q_range: an element format brings its own grid and range")
+        if rounding != "floor":
+            raise ValueError("element_format with a rounding: a minifloat grid rounds to nearest, ties to even, and nothing else")
+        if offset is not None:
+            raise ValueError("element_format with an offset: the microscaling formats are symmetric")
+        if scale_gradient not in (None, "ste"):
+            raise ValueError(f'element_format needs scale_gradient="ste", got {scale_gradient!r}')
+        if defer_scale_grad:
+            raise ValueError("element_format with defer_scale_grad: the all-reduced dP of a saturating layer no longer holds the dy "
+                             "of its saturated elements, so ds cannot be recomputed from it")
+        return _MxQuantFn.apply(parameter, scale, element_format, scale_format, None if group_size is None else int(group_size),
+                                float(grad_scale))
     if offset is not None:
         if group_size is None:
             raise ValueError("offset needs a group_size: the asymmetric quantizer exists for group-wise scales only (a group_size "

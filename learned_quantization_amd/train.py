@@ -30,8 +30,9 @@ from . import layers as L
 from . import _hip
 from .ddp import CaptureRefused, DataParallel, capture_with_agreement, control_group
 from .losses import LossLog, SCCEDifference, SCCEInverse, SCCEMaxBin, sparse_categorical_crossentropy
-from .models import INPUT_SHAPES, build_model, check_asymmetric_model, check_clip_mode, check_group_mode
-from .ops import LAYER_SCALE_INITS, ROUNDINGS, check_minmax_range, check_rounding, q_range_of
+from .models import INPUT_SHAPES, build_model, check_asymmetric_model, check_clip_mode, check_group_mode, check_mx_model
+from .ops import (ELEMENT_FORMATS, LAYER_SCALE_INITS, MX_SCALE_INITS, ROUNDINGS, SCALE_FORMATS, check_element_format, check_minmax_range,
+                  check_rounding, check_scale_format, q_range_of)
 from .optim import KerasAdam, ScaleAdam, non_scale_parameters, scale_parameters
 
 LOSSES = {"maxbin": SCCEMaxBin, "difference": SCCEDifference, "inverse": SCCEInverse}
@@ -74,8 +75,12 @@ class Trainer:
                  force_collectives: bool = False, kernel_storage: str = "oihw", loss_values: bool = False,
                  loss_log_capacity: int = 4096, grad_scale=None, bits=None, signed=True, q_range=None, rounding="floor",
                  clipped_batch: bool = False, group_size=None, group_batch: bool = False, scale_init=None, asymmetric: bool = False,
-                 asymmetric_batch: bool = False):
-        """``asymmetric`` (with ``group_size``, a range and mode "ste"; eager, graphed and data-parallel mode "A"; per-tensor path
+                 asymmetric_batch: bool = False, element_format=None, scale_format="e8m0"):
+        """``element_format`` (one of ops.ELEMENT_FORMATS; mode "ste"; eager, graphed and data-parallel mode "A"; per-tensor path
+        only) with ``scale_format`` ("e8m0", the default, or "fp32"): the OCP microscaling quantizer for every quantised tensor
+        (models.build_model): kernels in blocks of ``group_size`` (32 by default), biases as one group.  It takes no range,
+        rounding, offsets or batch; ``scale_init`` is "mx" (the OCP rule) or "cover" (nothing saturates).
+        ``asymmetric`` (with ``group_size``, a range and mode "ste"; eager, graphed and data-parallel mode "A"; per-tensor path
         unless ``asymmetric_batch``): every group-wise kernel also learns an offset per group (models.build_model); the offsets
         are stepped by the scales' optimizer, without a lower bound.  ``scale_init="minmax"`` exists for such models only.
         ``asymmetric_batch`` (opt-in, with ``asymmetric``, ``group_batch`` and ``batched``; eager, graphed, data-parallel mode
@@ -112,6 +117,20 @@ class Trainer:
         ste = mode in ("ste", "stecl")
         self.group_size = group_size
         self.asymmetric = bool(asymmetric)
+        self.element_format, self.scale_format = element_format, (scale_format if element_format is not None else None)
+        if element_format is not None:
+            check_element_format(element_format)
+            check_scale_format(scale_format)
+            check_mx_model(mode, bits, signed, q_range, rounding, asymmetric, kernel_storage, scale_init)
+            if batched or clipped_batch or group_batch or asymmetric_batch:
+                raise ValueError("element_format with batched=True: none of the multi-tensor batches (default, clipped, group) carries "
+                                 "a minifloat grid; a model with an element format runs on the per-tensor path")
+            if ddp_mode == "B":
+                raise ValueError("element_format with ddp_mode 'B': it recomputes ds from the all-reduced dP, which no longer holds "
+                                 "the dy of the saturated elements; use ddp_mode 'A'")
+        elif scale_init in MX_SCALE_INITS:
+            raise ValueError(f"scale_init {scale_init!r} on a model without an element format: it writes the power-of-two scale of a "
+                             "microscaling block")
         if asymmetric:
             check_asymmetric_model(mode, bits is not None or q_range is not None, group_size, kernel_storage)
             if batched and not asymmetric_batch:
@@ -130,7 +149,7 @@ class Trainer:
                 raise ValueError('scale_init "minmax" on a symmetric model: it places each group\'s range over [min, max] through an '
                                  "offset, which only asymmetric=True layers have")
             check_minmax_range(*q_range_of(bits, signed, q_range))
-        if group_size is not None:
+        if group_size is not None and element_format is None:
             check_group_mode(mode, bits is not None or q_range is not None)
             if batched and (not group_batch or clipped_batch):
                 raise ValueError("group_size with batched=True: the multi-tensor batch describes every tensor by one-axis "
@@ -171,11 +190,12 @@ class Trainer:
         # fake-quantised kernel goes to the convolution as written and its weight gradient is dP
         self.model = build_model(config, mode=mode, value=value, seed=seed, orientation=orientation, device=self.device,
                                  kernel_storage=kernel_storage, grad_scale=grad_scale, q_range=self.q_range, rounding=rounding,
-                                 group_size=group_size, asymmetric=self.asymmetric)
+                                 group_size=group_size, asymmetric=self.asymmetric, element_format=element_format,
+                                 scale_format=scale_format)
         self.model.to(self.device)
         self.scale_init = scale_init
         if scale_init is not None:
-            if self.q_range is None:
+            if self.q_range is None and element_format is None:
                 raise ValueError("scale_init needs bits / q_range: the unbounded quantizer clips nothing, there is no range to cover")
             L.init_scales(self.model, scale_init)
         self.custom_layers = L.custom_layers_of(self.model)
@@ -465,6 +485,20 @@ class DriverParser(argparse.ArgumentParser):
                                                            and getattr(ns, "batched", False)):
             self.error("--asymmetric-batch needs --asymmetric, --group-batch and --batched: it lets the group batch carry the "
                        "offsets of an asymmetric model")
+        if getattr(ns, "element_format", None) is None:
+            if getattr(ns, "scale_init", None) in MX_SCALE_INITS:
+                self.error("--scale-init mx / cover needs --element-format: it writes the power-of-two scale of a microscaling block")
+            if getattr(ns, "scale_format", None) is not None:
+                self.error("--scale-format needs --element-format")
+        else:
+            for flag, bad in (("--bits", getattr(ns, "bits", None) is not None), ("--unsigned", getattr(ns, "unsigned", False)),
+                              ("--rounding", getattr(ns, "rounding", "floor") != "floor"), ("--asymmetric", getattr(ns, "asymmetric", False)),
+                              ("--batched", getattr(ns, "batched", False))):
+                if bad:
+                    self.error(f"--element-format with {flag}: an element format brings its own grid, range and rounding, has no "
+                               "offsets and runs on the per-tensor path")
+            if getattr(ns, "scale_init", None) not in (None,) + MX_SCALE_INITS:
+                self.error("--element-format takes --scale-init mx or cover: a microscaling scale is a power of two")
         if getattr(ns, "scale_init", None) == "minmax" and not getattr(ns, "asymmetric", False):
             self.error("--scale-init minmax needs --asymmetric: it places each group's range over [min, max] through an offset, "
                        "which a symmetric layer does not have")
@@ -489,7 +523,12 @@ def build_parser():
     ap.add_argument("--asymmetric", action="store_true",
                     help="with --bits, --group-size and mode ste: every group-wise kernel also learns an offset per group (per-tensor "
                          "path unless --asymmetric-batch; biases stay symmetric)")
-    ap.add_argument("--scale-init", default=None, choices=list(LAYER_SCALE_INITS),
+    ap.add_argument("--element-format", default=None, choices=list(ELEMENT_FORMATS),
+                    help="mode ste: OCP microscaling quantizer, elements on this minifloat grid under one scale per block of "
+                         "--group-size elements (default 32); replaces --orientation, --bits and --rounding; biases are one block")
+    ap.add_argument("--scale-format", default=None, choices=list(SCALE_FORMATS),
+                    help="with --element-format: e8m0 (default; the scale is rounded to a power of two) or fp32")
+    ap.add_argument("--scale-init", default=None, choices=list(LAYER_SCALE_INITS + MX_SCALE_INITS),
                     help="with --bits: start every scale from its weights (absmax: nothing clipped; lsq: 2 mean|w| / sqrt(Qp); mse: "
                          "least squared error below absmax; minmax, with --asymmetric only: scale and offset from each group's "
                          "minimum and maximum) instead of the library's initial value, which clips every weight")
@@ -579,7 +618,8 @@ def main(argv=None):
                              (args.grad_scale if args.grad_scale == "rsqrt_group" else float(args.grad_scale))),
                  bits=args.bits, signed=not args.unsigned, rounding=args.rounding, clipped_batch=args.clipped_batch,
                  group_size=args.group_size, group_batch=args.group_batch, scale_init=args.scale_init,
-                 asymmetric=args.asymmetric, asymmetric_batch=args.asymmetric_batch)
+                 asymmetric=args.asymmetric, asymmetric_batch=args.asymmetric_batch, element_format=args.element_format,
+                 scale_format=args.scale_format or "e8m0")
     do_step = tr.step_graphed if args.graph else tr.step
     g = torch.Generator(device=dev).manual_seed(args.seed + rank)
     batches = [synthetic_batch(args.config, args.batch, dev, g) for _ in range(4)]
@@ -609,7 +649,8 @@ def main(argv=None):
             "metric": "images/sec end-to-end training step (synthetic data)", "config": args.config, "mode": args.mode,
             "value": world * args.batch * args.steps / dt, "unit": "images/s", "n_gpus": world,
             "ms_per_step": dt / args.steps * 1e3, "per_gpu_batch": args.batch,
-            "orientation": ("groupwise" if args.group_size is not None else args.orientation),
+            "orientation": ("groupwise" if args.group_size is not None or tr.element_format is not None else args.orientation),
+            **({"element_format": tr.element_format, "scale_format": tr.scale_format} if tr.element_format is not None else {}),
             "loss_term": args.loss, "quantized_elements": n_q, "final_loss": float(loss.detach()), "ddp_mode": args.ddp_mode,
             "hipgraph": bool(args.graph), "graph_collectives": bool(tr.graph_collectives and args.graph and use_dist),
             **({"graph_note": tr.graph_note} if tr.graph_note else {}), "batched": bool(args.batched),
@@ -620,7 +661,8 @@ def main(argv=None):
             "channels_last": bool(args.channels_last), "kernel_storage": args.kernel_storage,
             **({"q_range": list(tr.q_range)} if tr.q_range else {}),
             **({"rounding": tr.rounding} if tr.rounding != "floor" else {}),
-            **({"group_size": tr.group_size} if tr.group_size is not None else {}),
+            **({"group_size": tr.custom_layers[0].group_size if tr.element_format is not None else tr.group_size}
+               if tr.group_size is not None or tr.element_format is not None else {}),
             **({"asymmetric": True} if tr.asymmetric else {}),
             **({"scale_init": tr.scale_init} if tr.scale_init is not None else {}),
             **({"loss_values": True, "loss_log_rows": log_rows[0], "loss_log_dropped": log_rows[1]} if log_rows else {}),

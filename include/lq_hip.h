@@ -598,6 +598,30 @@ typedef struct lq_group_offset {
 int lq_group_batch_create_affine(const lq_group_desc* descs, const lq_group_offset* offs /* [n] or NULL */,
                                  int n, int rounding, lq_group_batch** out);
 
+/* ---- microscaling (MX) tensors in the batch ----
+ * lq_group_batch_create_mx builds the same kind of batch from the same descriptors plus, per tensor, an element format and a
+ * scale format: tensor i is lq_fq_forward_mx / lq_fq_backward_mx (the definition stated in "OCP microscaling (MX) element
+ * formats" above) with fmts[i].  The format lives in the device-resident task table, per tensor: one batch may hold tensors of
+ * different element formats and scale formats.  qmin / qmax of a descriptor are not read (the range is the format's +-max) and
+ * there is no rounding argument (a minifloat grid has one rounding, ties to even).  A 1-D parameter with a scalar scale (a bias)
+ * is the one-group line R = 1, C = numel, axis = 1, gs = numel, as in lq_fq_*_mx.
+ * The handle is an lq_group_batch: _forward, _backward, _clip_counts (the counts are the saturation counts), _workspace_bytes
+ * (still 0: no workspace is used) and _destroy serve it unchanged, ONE launch per pass.  Each tensor takes the form the
+ * single-tensor MX call takes for the same geometry and alignment.
+ * out, dP, the saturation counts AND ds of every tensor are bit-identical to lq_fq_forward_mx / lq_fq_backward_mx on the same
+ * buffers with the same grad_scale: a block runs the same code on the same unit of work.  No encodings are written (the batch
+ * has no `code` output).
+ * Backward: the dy rules of lq_group_batch_backward hold (a NULL entry: LQ_EINVAL; an entry off the 16-byte grid for a tensor
+ * whose backward uses 16-byte accesses: LQ_EALIGN, before any launch); grad_scale == NULL stays "mask only": no ds is written.
+ * Refused before the first HIP call, in addition to everything lq_group_batch_create refuses (its range checks aside): a NULL
+ * fmts, an unknown format or scale_format (LQ_EINVAL).  The message names the tensor.
+ * create is a HOST call (allocates and uploads: never inside a capture); both passes only enqueue and can be captured.  */
+typedef struct lq_group_mx_format {
+    int32_t format;        /* lq_elem_format  */
+    int32_t scale_format;  /* lq_scale_format */
+} lq_group_mx_format;
+int lq_group_batch_create_mx(const lq_group_desc* descs, const lq_group_mx_format* fmts /* [n] */, int n, lq_group_batch** out);
+
 /* VALUE of the custom-loss-term penalty for the whole batch (compute_{maxbin,difference,inverse}_penalty,
  *   custom_loss_functions.py:75-116, 161-195, 240-275), the number compute_total_loss adds to the cross-entropy (:47-58).
  * Per-tensor term t_i as in lq_penalty_{maxbin,difference,inverse}_fwd; the model penalty in the reference's order (:102-116):

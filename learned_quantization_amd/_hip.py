@@ -144,9 +144,15 @@ class GroupOffset(ctypes.Structure):
     _fields_ = [("b", _c_p), ("db", _c_p), ("offset_grad_scale", _c_f)]
 
 
+class GroupMxFormat(ctypes.Structure):
+    """lq_group_mx_format of include/lq_hip.h."""
+    _fields_ = [("format", _c_i32), ("scale_format", _c_i32)]
+
+
 SIGNATURES.update({
     "lq_group_batch_create_affine": (_c_int, [ctypes.POINTER(GroupDesc), ctypes.POINTER(GroupOffset), _c_int, _c_int,
                                               ctypes.POINTER(_c_p)]),
+    "lq_group_batch_create_mx": (_c_int, [ctypes.POINTER(GroupDesc), ctypes.POINTER(GroupMxFormat), _c_int, ctypes.POINTER(_c_p)]),
     "lq_group_batch_create": (_c_int, [ctypes.POINTER(GroupDesc), _c_int, _c_int, ctypes.POINTER(_c_p)]),
     "lq_group_batch_destroy": (_c_int, [_c_p]),
     "lq_group_batch_workspace_bytes": (_c_sz, [_c_p]),

@@ -27,7 +27,7 @@ import torch
 from . import _hip
 from .descriptor import group_geometry, memory_descriptor
 from .layers import _ConvBase, _HostLayer, custom_layers_of
-from .ops import ROUNDINGS
+from .ops import ROUNDINGS, check_element_format, check_scale_format
 
 
 class _Entry:
@@ -245,6 +245,7 @@ class _GroupKind(_Kind):
     name = "a group batch (with or without asymmetric=True: the offsets step with the scales in the Adam set's one launch)"
     group = None           # the lq_group_batch handle
     adam_set = None
+    mx = False             # the microscaling batch (_MxGroupKind): lq_group_batch_create_mx, a format per tensor
 
     def refuse(self, what: str):
         raise ValueError(f"{what} is not available on FakeQuantBatch(group_batch=True): group-wise scales have no loss term and "
@@ -299,10 +300,15 @@ class _GroupKind(_Kind):
         arr = (_hip.GroupDesc * n)()
         for i, e in enumerate(self.entries):
             R, C, axis, gs = e.desc
+            qmin, qmax = (0, 0) if self.mx else e.nested.q_range      # an element format brings its own range
             arr[i] = _hip.GroupDesc(e.param.data_ptr(), e.scale.data_ptr(), e.out.data_ptr(), e.dp.data_ptr(), e.ds.data_ptr(),
-                                    R, C, gs, axis, int(e.nested.q_range[0]), int(e.nested.q_range[1]))
+                                    R, C, gs, axis, int(qmin), int(qmax))
         handle = ctypes.c_void_p()
-        if affine:
+        if self.mx:
+            fmts = (_hip.GroupMxFormat * n)(*[_hip.GroupMxFormat(check_element_format(e.nested.element_format).id,
+                                                                 check_scale_format(e.nested.scale_format)) for e in self.entries])
+            _hip.check(lib.lq_group_batch_create_mx(arr, fmts, n, ctypes.byref(handle)), "lq_group_batch_create_mx")
+        elif affine:
             # kb is the layer's factor (ops.fq_backward_group_affine: the offset's defaults to the scale's), fixed for the batch's life
             offs = (_hip.GroupOffset * n)()
             for i, e in enumerate(self.entries):
@@ -354,10 +360,32 @@ class _GroupKind(_Kind):
                    "lq_adam_set_step")
 
 
+class _MxGroupKind(_GroupKind):
+    """The group batch over layers with an element format (``lq_group_batch_create_mx``): every tensor its own element format
+    and scale format, the straight-through rule and the one rounding of a minifloat grid for all."""
+    name = "a microscaling group batch (mx=True)"
+    mx = True
+
+    def check(self, layers, nested_layers):
+        plain = [n for n in nested_layers if getattr(n, "element_format", None) is None]
+        if plain:
+            raise ValueError("FakeQuantBatch(group_batch=True, mx=True) over a layer without an element format: every quantised "
+                             "tensor of a microscaling batch needs an element_format (formats and scale formats may differ between "
+                             "layers; an integer model runs the plain group batch)")
+        if any(n.penalty_threshold is not None or n.penalty_rate is not None for n in nested_layers):
+            raise ValueError("FakeQuantBatch(group_batch=True, mx=True) with a loss term / penalty_threshold: the penalty kernels "
+                             "know the integer grid only; a microscaling layer has no loss term")
+        if any(isinstance(layer, _ConvBase) and layer.kernel_storage == "hwio" for layer in layers):
+            raise ValueError('FakeQuantBatch(group_batch=True, mx=True) with kernel_storage="hwio": the blocks are defined in the '
+                             'memory order the convolution consumes; build the model with kernel_storage="oihw"')
+        self.ste = True                # a layer with an element format has the straight-through scale gradient
+        self.rounding = "nearest"      # a minifloat grid has one rounding: ties to even
+
+
 class FakeQuantBatch:
     def __init__(self, model_or_layers, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-7, mode: str = "keras",
                  oihw: bool = True, hwio_out: bool = True, autograd: bool = True, clipped: bool = False,
-                 group_batch: bool = False, asymmetric: bool = False):
+                 group_batch: bool = False, asymmetric: bool = False, mx: bool = False):
         """``autograd=True``: ``quantize_all()`` is ONE autograd node (2 x tensors inputs, one output per tensor) and everything happens
         inside ``loss.backward()``.  Convenient -- and, for 40 tensors, 0.4-0.6 ms of autograd-engine work per step (an 80-input node,
         40 output wrappers, an AccumulateGrad per parameter that adds into the data-parallel bucket with a launch of its own).
@@ -389,7 +417,15 @@ class FakeQuantBatch:
         launch.  That set holds 256 tensors at most (scales + offsets; the ResNet-50-like model has 108 + 54 = 162): a larger model is
         refused at construction, never split silently.  Over a model without an asymmetric layer this is the plain group batch.
         Everything the group batch refuses stays refused (``clipped``, a loss term, HWIO storage, ``defer_scale_grads``,
-        ``BatchedScaleAdam(fused=True)``)."""
+        ``BatchedScaleAdam(fused=True)``).
+        ``mx=True`` (opt-in, with ``group_batch=True`` only, not together with ``clipped`` or ``asymmetric``): a group batch over
+        layers with an ``element_format`` (``lq_group_batch_create_mx``): still ONE launch per pass.  Every quantised tensor of
+        the model must carry an element format; the format and the scale format live per tensor in the batch's task table, so
+        layers of different formats (``layer.make_mx(...)``) share one batch.  ``out``, ``dP``, ds and the saturation counts
+        (``clip_counts()``) are the per-tensor microscaling ops' bit for bit, kernels and biases alike (a bias is the one-group
+        line, as on the per-tensor path).  Each tensor's gradient factor is its layer's ``grad_scale_value``; the scales join
+        the Adam set with their constraint's lower bound.  Everything the group batch refuses stays refused (a loss term, HWIO
+        storage, ``defer_scale_grads``, ``BatchedScaleAdam(fused=True)``)."""
         layers = custom_layers_of(model_or_layers) if isinstance(model_or_layers, torch.nn.Module) else list(model_or_layers)
         self.layers = layers
         self.autograd = bool(autograd)
@@ -398,12 +434,12 @@ class FakeQuantBatch:
         self.entries: List[_Entry] = []
         nested_layers = [getattr(layer, a) for layer in layers for a in ("nested_q_w_layer", "nested_q_k_layer", "nested_q_b_layer")
                          if hasattr(layer, a)]
-        mx = [n for n in nested_layers if getattr(n, "element_format", None) is not None]
-        if mx:
-            raise ValueError(f"FakeQuantBatch over a layer with an element format ({mx[0].element_format!r}): none of the multi-tensor "
+        fmt = [n for n in nested_layers if getattr(n, "element_format", None) is not None]
+        if fmt and not mx:        # the microscaling batch is an opt-in of its own: FakeQuantBatch(..., group_batch=True, mx=True)
+            raise ValueError(f"FakeQuantBatch over a layer with an element format ({fmt[0].element_format!r}): none of the multi-tensor "
                              "batches (default, clipped, group) carries a minifloat grid; run such a model on the per-tensor path "
                              "(batched=False)")
-        kind = self._set_kind(clipped, group_batch, asymmetric)
+        kind = self._set_kind(clipped, group_batch, asymmetric, mx)
         if not asymmetric and any(getattr(n, "asymmetric", False) for n in nested_layers):
             raise ValueError("FakeQuantBatch over an asymmetric layer: the offsets and their gradients travel only in the group "
                              "batch that was asked to carry them; opt in with FakeQuantBatch(..., group_batch=True, asymmetric=True), "
@@ -455,11 +491,18 @@ class FakeQuantBatch:
                 self._static_pre = [(layer.__dict__, (None if ik is None else self._leaf[ik], None if ib is None else self._leaf[ib], None))
                                     for layer, ik, ib in self._layer_slots]
 
-    def _set_kind(self, clipped: bool, group_batch: bool, asymmetric: bool):
-        """The three opt-ins as read-only facts and the kind they resolve to -- the only place that reads them.  No device call."""
+    def _set_kind(self, clipped: bool, group_batch: bool, asymmetric: bool, mx: bool = False):
+        """The four opt-ins as read-only facts and the kind they resolve to -- the only place that reads them.  No device call."""
         self.clipped = bool(clipped)
         self.group_batch = bool(group_batch)
         self.asymmetric = bool(asymmetric)
+        self.mx = bool(mx)
+        if mx and not group_batch:
+            raise ValueError("mx=True belongs to group_batch=True: only the group batch carries an element format per tensor "
+                             "(FakeQuantBatch(..., group_batch=True, mx=True))")
+        if mx and (clipped or asymmetric):
+            raise ValueError(f"mx=True together with {'clipped' if clipped else 'asymmetric'}=True: the microscaling formats are "
+                             "symmetric and bring their own range; a microscaling batch is group_batch=True, mx=True alone")
         if asymmetric and clipped:
             raise ValueError("asymmetric=True together with clipped=True: the clipped one-axis batch carries no offset per group; "
                              "offsets travel in the group batch only (group_batch=True, asymmetric=True)")
@@ -469,7 +512,7 @@ class FakeQuantBatch:
         if group_batch and clipped:
             raise ValueError("group_batch=True together with clipped=True: a batch is either the group batch (group-wise layers and "
                              "their biases) or the clipped batch (one-axis scales), not both")
-        self._kind = _GroupKind() if group_batch else _ClippedKind() if clipped else _DefaultKind()
+        self._kind = _MxGroupKind() if mx else _GroupKind() if group_batch else _ClippedKind() if clipped else _DefaultKind()
         return self._kind
 
     def _grad_buffer(self, t):

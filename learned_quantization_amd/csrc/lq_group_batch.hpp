@@ -28,10 +28,25 @@
 // The backward's static LDS is 8 KB sh_sum + 8 KB sh_sumb + 4 KB sh_cnt = 20 KB for every form: 8 blocks x 20 KB are the CU's
 // 160 KB, exactly the 8 blocks of 256 threads a CU holds, so the 72 registers bound occupancy (7 waves) before LDS does.  The
 // float4 column body keeps its one row in flight (lq_group.hpp, unroll(1) with an offset in the backward).
+//
+// Microscaling tensors (lq_group_batch_create_mx) run k_group_batch_mx on a table of GroupMxTask: a GroupTask followed by the
+// values of the tensor's element format and scale format (M, emin, bits, e8m0_mask; lo / hi of the GroupParams are the format's
+// -max / +max).  The format is the task's own: one batch holds tensors of different formats.  A block builds the MX parameter
+// struct from its task and runs the bodies with the element step of lq_mx.hpp, what k_group_mx_cols / k_group_mx_rows run, so
+// out, dP, the saturation counts and ds are lq_fq_*_mx's bit for bit, a bias (the one-group line) included.  The format values are
+// block-uniform where the single-tensor kernels have them kernel-uniform: the table is read at a uniform index with scalar loads
+// (the four words after the GroupTask come by one s_load_dwordx4 in the forward, s_load_dwordx2 + 2 x s_load_dword in the
+// backward) and they stay in scalar registers.
+// Resources of k_group_batch_mx on gfx950 (compiler's report, profiles/mx_batch/kernel_resources.txt):
+//   forward   39 VGPRs, 70 SGPRs, no LDS, no scratch, 8 waves per SIMD      (k_group_batch: 39 VGPRs, 8 waves)
+//   backward  64 VGPRs, 78 SGPRs, 12288 bytes of LDS, no scratch, 8 waves per SIMD
+//             (k_group_batch: 66 VGPRs, 12288 bytes, 7 waves; k_group_mx_cols<true, 4, 16>: 76 VGPRs, 12288 bytes, 6 waves)
+// The backward's static LDS is the symmetric batch's (8 KB sh_sum + 4 KB sh_cnt; there is no sh_sumb).
 #ifndef LQ_GROUP_BATCH_HPP_
 #define LQ_GROUP_BATCH_HPP_
 #include "lq_group.hpp"
 #include "lq_batch.hpp"
+#include "lq_mx.hpp"
 
 namespace lq {
 
@@ -134,6 +149,44 @@ __global__ __launch_bounds__(kBlock) void k_group_batch_affine(const GroupAffine
     // block-uniform: every thread of a block takes the same side, and a column form's two barriers with it
     if (ap.b != nullptr) group_batch_unit<RNE, BWD>(ap, t, b, sh_sum, sh_sumb, sh_cnt);
     else group_batch_unit<RNE, BWD>(ap.g, t, b, sh_sum, nullptr, sh_cnt);
+}
+
+// A GroupTask of a microscaling tensor: the mx table's entry (lq_group_batch_create_mx).  The format is the task's own, so one
+// batch holds tensors of different element formats and scale formats; t.p.lo / hi are the format's -max / +max.
+struct GroupMxTask {
+    GroupTask t;
+    int32_t M, emin, bits;    // as GroupMxParams
+    uint32_t e8m0_mask;
+};
+
+// The batch's own name for GroupMxParams, for the reason GroupBatchAffineParams has one: the bodies are instantiated apart from
+// k_group_mx_cols / k_group_mx_rows, which keep their instruction streams.  The element step is GroupMxParams' own.
+struct GroupBatchMxParams : GroupMxParams {};
+template <bool RNE>
+struct GroupStep<RNE, GroupBatchMxParams> : GroupStep<RNE, GroupMxParams> {};
+
+// The format values (M, emin, bits, the scale-format mask, lo / hi) are block-uniform here where the single-tensor kernels have
+// them kernel-uniform: they are read from the table at a uniform index, by scalar loads into scalar registers.
+template <bool BWD>
+__global__ __launch_bounds__(kBlock) void k_group_batch_mx(const GroupMxTask* __restrict__ tasks, const uint32_t* __restrict__ block_task,
+                                                           PtrPack pk, CoefPack cf, int mask_only) {
+    __shared__ double sh_sum[BWD ? kGroupBatchLdsSum : 1];
+    __shared__ uint32_t sh_cnt[BWD ? kGroupBatchLdsSum : 1];
+    const int ti = (int)block_task[blockIdx.x];
+    const GroupMxTask& mt = tasks[ti];
+    const GroupTask& t = mt.t;
+    GroupBatchMxParams mp;
+    mp.g = t.p;
+    mp.M = mt.M;
+    mp.emin = mt.emin;
+    mp.bits = mt.bits;
+    mp.e8m0_mask = mt.e8m0_mask;
+    if constexpr (BWD) {
+        mp.g.dy = pk.dy[ti];
+        mp.g.k = cf.c[ti];
+        if (mask_only) mp.g.ds = nullptr;
+    }
+    group_batch_unit<true, BWD>(mp, t, blockIdx.x - t.first_block, sh_sum, nullptr, sh_cnt);
 }
 
 }  // namespace lq

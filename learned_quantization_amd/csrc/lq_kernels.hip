@@ -2858,6 +2858,7 @@ struct lq_group_table {
     std::vector<int> index;               // table position -> descriptor index (tasks are ordered by work per block)
     lq::GroupTask* d = nullptr;           // a batch without offsets
     lq::GroupAffineTask* da = nullptr;    // a batch with offsets: the same tasks, each with its b, db and kb
+    lq::GroupMxTask* dm = nullptr;        // a microscaling batch: the same tasks, each with its format
     uint32_t* block_task_d = nullptr;     // [blocks] task of every block
     uint32_t blocks = 0;
 };
@@ -2867,6 +2868,8 @@ struct lq_group_batch {
     int rounding = 0;
     bool affine = false;                  // some tensor has an offset: the tables are GroupAffineTask, the kernel k_group_batch_affine
     std::vector<lq_group_offset> offs;    // per descriptor; empty without offsets
+    bool mx = false;                      // lq_group_batch_create_mx: the tables are GroupMxTask, the kernel k_group_batch_mx
+    std::vector<lq_group_mx_format> fmts; // per descriptor; empty unless mx
     lq_group_table fwd, bwd;
     std::vector<const uint32_t*> counts;  // per descriptor: its slice of counts_d
     std::vector<int64_t> groups;          // per descriptor: scale elements
@@ -2889,8 +2892,8 @@ static void fill_group_task(GroupTask& t, const GroupParams& p, int axis, bool v
 }
 
 // Orders the table so that the heaviest units start first (as finish_table), assigns the block prefix, uploads the block table and
-// allocates the task table; affine: its entries are GroupAffineTask (a batch with offsets), else GroupTask
-static int finish_group_table(lq_group_table& tb, bool affine) {
+// allocates the task table; affine: its entries are GroupAffineTask (a batch with offsets), mx: GroupMxTask, else GroupTask
+static int finish_group_table(lq_group_table& tb, bool affine, bool mx) {
     const size_t n = tb.h.size();
     std::vector<size_t> order(n);
     for (size_t i = 0; i < n; ++i) order[i] = i;
@@ -2917,7 +2920,8 @@ static int finish_group_table(lq_group_table& tb, bool affine) {
     }
     hipError_t e = hipMalloc(&tb.block_task_d, bt.size() * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMemcpy(tb.block_task_d, bt.data(), bt.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = affine ? hipMalloc(&tb.da, n * sizeof(GroupAffineTask)) : hipMalloc(&tb.d, n * sizeof(GroupTask));
+    if (e == hipSuccess)
+        e = affine ? hipMalloc(&tb.da, n * sizeof(GroupAffineTask)) : (mx ? hipMalloc(&tb.dm, n * sizeof(GroupMxTask)) : hipMalloc(&tb.d, n * sizeof(GroupTask)));
     if (e != hipSuccess) return fail(LQ_EHIP, "lq_group_batch_create: %s", hipGetErrorString(e));
     return LQ_OK;
 }
@@ -2925,9 +2929,11 @@ static int finish_group_table(lq_group_table& tb, bool affine) {
 static void free_group_table(lq_group_table& tb) {
     if (tb.d) (void)hipFree(tb.d);
     if (tb.da) (void)hipFree(tb.da);
+    if (tb.dm) (void)hipFree(tb.dm);
     if (tb.block_task_d) (void)hipFree(tb.block_task_d);
     tb.d = nullptr;
     tb.da = nullptr;
+    tb.dm = nullptr;
     tb.block_task_d = nullptr;
 }
 
@@ -2935,13 +2941,15 @@ static void free_group_table(lq_group_table& tb) {
 
 extern "C" {
 
-// lq_group_batch_create and lq_group_batch_create_affine.  offs == NULL, or no tensor with a b: the tables and the kernel of a
-// batch without offsets
-static int group_batch_create(const char* fn, const lq_group_desc* descs, const lq_group_offset* offs, int n, int rounding,
-                              lq_group_batch** out) {
+// lq_group_batch_create, lq_group_batch_create_affine and lq_group_batch_create_mx.  offs == NULL, or no tensor with a b: the
+// tables and the kernel of a batch without offsets.  mx: fmts holds every tensor's format, the range is the format's and the
+// descriptor's qmin / qmax are not read
+static int group_batch_create(const char* fn, const lq_group_desc* descs, const lq_group_offset* offs, const lq_group_mx_format* fmts,
+                              bool mx, int n, int rounding, lq_group_batch** out) {
     if (!out) return fail(LQ_EINVAL, "%s: out is NULL", fn);
     *out = nullptr;
     if (!descs) return fail(LQ_EINVAL, "%s: descs is NULL", fn);
+    if (mx && !fmts) return fail(LQ_EINVAL, "%s: fmts is NULL", fn);
     if (n < 1 || n > kBatchMax) return fail(LQ_EINVAL, "%s: %d tensors (1 .. %d)", fn, n, kBatchMax);
     int rc = check_rounding(fn, rounding);
     if (rc) return rc;
@@ -2955,7 +2963,8 @@ static int group_batch_create(const char* fn, const lq_group_desc* descs, const 
         if (!aligned(d.P, 4) || !aligned(d.s, 4) || !aligned(d.out, 4) || !aligned(d.dp, 4) || (d.ds && !aligned(d.ds, 4)))
             return fail(LQ_EALIGN, "%s: P, s, out, dp and ds must be 4-byte aligned", who);
         if ((rc = check_group(who, d.R, d.C, d.axis, d.gs))) return rc;
-        if ((rc = check_clip_range(who, d.qmin, d.qmax))) return rc;
+        rc = mx ? check_mx(who, fmts[i].format, fmts[i].scale_format) : check_clip_range(who, d.qmin, d.qmax);
+        if (rc) return rc;
     }
     bool affine = false;
     for (int i = 0; offs && i < n; ++i) {
@@ -2973,13 +2982,15 @@ static int group_batch_create(const char* fn, const lq_group_desc* descs, const 
     b->rounding = rounding;
     b->affine = affine;
     if (affine) b->offs.assign(offs, offs + n);
+    b->mx = mx;
+    if (mx) b->fmts.assign(fmts, fmts + n);
     b->counts.resize(n);
     b->groups.resize(n);
     int64_t total = 0;
     std::vector<int64_t> first(n);
     for (int i = 0; i < n; ++i) {
         const lq_group_desc& d = descs[i];
-        const GroupParams p = group_params(d.P, d.s, d.qmin, d.qmax, d.R, d.C, d.axis, d.gs);
+        const GroupParams p = group_params(d.P, d.s, 0, 0, d.R, d.C, d.axis, d.gs);      // the geometry alone
         first[i] = total;
         b->groups[i] = d.axis == 0 ? (int64_t)p.nb * p.C : (int64_t)p.R * p.nb;
         total += b->groups[i];
@@ -2989,7 +3000,11 @@ static int group_batch_create(const char* fn, const lq_group_desc* descs, const 
     for (int i = 0; i < n && !rc; ++i) {
         const lq_group_desc& d = descs[i];
         b->counts[i] = b->counts_d + first[i];
-        GroupParams p = group_params(d.P, d.s, d.qmin, d.qmax, d.R, d.C, d.axis, d.gs);
+        GroupParams p = group_params(d.P, d.s, mx ? 0 : d.qmin, mx ? 0 : d.qmax, d.R, d.C, d.axis, d.gs);
+        if (mx) {      // lo = -max, hi = +max of the tensor's format, as lq_fq_*_mx
+            p.lo = -kMxFormats[fmts[i].format].mx;
+            p.hi = kMxFormats[fmts[i].format].mx;
+        }
         GroupTask t;
         p.out = d.out;
         fill_group_task(t, p, d.axis, group_vec_ok(p, d.axis) && aligned(d.P, 16) && aligned(d.out, 16), false);
@@ -3003,7 +3018,7 @@ static int group_batch_create(const char* fn, const lq_group_desc* descs, const 
         b->bwd.index.push_back(i);
     }
     for (lq_group_table* tb : {&b->fwd, &b->bwd}) {
-        if (!rc) rc = finish_group_table(*tb, affine);
+        if (!rc) rc = finish_group_table(*tb, affine, mx);
         if (rc) break;
         hipError_t e;
         if (affine) {      // the ordered tasks, each with its descriptor's offset; db only where the backward writes it
@@ -3017,6 +3032,20 @@ static int group_batch_create(const char* fn, const lq_group_desc* descs, const 
                 ha[k].kb = o.b ? o.offset_grad_scale : 0.0f;
             }
             e = hipMemcpy(tb->da, ha.data(), ha.size() * sizeof(GroupAffineTask), hipMemcpyHostToDevice);
+        } else if (mx) {      // the ordered tasks, each with its descriptor's format
+            std::vector<GroupMxTask> hm(tb->h.size());
+            for (size_t k = 0; k < hm.size(); ++k) {
+                const lq_group_mx_format& f = b->fmts[tb->index[k]];
+                GroupMxParams mp{};
+                mx_fill(mp, f.format, f.scale_format);
+                memset(&hm[k], 0, sizeof(GroupMxTask));
+                hm[k].t = tb->h[k];
+                hm[k].M = mp.M;
+                hm[k].emin = mp.emin;
+                hm[k].bits = mp.bits;
+                hm[k].e8m0_mask = mp.e8m0_mask;
+            }
+            e = hipMemcpy(tb->dm, hm.data(), hm.size() * sizeof(GroupMxTask), hipMemcpyHostToDevice);
         } else {
             e = hipMemcpy(tb->d, tb->h.data(), tb->h.size() * sizeof(GroupTask), hipMemcpyHostToDevice);
         }
@@ -3031,11 +3060,15 @@ static int group_batch_create(const char* fn, const lq_group_desc* descs, const 
 }
 
 int lq_group_batch_create(const lq_group_desc* descs, int n, int rounding, lq_group_batch** out) {
-    return group_batch_create("lq_group_batch_create", descs, nullptr, n, rounding, out);
+    return group_batch_create("lq_group_batch_create", descs, nullptr, nullptr, false, n, rounding, out);
 }
 
 int lq_group_batch_create_affine(const lq_group_desc* descs, const lq_group_offset* offs, int n, int rounding, lq_group_batch** out) {
-    return group_batch_create("lq_group_batch_create_affine", descs, offs, n, rounding, out);
+    return group_batch_create("lq_group_batch_create_affine", descs, offs, nullptr, false, n, rounding, out);
+}
+
+int lq_group_batch_create_mx(const lq_group_desc* descs, const lq_group_mx_format* fmts, int n, lq_group_batch** out) {
+    return group_batch_create("lq_group_batch_create_mx", descs, nullptr, fmts, true, n, LQ_ROUND_NEAREST_EVEN, out);
 }
 
 int lq_group_batch_destroy(lq_group_batch* b) {
@@ -3061,7 +3094,9 @@ int lq_group_batch_forward(const lq_group_batch* b, void* stream) {
     const lq_group_table& tb = b->fwd;
     hipStream_t st = (hipStream_t)stream;
     const bool rne = b->rounding == LQ_ROUND_NEAREST_EVEN;
-    if (b->affine) {
+    if (b->mx) {
+        hipLaunchKernelGGL((k_group_batch_mx<false>), dim3(tb.blocks), dim3(kBlock), 0, st, tb.dm, tb.block_task_d, pk, cf, 0);
+    } else if (b->affine) {
         if (rne) hipLaunchKernelGGL((k_group_batch_affine<true, false>), dim3(tb.blocks), dim3(kBlock), 0, st, tb.da, tb.block_task_d, pk, cf, 0);
         else hipLaunchKernelGGL((k_group_batch_affine<false, false>), dim3(tb.blocks), dim3(kBlock), 0, st, tb.da, tb.block_task_d, pk, cf, 0);
     } else if (rne)
@@ -3097,7 +3132,9 @@ int lq_group_batch_backward(const lq_group_batch* b, const float* const* dy, con
     hipStream_t st = (hipStream_t)stream;
     const int mask_only = grad_scale ? 0 : 1;
     const bool rne = b->rounding == LQ_ROUND_NEAREST_EVEN;
-    if (b->affine) {
+    if (b->mx) {
+        hipLaunchKernelGGL((k_group_batch_mx<true>), dim3(tb.blocks), dim3(kBlock), 0, st, tb.dm, tb.block_task_d, pk, cf, mask_only);
+    } else if (b->affine) {
         if (rne) hipLaunchKernelGGL((k_group_batch_affine<true, true>), dim3(tb.blocks), dim3(kBlock), 0, st, tb.da, tb.block_task_d, pk, cf, mask_only);
         else hipLaunchKernelGGL((k_group_batch_affine<false, true>), dim3(tb.blocks), dim3(kBlock), 0, st, tb.da, tb.block_task_d, pk, cf, mask_only);
     } else if (rne)

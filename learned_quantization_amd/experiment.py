@@ -130,7 +130,7 @@ def build_parser():
     ap.add_argument("--asymmetric", action="store_true",
                     help="with --bits, --group-size and --scale-gradient ste: every group-wise kernel also learns an offset per group")
     ap.add_argument("--element-format", default=None, choices=["fp4_e2m1", "fp6_e2m3", "fp6_e3m2", "fp8_e4m3", "fp8_e5m2"],
-                    help="with --scale-gradient ste (no --custom_loss, --bits, --rounding or --batched): OCP microscaling quantizer, "
+                    help="with --scale-gradient ste (no --custom_loss, --bits or --rounding; --batched with --mx-batch only): OCP microscaling quantizer, "
                          "elements on this minifloat grid under one scale per block of --group-size elements (default 32)")
     ap.add_argument("--scale-format", default=None, choices=["e8m0", "fp32"],
                     help="with --element-format: e8m0 (default; the scale is rounded to a power of two) or fp32")
@@ -151,6 +151,9 @@ def build_parser():
                     help="with --batched, --bits and --group-size: run the group-wise layers in the group batch (opt-in, see train.py)")
     ap.add_argument("--asymmetric-batch", action="store_true",
                     help="with --asymmetric, --batched and --group-batch: the group batch also carries the offsets (opt-in, see train.py)")
+    ap.add_argument("--mx-batch", action="store_true",
+                    help="with --element-format, --batched and --group-batch: run the microscaling layers in the group batch (opt-in, "
+                         "see train.py)")
     ap.add_argument("--loss-values", action="store_true",
                     help="with --custom_loss: loss and val_loss include rate * penalty (what Keras reports for compute_total_loss) "
                          "and custom_losses/*.log get one line per step, from a device-side log flushed at every epoch end")
@@ -182,7 +185,7 @@ def main(argv=None):
                  clipped_batch=args.clipped_batch, group_size=args.group_size,
                  group_batch=args.group_batch, scale_init=args.scale_init, asymmetric=args.asymmetric,
                  asymmetric_batch=args.asymmetric_batch, element_format=args.element_format,
-                 scale_format=args.scale_format or "e8m0")
+                 scale_format=args.scale_format or "e8m0", mx_batch=args.mx_batch)
     if args.training == "post_training":
         if args.config != "mnist" or not args.baseline_weights:
             raise SystemExit("post_training needs --config mnist --baseline-weights <npz with W1,b1,W2,b2> "

@@ -75,11 +75,15 @@ class Trainer:
                  force_collectives: bool = False, kernel_storage: str = "oihw", loss_values: bool = False,
                  loss_log_capacity: int = 4096, grad_scale=None, bits=None, signed=True, q_range=None, rounding="floor",
                  clipped_batch: bool = False, group_size=None, group_batch: bool = False, scale_init=None, asymmetric: bool = False,
-                 asymmetric_batch: bool = False, element_format=None, scale_format="e8m0"):
+                 asymmetric_batch: bool = False, element_format=None, scale_format="e8m0", mx_batch: bool = False):
         """``element_format`` (one of ops.ELEMENT_FORMATS; mode "ste"; eager, graphed and data-parallel mode "A"; per-tensor path
-        only) with ``scale_format`` ("e8m0", the default, or "fp32"): the OCP microscaling quantizer for every quantised tensor
+        unless ``mx_batch``) with ``scale_format`` ("e8m0", the default, or "fp32"): the OCP microscaling quantizer for every quantised tensor
         (models.build_model): kernels in blocks of ``group_size`` (32 by default), biases as one group.  It takes no range,
-        rounding, offsets or batch; ``scale_init`` is "mx" (the OCP rule) or "cover" (nothing saturates).
+        rounding or offsets, and no batch but the one ``mx_batch`` asks for; ``scale_init`` is "mx" (the OCP rule) or "cover" (nothing saturates).
+        ``mx_batch`` (opt-in, with ``element_format``, ``group_batch`` and ``batched``; eager, graphed, data-parallel mode "A"):
+        the microscaling kernels and their biases run in the group batch (``FakeQuantBatch(group_batch=True, mx=True)``): one
+        forward and one backward launch for the whole model, results those of the per-tensor path bit for bit, and one launch
+        steps every scale.  ``group_size`` may be left at the microscaling default of 32.
         ``asymmetric`` (with ``group_size``, a range and mode "ste"; eager, graphed and data-parallel mode "A"; per-tensor path
         unless ``asymmetric_batch``): every group-wise kernel also learns an offset per group (models.build_model); the offsets
         are stepped by the scales' optimizer, without a lower bound.  ``scale_init="minmax"`` exists for such models only.
@@ -122,12 +126,21 @@ class Trainer:
             check_element_format(element_format)
             check_scale_format(scale_format)
             check_mx_model(mode, bits, signed, q_range, rounding, asymmetric, kernel_storage, scale_init)
-            if batched or clipped_batch or group_batch or asymmetric_batch:
+            if mx_batch and not (group_batch and batched):
+                raise ValueError("mx_batch=True belongs to element_format, group_batch=True and batched=True: it lets the group batch "
+                                 "carry the element formats of a microscaling model")
+            if mx_batch and (clipped_batch or asymmetric_batch):
+                raise ValueError("mx_batch=True with clipped_batch / asymmetric_batch: a microscaling model runs in the group batch "
+                                 "alone (batched=True, group_batch=True, mx_batch=True)")
+            if (batched or clipped_batch or group_batch or asymmetric_batch) and not mx_batch:
                 raise ValueError("element_format with batched=True: none of the multi-tensor batches (default, clipped, group) carries "
                                  "a minifloat grid; a model with an element format runs on the per-tensor path")
             if ddp_mode == "B":
                 raise ValueError("element_format with ddp_mode 'B': it recomputes ds from the all-reduced dP, which no longer holds "
                                  "the dy of the saturated elements; use ddp_mode 'A'")
+        elif mx_batch:
+            raise ValueError("mx_batch=True belongs to element_format, group_batch=True and batched=True: a model without an element "
+                             "format has no microscaling layer to batch")
         elif scale_init in MX_SCALE_INITS:
             raise ValueError(f"scale_init {scale_init!r} on a model without an element format: it writes the power-of-two scale of a "
                              "microscaling block")
@@ -144,6 +157,7 @@ class Trainer:
             raise ValueError("asymmetric_batch=True belongs to asymmetric=True, group_batch=True and batched=True: it lets the group "
                              "batch carry the offsets of an asymmetric model")
         self.asymmetric_batch = bool(asymmetric_batch)
+        self.mx_batch = bool(mx_batch)
         if scale_init == "minmax":
             if not asymmetric:
                 raise ValueError('scale_init "minmax" on a symmetric model: it places each group\'s range over [min, max] through an '
@@ -182,7 +196,7 @@ class Trainer:
             raise ValueError("clipped_batch=True needs bits / q_range: an unclipped model runs the default batch")
         if group_batch and not batched:
             raise ValueError("group_batch=True belongs to batched=True")
-        if group_batch and group_size is None:
+        if group_batch and group_size is None and not mx_batch:      # a microscaling model has its own default group size
             raise ValueError("group_batch=True needs group_size: a model of one-axis scales runs the default or the clipped batch")
         self.clipped_batch = bool(clipped_batch)
         self.group_batch = bool(group_batch)
@@ -232,7 +246,7 @@ class Trainer:
             # the convolutions consume the OIHW companions only; autograd=False: the fake-quantised tensors are leaves and
             # _backward_phase calls finish_backward() itself (0.4-0.6 ms less autograd-engine work per eager step for 40 tensors)
             self.batch = FakeQuantBatch(self.model, lr=lr, hwio_out=False, autograd=False, clipped=self.clipped_batch,
-                                        group_batch=self.group_batch, asymmetric=self.asymmetric_batch)
+                                        group_batch=self.group_batch, asymmetric=self.asymmetric_batch, mx=self.mx_batch)
             # nothing touches ds between its computation and the scales' update when there is no loss term and ds is not
             # exchanged (one process, or exact mode B): the finalize then applies the Adam step itself (one launch fewer)
             # (the fused finalize + Adam is the nested-quantization pass's: not for the straight-through modes, nor for a kind of
@@ -474,7 +488,8 @@ class Trainer:
 class DriverParser(argparse.ArgumentParser):
     """Argument parser of both drivers: what the flags refuse in combination is refused here, as a usage error, before any device
     is touched -- ``--scale-init minmax`` belongs to ``--asymmetric``, which belongs to ``--group-size``; ``--asymmetric-batch``
-    belongs to ``--asymmetric``, ``--group-batch`` and ``--batched``."""
+    belongs to ``--asymmetric``, ``--group-batch`` and ``--batched``; ``--mx-batch`` belongs to ``--element-format``,
+    ``--group-batch`` and ``--batched``, and is the only way an element format meets ``--batched``."""
 
     def parse_args(self, args=None, namespace=None):
         ns = super().parse_args(args, namespace)
@@ -485,6 +500,13 @@ class DriverParser(argparse.ArgumentParser):
                                                            and getattr(ns, "batched", False)):
             self.error("--asymmetric-batch needs --asymmetric, --group-batch and --batched: it lets the group batch carry the "
                        "offsets of an asymmetric model")
+        mx_batch = getattr(ns, "mx_batch", False)
+        if mx_batch and not (getattr(ns, "element_format", None) is not None and getattr(ns, "group_batch", False)
+                             and getattr(ns, "batched", False)):
+            self.error("--mx-batch needs --element-format, --group-batch and --batched: it lets the group batch carry the element "
+                       "formats of a microscaling model")
+        if mx_batch and (getattr(ns, "clipped_batch", False) or getattr(ns, "asymmetric_batch", False)):
+            self.error("--mx-batch with --clipped-batch / --asymmetric-batch: a microscaling model runs in the group batch alone")
         if getattr(ns, "element_format", None) is None:
             if getattr(ns, "scale_init", None) in MX_SCALE_INITS:
                 self.error("--scale-init mx / cover needs --element-format: it writes the power-of-two scale of a microscaling block")
@@ -493,7 +515,7 @@ class DriverParser(argparse.ArgumentParser):
         else:
             for flag, bad in (("--bits", getattr(ns, "bits", None) is not None), ("--unsigned", getattr(ns, "unsigned", False)),
                               ("--rounding", getattr(ns, "rounding", "floor") != "floor"), ("--asymmetric", getattr(ns, "asymmetric", False)),
-                              ("--batched", getattr(ns, "batched", False))):
+                              ("--batched", getattr(ns, "batched", False) and not mx_batch)):
                 if bad:
                     self.error(f"--element-format with {flag}: an element format brings its own grid, range and rounding, has no "
                                "offsets and runs on the per-tensor path")
@@ -562,6 +584,9 @@ def build_parser():
     ap.add_argument("--asymmetric-batch", action="store_true",
                     help="with --asymmetric, --batched and --group-batch: the group batch also carries the offsets (opt-in: still one "
                          "forward and one backward launch, which writes the offsets' gradients too)")
+    ap.add_argument("--mx-batch", action="store_true",
+                    help="with --element-format, --batched and --group-batch: run the microscaling layers and their biases in the "
+                         "group batch (opt-in: one forward and one backward launch for the whole model, formats per tensor)")
     ap.add_argument("--loss-values", action="store_true",
                     help="modes cl / nqcl: evaluate the penalty with its gradients, report mean(SCCE) + rate * penalty and keep the "
                          "reference's per-step loss logs in a device buffer (written at the end)")
@@ -619,7 +644,7 @@ def main(argv=None):
                  bits=args.bits, signed=not args.unsigned, rounding=args.rounding, clipped_batch=args.clipped_batch,
                  group_size=args.group_size, group_batch=args.group_batch, scale_init=args.scale_init,
                  asymmetric=args.asymmetric, asymmetric_batch=args.asymmetric_batch, element_format=args.element_format,
-                 scale_format=args.scale_format or "e8m0")
+                 scale_format=args.scale_format or "e8m0", mx_batch=args.mx_batch)
     do_step = tr.step_graphed if args.graph else tr.step
     g = torch.Generator(device=dev).manual_seed(args.seed + rank)
     batches = [synthetic_batch(args.config, args.batch, dev, g) for _ in range(4)]
@@ -657,6 +682,7 @@ def main(argv=None):
             **({"clipped_batch": True} if args.clipped_batch else {}),
             **({"group_batch": True} if args.group_batch else {}),
             **({"asymmetric_batch": True} if args.asymmetric_batch else {}),
+            **({"mx_batch": True} if args.mx_batch else {}),
             "backend": (args.backend if use_dist else None),
             "channels_last": bool(args.channels_last), "kernel_storage": args.kernel_storage,
             **({"q_range": list(tr.q_range)} if tr.q_range else {}),

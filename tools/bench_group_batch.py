@@ -21,8 +21,15 @@ three launches per bias.  Candidate: the batch of ``lq_group_batch_create_affine
 the same rounds, is the SYMMETRIC batch over the same buffers (it ignores the offsets): what the offsets cost inside the batch.
 Before anything is timed the tool asserts that out, dP, ds and db of the affine batch equal the per-tensor calls' bit for bit.
 
+``--element-format F [--scale-format S]``: the same three weight sets as microscaling tensors at ``gs = 32`` (every kernel in blocks
+of 32, every bias one block).  Yardstick: the per-tensor MX path, ``lq_fq_forward_mx`` + ``lq_fq_backward_mx`` per kernel AND per
+bias (two launches each).  Candidate: the batch of ``lq_group_batch_create_mx`` (two launches).  A third pair of variants, timed in
+the same rounds, is the INTEGER group batch (range [-8, 7], nearest, ``gs = 32``) over the same buffers: the denominator of what the
+minifloat step costs inside the batch.  Before anything is timed the tool asserts that out, dP and ds of the MX batch equal the
+per-tensor calls' bit for bit, biases included.
+
     python tools/bench_group_batch.py [--configs cifar imagenette resnet50] [--rounds 15] [--inner 10] [--sets 4] [--repeats 3] [--out FILE]
-                                      [--asymmetric]
+                                      [--asymmetric | --element-format F [--scale-format S]] [--rotate-variants]
 """
 import argparse
 import ctypes
@@ -37,7 +44,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 import learned_quantization_amd as lq  # noqa: E402
-from learned_quantization_amd import _hip  # noqa: E402
+from learned_quantization_amd import _hip, ops  # noqa: E402
 from learned_quantization_amd.descriptor import group_geometry  # noqa: E402
 
 
@@ -66,8 +73,21 @@ def main():
     ap.add_argument("--group-size", type=int, default=128)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--asymmetric", action="store_true", help="kernels with an offset per group: the affine batch against the affine per-tensor calls")
+    ap.add_argument("--element-format", default=None, choices=list(ops.ELEMENT_FORMATS),
+                    help="microscaling tensors at gs = 32: the MX batch against the per-tensor MX calls, and against the integer group batch")
+    ap.add_argument("--scale-format", default="e8m0", choices=list(ops.SCALE_FORMATS))
+    ap.add_argument("--rotate-variants", action="store_true",
+                    help="round r starts with variant r mod n instead of the first one: every variant follows every other equally often, "
+                         "which separates what a variant costs from what running after another one costs")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file as well")
     args = ap.parse_args()
+    mx = args.element_format is not None
+    if mx and args.asymmetric:
+        ap.error("--element-format with --asymmetric: the microscaling formats are symmetric")
+    if mx:
+        args.bits, args.group_size = 4, 32          # the integer batch of the comparison: [-8, 7], nearest, on the MX block size
+        fid, sid = ops.ELEMENT_FORMATS[args.element_format].id, ops.SCALE_FORMATS.index(args.scale_format)
+    rnd = 1 if mx else 0
     dev = torch.device("cuda:0")
     lib = _hip.load()
     sp = _hip.stream_ptr(dev)
@@ -105,7 +125,11 @@ def main():
                                                             t["geom"][0], t["geom"][1], t["geom"][3], t["geom"][2], t["qmin"], t["qmax"])
                                              for t, (P, dy, out, dp) in zip(tensors, bufs)])
                 h, hs = ctypes.c_void_p(), ctypes.c_void_p()
-                if args.asymmetric:
+                if mx:
+                    fmts = (_hip.GroupMxFormat * n)(*[_hip.GroupMxFormat(fid, sid) for _ in tensors])
+                    _hip.check(lib.lq_group_batch_create_mx(arr, fmts, n, ctypes.byref(h)), "lq_group_batch_create_mx")
+                    _hip.check(lib.lq_group_batch_create(arr, n, rnd, ctypes.byref(hs)), "lq_group_batch_create")
+                elif args.asymmetric:
                     offs = (_hip.GroupOffset * n)(*[_hip.GroupOffset(_hip.ptr(t["b"]), _hip.ptr(t["db"]), 1.0) for t in tensors])
                     _hip.check(lib.lq_group_batch_create_affine(arr, offs, n, 0, ctypes.byref(h)), "lq_group_batch_create_affine")
                     _hip.check(lib.lq_group_batch_create(arr, n, 0, ctypes.byref(hs)), "lq_group_batch_create")
@@ -122,7 +146,9 @@ def main():
                 rc = 0
                 for t, (P, dy, out, dp) in zip(tensors, sets[k]):
                     R, C, axis, gs = t["geom"]
-                    if t["b"] is not None:
+                    if mx:
+                        rc |= lib.lq_fq_forward_mx(P.data_ptr(), t["s"].data_ptr(), out.data_ptr(), None, _hip.LQ_Q_NONE, fid, sid, R, C, axis, gs, sp)
+                    elif t["b"] is not None:
                         rc |= lib.lq_fq_forward_group_affine(P.data_ptr(), t["s"].data_ptr(), t["b"].data_ptr(), out.data_ptr(), None,
                                                              _hip.LQ_Q_NONE, t["qmin"], t["qmax"], 0, R, C, axis, gs, sp)
                     elif t["group"]:
@@ -137,7 +163,10 @@ def main():
                 rc = 0
                 for t, (P, dy, out, dp) in zip(tensors, sets[k]):
                     R, C, axis, gs = t["geom"]
-                    if t["b"] is not None:
+                    if mx:
+                        rc |= lib.lq_fq_backward_mx(P.data_ptr(), t["s"].data_ptr(), dy.data_ptr(), fid, sid, 1.0, dp.data_ptr(), t["ds"].data_ptr(),
+                                                    t["cl"].data_ptr(), R, C, axis, gs, sp)
+                    elif t["b"] is not None:
                         rc |= lib.lq_fq_backward_group_affine(P.data_ptr(), t["s"].data_ptr(), t["b"].data_ptr(), dy.data_ptr(), t["qmin"],
                                                               t["qmax"], 0, 1.0, 1.0, dp.data_ptr(), t["ds"].data_ptr(), t["db"].data_ptr(),
                                                               t["cl"].data_ptr(), None, 0, R, C, axis, gs, sp)
@@ -157,6 +186,9 @@ def main():
 
             variants = {"forward_per_tensor": fwd_per_tensor, "forward_batch": fwd_batch, "backward_per_tensor": bwd_per_tensor,
                         "backward_batch": bwd_batch}
+            if mx:
+                variants["forward_integer_batch"] = lambda k: lib.lq_group_batch_forward(handles[k][2], sp)
+                variants["backward_integer_batch"] = lambda k: lib.lq_group_batch_backward(handles[k][2], handles[k][1], ks, None, 0, sp)
             if args.asymmetric:
                 variants["forward_symmetric_batch"] = lambda k: lib.lq_group_batch_forward(handles[k][2], sp)
                 variants["backward_symmetric_batch"] = lambda k: lib.lq_group_batch_backward(handles[k][2], handles[k][1], ks, None, 0, sp)
@@ -166,6 +198,17 @@ def main():
                 return ([(out.clone(), dp.clone()) for _, _, out, dp in sets[0]], [t["ds"].clone() for t in tensors],
                         [t["db"].clone() for t in tensors if t["db"] is not None])
 
+            if mx:                   # before anything is timed: the candidate computes what the yardstick computes, bit for bit
+                _hip.check(fwd_per_tensor(0) | bwd_per_tensor(0), "per-tensor pass")
+                w_out, w_ds, _ = outputs()
+                for t in tensors:
+                    t["ds"].fill_(float("nan"))
+                _hip.check(fwd_batch(0) | bwd_batch(0), "batch pass")
+                g_out, g_ds, _ = outputs()
+                assert all(torch.equal(a, c) and torch.equal(b, d) for (a, b), (c, d) in zip(g_out, w_out)), "out / dP differ"
+                assert all(torch.equal(a, b) and not bool(torch.isnan(a).any()) for a, b in zip(g_ds, w_ds)), "ds of a tensor differs"
+                assert all(bool((dp != 0).any()) for _, dp in g_out), "a tensor saturates everywhere"
+                assert all(bool((dp == 0).any()) for (_, dp), t in zip(g_out, tensors) if t["group"]), "a kernel saturates nowhere"
             if args.asymmetric:      # before anything is timed: the candidate computes what the yardstick computes, bit for bit
                 _hip.check(fwd_per_tensor(0) | bwd_per_tensor(0), "per-tensor pass")
                 w_out, w_ds, w_db = outputs()
@@ -185,8 +228,11 @@ def main():
                     _hip.check(fn(k), key)
             torch.cuda.synchronize(dev)
             k_set = 0
-            for _ in range(args.rounds):
-                for key, fn in variants.items():
+            for rnd_no in range(args.rounds):
+                order = list(variants.items())
+                if args.rotate_variants:
+                    order = order[rnd_no % len(order):] + order[:rnd_no % len(order)]
+                for key, fn in order:
                     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     a.record()
                     for _ in range(args.inner):
@@ -203,11 +249,16 @@ def main():
             fwd_batch(0), bwd_batch(0)
             torch.cuda.synchronize(dev)
             same = all(torch.equal(o, wo) and torch.equal(d, wd) for (_, _, o, d), (wo, wd) in zip(sets[0], want))
-            same_ds = all(torch.equal(t["ds"], w) for t, w in zip(tensors, want_ds) if t["group"])
+            same_ds = all(torch.equal(t["ds"], w) for t, w in zip(tensors, want_ds) if t["group"] or mx)
             row = {"set": config, "tensors": n, "kernels": sum(t["group"] for t in tensors), "elements": sum(t["numel"] for t in tensors),
                    "bits": args.bits, "group_size": args.group_size, "repeat": repeat, "rounds": args.rounds, "inner": args.inner,
-                   "buffer_sets": args.sets, "launches_per_tensor_path": sum(2 if t["group"] else 3 for t in tensors),
+                   "buffer_sets": args.sets, "launches_per_tensor_path": sum(2 if t["group"] or mx else 3 for t in tensors),
                    "launches_batch": 2, "out_dp_bit_identical": bool(same), "kernel_ds_bit_identical": bool(same_ds)}
+            if args.rotate_variants:
+                row["rotate_variants"] = True
+            if mx:
+                row.update({"element_format": args.element_format, "scale_format": args.scale_format,
+                            "ds_bit_identical_before_timing_biases_included": True})      # asserted above
             if args.asymmetric:
                 row["asymmetric"] = True
                 row["kernel_ds_db_bit_identical_before_timing"] = True      # asserted above
@@ -217,6 +268,10 @@ def main():
             row["us_sum_per_tensor"] = row["us_forward_per_tensor"] + row["us_backward_per_tensor"]
             row["us_sum_batch"] = row["us_forward_batch"] + row["us_backward_batch"]
             row["batch_over_per_tensor"] = row["us_sum_batch"] / row["us_sum_per_tensor"]
+            if mx:
+                row["us_sum_integer_batch"] = row["us_forward_integer_batch"] + row["us_backward_integer_batch"]
+                row["mx_batch_over_integer_batch"] = row["us_sum_batch"] / row["us_sum_integer_batch"]
+                row["per_tensor_over_batch"] = row["us_sum_per_tensor"] / row["us_sum_batch"]
             if args.asymmetric:
                 row["us_sum_symmetric_batch"] = row["us_forward_symmetric_batch"] + row["us_backward_symmetric_batch"]
                 row["affine_batch_over_symmetric_batch"] = row["us_sum_batch"] / row["us_sum_symmetric_batch"]

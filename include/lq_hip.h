@@ -364,6 +364,42 @@ int lq_group_stats(const float* P, const float* s, const float* b /* NULL: symme
                    uint32_t* below, uint32_t* above, double* err2, double* sig2, uint32_t* hist /* may be NULL */,
                    int64_t R, int64_t C, int axis, int64_t gs, void* stream);
 
+/* ---- quantization statistics of the microscaling pair: per group and per tensor, read only ----
+ * What lq_group_stats is for the integer grid, for the minifloat grids of lq_fq_forward_mx under the scales P has NOW: how much each
+ * group saturates on either side, how much of it the grid flushes to zero, its squared error and squared signal, and the
+ * histogram of the encodings of the tensor.
+ * Geometry is exactly lq_fq_forward_mx's: matrix [R][C] in memory order, axis, gs clamped to the line length, nb = ceil(len / gs),
+ * ragged last group; s is [nb][C] or [R][nb].  A bias with a scalar scale is R = 1, C = numel, axis = 1, gs = numel.
+ * Per element, the definition under "OCP microscaling (MX) element formats" above, operation for operation: s_eff by
+ * `scale_format`, t = P / s_eff, q0 (t on the element grid, ties to even), q = q0 < -mx ? -mx : (q0 > mx ? mx : q0),
+ * out = q * s_eff; mx is the format's max.
+ * Per group g, in the scale's shape:
+ *   below[g]   = #{ i in g : q0_i < -mx }     exact, uint32
+ *   above[g]   = #{ i in g : q0_i > mx }      exact, uint32      (below + above is lq_fq_backward_mx's clipped)
+ *   flushed[g] = #{ i in g : P_i != 0 and q_i == 0 }      exact, uint32: the elements the grid turns into +-0 (|t| <= half the
+ *                smallest subnormal 2^(emin - M)); a NaN q is not zero
+ *   err2[g]    = sum_{i in g} e_i * e_i  with e_i = (double)P_i - (double)out_i;  the product and the addition round separately
+ *   sig2[g]    = sum_{i in g} (double)P_i * (double)P_i
+ * The group's SQNR is 10 log10 of sig2 / err2.  The sums are f64 from the first addition and taken in one fixed order (no float
+ * atomics, no workspace): two runs give the same bits.  All five are written for every group.
+ * Per tensor, when hist != NULL: hist[code] += 1 for every element whose q is a number, `code` the element's encoding exactly as
+ * the forward's code view defines it (-0.0 keeps its sign bit); 2^bits uint32 bins (16 / 64 / 256) that the caller has zeroed
+ * (counts are ADDED).  A NaN q is not binned: its "code" 2^(E+M) - 1 is a value's code in the fp4 and fp6 formats.  The bins are
+ * summed with integer atomics, which are exact in any order.
+ * Non-finite values: a NaN q0 counts on neither side, is not flushed and is not binned, and its group's err2 is NaN by IEEE
+ * arithmetic; +-Inf t counts on its side and q saturates at +-mx.  An invalid E8M0 scale gives a NaN s_eff: nothing of its group
+ * is counted on any side, as flushed, or binned, the group's err2 is NaN and its sig2 is still the sum of squares.  Other groups
+ * are unaffected.
+ * A NULL P, s, below, above, flushed, err2 or sig2, an unknown `format` or `scale_format`, axis not in {0, 1}, gs < 1, a
+ * non-positive extent and R * C >= 2^31 return LQ_EINVAL before any launch.  P, s, below, above, flushed or hist off the 4-byte
+ * grid and err2 or sig2 off the 8-byte grid return LQ_EALIGN; 16-byte loads of P are used under the group rule (16-byte aligned P,
+ * C % 4 == 0, and gs % 4 == 0 on axis 1).  The kernels take the group-wise backward's form, team width and grid.  The call only
+ * enqueues ONE launch (capturable), allocates nothing, reads no environment, reads the extents of P and s and writes the extents
+ * of its six outputs and nothing else.  */
+int lq_mx_stats(const float* P, const float* s, int format, int scale_format, uint32_t* below, uint32_t* above, uint32_t* flushed,
+                double* err2, double* sig2, uint32_t* hist /* may be NULL */, int64_t R, int64_t C, int axis, int64_t gs,
+                void* stream);
+
 /* ---- K4: forward and NQ backward of one tensor in a single pass (benchmark path) ---
  * Same results as lq_fq_forward followed by lq_fq_scale_grad (out, max|q| and the vote count bit for bit; on
  * streaming-size tensors the vote sum may differ by fp32 summation order, ~1e-7 relative); P is read once.  */

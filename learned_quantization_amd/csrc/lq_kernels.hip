@@ -58,6 +58,7 @@
 #include "lq_scale_init.hpp"
 #include "lq_mx.hpp"
 #include "lq_group_stats.hpp"
+#include "lq_mx_stats.hpp"
 
 namespace lq {
 
@@ -1748,6 +1749,47 @@ int lq_group_stats(const float* P, const float* s, const float* b, int32_t qmin,
     const bool rne = rounding == LQ_ROUND_NEAREST_EVEN;
     if (b) return rne ? launch_group_stats<true, true>(L, sp, st) : launch_group_stats<false, true>(L, sp, st);
     return rne ? launch_group_stats<true, false>(L, sp, st) : launch_group_stats<false, false>(L, sp, st);
+}
+
+// ---- per-group statistics of the microscaling quantizer (lq_mx_stats.hpp) ----
+int lq_mx_stats(const float* P, const float* s, int format, int scale_format, uint32_t* below, uint32_t* above, uint32_t* flushed,
+                double* err2, double* sig2, uint32_t* hist, int64_t R, int64_t C, int axis, int64_t gs, void* stream) {
+    const char* fn = __func__;
+    int rc = check_group(fn, R, C, axis, gs);
+    if (rc) return rc;
+    LQ_REQUIRE_PTR_FN(fn, P);
+    LQ_REQUIRE_PTR_FN(fn, s);
+    LQ_REQUIRE_PTR_FN(fn, below);
+    LQ_REQUIRE_PTR_FN(fn, above);
+    LQ_REQUIRE_PTR_FN(fn, flushed);
+    if (!err2 || !sig2) return fail(LQ_EINVAL, "%s: argument '%s' is NULL", fn, err2 ? "sig2" : "err2");
+    if (!aligned(err2, 8) || !aligned(sig2, 8)) return fail(LQ_EALIGN, "%s: err2 and sig2 must be 8-byte aligned", fn);
+    if (hist && !aligned(hist, 4)) return fail(LQ_EALIGN, "%s: hist is not 4-byte aligned", fn);
+    if ((rc = check_mx(fn, format, scale_format))) return rc;
+    MxStatsParams sp{};
+    sp.mp.g = group_params(P, s, 0, 0, R, C, axis, gs);
+    mx_fill(sp.mp, format, scale_format);
+    sp.below = below;
+    sp.above = above;
+    sp.flushed = flushed;
+    sp.err2 = err2;
+    sp.sig2 = sig2;
+    sp.hist = hist;
+    sp.nbins = hist ? (int32_t)1 << sp.mp.bits : 0;
+    const bool vec = group_vec_ok(sp.mp.g, axis) && aligned(P, 16);
+    // the backward's launch shape (group_launch without a row split) with the block's histogram in dynamic LDS
+    const GroupLaunch L = group_launch(sp.mp.g, axis, vec, false, kGroupGridY);
+    const size_t lds = (size_t)sp.nbins * sizeof(uint32_t);
+    hipStream_t st = (hipStream_t)stream;
+    switch (L.form) {
+        case GROUP_COLS4: hipLaunchKernelGGL((k_mx_stats_cols<4, kGroupColsLanes4>), L.grid, dim3(kBlock), lds, st, sp); break;
+        case GROUP_COLS1: hipLaunchKernelGGL((k_mx_stats_cols<1, kGroupColsLanes1>), L.grid, dim3(kBlock), lds, st, sp); break;
+        case GROUP_ROWS4: hipLaunchKernelGGL((k_mx_stats_rows<4>), L.grid, dim3(kBlock), lds, st, sp, L.log_team); break;
+        default: hipLaunchKernelGGL((k_mx_stats_rows<1>), L.grid, dim3(kBlock), lds, st, sp, L.log_team); break;
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(LQ_EHIP, "microscaling statistics %s launch: %s", L.form <= GROUP_COLS1 ? "column" : "row", hipGetErrorString(e));
+    return LQ_OK;
 }
 
 int lq_fq_fwd_bwd_fused(const float* P, const float* s, const float* dy, float lambda, float* out, float* ds, void* ws,

@@ -60,8 +60,8 @@ __device__ __forceinline__ float mx_round(float t, const GroupMxParams& mp) {
     return copysignf(rintf(fabsf(t) * to_int) * u, t);
 }
 
-// the encoding of a clamped grid value q, as a float (the integer view's store converts it)
-__device__ __forceinline__ float mx_code(float q, int M, int emin, int bits) {
+// the encoding of a clamped grid value q, as the integer it is (lq_mx_stats.hpp bins by it)
+__device__ __forceinline__ uint32_t mx_code_bits(float q, int M, int emin, int bits) {
     const uint32_t qb = __float_as_uint(q);
     const uint32_t ab = qb & 0x7fffffffu;
     uint32_t mag;
@@ -71,9 +71,11 @@ __device__ __forceinline__ float mx_code(float q, int M, int emin, int bits) {
         mag = (ab >> (23 - M)) - ((uint32_t)(126 + emin) << M);           // (e - emin + 1) * 2^M + the M mantissa bits
     }
     const uint32_t top = 1u << (bits - 1);
-    const uint32_t code = (q != q) ? top - 1u : ((qb >> 31) ? top : 0u) + mag;      // a NaN has no sign to keep: all ones below the sign bit
-    return (float)code;
+    return (q != q) ? top - 1u : ((qb >> 31) ? top : 0u) + mag;      // a NaN has no sign to keep: all ones below the sign bit
 }
+
+// the same as a float (the integer view's store converts it)
+__device__ __forceinline__ float mx_code(float q, int M, int emin, int bits) { return (float)mx_code_bits(q, M, emin, bits); }
 
 template <bool RNE>
 struct GroupStep<RNE, GroupMxParams> {

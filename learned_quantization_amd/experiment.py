@@ -26,7 +26,7 @@ import torch
 
 from . import layers as L
 from .export import save_compress_parameters, save_packed_parameters
-from .tracking import AccuracyLossTrackingCallBack, GroupQuantTrackingCallback, NestedScaleTrackingCallback
+from .tracking import AccuracyLossTrackingCallBack, GroupQuantTrackingCallback, MxQuantTrackingCallback, NestedScaleTrackingCallback
 from .train import DriverParser, Trainer, synthetic_batch
 
 
@@ -203,13 +203,14 @@ def main(argv=None):
     log_model_structure(tr.model, log_dir)
     # the scale-tracking callback reads the unclipped integer view under one-axis scales: group-wise layers get the clipped
     # quantizer's own statistics instead (clipped shares, SQNR, codes in use), after the callbacks that were attached before
-    # layers with an element format have neither: both callbacks read an integer view, and the statistics kernel bins the codes of
-    # an integer range.  Such a run keeps the accuracy / loss log and the exports
+    # layers with an element format get the microscaling quantizer's statistics (saturated and flushed shares, SQNR, encodings in
+    # use): the other two callbacks read an integer view or bin the codes of an integer range
     callbacks = [NestedScaleTrackingCallback(layer, log_dir) for layer in tr.custom_layers
                  if layer.group_size is None and layer.element_format is None]
     group_callbacks = [GroupQuantTrackingCallback(layer, log_dir) for layer in tr.custom_layers
                        if layer.group_size is not None and layer.element_format is None]
-    callbacks += group_callbacks
+    mx_callbacks = [MxQuantTrackingCallback(layer, log_dir) for layer in tr.custom_layers if layer.element_format is not None]
+    callbacks += group_callbacks + mx_callbacks
     callbacks.append(AccuracyLossTrackingCallBack(log_dir))
     t0 = time.perf_counter()
     history = fit(tr, args.epochs, args.steps_per_epoch, args.batch, callbacks, args.lr,
@@ -229,6 +230,10 @@ def main(argv=None):
             stats = group_callbacks[0].stats()["kernel"]
             line.update({"first_layer_sqnr_db": stats["sqnr_db"], "first_layer_clip_low": stats["clip_low"],
                          "first_layer_clip_high": stats["clip_high"]})
+        if mx_callbacks:
+            stats = mx_callbacks[0].stats()["kernel"]
+            line.update({"first_layer_sqnr_db": stats["sqnr_db"], "first_layer_sat_low": stats["sat_low"],
+                         "first_layer_sat_high": stats["sat_high"], "first_layer_flushed": stats["flushed"]})
     if packed is not None:
         line["packed"] = packed
     if args.loss_values:

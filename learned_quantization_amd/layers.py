@@ -148,7 +148,7 @@ class CustomQuantizedScaleLayer(nn.Module):
     ``orientation="groupwise"`` (``group_size`` defaults to 32, the MX block) -- or "scalar", the one-group form the host layers
     give their biases -- and takes neither a range, a rounding, an offset nor a loss term; the gradients are the straight-through
     ones (``scale_gradient`` is "ste").  ``init_scale`` takes "mx" / "cover" (ops.scale_init_mx), ``quantized_integers`` returns
-    the elements' encodings, ``quant_stats`` is not available.
+    the elements' encodings, the statistics are ``mx_stats`` (``quant_stats`` is the integer range's and raises).
     """
 
     _SCALE_NAMES = {"rowwise": "Rowwise-scaler", "columnwise": "Columnwise-scaler",
@@ -313,7 +313,7 @@ class CustomQuantizedScaleLayer(nn.Module):
         (tracking.NestedScaleTrackingCallback)."""
         if self.element_format is not None:
             raise ValueError("quant_stats on a layer with an element format: the statistics kernel bins the codes of an integer range; "
-                             "a microscaling layer has none (its saturation counts are ops.fq_backward_mx's `clipped`)")
+                             "a microscaling layer has none (its statistics are `mx_stats`)")
         if self.q_range is None:
             raise ValueError("quant_stats needs bits or q_range: the unbounded quantizer clips nothing and has no fixed set of codes; "
                              "its statistics are ops.q_minmax / ops.q_unique / ops.q_absmax_over_axis "
@@ -323,6 +323,19 @@ class CustomQuantizedScaleLayer(nn.Module):
         with torch.no_grad():
             return ops.group_stats(parameter.detach(), self.scale.data, *self.q_range, self.group_size,
                                    offset=self.offset.data if self.asymmetric else None, rounding=self.rounding, want_hist=want_hist)
+
+    def mx_stats(self, parameter, want_hist=True):
+        """Statistics of this layer's microscaling quantizer on ``parameter`` as the scale stands now (ops.mx_stats, with the
+        layer's own element format, scale format and group size): an ops.MxStats record of device tensors, to be read with
+        ops.summarize_mx_stats.  One launch, no synchronisation.  A layer without an element format: ValueError; its statistics
+        are ``quant_stats``."""
+        if self.element_format is None:
+            raise ValueError("mx_stats on a layer without an element format: the statistics of an integer range are quant_stats")
+        if not self.built:
+            raise ValueError("mx_stats before the layer is built: there is no scale yet")
+        with torch.no_grad():
+            return ops.mx_stats(parameter.detach(), self.scale.data, self.element_format, self.group_size, self.scale_format,
+                                want_hist=want_hist)
 
     def quantized_integers(self, parameter, dtype=torch.float32):
         """The integer view of ``parameter`` under this layer's quantizer: floor(P/s), clamped when the layer has a range (then
@@ -827,7 +840,7 @@ def quant_stats(model: nn.Module, want_hist=True) -> dict:
     ops.summarize_stats dict of the tensor's ``CustomQuantizedScaleLayer.quant_stats``.  One launch per tensor, then all records
     go to the host together in one copy (one synchronisation: call it between steps, never inside a capture).  Every layer
     needs a range: ValueError otherwise.  Tensors of layers with an element format are skipped: the statistics kernel bins the
-    codes of an integer range."""
+    codes of an integer range; theirs is ``mx_quant_stats``."""
     tensors = [t for t in quantized_tensors(model) if t[2].element_format is None]
     for name, _, nested in tensors:      # before any launch
         if nested.q_range is None:
@@ -837,6 +850,18 @@ def quant_stats(model: nn.Module, want_hist=True) -> dict:
     records = [nested.quant_stats(param.data, want_hist and nested.q_range[1] - nested.q_range[0] < ops.STATS_MAX_BINS)
                for _, param, nested in tensors]
     summaries = ops.summarize_stats_many(records, [param.numel() for _, param, _ in tensors])
+    return {name: summary for (name, _, _), summary in zip(tensors, summaries)}
+
+
+def mx_quant_stats(model: nn.Module, want_hist=True) -> dict:
+    """{reference name: summary} of every tensor of ``model`` whose layer has an element format (``quantized_tensors``' walk;
+    the others are skipped: theirs is ``quant_stats``): the ops.summarize_mx_stats dict of the tensor's
+    ``CustomQuantizedScaleLayer.mx_stats``.  One launch per tensor, then all records go to the host together in one copy (one
+    synchronisation: call it between steps, never inside a capture).  ``{}`` for a model without such layers."""
+    tensors = [t for t in quantized_tensors(model) if t[2].element_format is not None]
+    records = [nested.mx_stats(param.data, want_hist) for _, param, nested in tensors]
+    summaries = ops.summarize_mx_stats_many(records, [param.numel() for _, param, _ in tensors],
+                                            [nested.element_format for _, _, nested in tensors])
     return {name: summary for (name, _, _), summary in zip(tensors, summaries)}
 
 

@@ -575,7 +575,7 @@ def _stats_to_host(records):
             a = flat[at:at + t.numel()].reshape(tuple(t.shape))
             at += t.numel()
             fields.append(a if t.dtype.is_floating_point else a.astype(np.int64))
-        host.append(GroupStats(*fields))
+        host.append(type(rec)(*fields) if hasattr(rec, "_fields") else GroupStats(*fields))      # GroupStats or MxStats
     return host
 
 
@@ -619,6 +619,92 @@ def summarize_stats_many(records, numels) -> list:
     """``summarize_stats`` of several records with all of them copied to the host together (one device->host copy)."""
     host = _stats_to_host(list(records))
     return [_summarize_host(rec, int(n)) for rec, n in zip(host, numels)]
+
+
+class MxStats(NamedTuple):
+    """What ``mx_stats`` returns, all on the device: ``below`` / ``above`` / ``flushed`` (int32 tensors holding the uint32 counts)
+    and ``err2`` / ``sig2`` (float64) in the scale's shape, ``hist`` (int32, 2^bits bins in code order) or None."""
+    below: torch.Tensor
+    above: torch.Tensor
+    flushed: torch.Tensor
+    err2: torch.Tensor
+    sig2: torch.Tensor
+    hist: Optional[torch.Tensor]
+
+
+def mx_stats(parameter: torch.Tensor, scale: torch.Tensor, element_format: str, group_size: Optional[int] = MX_GROUP_SIZE,
+             scale_format: str = "e8m0", *, want_hist: bool = True) -> MxStats:
+    """Statistics of the microscaling quantizer on ``parameter`` under ``scale`` as it is now (include/lq_hip.h, lq_mx_stats): per
+    group the elements that saturate below -max and above +max, the non-zero elements the grid flushes to zero, and the f64 sums
+    of squared error and squared signal; per tensor the histogram of the elements' encodings (the forward's code view).  Geometry
+    as ``fq_forward_mx``.  One launch, read only, no synchronisation."""
+    fmt = check_element_format(element_format)
+    sf = check_scale_format(scale_format)
+    lib = _hip.load()
+    p, s, (R, C, axis, gs) = _mx_param(parameter, scale, group_size)
+    below = torch.empty_like(s, dtype=torch.int32)
+    above = torch.empty_like(s, dtype=torch.int32)
+    flushed = torch.empty_like(s, dtype=torch.int32)
+    err2 = torch.empty_like(s, dtype=torch.float64)
+    sig2 = torch.empty_like(s, dtype=torch.float64)
+    hist = torch.zeros(1 << fmt.bits, dtype=torch.int32, device=p.device) if want_hist else None
+    _hip.check(lib.lq_mx_stats(_hip.ptr(p), _hip.ptr(s), fmt.id, sf, _hip.ptr(below), _hip.ptr(above), _hip.ptr(flushed),
+                               _hip.ptr(err2), _hip.ptr(sig2), _hip.ptr(hist), R, C, axis, gs, _hip.stream_ptr(p.device)),
+               "lq_mx_stats")
+    return MxStats(below, above, flushed, err2, sig2, hist)
+
+
+def _summarize_mx_host(rec: MxStats, numel: int, element_format: str) -> dict:
+    fmt = check_element_format(element_format)
+    n = float(numel)
+    err2 = np.asarray(rec.err2, dtype=np.float64).reshape(-1)
+    sig2 = np.asarray(rec.sig2, dtype=np.float64).reshape(-1)
+    out = {
+        "sat_low": float(np.asarray(rec.below, dtype=np.float64).sum() / n),
+        "sat_high": float(np.asarray(rec.above, dtype=np.float64).sum() / n),
+        "flushed": float(np.asarray(rec.flushed, dtype=np.float64).sum() / n),
+        "sqnr_db": _sqnr_db(float(sig2.sum()), float(err2.sum())),
+        "worst_group_sqnr_db": min((_sqnr_db(float(a), float(e)) for a, e in zip(sig2, err2)),
+                                   key=lambda v: -math.inf if math.isnan(v) else v),
+        "used_codes": None,
+        "entropy_bits": None,
+        "zero": None,
+        "subnormal": None,
+    }
+    if rec.hist is not None:
+        h = np.asarray(rec.hist, dtype=np.float64).reshape(-1)
+        if h.size != 1 << fmt.bits:
+            raise ValueError(f"a histogram of {h.size} bins is not {element_format}'s ({1 << fmt.bits} codes)")
+        used, total = h[h > 0], float(h.sum())
+        out["used_codes"] = int(used.size)
+        pr = used / total if total > 0 else used
+        out["entropy_bits"] = float(max(0.0, -(pr * np.log2(pr)).sum())) if used.size else 0.0
+        mag = np.arange(h.size) & ((1 << (fmt.bits - 1)) - 1)      # the code below its sign bit: exponent field, then M mantissa bits
+        out["zero"] = float(h[mag == 0].sum() / total) if total > 0 else 0.0
+        out["subnormal"] = float(h[(mag >> fmt.M == 0) & (mag != 0)].sum() / total) if total > 0 else 0.0
+    return out
+
+
+def summarize_mx_stats(record: MxStats, numel: int, *, element_format: str) -> dict:
+    """Host floats of one ``mx_stats`` record of a tensor of ``numel`` elements, computed in float64 on the host after ONE
+    device->host copy: ``sat_low`` / ``sat_high`` / ``flushed`` (shares of the elements saturated below / above and flushed to
+    zero), ``sqnr_db`` and ``worst_group_sqnr_db`` (``summarize_stats``' conventions), and from the histogram (None without one)
+    ``used_codes``, ``entropy_bits``, ``zero`` (share of the codes +0 and -0) and ``subnormal`` (share of the codes with exponent
+    field 0 and a non-zero mantissa).  ``element_format`` names the fields of a code.  The record's fields may be device tensors,
+    host tensors or NumPy arrays."""
+    numel = int(numel)
+    if numel < 1:
+        raise ValueError(f"numel must be positive, got {numel}")
+    check_element_format(element_format)
+    if any(isinstance(t, torch.Tensor) for t in record):
+        record = _stats_to_host([MxStats(*(t if t is None or isinstance(t, torch.Tensor) else torch.as_tensor(t) for t in record))])[0]
+    return _summarize_mx_host(record, numel, element_format)
+
+
+def summarize_mx_stats_many(records, numels, element_formats) -> list:
+    """``summarize_mx_stats`` of several records with all of them copied to the host together (one device->host copy)."""
+    host = _stats_to_host(list(records))
+    return [_summarize_mx_host(rec, int(n), f) for rec, n, f in zip(host, numels, element_formats)]
 
 
 def fq_fwd_bwd_fused(parameter: torch.Tensor, scale: torch.Tensor, dy: torch.Tensor, penalty_threshold: float,

@@ -14,7 +14,8 @@ results cross PCIe.  The reference's per-epoch dump of every raw kernel value (:
 
 ``GroupQuantTrackingCallback`` (not in the reference) logs the clipped b-bit quantizer in the same format: per group the
 clipped shares on either side and the SQNR, per tensor the SQNR, the codes in use and their entropy, from one
-``lq_group_stats`` launch per tensor.
+``lq_group_stats`` launch per tensor.  ``MxQuantTrackingCallback`` does the same for a layer with an element format (the OCP
+microscaling quantizer): saturated and flushed shares, SQNR, the encodings in use, from one ``lq_mx_stats`` launch per tensor.
 """
 from __future__ import annotations
 
@@ -220,6 +221,112 @@ class GroupQuantTrackingCallback:
                 for code, count in enumerate(rec.hist):
                     if count:
                         f.write(f"{np.float32(q.q_range[0] + code)}, {int(count)}\n")
+
+    def on_train_end(self, logs=None):
+        self._dump_hist("hist_end")
+
+    def on_train_begin(self, logs=None):
+        self._dump_hist("hist_begin")
+
+
+class MxQuantTrackingCallback:
+    """Per-epoch logs of a layer with an element format (the OCP microscaling quantizer), the counterpart of
+    ``GroupQuantTrackingCallback``: same directory layout and ``Epoch N`` + one-value-per-line format.  For the kernel and the
+    bias, per epoch end (group values in the scale's memory order):
+
+      <name>_<shape>_<scale name>_<scale shape>.log    the stored scales
+      Scale_exponent_<name>_<shape>.log                log2 of each group's effective scale (ops.mx_effective_scale; NaN: invalid)
+      Sat_low_<name>_<shape>.log / Sat_high_...        share of each group's elements saturated below -max / above +max
+      Flushed_<name>_<shape>.log                       share of each group's elements that are not zero and become zero
+      SQNR_dB_<name>_<shape>.log                       10 log10(sig2 / err2) of each group
+      SQNR_dB_tensor_<name>_<shape>.log                the same of the whole tensor (one value per epoch)
+      Used_codes_<name>_<shape>.log                    encodings of the format that occur
+      Code_entropy_bits_<name>_<shape>.log             Shannon entropy of the code distribution
+
+    and on train begin / train end the code histogram as ``value, count`` lines in code order, the value from
+    ops.mx_decode_table (``Unique_initial_quantized_...`` / ``Unique_quantized_...``).  One lq_mx_stats launch per tensor and one
+    device->host copy per call."""
+
+    _KEYS = ("scale", "exponent", "sat_low", "sat_high", "flushed", "sqnr", "sqnr_tensor", "used", "entropy")
+
+    def __init__(self, layer, log_dir):
+        self.layer = layer
+        if hasattr(layer, "kernel"):
+            param, nested, kernel_name = layer.kernel, layer.nested_q_k_layer, f"Kernel_{layer.name}"
+        else:
+            param, nested, kernel_name = layer.W, layer.nested_q_w_layer, "Weights"
+        bias_name = f"Bias_{layer.name}" if hasattr(layer, "kernel") else "Bias"
+        self.tensors = [("kernel", kernel_name, param, nested)]
+        if getattr(layer, "b", None) is not None and getattr(layer, "nested_q_b_layer", None) is not None:
+            self.tensors.append(("bias", bias_name, layer.b, layer.nested_q_b_layer))
+        for _, name, _, q in self.tensors:      # before any directory is made
+            if getattr(q, "element_format", None) is None:
+                raise ValueError(f"MxQuantTrackingCallback: the quantizer of {name} has no element format; use "
+                                 "GroupQuantTrackingCallback (a range) or NestedScaleTrackingCallback")
+        e, t, b0 = (os.path.join(log_dir, d) for d in ("on_epoch_end", "on_train_end", "on_train_begin"))
+        for d in (e, t, b0):
+            os.makedirs(d, exist_ok=True)
+        self.paths, self.sizes = {}, {}
+        for what, name, p, q in self.tensors:
+            self.sizes[what] = group_sizes(p, q.scale, q.group_size)
+            psh, ssh = _shape(p), _shape(q.scale)
+            self.paths[what] = {
+                "scale": f"{e}/{name}_{psh}_{q.scale_name}_{ssh}.log",
+                "exponent": f"{e}/Scale_exponent_{name}_{psh}.log",
+                "sat_low": f"{e}/Sat_low_{name}_{psh}.log",
+                "sat_high": f"{e}/Sat_high_{name}_{psh}.log",
+                "flushed": f"{e}/Flushed_{name}_{psh}.log",
+                "sqnr": f"{e}/SQNR_dB_{name}_{psh}.log",
+                "sqnr_tensor": f"{e}/SQNR_dB_tensor_{name}_{psh}.log",
+                "used": f"{e}/Used_codes_{name}_{psh}.log",
+                "entropy": f"{e}/Code_entropy_bits_{name}_{psh}.log",
+                "hist_begin": f"{b0}/Unique_initial_quantized_{name}_{psh}_{q.scale_name}_{ssh}.log",
+                "hist_end": f"{t}/Unique_quantized_{name}_{psh}_{q.scale_name}_{ssh}.log",
+            }
+
+    def epoch_files(self):
+        """Every file ``on_epoch_end`` appends to."""
+        return [self.paths[what][k] for what, *_ in self.tensors for k in self._KEYS]
+
+    def _records(self):
+        """The host copies of every tensor's statistics, taken together."""
+        return ops._stats_to_host([q.mx_stats(p.data) for _, _, p, q in self.tensors])
+
+    def stats(self):
+        """{"kernel": summary, "bias": summary}: ops.summarize_mx_stats of the tensors as they are now."""
+        return {what: ops._summarize_mx_host(rec, p.numel(), q.element_format)
+                for (what, _, p, q), rec in zip(self.tensors, self._records())}
+
+    _append = staticmethod(NestedScaleTrackingCallback._append)
+
+    def on_epoch_end(self, epoch, logs=None):
+        hdr = f"Epoch {epoch}\n"
+        out = {}
+        for (what, _, p, q), rec in zip(self.tensors, self._records()):
+            paths, n = self.paths[what], self.sizes[what].reshape(-1).astype(np.float64)
+            st = ops._summarize_mx_host(rec, p.numel(), q.element_format)
+            stored = q.scale.detach().flatten().cpu().numpy()
+            with np.errstate(all="ignore"):
+                exponent = np.log2(ops.mx_effective_scale(stored, q.scale_format).astype(np.float64))
+            self._append(paths["scale"], hdr, stored)
+            self._append(paths["exponent"], hdr, exponent)
+            self._append(paths["sat_low"], hdr, rec.below.reshape(-1) / n)
+            self._append(paths["sat_high"], hdr, rec.above.reshape(-1) / n)
+            self._append(paths["flushed"], hdr, rec.flushed.reshape(-1) / n)
+            self._append(paths["sqnr"], hdr, [ops._sqnr_db(float(a), float(b)) for a, b in zip(rec.sig2.reshape(-1), rec.err2.reshape(-1))])
+            self._append(paths["sqnr_tensor"], hdr, [st["sqnr_db"]])
+            self._append(paths["used"], hdr, [st["used_codes"]])
+            self._append(paths["entropy"], hdr, [st["entropy_bits"]])
+            out[what] = st
+        return out
+
+    def _dump_hist(self, key):
+        for (what, _, _, q), rec in zip(self.tensors, self._records()):
+            table = ops.mx_decode_table(q.element_format)
+            with open(self.paths[what][key], "a") as f:
+                for code, count in enumerate(rec.hist):
+                    if count:
+                        f.write(f"{table[code]}, {int(count)}\n")      # -0.0 prints as such
 
     def on_train_end(self, logs=None):
         self._dump_hist("hist_end")

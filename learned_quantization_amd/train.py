@@ -598,6 +598,9 @@ def build_parser():
     ap.add_argument("--quant-stats", action="store_true",
                     help="with --bits: add layers.quant_stats of the final parameters to the result line (per tensor: clipped "
                          "shares, SQNR in dB, codes in use, code entropy); taken after the timed steps")
+    ap.add_argument("--mx-stats", action="store_true",
+                    help="with --element-format: add layers.mx_quant_stats of the final parameters to the result line (per tensor: "
+                         "saturated and flushed shares, SQNR in dB, encodings in use, code entropy); taken after the timed steps")
     return ap
 
 
@@ -606,6 +609,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.quant_stats and args.bits is None:
         ap.error("--quant-stats needs --bits: the statistics are those of a quantizer with a range")
+    if args.mx_stats and args.element_format is None:
+        ap.error("--mx-stats needs --element-format: the statistics are those of the microscaling quantizer")
 
     # read by the HSA runtime when it initialises (the first torch.cuda call below): the host driver only supports dmabuf IPC
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -668,6 +673,7 @@ def main(argv=None):
         dt = float(t)
     log_rows = tr.flush_loss_log() if args.loss_values and rank == 0 else None     # every rank holds the same rows: one writes
     quant_stats = L.quant_stats(tr.model) if args.quant_stats and rank == 0 else None      # after the clock has stopped
+    mx_stats = L.mx_quant_stats(tr.model) if args.mx_stats and rank == 0 else None
     if rank == 0:
         n_q = sum(p.numel() for l in tr.custom_layers for p in l._regularized())
         print(json.dumps({
@@ -692,7 +698,8 @@ def main(argv=None):
             **({"asymmetric": True} if tr.asymmetric else {}),
             **({"scale_init": tr.scale_init} if tr.scale_init is not None else {}),
             **({"loss_values": True, "loss_log_rows": log_rows[0], "loss_log_dropped": log_rows[1]} if log_rows else {}),
-            **({"quant_stats": quant_stats} if quant_stats is not None else {})}))
+            **({"quant_stats": quant_stats} if quant_stats is not None else {}),
+            **({"mx_stats": mx_stats} if mx_stats is not None else {})}))
         if args.export_dir:
             from .export import save_compress_parameters
             print(json.dumps(save_compress_parameters(tr.model, args.export_dir)))

@@ -1418,14 +1418,16 @@ extern "C++" {      // templates inside the C-linkage block
 // The four instantiations of a kernel family, in launch_group_form's order: columns V = 4, V = 1, rows V = 4, V = 1
 #define LQ_GROUP_FAMILY(COLS, ROWS, ...) \
     COLS<__VA_ARGS__, 4, kGroupColsLanes4>, COLS<__VA_ARGS__, 1, kGroupColsLanes1>, ROWS<__VA_ARGS__, 4>, ROWS<__VA_ARGS__, 1>
+// the same of a family with no template arguments ahead of V
+#define LQ_GROUP_FAMILY0(COLS, ROWS) COLS<4, kGroupColsLanes4>, COLS<1, kGroupColsLanes1>, ROWS<4>, ROWS<1>
 
-// Launches the member of a family that the form names; `family` opens the message of a failed launch
+// Launches the member of a family that the form names; `family` opens the message of a failed launch, `lds` is dynamic LDS in bytes
 template <class Args>
 static int launch_group_form(const GroupLaunch& L, void (*cols4)(Args), void (*cols1)(Args), void (*rows4)(Args, int),
-                             void (*rows1)(Args, int), const Args& a, const char* family, hipStream_t st) {
+                             void (*rows1)(Args, int), const Args& a, const char* family, hipStream_t st, size_t lds = 0) {
     const bool cols = L.form <= GROUP_COLS1;
-    if (cols) hipLaunchKernelGGL(L.form == GROUP_COLS4 ? cols4 : cols1, L.grid, dim3(kBlock), 0, st, a);
-    else hipLaunchKernelGGL(L.form == GROUP_ROWS4 ? rows4 : rows1, L.grid, dim3(kBlock), 0, st, a, L.log_team);
+    if (cols) hipLaunchKernelGGL(L.form == GROUP_COLS4 ? cols4 : cols1, L.grid, dim3(kBlock), lds, st, a);
+    else hipLaunchKernelGGL(L.form == GROUP_ROWS4 ? rows4 : rows1, L.grid, dim3(kBlock), lds, st, a, L.log_team);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(LQ_EHIP, "%s %s launch: %s", family, cols ? "column" : "row", hipGetErrorString(e));
     return LQ_OK;
@@ -1688,24 +1690,20 @@ int lq_scale_init_mx(const float* P, float* s, int format, int method, float min
     return launch_scale_init<kInitMxCover, false>(ip, gp, axis, vec, "microscaling scale-init", stream);
 }
 
-// ---- per-group statistics (lq_group_stats.hpp) ----
-extern "C++" {
-// The backward's launch shape (group_launch without a row split) with the block's histogram in dynamic LDS
-template <bool RNE, bool AFF>
-static int launch_group_stats(const GroupLaunch& L, const StatsParams& sp, hipStream_t st) {
-    const size_t lds = sp.hist ? (size_t)sp.nbins * sizeof(uint32_t) : 0;
-    switch (L.form) {
-        case GROUP_COLS4: hipLaunchKernelGGL((k_stats_cols<RNE, AFF, 4, kGroupColsLanes4>), L.grid, dim3(kBlock), lds, st, sp); break;
-        case GROUP_COLS1: hipLaunchKernelGGL((k_stats_cols<RNE, AFF, 1, kGroupColsLanes1>), L.grid, dim3(kBlock), lds, st, sp); break;
-        case GROUP_ROWS4: hipLaunchKernelGGL((k_stats_rows<RNE, AFF, 4>), L.grid, dim3(kBlock), lds, st, sp, L.log_team); break;
-        default: hipLaunchKernelGGL((k_stats_rows<RNE, AFF, 1>), L.grid, dim3(kBlock), lds, st, sp, L.log_team); break;
-    }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(LQ_EHIP, "group statistics %s launch: %s", L.form <= GROUP_COLS1 ? "column" : "row", hipGetErrorString(e));
+// ---- per-group statistics (lq_group_stats.hpp, lq_mx_stats.hpp) ----
+// The output pointers of both entry points; `flushed` is checked where the quantizer has the third count
+static int check_stats_outputs(const char* fn, const uint32_t* below, const uint32_t* above, bool has_flushed, const uint32_t* flushed,
+                               const double* err2, const double* sig2, const uint32_t* hist) {
+    LQ_REQUIRE_PTR_FN(fn, below);
+    LQ_REQUIRE_PTR_FN(fn, above);
+    if (has_flushed) LQ_REQUIRE_PTR_FN(fn, flushed);
+    if (!err2 || !sig2) return fail(LQ_EINVAL, "%s: argument '%s' is NULL", fn, err2 ? "sig2" : "err2");
+    if (!aligned(err2, 8) || !aligned(sig2, 8)) return fail(LQ_EALIGN, "%s: err2 and sig2 must be 8-byte aligned", fn);
+    if (hist && !aligned(hist, 4)) return fail(LQ_EALIGN, "%s: hist is not 4-byte aligned", fn);
     return LQ_OK;
 }
-}  // extern "C++"
 
+// Both launch in the backward's shape (group_launch without a row split) with the block's histogram, nbins words, in dynamic LDS
 int lq_group_stats(const float* P, const float* s, const float* b, int32_t qmin, int32_t qmax, int rounding, uint32_t* below,
                    uint32_t* above, double* err2, double* sig2, uint32_t* hist, int64_t R, int64_t C, int axis, int64_t gs,
                    void* stream) {
@@ -1715,11 +1713,7 @@ int lq_group_stats(const float* P, const float* s, const float* b, int32_t qmin,
     LQ_REQUIRE_PTR_FN(fn, P);
     LQ_REQUIRE_PTR_FN(fn, s);
     if (b && !aligned(b, 4)) return fail(LQ_EALIGN, "%s: b is not 4-byte aligned", fn);
-    LQ_REQUIRE_PTR_FN(fn, below);
-    LQ_REQUIRE_PTR_FN(fn, above);
-    if (!err2 || !sig2) return fail(LQ_EINVAL, "%s: argument '%s' is NULL", fn, err2 ? "sig2" : "err2");
-    if (!aligned(err2, 8) || !aligned(sig2, 8)) return fail(LQ_EALIGN, "%s: err2 and sig2 must be 8-byte aligned", fn);
-    if (hist && !aligned(hist, 4)) return fail(LQ_EALIGN, "%s: hist is not 4-byte aligned", fn);
+    if ((rc = check_stats_outputs(fn, below, above, false, nullptr, err2, sig2, hist))) return rc;
     if ((rc = check_clip_range(fn, qmin, qmax))) return rc;
     if ((rc = check_rounding(fn, rounding))) return rc;
     const int64_t codes = (int64_t)qmax - (int64_t)qmin + 1;
@@ -1745,13 +1739,16 @@ int lq_group_stats(const float* P, const float* s, const float* b, int32_t qmin,
     sp.nb = gp.nb;
     const bool vec = group_vec_ok(gp, axis) && aligned(P, 16);
     const GroupLaunch L = group_launch(gp, axis, vec, false, kGroupGridY);
+    const size_t lds = (size_t)sp.nbins * sizeof(uint32_t);
     hipStream_t st = (hipStream_t)stream;
+    const char* family = "group statistics";
     const bool rne = rounding == LQ_ROUND_NEAREST_EVEN;
-    if (b) return rne ? launch_group_stats<true, true>(L, sp, st) : launch_group_stats<false, true>(L, sp, st);
-    return rne ? launch_group_stats<true, false>(L, sp, st) : launch_group_stats<false, false>(L, sp, st);
+    if (b && rne) return launch_group_form(L, LQ_GROUP_FAMILY(k_stats_cols, k_stats_rows, true, true), sp, family, st, lds);
+    if (b) return launch_group_form(L, LQ_GROUP_FAMILY(k_stats_cols, k_stats_rows, false, true), sp, family, st, lds);
+    if (rne) return launch_group_form(L, LQ_GROUP_FAMILY(k_stats_cols, k_stats_rows, true, false), sp, family, st, lds);
+    return launch_group_form(L, LQ_GROUP_FAMILY(k_stats_cols, k_stats_rows, false, false), sp, family, st, lds);
 }
 
-// ---- per-group statistics of the microscaling quantizer (lq_mx_stats.hpp) ----
 int lq_mx_stats(const float* P, const float* s, int format, int scale_format, uint32_t* below, uint32_t* above, uint32_t* flushed,
                 double* err2, double* sig2, uint32_t* hist, int64_t R, int64_t C, int axis, int64_t gs, void* stream) {
     const char* fn = __func__;
@@ -1759,12 +1756,7 @@ int lq_mx_stats(const float* P, const float* s, int format, int scale_format, ui
     if (rc) return rc;
     LQ_REQUIRE_PTR_FN(fn, P);
     LQ_REQUIRE_PTR_FN(fn, s);
-    LQ_REQUIRE_PTR_FN(fn, below);
-    LQ_REQUIRE_PTR_FN(fn, above);
-    LQ_REQUIRE_PTR_FN(fn, flushed);
-    if (!err2 || !sig2) return fail(LQ_EINVAL, "%s: argument '%s' is NULL", fn, err2 ? "sig2" : "err2");
-    if (!aligned(err2, 8) || !aligned(sig2, 8)) return fail(LQ_EALIGN, "%s: err2 and sig2 must be 8-byte aligned", fn);
-    if (hist && !aligned(hist, 4)) return fail(LQ_EALIGN, "%s: hist is not 4-byte aligned", fn);
+    if ((rc = check_stats_outputs(fn, below, above, true, flushed, err2, sig2, hist))) return rc;
     if ((rc = check_mx(fn, format, scale_format))) return rc;
     MxStatsParams sp{};
     sp.mp.g = group_params(P, s, 0, 0, R, C, axis, gs);
@@ -1777,19 +1769,9 @@ int lq_mx_stats(const float* P, const float* s, int format, int scale_format, ui
     sp.hist = hist;
     sp.nbins = hist ? (int32_t)1 << sp.mp.bits : 0;
     const bool vec = group_vec_ok(sp.mp.g, axis) && aligned(P, 16);
-    // the backward's launch shape (group_launch without a row split) with the block's histogram in dynamic LDS
     const GroupLaunch L = group_launch(sp.mp.g, axis, vec, false, kGroupGridY);
-    const size_t lds = (size_t)sp.nbins * sizeof(uint32_t);
-    hipStream_t st = (hipStream_t)stream;
-    switch (L.form) {
-        case GROUP_COLS4: hipLaunchKernelGGL((k_mx_stats_cols<4, kGroupColsLanes4>), L.grid, dim3(kBlock), lds, st, sp); break;
-        case GROUP_COLS1: hipLaunchKernelGGL((k_mx_stats_cols<1, kGroupColsLanes1>), L.grid, dim3(kBlock), lds, st, sp); break;
-        case GROUP_ROWS4: hipLaunchKernelGGL((k_mx_stats_rows<4>), L.grid, dim3(kBlock), lds, st, sp, L.log_team); break;
-        default: hipLaunchKernelGGL((k_mx_stats_rows<1>), L.grid, dim3(kBlock), lds, st, sp, L.log_team); break;
-    }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(LQ_EHIP, "microscaling statistics %s launch: %s", L.form <= GROUP_COLS1 ? "column" : "row", hipGetErrorString(e));
-    return LQ_OK;
+    return launch_group_form(L, LQ_GROUP_FAMILY0(k_mx_stats_cols, k_mx_stats_rows), sp, "microscaling statistics", (hipStream_t)stream,
+                             (size_t)sp.nbins * sizeof(uint32_t));
 }
 
 int lq_fq_fwd_bwd_fused(const float* P, const float* s, const float* dy, float lambda, float* out, float* ds, void* ws,

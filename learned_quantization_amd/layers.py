@@ -835,22 +835,33 @@ def quantized_tensors(model: nn.Module):
     return out
 
 
+def _model_stats(model: nn.Module, want_hist, mx: bool) -> dict:
+    """The walk of ``quant_stats`` (``mx=False``: the tensors without an element format) and ``mx_quant_stats`` (those with one):
+    one launch per tensor, then every record to the host in one copy."""
+    tensors = [t for t in quantized_tensors(model) if (t[2].element_format is not None) == mx]
+    numels = [param.numel() for _, param, _ in tensors]
+    if mx:
+        records = [nested.mx_stats(param.data, want_hist) for _, param, nested in tensors]
+        summaries = ops.summarize_mx_stats_many(records, numels, [nested.element_format for _, _, nested in tensors])
+    else:
+        for name, _, nested in tensors:      # before any launch
+            if nested.q_range is None:
+                raise ValueError(f"quant_stats: the quantizer of {name!r} has no range (bits / q_range); the unbounded quantizer's "
+                                 "statistics are tracking.NestedScaleTrackingCallback's")
+        # a range of more than ops.STATS_MAX_BINS codes has no histogram: its summary holds None for the two code statistics
+        records = [nested.quant_stats(param.data, want_hist and nested.q_range[1] - nested.q_range[0] < ops.STATS_MAX_BINS)
+                   for _, param, nested in tensors]
+        summaries = ops.summarize_stats_many(records, numels)
+    return {name: summary for (name, _, _), summary in zip(tensors, summaries)}
+
+
 def quant_stats(model: nn.Module, want_hist=True) -> dict:
     """{reference name: summary} of every quantized tensor of ``model`` (``quantized_tensors``' walk): the
     ops.summarize_stats dict of the tensor's ``CustomQuantizedScaleLayer.quant_stats``.  One launch per tensor, then all records
     go to the host together in one copy (one synchronisation: call it between steps, never inside a capture).  Every layer
     needs a range: ValueError otherwise.  Tensors of layers with an element format are skipped: the statistics kernel bins the
     codes of an integer range; theirs is ``mx_quant_stats``."""
-    tensors = [t for t in quantized_tensors(model) if t[2].element_format is None]
-    for name, _, nested in tensors:      # before any launch
-        if nested.q_range is None:
-            raise ValueError(f"quant_stats: the quantizer of {name!r} has no range (bits / q_range); the unbounded quantizer's "
-                             "statistics are tracking.NestedScaleTrackingCallback's")
-    # a range of more than ops.STATS_MAX_BINS codes has no histogram: its summary holds None for the two code statistics
-    records = [nested.quant_stats(param.data, want_hist and nested.q_range[1] - nested.q_range[0] < ops.STATS_MAX_BINS)
-               for _, param, nested in tensors]
-    summaries = ops.summarize_stats_many(records, [param.numel() for _, param, _ in tensors])
-    return {name: summary for (name, _, _), summary in zip(tensors, summaries)}
+    return _model_stats(model, want_hist, mx=False)
 
 
 def mx_quant_stats(model: nn.Module, want_hist=True) -> dict:
@@ -858,11 +869,7 @@ def mx_quant_stats(model: nn.Module, want_hist=True) -> dict:
     the others are skipped: theirs is ``quant_stats``): the ops.summarize_mx_stats dict of the tensor's
     ``CustomQuantizedScaleLayer.mx_stats``.  One launch per tensor, then all records go to the host together in one copy (one
     synchronisation: call it between steps, never inside a capture).  ``{}`` for a model without such layers."""
-    tensors = [t for t in quantized_tensors(model) if t[2].element_format is not None]
-    records = [nested.mx_stats(param.data, want_hist) for _, param, nested in tensors]
-    summaries = ops.summarize_mx_stats_many(records, [param.numel() for _, param, _ in tensors],
-                                            [nested.element_format for _, _, nested in tensors])
-    return {name: summary for (name, _, _), summary in zip(tensors, summaries)}
+    return _model_stats(model, want_hist, mx=True)
 
 
 def init_scales(model: nn.Module, method) -> nn.Module:

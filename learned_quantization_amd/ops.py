@@ -509,6 +509,24 @@ class GroupStats(NamedTuple):
     hist: Optional[torch.Tensor]
 
 
+class MxStats(NamedTuple):
+    """What ``mx_stats`` returns, all on the device: ``below`` / ``above`` / ``flushed`` (int32 tensors holding the uint32 counts)
+    and ``err2`` / ``sig2`` (float64) in the scale's shape, ``hist`` (int32, 2^bits bins in code order) or None."""
+    below: torch.Tensor
+    above: torch.Tensor
+    flushed: torch.Tensor
+    err2: torch.Tensor
+    sig2: torch.Tensor
+    hist: Optional[torch.Tensor]
+
+
+def _stats_outputs(s: torch.Tensor, counts: int, nbins: Optional[int]) -> list:
+    """The outputs of a statistics call in its argument order: ``counts`` int32 and two float64 tensors in the scale's shape, and
+    the zeroed histogram of ``nbins`` bins (None: no histogram)."""
+    out = [torch.empty_like(s, dtype=torch.int32) for _ in range(counts)] + [torch.empty_like(s, dtype=torch.float64) for _ in range(2)]
+    return out + [None if nbins is None else torch.zeros(nbins, dtype=torch.int32, device=s.device)]
+
+
 def group_stats(parameter: torch.Tensor, scale: torch.Tensor, qmin: int, qmax: int, group_size: Optional[int], *,
                 offset: Optional[torch.Tensor] = None, rounding: str = "floor", want_hist: bool = True) -> GroupStats:
     """Statistics of the clipped quantizer on ``parameter`` under ``scale`` (and ``offset``) as they are now (include/lq_hip.h,
@@ -525,16 +543,26 @@ def group_stats(parameter: torch.Tensor, scale: torch.Tensor, qmin: int, qmax: i
     s = _hip.require_device_f32(scale, "scale")
     b = None if offset is None else _offset_like(offset, s)
     R, C, axis, gs = init_geometry(tuple(p.shape), p.stride(), tuple(s.shape), group_size)
-    below = torch.empty_like(s, dtype=torch.int32)
-    above = torch.empty_like(s, dtype=torch.int32)
-    err2 = torch.empty_like(s, dtype=torch.float64)
-    sig2 = torch.empty_like(s, dtype=torch.float64)
-    hist = torch.zeros(qmax - qmin + 1, dtype=torch.int32, device=p.device) if want_hist else None
+    out = _stats_outputs(s, 2, qmax - qmin + 1 if want_hist else None)
+    _hip.check(_hip.load().lq_group_stats(_hip.ptr(p), _hip.ptr(s), _hip.ptr(b), qmin, qmax, rnd, *map(_hip.ptr, out), R, C, axis, gs,
+                                          _hip.stream_ptr(p.device)), "lq_group_stats")
+    return GroupStats(*out)
+
+
+def mx_stats(parameter: torch.Tensor, scale: torch.Tensor, element_format: str, group_size: Optional[int] = MX_GROUP_SIZE,
+             scale_format: str = "e8m0", *, want_hist: bool = True) -> MxStats:
+    """Statistics of the microscaling quantizer on ``parameter`` under ``scale`` as it is now (include/lq_hip.h, lq_mx_stats): per
+    group the elements that saturate below -max and above +max, the non-zero elements the grid flushes to zero, and the f64 sums
+    of squared error and squared signal; per tensor the histogram of the elements' encodings (the forward's code view).  Geometry
+    as ``fq_forward_mx``.  One launch, read only, no synchronisation."""
+    fmt = check_element_format(element_format)
+    sf = check_scale_format(scale_format)
     lib = _hip.load()
-    _hip.check(lib.lq_group_stats(_hip.ptr(p), _hip.ptr(s), _hip.ptr(b), qmin, qmax, rnd, _hip.ptr(below), _hip.ptr(above),
-                                  _hip.ptr(err2), _hip.ptr(sig2), _hip.ptr(hist), R, C, axis, gs, _hip.stream_ptr(p.device)),
-               "lq_group_stats")
-    return GroupStats(below, above, err2, sig2, hist)
+    p, s, (R, C, axis, gs) = _mx_param(parameter, scale, group_size)
+    out = _stats_outputs(s, 3, 1 << fmt.bits if want_hist else None)
+    _hip.check(lib.lq_mx_stats(_hip.ptr(p), _hip.ptr(s), fmt.id, sf, *map(_hip.ptr, out), R, C, axis, gs, _hip.stream_ptr(p.device)),
+               "lq_mx_stats")
+    return MxStats(*out)
 
 
 def _sqnr_db(sig2: float, err2: float) -> float:
@@ -553,8 +581,8 @@ def _sqnr_db(sig2: float, err2: float) -> float:
 
 
 def _stats_to_host(records):
-    """The records' tensors in ONE device->host copy, as records of NumPy arrays: float64 sums, int64 counts and bins (the
-    uint32 values behind the int32 tensors, which float64 carries exactly)."""
+    """The records' tensors in ONE device->host copy, as records (of their own type) of NumPy arrays: float64 sums, int64 counts
+    and bins (the uint32 values behind the int32 tensors, which float64 carries exactly)."""
     def f64(t):
         t = t.reshape(-1)
         if t.dtype == torch.int32:
@@ -575,29 +603,62 @@ def _stats_to_host(records):
             a = flat[at:at + t.numel()].reshape(tuple(t.shape))
             at += t.numel()
             fields.append(a if t.dtype.is_floating_point else a.astype(np.int64))
-        host.append(type(rec)(*fields) if hasattr(rec, "_fields") else GroupStats(*fields))      # GroupStats or MxStats
+        host.append(type(rec)(*fields))
     return host
 
 
-def _summarize_host(rec: GroupStats, numel: int) -> dict:
-    n = float(numel)
+def _host_record(record, numel):
+    """(``record`` with NumPy fields, after ONE device->host copy where a field is a tensor; ``numel`` as a positive int)"""
+    numel = int(numel)
+    if numel < 1:
+        raise ValueError(f"numel must be positive, got {numel}")
+    if any(isinstance(t, torch.Tensor) for t in record):
+        record = _stats_to_host([type(record)(*(t if t is None or isinstance(t, torch.Tensor) else torch.as_tensor(t) for t in record))])[0]
+    return record, numel
+
+
+def _summarize_sums(rec) -> dict:
+    """What both summaries compute alike: ``sqnr_db``, ``worst_group_sqnr_db``, and from the histogram (None without one) ``used``
+    (bins that occur) and ``entropy_bits``."""
     err2 = np.asarray(rec.err2, dtype=np.float64).reshape(-1)
     sig2 = np.asarray(rec.sig2, dtype=np.float64).reshape(-1)
-    out = {
-        "clip_low": float(np.asarray(rec.below, dtype=np.float64).sum() / n),
-        "clip_high": float(np.asarray(rec.above, dtype=np.float64).sum() / n),
-        "sqnr_db": _sqnr_db(float(sig2.sum()), float(err2.sum())),
-        "worst_group_sqnr_db": min((_sqnr_db(float(a), float(e)) for a, e in zip(sig2, err2)),
-                                   key=lambda v: -math.inf if math.isnan(v) else v),
-        "used_levels": None,
-        "entropy_bits": None,
-    }
+    out = {"sqnr_db": _sqnr_db(float(sig2.sum()), float(err2.sum())),
+           "worst_group_sqnr_db": min((_sqnr_db(float(a), float(e)) for a, e in zip(sig2, err2)),
+                                      key=lambda v: -math.inf if math.isnan(v) else v),
+           "used": None, "entropy_bits": None}
     if rec.hist is not None:
         h = np.asarray(rec.hist, dtype=np.float64).reshape(-1)
         used, total = h[h > 0], float(h.sum())
-        out["used_levels"] = int(used.size)
+        out["used"] = int(used.size)
         pr = used / total if total > 0 else used
         out["entropy_bits"] = float(max(0.0, -(pr * np.log2(pr)).sum())) if used.size else 0.0
+    return out
+
+
+def _share(counts, numel: int) -> float:
+    return float(np.asarray(counts, dtype=np.float64).sum() / float(numel))
+
+
+def _summarize_host(rec: GroupStats, numel: int) -> dict:
+    c = _summarize_sums(rec)
+    return {"clip_low": _share(rec.below, numel), "clip_high": _share(rec.above, numel), "sqnr_db": c["sqnr_db"],
+            "worst_group_sqnr_db": c["worst_group_sqnr_db"], "used_levels": c["used"], "entropy_bits": c["entropy_bits"]}
+
+
+def _summarize_mx_host(rec: MxStats, numel: int, element_format: str) -> dict:
+    fmt = check_element_format(element_format)
+    if rec.hist is not None and np.size(rec.hist) != 1 << fmt.bits:
+        raise ValueError(f"a histogram of {np.size(rec.hist)} bins is not {element_format}'s ({1 << fmt.bits} codes)")
+    c = _summarize_sums(rec)
+    out = {"sat_low": _share(rec.below, numel), "sat_high": _share(rec.above, numel), "flushed": _share(rec.flushed, numel),
+           "sqnr_db": c["sqnr_db"], "worst_group_sqnr_db": c["worst_group_sqnr_db"], "used_codes": c["used"],
+           "entropy_bits": c["entropy_bits"], "zero": None, "subnormal": None}
+    if rec.hist is not None:
+        h = np.asarray(rec.hist, dtype=np.float64).reshape(-1)
+        total = float(h.sum())
+        mag = np.arange(h.size) & ((1 << (fmt.bits - 1)) - 1)      # the code below its sign bit: exponent field, then M mantissa bits
+        out["zero"] = float(h[mag == 0].sum() / total) if total > 0 else 0.0
+        out["subnormal"] = float(h[(mag >> fmt.M == 0) & (mag != 0)].sum() / total) if total > 0 else 0.0
     return out
 
 
@@ -607,82 +668,12 @@ def summarize_stats(record: GroupStats, numel: int) -> dict:
     sig2 / sum err2) (inf for zero error), ``worst_group_sqnr_db`` (the smallest group's; NaN if a group's is NaN),
     ``used_levels`` (codes that occur) and ``entropy_bits`` (Shannon entropy of the code distribution; both None without a
     histogram).  The record's fields may be device tensors, host tensors or NumPy arrays."""
-    numel = int(numel)
-    if numel < 1:
-        raise ValueError(f"numel must be positive, got {numel}")
-    if any(isinstance(t, torch.Tensor) for t in record):
-        record = _stats_to_host([GroupStats(*(t if t is None or isinstance(t, torch.Tensor) else torch.as_tensor(t) for t in record))])[0]
-    return _summarize_host(record, numel)
+    return _summarize_host(*_host_record(record, numel))
 
 
 def summarize_stats_many(records, numels) -> list:
     """``summarize_stats`` of several records with all of them copied to the host together (one device->host copy)."""
-    host = _stats_to_host(list(records))
-    return [_summarize_host(rec, int(n)) for rec, n in zip(host, numels)]
-
-
-class MxStats(NamedTuple):
-    """What ``mx_stats`` returns, all on the device: ``below`` / ``above`` / ``flushed`` (int32 tensors holding the uint32 counts)
-    and ``err2`` / ``sig2`` (float64) in the scale's shape, ``hist`` (int32, 2^bits bins in code order) or None."""
-    below: torch.Tensor
-    above: torch.Tensor
-    flushed: torch.Tensor
-    err2: torch.Tensor
-    sig2: torch.Tensor
-    hist: Optional[torch.Tensor]
-
-
-def mx_stats(parameter: torch.Tensor, scale: torch.Tensor, element_format: str, group_size: Optional[int] = MX_GROUP_SIZE,
-             scale_format: str = "e8m0", *, want_hist: bool = True) -> MxStats:
-    """Statistics of the microscaling quantizer on ``parameter`` under ``scale`` as it is now (include/lq_hip.h, lq_mx_stats): per
-    group the elements that saturate below -max and above +max, the non-zero elements the grid flushes to zero, and the f64 sums
-    of squared error and squared signal; per tensor the histogram of the elements' encodings (the forward's code view).  Geometry
-    as ``fq_forward_mx``.  One launch, read only, no synchronisation."""
-    fmt = check_element_format(element_format)
-    sf = check_scale_format(scale_format)
-    lib = _hip.load()
-    p, s, (R, C, axis, gs) = _mx_param(parameter, scale, group_size)
-    below = torch.empty_like(s, dtype=torch.int32)
-    above = torch.empty_like(s, dtype=torch.int32)
-    flushed = torch.empty_like(s, dtype=torch.int32)
-    err2 = torch.empty_like(s, dtype=torch.float64)
-    sig2 = torch.empty_like(s, dtype=torch.float64)
-    hist = torch.zeros(1 << fmt.bits, dtype=torch.int32, device=p.device) if want_hist else None
-    _hip.check(lib.lq_mx_stats(_hip.ptr(p), _hip.ptr(s), fmt.id, sf, _hip.ptr(below), _hip.ptr(above), _hip.ptr(flushed),
-                               _hip.ptr(err2), _hip.ptr(sig2), _hip.ptr(hist), R, C, axis, gs, _hip.stream_ptr(p.device)),
-               "lq_mx_stats")
-    return MxStats(below, above, flushed, err2, sig2, hist)
-
-
-def _summarize_mx_host(rec: MxStats, numel: int, element_format: str) -> dict:
-    fmt = check_element_format(element_format)
-    n = float(numel)
-    err2 = np.asarray(rec.err2, dtype=np.float64).reshape(-1)
-    sig2 = np.asarray(rec.sig2, dtype=np.float64).reshape(-1)
-    out = {
-        "sat_low": float(np.asarray(rec.below, dtype=np.float64).sum() / n),
-        "sat_high": float(np.asarray(rec.above, dtype=np.float64).sum() / n),
-        "flushed": float(np.asarray(rec.flushed, dtype=np.float64).sum() / n),
-        "sqnr_db": _sqnr_db(float(sig2.sum()), float(err2.sum())),
-        "worst_group_sqnr_db": min((_sqnr_db(float(a), float(e)) for a, e in zip(sig2, err2)),
-                                   key=lambda v: -math.inf if math.isnan(v) else v),
-        "used_codes": None,
-        "entropy_bits": None,
-        "zero": None,
-        "subnormal": None,
-    }
-    if rec.hist is not None:
-        h = np.asarray(rec.hist, dtype=np.float64).reshape(-1)
-        if h.size != 1 << fmt.bits:
-            raise ValueError(f"a histogram of {h.size} bins is not {element_format}'s ({1 << fmt.bits} codes)")
-        used, total = h[h > 0], float(h.sum())
-        out["used_codes"] = int(used.size)
-        pr = used / total if total > 0 else used
-        out["entropy_bits"] = float(max(0.0, -(pr * np.log2(pr)).sum())) if used.size else 0.0
-        mag = np.arange(h.size) & ((1 << (fmt.bits - 1)) - 1)      # the code below its sign bit: exponent field, then M mantissa bits
-        out["zero"] = float(h[mag == 0].sum() / total) if total > 0 else 0.0
-        out["subnormal"] = float(h[(mag >> fmt.M == 0) & (mag != 0)].sum() / total) if total > 0 else 0.0
-    return out
+    return [_summarize_host(rec, int(n)) for rec, n in zip(_stats_to_host(list(records)), numels)]
 
 
 def summarize_mx_stats(record: MxStats, numel: int, *, element_format: str) -> dict:
@@ -692,19 +683,12 @@ def summarize_mx_stats(record: MxStats, numel: int, *, element_format: str) -> d
     ``used_codes``, ``entropy_bits``, ``zero`` (share of the codes +0 and -0) and ``subnormal`` (share of the codes with exponent
     field 0 and a non-zero mantissa).  ``element_format`` names the fields of a code.  The record's fields may be device tensors,
     host tensors or NumPy arrays."""
-    numel = int(numel)
-    if numel < 1:
-        raise ValueError(f"numel must be positive, got {numel}")
-    check_element_format(element_format)
-    if any(isinstance(t, torch.Tensor) for t in record):
-        record = _stats_to_host([MxStats(*(t if t is None or isinstance(t, torch.Tensor) else torch.as_tensor(t) for t in record))])[0]
-    return _summarize_mx_host(record, numel, element_format)
+    return _summarize_mx_host(*_host_record(record, numel), element_format)
 
 
 def summarize_mx_stats_many(records, numels, element_formats) -> list:
     """``summarize_mx_stats`` of several records with all of them copied to the host together (one device->host copy)."""
-    host = _stats_to_host(list(records))
-    return [_summarize_mx_host(rec, int(n), f) for rec, n, f in zip(host, numels, element_formats)]
+    return [_summarize_mx_host(rec, int(n), f) for rec, n, f in zip(_stats_to_host(list(records)), numels, element_formats)]
 
 
 def fq_fwd_bwd_fused(parameter: torch.Tensor, scale: torch.Tensor, dy: torch.Tensor, penalty_threshold: float,

@@ -130,7 +130,92 @@ def group_sizes(param, scale, group_size) -> np.ndarray:
     return n.reshape(tuple(scale.shape))
 
 
-class GroupQuantTrackingCallback:
+class _StatsTrackingCallback:
+    """What the two statistics callbacks share: the layer's quantized tensors, the directories, the file table, one statistics
+    launch per tensor with one device->host copy per call, the ``Epoch N`` + one-value-per-line appends and the histogram dump.
+    A subclass supplies
+
+      _STEMS                    (key, file name stem) of its per-epoch files after the scales and offsets, in the order written
+      _refuse(name, q)          raises ValueError for a quantizer it does not log; called before any directory is made
+      _device_stats(p, q)       the statistics record of one tensor, on the device
+      _summary(rec, p, q)       the summary of a host record
+      _rows(rec, st, n, q)      [(key, values)] that ``on_epoch_end`` appends; ``n``: float64 elements per group, flat
+      _code_value(q)            code -> what the histogram dump prints for it"""
+
+    def __init__(self, layer, log_dir):
+        self.layer = layer
+        if hasattr(layer, "kernel"):
+            param, nested, kernel_name = layer.kernel, layer.nested_q_k_layer, f"Kernel_{layer.name}"
+        else:
+            param, nested, kernel_name = layer.W, layer.nested_q_w_layer, "Weights"
+        bias_name = f"Bias_{layer.name}" if hasattr(layer, "kernel") else "Bias"
+        self.tensors = [("kernel", kernel_name, param, nested)]
+        if getattr(layer, "b", None) is not None and getattr(layer, "nested_q_b_layer", None) is not None:
+            self.tensors.append(("bias", bias_name, layer.b, layer.nested_q_b_layer))
+        for _, name, _, q in self.tensors:
+            self._refuse(name, q)
+        e, t, b0 = (os.path.join(log_dir, d) for d in ("on_epoch_end", "on_train_end", "on_train_begin"))
+        for d in (e, t, b0):
+            os.makedirs(d, exist_ok=True)
+        self.paths, self.sizes = {}, {}
+        for what, name, p, q in self.tensors:
+            self.sizes[what] = group_sizes(p, q.scale, q.group_size)      # ValueError where the groups are not lines of a matrix
+            psh, ssh = _shape(p), _shape(q.scale)
+            self.paths[what] = {
+                "scale": f"{e}/{name}_{psh}_{q.scale_name}_{ssh}.log",
+                "offset": f"{e}/{name}_{psh}_Offset_{ssh}.log" if getattr(q, "asymmetric", False) else None,
+                **{key: f"{e}/{stem}_{name}_{psh}.log" for key, stem in self._STEMS},
+                "hist_begin": f"{b0}/Unique_initial_quantized_{name}_{psh}_{q.scale_name}_{ssh}.log",
+                "hist_end": f"{t}/Unique_quantized_{name}_{psh}_{q.scale_name}_{ssh}.log",
+            }
+
+    def epoch_files(self):
+        """Every file ``on_epoch_end`` appends to."""
+        return [path for what, *_ in self.tensors for key, path in self.paths[what].items()
+                if path is not None and not key.startswith("hist_")]
+
+    def _records(self):
+        """The host copies of every tensor's statistics, taken together."""
+        return ops._stats_to_host([self._device_stats(p.data, q) for _, _, p, q in self.tensors])
+
+    def stats(self):
+        """{"kernel": summary, "bias": summary} of the tensors as they are now."""
+        return {what: self._summary(rec, p, q) for (what, _, p, q), rec in zip(self.tensors, self._records())}
+
+    _append = staticmethod(NestedScaleTrackingCallback._append)
+
+    @staticmethod
+    def _sqnr_rows(rec, st):
+        return [("sqnr", [ops._sqnr_db(float(a), float(b)) for a, b in zip(rec.sig2.reshape(-1), rec.err2.reshape(-1))]),
+                ("sqnr_tensor", [st["sqnr_db"]])]
+
+    def on_epoch_end(self, epoch, logs=None):
+        hdr = f"Epoch {epoch}\n"
+        out = {}
+        for (what, _, p, q), rec in zip(self.tensors, self._records()):
+            st = out[what] = self._summary(rec, p, q)
+            for key, values in self._rows(rec, st, self.sizes[what].reshape(-1).astype(np.float64), q):
+                self._append(self.paths[what][key], hdr, values)
+        return out
+
+    def _dump_hist(self, key):
+        for (what, _, _, q), rec in zip(self.tensors, self._records()):
+            if rec.hist is None:
+                continue
+            value = self._code_value(q)
+            with open(self.paths[what][key], "a") as f:
+                for code, count in enumerate(rec.hist):
+                    if count:
+                        f.write(f"{value(code)}, {int(count)}\n")
+
+    def on_train_end(self, logs=None):
+        self._dump_hist("hist_end")
+
+    def on_train_begin(self, logs=None):
+        self._dump_hist("hist_begin")
+
+
+class GroupQuantTrackingCallback(_StatsTrackingCallback):
     """Per-epoch logs of a layer whose quantizer has a range (``bits`` / ``q_range``), with any scale ops.group_stats takes:
     group-wise (symmetric or with offsets), scalar, a Dense orientation, channel-wise on OIHW storage.  Same directory layout
     and ``Epoch N`` + one-value-per-line format as ``NestedScaleTrackingCallback``.  For the kernel and the bias, per epoch end
@@ -144,92 +229,36 @@ class GroupQuantTrackingCallback:
       Code_entropy_bits_<name>_<shape>.log             Shannon entropy of the code distribution
 
     and on train begin / train end the code histogram as ``value, count`` lines (``Unique_initial_quantized_...`` /
-    ``Unique_quantized_...``).  One lq_group_stats launch per tensor and one device->host copy per call."""
+    ``Unique_quantized_...``).  One lq_group_stats launch per tensor and one device->host copy per call.  ``stats()`` holds
+    ops.summarize_stats of each tensor."""
 
-    def __init__(self, layer, log_dir):
-        self.layer = layer
-        if hasattr(layer, "kernel"):
-            param, nested, kernel_name = layer.kernel, layer.nested_q_k_layer, f"Kernel_{layer.name}"
-        else:
-            param, nested, kernel_name = layer.W, layer.nested_q_w_layer, "Weights"
-        bias_name = f"Bias_{layer.name}" if hasattr(layer, "kernel") else "Bias"
-        self.tensors = [("kernel", kernel_name, param, nested)]
-        if getattr(layer, "b", None) is not None and getattr(layer, "nested_q_b_layer", None) is not None:
-            self.tensors.append(("bias", bias_name, layer.b, layer.nested_q_b_layer))
-        e, t, b0 = (os.path.join(log_dir, d) for d in ("on_epoch_end", "on_train_end", "on_train_begin"))
-        for d in (e, t, b0):
-            os.makedirs(d, exist_ok=True)
-        self.paths, self.sizes = {}, {}
-        for what, name, p, q in self.tensors:
-            if q.q_range is None:
-                raise ValueError(f"GroupQuantTrackingCallback: the quantizer of {name} has no range; use NestedScaleTrackingCallback")
-            self.sizes[what] = group_sizes(p, q.scale, q.group_size)      # ValueError where the groups are not lines of a matrix
-            psh, ssh = _shape(p), _shape(q.scale)
-            self.paths[what] = {
-                "scale": f"{e}/{name}_{psh}_{q.scale_name}_{ssh}.log",
-                "offset": f"{e}/{name}_{psh}_Offset_{ssh}.log" if q.asymmetric else None,
-                "clip_low": f"{e}/Clip_low_{name}_{psh}.log",
-                "clip_high": f"{e}/Clip_high_{name}_{psh}.log",
-                "sqnr": f"{e}/SQNR_dB_{name}_{psh}.log",
-                "sqnr_tensor": f"{e}/SQNR_dB_tensor_{name}_{psh}.log",
-                "used": f"{e}/Used_levels_{name}_{psh}.log",
-                "entropy": f"{e}/Code_entropy_bits_{name}_{psh}.log",
-                "hist_begin": f"{b0}/Unique_initial_quantized_{name}_{psh}_{q.scale_name}_{ssh}.log",
-                "hist_end": f"{t}/Unique_quantized_{name}_{psh}_{q.scale_name}_{ssh}.log",
-            }
+    _STEMS = (("clip_low", "Clip_low"), ("clip_high", "Clip_high"), ("sqnr", "SQNR_dB"), ("sqnr_tensor", "SQNR_dB_tensor"),
+              ("used", "Used_levels"), ("entropy", "Code_entropy_bits"))
 
-    def epoch_files(self):
-        """Every file ``on_epoch_end`` appends to."""
-        keys = ("scale", "offset", "clip_low", "clip_high", "sqnr", "sqnr_tensor", "used", "entropy")
-        return [self.paths[what][k] for what, *_ in self.tensors for k in keys if self.paths[what][k] is not None]
+    def _refuse(self, name, q):
+        if q.q_range is None:
+            raise ValueError(f"GroupQuantTrackingCallback: the quantizer of {name} has no range; use NestedScaleTrackingCallback")
 
-    def _records(self):
-        """The host copies of every tensor's statistics, taken together."""
-        return ops._stats_to_host([q.quant_stats(p.data, want_hist=q.q_range[1] - q.q_range[0] < ops.STATS_MAX_BINS)
-                                   for _, _, p, q in self.tensors])
+    def _device_stats(self, p, q):
+        return q.quant_stats(p, want_hist=q.q_range[1] - q.q_range[0] < ops.STATS_MAX_BINS)
 
-    def stats(self):
-        """{"kernel": summary, "bias": summary}: ops.summarize_stats of the tensors as they are now."""
-        return {what: ops._summarize_host(rec, p.numel()) for (what, _, p, _), rec in zip(self.tensors, self._records())}
+    def _summary(self, rec, p, q):
+        return ops._summarize_host(rec, p.numel())
 
-    _append = staticmethod(NestedScaleTrackingCallback._append)
+    def _rows(self, rec, st, n, q):
+        rows = [("scale", q.scale.detach().flatten().cpu().numpy())]
+        if q.asymmetric:
+            rows.append(("offset", q.offset.detach().flatten().cpu().numpy()))
+        rows += [("clip_low", rec.below.reshape(-1) / n), ("clip_high", rec.above.reshape(-1) / n)] + self._sqnr_rows(rec, st)
+        if rec.hist is not None:      # a range of more than ops.STATS_MAX_BINS codes has no histogram
+            rows += [("used", [st["used_levels"]]), ("entropy", [st["entropy_bits"]])]
+        return rows
 
-    def on_epoch_end(self, epoch, logs=None):
-        hdr = f"Epoch {epoch}\n"
-        out = {}
-        for (what, _, p, q), rec in zip(self.tensors, self._records()):
-            paths, n = self.paths[what], self.sizes[what].reshape(-1).astype(np.float64)
-            st = ops._summarize_host(rec, p.numel())
-            self._append(paths["scale"], hdr, q.scale.detach().flatten().cpu().numpy())
-            if paths["offset"] is not None:
-                self._append(paths["offset"], hdr, q.offset.detach().flatten().cpu().numpy())
-            self._append(paths["clip_low"], hdr, rec.below.reshape(-1) / n)
-            self._append(paths["clip_high"], hdr, rec.above.reshape(-1) / n)
-            self._append(paths["sqnr"], hdr, [ops._sqnr_db(float(a), float(b)) for a, b in zip(rec.sig2.reshape(-1), rec.err2.reshape(-1))])
-            self._append(paths["sqnr_tensor"], hdr, [st["sqnr_db"]])
-            if rec.hist is not None:      # a range of more than ops.STATS_MAX_BINS codes has no histogram
-                self._append(paths["used"], hdr, [st["used_levels"]])
-                self._append(paths["entropy"], hdr, [st["entropy_bits"]])
-            out[what] = st
-        return out
-
-    def _dump_hist(self, key):
-        for (what, _, _, q), rec in zip(self.tensors, self._records()):
-            if rec.hist is None:
-                continue
-            with open(self.paths[what][key], "a") as f:
-                for code, count in enumerate(rec.hist):
-                    if count:
-                        f.write(f"{np.float32(q.q_range[0] + code)}, {int(count)}\n")
-
-    def on_train_end(self, logs=None):
-        self._dump_hist("hist_end")
-
-    def on_train_begin(self, logs=None):
-        self._dump_hist("hist_begin")
+    def _code_value(self, q):
+        return lambda code: np.float32(q.q_range[0] + code)
 
 
-class MxQuantTrackingCallback:
+class MxQuantTrackingCallback(_StatsTrackingCallback):
     """Per-epoch logs of a layer with an element format (the OCP microscaling quantizer), the counterpart of
     ``GroupQuantTrackingCallback``: same directory layout and ``Epoch N`` + one-value-per-line format.  For the kernel and the
     bias, per epoch end (group values in the scale's memory order):
@@ -245,94 +274,32 @@ class MxQuantTrackingCallback:
 
     and on train begin / train end the code histogram as ``value, count`` lines in code order, the value from
     ops.mx_decode_table (``Unique_initial_quantized_...`` / ``Unique_quantized_...``).  One lq_mx_stats launch per tensor and one
-    device->host copy per call."""
+    device->host copy per call.  ``stats()`` holds ops.summarize_mx_stats of each tensor."""
 
-    _KEYS = ("scale", "exponent", "sat_low", "sat_high", "flushed", "sqnr", "sqnr_tensor", "used", "entropy")
+    _STEMS = (("exponent", "Scale_exponent"), ("sat_low", "Sat_low"), ("sat_high", "Sat_high"), ("flushed", "Flushed"),
+              ("sqnr", "SQNR_dB"), ("sqnr_tensor", "SQNR_dB_tensor"), ("used", "Used_codes"), ("entropy", "Code_entropy_bits"))
 
-    def __init__(self, layer, log_dir):
-        self.layer = layer
-        if hasattr(layer, "kernel"):
-            param, nested, kernel_name = layer.kernel, layer.nested_q_k_layer, f"Kernel_{layer.name}"
-        else:
-            param, nested, kernel_name = layer.W, layer.nested_q_w_layer, "Weights"
-        bias_name = f"Bias_{layer.name}" if hasattr(layer, "kernel") else "Bias"
-        self.tensors = [("kernel", kernel_name, param, nested)]
-        if getattr(layer, "b", None) is not None and getattr(layer, "nested_q_b_layer", None) is not None:
-            self.tensors.append(("bias", bias_name, layer.b, layer.nested_q_b_layer))
-        for _, name, _, q in self.tensors:      # before any directory is made
-            if getattr(q, "element_format", None) is None:
-                raise ValueError(f"MxQuantTrackingCallback: the quantizer of {name} has no element format; use "
-                                 "GroupQuantTrackingCallback (a range) or NestedScaleTrackingCallback")
-        e, t, b0 = (os.path.join(log_dir, d) for d in ("on_epoch_end", "on_train_end", "on_train_begin"))
-        for d in (e, t, b0):
-            os.makedirs(d, exist_ok=True)
-        self.paths, self.sizes = {}, {}
-        for what, name, p, q in self.tensors:
-            self.sizes[what] = group_sizes(p, q.scale, q.group_size)
-            psh, ssh = _shape(p), _shape(q.scale)
-            self.paths[what] = {
-                "scale": f"{e}/{name}_{psh}_{q.scale_name}_{ssh}.log",
-                "exponent": f"{e}/Scale_exponent_{name}_{psh}.log",
-                "sat_low": f"{e}/Sat_low_{name}_{psh}.log",
-                "sat_high": f"{e}/Sat_high_{name}_{psh}.log",
-                "flushed": f"{e}/Flushed_{name}_{psh}.log",
-                "sqnr": f"{e}/SQNR_dB_{name}_{psh}.log",
-                "sqnr_tensor": f"{e}/SQNR_dB_tensor_{name}_{psh}.log",
-                "used": f"{e}/Used_codes_{name}_{psh}.log",
-                "entropy": f"{e}/Code_entropy_bits_{name}_{psh}.log",
-                "hist_begin": f"{b0}/Unique_initial_quantized_{name}_{psh}_{q.scale_name}_{ssh}.log",
-                "hist_end": f"{t}/Unique_quantized_{name}_{psh}_{q.scale_name}_{ssh}.log",
-            }
+    def _refuse(self, name, q):
+        if getattr(q, "element_format", None) is None:
+            raise ValueError(f"MxQuantTrackingCallback: the quantizer of {name} has no element format; use "
+                             "GroupQuantTrackingCallback (a range) or NestedScaleTrackingCallback")
 
-    def epoch_files(self):
-        """Every file ``on_epoch_end`` appends to."""
-        return [self.paths[what][k] for what, *_ in self.tensors for k in self._KEYS]
+    def _device_stats(self, p, q):
+        return q.mx_stats(p)
 
-    def _records(self):
-        """The host copies of every tensor's statistics, taken together."""
-        return ops._stats_to_host([q.mx_stats(p.data) for _, _, p, q in self.tensors])
+    def _summary(self, rec, p, q):
+        return ops._summarize_mx_host(rec, p.numel(), q.element_format)
 
-    def stats(self):
-        """{"kernel": summary, "bias": summary}: ops.summarize_mx_stats of the tensors as they are now."""
-        return {what: ops._summarize_mx_host(rec, p.numel(), q.element_format)
-                for (what, _, p, q), rec in zip(self.tensors, self._records())}
+    def _rows(self, rec, st, n, q):
+        stored = q.scale.detach().flatten().cpu().numpy()
+        with np.errstate(all="ignore"):
+            exponent = np.log2(ops.mx_effective_scale(stored, q.scale_format).astype(np.float64))
+        return [("scale", stored), ("exponent", exponent), ("sat_low", rec.below.reshape(-1) / n), ("sat_high", rec.above.reshape(-1) / n),
+                ("flushed", rec.flushed.reshape(-1) / n)] + self._sqnr_rows(rec, st) + [("used", [st["used_codes"]]),
+                                                                                       ("entropy", [st["entropy_bits"]])]
 
-    _append = staticmethod(NestedScaleTrackingCallback._append)
-
-    def on_epoch_end(self, epoch, logs=None):
-        hdr = f"Epoch {epoch}\n"
-        out = {}
-        for (what, _, p, q), rec in zip(self.tensors, self._records()):
-            paths, n = self.paths[what], self.sizes[what].reshape(-1).astype(np.float64)
-            st = ops._summarize_mx_host(rec, p.numel(), q.element_format)
-            stored = q.scale.detach().flatten().cpu().numpy()
-            with np.errstate(all="ignore"):
-                exponent = np.log2(ops.mx_effective_scale(stored, q.scale_format).astype(np.float64))
-            self._append(paths["scale"], hdr, stored)
-            self._append(paths["exponent"], hdr, exponent)
-            self._append(paths["sat_low"], hdr, rec.below.reshape(-1) / n)
-            self._append(paths["sat_high"], hdr, rec.above.reshape(-1) / n)
-            self._append(paths["flushed"], hdr, rec.flushed.reshape(-1) / n)
-            self._append(paths["sqnr"], hdr, [ops._sqnr_db(float(a), float(b)) for a, b in zip(rec.sig2.reshape(-1), rec.err2.reshape(-1))])
-            self._append(paths["sqnr_tensor"], hdr, [st["sqnr_db"]])
-            self._append(paths["used"], hdr, [st["used_codes"]])
-            self._append(paths["entropy"], hdr, [st["entropy_bits"]])
-            out[what] = st
-        return out
-
-    def _dump_hist(self, key):
-        for (what, _, _, q), rec in zip(self.tensors, self._records()):
-            table = ops.mx_decode_table(q.element_format)
-            with open(self.paths[what][key], "a") as f:
-                for code, count in enumerate(rec.hist):
-                    if count:
-                        f.write(f"{table[code]}, {int(count)}\n")      # -0.0 prints as such
-
-    def on_train_end(self, logs=None):
-        self._dump_hist("hist_end")
-
-    def on_train_begin(self, logs=None):
-        self._dump_hist("hist_begin")
+    def _code_value(self, q):
+        return ops.mx_decode_table(q.element_format).__getitem__      # -0.0 prints as such
 
 
 class AccuracyLossTrackingCallBack:

@@ -400,6 +400,52 @@ int lq_mx_stats(const float* P, const float* s, int format, int scale_format, ui
                 double* err2, double* sig2, uint32_t* hist /* may be NULL */, int64_t R, int64_t C, int axis, int64_t gs,
                 void* stream);
 
+/* ---- packed MX operands and the block-scaled GEMM ----
+ * An OPERAND is a matrix of L lines by K reduction elements in the order gfx950's v_mfma_scale_f32_16x16x128_f8f6f4 consumes it:
+ * element codes at the instruction's width (8 bits: LQ_ELEM_FP8_E4M3, LQ_ELEM_FP8_E5M2; 4 bits: LQ_ELEM_FP4_E2M1) and one E8M0 byte
+ * per block of 32 along K.  To callers it is opaque apart from its size (lq_mx_operand_bytes); the layout is stated here so that it
+ * can be checked:
+ *   LT = ceil(L / 16), KT = ceil(K / 128), KG = ceil(KT / 4), FB = 32 (fp8) or 16 (fp4) bytes per fragment
+ *   codes   [LT][KT][64][FB]   fragment `lane` of tile (lt, kt) holds line 16 lt + (lane & 15) and, with g = lane >> 4, of K step kt
+ *                              fp4: k = 32 g + j, j = 0 .. 31 (one MX block), element j in bits 4 (j & 1) .. + 3 of byte j >> 1;
+ *                              fp8: k = 16 g + j in byte j and k = 64 + 16 g + j in byte 16 + j, j = 0 .. 15 (halves of two blocks)
+ *   scales  [LT][KG][64][4]    byte u of dword `lane` of cell (lt, kg) is the E8M0 byte of block g (k = 32 g .. 32 g + 31) of K step
+ *                              kt = 4 kg + u of that line, for every format
+ *   code_bytes = LT * KT * 64 * FB, scale_bytes = LT * KG * 256.  Lines past L and elements past K hold code 0 under byte 127.
+ * This is the lane map of the instruction as pinned on the device by exact-arithmetic GEMM tests (tests/test_gpu_mx_gemm.py): lane l
+ * supplies the A (B) line l & 15; 4-bit data is one block per lane, 8-bit data two half blocks 64 apart; the scale byte selected by
+ * op-sel from lane l's scale register applies to block l >> 4 whichever lane holds its data; the result tile has column l & 15 on the
+ * lane and rows 4 (l >> 4) + r in register r.
+ * The scale byte of a block is the biased exponent of its s_eff (a power of two in [2^-126, 2^127]: bytes 1 .. 254); byte 255
+ * marks a block whose s_eff is NaN.
+ *
+ * lq_mx_operand_pack: the operand of a stored parameter under its stored scales.  Geometry is lq_fq_forward_group's ([R][C] in
+ * memory order, s [nb][C] or [R][nb]).  axis 0: the lines are the C columns and K = R (a Dense kernel (in, out)); axis 1: the lines
+ * are the R rows and K = C (a conv kernel stored OIHW seen as (co, ci kh kw)).  The code of every element is bit for bit the code
+ * view of lq_fq_forward_mx under LQ_SCALE_E8M0, NaN code rule included; the element step is that kernel's.
+ * lq_mx_operand_quantize: the operand of a row-major X [M][K] (lines: rows; blocks of 32 along the contiguous axis) under scales
+ * taken from X itself: per block what lq_scale_init_mx(X, s, format, method, min_value = 2^-126, M, K, axis 1, gs 32) writes, then
+ * the codes of lq_fq_forward_mx under that scale.  A block holding a NaN or an Inf gets byte 255.  One read of X.
+ * lq_mx_operand_decode: out [L][K] row-major, out = value(code) * 2^(byte - 127) in fp32 (byte 255: NaN) -- for a packed parameter
+ * lq_fq_forward_mx's `out` bit for bit, except where the format has no NaN code (fp4) and the element is NaN under a valid scale.
+ * lq_mx_gemm: Y[m][n] = sum_k A[m][k] * B[n][k] (+ bias[n]) in fp32, Y row-major with leading dimension ldy >= N, A and B operands of
+ * M and N lines over the same K, any of the nine format pairs.  The products and the sum of a K step of 128 are the instruction's;
+ * the steps accumulate in ascending K into fp32; the bias is added last, one fp32 addition.  No atomics: run-to-run bit-stable.
+ *
+ * LQ_EINVAL before any launch: a NULL pointer (bias may be NULL), a non-positive extent, L * K >= 2^31, an unknown format or
+ * method, an fp6 format (6-bit lanes need a 96-byte fragment packing of their own: not built), scale_format LQ_SCALE_FP32 (the
+ * instruction takes E8M0 only), gs != 32, ldy < N.  LQ_EALIGN: codes off the 16-byte grid; scales, P, s, X, bias, out or Y off the
+ * 4-byte grid.  16-byte loads of P / X are used where the base is 16-byte aligned and the contiguous axis a multiple of 4 (axis 1
+ * and quantize).  Each call only enqueues ONE launch (capturable), allocates nothing, reads no environment, and writes exactly
+ * code_bytes and scale_bytes (pack, quantize), L * K floats (decode) or the M x N elements of Y (gemm).  */
+int lq_mx_operand_bytes(int format, int64_t L, int64_t K, size_t* code_bytes, size_t* scale_bytes);
+int lq_mx_operand_pack(const float* P, const float* s, int format, int scale_format, int64_t R, int64_t C, int axis, int64_t gs,
+                       void* codes, void* scales, void* stream);
+int lq_mx_operand_quantize(const float* X, int format, int method, int64_t M, int64_t K, void* codes, void* scales, void* stream);
+int lq_mx_operand_decode(const void* codes, const void* scales, int format, int64_t L, int64_t K, float* out, void* stream);
+int lq_mx_gemm(const void* a_codes, const void* a_scales, int a_format, const void* b_codes, const void* b_scales, int b_format,
+               const float* bias /* may be NULL */, float* Y, int64_t M, int64_t N, int64_t K, int64_t ldy, void* stream);
+
 /* ---- K4: forward and NQ backward of one tensor in a single pass (benchmark path) ---
  * Same results as lq_fq_forward followed by lq_fq_scale_grad (out, max|q| and the vote count bit for bit; on
  * streaming-size tensors the vote sum may differ by fp32 summation order, ~1e-7 relative); P is read once.  */

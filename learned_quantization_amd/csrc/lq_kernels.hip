@@ -14,6 +14,8 @@
 //   lq_group_batch.hpp  group-wise tensors in one launch per pass
 //   lq_scale_init.hpp   scales and offsets from the weights: absmax / LSQ / MSE / min-max on the group-wise unit shapes
 //   lq_mx.hpp           OCP microscaling element formats: the group-wise traversal bodies with a minifloat element step
+//   lq_mx_operand.hpp   packed MX operands in the block-scaled matrix instruction's fragment order: pack, dynamic quantize, decode
+//   lq_mx_gemm.hpp      the GEMM of two packed operands on v_mfma_scale_f32_16x16x128_f8f6f4
 //   this file           host side: traversal plan, launchers, the extern "C" entry points
 //
 // The path is elementwise + per-group reductions: HBM-bound, no MFMA.  Design rules
@@ -59,6 +61,8 @@
 #include "lq_mx.hpp"
 #include "lq_group_stats.hpp"
 #include "lq_mx_stats.hpp"
+#include "lq_mx_operand.hpp"
+#include "lq_mx_gemm.hpp"
 
 namespace lq {
 
@@ -1772,6 +1776,199 @@ int lq_mx_stats(const float* P, const float* s, int format, int scale_format, ui
     const GroupLaunch L = group_launch(sp.mp.g, axis, vec, false, kGroupGridY);
     return launch_group_form(L, LQ_GROUP_FAMILY0(k_mx_stats_cols, k_mx_stats_rows), sp, "microscaling statistics", (hipStream_t)stream,
                              (size_t)sp.nbins * sizeof(uint32_t));
+}
+
+// ---- packed MX operands and the block-scaled GEMM (lq_mx_operand.hpp, lq_mx_gemm.hpp) ----
+// the three element formats whose fragments are built: the 6-bit formats need a 96-byte fragment packing of their own
+static int check_mx_operand_format(const char* fn, int format) {
+    if (format == LQ_ELEM_FP6_E2M3 || format == LQ_ELEM_FP6_E3M2)
+        return fail(LQ_EINVAL, "%s: fp6 operands are not supported (element format %d): 6-bit lanes need their own fragment packing", fn, format);
+    if (format != LQ_ELEM_FP4_E2M1 && format != LQ_ELEM_FP8_E4M3 && format != LQ_ELEM_FP8_E5M2)
+        return fail(LQ_EINVAL, "%s: bad element format %d", fn, format);
+    return LQ_OK;
+}
+
+struct MxOperandDims {
+    int64_t LT, KT, KG, fb;
+    size_t code_bytes, scale_bytes;
+};
+
+static int mx_operand_dims(const char* fn, int format, int64_t L, int64_t K, MxOperandDims& d) {
+    int rc = check_mx_operand_format(fn, format);
+    if (rc) return rc;
+    if (L <= 0 || K <= 0) return fail(LQ_EINVAL, "%s: extents must be positive (L=%lld K=%lld)", fn, (long long)L, (long long)K);
+    if ((double)L * (double)K >= 2147483648.0) return fail(LQ_EINVAL, "%s: L * K = %lld * %lld is not below 2^31", fn, (long long)L, (long long)K);
+    d.LT = (L + kMxTileLines - 1) / kMxTileLines;
+    d.KT = (K + kMxTileK - 1) / kMxTileK;
+    d.KG = (d.KT + 3) / 4;
+    d.fb = format == LQ_ELEM_FP4_E2M1 ? 16 : 32;
+    d.code_bytes = (size_t)(d.LT * d.KT * 64 * d.fb);
+    d.scale_bytes = (size_t)(d.LT * d.KG * 256);
+    return LQ_OK;
+}
+
+int lq_mx_operand_bytes(int format, int64_t L, int64_t K, size_t* code_bytes, size_t* scale_bytes) {
+    const char* fn = __func__;
+    if (!code_bytes || !scale_bytes) return fail(LQ_EINVAL, "%s: code_bytes or scale_bytes is NULL", fn);
+    MxOperandDims d;
+    int rc = mx_operand_dims(fn, format, L, K, d);
+    if (rc) return rc;
+    *code_bytes = d.code_bytes;
+    *scale_bytes = d.scale_bytes;
+    return LQ_OK;
+}
+
+static int check_mx_operand_buffers(const char* fn, const void* codes, const void* scales) {
+    if (!codes || !scales) return fail(LQ_EINVAL, "%s: argument '%s' is NULL", fn, codes ? "scales" : "codes");
+    if (!aligned(codes, 16)) return fail(LQ_EALIGN, "%s: codes is not 16-byte aligned", fn);
+    if (!aligned(scales, 4)) return fail(LQ_EALIGN, "%s: scales is not 4-byte aligned", fn);
+    return LQ_OK;
+}
+
+extern "C++" {      // templates inside the C-linkage block
+template <bool DYN, int METHOD, bool LINE_FAST>
+static int launch_mx_operand(const MxOperandParams& op, bool fp4, bool vec, const char* what, void* stream) {
+    const int64_t threads = (int64_t)op.LT * kMxTileLines * op.KT * 4;
+    const dim3 grid((unsigned)((threads + kBlock - 1) / kBlock)), block(kBlock);
+    hipStream_t st = (hipStream_t)stream;
+    constexpr bool kVecForm = !LINE_FAST;      // float4 loads need the blocks along the contiguous axis: axis 1 and quantize
+    if (fp4) {
+        if (kVecForm && vec) hipLaunchKernelGGL((k_mx_operand<DYN, METHOD, true, kVecForm, LINE_FAST>), grid, block, 0, st, op);
+        else hipLaunchKernelGGL((k_mx_operand<DYN, METHOD, true, false, LINE_FAST>), grid, block, 0, st, op);
+    } else {
+        if (kVecForm && vec) hipLaunchKernelGGL((k_mx_operand<DYN, METHOD, false, kVecForm, LINE_FAST>), grid, block, 0, st, op);
+        else hipLaunchKernelGGL((k_mx_operand<DYN, METHOD, false, false, LINE_FAST>), grid, block, 0, st, op);
+    }
+    return check_hip(what);
+}
+
+template <int FA>
+static void launch_mx_gemm_b(const MxGemmParams& p, int b_format, dim3 grid, hipStream_t st) {
+    if (b_format == LQ_ELEM_FP4_E2M1) hipLaunchKernelGGL((k_mx_gemm<FA, LQ_ELEM_FP4_E2M1>), grid, dim3(kBlock), 0, st, p);
+    else if (b_format == LQ_ELEM_FP8_E4M3) hipLaunchKernelGGL((k_mx_gemm<FA, LQ_ELEM_FP8_E4M3>), grid, dim3(kBlock), 0, st, p);
+    else hipLaunchKernelGGL((k_mx_gemm<FA, LQ_ELEM_FP8_E5M2>), grid, dim3(kBlock), 0, st, p);
+}
+}  // extern "C++"
+
+static void mx_operand_fill(MxOperandParams& op, const MxOperandDims& d, int format, int64_t L, int64_t K, void* codes, void* scales) {
+    mx_fill(op.mp, format, LQ_SCALE_E8M0);
+    op.codes = (uint8_t*)codes;
+    op.scales = (uint8_t*)scales;
+    op.L = (int32_t)L;
+    op.K = (int32_t)K;
+    op.nbk = (int32_t)((K + kMxBlockLen - 1) / kMxBlockLen);
+    op.LT = (int32_t)d.LT;
+    op.KT = (int32_t)d.KT;
+    op.KG = (int32_t)d.KG;
+}
+
+int lq_mx_operand_pack(const float* P, const float* s, int format, int scale_format, int64_t R, int64_t C, int axis, int64_t gs,
+                       void* codes, void* scales, void* stream) {
+    const char* fn = __func__;
+    int rc = check_group(fn, R, C, axis, gs);
+    if (rc) return rc;
+    LQ_REQUIRE_PTR_FN(fn, P);
+    LQ_REQUIRE_PTR_FN(fn, s);
+    if ((rc = check_mx(fn, format, scale_format))) return rc;
+    if (scale_format != LQ_SCALE_E8M0)
+        return fail(LQ_EINVAL, "%s: fp32 scales cannot be packed: the block-scaled matrix instruction takes E8M0 scales only", fn);
+    if (gs != kMxBlockLen) return fail(LQ_EINVAL, "%s: group size %lld: the instruction's block is %d", fn, (long long)gs, kMxBlockLen);
+    const int64_t L = axis == 0 ? C : R, K = axis == 0 ? R : C;
+    MxOperandDims d;
+    if ((rc = mx_operand_dims(fn, format, L, K, d))) return rc;
+    if ((rc = check_mx_operand_buffers(fn, codes, scales))) return rc;
+    MxOperandParams op{};
+    mx_operand_fill(op, d, format, L, K, codes, scales);
+    op.mp.g.P = P;
+    op.mp.g.s = s;
+    op.line_stride = axis == 0 ? 1 : C;
+    op.k_stride = axis == 0 ? C : 1;
+    op.s_line_stride = axis == 0 ? 1 : op.nbk;      // [nb][C] | [R][nb]
+    op.s_blk_stride = axis == 0 ? C : 1;
+    const bool fp4 = format == LQ_ELEM_FP4_E2M1;
+    if (axis == 0) return launch_mx_operand<false, kInitMxOcp, true>(op, fp4, false, "microscaling operand pack", stream);
+    return launch_mx_operand<false, kInitMxOcp, false>(op, fp4, C % 4 == 0 && aligned(P, 16), "microscaling operand pack", stream);
+}
+
+int lq_mx_operand_quantize(const float* X, int format, int method, int64_t M, int64_t K, void* codes, void* scales, void* stream) {
+    const char* fn = __func__;
+    LQ_REQUIRE_PTR_FN(fn, X);
+    if (method != LQ_MX_INIT_OCP && method != LQ_MX_INIT_COVER) return fail(LQ_EINVAL, "%s: bad method %d", fn, method);
+    MxOperandDims d;
+    int rc = mx_operand_dims(fn, format, M, K, d);
+    if (rc) return rc;
+    if ((rc = check_mx_operand_buffers(fn, codes, scales))) return rc;
+    MxOperandParams op{};
+    mx_operand_fill(op, d, format, M, K, codes, scales);
+    op.mp.g.P = X;
+    op.line_stride = K;
+    op.k_stride = 1;
+    op.ip.emax = kMxFormats[format].emax;
+    op.ip.mm_frac = kMxFormats[format].mm_frac;
+    op.ip.min_value = 1.17549435082228750797e-38f;      // 2^-126: the smallest scale an E8M0 byte of s_eff can hold
+    const bool fp4 = format == LQ_ELEM_FP4_E2M1;
+    const bool vec = K % 4 == 0 && aligned(X, 16);
+    if (method == LQ_MX_INIT_OCP) return launch_mx_operand<true, kInitMxOcp, false>(op, fp4, vec, "microscaling operand quantize", stream);
+    return launch_mx_operand<true, kInitMxCover, false>(op, fp4, vec, "microscaling operand quantize", stream);
+}
+
+int lq_mx_operand_decode(const void* codes, const void* scales, int format, int64_t L, int64_t K, float* out, void* stream) {
+    const char* fn = __func__;
+    MxOperandDims d;
+    int rc = mx_operand_dims(fn, format, L, K, d);
+    if (rc) return rc;
+    if ((rc = check_mx_operand_buffers(fn, codes, scales))) return rc;
+    LQ_REQUIRE_PTR_FN(fn, out);
+    MxDecodeParams dp{};
+    dp.codes = (const uint8_t*)codes;
+    dp.scales = (const uint8_t*)scales;
+    dp.out = out;
+    dp.L = (int32_t)L;
+    dp.K = (int32_t)K;
+    dp.KT = (int32_t)d.KT;
+    dp.KG = (int32_t)d.KG;
+    dp.M = kMxFormats[format].M;
+    dp.emin = kMxFormats[format].emin;
+    dp.bits = kMxFormats[format].bits;
+    const int64_t n = L * K;
+    hipLaunchKernelGGL(k_mx_operand_decode, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream, dp);
+    return check_hip("microscaling operand decode");
+}
+
+int lq_mx_gemm(const void* a_codes, const void* a_scales, int a_format, const void* b_codes, const void* b_scales, int b_format,
+               const float* bias, float* Y, int64_t M, int64_t N, int64_t K, int64_t ldy, void* stream) {
+    const char* fn = __func__;
+    MxOperandDims da, db;
+    int rc = mx_operand_dims(fn, a_format, M, K, da);
+    if (rc || (rc = mx_operand_dims(fn, b_format, N, K, db))) return rc;
+    if ((rc = check_mx_operand_buffers(fn, a_codes, a_scales))) return rc;
+    if ((rc = check_mx_operand_buffers(fn, b_codes, b_scales))) return rc;
+    LQ_REQUIRE_PTR_FN(fn, Y);
+    if (bias && !aligned(bias, 4)) return fail(LQ_EALIGN, "%s: bias is not 4-byte aligned", fn);
+    if (ldy < N) return fail(LQ_EINVAL, "%s: ldy = %lld is below N = %lld", fn, (long long)ldy, (long long)N);
+    if ((double)M * (double)ldy >= 9.0e15) return fail(LQ_EINVAL, "%s: Y is too large", fn);
+    MxGemmParams p{};
+    p.a_codes = (const uint8_t*)a_codes;
+    p.a_scales = (const uint8_t*)a_scales;
+    p.b_codes = (const uint8_t*)b_codes;
+    p.b_scales = (const uint8_t*)b_scales;
+    p.bias = bias;
+    p.Y = Y;
+    p.ldy = ldy;
+    p.M = (int32_t)M;
+    p.N = (int32_t)N;
+    p.MT = (int32_t)da.LT;
+    p.NT = (int32_t)db.LT;
+    p.KT = (int32_t)da.KT;
+    p.KG = (int32_t)da.KG;
+    const int64_t gx = (db.LT + 3) / 4, gy = (da.LT + 3) / 4;      // a block is 4 x 4 tiles: 64 x 64 of Y
+    if (gy > 65535) return fail(LQ_EINVAL, "%s: M = %lld is above 65535 * 64", fn, (long long)M);
+    const dim3 grid((unsigned)gx, (unsigned)gy);
+    hipStream_t st = (hipStream_t)stream;
+    if (a_format == LQ_ELEM_FP4_E2M1) launch_mx_gemm_b<LQ_ELEM_FP4_E2M1>(p, b_format, grid, st);
+    else if (a_format == LQ_ELEM_FP8_E4M3) launch_mx_gemm_b<LQ_ELEM_FP8_E4M3>(p, b_format, grid, st);
+    else launch_mx_gemm_b<LQ_ELEM_FP8_E5M2>(p, b_format, grid, st);
+    return check_hip("microscaling GEMM");
 }
 
 int lq_fq_fwd_bwd_fused(const float* P, const float* s, const float* dy, float lambda, float* out, float* ds, void* ws,

@@ -642,10 +642,43 @@ class CustomDenseLayer(_HostLayer):
     def call(self, inputs):
         if not self.built:
             self.build(tuple(inputs.shape), device=inputs.device)
+        hw = getattr(self, "_mx_hw", None)
+        if hw is not None and not self.training:                  # inside layers.mx_hardware(...), eval mode
+            self._q_pre = None                                    # a batch's fake-quantised pair is not what this path multiplies
+            return self._mx_product(inputs, *hw)
         qw, qb = self.quantized_parameters()
         return torch.add(torch.matmul(inputs, qw), qb)           # NQ-L:268
 
     forward = call
+
+    def mx_operand(self) -> "ops.MxOperand":
+        """The kernel under its current scales as an operand of the block-scaled matrix instruction (ops.mx_operand_pack): ``units``
+        lines over K = in.  ValueError naming the reason for a layer without an element format, with ``scale_format="fp32"``, with
+        an fp6 format or with a group size other than 32."""
+        ops.check_mx_operand_layer(self.element_format, self.scale_format, self.group_size)
+        if not self.built:
+            raise ValueError(f"{self.name}: the layer is not built yet (no kernel to pack)")
+        return ops.mx_operand_pack(self.W.detach(), self.nested_q_w_layer.scale.data, self.element_format, self.group_size,
+                                   self.scale_format)
+
+    def _mx_product(self, inputs, operand, qb, act_format, act_scale):
+        with torch.no_grad():
+            x = inputs.reshape(-1, inputs.shape[-1])
+            a = ops.mx_operand_quantize(x, act_format, act_scale)
+            if isinstance(operand, torch.Tensor):                 # mx_hardware(emulate=True): the fake-quantised kernel itself
+                y = torch.add(torch.matmul(ops.mx_operand_decode(a), operand), qb)
+            else:
+                y = ops.mx_gemm(a, operand, qb)
+            return y.reshape(*inputs.shape[:-1], y.shape[-1])
+
+    def call_mx(self, inputs, act_format="fp8_e4m3", act_scale="mx"):
+        """The layer on the block-scaled matrix instruction, under ``no_grad``: the inputs quantised per block of 32 along their last
+        axis (``act_format`` elements under the ``act_scale`` rule, ops.mx_operand_quantize), multiplied with ``mx_operand()`` by
+        ops.mx_gemm, plus the fake-quantised bias.  Inference only: there is no backward through this path."""
+        if not self.built:
+            self.build(tuple(inputs.shape), device=inputs.device)
+        with torch.no_grad():
+            return self._mx_product(inputs, self.mx_operand(), self.nested_q_b_layer(self.b), act_format, act_scale)
 
 
 _KERNEL_STORAGE = ["oihw"]
@@ -817,6 +850,41 @@ def custom_layers_of(model: nn.Module):
     """The reference selects layers by name substring (experiment.py:73, custom_loss_terms/experiment.py:446)."""
     return [m for m in model.modules()
             if isinstance(m, (CustomDenseLayer, _ConvBase))]
+
+
+def mx_hardware_eligible(layer: nn.Module) -> bool:
+    """Whether ``layer`` takes the block-scaled GEMM under ``mx_hardware``: a built Dense layer with an fp4 / fp8 element format,
+    E8M0 scales and blocks of 32.  Conv layers keep the fake-quantised path (no implicit GEMM is built)."""
+    return (isinstance(layer, CustomDenseLayer) and layer.built and layer.element_format in ops.MX_OPERAND_FORMATS
+            and layer.scale_format == "e8m0" and layer.group_size == ops.MX_GROUP_SIZE)
+
+
+class mx_hardware:
+    """Context manager: inside it every eligible Dense layer of ``model`` (``mx_hardware_eligible``) computes its eval-mode ``call``
+    as ``call_mx`` does -- activations quantised per block (``act_format``, ``act_scale``), the product on the block-scaled matrix
+    instruction.  The operands and the fake-quantised biases are built ONCE, on entry, from the scales the layers have then;
+    training-mode calls and every other layer keep the fake-quantised path.  ``layers`` lists the layers that switched.
+    ``emulate=True`` is the yardstick of that path in stock arithmetic: the same quantised activations, decoded, times the
+    fake-quantised kernel with ``torch.matmul`` -- what the block-scaled product is compared against."""
+
+    def __init__(self, model: nn.Module, act_format="fp8_e4m3", act_scale="mx", emulate=False):
+        ops.check_mx_operand_format(act_format)
+        ops.check_mx_scale_init(act_scale)
+        self.model, self.act_format, self.act_scale, self.emulate = model, act_format, act_scale, bool(emulate)
+        self.layers = []
+
+    def __enter__(self):
+        self.layers = [m for m in custom_layers_of(self.model) if mx_hardware_eligible(m)]
+        with torch.no_grad():
+            for m in self.layers:
+                weight = m.nested_q_w_layer(m.W).detach() if self.emulate else m.mx_operand()
+                m._mx_hw = (weight, m.nested_q_b_layer(m.b).detach(), self.act_format, self.act_scale)
+        return self
+
+    def __exit__(self, *exc):
+        for m in self.layers:
+            m._mx_hw = None
+        return False
 
 
 def quantized_tensors(model: nn.Module):

@@ -496,6 +496,120 @@ def scale_init_mx(parameter: torch.Tensor, scale: torch.Tensor, element_format: 
     return scale
 
 
+# --------------------------------------------------------------------------- packed MX operands and the block-scaled GEMM
+MX_OPERAND_FORMATS = ("fp4_e2m1", "fp8_e4m3", "fp8_e5m2")      # what the fragments are built for (include/lq_hip.h)
+
+
+class MxOperand(NamedTuple):
+    """A matrix of ``lines`` by ``K`` in the order gfx950's block-scaled matrix instruction consumes it (include/lq_hip.h, "packed
+    MX operands"): ``codes`` and ``scales`` are opaque uint8 buffers of lq_mx_operand_bytes' sizes."""
+    codes: torch.Tensor
+    scales: torch.Tensor
+    format: str
+    lines: int
+    K: int
+
+
+def check_mx_operand_format(element_format) -> ElementFormat:
+    """The table row of an operand's ``element_format``, or ValueError: the fp6 formats are not built."""
+    fmt = check_element_format(element_format)
+    if element_format not in MX_OPERAND_FORMATS:
+        raise ValueError(f"element_format={element_format!r}: fp6 operands are not supported (6-bit lanes need a fragment packing "
+                         f"of their own); the block-scaled GEMM takes one of {MX_OPERAND_FORMATS}")
+    return fmt
+
+
+def check_mx_operand_layer(element_format, scale_format, group_size) -> ElementFormat:
+    """What a quantizer must be to run on the block-scaled matrix instruction, or ValueError naming the reason."""
+    if element_format is None:
+        raise ValueError("the block-scaled GEMM needs a layer with an element_format (a microscaling layer)")
+    fmt = check_mx_operand_format(element_format)
+    if scale_format != "e8m0":
+        raise ValueError(f'scale_format={scale_format!r}: the block-scaled matrix instruction takes E8M0 (power-of-two) scales only')
+    if group_size != MX_GROUP_SIZE:
+        raise ValueError(f"group_size={group_size!r}: the block of the block-scaled matrix instruction is {MX_GROUP_SIZE}")
+    return fmt
+
+
+def mx_operand_bytes(element_format: str, lines: int, K: int) -> Tuple[int, int]:
+    """(code_bytes, scale_bytes) of an operand (include/lq_hip.h, lq_mx_operand_bytes).  Needs no device."""
+    import ctypes
+    fmt = check_mx_operand_format(element_format)
+    cb, sb = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _hip.check(_hip.load().lq_mx_operand_bytes(fmt.id, int(lines), int(K), ctypes.byref(cb), ctypes.byref(sb)), "lq_mx_operand_bytes")
+    return int(cb.value), int(sb.value)
+
+
+def _mx_operand_buffers(element_format: str, lines: int, K: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
+    cb, sb = mx_operand_bytes(element_format, lines, K)
+    return torch.empty(cb, dtype=torch.uint8, device=device), torch.empty(sb, dtype=torch.uint8, device=device)
+
+
+def mx_operand_pack(parameter: torch.Tensor, scale: torch.Tensor, element_format: str, group_size: int = MX_GROUP_SIZE,
+                    scale_format: str = "e8m0") -> MxOperand:
+    """The operand of a stored parameter under its stored group-wise scales (include/lq_hip.h, lq_mx_operand_pack): the codes are
+    those of ``fq_forward_mx``'s code view, the scale bytes the exponents of its effective scales.  The lines are the parameter's
+    columns when the blocks run along its strided axis (a Dense kernel (in, out)), its rows otherwise.  One launch."""
+    fmt = check_mx_operand_layer(element_format, scale_format, group_size)
+    lib = _hip.load()
+    p, s, (R, C, axis) = _group_param(parameter, scale, group_size)
+    lines, K = (C, R) if axis == 0 else (R, C)
+    codes, scales = _mx_operand_buffers(element_format, lines, K, p.device)
+    _hip.check(lib.lq_mx_operand_pack(_hip.ptr(p), _hip.ptr(s), fmt.id, check_scale_format(scale_format), R, C, axis, int(group_size),
+                                      _hip.ptr(codes), _hip.ptr(scales), _hip.stream_ptr(p.device)), "lq_mx_operand_pack")
+    return MxOperand(codes, scales, element_format, lines, K)
+
+
+def mx_operand_quantize(x: torch.Tensor, element_format: str = "fp8_e4m3", method: str = "mx") -> MxOperand:
+    """The operand of a row-major activation matrix ``x (M, K)`` under scales taken from ``x`` itself (include/lq_hip.h,
+    lq_mx_operand_quantize): per block of 32 along K what ``scale_init_mx(method, min_value=2^-126)`` writes, then the codes of
+    ``fq_forward_mx`` under it.  No learned state, no backward.  One launch, one read of ``x``."""
+    fmt = check_mx_operand_format(element_format)
+    m = check_mx_scale_init(method)
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise ValueError(f"x must be a matrix (M, K), got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
+    lib = _hip.load()
+    xc = _hip.require_device_f32(x, "x")
+    M, K = (int(d) for d in xc.shape)
+    codes, scales = _mx_operand_buffers(element_format, M, K, xc.device)
+    _hip.check(lib.lq_mx_operand_quantize(_hip.ptr(xc), fmt.id, m, M, K, _hip.ptr(codes), _hip.ptr(scales),
+                                          _hip.stream_ptr(xc.device)), "lq_mx_operand_quantize")
+    return MxOperand(codes, scales, element_format, M, K)
+
+
+def mx_operand_decode(operand: MxOperand) -> torch.Tensor:
+    """float32 ``(lines, K)``: value(code) * 2^(byte - 127) of every element (include/lq_hip.h, lq_mx_operand_decode)."""
+    fmt = check_mx_operand_format(operand.format)
+    lib = _hip.load()
+    out = torch.empty((operand.lines, operand.K), dtype=torch.float32, device=operand.codes.device)
+    _hip.check(lib.lq_mx_operand_decode(_hip.ptr(operand.codes), _hip.ptr(operand.scales), fmt.id, operand.lines, operand.K,
+                                        _hip.ptr(out), _hip.stream_ptr(out.device)), "lq_mx_operand_decode")
+    return out
+
+
+def mx_gemm(a: MxOperand, b: MxOperand, bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``Y (a.lines, b.lines) = A B^T (+ bias)`` in fp32 on v_mfma_scale_f32_16x16x128_f8f6f4 (include/lq_hip.h, lq_mx_gemm).
+    ``out``: a float32 matrix to write into; its row stride is the leading dimension."""
+    fa, fb = check_mx_operand_format(a.format), check_mx_operand_format(b.format)
+    if a.K != b.K:
+        raise ValueError(f"the operands reduce over different K: {a.K} and {b.K}")
+    lib = _hip.load()
+    M, N = a.lines, b.lines
+    dev = a.codes.device
+    if bias is not None:
+        bias = _hip.require_device_f32(bias, "bias")
+        if tuple(bias.shape) != (N,):
+            raise ValueError(f"bias must have shape ({N},), got {tuple(bias.shape)}")
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (M, N) or (N > 1 and out.stride(1) != 1) or not out.is_cuda:
+        raise ValueError(f"out must be a float32 device matrix ({M}, {N}) with unit column stride")
+    ldy = out.stride(0) if M > 1 else max(N, out.stride(0))
+    _hip.check(lib.lq_mx_gemm(_hip.ptr(a.codes), _hip.ptr(a.scales), fa.id, _hip.ptr(b.codes), _hip.ptr(b.scales), fb.id,
+                              _hip.ptr(bias), _hip.ptr(out), M, N, a.K, ldy, _hip.stream_ptr(dev)), "lq_mx_gemm")
+    return out
+
+
 STATS_MAX_BINS = 4096     # include/lq_hip.h, lq_group_stats: the widest range whose codes it bins
 
 

@@ -31,7 +31,7 @@ from . import _hip
 from .ddp import CaptureRefused, DataParallel, capture_with_agreement, control_group
 from .losses import LossLog, SCCEDifference, SCCEInverse, SCCEMaxBin, sparse_categorical_crossentropy
 from .models import INPUT_SHAPES, build_model, check_asymmetric_model, check_clip_mode, check_group_mode, check_mx_model
-from .ops import (ELEMENT_FORMATS, LAYER_SCALE_INITS, MX_SCALE_INITS, ROUNDINGS, SCALE_FORMATS, check_element_format, check_minmax_range,
+from .ops import (ELEMENT_FORMATS, LAYER_SCALE_INITS, MX_OPERAND_FORMATS, MX_SCALE_INITS, ROUNDINGS, SCALE_FORMATS, check_element_format, check_minmax_range,
                   check_rounding, check_scale_format, q_range_of)
 from .optim import KerasAdam, ScaleAdam, non_scale_parameters, scale_parameters
 
@@ -601,12 +601,47 @@ def build_parser():
     ap.add_argument("--mx-stats", action="store_true",
                     help="with --element-format: add layers.mx_quant_stats of the final parameters to the result line (per tensor: "
                          "saturated and flushed shares, SQNR in dB, encodings in use, code entropy); taken after the timed steps")
+    ap.add_argument("--mx-eval", nargs="?", const="fp8_e4m3", default=None, choices=list(MX_OPERAND_FORMATS), metavar="ACT_FORMAT",
+                    help="with --element-format: evaluate the final model once more under layers.mx_hardware (Dense layers on the "
+                         "block-scaled matrix instruction, activations quantised per block to ACT_FORMAT, default fp8_e4m3) and add "
+                         "mx_eval_accuracy, mx_eval_accuracy_fake (the same quantised activations times the fake-quantised weights "
+                         "with torch.matmul) and mx_eval_max_logit_diff to the result line")
     return ap
+
+
+@torch.no_grad()
+def mx_eval(model, x, y, act_format="fp8_e4m3", act_scale="mx"):
+    """One evaluation of ``model`` on (x, y) under layers.mx_hardware and one under its ``emulate=True`` yardstick: a dict of both
+    accuracies and the largest |difference| of the outputs of the last Dense layer that took the path (the logits of the MNIST
+    model)."""
+    was_training = model.training
+    model.eval()
+    acc, logits = [], []
+    try:
+        for emulate in (False, True):
+            with L.mx_hardware(model, act_format, act_scale, emulate=emulate) as hw:
+                if not hw.layers:
+                    raise ValueError("mx_eval: the model has no Dense layer that can run on the block-scaled matrix instruction "
+                                     "(fp4 / fp8 element format, E8M0 scales, blocks of 32)")
+                seen = []
+                hook = hw.layers[-1].register_forward_hook(lambda m, i, o: seen.append(o.detach()))
+                try:
+                    p = model(x)
+                finally:
+                    hook.remove()
+                acc.append(float((p.argmax(1) == y).float().mean()))
+                logits.append(seen[-1])
+    finally:
+        model.train(was_training)
+    return {"mx_eval_act_format": act_format, "mx_eval_layers": len(hw.layers), "mx_eval_accuracy": acc[0],
+            "mx_eval_accuracy_fake": acc[1], "mx_eval_max_logit_diff": float((logits[0] - logits[1]).abs().max())}
 
 
 def main(argv=None):
     ap = build_parser()
     args = ap.parse_args(argv)
+    if args.mx_eval is not None and args.element_format is None:
+        ap.error("--mx-eval needs --element-format: it runs the layers of a microscaling model on the block-scaled matrix instruction")
     if args.quant_stats and args.bits is None:
         ap.error("--quant-stats needs --bits: the statistics are those of a quantizer with a range")
     if args.mx_stats and args.element_format is None:
@@ -674,6 +709,7 @@ def main(argv=None):
     log_rows = tr.flush_loss_log() if args.loss_values and rank == 0 else None     # every rank holds the same rows: one writes
     quant_stats = L.quant_stats(tr.model) if args.quant_stats and rank == 0 else None      # after the clock has stopped
     mx_stats = L.mx_quant_stats(tr.model) if args.mx_stats and rank == 0 else None
+    mx_eval_fields = mx_eval(tr.model, *batches[0], act_format=args.mx_eval) if args.mx_eval is not None and rank == 0 else None
     if rank == 0:
         n_q = sum(p.numel() for l in tr.custom_layers for p in l._regularized())
         print(json.dumps({
@@ -699,7 +735,8 @@ def main(argv=None):
             **({"scale_init": tr.scale_init} if tr.scale_init is not None else {}),
             **({"loss_values": True, "loss_log_rows": log_rows[0], "loss_log_dropped": log_rows[1]} if log_rows else {}),
             **({"quant_stats": quant_stats} if quant_stats is not None else {}),
-            **({"mx_stats": mx_stats} if mx_stats is not None else {})}))
+            **({"mx_stats": mx_stats} if mx_stats is not None else {}),
+            **(mx_eval_fields or {})}))
         if args.export_dir:
             from .export import save_compress_parameters
             print(json.dumps(save_compress_parameters(tr.model, args.export_dir)))

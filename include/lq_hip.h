@@ -411,13 +411,15 @@ int lq_mx_stats(const float* P, const float* s, int format, int scale_format, ui
  *                              fp8: k = 16 g + j in byte j and k = 64 + 16 g + j in byte 16 + j, j = 0 .. 15 (halves of two blocks)
  *   scales  [LT][KG][64][4]    byte u of dword `lane` of cell (lt, kg) is the E8M0 byte of block g (k = 32 g .. 32 g + 31) of K step
  *                              kt = 4 kg + u of that line, for every format
- *   code_bytes = LT * KT * 64 * FB, scale_bytes = LT * KG * 256.  Lines past L and elements past K hold code 0 under byte 127.
+ *   code_bytes = LT * KT * 64 * FB, scale_bytes = LT * KG * 256.  Lines past L and elements past K hold code 0 under byte 127, and
+ *   the scale bytes of the K steps KT .. 4 KG - 1, which no instruction reads, are 127 too: the buffers are a function of the input.
  * This is the lane map of the instruction as pinned on the device by exact-arithmetic GEMM tests (tests/test_gpu_mx_gemm.py): lane l
  * supplies the A (B) line l & 15; 4-bit data is one block per lane, 8-bit data two half blocks 64 apart; the scale byte selected by
  * op-sel from lane l's scale register applies to block l >> 4 whichever lane holds its data; the result tile has column l & 15 on the
  * lane and rows 4 (l >> 4) + r in register r.
  * The scale byte of a block is the biased exponent of its s_eff (a power of two in [2^-126, 2^127]: bytes 1 .. 254); byte 255
- * marks a block whose s_eff is NaN.
+ * marks a block whose s_eff is NaN.  Pack and quantize never write byte 0; decode and the GEMM accept it in a buffer built elsewhere
+ * and read it as OCP defines E8M0, 2^-127.
  *
  * lq_mx_operand_pack: the operand of a stored parameter under its stored scales.  Geometry is lq_fq_forward_group's ([R][C] in
  * memory order, s [nb][C] or [R][nb]).  axis 0: the lines are the C columns and K = R (a Dense kernel (in, out)); axis 1: the lines
@@ -431,6 +433,12 @@ int lq_mx_stats(const float* P, const float* s, int format, int scale_format, ui
  * lq_mx_gemm: Y[m][n] = sum_k A[m][k] * B[n][k] (+ bias[n]) in fp32, Y row-major with leading dimension ldy >= N, A and B operands of
  * M and N lines over the same K, any of the nine format pairs.  The products and the sum of a K step of 128 are the instruction's;
  * the steps accumulate in ascending K into fp32; the bias is added last, one fp32 addition.  No atomics: run-to-run bit-stable.
+ * Every element code is the instruction's: subnormals, the top binade, NaN (fp8_e4m3 S.1111.111; fp8_e5m2 S.11111.mm) and +-Inf
+ * (fp8_e5m2) multiply as IEEE values do (0 * Inf = NaN).  The two scale bytes of a product act on its EXPONENT, not on one operand at
+ * a time in fp32: a product under bytes 254 and 1, or 0 and 254, is exact although one scaled operand alone leaves fp32's normal
+ * range; a block under byte 255 makes its line's results NaN.  Measured on an MI355X, one term per output, bytes 0 .. 255 on both
+ * sides (tests/test_gpu_mx_gemm_codes.py): exact inside [2^-126, 2^128), +-Inf from 2^128, and below 2^-126 the correctly rounded
+ * fp32 SUBNORMAL (nearest, ties to even) -- nothing is flushed; a result that rounds to zero is +0 whatever the product's sign.
  *
  * LQ_EINVAL before any launch: a NULL pointer (bias may be NULL), a non-positive extent, L * K >= 2^31, an unknown format or
  * method, an fp6 format (6-bit lanes need a 96-byte fragment packing of their own: not built), scale_format LQ_SCALE_FP32 (the

@@ -4,7 +4,9 @@ that tests/test_mx_gemm_cpu.py can assert every data condition without a device.
 
 An operand is held in its LOGICAL form: codes int64 (L, K) and E8M0 bytes int64 (L, ceil(K / 32)), both taken from
 tests/_mx_reference.py (mx_reference / init_reference: the definitions the quantizer itself is tested against).  The tile and lane
-order of the device buffers never enters: the tests reach them through decode and through the GEMM's results only.
+order of the device buffers enters in ONE place, pack_layout / unpack_layout: a restatement of the text of include/lq_hip.h ("packed
+MX operands"), not of csrc/lq_mx_operand.hpp, so that the bytes the device writes are held to the documented format and buffers
+built here can be handed to decode and to the GEMM.
 Values come from learned_quantization_amd.ops.mx_decode_table; Y and sum|terms| are float64."""
 from collections import namedtuple
 
@@ -41,14 +43,16 @@ def operand_of_activation(x, name, method):
 
 
 def decode(op, dtype=np.float64):
-    """value(code) * 2^(byte - 127), (L, K); float32: one rounding, as the device multiplies."""
+    """value(code) * 2^(byte - 127), (L, K): byte 255 is NaN, byte 0 is 2^-127 as OCP defines E8M0.  The float64 product is exact
+    (at most 4 significant bits times a power of two); float32 is that product rounded ONCE, as the device's one fp32
+    multiplication rounds it -- into the float32 subnormals below 2^-126, to +-Inf from 2^128."""
     from learned_quantization_amd import ops
     table = ops.mx_decode_table(op.name)
     K = op.codes.shape[1]
     with np.errstate(all="ignore"):
-        scale = np.where(op.bytes == 255, np.nan, np.exp2(op.bytes.astype(np.float64) - 127.0))
+        scale = np.where(op.bytes == 255, np.nan, np.ldexp(1.0, (op.bytes - 127).astype(np.int64)))
         scale = np.repeat(scale, BLOCK, axis=1)[:, :K]
-        return (table[op.codes].astype(dtype) * scale.astype(dtype)).astype(dtype)
+        return (table[op.codes].astype(np.float64) * scale).astype(dtype)
 
 
 def gemm_reference(a, b, bias=None):
@@ -60,14 +64,93 @@ def gemm_reference(a, b, bias=None):
     return Y, T
 
 
+# ------------------------------------------------------------------------------------- the documented layout (include/lq_hip.h)
+def layout_dims(L, K):
+    """(LT, KT, KG): tiles of 16 lines, K steps of 128, scale dwords per lane."""
+    KT = -(-K // 128)
+    return -(-L // 16), KT, -(-KT // 4)
+
+
+def _layout_offsets(name, L, K):
+    """(code byte offset (L, K), nibble shift (L, K), scale byte offset (L, nb)) of every live element and block, from the header:
+    fragment `lane` = 16 g + r of tile (lt, kt) holds line 16 lt + r; fp4: k = 32 g + j in nibble j & 1 of byte j >> 1; fp8:
+    k = 16 g + j in byte j and k = 64 + 16 g + j in byte 16 + j; byte u of dword `lane` of cell (lt, kg) is block g of K step 4 kg + u."""
+    LT, KT, KG = layout_dims(L, K)
+    ln, k = np.arange(L, dtype=np.int64)[:, None], np.arange(K, dtype=np.int64)[None, :]
+    lt, r, kt, kk = ln >> 4, ln & 15, k >> 7, k & 127
+    if name == "fp4_e2m1":
+        g, j = kk >> 5, kk & 31
+        off, shift = ((lt * KT + kt) * 64 + 16 * g + r) * 16 + (j >> 1), 4 * (j & 1) + 0 * ln
+    else:
+        h, g, j = kk >> 6, (kk & 63) >> 4, kk & 15
+        off, shift = ((lt * KT + kt) * 64 + 16 * g + r) * 32 + 16 * h + j, 0 * (ln + k)
+    kb = np.arange(-(-K // BLOCK), dtype=np.int64)[None, :]
+    kt, g = kb >> 2, kb & 3
+    soff = ((lt * KG + (kt >> 2)) * 64 + 16 * g + r) * 4 + (kt & 3)
+    return off, shift, soff
+
+
+def pack_layout(codes, bytes_, name):
+    """The two uint8 buffers of lq_mx_operand_bytes' sizes that hold the logical operand codes (L, K), bytes (L, ceil(K / 32)) in
+    the documented order.  Everything no live (line, k) addresses is code 0 and byte 127: the lines L .. 16 LT - 1, the elements
+    past K and the scale bytes of the K steps KT .. 4 KG - 1."""
+    codes, bytes_ = np.asarray(codes, np.int64), np.asarray(bytes_, np.int64)
+    L, K = codes.shape
+    assert name in OPERAND_FORMATS and bytes_.shape == (L, -(-K // BLOCK))
+    assert codes.min() >= 0 and codes.max() < (16 if name == "fp4_e2m1" else 256) and bytes_.min() >= 0 and bytes_.max() <= 255
+    LT, KT, KG = layout_dims(L, K)
+    cbuf = np.zeros(LT * KT * 64 * (16 if name == "fp4_e2m1" else 32), np.uint8)
+    sbuf = np.full(LT * KG * 256, 127, np.uint8)
+    off, shift, soff = _layout_offsets(name, L, K)
+    np.bitwise_or.at(cbuf, off.reshape(-1), (codes << shift).astype(np.uint8).reshape(-1))      # two nibbles share a byte
+    assert np.unique(soff).size == soff.size
+    sbuf[soff.reshape(-1)] = bytes_.astype(np.uint8).reshape(-1)
+    return cbuf, sbuf
+
+
+def unpack_layout(cbuf, sbuf, name, L, K):
+    """The inverse of pack_layout on the live part: (codes (L, K), bytes (L, ceil(K / 32))), int64."""
+    cbuf, sbuf = np.asarray(cbuf, np.uint8).reshape(-1), np.asarray(sbuf, np.uint8).reshape(-1)
+    LT, KT, KG = layout_dims(L, K)
+    assert name in OPERAND_FORMATS and cbuf.size == LT * KT * 64 * (16 if name == "fp4_e2m1" else 32) and sbuf.size == LT * KG * 256
+    off, shift, soff = _layout_offsets(name, L, K)
+    return (cbuf[off].astype(np.int64) >> shift) & (15 if name == "fp4_e2m1" else 255), sbuf[soff].astype(np.int64)
+
+
+def layout_mismatch(cbuf, sbuf, ref):
+    """None if the device buffers hold exactly pack_layout(ref), padding included; otherwise a message that names the first
+    differing (line, k) or (line, block) through unpack_layout, or the first differing padding byte."""
+    L, K = ref.codes.shape
+    cbuf, sbuf = np.asarray(cbuf, np.uint8).reshape(-1), np.asarray(sbuf, np.uint8).reshape(-1)
+    wc, ws = pack_layout(ref.codes, ref.bytes, ref.name)
+    if cbuf.size != wc.size or sbuf.size != ws.size:
+        return f"sizes ({cbuf.size}, {sbuf.size}), documented ({wc.size}, {ws.size})"
+    if np.array_equal(cbuf, wc) and np.array_equal(sbuf, ws):
+        return None
+    codes, bytes_ = unpack_layout(cbuf, sbuf, ref.name, L, K)
+    bad = np.argwhere(codes != ref.codes)
+    if bad.size:
+        ln, k = bad[0]
+        return f"{len(bad)} codes differ, first at (line, k) = ({ln}, {k}): buffer holds {codes[ln, k]}, reference {ref.codes[ln, k]}"
+    bad = np.argwhere(bytes_ != ref.bytes)
+    if bad.size:
+        ln, kb = bad[0]
+        return f"{len(bad)} scale bytes differ, first at (line, block) = ({ln}, {kb}): buffer holds {bytes_[ln, kb]}, reference {ref.bytes[ln, kb]}"
+    bc, bs = np.flatnonzero(cbuf != wc), np.flatnonzero(sbuf != ws)
+    if bc.size:
+        return f"{bc.size} padding code bytes are not 0, first at byte {bc[0]}: {cbuf[bc[0]]}"
+    return f"{bs.size} padding scale bytes are not 127, first at byte {bs[0]}: {sbuf[bs[0]]}"
+
+
 # ----------------------------------------------------------------------------------------------------------------- data sets
 PACK_SHAPES = [(70, 40, 0), (160, 17, 0), (9, 200, 1), (33, 288, 1)]      # (R, C, axis): see tests/test_gpu_mx_gemm.py
 QUANT_SHAPES = [(5, 100), (33, 288)]
-EXACT_SHAPES = [(16, 16, 128), (19, 21, 160), (37, 10, 784), (64, 48, 512)]      # (M, N, K)
-EXACT_CASES = [(s, False) for s in EXACT_SHAPES] + [((19, 21, 160), True)]      # (shape, A is the identity pattern)
+EXACT_SHAPES = [(16, 16, 128), (19, 21, 160), (37, 10, 784), (64, 48, 512), (81, 70, 160), (17, 18, 1184), (129, 17, 160),
+                (17, 129, 160)]      # (M, N, K)
+EXACT_CASES = [(s, False) for s in EXACT_SHAPES] + [((19, 21, 160), True), ((81, 70, 160), True)]      # (shape, A is the identity pattern)
 RANDOM_SHAPES =[(37, 10, 784), (64, 48, 1024)]
 # Exact sets.  Elements are 0, +-1, +-1.5, +-2 (on the grid of all three formats), block scales 2^-2 .. 2^3 per block and line:
-# a nonzero term |a b| sa sb lies in [2^-4, 2^8], a range of 2^12, and is a multiple of 2^-6.  A sum of K <= 784 of them stays
+# a nonzero term |a b| sa sb lies in [2^-4, 2^8], a range of 2^12, and is a multiple of 2^-6.  A sum of K <= 1184 of them stays
 # far below 2^24 * 2^-6 = 2^18, so every partial sum in every order is a float32: tests/test_mx_gemm_cpu.py asserts it.
 EXACT_VALUES = np.array([0.0, 1.0, -1.0, 1.5, -1.5, 2.0, -2.0, 1.0, -2.0], np.float32)
 
@@ -139,3 +222,57 @@ def quantize_case(M, K):
     x[1, 32:64] = 0.0
     x[M - 1, K - 3] = np.inf
     return x
+
+
+# ------------------------------------------------------------------------------- one term per output: every code, every scale byte
+# Operands that are zero (code 0 under byte 127) except column k0, so that Y[m][n] is ONE product plus zeros and nothing is summed:
+# K = 160 is two K steps, the second a quarter full; k0 = 5 and 77 lie in the first and the second half of an fp8 fragment, 133 in the
+# second K step.  The buffers come from pack_layout, so codes and bytes no quantizer emits reach the instruction.
+SWEEP_K = 160
+CODE_K0S = (5, 77, 133)
+SCALE_K0 = 77
+SCALE_PAIRS = [("fp4_e2m1", "fp4_e2m1"), ("fp8_e4m3", "fp8_e5m2"), ("fp8_e5m2", "fp4_e2m1")]
+
+
+def _sweep_operand(name, column, k0, line_bytes=None):
+    L = len(column)
+    codes = np.zeros((L, SWEEP_K), np.int64)
+    codes[:, k0] = column
+    bytes_ = np.full((L, -(-SWEEP_K // BLOCK)), 127, np.int64)
+    if line_bytes is not None:
+        bytes_[:, k0 // BLOCK] = line_bytes
+    return RefOperand(codes, bytes_, name, None)
+
+
+def code_sweep_operand(name, k0):
+    """One line per code of the format (16 or 256 lines): line i holds code i at k0, every scale byte is 127."""
+    return _sweep_operand(name, np.arange(16 if name == "fp4_e2m1" else 256), k0)
+
+
+def code_of(name, value):
+    """The code of a value the format holds exactly."""
+    from learned_quantization_amd import ops
+    hit = np.flatnonzero(ops.mx_decode_table(name) == np.float32(value))
+    assert hit.size == 1, (name, value)
+    return int(hit[0])
+
+
+def scale_sweep_operand(name, negate_odd):
+    """256 lines: line i holds 1.5 (-1.5 on odd lines when ``negate_odd``) at SCALE_K0 under byte i (0 .. 255) for that block."""
+    sign = np.where((np.arange(256) & 1).astype(bool) & negate_odd, -1.5, 1.5)
+    column = np.array([code_of(name, v) for v in sign])
+    return _sweep_operand(name, column, SCALE_K0, np.arange(256))
+
+
+def scale_sweep_classes(ref):
+    """(normal, over, under): masks of the finite reference products in [2^-126, 2^128), from 2^128, below 2^-126."""
+    mag = np.abs(ref)
+    fin = ~np.isnan(ref)
+    return fin & (mag >= 2.0 ** -126) & (mag < 2.0 ** 128), fin & (mag >= 2.0 ** 128), fin & (mag < 2.0 ** -126)
+
+
+def decode_sweep_operand(name):
+    """256 lines by K = 256: line i under byte i in all of its blocks, column c holding code c mod 2^bits."""
+    n = 16 if name == "fp4_e2m1" else 256
+    codes = np.broadcast_to(np.arange(256, dtype=np.int64) % n, (256, 256)).copy()
+    return RefOperand(codes, np.repeat(np.arange(256, dtype=np.int64)[:, None], 256 // BLOCK, axis=1), name, None)

@@ -10,7 +10,15 @@ their conditions are tests/_mx_gemm_reference.py's, asserted without a device by
 Shapes, the smallest at which each mechanism can go wrong:  pack (70, 40) axis 0: one K step, a last block of 6 elements, 40 lines are
 no tile multiple; (160, 17) axis 0: a second K step that is a quarter full; (9, 200) and (33, 288) axis 1: the float4 loads, a ragged
 block, three line tiles.  GEMM (16, 16, 128): one instruction; (19, 21, 160): every edge masked, a second K step; (37, 10, 784): the
-MNIST layer, seven K steps -- a second scale dword, op-sel 0 .. 3; (64, 48, 512): a full block of four waves, an idle wave column."""
+MNIST layer, seven K steps -- a second scale dword, op-sel 0 .. 3; (64, 48, 512): a full block of four waves, an idle wave column;
+(81, 70, 160): MT = 6, NT = 5, a grid of 2 x 2 blocks -- blockIdx 1 on both axes, where block 1 has a clamped second N tile and a wave
+that leaves on each axis; (17, 18, 1184): KT = 10, KG = 3, a third scale dword that holds two steps, the last a quarter full;
+(129, 17, 160) and (17, 129, 160): nine tiles, THREE blocks on one axis -- with two blocks a block stride of one wave instead of two
+(blockIdx * 2 -> blockIdx) still covers every tile, twice over, and every result is right; the third block's last tile shows it.
+
+The buffers of pack and quantize are also compared BYTE FOR BYTE, padding included, with the NumPy packer of the layout that
+include/lq_hip.h documents (G.pack_layout): the device's decode shares its offset functions with pack and cannot see a wrong order.
+Every code and every scale byte through the instruction, one term per output: tests/test_gpu_mx_gemm_codes.py."""
 import ctypes
 import os
 import sys
@@ -68,6 +76,9 @@ def test_pack_then_decode_is_the_fake_quantised_parameter(dev, kind, name, shape
     got = _np(ops.mx_operand_decode(op))
     # codes and bytes, through decode: value(code) * 2^(byte - 127) of the reference's code view and scale bytes
     assert bits_equal(got, G.decode(ref, np.float32)), "decode differs from the reference's codes and scale bytes"
+    # the buffers themselves, byte for byte, padding included, against the layout include/lq_hip.h documents
+    bad = G.layout_mismatch(_np(op.codes), _np(op.scales), ref)
+    assert bad is None, f"the buffers are not the documented layout of the reference operand: {bad}"
     # and the device's own forward: `out` bit for bit, its code view through the table
     out, code = ops.fq_forward_mx(Pt, st, name, 32, "e8m0", q_dtype=torch.int32)
     turn = (lambda a: np.ascontiguousarray(a.T)) if axis == 0 else np.ascontiguousarray
@@ -102,6 +113,8 @@ def test_quantize_is_scale_init_then_forward(dev, name, method, shape):
     # and the NumPy reference of both steps
     ref, s_ref = G.operand_of_activation(x, name, method)
     assert bits_equal(_np(s), s_ref) and bits_equal(got, G.decode(ref, np.float32))
+    bad = G.layout_mismatch(_np(op.codes), _np(op.scales), ref)
+    assert bad is None, f"the buffers are not the documented layout of the reference operand: {bad}"
     again = ops.mx_operand_quantize(xt, name, method)
     assert torch.equal(again.codes, op.codes) and torch.equal(again.scales, op.scales), "two quantizations differ"
 
@@ -212,7 +225,7 @@ def test_memory_contract_of_quantize(dev, name, shape):
     assert torch.equal(ar.bytes("codes"), want.codes) and torch.equal(ar.bytes("scales"), want.scales)
 
 
-@pytest.mark.parametrize("shape", [(19, 21, 160), (37, 10, 784)], ids=_ids)
+@pytest.mark.parametrize("shape", [(19, 21, 160), (37, 10, 784), (81, 70, 160)], ids=_ids)
 def test_memory_contract_of_gemm(dev, shape):
     """Guard bands around Y with ldy = N + 3: the three columns between the rows keep the sentinel; the bias 4 bytes off the grid."""
     M, N, K = shape
@@ -237,7 +250,71 @@ def test_memory_contract_of_gemm(dev, shape):
     assert np.array_equal(np.ascontiguousarray(flat[:, :N]).view(np.float32).astype(np.float64), ref)
 
 
-# ----------------------------------------------------------------------------------------------------------------- 6 layers
+# ------------------------------------------------------------------------------------------------------ 6 capture and out=
+def test_capture_and_replay(dev):
+    """pack -> quantize -> gemm -> decode, one launch each, captured into pre-allocated buffers in one graph; the outputs are
+    poisoned before each of two replays and equal the eager results bit for bit."""
+    M, N, K = 19, 21, 160
+    fa, fb = "fp8_e4m3", "fp4_e2m1"
+    c = G.random_case(M, N, K, fa, fb)
+    x, W, sw, bias = _t(c["x"], dev), _t(c["W"], dev), _t(c["sw"], dev), _t(c["bias"], dev)
+    ea, eb = ops.mx_operand_quantize(x, fa, "mx"), ops.mx_operand_pack(W, sw, fb)
+    eager = [eb.codes, eb.scales, ea.codes, ea.scales, ops.mx_gemm(ea, eb, bias), ops.mx_operand_decode(ea)]
+    u8 = lambda n: torch.empty(n, dtype=torch.uint8, device=dev)      # noqa: E731
+    ac, as_, bc, bs = (u8(n) for n in ops.mx_operand_bytes(fa, M, K) + ops.mx_operand_bytes(fb, N, K))
+    Y, D = torch.empty((M, N), device=dev), torch.empty((M, K), device=dev)
+    outs = [bc, bs, ac, as_, Y, D]
+    lib = _hip.load()
+    ida, idb = X.FORMATS[fa].id, X.FORMATS[fb].id
+
+    def launch():
+        st = _hip.stream_ptr(dev)
+        _hip.check(lib.lq_mx_operand_pack(_hip.ptr(W), _hip.ptr(sw), idb, 0, K, N, 0, 32, _hip.ptr(bc), _hip.ptr(bs), st), "pack")
+        _hip.check(lib.lq_mx_operand_quantize(_hip.ptr(x), ida, ops.check_mx_scale_init("mx"), M, K, _hip.ptr(ac), _hip.ptr(as_), st), "quantize")
+        _hip.check(lib.lq_mx_gemm(_hip.ptr(ac), _hip.ptr(as_), ida, _hip.ptr(bc), _hip.ptr(bs), idb, _hip.ptr(bias), _hip.ptr(Y), M, N, K,
+                                  N, st), "gemm")
+        _hip.check(lib.lq_mx_operand_decode(_hip.ptr(ac), _hip.ptr(as_), ida, M, K, _hip.ptr(D), st), "decode")
+
+    torch.cuda.synchronize(dev)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        launch()
+    for _ in range(2):
+        for o in outs:
+            o.fill_(0xEE if o.dtype == torch.uint8 else -7.0)
+        g.replay()
+        torch.cuda.synchronize(dev)
+        for k, (o, e) in enumerate(zip(outs, eager)):
+            assert torch.equal(o.view(torch.uint8), e.view(torch.uint8)), f"output {k} of the replay differs from the eager call"
+    ref, terms = G.gemm_reference(*(G.operand_of_activation(c["x"], fa, "mx")[0], G.operand_of_parameter(c["W"], c["sw"], fb, 0)), c["bias"])
+    assert_within_terms(_np(Y), ref, terms, "captured mx_gemm")
+
+
+def test_gemm_out_with_a_row_stride(dev):
+    """out= a view of a wider matrix: its row stride is the leading dimension, the spare columns keep their contents."""
+    M, N, K = 19, 21, 160
+    c = _exact((M, N, K), False)
+    a = ops.mx_operand_pack(_t(c["A"], dev), _t(c["sa"], dev), "fp8_e4m3")
+    b = ops.mx_operand_pack(_t(c["W"], dev), _t(c["sw"], dev), "fp4_e2m1")
+    bias = _t(c["bias"], dev)
+    want = ops.mx_gemm(a, b, bias)
+    buf = torch.full((M, N + 3), -7.0, device=dev)
+    out = buf[:, :N]
+    assert out.stride() == (N + 3, 1)
+    got = ops.mx_gemm(a, b, bias, out=out)
+    assert got is out
+    assert torch.equal(buf[:, :N].contiguous().view(torch.int32), want.view(torch.int32)) and (buf[:, N:] == -7.0).all()
+    ref, _ = G.gemm_reference(*G.exact_operands(c, "fp8_e4m3", "fp4_e2m1"), c["bias"])
+    assert np.array_equal(_np(want).astype(np.float64), ref)
+    for bad in (torch.empty((M, N + 1), device=dev), torch.empty((M + 1, N), device=dev), torch.empty((N, M), device=dev),
+                torch.empty((M, N), dtype=torch.float64, device=dev), torch.empty((M, N), dtype=torch.int32, device=dev),
+                torch.empty((N, M), device=dev).t(), torch.empty((M, 2 * N), device=dev)[:, ::2]):
+        with pytest.raises(ValueError, match="out must be a float32 device matrix"):
+            ops.mx_gemm(a, b, bias, out=bad)
+    assert (buf[:, N:] == -7.0).all()
+
+
+# ----------------------------------------------------------------------------------------------------------------- 7 layers
 def _layer_reference(layer, x, act_format, act_scale):
     """(Y, sum|terms|) in float64: quantize -> decode -> matmul with the fake-quantised weight, plus the fake-quantised bias."""
     with torch.no_grad():

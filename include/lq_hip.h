@@ -454,6 +454,23 @@ int lq_mx_operand_decode(const void* codes, const void* scales, int format, int6
 int lq_mx_gemm(const void* a_codes, const void* a_scales, int a_format, const void* b_codes, const void* b_scales, int b_format,
                const float* bias /* may be NULL */, float* Y, int64_t M, int64_t N, int64_t K, int64_t ldy, void* stream);
 
+/* lq_mx_gemm_quantize: lq_mx_gemm with an operand-out epilogue.  Instead of an fp32 Y it writes the operand of act(Y) for the NEXT
+ * product: L = M lines over K' = N, elements of out_format (LQ_ELEM_FP8_E4M3, LQ_ELEM_FP8_E5M2 or LQ_ELEM_FP4_E2M1) under block
+ * scales taken from act(Y) by `method` (lq_mx_init_method).  out_codes / out_scales have lq_mx_operand_bytes(out_format, M, N)
+ * bytes, and byte for byte they are what
+ *     lq_mx_operand_quantize(act(lq_mx_gemm(a, b, bias)), out_format, method, M, N)
+ * writes, padding included: the K loop is lq_mx_gemm's (same fragments, same instructions, ascending K), the bias is the same one
+ * fp32 addition, and the scale rule and the element step are lq_mx_operand_quantize's.  LQ_ACT_NONE leaves v as it is; LQ_ACT_RELU
+ * is v > 0 ? v : (v != v ? v : +0): a NaN stays NaN, negative values and -0 become +0.
+ * It writes exactly those bytes in ONE launch (no memset, no fp32 intermediate), is capturable, allocates nothing and reads no
+ * environment.  LQ_EINVAL before any launch: a NULL pointer (bias may be NULL), a non-positive extent, M * K, N * K or M * N >= 2^31,
+ * an unknown or fp6 format on any of the three sides, a bad method, a bad activation, M above 65535 * 64.  LQ_EALIGN: codes off the
+ * 16-byte grid; scales or bias off the 4-byte grid.  */
+typedef enum lq_mx_activation { LQ_ACT_NONE = 0, LQ_ACT_RELU = 1 } lq_mx_activation;
+int lq_mx_gemm_quantize(const void* a_codes, const void* a_scales, int a_format, const void* b_codes, const void* b_scales, int b_format,
+                        const float* bias /* may be NULL */, int activation, int out_format, int method, void* out_codes,
+                        void* out_scales, int64_t M, int64_t N, int64_t K, void* stream);
+
 /* ---- K4: forward and NQ backward of one tensor in a single pass (benchmark path) ---
  * Same results as lq_fq_forward followed by lq_fq_scale_grad (out, max|q| and the vote count bit for bit; on
  * streaming-size tensors the vote sum may differ by fp32 summation order, ~1e-7 relative); P is read once.  */

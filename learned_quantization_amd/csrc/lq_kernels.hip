@@ -1848,6 +1848,19 @@ static void launch_mx_gemm_b(const MxGemmParams& p, int b_format, dim3 grid, hip
     else if (b_format == LQ_ELEM_FP8_E4M3) hipLaunchKernelGGL((k_mx_gemm<FA, LQ_ELEM_FP8_E4M3>), grid, dim3(kBlock), 0, st, p);
     else hipLaunchKernelGGL((k_mx_gemm<FA, LQ_ELEM_FP8_E5M2>), grid, dim3(kBlock), 0, st, p);
 }
+
+// 3 x 3 x 2 instantiations: the input formats are immediates of the instruction, of the output format only the width is compile-time
+template <int FA, int FB>
+static void launch_mx_gemm_quantize_o(const MxGemmQuantParams& p, bool out_fp4, dim3 grid, hipStream_t st) {
+    if (out_fp4) hipLaunchKernelGGL((k_mx_gemm_quantize<FA, FB, true>), grid, dim3(kBlock), 0, st, p);
+    else hipLaunchKernelGGL((k_mx_gemm_quantize<FA, FB, false>), grid, dim3(kBlock), 0, st, p);
+}
+template <int FA>
+static void launch_mx_gemm_quantize_b(const MxGemmQuantParams& p, int b_format, bool out_fp4, dim3 grid, hipStream_t st) {
+    if (b_format == LQ_ELEM_FP4_E2M1) launch_mx_gemm_quantize_o<FA, LQ_ELEM_FP4_E2M1>(p, out_fp4, grid, st);
+    else if (b_format == LQ_ELEM_FP8_E4M3) launch_mx_gemm_quantize_o<FA, LQ_ELEM_FP8_E4M3>(p, out_fp4, grid, st);
+    else launch_mx_gemm_quantize_o<FA, LQ_ELEM_FP8_E5M2>(p, out_fp4, grid, st);
+}
 }  // extern "C++"
 
 static void mx_operand_fill(MxOperandParams& op, const MxOperandDims& d, int format, int64_t L, int64_t K, void* codes, void* scales) {
@@ -1969,6 +1982,53 @@ int lq_mx_gemm(const void* a_codes, const void* a_scales, int a_format, const vo
     else if (a_format == LQ_ELEM_FP8_E4M3) launch_mx_gemm_b<LQ_ELEM_FP8_E4M3>(p, b_format, grid, st);
     else launch_mx_gemm_b<LQ_ELEM_FP8_E5M2>(p, b_format, grid, st);
     return check_hip("microscaling GEMM");
+}
+
+int lq_mx_gemm_quantize(const void* a_codes, const void* a_scales, int a_format, const void* b_codes, const void* b_scales, int b_format,
+                        const float* bias, int activation, int out_format, int method, void* out_codes, void* out_scales, int64_t M,
+                        int64_t N, int64_t K, void* stream) {
+    const char* fn = __func__;
+    MxOperandDims da, db, dout;
+    int rc = mx_operand_dims(fn, a_format, M, K, da);
+    if (rc || (rc = mx_operand_dims(fn, b_format, N, K, db)) || (rc = mx_operand_dims(fn, out_format, M, N, dout))) return rc;
+    if (method != LQ_MX_INIT_OCP && method != LQ_MX_INIT_COVER) return fail(LQ_EINVAL, "%s: bad method %d", fn, method);
+    if (activation != LQ_ACT_NONE && activation != LQ_ACT_RELU) return fail(LQ_EINVAL, "%s: bad activation %d", fn, activation);
+    if ((rc = check_mx_operand_buffers(fn, a_codes, a_scales))) return rc;
+    if ((rc = check_mx_operand_buffers(fn, b_codes, b_scales))) return rc;
+    if ((rc = check_mx_operand_buffers(fn, out_codes, out_scales))) return rc;
+    if (bias && !aligned(bias, 4)) return fail(LQ_EALIGN, "%s: bias is not 4-byte aligned", fn);
+    MxGemmQuantParams p{};
+    p.g.a_codes = (const uint8_t*)a_codes;
+    p.g.a_scales = (const uint8_t*)a_scales;
+    p.g.b_codes = (const uint8_t*)b_codes;
+    p.g.b_scales = (const uint8_t*)b_scales;
+    p.g.bias = bias;
+    p.g.M = (int32_t)M;
+    p.g.N = (int32_t)N;
+    p.g.MT = (int32_t)da.LT;
+    p.g.NT = (int32_t)db.LT;
+    p.g.KT = (int32_t)da.KT;
+    p.g.KG = (int32_t)da.KG;
+    mx_fill(p.mp, out_format, LQ_SCALE_E8M0);
+    p.ip.emax = kMxFormats[out_format].emax;
+    p.ip.mm_frac = kMxFormats[out_format].mm_frac;
+    p.ip.min_value = 1.17549435082228750797e-38f;      // 2^-126, as lq_mx_operand_quantize
+    p.codes = (uint8_t*)out_codes;
+    p.scales = (uint8_t*)out_scales;
+    p.act = activation;
+    p.cover = method == LQ_MX_INIT_COVER ? 1 : 0;
+    p.OKT = (int32_t)dout.KT;
+    p.OKG = (int32_t)dout.KG;
+    // a block is 64 x 64 of Y; along n the grid spans the padded operand, 128 OKT columns, so that its padding is written too
+    const int64_t gx = 2 * dout.KT, gy = (da.LT + 3) / 4;
+    if (gy > 65535) return fail(LQ_EINVAL, "%s: M = %lld is above 65535 * 64", fn, (long long)M);
+    const dim3 grid((unsigned)gx, (unsigned)gy);
+    hipStream_t st = (hipStream_t)stream;
+    const bool out_fp4 = out_format == LQ_ELEM_FP4_E2M1;
+    if (a_format == LQ_ELEM_FP4_E2M1) launch_mx_gemm_quantize_b<LQ_ELEM_FP4_E2M1>(p, b_format, out_fp4, grid, st);
+    else if (a_format == LQ_ELEM_FP8_E4M3) launch_mx_gemm_quantize_b<LQ_ELEM_FP8_E4M3>(p, b_format, out_fp4, grid, st);
+    else launch_mx_gemm_quantize_b<LQ_ELEM_FP8_E5M2>(p, b_format, out_fp4, grid, st);
+    return check_hip("microscaling GEMM with operand-out epilogue");
 }
 
 int lq_fq_fwd_bwd_fused(const float* P, const float* s, const float* dy, float lambda, float* out, float* ds, void* ws,

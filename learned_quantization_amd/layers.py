@@ -661,24 +661,48 @@ class CustomDenseLayer(_HostLayer):
         return ops.mx_operand_pack(self.W.detach(), self.nested_q_w_layer.scale.data, self.element_format, self.group_size,
                                    self.scale_format)
 
-    def _mx_product(self, inputs, operand, qb, act_format, act_scale):
-        with torch.no_grad():
-            x = inputs.reshape(-1, inputs.shape[-1])
-            a = ops.mx_operand_quantize(x, act_format, act_scale)
-            if isinstance(operand, torch.Tensor):                 # mx_hardware(emulate=True): the fake-quantised kernel itself
-                y = torch.add(torch.matmul(ops.mx_operand_decode(a), operand), qb)
-            else:
-                y = ops.mx_gemm(a, operand, qb)
-            return y.reshape(*inputs.shape[:-1], y.shape[-1])
+    def _check_mx_input(self, operand):
+        if operand.K != self.W.shape[0]:
+            raise ValueError(f"{self.name}: the input operand reduces over K = {operand.K}, the layer over in = {self.W.shape[0]}")
 
-    def call_mx(self, inputs, act_format="fp8_e4m3", act_scale="mx"):
+    def _mx_product(self, inputs, operand, qb, act_format, act_scale, out_format=None, activation=None):
+        with torch.no_grad():
+            if isinstance(inputs, ops.MxOperand):                 # a previous layer's operand-out epilogue wrote it: used as it is
+                self._check_mx_input(inputs)
+                a, lead = inputs, (inputs.lines,)
+            else:
+                a, lead = ops.mx_operand_quantize(inputs.reshape(-1, inputs.shape[-1]), act_format, act_scale), tuple(inputs.shape[:-1])
+            if out_format is None:
+                if activation is not None:
+                    raise ValueError(f"{self.name}: activation={activation!r} is fused into the operand-out epilogue: give out_format")
+                if isinstance(operand, torch.Tensor):             # mx_hardware(emulate=True): the fake-quantised kernel itself
+                    y = torch.add(torch.matmul(ops.mx_operand_decode(a), operand), qb)
+                else:
+                    y = ops.mx_gemm(a, operand, qb)
+                return y.reshape(*lead, y.shape[-1])
+            if isinstance(operand, torch.Tensor):
+                raise ValueError(f"{self.name}: the emulated path has no operand-out epilogue (out_format={out_format!r})")
+            return ops.mx_gemm_quantize(a, operand, qb, activation, out_format, act_scale)
+
+    def call_mx(self, inputs, act_format="fp8_e4m3", act_scale="mx", out_format=None, activation=None):
         """The layer on the block-scaled matrix instruction, under ``no_grad``: the inputs quantised per block of 32 along their last
         axis (``act_format`` elements under the ``act_scale`` rule, ops.mx_operand_quantize), multiplied with ``mx_operand()`` by
-        ops.mx_gemm, plus the fake-quantised bias.  Inference only: there is no backward through this path."""
+        ops.mx_gemm, plus the fake-quantised bias.  Inference only: there is no backward through this path.
+        ``inputs`` may be an ops.MxOperand (``lines`` rows over ``K`` = in), which is multiplied as it is.  With ``out_format`` the
+        result is not the fp32 matrix but the NEXT layer's operand, ``activation`` (None or "relu") applied and quantised under
+        ``act_scale`` by the product's own epilogue (ops.mx_gemm_quantize): one launch, no fp32 activation in memory."""
         if not self.built:
+            if isinstance(inputs, ops.MxOperand):
+                raise ValueError(f"{self.name}: the layer is not built yet (no kernel to pack)")
             self.build(tuple(inputs.shape), device=inputs.device)
+        if isinstance(inputs, ops.MxOperand):
+            self._check_mx_input(inputs)
+        if out_format is not None:
+            ops.check_mx_operand_format(out_format)
+        ops.check_mx_activation(activation)
         with torch.no_grad():
-            return self._mx_product(inputs, self.mx_operand(), self.nested_q_b_layer(self.b), act_format, act_scale)
+            return self._mx_product(inputs, self.mx_operand(), self.nested_q_b_layer(self.b), act_format, act_scale, out_format,
+                                    activation)
 
 
 _KERNEL_STORAGE = ["oihw"]
@@ -865,13 +889,21 @@ class mx_hardware:
     instruction.  The operands and the fake-quantised biases are built ONCE, on entry, from the scales the layers have then;
     training-mode calls and every other layer keep the fake-quantised path.  ``layers`` lists the layers that switched.
     ``emulate=True`` is the yardstick of that path in stock arithmetic: the same quantised activations, decoded, times the
-    fake-quantised kernel with ``torch.matmul`` -- what the block-scaled product is compared against."""
+    fake-quantised kernel with ``torch.matmul`` -- what the block-scaled product is compared against.
+    ``fused=True``: a module of ``model`` that states its Dense tail as ``mx_chain()`` -- [(layer, activation), ...] with nothing but
+    relu between the layers, as models.MNISTDense does -- evaluates it in eval mode through ``mx_dense_chain``: every layer but the
+    last writes the next layer's operand from its own epilogue, and no fp32 hidden activation exists.  Same bits as ``fused=False``.
+    ``fused_layers`` lists the layers that fused; a model without such a tail (BatchNorm between its Dense layers) keeps the
+    per-layer path and lists none.  ``emulate=True`` with ``fused=True`` is refused: the yardstick is the unfused path."""
 
-    def __init__(self, model: nn.Module, act_format="fp8_e4m3", act_scale="mx", emulate=False):
+    def __init__(self, model: nn.Module, act_format="fp8_e4m3", act_scale="mx", emulate=False, fused=False):
         ops.check_mx_operand_format(act_format)
         ops.check_mx_scale_init(act_scale)
-        self.model, self.act_format, self.act_scale, self.emulate = model, act_format, act_scale, bool(emulate)
-        self.layers = []
+        if emulate and fused:
+            raise ValueError("mx_hardware: emulate=True with fused=True: the emulated path is the yardstick of the unfused path and "
+                             "has no operand-out epilogue")
+        self.model, self.act_format, self.act_scale, self.emulate, self.fused = model, act_format, act_scale, bool(emulate), bool(fused)
+        self.layers, self.fused_layers, self._fused_modules = [], [], []
 
     def __enter__(self):
         self.layers = [m for m in custom_layers_of(self.model) if mx_hardware_eligible(m)]
@@ -879,12 +911,62 @@ class mx_hardware:
             for m in self.layers:
                 weight = m.nested_q_w_layer(m.W).detach() if self.emulate else m.mx_operand()
                 m._mx_hw = (weight, m.nested_q_b_layer(m.b).detach(), self.act_format, self.act_scale)
+        self.fused_layers, self._fused_modules = [], []
+        if self.fused:
+            for mod in self.model.modules():
+                chain = mod.mx_chain() if callable(getattr(mod, "mx_chain", None)) else []
+                if len(chain) > 1 and all(mx_hardware_eligible(layer) and act in ops.MX_ACTIVATIONS for layer, act in chain):
+                    mod._mx_fused = (self.act_format, self.act_scale)
+                    self._fused_modules.append(mod)
+                    self.fused_layers += [layer for layer, _ in chain]
         return self
 
     def __exit__(self, *exc):
         for m in self.layers:
             m._mx_hw = None
+        for mod in self._fused_modules:
+            mod._mx_fused = None
         return False
+
+
+def mx_dense_chain(x, chain, act_format="fp8_e4m3", act_scale="mx"):
+    """``chain`` = [(layer, activation), ...]: Dense layers applied one after the other on the block-scaled matrix instruction, under
+    ``no_grad``.  ``x`` is quantised once (ops.mx_operand_quantize); every layer but the last goes through ops.mx_gemm_quantize, which
+    applies its activation (None or "relu") and writes the next layer's operand (``act_format`` under ``act_scale``) in the product's
+    epilogue; the last goes through ops.mx_gemm to fp32 and takes no activation.  Bit for bit ``call_mx`` -> activation -> ``call_mx``
+    ..., without the fp32 activations and their launches.  Inside ``mx_hardware`` the operands and biases built on its entry are
+    used, otherwise they are built here.  ValueError naming the reason for a layer that cannot take the path
+    (``mx_hardware_eligible``) or an activation other than None / "relu"."""
+    chain = list(chain)
+    if not chain:
+        raise ValueError("mx_dense_chain: the chain is empty")
+    for k, (layer, activation) in enumerate(chain):
+        if not isinstance(layer, CustomDenseLayer):
+            raise ValueError(f"mx_dense_chain: layer {k} is a {type(layer).__name__}: only Dense layers run on the block-scaled GEMM")
+        if not layer.built:
+            raise ValueError(f"mx_dense_chain: {layer.name}: the layer is not built yet (no kernel to pack)")
+        try:
+            ops.check_mx_operand_layer(layer.element_format, layer.scale_format, layer.group_size)
+            ops.check_mx_activation(activation)
+        except ValueError as e:
+            raise ValueError(f"mx_dense_chain: {layer.name}: {e}") from None
+        if k == len(chain) - 1 and activation is not None:
+            raise ValueError(f"mx_dense_chain: {layer.name}: the last layer writes fp32 and takes no activation (got {activation!r}): "
+                             "apply it to the result")
+    ops.check_mx_operand_format(act_format)
+    ops.check_mx_scale_init(act_scale)
+    with torch.no_grad():
+        lead = tuple(x.shape[:-1])
+        a = ops.mx_operand_quantize(x.reshape(-1, x.shape[-1]), act_format, act_scale)
+        for k, (layer, activation) in enumerate(chain):
+            hw = getattr(layer, "_mx_hw", None)
+            if hw is not None and not isinstance(hw[0], torch.Tensor):
+                operand, qb = hw[0], hw[1]
+            else:
+                operand, qb = layer.mx_operand(), layer.nested_q_b_layer(layer.b)
+            last = k == len(chain) - 1
+            a = layer._mx_product(a, operand, qb, act_format, act_scale, None if last else act_format, activation)
+        return a.reshape(*lead, a.shape[-1])
 
 
 def quantized_tensors(model: nn.Module):

@@ -33,7 +33,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .layers import CustomConv2DLayer, CustomDenseLayer, RandomNormal, l2
+from .layers import CustomConv2DLayer, CustomDenseLayer, RandomNormal, l2, mx_dense_chain
 from .losses import softmax
 
 
@@ -81,10 +81,20 @@ class MNISTDense(nn.Module):
                                         name="custom_dense_layer_2", regularizer=None, trained_weights=tw[1],
                                         input_shape=128, device=device, **_kw(mode, value))
 
-    def forward(self, x):
+    def mx_chain(self):
+        """The Dense tail as layers.mx_dense_chain takes it: nothing but relu lies between the two layers."""
+        return [(self.dense_1, "relu"), (self.dense_2, None)]
+
+    def logits(self, x):
         x = torch.flatten(x, 1)
+        fused = getattr(self, "_mx_fused", None)
+        if fused is not None and not self.training:               # inside layers.mx_hardware(..., fused=True), eval mode
+            return mx_dense_chain(x, self.mx_chain(), *fused)
         x = F.relu(self.dense_1(x))
-        return softmax(self.dense_2(x), dim=1)
+        return self.dense_2(x)
+
+    def forward(self, x):
+        return softmax(self.logits(x), dim=1)
 
 
 class CIFARCNN(nn.Module):

@@ -610,7 +610,41 @@ def mx_gemm(a: MxOperand, b: MxOperand, bias: Optional[torch.Tensor] = None, out
     return out
 
 
-STATS_MAX_BINS = 4096     # include/lq_hip.h, lq_group_stats: the widest range whose codes it bins
+MX_ACTIVATIONS = (None, "relu")        # include/lq_hip.h: LQ_ACT_NONE, LQ_ACT_RELU
+
+
+def check_mx_activation(activation) -> int:
+    """The C ABI's value of an ``activation`` fused into the operand-out epilogue, or ValueError: one of MX_ACTIVATIONS."""
+    if activation is not None and not isinstance(activation, str) or activation not in MX_ACTIVATIONS:
+        raise ValueError(f"activation must be one of {MX_ACTIVATIONS}, got {activation!r}: the operand-out epilogue fuses relu only")
+    return MX_ACTIVATIONS.index(activation)
+
+
+def mx_gemm_quantize(a: MxOperand, b: MxOperand, bias: Optional[torch.Tensor] = None, activation=None, out_format: str = "fp8_e4m3",
+                     method: str = "mx") -> MxOperand:
+    """The operand of ``activation(A B^T (+ bias))`` for the next product, ``a.lines`` lines over ``K = b.lines``, written by the
+    GEMM's own epilogue (include/lq_hip.h, lq_mx_gemm_quantize): byte for byte
+    ``mx_operand_quantize(act(mx_gemm(a, b, bias)), out_format, method)``, in one launch and without the fp32 matrix."""
+    fa, fb, fo = check_mx_operand_format(a.format), check_mx_operand_format(b.format), check_mx_operand_format(out_format)
+    m = check_mx_scale_init(method)
+    act = check_mx_activation(activation)
+    if a.K != b.K:
+        raise ValueError(f"the operands reduce over different K: {a.K} and {b.K}")
+    lib = _hip.load()
+    M, N = a.lines, b.lines
+    dev = a.codes.device
+    if bias is not None:
+        bias = _hip.require_device_f32(bias, "bias")
+        if tuple(bias.shape) != (N,):
+            raise ValueError(f"bias must have shape ({N},), got {tuple(bias.shape)}")
+    codes, scales = _mx_operand_buffers(out_format, M, N, dev)
+    _hip.check(lib.lq_mx_gemm_quantize(_hip.ptr(a.codes), _hip.ptr(a.scales), fa.id, _hip.ptr(b.codes), _hip.ptr(b.scales), fb.id,
+                                       _hip.ptr(bias), act, fo.id, m, _hip.ptr(codes), _hip.ptr(scales), M, N, a.K,
+                                       _hip.stream_ptr(dev)), "lq_mx_gemm_quantize")
+    return MxOperand(codes, scales, out_format, M, N)
+
+
+STATS_MAX_BINS = 4096    # include/lq_hip.h, lq_group_stats: the widest range whose codes it bins
 
 
 class GroupStats(NamedTuple):

@@ -606,14 +606,20 @@ def build_parser():
                          "block-scaled matrix instruction, activations quantised per block to ACT_FORMAT, default fp8_e4m3) and add "
                          "mx_eval_accuracy, mx_eval_accuracy_fake (the same quantised activations times the fake-quantised weights "
                          "with torch.matmul) and mx_eval_max_logit_diff to the result line")
+    ap.add_argument("--mx-eval-fused", action="store_true",
+                    help="with --mx-eval: evaluate once more under layers.mx_hardware(fused=True) (the Dense tail through "
+                         "layers.mx_dense_chain: relu and the next operand's quantisation in the GEMM's epilogue) and add "
+                         "mx_eval_fused_layers, mx_eval_fused_accuracy and mx_eval_fused_max_logit_diff (against the unfused "
+                         "hardware path; 0.0 is expected) to the result line")
     return ap
 
 
 @torch.no_grad()
-def mx_eval(model, x, y, act_format="fp8_e4m3", act_scale="mx"):
+def mx_eval(model, x, y, act_format="fp8_e4m3", act_scale="mx", fused=False):
     """One evaluation of ``model`` on (x, y) under layers.mx_hardware and one under its ``emulate=True`` yardstick: a dict of both
     accuracies and the largest |difference| of the outputs of the last Dense layer that took the path (the logits of the MNIST
-    model)."""
+    model).  ``fused=True`` adds a third evaluation under ``mx_hardware(fused=True)``: its accuracy and the largest |difference| of
+    the model's ``logits`` from the unfused hardware path's (the same bits are expected: 0.0)."""
     was_training = model.training
     model.eval()
     acc, logits = [], []
@@ -631,10 +637,19 @@ def mx_eval(model, x, y, act_format="fp8_e4m3", act_scale="mx"):
                     hook.remove()
                 acc.append(float((p.argmax(1) == y).float().mean()))
                 logits.append(seen[-1])
+        fields = {}
+        if fused:
+            with L.mx_hardware(model, act_format, act_scale, fused=True) as hwf:
+                if not hwf.fused_layers or not callable(getattr(model, "logits", None)):
+                    raise ValueError("mx_eval: fused=True needs a model whose Dense tail fuses (mx_chain() and logits(), as "
+                                     "models.MNISTDense has): nothing but relu between eligible Dense layers")
+                fused_logits, p = model.logits(x), model(x)
+                fields = {"mx_eval_fused_layers": len(hwf.fused_layers), "mx_eval_fused_accuracy": float((p.argmax(1) == y).float().mean()),
+                          "mx_eval_fused_max_logit_diff": float((fused_logits - logits[0]).abs().max())}
     finally:
         model.train(was_training)
     return {"mx_eval_act_format": act_format, "mx_eval_layers": len(hw.layers), "mx_eval_accuracy": acc[0],
-            "mx_eval_accuracy_fake": acc[1], "mx_eval_max_logit_diff": float((logits[0] - logits[1]).abs().max())}
+            "mx_eval_accuracy_fake": acc[1], "mx_eval_max_logit_diff": float((logits[0] - logits[1]).abs().max()), **fields}
 
 
 def main(argv=None):
@@ -642,6 +657,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.mx_eval is not None and args.element_format is None:
         ap.error("--mx-eval needs --element-format: it runs the layers of a microscaling model on the block-scaled matrix instruction")
+    if args.mx_eval_fused and args.mx_eval is None:
+        ap.error("--mx-eval-fused needs --mx-eval: it compares the fused Dense tail with the unfused hardware path")
     if args.quant_stats and args.bits is None:
         ap.error("--quant-stats needs --bits: the statistics are those of a quantizer with a range")
     if args.mx_stats and args.element_format is None:
@@ -709,7 +726,7 @@ def main(argv=None):
     log_rows = tr.flush_loss_log() if args.loss_values and rank == 0 else None     # every rank holds the same rows: one writes
     quant_stats = L.quant_stats(tr.model) if args.quant_stats and rank == 0 else None      # after the clock has stopped
     mx_stats = L.mx_quant_stats(tr.model) if args.mx_stats and rank == 0 else None
-    mx_eval_fields = mx_eval(tr.model, *batches[0], act_format=args.mx_eval) if args.mx_eval is not None and rank == 0 else None
+    mx_eval_fields = mx_eval(tr.model, *batches[0], act_format=args.mx_eval, fused=args.mx_eval_fused) if args.mx_eval is not None and rank == 0 else None
     if rank == 0:
         n_q = sum(p.numel() for l in tr.custom_layers for p in l._regularized())
         print(json.dumps({

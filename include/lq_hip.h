@@ -471,6 +471,33 @@ int lq_mx_gemm_quantize(const void* a_codes, const void* a_scales, int a_format,
                         const float* bias /* may be NULL */, int activation, int out_format, int method, void* out_codes,
                         void* out_scales, int64_t M, int64_t N, int64_t K, void* stream);
 
+/* lq_mx_operand_im2col: the A operand of a convolution run as a GEMM, gathered from the input in one launch -- the im2col matrix
+ * never exists in fp32.  With OH = (H + pad_top + pad_bottom - KH) / stride_h + 1 (rounded down; OW likewise from W, the left and
+ * right pads, KW and stride_w), M = B * OH * OW lines and K = C * KH * KW:
+ *     line m = (b * OH + oh) * OW + ow,  reduction index k = (c * KH + i) * KW + j
+ *     A[m][k] = X[b][c][oh * stride_h - pad_top + i][ow * stride_w - pad_left + j]   where that pixel exists, +0 otherwise
+ * k is the memory order of the (ci, kh, kw) run of an OIHW kernel, so the B side is lq_mx_operand_pack(kernel, R = co,
+ * C = ci * kh * kw, axis 1) and lq_mx_gemm(A, B) is the convolution as [M][co], i.e. NHWC.  codes / scales have
+ * lq_mx_operand_bytes(format, M, K) bytes and, byte for byte, padding and idle scale bytes included, hold what
+ * lq_mx_operand_quantize(A, format, method, M, K) writes: a padding zero takes part in its block as a zero, an all-zero block gets
+ * byte 1, and a block whose window covers a NaN or Inf pixel gets byte 255 -- no other block does.  X is addressed through its
+ * strides, given in ELEMENTS (NCHW-contiguous, channels_last or any view with non-negative strides), in 64-bit arithmetic, with
+ * 4-byte loads; no byte of X is read that the definition does not name.
+ * lq_mx_im2col_dims answers M, K, OH and OW of a geometry (the strides of X are not read) and runs nothing on a device; it accepts
+ * an M * K that the operand call refuses, so that a caller can cut the batch.
+ * LQ_EINVAL before any launch: a NULL pointer, a non-positive extent, kernel size or stride, a negative pad, OH or OW < 1, an
+ * unknown or fp6 format, an unknown method, M * K >= 2^31, a negative stride of X.  LQ_EALIGN: codes off the 16-byte grid; scales or
+ * X off the 4-byte grid.  The operand call only enqueues ONE launch (capturable), allocates nothing, reads no environment and writes
+ * exactly code_bytes and scale_bytes.  Dilation and groups are not built.  */
+typedef struct lq_conv_geom {
+    int64_t B, C, H, W;               /* the input, logically [B][C][H][W] */
+    int64_t xs_b, xs_c, xs_h, xs_w;   /* its strides in ELEMENTS */
+    int32_t KH, KW, stride_h, stride_w;
+    int32_t pad_top, pad_left, pad_bottom, pad_right;   /* zero padding, each >= 0 */
+} lq_conv_geom;
+int lq_mx_im2col_dims(const lq_conv_geom* g, int64_t* M, int64_t* K, int64_t* OH, int64_t* OW);
+int lq_mx_operand_im2col(const float* X, const lq_conv_geom* g, int format, int method, void* codes, void* scales, void* stream);
+
 /* ---- K4: forward and NQ backward of one tensor in a single pass (benchmark path) ---
  * Same results as lq_fq_forward followed by lq_fq_scale_grad (out, max|q| and the vote count bit for bit; on
  * streaming-size tensors the vote sum may differ by fp32 summation order, ~1e-7 relative); P is read once.  */

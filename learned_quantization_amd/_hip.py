@@ -141,6 +141,21 @@ SIGNATURES.update({
 
 
 
+class ConvGeom(ctypes.Structure):
+    """lq_conv_geom of include/lq_hip.h."""
+    _fields_ = [("B", _c_i64), ("C", _c_i64), ("H", _c_i64), ("W", _c_i64),
+                ("xs_b", _c_i64), ("xs_c", _c_i64), ("xs_h", _c_i64), ("xs_w", _c_i64),
+                ("KH", _c_i32), ("KW", _c_i32), ("stride_h", _c_i32), ("stride_w", _c_i32),
+                ("pad_top", _c_i32), ("pad_left", _c_i32), ("pad_bottom", _c_i32), ("pad_right", _c_i32)]
+
+
+SIGNATURES.update({
+    "lq_mx_im2col_dims": (_c_int, [ctypes.POINTER(ConvGeom), ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64),
+                                   ctypes.POINTER(_c_i64)]),
+    "lq_mx_operand_im2col": (_c_int, [_c_p, ctypes.POINTER(ConvGeom), _c_int, _c_int, _c_p, _c_p, _c_p]),
+})
+
+
 class GroupDesc(ctypes.Structure):
     """lq_group_desc of include/lq_hip.h."""
     _fields_ = [("P", _c_p), ("s", _c_p), ("out", _c_p), ("dp", _c_p), ("ds", _c_p),

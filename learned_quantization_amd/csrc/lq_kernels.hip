@@ -16,6 +16,7 @@
 //   lq_mx.hpp           OCP microscaling element formats: the group-wise traversal bodies with a minifloat element step
 //   lq_mx_operand.hpp   packed MX operands in the block-scaled matrix instruction's fragment order: pack, dynamic quantize, decode
 //   lq_mx_gemm.hpp      the GEMM of two packed operands on v_mfma_scale_f32_16x16x128_f8f6f4
+//   lq_mx_conv.hpp      the operand of a convolution's im2col matrix, gathered from the input in one launch
 //   this file           host side: traversal plan, launchers, the extern "C" entry points
 //
 // The path is elementwise + per-group reductions: HBM-bound, no MFMA.  Design rules
@@ -63,6 +64,7 @@
 #include "lq_mx_stats.hpp"
 #include "lq_mx_operand.hpp"
 #include "lq_mx_gemm.hpp"
+#include "lq_mx_conv.hpp"
 
 namespace lq {
 
@@ -2029,6 +2031,110 @@ int lq_mx_gemm_quantize(const void* a_codes, const void* a_scales, int a_format,
     else if (a_format == LQ_ELEM_FP8_E4M3) launch_mx_gemm_quantize_b<LQ_ELEM_FP8_E4M3>(p, b_format, out_fp4, grid, st);
     else launch_mx_gemm_quantize_b<LQ_ELEM_FP8_E5M2>(p, b_format, out_fp4, grid, st);
     return check_hip("microscaling GEMM with operand-out epilogue");
+}
+
+// ---- the operand of a convolution's im2col matrix (lq_mx_conv.hpp) ----
+struct ConvDims {
+    int64_t M, K, OH, OW;
+};
+
+// the geometry alone: what lq_mx_im2col_dims answers.  M and K are formed in double first, so that no int64 product overflows
+static int conv_geom_dims(const char* fn, const lq_conv_geom* g, ConvDims& d) {
+    if (!g) return fail(LQ_EINVAL, "%s: argument 'g' is NULL", fn);
+    if (g->B <= 0 || g->C <= 0 || g->H <= 0 || g->W <= 0)
+        return fail(LQ_EINVAL, "%s: extents must be positive (B=%lld C=%lld H=%lld W=%lld)", fn, (long long)g->B, (long long)g->C,
+                    (long long)g->H, (long long)g->W);
+    if (g->KH <= 0 || g->KW <= 0) return fail(LQ_EINVAL, "%s: kernel size must be positive (KH=%d KW=%d)", fn, g->KH, g->KW);
+    if (g->stride_h <= 0 || g->stride_w <= 0)
+        return fail(LQ_EINVAL, "%s: strides must be positive (stride_h=%d stride_w=%d)", fn, g->stride_h, g->stride_w);
+    if (g->pad_top < 0 || g->pad_left < 0 || g->pad_bottom < 0 || g->pad_right < 0)
+        return fail(LQ_EINVAL, "%s: padding must not be negative (top=%d left=%d bottom=%d right=%d)", fn, g->pad_top, g->pad_left,
+                    g->pad_bottom, g->pad_right);
+    if (g->H > (INT64_MAX >> 1) || g->W > (INT64_MAX >> 1))
+        return fail(LQ_EINVAL, "%s: H=%lld or W=%lld does not leave room for the padding", fn, (long long)g->H, (long long)g->W);
+    const int64_t span_h = g->H + g->pad_top + g->pad_bottom - g->KH, span_w = g->W + g->pad_left + g->pad_right - g->KW;
+    d.OH = span_h < 0 ? 0 : span_h / g->stride_h + 1;
+    d.OW = span_w < 0 ? 0 : span_w / g->stride_w + 1;
+    if (d.OH < 1 || d.OW < 1)
+        return fail(LQ_EINVAL, "%s: the kernel does not fit the padded input (OH=%lld OW=%lld)", fn, (long long)d.OH, (long long)d.OW);
+    const double m = (double)g->B * (double)d.OH * (double)d.OW, k = (double)g->C * (double)g->KH * (double)g->KW;
+    if (m >= 4611686018427387904.0 || k >= 4611686018427387904.0)
+        return fail(LQ_EINVAL, "%s: M = B * OH * OW or K = C * KH * KW is not below 2^62", fn);
+    d.M = g->B * d.OH * d.OW;
+    d.K = g->C * g->KH * g->KW;
+    return LQ_OK;
+}
+
+int lq_mx_im2col_dims(const lq_conv_geom* g, int64_t* M, int64_t* K, int64_t* OH, int64_t* OW) {
+    const char* fn = __func__;
+    if (!M || !K || !OH || !OW) return fail(LQ_EINVAL, "%s: argument '%s' is NULL", fn, !M ? "M" : !K ? "K" : !OH ? "OH" : "OW");
+    ConvDims d;
+    int rc = conv_geom_dims(fn, g, d);
+    if (rc) return rc;
+    *M = d.M;
+    *K = d.K;
+    *OH = d.OH;
+    *OW = d.OW;
+    return LQ_OK;
+}
+
+int lq_mx_operand_im2col(const float* X, const lq_conv_geom* g, int format, int method, void* codes, void* scales, void* stream) {
+    const char* fn = __func__;
+    LQ_REQUIRE_PTR_FN(fn, X);
+    if (method != LQ_MX_INIT_OCP && method != LQ_MX_INIT_COVER) return fail(LQ_EINVAL, "%s: bad method %d", fn, method);
+    ConvDims cd;
+    int rc = conv_geom_dims(fn, g, cd);
+    if (rc) return rc;
+    if (g->xs_b < 0 || g->xs_c < 0 || g->xs_h < 0 || g->xs_w < 0)
+        return fail(LQ_EINVAL, "%s: strides of X must not be negative (xs_b=%lld xs_c=%lld xs_h=%lld xs_w=%lld)", fn, (long long)g->xs_b,
+                    (long long)g->xs_c, (long long)g->xs_h, (long long)g->xs_w);
+    MxOperandDims d;
+    if ((rc = mx_operand_dims(fn, format, cd.M, cd.K, d))) return rc;      // the format, M * K < 2^31
+    if ((rc = check_mx_operand_buffers(fn, codes, scales))) return rc;
+    MxIm2colParams op{};
+    mx_fill(op.mp, format, LQ_SCALE_E8M0);
+    op.mp.g.P = X;
+    op.ip.emax = kMxFormats[format].emax;
+    op.ip.mm_frac = kMxFormats[format].mm_frac;
+    op.ip.min_value = 1.17549435082228750797e-38f;      // 2^-126, as lq_mx_operand_quantize
+    op.codes = (uint8_t*)codes;
+    op.scales = (uint8_t*)scales;
+    op.xs_b = g->xs_b;
+    op.xs_c = g->xs_c;
+    op.xs_h = g->xs_h;
+    op.xs_w = g->xs_w;
+    op.H = g->H;
+    op.W = g->W;
+    // M * K < 2^31 bounds OH * OW, OW, KH * KW and KW: every divisor and dividend is a 32-bit number
+    op.ohow = make_fastdiv((uint32_t)(cd.OH * cd.OW));
+    op.ow = make_fastdiv((uint32_t)cd.OW);
+    op.khkw = make_fastdiv((uint32_t)((int64_t)g->KH * g->KW));
+    op.kw = make_fastdiv((uint32_t)g->KW);
+    op.KH = g->KH;
+    op.stride_h = g->stride_h;
+    op.stride_w = g->stride_w;
+    op.pad_top = g->pad_top;
+    op.pad_left = g->pad_left;
+    op.L = (int32_t)cd.M;
+    op.K = (int32_t)cd.K;
+    op.nbk = (int32_t)((cd.K + kMxBlockLen - 1) / kMxBlockLen);
+    op.LT = (int32_t)d.LT;
+    op.KT = (int32_t)d.KT;
+    op.KG = (int32_t)d.KG;
+    // a thread block is kBlock consecutive lines of one k block: chunks per k block, k blocks slowest
+    const int64_t chunks = (d.LT * kMxTileLines + kBlock - 1) / kBlock;
+    op.chunks = make_fastdiv((uint32_t)chunks);
+    const dim3 grid((unsigned)(chunks * d.KT * 4)), block(kBlock);      // below 2^31: at most M K / 8192 + M / 64 + K / 32 + 4
+    hipStream_t st = (hipStream_t)stream;
+    const bool fp4 = format == LQ_ELEM_FP4_E2M1;
+    if (method == LQ_MX_INIT_OCP) {
+        if (fp4) hipLaunchKernelGGL((k_mx_im2col<kInitMxOcp, true>), grid, block, 0, st, op);
+        else hipLaunchKernelGGL((k_mx_im2col<kInitMxOcp, false>), grid, block, 0, st, op);
+    } else {
+        if (fp4) hipLaunchKernelGGL((k_mx_im2col<kInitMxCover, true>), grid, block, 0, st, op);
+        else hipLaunchKernelGGL((k_mx_im2col<kInitMxCover, false>), grid, block, 0, st, op);
+    }
+    return check_hip("microscaling im2col operand");
 }
 
 int lq_fq_fwd_bwd_fused(const float* P, const float* s, const float* dy, float lambda, float* out, float* ds, void* ws,

@@ -1,0 +1,98 @@
+// lq_mx_conv.hpp -- the packed MX operand of the im2col matrix of a convolution's input, without the matrix
+// (lq_hip.h: lq_mx_im2col_dims / lq_mx_operand_im2col)
+//
+// A[m][k] with m = (b OH + oh) OW + ow and k = (c KH + i) KW + j is X[b][c][oh stride_h - pad_top + i][ow stride_w - pad_left + j]
+// where that pixel exists and +0 otherwise; the operand of A is what lq_mx_operand_quantize(A, M, K) writes (lq_mx_operand.hpp: the
+// layout, mx_code_offset / mx_scale_offset).  k is the memory order of an OIHW kernel's (ci, kh, kw) run, so the B side is
+// lq_mx_operand_pack(kernel, axis 1).
+//
+// One thread per (line, block of 32 k), as k_mx_operand has it, lines fastest: a thread block is kBlock consecutive lines of ONE k
+// block, so (c, i, j) of each of the 32 taps is uniform over the block (scalar registers) and only (b, oh, ow) is per lane.  For an
+// NCHW input at stride 1 a wave's load of one tap is 64 consecutive addresses (up to the row ends), and the fragment stores of 16
+// neighbouring lines are contiguous.  The gather is 32 predicated 4-byte loads -- zero outside the image and past K, and no address
+// is formed into a load unless the definition names it -- addressed in int64 through the strides of X (NCHW, channels_last or any
+// view with non-negative strides).  The scale rule and the element step are those k_mx_operand runs, called, not restated:
+// init_take / init_raw / init_final, GroupStep<true, GroupMxParams>, mx_code_bits.  The few lines around them (block scale byte,
+// code packing, fragment stores, idle scale bytes) are copied from k_mx_operand instead of shared with it, so that its instruction
+// streams stay what they were (the precedent is mx_gemm_accumulate).  No LDS, no scratch, no atomics.
+#ifndef LQ_MX_CONV_HPP_
+#define LQ_MX_CONV_HPP_
+#include "lq_fastdiv.hpp"
+#include "lq_mx_operand.hpp"
+
+namespace lq {
+
+struct MxIm2colParams {
+    GroupMxParams mp;         // the format; g.P is X
+    InitParams ip;            // emax, mm_frac, min_value
+    uint8_t* codes;
+    uint8_t* scales;
+    int64_t xs_b, xs_c, xs_h, xs_w;       // of X, in elements
+    int64_t H, W;
+    FastDiv ohow, ow;         // m -> (b, oh, ow)
+    FastDiv khkw, kw;         // k -> (c, i, j)
+    FastDiv chunks;           // blockIdx.x -> (k block, chunk of kBlock lines)
+    int32_t KH, stride_h, stride_w, pad_top, pad_left;
+    int32_t L, K, nbk;        // L = M lines; nbk = ceil(K / 32)
+    int32_t LT, KT, KG;
+};
+
+template <int METHOD, bool FP4>
+__global__ __launch_bounds__(kBlock) void k_mx_im2col(const MxIm2colParams op) {
+    using Step = GroupStep<true, GroupMxParams>;
+    const int32_t kb = (int32_t)fd_div(op.chunks, blockIdx.x);                         // uniform over the block
+    const int64_t line = (int64_t)(blockIdx.x - (uint32_t)kb * op.chunks.d) * kBlock + threadIdx.x;
+    if (line >= (int64_t)op.LT * kMxTileLines) return;
+    const int32_t ln = (int32_t)line;
+    const bool live = ln < op.L && kb < op.nbk;
+    uint32_t w[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    uint32_t byte = 127u;
+    if (live) {
+        const int n = min(kMxBlockLen, op.K - kb * kMxBlockLen);
+        const uint32_t b = fd_div(op.ohow, (uint32_t)ln), r = (uint32_t)ln - b * op.ohow.d;
+        const uint32_t oh = fd_div(op.ow, r), ow = r - oh * op.ow.d;
+        const int64_t ih0 = (int64_t)oh * op.stride_h - op.pad_top, iw0 = (int64_t)ow * op.stride_w - op.pad_left;
+        const int64_t base = (int64_t)b * op.xs_b + ih0 * op.xs_h + iw0 * op.xs_w;      // of the window's corner: may lie outside X
+        const uint32_t k0 = (uint32_t)kb * kMxBlockLen;
+        uint32_t c = fd_div(op.khkw, k0);
+        const uint32_t rk = k0 - c * op.khkw.d;
+        uint32_t i = fd_div(op.kw, rk), j = rk - i * op.kw.d;
+        const float* X = op.mp.g.P;
+        float x[kMxBlockLen];
+#pragma unroll
+        for (int e = 0; e < kMxBlockLen; ++e) {
+            const int64_t ih = ih0 + i, iw = iw0 + j;
+            const bool in = e < n && (uint64_t)ih < (uint64_t)op.H && (uint64_t)iw < (uint64_t)op.W;
+            x[e] = 0.f;
+            if (in) x[e] = X[base + (int64_t)c * op.xs_c + (int64_t)i * op.xs_h + (int64_t)j * op.xs_w];
+            if (++j == op.kw.d) {
+                j = 0u;
+                if (++i == (uint32_t)op.KH) { i = 0u; ++c; }
+            }
+        }
+        InitAcc a{0.f, 0.f, 0.0, 0u};      // the zeros of the padding and past n change neither maximum
+#pragma unroll
+        for (int e = 0; e < kMxBlockLen; ++e) init_take<METHOD>(x[e], a);
+        const float s = init_final(op.ip, init_raw<METHOD>(op.ip, a, n), a.bad);
+        const Ctx cx = Step::ctx(op.mp, s);
+        byte = (cx.s != cx.s) ? 255u : (__float_as_uint(cx.s) >> 23);      // s_eff is a power of two in [2^-126, 2^127], or NaN
+#pragma unroll
+        for (int e = 0; e < kMxBlockLen; ++e) {
+            const float q = Step::quant(op.mp, cx, div_by_uniform(x[e], cx));
+            const uint32_t code = e < n ? mx_code_bits(q, op.mp.M, op.mp.emin, op.mp.bits) : 0u;
+            if constexpr (FP4) w[e >> 3] |= code << (4 * (e & 7));
+            else w[e >> 2] |= code << (8 * (e & 3));
+        }
+    }
+    // as k_mx_operand stores them: fp4 one fragment, fp8 the halves of two; then the scale byte and the idle bytes of steps KT .. 4 KG - 1
+    *reinterpret_cast<uint4*>(op.codes + mx_code_offset(op.KT, FP4, ln, kb * kMxBlockLen)) = make_uint4(w[0], w[1], w[2], w[3]);
+    if constexpr (!FP4)
+        *reinterpret_cast<uint4*>(op.codes + mx_code_offset(op.KT, false, ln, kb * kMxBlockLen + 16)) = make_uint4(w[4], w[5], w[6], w[7]);
+    op.scales[mx_scale_offset(op.KG, ln, kb)] = (uint8_t)byte;
+    if ((kb >> 2) == op.KT - 1)
+        for (int32_t kt = op.KT; kt < 4 * op.KG; ++kt) op.scales[mx_scale_offset(op.KG, ln, kt * 4 + (kb & 3))] = 127u;
+}
+
+}  // namespace lq
+
+#endif

@@ -843,6 +843,10 @@ class _ConvBase(_HostLayer):
     def call(self, inputs):
         if not self.built:
             self.build(tuple(inputs.shape), device=inputs.device)
+        hw = getattr(self, "_mx_hw", None)
+        if hw is not None and not self.training:                  # inside layers.mx_hardware(..., convs=True), eval mode
+            self._q_pre = None                                    # a batch's fake-quantised pair is not what this path multiplies
+            return self._mx_conv(inputs, *hw)
         x = inputs.permute(0, 3, 1, 2) if self.data_format == "NHWC" else inputs
         w, qb = self.quantized_parameters()
         if self.padding == "SAME":
@@ -859,6 +863,70 @@ class _ConvBase(_HostLayer):
         return y.permute(0, 2, 3, 1) if self.data_format == "NHWC" else y
 
     forward = call
+
+    def mx_operand(self) -> "ops.MxOperand":
+        """The kernel under its current scales as an operand of the block-scaled matrix instruction (ops.mx_operand_pack, blocks
+        along the contiguous axis): ``filters`` lines over K = ci kh kw, the reduction order of ops.mx_operand_im2col.  ValueError
+        naming the reason for ``kernel_storage="hwio"``, for a layer without an element format, with ``scale_format="fp32"``, with an
+        fp6 format or with a group size other than 32, and for a layer that is not built."""
+        if self.kernel_storage != "oihw":
+            raise ValueError(f'{self.name}: kernel_storage="hwio": the block-scaled GEMM reduces over the (ci, kh, kw) memory run of a '
+                             'kernel stored "oihw"')
+        ops.check_mx_operand_layer(self.element_format, self.scale_format, self.group_size)
+        if not self.built:
+            raise ValueError(f"{self.name}: the layer is not built yet (no kernel to pack)")
+        return ops.mx_operand_pack(self.kernel.detach(), self.nested_q_k_layer.scale.data, self.element_format, self.group_size,
+                                   self.scale_format)
+
+    def _mx_padding(self, h: int, w: int) -> Tuple[int, int, int, int]:
+        """(top, bottom, left, right) of this layer on an h x w input: TensorFlow 'SAME' (asymmetric where it is) or none."""
+        if self.padding != "SAME":
+            return (0, 0, 0, 0)
+        return (*_same_padding(h, self.kernel_size[0], self.strides[0]), *_same_padding(w, self.kernel_size[1], self.strides[1]))
+
+    def _mx_conv(self, inputs, operand, qb, act_format, act_scale, max_lines=None):
+        with torch.no_grad():
+            if inputs.dim() != 4:
+                raise ValueError(f"{self.name}: the input must have four axes, got shape {tuple(inputs.shape)}")
+            x = inputs.permute(0, 3, 1, 2) if self.data_format == "NHWC" else inputs       # a view: the operand reads its strides
+            padding = self._mx_padding(x.shape[2], x.shape[3])
+            M, K, OH, OW = ops.mx_im2col_dims(x.shape, self.kernel_size, self.strides, padding)
+            B, per = x.shape[0], OH * OW
+            # runs of whole images whose operand the C surface takes (M K < 2^31) and that hold at most max_lines lines
+            fit = ((1 << 31) - 1) // K if max_lines is None else min(int(max_lines), ((1 << 31) - 1) // K)
+            images = max(1, min(B, fit // per))
+            y = torch.empty((M, self.filters), dtype=torch.float32, device=x.device)
+            for b0 in range(0, B, images):
+                b1 = min(B, b0 + images)
+                a = ops.mx_operand_im2col(x[b0:b1], self.kernel_size, self.strides, padding, act_format, act_scale)
+                rows = y[b0 * per:b1 * per]
+                if isinstance(operand, torch.Tensor):             # mx_hardware(emulate=True): the fake-quantised kernel (K, co)
+                    torch.matmul(ops.mx_operand_decode(a), operand, out=rows)
+                    if qb is not None:
+                        rows.add_(qb)
+                else:
+                    ops.mx_gemm(a, operand, qb, out=rows)
+            y = y.view(B, OH, OW, self.filters)                   # the GEMM's [M][co] is NHWC: no transposition launch
+            return y if self.data_format == "NHWC" else y.permute(0, 3, 1, 2)
+
+    def call_mx(self, inputs, act_format="fp8_e4m3", act_scale="mx", max_lines=None):
+        """The layer on the block-scaled matrix instruction, under ``no_grad``: the im2col matrix of the inputs quantised per block
+        of 32 along (ci, kh, kw) (``act_format`` elements under the ``act_scale`` rule) by ops.mx_operand_im2col -- TensorFlow 'SAME'
+        padding as ``call`` pads, or 'VALID' -- multiplied with ``mx_operand()`` by ops.mx_gemm, plus the fake-quantised bias where
+        the layer has one.  Inference only: there is no backward through this path.  The result is a view of the GEMM's (M, co)
+        matrix: ``(B, co, OH, OW)`` with channels-last strides for ``data_format="NCHW"``, ``(B, OH, OW, co)`` for "NHWC".  A batch
+        whose im2col matrix has 2^31 elements or more, or more than ``max_lines`` lines, is cut into runs of whole images that
+        write their rows of the one result; the result does not depend on the cut."""
+        if max_lines is not None and (not isinstance(max_lines, int) or isinstance(max_lines, bool) or max_lines < 1):
+            raise ValueError(f"max_lines must be a positive integer or None, got {max_lines!r}")
+        ops.check_mx_operand_format(act_format)
+        ops.check_mx_scale_init(act_scale)
+        if not self.built:
+            self.build(tuple(inputs.shape), device=inputs.device)
+        with torch.no_grad():
+            operand = self.mx_operand()
+            qb = self.nested_q_b_layer(self.b) if self._has_bias else None
+            return self._mx_conv(inputs, operand, qb, act_format, act_scale, max_lines)
 
 
 class CustomConv2DLayer(_ConvBase):
@@ -883,6 +951,13 @@ def mx_hardware_eligible(layer: nn.Module) -> bool:
             and layer.scale_format == "e8m0" and layer.group_size == ops.MX_GROUP_SIZE)
 
 
+def mx_conv_eligible(layer: nn.Module) -> bool:
+    """Whether ``layer`` takes the block-scaled GEMM under ``mx_hardware(convs=True)``: a built conv layer with an fp4 / fp8 element
+    format, E8M0 scales, blocks of 32 and the kernel stored "oihw" (the blocks then run along the im2col operand's K)."""
+    return (isinstance(layer, _ConvBase) and layer.built and layer.element_format in ops.MX_OPERAND_FORMATS
+            and layer.scale_format == "e8m0" and layer.group_size == ops.MX_GROUP_SIZE and layer.kernel_storage == "oihw")
+
+
 class mx_hardware:
     """Context manager: inside it every eligible Dense layer of ``model`` (``mx_hardware_eligible``) computes its eval-mode ``call``
     as ``call_mx`` does -- activations quantised per block (``act_format``, ``act_scale``), the product on the block-scaled matrix
@@ -894,15 +969,22 @@ class mx_hardware:
     relu between the layers, as models.MNISTDense does -- evaluates it in eval mode through ``mx_dense_chain``: every layer but the
     last writes the next layer's operand from its own epilogue, and no fp32 hidden activation exists.  Same bits as ``fused=False``.
     ``fused_layers`` lists the layers that fused; a model without such a tail (BatchNorm between its Dense layers) keeps the
-    per-layer path and lists none.  ``emulate=True`` with ``fused=True`` is refused: the yardstick is the unfused path."""
+    per-layer path and lists none.  ``emulate=True`` with ``fused=True`` is refused: the yardstick is the unfused path.
+    ``convs=True``: every conv layer that can (``mx_conv_eligible``) switches its eval-mode ``call`` too, to what its ``call_mx``
+    does -- the im2col operand of its input gathered and quantised in one launch (ops.mx_operand_im2col), times the kernel's
+    operand, plus the fake-quantised bias; the result is a channels-last view for ``data_format="NCHW"``.  Operand and bias are
+    built once, on entry, and the layer is listed in ``layers`` after the Dense layers.  Under ``emulate=True`` such a layer
+    multiplies the decoded im2col operand with the fake-quantised kernel by ``torch.matmul`` instead.  Without ``convs`` (the
+    default) conv layers keep the fake-quantised path."""
 
-    def __init__(self, model: nn.Module, act_format="fp8_e4m3", act_scale="mx", emulate=False, fused=False):
+    def __init__(self, model: nn.Module, act_format="fp8_e4m3", act_scale="mx", emulate=False, fused=False, convs=False):
         ops.check_mx_operand_format(act_format)
         ops.check_mx_scale_init(act_scale)
         if emulate and fused:
             raise ValueError("mx_hardware: emulate=True with fused=True: the emulated path is the yardstick of the unfused path and "
                              "has no operand-out epilogue")
         self.model, self.act_format, self.act_scale, self.emulate, self.fused = model, act_format, act_scale, bool(emulate), bool(fused)
+        self.convs = bool(convs)
         self.layers, self.fused_layers, self._fused_modules = [], [], []
 
     def __enter__(self):
@@ -911,6 +993,12 @@ class mx_hardware:
             for m in self.layers:
                 weight = m.nested_q_w_layer(m.W).detach() if self.emulate else m.mx_operand()
                 m._mx_hw = (weight, m.nested_q_b_layer(m.b).detach(), self.act_format, self.act_scale)
+            for m in [m for m in custom_layers_of(self.model) if mx_conv_eligible(m)] if self.convs else []:
+                # emulate: the fake-quantised kernel as the (K, co) matrix the decoded im2col operand multiplies
+                weight = m.nested_q_k_layer(m.kernel).detach().permute(3, 2, 0, 1).reshape(m.filters, -1).t() if self.emulate \
+                    else m.mx_operand()
+                m._mx_hw = (weight, m.nested_q_b_layer(m.b).detach() if m._has_bias else None, self.act_format, self.act_scale)
+                self.layers.append(m)
         self.fused_layers, self._fused_modules = [], []
         if self.fused:
             for mod in self.model.modules():

@@ -644,7 +644,72 @@ def mx_gemm_quantize(a: MxOperand, b: MxOperand, bias: Optional[torch.Tensor] = 
     return MxOperand(codes, scales, out_format, M, N)
 
 
-STATS_MAX_BINS = 4096    # include/lq_hip.h, lq_group_stats: the widest range whose codes it bins
+class MxConvOperand(MxOperand):
+    """The MxOperand of an im2col matrix (``mx_operand_im2col``): the same five fields, and ``out_hw = (OH, OW)`` of the convolution
+    whose ``lines = B * OH * OW`` it holds."""
+    out_hw: Tuple[int, int] = (0, 0)
+
+
+def _conv_geom(shape, stride, kernel_size, strides, padding) -> "_hip.ConvGeom":
+    def ints(v, n, what):
+        v = (v,) * n if isinstance(v, int) else tuple(v)
+        if len(v) != n or not all(isinstance(e, int) and not isinstance(e, bool) for e in v):
+            raise ValueError(f"{what} must be {n} integers, got {v!r}")
+        return v
+    shape = tuple(int(d) for d in shape)
+    if len(shape) != 4:
+        raise ValueError(f"the input must have four axes (B, C, H, W), got shape {shape}")
+    (kh, kw), (sh, sw) = ints(kernel_size, 2, "kernel_size"), ints(strides, 2, "strides")
+    top, bottom, left, right = ints(padding, 4, "padding (top, bottom, left, right)")
+    for what, v in (("kernel_size", (kh, kw)), ("strides", (sh, sw)), ("padding", (top, bottom, left, right))):
+        if any(abs(e) >= 1 << 31 for e in v):
+            raise ValueError(f"{what} {v!r} does not fit 32 bits")
+    return _hip.ConvGeom(*shape, *(int(e) for e in stride), kh, kw, sh, sw, top, left, bottom, right)
+
+
+def mx_im2col_dims(input_shape, kernel_size, strides=(1, 1), padding=(0, 0, 0, 0)) -> Tuple[int, int, int, int]:
+    """``(M, K, OH, OW)`` of the im2col matrix of an input ``(B, C, H, W)`` (include/lq_hip.h, lq_mx_im2col_dims): ``OH = (H + top +
+    bottom - KH) // stride_h + 1``, ``M = B OH OW`` lines over ``K = C KH KW``.  ``padding`` is (top, bottom, left, right).  Needs no
+    device, and answers for an ``M * K`` that the operand itself refuses."""
+    import ctypes
+    g = _conv_geom(input_shape, (0, 0, 0, 0), kernel_size, strides, padding)
+    out = [ctypes.c_int64(0) for _ in range(4)]
+    _hip.check(_hip.load().lq_mx_im2col_dims(ctypes.byref(g), *(ctypes.byref(o) for o in out)), "lq_mx_im2col_dims")
+    return tuple(int(o.value) for o in out)
+
+
+def mx_operand_im2col(x: torch.Tensor, kernel_size, strides=(1, 1), padding=(0, 0, 0, 0), element_format: str = "fp8_e4m3",
+                      method: str = "mx") -> MxOperand:
+    """The operand of the im2col matrix of ``x (B, C, H, W)`` -- line ``(b OH + oh) OW + ow``, reduction index ``(c KH + i) KW + j``,
+    zero ``padding`` (top, bottom, left, right) -- under scales taken from it (include/lq_hip.h, lq_mx_operand_im2col): byte for
+    byte ``mx_operand_quantize`` of that matrix, which is never built.  ``x`` is read through its own strides (NCHW-contiguous,
+    channels_last or any view): no copy.  One launch.  The result is an MxOperand whose ``out_hw`` is ``(OH, OW)``."""
+    import ctypes
+    fmt = check_mx_operand_format(element_format)
+    m = check_mx_scale_init(method)
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError(f"x must have four axes (B, C, H, W), got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
+    if not x.is_cuda:
+        raise RuntimeError(f"x is on {x.device}: the learned-quantization ops run only on a HIP device (MI355X); there is no CPU fallback")
+    if x.dtype != torch.float32:
+        raise TypeError(f"x must be float32, got {x.dtype}")
+    if x.device.index is not None and x.device.index != torch.cuda.current_device():
+        raise RuntimeError(f"x lives on {x.device} but the current device is cuda:{torch.cuda.current_device()}: call "
+                           "torch.cuda.set_device(...) before using the ops")
+    lib = _hip.load()
+    g = _conv_geom(x.shape, x.stride(), kernel_size, strides, padding)
+    dims = [ctypes.c_int64(0) for _ in range(4)]
+    _hip.check(lib.lq_mx_im2col_dims(ctypes.byref(g), *(ctypes.byref(o) for o in dims)), "lq_mx_im2col_dims")
+    M, K, OH, OW = (int(o.value) for o in dims)
+    codes, scales = _mx_operand_buffers(element_format, M, K, x.device)
+    _hip.check(lib.lq_mx_operand_im2col(_hip.ptr(x), ctypes.byref(g), fmt.id, m, _hip.ptr(codes), _hip.ptr(scales),
+                                        _hip.stream_ptr(x.device)), "lq_mx_operand_im2col")
+    op = MxConvOperand(codes, scales, element_format, M, K)
+    op.out_hw = (OH, OW)
+    return op
+
+
+STATS_MAX_BINS = 4096   # include/lq_hip.h, lq_group_stats: the widest range whose codes it bins
 
 
 class GroupStats(NamedTuple):

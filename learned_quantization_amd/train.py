@@ -611,26 +611,34 @@ def build_parser():
                          "layers.mx_dense_chain: relu and the next operand's quantisation in the GEMM's epilogue) and add "
                          "mx_eval_fused_layers, mx_eval_fused_accuracy and mx_eval_fused_max_logit_diff (against the unfused "
                          "hardware path; 0.0 is expected) to the result line")
+    ap.add_argument("--mx-eval-convs", action="store_true",
+                    help="with --mx-eval: evaluate once more under layers.mx_hardware(convs=True) (conv layers too on the block-scaled "
+                         "matrix instruction, their im2col operand gathered by ops.mx_operand_im2col) and add mx_eval_conv_layers, "
+                         "mx_eval_conv_accuracy and mx_eval_conv_max_logit_diff (the model's outputs against the emulated path with "
+                         "convs=True) to the result line")
     return ap
 
 
 @torch.no_grad()
-def mx_eval(model, x, y, act_format="fp8_e4m3", act_scale="mx", fused=False):
+def mx_eval(model, x, y, act_format="fp8_e4m3", act_scale="mx", fused=False, convs=False):
     """One evaluation of ``model`` on (x, y) under layers.mx_hardware and one under its ``emulate=True`` yardstick: a dict of both
     accuracies and the largest |difference| of the outputs of the last Dense layer that took the path (the logits of the MNIST
     model).  ``fused=True`` adds a third evaluation under ``mx_hardware(fused=True)``: its accuracy and the largest |difference| of
-    the model's ``logits`` from the unfused hardware path's (the same bits are expected: 0.0)."""
+    the model's ``logits`` from the unfused hardware path's (the same bits are expected: 0.0).  ``convs=True`` adds an evaluation under
+    ``mx_hardware(convs=True)`` and one under its emulation: the number of conv layers that took the path, the accuracy, and the
+    largest |difference| of the model's outputs between the two; a model without Dense layers is then accepted."""
     was_training = model.training
     model.eval()
     acc, logits = [], []
     try:
         for emulate in (False, True):
             with L.mx_hardware(model, act_format, act_scale, emulate=emulate) as hw:
-                if not hw.layers:
+                if not hw.layers and not convs:
                     raise ValueError("mx_eval: the model has no Dense layer that can run on the block-scaled matrix instruction "
                                      "(fp4 / fp8 element format, E8M0 scales, blocks of 32)")
                 seen = []
-                hook = hw.layers[-1].register_forward_hook(lambda m, i, o: seen.append(o.detach()))
+                # with convs=True a model without such a Dense layer is accepted: its Dense fields are those of the model's own output
+                hook = (hw.layers[-1] if hw.layers else model).register_forward_hook(lambda m, i, o: seen.append(o.detach()))
                 try:
                     p = model(x)
                 finally:
@@ -646,6 +654,17 @@ def mx_eval(model, x, y, act_format="fp8_e4m3", act_scale="mx", fused=False):
                 fused_logits, p = model.logits(x), model(x)
                 fields = {"mx_eval_fused_layers": len(hwf.fused_layers), "mx_eval_fused_accuracy": float((p.argmax(1) == y).float().mean()),
                           "mx_eval_fused_max_logit_diff": float((fused_logits - logits[0]).abs().max())}
+        if convs:
+            outs = []
+            for emulate in (False, True):
+                with L.mx_hardware(model, act_format, act_scale, emulate=emulate, convs=True) as hwc:
+                    n_convs = sum(L.mx_conv_eligible(m) for m in hwc.layers)
+                    if not n_convs:
+                        raise ValueError("mx_eval: convs=True needs a model with a conv layer that can run on the block-scaled matrix "
+                                         "instruction (fp4 / fp8 element format, E8M0 scales, blocks of 32, kernel stored oihw)")
+                    outs.append(model(x))
+            fields.update({"mx_eval_conv_layers": n_convs, "mx_eval_conv_accuracy": float((outs[0].argmax(1) == y).float().mean()),
+                           "mx_eval_conv_max_logit_diff": float((outs[0] - outs[1]).abs().max())})
     finally:
         model.train(was_training)
     return {"mx_eval_act_format": act_format, "mx_eval_layers": len(hw.layers), "mx_eval_accuracy": acc[0],
@@ -659,6 +678,8 @@ def main(argv=None):
         ap.error("--mx-eval needs --element-format: it runs the layers of a microscaling model on the block-scaled matrix instruction")
     if args.mx_eval_fused and args.mx_eval is None:
         ap.error("--mx-eval-fused needs --mx-eval: it compares the fused Dense tail with the unfused hardware path")
+    if args.mx_eval_convs and args.mx_eval is None:
+        ap.error("--mx-eval-convs needs --mx-eval: it adds the conv layers to the hardware path that --mx-eval evaluates")
     if args.quant_stats and args.bits is None:
         ap.error("--quant-stats needs --bits: the statistics are those of a quantizer with a range")
     if args.mx_stats and args.element_format is None:
@@ -726,7 +747,7 @@ def main(argv=None):
     log_rows = tr.flush_loss_log() if args.loss_values and rank == 0 else None     # every rank holds the same rows: one writes
     quant_stats = L.quant_stats(tr.model) if args.quant_stats and rank == 0 else None      # after the clock has stopped
     mx_stats = L.mx_quant_stats(tr.model) if args.mx_stats and rank == 0 else None
-    mx_eval_fields = mx_eval(tr.model, *batches[0], act_format=args.mx_eval, fused=args.mx_eval_fused) if args.mx_eval is not None and rank == 0 else None
+    mx_eval_fields = mx_eval(tr.model, *batches[0], act_format=args.mx_eval, fused=args.mx_eval_fused, convs=args.mx_eval_convs) if args.mx_eval is not None and rank == 0 else None
     if rank == 0:
         n_q = sum(p.numel() for l in tr.custom_layers for p in l._regularized())
         print(json.dumps({

@@ -498,6 +498,69 @@ typedef struct lq_conv_geom {
 int lq_mx_im2col_dims(const lq_conv_geom* g, int64_t* M, int64_t* K, int64_t* OH, int64_t* OW);
 int lq_mx_operand_im2col(const float* X, const lq_conv_geom* g, int format, int method, void* codes, void* scales, void* stream);
 
+/* ---- packed int8 operands and the int8 GEMM ----
+ * The integer counterpart of the packed MX operands: a trained b-bit layer (b <= 8, signed range) multiplied on gfx950's
+ * v_mfma_i32_16x16x64_i8.  An OPERAND is a matrix of L lines by K reduction elements: one int8 code per element and fp32 scales,
+ * one per line and per SCALE BLOCK of `block` consecutive k.  block == 0: one scale per line (nbs = 1); otherwise
+ * block % 64 == 0 and nbs = ceil(K / block), the last block may be short.  To callers it is opaque apart from its sizes
+ * (lq_i8_operand_bytes); the layout is stated here so that it can be checked:
+ *   LT = ceil(L / 16), KT = ceil(K / 64)
+ *   codes   [LT][KT][64][16]   fragment `lane` of tile (lt, kt) holds line 16 lt + (lane & 15) and k = 64 kt + 16 (lane >> 4) + j in
+ *                              byte j, j = 0 .. 15 (two's complement).  The byte of (line, k) is at
+ *                              (((line >> 4) * KT + (k >> 6)) * 64 + 16 * ((k & 63) >> 4) + (line & 15)) * 16 + (k & 15)
+ *   scales  [nbs][16 LT] fp32  the scale of (block, line) at index block * 16 LT + line
+ *   code_bytes = LT * KT * 1024, scale_bytes = nbs * LT * 64.  Lines past L and k past K hold code 0; scales of lines past L are 1.0f.
+ * What the device pins about the instruction (tests/test_gpu_i8.py: one-hot operands for every k = 0 .. 127, every code against
+ * {-128, -1, 1, 127}): lane l supplies line l & 15 of A and of B; A's lines are the result's rows, B's its columns (column l & 15 on
+ * the lane, rows 4 (l >> 4) + r in register r); both operands take the same k from the same (lane >> 4, byte).  The instruction
+ * adds all 64 k of a step into one int32, so the NAME of the k that a (lane >> 4, byte) pair holds cannot be observed: any
+ * permutation of k inside a step applied to both operands gives the same sums.  The rule above -- 16 consecutive k per lane, no
+ * two half blocks as 8-bit data in the block-scaled instruction -- is therefore this library's definition, not a hardware fact, and
+ * scale blocks are whole steps so that nothing depends on it.
+ *
+ * lq_i8_operand_pack: the operand of a stored parameter under its stored scales, in lq_fq_forward_group's geometry exactly
+ * ([R][C] in memory order; axis 0: s [nb][C], the lines are the C columns and K = R; axis 1: s [R][nb], the lines are the R rows and
+ * K = C).  The codes are the clamped integers of lq_fq_forward_group's LQ_Q_I8 integer view (the same element step, `rounding`
+ * included); the scales are s copied bit for bit.  gs >= K gives block = 0; otherwise gs % 64 == 0 is required and block = gs.
+ * lq_i8_operand_quantize: the dynamic symmetric quantizer of a row-major X [M][K] (lines: rows).  Per (row, scale block) the scale
+ * is lq_scale_init_group's LQ_INIT_ABSMAX with qmin = -127, qmax = 127, min_value = 2^-126, and the codes are the clipped step
+ * with LQ_ROUND_NEAREST_EVEN under that scale: byte for byte the buffers of
+ *     lq_i8_operand_pack(X, lq_scale_init_group(X, ABSMAX, -127, 127, axis 1, gs = block or K), -127, 127, nearest, M, K, axis 1, ...)
+ * A row block of zeros gets scale 2^-126 and codes 0.  A NaN or +-Inf element gives that one block a NaN scale; its codes are
+ * then all 0, because the integer view stores 0 for a NaN quotient (as lq_fq_forward_group's does).  One launch; a scale block
+ * (a row for block == 0) of up to 4096 elements (1024 where K % 4 != 0 or X is off the 16-byte grid) is read from memory once,
+ * the tail of a longer one a second time.
+ * lq_i8_operand_decode: out [L][K] row-major, out = (float)code * scale, one fp32 product.  For a packed parameter this equals
+ * lq_fq_forward_group's `out` as values, with two exceptions that both come from code 0: a -0.0 there (a negative element that
+ * rounds to zero) decodes as +0.0, and a NaN element under a valid scale, NaN there, decodes as 0 (the integer view stores 0 for
+ * it).  Under a NaN scale both are NaN.
+ * lq_i8_gemm: Y[m][n] = sum_k A[m][k] B[n][k] (+ bias[n]), Y row-major with leading dimension ldy >= N, A and B operands of M and N
+ * lines over the same K with scale blocks a_block and b_block.  DEFINITION (bit exact; tests/_i8_reference.py states it in NumPy):
+ *   a PERIOD is a maximal run of k on which neither operand's scale changes: the whole K if both blocks are 0, otherwise runs of
+ *   F = the smaller non-zero block (the larger must be a multiple of it, else LQ_EINVAL); the last period may be short.  A period
+ *   longer than 65536 is refused: |a b| <= 2^14, so 65536 terms stay inside int32.  For output (m, n), over the periods p in
+ *   ascending k, starting from y = +0:
+ *       I_p = sum_{k in p} a[m][k] * b[n][k]            exact, int32
+ *       t_p = RN(sa[m][p] * sb[n][p])                   fp32
+ *       y   = RN(y + RN((float)I_p * t_p))              (float): round to nearest even; the product and the sum round separately
+ *   and last, with a bias, y = RN(y + bias[n]).  A NaN scale makes its row or column NaN and touches nothing else.  No atomics:
+ *   run-to-run bit-stable.
+ *
+ * LQ_EINVAL before any launch: a NULL pointer (bias may be NULL), a non-positive extent, L * K >= 2^31, a block that is negative
+ * or no multiple of 64, a period above 65536, blocks of which neither divides the other, ldy < N, M above 65535 * 64; for pack also
+ * a range not inside [-128, 127], a gs that is neither >= K nor a multiple of 64, and everything lq_fq_forward_group refuses.
+ * LQ_EALIGN: codes or scales off the 16-byte grid; P, s, X, bias, out or Y off the 4-byte grid.  Each call only enqueues ONE launch
+ * (capturable), allocates nothing, reads no environment, and writes exactly code_bytes and scale_bytes (pack, quantize), L * K
+ * floats (decode) or the M x N elements of Y (gemm).
+ * Not built: conv layers, an operand-out epilogue, asymmetric (offset) layers, any backward, sub-byte packing of 4-bit codes.  */
+int lq_i8_operand_bytes(int64_t L, int64_t K, int64_t block, size_t* code_bytes, size_t* scale_bytes);
+int lq_i8_operand_pack(const float* P, const float* s, int32_t qmin, int32_t qmax, int rounding, int64_t R, int64_t C, int axis,
+                       int64_t gs, void* codes, void* scales, void* stream);
+int lq_i8_operand_quantize(const float* X, int64_t M, int64_t K, int64_t block, void* codes, void* scales, void* stream);
+int lq_i8_operand_decode(const void* codes, const void* scales, int64_t L, int64_t K, int64_t block, float* out, void* stream);
+int lq_i8_gemm(const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes, const void* b_scales, int64_t b_block,
+               const float* bias /* may be NULL */, float* Y, int64_t ldy, int64_t M, int64_t N, int64_t K, void* stream);
+
 /* ---- K4: forward and NQ backward of one tensor in a single pass (benchmark path) ---
  * Same results as lq_fq_forward followed by lq_fq_scale_grad (out, max|q| and the vote count bit for bit; on
  * streaming-size tensors the vote sum may differ by fp32 summation order, ~1e-7 relative); P is read once.  */

@@ -16,6 +16,8 @@
 //   lq_mx.hpp           OCP microscaling element formats: the group-wise traversal bodies with a minifloat element step
 //   lq_mx_operand.hpp   packed MX operands in the block-scaled matrix instruction's fragment order: pack, dynamic quantize, decode
 //   lq_mx_gemm.hpp      the GEMM of two packed operands on v_mfma_scale_f32_16x16x128_f8f6f4
+//   lq_i8_operand.hpp   packed int8 operands with fp32 scales per line and scale block: pack, dynamic quantize, decode
+//   lq_i8_gemm.hpp      the GEMM of two packed int8 operands on v_mfma_i32_16x16x64_i8
 //   lq_mx_conv.hpp      the operand of a convolution's im2col matrix, gathered from the input in one launch
 //   this file           host side: traversal plan, launchers, the extern "C" entry points
 //
@@ -65,6 +67,8 @@
 #include "lq_mx_operand.hpp"
 #include "lq_mx_gemm.hpp"
 #include "lq_mx_conv.hpp"
+#include "lq_i8_operand.hpp"
+#include "lq_i8_gemm.hpp"
 
 namespace lq {
 
@@ -2135,6 +2139,188 @@ int lq_mx_operand_im2col(const float* X, const lq_conv_geom* g, int format, int 
         else hipLaunchKernelGGL((k_mx_im2col<kInitMxCover, false>), grid, block, 0, st, op);
     }
     return check_hip("microscaling im2col operand");
+}
+
+// ---- packed int8 operands and the int8 GEMM (lq_i8_operand.hpp, lq_i8_gemm.hpp) ----
+struct I8OperandDims {
+    int64_t LT, KT, nbs;
+    size_t code_bytes, scale_bytes;
+};
+
+static int i8_operand_dims(const char* fn, int64_t L, int64_t K, int64_t block, I8OperandDims& d) {
+    if (L <= 0 || K <= 0) return fail(LQ_EINVAL, "%s: extents must be positive (L=%lld K=%lld)", fn, (long long)L, (long long)K);
+    if ((double)L * (double)K >= 2147483648.0 || K > 2147483647 - kI8TileK)
+        return fail(LQ_EINVAL, "%s: L * K = %lld * %lld is not below 2^31", fn, (long long)L, (long long)K);
+    if (block < 0 || block % kI8TileK != 0 || block > (1 << 30))
+        return fail(LQ_EINVAL, "%s: scale block %lld is neither 0 (one scale per line) nor a multiple of %d up to 2^30: a scale "
+                    "must not change inside a step of the instruction", fn, (long long)block, kI8TileK);
+    d.LT = (L + kI8TileLines - 1) / kI8TileLines;
+    d.KT = (K + kI8TileK - 1) / kI8TileK;
+    d.nbs = block ? (K + block - 1) / block : 1;
+    d.code_bytes = (size_t)(d.LT * d.KT * 1024);
+    d.scale_bytes = (size_t)(d.nbs * d.LT * kI8TileLines * 4);
+    return LQ_OK;
+}
+
+int lq_i8_operand_bytes(int64_t L, int64_t K, int64_t block, size_t* code_bytes, size_t* scale_bytes) {
+    const char* fn = __func__;
+    if (!code_bytes || !scale_bytes) return fail(LQ_EINVAL, "%s: code_bytes or scale_bytes is NULL", fn);
+    I8OperandDims d;
+    int rc = i8_operand_dims(fn, L, K, block, d);
+    if (rc) return rc;
+    *code_bytes = d.code_bytes;
+    *scale_bytes = d.scale_bytes;
+    return LQ_OK;
+}
+
+static int check_i8_operand_buffers(const char* fn, const void* codes, const void* scales) {
+    if (!codes || !scales) return fail(LQ_EINVAL, "%s: argument '%s' is NULL", fn, codes ? "scales" : "codes");
+    if (!aligned(codes, 16)) return fail(LQ_EALIGN, "%s: codes is not 16-byte aligned", fn);
+    if (!aligned(scales, 16)) return fail(LQ_EALIGN, "%s: scales is not 16-byte aligned", fn);
+    return LQ_OK;
+}
+
+int lq_i8_operand_pack(const float* P, const float* s, int32_t qmin, int32_t qmax, int rounding, int64_t R, int64_t C, int axis,
+                       int64_t gs, void* codes, void* scales, void* stream) {
+    const char* fn = __func__;
+    int rc = check_group(fn, R, C, axis, gs);
+    if (rc) return rc;
+    LQ_REQUIRE_PTR_FN(fn, P);
+    LQ_REQUIRE_PTR_FN(fn, s);
+    if ((rc = check_clip_range(fn, qmin, qmax))) return rc;
+    if ((rc = check_rounding(fn, rounding))) return rc;
+    if (qmin < -128 || qmax > 127)
+        return fail(LQ_EINVAL, "%s: range [%d, %d] is not inside [-128, 127], the operands of the int8 matrix instruction", fn, (int)qmin,
+                    (int)qmax);
+    const int64_t L = axis == 0 ? C : R, K = axis == 0 ? R : C;
+    if (gs < K && gs % kI8TileK != 0)
+        return fail(LQ_EINVAL, "%s: group size %lld is neither the whole line (%lld) nor a multiple of %d: a scale must not change "
+                    "inside a step of the instruction", fn, (long long)gs, (long long)K, kI8TileK);
+    const int64_t block = gs >= K ? 0 : gs;
+    I8OperandDims d;
+    if ((rc = i8_operand_dims(fn, L, K, block, d))) return rc;
+    if ((rc = check_i8_operand_buffers(fn, codes, scales))) return rc;
+    I8PackParams op{};
+    op.g = group_params(P, s, qmin, qmax, R, C, axis, gs);
+    op.codes = (uint8_t*)codes;
+    op.scales = (float*)scales;
+    op.line_stride = axis == 0 ? 1 : C;
+    op.k_stride = axis == 0 ? C : 1;
+    op.s_line_stride = axis == 0 ? 1 : d.nbs;      // [nb][C] | [R][nb]
+    op.s_blk_stride = axis == 0 ? C : 1;
+    op.L = (int32_t)L;
+    op.K = (int32_t)K;
+    op.block = (int32_t)block;
+    op.LT = (int32_t)d.LT;
+    op.KT = (int32_t)d.KT;
+    const int64_t threads = d.LT * kI8TileLines * d.KT * 4;
+    const dim3 grid((unsigned)((threads + kBlock - 1) / kBlock)), blk(kBlock);
+    hipStream_t st = (hipStream_t)stream;
+    const bool rne = rounding == LQ_ROUND_NEAREST_EVEN;
+    if (axis == 0) {
+        if (rne) hipLaunchKernelGGL((k_i8_pack<true, true>), grid, blk, 0, st, op);
+        else hipLaunchKernelGGL((k_i8_pack<false, true>), grid, blk, 0, st, op);
+    } else {
+        if (rne) hipLaunchKernelGGL((k_i8_pack<true, false>), grid, blk, 0, st, op);
+        else hipLaunchKernelGGL((k_i8_pack<false, false>), grid, blk, 0, st, op);
+    }
+    return check_hip("int8 operand pack");
+}
+
+int lq_i8_operand_quantize(const float* X, int64_t M, int64_t K, int64_t block, void* codes, void* scales, void* stream) {
+    const char* fn = __func__;
+    LQ_REQUIRE_PTR_FN(fn, X);
+    I8OperandDims d;
+    int rc = i8_operand_dims(fn, M, K, block, d);
+    if (rc) return rc;
+    if ((rc = check_i8_operand_buffers(fn, codes, scales))) return rc;
+    I8QuantParams op{};
+    op.g.P = X;
+    op.g.lo = op.ip.lo = -127.0f;
+    op.g.hi = op.ip.hi = 127.0f;
+    op.ip.min_value = 1.17549435082228750797e-38f;      // 2^-126, as lq_mx_operand_quantize
+    op.codes = (uint8_t*)codes;
+    op.scales = (float*)scales;
+    op.M = (int32_t)M;
+    op.K = (int32_t)K;
+    op.block = (int32_t)block;
+    op.nbs = (int32_t)d.nbs;
+    op.LT = (int32_t)d.LT;
+    op.KT = (int32_t)d.KT;
+    // the team covers its scale block (or row) in one access per lane where 64 lanes can
+    const int v = (K % 4 == 0 && aligned(X, 16)) ? 4 : 1;
+    const int64_t span = std::min<int64_t>(block ? block : d.KT * kI8TileK, 64 * v);
+    int log_team = 0;
+    while (log_team < 6 && ((int64_t)v << log_team) < span) ++log_team;
+    const int64_t pairs = d.LT * kI8TileLines * d.nbs, per_block = kBlock >> log_team;
+    const dim3 grid((unsigned)((pairs + per_block - 1) / per_block)), blk(kBlock);
+    if (v == 4) hipLaunchKernelGGL(k_i8_quantize<4>, grid, blk, 0, (hipStream_t)stream, op, log_team);
+    else hipLaunchKernelGGL(k_i8_quantize<1>, grid, blk, 0, (hipStream_t)stream, op, log_team);
+    return check_hip("int8 operand quantize");
+}
+
+int lq_i8_operand_decode(const void* codes, const void* scales, int64_t L, int64_t K, int64_t block, float* out, void* stream) {
+    const char* fn = __func__;
+    I8OperandDims d;
+    int rc = i8_operand_dims(fn, L, K, block, d);
+    if (rc) return rc;
+    if ((rc = check_i8_operand_buffers(fn, codes, scales))) return rc;
+    LQ_REQUIRE_PTR_FN(fn, out);
+    I8DecodeParams dp{};
+    dp.codes = (const uint8_t*)codes;
+    dp.scales = (const float*)scales;
+    dp.out = out;
+    dp.L = (int32_t)L;
+    dp.K = (int32_t)K;
+    dp.block = (int32_t)block;
+    dp.LT = (int32_t)d.LT;
+    dp.KT = (int32_t)d.KT;
+    const int64_t n = L * K;
+    hipLaunchKernelGGL(k_i8_decode, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream, dp);
+    return check_hip("int8 operand decode");
+}
+
+int lq_i8_gemm(const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes, const void* b_scales, int64_t b_block,
+               const float* bias, float* Y, int64_t ldy, int64_t M, int64_t N, int64_t K, void* stream) {
+    const char* fn = __func__;
+    I8OperandDims da, db;
+    int rc = i8_operand_dims(fn, M, K, a_block, da);
+    if (rc || (rc = i8_operand_dims(fn, N, K, b_block, db))) return rc;
+    const int64_t lo = std::min(a_block, b_block), hi = std::max(a_block, b_block);
+    if (lo > 0 && hi % lo != 0)
+        return fail(LQ_EINVAL, "%s: scale blocks %lld and %lld: the larger must be a multiple of the smaller", fn, (long long)a_block,
+                    (long long)b_block);
+    const int64_t F = lo > 0 ? lo : hi;            // the period: the smaller non-zero block, or 0 for the whole K
+    const int64_t period = F > 0 ? std::min(F, K) : K;
+    if (period > 65536)
+        return fail(LQ_EINVAL, "%s: a period of %lld k between two scale changes is above 65536: the int32 sum of that many products of "
+                    "magnitude up to 2^14 could overflow", fn, (long long)period);
+    if ((rc = check_i8_operand_buffers(fn, a_codes, a_scales))) return rc;
+    if ((rc = check_i8_operand_buffers(fn, b_codes, b_scales))) return rc;
+    LQ_REQUIRE_PTR_FN(fn, Y);
+    if (bias && !aligned(bias, 4)) return fail(LQ_EALIGN, "%s: bias is not 4-byte aligned", fn);
+    if (ldy < N) return fail(LQ_EINVAL, "%s: ldy = %lld is below N = %lld", fn, (long long)ldy, (long long)N);
+    if ((double)M * (double)ldy >= 9.0e15) return fail(LQ_EINVAL, "%s: Y is too large", fn);
+    I8GemmParams p{};
+    p.a_codes = (const uint8_t*)a_codes;
+    p.a_scales = (const float*)a_scales;
+    p.b_codes = (const uint8_t*)b_codes;
+    p.b_scales = (const float*)b_scales;
+    p.bias = bias;
+    p.Y = Y;
+    p.ldy = ldy;
+    p.M = (int32_t)M;
+    p.N = (int32_t)N;
+    p.MT = (int32_t)da.LT;
+    p.NT = (int32_t)db.LT;
+    p.KT = (int32_t)da.KT;
+    p.ps = (int32_t)(F > 0 ? std::min(F / kI8TileK, da.KT) : da.KT);
+    p.a_every = a_block > 0 ? (int32_t)(a_block / F) : INT32_MAX;
+    p.b_every = b_block > 0 ? (int32_t)(b_block / F) : INT32_MAX;
+    const int64_t gx = (db.LT + 3) / 4, gy = (da.LT + 3) / 4;      // a block is 4 x 4 tiles: 64 x 64 of Y
+    if (gy > 65535) return fail(LQ_EINVAL, "%s: M = %lld is above 65535 * 64", fn, (long long)M);
+    hipLaunchKernelGGL(k_i8_gemm, dim3((unsigned)gx, (unsigned)gy), dim3(kBlock), 0, (hipStream_t)stream, p);
+    return check_hip("int8 GEMM");
 }
 
 int lq_fq_fwd_bwd_fused(const float* P, const float* s, const float* dy, float lambda, float* out, float* ds, void* ws,

@@ -646,10 +646,55 @@ class CustomDenseLayer(_HostLayer):
         if hw is not None and not self.training:                  # inside layers.mx_hardware(...), eval mode
             self._q_pre = None                                    # a batch's fake-quantised pair is not what this path multiplies
             return self._mx_product(inputs, *hw)
+        hw = getattr(self, "_i8_hw", None)
+        if hw is not None and not self.training:                  # inside layers.i8_hardware(...), eval mode
+            self._q_pre = None
+            return self._i8_product(inputs, *hw)
         qw, qb = self.quantized_parameters()
         return torch.add(torch.matmul(inputs, qw), qb)           # NQ-L:268
 
     forward = call
+
+    def _check_i8(self):
+        """(qmin, qmax) of a layer that can run on the int8 matrix instruction, or ValueError naming the reason."""
+        q_range = ops.check_i8_operand_layer(self.q_range, self.nested_q_w_layer.orientation, self.group_size, self.asymmetric,
+                                             self.element_format, self.W.shape[0] if self.built else None)
+        if not self.built:
+            raise ValueError(f"{self.name}: the layer is not built yet (no kernel to pack)")
+        return q_range
+
+    def i8_operand(self) -> "ops.I8Operand":
+        """The kernel under its current scales as an operand of the int8 matrix instruction (ops.i8_operand_pack): ``units`` lines
+        over K = in.  A "groupwise" layer passes its scale as it is; a "scalar" or "columnwise" layer its scale broadcast to
+        ``(1, out)``, one group per output unit.  ValueError naming the reason for a layer without a range, with a range outside
+        [-128, 127], with an offset, with "rowwise" scales, with an element format, or not built."""
+        qmin, qmax = self._check_i8()
+        fan_in, units = self.W.shape
+        scale = self.nested_q_w_layer.scale.data
+        if self.nested_q_w_layer.orientation == "groupwise":
+            gs = self.group_size
+        else:
+            scale, gs = scale.reshape(1, -1).expand(1, units).contiguous(), fan_in
+        return ops.i8_operand_pack(self.W.detach(), scale, qmin, qmax, gs, self.rounding)
+
+    def _i8_product(self, inputs, operand, qb, act_block):
+        with torch.no_grad():
+            a = ops.i8_operand_quantize(inputs.reshape(-1, inputs.shape[-1]), act_block)
+            if isinstance(operand, torch.Tensor):                 # i8_hardware(emulate=True): the fake-quantised kernel itself
+                y = torch.add(torch.matmul(ops.i8_operand_decode(a), operand), qb)
+            else:
+                y = ops.i8_gemm(a, operand, qb)
+            return y.reshape(*inputs.shape[:-1], y.shape[-1])
+
+    def call_i8(self, inputs, act_block=0):
+        """The layer on the int8 matrix instruction, under ``no_grad``: the inputs quantised per row and ``act_block`` consecutive
+        inputs (0: per row) to symmetric 8-bit integers (ops.i8_operand_quantize), multiplied with ``i8_operand()`` by ops.i8_gemm,
+        plus the fake-quantised bias.  Inference only: there is no backward through this path."""
+        ops.check_i8_block(act_block)
+        if not self.built:
+            self.build(tuple(inputs.shape), device=inputs.device)
+        with torch.no_grad():
+            return self._i8_product(inputs, self.i8_operand(), self.nested_q_b_layer(self.b), act_block)
 
     def mx_operand(self) -> "ops.MxOperand":
         """The kernel under its current scales as an operand of the block-scaled matrix instruction (ops.mx_operand_pack): ``units``
@@ -1014,6 +1059,45 @@ class mx_hardware:
             m._mx_hw = None
         for mod in self._fused_modules:
             mod._mx_fused = None
+        return False
+
+
+def i8_hardware_eligible(layer: nn.Module) -> bool:
+    """Whether ``layer`` takes the int8 GEMM under ``i8_hardware``: a built Dense layer with a range inside [-128, 127], symmetric,
+    with scalar, columnwise or groupwise scales (group size a multiple of 64, or the whole input) and no element format.  Conv
+    layers keep the fake-quantised path."""
+    if not isinstance(layer, CustomDenseLayer):
+        return False
+    try:
+        layer._check_i8()
+    except ValueError:
+        return False
+    return True
+
+
+class i8_hardware:
+    """Context manager beside ``mx_hardware``: inside it every eligible Dense layer of ``model`` (``i8_hardware_eligible``) computes
+    its eval-mode ``call`` as ``call_i8`` does -- activations quantised per row and ``act_block`` inputs to symmetric 8-bit
+    integers, the product on the int8 matrix instruction.  The operands and the fake-quantised biases are built ONCE, on entry,
+    from the scales the layers have then; training-mode calls and every other layer keep the fake-quantised path.  ``layers`` lists
+    the layers that switched.  ``emulate=True`` is the yardstick of that path in stock arithmetic: the same quantised activations,
+    decoded, times the fake-quantised kernel with ``torch.matmul`` in fp32."""
+
+    def __init__(self, model: nn.Module, act_block=0, emulate=False):
+        self.model, self.act_block, self.emulate = model, ops.check_i8_block(act_block), bool(emulate)
+        self.layers = []
+
+    def __enter__(self):
+        self.layers = [m for m in custom_layers_of(self.model) if i8_hardware_eligible(m)]
+        with torch.no_grad():
+            for m in self.layers:
+                weight = m.nested_q_w_layer(m.W).detach() if self.emulate else m.i8_operand()
+                m._i8_hw = (weight, m.nested_q_b_layer(m.b).detach(), self.act_block)
+        return self
+
+    def __exit__(self, *exc):
+        for m in self.layers:
+            m._i8_hw = None
         return False
 
 

@@ -610,6 +610,158 @@ def mx_gemm(a: MxOperand, b: MxOperand, bias: Optional[torch.Tensor] = None, out
     return out
 
 
+# --------------------------------------------------------------------------- packed int8 operands and the int8 GEMM
+I8_RANGE = (-128, 127)       # what an operand byte of v_mfma_i32_16x16x64_i8 holds
+I8_BLOCK_UNIT = 64           # K of one instruction: a scale block is a whole number of them (include/lq_hip.h)
+I8_MAX_PERIOD = 65536        # the longest run of k between two scale changes whose int32 sum cannot overflow
+
+
+class I8Operand(NamedTuple):
+    """A matrix of ``lines`` by ``K`` in the order gfx950's int8 matrix instruction consumes it (include/lq_hip.h, "packed int8
+    operands"): ``codes`` (uint8) and ``scales`` (float32) are opaque buffers of lq_i8_operand_bytes' sizes; ``block`` is the
+    number of consecutive k that share a scale, 0 for one scale per line."""
+    codes: torch.Tensor
+    scales: torch.Tensor
+    lines: int
+    K: int
+    block: int
+
+
+def check_i8_block(block) -> int:
+    """``block`` as an int, or ValueError: 0 (one scale per line) or a positive multiple of 64."""
+    if isinstance(block, bool) or int(block) != block or int(block) < 0 or int(block) % I8_BLOCK_UNIT:
+        raise ValueError(f"block={block!r}: a scale block is 0 (one scale per line) or a multiple of {I8_BLOCK_UNIT}, the K of one "
+                         "int8 matrix instruction")
+    return int(block)
+
+
+def check_i8_operand_layer(q_range, orientation, group_size=None, asymmetric=False, element_format=None, fan_in=None) -> Tuple[int, int]:
+    """What a quantizer must be to run on the int8 matrix instruction -- (qmin, qmax) -- or ValueError naming the reason."""
+    if element_format is not None:
+        raise ValueError(f"element_format={element_format!r}: a microscaling layer runs on the block-scaled matrix instruction "
+                         "(mx_hardware), not on the int8 one")
+    if q_range is None:
+        raise ValueError("the int8 GEMM needs a layer with bits or q_range: the reference's unbounded quantizer has no range that "
+                         "fits a byte")
+    qmin, qmax = check_q_range(*q_range)
+    if qmin < I8_RANGE[0] or qmax > I8_RANGE[1]:
+        raise ValueError(f"q_range ({qmin}, {qmax}) is not inside [{I8_RANGE[0]}, {I8_RANGE[1]}], the signed bytes the int8 matrix "
+                         "instruction multiplies (an unsigned 8-bit range does not fit)")
+    if asymmetric:
+        raise ValueError("asymmetric=True: an offset per group needs the row sums of the activation codes in the product; that "
+                         "term is not built")
+    if orientation == "rowwise":
+        raise ValueError('orientation="rowwise": a scale per input row varies along K inside a step of the instruction')
+    if orientation not in ("scalar", "columnwise", "groupwise"):
+        raise ValueError(f"orientation={orientation!r}: the int8 GEMM takes scalar, columnwise or groupwise scales")
+    if orientation == "groupwise" and (fan_in is None or group_size < fan_in) and group_size % I8_BLOCK_UNIT:
+        raise ValueError(f"group_size={group_size!r}: a scale block of the int8 GEMM is the whole input or a multiple of "
+                         f"{I8_BLOCK_UNIT}, the K of one instruction")
+    return qmin, qmax
+
+
+def i8_operand_bytes(lines: int, K: int, block: int = 0) -> Tuple[int, int]:
+    """(code_bytes, scale_bytes) of an operand (include/lq_hip.h, lq_i8_operand_bytes).  Needs no device."""
+    import ctypes
+    cb, sb = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _hip.check(_hip.load().lq_i8_operand_bytes(int(lines), int(K), check_i8_block(block), ctypes.byref(cb), ctypes.byref(sb)),
+               "lq_i8_operand_bytes")
+    return int(cb.value), int(sb.value)
+
+
+def _i8_operand_buffers(lines: int, K: int, block: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
+    cb, sb = i8_operand_bytes(lines, K, block)
+    return torch.empty(cb, dtype=torch.uint8, device=device), torch.empty(sb // 4, dtype=torch.float32, device=device)
+
+
+def i8_operand_pack(parameter: torch.Tensor, scale: torch.Tensor, qmin: int, qmax: int, group_size: int,
+                    rounding: str = "floor") -> I8Operand:
+    """The operand of a stored parameter under its stored group-wise scales (include/lq_hip.h, lq_i8_operand_pack): the codes are
+    the clamped integers of ``fq_forward_group``'s int8 view, the scales are ``scale`` bit for bit.  The lines are the parameter's
+    columns when the groups run along its strided axis (a Dense kernel (in, out)), its rows otherwise.  ``group_size`` at least the
+    line length gives one scale per line; otherwise it must be a multiple of 64.  One launch."""
+    qmin, qmax = check_q_range(qmin, qmax)
+    if qmin < I8_RANGE[0] or qmax > I8_RANGE[1]:
+        raise ValueError(f"range ({qmin}, {qmax}) is not inside [{I8_RANGE[0]}, {I8_RANGE[1]}], the signed bytes the int8 matrix "
+                         "instruction multiplies")
+    rnd = check_rounding(rounding)
+    p, s, (R, C, axis) = _group_param(parameter, scale, group_size)
+    lines, K = (C, R) if axis == 0 else (R, C)
+    gs = int(group_size)
+    if gs < K and gs % I8_BLOCK_UNIT:
+        raise ValueError(f"group_size={gs}: a scale block of the int8 GEMM is the whole line ({K}) or a multiple of {I8_BLOCK_UNIT}")
+    block = 0 if gs >= K else gs
+    lib = _hip.load()
+    codes, scales = _i8_operand_buffers(lines, K, block, p.device)
+    _hip.check(lib.lq_i8_operand_pack(_hip.ptr(p), _hip.ptr(s), qmin, qmax, rnd, R, C, axis, gs, _hip.ptr(codes), _hip.ptr(scales),
+                                      _hip.stream_ptr(p.device)), "lq_i8_operand_pack")
+    return I8Operand(codes, scales, lines, K, block)
+
+
+def i8_operand_quantize(x: torch.Tensor, block: int = 0) -> I8Operand:
+    """The operand of a row-major activation matrix ``x (M, K)`` under scales taken from ``x`` itself (include/lq_hip.h,
+    lq_i8_operand_quantize): per row and scale block what ``scale_init_group("absmax", -127, 127, min_value=2^-126)`` writes, then
+    the nearest-rounded clipped integers under it.  No learned state, no backward.  One launch."""
+    block = check_i8_block(block)
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise ValueError(f"x must be a matrix (M, K), got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
+    lib = _hip.load()
+    xc = _hip.require_device_f32(x, "x")
+    M, K = (int(d) for d in xc.shape)
+    codes, scales = _i8_operand_buffers(M, K, block, xc.device)
+    _hip.check(lib.lq_i8_operand_quantize(_hip.ptr(xc), M, K, block, _hip.ptr(codes), _hip.ptr(scales), _hip.stream_ptr(xc.device)),
+               "lq_i8_operand_quantize")
+    return I8Operand(codes, scales, M, K, block)
+
+
+def i8_operand_decode(operand: I8Operand) -> torch.Tensor:
+    """float32 ``(lines, K)``: code * scale of every element (include/lq_hip.h, lq_i8_operand_decode)."""
+    lib = _hip.load()
+    out = torch.empty((operand.lines, operand.K), dtype=torch.float32, device=operand.codes.device)
+    _hip.check(lib.lq_i8_operand_decode(_hip.ptr(operand.codes), _hip.ptr(operand.scales), operand.lines, operand.K,
+                                        check_i8_block(operand.block), _hip.ptr(out), _hip.stream_ptr(out.device)),
+               "lq_i8_operand_decode")
+    return out
+
+
+def i8_period(a_block: int, b_block: int, K: int) -> int:
+    """The length of a period of the int8 GEMM -- a maximal run of k on which neither operand's scale changes (the last may be
+    shorter) -- or ValueError: two non-zero blocks of which neither divides the other, or a period above 65536."""
+    a_block, b_block = check_i8_block(a_block), check_i8_block(b_block)
+    lo, hi = min(a_block, b_block), max(a_block, b_block)
+    if lo > 0 and hi % lo:
+        raise ValueError(f"scale blocks {a_block} and {b_block}: the larger must be a multiple of the smaller")
+    F = lo if lo > 0 else hi
+    period = min(F, K) if F > 0 else K
+    if period > I8_MAX_PERIOD:
+        raise ValueError(f"a period of {period} k between two scale changes is above {I8_MAX_PERIOD}: its int32 sum could overflow")
+    return period
+
+
+def i8_gemm(a: I8Operand, b: I8Operand, bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``Y (a.lines, b.lines) = A B^T (+ bias)`` on v_mfma_i32_16x16x64_i8 (include/lq_hip.h, lq_i8_gemm): exact int32 sums per
+    period, scaled into fp32 by the product of the two operands' scales, bit for bit the definition stated there.
+    ``out``: a float32 matrix to write into; its row stride is the leading dimension."""
+    if a.K != b.K:
+        raise ValueError(f"the operands reduce over different K: {a.K} and {b.K}")
+    i8_period(a.block, b.block, a.K)
+    lib = _hip.load()
+    M, N = a.lines, b.lines
+    dev = a.codes.device
+    if bias is not None:
+        bias = _hip.require_device_f32(bias, "bias")
+        if tuple(bias.shape) != (N,):
+            raise ValueError(f"bias must have shape ({N},), got {tuple(bias.shape)}")
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (M, N) or (N > 1 and out.stride(1) != 1) or not out.is_cuda:
+        raise ValueError(f"out must be a float32 device matrix ({M}, {N}) with unit column stride")
+    ldy = out.stride(0) if M > 1 else max(N, out.stride(0))
+    _hip.check(lib.lq_i8_gemm(_hip.ptr(a.codes), _hip.ptr(a.scales), a.block, _hip.ptr(b.codes), _hip.ptr(b.scales), b.block,
+                              _hip.ptr(bias), _hip.ptr(out), ldy, M, N, a.K, _hip.stream_ptr(dev)), "lq_i8_gemm")
+    return out
+
+
 MX_ACTIVATIONS = (None, "relu")        # include/lq_hip.h: LQ_ACT_NONE, LQ_ACT_RELU
 
 

@@ -616,7 +616,52 @@ def build_parser():
                          "matrix instruction, their im2col operand gathered by ops.mx_operand_im2col) and add mx_eval_conv_layers, "
                          "mx_eval_conv_accuracy and mx_eval_conv_max_logit_diff (the model's outputs against the emulated path with "
                          "convs=True) to the result line")
+    ap.add_argument("--i8-eval", action="store_true",
+                    help="with --bits (a signed range of at most 8 bits): evaluate the final model once more under layers.i8_hardware "
+                         "(Dense layers on the int8 matrix instruction, activations quantised per row to 8-bit integers) and add "
+                         "i8_eval_accuracy, i8_eval_accuracy_emulated, i8_eval_accuracy_fake, i8_eval_max_logit_diff (against "
+                         "emulate=True: the same quantised activations times the fake-quantised weights with torch.matmul) and "
+                         "i8_eval_max_logit_diff_fake (against the fake-quantised model) to the result line")
+    ap.add_argument("--i8-eval-act-block", type=int, default=0, metavar="B",
+                    help="with --i8-eval: one activation scale per row and B consecutive inputs (a multiple of 64) instead of one per row")
     return ap
+
+
+@torch.no_grad()
+def i8_eval(model, x, y, act_block=0):
+    """One evaluation of ``model`` on (x, y) under layers.i8_hardware, one under its ``emulate=True`` yardstick and one of the
+    fake-quantised model as it stands: a dict of the three accuracies and the largest |difference| of the outputs of the last Dense
+    layer that took the path (the logits of the MNIST model) between the hardware path and each of the other two.  ValueError for
+    a model without a Dense layer that can take the path."""
+    was_training = model.training
+    model.eval()
+    acc, logits = [], []
+    try:
+        probe = L.i8_hardware(model, act_block)
+        last = ([m for m in L.custom_layers_of(model) if L.i8_hardware_eligible(m)] or [None])[-1]
+        if last is None:
+            raise ValueError("i8_eval: the model has no Dense layer that can run on the int8 matrix instruction (a signed range of at "
+                             "most 8 bits, symmetric, scalar / columnwise scales or groups of a multiple of 64 inputs)")
+        for how in ("hardware", "emulate", "fake"):
+            seen = []
+            hook = last.register_forward_hook(lambda m, i, o: seen.append(o.detach()))
+            try:
+                if how == "fake":
+                    p = model(x)
+                else:
+                    with L.i8_hardware(model, probe.act_block, emulate=how == "emulate") as hw:
+                        n_layers = len(hw.layers)
+                        p = model(x)
+            finally:
+                hook.remove()
+            acc.append(float((p.argmax(1) == y).float().mean()))
+            logits.append(seen[-1])
+    finally:
+        model.train(was_training)
+    return {"i8_eval_act_block": probe.act_block, "i8_eval_layers": n_layers, "i8_eval_accuracy": acc[0],
+            "i8_eval_accuracy_emulated": acc[1], "i8_eval_accuracy_fake": acc[2],
+            "i8_eval_max_logit_diff": float((logits[0] - logits[1]).abs().max()),
+            "i8_eval_max_logit_diff_fake": float((logits[0] - logits[2]).abs().max())}
 
 
 @torch.no_grad()
@@ -680,6 +725,11 @@ def main(argv=None):
         ap.error("--mx-eval-fused needs --mx-eval: it compares the fused Dense tail with the unfused hardware path")
     if args.mx_eval_convs and args.mx_eval is None:
         ap.error("--mx-eval-convs needs --mx-eval: it adds the conv layers to the hardware path that --mx-eval evaluates")
+    if args.i8_eval and (args.bits is None or args.bits > 8 or args.unsigned or args.asymmetric or args.element_format is not None):
+        ap.error("--i8-eval needs --bits of at most 8, signed and symmetric, and no --element-format: it runs the Dense layers of an "
+                 "integer model on the int8 matrix instruction")
+    if args.i8_eval_act_block and not args.i8_eval:
+        ap.error("--i8-eval-act-block needs --i8-eval")
     if args.quant_stats and args.bits is None:
         ap.error("--quant-stats needs --bits: the statistics are those of a quantizer with a range")
     if args.mx_stats and args.element_format is None:
@@ -748,6 +798,7 @@ def main(argv=None):
     quant_stats = L.quant_stats(tr.model) if args.quant_stats and rank == 0 else None      # after the clock has stopped
     mx_stats = L.mx_quant_stats(tr.model) if args.mx_stats and rank == 0 else None
     mx_eval_fields = mx_eval(tr.model, *batches[0], act_format=args.mx_eval, fused=args.mx_eval_fused, convs=args.mx_eval_convs) if args.mx_eval is not None and rank == 0 else None
+    i8_eval_fields = i8_eval(tr.model, *batches[0], act_block=args.i8_eval_act_block) if args.i8_eval and rank == 0 else None
     if rank == 0:
         n_q = sum(p.numel() for l in tr.custom_layers for p in l._regularized())
         print(json.dumps({
@@ -774,7 +825,7 @@ def main(argv=None):
             **({"loss_values": True, "loss_log_rows": log_rows[0], "loss_log_dropped": log_rows[1]} if log_rows else {}),
             **({"quant_stats": quant_stats} if quant_stats is not None else {}),
             **({"mx_stats": mx_stats} if mx_stats is not None else {}),
-            **(mx_eval_fields or {})}))
+            **(mx_eval_fields or {}), **(i8_eval_fields or {})}))
         if args.export_dir:
             from .export import save_compress_parameters
             print(json.dumps(save_compress_parameters(tr.model, args.export_dir)))

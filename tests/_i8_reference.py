@@ -181,6 +181,8 @@ PACK_CASES = [(70, 40, 0, 70), (160, 17, 0, 64), (9, 200, 1, 64), (9, 200, 1, 12
 PACK_RANGES = [(-128, 127), (-8, 7), (-7, 7)]
 QUANT_SHAPES = [(3, 70), (37, 784), (17, 320)]
 QUANT_BLOCKS = [0, 64, 128]
+LONG_QUANT_SHAPES = [(3, 4100), (2, 4160)]      # rows past the 4096 / 1024 elements a team keeps in registers, block == 0
+EXTRA_GEMM_KEYS = [(81, 70, 192, 64, 128), (129, 17, 128, 64, 64)]      # (M, N, K, a_block, b_block)
 
 
 def random_operand(rng, L, K, block):

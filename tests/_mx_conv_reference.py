@@ -11,7 +11,8 @@ import numpy as np
 import _mx_gemm_reference as G
 from _bounds import stable_seed
 
-Geom = namedtuple("Geom", "B C H W KH KW sh sw padding")      # padding: "SAME" (TensorFlow's, asymmetric where it is) or "VALID"
+# padding: "SAME" (TensorFlow's, asymmetric where it is), "VALID", or an explicit (top, bottom, left, right)
+Geom = namedtuple("Geom", "B C H W KH KW sh sw padding")
 
 # what each exercises: tests/test_gpu_mx_conv.py's docstring
 GEOMS = [
@@ -29,7 +30,8 @@ METHODS = ("mx", "cover")
 
 
 def geom_id(g):
-    return f"{g.B}x{g.C}x{g.H}x{g.W}-k{g.KH}x{g.KW}-s{g.sh}x{g.sw}-{g.padding.lower()}"
+    pad = g.padding.lower() if isinstance(g.padding, str) else "p" + ".".join(map(str, g.padding))
+    return f"{g.B}x{g.C}x{g.H}x{g.W}-k{g.KH}x{g.KW}-s{g.sh}x{g.sw}-{pad}"
 
 
 def same_padding(size, k, s):
@@ -41,6 +43,9 @@ def same_padding(size, k, s):
 
 def padding_of(g):
     """(top, bottom, left, right)."""
+    if not isinstance(g.padding, str):
+        top, bottom, left, right = (int(p) for p in g.padding)
+        return (top, bottom, left, right)
     if g.padding == "VALID":
         return (0, 0, 0, 0)
     return (*same_padding(g.H, g.KH, g.sh), *same_padding(g.W, g.KW, g.sw))

@@ -149,6 +149,9 @@ EXACT_SHAPES = [(16, 16, 128), (19, 21, 160), (37, 10, 784), (64, 48, 512), (81,
                 (17, 129, 160)]      # (M, N, K)
 EXACT_CASES = [(s, False) for s in EXACT_SHAPES] + [((19, 21, 160), True), ((81, 70, 160), True)]      # (shape, A is the identity pattern)
 RANDOM_SHAPES =[(37, 10, 784), (64, 48, 1024)]
+# the operand-out GEMM (M, N, K): what each exercises is in tests/test_gpu_mx_gemm_fused.py's docstring
+FUSED_BIG = (81, 70, 160)
+FUSED_SMALL = [(17, 33, 160), (16, 129, 160), (19, 513, 128), (129, 17, 160), (1, 1, 32)]
 # Exact sets.  Elements are 0, +-1, +-1.5, +-2 (on the grid of all three formats), block scales 2^-2 .. 2^3 per block and line:
 # a nonzero term |a b| sa sb lies in [2^-4, 2^8], a range of 2^12, and is a multiple of 2^-6.  A sum of K <= 1184 of them stays
 # far below 2^24 * 2^-6 = 2^18, so every partial sum in every order is a float32: tests/test_mx_gemm_cpu.py asserts it.

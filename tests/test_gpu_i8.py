@@ -150,7 +150,7 @@ def test_quantize_is_scale_init_then_forward(dev, shape, block):
 
 def test_quantize_rows_longer_than_the_register_cache(dev):
     """Rows of 4100 and 4160 elements: past the 4096 (16-byte loads) and 1024 (4-byte loads) a team keeps in registers."""
-    for M, K in ((3, 4100), (2, 4160)):
+    for M, K in G.LONG_QUANT_SHAPES:
         x = np.random.default_rng(K).normal(0.0, 1.0, (M, K)).astype(np.float32)
         x[0, K - 2] = 7.5                                  # the row's maximum lies in the tail
         for xd in (_t(x, dev), torch.empty(M * K + 1, device=dev)[1:].view(M, K).copy_(_t(x, dev))):
@@ -161,7 +161,7 @@ def test_quantize_rows_longer_than_the_register_cache(dev):
 
 # -------------------------------------------------------------------------------------------------------------- 4 gemm
 _GEMM_KEYS = [s + (0, 0) for s in G.GEMM_SHAPES] + [G.BLOCK_PAIR_SHAPE + p for p in G.BLOCK_PAIRS if p != (0, 0)] + \
-    [G.BLOCK_PAIR_SHAPE + (0, 0), (81, 70, 192, 64, 128), (129, 17, 128, 64, 64)]
+    [G.BLOCK_PAIR_SHAPE + (0, 0)] + G.EXTRA_GEMM_KEYS
 
 
 @pytest.mark.parametrize("key", _GEMM_KEYS, ids=_ids)

@@ -32,8 +32,7 @@ from learned_quantization_amd import _hip, layers as L, ops, train              
 pytestmark = pytest.mark.gpu
 NAMES = list(G.OPERAND_FORMATS)
 METHODS = ("mx", "cover")
-BIG = (81, 70, 160)
-SMALL = [(17, 33, 160), (16, 129, 160), (19, 513, 128), (129, 17, 160), (1, 1, 32)]
+BIG, SMALL = G.FUSED_BIG, G.FUSED_SMALL
 _ids = lambda d: "x".join(map(str, d)) if isinstance(d, tuple) else str(d)      # noqa: E731
 
 

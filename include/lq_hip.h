@@ -552,12 +552,31 @@ int lq_mx_operand_im2col(const float* X, const lq_conv_geom* g, int format, int 
  * LQ_EALIGN: codes or scales off the 16-byte grid; P, s, X, bias, out or Y off the 4-byte grid.  Each call only enqueues ONE launch
  * (capturable), allocates nothing, reads no environment, and writes exactly code_bytes and scale_bytes (pack, quantize), L * K
  * floats (decode) or the M x N elements of Y (gemm).
- * Not built: conv layers, an operand-out epilogue, asymmetric (offset) layers, any backward, sub-byte packing of 4-bit codes.  */
+ *
+ * lq_i8_operand_im2col: the A operand of a convolution run as an int8 GEMM, gathered from the input in one launch -- the im2col
+ * matrix never exists in fp32.  M, K, OH, OW and A[m][k] are exactly lq_mx_operand_im2col's (lq_mx_im2col_dims answers the
+ * extents): line m = (b * OH + oh) * OW + ow, k = (c * KH + i) * KW + j, +0 where the pixel does not exist.  codes / scales have
+ * lq_i8_operand_bytes(M, K, block) bytes and hold, byte for byte, what lq_i8_operand_quantize(A, M, K, block) writes, the padding
+ * of lines and of k and the scales of lines past M included: a (line, scale block) whose taps are all padding or all zero gets
+ * scale 2^-126 and codes 0; one whose taps cover a NaN or +-Inf pixel gets a NaN scale and codes 0, and no other pair does.  k is
+ * the memory order of the (ci, kh, kw) run of an OIHW kernel, so the B side is lq_i8_operand_pack(kernel, R = co,
+ * C = ci * kh * kw, axis 1) and lq_i8_gemm(A, B) is the convolution as [M][co].  X is addressed through its strides, given in
+ * ELEMENTS (NCHW-contiguous, channels_last or any view with non-negative strides), in 64-bit arithmetic, with 4-byte loads; no
+ * byte of X is read that the definition does not name.  A span (scale block, or the padded row for block == 0) of more than 64 k is
+ * split over the four waves of a thread block and merged through LDS; the result does not depend on the form.
+ * LQ_EINVAL before any launch: everything lq_mx_operand_im2col refuses about the geometry (a NULL pointer, a non-positive extent,
+ * kernel size or stride, a negative pad, OH or OW < 1, a negative stride of X) and everything lq_i8_operand_quantize refuses about
+ * M, K and block (M * K >= 2^31, a block that is negative or no multiple of 64).  LQ_EALIGN: codes or scales off the 16-byte grid, X
+ * off the 4-byte grid.  ONE launch (capturable), no memset, no atomics; allocates nothing, reads no environment and writes exactly
+ * code_bytes and scale_bytes.  Dilation and groups are not built.
+ * Not built: an operand-out epilogue, asymmetric (offset) layers, HWIO-stored conv kernels, any backward, sub-byte packing of
+ * 4-bit codes.  */
 int lq_i8_operand_bytes(int64_t L, int64_t K, int64_t block, size_t* code_bytes, size_t* scale_bytes);
 int lq_i8_operand_pack(const float* P, const float* s, int32_t qmin, int32_t qmax, int rounding, int64_t R, int64_t C, int axis,
                        int64_t gs, void* codes, void* scales, void* stream);
 int lq_i8_operand_quantize(const float* X, int64_t M, int64_t K, int64_t block, void* codes, void* scales, void* stream);
 int lq_i8_operand_decode(const void* codes, const void* scales, int64_t L, int64_t K, int64_t block, float* out, void* stream);
+int lq_i8_operand_im2col(const float* X, const lq_conv_geom* g, int64_t block, void* codes, void* scales, void* stream);
 int lq_i8_gemm(const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes, const void* b_scales, int64_t b_block,
                const float* bias /* may be NULL */, float* Y, int64_t ldy, int64_t M, int64_t N, int64_t K, void* stream);
 

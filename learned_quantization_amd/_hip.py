@@ -158,6 +158,7 @@ SIGNATURES.update({
     "lq_mx_im2col_dims": (_c_int, [ctypes.POINTER(ConvGeom), ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64),
                                    ctypes.POINTER(_c_i64)]),
     "lq_mx_operand_im2col": (_c_int, [_c_p, ctypes.POINTER(ConvGeom), _c_int, _c_int, _c_p, _c_p, _c_p]),
+    "lq_i8_operand_im2col": (_c_int, [_c_p, ctypes.POINTER(ConvGeom), _c_i64, _c_p, _c_p, _c_p]),
 })
 
 

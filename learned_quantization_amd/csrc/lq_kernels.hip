@@ -19,6 +19,7 @@
 //   lq_i8_operand.hpp   packed int8 operands with fp32 scales per line and scale block: pack, dynamic quantize, decode
 //   lq_i8_gemm.hpp      the GEMM of two packed int8 operands on v_mfma_i32_16x16x64_i8
 //   lq_mx_conv.hpp      the operand of a convolution's im2col matrix, gathered from the input in one launch
+//   lq_i8_conv.hpp      the int8 operand of the same matrix: absmax scales per (line, scale block), two passes over the gather
 //   this file           host side: traversal plan, launchers, the extern "C" entry points
 //
 // The path is elementwise + per-group reductions: HBM-bound, no MFMA.  Design rules
@@ -69,6 +70,7 @@
 #include "lq_mx_conv.hpp"
 #include "lq_i8_operand.hpp"
 #include "lq_i8_gemm.hpp"
+#include "lq_i8_conv.hpp"
 
 namespace lq {
 
@@ -2257,6 +2259,66 @@ int lq_i8_operand_quantize(const float* X, int64_t M, int64_t K, int64_t block, 
     if (v == 4) hipLaunchKernelGGL(k_i8_quantize<4>, grid, blk, 0, (hipStream_t)stream, op, log_team);
     else hipLaunchKernelGGL(k_i8_quantize<1>, grid, blk, 0, (hipStream_t)stream, op, log_team);
     return check_hip("int8 operand quantize");
+}
+
+// the launch form of lq_i8_operand_im2col (tests/_i8_conv_forms.py restates it): a span that one thread's registers hold takes the
+// plain form, a longer one is split over kI8ConvSlices slices -- whatever the number of lines: measured, the split form is never
+// slower and up to 2.4 times faster where the plain form had filled the device too
+static int i8_conv_slices(int64_t units) { return units > kI8ConvCache ? kI8ConvSlices : 1; }
+
+int lq_i8_operand_im2col(const float* X, const lq_conv_geom* g, int64_t block, void* codes, void* scales, void* stream) {
+    const char* fn = __func__;
+    LQ_REQUIRE_PTR_FN(fn, X);
+    ConvDims cd;
+    int rc = conv_geom_dims(fn, g, cd);
+    if (rc) return rc;
+    if (g->xs_b < 0 || g->xs_c < 0 || g->xs_h < 0 || g->xs_w < 0)
+        return fail(LQ_EINVAL, "%s: strides of X must not be negative (xs_b=%lld xs_c=%lld xs_h=%lld xs_w=%lld)", fn, (long long)g->xs_b,
+                    (long long)g->xs_c, (long long)g->xs_h, (long long)g->xs_w);
+    I8OperandDims d;
+    if ((rc = i8_operand_dims(fn, cd.M, cd.K, block, d))) return rc;      // M * K < 2^31, the block
+    if ((rc = check_i8_operand_buffers(fn, codes, scales))) return rc;
+    I8Im2colParams op{};
+    op.g.P = X;
+    op.g.lo = op.ip.lo = -127.0f;
+    op.g.hi = op.ip.hi = 127.0f;
+    op.ip.min_value = 1.17549435082228750797e-38f;      // 2^-126, as lq_i8_operand_quantize
+    op.codes = (uint8_t*)codes;
+    op.scales = (float*)scales;
+    op.xs_b = g->xs_b;
+    op.xs_c = g->xs_c;
+    op.xs_h = g->xs_h;
+    op.xs_w = g->xs_w;
+    op.H = g->H;
+    op.W = g->W;
+    // M * K < 2^31 bounds OH * OW, OW, KH * KW and KW: every divisor and dividend is a 32-bit number
+    op.ohow = make_fastdiv((uint32_t)(cd.OH * cd.OW));
+    op.ow = make_fastdiv((uint32_t)cd.OW);
+    op.khkw = make_fastdiv((uint32_t)((int64_t)g->KH * g->KW));
+    op.kw = make_fastdiv((uint32_t)g->KW);
+    op.KH = g->KH;
+    op.stride_h = g->stride_h;
+    op.stride_w = g->stride_w;
+    op.pad_top = g->pad_top;
+    op.pad_left = g->pad_left;
+    op.M = (int32_t)cd.M;
+    op.K = (int32_t)cd.K;
+    op.block = (int32_t)block;
+    op.nbs = (int32_t)d.nbs;
+    op.LT = (int32_t)d.LT;
+    op.KT = (int32_t)d.KT;
+    // the longest span in units: the first scale block, or the padded row
+    const int64_t lines = d.LT * kI8TileLines;
+    const int64_t units = (d.nbs > 1 ? block : d.KT * kI8TileK) / kI8ConvUnit;
+    const int slices = i8_conv_slices(units);
+    // a thread block is kBlock / slices consecutive lines of one scale block: chunks per scale block, scale blocks slowest
+    const int64_t per = kBlock / slices, chunks = (lines + per - 1) / per;
+    op.chunks = make_fastdiv((uint32_t)chunks);
+    const dim3 grid((unsigned)(chunks * d.nbs)), blk(kBlock);      // below 2^31: at most M K / 4096 + M / 64 + K / 64 + 1
+    hipStream_t st = (hipStream_t)stream;
+    if (slices == 1) hipLaunchKernelGGL(k_i8_im2col<1>, grid, blk, 0, st, op);
+    else hipLaunchKernelGGL(k_i8_im2col<kI8ConvSlices>, grid, blk, 0, st, op);
+    return check_hip("int8 im2col operand");
 }
 
 int lq_i8_operand_decode(const void* codes, const void* scales, int64_t L, int64_t K, int64_t block, float* out, void* stream) {

@@ -892,6 +892,10 @@ class _ConvBase(_HostLayer):
         if hw is not None and not self.training:                  # inside layers.mx_hardware(..., convs=True), eval mode
             self._q_pre = None                                    # a batch's fake-quantised pair is not what this path multiplies
             return self._mx_conv(inputs, *hw)
+        hw = getattr(self, "_i8_hw", None)
+        if hw is not None and not self.training:                  # inside layers.i8_hardware(..., convs=True), eval mode
+            self._q_pre = None
+            return self._i8_conv(inputs, *hw)
         x = inputs.permute(0, 3, 1, 2) if self.data_format == "NHWC" else inputs
         w, qb = self.quantized_parameters()
         if self.padding == "SAME":
@@ -972,6 +976,77 @@ class _ConvBase(_HostLayer):
             operand = self.mx_operand()
             qb = self.nested_q_b_layer(self.b) if self._has_bias else None
             return self._mx_conv(inputs, operand, qb, act_format, act_scale, max_lines)
+
+
+    def _check_i8(self):
+        """(qmin, qmax) of a conv layer that can run on the int8 matrix instruction, or ValueError naming the reason."""
+        fan_in = self.kernel.shape[0] * self.kernel.shape[1] * self.kernel.shape[2] if self.built else None
+        q_range = ops.check_i8_conv_operand_layer(self.q_range, self.nested_q_k_layer.orientation, self.group_size, self.asymmetric,
+                                                  self.element_format, fan_in, self.kernel_storage)
+        if not self.built:
+            raise ValueError(f"{self.name}: the layer is not built yet (no kernel to pack)")
+        return q_range
+
+    def i8_operand(self) -> "ops.I8Operand":
+        """The kernel under its current scales as an operand of the int8 matrix instruction (ops.i8_operand_pack, groups along the
+        contiguous axis): ``filters`` lines over K = ci kh kw, the reduction order of ops.i8_operand_im2col.  A "groupwise" layer
+        passes its scale as it is; a "scalar" layer its scale broadcast to ``(filters, 1)``, one group per output channel.
+        ValueError naming the reason for a one-axis orientation, ``kernel_storage="hwio"``, a layer without a range, with a range
+        outside [-128, 127], with an offset, with an element format, or not built."""
+        qmin, qmax = self._check_i8()
+        K = self.kernel.numel() // self.filters
+        scale = self.nested_q_k_layer.scale.data
+        if self.nested_q_k_layer.orientation == "groupwise":
+            gs = self.group_size
+        else:
+            scale, gs = scale.reshape(1, 1).expand(self.filters, 1).contiguous(), K
+        return ops.i8_operand_pack(self.kernel.detach(), scale, qmin, qmax, gs, self.rounding)
+
+    def _i8_conv(self, inputs, operand, qb, act_block, max_lines=None):
+        with torch.no_grad():
+            if inputs.dim() != 4:
+                raise ValueError(f"{self.name}: the input must have four axes, got shape {tuple(inputs.shape)}")
+            x = inputs.permute(0, 3, 1, 2) if self.data_format == "NHWC" else inputs       # a view: the operand reads its strides
+            padding = self._mx_padding(x.shape[2], x.shape[3])
+            M, K, OH, OW = ops.mx_im2col_dims(x.shape, self.kernel_size, self.strides, padding)
+            B, per = x.shape[0], OH * OW
+            # runs of whole images whose operand the C surface takes (M K < 2^31), that the GEMM's grid takes (65535 * 64 lines)
+            # and that hold at most max_lines lines
+            fit = min(((1 << 31) - 1) // K, 65535 * 64)
+            if max_lines is not None:
+                fit = min(fit, int(max_lines))
+            images = max(1, min(B, fit // per))
+            y = torch.empty((M, self.filters), dtype=torch.float32, device=x.device)
+            for b0 in range(0, B, images):
+                b1 = min(B, b0 + images)
+                a = ops.i8_operand_im2col(x[b0:b1], self.kernel_size, self.strides, padding, act_block)
+                rows = y[b0 * per:b1 * per]
+                if isinstance(operand, torch.Tensor):             # i8_hardware(emulate=True): the fake-quantised kernel (K, co)
+                    torch.matmul(ops.i8_operand_decode(a), operand, out=rows)
+                    if qb is not None:
+                        rows.add_(qb)
+                else:
+                    ops.i8_gemm(a, operand, qb, out=rows)
+            y = y.view(B, OH, OW, self.filters)                   # the GEMM's [M][co] is NHWC: no transposition launch
+            return y if self.data_format == "NHWC" else y.permute(0, 3, 1, 2)
+
+    def call_i8(self, inputs, act_block=0, max_lines=None):
+        """The layer on the int8 matrix instruction, under ``no_grad``: the im2col matrix of the inputs quantised per line and
+        ``act_block`` consecutive k of (ci, kh, kw) (0: per line) to symmetric 8-bit integers by ops.i8_operand_im2col -- TensorFlow
+        'SAME' padding as ``call`` pads, or 'VALID' -- multiplied with ``i8_operand()`` by ops.i8_gemm, plus the fake-quantised bias
+        where the layer has one.  Inference only: there is no backward through this path.  The result is a view of the GEMM's
+        (M, co) matrix: ``(B, co, OH, OW)`` with channels-last strides for ``data_format="NCHW"``, ``(B, OH, OW, co)`` for "NHWC".  A
+        batch whose im2col matrix has 2^31 elements or more, more than 65535 * 64 lines or more than ``max_lines`` lines is cut into
+        runs of whole images that write their rows of the one result; the result does not depend on the cut."""
+        if max_lines is not None and (not isinstance(max_lines, int) or isinstance(max_lines, bool) or max_lines < 1):
+            raise ValueError(f"max_lines must be a positive integer or None, got {max_lines!r}")
+        ops.check_i8_block(act_block)
+        if not self.built:
+            self.build(tuple(inputs.shape), device=inputs.device)
+        with torch.no_grad():
+            operand = self.i8_operand()
+            qb = self.nested_q_b_layer(self.b) if self._has_bias else None
+            return self._i8_conv(inputs, operand, qb, act_block, max_lines)
 
 
 class CustomConv2DLayer(_ConvBase):
@@ -1065,8 +1140,21 @@ class mx_hardware:
 def i8_hardware_eligible(layer: nn.Module) -> bool:
     """Whether ``layer`` takes the int8 GEMM under ``i8_hardware``: a built Dense layer with a range inside [-128, 127], symmetric,
     with scalar, columnwise or groupwise scales (group size a multiple of 64, or the whole input) and no element format.  Conv
-    layers keep the fake-quantised path."""
+    layers are judged by ``i8_conv_eligible``."""
     if not isinstance(layer, CustomDenseLayer):
+        return False
+    try:
+        layer._check_i8()
+    except ValueError:
+        return False
+    return True
+
+
+def i8_conv_eligible(layer: nn.Module) -> bool:
+    """Whether ``layer`` takes the int8 GEMM under ``i8_hardware(convs=True)``: a built conv layer with a range inside
+    [-128, 127], symmetric, with a scalar scale or groupwise scales (group size a multiple of 64, or at least ci kh kw), no
+    element format and the kernel stored "oihw" (the groups then run along the im2col operand's K)."""
+    if not isinstance(layer, _ConvBase):
         return False
     try:
         layer._check_i8()
@@ -1081,10 +1169,17 @@ class i8_hardware:
     integers, the product on the int8 matrix instruction.  The operands and the fake-quantised biases are built ONCE, on entry,
     from the scales the layers have then; training-mode calls and every other layer keep the fake-quantised path.  ``layers`` lists
     the layers that switched.  ``emulate=True`` is the yardstick of that path in stock arithmetic: the same quantised activations,
-    decoded, times the fake-quantised kernel with ``torch.matmul`` in fp32."""
+    decoded, times the fake-quantised kernel with ``torch.matmul`` in fp32.
+    ``convs=True``: every conv layer that can (``i8_conv_eligible``) switches its eval-mode ``call`` too, to what its ``call_i8``
+    does -- the im2col operand of its input gathered and quantised in one launch (ops.i8_operand_im2col), times the kernel's
+    operand, plus the fake-quantised bias; the result is a channels-last view for ``data_format="NCHW"``.  Operand and bias are
+    built once, on entry, and the layer is listed in ``layers`` after the Dense layers.  Under ``emulate=True`` such a layer
+    multiplies the decoded im2col operand with the fake-quantised kernel as a (K, co) matrix by ``torch.matmul`` instead.  Without
+    ``convs`` (the default) conv layers keep the fake-quantised path."""
 
-    def __init__(self, model: nn.Module, act_block=0, emulate=False):
+    def __init__(self, model: nn.Module, act_block=0, emulate=False, convs=False):
         self.model, self.act_block, self.emulate = model, ops.check_i8_block(act_block), bool(emulate)
+        self.convs = bool(convs)
         self.layers = []
 
     def __enter__(self):
@@ -1093,6 +1188,12 @@ class i8_hardware:
             for m in self.layers:
                 weight = m.nested_q_w_layer(m.W).detach() if self.emulate else m.i8_operand()
                 m._i8_hw = (weight, m.nested_q_b_layer(m.b).detach(), self.act_block)
+            for m in [m for m in custom_layers_of(self.model) if i8_conv_eligible(m)] if self.convs else []:
+                # emulate: the fake-quantised kernel as the (K, co) matrix the decoded im2col operand multiplies
+                weight = m.nested_q_k_layer(m.kernel).detach().permute(3, 2, 0, 1).reshape(m.filters, -1).t() if self.emulate \
+                    else m.i8_operand()
+                m._i8_hw = (weight, m.nested_q_b_layer(m.b).detach() if m._has_bias else None, self.act_block)
+                self.layers.append(m)
         return self
 
     def __exit__(self, *exc):

@@ -660,6 +660,28 @@ def check_i8_operand_layer(q_range, orientation, group_size=None, asymmetric=Fal
     return qmin, qmax
 
 
+def check_i8_conv_operand_layer(q_range, orientation, group_size=None, asymmetric=False, element_format=None, fan_in=None,
+                                kernel_storage="oihw") -> Tuple[int, int]:
+    """What a conv layer's quantizer must be to run on the int8 matrix instruction -- (qmin, qmax) -- or ValueError naming the
+    reason.  ``fan_in`` is ci kh kw, the K of the im2col operand.  A conv kernel is HWIO-shaped, so "rowwise", "columnwise" and
+    "channelwise" put the scale on kh, kw and ci: it varies along K inside a step of the instruction -- the Dense check's
+    acceptance of "columnwise" does not carry over.  Eligible: "scalar", and "groupwise" with a group size that is a multiple of 64
+    or at least ``fan_in`` (one scale per output channel)."""
+    # range, offset and element format first, as the Dense check words them; the orientation is judged here
+    qmin, qmax = check_i8_operand_layer(q_range, "groupwise" if orientation == "groupwise" else "scalar", group_size, asymmetric,
+                                        element_format, fan_in)
+    if orientation in ("rowwise", "columnwise", "channelwise"):
+        axis = {"rowwise": "kh", "columnwise": "kw", "channelwise": "ci"}[orientation]
+        raise ValueError(f'orientation="{orientation}": on an HWIO-shaped conv kernel the scale lies on {axis} and varies along '
+                         "K = (ci, kh, kw) inside a step of the instruction")
+    if orientation not in ("scalar", "groupwise"):
+        raise ValueError(f"orientation={orientation!r}: the int8 GEMM of a conv layer takes scalar or groupwise scales")
+    if kernel_storage != "oihw":
+        raise ValueError(f'kernel_storage="{kernel_storage}": the int8 GEMM reduces over the (ci, kh, kw) memory run of a kernel '
+                         'stored "oihw"')
+    return qmin, qmax
+
+
 def i8_operand_bytes(lines: int, K: int, block: int = 0) -> Tuple[int, int]:
     """(code_bytes, scale_bytes) of an operand (include/lq_hip.h, lq_i8_operand_bytes).  Needs no device."""
     import ctypes
@@ -857,6 +879,40 @@ def mx_operand_im2col(x: torch.Tensor, kernel_size, strides=(1, 1), padding=(0, 
     _hip.check(lib.lq_mx_operand_im2col(_hip.ptr(x), ctypes.byref(g), fmt.id, m, _hip.ptr(codes), _hip.ptr(scales),
                                         _hip.stream_ptr(x.device)), "lq_mx_operand_im2col")
     op = MxConvOperand(codes, scales, element_format, M, K)
+    op.out_hw = (OH, OW)
+    return op
+
+
+class I8ConvOperand(I8Operand):
+    """The I8Operand of an im2col matrix (``i8_operand_im2col``): the same five fields, and ``out_hw = (OH, OW)`` of the convolution
+    whose ``lines = B * OH * OW`` it holds."""
+    out_hw: Tuple[int, int] = (0, 0)
+
+
+def i8_operand_im2col(x: torch.Tensor, kernel_size, strides=(1, 1), padding=(0, 0, 0, 0), block: int = 0) -> I8Operand:
+    """The int8 operand of the im2col matrix of ``x (B, C, H, W)`` -- line ``(b OH + oh) OW + ow``, reduction index
+    ``(c KH + i) KW + j``, zero ``padding`` (top, bottom, left, right) -- under absmax scales taken from it per line and ``block``
+    consecutive k (0: per line) (include/lq_hip.h, lq_i8_operand_im2col): byte for byte ``i8_operand_quantize`` of that matrix,
+    which is never built.  ``x`` is read through its own strides (NCHW-contiguous, channels_last or any view): no copy.  One launch.
+    The result is an I8Operand whose ``out_hw`` is ``(OH, OW)``."""
+    import ctypes
+    block = check_i8_block(block)
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError(f"x must have four axes (B, C, H, W), got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
+    if not x.is_cuda:
+        raise RuntimeError(f"x is on {x.device}: the learned-quantization ops run only on a HIP device (MI355X); there is no CPU fallback")
+    if x.dtype != torch.float32:
+        raise TypeError(f"x must be float32, got {x.dtype}")
+    if x.device.index is not None and x.device.index != torch.cuda.current_device():
+        raise RuntimeError(f"x lives on {x.device} but the current device is cuda:{torch.cuda.current_device()}: call "
+                           "torch.cuda.set_device(...) before using the ops")
+    lib = _hip.load()
+    g = _conv_geom(x.shape, x.stride(), kernel_size, strides, padding)
+    M, K, OH, OW = mx_im2col_dims(x.shape, kernel_size, strides, padding)
+    codes, scales = _i8_operand_buffers(M, K, block, x.device)
+    _hip.check(lib.lq_i8_operand_im2col(_hip.ptr(x), ctypes.byref(g), block, _hip.ptr(codes), _hip.ptr(scales),
+                                        _hip.stream_ptr(x.device)), "lq_i8_operand_im2col")
+    op = I8ConvOperand(codes, scales, M, K, block)
     op.out_hw = (OH, OW)
     return op
 

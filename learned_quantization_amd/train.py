@@ -624,21 +624,30 @@ def build_parser():
                          "i8_eval_max_logit_diff_fake (against the fake-quantised model) to the result line")
     ap.add_argument("--i8-eval-act-block", type=int, default=0, metavar="B",
                     help="with --i8-eval: one activation scale per row and B consecutive inputs (a multiple of 64) instead of one per row")
+    ap.add_argument("--i8-eval-convs", action="store_true",
+                    help="with --i8-eval: evaluate once more under layers.i8_hardware(convs=True) (conv layers too on the int8 matrix "
+                         "instruction, their im2col operand gathered by ops.i8_operand_im2col) and add i8_eval_conv_layers, "
+                         "i8_eval_conv_accuracy and i8_eval_conv_max_logit_diff (the model's outputs against the emulated path with "
+                         "convs=True) to the result line")
     return ap
 
 
 @torch.no_grad()
-def i8_eval(model, x, y, act_block=0):
+def i8_eval(model, x, y, act_block=0, convs=False):
     """One evaluation of ``model`` on (x, y) under layers.i8_hardware, one under its ``emulate=True`` yardstick and one of the
     fake-quantised model as it stands: a dict of the three accuracies and the largest |difference| of the outputs of the last Dense
     layer that took the path (the logits of the MNIST model) between the hardware path and each of the other two.  ValueError for
-    a model without a Dense layer that can take the path."""
+    a model without a Dense layer that can take the path.  ``convs=True`` adds an evaluation under ``i8_hardware(convs=True)`` and one
+    under its emulation: the number of conv layers that took the path, the accuracy, and the largest |difference| of the model's
+    outputs between the two; a model without such a Dense layer is then accepted, and its Dense fields are those of the model's
+    own output with no layer switched."""
     was_training = model.training
     model.eval()
     acc, logits = [], []
+    fields = {}
     try:
         probe = L.i8_hardware(model, act_block)
-        last = ([m for m in L.custom_layers_of(model) if L.i8_hardware_eligible(m)] or [None])[-1]
+        last = ([m for m in L.custom_layers_of(model) if L.i8_hardware_eligible(m)] or [model if convs else None])[-1]
         if last is None:
             raise ValueError("i8_eval: the model has no Dense layer that can run on the int8 matrix instruction (a signed range of at "
                              "most 8 bits, symmetric, scalar / columnwise scales or groups of a multiple of 64 inputs)")
@@ -656,12 +665,24 @@ def i8_eval(model, x, y, act_block=0):
                 hook.remove()
             acc.append(float((p.argmax(1) == y).float().mean()))
             logits.append(seen[-1])
+        if convs:
+            outs = []
+            for emulate in (False, True):
+                with L.i8_hardware(model, probe.act_block, emulate=emulate, convs=True) as hwc:
+                    n_convs = sum(L.i8_conv_eligible(m) for m in hwc.layers)
+                    if not n_convs:
+                        raise ValueError("i8_eval: convs=True needs a model with a conv layer that can run on the int8 matrix "
+                                         "instruction (a signed range of at most 8 bits, symmetric, a scalar scale or groups of a "
+                                         "multiple of 64 along (ci, kh, kw), kernel stored oihw)")
+                    outs.append(model(x))
+            fields = {"i8_eval_conv_layers": n_convs, "i8_eval_conv_accuracy": float((outs[0].argmax(1) == y).float().mean()),
+                      "i8_eval_conv_max_logit_diff": float((outs[0] - outs[1]).abs().max())}
     finally:
         model.train(was_training)
     return {"i8_eval_act_block": probe.act_block, "i8_eval_layers": n_layers, "i8_eval_accuracy": acc[0],
             "i8_eval_accuracy_emulated": acc[1], "i8_eval_accuracy_fake": acc[2],
             "i8_eval_max_logit_diff": float((logits[0] - logits[1]).abs().max()),
-            "i8_eval_max_logit_diff_fake": float((logits[0] - logits[2]).abs().max())}
+            "i8_eval_max_logit_diff_fake": float((logits[0] - logits[2]).abs().max()), **fields}
 
 
 @torch.no_grad()
@@ -730,6 +751,8 @@ def main(argv=None):
                  "integer model on the int8 matrix instruction")
     if args.i8_eval_act_block and not args.i8_eval:
         ap.error("--i8-eval-act-block needs --i8-eval")
+    if args.i8_eval_convs and not args.i8_eval:
+        ap.error("--i8-eval-convs needs --i8-eval: it adds the conv layers to the hardware path that --i8-eval evaluates")
     if args.quant_stats and args.bits is None:
         ap.error("--quant-stats needs --bits: the statistics are those of a quantizer with a range")
     if args.mx_stats and args.element_format is None:
@@ -798,7 +821,7 @@ def main(argv=None):
     quant_stats = L.quant_stats(tr.model) if args.quant_stats and rank == 0 else None      # after the clock has stopped
     mx_stats = L.mx_quant_stats(tr.model) if args.mx_stats and rank == 0 else None
     mx_eval_fields = mx_eval(tr.model, *batches[0], act_format=args.mx_eval, fused=args.mx_eval_fused, convs=args.mx_eval_convs) if args.mx_eval is not None and rank == 0 else None
-    i8_eval_fields = i8_eval(tr.model, *batches[0], act_block=args.i8_eval_act_block) if args.i8_eval and rank == 0 else None
+    i8_eval_fields = i8_eval(tr.model, *batches[0], act_block=args.i8_eval_act_block, convs=args.i8_eval_convs) if args.i8_eval and rank == 0 else None
     if rank == 0:
         n_q = sum(p.numel() for l in tr.custom_layers for p in l._regularized())
         print(json.dumps({

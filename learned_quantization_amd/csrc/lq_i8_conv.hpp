@@ -5,26 +5,25 @@
 // operand of A is what lq_i8_operand_quantize(A, M, K, block) writes (lq_i8_operand.hpp: the layout, i8_code_offset): one fp32
 // absmax scale per (line, scale block) -- the whole row for block == 0 -- and the clipped nearest-even codes under it.
 //
-// The gather of k_mx_im2col around the scale rule and element step of k_i8_quantize.  Lines lie along the lanes: a thread block
-// is kBlock / S consecutive lines of ONE scale block, so (c, i, j) of every tap is uniform over a wave (scalar registers), a wave's
-// load of one tap of an NCHW input at stride 1 is one contiguous run, and the 16-byte code stores of 16 neighbouring lines are
-// contiguous 256 B.  A UNIT is 16 consecutive k from a multiple of 16: one 16-byte fragment of a line.  The span of a work item
+// The gather of lq_im2col.hpp, which k_mx_im2col shares, around the scale rule and element step of k_i8_quantize.  Lines lie
+// along the lanes: a thread block is kBlock / S consecutive lines of ONE scale block, so (c, i, j) of every tap is uniform over a
+// wave (scalar registers), a wave's load of one tap of an NCHW input at stride 1 is one contiguous run, and the 16-byte code
+// stores of 16 neighbouring lines are contiguous 256 B.  A UNIT is 16 consecutive k from a multiple of 16: one 16-byte fragment of a line.  The span of a work item
 // (line, scale block) is cut into units, and S SLICES -- the S waves of the thread block -- take the units s, s + S, ...:
 // with one scale per row a late-network shape has few lines and a long row, and one thread per line would leave the device idle.
 // Two passes: maxima, then codes.  A slice keeps its first kI8ConvCache units (16 floats each) in registers between them and
 // gathers the rest a second time, from the cache hierarchy.  The host launches the plain form (S == 1) only for spans of at most
 // kI8ConvCache units -- one K step of the instruction --, so that form has no second gather.  The slices' absmax partials are two maxima and an OR, merged through
 // LDS by every thread for its own line: order-free, therefore exact.  The last scale block of a line writes the k padding up to
-// 64 KT; lines past M up to 16 LT get codes 0 and scale 1.0f; slice 0 writes the scale.  Every load is predicated -- zero outside
-// the image and past K, and no address is formed into a load unless the definition names it -- and addressed in int64 through the
-// strides of X.  The arithmetic is called, not restated: init_take / init_merge / init_raw / init_final, GroupStep<true,
-// GroupParams>, div_by_uniform, i8_view_byte.  The few lines around them are copied from k_i8_quantize and k_mx_im2col instead of
-// shared with them, so that their instruction streams stay what they were (the precedent is mx_gemm_accumulate).  No scratch, no
-// atomics.
+// 64 KT; lines past M up to 16 LT get codes 0 and scale 1.0f; slice 0 writes the scale.  Geometry, window and the predicated
+// loads are lq_im2col.hpp's.  The arithmetic is called, not restated: init_take / init_merge / init_raw / init_final, GroupStep<true,
+// GroupParams>, div_by_uniform, i8_view_byte.  The few lines around them repeat k_i8_quantize's: that kernel walks a row with a
+// team of lanes, this one a window with one lane per line, and k_i8_quantize's instruction streams are pinned ("One
+// im2col gather").  No scratch, no atomics.
 #ifndef LQ_I8_CONV_HPP_
 #define LQ_I8_CONV_HPP_
-#include "lq_fastdiv.hpp"
 #include "lq_i8_operand.hpp"
+#include "lq_im2col.hpp"
 
 namespace lq {
 
@@ -37,42 +36,10 @@ struct I8Im2colParams {
     InitParams ip;            // lo, hi, min_value
     uint8_t* codes;
     float* scales;
-    int64_t xs_b, xs_c, xs_h, xs_w;       // of X, in elements
-    int64_t H, W;
-    FastDiv ohow, ow;         // m -> (b, oh, ow)
-    FastDiv khkw, kw;         // k -> (c, i, j)
-    FastDiv chunks;           // blockIdx.x -> (scale block, chunk of kBlock / S lines)
-    int32_t KH, stride_h, stride_w, pad_top, pad_left;
-    int32_t M, K, block;      // block == 0: one scale per line
+    Im2colGeom geom;          // geom.M lines; geom.chunks: blockIdx.x -> (scale block, chunk of kBlock / S lines)
+    int32_t K, block;         // block == 0: one scale per line
     int32_t nbs, LT, KT;
 };
-
-// the window of one line: the corner's coordinates and its offset in X (which may lie outside X: it is never loaded from)
-struct I8ConvWindow {
-    int64_t ih0, iw0, base;
-};
-
-// 16 taps from k0 (a multiple of 16, uniform over the wave) of the line whose window is w; taps at or past k1 and outside the
-// image are +0
-__device__ __forceinline__ void i8_conv_gather(const I8Im2colParams& op, const I8ConvWindow& w, int32_t k0, int32_t k1,
-                                               float (&x)[kI8ConvUnit]) {
-    const int n = min(kI8ConvUnit, k1 - k0);
-    uint32_t c = fd_div(op.khkw, (uint32_t)k0);
-    const uint32_t rk = (uint32_t)k0 - c * op.khkw.d;
-    uint32_t i = fd_div(op.kw, rk), j = rk - i * op.kw.d;
-    const float* X = op.g.P;
-#pragma unroll
-    for (int e = 0; e < kI8ConvUnit; ++e) {
-        const int64_t ih = w.ih0 + i, iw = w.iw0 + j;
-        const bool in = e < n && (uint64_t)ih < (uint64_t)op.H && (uint64_t)iw < (uint64_t)op.W;
-        x[e] = 0.f;
-        if (in) x[e] = X[w.base + (int64_t)c * op.xs_c + (int64_t)i * op.xs_h + (int64_t)j * op.xs_w];
-        if (++j == op.kw.d) {
-            j = 0u;
-            if (++i == (uint32_t)op.KH) { i = 0u; ++c; }
-        }
-    }
-}
 
 // S slices of kBlock / S lines each.  S == 1: a thread owns its (line, scale block), whose span is at most kI8ConvCache units;
 // S == kI8ConvSlices: a wave per slice
@@ -81,13 +48,13 @@ __global__ __launch_bounds__(kBlock) void k_i8_im2col(const I8Im2colParams op) {
     using Step = GroupStep<true, GroupParams>;
     constexpr int kLines = kBlock / S;
     static_assert(S == 1 || kLines == 64, "a slice is one wave: its units are wave-uniform");
-    const int32_t sb = (int32_t)fd_div(op.chunks, blockIdx.x);                         // uniform over the block
+    const int32_t sb = (int32_t)fd_div(op.geom.chunks, blockIdx.x);                    // uniform over the block
     const int32_t slice = S == 1 ? 0 : __builtin_amdgcn_readfirstlane((int32_t)(threadIdx.x / kLines));
     const int64_t lines = (int64_t)op.LT * kI8TileLines;
-    const int64_t line = (int64_t)(blockIdx.x - (uint32_t)sb * op.chunks.d) * kLines + (threadIdx.x % kLines);
+    const int64_t line = (int64_t)(blockIdx.x - (uint32_t)sb * op.geom.chunks.d) * kLines + (threadIdx.x % kLines);
     const bool valid = line < lines;          // no early return: the split form meets at a barrier
     const int32_t ln = (int32_t)line;
-    const bool live = valid && ln < op.M;
+    const bool live = valid && ln < op.geom.M;
     const int32_t span = op.block ? op.block : op.K;
     const int32_t c0 = sb * span;                                         // < K: nbs = ceil(K / block)
     const int32_t c1 = min(c0 + span, op.K);                              // elements read
@@ -95,15 +62,8 @@ __global__ __launch_bounds__(kBlock) void k_i8_im2col(const I8Im2colParams op) {
     // in units from c0, so that no index past the span is ever formed: those read (rounded up) and those written
     const int32_t nu1 = (c1 - c0 + kI8ConvUnit - 1) / kI8ConvUnit, nus = (c1s - c0) / kI8ConvUnit;
 
-    I8ConvWindow w{0, 0, 0};
-    if (live) {
-        const uint32_t b = fd_div(op.ohow, (uint32_t)ln), r = (uint32_t)ln - b * op.ohow.d;
-        const uint32_t oh = fd_div(op.ow, r), ow = r - oh * op.ow.d;
-        w.ih0 = (int64_t)oh * op.stride_h - op.pad_top;
-        w.iw0 = (int64_t)ow * op.stride_w - op.pad_left;
-        w.base = (int64_t)b * op.xs_b + w.ih0 * op.xs_h + w.iw0 * op.xs_w;
-    }
-
+    Im2colWindow w{0, 0, 0};
+    if (live) w = im2col_window(op.geom, ln);
     float x[kI8ConvCache][kI8ConvUnit];
     InitAcc a{0.f, 0.f, 0.0, 0u};             // the zeros of the padding and past c1 change neither maximum
 #pragma unroll
@@ -112,7 +72,8 @@ __global__ __launch_bounds__(kBlock) void k_i8_im2col(const I8Im2colParams op) {
         for (int e = 0; e < kI8ConvUnit; ++e) x[it][e] = 0.f;
         if (slice + it * S >= nu1) continue;  // wave-uniform
         if (live) {
-            i8_conv_gather(op, w, c0 + (slice + it * S) * kI8ConvUnit, c1, x[it]);
+            const int32_t k0 = c0 + (slice + it * S) * kI8ConvUnit;      // taps at or past c1 are +0
+            im2col_gather(op.geom, op.g.P, w, (uint32_t)k0, c1 - k0, x[it]);
 #pragma unroll
             for (int e = 0; e < kI8ConvUnit; ++e) init_take<LQ_INIT_ABSMAX>(x[it][e], a);
         }
@@ -121,7 +82,8 @@ __global__ __launch_bounds__(kBlock) void k_i8_im2col(const I8Im2colParams op) {
         for (int32_t u = slice + kI8ConvCache * S; u < nu1; u += S) {      // what the registers do not hold
             if (live) {
                 float t[kI8ConvUnit];
-                i8_conv_gather(op, w, c0 + u * kI8ConvUnit, c1, t);
+                const int32_t k0 = c0 + u * kI8ConvUnit;
+                im2col_gather(op.geom, op.g.P, w, (uint32_t)k0, c1 - k0, t);
 #pragma unroll
                 for (int e = 0; e < kI8ConvUnit; ++e) init_take<LQ_INIT_ABSMAX>(t[e], a);
             }
@@ -165,7 +127,7 @@ __global__ __launch_bounds__(kBlock) void k_i8_im2col(const I8Im2colParams op) {
             float t[kI8ConvUnit];
 #pragma unroll
             for (int e = 0; e < kI8ConvUnit; ++e) t[e] = 0.f;
-            if (k0 < c1l) i8_conv_gather(op, w, k0, c1, t);
+            if (k0 < c1l) im2col_gather(op.geom, op.g.P, w, (uint32_t)k0, c1 - k0, t);
             emit(k0, t);
         }
     }

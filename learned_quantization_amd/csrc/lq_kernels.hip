@@ -18,7 +18,8 @@
 //   lq_mx_gemm.hpp      the GEMM of two packed operands on v_mfma_scale_f32_16x16x128_f8f6f4
 //   lq_i8_operand.hpp   packed int8 operands with fp32 scales per line and scale block: pack, dynamic quantize, decode
 //   lq_i8_gemm.hpp      the GEMM of two packed int8 operands on v_mfma_i32_16x16x64_i8
-//   lq_mx_conv.hpp      the operand of a convolution's im2col matrix, gathered from the input in one launch
+//   lq_im2col.hpp       a convolution's im2col matrix without the matrix: geometry, a line's window, the predicated gather
+//   lq_mx_conv.hpp      the MX operand of that matrix, gathered from the input in one launch
 //   lq_i8_conv.hpp      the int8 operand of the same matrix: absmax scales per (line, scale block), two passes over the gather
 //   this file           host side: traversal plan, launchers, the extern "C" entry points
 //
@@ -1786,6 +1787,40 @@ int lq_mx_stats(const float* P, const float* s, int format, int scale_format, ui
                              (size_t)sp.nbins * sizeof(uint32_t));
 }
 
+// ---- the matrix path: what the MX and the int8 family share on the host ----
+// 2^-126, the floor of every scale an operand quantizer takes from its data: the smallest an E8M0 byte of s_eff can hold
+constexpr float kOperandMinScale = 1.17549435082228750797e-38f;
+// what the GEMMs read the scales as: an MX operand's bytes as words, an int8 operand's floats as float4
+constexpr int kMxScaleAlign = 4, kI8ScaleAlign = 16;
+
+static int check_operand_buffers(const char* fn, const void* codes, const void* scales, int scale_align) {
+    if (!codes || !scales) return fail(LQ_EINVAL, "%s: argument '%s' is NULL", fn, codes ? "scales" : "codes");
+    if (!aligned(codes, 16)) return fail(LQ_EALIGN, "%s: codes is not 16-byte aligned", fn);
+    if (!aligned(scales, scale_align)) return fail(LQ_EALIGN, "%s: scales is not %d-byte aligned", fn, scale_align);
+    return LQ_OK;
+}
+
+static int check_gemm_bias(const char* fn, const float* bias) {
+    return bias && !aligned(bias, 4) ? fail(LQ_EALIGN, "%s: bias is not 4-byte aligned", fn) : LQ_OK;
+}
+
+// Y (M, N) in fp32 with leading dimension ldy, and the optional bias
+static int check_gemm_output(const char* fn, const float* bias, const float* Y, int64_t ldy, int64_t M, int64_t N) {
+    LQ_REQUIRE_PTR_FN(fn, Y);
+    if (int rc = check_gemm_bias(fn, bias)) return rc;
+    if (ldy < N) return fail(LQ_EINVAL, "%s: ldy = %lld is below N = %lld", fn, (long long)ldy, (long long)N);
+    if ((double)M * (double)ldy >= 9.0e15) return fail(LQ_EINVAL, "%s: Y is too large", fn);
+    return LQ_OK;
+}
+
+// a thread block is 4 x 4 tiles, 64 x 64 of Y: gx blocks along n, the MT tiles of 16 lines along m in grid.y, which takes 65535
+static int gemm_grid(const char* fn, int64_t gx, int64_t MT, int64_t M, dim3& grid) {
+    const int64_t gy = (MT + 3) / 4;
+    if (gy > 65535) return fail(LQ_EINVAL, "%s: M = %lld is above 65535 * 64", fn, (long long)M);
+    grid = dim3((unsigned)gx, (unsigned)gy);
+    return LQ_OK;
+}
+
 // ---- packed MX operands and the block-scaled GEMM (lq_mx_operand.hpp, lq_mx_gemm.hpp) ----
 // the three element formats whose fragments are built: the 6-bit formats need a 96-byte fragment packing of their own
 static int check_mx_operand_format(const char* fn, int format) {
@@ -1823,13 +1858,6 @@ int lq_mx_operand_bytes(int format, int64_t L, int64_t K, size_t* code_bytes, si
     if (rc) return rc;
     *code_bytes = d.code_bytes;
     *scale_bytes = d.scale_bytes;
-    return LQ_OK;
-}
-
-static int check_mx_operand_buffers(const char* fn, const void* codes, const void* scales) {
-    if (!codes || !scales) return fail(LQ_EINVAL, "%s: argument '%s' is NULL", fn, codes ? "scales" : "codes");
-    if (!aligned(codes, 16)) return fail(LQ_EALIGN, "%s: codes is not 16-byte aligned", fn);
-    if (!aligned(scales, 4)) return fail(LQ_EALIGN, "%s: scales is not 4-byte aligned", fn);
     return LQ_OK;
 }
 
@@ -1897,7 +1925,7 @@ int lq_mx_operand_pack(const float* P, const float* s, int format, int scale_for
     const int64_t L = axis == 0 ? C : R, K = axis == 0 ? R : C;
     MxOperandDims d;
     if ((rc = mx_operand_dims(fn, format, L, K, d))) return rc;
-    if ((rc = check_mx_operand_buffers(fn, codes, scales))) return rc;
+    if ((rc = check_operand_buffers(fn, codes, scales, kMxScaleAlign))) return rc;
     MxOperandParams op{};
     mx_operand_fill(op, d, format, L, K, codes, scales);
     op.mp.g.P = P;
@@ -1918,7 +1946,7 @@ int lq_mx_operand_quantize(const float* X, int format, int method, int64_t M, in
     MxOperandDims d;
     int rc = mx_operand_dims(fn, format, M, K, d);
     if (rc) return rc;
-    if ((rc = check_mx_operand_buffers(fn, codes, scales))) return rc;
+    if ((rc = check_operand_buffers(fn, codes, scales, kMxScaleAlign))) return rc;
     MxOperandParams op{};
     mx_operand_fill(op, d, format, M, K, codes, scales);
     op.mp.g.P = X;
@@ -1926,7 +1954,7 @@ int lq_mx_operand_quantize(const float* X, int format, int method, int64_t M, in
     op.k_stride = 1;
     op.ip.emax = kMxFormats[format].emax;
     op.ip.mm_frac = kMxFormats[format].mm_frac;
-    op.ip.min_value = 1.17549435082228750797e-38f;      // 2^-126: the smallest scale an E8M0 byte of s_eff can hold
+    op.ip.min_value = kOperandMinScale;
     const bool fp4 = format == LQ_ELEM_FP4_E2M1;
     const bool vec = K % 4 == 0 && aligned(X, 16);
     if (method == LQ_MX_INIT_OCP) return launch_mx_operand<true, kInitMxOcp, false>(op, fp4, vec, "microscaling operand quantize", stream);
@@ -1938,7 +1966,7 @@ int lq_mx_operand_decode(const void* codes, const void* scales, int format, int6
     MxOperandDims d;
     int rc = mx_operand_dims(fn, format, L, K, d);
     if (rc) return rc;
-    if ((rc = check_mx_operand_buffers(fn, codes, scales))) return rc;
+    if ((rc = check_operand_buffers(fn, codes, scales, kMxScaleAlign))) return rc;
     LQ_REQUIRE_PTR_FN(fn, out);
     MxDecodeParams dp{};
     dp.codes = (const uint8_t*)codes;
@@ -1962,12 +1990,9 @@ int lq_mx_gemm(const void* a_codes, const void* a_scales, int a_format, const vo
     MxOperandDims da, db;
     int rc = mx_operand_dims(fn, a_format, M, K, da);
     if (rc || (rc = mx_operand_dims(fn, b_format, N, K, db))) return rc;
-    if ((rc = check_mx_operand_buffers(fn, a_codes, a_scales))) return rc;
-    if ((rc = check_mx_operand_buffers(fn, b_codes, b_scales))) return rc;
-    LQ_REQUIRE_PTR_FN(fn, Y);
-    if (bias && !aligned(bias, 4)) return fail(LQ_EALIGN, "%s: bias is not 4-byte aligned", fn);
-    if (ldy < N) return fail(LQ_EINVAL, "%s: ldy = %lld is below N = %lld", fn, (long long)ldy, (long long)N);
-    if ((double)M * (double)ldy >= 9.0e15) return fail(LQ_EINVAL, "%s: Y is too large", fn);
+    if ((rc = check_operand_buffers(fn, a_codes, a_scales, kMxScaleAlign))) return rc;
+    if ((rc = check_operand_buffers(fn, b_codes, b_scales, kMxScaleAlign))) return rc;
+    if ((rc = check_gemm_output(fn, bias, Y, ldy, M, N))) return rc;
     MxGemmParams p{};
     p.a_codes = (const uint8_t*)a_codes;
     p.a_scales = (const uint8_t*)a_scales;
@@ -1982,9 +2007,8 @@ int lq_mx_gemm(const void* a_codes, const void* a_scales, int a_format, const vo
     p.NT = (int32_t)db.LT;
     p.KT = (int32_t)da.KT;
     p.KG = (int32_t)da.KG;
-    const int64_t gx = (db.LT + 3) / 4, gy = (da.LT + 3) / 4;      // a block is 4 x 4 tiles: 64 x 64 of Y
-    if (gy > 65535) return fail(LQ_EINVAL, "%s: M = %lld is above 65535 * 64", fn, (long long)M);
-    const dim3 grid((unsigned)gx, (unsigned)gy);
+    dim3 grid;
+    if ((rc = gemm_grid(fn, (db.LT + 3) / 4, da.LT, M, grid))) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (a_format == LQ_ELEM_FP4_E2M1) launch_mx_gemm_b<LQ_ELEM_FP4_E2M1>(p, b_format, grid, st);
     else if (a_format == LQ_ELEM_FP8_E4M3) launch_mx_gemm_b<LQ_ELEM_FP8_E4M3>(p, b_format, grid, st);
@@ -2001,10 +2025,10 @@ int lq_mx_gemm_quantize(const void* a_codes, const void* a_scales, int a_format,
     if (rc || (rc = mx_operand_dims(fn, b_format, N, K, db)) || (rc = mx_operand_dims(fn, out_format, M, N, dout))) return rc;
     if (method != LQ_MX_INIT_OCP && method != LQ_MX_INIT_COVER) return fail(LQ_EINVAL, "%s: bad method %d", fn, method);
     if (activation != LQ_ACT_NONE && activation != LQ_ACT_RELU) return fail(LQ_EINVAL, "%s: bad activation %d", fn, activation);
-    if ((rc = check_mx_operand_buffers(fn, a_codes, a_scales))) return rc;
-    if ((rc = check_mx_operand_buffers(fn, b_codes, b_scales))) return rc;
-    if ((rc = check_mx_operand_buffers(fn, out_codes, out_scales))) return rc;
-    if (bias && !aligned(bias, 4)) return fail(LQ_EALIGN, "%s: bias is not 4-byte aligned", fn);
+    if ((rc = check_operand_buffers(fn, a_codes, a_scales, kMxScaleAlign))) return rc;
+    if ((rc = check_operand_buffers(fn, b_codes, b_scales, kMxScaleAlign))) return rc;
+    if ((rc = check_operand_buffers(fn, out_codes, out_scales, kMxScaleAlign))) return rc;
+    if ((rc = check_gemm_bias(fn, bias))) return rc;
     MxGemmQuantParams p{};
     p.g.a_codes = (const uint8_t*)a_codes;
     p.g.a_scales = (const uint8_t*)a_scales;
@@ -2020,17 +2044,16 @@ int lq_mx_gemm_quantize(const void* a_codes, const void* a_scales, int a_format,
     mx_fill(p.mp, out_format, LQ_SCALE_E8M0);
     p.ip.emax = kMxFormats[out_format].emax;
     p.ip.mm_frac = kMxFormats[out_format].mm_frac;
-    p.ip.min_value = 1.17549435082228750797e-38f;      // 2^-126, as lq_mx_operand_quantize
+    p.ip.min_value = kOperandMinScale;
     p.codes = (uint8_t*)out_codes;
     p.scales = (uint8_t*)out_scales;
     p.act = activation;
     p.cover = method == LQ_MX_INIT_COVER ? 1 : 0;
     p.OKT = (int32_t)dout.KT;
     p.OKG = (int32_t)dout.KG;
-    // a block is 64 x 64 of Y; along n the grid spans the padded operand, 128 OKT columns, so that its padding is written too
-    const int64_t gx = 2 * dout.KT, gy = (da.LT + 3) / 4;
-    if (gy > 65535) return fail(LQ_EINVAL, "%s: M = %lld is above 65535 * 64", fn, (long long)M);
-    const dim3 grid((unsigned)gx, (unsigned)gy);
+    // along n the grid spans the padded operand, 128 OKT columns, so that its padding is written too
+    dim3 grid;
+    if ((rc = gemm_grid(fn, 2 * dout.KT, da.LT, M, grid))) return rc;
     hipStream_t st = (hipStream_t)stream;
     const bool out_fp4 = out_format == LQ_ELEM_FP4_E2M1;
     if (a_format == LQ_ELEM_FP4_E2M1) launch_mx_gemm_quantize_b<LQ_ELEM_FP4_E2M1>(p, b_format, out_fp4, grid, st);
@@ -2084,44 +2107,56 @@ int lq_mx_im2col_dims(const lq_conv_geom* g, int64_t* M, int64_t* K, int64_t* OH
     return LQ_OK;
 }
 
+// the geometry with the strides of X, as both im2col operands take it
+static int conv_geom_dims_strided(const char* fn, const lq_conv_geom* g, ConvDims& d) {
+    int rc = conv_geom_dims(fn, g, d);
+    if (rc) return rc;
+    if (g->xs_b < 0 || g->xs_c < 0 || g->xs_h < 0 || g->xs_w < 0)
+        return fail(LQ_EINVAL, "%s: strides of X must not be negative (xs_b=%lld xs_c=%lld xs_h=%lld xs_w=%lld)", fn, (long long)g->xs_b,
+                    (long long)g->xs_c, (long long)g->xs_h, (long long)g->xs_w);
+    return LQ_OK;
+}
+
+// all of the device's geometry but `chunks`, which is the kernel's own cut of its grid.  Call once M * K < 2^31 is known: that
+// bounds OH * OW, OW, KH * KW and KW, so every divisor and dividend is a 32-bit number
+static void fill_im2col_geom(Im2colGeom& ig, const lq_conv_geom* g, const ConvDims& cd) {
+    ig.xs_b = g->xs_b;
+    ig.xs_c = g->xs_c;
+    ig.xs_h = g->xs_h;
+    ig.xs_w = g->xs_w;
+    ig.H = g->H;
+    ig.W = g->W;
+    ig.ohow = make_fastdiv((uint32_t)(cd.OH * cd.OW));
+    ig.ow = make_fastdiv((uint32_t)cd.OW);
+    ig.khkw = make_fastdiv((uint32_t)((int64_t)g->KH * g->KW));
+    ig.kw = make_fastdiv((uint32_t)g->KW);
+    ig.KH = g->KH;
+    ig.stride_h = g->stride_h;
+    ig.stride_w = g->stride_w;
+    ig.pad_top = g->pad_top;
+    ig.pad_left = g->pad_left;
+    ig.M = (int32_t)cd.M;
+}
+
 int lq_mx_operand_im2col(const float* X, const lq_conv_geom* g, int format, int method, void* codes, void* scales, void* stream) {
     const char* fn = __func__;
     LQ_REQUIRE_PTR_FN(fn, X);
     if (method != LQ_MX_INIT_OCP && method != LQ_MX_INIT_COVER) return fail(LQ_EINVAL, "%s: bad method %d", fn, method);
     ConvDims cd;
-    int rc = conv_geom_dims(fn, g, cd);
+    int rc = conv_geom_dims_strided(fn, g, cd);
     if (rc) return rc;
-    if (g->xs_b < 0 || g->xs_c < 0 || g->xs_h < 0 || g->xs_w < 0)
-        return fail(LQ_EINVAL, "%s: strides of X must not be negative (xs_b=%lld xs_c=%lld xs_h=%lld xs_w=%lld)", fn, (long long)g->xs_b,
-                    (long long)g->xs_c, (long long)g->xs_h, (long long)g->xs_w);
     MxOperandDims d;
     if ((rc = mx_operand_dims(fn, format, cd.M, cd.K, d))) return rc;      // the format, M * K < 2^31
-    if ((rc = check_mx_operand_buffers(fn, codes, scales))) return rc;
+    if ((rc = check_operand_buffers(fn, codes, scales, kMxScaleAlign))) return rc;
     MxIm2colParams op{};
     mx_fill(op.mp, format, LQ_SCALE_E8M0);
     op.mp.g.P = X;
     op.ip.emax = kMxFormats[format].emax;
     op.ip.mm_frac = kMxFormats[format].mm_frac;
-    op.ip.min_value = 1.17549435082228750797e-38f;      // 2^-126, as lq_mx_operand_quantize
+    op.ip.min_value = kOperandMinScale;
     op.codes = (uint8_t*)codes;
     op.scales = (uint8_t*)scales;
-    op.xs_b = g->xs_b;
-    op.xs_c = g->xs_c;
-    op.xs_h = g->xs_h;
-    op.xs_w = g->xs_w;
-    op.H = g->H;
-    op.W = g->W;
-    // M * K < 2^31 bounds OH * OW, OW, KH * KW and KW: every divisor and dividend is a 32-bit number
-    op.ohow = make_fastdiv((uint32_t)(cd.OH * cd.OW));
-    op.ow = make_fastdiv((uint32_t)cd.OW);
-    op.khkw = make_fastdiv((uint32_t)((int64_t)g->KH * g->KW));
-    op.kw = make_fastdiv((uint32_t)g->KW);
-    op.KH = g->KH;
-    op.stride_h = g->stride_h;
-    op.stride_w = g->stride_w;
-    op.pad_top = g->pad_top;
-    op.pad_left = g->pad_left;
-    op.L = (int32_t)cd.M;
+    fill_im2col_geom(op.geom, g, cd);
     op.K = (int32_t)cd.K;
     op.nbk = (int32_t)((cd.K + kMxBlockLen - 1) / kMxBlockLen);
     op.LT = (int32_t)d.LT;
@@ -2129,8 +2164,8 @@ int lq_mx_operand_im2col(const float* X, const lq_conv_geom* g, int format, int 
     op.KG = (int32_t)d.KG;
     // a thread block is kBlock consecutive lines of one k block: chunks per k block, k blocks slowest
     const int64_t chunks = (d.LT * kMxTileLines + kBlock - 1) / kBlock;
-    op.chunks = make_fastdiv((uint32_t)chunks);
-    const dim3 grid((unsigned)(chunks * d.KT * 4)), block(kBlock);      // below 2^31: at most M K / 8192 + M / 64 + K / 32 + 4
+    op.geom.chunks = make_fastdiv((uint32_t)chunks);
+    const dim3 grid((unsigned)(chunks * d.KT * 4)), block(kBlock);     // below 2^31: at most M K / 8192 + M / 64 + K / 32 + 4
     hipStream_t st = (hipStream_t)stream;
     const bool fp4 = format == LQ_ELEM_FP4_E2M1;
     if (method == LQ_MX_INIT_OCP) {
@@ -2175,13 +2210,6 @@ int lq_i8_operand_bytes(int64_t L, int64_t K, int64_t block, size_t* code_bytes,
     return LQ_OK;
 }
 
-static int check_i8_operand_buffers(const char* fn, const void* codes, const void* scales) {
-    if (!codes || !scales) return fail(LQ_EINVAL, "%s: argument '%s' is NULL", fn, codes ? "scales" : "codes");
-    if (!aligned(codes, 16)) return fail(LQ_EALIGN, "%s: codes is not 16-byte aligned", fn);
-    if (!aligned(scales, 16)) return fail(LQ_EALIGN, "%s: scales is not 16-byte aligned", fn);
-    return LQ_OK;
-}
-
 int lq_i8_operand_pack(const float* P, const float* s, int32_t qmin, int32_t qmax, int rounding, int64_t R, int64_t C, int axis,
                        int64_t gs, void* codes, void* scales, void* stream) {
     const char* fn = __func__;
@@ -2201,7 +2229,7 @@ int lq_i8_operand_pack(const float* P, const float* s, int32_t qmin, int32_t qma
     const int64_t block = gs >= K ? 0 : gs;
     I8OperandDims d;
     if ((rc = i8_operand_dims(fn, L, K, block, d))) return rc;
-    if ((rc = check_i8_operand_buffers(fn, codes, scales))) return rc;
+    if ((rc = check_operand_buffers(fn, codes, scales, kI8ScaleAlign))) return rc;
     I8PackParams op{};
     op.g = group_params(P, s, qmin, qmax, R, C, axis, gs);
     op.codes = (uint8_t*)codes;
@@ -2235,12 +2263,12 @@ int lq_i8_operand_quantize(const float* X, int64_t M, int64_t K, int64_t block, 
     I8OperandDims d;
     int rc = i8_operand_dims(fn, M, K, block, d);
     if (rc) return rc;
-    if ((rc = check_i8_operand_buffers(fn, codes, scales))) return rc;
+    if ((rc = check_operand_buffers(fn, codes, scales, kI8ScaleAlign))) return rc;
     I8QuantParams op{};
     op.g.P = X;
     op.g.lo = op.ip.lo = -127.0f;
     op.g.hi = op.ip.hi = 127.0f;
-    op.ip.min_value = 1.17549435082228750797e-38f;      // 2^-126, as lq_mx_operand_quantize
+    op.ip.min_value = kOperandMinScale;
     op.codes = (uint8_t*)codes;
     op.scales = (float*)scales;
     op.M = (int32_t)M;
@@ -2270,38 +2298,19 @@ int lq_i8_operand_im2col(const float* X, const lq_conv_geom* g, int64_t block, v
     const char* fn = __func__;
     LQ_REQUIRE_PTR_FN(fn, X);
     ConvDims cd;
-    int rc = conv_geom_dims(fn, g, cd);
+    int rc = conv_geom_dims_strided(fn, g, cd);
     if (rc) return rc;
-    if (g->xs_b < 0 || g->xs_c < 0 || g->xs_h < 0 || g->xs_w < 0)
-        return fail(LQ_EINVAL, "%s: strides of X must not be negative (xs_b=%lld xs_c=%lld xs_h=%lld xs_w=%lld)", fn, (long long)g->xs_b,
-                    (long long)g->xs_c, (long long)g->xs_h, (long long)g->xs_w);
     I8OperandDims d;
     if ((rc = i8_operand_dims(fn, cd.M, cd.K, block, d))) return rc;      // M * K < 2^31, the block
-    if ((rc = check_i8_operand_buffers(fn, codes, scales))) return rc;
+    if ((rc = check_operand_buffers(fn, codes, scales, kI8ScaleAlign))) return rc;
     I8Im2colParams op{};
     op.g.P = X;
     op.g.lo = op.ip.lo = -127.0f;
     op.g.hi = op.ip.hi = 127.0f;
-    op.ip.min_value = 1.17549435082228750797e-38f;      // 2^-126, as lq_i8_operand_quantize
+    op.ip.min_value = kOperandMinScale;
     op.codes = (uint8_t*)codes;
     op.scales = (float*)scales;
-    op.xs_b = g->xs_b;
-    op.xs_c = g->xs_c;
-    op.xs_h = g->xs_h;
-    op.xs_w = g->xs_w;
-    op.H = g->H;
-    op.W = g->W;
-    // M * K < 2^31 bounds OH * OW, OW, KH * KW and KW: every divisor and dividend is a 32-bit number
-    op.ohow = make_fastdiv((uint32_t)(cd.OH * cd.OW));
-    op.ow = make_fastdiv((uint32_t)cd.OW);
-    op.khkw = make_fastdiv((uint32_t)((int64_t)g->KH * g->KW));
-    op.kw = make_fastdiv((uint32_t)g->KW);
-    op.KH = g->KH;
-    op.stride_h = g->stride_h;
-    op.stride_w = g->stride_w;
-    op.pad_top = g->pad_top;
-    op.pad_left = g->pad_left;
-    op.M = (int32_t)cd.M;
+    fill_im2col_geom(op.geom, g, cd);
     op.K = (int32_t)cd.K;
     op.block = (int32_t)block;
     op.nbs = (int32_t)d.nbs;
@@ -2313,7 +2322,7 @@ int lq_i8_operand_im2col(const float* X, const lq_conv_geom* g, int64_t block, v
     const int slices = i8_conv_slices(units);
     // a thread block is kBlock / slices consecutive lines of one scale block: chunks per scale block, scale blocks slowest
     const int64_t per = kBlock / slices, chunks = (lines + per - 1) / per;
-    op.chunks = make_fastdiv((uint32_t)chunks);
+    op.geom.chunks = make_fastdiv((uint32_t)chunks);
     const dim3 grid((unsigned)(chunks * d.nbs)), blk(kBlock);      // below 2^31: at most M K / 4096 + M / 64 + K / 64 + 1
     hipStream_t st = (hipStream_t)stream;
     if (slices == 1) hipLaunchKernelGGL(k_i8_im2col<1>, grid, blk, 0, st, op);
@@ -2326,7 +2335,7 @@ int lq_i8_operand_decode(const void* codes, const void* scales, int64_t L, int64
     I8OperandDims d;
     int rc = i8_operand_dims(fn, L, K, block, d);
     if (rc) return rc;
-    if ((rc = check_i8_operand_buffers(fn, codes, scales))) return rc;
+    if ((rc = check_operand_buffers(fn, codes, scales, kI8ScaleAlign))) return rc;
     LQ_REQUIRE_PTR_FN(fn, out);
     I8DecodeParams dp{};
     dp.codes = (const uint8_t*)codes;
@@ -2357,12 +2366,9 @@ int lq_i8_gemm(const void* a_codes, const void* a_scales, int64_t a_block, const
     if (period > 65536)
         return fail(LQ_EINVAL, "%s: a period of %lld k between two scale changes is above 65536: the int32 sum of that many products of "
                     "magnitude up to 2^14 could overflow", fn, (long long)period);
-    if ((rc = check_i8_operand_buffers(fn, a_codes, a_scales))) return rc;
-    if ((rc = check_i8_operand_buffers(fn, b_codes, b_scales))) return rc;
-    LQ_REQUIRE_PTR_FN(fn, Y);
-    if (bias && !aligned(bias, 4)) return fail(LQ_EALIGN, "%s: bias is not 4-byte aligned", fn);
-    if (ldy < N) return fail(LQ_EINVAL, "%s: ldy = %lld is below N = %lld", fn, (long long)ldy, (long long)N);
-    if ((double)M * (double)ldy >= 9.0e15) return fail(LQ_EINVAL, "%s: Y is too large", fn);
+    if ((rc = check_operand_buffers(fn, a_codes, a_scales, kI8ScaleAlign))) return rc;
+    if ((rc = check_operand_buffers(fn, b_codes, b_scales, kI8ScaleAlign))) return rc;
+    if ((rc = check_gemm_output(fn, bias, Y, ldy, M, N))) return rc;
     I8GemmParams p{};
     p.a_codes = (const uint8_t*)a_codes;
     p.a_scales = (const float*)a_scales;
@@ -2379,9 +2385,9 @@ int lq_i8_gemm(const void* a_codes, const void* a_scales, int64_t a_block, const
     p.ps = (int32_t)(F > 0 ? std::min(F / kI8TileK, da.KT) : da.KT);
     p.a_every = a_block > 0 ? (int32_t)(a_block / F) : INT32_MAX;
     p.b_every = b_block > 0 ? (int32_t)(b_block / F) : INT32_MAX;
-    const int64_t gx = (db.LT + 3) / 4, gy = (da.LT + 3) / 4;      // a block is 4 x 4 tiles: 64 x 64 of Y
-    if (gy > 65535) return fail(LQ_EINVAL, "%s: M = %lld is above 65535 * 64", fn, (long long)M);
-    hipLaunchKernelGGL(k_i8_gemm, dim3((unsigned)gx, (unsigned)gy), dim3(kBlock), 0, (hipStream_t)stream, p);
+    dim3 grid;
+    if ((rc = gemm_grid(fn, (db.LT + 3) / 4, da.LT, M, grid))) return rc;
+    hipLaunchKernelGGL(k_i8_gemm, grid, dim3(kBlock), 0, (hipStream_t)stream, p);
     return check_hip("int8 GEMM");
 }
 

@@ -9,15 +9,16 @@
 // One thread per (line, block of 32 k), as k_mx_operand has it, lines fastest: a thread block is kBlock consecutive lines of ONE k
 // block, so (c, i, j) of each of the 32 taps is uniform over the block (scalar registers) and only (b, oh, ow) is per lane.  For an
 // NCHW input at stride 1 a wave's load of one tap is 64 consecutive addresses (up to the row ends), and the fragment stores of 16
-// neighbouring lines are contiguous.  The gather is 32 predicated 4-byte loads -- zero outside the image and past K, and no address
-// is formed into a load unless the definition names it -- addressed in int64 through the strides of X (NCHW, channels_last or any
-// view with non-negative strides).  The scale rule and the element step are those k_mx_operand runs, called, not restated:
-// init_take / init_raw / init_final, GroupStep<true, GroupMxParams>, mx_code_bits.  The few lines around them (block scale byte,
-// code packing, fragment stores, idle scale bytes) are copied from k_mx_operand instead of shared with it, so that its instruction
-// streams stay what they were (the precedent is mx_gemm_accumulate).  No LDS, no scratch, no atomics.
+// neighbouring lines are contiguous.  The geometry and the line's window are lq_im2col.hpp's, shared with k_i8_im2col; the gather
+// -- 32 predicated 4-byte loads, zero outside the image and past K -- is im2col_gather's tap walk written out in the kernel, because
+// the call measured slower here ("One im2col gather").  The scale rule and the element step are those k_mx_operand
+// runs, called, not restated: init_take / init_raw / init_final, GroupStep<true, GroupMxParams>, mx_code_bits.  The few lines
+// around them (block scale byte, code packing, fragment stores, idle scale bytes) repeat k_mx_operand's: the two kernels differ in
+// what feeds those lines (a strided row there, a gathered window here), and k_mx_operand's instruction streams are pinned
+// ("One im2col gather").  No LDS, no scratch, no atomics.
 #ifndef LQ_MX_CONV_HPP_
 #define LQ_MX_CONV_HPP_
-#include "lq_fastdiv.hpp"
+#include "lq_im2col.hpp"
 #include "lq_mx_operand.hpp"
 
 namespace lq {
@@ -27,47 +28,41 @@ struct MxIm2colParams {
     InitParams ip;            // emax, mm_frac, min_value
     uint8_t* codes;
     uint8_t* scales;
-    int64_t xs_b, xs_c, xs_h, xs_w;       // of X, in elements
-    int64_t H, W;
-    FastDiv ohow, ow;         // m -> (b, oh, ow)
-    FastDiv khkw, kw;         // k -> (c, i, j)
-    FastDiv chunks;           // blockIdx.x -> (k block, chunk of kBlock lines)
-    int32_t KH, stride_h, stride_w, pad_top, pad_left;
-    int32_t L, K, nbk;        // L = M lines; nbk = ceil(K / 32)
+    Im2colGeom geom;          // geom.M lines; geom.chunks: blockIdx.x -> (k block, chunk of kBlock lines)
+    int32_t K, nbk;           // nbk = ceil(K / 32)
     int32_t LT, KT, KG;
 };
 
 template <int METHOD, bool FP4>
 __global__ __launch_bounds__(kBlock) void k_mx_im2col(const MxIm2colParams op) {
     using Step = GroupStep<true, GroupMxParams>;
-    const int32_t kb = (int32_t)fd_div(op.chunks, blockIdx.x);                         // uniform over the block
-    const int64_t line = (int64_t)(blockIdx.x - (uint32_t)kb * op.chunks.d) * kBlock + threadIdx.x;
+    const int32_t kb = (int32_t)fd_div(op.geom.chunks, blockIdx.x);                    // uniform over the block
+    const int64_t line = (int64_t)(blockIdx.x - (uint32_t)kb * op.geom.chunks.d) * kBlock + threadIdx.x;
     if (line >= (int64_t)op.LT * kMxTileLines) return;
     const int32_t ln = (int32_t)line;
-    const bool live = ln < op.L && kb < op.nbk;
+    const bool live = ln < op.geom.M && kb < op.nbk;
     uint32_t w[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
     uint32_t byte = 127u;
     if (live) {
         const int n = min(kMxBlockLen, op.K - kb * kMxBlockLen);
-        const uint32_t b = fd_div(op.ohow, (uint32_t)ln), r = (uint32_t)ln - b * op.ohow.d;
-        const uint32_t oh = fd_div(op.ow, r), ow = r - oh * op.ow.d;
-        const int64_t ih0 = (int64_t)oh * op.stride_h - op.pad_top, iw0 = (int64_t)ow * op.stride_w - op.pad_left;
-        const int64_t base = (int64_t)b * op.xs_b + ih0 * op.xs_h + iw0 * op.xs_w;      // of the window's corner: may lie outside X
+        const Im2colGeom& g = op.geom;
+        const Im2colWindow win = im2col_window(g, ln);
+        // im2col_gather<32>, written out: called, it costs this kernel about 9 instructions and 0.4 % on two of nine shapes
         const uint32_t k0 = (uint32_t)kb * kMxBlockLen;
-        uint32_t c = fd_div(op.khkw, k0);
-        const uint32_t rk = k0 - c * op.khkw.d;
-        uint32_t i = fd_div(op.kw, rk), j = rk - i * op.kw.d;
+        uint32_t c = fd_div(g.khkw, k0);
+        const uint32_t rk = k0 - c * g.khkw.d;
+        uint32_t i = fd_div(g.kw, rk), j = rk - i * g.kw.d;
         const float* X = op.mp.g.P;
         float x[kMxBlockLen];
 #pragma unroll
         for (int e = 0; e < kMxBlockLen; ++e) {
-            const int64_t ih = ih0 + i, iw = iw0 + j;
-            const bool in = e < n && (uint64_t)ih < (uint64_t)op.H && (uint64_t)iw < (uint64_t)op.W;
+            const int64_t ih = win.ih0 + i, iw = win.iw0 + j;
+            const bool in = e < n && (uint64_t)ih < (uint64_t)g.H && (uint64_t)iw < (uint64_t)g.W;
             x[e] = 0.f;
-            if (in) x[e] = X[base + (int64_t)c * op.xs_c + (int64_t)i * op.xs_h + (int64_t)j * op.xs_w];
-            if (++j == op.kw.d) {
+            if (in) x[e] = X[win.base + (int64_t)c * g.xs_c + (int64_t)i * g.xs_h + (int64_t)j * g.xs_w];
+            if (++j == g.kw.d) {
                 j = 0u;
-                if (++i == (uint32_t)op.KH) { i = 0u; ++c; }
+                if (++i == (uint32_t)g.KH) { i = 0u; ++c; }
             }
         }
         InitAcc a{0.f, 0.f, 0.0, 0u};      // the zeros of the padding and past n change neither maximum

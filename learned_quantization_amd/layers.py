@@ -42,7 +42,7 @@ at construction (NQ-L:133-145) are dropped.
 from __future__ import annotations
 
 import math
-from typing import Optional, Tuple
+from typing import Callable, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -580,6 +580,34 @@ class _HostLayer(nn.Module):
         return total
 
 
+class _MatrixFamily(NamedTuple):
+    """One hardware matrix path as the layers use it.  ``act`` below is the family's activation arguments: (act_format, act_scale)
+    of the block-scaled path, (act_block,) of the int8 path."""
+    hw: str                   # the layer attribute under which a context manager parks (operand, bias, *act)
+    operand: str              # the layer method that packs the kernel
+    quantize: Callable        # (matrix, *act) -> operand
+    im2col: Callable          # (x, kernel_size, strides, padding, *act) -> operand
+    decode: Callable          # operand -> fp32 matrix
+    gemm: Callable            # (a, b, bias, out) -> fp32 matrix
+
+    def product(self, a, operand, qb, out=None):
+        """``a`` times the layer's ``operand`` plus ``qb`` on the matrix instruction -- or, where ``operand`` is a tensor (the
+        fake-quantised kernel as a (K, out) matrix: ``emulate=True``), the decoded ``a`` times it by ``torch.matmul``."""
+        if not isinstance(operand, torch.Tensor):
+            return self.gemm(a, operand, qb, out=out)
+        y = torch.matmul(self.decode(a), operand, out=out)
+        return y if qb is None else y.add_(qb)
+
+
+_MX = _MatrixFamily("_mx_hw", "mx_operand", ops.mx_operand_quantize, ops.mx_operand_im2col, ops.mx_operand_decode, ops.mx_gemm)
+_I8 = _MatrixFamily("_i8_hw", "i8_operand", ops.i8_operand_quantize, ops.i8_operand_im2col, ops.i8_operand_decode, ops.i8_gemm)
+
+
+def _check_max_lines(max_lines) -> None:
+    if max_lines is not None and (not isinstance(max_lines, int) or isinstance(max_lines, bool) or max_lines < 1):
+        raise ValueError(f"max_lines must be a positive integer or None, got {max_lines!r}")
+
+
 class CustomDenseLayer(_HostLayer):
     """Standard dense layer with nested quantization layers for weights and bias (NQ-L:203-268)."""
 
@@ -642,14 +670,11 @@ class CustomDenseLayer(_HostLayer):
     def call(self, inputs):
         if not self.built:
             self.build(tuple(inputs.shape), device=inputs.device)
-        hw = getattr(self, "_mx_hw", None)
-        if hw is not None and not self.training:                  # inside layers.mx_hardware(...), eval mode
-            self._q_pre = None                                    # a batch's fake-quantised pair is not what this path multiplies
-            return self._mx_product(inputs, *hw)
-        hw = getattr(self, "_i8_hw", None)
-        if hw is not None and not self.training:                  # inside layers.i8_hardware(...), eval mode
-            self._q_pre = None
-            return self._i8_product(inputs, *hw)
+        for family in (_MX, _I8):
+            hw = getattr(self, family.hw, None)
+            if hw is not None and not self.training:              # inside layers.mx_hardware(...) / i8_hardware(...), eval mode
+                self._q_pre = None                                # a batch's fake-quantised pair is not what this path multiplies
+                return self._matrix_product(inputs, hw[0], hw[1], family, hw[2:])
         qw, qb = self.quantized_parameters()
         return torch.add(torch.matmul(inputs, qw), qb)           # NQ-L:268
 
@@ -677,15 +702,6 @@ class CustomDenseLayer(_HostLayer):
             scale, gs = scale.reshape(1, -1).expand(1, units).contiguous(), fan_in
         return ops.i8_operand_pack(self.W.detach(), scale, qmin, qmax, gs, self.rounding)
 
-    def _i8_product(self, inputs, operand, qb, act_block):
-        with torch.no_grad():
-            a = ops.i8_operand_quantize(inputs.reshape(-1, inputs.shape[-1]), act_block)
-            if isinstance(operand, torch.Tensor):                 # i8_hardware(emulate=True): the fake-quantised kernel itself
-                y = torch.add(torch.matmul(ops.i8_operand_decode(a), operand), qb)
-            else:
-                y = ops.i8_gemm(a, operand, qb)
-            return y.reshape(*inputs.shape[:-1], y.shape[-1])
-
     def call_i8(self, inputs, act_block=0):
         """The layer on the int8 matrix instruction, under ``no_grad``: the inputs quantised per row and ``act_block`` consecutive
         inputs (0: per row) to symmetric 8-bit integers (ops.i8_operand_quantize), multiplied with ``i8_operand()`` by ops.i8_gemm,
@@ -694,7 +710,7 @@ class CustomDenseLayer(_HostLayer):
         if not self.built:
             self.build(tuple(inputs.shape), device=inputs.device)
         with torch.no_grad():
-            return self._i8_product(inputs, self.i8_operand(), self.nested_q_b_layer(self.b), act_block)
+            return self._matrix_product(inputs, self.i8_operand(), self.nested_q_b_layer(self.b), _I8, (act_block,))
 
     def mx_operand(self) -> "ops.MxOperand":
         """The kernel under its current scales as an operand of the block-scaled matrix instruction (ops.mx_operand_pack): ``units``
@@ -710,24 +726,22 @@ class CustomDenseLayer(_HostLayer):
         if operand.K != self.W.shape[0]:
             raise ValueError(f"{self.name}: the input operand reduces over K = {operand.K}, the layer over in = {self.W.shape[0]}")
 
-    def _mx_product(self, inputs, operand, qb, act_format, act_scale, out_format=None, activation=None):
+    def _matrix_product(self, inputs, operand, qb, family, act, out_format=None, activation=None):
+        """``out_format`` and ``activation``: the block-scaled path's operand-out epilogue; only that path takes an operand as input."""
         with torch.no_grad():
-            if isinstance(inputs, ops.MxOperand):                 # a previous layer's operand-out epilogue wrote it: used as it is
+            if family is _MX and isinstance(inputs, ops.MxOperand):      # a previous layer's epilogue wrote it: used as it is
                 self._check_mx_input(inputs)
                 a, lead = inputs, (inputs.lines,)
             else:
-                a, lead = ops.mx_operand_quantize(inputs.reshape(-1, inputs.shape[-1]), act_format, act_scale), tuple(inputs.shape[:-1])
+                a, lead = family.quantize(inputs.reshape(-1, inputs.shape[-1]), *act), tuple(inputs.shape[:-1])
             if out_format is None:
                 if activation is not None:
                     raise ValueError(f"{self.name}: activation={activation!r} is fused into the operand-out epilogue: give out_format")
-                if isinstance(operand, torch.Tensor):             # mx_hardware(emulate=True): the fake-quantised kernel itself
-                    y = torch.add(torch.matmul(ops.mx_operand_decode(a), operand), qb)
-                else:
-                    y = ops.mx_gemm(a, operand, qb)
+                y = family.product(a, operand, qb)
                 return y.reshape(*lead, y.shape[-1])
             if isinstance(operand, torch.Tensor):
                 raise ValueError(f"{self.name}: the emulated path has no operand-out epilogue (out_format={out_format!r})")
-            return ops.mx_gemm_quantize(a, operand, qb, activation, out_format, act_scale)
+            return ops.mx_gemm_quantize(a, operand, qb, activation, out_format, act[1])
 
     def call_mx(self, inputs, act_format="fp8_e4m3", act_scale="mx", out_format=None, activation=None):
         """The layer on the block-scaled matrix instruction, under ``no_grad``: the inputs quantised per block of 32 along their last
@@ -746,8 +760,8 @@ class CustomDenseLayer(_HostLayer):
             ops.check_mx_operand_format(out_format)
         ops.check_mx_activation(activation)
         with torch.no_grad():
-            return self._mx_product(inputs, self.mx_operand(), self.nested_q_b_layer(self.b), act_format, act_scale, out_format,
-                                    activation)
+            return self._matrix_product(inputs, self.mx_operand(), self.nested_q_b_layer(self.b), _MX, (act_format, act_scale),
+                                        out_format, activation)
 
 
 _KERNEL_STORAGE = ["oihw"]
@@ -888,14 +902,11 @@ class _ConvBase(_HostLayer):
     def call(self, inputs):
         if not self.built:
             self.build(tuple(inputs.shape), device=inputs.device)
-        hw = getattr(self, "_mx_hw", None)
-        if hw is not None and not self.training:                  # inside layers.mx_hardware(..., convs=True), eval mode
-            self._q_pre = None                                    # a batch's fake-quantised pair is not what this path multiplies
-            return self._mx_conv(inputs, *hw)
-        hw = getattr(self, "_i8_hw", None)
-        if hw is not None and not self.training:                  # inside layers.i8_hardware(..., convs=True), eval mode
-            self._q_pre = None
-            return self._i8_conv(inputs, *hw)
+        for family in (_MX, _I8):
+            hw = getattr(self, family.hw, None)
+            if hw is not None and not self.training:              # inside layers.mx_hardware / i8_hardware(..., convs=True), eval mode
+                self._q_pre = None                                # a batch's fake-quantised pair is not what this path multiplies
+                return self._matrix_conv(inputs, hw[0], hw[1], family, hw[2:])
         x = inputs.permute(0, 3, 1, 2) if self.data_format == "NHWC" else inputs
         w, qb = self.quantized_parameters()
         if self.padding == "SAME":
@@ -928,12 +939,15 @@ class _ConvBase(_HostLayer):
                                    self.scale_format)
 
     def _mx_padding(self, h: int, w: int) -> Tuple[int, int, int, int]:
-        """(top, bottom, left, right) of this layer on an h x w input: TensorFlow 'SAME' (asymmetric where it is) or none."""
+        """(top, bottom, left, right) of this layer on an h x w input: TensorFlow 'SAME' (asymmetric where it is) or none.  Both
+        matrix paths pad by it."""
         if self.padding != "SAME":
             return (0, 0, 0, 0)
         return (*_same_padding(h, self.kernel_size[0], self.strides[0]), *_same_padding(w, self.kernel_size[1], self.strides[1]))
 
-    def _mx_conv(self, inputs, operand, qb, act_format, act_scale, max_lines=None):
+    def _matrix_conv(self, inputs, operand, qb, family, act, max_lines=None):
+        """The layer on ``family``'s matrix instruction: per run of whole images (ops.im2col_runs) the im2col operand of the
+        inputs, times ``operand``, plus ``qb``, into its rows of the one result."""
         with torch.no_grad():
             if inputs.dim() != 4:
                 raise ValueError(f"{self.name}: the input must have four axes, got shape {tuple(inputs.shape)}")
@@ -941,22 +955,20 @@ class _ConvBase(_HostLayer):
             padding = self._mx_padding(x.shape[2], x.shape[3])
             M, K, OH, OW = ops.mx_im2col_dims(x.shape, self.kernel_size, self.strides, padding)
             B, per = x.shape[0], OH * OW
-            # runs of whole images whose operand the C surface takes (M K < 2^31) and that hold at most max_lines lines
-            fit = ((1 << 31) - 1) // K if max_lines is None else min(int(max_lines), ((1 << 31) - 1) // K)
-            images = max(1, min(B, fit // per))
             y = torch.empty((M, self.filters), dtype=torch.float32, device=x.device)
-            for b0 in range(0, B, images):
-                b1 = min(B, b0 + images)
-                a = ops.mx_operand_im2col(x[b0:b1], self.kernel_size, self.strides, padding, act_format, act_scale)
-                rows = y[b0 * per:b1 * per]
-                if isinstance(operand, torch.Tensor):             # mx_hardware(emulate=True): the fake-quantised kernel (K, co)
-                    torch.matmul(ops.mx_operand_decode(a), operand, out=rows)
-                    if qb is not None:
-                        rows.add_(qb)
-                else:
-                    ops.mx_gemm(a, operand, qb, out=rows)
+            for b0, b1 in ops.im2col_runs(B, per, K, max_lines):
+                a = family.im2col(x[b0:b1], self.kernel_size, self.strides, padding, *act)
+                family.product(a, operand, qb, out=y[b0 * per:b1 * per])
             y = y.view(B, OH, OW, self.filters)                   # the GEMM's [M][co] is NHWC: no transposition launch
             return y if self.data_format == "NHWC" else y.permute(0, 3, 1, 2)
+
+    def _call_matrix(self, inputs, family, act, max_lines):
+        if not self.built:
+            self.build(tuple(inputs.shape), device=inputs.device)
+        with torch.no_grad():
+            operand = getattr(self, family.operand)()
+            qb = self.nested_q_b_layer(self.b) if self._has_bias else None
+            return self._matrix_conv(inputs, operand, qb, family, act, max_lines)
 
     def call_mx(self, inputs, act_format="fp8_e4m3", act_scale="mx", max_lines=None):
         """The layer on the block-scaled matrix instruction, under ``no_grad``: the im2col matrix of the inputs quantised per block
@@ -964,19 +976,12 @@ class _ConvBase(_HostLayer):
         padding as ``call`` pads, or 'VALID' -- multiplied with ``mx_operand()`` by ops.mx_gemm, plus the fake-quantised bias where
         the layer has one.  Inference only: there is no backward through this path.  The result is a view of the GEMM's (M, co)
         matrix: ``(B, co, OH, OW)`` with channels-last strides for ``data_format="NCHW"``, ``(B, OH, OW, co)`` for "NHWC".  A batch
-        whose im2col matrix has 2^31 elements or more, or more than ``max_lines`` lines, is cut into runs of whole images that
-        write their rows of the one result; the result does not depend on the cut."""
-        if max_lines is not None and (not isinstance(max_lines, int) or isinstance(max_lines, bool) or max_lines < 1):
-            raise ValueError(f"max_lines must be a positive integer or None, got {max_lines!r}")
+        whose im2col matrix has 2^31 elements or more, more than 65535 * 64 lines or more than ``max_lines`` lines is cut into runs
+        of whole images that write their rows of the one result; the result does not depend on the cut."""
+        _check_max_lines(max_lines)
         ops.check_mx_operand_format(act_format)
         ops.check_mx_scale_init(act_scale)
-        if not self.built:
-            self.build(tuple(inputs.shape), device=inputs.device)
-        with torch.no_grad():
-            operand = self.mx_operand()
-            qb = self.nested_q_b_layer(self.b) if self._has_bias else None
-            return self._mx_conv(inputs, operand, qb, act_format, act_scale, max_lines)
-
+        return self._call_matrix(inputs, _MX, (act_format, act_scale), max_lines)
 
     def _check_i8(self):
         """(qmin, qmax) of a conv layer that can run on the int8 matrix instruction, or ValueError naming the reason."""
@@ -1002,34 +1007,6 @@ class _ConvBase(_HostLayer):
             scale, gs = scale.reshape(1, 1).expand(self.filters, 1).contiguous(), K
         return ops.i8_operand_pack(self.kernel.detach(), scale, qmin, qmax, gs, self.rounding)
 
-    def _i8_conv(self, inputs, operand, qb, act_block, max_lines=None):
-        with torch.no_grad():
-            if inputs.dim() != 4:
-                raise ValueError(f"{self.name}: the input must have four axes, got shape {tuple(inputs.shape)}")
-            x = inputs.permute(0, 3, 1, 2) if self.data_format == "NHWC" else inputs       # a view: the operand reads its strides
-            padding = self._mx_padding(x.shape[2], x.shape[3])
-            M, K, OH, OW = ops.mx_im2col_dims(x.shape, self.kernel_size, self.strides, padding)
-            B, per = x.shape[0], OH * OW
-            # runs of whole images whose operand the C surface takes (M K < 2^31), that the GEMM's grid takes (65535 * 64 lines)
-            # and that hold at most max_lines lines
-            fit = min(((1 << 31) - 1) // K, 65535 * 64)
-            if max_lines is not None:
-                fit = min(fit, int(max_lines))
-            images = max(1, min(B, fit // per))
-            y = torch.empty((M, self.filters), dtype=torch.float32, device=x.device)
-            for b0 in range(0, B, images):
-                b1 = min(B, b0 + images)
-                a = ops.i8_operand_im2col(x[b0:b1], self.kernel_size, self.strides, padding, act_block)
-                rows = y[b0 * per:b1 * per]
-                if isinstance(operand, torch.Tensor):             # i8_hardware(emulate=True): the fake-quantised kernel (K, co)
-                    torch.matmul(ops.i8_operand_decode(a), operand, out=rows)
-                    if qb is not None:
-                        rows.add_(qb)
-                else:
-                    ops.i8_gemm(a, operand, qb, out=rows)
-            y = y.view(B, OH, OW, self.filters)                   # the GEMM's [M][co] is NHWC: no transposition launch
-            return y if self.data_format == "NHWC" else y.permute(0, 3, 1, 2)
-
     def call_i8(self, inputs, act_block=0, max_lines=None):
         """The layer on the int8 matrix instruction, under ``no_grad``: the im2col matrix of the inputs quantised per line and
         ``act_block`` consecutive k of (ci, kh, kw) (0: per line) to symmetric 8-bit integers by ops.i8_operand_im2col -- TensorFlow
@@ -1038,15 +1015,9 @@ class _ConvBase(_HostLayer):
         (M, co) matrix: ``(B, co, OH, OW)`` with channels-last strides for ``data_format="NCHW"``, ``(B, OH, OW, co)`` for "NHWC".  A
         batch whose im2col matrix has 2^31 elements or more, more than 65535 * 64 lines or more than ``max_lines`` lines is cut into
         runs of whole images that write their rows of the one result; the result does not depend on the cut."""
-        if max_lines is not None and (not isinstance(max_lines, int) or isinstance(max_lines, bool) or max_lines < 1):
-            raise ValueError(f"max_lines must be a positive integer or None, got {max_lines!r}")
+        _check_max_lines(max_lines)
         ops.check_i8_block(act_block)
-        if not self.built:
-            self.build(tuple(inputs.shape), device=inputs.device)
-        with torch.no_grad():
-            operand = self.i8_operand()
-            qb = self.nested_q_b_layer(self.b) if self._has_bias else None
-            return self._i8_conv(inputs, operand, qb, act_block, max_lines)
+        return self._call_matrix(inputs, _I8, (act_block,), max_lines)
 
 
 class CustomConv2DLayer(_ConvBase):
@@ -1078,7 +1049,36 @@ def mx_conv_eligible(layer: nn.Module) -> bool:
             and layer.scale_format == "e8m0" and layer.group_size == ops.MX_GROUP_SIZE and layer.kernel_storage == "oihw")
 
 
-class mx_hardware:
+class _matrix_hardware:
+    """Entry and exit of ``mx_hardware`` and ``i8_hardware``: the eligible Dense layers, then (``convs``) the eligible conv layers,
+    get ``(operand, bias, *act)`` under the family's attribute -- built once, on entry -- and lose it on exit."""
+    _family = _dense_eligible = _conv_eligible = None
+
+    def __enter__(self):
+        family, custom = self._family, custom_layers_of(self.model)
+        switching = [m for m in custom if self._dense_eligible(m)]
+        switching += [m for m in custom if self._conv_eligible(m)] if self.convs else []
+        self.layers = []
+        with torch.no_grad():
+            for m in switching:
+                if not self.emulate:
+                    weight = getattr(m, family.operand)()
+                elif isinstance(m, _ConvBase):      # the fake-quantised kernel as the (K, co) matrix the decoded operand multiplies
+                    weight = m.nested_q_k_layer(m.kernel).detach().permute(3, 2, 0, 1).reshape(m.filters, -1).t()
+                else:
+                    weight = m.nested_q_w_layer(m.W).detach()
+                bias = m.nested_q_b_layer(m.b).detach() if getattr(m, "_has_bias", True) else None
+                setattr(m, family.hw, (weight, bias, *self._act))
+                self.layers.append(m)
+        return self
+
+    def __exit__(self, *exc):
+        for m in self.layers:
+            setattr(m, self._family.hw, None)
+        return False
+
+
+class mx_hardware(_matrix_hardware):
     """Context manager: inside it every eligible Dense layer of ``model`` (``mx_hardware_eligible``) computes its eval-mode ``call``
     as ``call_mx`` does -- activations quantised per block (``act_format``, ``act_scale``), the product on the block-scaled matrix
     instruction.  The operands and the fake-quantised biases are built ONCE, on entry, from the scales the layers have then;
@@ -1097,6 +1097,8 @@ class mx_hardware:
     multiplies the decoded im2col operand with the fake-quantised kernel by ``torch.matmul`` instead.  Without ``convs`` (the
     default) conv layers keep the fake-quantised path."""
 
+    _family, _dense_eligible, _conv_eligible = _MX, staticmethod(mx_hardware_eligible), staticmethod(mx_conv_eligible)
+
     def __init__(self, model: nn.Module, act_format="fp8_e4m3", act_scale="mx", emulate=False, fused=False, convs=False):
         ops.check_mx_operand_format(act_format)
         ops.check_mx_scale_init(act_scale)
@@ -1104,21 +1106,11 @@ class mx_hardware:
             raise ValueError("mx_hardware: emulate=True with fused=True: the emulated path is the yardstick of the unfused path and "
                              "has no operand-out epilogue")
         self.model, self.act_format, self.act_scale, self.emulate, self.fused = model, act_format, act_scale, bool(emulate), bool(fused)
-        self.convs = bool(convs)
+        self.convs, self._act = bool(convs), (act_format, act_scale)
         self.layers, self.fused_layers, self._fused_modules = [], [], []
 
     def __enter__(self):
-        self.layers = [m for m in custom_layers_of(self.model) if mx_hardware_eligible(m)]
-        with torch.no_grad():
-            for m in self.layers:
-                weight = m.nested_q_w_layer(m.W).detach() if self.emulate else m.mx_operand()
-                m._mx_hw = (weight, m.nested_q_b_layer(m.b).detach(), self.act_format, self.act_scale)
-            for m in [m for m in custom_layers_of(self.model) if mx_conv_eligible(m)] if self.convs else []:
-                # emulate: the fake-quantised kernel as the (K, co) matrix the decoded im2col operand multiplies
-                weight = m.nested_q_k_layer(m.kernel).detach().permute(3, 2, 0, 1).reshape(m.filters, -1).t() if self.emulate \
-                    else m.mx_operand()
-                m._mx_hw = (weight, m.nested_q_b_layer(m.b).detach() if m._has_bias else None, self.act_format, self.act_scale)
-                self.layers.append(m)
+        super().__enter__()
         self.fused_layers, self._fused_modules = [], []
         if self.fused:
             for mod in self.model.modules():
@@ -1130,40 +1122,36 @@ class mx_hardware:
         return self
 
     def __exit__(self, *exc):
-        for m in self.layers:
-            m._mx_hw = None
         for mod in self._fused_modules:
             mod._mx_fused = None
+        return super().__exit__(*exc)
+
+
+def _passes_check_i8(layer: nn.Module, cls) -> bool:
+    if not isinstance(layer, cls):
         return False
+    try:
+        layer._check_i8()
+    except ValueError:
+        return False
+    return True
 
 
 def i8_hardware_eligible(layer: nn.Module) -> bool:
     """Whether ``layer`` takes the int8 GEMM under ``i8_hardware``: a built Dense layer with a range inside [-128, 127], symmetric,
     with scalar, columnwise or groupwise scales (group size a multiple of 64, or the whole input) and no element format.  Conv
     layers are judged by ``i8_conv_eligible``."""
-    if not isinstance(layer, CustomDenseLayer):
-        return False
-    try:
-        layer._check_i8()
-    except ValueError:
-        return False
-    return True
+    return _passes_check_i8(layer, CustomDenseLayer)
 
 
 def i8_conv_eligible(layer: nn.Module) -> bool:
     """Whether ``layer`` takes the int8 GEMM under ``i8_hardware(convs=True)``: a built conv layer with a range inside
     [-128, 127], symmetric, with a scalar scale or groupwise scales (group size a multiple of 64, or at least ci kh kw), no
     element format and the kernel stored "oihw" (the groups then run along the im2col operand's K)."""
-    if not isinstance(layer, _ConvBase):
-        return False
-    try:
-        layer._check_i8()
-    except ValueError:
-        return False
-    return True
+    return _passes_check_i8(layer, _ConvBase)
 
 
-class i8_hardware:
+class i8_hardware(_matrix_hardware):
     """Context manager beside ``mx_hardware``: inside it every eligible Dense layer of ``model`` (``i8_hardware_eligible``) computes
     its eval-mode ``call`` as ``call_i8`` does -- activations quantised per row and ``act_block`` inputs to symmetric 8-bit
     integers, the product on the int8 matrix instruction.  The operands and the fake-quantised biases are built ONCE, on entry,
@@ -1177,29 +1165,12 @@ class i8_hardware:
     multiplies the decoded im2col operand with the fake-quantised kernel as a (K, co) matrix by ``torch.matmul`` instead.  Without
     ``convs`` (the default) conv layers keep the fake-quantised path."""
 
+    _family, _dense_eligible, _conv_eligible = _I8, staticmethod(i8_hardware_eligible), staticmethod(i8_conv_eligible)
+
     def __init__(self, model: nn.Module, act_block=0, emulate=False, convs=False):
         self.model, self.act_block, self.emulate = model, ops.check_i8_block(act_block), bool(emulate)
-        self.convs = bool(convs)
+        self.convs, self._act = bool(convs), (self.act_block,)
         self.layers = []
-
-    def __enter__(self):
-        self.layers = [m for m in custom_layers_of(self.model) if i8_hardware_eligible(m)]
-        with torch.no_grad():
-            for m in self.layers:
-                weight = m.nested_q_w_layer(m.W).detach() if self.emulate else m.i8_operand()
-                m._i8_hw = (weight, m.nested_q_b_layer(m.b).detach(), self.act_block)
-            for m in [m for m in custom_layers_of(self.model) if i8_conv_eligible(m)] if self.convs else []:
-                # emulate: the fake-quantised kernel as the (K, co) matrix the decoded im2col operand multiplies
-                weight = m.nested_q_k_layer(m.kernel).detach().permute(3, 2, 0, 1).reshape(m.filters, -1).t() if self.emulate \
-                    else m.i8_operand()
-                m._i8_hw = (weight, m.nested_q_b_layer(m.b).detach() if m._has_bias else None, self.act_block)
-                self.layers.append(m)
-        return self
-
-    def __exit__(self, *exc):
-        for m in self.layers:
-            m._i8_hw = None
-        return False
 
 
 def mx_dense_chain(x, chain, act_format="fp8_e4m3", act_scale="mx"):
@@ -1238,7 +1209,7 @@ def mx_dense_chain(x, chain, act_format="fp8_e4m3", act_scale="mx"):
             else:
                 operand, qb = layer.mx_operand(), layer.nested_q_b_layer(layer.b)
             last = k == len(chain) - 1
-            a = layer._mx_product(a, operand, qb, act_format, act_scale, None if last else act_format, activation)
+            a = layer._matrix_product(a, operand, qb, _MX, (act_format, act_scale), None if last else act_format, activation)
         return a.reshape(*lead, a.shape[-1])
 
 

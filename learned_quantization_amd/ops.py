@@ -587,6 +587,23 @@ def mx_operand_decode(operand: MxOperand) -> torch.Tensor:
     return out
 
 
+def _gemm_output(a, b, bias: Optional[torch.Tensor], out: Optional[torch.Tensor] = None, fp32_out: bool = True):
+    """``(bias, out, ldy)`` of the product of two operands: the bias checked, ``out`` checked or made, its leading dimension.
+    ``fp32_out=False`` (the operand-out epilogue writes no fp32 matrix) checks the bias alone."""
+    M, N = a.lines, b.lines
+    if bias is not None:
+        bias = _hip.require_device_f32(bias, "bias")
+        if tuple(bias.shape) != (N,):
+            raise ValueError(f"bias must have shape ({N},), got {tuple(bias.shape)}")
+    if not fp32_out:
+        return bias, None, 0
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=a.codes.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (M, N) or (N > 1 and out.stride(1) != 1) or not out.is_cuda:
+        raise ValueError(f"out must be a float32 device matrix ({M}, {N}) with unit column stride")
+    return bias, out, out.stride(0) if M > 1 else max(N, out.stride(0))
+
+
 def mx_gemm(a: MxOperand, b: MxOperand, bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``Y (a.lines, b.lines) = A B^T (+ bias)`` in fp32 on v_mfma_scale_f32_16x16x128_f8f6f4 (include/lq_hip.h, lq_mx_gemm).
     ``out``: a float32 matrix to write into; its row stride is the leading dimension."""
@@ -596,15 +613,7 @@ def mx_gemm(a: MxOperand, b: MxOperand, bias: Optional[torch.Tensor] = None, out
     lib = _hip.load()
     M, N = a.lines, b.lines
     dev = a.codes.device
-    if bias is not None:
-        bias = _hip.require_device_f32(bias, "bias")
-        if tuple(bias.shape) != (N,):
-            raise ValueError(f"bias must have shape ({N},), got {tuple(bias.shape)}")
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.float32, device=dev)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (M, N) or (N > 1 and out.stride(1) != 1) or not out.is_cuda:
-        raise ValueError(f"out must be a float32 device matrix ({M}, {N}) with unit column stride")
-    ldy = out.stride(0) if M > 1 else max(N, out.stride(0))
+    bias, out, ldy = _gemm_output(a, b, bias, out)
     _hip.check(lib.lq_mx_gemm(_hip.ptr(a.codes), _hip.ptr(a.scales), fa.id, _hip.ptr(b.codes), _hip.ptr(b.scales), fb.id,
                               _hip.ptr(bias), _hip.ptr(out), M, N, a.K, ldy, _hip.stream_ptr(dev)), "lq_mx_gemm")
     return out
@@ -770,15 +779,7 @@ def i8_gemm(a: I8Operand, b: I8Operand, bias: Optional[torch.Tensor] = None, out
     lib = _hip.load()
     M, N = a.lines, b.lines
     dev = a.codes.device
-    if bias is not None:
-        bias = _hip.require_device_f32(bias, "bias")
-        if tuple(bias.shape) != (N,):
-            raise ValueError(f"bias must have shape ({N},), got {tuple(bias.shape)}")
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.float32, device=dev)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (M, N) or (N > 1 and out.stride(1) != 1) or not out.is_cuda:
-        raise ValueError(f"out must be a float32 device matrix ({M}, {N}) with unit column stride")
-    ldy = out.stride(0) if M > 1 else max(N, out.stride(0))
+    bias, out, ldy = _gemm_output(a, b, bias, out)
     _hip.check(lib.lq_i8_gemm(_hip.ptr(a.codes), _hip.ptr(a.scales), a.block, _hip.ptr(b.codes), _hip.ptr(b.scales), b.block,
                               _hip.ptr(bias), _hip.ptr(out), ldy, M, N, a.K, _hip.stream_ptr(dev)), "lq_i8_gemm")
     return out
@@ -807,10 +808,7 @@ def mx_gemm_quantize(a: MxOperand, b: MxOperand, bias: Optional[torch.Tensor] = 
     lib = _hip.load()
     M, N = a.lines, b.lines
     dev = a.codes.device
-    if bias is not None:
-        bias = _hip.require_device_f32(bias, "bias")
-        if tuple(bias.shape) != (N,):
-            raise ValueError(f"bias must have shape ({N},), got {tuple(bias.shape)}")
+    bias = _gemm_output(a, b, bias, fp32_out=False)[0]
     codes, scales = _mx_operand_buffers(out_format, M, N, dev)
     _hip.check(lib.lq_mx_gemm_quantize(_hip.ptr(a.codes), _hip.ptr(a.scales), fa.id, _hip.ptr(b.codes), _hip.ptr(b.scales), fb.id,
                                        _hip.ptr(bias), act, fo.id, m, _hip.ptr(codes), _hip.ptr(scales), M, N, a.K,
@@ -845,11 +843,38 @@ def mx_im2col_dims(input_shape, kernel_size, strides=(1, 1), padding=(0, 0, 0, 0
     """``(M, K, OH, OW)`` of the im2col matrix of an input ``(B, C, H, W)`` (include/lq_hip.h, lq_mx_im2col_dims): ``OH = (H + top +
     bottom - KH) // stride_h + 1``, ``M = B OH OW`` lines over ``K = C KH KW``.  ``padding`` is (top, bottom, left, right).  Needs no
     device, and answers for an ``M * K`` that the operand itself refuses."""
-    import ctypes
-    g = _conv_geom(input_shape, (0, 0, 0, 0), kernel_size, strides, padding)
-    out = [ctypes.c_int64(0) for _ in range(4)]
-    _hip.check(_hip.load().lq_mx_im2col_dims(ctypes.byref(g), *(ctypes.byref(o) for o in out)), "lq_mx_im2col_dims")
-    return tuple(int(o.value) for o in out)
+    return _geom_dims(_hip.load(), _conv_geom(input_shape, (0, 0, 0, 0), kernel_size, strides, padding))
+
+
+def _geom_dims(lib, g: "_hip.ConvGeom") -> Tuple[int, int, int, int]:
+    from ctypes import byref, c_int64
+    M, K, OH, OW = c_int64(0), c_int64(0), c_int64(0), c_int64(0)
+    _hip.check(lib.lq_mx_im2col_dims(byref(g), byref(M), byref(K), byref(OH), byref(OW)), "lq_mx_im2col_dims")
+    return M.value, K.value, OH.value, OW.value
+
+
+def _require_conv_input(x) -> None:
+    """``x`` as both im2col operands read it -- float32, four axes, any strides, on the current device -- or an exception."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError(f"x must have four axes (B, C, H, W), got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
+    if not x.is_cuda:
+        raise RuntimeError(f"x is on {x.device}: the learned-quantization ops run only on a HIP device (MI355X); there is no CPU fallback")
+    if x.dtype != torch.float32:
+        raise TypeError(f"x must be float32, got {x.dtype}")
+    if x.device.index is not None and x.device.index != torch.cuda.current_device():
+        raise RuntimeError(f"x lives on {x.device} but the current device is cuda:{torch.cuda.current_device()}: call "
+                           "torch.cuda.set_device(...) before using the ops")
+
+
+def im2col_runs(B: int, lines_per_image: int, K: int, max_lines: Optional[int] = None):
+    """``[(b0, b1), ...]``: the batch ``range(B)`` cut, in order, into runs of whole images whose im2col operand the C surface takes
+    (``lines * K < 2^31``), whose product the grid of either GEMM takes (65535 * 64 lines) and that hold at most ``max_lines``
+    lines.  A run is never shorter than one image: a single image beyond a limit is left to the C surface to refuse."""
+    fit = min(((1 << 31) - 1) // K, 65535 * 64)
+    if max_lines is not None:
+        fit = min(fit, int(max_lines))
+    images = max(1, min(B, fit // lines_per_image))
+    return [(b0, min(B, b0 + images)) for b0 in range(0, B, images)]
 
 
 def mx_operand_im2col(x: torch.Tensor, kernel_size, strides=(1, 1), padding=(0, 0, 0, 0), element_format: str = "fp8_e4m3",
@@ -861,20 +886,10 @@ def mx_operand_im2col(x: torch.Tensor, kernel_size, strides=(1, 1), padding=(0, 
     import ctypes
     fmt = check_mx_operand_format(element_format)
     m = check_mx_scale_init(method)
-    if not isinstance(x, torch.Tensor) or x.dim() != 4:
-        raise ValueError(f"x must have four axes (B, C, H, W), got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
-    if not x.is_cuda:
-        raise RuntimeError(f"x is on {x.device}: the learned-quantization ops run only on a HIP device (MI355X); there is no CPU fallback")
-    if x.dtype != torch.float32:
-        raise TypeError(f"x must be float32, got {x.dtype}")
-    if x.device.index is not None and x.device.index != torch.cuda.current_device():
-        raise RuntimeError(f"x lives on {x.device} but the current device is cuda:{torch.cuda.current_device()}: call "
-                           "torch.cuda.set_device(...) before using the ops")
+    _require_conv_input(x)
     lib = _hip.load()
     g = _conv_geom(x.shape, x.stride(), kernel_size, strides, padding)
-    dims = [ctypes.c_int64(0) for _ in range(4)]
-    _hip.check(lib.lq_mx_im2col_dims(ctypes.byref(g), *(ctypes.byref(o) for o in dims)), "lq_mx_im2col_dims")
-    M, K, OH, OW = (int(o.value) for o in dims)
+    M, K, OH, OW = _geom_dims(lib, g)
     codes, scales = _mx_operand_buffers(element_format, M, K, x.device)
     _hip.check(lib.lq_mx_operand_im2col(_hip.ptr(x), ctypes.byref(g), fmt.id, m, _hip.ptr(codes), _hip.ptr(scales),
                                         _hip.stream_ptr(x.device)), "lq_mx_operand_im2col")
@@ -897,18 +912,10 @@ def i8_operand_im2col(x: torch.Tensor, kernel_size, strides=(1, 1), padding=(0, 
     The result is an I8Operand whose ``out_hw`` is ``(OH, OW)``."""
     import ctypes
     block = check_i8_block(block)
-    if not isinstance(x, torch.Tensor) or x.dim() != 4:
-        raise ValueError(f"x must have four axes (B, C, H, W), got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
-    if not x.is_cuda:
-        raise RuntimeError(f"x is on {x.device}: the learned-quantization ops run only on a HIP device (MI355X); there is no CPU fallback")
-    if x.dtype != torch.float32:
-        raise TypeError(f"x must be float32, got {x.dtype}")
-    if x.device.index is not None and x.device.index != torch.cuda.current_device():
-        raise RuntimeError(f"x lives on {x.device} but the current device is cuda:{torch.cuda.current_device()}: call "
-                           "torch.cuda.set_device(...) before using the ops")
+    _require_conv_input(x)
     lib = _hip.load()
     g = _conv_geom(x.shape, x.stride(), kernel_size, strides, padding)
-    M, K, OH, OW = mx_im2col_dims(x.shape, kernel_size, strides, padding)
+    M, K, OH, OW = _geom_dims(lib, g)
     codes, scales = _i8_operand_buffers(M, K, block, x.device)
     _hip.check(lib.lq_i8_operand_im2col(_hip.ptr(x), ctypes.byref(g), block, _hip.ptr(codes), _hip.ptr(scales),
                                         _hip.stream_ptr(x.device)), "lq_i8_operand_im2col")

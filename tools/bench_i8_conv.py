@@ -35,7 +35,7 @@ import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
 import learned_quantization_amd as lq  # noqa: E402
-from learned_quantization_amd import _hip, ops  # noqa: E402
+from learned_quantization_amd import _hip, layers, ops  # noqa: E402
 from tools.bench_mx_conv import SHAPES  # noqa: E402
 from tools.bench_mx_gemm import timed  # noqa: E402
 
@@ -108,13 +108,14 @@ def main():
                 _hip.check(lib.lq_mx_operand_im2col(ptr(xs[i]), ctypes.byref(geoms[i]), fa, 0, ptr(mx_bufs[i][0]), ptr(mx_bufs[i][1]), sp),
                            "lq_mx_operand_im2col")
 
-            variants = {"mx_im2col": mx_im2col, "call_mx": lambda i: mx_layer._mx_conv(xs[i], mx_operand, mx_qb, MX_FORMAT, "mx"),
+            variants = {"mx_im2col": mx_im2col,
+                        "call_mx": lambda i: mx_layer._matrix_conv(xs[i], mx_operand, mx_qb, layers._MX, (MX_FORMAT, "mx")),
                         "conv2d_nchw": lambda i: conv2d(xs[i]), "conv2d_nhwc": lambda i: conv2d(xl[i])}
             for b in BLOCKS:
                 variants[f"i8_im2col_b{b}"] = i8_im2col(b)
                 variants[f"quantize_b{b}"] = quantize(b)
                 variants[f"composition_b{b}"] = lambda i, b=b: ops.i8_operand_quantize(unfolded(i), b)
-                variants[f"call_i8_b{b}"] = lambda i, b=b: layer._i8_conv(xs[i], operand, qb, b)
+                variants[f"call_i8_b{b}"] = lambda i, b=b: layer._matrix_conv(xs[i], operand, qb, layers._I8, (b,))
 
             with torch.no_grad():
                 for b in BLOCKS:                               # the gathered operand equals the composition's byte for byte: checked once

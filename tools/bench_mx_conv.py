@@ -33,7 +33,7 @@ import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
 import learned_quantization_amd as lq  # noqa: E402
-from learned_quantization_amd import _hip, ops  # noqa: E402
+from learned_quantization_amd import _hip, layers, ops  # noqa: E402
 from tools.bench_mx_gemm import timed  # noqa: E402
 
 # (name, B, C, H, W, co, k, stride)
@@ -88,10 +88,10 @@ def main():
                 return ops.mx_gemm(a, operand, qb)
 
             def mx_nchw(i):
-                return layer._mx_conv(xs[i], operand, qb, ACT_FORMAT, ACT_SCALE)
+                return layer._matrix_conv(xs[i], operand, qb, layers._MX, (ACT_FORMAT, ACT_SCALE))
 
             def mx_nhwc(i):
-                return layer._mx_conv(xl[i], operand, qb, ACT_FORMAT, ACT_SCALE)
+                return layer._matrix_conv(xl[i], operand, qb, layers._MX, (ACT_FORMAT, ACT_SCALE))
 
             def im2col(i):
                 _hip.check(lib.lq_mx_operand_im2col(ptr(xs[i]), ctypes.byref(geoms[i]), fa, 0, ptr(bufs[i][0]), ptr(bufs[i][1]), sp),

@@ -8,7 +8,7 @@ Per shape (M, K, N), fp8_e4m3 activations times fp4_e2m1 weights with a bias, an
 
   * ``gemm``         (a) lq_mx_gemm alone: the fp32 Y.
   * ``composition``  (b) lq_mx_gemm -> F.relu -> lq_mx_operand_quantize: three launches, Y written, read, written and read again.
-                         What CustomDenseLayer._mx_product and the model run between two MX layers without the epilogue: the yardstick.
+                         What CustomDenseLayer._matrix_product and the model run between two MX layers without the epilogue: the yardstick.
   * ``fused``        (c) lq_mx_gemm_quantize with LQ_ACT_RELU: one launch, the next operand only.
 
 One JSON line per shape, output format and repeat: the three medians, their min / max over the rounds, fused / composition and

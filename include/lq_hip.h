@@ -569,7 +569,24 @@ int lq_mx_operand_im2col(const float* X, const lq_conv_geom* g, int format, int 
  * M, K and block (M * K >= 2^31, a block that is negative or no multiple of 64).  LQ_EALIGN: codes or scales off the 16-byte grid, X
  * off the 4-byte grid.  ONE launch (capturable), no memset, no atomics; allocates nothing, reads no environment and writes exactly
  * code_bytes and scale_bytes.  Dilation and groups are not built.
- * Not built: an operand-out epilogue, asymmetric (offset) layers, HWIO-stored conv kernels, any backward, sub-byte packing of
+ *
+ * lq_i8_gemm_quantize: lq_i8_gemm with an operand-out epilogue.  Instead of an fp32 Y it writes the int8 operand of act(Y) for the
+ * NEXT product: L = M lines over K' = N with scale blocks of out_block.  out_codes / out_scales have
+ * lq_i8_operand_bytes(M, N, out_block) bytes, and byte for byte they are what
+ *     lq_i8_operand_quantize(act(lq_i8_gemm(a, b, bias)), M, N, out_block)
+ * writes, the padding included: codes of lines past M and of k past N up to 64 ceil(N / 64) are 0, scales of lines
+ * M .. 16 ceil(M / 16) - 1 are 1.0f.  Y is lq_i8_gemm's DEFINITION exactly (it does not depend on a tiling, so the kernel's wave
+ * shape is its own: 16 rows by 64 columns), the bias is the same single RN addition, and the scale rule and the element step are
+ * lq_i8_operand_quantize's.  `activation` is an lq_mx_activation: LQ_ACT_NONE leaves v as it is; LQ_ACT_RELU is
+ * v > 0 ? v : (v != v ? v : +0).  A (row, block) of zeros -- or all non-positive under relu -- gets scale 2^-126 and codes 0; a NaN
+ * or +-Inf value gives that one (row, block) a NaN scale and codes 0 and touches no other pair.
+ * out_block must be 64: a block of 64 outputs is the smallest the layout allows, and one thread block's 64 columns cover it.  One
+ * scale per row (0) or a larger block needs every column tile of the row before the first code: a different kernel, refused.
+ * ONE launch (capturable): no memset, no fp32 intermediate, no atomics, no workspace; it reads no environment and writes exactly
+ * code_bytes and scale_bytes.  LQ_EINVAL before any launch: everything lq_i8_gemm refuses about pointers, extents, blocks and
+ * periods (there is no ldy), out_block != 64, an unknown activation, M * N >= 2^31, M above 65535 * 64.  LQ_EALIGN: what lq_i8_gemm
+ * refuses, and out_codes or out_scales off the 16-byte grid.
+ * Not built: epilogue output blocks other than 64 (per row, 128), asymmetric (offset) layers, HWIO-stored conv kernels, any backward, sub-byte packing of
  * 4-bit codes.  */
 int lq_i8_operand_bytes(int64_t L, int64_t K, int64_t block, size_t* code_bytes, size_t* scale_bytes);
 int lq_i8_operand_pack(const float* P, const float* s, int32_t qmin, int32_t qmax, int rounding, int64_t R, int64_t C, int axis,
@@ -579,6 +596,9 @@ int lq_i8_operand_decode(const void* codes, const void* scales, int64_t L, int64
 int lq_i8_operand_im2col(const float* X, const lq_conv_geom* g, int64_t block, void* codes, void* scales, void* stream);
 int lq_i8_gemm(const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes, const void* b_scales, int64_t b_block,
                const float* bias /* may be NULL */, float* Y, int64_t ldy, int64_t M, int64_t N, int64_t K, void* stream);
+int lq_i8_gemm_quantize(const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes, const void* b_scales,
+                        int64_t b_block, const float* bias /* may be NULL */, int activation /* lq_mx_activation */,
+                        int64_t out_block, void* out_codes, void* out_scales, int64_t M, int64_t N, int64_t K, void* stream);
 
 /* ---- K4: forward and NQ backward of one tensor in a single pass (benchmark path) ---
  * Same results as lq_fq_forward followed by lq_fq_scale_grad (out, max|q| and the vote count bit for bit; on

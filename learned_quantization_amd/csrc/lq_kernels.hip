@@ -18,6 +18,7 @@
 //   lq_mx_gemm.hpp      the GEMM of two packed operands on v_mfma_scale_f32_16x16x128_f8f6f4
 //   lq_i8_operand.hpp   packed int8 operands with fp32 scales per line and scale block: pack, dynamic quantize, decode
 //   lq_i8_gemm.hpp      the GEMM of two packed int8 operands on v_mfma_i32_16x16x64_i8
+//   lq_i8_gemm_quant.hpp  the same product with an operand-out epilogue: it writes the next layer's int8 operand
 //   lq_im2col.hpp       a convolution's im2col matrix without the matrix: geometry, a line's window, the predicated gather
 //   lq_mx_conv.hpp      the MX operand of that matrix, gathered from the input in one launch
 //   lq_i8_conv.hpp      the int8 operand of the same matrix: absmax scales per (line, scale block), two passes over the gather
@@ -72,6 +73,7 @@
 #include "lq_i8_operand.hpp"
 #include "lq_i8_gemm.hpp"
 #include "lq_i8_conv.hpp"
+#include "lq_i8_gemm_quant.hpp"
 
 namespace lq {
 
@@ -2389,6 +2391,60 @@ int lq_i8_gemm(const void* a_codes, const void* a_scales, int64_t a_block, const
     if ((rc = gemm_grid(fn, (db.LT + 3) / 4, da.LT, M, grid))) return rc;
     hipLaunchKernelGGL(k_i8_gemm, grid, dim3(kBlock), 0, (hipStream_t)stream, p);
     return check_hip("int8 GEMM");
+}
+
+int lq_i8_gemm_quantize(const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes, const void* b_scales,
+                        int64_t b_block, const float* bias, int activation, int64_t out_block, void* out_codes, void* out_scales,
+                        int64_t M, int64_t N, int64_t K, void* stream) {
+    const char* fn = __func__;
+    I8OperandDims da, db, dout;
+    int rc = i8_operand_dims(fn, M, K, a_block, da);
+    if (rc || (rc = i8_operand_dims(fn, N, K, b_block, db))) return rc;
+    const int64_t lo = std::min(a_block, b_block), hi = std::max(a_block, b_block);
+    if (lo > 0 && hi % lo != 0)
+        return fail(LQ_EINVAL, "%s: scale blocks %lld and %lld: the larger must be a multiple of the smaller", fn, (long long)a_block,
+                    (long long)b_block);
+    const int64_t F = lo > 0 ? lo : hi;            // the period, as lq_i8_gemm takes it
+    const int64_t period = F > 0 ? std::min(F, K) : K;
+    if (period > 65536)
+        return fail(LQ_EINVAL, "%s: a period of %lld k between two scale changes is above 65536: the int32 sum of that many products of "
+                    "magnitude up to 2^14 could overflow", fn, (long long)period);
+    if (out_block != kI8TileK)
+        return fail(LQ_EINVAL, "%s: out_block = %lld: the epilogue writes scale blocks of %d, the columns of one thread block; one "
+                    "scale per row (0) or a larger block needs every column tile of the row before the first code", fn,
+                    (long long)out_block, kI8TileK);
+    if (activation != LQ_ACT_NONE && activation != LQ_ACT_RELU) return fail(LQ_EINVAL, "%s: bad activation %d", fn, activation);
+    if ((rc = i8_operand_dims(fn, M, N, out_block, dout))) return rc;      // M * N < 2^31
+    if ((rc = check_operand_buffers(fn, a_codes, a_scales, kI8ScaleAlign))) return rc;
+    if ((rc = check_operand_buffers(fn, b_codes, b_scales, kI8ScaleAlign))) return rc;
+    if ((rc = check_operand_buffers(fn, out_codes, out_scales, kI8ScaleAlign))) return rc;
+    if ((rc = check_gemm_bias(fn, bias))) return rc;
+    I8GemmQuantParams p{};
+    p.g.a_codes = (const uint8_t*)a_codes;
+    p.g.a_scales = (const float*)a_scales;
+    p.g.b_codes = (const uint8_t*)b_codes;
+    p.g.b_scales = (const float*)b_scales;
+    p.g.bias = bias;
+    p.g.M = (int32_t)M;
+    p.g.N = (int32_t)N;
+    p.g.MT = (int32_t)da.LT;
+    p.g.NT = (int32_t)db.LT;
+    p.g.KT = (int32_t)da.KT;
+    p.g.ps = (int32_t)(F > 0 ? std::min(F / kI8TileK, da.KT) : da.KT);
+    p.g.a_every = a_block > 0 ? (int32_t)(a_block / F) : INT32_MAX;
+    p.g.b_every = b_block > 0 ? (int32_t)(b_block / F) : INT32_MAX;
+    p.gp.lo = p.ip.lo = -127.0f;
+    p.gp.hi = p.ip.hi = 127.0f;
+    p.ip.min_value = kOperandMinScale;
+    p.codes = (uint8_t*)out_codes;
+    p.scales = (float*)out_scales;
+    p.act = activation;
+    p.OKT = (int32_t)dout.KT;
+    // along n the grid spans the padded operand, 64 OKT columns, so that its padding is written too
+    dim3 grid;
+    if ((rc = gemm_grid(fn, dout.KT, da.LT, M, grid))) return rc;
+    hipLaunchKernelGGL(k_i8_gemm_quantize, grid, dim3(kBlock), 0, (hipStream_t)stream, p);
+    return check_hip("int8 GEMM with operand-out epilogue");
 }
 
 int lq_fq_fwd_bwd_fused(const float* P, const float* s, const float* dy, float lambda, float* out, float* ds, void* ws,

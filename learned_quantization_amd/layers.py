@@ -589,6 +589,11 @@ class _MatrixFamily(NamedTuple):
     im2col: Callable          # (x, kernel_size, strides, padding, *act) -> operand
     decode: Callable          # operand -> fp32 matrix
     gemm: Callable            # (a, b, bias, out) -> fp32 matrix
+    operand_type: type        # what ``quantize`` and the epilogue return: a layer multiplies an input of this type as it is
+    gemm_quantize: Callable   # (a, b, bias, activation, out, act) -> the next layer's operand: the operand-out epilogue
+    out_name: str             # the argument of call_mx / call_i8 that asks for the epilogue
+    chain: str                # the module method that states a Dense tail for the family's fused path
+    fused: str                # the module attribute under which a context manager parks ``act`` for that tail
 
     def product(self, a, operand, qb, out=None):
         """``a`` times the layer's ``operand`` plus ``qb`` on the matrix instruction -- or, where ``operand`` is a tensor (the
@@ -599,8 +604,12 @@ class _MatrixFamily(NamedTuple):
         return y if qb is None else y.add_(qb)
 
 
-_MX = _MatrixFamily("_mx_hw", "mx_operand", ops.mx_operand_quantize, ops.mx_operand_im2col, ops.mx_operand_decode, ops.mx_gemm)
-_I8 = _MatrixFamily("_i8_hw", "i8_operand", ops.i8_operand_quantize, ops.i8_operand_im2col, ops.i8_operand_decode, ops.i8_gemm)
+_MX = _MatrixFamily("_mx_hw", "mx_operand", ops.mx_operand_quantize, ops.mx_operand_im2col, ops.mx_operand_decode, ops.mx_gemm,
+                    ops.MxOperand, lambda a, b, bias, activation, out, act: ops.mx_gemm_quantize(a, b, bias, activation, out, act[1]),
+                    "out_format", "mx_chain", "_mx_fused")
+_I8 = _MatrixFamily("_i8_hw", "i8_operand", ops.i8_operand_quantize, ops.i8_operand_im2col, ops.i8_operand_decode, ops.i8_gemm,
+                    ops.I8Operand, lambda a, b, bias, activation, out, act: ops.i8_gemm_quantize(a, b, bias, activation, out),
+                    "out_block", "i8_chain", "_i8_fused")
 
 
 def _check_max_lines(max_lines) -> None:
@@ -702,15 +711,29 @@ class CustomDenseLayer(_HostLayer):
             scale, gs = scale.reshape(1, -1).expand(1, units).contiguous(), fan_in
         return ops.i8_operand_pack(self.W.detach(), scale, qmin, qmax, gs, self.rounding)
 
-    def call_i8(self, inputs, act_block=0):
+    def call_i8(self, inputs, act_block=0, out_block=None, activation=None):
         """The layer on the int8 matrix instruction, under ``no_grad``: the inputs quantised per row and ``act_block`` consecutive
         inputs (0: per row) to symmetric 8-bit integers (ops.i8_operand_quantize), multiplied with ``i8_operand()`` by ops.i8_gemm,
-        plus the fake-quantised bias.  Inference only: there is no backward through this path."""
-        ops.check_i8_block(act_block)
+        plus the fake-quantised bias.  Inference only: there is no backward through this path.
+        ``inputs`` may be an ops.I8Operand (``lines`` rows over ``K`` = in), which is multiplied as it is; ``act_block`` is then not
+        read.  With ``out_block`` (64) the result is not the fp32 matrix but the NEXT layer's operand, ``activation`` (None or
+        "relu") applied and quantised per row and block of 64 by the product's own epilogue (ops.i8_gemm_quantize): one launch, no
+        fp32 activation in memory."""
+        given = isinstance(inputs, ops.I8Operand)
+        if not given:
+            ops.check_i8_block(act_block)
         if not self.built:
+            if given:
+                raise ValueError(f"{self.name}: the layer is not built yet (no kernel to pack)")
             self.build(tuple(inputs.shape), device=inputs.device)
+        if given:
+            self._check_operand_input(inputs)
+        if out_block is not None:
+            ops.check_i8_out_block(out_block)
+        ops.check_activation(activation)
         with torch.no_grad():
-            return self._matrix_product(inputs, self.i8_operand(), self.nested_q_b_layer(self.b), _I8, (act_block,))
+            return self._matrix_product(inputs, self.i8_operand(), self.nested_q_b_layer(self.b), _I8, (act_block,), out_block,
+                                        activation)
 
     def mx_operand(self) -> "ops.MxOperand":
         """The kernel under its current scales as an operand of the block-scaled matrix instruction (ops.mx_operand_pack): ``units``
@@ -722,26 +745,28 @@ class CustomDenseLayer(_HostLayer):
         return ops.mx_operand_pack(self.W.detach(), self.nested_q_w_layer.scale.data, self.element_format, self.group_size,
                                    self.scale_format)
 
-    def _check_mx_input(self, operand):
+    def _check_operand_input(self, operand):
         if operand.K != self.W.shape[0]:
             raise ValueError(f"{self.name}: the input operand reduces over K = {operand.K}, the layer over in = {self.W.shape[0]}")
 
-    def _matrix_product(self, inputs, operand, qb, family, act, out_format=None, activation=None):
-        """``out_format`` and ``activation``: the block-scaled path's operand-out epilogue; only that path takes an operand as input."""
+    def _matrix_product(self, inputs, operand, qb, family, act, out=None, activation=None):
+        """``out`` (the family's out_format / out_block) and ``activation``: the operand-out epilogue.  An input of the family's
+        operand type is multiplied as it is."""
         with torch.no_grad():
-            if family is _MX and isinstance(inputs, ops.MxOperand):      # a previous layer's epilogue wrote it: used as it is
-                self._check_mx_input(inputs)
+            if isinstance(inputs, family.operand_type):      # a previous layer's epilogue wrote it: used as it is
+                self._check_operand_input(inputs)
                 a, lead = inputs, (inputs.lines,)
             else:
                 a, lead = family.quantize(inputs.reshape(-1, inputs.shape[-1]), *act), tuple(inputs.shape[:-1])
-            if out_format is None:
+            if out is None:
                 if activation is not None:
-                    raise ValueError(f"{self.name}: activation={activation!r} is fused into the operand-out epilogue: give out_format")
+                    raise ValueError(f"{self.name}: activation={activation!r} is fused into the operand-out epilogue: give "
+                                     f"{family.out_name}")
                 y = family.product(a, operand, qb)
                 return y.reshape(*lead, y.shape[-1])
             if isinstance(operand, torch.Tensor):
-                raise ValueError(f"{self.name}: the emulated path has no operand-out epilogue (out_format={out_format!r})")
-            return ops.mx_gemm_quantize(a, operand, qb, activation, out_format, act[1])
+                raise ValueError(f"{self.name}: the emulated path has no operand-out epilogue ({family.out_name}={out!r})")
+            return family.gemm_quantize(a, operand, qb, activation, out, act)
 
     def call_mx(self, inputs, act_format="fp8_e4m3", act_scale="mx", out_format=None, activation=None):
         """The layer on the block-scaled matrix instruction, under ``no_grad``: the inputs quantised per block of 32 along their last
@@ -755,7 +780,7 @@ class CustomDenseLayer(_HostLayer):
                 raise ValueError(f"{self.name}: the layer is not built yet (no kernel to pack)")
             self.build(tuple(inputs.shape), device=inputs.device)
         if isinstance(inputs, ops.MxOperand):
-            self._check_mx_input(inputs)
+            self._check_operand_input(inputs)
         if out_format is not None:
             ops.check_mx_operand_format(out_format)
         ops.check_mx_activation(activation)
@@ -1070,9 +1095,20 @@ class _matrix_hardware:
                 bias = m.nested_q_b_layer(m.b).detach() if getattr(m, "_has_bias", True) else None
                 setattr(m, family.hw, (weight, bias, *self._act))
                 self.layers.append(m)
+        # fused: a module that states its Dense tail (the family's chain method) evaluates it through the family's dense chain
+        self.fused_layers, self._fused_modules = [], []
+        if self.fused:
+            for mod in self.model.modules():
+                chain = getattr(mod, family.chain)() if callable(getattr(mod, family.chain, None)) else []
+                if len(chain) > 1 and all(self._dense_eligible(layer) and act in ops.MX_ACTIVATIONS for layer, act in chain):
+                    setattr(mod, family.fused, self._act)
+                    self._fused_modules.append(mod)
+                    self.fused_layers += [layer for layer, _ in chain]
         return self
 
     def __exit__(self, *exc):
+        for mod in self._fused_modules:
+            setattr(mod, self._family.fused, None)
         for m in self.layers:
             setattr(m, self._family.hw, None)
         return False
@@ -1108,23 +1144,6 @@ class mx_hardware(_matrix_hardware):
         self.model, self.act_format, self.act_scale, self.emulate, self.fused = model, act_format, act_scale, bool(emulate), bool(fused)
         self.convs, self._act = bool(convs), (act_format, act_scale)
         self.layers, self.fused_layers, self._fused_modules = [], [], []
-
-    def __enter__(self):
-        super().__enter__()
-        self.fused_layers, self._fused_modules = [], []
-        if self.fused:
-            for mod in self.model.modules():
-                chain = mod.mx_chain() if callable(getattr(mod, "mx_chain", None)) else []
-                if len(chain) > 1 and all(mx_hardware_eligible(layer) and act in ops.MX_ACTIVATIONS for layer, act in chain):
-                    mod._mx_fused = (self.act_format, self.act_scale)
-                    self._fused_modules.append(mod)
-                    self.fused_layers += [layer for layer, _ in chain]
-        return self
-
-    def __exit__(self, *exc):
-        for mod in self._fused_modules:
-            mod._mx_fused = None
-        return super().__exit__(*exc)
 
 
 def _passes_check_i8(layer: nn.Module, cls) -> bool:
@@ -1163,14 +1182,59 @@ class i8_hardware(_matrix_hardware):
     operand, plus the fake-quantised bias; the result is a channels-last view for ``data_format="NCHW"``.  Operand and bias are
     built once, on entry, and the layer is listed in ``layers`` after the Dense layers.  Under ``emulate=True`` such a layer
     multiplies the decoded im2col operand with the fake-quantised kernel as a (K, co) matrix by ``torch.matmul`` instead.  Without
-    ``convs`` (the default) conv layers keep the fake-quantised path."""
+    ``convs`` (the default) conv layers keep the fake-quantised path.
+    ``fused=True``: a module of ``model`` that states its Dense tail as ``i8_chain()`` -- [(layer, activation), ...] with nothing but
+    relu between the layers, as models.MNISTDense does -- evaluates it in eval mode through ``i8_dense_chain``: every layer but the
+    last writes the next layer's operand from its own epilogue, and no fp32 hidden activation exists.  The epilogue writes scale
+    blocks of 64, so ``fused=True`` needs ``act_block=64`` -- then the bits are those of ``fused=False`` -- and is refused with any
+    other.  ``fused_layers`` lists the layers that fused.  ``emulate=True`` with ``fused=True`` is refused, as on ``mx_hardware``."""
 
     _family, _dense_eligible, _conv_eligible = _I8, staticmethod(i8_hardware_eligible), staticmethod(i8_conv_eligible)
 
-    def __init__(self, model: nn.Module, act_block=0, emulate=False, convs=False):
-        self.model, self.act_block, self.emulate = model, ops.check_i8_block(act_block), bool(emulate)
+    def __init__(self, model: nn.Module, act_block=0, emulate=False, convs=False, fused=False):
+        self.model, self.act_block, self.emulate, self.fused = model, ops.check_i8_block(act_block), bool(emulate), bool(fused)
+        if self.fused and self.emulate:
+            raise ValueError("i8_hardware: emulate=True with fused=True: the emulated path is the yardstick of the unfused path and "
+                             "has no operand-out epilogue")
+        if self.fused and self.act_block != ops.I8_OUT_BLOCK:
+            raise ValueError(f"i8_hardware: fused=True with act_block={self.act_block}: the epilogue writes scale blocks of "
+                             f"{ops.I8_OUT_BLOCK}, so the fused model would not be the unfused one; give act_block={ops.I8_OUT_BLOCK}")
         self.convs, self._act = bool(convs), (self.act_block,)
-        self.layers = []
+        self.layers, self.fused_layers, self._fused_modules = [], [], []
+
+
+def _dense_chain(fn, family, gemm_name, check_layer, check_act, x, chain, act, out):
+    """The body of ``mx_dense_chain`` and ``i8_dense_chain``: the chain checked before any launch, ``x`` quantised once, every layer
+    but the last through the family's operand-out epilogue (``out``), the last to fp32."""
+    chain = list(chain)
+    if not chain:
+        raise ValueError(f"{fn}: the chain is empty")
+    for k, (layer, activation) in enumerate(chain):
+        if not isinstance(layer, CustomDenseLayer):
+            raise ValueError(f"{fn}: layer {k} is a {type(layer).__name__}: only Dense layers run on the {gemm_name} GEMM")
+        if not layer.built:
+            raise ValueError(f"{fn}: {layer.name}: the layer is not built yet (no kernel to pack)")
+        try:
+            check_layer(layer)
+            ops.check_activation(activation)
+        except ValueError as e:
+            raise ValueError(f"{fn}: {layer.name}: {e}") from None
+        if k == len(chain) - 1 and activation is not None:
+            raise ValueError(f"{fn}: {layer.name}: the last layer writes fp32 and takes no activation (got {activation!r}): "
+                             "apply it to the result")
+    check_act()
+    with torch.no_grad():
+        lead = tuple(x.shape[:-1])
+        a = family.quantize(x.reshape(-1, x.shape[-1]), *act)
+        for k, (layer, activation) in enumerate(chain):
+            hw = getattr(layer, family.hw, None)
+            if hw is not None and not isinstance(hw[0], torch.Tensor):
+                operand, qb = hw[0], hw[1]
+            else:
+                operand, qb = getattr(layer, family.operand)(), layer.nested_q_b_layer(layer.b)
+            last = k == len(chain) - 1
+            a = layer._matrix_product(a, operand, qb, family, act, None if last else out, activation)
+        return a.reshape(*lead, a.shape[-1])
 
 
 def mx_dense_chain(x, chain, act_format="fp8_e4m3", act_scale="mx"):
@@ -1181,36 +1245,24 @@ def mx_dense_chain(x, chain, act_format="fp8_e4m3", act_scale="mx"):
     ..., without the fp32 activations and their launches.  Inside ``mx_hardware`` the operands and biases built on its entry are
     used, otherwise they are built here.  ValueError naming the reason for a layer that cannot take the path
     (``mx_hardware_eligible``) or an activation other than None / "relu"."""
-    chain = list(chain)
-    if not chain:
-        raise ValueError("mx_dense_chain: the chain is empty")
-    for k, (layer, activation) in enumerate(chain):
-        if not isinstance(layer, CustomDenseLayer):
-            raise ValueError(f"mx_dense_chain: layer {k} is a {type(layer).__name__}: only Dense layers run on the block-scaled GEMM")
-        if not layer.built:
-            raise ValueError(f"mx_dense_chain: {layer.name}: the layer is not built yet (no kernel to pack)")
-        try:
-            ops.check_mx_operand_layer(layer.element_format, layer.scale_format, layer.group_size)
-            ops.check_mx_activation(activation)
-        except ValueError as e:
-            raise ValueError(f"mx_dense_chain: {layer.name}: {e}") from None
-        if k == len(chain) - 1 and activation is not None:
-            raise ValueError(f"mx_dense_chain: {layer.name}: the last layer writes fp32 and takes no activation (got {activation!r}): "
-                             "apply it to the result")
-    ops.check_mx_operand_format(act_format)
-    ops.check_mx_scale_init(act_scale)
-    with torch.no_grad():
-        lead = tuple(x.shape[:-1])
-        a = ops.mx_operand_quantize(x.reshape(-1, x.shape[-1]), act_format, act_scale)
-        for k, (layer, activation) in enumerate(chain):
-            hw = getattr(layer, "_mx_hw", None)
-            if hw is not None and not isinstance(hw[0], torch.Tensor):
-                operand, qb = hw[0], hw[1]
-            else:
-                operand, qb = layer.mx_operand(), layer.nested_q_b_layer(layer.b)
-            last = k == len(chain) - 1
-            a = layer._matrix_product(a, operand, qb, _MX, (act_format, act_scale), None if last else act_format, activation)
-        return a.reshape(*lead, a.shape[-1])
+    def check_act():
+        ops.check_mx_operand_format(act_format)
+        ops.check_mx_scale_init(act_scale)
+    return _dense_chain("mx_dense_chain", _MX, "block-scaled",
+                        lambda layer: ops.check_mx_operand_layer(layer.element_format, layer.scale_format, layer.group_size), check_act,
+                        x, chain, (act_format, act_scale), act_format)
+
+
+def i8_dense_chain(x, chain, act_block=64):
+    """``chain`` = [(layer, activation), ...]: Dense layers applied one after the other on the int8 matrix instruction, under
+    ``no_grad``.  ``x`` is quantised once per row and ``act_block`` inputs (ops.i8_operand_quantize); every layer but the last goes
+    through ops.i8_gemm_quantize, which applies its activation (None or "relu") and writes the next layer's operand, per row and
+    block of 64, in the product's epilogue; the last goes through ops.i8_gemm to fp32 and takes no activation.  Bit for bit
+    ``call_i8(act_block)`` -> activation -> ``call_i8(act_block=64)`` ..., without the fp32 activations and their launches.  Inside
+    ``i8_hardware`` the operands and biases built on its entry are used, otherwise they are built here.  ValueError naming the
+    reason for a layer that cannot take the path (``i8_hardware_eligible``) or an activation other than None / "relu"."""
+    return _dense_chain("i8_dense_chain", _I8, "int8", lambda layer: layer._check_i8(), lambda: ops.check_i8_block(act_block),
+                        x, chain, (act_block,), ops.I8_OUT_BLOCK)
 
 
 def quantized_tensors(model: nn.Module):

@@ -33,7 +33,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .layers import CustomConv2DLayer, CustomDenseLayer, RandomNormal, l2, mx_dense_chain
+from .layers import CustomConv2DLayer, CustomDenseLayer, RandomNormal, i8_dense_chain, l2, mx_dense_chain
 from .losses import softmax
 
 
@@ -85,11 +85,16 @@ class MNISTDense(nn.Module):
         """The Dense tail as layers.mx_dense_chain takes it: nothing but relu lies between the two layers."""
         return [(self.dense_1, "relu"), (self.dense_2, None)]
 
+    i8_chain = mx_chain        # the same tail, as layers.i8_dense_chain takes it
+
     def logits(self, x):
         x = torch.flatten(x, 1)
         fused = getattr(self, "_mx_fused", None)
         if fused is not None and not self.training:               # inside layers.mx_hardware(..., fused=True), eval mode
             return mx_dense_chain(x, self.mx_chain(), *fused)
+        fused = getattr(self, "_i8_fused", None)
+        if fused is not None and not self.training:               # inside layers.i8_hardware(..., fused=True), eval mode
+            return i8_dense_chain(x, self.i8_chain(), *fused)
         x = F.relu(self.dense_1(x))
         return self.dense_2(x)
 

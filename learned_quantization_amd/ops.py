@@ -816,6 +816,41 @@ def mx_gemm_quantize(a: MxOperand, b: MxOperand, bias: Optional[torch.Tensor] = 
     return MxOperand(codes, scales, out_format, M, N)
 
 
+I8_ACTIVATIONS = MX_ACTIVATIONS        # the two epilogues fuse the same activations, under the same C values
+I8_OUT_BLOCK = 64                      # the scale block the int8 epilogue writes: one thread block's 64 columns
+check_activation = check_mx_activation
+
+
+def check_i8_out_block(out_block) -> int:
+    """``out_block`` of the int8 operand-out epilogue as an int, or ValueError: it writes scale blocks of 64 only."""
+    if isinstance(out_block, bool) or not isinstance(out_block, int) or out_block != I8_OUT_BLOCK:
+        raise ValueError(f"out_block={out_block!r}: the int8 operand-out epilogue writes scale blocks of {I8_OUT_BLOCK}, the columns "
+                         "of one thread block; one scale per row (0) or a larger block needs every column tile of a row before its "
+                         "first code")
+    return out_block
+
+
+def i8_gemm_quantize(a: I8Operand, b: I8Operand, bias: Optional[torch.Tensor] = None, activation=None,
+                     out_block: int = I8_OUT_BLOCK) -> I8Operand:
+    """The int8 operand of ``activation(A B^T (+ bias))`` for the next product, ``a.lines`` lines over ``K = b.lines`` with scale
+    blocks of ``out_block`` (64), written by the GEMM's own epilogue (include/lq_hip.h, lq_i8_gemm_quantize): byte for byte
+    ``i8_operand_quantize(act(i8_gemm(a, b, bias)), out_block)``, in one launch and without the fp32 matrix."""
+    out_block = check_i8_out_block(out_block)
+    act = check_activation(activation)
+    if a.K != b.K:
+        raise ValueError(f"the operands reduce over different K: {a.K} and {b.K}")
+    i8_period(a.block, b.block, a.K)
+    lib = _hip.load()
+    M, N = a.lines, b.lines
+    dev = a.codes.device
+    bias = _gemm_output(a, b, bias, fp32_out=False)[0]
+    codes, scales = _i8_operand_buffers(M, N, out_block, dev)
+    _hip.check(lib.lq_i8_gemm_quantize(_hip.ptr(a.codes), _hip.ptr(a.scales), a.block, _hip.ptr(b.codes), _hip.ptr(b.scales), b.block,
+                                       _hip.ptr(bias), act, out_block, _hip.ptr(codes), _hip.ptr(scales), M, N, a.K,
+                                       _hip.stream_ptr(dev)), "lq_i8_gemm_quantize")
+    return I8Operand(codes, scales, M, N, out_block)
+
+
 class MxConvOperand(MxOperand):
     """The MxOperand of an im2col matrix (``mx_operand_im2col``): the same five fields, and ``out_hw = (OH, OW)`` of the convolution
     whose ``lines = B * OH * OW`` it holds."""

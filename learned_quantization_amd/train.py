@@ -629,18 +629,25 @@ def build_parser():
                          "instruction, their im2col operand gathered by ops.i8_operand_im2col) and add i8_eval_conv_layers, "
                          "i8_eval_conv_accuracy and i8_eval_conv_max_logit_diff (the model's outputs against the emulated path with "
                          "convs=True) to the result line")
+    ap.add_argument("--i8-eval-fused", action="store_true",
+                    help="with --i8-eval --i8-eval-act-block 64: evaluate once more under layers.i8_hardware(fused=True) (the Dense "
+                         "tail through layers.i8_dense_chain: relu and the next operand's quantisation, per row and block of 64, in "
+                         "the GEMM's epilogue) and add i8_eval_fused_layers, i8_eval_fused_accuracy and "
+                         "i8_eval_fused_max_logit_diff (against the unfused hardware path; 0.0 is expected) to the result line")
     return ap
 
 
 @torch.no_grad()
-def i8_eval(model, x, y, act_block=0, convs=False):
+def i8_eval(model, x, y, act_block=0, convs=False, fused=False):
     """One evaluation of ``model`` on (x, y) under layers.i8_hardware, one under its ``emulate=True`` yardstick and one of the
     fake-quantised model as it stands: a dict of the three accuracies and the largest |difference| of the outputs of the last Dense
     layer that took the path (the logits of the MNIST model) between the hardware path and each of the other two.  ValueError for
     a model without a Dense layer that can take the path.  ``convs=True`` adds an evaluation under ``i8_hardware(convs=True)`` and one
     under its emulation: the number of conv layers that took the path, the accuracy, and the largest |difference| of the model's
     outputs between the two; a model without such a Dense layer is then accepted, and its Dense fields are those of the model's
-    own output with no layer switched."""
+    own output with no layer switched.  ``fused=True`` (``act_block`` must be 64) adds an evaluation under
+    ``i8_hardware(fused=True)``: the number of layers that fused, its accuracy and the largest |difference| of the model's ``logits``
+    from the unfused hardware path's (the same bits are expected: 0.0)."""
     was_training = model.training
     model.eval()
     acc, logits = [], []
@@ -665,6 +672,14 @@ def i8_eval(model, x, y, act_block=0, convs=False):
                 hook.remove()
             acc.append(float((p.argmax(1) == y).float().mean()))
             logits.append(seen[-1])
+        if fused:
+            with L.i8_hardware(model, probe.act_block, fused=True) as hwf:
+                if not hwf.fused_layers or not callable(getattr(model, "logits", None)):
+                    raise ValueError("i8_eval: fused=True needs a model whose Dense tail fuses (i8_chain() and logits(), as "
+                                     "models.MNISTDense has): nothing but relu between eligible Dense layers")
+                fused_logits, p = model.logits(x), model(x)
+                fields = {"i8_eval_fused_layers": len(hwf.fused_layers), "i8_eval_fused_accuracy": float((p.argmax(1) == y).float().mean()),
+                          "i8_eval_fused_max_logit_diff": float((fused_logits - logits[0]).abs().max())}
         if convs:
             outs = []
             for emulate in (False, True):
@@ -675,8 +690,8 @@ def i8_eval(model, x, y, act_block=0, convs=False):
                                          "instruction (a signed range of at most 8 bits, symmetric, a scalar scale or groups of a "
                                          "multiple of 64 along (ci, kh, kw), kernel stored oihw)")
                     outs.append(model(x))
-            fields = {"i8_eval_conv_layers": n_convs, "i8_eval_conv_accuracy": float((outs[0].argmax(1) == y).float().mean()),
-                      "i8_eval_conv_max_logit_diff": float((outs[0] - outs[1]).abs().max())}
+            fields.update({"i8_eval_conv_layers": n_convs, "i8_eval_conv_accuracy": float((outs[0].argmax(1) == y).float().mean()),
+                           "i8_eval_conv_max_logit_diff": float((outs[0] - outs[1]).abs().max())})
     finally:
         model.train(was_training)
     return {"i8_eval_act_block": probe.act_block, "i8_eval_layers": n_layers, "i8_eval_accuracy": acc[0],
@@ -753,6 +768,11 @@ def main(argv=None):
         ap.error("--i8-eval-act-block needs --i8-eval")
     if args.i8_eval_convs and not args.i8_eval:
         ap.error("--i8-eval-convs needs --i8-eval: it adds the conv layers to the hardware path that --i8-eval evaluates")
+    if args.i8_eval_fused and not args.i8_eval:
+        ap.error("--i8-eval-fused needs --i8-eval: it compares the fused Dense tail with the unfused hardware path")
+    if args.i8_eval_fused and args.i8_eval_act_block != 64:
+        ap.error("--i8-eval-fused needs --i8-eval-act-block 64: the epilogue writes scale blocks of 64, so under any other "
+                 "activation block the fused model would not be the unfused one")
     if args.quant_stats and args.bits is None:
         ap.error("--quant-stats needs --bits: the statistics are those of a quantizer with a range")
     if args.mx_stats and args.element_format is None:
@@ -821,7 +841,7 @@ def main(argv=None):
     quant_stats = L.quant_stats(tr.model) if args.quant_stats and rank == 0 else None      # after the clock has stopped
     mx_stats = L.mx_quant_stats(tr.model) if args.mx_stats and rank == 0 else None
     mx_eval_fields = mx_eval(tr.model, *batches[0], act_format=args.mx_eval, fused=args.mx_eval_fused, convs=args.mx_eval_convs) if args.mx_eval is not None and rank == 0 else None
-    i8_eval_fields = i8_eval(tr.model, *batches[0], act_block=args.i8_eval_act_block, convs=args.i8_eval_convs) if args.i8_eval and rank == 0 else None
+    i8_eval_fields = i8_eval(tr.model, *batches[0], act_block=args.i8_eval_act_block, convs=args.i8_eval_convs, fused=args.i8_eval_fused) if args.i8_eval and rank == 0 else None
     if rank == 0:
         n_q = sum(p.numel() for l in tr.custom_layers for p in l._regularized())
         print(json.dumps({

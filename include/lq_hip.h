@@ -586,7 +586,33 @@ int lq_mx_operand_im2col(const float* X, const lq_conv_geom* g, int format, int 
  * code_bytes and scale_bytes.  LQ_EINVAL before any launch: everything lq_i8_gemm refuses about pointers, extents, blocks and
  * periods (there is no ldy), out_block != 64, an unknown activation, M * N >= 2^31, M above 65535 * 64.  LQ_EALIGN: what lq_i8_gemm
  * refuses, and out_codes or out_scales off the 16-byte grid.
- * Not built: epilogue output blocks other than 64 (per row, 128), asymmetric (offset) layers, HWIO-stored conv kernels, any backward, sub-byte packing of
+ *
+ * OFFSETS ON THE B OPERAND (asymmetric group-wise layers, W[n][k] = q[n][k] s[n][g] + b[n][g]).  An operand's `offsets` is an fp32
+ * buffer in the layout of its scales: [nbs][16 LT], scale_bytes long, on the 16-byte grid, the offset of (block, line) at index
+ * block * 16 LT + line; offsets of lines past L are +0.0f.  Only B carries offsets; the A side (lq_i8_operand_quantize,
+ * lq_i8_operand_im2col) is unchanged, and its padded k and padded conv taps hold code 0 and so add nothing to a row sum.
+ * lq_i8_operand_pack_affine: lq_i8_operand_pack's geometry and refusals; b has the shape of s.  The codes are the clamped integers
+ * of lq_fq_forward_group_affine's LQ_Q_I8 integer view, from the same element step (u = P - b, the quotient, the rounding and the
+ * clamp); scales is s bit for bit and offsets is b bit for bit.
+ * lq_i8_operand_decode_affine: out = RN(RN((float)code * scale) + offset).  For a packed parameter this equals
+ * lq_fq_forward_group_affine's `out` as values, except for a NaN element under a valid scale (code 0 decodes as the offset).
+ * lq_i8_gemm_affine: lq_i8_gemm's refusals and periods; B's offsets change where its scales change.  DEFINITION (bit exact;
+ * tests/_i8_affine_reference.py states it in NumPy): everything of lq_i8_gemm holds, and in each period p, directly after
+ * y = RN(y + RN((float)I_p * t_p)):
+ *       R_p = sum_{k in p} a[m][k]                      exact, int32 (|R_p| <= 2^23: a period is at most 65536)
+ *       c_p = RN((float)R_p * sa[m][p])                 fp32, per row: independent of n
+ *       y   = RN(y + RN(c_p * ob[n][p]))                the product and the sum round separately
+ *   The bias follows last, as before.  A NaN offset makes its column NaN and touches nothing else.  With all offsets +-0 and
+ *   finite scales Y is lq_i8_gemm's bit for bit (y is never -0).  The definition does not depend on a tiling.
+ * lq_i8_gemm_quantize_affine: lq_i8_gemm_quantize with b_offsets: byte for byte
+ *     lq_i8_operand_quantize(act(lq_i8_gemm_affine(a, b, bias)), M, N, 64)
+ * the padding included.
+ * Each of the four is ONE launch (capturable); none allocates, uses atomics or a workspace, or reads the environment.  They refuse
+ * what their symmetric twins refuse, and LQ_EINVAL for a NULL b / offsets / b_offsets, LQ_EALIGN for b off the 4-byte grid or
+ * offsets off the 16-byte grid.  The row sums cost matrix instructions (one more per A tile and K step: 6 instead of 4 in
+ * lq_i8_gemm_affine, 5 instead of 4 in lq_i8_gemm_quantize_affine), which is why a caller opts in.
+ *
+ * Not built: epilogue output blocks other than 64 (per row, 128), offsets on the A operand (asymmetric activations), HWIO-stored conv kernels, any backward, sub-byte packing of
  * 4-bit codes.  */
 int lq_i8_operand_bytes(int64_t L, int64_t K, int64_t block, size_t* code_bytes, size_t* scale_bytes);
 int lq_i8_operand_pack(const float* P, const float* s, int32_t qmin, int32_t qmax, int rounding, int64_t R, int64_t C, int axis,
@@ -599,6 +625,17 @@ int lq_i8_gemm(const void* a_codes, const void* a_scales, int64_t a_block, const
 int lq_i8_gemm_quantize(const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes, const void* b_scales,
                         int64_t b_block, const float* bias /* may be NULL */, int activation /* lq_mx_activation */,
                         int64_t out_block, void* out_codes, void* out_scales, int64_t M, int64_t N, int64_t K, void* stream);
+int lq_i8_operand_pack_affine(const float* P, const float* s, const float* b, int32_t qmin, int32_t qmax, int rounding, int64_t R,
+                              int64_t C, int axis, int64_t gs, void* codes, void* scales, void* offsets, void* stream);
+int lq_i8_operand_decode_affine(const void* codes, const void* scales, const void* offsets, int64_t L, int64_t K, int64_t block,
+                                float* out, void* stream);
+int lq_i8_gemm_affine(const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes, const void* b_scales,
+                      const void* b_offsets, int64_t b_block, const float* bias /* may be NULL */, float* Y, int64_t ldy, int64_t M,
+                      int64_t N, int64_t K, void* stream);
+int lq_i8_gemm_quantize_affine(const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes, const void* b_scales,
+                               const void* b_offsets, int64_t b_block, const float* bias /* may be NULL */,
+                               int activation /* lq_mx_activation */, int64_t out_block, void* out_codes, void* out_scales, int64_t M,
+                               int64_t N, int64_t K, void* stream);
 
 /* ---- K4: forward and NQ backward of one tensor in a single pass (benchmark path) ---
  * Same results as lq_fq_forward followed by lq_fq_scale_grad (out, max|q| and the vote count bit for bit; on

@@ -16,7 +16,7 @@ from .ops import (difference_term, fq_backward_clip, fq_backward_group, fq_forwa
                   fq_backward_group_affine, fq_forward_group_affine, scale_init_group_minmax, GroupStats, group_stats, summarize_stats,
                   ELEMENT_FORMATS, check_element_format, fq_backward_mx, fq_forward_mx, scale_init_mx, MxStats, mx_stats, summarize_mx_stats,
                   MxOperand, mx_gemm, mx_gemm_quantize, mx_im2col_dims, mx_operand_decode, mx_operand_im2col, mx_operand_pack, mx_operand_quantize,
-                  I8Operand, check_i8_conv_operand_layer, check_i8_operand_layer, i8_gemm, i8_gemm_quantize, i8_operand_bytes, i8_operand_decode, i8_operand_im2col, i8_operand_pack, i8_operand_quantize,
+                  I8AffineOperand, I8Operand, check_i8_conv_operand_layer, check_i8_operand_layer, i8_gemm, i8_gemm_quantize, i8_operand_bytes, i8_operand_decode, i8_operand_im2col, i8_operand_pack, i8_operand_quantize,
                   my_custom_gradient, q_absmax_over_axis, q_minmax, q_pack, q_range_of, q_unique, q_unpack, quantized_integers, SCALE_INITS, scale_init_group)
 from .optim import KerasAdam, ScaleAdam, apply_constraints, non_scale_parameters, scale_parameters
 from .ddp import DataParallel, GradBucket

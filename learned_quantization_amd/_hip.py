@@ -88,6 +88,12 @@ SIGNATURES = {
     "lq_i8_gemm": (_c_int, [_c_p, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p]),
     "lq_i8_gemm_quantize": (_c_int, [_c_p, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_p, _c_int, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_i64,
                                      _c_p]),
+    "lq_i8_operand_pack_affine": (_c_int, [_c_p, _c_p, _c_p, _c_i32, _c_i32, _c_int, _c_i64, _c_i64, _c_int, _c_i64, _c_p, _c_p, _c_p,
+                                           _c_p]),
+    "lq_i8_operand_decode_affine": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p]),
+    "lq_i8_gemm_affine": (_c_int, [_c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p]),
+    "lq_i8_gemm_quantize_affine": (_c_int, [_c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_int, _c_i64, _c_p, _c_p, _c_i64,
+                                            _c_i64, _c_i64, _c_p]),
     "lq_fq_fwd_bwd_fused": (_c_int, [_c_p, _c_p, _c_p, _c_f, _c_p, _c_p, _c_p, _c_sz, _c_i64, _c_i64, _c_i64, _c_p]),
     "lq_penalty_maxbin_fwd": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_sz, _c_i64, _c_i64, _c_i64, _c_p]),
     "lq_penalty_maxbin_bwd": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_f, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p]),

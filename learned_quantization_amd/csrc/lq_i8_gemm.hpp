@@ -43,7 +43,21 @@ __device__ __forceinline__ i8_v4i i8_load_frag(const uint8_t* codes, int32_t KT,
     return f;
 }
 
-__global__ __launch_bounds__(kBlock) void k_i8_gemm(const I8GemmParams p) {
+// B with an offset per (line, scale block) (lq_hip.h: lq_i8_gemm_affine): W = q s + b adds, per period, RN(c_p * ob[n][p]) with
+// c_p = RN((float)R_p * sa[m][p]) and R_p the exact row sum of A's codes over the period.
+struct I8GemmAffineParams : I8GemmParams {
+    const float* b_offsets;   // [b_nbs][16 NT], the layout of b_scales
+};
+
+// the B fragment whose 64 x 16 codes are all 1: the instruction then sums A's codes over the step, and the result tile holds that
+// row sum for rows 4 (lane >> 4) + r in register r of every lane -- the layout of y[..][..][r], no cross-lane step
+__device__ __forceinline__ i8_v4i i8_ones_frag() { return i8_v4i{0x01010101, 0x01010101, 0x01010101, 0x01010101}; }
+
+// AFF false: the symmetric product.  AFF true: one more instruction per A tile and K step for the row sums (6 per step instead of
+// 4), and at a period's end c once per row, then one product and one add per element, after the symmetric term.  B's offsets are
+// loaded where its scales are, from the same index.
+template <bool AFF>
+__global__ __launch_bounds__(kBlock) void k_i8_gemm(const std::conditional_t<AFF, I8GemmAffineParams, I8GemmParams> p) {
     const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
     const int32_t mt0 = ((int32_t)blockIdx.y * 2 + (wave & 1)) * 2;
     const int32_t nt0 = ((int32_t)blockIdx.x * 2 + (wave >> 1)) * 2;
@@ -61,6 +75,16 @@ __global__ __launch_bounds__(kBlock) void k_i8_gemm(const I8GemmParams p) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) y[i][j][r] = 0.f;
         }
+    [[maybe_unused]] i8_v4i racc[2] = {i8_v4i{0, 0, 0, 0}, i8_v4i{0, 0, 0, 0}};      // AFF: the row sums of A's tiles
+    [[maybe_unused]] const float* ob_base[2] = {nullptr, nullptr};
+    [[maybe_unused]] float ob[2] = {0.f, 0.f};
+    if constexpr (AFF) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            ob_base[j] = p.b_offsets + nt[j] * kI8TileLines + (lane & 15);
+            ob[j] = ob_base[j][0];
+        }
+    }
 
     // the lane's scales of the running period: rows 4 (lane >> 4) + r of A's tiles, column (lane & 15) of B's
     const float* sa_base[2];
@@ -101,6 +125,10 @@ __global__ __launch_bounds__(kBlock) void k_i8_gemm(const I8GemmParams p) {
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[i], b[j], acc[i][j], 0, 0, 0);
+        if constexpr (AFF) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) racc[i] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[i], i8_ones_frag(), racc[i], 0, 0, 0);
+        }
         if (--left == 0 || kt == p.KT - 1) {      // kernel-uniform: the period ends
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
@@ -114,6 +142,15 @@ __global__ __launch_bounds__(kBlock) void k_i8_gemm(const I8GemmParams p) {
                     }
                     acc[i][j] = i8_v4i{0, 0, 0, 0};
                 }
+                if constexpr (AFF) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float c = __fmul_rn((float)racc[i][r], sar[r]);
+#pragma unroll
+                        for (int j = 0; j < 2; ++j) y[i][j][r] = __fadd_rn(y[i][j][r], __fmul_rn(c, ob[j]));
+                    }
+                    racc[i] = i8_v4i{0, 0, 0, 0};
+                }
             }
             left = p.ps;
             if (++ca == p.a_every) { ca = 0; ++ia; }
@@ -123,6 +160,7 @@ __global__ __launch_bounds__(kBlock) void k_i8_gemm(const I8GemmParams p) {
                 for (int i = 0; i < 2; ++i) {
                     sa[i] = *reinterpret_cast<const float4*>(sa_base[i] + ia * a_row);
                     sb[i] = sb_base[i][ib * b_row];
+                    if constexpr (AFF) ob[i] = ob_base[i][ib * b_row];
                 }
             }
         }

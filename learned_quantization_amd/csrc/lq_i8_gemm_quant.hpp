@@ -37,7 +37,14 @@ __device__ __forceinline__ void i8_merge_dpp(InitAcc& a) {
                                0.0, mx_dpp<CTRL>(a.bad));
 }
 
-__global__ __launch_bounds__(kBlock) void k_i8_gemm_quantize(const I8GemmQuantParams p) {
+struct I8GemmQuantAffineParams : I8GemmQuantParams {
+    const float* b_offsets;   // [b_nbs][16 NT], the layout of b_scales
+};
+
+// AFF: k_i8_gemm<true>'s offset term in this kernel's tiling -- one more instruction per K step for the wave's one A tile (5 instead
+// of 4), and at a period's end c once per row, then one product and one add per element
+template <bool AFF>
+__global__ __launch_bounds__(kBlock) void k_i8_gemm_quantize(const std::conditional_t<AFF, I8GemmQuantAffineParams, I8GemmQuantParams> p) {
     using Step = GroupStep<true, GroupParams>;
     const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
     const int32_t mt = (int32_t)blockIdx.y * 4 + wave;
@@ -67,6 +74,16 @@ __global__ __launch_bounds__(kBlock) void k_i8_gemm_quantize(const I8GemmQuantPa
     float sb[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) sb[j] = sb_base[j][0];
+    [[maybe_unused]] i8_v4i racc = i8_v4i{0, 0, 0, 0};      // AFF: the row sums of A's tile
+    [[maybe_unused]] const float* ob_base[4] = {nullptr, nullptr, nullptr, nullptr};
+    [[maybe_unused]] float ob[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (AFF) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            ob_base[j] = p.b_offsets + nt[j] * kI8TileLines + (lane & 15);
+            ob[j] = ob_base[j][0];
+        }
+    }
 
     i8_v4i a, an, b[4], bn[4];
     an = i8_load_frag(p.g.a_codes, p.g.KT, mt, 0, lane);
@@ -85,6 +102,7 @@ __global__ __launch_bounds__(kBlock) void k_i8_gemm_quantize(const I8GemmQuantPa
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b[j], acc[j], 0, 0, 0);
+        if constexpr (AFF) racc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, i8_ones_frag(), racc, 0, 0, 0);
         if (--left == 0 || kt == p.g.KT - 1) {         // kernel-uniform: the period ends; lq_i8_gemm's three roundings
             const float sar[4] = {sa.x, sa.y, sa.z, sa.w};
 #pragma unroll
@@ -96,6 +114,15 @@ __global__ __launch_bounds__(kBlock) void k_i8_gemm_quantize(const I8GemmQuantPa
                 }
                 acc[j] = i8_v4i{0, 0, 0, 0};
             }
+            if constexpr (AFF) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float c = __fmul_rn((float)racc[r], sar[r]);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) y[j][r] = __fadd_rn(y[j][r], __fmul_rn(c, ob[j]));
+                }
+                racc = i8_v4i{0, 0, 0, 0};
+            }
             left = p.g.ps;
             if (++ca == p.g.a_every) { ca = 0; ++ia; }
             if (++cb == p.g.b_every) { cb = 0; ++ib; }
@@ -103,6 +130,10 @@ __global__ __launch_bounds__(kBlock) void k_i8_gemm_quantize(const I8GemmQuantPa
                 sa = *reinterpret_cast<const float4*>(sa_base + ia * a_row);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) sb[j] = sb_base[j][ib * b_row];
+                if constexpr (AFF) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) ob[j] = ob_base[j][ib * b_row];
+                }
             }
         }
     }

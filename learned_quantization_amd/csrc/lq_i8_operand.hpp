@@ -60,9 +60,17 @@ struct I8PackParams {
     int32_t LT, KT;
 };
 
-// LINE_FAST: neighbouring threads hold neighbouring lines (the parameter's contiguous axis under axis 0), else neighbouring k runs
-template <bool RNE, bool LINE_FAST>
-__global__ __launch_bounds__(kBlock) void k_i8_pack(const I8PackParams op) {
+// with an offset per group (lq_i8_operand_pack_affine): b in the layout of s, offsets in the layout of scales
+struct I8PackAffineParams : I8PackParams {
+    const float* b;
+    float* offsets;
+};
+
+// LINE_FAST: neighbouring threads hold neighbouring lines (the parameter's contiguous axis under axis 0), else neighbouring k runs.
+// AFF: the element step of lq_fq_forward_group_affine, u = P - b before the quotient, and the offset of a scale block carried
+// across like its scale; lines past L get offset +0.
+template <bool RNE, bool LINE_FAST, bool AFF = false>
+__global__ __launch_bounds__(kBlock) void k_i8_pack(const std::conditional_t<AFF, I8PackAffineParams, I8PackParams> op) {
     using Step = GroupStep<RNE, GroupParams>;
     const int64_t lines = (int64_t)op.LT * kI8TileLines, runs = (int64_t)op.KT * 4;
     const int64_t tid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -74,6 +82,10 @@ __global__ __launch_bounds__(kBlock) void k_i8_pack(const I8PackParams op) {
     uint32_t w[4] = {0u, 0u, 0u, 0u};
     float s = 1.0f;
     if (live) s = op.g.s[(int64_t)ln * op.s_line_stride + (int64_t)blk * op.s_blk_stride];
+    [[maybe_unused]] float b = 0.f;
+    if constexpr (AFF) {
+        if (live) b = op.b[(int64_t)ln * op.s_line_stride + (int64_t)blk * op.s_blk_stride];
+    }
     if (live) {
         const Ctx c = Step::ctx(op.g, s);
         const int n = min(16, op.K - k0);
@@ -81,14 +93,19 @@ __global__ __launch_bounds__(kBlock) void k_i8_pack(const I8PackParams op) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             if (j < n) {
-                const float q = Step::quant(op.g, c, div_by_uniform(src[(int64_t)j * op.k_stride], c));
+                float u = src[(int64_t)j * op.k_stride];
+                if constexpr (AFF) u = u - b;
+                const float q = Step::quant(op.g, c, div_by_uniform(u, c));
                 w[j >> 2] |= i8_view_byte(Step::view(op.g, q)) << (8 * (j & 3));
             }
         }
     }
     *reinterpret_cast<uint4*>(op.codes + i8_code_offset(op.KT, ln, k0)) = make_uint4(w[0], w[1], w[2], w[3]);
     // the first run of a scale block carries its scale across, bit for bit
-    if (k0 < op.K && (op.block ? k0 % op.block == 0 : k0 == 0)) op.scales[(int64_t)blk * lines + ln] = s;
+    if (k0 < op.K && (op.block ? k0 % op.block == 0 : k0 == 0)) {
+        op.scales[(int64_t)blk * lines + ln] = s;
+        if constexpr (AFF) op.offsets[(int64_t)blk * lines + ln] = b;
+    }
 }
 
 struct I8QuantParams {
@@ -190,6 +207,11 @@ struct I8DecodeParams {
     int32_t L, K, block, LT, KT;
 };
 
+struct I8DecodeAffineParams {
+    I8DecodeParams d;
+    const float* offsets;     // the layout of scales
+};
+
 __global__ __launch_bounds__(kBlock) void k_i8_decode(const I8DecodeParams dp) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= (int64_t)dp.L * dp.K) return;
@@ -197,6 +219,18 @@ __global__ __launch_bounds__(kBlock) void k_i8_decode(const I8DecodeParams dp) {
     const int32_t blk = dp.block ? k / dp.block : 0;
     const float code = (float)(int8_t)dp.codes[i8_code_offset(dp.KT, ln, k)];
     dp.out[i] = code * dp.scales[(int64_t)blk * dp.LT * kI8TileLines + ln];
+}
+
+// out = RN(RN(code * scale) + offset): the two roundings of lq_fq_forward_group_affine's out
+__global__ __launch_bounds__(kBlock) void k_i8_decode_affine(const I8DecodeAffineParams ap) {
+    const I8DecodeParams& dp = ap.d;
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= (int64_t)dp.L * dp.K) return;
+    const int32_t ln = (int32_t)(i / dp.K), k = (int32_t)(i % dp.K);
+    const int32_t blk = dp.block ? k / dp.block : 0;
+    const float code = (float)(int8_t)dp.codes[i8_code_offset(dp.KT, ln, k)];
+    const int64_t si = (int64_t)blk * dp.LT * kI8TileLines + ln;
+    dp.out[i] = __fadd_rn(__fmul_rn(code, dp.scales[si]), ap.offsets[si]);
 }
 
 }  // namespace lq

@@ -2212,13 +2212,24 @@ int lq_i8_operand_bytes(int64_t L, int64_t K, int64_t block, size_t* code_bytes,
     return LQ_OK;
 }
 
-int lq_i8_operand_pack(const float* P, const float* s, int32_t qmin, int32_t qmax, int rounding, int64_t R, int64_t C, int axis,
-                       int64_t gs, void* codes, void* scales, void* stream) {
-    const char* fn = __func__;
+// an operand's offsets (the affine entry points): a buffer in the layout of its scales, on the same grid
+static int check_operand_offsets(const char* fn, const void* offsets) {
+    if (!offsets) return fail(LQ_EINVAL, "%s: argument 'offsets' is NULL", fn);
+    if (!aligned(offsets, kI8ScaleAlign)) return fail(LQ_EALIGN, "%s: offsets is not %d-byte aligned", fn, kI8ScaleAlign);
+    return LQ_OK;
+}
+
+// lq_i8_operand_pack (b == NULL, offsets == NULL, affine false) and lq_i8_operand_pack_affine: one geometry, one set of refusals
+static int i8_operand_pack(const char* fn, bool affine, const float* P, const float* s, const float* b, int32_t qmin, int32_t qmax,
+                           int rounding, int64_t R, int64_t C, int axis, int64_t gs, void* codes, void* scales, void* offsets,
+                           void* stream) {
     int rc = check_group(fn, R, C, axis, gs);
     if (rc) return rc;
     LQ_REQUIRE_PTR_FN(fn, P);
     LQ_REQUIRE_PTR_FN(fn, s);
+    if (affine) {
+        LQ_REQUIRE_PTR_FN(fn, b);
+    }
     if ((rc = check_clip_range(fn, qmin, qmax))) return rc;
     if ((rc = check_rounding(fn, rounding))) return rc;
     if (qmin < -128 || qmax > 127)
@@ -2232,6 +2243,7 @@ int lq_i8_operand_pack(const float* P, const float* s, int32_t qmin, int32_t qma
     I8OperandDims d;
     if ((rc = i8_operand_dims(fn, L, K, block, d))) return rc;
     if ((rc = check_operand_buffers(fn, codes, scales, kI8ScaleAlign))) return rc;
+    if (affine && (rc = check_operand_offsets(fn, offsets))) return rc;
     I8PackParams op{};
     op.g = group_params(P, s, qmin, qmax, R, C, axis, gs);
     op.codes = (uint8_t*)codes;
@@ -2249,6 +2261,20 @@ int lq_i8_operand_pack(const float* P, const float* s, int32_t qmin, int32_t qma
     const dim3 grid((unsigned)((threads + kBlock - 1) / kBlock)), blk(kBlock);
     hipStream_t st = (hipStream_t)stream;
     const bool rne = rounding == LQ_ROUND_NEAREST_EVEN;
+    if (affine) {
+        I8PackAffineParams ap{};
+        static_cast<I8PackParams&>(ap) = op;
+        ap.b = b;
+        ap.offsets = (float*)offsets;
+        if (axis == 0) {
+            if (rne) hipLaunchKernelGGL((k_i8_pack<true, true, true>), grid, blk, 0, st, ap);
+            else hipLaunchKernelGGL((k_i8_pack<false, true, true>), grid, blk, 0, st, ap);
+        } else {
+            if (rne) hipLaunchKernelGGL((k_i8_pack<true, false, true>), grid, blk, 0, st, ap);
+            else hipLaunchKernelGGL((k_i8_pack<false, false, true>), grid, blk, 0, st, ap);
+        }
+        return check_hip("int8 operand pack with offsets");
+    }
     if (axis == 0) {
         if (rne) hipLaunchKernelGGL((k_i8_pack<true, true>), grid, blk, 0, st, op);
         else hipLaunchKernelGGL((k_i8_pack<false, true>), grid, blk, 0, st, op);
@@ -2257,6 +2283,16 @@ int lq_i8_operand_pack(const float* P, const float* s, int32_t qmin, int32_t qma
         else hipLaunchKernelGGL((k_i8_pack<false, false>), grid, blk, 0, st, op);
     }
     return check_hip("int8 operand pack");
+}
+
+int lq_i8_operand_pack(const float* P, const float* s, int32_t qmin, int32_t qmax, int rounding, int64_t R, int64_t C, int axis,
+                       int64_t gs, void* codes, void* scales, void* stream) {
+    return i8_operand_pack(__func__, false, P, s, nullptr, qmin, qmax, rounding, R, C, axis, gs, codes, scales, nullptr, stream);
+}
+
+int lq_i8_operand_pack_affine(const float* P, const float* s, const float* b, int32_t qmin, int32_t qmax, int rounding, int64_t R,
+                              int64_t C, int axis, int64_t gs, void* codes, void* scales, void* offsets, void* stream) {
+    return i8_operand_pack(__func__, true, P, s, b, qmin, qmax, rounding, R, C, axis, gs, codes, scales, offsets, stream);
 }
 
 int lq_i8_operand_quantize(const float* X, int64_t M, int64_t K, int64_t block, void* codes, void* scales, void* stream) {
@@ -2332,12 +2368,13 @@ int lq_i8_operand_im2col(const float* X, const lq_conv_geom* g, int64_t block, v
     return check_hip("int8 im2col operand");
 }
 
-int lq_i8_operand_decode(const void* codes, const void* scales, int64_t L, int64_t K, int64_t block, float* out, void* stream) {
-    const char* fn = __func__;
+static int i8_operand_decode(const char* fn, bool affine, const void* codes, const void* scales, const void* offsets, int64_t L,
+                             int64_t K, int64_t block, float* out, void* stream) {
     I8OperandDims d;
     int rc = i8_operand_dims(fn, L, K, block, d);
     if (rc) return rc;
     if ((rc = check_operand_buffers(fn, codes, scales, kI8ScaleAlign))) return rc;
+    if (affine && (rc = check_operand_offsets(fn, offsets))) return rc;
     LQ_REQUIRE_PTR_FN(fn, out);
     I8DecodeParams dp{};
     dp.codes = (const uint8_t*)codes;
@@ -2349,13 +2386,31 @@ int lq_i8_operand_decode(const void* codes, const void* scales, int64_t L, int64
     dp.LT = (int32_t)d.LT;
     dp.KT = (int32_t)d.KT;
     const int64_t n = L * K;
-    hipLaunchKernelGGL(k_i8_decode, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream, dp);
+    const dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
+    if (affine) {
+        I8DecodeAffineParams ap{};
+        ap.d = dp;
+        ap.offsets = (const float*)offsets;
+        hipLaunchKernelGGL(k_i8_decode_affine, grid, dim3(kBlock), 0, (hipStream_t)stream, ap);
+        return check_hip("int8 operand decode with offsets");
+    }
+    hipLaunchKernelGGL(k_i8_decode, grid, dim3(kBlock), 0, (hipStream_t)stream, dp);
     return check_hip("int8 operand decode");
 }
 
-int lq_i8_gemm(const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes, const void* b_scales, int64_t b_block,
-               const float* bias, float* Y, int64_t ldy, int64_t M, int64_t N, int64_t K, void* stream) {
-    const char* fn = __func__;
+int lq_i8_operand_decode(const void* codes, const void* scales, int64_t L, int64_t K, int64_t block, float* out, void* stream) {
+    return i8_operand_decode(__func__, false, codes, scales, nullptr, L, K, block, out, stream);
+}
+
+int lq_i8_operand_decode_affine(const void* codes, const void* scales, const void* offsets, int64_t L, int64_t K, int64_t block,
+                                float* out, void* stream) {
+    return i8_operand_decode(__func__, true, codes, scales, offsets, L, K, block, out, stream);
+}
+
+// lq_i8_gemm (b_offsets == NULL, affine false) and lq_i8_gemm_affine: one set of refusals, one period rule, one grid
+static int i8_gemm(const char* fn, bool affine, const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes,
+                   const void* b_scales, const void* b_offsets, int64_t b_block, const float* bias, float* Y, int64_t ldy, int64_t M,
+                   int64_t N, int64_t K, void* stream) {
     I8OperandDims da, db;
     int rc = i8_operand_dims(fn, M, K, a_block, da);
     if (rc || (rc = i8_operand_dims(fn, N, K, b_block, db))) return rc;
@@ -2370,6 +2425,7 @@ int lq_i8_gemm(const void* a_codes, const void* a_scales, int64_t a_block, const
                     "magnitude up to 2^14 could overflow", fn, (long long)period);
     if ((rc = check_operand_buffers(fn, a_codes, a_scales, kI8ScaleAlign))) return rc;
     if ((rc = check_operand_buffers(fn, b_codes, b_scales, kI8ScaleAlign))) return rc;
+    if (affine && (rc = check_operand_offsets(fn, b_offsets))) return rc;
     if ((rc = check_gemm_output(fn, bias, Y, ldy, M, N))) return rc;
     I8GemmParams p{};
     p.a_codes = (const uint8_t*)a_codes;
@@ -2389,14 +2445,32 @@ int lq_i8_gemm(const void* a_codes, const void* a_scales, int64_t a_block, const
     p.b_every = b_block > 0 ? (int32_t)(b_block / F) : INT32_MAX;
     dim3 grid;
     if ((rc = gemm_grid(fn, (db.LT + 3) / 4, da.LT, M, grid))) return rc;
-    hipLaunchKernelGGL(k_i8_gemm, grid, dim3(kBlock), 0, (hipStream_t)stream, p);
+    if (affine) {
+        I8GemmAffineParams ap{};
+        static_cast<I8GemmParams&>(ap) = p;
+        ap.b_offsets = (const float*)b_offsets;
+        hipLaunchKernelGGL(k_i8_gemm<true>, grid, dim3(kBlock), 0, (hipStream_t)stream, ap);
+        return check_hip("int8 GEMM with offsets");
+    }
+    hipLaunchKernelGGL(k_i8_gemm<false>, grid, dim3(kBlock), 0, (hipStream_t)stream, p);
     return check_hip("int8 GEMM");
 }
 
-int lq_i8_gemm_quantize(const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes, const void* b_scales,
-                        int64_t b_block, const float* bias, int activation, int64_t out_block, void* out_codes, void* out_scales,
-                        int64_t M, int64_t N, int64_t K, void* stream) {
-    const char* fn = __func__;
+int lq_i8_gemm(const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes, const void* b_scales, int64_t b_block,
+               const float* bias, float* Y, int64_t ldy, int64_t M, int64_t N, int64_t K, void* stream) {
+    return i8_gemm(__func__, false, a_codes, a_scales, a_block, b_codes, b_scales, nullptr, b_block, bias, Y, ldy, M, N, K, stream);
+}
+
+int lq_i8_gemm_affine(const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes, const void* b_scales,
+                      const void* b_offsets, int64_t b_block, const float* bias, float* Y, int64_t ldy, int64_t M, int64_t N,
+                      int64_t K, void* stream) {
+    return i8_gemm(__func__, true, a_codes, a_scales, a_block, b_codes, b_scales, b_offsets, b_block, bias, Y, ldy, M, N, K, stream);
+}
+
+static int i8_gemm_quantize(const char* fn, bool affine, const void* a_codes, const void* a_scales, int64_t a_block,
+                            const void* b_codes, const void* b_scales, const void* b_offsets, int64_t b_block, const float* bias,
+                            int activation, int64_t out_block, void* out_codes, void* out_scales, int64_t M, int64_t N, int64_t K,
+                            void* stream) {
     I8OperandDims da, db, dout;
     int rc = i8_operand_dims(fn, M, K, a_block, da);
     if (rc || (rc = i8_operand_dims(fn, N, K, b_block, db))) return rc;
@@ -2417,6 +2491,7 @@ int lq_i8_gemm_quantize(const void* a_codes, const void* a_scales, int64_t a_blo
     if ((rc = i8_operand_dims(fn, M, N, out_block, dout))) return rc;      // M * N < 2^31
     if ((rc = check_operand_buffers(fn, a_codes, a_scales, kI8ScaleAlign))) return rc;
     if ((rc = check_operand_buffers(fn, b_codes, b_scales, kI8ScaleAlign))) return rc;
+    if (affine && (rc = check_operand_offsets(fn, b_offsets))) return rc;
     if ((rc = check_operand_buffers(fn, out_codes, out_scales, kI8ScaleAlign))) return rc;
     if ((rc = check_gemm_bias(fn, bias))) return rc;
     I8GemmQuantParams p{};
@@ -2443,8 +2518,29 @@ int lq_i8_gemm_quantize(const void* a_codes, const void* a_scales, int64_t a_blo
     // along n the grid spans the padded operand, 64 OKT columns, so that its padding is written too
     dim3 grid;
     if ((rc = gemm_grid(fn, dout.KT, da.LT, M, grid))) return rc;
-    hipLaunchKernelGGL(k_i8_gemm_quantize, grid, dim3(kBlock), 0, (hipStream_t)stream, p);
+    if (affine) {
+        I8GemmQuantAffineParams ap{};
+        static_cast<I8GemmQuantParams&>(ap) = p;
+        ap.b_offsets = (const float*)b_offsets;
+        hipLaunchKernelGGL(k_i8_gemm_quantize<true>, grid, dim3(kBlock), 0, (hipStream_t)stream, ap);
+        return check_hip("int8 GEMM with offsets and operand-out epilogue");
+    }
+    hipLaunchKernelGGL(k_i8_gemm_quantize<false>, grid, dim3(kBlock), 0, (hipStream_t)stream, p);
     return check_hip("int8 GEMM with operand-out epilogue");
+}
+
+int lq_i8_gemm_quantize(const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes, const void* b_scales,
+                        int64_t b_block, const float* bias, int activation, int64_t out_block, void* out_codes, void* out_scales,
+                        int64_t M, int64_t N, int64_t K, void* stream) {
+    return i8_gemm_quantize(__func__, false, a_codes, a_scales, a_block, b_codes, b_scales, nullptr, b_block, bias, activation,
+                            out_block, out_codes, out_scales, M, N, K, stream);
+}
+
+int lq_i8_gemm_quantize_affine(const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes, const void* b_scales,
+                               const void* b_offsets, int64_t b_block, const float* bias, int activation, int64_t out_block,
+                               void* out_codes, void* out_scales, int64_t M, int64_t N, int64_t K, void* stream) {
+    return i8_gemm_quantize(__func__, true, a_codes, a_scales, a_block, b_codes, b_scales, b_offsets, b_block, bias, activation,
+                            out_block, out_codes, out_scales, M, N, K, stream);
 }
 
 int lq_fq_fwd_bwd_fused(const float* P, const float* s, const float* dy, float lambda, float* out, float* ds, void* ws,

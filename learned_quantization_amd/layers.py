@@ -593,7 +593,7 @@ class _MatrixFamily(NamedTuple):
     gemm_quantize: Callable   # (a, b, bias, activation, out, act) -> the next layer's operand: the operand-out epilogue
     out_name: str             # the argument of call_mx / call_i8 that asks for the epilogue
     chain: str                # the module method that states a Dense tail for the family's fused path
-    fused: str                # the module attribute under which a context manager parks ``act`` for that tail
+    fused: str                # the module attribute under which a context manager parks ``(act, keywords)`` for that tail
 
     def product(self, a, operand, qb, out=None):
         """``a`` times the layer's ``operand`` plus ``qb`` on the matrix instruction -- or, where ``operand`` is a tensor (the
@@ -689,36 +689,40 @@ class CustomDenseLayer(_HostLayer):
 
     forward = call
 
-    def _check_i8(self):
-        """(qmin, qmax) of a layer that can run on the int8 matrix instruction, or ValueError naming the reason."""
+    def _check_i8(self, offsets=False):
+        """(qmin, qmax) of a layer that can run on the int8 matrix instruction, or ValueError naming the reason.  ``offsets=True``
+        lets an asymmetric layer pass (ops.check_i8_operand_layer)."""
         q_range = ops.check_i8_operand_layer(self.q_range, self.nested_q_w_layer.orientation, self.group_size, self.asymmetric,
-                                             self.element_format, self.W.shape[0] if self.built else None)
+                                             self.element_format, self.W.shape[0] if self.built else None, offsets=offsets)
         if not self.built:
             raise ValueError(f"{self.name}: the layer is not built yet (no kernel to pack)")
         return q_range
 
-    def i8_operand(self) -> "ops.I8Operand":
+    def i8_operand(self, offsets=False) -> "ops.I8Operand":
         """The kernel under its current scales as an operand of the int8 matrix instruction (ops.i8_operand_pack): ``units`` lines
         over K = in.  A "groupwise" layer passes its scale as it is; a "scalar" or "columnwise" layer its scale broadcast to
         ``(1, out)``, one group per output unit.  ValueError naming the reason for a layer without a range, with a range outside
-        [-128, 127], with an offset, with "rowwise" scales, with an element format, or not built."""
-        qmin, qmax = self._check_i8()
+        [-128, 127], with an offset, with "rowwise" scales, with an element format, or not built.
+        ``offsets=True``: an asymmetric layer is packed with its ``(nb, out)`` scale and offset into an ops.I8AffineOperand, whose
+        product adds the offset's row-sum term; a symmetric layer takes the path it always took."""
+        qmin, qmax = self._check_i8(offsets)
         fan_in, units = self.W.shape
         scale = self.nested_q_w_layer.scale.data
         if self.nested_q_w_layer.orientation == "groupwise":
             gs = self.group_size
         else:
             scale, gs = scale.reshape(1, -1).expand(1, units).contiguous(), fan_in
-        return ops.i8_operand_pack(self.W.detach(), scale, qmin, qmax, gs, self.rounding)
+        offset = self.nested_q_w_layer.offset.data if self.asymmetric else None
+        return ops.i8_operand_pack(self.W.detach(), scale, qmin, qmax, gs, self.rounding, offset)
 
-    def call_i8(self, inputs, act_block=0, out_block=None, activation=None):
+    def call_i8(self, inputs, act_block=0, out_block=None, activation=None, offsets=False):
         """The layer on the int8 matrix instruction, under ``no_grad``: the inputs quantised per row and ``act_block`` consecutive
         inputs (0: per row) to symmetric 8-bit integers (ops.i8_operand_quantize), multiplied with ``i8_operand()`` by ops.i8_gemm,
         plus the fake-quantised bias.  Inference only: there is no backward through this path.
         ``inputs`` may be an ops.I8Operand (``lines`` rows over ``K`` = in), which is multiplied as it is; ``act_block`` is then not
         read.  With ``out_block`` (64) the result is not the fp32 matrix but the NEXT layer's operand, ``activation`` (None or
         "relu") applied and quantised per row and block of 64 by the product's own epilogue (ops.i8_gemm_quantize): one launch, no
-        fp32 activation in memory."""
+        fp32 activation in memory.  ``offsets=True`` lets an asymmetric layer run (``i8_operand(offsets=True)``)."""
         given = isinstance(inputs, ops.I8Operand)
         if not given:
             ops.check_i8_block(act_block)
@@ -732,7 +736,7 @@ class CustomDenseLayer(_HostLayer):
             ops.check_i8_out_block(out_block)
         ops.check_activation(activation)
         with torch.no_grad():
-            return self._matrix_product(inputs, self.i8_operand(), self.nested_q_b_layer(self.b), _I8, (act_block,), out_block,
+            return self._matrix_product(inputs, self.i8_operand(offsets), self.nested_q_b_layer(self.b), _I8, (act_block,), out_block,
                                         activation)
 
     def mx_operand(self) -> "ops.MxOperand":
@@ -987,11 +991,11 @@ class _ConvBase(_HostLayer):
             y = y.view(B, OH, OW, self.filters)                   # the GEMM's [M][co] is NHWC: no transposition launch
             return y if self.data_format == "NHWC" else y.permute(0, 3, 1, 2)
 
-    def _call_matrix(self, inputs, family, act, max_lines):
+    def _call_matrix(self, inputs, family, act, max_lines, **operand_kwargs):
         if not self.built:
             self.build(tuple(inputs.shape), device=inputs.device)
         with torch.no_grad():
-            operand = getattr(self, family.operand)()
+            operand = getattr(self, family.operand)(**operand_kwargs)
             qb = self.nested_q_b_layer(self.b) if self._has_bias else None
             return self._matrix_conv(inputs, operand, qb, family, act, max_lines)
 
@@ -1008,41 +1012,47 @@ class _ConvBase(_HostLayer):
         ops.check_mx_scale_init(act_scale)
         return self._call_matrix(inputs, _MX, (act_format, act_scale), max_lines)
 
-    def _check_i8(self):
-        """(qmin, qmax) of a conv layer that can run on the int8 matrix instruction, or ValueError naming the reason."""
+    def _check_i8(self, offsets=False):
+        """(qmin, qmax) of a conv layer that can run on the int8 matrix instruction, or ValueError naming the reason.
+        ``offsets=True`` lets an asymmetric layer pass (ops.check_i8_conv_operand_layer)."""
         fan_in = self.kernel.shape[0] * self.kernel.shape[1] * self.kernel.shape[2] if self.built else None
         q_range = ops.check_i8_conv_operand_layer(self.q_range, self.nested_q_k_layer.orientation, self.group_size, self.asymmetric,
-                                                  self.element_format, fan_in, self.kernel_storage)
+                                                  self.element_format, fan_in, self.kernel_storage, offsets=offsets)
         if not self.built:
             raise ValueError(f"{self.name}: the layer is not built yet (no kernel to pack)")
         return q_range
 
-    def i8_operand(self) -> "ops.I8Operand":
+    def i8_operand(self, offsets=False) -> "ops.I8Operand":
         """The kernel under its current scales as an operand of the int8 matrix instruction (ops.i8_operand_pack, groups along the
         contiguous axis): ``filters`` lines over K = ci kh kw, the reduction order of ops.i8_operand_im2col.  A "groupwise" layer
         passes its scale as it is; a "scalar" layer its scale broadcast to ``(filters, 1)``, one group per output channel.
         ValueError naming the reason for a one-axis orientation, ``kernel_storage="hwio"``, a layer without a range, with a range
-        outside [-128, 127], with an offset, with an element format, or not built."""
-        qmin, qmax = self._check_i8()
+        outside [-128, 127], with an offset, with an element format, or not built.
+        ``offsets=True``: an asymmetric layer is packed with its ``(co, nb)`` scale and offset into an ops.I8AffineOperand, whose
+        product adds the offset's row-sum term (padded taps hold code 0 and add no offset); a symmetric layer takes the path it
+        always took."""
+        qmin, qmax = self._check_i8(offsets)
         K = self.kernel.numel() // self.filters
         scale = self.nested_q_k_layer.scale.data
         if self.nested_q_k_layer.orientation == "groupwise":
             gs = self.group_size
         else:
             scale, gs = scale.reshape(1, 1).expand(self.filters, 1).contiguous(), K
-        return ops.i8_operand_pack(self.kernel.detach(), scale, qmin, qmax, gs, self.rounding)
+        offset = self.nested_q_k_layer.offset.data if self.asymmetric else None
+        return ops.i8_operand_pack(self.kernel.detach(), scale, qmin, qmax, gs, self.rounding, offset)
 
-    def call_i8(self, inputs, act_block=0, max_lines=None):
+    def call_i8(self, inputs, act_block=0, max_lines=None, offsets=False):
         """The layer on the int8 matrix instruction, under ``no_grad``: the im2col matrix of the inputs quantised per line and
         ``act_block`` consecutive k of (ci, kh, kw) (0: per line) to symmetric 8-bit integers by ops.i8_operand_im2col -- TensorFlow
         'SAME' padding as ``call`` pads, or 'VALID' -- multiplied with ``i8_operand()`` by ops.i8_gemm, plus the fake-quantised bias
         where the layer has one.  Inference only: there is no backward through this path.  The result is a view of the GEMM's
         (M, co) matrix: ``(B, co, OH, OW)`` with channels-last strides for ``data_format="NCHW"``, ``(B, OH, OW, co)`` for "NHWC".  A
         batch whose im2col matrix has 2^31 elements or more, more than 65535 * 64 lines or more than ``max_lines`` lines is cut into
-        runs of whole images that write their rows of the one result; the result does not depend on the cut."""
+        runs of whole images that write their rows of the one result; the result does not depend on the cut.  ``offsets=True``
+        lets an asymmetric layer run (``i8_operand(offsets=True)``)."""
         _check_max_lines(max_lines)
         ops.check_i8_block(act_block)
-        return self._call_matrix(inputs, _I8, (act_block,), max_lines)
+        return self._call_matrix(inputs, _I8, (act_block,), max_lines, offsets=offsets)
 
 
 class CustomConv2DLayer(_ConvBase):
@@ -1078,16 +1088,17 @@ class _matrix_hardware:
     """Entry and exit of ``mx_hardware`` and ``i8_hardware``: the eligible Dense layers, then (``convs``) the eligible conv layers,
     get ``(operand, bias, *act)`` under the family's attribute -- built once, on entry -- and lose it on exit."""
     _family = _dense_eligible = _conv_eligible = None
+    _opt_in = {}              # keywords of the eligibility tests and of the layers' operand method (i8_hardware: offsets)
 
     def __enter__(self):
-        family, custom = self._family, custom_layers_of(self.model)
-        switching = [m for m in custom if self._dense_eligible(m)]
-        switching += [m for m in custom if self._conv_eligible(m)] if self.convs else []
+        family, custom, opt_in = self._family, custom_layers_of(self.model), self._opt_in
+        switching = [m for m in custom if self._dense_eligible(m, **opt_in)]
+        switching += [m for m in custom if self._conv_eligible(m, **opt_in)] if self.convs else []
         self.layers = []
         with torch.no_grad():
             for m in switching:
                 if not self.emulate:
-                    weight = getattr(m, family.operand)()
+                    weight = getattr(m, family.operand)(**opt_in)
                 elif isinstance(m, _ConvBase):      # the fake-quantised kernel as the (K, co) matrix the decoded operand multiplies
                     weight = m.nested_q_k_layer(m.kernel).detach().permute(3, 2, 0, 1).reshape(m.filters, -1).t()
                 else:
@@ -1100,8 +1111,9 @@ class _matrix_hardware:
         if self.fused:
             for mod in self.model.modules():
                 chain = getattr(mod, family.chain)() if callable(getattr(mod, family.chain, None)) else []
-                if len(chain) > 1 and all(self._dense_eligible(layer) and act in ops.MX_ACTIVATIONS for layer, act in chain):
-                    setattr(mod, family.fused, self._act)
+                if len(chain) > 1 and all(self._dense_eligible(layer, **opt_in) and act in ops.MX_ACTIVATIONS
+                                          for layer, act in chain):
+                    setattr(mod, family.fused, (self._act, dict(opt_in)))      # the dense chain's arguments after the chain, and its keywords
                     self._fused_modules.append(mod)
                     self.fused_layers += [layer for layer, _ in chain]
         return self
@@ -1146,28 +1158,29 @@ class mx_hardware(_matrix_hardware):
         self.layers, self.fused_layers, self._fused_modules = [], [], []
 
 
-def _passes_check_i8(layer: nn.Module, cls) -> bool:
+def _passes_check_i8(layer: nn.Module, cls, offsets=False) -> bool:
     if not isinstance(layer, cls):
         return False
     try:
-        layer._check_i8()
+        layer._check_i8(offsets)
     except ValueError:
         return False
     return True
 
 
-def i8_hardware_eligible(layer: nn.Module) -> bool:
+def i8_hardware_eligible(layer: nn.Module, offsets=False) -> bool:
     """Whether ``layer`` takes the int8 GEMM under ``i8_hardware``: a built Dense layer with a range inside [-128, 127], symmetric,
     with scalar, columnwise or groupwise scales (group size a multiple of 64, or the whole input) and no element format.  Conv
-    layers are judged by ``i8_conv_eligible``."""
-    return _passes_check_i8(layer, CustomDenseLayer)
+    layers are judged by ``i8_conv_eligible``.  ``offsets=True``: an asymmetric layer is eligible too."""
+    return _passes_check_i8(layer, CustomDenseLayer, offsets)
 
 
-def i8_conv_eligible(layer: nn.Module) -> bool:
+def i8_conv_eligible(layer: nn.Module, offsets=False) -> bool:
     """Whether ``layer`` takes the int8 GEMM under ``i8_hardware(convs=True)``: a built conv layer with a range inside
     [-128, 127], symmetric, with a scalar scale or groupwise scales (group size a multiple of 64, or at least ci kh kw), no
-    element format and the kernel stored "oihw" (the groups then run along the im2col operand's K)."""
-    return _passes_check_i8(layer, _ConvBase)
+    element format and the kernel stored "oihw" (the groups then run along the im2col operand's K).  ``offsets=True``: an
+    asymmetric layer is eligible too."""
+    return _passes_check_i8(layer, _ConvBase, offsets)
 
 
 class i8_hardware(_matrix_hardware):
@@ -1187,11 +1200,17 @@ class i8_hardware(_matrix_hardware):
     relu between the layers, as models.MNISTDense does -- evaluates it in eval mode through ``i8_dense_chain``: every layer but the
     last writes the next layer's operand from its own epilogue, and no fp32 hidden activation exists.  The epilogue writes scale
     blocks of 64, so ``fused=True`` needs ``act_block=64`` -- then the bits are those of ``fused=False`` -- and is refused with any
-    other.  ``fused_layers`` lists the layers that fused.  ``emulate=True`` with ``fused=True`` is refused, as on ``mx_hardware``."""
+    other.  ``fused_layers`` lists the layers that fused.  ``emulate=True`` with ``fused=True`` is refused, as on ``mx_hardware``.
+    ``offsets=True``: asymmetric layers (a learned offset per group) switch too, and ``layers`` lists them: their operand carries
+    the offsets and their product adds the offset's row-sum term, which costs matrix instructions that a symmetric product does
+    not pay -- hence the opt-in.  It combines with ``convs``, ``fused`` and ``emulate`` (which needs nothing new: it multiplies the
+    decoded activation with the fake-quantised kernel); a symmetric model is bit-identical with or without it."""
 
     _family, _dense_eligible, _conv_eligible = _I8, staticmethod(i8_hardware_eligible), staticmethod(i8_conv_eligible)
 
-    def __init__(self, model: nn.Module, act_block=0, emulate=False, convs=False, fused=False):
+    def __init__(self, model: nn.Module, act_block=0, emulate=False, convs=False, fused=False, offsets=False):
+        self.offsets = bool(offsets)
+        self._opt_in = {"offsets": True} if self.offsets else {}
         self.model, self.act_block, self.emulate, self.fused = model, ops.check_i8_block(act_block), bool(emulate), bool(fused)
         if self.fused and self.emulate:
             raise ValueError("i8_hardware: emulate=True with fused=True: the emulated path is the yardstick of the unfused path and "
@@ -1203,7 +1222,7 @@ class i8_hardware(_matrix_hardware):
         self.layers, self.fused_layers, self._fused_modules = [], [], []
 
 
-def _dense_chain(fn, family, gemm_name, check_layer, check_act, x, chain, act, out):
+def _dense_chain(fn, family, gemm_name, check_layer, check_act, x, chain, act, out, **operand_kwargs):
     """The body of ``mx_dense_chain`` and ``i8_dense_chain``: the chain checked before any launch, ``x`` quantised once, every layer
     but the last through the family's operand-out epilogue (``out``), the last to fp32."""
     chain = list(chain)
@@ -1231,7 +1250,7 @@ def _dense_chain(fn, family, gemm_name, check_layer, check_act, x, chain, act, o
             if hw is not None and not isinstance(hw[0], torch.Tensor):
                 operand, qb = hw[0], hw[1]
             else:
-                operand, qb = getattr(layer, family.operand)(), layer.nested_q_b_layer(layer.b)
+                operand, qb = getattr(layer, family.operand)(**operand_kwargs), layer.nested_q_b_layer(layer.b)
             last = k == len(chain) - 1
             a = layer._matrix_product(a, operand, qb, family, act, None if last else out, activation)
         return a.reshape(*lead, a.shape[-1])
@@ -1253,16 +1272,19 @@ def mx_dense_chain(x, chain, act_format="fp8_e4m3", act_scale="mx"):
                         x, chain, (act_format, act_scale), act_format)
 
 
-def i8_dense_chain(x, chain, act_block=64):
+def i8_dense_chain(x, chain, act_block=64, offsets=False):
     """``chain`` = [(layer, activation), ...]: Dense layers applied one after the other on the int8 matrix instruction, under
     ``no_grad``.  ``x`` is quantised once per row and ``act_block`` inputs (ops.i8_operand_quantize); every layer but the last goes
     through ops.i8_gemm_quantize, which applies its activation (None or "relu") and writes the next layer's operand, per row and
     block of 64, in the product's epilogue; the last goes through ops.i8_gemm to fp32 and takes no activation.  Bit for bit
     ``call_i8(act_block)`` -> activation -> ``call_i8(act_block=64)`` ..., without the fp32 activations and their launches.  Inside
     ``i8_hardware`` the operands and biases built on its entry are used, otherwise they are built here.  ValueError naming the
-    reason for a layer that cannot take the path (``i8_hardware_eligible``) or an activation other than None / "relu"."""
-    return _dense_chain("i8_dense_chain", _I8, "int8", lambda layer: layer._check_i8(), lambda: ops.check_i8_block(act_block),
-                        x, chain, (act_block,), ops.I8_OUT_BLOCK)
+    reason for a layer that cannot take the path (``i8_hardware_eligible``) or an activation other than None / "relu".
+    ``offsets=True`` lets asymmetric layers take the path (``i8_operand(offsets=True)``): the epilogue's product adds the offset
+    term too, so the bits stay those of the unfused path."""
+    opt_in = {"offsets": True} if offsets else {}
+    return _dense_chain("i8_dense_chain", _I8, "int8", lambda layer: layer._check_i8(**opt_in),
+                        lambda: ops.check_i8_block(act_block), x, chain, (act_block,), ops.I8_OUT_BLOCK, **opt_in)
 
 
 def quantized_tensors(model: nn.Module):

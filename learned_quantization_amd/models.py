@@ -91,10 +91,10 @@ class MNISTDense(nn.Module):
         x = torch.flatten(x, 1)
         fused = getattr(self, "_mx_fused", None)
         if fused is not None and not self.training:               # inside layers.mx_hardware(..., fused=True), eval mode
-            return mx_dense_chain(x, self.mx_chain(), *fused)
+            return mx_dense_chain(x, self.mx_chain(), *fused[0], **fused[1])
         fused = getattr(self, "_i8_fused", None)
         if fused is not None and not self.training:               # inside layers.i8_hardware(..., fused=True), eval mode
-            return i8_dense_chain(x, self.i8_chain(), *fused)
+            return i8_dense_chain(x, self.i8_chain(), *fused[0], **fused[1])
         x = F.relu(self.dense_1(x))
         return self.dense_2(x)
 

@@ -636,6 +636,27 @@ class I8Operand(NamedTuple):
     block: int
 
 
+class I8AffineOperand(I8Operand):
+    """An I8Operand of a parameter with an offset per group (``i8_operand_pack(..., offset=...)``): the same five fields, and
+    ``offsets``, a float32 buffer in the layout of ``scales`` (include/lq_hip.h, "offsets on the B operand").  Only the B side of a
+    product carries offsets."""
+    offsets: Optional[torch.Tensor] = None
+
+
+def _i8_offsets(operand: I8Operand) -> Optional[torch.Tensor]:
+    """The offsets buffer of an operand, or None for a symmetric one."""
+    return getattr(operand, "offsets", None) if isinstance(operand, I8AffineOperand) else None
+
+
+def _check_i8_a_operand(a: I8Operand) -> None:
+    if _i8_offsets(a) is not None:
+        raise ValueError("only the B operand carries offsets: activation offsets are not built")
+
+
+I8_OFFSETS_OPT_IN = ("pass offsets=True (i8_operand / call_i8 / i8_hardware; train.py --i8-eval-offsets) to add the offset's "
+                     "row-sum term, which costs matrix instructions that a symmetric product does not pay")
+
+
 def check_i8_block(block) -> int:
     """``block`` as an int, or ValueError: 0 (one scale per line) or a positive multiple of 64."""
     if isinstance(block, bool) or int(block) != block or int(block) < 0 or int(block) % I8_BLOCK_UNIT:
@@ -644,8 +665,10 @@ def check_i8_block(block) -> int:
     return int(block)
 
 
-def check_i8_operand_layer(q_range, orientation, group_size=None, asymmetric=False, element_format=None, fan_in=None) -> Tuple[int, int]:
-    """What a quantizer must be to run on the int8 matrix instruction -- (qmin, qmax) -- or ValueError naming the reason."""
+def check_i8_operand_layer(q_range, orientation, group_size=None, asymmetric=False, element_format=None, fan_in=None, *,
+                           offsets=False) -> Tuple[int, int]:
+    """What a quantizer must be to run on the int8 matrix instruction -- (qmin, qmax) -- or ValueError naming the reason.
+    ``offsets=True`` opts into the offset's row-sum term, with which an asymmetric layer passes."""
     if element_format is not None:
         raise ValueError(f"element_format={element_format!r}: a microscaling layer runs on the block-scaled matrix instruction "
                          "(mx_hardware), not on the int8 one")
@@ -656,9 +679,9 @@ def check_i8_operand_layer(q_range, orientation, group_size=None, asymmetric=Fal
     if qmin < I8_RANGE[0] or qmax > I8_RANGE[1]:
         raise ValueError(f"q_range ({qmin}, {qmax}) is not inside [{I8_RANGE[0]}, {I8_RANGE[1]}], the signed bytes the int8 matrix "
                          "instruction multiplies (an unsigned 8-bit range does not fit)")
-    if asymmetric:
-        raise ValueError("asymmetric=True: an offset per group needs the row sums of the activation codes in the product; that "
-                         "term is not built")
+    if asymmetric and not offsets:
+        raise ValueError("asymmetric=True: an offset per group needs the row sums of the activation codes in the product; "
+                         + I8_OFFSETS_OPT_IN)
     if orientation == "rowwise":
         raise ValueError('orientation="rowwise": a scale per input row varies along K inside a step of the instruction')
     if orientation not in ("scalar", "columnwise", "groupwise"):
@@ -670,7 +693,7 @@ def check_i8_operand_layer(q_range, orientation, group_size=None, asymmetric=Fal
 
 
 def check_i8_conv_operand_layer(q_range, orientation, group_size=None, asymmetric=False, element_format=None, fan_in=None,
-                                kernel_storage="oihw") -> Tuple[int, int]:
+                                kernel_storage="oihw", *, offsets=False) -> Tuple[int, int]:
     """What a conv layer's quantizer must be to run on the int8 matrix instruction -- (qmin, qmax) -- or ValueError naming the
     reason.  ``fan_in`` is ci kh kw, the K of the im2col operand.  A conv kernel is HWIO-shaped, so "rowwise", "columnwise" and
     "channelwise" put the scale on kh, kw and ci: it varies along K inside a step of the instruction -- the Dense check's
@@ -678,7 +701,7 @@ def check_i8_conv_operand_layer(q_range, orientation, group_size=None, asymmetri
     or at least ``fan_in`` (one scale per output channel)."""
     # range, offset and element format first, as the Dense check words them; the orientation is judged here
     qmin, qmax = check_i8_operand_layer(q_range, "groupwise" if orientation == "groupwise" else "scalar", group_size, asymmetric,
-                                        element_format, fan_in)
+                                        element_format, fan_in, offsets=offsets)
     if orientation in ("rowwise", "columnwise", "channelwise"):
         axis = {"rowwise": "kh", "columnwise": "kw", "channelwise": "ci"}[orientation]
         raise ValueError(f'orientation="{orientation}": on an HWIO-shaped conv kernel the scale lies on {axis} and varies along '
@@ -706,17 +729,20 @@ def _i8_operand_buffers(lines: int, K: int, block: int, device) -> Tuple[torch.T
 
 
 def i8_operand_pack(parameter: torch.Tensor, scale: torch.Tensor, qmin: int, qmax: int, group_size: int,
-                    rounding: str = "floor") -> I8Operand:
+                    rounding: str = "floor", offset: Optional[torch.Tensor] = None) -> I8Operand:
     """The operand of a stored parameter under its stored group-wise scales (include/lq_hip.h, lq_i8_operand_pack): the codes are
     the clamped integers of ``fq_forward_group``'s int8 view, the scales are ``scale`` bit for bit.  The lines are the parameter's
     columns when the groups run along its strided axis (a Dense kernel (in, out)), its rows otherwise.  ``group_size`` at least the
-    line length gives one scale per line; otherwise it must be a multiple of 64.  One launch."""
+    line length gives one scale per line; otherwise it must be a multiple of 64.  One launch.
+    ``offset`` (the scale's shape): the operand of an asymmetric parameter, an I8AffineOperand (lq_i8_operand_pack_affine) whose
+    codes are ``fq_forward_group_affine``'s and whose ``offsets`` are ``offset`` bit for bit."""
     qmin, qmax = check_q_range(qmin, qmax)
     if qmin < I8_RANGE[0] or qmax > I8_RANGE[1]:
         raise ValueError(f"range ({qmin}, {qmax}) is not inside [{I8_RANGE[0]}, {I8_RANGE[1]}], the signed bytes the int8 matrix "
                          "instruction multiplies")
     rnd = check_rounding(rounding)
     p, s, (R, C, axis) = _group_param(parameter, scale, group_size)
+    b = None if offset is None else _offset_like(offset, s)
     lines, K = (C, R) if axis == 0 else (R, C)
     gs = int(group_size)
     if gs < K and gs % I8_BLOCK_UNIT:
@@ -724,6 +750,14 @@ def i8_operand_pack(parameter: torch.Tensor, scale: torch.Tensor, qmin: int, qma
     block = 0 if gs >= K else gs
     lib = _hip.load()
     codes, scales = _i8_operand_buffers(lines, K, block, p.device)
+    if b is not None:
+        offsets = torch.empty_like(scales)
+        _hip.check(lib.lq_i8_operand_pack_affine(_hip.ptr(p), _hip.ptr(s), _hip.ptr(b), qmin, qmax, rnd, R, C, axis, gs,
+                                                 _hip.ptr(codes), _hip.ptr(scales), _hip.ptr(offsets), _hip.stream_ptr(p.device)),
+                   "lq_i8_operand_pack_affine")
+        op = I8AffineOperand(codes, scales, lines, K, block)
+        op.offsets = offsets
+        return op
     _hip.check(lib.lq_i8_operand_pack(_hip.ptr(p), _hip.ptr(s), qmin, qmax, rnd, R, C, axis, gs, _hip.ptr(codes), _hip.ptr(scales),
                                       _hip.stream_ptr(p.device)), "lq_i8_operand_pack")
     return I8Operand(codes, scales, lines, K, block)
@@ -746,9 +780,16 @@ def i8_operand_quantize(x: torch.Tensor, block: int = 0) -> I8Operand:
 
 
 def i8_operand_decode(operand: I8Operand) -> torch.Tensor:
-    """float32 ``(lines, K)``: code * scale of every element (include/lq_hip.h, lq_i8_operand_decode)."""
+    """float32 ``(lines, K)``: code * scale of every element (include/lq_hip.h, lq_i8_operand_decode); of an I8AffineOperand
+    ``code * scale + offset``, two roundings (lq_i8_operand_decode_affine)."""
     lib = _hip.load()
     out = torch.empty((operand.lines, operand.K), dtype=torch.float32, device=operand.codes.device)
+    offsets = _i8_offsets(operand)
+    if offsets is not None:
+        _hip.check(lib.lq_i8_operand_decode_affine(_hip.ptr(operand.codes), _hip.ptr(operand.scales), _hip.ptr(offsets),
+                                                   operand.lines, operand.K, check_i8_block(operand.block), _hip.ptr(out),
+                                                   _hip.stream_ptr(out.device)), "lq_i8_operand_decode_affine")
+        return out
     _hip.check(lib.lq_i8_operand_decode(_hip.ptr(operand.codes), _hip.ptr(operand.scales), operand.lines, operand.K,
                                         check_i8_block(operand.block), _hip.ptr(out), _hip.stream_ptr(out.device)),
                "lq_i8_operand_decode")
@@ -775,11 +816,18 @@ def i8_gemm(a: I8Operand, b: I8Operand, bias: Optional[torch.Tensor] = None, out
     ``out``: a float32 matrix to write into; its row stride is the leading dimension."""
     if a.K != b.K:
         raise ValueError(f"the operands reduce over different K: {a.K} and {b.K}")
+    _check_i8_a_operand(a)
     i8_period(a.block, b.block, a.K)
     lib = _hip.load()
     M, N = a.lines, b.lines
     dev = a.codes.device
     bias, out, ldy = _gemm_output(a, b, bias, out)
+    offsets = _i8_offsets(b)
+    if offsets is not None:      # B = q s + b: the offset's row-sum term (lq_i8_gemm_affine)
+        _hip.check(lib.lq_i8_gemm_affine(_hip.ptr(a.codes), _hip.ptr(a.scales), a.block, _hip.ptr(b.codes), _hip.ptr(b.scales),
+                                         _hip.ptr(offsets), b.block, _hip.ptr(bias), _hip.ptr(out), ldy, M, N, a.K,
+                                         _hip.stream_ptr(dev)), "lq_i8_gemm_affine")
+        return out
     _hip.check(lib.lq_i8_gemm(_hip.ptr(a.codes), _hip.ptr(a.scales), a.block, _hip.ptr(b.codes), _hip.ptr(b.scales), b.block,
                               _hip.ptr(bias), _hip.ptr(out), ldy, M, N, a.K, _hip.stream_ptr(dev)), "lq_i8_gemm")
     return out
@@ -839,12 +887,20 @@ def i8_gemm_quantize(a: I8Operand, b: I8Operand, bias: Optional[torch.Tensor] = 
     act = check_activation(activation)
     if a.K != b.K:
         raise ValueError(f"the operands reduce over different K: {a.K} and {b.K}")
+    _check_i8_a_operand(a)
     i8_period(a.block, b.block, a.K)
     lib = _hip.load()
     M, N = a.lines, b.lines
     dev = a.codes.device
     bias = _gemm_output(a, b, bias, fp32_out=False)[0]
     codes, scales = _i8_operand_buffers(M, N, out_block, dev)
+    offsets = _i8_offsets(b)
+    if offsets is not None:
+        _hip.check(lib.lq_i8_gemm_quantize_affine(_hip.ptr(a.codes), _hip.ptr(a.scales), a.block, _hip.ptr(b.codes),
+                                                  _hip.ptr(b.scales), _hip.ptr(offsets), b.block, _hip.ptr(bias), act, out_block,
+                                                  _hip.ptr(codes), _hip.ptr(scales), M, N, a.K, _hip.stream_ptr(dev)),
+                   "lq_i8_gemm_quantize_affine")
+        return I8Operand(codes, scales, M, N, out_block)
     _hip.check(lib.lq_i8_gemm_quantize(_hip.ptr(a.codes), _hip.ptr(a.scales), a.block, _hip.ptr(b.codes), _hip.ptr(b.scales), b.block,
                                        _hip.ptr(bias), act, out_block, _hip.ptr(codes), _hip.ptr(scales), M, N, a.K,
                                        _hip.stream_ptr(dev)), "lq_i8_gemm_quantize")

@@ -634,11 +634,15 @@ def build_parser():
                          "tail through layers.i8_dense_chain: relu and the next operand's quantisation, per row and block of 64, in "
                          "the GEMM's epilogue) and add i8_eval_fused_layers, i8_eval_fused_accuracy and "
                          "i8_eval_fused_max_logit_diff (against the unfused hardware path; 0.0 is expected) to the result line")
+    ap.add_argument("--i8-eval-offsets", action="store_true",
+                    help="with --i8-eval: asymmetric layers (--asymmetric) take the hardware path too (layers.i8_hardware(offsets=True): "
+                         "their operand carries the offsets and the product adds the offset's row-sum term, at the price of more "
+                         "matrix instructions per step); without it --i8-eval --asymmetric is refused")
     return ap
 
 
 @torch.no_grad()
-def i8_eval(model, x, y, act_block=0, convs=False, fused=False):
+def i8_eval(model, x, y, act_block=0, convs=False, fused=False, offsets=False):
     """One evaluation of ``model`` on (x, y) under layers.i8_hardware, one under its ``emulate=True`` yardstick and one of the
     fake-quantised model as it stands: a dict of the three accuracies and the largest |difference| of the outputs of the last Dense
     layer that took the path (the logits of the MNIST model) between the hardware path and each of the other two.  ValueError for
@@ -654,7 +658,7 @@ def i8_eval(model, x, y, act_block=0, convs=False, fused=False):
     fields = {}
     try:
         probe = L.i8_hardware(model, act_block)
-        last = ([m for m in L.custom_layers_of(model) if L.i8_hardware_eligible(m)] or [model if convs else None])[-1]
+        last = ([m for m in L.custom_layers_of(model) if L.i8_hardware_eligible(m, offsets)] or [model if convs else None])[-1]
         if last is None:
             raise ValueError("i8_eval: the model has no Dense layer that can run on the int8 matrix instruction (a signed range of at "
                              "most 8 bits, symmetric, scalar / columnwise scales or groups of a multiple of 64 inputs)")
@@ -665,7 +669,7 @@ def i8_eval(model, x, y, act_block=0, convs=False, fused=False):
                 if how == "fake":
                     p = model(x)
                 else:
-                    with L.i8_hardware(model, probe.act_block, emulate=how == "emulate") as hw:
+                    with L.i8_hardware(model, probe.act_block, emulate=how == "emulate", offsets=offsets) as hw:
                         n_layers = len(hw.layers)
                         p = model(x)
             finally:
@@ -673,7 +677,7 @@ def i8_eval(model, x, y, act_block=0, convs=False, fused=False):
             acc.append(float((p.argmax(1) == y).float().mean()))
             logits.append(seen[-1])
         if fused:
-            with L.i8_hardware(model, probe.act_block, fused=True) as hwf:
+            with L.i8_hardware(model, probe.act_block, fused=True, offsets=offsets) as hwf:
                 if not hwf.fused_layers or not callable(getattr(model, "logits", None)):
                     raise ValueError("i8_eval: fused=True needs a model whose Dense tail fuses (i8_chain() and logits(), as "
                                      "models.MNISTDense has): nothing but relu between eligible Dense layers")
@@ -683,8 +687,8 @@ def i8_eval(model, x, y, act_block=0, convs=False, fused=False):
         if convs:
             outs = []
             for emulate in (False, True):
-                with L.i8_hardware(model, probe.act_block, emulate=emulate, convs=True) as hwc:
-                    n_convs = sum(L.i8_conv_eligible(m) for m in hwc.layers)
+                with L.i8_hardware(model, probe.act_block, emulate=emulate, convs=True, offsets=offsets) as hwc:
+                    n_convs = sum(L.i8_conv_eligible(m, offsets) for m in hwc.layers)
                     if not n_convs:
                         raise ValueError("i8_eval: convs=True needs a model with a conv layer that can run on the int8 matrix "
                                          "instruction (a signed range of at most 8 bits, symmetric, a scalar scale or groups of a "
@@ -761,9 +765,13 @@ def main(argv=None):
         ap.error("--mx-eval-fused needs --mx-eval: it compares the fused Dense tail with the unfused hardware path")
     if args.mx_eval_convs and args.mx_eval is None:
         ap.error("--mx-eval-convs needs --mx-eval: it adds the conv layers to the hardware path that --mx-eval evaluates")
-    if args.i8_eval and (args.bits is None or args.bits > 8 or args.unsigned or args.asymmetric or args.element_format is not None):
-        ap.error("--i8-eval needs --bits of at most 8, signed and symmetric, and no --element-format: it runs the Dense layers of an "
-                 "integer model on the int8 matrix instruction")
+    if args.i8_eval_offsets and not args.i8_eval:
+        ap.error("--i8-eval-offsets needs --i8-eval: it lets the asymmetric layers take the hardware path that --i8-eval evaluates")
+    if args.i8_eval and (args.bits is None or args.bits > 8 or args.unsigned or (args.asymmetric and not args.i8_eval_offsets)
+                         or args.element_format is not None):
+        ap.error("--i8-eval needs --bits of at most 8, signed and symmetric (or --asymmetric with --i8-eval-offsets, which adds the "
+                 "offset's row-sum term to the product), and no --element-format: it runs the Dense layers of an integer model on "
+                 "the int8 matrix instruction")
     if args.i8_eval_act_block and not args.i8_eval:
         ap.error("--i8-eval-act-block needs --i8-eval")
     if args.i8_eval_convs and not args.i8_eval:
@@ -841,7 +849,7 @@ def main(argv=None):
     quant_stats = L.quant_stats(tr.model) if args.quant_stats and rank == 0 else None      # after the clock has stopped
     mx_stats = L.mx_quant_stats(tr.model) if args.mx_stats and rank == 0 else None
     mx_eval_fields = mx_eval(tr.model, *batches[0], act_format=args.mx_eval, fused=args.mx_eval_fused, convs=args.mx_eval_convs) if args.mx_eval is not None and rank == 0 else None
-    i8_eval_fields = i8_eval(tr.model, *batches[0], act_block=args.i8_eval_act_block, convs=args.i8_eval_convs, fused=args.i8_eval_fused) if args.i8_eval and rank == 0 else None
+    i8_eval_fields = i8_eval(tr.model, *batches[0], act_block=args.i8_eval_act_block, convs=args.i8_eval_convs, fused=args.i8_eval_fused, offsets=args.i8_eval_offsets) if args.i8_eval and rank == 0 else None
     if rank == 0:
         n_q = sum(p.numel() for l in tr.custom_layers for p in l._regularized())
         print(json.dumps({

@@ -2,7 +2,7 @@
 """Compares the device assembly of two builds function by function (profiles/*/asm_compare.txt).
 
     make -C learned_quantization_amd/csrc asm          # at the parent commit and at this one; keep the gfx950 .s of each
-    python3 tools/asm_compare.py PARENT.s THIS.s
+    python3 tools/asm_compare.py PARENT.s THIS.s [--rename PARENT_NAME=THIS_NAME ...]
 
 A function's instruction stream is what is left of its body once labels, comments and the directives that only carry
 addresses or sizes are gone; local labels that instructions name (branch targets) are renumbered in order of first use, so
@@ -50,10 +50,28 @@ def functions(path):
     return norm
 
 
+def renamed(fns, pairs):
+    """``fns`` with every parent name of ``pairs`` replaced by this build's name, in the keys and inside the streams (a kernel that
+    became an instantiation of a template keeps its stream but not its mangled name)."""
+    for old, new in pairs:
+        if old not in fns:
+            sys.exit(f"--rename: no function {old} in the parent")
+        fns = {(new if k == old else k): v.replace(old, new) for k, v in fns.items()}
+    return fns
+
+
 def main():
-    if len(sys.argv) != 3:
+    args = sys.argv[1:]
+    pairs = []
+    while "--rename" in args:      # --rename PARENT_NAME=THIS_NAME, any number of times
+        i = args.index("--rename")
+        pairs.append(tuple(args[i + 1].split("=", 1)))
+        del args[i:i + 2]
+    if len(args) != 2:
         sys.exit(__doc__)
-    a, b = functions(sys.argv[1]), functions(sys.argv[2])
+    a, b = renamed(functions(args[0]), pairs), functions(args[1])
+    for old, new in pairs:
+        print(f"renamed: {old} -> {new}")
     same = sorted(f for f in a if f in b and a[f] == b[f])
     diff = sorted(f for f in a if f in b and a[f] != b[f])
     missing = sorted(f for f in a if f not in b)

@@ -17,8 +17,10 @@ MIN_SCALE = np.float32(2.0 ** -126)
 # second K step with one live k.  (33, 10, 784): the MNIST layer's K under one-step periods of A; N below a block, three clamped
 # tiles.  (70, 130, 200): two thread blocks along m (the second with 6 live lines in its one tile), three along n (the last with two
 # live columns), periods of one step with B's scale changing every second one, a short last period.  (64, 128, 128): whole tiles
-# everywhere, A's scale changing every second period.  (100, 192, 256): periods of two steps, a last row tile of 4 lines.
-# (31, 63, 192): 15 live lines in the last tile, N one below a block, periods of two steps.
+# everywhere, a_every = 2 -- but K = 128 under a_block = 128 is ONE scale block of A: its scale never changes, and ia is advanced
+# only after the last read (a scale of A that does change under a_every >= 2 is tests/_matrix_forms.py's NEW_I8_FUSED).
+# (100, 192, 256): periods of two steps, a last row tile of 4 lines.  (31, 63, 192): 15 live lines in the last tile, N one below a
+# block, periods of two steps.
 CASES = [(1, 1, 1, 0, 0), (16, 64, 64, 0, 0), (17, 65, 65, 0, 0), (33, 10, 784, 64, 0), (70, 130, 200, 64, 128), (64, 128, 128, 128, 64),
          (100, 192, 256, 0, 128), (31, 63, 192, 128, 0)]
 # Every case is _i8_reference.gemm_case's seed 0; for (1, 1, 1) it gives Y > 0 with and without the bias, so relu does not empty the

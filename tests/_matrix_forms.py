@@ -10,9 +10,15 @@ tests/_i8_reference.py, tests/_mx_gemm_reference.py and tests/_mx_conv_reference
 
 Each ``FORMS_*`` table is the union of the shapes the earlier GPU files already run (imported, not copied) and the ``NEW_*`` rows
 that tests/test_gpu_matrix_forms.py runs.  The second half builds the inputs of the new quantize cases, so that the CPU file can
-assert their conditions on the reference without a device."""
+assert their conditions on the reference without a device.
+
+``i8_gemm_quantize_form``, ``FORMS_I8_FUSED`` and ``FORMS_I8_GEMM_AFFINE`` do the same for the three other kernels that carry the
+int8 GEMM's period bookkeeping (k_i8_gemm<true>, k_i8_gemm_quantize<false> and <true>): tests/test_i8_period_forms_cpu.py holds
+their reach proof and tests/test_gpu_i8_period_forms.py runs their new rows."""
 import numpy as np
 
+import _i8_affine_reference as AF
+import _i8_fused_reference as FR
 import _i8_reference as I
 import _mx_conv_reference as C
 import _mx_gemm_reference as G
@@ -76,20 +82,67 @@ def _waves(MT, NT):
     return dict(grid=(gx, gy), clamped_m=MT % 2 == 1, clamped_n=NT % 2 == 1, leaving=4 * gx * gy - live)
 
 
-def i8_gemm_form(M, N, K, a_block, b_block):
-    """lq_i8_gemm / k_i8_gemm.  ps: K steps per period; a_every / b_every: periods per scale block (ONE_PER_LINE for block 0);
-    periods: their number; steps: the length of each; short_last: the last period is cut by K; a_whole / b_whole: a block that is
-    not 0 but at least K (one scale block)."""
-    MT, NT, KT = _cdiv(M, 16), _cdiv(N, 16), _cdiv(K, 64)
+def _period_rule(K, a_block, b_block):
+    """The ``ps`` / ``a_every`` / ``b_every`` rule that the host functions i8_gemm and i8_gemm_quantize each write out, and what
+    the kernels' loop over K does with it.  The loop is walked as the kernels write it: ``left`` counts down from ps, a period ends on
+    ``--left == 0 || kt == KT - 1``, then ``++ca == a_every`` resets ca and advances ia (the same for B), and the scales of the next
+    period are read at ia / ib unless this was the last K step.  a_changes / b_changes: the reloads that read an index advanced
+    since the last read; a_wraps / b_wraps: those of them under ``every >= 2``, that is the resets of ca / cb to 0 after which the
+    index is read (with every == 1 the counter never leaves 0 between periods, and a reset at the end of K is read by nobody)."""
+    KT = _cdiv(K, 64)
     lo, hi = min(a_block, b_block), max(a_block, b_block)
     assert lo == 0 or hi % lo == 0
     F = lo if lo > 0 else hi
     ps = min(F // 64, KT) if F > 0 else KT
     every = lambda blk: blk // F if blk > 0 else ONE_PER_LINE      # noqa: E731
-    steps = [min(ps, KT - k) for k in range(0, KT, ps)]
-    d = _waves(MT, NT)
-    d.update(ps=ps, KT=KT, a_every=every(a_block), b_every=every(b_block), periods=len(steps), steps=steps, short_last=KT % ps != 0,
-             a_whole=a_block >= K, b_whole=b_block >= K)
+    ev = dict(a=every(a_block), b=every(b_block))
+    steps, count, idx, seen = [], dict(a=0, b=0), dict(a=0, b=0), dict(a=0, b=0)
+    changes, wraps = dict(a=0, b=0), dict(a=0, b=0)
+    left, run = ps, 0
+    for kt in range(KT):
+        left, run = left - 1, run + 1
+        if left == 0 or kt == KT - 1:
+            steps.append(run)
+            left, run = ps, 0
+            for o in "ab":
+                count[o] += 1
+                if count[o] == ev[o]:                      # ONE_PER_LINE never compares equal: INT32_MAX on the device
+                    count[o], idx[o] = 0, idx[o] + 1
+            if kt != KT - 1:
+                for o in "ab":
+                    if idx[o] != seen[o]:
+                        changes[o] += 1
+                        wraps[o] += ev[o] >= 2
+                        seen[o] = idx[o]
+    # what the reloads read stays inside the scale buffers: the largest index read is below the operand's number of scale blocks
+    for o, blk in (("a", a_block), ("b", b_block)):
+        assert seen[o] < (_cdiv(K, blk) if blk else 1), (K, a_block, b_block)
+    return dict(ps=ps, KT=KT, a_every=ev["a"], b_every=ev["b"], periods=len(steps), steps=steps, short_last=KT % ps != 0,
+                a_whole=a_block >= K, b_whole=b_block >= K, a_above=a_block > K, b_above=b_block > K,
+                a_changes=changes["a"], b_changes=changes["b"], a_wraps=wraps["a"], b_wraps=wraps["b"])
+
+
+def i8_gemm_form(M, N, K, a_block, b_block):
+    """lq_i8_gemm / k_i8_gemm<AFF>.  ps: K steps per period; a_every / b_every: periods per scale block (ONE_PER_LINE for block 0);
+    periods: their number; steps: the length of each; short_last: the last period is cut by K; a_whole / b_whole: a block that is
+    not 0 but at least K (one scale block); a_above / b_above: a block above K, where the host's ``min(F / 64, KT)`` can cut;
+    a_changes / b_changes / a_wraps / b_wraps: see _period_rule."""
+    d = _waves(_cdiv(M, 16), _cdiv(N, 16))
+    d.update(_period_rule(K, a_block, b_block))
+    return d
+
+
+def i8_gemm_quantize_form(M, N, K, a_block, b_block):
+    """lq_i8_gemm_quantize / k_i8_gemm_quantize<AFF>: a wave owns 1 x 4 tiles, a thread block 64 x 64, and along n the grid spans the
+    padded OUTPUT operand.  grid = (OKT, ceil(MT / 4)); leaving: the waves with mt >= MT (every block column has the same
+    ``leaving // OKT`` of them, in its last block row); clamped_last = 4 OKT - NT: the tiles of the last block column that are
+    ``min(nt0 + j, NT - 1)`` copies of B's last tile, all of their columns masked by live_n; masked_cols: the columns past N of B's
+    last tile itself (live_n masks part of a tile); dead_lines: the rows past M of the last row tile (live_m); the period keys are
+    _period_rule's, which this host function writes out a second time."""
+    MT, NT, OKT = _cdiv(M, 16), _cdiv(N, 16), _cdiv(N, 64)
+    gy = _cdiv(MT, 4)
+    d = dict(grid=(OKT, gy), leaving=(4 * gy - MT) * OKT, clamped_last=4 * OKT - NT, masked_cols=16 * NT - N, dead_lines=16 * MT - M)
+    d.update(_period_rule(K, a_block, b_block))
     return d
 
 
@@ -176,6 +229,26 @@ NEW_I8_GEMM = [
     ((17, 18, 320, 384, 128), "A's block above K next to three blocks of B: a_every = 3 is never completed"),
 ]
 FORMS_I8_GEMM = OLD_I8_GEMM + [c for c, _ in NEW_I8_GEMM]
+# k_i8_gemm<true>: tests/test_gpu_i8_affine.py runs all_gemm_affine_keys(), tests/test_gpu_i8_period_forms.py the NEW_I8_GEMM rows
+FORMS_I8_GEMM_AFFINE = AF.all_gemm_affine_keys() + [c for c, _ in NEW_I8_GEMM]
+
+# k_i8_gemm_quantize<false> and <true> (M, N, K, a_block, b_block): tests/test_gpu_i8_fused.py and the fused tests of
+# tests/test_gpu_i8_affine.py run FR.CASES, tests/test_gpu_i8_period_forms.py the new rows
+NEW_I8_FUSED = [
+    ((33, 40, 320, 128, 64), "a_every = 2 over three blocks of A: ia is read after two wraps; NT = 3: one clamped tile, 8 masked "
+                             "columns; MT = 3: one leaving wave"),
+    ((17, 40, 448, 64, 192), "b_every = 3, seven periods: cb wraps twice (blocks of 192, 192 and 64)"),
+    ((17, 96, 448, 192, 64), "a_every = 3; NT = 6: the second column block has two clamped tiles"),
+    ((17, 96, 448, 128, 256), "ps = 2, b_every = 2: periods of 2, 2, 2 and 1 steps"),
+    ((17, 65, 448, 256, 128), "its mirror: a_every = 2"),
+    ((17, 40, 448, 192, 192), "ps = 3: periods of 3, 3 and 1 steps"),
+    ((17, 65, 320, 384, 0), "A's block above K: ps = KT, one scale block"),
+    ((17, 65, 320, 0, 384), "the same on B"),
+    ((17, 65, 320, 384, 128), "A's block above K beside three blocks of B"),
+    ((33, 130, 448, 64, 256), "the fused chain's shape: a_block = 64 from the previous epilogue, b_every = 4 over two blocks of B"),
+]
+FORMS_I8_FUSED = list(FR.CASES) + [c for c, _ in NEW_I8_FUSED]
+I8_CONTRACT_KEYS = [(17, 96, 448, 192, 64), (33, 40, 320, 128, 64)]      # the rows of the new memory-contract test
 I8_END_TO_END = dict(x=(3, 70), act_block=128, w=(70, 40), gs=70)      # quantize(block = 128 >= K) times a packed (70, 40) kernel
 
 # MX operand (L, K, fp4, vec, line_fast): pack runs PACK_SHAPES aligned in all three formats, its memory contract (70, 40, 0) and

@@ -612,6 +612,45 @@ int lq_mx_operand_im2col(const float* X, const lq_conv_geom* g, int format, int 
  * offsets off the 16-byte grid.  The row sums cost matrix instructions (one more per A tile and K step: 6 instead of 4 in
  * lq_i8_gemm_affine, 5 instead of 4 in lq_i8_gemm_quantize_affine), which is why a caller opts in.
  *
+ * DIRECT INT8 CONVOLUTION (no im2col matrix).  The input is quantised ONCE per pixel into an int8 NHWC copy, the kernel is packed per
+ * tap, and the product gathers its windows itself: about KH * KW times fewer operand bytes than lq_i8_operand_im2col + lq_i8_gemm.
+ * lq_i8_pixels_quantize: X, logically [B][C][H][W], is read through the xs_* element strides of `g` (NCHW, channels_last or any view
+ * with non-negative strides; 64-bit addressing, 4-byte loads of elements the pixel holds and of no others: a channel index past C
+ * is clamped to C - 1, not predicated; B, C, H, W and xs_* are the only fields read).  It writes
+ *   codes   [B][H][W][CP] int8, plain NHWC, CP = 32 * ceil(C / 32); channels past C hold code 0
+ *   scales  [B][H][W] fp32, one per pixel
+ * and the scale and codes of pixel (b, h, w) are what lq_i8_operand_quantize gives row (b * H + h) * W + w of the matrix
+ * X.permute(0, 2, 3, 1).reshape(B * H * W, C) with block = 0: absmax over the pixel's C channels, qmin -127, qmax 127, min_value
+ * 2^-126, nearest even -- that kernel's own scale rule and element step.  A zero pixel gets scale 2^-126 and codes 0; a pixel
+ * holding a NaN or +-Inf gets a NaN scale and codes 0, and no other pixel does.  X is read once where C <= 64, the channels past 64
+ * a second time.  code_bytes = B * H * W * CP, scale_bytes = 4 * B * H * W (lq_i8_pixels_bytes).
+ * lq_i8_conv_kernel_pack: an OIHW-stored kernel P[co][ci][kh][kw] under ONE scale per filter, s[co], in fragment order:
+ *   codes   [NT][KH * KW][CS][64 lanes][FB], NT = ceil(co / 16), tap index i * KW + j, CP = 32 * ceil(ci / 32).
+ *           CP % 64 == 0: STEP = 64, FB = 16, CS = CP / 64, lane l holds filter 16 nt + (l & 15), channels 64 cs + 16 (l >> 4) + jj in
+ *           byte jj.  Otherwise STEP = 32, FB = 8, CS = CP / 32, channels 32 cs + 8 (l >> 4) + jj.
+ *   scales  [16 NT] fp32, s copied bit for bit; filters past co and channels past ci hold code 0, scales of filters past co are 1.0f
+ * The codes are the clamped integers of lq_i8_operand_pack for the same element (the same element step, `rounding` included).  As
+ * argued above for v_mfma_i32_16x16x64_i8 (and equally for v_mfma_i32_16x16x32_i8), the name of a k inside a step cannot be
+ * observed: the channel-to-(lane, byte) rule is this library's definition, and the product reads the pixel codes by the same rule.
+ * code_bytes = 16 NT * KH * KW * CP, scale_bytes = 64 NT (lq_i8_conv_kernel_bytes).
+ * lq_i8_conv2d: Y[m][n], fp32 row-major with leading dimension ldy >= co -- NHWC, as the GEMM's result is.  M, OH, OW are
+ * lq_mx_im2col_dims', line m = (b * OH + oh) * OW + ow; the xs_* fields of g are not read.  DEFINITION (bit exact, independent of
+ * any tiling; tests/_i8_direct_reference.py states it in NumPy).  For output (m, n), from y = +0, over the taps (i, j) in ascending
+ * i, then j:
+ *       ih = oh * stride_h - pad_top + i, iw = ow * stride_w - pad_left + j; a tap outside the image is skipped; otherwise
+ *       I = sum_c a[b][ih][iw][c] * q[n][c][i][j]       exact, int32 (C <= 65536)
+ *       y = RN(y + RN((float)I * sa[b][ih][iw]))        the product and the sum round separately
+ *   after the last tap y = RN(y * sk[n]), and with a bias y = RN(y + bias[n]).  A NaN pixel scale makes NaN exactly the outputs
+ *   whose window covers the pixel; a NaN filter scale makes its column NaN.  No atomics: run-to-run bit-stable.
+ * Each of the three calls only enqueues ONE launch (capturable), allocates nothing, uses no workspace, atomics or memset, reads no
+ * environment and writes exactly code_bytes and scale_bytes, or the M x co elements of Y.  LQ_EINVAL before any launch: a NULL
+ * pointer (bias may be NULL), a non-positive extent, kernel size or stride, a negative pad, OH or OW < 1, a negative stride of X,
+ * C (ci) > 65536 (a tap's int32 sum must stay exact), M above 65535 * 64, ldy < co, a buffer of 2^31 bytes or more, a padded input
+ * extent of 2^31 or more; for pack a range outside [-128, 127] and a bad rounding.  LQ_EALIGN: codes or scales off the 16-byte
+ * grid; X, P, s, bias or Y off the 4-byte grid.
+ * Not built on this path: weight scales that vary along K (a group size below ci * kh * kw stays on the im2col path), offsets
+ * (asymmetric layers), MX elements, an epilogue that writes the next layer's pixel operand, dilation and groups.
+ *
  * Not built: epilogue output blocks other than 64 (per row, 128), offsets on the A operand (asymmetric activations), HWIO-stored conv kernels, any backward, sub-byte packing of
  * 4-bit codes.  */
 int lq_i8_operand_bytes(int64_t L, int64_t K, int64_t block, size_t* code_bytes, size_t* scale_bytes);
@@ -636,6 +675,13 @@ int lq_i8_gemm_quantize_affine(const void* a_codes, const void* a_scales, int64_
                                const void* b_offsets, int64_t b_block, const float* bias /* may be NULL */,
                                int activation /* lq_mx_activation */, int64_t out_block, void* out_codes, void* out_scales, int64_t M,
                                int64_t N, int64_t K, void* stream);
+int lq_i8_pixels_bytes(int64_t B, int64_t C, int64_t H, int64_t W, size_t* code_bytes, size_t* scale_bytes);
+int lq_i8_pixels_quantize(const float* X, const lq_conv_geom* g, void* codes, void* scales, void* stream);
+int lq_i8_conv_kernel_bytes(int64_t co, int64_t ci, int64_t KH, int64_t KW, size_t* code_bytes, size_t* scale_bytes);
+int lq_i8_conv_kernel_pack(const float* P, const float* s, int32_t qmin, int32_t qmax, int rounding, int64_t co, int64_t ci, int64_t KH,
+                           int64_t KW, void* codes, void* scales, void* stream);
+int lq_i8_conv2d(const void* pix_codes, const void* pix_scales, const void* k_codes, const void* k_scales,
+                 const float* bias /* may be NULL */, float* Y, int64_t ldy, const lq_conv_geom* g, int64_t co, void* stream);
 
 /* ---- K4: forward and NQ backward of one tensor in a single pass (benchmark path) ---
  * Same results as lq_fq_forward followed by lq_fq_scale_grad (out, max|q| and the vote count bit for bit; on

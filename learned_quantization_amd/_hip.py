@@ -167,6 +167,11 @@ SIGNATURES.update({
                                    ctypes.POINTER(_c_i64)]),
     "lq_mx_operand_im2col": (_c_int, [_c_p, ctypes.POINTER(ConvGeom), _c_int, _c_int, _c_p, _c_p, _c_p]),
     "lq_i8_operand_im2col": (_c_int, [_c_p, ctypes.POINTER(ConvGeom), _c_i64, _c_p, _c_p, _c_p]),
+    "lq_i8_pixels_bytes": (_c_int, [_c_i64, _c_i64, _c_i64, _c_i64, ctypes.POINTER(_c_sz), ctypes.POINTER(_c_sz)]),
+    "lq_i8_pixels_quantize": (_c_int, [_c_p, ctypes.POINTER(ConvGeom), _c_p, _c_p, _c_p]),
+    "lq_i8_conv_kernel_bytes": (_c_int, [_c_i64, _c_i64, _c_i64, _c_i64, ctypes.POINTER(_c_sz), ctypes.POINTER(_c_sz)]),
+    "lq_i8_conv_kernel_pack": (_c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p]),
+    "lq_i8_conv2d": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, ctypes.POINTER(ConvGeom), _c_i64, _c_p]),
 })
 
 

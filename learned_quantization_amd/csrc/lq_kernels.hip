@@ -22,6 +22,7 @@
 //   lq_im2col.hpp       a convolution's im2col matrix without the matrix: geometry, a line's window, the predicated gather
 //   lq_mx_conv.hpp      the MX operand of that matrix, gathered from the input in one launch
 //   lq_i8_conv.hpp      the int8 operand of the same matrix: absmax scales per (line, scale block), two passes over the gather
+//   lq_i8_direct.hpp    the direct int8 convolution: NHWC pixel operand, per-tap kernel operand, the product that gathers its windows
 //   this file           host side: traversal plan, launchers, the extern "C" entry points
 //
 // The path is elementwise + per-group reductions: HBM-bound, no MFMA.  Design rules
@@ -74,6 +75,7 @@
 #include "lq_i8_gemm.hpp"
 #include "lq_i8_conv.hpp"
 #include "lq_i8_gemm_quant.hpp"
+#include "lq_i8_direct.hpp"
 
 namespace lq {
 
@@ -2366,6 +2368,194 @@ int lq_i8_operand_im2col(const float* X, const lq_conv_geom* g, int64_t block, v
     if (slices == 1) hipLaunchKernelGGL(k_i8_im2col<1>, grid, blk, 0, st, op);
     else hipLaunchKernelGGL(k_i8_im2col<kI8ConvSlices>, grid, blk, 0, st, op);
     return check_hip("int8 im2col operand");
+}
+
+// ---- the direct int8 convolution (lq_i8_direct.hpp) ----
+struct I8DirectDims {
+    int64_t CP, step, CS, NT;
+    size_t code_bytes, scale_bytes;
+};
+
+// the padded channel count and the form of the product that follows from it; C <= 65536 keeps a tap's int32 sum exact
+static int i8_direct_channels(const char* fn, int64_t C, I8DirectDims& d) {
+    if (C > 65536)
+        return fail(LQ_EINVAL, "%s: C = %lld channels is above 65536: the int32 sum of one tap, that many products of magnitude up to "
+                    "2^14, could overflow", fn, (long long)C);
+    d.CP = (C + kI8PixAlign - 1) / kI8PixAlign * kI8PixAlign;
+    d.step = d.CP % 64 == 0 ? 64 : 32;
+    d.CS = d.CP / d.step;
+    return LQ_OK;
+}
+
+static int i8_pixels_dims(const char* fn, int64_t B, int64_t C, int64_t H, int64_t W, I8DirectDims& d) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0)
+        return fail(LQ_EINVAL, "%s: extents must be positive (B=%lld C=%lld H=%lld W=%lld)", fn, (long long)B, (long long)C, (long long)H,
+                    (long long)W);
+    if (int rc = i8_direct_channels(fn, C, d)) return rc;
+    const double bytes = (double)B * (double)H * (double)W * (double)d.CP;
+    if (bytes >= 2147483648.0)
+        return fail(LQ_EINVAL, "%s: the pixel codes, B * H * W * CP = %lld * %lld * %lld * %lld bytes, are not below 2^31", fn, (long long)B,
+                    (long long)H, (long long)W, (long long)d.CP);
+    d.code_bytes = (size_t)(B * H * W * d.CP);
+    d.scale_bytes = (size_t)(B * H * W * 4);
+    return LQ_OK;
+}
+
+static int i8_conv_kernel_dims(const char* fn, int64_t co, int64_t ci, int64_t KH, int64_t KW, I8DirectDims& d) {
+    if (co <= 0 || ci <= 0) return fail(LQ_EINVAL, "%s: extents must be positive (co=%lld ci=%lld)", fn, (long long)co, (long long)ci);
+    if (KH <= 0 || KW <= 0) return fail(LQ_EINVAL, "%s: kernel size must be positive (KH=%lld KW=%lld)", fn, (long long)KH, (long long)KW);
+    if (int rc = i8_direct_channels(fn, ci, d)) return rc;
+    if (co > 2147483647 - kI8TileLines) return fail(LQ_EINVAL, "%s: co = %lld is not below 2^31", fn, (long long)co);
+    d.NT = (co + kI8TileLines - 1) / kI8TileLines;
+    const double bytes = (double)(d.NT * kI8TileLines) * (double)KH * (double)KW * (double)d.CP;
+    if (bytes >= 2147483648.0)
+        return fail(LQ_EINVAL, "%s: the kernel codes, 16 NT * KH * KW * CP bytes (co=%lld ci=%lld KH=%lld KW=%lld), are not below 2^31", fn,
+                    (long long)co, (long long)ci, (long long)KH, (long long)KW);
+    d.code_bytes = (size_t)(d.NT * kI8TileLines * KH * KW * d.CP);
+    d.scale_bytes = (size_t)(d.NT * kI8TileLines * 4);
+    return LQ_OK;
+}
+
+int lq_i8_pixels_bytes(int64_t B, int64_t C, int64_t H, int64_t W, size_t* code_bytes, size_t* scale_bytes) {
+    const char* fn = __func__;
+    if (!code_bytes || !scale_bytes) return fail(LQ_EINVAL, "%s: code_bytes or scale_bytes is NULL", fn);
+    I8DirectDims d{};
+    int rc = i8_pixels_dims(fn, B, C, H, W, d);
+    if (rc) return rc;
+    *code_bytes = d.code_bytes;
+    *scale_bytes = d.scale_bytes;
+    return LQ_OK;
+}
+
+int lq_i8_conv_kernel_bytes(int64_t co, int64_t ci, int64_t KH, int64_t KW, size_t* code_bytes, size_t* scale_bytes) {
+    const char* fn = __func__;
+    if (!code_bytes || !scale_bytes) return fail(LQ_EINVAL, "%s: code_bytes or scale_bytes is NULL", fn);
+    I8DirectDims d{};
+    int rc = i8_conv_kernel_dims(fn, co, ci, KH, KW, d);
+    if (rc) return rc;
+    *code_bytes = d.code_bytes;
+    *scale_bytes = d.scale_bytes;
+    return LQ_OK;
+}
+
+int lq_i8_pixels_quantize(const float* X, const lq_conv_geom* g, void* codes, void* scales, void* stream) {
+    const char* fn = __func__;
+    LQ_REQUIRE_PTR_FN(fn, X);
+    if (!g) return fail(LQ_EINVAL, "%s: argument 'g' is NULL", fn);
+    I8DirectDims d{};
+    int rc = i8_pixels_dims(fn, g->B, g->C, g->H, g->W, d);
+    if (rc) return rc;
+    if (g->xs_b < 0 || g->xs_c < 0 || g->xs_h < 0 || g->xs_w < 0)
+        return fail(LQ_EINVAL, "%s: strides of X must not be negative (xs_b=%lld xs_c=%lld xs_h=%lld xs_w=%lld)", fn, (long long)g->xs_b,
+                    (long long)g->xs_c, (long long)g->xs_h, (long long)g->xs_w);
+    if ((rc = check_operand_buffers(fn, codes, scales, kI8ScaleAlign))) return rc;
+    I8PixelsParams op{};
+    op.g.P = X;
+    op.g.lo = op.ip.lo = -127.0f;
+    op.g.hi = op.ip.hi = 127.0f;
+    op.ip.min_value = kOperandMinScale;
+    op.codes = (uint8_t*)codes;
+    op.scales = (float*)scales;
+    op.xs_b = g->xs_b;
+    op.xs_c = g->xs_c;
+    op.xs_h = g->xs_h;
+    op.xs_w = g->xs_w;
+    op.hw = make_fastdiv((uint32_t)(g->H * g->W));      // B H W CP < 2^31 bounds every product of the extents
+    op.w = make_fastdiv((uint32_t)g->W);
+    op.NP = (int32_t)(g->B * g->H * g->W);
+    op.C = (int32_t)g->C;
+    op.CP = (int32_t)d.CP;
+    const dim3 grid((unsigned)(((int64_t)op.NP + kBlock - 1) / kBlock)), blk(kBlock);
+    hipLaunchKernelGGL(k_i8_pixels, grid, blk, 0, (hipStream_t)stream, op);
+    return check_hip("int8 pixel operand");
+}
+
+int lq_i8_conv_kernel_pack(const float* P, const float* s, int32_t qmin, int32_t qmax, int rounding, int64_t co, int64_t ci, int64_t KH,
+                           int64_t KW, void* codes, void* scales, void* stream) {
+    const char* fn = __func__;
+    LQ_REQUIRE_PTR_FN(fn, P);
+    LQ_REQUIRE_PTR_FN(fn, s);
+    int rc = check_clip_range(fn, qmin, qmax);
+    if (rc || (rc = check_rounding(fn, rounding))) return rc;
+    if (qmin < -128 || qmax > 127)
+        return fail(LQ_EINVAL, "%s: range [%d, %d] is not inside [-128, 127], the operands of the int8 matrix instruction", fn, (int)qmin,
+                    (int)qmax);
+    I8DirectDims d{};
+    if ((rc = i8_conv_kernel_dims(fn, co, ci, KH, KW, d))) return rc;
+    if ((rc = check_operand_buffers(fn, codes, scales, kI8ScaleAlign))) return rc;
+    I8ConvPackParams op{};
+    op.g.P = P;
+    op.g.s = s;
+    op.g.lo = (float)qmin;
+    op.g.hi = (float)qmax;
+    op.g.k = 1.0f;
+    op.codes = (uint8_t*)codes;
+    op.scales = (float*)scales;
+    op.co = (int32_t)co;
+    op.ci = (int32_t)ci;
+    op.KHKW = (int32_t)(KH * KW);
+    op.NT = (int32_t)d.NT;
+    op.CS = (int32_t)d.CS;
+    const int64_t threads = d.NT * KH * KW * d.CS * 64;
+    const dim3 grid((unsigned)((threads + kBlock - 1) / kBlock)), blk(kBlock);
+    hipStream_t st = (hipStream_t)stream;
+    const bool rne = rounding == LQ_ROUND_NEAREST_EVEN;
+    if (d.step == 64) {
+        if (rne) hipLaunchKernelGGL((k_i8_conv_pack<true, 64>), grid, blk, 0, st, op);
+        else hipLaunchKernelGGL((k_i8_conv_pack<false, 64>), grid, blk, 0, st, op);
+    } else {
+        if (rne) hipLaunchKernelGGL((k_i8_conv_pack<true, 32>), grid, blk, 0, st, op);
+        else hipLaunchKernelGGL((k_i8_conv_pack<false, 32>), grid, blk, 0, st, op);
+    }
+    return check_hip("int8 conv kernel pack");
+}
+
+int lq_i8_conv2d(const void* pix_codes, const void* pix_scales, const void* k_codes, const void* k_scales, const float* bias, float* Y,
+                 int64_t ldy, const lq_conv_geom* g, int64_t co, void* stream) {
+    const char* fn = __func__;
+    ConvDims cd;
+    int rc = conv_geom_dims(fn, g, cd);            // the xs_* fields are not read
+    if (rc) return rc;
+    I8DirectDims dp{}, dk{};
+    if ((rc = i8_pixels_dims(fn, g->B, g->C, g->H, g->W, dp))) return rc;
+    if ((rc = i8_conv_kernel_dims(fn, co, g->C, g->KH, g->KW, dk))) return rc;
+    if ((rc = check_operand_buffers(fn, pix_codes, pix_scales, kI8ScaleAlign))) return rc;
+    if ((rc = check_operand_buffers(fn, k_codes, k_scales, kI8ScaleAlign))) return rc;
+    if ((rc = check_gemm_output(fn, bias, Y, ldy, cd.M, co))) return rc;
+    // the kernel forms a window's corner, oh * stride_h - pad_top, in 32 bits
+    if (g->H + g->pad_top + g->pad_bottom > 2147483647 || g->W + g->pad_left + g->pad_right > 2147483647)
+        return fail(LQ_EINVAL, "%s: the padded input (%lld x %lld) does not fit 32 bits", fn, (long long)(g->H + g->pad_top + g->pad_bottom),
+                    (long long)(g->W + g->pad_left + g->pad_right));
+    const int64_t MT = (cd.M + kI8TileLines - 1) / kI8TileLines;
+    dim3 grid;
+    if ((rc = gemm_grid(fn, (dk.NT + 3) / 4, MT, cd.M, grid))) return rc;
+    I8Conv2dParams p{};
+    p.pix_codes = (const uint8_t*)pix_codes;
+    p.pix_scales = (const float*)pix_scales;
+    p.k_codes = (const uint8_t*)k_codes;
+    p.k_scales = (const float*)k_scales;
+    p.bias = bias;
+    p.Y = Y;
+    p.ldy = ldy;
+    p.ohow = make_fastdiv((uint32_t)(cd.OH * cd.OW));      // M <= 65535 * 64 bounds OH * OW and OW
+    p.ow = make_fastdiv((uint32_t)cd.OW);
+    p.M = (int32_t)cd.M;
+    p.N = (int32_t)co;
+    p.MT = (int32_t)MT;
+    p.NT = (int32_t)dk.NT;
+    p.CS = (int32_t)dk.CS;
+    p.CP = (int32_t)dk.CP;
+    p.H = (int32_t)g->H;
+    p.W = (int32_t)g->W;
+    p.KH = g->KH;
+    p.KW = g->KW;
+    p.stride_h = g->stride_h;
+    p.stride_w = g->stride_w;
+    p.pad_top = g->pad_top;
+    p.pad_left = g->pad_left;
+    if (dk.step == 64) hipLaunchKernelGGL(k_i8_conv2d<64>, grid, dim3(kBlock), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(k_i8_conv2d<32>, grid, dim3(kBlock), 0, (hipStream_t)stream, p);
+    return check_hip("direct int8 convolution");
 }
 
 static int i8_operand_decode(const char* fn, bool affine, const void* codes, const void* scales, const void* offsets, int64_t L,

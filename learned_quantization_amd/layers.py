@@ -830,6 +830,7 @@ def _same_padding(size: int, k: int, s: int) -> Tuple[int, int]:
 class _ConvBase(_HostLayer):
     _prefix = "custom_conv2d_layer"
     _has_bias = True
+    _i8_direct_hw = None      # (operand, bias) parked by i8_hardware(convs=True, direct=True)
 
     def __init__(self, seed=None, penalty_threshold=None, orientation="scalar", initializer=None, filters=None,
                  kernel_size=(3, 3), strides=(1, 1), padding="same", name=None, regularizer=None,
@@ -931,6 +932,10 @@ class _ConvBase(_HostLayer):
     def call(self, inputs):
         if not self.built:
             self.build(tuple(inputs.shape), device=inputs.device)
+        direct = self._i8_direct_hw
+        if direct is not None and not self.training:              # inside layers.i8_hardware(..., convs=True, direct=True), eval mode
+            self._q_pre = None
+            return self._direct_conv(inputs, direct[0], direct[1])
         for family in (_MX, _I8):
             hw = getattr(self, family.hw, None)
             if hw is not None and not self.training:              # inside layers.mx_hardware / i8_hardware(..., convs=True), eval mode
@@ -1053,6 +1058,66 @@ class _ConvBase(_HostLayer):
         _check_max_lines(max_lines)
         ops.check_i8_block(act_block)
         return self._call_matrix(inputs, _I8, (act_block,), max_lines, offsets=offsets)
+
+    def _check_i8_direct(self):
+        """(qmin, qmax) of a conv layer that can run as a direct int8 convolution, or ValueError naming the reason
+        (ops.check_i8_direct_layer): what ``_check_i8`` asks, symmetric, and one scale per filter."""
+        fan_in = self.kernel.shape[0] * self.kernel.shape[1] * self.kernel.shape[2] if self.built else None
+        q_range = ops.check_i8_direct_layer(self.q_range, self.nested_q_k_layer.orientation, self.group_size, self.asymmetric,
+                                            self.element_format, fan_in, self.kernel_storage)
+        if not self.built:
+            raise ValueError(f"{self.name}: the layer is not built yet (no kernel to pack)")
+        return q_range
+
+    def i8_direct_operand(self) -> "ops.I8ConvKernel":
+        """The kernel under its current scales as the per-tap operand of the direct int8 convolution (ops.i8_conv_kernel_pack): the
+        codes of ``i8_operand()``, in the order ops.i8_conv2d reads them, under one scale per filter.  ValueError naming the reason
+        for everything ``i8_operand()`` refuses, for an asymmetric layer and for group-wise scales that vary along (ci, kh, kw)."""
+        qmin, qmax = self._check_i8_direct()
+        scale = self.nested_q_k_layer.scale.data.reshape(-1)      # one element ("scalar"), or one per filter ("groupwise", (co, 1))
+        return ops.i8_conv_kernel_pack(self.kernel.detach().permute(3, 2, 0, 1), scale, qmin, qmax, self.rounding)
+
+    def _direct_conv(self, inputs, operand, qb, max_lines=None):
+        """The layer as a direct int8 convolution: per run of whole images (by lines) the pixel operand of the inputs, convolved
+        with ``operand``, plus ``qb``, into its rows of the one result.  Where ``operand`` is a tensor (the fake-quantised OIHW
+        kernel: ``emulate=True``) the decoded pixel operand is convolved with it by ``F.conv2d`` instead."""
+        with torch.no_grad():
+            if inputs.dim() != 4:
+                raise ValueError(f"{self.name}: the input must have four axes, got shape {tuple(inputs.shape)}")
+            x = inputs.permute(0, 3, 1, 2) if self.data_format == "NHWC" else inputs       # a view: the quantizer reads its strides
+            top, bottom, left, right = padding = self._mx_padding(x.shape[2], x.shape[3])
+            M, _, OH, OW = ops.mx_im2col_dims(x.shape, self.kernel_size, self.strides, padding)
+            B, C, per = x.shape[0], x.shape[1], OH * OW
+            y = torch.empty((M, self.filters), dtype=torch.float32, device=x.device)
+            fit = 65535 * 64 if max_lines is None else min(65535 * 64, max_lines)
+            images = max(1, min(B, fit // per))
+            for b0 in range(0, B, images):
+                b1 = min(B, b0 + images)
+                pixels = ops.i8_pixels_quantize(x[b0:b1])
+                if not isinstance(operand, torch.Tensor):
+                    ops.i8_conv2d(pixels, operand, qb, self.strides, padding, out=y[b0 * per:b1 * per])
+                    continue
+                decoded = pixels.codes[..., :C].view(torch.int8).float().mul_(pixels.scales.unsqueeze(-1)).permute(0, 3, 1, 2)
+                out = F.conv2d(F.pad(decoded, (left, right, top, bottom)), operand, qb, self.strides)
+                y[b0 * per:b1 * per].copy_(out.permute(0, 2, 3, 1).reshape(-1, self.filters))
+            y = y.view(B, OH, OW, self.filters)                   # [M][co] is NHWC: no transposition launch
+            return y if self.data_format == "NHWC" else y.permute(0, 3, 1, 2)
+
+    def call_i8_direct(self, inputs, max_lines=None):
+        """The layer as a direct int8 convolution, under ``no_grad``: the inputs quantised ONCE per pixel to symmetric 8-bit integers
+        (ops.i8_pixels_quantize: an int8 NHWC copy, one scale per pixel), convolved with ``i8_direct_operand()`` on the int8 matrix
+        instruction by ops.i8_conv2d -- TensorFlow 'SAME' padding as ``call`` pads, or 'VALID' -- plus the fake-quantised bias where
+        the layer has one.  No im2col matrix is written.  Inference only.  The result is the kind of view ``call_i8`` returns.  A
+        batch of more than 65535 * 64 lines or more than ``max_lines`` lines is cut into runs of whole images; the result does not
+        depend on the cut.  The activation scale is per PIXEL here and per im2col LINE in ``call_i8``: the two paths round the
+        activations differently and are not bit-identical."""
+        _check_max_lines(max_lines)
+        if not self.built:
+            self.build(tuple(inputs.shape), device=inputs.device)
+        with torch.no_grad():
+            operand = self.i8_direct_operand()
+            qb = self.nested_q_b_layer(self.b) if self._has_bias else None
+            return self._direct_conv(inputs, operand, qb, max_lines)
 
 
 class CustomConv2DLayer(_ConvBase):
@@ -1183,6 +1248,24 @@ def i8_conv_eligible(layer: nn.Module, offsets=False) -> bool:
     return _passes_check_i8(layer, _ConvBase, offsets)
 
 
+def i8_direct_eligible(layer: nn.Module) -> bool:
+    """Whether ``layer`` can run as a direct int8 convolution (``call_i8_direct``): it passes ``i8_conv_eligible``, is symmetric, and
+    has one scale per filter ("scalar", or "groupwise" with ``group_size >= ci kh kw``)."""
+    if not isinstance(layer, _ConvBase):
+        return False
+    try:
+        layer._check_i8_direct()
+    except ValueError:
+        return False
+    return True
+
+
+def _takes_direct(layer: nn.Module) -> bool:
+    """What ``i8_hardware(direct=True)`` sends down the direct path: an eligible conv whose input channels fill whole steps of 32
+    (a first layer of 3 channels would multiply 29 padded zeros per tap: it stays on the im2col path)."""
+    return i8_direct_eligible(layer) and layer.kernel.shape[2] % 32 == 0
+
+
 class i8_hardware(_matrix_hardware):
     """Context manager beside ``mx_hardware``: inside it every eligible Dense layer of ``model`` (``i8_hardware_eligible``) computes
     its eval-mode ``call`` as ``call_i8`` does -- activations quantised per row and ``act_block`` inputs to symmetric 8-bit
@@ -1204,11 +1287,18 @@ class i8_hardware(_matrix_hardware):
     ``offsets=True``: asymmetric layers (a learned offset per group) switch too, and ``layers`` lists them: their operand carries
     the offsets and their product adds the offset's row-sum term, which costs matrix instructions that a symmetric product does
     not pay -- hence the opt-in.  It combines with ``convs``, ``fused`` and ``emulate`` (which needs nothing new: it multiplies the
-    decoded activation with the fake-quantised kernel); a symmetric model is bit-identical with or without it."""
+    decoded activation with the fake-quantised kernel); a symmetric model is bit-identical with or without it.
+    ``direct=True`` (with ``convs=True``): an eligible conv layer with one scale per filter, symmetric, whose input channels are a
+    multiple of 32 (``i8_direct_eligible``) computes what its ``call_i8_direct`` does instead -- its input quantised once per pixel
+    (ops.i8_pixels_quantize), the windows gathered inside the product (ops.i8_conv2d), no im2col matrix -- and is listed in
+    ``direct_layers`` as well as in ``layers``; ``act_block`` does not apply to it (the scale is per pixel).  Every other layer goes
+    where it goes without ``direct``.  Under ``emulate=True`` such a layer convolves the decoded pixel operand with the
+    fake-quantised kernel by ``F.conv2d``.  Without ``direct`` (the default) nothing changes."""
 
-    _family, _dense_eligible, _conv_eligible = _I8, staticmethod(i8_hardware_eligible), staticmethod(i8_conv_eligible)
+    _family, _dense_eligible = _I8, staticmethod(i8_hardware_eligible)
 
-    def __init__(self, model: nn.Module, act_block=0, emulate=False, convs=False, fused=False, offsets=False):
+    def __init__(self, model: nn.Module, act_block=0, emulate=False, convs=False, fused=False, offsets=False, direct=False):
+        self.direct, self.direct_layers = bool(direct), []
         self.offsets = bool(offsets)
         self._opt_in = {"offsets": True} if self.offsets else {}
         self.model, self.act_block, self.emulate, self.fused = model, ops.check_i8_block(act_block), bool(emulate), bool(fused)
@@ -1220,6 +1310,31 @@ class i8_hardware(_matrix_hardware):
                              f"{ops.I8_OUT_BLOCK}, so the fused model would not be the unfused one; give act_block={ops.I8_OUT_BLOCK}")
         self.convs, self._act = bool(convs), (self.act_block,)
         self.layers, self.fused_layers, self._fused_modules = [], [], []
+
+    def _conv_eligible(self, layer, **opt_in):
+        """The convs of the im2col path: with ``direct`` those that the direct path does not take."""
+        return i8_conv_eligible(layer, **opt_in) and not (self.direct and _takes_direct(layer))
+
+    def __enter__(self):
+        direct = [m for m in custom_layers_of(self.model) if _takes_direct(m)] if self.direct and self.convs else []
+        with torch.no_grad():     # every operand before any layer switches: an exception here leaves the model as it was
+            parked = [(m.nested_q_k_layer(m.kernel).detach().permute(3, 2, 0, 1) if self.emulate else m.i8_direct_operand(),
+                       m.nested_q_b_layer(m.b).detach() if m._has_bias else None) for m in direct]
+        super().__enter__()
+        for m, hw in zip(direct, parked):
+            m._i8_direct_hw = hw
+        self.direct_layers = direct
+        if direct:                # ``layers``: the Dense layers, then the conv layers of either path in module order
+            order = {id(m): k for k, m in enumerate(custom_layers_of(self.model))}
+            dense = [m for m in self.layers if isinstance(m, CustomDenseLayer)]
+            convs = [m for m in self.layers if not isinstance(m, CustomDenseLayer)] + direct
+            self.layers = dense + sorted(convs, key=lambda m: order[id(m)])
+        return self
+
+    def __exit__(self, *exc):
+        for m in self.direct_layers:
+            m._i8_direct_hw = None
+        return super().__exit__(*exc)
 
 
 def _dense_chain(fn, family, gemm_name, check_layer, check_act, x, chain, act, out, **operand_kwargs):

@@ -590,7 +590,11 @@ def mx_operand_decode(operand: MxOperand) -> torch.Tensor:
 def _gemm_output(a, b, bias: Optional[torch.Tensor], out: Optional[torch.Tensor] = None, fp32_out: bool = True):
     """``(bias, out, ldy)`` of the product of two operands: the bias checked, ``out`` checked or made, its leading dimension.
     ``fp32_out=False`` (the operand-out epilogue writes no fp32 matrix) checks the bias alone."""
-    M, N = a.lines, b.lines
+    return _matrix_output(a.lines, b.lines, a.codes.device, bias, out, fp32_out)
+
+
+def _matrix_output(M: int, N: int, device, bias: Optional[torch.Tensor], out: Optional[torch.Tensor] = None, fp32_out: bool = True):
+    """``_gemm_output`` from the extents: a result of M lines by N columns on ``device``."""
     if bias is not None:
         bias = _hip.require_device_f32(bias, "bias")
         if tuple(bias.shape) != (N,):
@@ -598,7 +602,7 @@ def _gemm_output(a, b, bias: Optional[torch.Tensor], out: Optional[torch.Tensor]
     if not fp32_out:
         return bias, None, 0
     if out is None:
-        out = torch.empty((M, N), dtype=torch.float32, device=a.codes.device)
+        out = torch.empty((M, N), dtype=torch.float32, device=device)
     elif out.dtype != torch.float32 or tuple(out.shape) != (M, N) or (N > 1 and out.stride(1) != 1) or not out.is_cuda:
         raise ValueError(f"out must be a float32 device matrix ({M}, {N}) with unit column stride")
     return bias, out, out.stride(0) if M > 1 else max(N, out.stride(0))
@@ -1013,6 +1017,137 @@ def i8_operand_im2col(x: torch.Tensor, kernel_size, strides=(1, 1), padding=(0, 
     op = I8ConvOperand(codes, scales, M, K, block)
     op.out_hw = (OH, OW)
     return op
+
+
+# --------------------------------------------------------------------------- the direct int8 convolution (no im2col matrix)
+I8_DIRECT_MAX_CHANNELS = 65536       # a tap's int32 sum over the channels stays exact (include/lq_hip.h)
+
+
+class I8Pixels(NamedTuple):
+    """An input ``(B, C, H, W)`` quantised once per pixel (``i8_pixels_quantize``; include/lq_hip.h, "direct int8 convolution"):
+    ``codes`` uint8 ``(B, H, W, CP)``, plain NHWC with ``CP = 32 ceil(C / 32)`` and code 0 past C; ``scales`` float32 ``(B, H, W)``;
+    ``shape`` the input's logical ``(B, C, H, W)``."""
+    codes: torch.Tensor
+    scales: torch.Tensor
+    shape: Tuple[int, int, int, int]
+
+
+class I8ConvKernel(NamedTuple):
+    """A conv kernel ``(co, ci, kh, kw)`` under one scale per filter, packed per tap in fragment order (``i8_conv_kernel_pack``):
+    ``codes`` (uint8) and ``scales`` (float32, ``16 ceil(co / 16)``) are opaque buffers of lq_i8_conv_kernel_bytes' sizes."""
+    codes: torch.Tensor
+    scales: torch.Tensor
+    filters: int
+    channels: int
+    kernel_size: Tuple[int, int]
+
+
+def check_i8_direct_layer(q_range, orientation, group_size=None, asymmetric=False, element_format=None, fan_in=None,
+                          kernel_storage="oihw") -> Tuple[int, int]:
+    """What a conv layer's quantizer must be to run as a direct int8 convolution -- (qmin, qmax) -- or ValueError naming the
+    reason: everything ``check_i8_conv_operand_layer`` asks of a symmetric layer, and ONE scale per filter ("scalar", or "groupwise"
+    with ``group_size >= fan_in = ci kh kw``): the product applies the filter's scale once, after the last tap."""
+    qmin, qmax = check_i8_conv_operand_layer(q_range, orientation, group_size, asymmetric, element_format, fan_in, kernel_storage)
+    if orientation == "groupwise" and (fan_in is None or group_size < fan_in):
+        raise ValueError(f"group_size={group_size!r}: the direct int8 convolution takes one scale per filter; a scale that varies "
+                         f"along K = ci kh kw ({fan_in}) stays on the im2col path (call_i8)")
+    return qmin, qmax
+
+
+def _byte_pair(lib_fn, what, *extents) -> Tuple[int, int]:
+    import ctypes
+    cb, sb = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _hip.check(lib_fn(*(int(e) for e in extents), ctypes.byref(cb), ctypes.byref(sb)), what)
+    return int(cb.value), int(sb.value)
+
+
+def i8_pixels_bytes(B: int, C: int, H: int, W: int) -> Tuple[int, int]:
+    """(code_bytes, scale_bytes) of the pixel operand of an input ``(B, C, H, W)`` (lq_i8_pixels_bytes).  Needs no device."""
+    return _byte_pair(_hip.load().lq_i8_pixels_bytes, "lq_i8_pixels_bytes", B, C, H, W)
+
+
+def i8_conv_kernel_bytes(co: int, ci: int, kh: int, kw: int) -> Tuple[int, int]:
+    """(code_bytes, scale_bytes) of a packed conv kernel (lq_i8_conv_kernel_bytes).  Needs no device."""
+    return _byte_pair(_hip.load().lq_i8_conv_kernel_bytes, "lq_i8_conv_kernel_bytes", co, ci, kh, kw)
+
+
+def i8_pixels_quantize(x: torch.Tensor) -> I8Pixels:
+    """The pixel operand of ``x (B, C, H, W)``: per pixel the absmax scale of its C channels and the nearest-rounded symmetric 8-bit
+    codes under it -- ``i8_operand_quantize`` of the row ``x.permute(0, 2, 3, 1).reshape(-1, C)`` -- as an int8 NHWC copy
+    (include/lq_hip.h, lq_i8_pixels_quantize).  ``x`` is read through its own strides (NCHW-contiguous, channels_last or any view):
+    no copy.  One launch."""
+    import ctypes
+    _require_conv_input(x)
+    lib = _hip.load()
+    B, C, H, W = (int(d) for d in x.shape)
+    cb, sb = i8_pixels_bytes(B, C, H, W)
+    g = _hip.ConvGeom(B, C, H, W, *(int(e) for e in x.stride()), 1, 1, 1, 1, 0, 0, 0, 0)
+    codes = torch.empty((B, H, W, cb // (B * H * W)), dtype=torch.uint8, device=x.device)
+    scales = torch.empty((B, H, W), dtype=torch.float32, device=x.device)
+    _hip.check(lib.lq_i8_pixels_quantize(_hip.ptr(x), ctypes.byref(g), _hip.ptr(codes), _hip.ptr(scales), _hip.stream_ptr(x.device)),
+               "lq_i8_pixels_quantize")
+    return I8Pixels(codes, scales, (B, C, H, W))
+
+
+def i8_conv_kernel_pack(kernel: torch.Tensor, scale: torch.Tensor, qmin: int, qmax: int, rounding: str = "floor") -> I8ConvKernel:
+    """The operand of a conv kernel ``(co, ci, kh, kw)`` (OIHW; a non-contiguous tensor is copied) under ``scale``, one per filter
+    (``co`` elements, or one element for all filters): the clamped integers of ``i8_operand_pack`` for the same elements, per tap in
+    the fragment order the product reads (include/lq_hip.h, lq_i8_conv_kernel_pack).  One launch."""
+    qmin, qmax = check_q_range(qmin, qmax)
+    if qmin < I8_RANGE[0] or qmax > I8_RANGE[1]:
+        raise ValueError(f"range ({qmin}, {qmax}) is not inside [{I8_RANGE[0]}, {I8_RANGE[1]}], the signed bytes the int8 matrix "
+                         "instruction multiplies")
+    rnd = check_rounding(rounding)
+    if not isinstance(kernel, torch.Tensor) or kernel.dim() != 4:
+        raise ValueError(f"kernel must have four axes (co, ci, kh, kw), got {tuple(kernel.shape) if isinstance(kernel, torch.Tensor) else type(kernel).__name__}")
+    p = _hip.require_device_f32(kernel, "kernel")
+    co, ci, kh, kw = (int(d) for d in p.shape)
+    s = _hip.require_device_f32(scale, "scale").reshape(-1)
+    if s.numel() not in (1, co):
+        raise ValueError(f"scale must hold one element or one per filter ({co}), got shape {tuple(scale.shape)}")
+    s = s.expand(co).contiguous()
+    lib = _hip.load()
+    cb, sb = i8_conv_kernel_bytes(co, ci, kh, kw)
+    codes = torch.empty(cb, dtype=torch.uint8, device=p.device)
+    scales = torch.empty(sb // 4, dtype=torch.float32, device=p.device)
+    _hip.check(lib.lq_i8_conv_kernel_pack(_hip.ptr(p), _hip.ptr(s), qmin, qmax, rnd, co, ci, kh, kw, _hip.ptr(codes), _hip.ptr(scales),
+                                          _hip.stream_ptr(p.device)), "lq_i8_conv_kernel_pack")
+    return I8ConvKernel(codes, scales, co, ci, (kh, kw))
+
+
+def i8_conv2d(pixels: I8Pixels, kernel: I8ConvKernel, bias: Optional[torch.Tensor] = None, strides=(1, 1), padding=(0, 0, 0, 0),
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The convolution of a pixel operand with a packed kernel on the int8 matrix instruction, ``Y (B OH OW, co)`` in fp32 -- NHWC
+    once reshaped -- bit for bit the definition of include/lq_hip.h, lq_i8_conv2d: per tap an exact int32 sum over the channels
+    under that pixel's scale, the filter's scale after the last tap, then the bias.  The extents come from the operands;
+    ``padding`` is (top, bottom, left, right).  ``out``: a float32 matrix to write into; its row stride is the leading dimension.
+    One launch, no im2col matrix."""
+    import ctypes
+    B, C, H, W = (int(d) for d in pixels.shape)
+    if C != kernel.channels:
+        raise ValueError(f"the input has {C} channels and the kernel {kernel.channels}")
+    dev = pixels.codes.device
+    pcb, psb = i8_pixels_bytes(B, C, H, W)
+    kcb, ksb = i8_conv_kernel_bytes(kernel.filters, kernel.channels, *kernel.kernel_size)
+    # the kernel reads the buffers by the extents named here: each must be the whole buffer of those extents, on this device
+    for name, t, dtype, numel in (("pixels.codes", pixels.codes, torch.uint8, pcb), ("pixels.scales", pixels.scales, torch.float32, psb // 4),
+                                  ("kernel.codes", kernel.codes, torch.uint8, kcb), ("kernel.scales", kernel.scales, torch.float32, ksb // 4)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.numel() != numel or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dtype} tensor of {numel} elements for an input {(B, C, H, W)} and a kernel "
+                             f"({kernel.filters}, {kernel.channels}, {kernel.kernel_size[0]}, {kernel.kernel_size[1]})")
+    if tuple(pixels.codes.shape) != (B, H, W, pcb // (B * H * W)):
+        raise ValueError(f"pixels.codes has shape {tuple(pixels.codes.shape)}, not (B, H, W, CP) = {(B, H, W, pcb // (B * H * W))}")
+    for name, t in (("pixels.codes", pixels.codes), ("pixels.scales", pixels.scales), ("kernel.codes", kernel.codes), ("kernel.scales", kernel.scales)):
+        if not t.is_cuda or t.device != dev or (dev.index is not None and dev.index != torch.cuda.current_device()):
+            raise RuntimeError(f"{name} is on {t.device}: both operands must be on the current HIP device; there is no CPU fallback")
+    lib = _hip.load()
+    g = _conv_geom(pixels.shape, (0, 0, 0, 0), kernel.kernel_size, strides, padding)
+    M = _geom_dims(lib, g)[0]
+    bias, out, ldy = _matrix_output(M, kernel.filters, dev, bias, out)
+    _hip.check(lib.lq_i8_conv2d(_hip.ptr(pixels.codes), _hip.ptr(pixels.scales), _hip.ptr(kernel.codes), _hip.ptr(kernel.scales),
+                                _hip.ptr(bias), _hip.ptr(out), ldy, ctypes.byref(g), kernel.filters, _hip.stream_ptr(out.device)),
+               "lq_i8_conv2d")
+    return out
 
 
 STATS_MAX_BINS = 4096   # include/lq_hip.h, lq_group_stats: the widest range whose codes it bins

@@ -629,6 +629,12 @@ def build_parser():
                          "instruction, their im2col operand gathered by ops.i8_operand_im2col) and add i8_eval_conv_layers, "
                          "i8_eval_conv_accuracy and i8_eval_conv_max_logit_diff (the model's outputs against the emulated path with "
                          "convs=True) to the result line")
+    ap.add_argument("--i8-eval-direct", action="store_true",
+                    help="with --i8-eval --i8-eval-convs: evaluate once more under layers.i8_hardware(convs=True, direct=True) (conv "
+                         "layers with one scale per filter and a multiple of 32 input channels as a direct int8 convolution: the "
+                         "input quantised once per pixel, no im2col matrix) and add i8_eval_direct_layers, "
+                         "i8_eval_direct_im2col_layers (the convs that stay on the im2col path), i8_eval_direct_accuracy and "
+                         "i8_eval_direct_max_logit_diff (the model's outputs against the emulated path) to the result line")
     ap.add_argument("--i8-eval-fused", action="store_true",
                     help="with --i8-eval --i8-eval-act-block 64: evaluate once more under layers.i8_hardware(fused=True) (the Dense "
                          "tail through layers.i8_dense_chain: relu and the next operand's quantisation, per row and block of 64, in "
@@ -642,7 +648,7 @@ def build_parser():
 
 
 @torch.no_grad()
-def i8_eval(model, x, y, act_block=0, convs=False, fused=False, offsets=False):
+def i8_eval(model, x, y, act_block=0, convs=False, fused=False, offsets=False, direct=False):
     """One evaluation of ``model`` on (x, y) under layers.i8_hardware, one under its ``emulate=True`` yardstick and one of the
     fake-quantised model as it stands: a dict of the three accuracies and the largest |difference| of the outputs of the last Dense
     layer that took the path (the logits of the MNIST model) between the hardware path and each of the other two.  ValueError for
@@ -651,7 +657,9 @@ def i8_eval(model, x, y, act_block=0, convs=False, fused=False, offsets=False):
     outputs between the two; a model without such a Dense layer is then accepted, and its Dense fields are those of the model's
     own output with no layer switched.  ``fused=True`` (``act_block`` must be 64) adds an evaluation under
     ``i8_hardware(fused=True)``: the number of layers that fused, its accuracy and the largest |difference| of the model's ``logits``
-    from the unfused hardware path's (the same bits are expected: 0.0)."""
+    from the unfused hardware path's (the same bits are expected: 0.0).  ``direct=True`` (with ``convs=True``) adds an evaluation
+    under ``i8_hardware(convs=True, direct=True)`` and one under its emulation: the conv layers on the direct int8 convolution, those
+    left on the im2col path, the accuracy, and the largest |difference| of the model's outputs between the two."""
     was_training = model.training
     model.eval()
     acc, logits = [], []
@@ -696,6 +704,19 @@ def i8_eval(model, x, y, act_block=0, convs=False, fused=False, offsets=False):
                     outs.append(model(x))
             fields.update({"i8_eval_conv_layers": n_convs, "i8_eval_conv_accuracy": float((outs[0].argmax(1) == y).float().mean()),
                            "i8_eval_conv_max_logit_diff": float((outs[0] - outs[1]).abs().max())})
+        if convs and direct:
+            outs = []
+            for emulate in (False, True):
+                with L.i8_hardware(model, probe.act_block, emulate=emulate, convs=True, offsets=offsets, direct=True) as hwd:
+                    if not hwd.direct_layers:
+                        raise ValueError("i8_eval: direct=True needs a conv layer that can run as a direct int8 convolution (one scale "
+                                         "per filter, symmetric, a multiple of 32 input channels)")
+                    n_direct = len(hwd.direct_layers)
+                    n_im2col = sum(L.i8_conv_eligible(m, offsets) for m in hwd.layers) - n_direct
+                    outs.append(model(x))
+            fields.update({"i8_eval_direct_layers": n_direct, "i8_eval_direct_im2col_layers": n_im2col,
+                           "i8_eval_direct_accuracy": float((outs[0].argmax(1) == y).float().mean()),
+                           "i8_eval_direct_max_logit_diff": float((outs[0] - outs[1]).abs().max())})
     finally:
         model.train(was_training)
     return {"i8_eval_act_block": probe.act_block, "i8_eval_layers": n_layers, "i8_eval_accuracy": acc[0],
@@ -776,6 +797,9 @@ def main(argv=None):
         ap.error("--i8-eval-act-block needs --i8-eval")
     if args.i8_eval_convs and not args.i8_eval:
         ap.error("--i8-eval-convs needs --i8-eval: it adds the conv layers to the hardware path that --i8-eval evaluates")
+    if args.i8_eval_direct and not args.i8_eval_convs:
+        ap.error("--i8-eval-direct needs --i8-eval --i8-eval-convs: it sends eligible conv layers of that evaluation down the direct "
+                 "int8 convolution")
     if args.i8_eval_fused and not args.i8_eval:
         ap.error("--i8-eval-fused needs --i8-eval: it compares the fused Dense tail with the unfused hardware path")
     if args.i8_eval_fused and args.i8_eval_act_block != 64:
@@ -849,7 +873,7 @@ def main(argv=None):
     quant_stats = L.quant_stats(tr.model) if args.quant_stats and rank == 0 else None      # after the clock has stopped
     mx_stats = L.mx_quant_stats(tr.model) if args.mx_stats and rank == 0 else None
     mx_eval_fields = mx_eval(tr.model, *batches[0], act_format=args.mx_eval, fused=args.mx_eval_fused, convs=args.mx_eval_convs) if args.mx_eval is not None and rank == 0 else None
-    i8_eval_fields = i8_eval(tr.model, *batches[0], act_block=args.i8_eval_act_block, convs=args.i8_eval_convs, fused=args.i8_eval_fused, offsets=args.i8_eval_offsets) if args.i8_eval and rank == 0 else None
+    i8_eval_fields = i8_eval(tr.model, *batches[0], act_block=args.i8_eval_act_block, convs=args.i8_eval_convs, fused=args.i8_eval_fused, offsets=args.i8_eval_offsets, direct=args.i8_eval_direct) if args.i8_eval and rank == 0 else None
     if rank == 0:
         n_q = sum(p.numel() for l in tr.custom_layers for p in l._regularized())
         print(json.dumps({

@@ -651,8 +651,28 @@ int lq_mx_operand_im2col(const float* X, const lq_conv_geom* g, int format, int 
  * Not built on this path: weight scales that vary along K (a group size below ci * kh * kw stays on the im2col path), offsets
  * (asymmetric layers), MX elements, an epilogue that writes the next layer's pixel operand, dilation and groups.
  *
- * Not built: epilogue output blocks other than 64 (per row, 128), offsets on the A operand (asymmetric activations), HWIO-stored conv kernels, any backward, sub-byte packing of
- * 4-bit codes.  */
+ * PACKED 4-BIT B OPERAND (W4A8).  An operand of L lines by K whose codes lie in [-8, 7] stores them two to a byte, under the same
+ * fp32 scales (and, for an asymmetric parameter, offsets) in exactly the layout above:
+ *   codes   [LT][KT][64 lanes][8 bytes]       LT = ceil(L / 16), KT = ceil(K / 64)
+ *           fragment `lane` of tile (lt, kt) holds line 16 lt + (lane & 15).  With g = lane >> 4, byte 4 d + t (d = 0, 1; t = 0 .. 3)
+ *           holds code k = 64 kt + 16 g + 8 d + t in its low nibble and code k = 64 kt + 16 g + 8 d + 4 + t in its high nibble;
+ *           each nibble is the low four bits of the two's-complement code
+ *   Read as two little-endian dwords x0, x1: (x_d << 4) & 0xF0F0F0F0 is dword 2 d of the int8 fragment with every byte multiplied
+ *   by 16, and x_d & 0xF0F0F0F0 is dword 2 d + 1 of it with every byte multiplied by 16.
+ * Lines past L and k past K hold nibble 0; scales of lines past L are 1.0f.  lq_i4_operand_bytes: code_bytes is exactly half of
+ * lq_i8_operand_bytes' value and scale_bytes is equal to it.
+ * lq_i4_operand_pack / lq_i4_operand_pack_affine: the signatures, geometry, element step and refusals of lq_i8_operand_pack /
+ * lq_i8_operand_pack_affine; the nibbles are the low four bits of the codes those write, scales and offsets are theirs bit for bit.
+ * LQ_EINVAL before any launch for qmin < -8 or qmax > 7 (an unsigned 4-bit range [0, 15] does not fit: not built).
+ * lq_i4_operand_decode / lq_i4_operand_decode_affine: bit for bit lq_i8_operand_decode / _affine of the same codes stored in bytes.
+ * lq_i8_gemm_w4, lq_i8_gemm_w4_affine, lq_i8_gemm_quantize_w4, lq_i8_gemm_quantize_w4_affine: the signatures and refusals of the
+ * entry points without _w4; b_codes is a packed 4-bit operand, A an int8 operand as ever (a 4-bit A is not built).  The result is
+ * BIT FOR BIT what the entry point without _w4 gives on the same codes stored in bytes: the kernels multiply 16 q as a signed byte
+ * (|16 q| <= 128, so the period rule is unchanged) and shift each period's int32 sum right by 4, which is exact.
+ * Each of the nine is ONE launch (capturable), allocates nothing and uses no workspace, atomics or memset.
+ *
+ * Not built: epilogue output blocks other than 64 (per row, 128), offsets on the A operand (asymmetric activations), HWIO-stored conv kernels, any backward, an unsigned
+ * 4-bit range, a 4-bit A operand, a 4-bit per-tap operand of the direct convolution, 2-bit and 3-bit packing.  */
 int lq_i8_operand_bytes(int64_t L, int64_t K, int64_t block, size_t* code_bytes, size_t* scale_bytes);
 int lq_i8_operand_pack(const float* P, const float* s, int32_t qmin, int32_t qmax, int rounding, int64_t R, int64_t C, int axis,
                        int64_t gs, void* codes, void* scales, void* stream);
@@ -675,6 +695,26 @@ int lq_i8_gemm_quantize_affine(const void* a_codes, const void* a_scales, int64_
                                const void* b_offsets, int64_t b_block, const float* bias /* may be NULL */,
                                int activation /* lq_mx_activation */, int64_t out_block, void* out_codes, void* out_scales, int64_t M,
                                int64_t N, int64_t K, void* stream);
+int lq_i4_operand_bytes(int64_t L, int64_t K, int64_t block, size_t* code_bytes, size_t* scale_bytes);
+int lq_i4_operand_pack(const float* P, const float* s, int32_t qmin, int32_t qmax, int rounding, int64_t R, int64_t C, int axis,
+                       int64_t gs, void* codes, void* scales, void* stream);
+int lq_i4_operand_pack_affine(const float* P, const float* s, const float* b, int32_t qmin, int32_t qmax, int rounding, int64_t R,
+                              int64_t C, int axis, int64_t gs, void* codes, void* scales, void* offsets, void* stream);
+int lq_i4_operand_decode(const void* codes, const void* scales, int64_t L, int64_t K, int64_t block, float* out, void* stream);
+int lq_i4_operand_decode_affine(const void* codes, const void* scales, const void* offsets, int64_t L, int64_t K, int64_t block,
+                                float* out, void* stream);
+int lq_i8_gemm_w4(const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes, const void* b_scales, int64_t b_block,
+                  const float* bias /* may be NULL */, float* Y, int64_t ldy, int64_t M, int64_t N, int64_t K, void* stream);
+int lq_i8_gemm_w4_affine(const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes, const void* b_scales,
+                         const void* b_offsets, int64_t b_block, const float* bias /* may be NULL */, float* Y, int64_t ldy, int64_t M,
+                         int64_t N, int64_t K, void* stream);
+int lq_i8_gemm_quantize_w4(const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes, const void* b_scales,
+                           int64_t b_block, const float* bias /* may be NULL */, int activation /* lq_mx_activation */,
+                           int64_t out_block, void* out_codes, void* out_scales, int64_t M, int64_t N, int64_t K, void* stream);
+int lq_i8_gemm_quantize_w4_affine(const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes, const void* b_scales,
+                                  const void* b_offsets, int64_t b_block, const float* bias /* may be NULL */,
+                                  int activation /* lq_mx_activation */, int64_t out_block, void* out_codes, void* out_scales,
+                                  int64_t M, int64_t N, int64_t K, void* stream);
 int lq_i8_pixels_bytes(int64_t B, int64_t C, int64_t H, int64_t W, size_t* code_bytes, size_t* scale_bytes);
 int lq_i8_pixels_quantize(const float* X, const lq_conv_geom* g, void* codes, void* scales, void* stream);
 int lq_i8_conv_kernel_bytes(int64_t co, int64_t ci, int64_t KH, int64_t KW, size_t* code_bytes, size_t* scale_bytes);

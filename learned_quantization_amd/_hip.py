@@ -106,6 +106,13 @@ SIGNATURES = {
     "lq_min_value_project": (_c_int, [_c_p, _c_i64, _c_f, _c_p]),
     "lq_q_absmax_over_axis": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_p]),
 }
+# the packed 4-bit B operand (include/lq_hip.h): every entry point takes the signature of its int8 twin
+SIGNATURES.update({i4: SIGNATURES[i8] for i4, i8 in (
+    ("lq_i4_operand_bytes", "lq_i8_operand_bytes"), ("lq_i4_operand_pack", "lq_i8_operand_pack"),
+    ("lq_i4_operand_pack_affine", "lq_i8_operand_pack_affine"), ("lq_i4_operand_decode", "lq_i8_operand_decode"),
+    ("lq_i4_operand_decode_affine", "lq_i8_operand_decode_affine"), ("lq_i8_gemm_w4", "lq_i8_gemm"),
+    ("lq_i8_gemm_w4_affine", "lq_i8_gemm_affine"), ("lq_i8_gemm_quantize_w4", "lq_i8_gemm_quantize"),
+    ("lq_i8_gemm_quantize_w4_affine", "lq_i8_gemm_quantize_affine"))})
 
 
 

@@ -17,10 +17,12 @@
 #ifndef LQ_I8_GEMM_HPP_
 #define LQ_I8_GEMM_HPP_
 #include "lq_i8_operand.hpp"
+#include "lq_i4_operand.hpp"
 
 namespace lq {
 
 typedef int i8_v4i __attribute__((ext_vector_type(4)));
+typedef int i8_v2i __attribute__((ext_vector_type(2)));
 
 struct I8GemmParams {
     const uint8_t* a_codes;
@@ -43,6 +45,38 @@ __device__ __forceinline__ i8_v4i i8_load_frag(const uint8_t* codes, int32_t KT,
     return f;
 }
 
+// W4: B is a packed 4-bit operand (lq_i4_operand.hpp).  A lane loads 8 bytes per B fragment and step, so what waits in registers
+// for the next step is two dwords per fragment instead of four; when the step takes them, three VALU operations per dword (a
+// shift and two masks) make the four operand dwords, every byte 16 q as a signed byte.  The accumulators therefore hold 16 x the
+// true sums -- |16 q| <= 128, the bound every int8 operand has, so the period rule is unchanged -- and the flush shifts them
+// right arithmetically by 4, which is exact, before the conversion.  A is an int8 operand as ever; the ones fragment of the affine
+// row sums multiplies A alone and is not shifted.
+template <bool W4>
+using i8_b_frag = std::conditional_t<W4, i8_v2i, i8_v4i>;
+
+template <bool W4>
+__device__ __forceinline__ i8_b_frag<W4> i8_load_b(const uint8_t* codes, int32_t KT, int32_t lt, int32_t kt, int lane) {
+    if constexpr (W4) {
+        const uint2 v = *reinterpret_cast<const uint2*>(codes + (((int64_t)lt * KT + kt) * 64 + lane) * 8);
+        return i8_v2i{(int)v.x, (int)v.y};
+    } else {
+        return i8_load_frag(codes, KT, lt, kt, lane);
+    }
+}
+
+__device__ __forceinline__ i8_v4i i8_b_operand(i8_v4i f) { return f; }
+__device__ __forceinline__ i8_v4i i8_b_operand(i8_v2i x) {
+    const int hi = (int)0xF0F0F0F0u;
+    return i8_v4i{(x[0] << 4) & hi, x[0] & hi, (x[1] << 4) & hi, x[1] & hi};
+}
+
+// an accumulator of a period as the float the flush scales: the exact sum
+template <bool W4>
+__device__ __forceinline__ float i8_sum(int acc) {
+    if constexpr (W4) return (float)(acc >> 4);
+    else return (float)acc;
+}
+
 // B with an offset per (line, scale block) (lq_hip.h: lq_i8_gemm_affine): W = q s + b adds, per period, RN(c_p * ob[n][p]) with
 // c_p = RN((float)R_p * sa[m][p]) and R_p the exact row sum of A's codes over the period.
 struct I8GemmAffineParams : I8GemmParams {
@@ -56,7 +90,7 @@ __device__ __forceinline__ i8_v4i i8_ones_frag() { return i8_v4i{0x01010101, 0x0
 // AFF false: the symmetric product.  AFF true: one more instruction per A tile and K step for the row sums (6 per step instead of
 // 4), and at a period's end c once per row, then one product and one add per element, after the symmetric term.  B's offsets are
 // loaded where its scales are, from the same index.
-template <bool AFF>
+template <bool AFF, bool W4 = false>
 __global__ __launch_bounds__(kBlock) void k_i8_gemm(const std::conditional_t<AFF, I8GemmAffineParams, I8GemmParams> p) {
     const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
     const int32_t mt0 = ((int32_t)blockIdx.y * 2 + (wave & 1)) * 2;
@@ -104,11 +138,12 @@ __global__ __launch_bounds__(kBlock) void k_i8_gemm(const std::conditional_t<AFF
         sb[i] = sb_base[i][0];
     }
 
-    i8_v4i a[2], b[2], an[2], bn[2];
+    i8_v4i a[2], b[2], an[2];
+    i8_b_frag<W4> bn[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         an[i] = i8_load_frag(p.a_codes, p.KT, mt[i], 0, lane);
-        bn[i] = i8_load_frag(p.b_codes, p.KT, nt[i], 0, lane);
+        bn[i] = i8_load_b<W4>(p.b_codes, p.KT, nt[i], 0, lane);
     }
     int32_t left = p.ps;
     for (int32_t kt = 0; kt < p.KT; ++kt) {
@@ -117,9 +152,9 @@ __global__ __launch_bounds__(kBlock) void k_i8_gemm(const std::conditional_t<AFF
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             a[i] = an[i];
-            b[i] = bn[i];
+            b[i] = i8_b_operand(bn[i]);
             an[i] = i8_load_frag(p.a_codes, p.KT, mt[i], ktn, lane);
-            bn[i] = i8_load_frag(p.b_codes, p.KT, nt[i], ktn, lane);
+            bn[i] = i8_load_b<W4>(p.b_codes, p.KT, nt[i], ktn, lane);
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -138,7 +173,7 @@ __global__ __launch_bounds__(kBlock) void k_i8_gemm(const std::conditional_t<AFF
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const float t = __fmul_rn(sar[r], sb[j]);
-                        y[i][j][r] = __fadd_rn(y[i][j][r], __fmul_rn((float)acc[i][j][r], t));
+                        y[i][j][r] = __fadd_rn(y[i][j][r], __fmul_rn(i8_sum<W4>(acc[i][j][r]), t));
                     }
                     acc[i][j] = i8_v4i{0, 0, 0, 0};
                 }

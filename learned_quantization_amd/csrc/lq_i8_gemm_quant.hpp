@@ -43,7 +43,8 @@ struct I8GemmQuantAffineParams : I8GemmQuantParams {
 
 // AFF: k_i8_gemm<true>'s offset term in this kernel's tiling -- one more instruction per K step for the wave's one A tile (5 instead
 // of 4), and at a period's end c once per row, then one product and one add per element
-template <bool AFF>
+// W4: a packed 4-bit B, as in k_i8_gemm (lq_i8_gemm.hpp)
+template <bool AFF, bool W4 = false>
 __global__ __launch_bounds__(kBlock) void k_i8_gemm_quantize(const std::conditional_t<AFF, I8GemmQuantAffineParams, I8GemmQuantParams> p) {
     using Step = GroupStep<true, GroupParams>;
     const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
@@ -85,10 +86,11 @@ __global__ __launch_bounds__(kBlock) void k_i8_gemm_quantize(const std::conditio
         }
     }
 
-    i8_v4i a, an, b[4], bn[4];
+    i8_v4i a, an, b[4];
+    i8_b_frag<W4> bn[4];
     an = i8_load_frag(p.g.a_codes, p.g.KT, mt, 0, lane);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) bn[j] = i8_load_frag(p.g.b_codes, p.g.KT, nt[j], 0, lane);
+    for (int j = 0; j < 4; ++j) bn[j] = i8_load_b<W4>(p.g.b_codes, p.g.KT, nt[j], 0, lane);
     int32_t left = p.g.ps;
     for (int32_t kt = 0; kt < p.g.KT; ++kt) {
         // take the fragments requested a step ago, request the next step's (the last step asks for itself again), multiply
@@ -97,8 +99,8 @@ __global__ __launch_bounds__(kBlock) void k_i8_gemm_quantize(const std::conditio
         an = i8_load_frag(p.g.a_codes, p.g.KT, mt, ktn, lane);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            b[j] = bn[j];
-            bn[j] = i8_load_frag(p.g.b_codes, p.g.KT, nt[j], ktn, lane);
+            b[j] = i8_b_operand(bn[j]);
+            bn[j] = i8_load_b<W4>(p.g.b_codes, p.g.KT, nt[j], ktn, lane);
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b[j], acc[j], 0, 0, 0);
@@ -110,7 +112,7 @@ __global__ __launch_bounds__(kBlock) void k_i8_gemm_quantize(const std::conditio
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const float t = __fmul_rn(sar[r], sb[j]);
-                    y[j][r] = __fadd_rn(y[j][r], __fmul_rn((float)acc[j][r], t));
+                    y[j][r] = __fadd_rn(y[j][r], __fmul_rn(i8_sum<W4>(acc[j][r]), t));
                 }
                 acc[j] = i8_v4i{0, 0, 0, 0};
             }

@@ -66,10 +66,21 @@ struct I8PackAffineParams : I8PackParams {
     float* offsets;
 };
 
+// where the 16 codes of a run (k0 .. k0 + 15 of one line) go: a byte each, 16 consecutive bytes
+struct I8RunStore {
+    static constexpr int kWords = 4;
+    static __device__ __forceinline__ int word(int j) { return j >> 2; }
+    static __device__ __forceinline__ uint32_t place(uint32_t byte, int j) { return byte << (8 * (j & 3)); }
+    static __device__ __forceinline__ void store(uint8_t* codes, int32_t KT, int32_t ln, int32_t k0, const uint32_t* w) {
+        *reinterpret_cast<uint4*>(codes + i8_code_offset(KT, ln, k0)) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+};
+
+// One thread, one (line, 16 k).  Store: I8RunStore, or I4RunStore for the packed 4-bit operand (lq_i4_operand.hpp).
 // LINE_FAST: neighbouring threads hold neighbouring lines (the parameter's contiguous axis under axis 0), else neighbouring k runs.
 // AFF: the element step of lq_fq_forward_group_affine, u = P - b before the quotient, and the offset of a scale block carried
 // across like its scale; lines past L get offset +0.
-template <bool RNE, bool LINE_FAST, bool AFF = false>
+template <bool RNE, bool LINE_FAST, bool AFF = false, class Store = I8RunStore>
 __global__ __launch_bounds__(kBlock) void k_i8_pack(const std::conditional_t<AFF, I8PackAffineParams, I8PackParams> op) {
     using Step = GroupStep<RNE, GroupParams>;
     const int64_t lines = (int64_t)op.LT * kI8TileLines, runs = (int64_t)op.KT * 4;
@@ -79,7 +90,7 @@ __global__ __launch_bounds__(kBlock) void k_i8_pack(const std::conditional_t<AFF
     const int32_t k0 = (int32_t)(LINE_FAST ? tid / lines : tid % runs) * 16;
     const int32_t blk = op.block ? k0 / op.block : 0;
     const bool live = ln < op.L && k0 < op.K;
-    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    uint32_t w[Store::kWords] = {};
     float s = 1.0f;
     if (live) s = op.g.s[(int64_t)ln * op.s_line_stride + (int64_t)blk * op.s_blk_stride];
     [[maybe_unused]] float b = 0.f;
@@ -96,11 +107,11 @@ __global__ __launch_bounds__(kBlock) void k_i8_pack(const std::conditional_t<AFF
                 float u = src[(int64_t)j * op.k_stride];
                 if constexpr (AFF) u = u - b;
                 const float q = Step::quant(op.g, c, div_by_uniform(u, c));
-                w[j >> 2] |= i8_view_byte(Step::view(op.g, q)) << (8 * (j & 3));
+                w[Store::word(j)] |= Store::place(i8_view_byte(Step::view(op.g, q)), j);
             }
         }
     }
-    *reinterpret_cast<uint4*>(op.codes + i8_code_offset(op.KT, ln, k0)) = make_uint4(w[0], w[1], w[2], w[3]);
+    Store::store(op.codes, op.KT, ln, k0, w);
     // the first run of a scale block carries its scale across, bit for bit
     if (k0 < op.K && (op.block ? k0 % op.block == 0 : k0 == 0)) {
         op.scales[(int64_t)blk * lines + ln] = s;

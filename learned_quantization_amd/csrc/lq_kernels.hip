@@ -17,6 +17,7 @@
 //   lq_mx_operand.hpp   packed MX operands in the block-scaled matrix instruction's fragment order: pack, dynamic quantize, decode
 //   lq_mx_gemm.hpp      the GEMM of two packed operands on v_mfma_scale_f32_16x16x128_f8f6f4
 //   lq_i8_operand.hpp   packed int8 operands with fp32 scales per line and scale block: pack, dynamic quantize, decode
+//   lq_i4_operand.hpp   4-bit codes two to a byte as the B operand of the int8 GEMM: pack, decode
 //   lq_i8_gemm.hpp      the GEMM of two packed int8 operands on v_mfma_i32_16x16x64_i8
 //   lq_i8_gemm_quant.hpp  the same product with an operand-out epilogue: it writes the next layer's int8 operand
 //   lq_im2col.hpp       a convolution's im2col matrix without the matrix: geometry, a line's window, the predicated gather
@@ -72,6 +73,7 @@
 #include "lq_mx_gemm.hpp"
 #include "lq_mx_conv.hpp"
 #include "lq_i8_operand.hpp"
+#include "lq_i4_operand.hpp"
 #include "lq_i8_gemm.hpp"
 #include "lq_i8_conv.hpp"
 #include "lq_i8_gemm_quant.hpp"
@@ -2214,6 +2216,24 @@ int lq_i8_operand_bytes(int64_t L, int64_t K, int64_t block, size_t* code_bytes,
     return LQ_OK;
 }
 
+// a 4-bit operand (lq_i4_operand.hpp): the tiles, scale blocks and refusals of the int8 operand, half the code bytes
+static int i4_operand_dims(const char* fn, int64_t L, int64_t K, int64_t block, I8OperandDims& d) {
+    const int rc = i8_operand_dims(fn, L, K, block, d);
+    if (rc == LQ_OK) d.code_bytes /= 2;
+    return rc;
+}
+
+int lq_i4_operand_bytes(int64_t L, int64_t K, int64_t block, size_t* code_bytes, size_t* scale_bytes) {
+    const char* fn = __func__;
+    if (!code_bytes || !scale_bytes) return fail(LQ_EINVAL, "%s: code_bytes or scale_bytes is NULL", fn);
+    I8OperandDims d;
+    int rc = i4_operand_dims(fn, L, K, block, d);
+    if (rc) return rc;
+    *code_bytes = d.code_bytes;
+    *scale_bytes = d.scale_bytes;
+    return LQ_OK;
+}
+
 // an operand's offsets (the affine entry points): a buffer in the layout of its scales, on the same grid
 static int check_operand_offsets(const char* fn, const void* offsets) {
     if (!offsets) return fail(LQ_EINVAL, "%s: argument 'offsets' is NULL", fn);
@@ -2221,8 +2241,9 @@ static int check_operand_offsets(const char* fn, const void* offsets) {
     return LQ_OK;
 }
 
-// lq_i8_operand_pack (b == NULL, offsets == NULL, affine false) and lq_i8_operand_pack_affine: one geometry, one set of refusals
-static int i8_operand_pack(const char* fn, bool affine, const float* P, const float* s, const float* b, int32_t qmin, int32_t qmax,
+// lq_i8_operand_pack (b == NULL, offsets == NULL, affine false) and lq_i8_operand_pack_affine: one geometry, one set of refusals;
+// w4: lq_i4_operand_pack and lq_i4_operand_pack_affine, the same geometry and refusals with the range of a nibble
+static int i8_operand_pack(const char* fn, bool affine, bool w4, const float* P, const float* s, const float* b, int32_t qmin, int32_t qmax,
                            int rounding, int64_t R, int64_t C, int axis, int64_t gs, void* codes, void* scales, void* offsets,
                            void* stream) {
     int rc = check_group(fn, R, C, axis, gs);
@@ -2237,6 +2258,9 @@ static int i8_operand_pack(const char* fn, bool affine, const float* P, const fl
     if (qmin < -128 || qmax > 127)
         return fail(LQ_EINVAL, "%s: range [%d, %d] is not inside [-128, 127], the operands of the int8 matrix instruction", fn, (int)qmin,
                     (int)qmax);
+    if (w4 && (qmin < kI4Min || qmax > kI4Max))
+        return fail(LQ_EINVAL, "%s: range [%d, %d] is not inside [%d, %d], the signed codes a nibble holds", fn, (int)qmin, (int)qmax,
+                    kI4Min, kI4Max);
     const int64_t L = axis == 0 ? C : R, K = axis == 0 ? R : C;
     if (gs < K && gs % kI8TileK != 0)
         return fail(LQ_EINVAL, "%s: group size %lld is neither the whole line (%lld) nor a multiple of %d: a scale must not change "
@@ -2263,11 +2287,31 @@ static int i8_operand_pack(const char* fn, bool affine, const float* P, const fl
     const dim3 grid((unsigned)((threads + kBlock - 1) / kBlock)), blk(kBlock);
     hipStream_t st = (hipStream_t)stream;
     const bool rne = rounding == LQ_ROUND_NEAREST_EVEN;
+    I8PackAffineParams ap{};
+    static_cast<I8PackParams&>(ap) = op;
+    ap.b = b;
+    ap.offsets = (float*)offsets;
+    if (w4) {
+        if (affine) {
+            if (axis == 0) {
+                if (rne) hipLaunchKernelGGL((k_i8_pack<true, true, true, I4RunStore>), grid, blk, 0, st, ap);
+                else hipLaunchKernelGGL((k_i8_pack<false, true, true, I4RunStore>), grid, blk, 0, st, ap);
+            } else {
+                if (rne) hipLaunchKernelGGL((k_i8_pack<true, false, true, I4RunStore>), grid, blk, 0, st, ap);
+                else hipLaunchKernelGGL((k_i8_pack<false, false, true, I4RunStore>), grid, blk, 0, st, ap);
+            }
+            return check_hip("4-bit operand pack with offsets");
+        }
+        if (axis == 0) {
+            if (rne) hipLaunchKernelGGL((k_i8_pack<true, true, false, I4RunStore>), grid, blk, 0, st, op);
+            else hipLaunchKernelGGL((k_i8_pack<false, true, false, I4RunStore>), grid, blk, 0, st, op);
+        } else {
+            if (rne) hipLaunchKernelGGL((k_i8_pack<true, false, false, I4RunStore>), grid, blk, 0, st, op);
+            else hipLaunchKernelGGL((k_i8_pack<false, false, false, I4RunStore>), grid, blk, 0, st, op);
+        }
+        return check_hip("4-bit operand pack");
+    }
     if (affine) {
-        I8PackAffineParams ap{};
-        static_cast<I8PackParams&>(ap) = op;
-        ap.b = b;
-        ap.offsets = (float*)offsets;
         if (axis == 0) {
             if (rne) hipLaunchKernelGGL((k_i8_pack<true, true, true>), grid, blk, 0, st, ap);
             else hipLaunchKernelGGL((k_i8_pack<false, true, true>), grid, blk, 0, st, ap);
@@ -2289,12 +2333,22 @@ static int i8_operand_pack(const char* fn, bool affine, const float* P, const fl
 
 int lq_i8_operand_pack(const float* P, const float* s, int32_t qmin, int32_t qmax, int rounding, int64_t R, int64_t C, int axis,
                        int64_t gs, void* codes, void* scales, void* stream) {
-    return i8_operand_pack(__func__, false, P, s, nullptr, qmin, qmax, rounding, R, C, axis, gs, codes, scales, nullptr, stream);
+    return i8_operand_pack(__func__, false, false, P, s, nullptr, qmin, qmax, rounding, R, C, axis, gs, codes, scales, nullptr, stream);
 }
 
 int lq_i8_operand_pack_affine(const float* P, const float* s, const float* b, int32_t qmin, int32_t qmax, int rounding, int64_t R,
                               int64_t C, int axis, int64_t gs, void* codes, void* scales, void* offsets, void* stream) {
-    return i8_operand_pack(__func__, true, P, s, b, qmin, qmax, rounding, R, C, axis, gs, codes, scales, offsets, stream);
+    return i8_operand_pack(__func__, true, false, P, s, b, qmin, qmax, rounding, R, C, axis, gs, codes, scales, offsets, stream);
+}
+
+int lq_i4_operand_pack(const float* P, const float* s, int32_t qmin, int32_t qmax, int rounding, int64_t R, int64_t C, int axis,
+                       int64_t gs, void* codes, void* scales, void* stream) {
+    return i8_operand_pack(__func__, false, true, P, s, nullptr, qmin, qmax, rounding, R, C, axis, gs, codes, scales, nullptr, stream);
+}
+
+int lq_i4_operand_pack_affine(const float* P, const float* s, const float* b, int32_t qmin, int32_t qmax, int rounding, int64_t R,
+                              int64_t C, int axis, int64_t gs, void* codes, void* scales, void* offsets, void* stream) {
+    return i8_operand_pack(__func__, true, true, P, s, b, qmin, qmax, rounding, R, C, axis, gs, codes, scales, offsets, stream);
 }
 
 int lq_i8_operand_quantize(const float* X, int64_t M, int64_t K, int64_t block, void* codes, void* scales, void* stream) {
@@ -2558,7 +2612,7 @@ int lq_i8_conv2d(const void* pix_codes, const void* pix_scales, const void* k_co
     return check_hip("direct int8 convolution");
 }
 
-static int i8_operand_decode(const char* fn, bool affine, const void* codes, const void* scales, const void* offsets, int64_t L,
+static int i8_operand_decode(const char* fn, bool affine, bool w4, const void* codes, const void* scales, const void* offsets, int64_t L,
                              int64_t K, int64_t block, float* out, void* stream) {
     I8OperandDims d;
     int rc = i8_operand_dims(fn, L, K, block, d);
@@ -2581,24 +2635,36 @@ static int i8_operand_decode(const char* fn, bool affine, const void* codes, con
         I8DecodeAffineParams ap{};
         ap.d = dp;
         ap.offsets = (const float*)offsets;
-        hipLaunchKernelGGL(k_i8_decode_affine, grid, dim3(kBlock), 0, (hipStream_t)stream, ap);
-        return check_hip("int8 operand decode with offsets");
+        if (w4) hipLaunchKernelGGL(k_i4_decode_affine, grid, dim3(kBlock), 0, (hipStream_t)stream, ap);
+        else hipLaunchKernelGGL(k_i8_decode_affine, grid, dim3(kBlock), 0, (hipStream_t)stream, ap);
+        return check_hip("operand decode with offsets");
     }
-    hipLaunchKernelGGL(k_i8_decode, grid, dim3(kBlock), 0, (hipStream_t)stream, dp);
-    return check_hip("int8 operand decode");
+    if (w4) hipLaunchKernelGGL(k_i4_decode, grid, dim3(kBlock), 0, (hipStream_t)stream, dp);
+    else hipLaunchKernelGGL(k_i8_decode, grid, dim3(kBlock), 0, (hipStream_t)stream, dp);
+    return check_hip("operand decode");
 }
 
 int lq_i8_operand_decode(const void* codes, const void* scales, int64_t L, int64_t K, int64_t block, float* out, void* stream) {
-    return i8_operand_decode(__func__, false, codes, scales, nullptr, L, K, block, out, stream);
+    return i8_operand_decode(__func__, false, false, codes, scales, nullptr, L, K, block, out, stream);
 }
 
 int lq_i8_operand_decode_affine(const void* codes, const void* scales, const void* offsets, int64_t L, int64_t K, int64_t block,
                                 float* out, void* stream) {
-    return i8_operand_decode(__func__, true, codes, scales, offsets, L, K, block, out, stream);
+    return i8_operand_decode(__func__, true, false, codes, scales, offsets, L, K, block, out, stream);
 }
 
-// lq_i8_gemm (b_offsets == NULL, affine false) and lq_i8_gemm_affine: one set of refusals, one period rule, one grid
-static int i8_gemm(const char* fn, bool affine, const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes,
+int lq_i4_operand_decode(const void* codes, const void* scales, int64_t L, int64_t K, int64_t block, float* out, void* stream) {
+    return i8_operand_decode(__func__, false, true, codes, scales, nullptr, L, K, block, out, stream);
+}
+
+int lq_i4_operand_decode_affine(const void* codes, const void* scales, const void* offsets, int64_t L, int64_t K, int64_t block,
+                                float* out, void* stream) {
+    return i8_operand_decode(__func__, true, true, codes, scales, offsets, L, K, block, out, stream);
+}
+
+// lq_i8_gemm (b_offsets == NULL, affine false) and lq_i8_gemm_affine: one set of refusals, one period rule, one grid;
+// w4: lq_i8_gemm_w4 and lq_i8_gemm_w4_affine, B a packed 4-bit operand (the same tiles and scales: nothing else differs)
+static int i8_gemm(const char* fn, bool affine, bool w4, const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes,
                    const void* b_scales, const void* b_offsets, int64_t b_block, const float* bias, float* Y, int64_t ldy, int64_t M,
                    int64_t N, int64_t K, void* stream) {
     I8OperandDims da, db;
@@ -2639,25 +2705,38 @@ static int i8_gemm(const char* fn, bool affine, const void* a_codes, const void*
         I8GemmAffineParams ap{};
         static_cast<I8GemmParams&>(ap) = p;
         ap.b_offsets = (const float*)b_offsets;
-        hipLaunchKernelGGL(k_i8_gemm<true>, grid, dim3(kBlock), 0, (hipStream_t)stream, ap);
+        if (w4) hipLaunchKernelGGL((k_i8_gemm<true, true>), grid, dim3(kBlock), 0, (hipStream_t)stream, ap);
+        else hipLaunchKernelGGL(k_i8_gemm<true>, grid, dim3(kBlock), 0, (hipStream_t)stream, ap);
         return check_hip("int8 GEMM with offsets");
     }
-    hipLaunchKernelGGL(k_i8_gemm<false>, grid, dim3(kBlock), 0, (hipStream_t)stream, p);
+    if (w4) hipLaunchKernelGGL((k_i8_gemm<false, true>), grid, dim3(kBlock), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(k_i8_gemm<false>, grid, dim3(kBlock), 0, (hipStream_t)stream, p);
     return check_hip("int8 GEMM");
 }
 
 int lq_i8_gemm(const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes, const void* b_scales, int64_t b_block,
                const float* bias, float* Y, int64_t ldy, int64_t M, int64_t N, int64_t K, void* stream) {
-    return i8_gemm(__func__, false, a_codes, a_scales, a_block, b_codes, b_scales, nullptr, b_block, bias, Y, ldy, M, N, K, stream);
+    return i8_gemm(__func__, false, false, a_codes, a_scales, a_block, b_codes, b_scales, nullptr, b_block, bias, Y, ldy, M, N, K, stream);
 }
 
 int lq_i8_gemm_affine(const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes, const void* b_scales,
                       const void* b_offsets, int64_t b_block, const float* bias, float* Y, int64_t ldy, int64_t M, int64_t N,
                       int64_t K, void* stream) {
-    return i8_gemm(__func__, true, a_codes, a_scales, a_block, b_codes, b_scales, b_offsets, b_block, bias, Y, ldy, M, N, K, stream);
+    return i8_gemm(__func__, true, false, a_codes, a_scales, a_block, b_codes, b_scales, b_offsets, b_block, bias, Y, ldy, M, N, K, stream);
 }
 
-static int i8_gemm_quantize(const char* fn, bool affine, const void* a_codes, const void* a_scales, int64_t a_block,
+int lq_i8_gemm_w4(const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes, const void* b_scales, int64_t b_block,
+                  const float* bias, float* Y, int64_t ldy, int64_t M, int64_t N, int64_t K, void* stream) {
+    return i8_gemm(__func__, false, true, a_codes, a_scales, a_block, b_codes, b_scales, nullptr, b_block, bias, Y, ldy, M, N, K, stream);
+}
+
+int lq_i8_gemm_w4_affine(const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes, const void* b_scales,
+                         const void* b_offsets, int64_t b_block, const float* bias, float* Y, int64_t ldy, int64_t M, int64_t N,
+                         int64_t K, void* stream) {
+    return i8_gemm(__func__, true, true, a_codes, a_scales, a_block, b_codes, b_scales, b_offsets, b_block, bias, Y, ldy, M, N, K, stream);
+}
+
+static int i8_gemm_quantize(const char* fn, bool affine, bool w4, const void* a_codes, const void* a_scales, int64_t a_block,
                             const void* b_codes, const void* b_scales, const void* b_offsets, int64_t b_block, const float* bias,
                             int activation, int64_t out_block, void* out_codes, void* out_scales, int64_t M, int64_t N, int64_t K,
                             void* stream) {
@@ -2712,24 +2791,40 @@ static int i8_gemm_quantize(const char* fn, bool affine, const void* a_codes, co
         I8GemmQuantAffineParams ap{};
         static_cast<I8GemmQuantParams&>(ap) = p;
         ap.b_offsets = (const float*)b_offsets;
-        hipLaunchKernelGGL(k_i8_gemm_quantize<true>, grid, dim3(kBlock), 0, (hipStream_t)stream, ap);
+        if (w4) hipLaunchKernelGGL((k_i8_gemm_quantize<true, true>), grid, dim3(kBlock), 0, (hipStream_t)stream, ap);
+        else hipLaunchKernelGGL(k_i8_gemm_quantize<true>, grid, dim3(kBlock), 0, (hipStream_t)stream, ap);
         return check_hip("int8 GEMM with offsets and operand-out epilogue");
     }
-    hipLaunchKernelGGL(k_i8_gemm_quantize<false>, grid, dim3(kBlock), 0, (hipStream_t)stream, p);
+    if (w4) hipLaunchKernelGGL((k_i8_gemm_quantize<false, true>), grid, dim3(kBlock), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(k_i8_gemm_quantize<false>, grid, dim3(kBlock), 0, (hipStream_t)stream, p);
     return check_hip("int8 GEMM with operand-out epilogue");
 }
 
 int lq_i8_gemm_quantize(const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes, const void* b_scales,
                         int64_t b_block, const float* bias, int activation, int64_t out_block, void* out_codes, void* out_scales,
                         int64_t M, int64_t N, int64_t K, void* stream) {
-    return i8_gemm_quantize(__func__, false, a_codes, a_scales, a_block, b_codes, b_scales, nullptr, b_block, bias, activation,
+    return i8_gemm_quantize(__func__, false, false, a_codes, a_scales, a_block, b_codes, b_scales, nullptr, b_block, bias, activation,
                             out_block, out_codes, out_scales, M, N, K, stream);
 }
 
 int lq_i8_gemm_quantize_affine(const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes, const void* b_scales,
                                const void* b_offsets, int64_t b_block, const float* bias, int activation, int64_t out_block,
                                void* out_codes, void* out_scales, int64_t M, int64_t N, int64_t K, void* stream) {
-    return i8_gemm_quantize(__func__, true, a_codes, a_scales, a_block, b_codes, b_scales, b_offsets, b_block, bias, activation,
+    return i8_gemm_quantize(__func__, true, false, a_codes, a_scales, a_block, b_codes, b_scales, b_offsets, b_block, bias, activation,
+                            out_block, out_codes, out_scales, M, N, K, stream);
+}
+
+int lq_i8_gemm_quantize_w4(const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes, const void* b_scales,
+                           int64_t b_block, const float* bias, int activation, int64_t out_block, void* out_codes, void* out_scales,
+                           int64_t M, int64_t N, int64_t K, void* stream) {
+    return i8_gemm_quantize(__func__, false, true, a_codes, a_scales, a_block, b_codes, b_scales, nullptr, b_block, bias, activation,
+                            out_block, out_codes, out_scales, M, N, K, stream);
+}
+
+int lq_i8_gemm_quantize_w4_affine(const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes, const void* b_scales,
+                                  const void* b_offsets, int64_t b_block, const float* bias, int activation, int64_t out_block,
+                                  void* out_codes, void* out_scales, int64_t M, int64_t N, int64_t K, void* stream) {
+    return i8_gemm_quantize(__func__, true, true, a_codes, a_scales, a_block, b_codes, b_scales, b_offsets, b_block, bias, activation,
                             out_block, out_codes, out_scales, M, N, K, stream);
 }
 

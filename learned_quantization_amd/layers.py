@@ -689,23 +689,27 @@ class CustomDenseLayer(_HostLayer):
 
     forward = call
 
-    def _check_i8(self, offsets=False):
+    def _check_i8(self, offsets=False, int4=False):
         """(qmin, qmax) of a layer that can run on the int8 matrix instruction, or ValueError naming the reason.  ``offsets=True``
-        lets an asymmetric layer pass (ops.check_i8_operand_layer)."""
-        q_range = ops.check_i8_operand_layer(self.q_range, self.nested_q_w_layer.orientation, self.group_size, self.asymmetric,
-                                             self.element_format, self.W.shape[0] if self.built else None, offsets=offsets)
+        lets an asymmetric layer pass (ops.check_i8_operand_layer); ``int4=True`` asks for a range that fits the packed 4-bit
+        operand as well (ops.check_i4_operand_layer)."""
+        check = ops.check_i4_operand_layer if int4 else ops.check_i8_operand_layer
+        q_range = check(self.q_range, self.nested_q_w_layer.orientation, self.group_size, self.asymmetric,
+                        self.element_format, self.W.shape[0] if self.built else None, offsets=offsets)
         if not self.built:
             raise ValueError(f"{self.name}: the layer is not built yet (no kernel to pack)")
         return q_range
 
-    def i8_operand(self, offsets=False) -> "ops.I8Operand":
+    def i8_operand(self, offsets=False, int4=False) -> "ops.I8Operand":
         """The kernel under its current scales as an operand of the int8 matrix instruction (ops.i8_operand_pack): ``units`` lines
         over K = in.  A "groupwise" layer passes its scale as it is; a "scalar" or "columnwise" layer its scale broadcast to
         ``(1, out)``, one group per output unit.  ValueError naming the reason for a layer without a range, with a range outside
         [-128, 127], with an offset, with "rowwise" scales, with an element format, or not built.
         ``offsets=True``: an asymmetric layer is packed with its ``(nb, out)`` scale and offset into an ops.I8AffineOperand, whose
-        product adds the offset's row-sum term; a symmetric layer takes the path it always took."""
-        qmin, qmax = self._check_i8(offsets)
+        product adds the offset's row-sum term; a symmetric layer takes the path it always took.
+        ``int4=True``: the same codes two to a byte, an ops.I4Operand (ops.i4_operand_pack), for a layer whose range lies inside
+        [-8, 7]; its products are bit for bit those of the byte operand."""
+        qmin, qmax = self._check_i8(offsets, int4)
         fan_in, units = self.W.shape
         scale = self.nested_q_w_layer.scale.data
         if self.nested_q_w_layer.orientation == "groupwise":
@@ -713,16 +717,18 @@ class CustomDenseLayer(_HostLayer):
         else:
             scale, gs = scale.reshape(1, -1).expand(1, units).contiguous(), fan_in
         offset = self.nested_q_w_layer.offset.data if self.asymmetric else None
-        return ops.i8_operand_pack(self.W.detach(), scale, qmin, qmax, gs, self.rounding, offset)
+        pack = ops.i4_operand_pack if int4 else ops.i8_operand_pack
+        return pack(self.W.detach(), scale, qmin, qmax, gs, self.rounding, offset)
 
-    def call_i8(self, inputs, act_block=0, out_block=None, activation=None, offsets=False):
+    def call_i8(self, inputs, act_block=0, out_block=None, activation=None, offsets=False, int4=False):
         """The layer on the int8 matrix instruction, under ``no_grad``: the inputs quantised per row and ``act_block`` consecutive
         inputs (0: per row) to symmetric 8-bit integers (ops.i8_operand_quantize), multiplied with ``i8_operand()`` by ops.i8_gemm,
         plus the fake-quantised bias.  Inference only: there is no backward through this path.
         ``inputs`` may be an ops.I8Operand (``lines`` rows over ``K`` = in), which is multiplied as it is; ``act_block`` is then not
         read.  With ``out_block`` (64) the result is not the fp32 matrix but the NEXT layer's operand, ``activation`` (None or
         "relu") applied and quantised per row and block of 64 by the product's own epilogue (ops.i8_gemm_quantize): one launch, no
-        fp32 activation in memory.  ``offsets=True`` lets an asymmetric layer run (``i8_operand(offsets=True)``)."""
+        fp32 activation in memory.  ``offsets=True`` lets an asymmetric layer run (``i8_operand(offsets=True)``); ``int4=True``
+        multiplies with the packed 4-bit operand (``i8_operand(int4=True)``), the same bits from half the weight bytes."""
         given = isinstance(inputs, ops.I8Operand)
         if not given:
             ops.check_i8_block(act_block)
@@ -736,8 +742,8 @@ class CustomDenseLayer(_HostLayer):
             ops.check_i8_out_block(out_block)
         ops.check_activation(activation)
         with torch.no_grad():
-            return self._matrix_product(inputs, self.i8_operand(offsets), self.nested_q_b_layer(self.b), _I8, (act_block,), out_block,
-                                        activation)
+            return self._matrix_product(inputs, self.i8_operand(offsets, int4), self.nested_q_b_layer(self.b), _I8, (act_block,),
+                                        out_block, activation)
 
     def mx_operand(self) -> "ops.MxOperand":
         """The kernel under its current scales as an operand of the block-scaled matrix instruction (ops.mx_operand_pack): ``units``
@@ -1017,17 +1023,24 @@ class _ConvBase(_HostLayer):
         ops.check_mx_scale_init(act_scale)
         return self._call_matrix(inputs, _MX, (act_format, act_scale), max_lines)
 
-    def _check_i8(self, offsets=False):
+    def _check_i8(self, offsets=False, int4=False):
         """(qmin, qmax) of a conv layer that can run on the int8 matrix instruction, or ValueError naming the reason.
-        ``offsets=True`` lets an asymmetric layer pass (ops.check_i8_conv_operand_layer)."""
+        ``offsets=True`` lets an asymmetric layer pass (ops.check_i8_conv_operand_layer); ``int4=True`` asks for a range that fits
+        the packed 4-bit operand as well (ops.check_i4_operand_layer)."""
         fan_in = self.kernel.shape[0] * self.kernel.shape[1] * self.kernel.shape[2] if self.built else None
-        q_range = ops.check_i8_conv_operand_layer(self.q_range, self.nested_q_k_layer.orientation, self.group_size, self.asymmetric,
-                                                  self.element_format, fan_in, self.kernel_storage, offsets=offsets)
+        if int4:
+            q_range = ops.check_i4_operand_layer(self.q_range, self.nested_q_k_layer.orientation, self.group_size, self.asymmetric,
+                                                 self.element_format, fan_in, offsets=offsets, conv=True,
+                                                 kernel_storage=self.kernel_storage)
+        else:
+            q_range = ops.check_i8_conv_operand_layer(self.q_range, self.nested_q_k_layer.orientation, self.group_size,
+                                                      self.asymmetric, self.element_format, fan_in, self.kernel_storage,
+                                                      offsets=offsets)
         if not self.built:
             raise ValueError(f"{self.name}: the layer is not built yet (no kernel to pack)")
         return q_range
 
-    def i8_operand(self, offsets=False) -> "ops.I8Operand":
+    def i8_operand(self, offsets=False, int4=False) -> "ops.I8Operand":
         """The kernel under its current scales as an operand of the int8 matrix instruction (ops.i8_operand_pack, groups along the
         contiguous axis): ``filters`` lines over K = ci kh kw, the reduction order of ops.i8_operand_im2col.  A "groupwise" layer
         passes its scale as it is; a "scalar" layer its scale broadcast to ``(filters, 1)``, one group per output channel.
@@ -1035,8 +1048,9 @@ class _ConvBase(_HostLayer):
         outside [-128, 127], with an offset, with an element format, or not built.
         ``offsets=True``: an asymmetric layer is packed with its ``(co, nb)`` scale and offset into an ops.I8AffineOperand, whose
         product adds the offset's row-sum term (padded taps hold code 0 and add no offset); a symmetric layer takes the path it
-        always took."""
-        qmin, qmax = self._check_i8(offsets)
+        always took.  ``int4=True``: the same ``(co, ci kh kw)`` codes two to a byte, an ops.I4Operand of the im2col path, for a
+        layer whose range lies inside [-8, 7]."""
+        qmin, qmax = self._check_i8(offsets, int4)
         K = self.kernel.numel() // self.filters
         scale = self.nested_q_k_layer.scale.data
         if self.nested_q_k_layer.orientation == "groupwise":
@@ -1044,9 +1058,10 @@ class _ConvBase(_HostLayer):
         else:
             scale, gs = scale.reshape(1, 1).expand(self.filters, 1).contiguous(), K
         offset = self.nested_q_k_layer.offset.data if self.asymmetric else None
-        return ops.i8_operand_pack(self.kernel.detach(), scale, qmin, qmax, gs, self.rounding, offset)
+        pack = ops.i4_operand_pack if int4 else ops.i8_operand_pack
+        return pack(self.kernel.detach(), scale, qmin, qmax, gs, self.rounding, offset)
 
-    def call_i8(self, inputs, act_block=0, max_lines=None, offsets=False):
+    def call_i8(self, inputs, act_block=0, max_lines=None, offsets=False, int4=False):
         """The layer on the int8 matrix instruction, under ``no_grad``: the im2col matrix of the inputs quantised per line and
         ``act_block`` consecutive k of (ci, kh, kw) (0: per line) to symmetric 8-bit integers by ops.i8_operand_im2col -- TensorFlow
         'SAME' padding as ``call`` pads, or 'VALID' -- multiplied with ``i8_operand()`` by ops.i8_gemm, plus the fake-quantised bias
@@ -1054,10 +1069,11 @@ class _ConvBase(_HostLayer):
         (M, co) matrix: ``(B, co, OH, OW)`` with channels-last strides for ``data_format="NCHW"``, ``(B, OH, OW, co)`` for "NHWC".  A
         batch whose im2col matrix has 2^31 elements or more, more than 65535 * 64 lines or more than ``max_lines`` lines is cut into
         runs of whole images that write their rows of the one result; the result does not depend on the cut.  ``offsets=True``
-        lets an asymmetric layer run (``i8_operand(offsets=True)``)."""
+        lets an asymmetric layer run (``i8_operand(offsets=True)``); ``int4=True`` multiplies with the packed 4-bit operand
+        (``i8_operand(int4=True)``), the same bits from half the weight bytes."""
         _check_max_lines(max_lines)
         ops.check_i8_block(act_block)
-        return self._call_matrix(inputs, _I8, (act_block,), max_lines, offsets=offsets)
+        return self._call_matrix(inputs, _I8, (act_block,), max_lines, offsets=offsets, int4=int4)
 
     def _check_i8_direct(self):
         """(qmin, qmax) of a conv layer that can run as a direct int8 convolution, or ValueError naming the reason
@@ -1155,6 +1171,10 @@ class _matrix_hardware:
     _family = _dense_eligible = _conv_eligible = None
     _opt_in = {}              # keywords of the eligibility tests and of the layers' operand method (i8_hardware: offsets)
 
+    def _operand_kwargs(self, layer):
+        """The keywords of ``layer``'s operand method: the opt-ins, and what a subclass decides per layer."""
+        return self._opt_in
+
     def __enter__(self):
         family, custom, opt_in = self._family, custom_layers_of(self.model), self._opt_in
         switching = [m for m in custom if self._dense_eligible(m, **opt_in)]
@@ -1163,7 +1183,7 @@ class _matrix_hardware:
         with torch.no_grad():
             for m in switching:
                 if not self.emulate:
-                    weight = getattr(m, family.operand)(**opt_in)
+                    weight = getattr(m, family.operand)(**self._operand_kwargs(m))
                 elif isinstance(m, _ConvBase):      # the fake-quantised kernel as the (K, co) matrix the decoded operand multiplies
                     weight = m.nested_q_k_layer(m.kernel).detach().permute(3, 2, 0, 1).reshape(m.filters, -1).t()
                 else:
@@ -1223,11 +1243,11 @@ class mx_hardware(_matrix_hardware):
         self.layers, self.fused_layers, self._fused_modules = [], [], []
 
 
-def _passes_check_i8(layer: nn.Module, cls, offsets=False) -> bool:
+def _passes_check_i8(layer: nn.Module, cls, offsets=False, int4=False) -> bool:
     if not isinstance(layer, cls):
         return False
     try:
-        layer._check_i8(offsets)
+        layer._check_i8(offsets, int4)
     except ValueError:
         return False
     return True
@@ -1246,6 +1266,13 @@ def i8_conv_eligible(layer: nn.Module, offsets=False) -> bool:
     element format and the kernel stored "oihw" (the groups then run along the im2col operand's K).  ``offsets=True``: an
     asymmetric layer is eligible too."""
     return _passes_check_i8(layer, _ConvBase, offsets)
+
+
+def i8_int4_eligible(layer: nn.Module, offsets=False) -> bool:
+    """Whether ``layer`` can take the packed 4-bit operand (``i8_operand(int4=True)``): a Dense layer that passes
+    ``i8_hardware_eligible`` or a conv layer that passes ``i8_conv_eligible``, with a range inside [-8, 7] (``bits`` of at most 4,
+    signed)."""
+    return _passes_check_i8(layer, (CustomDenseLayer, _ConvBase), offsets, True)
 
 
 def i8_direct_eligible(layer: nn.Module) -> bool:
@@ -1293,12 +1320,19 @@ class i8_hardware(_matrix_hardware):
     (ops.i8_pixels_quantize), the windows gathered inside the product (ops.i8_conv2d), no im2col matrix -- and is listed in
     ``direct_layers`` as well as in ``layers``; ``act_block`` does not apply to it (the scale is per pixel).  Every other layer goes
     where it goes without ``direct``.  Under ``emulate=True`` such a layer convolves the decoded pixel operand with the
-    fake-quantised kernel by ``F.conv2d``.  Without ``direct`` (the default) nothing changes."""
+    fake-quantised kernel by ``F.conv2d``.  Without ``direct`` (the default) nothing changes.
+    ``int4=True``: a layer that switches and whose range lies inside [-8, 7] (``i8_int4_eligible``) gets the packed 4-bit operand
+    (``i8_operand(int4=True)``: half the weight bytes, the same bits) and is listed in ``int4_layers``; every other layer that
+    switches keeps its byte operand.  It combines with ``convs``, ``fused``, ``offsets`` and ``emulate`` (which multiplies no
+    operand and lists none); with ``direct`` the direct convs keep their own per-tap byte operand (a 4-bit one is not built).
+    Without ``int4`` (the default) nothing changes."""
 
     _family, _dense_eligible = _I8, staticmethod(i8_hardware_eligible)
 
-    def __init__(self, model: nn.Module, act_block=0, emulate=False, convs=False, fused=False, offsets=False, direct=False):
+    def __init__(self, model: nn.Module, act_block=0, emulate=False, convs=False, fused=False, offsets=False, direct=False,
+                 int4=False):
         self.direct, self.direct_layers = bool(direct), []
+        self.int4, self.int4_layers = bool(int4), []
         self.offsets = bool(offsets)
         self._opt_in = {"offsets": True} if self.offsets else {}
         self.model, self.act_block, self.emulate, self.fused = model, ops.check_i8_block(act_block), bool(emulate), bool(fused)
@@ -1315,12 +1349,17 @@ class i8_hardware(_matrix_hardware):
         """The convs of the im2col path: with ``direct`` those that the direct path does not take."""
         return i8_conv_eligible(layer, **opt_in) and not (self.direct and _takes_direct(layer))
 
+    def _operand_kwargs(self, layer):
+        return {**self._opt_in, "int4": True} if self.int4 and i8_int4_eligible(layer, **self._opt_in) else self._opt_in
+
     def __enter__(self):
         direct = [m for m in custom_layers_of(self.model) if _takes_direct(m)] if self.direct and self.convs else []
+        self.int4_layers = []
         with torch.no_grad():     # every operand before any layer switches: an exception here leaves the model as it was
             parked = [(m.nested_q_k_layer(m.kernel).detach().permute(3, 2, 0, 1) if self.emulate else m.i8_direct_operand(),
                        m.nested_q_b_layer(m.b).detach() if m._has_bias else None) for m in direct]
         super().__enter__()
+        self.int4_layers = [m for m in self.layers if isinstance(getattr(m, _I8.hw)[0], ops.I4Operand)]
         for m, hw in zip(direct, parked):
             m._i8_direct_hw = hw
         self.direct_layers = direct
@@ -1387,7 +1426,7 @@ def mx_dense_chain(x, chain, act_format="fp8_e4m3", act_scale="mx"):
                         x, chain, (act_format, act_scale), act_format)
 
 
-def i8_dense_chain(x, chain, act_block=64, offsets=False):
+def i8_dense_chain(x, chain, act_block=64, offsets=False, int4=False):
     """``chain`` = [(layer, activation), ...]: Dense layers applied one after the other on the int8 matrix instruction, under
     ``no_grad``.  ``x`` is quantised once per row and ``act_block`` inputs (ops.i8_operand_quantize); every layer but the last goes
     through ops.i8_gemm_quantize, which applies its activation (None or "relu") and writes the next layer's operand, per row and
@@ -1396,8 +1435,12 @@ def i8_dense_chain(x, chain, act_block=64, offsets=False):
     ``i8_hardware`` the operands and biases built on its entry are used, otherwise they are built here.  ValueError naming the
     reason for a layer that cannot take the path (``i8_hardware_eligible``) or an activation other than None / "relu".
     ``offsets=True`` lets asymmetric layers take the path (``i8_operand(offsets=True)``): the epilogue's product adds the offset
-    term too, so the bits stay those of the unfused path."""
+    term too, so the bits stay those of the unfused path.  ``int4=True``: every layer multiplies with its packed 4-bit operand
+    (``i8_operand(int4=True)``; a layer whose range does not fit [-8, 7] is refused) -- the same bits again.  Inside ``i8_hardware``
+    the operands parked on its entry are used whatever ``int4`` says here, packed or not: the bits are the same."""
     opt_in = {"offsets": True} if offsets else {}
+    if int4:
+        opt_in["int4"] = True
     return _dense_chain("i8_dense_chain", _I8, "int8", lambda layer: layer._check_i8(**opt_in),
                         lambda: ops.check_i8_block(act_block), x, chain, (act_block,), ops.I8_OUT_BLOCK, **opt_in)
 

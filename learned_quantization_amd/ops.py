@@ -647,12 +647,40 @@ class I8AffineOperand(I8Operand):
     offsets: Optional[torch.Tensor] = None
 
 
-def _i8_offsets(operand: I8Operand) -> Optional[torch.Tensor]:
+I4_RANGE = (-8, 7)           # what a nibble of the packed 4-bit operand holds
+
+
+class I4Operand(NamedTuple):
+    """A B operand of ``lines`` by ``K`` whose codes lie in [-8, 7], stored two to a byte (include/lq_hip.h, "packed 4-bit B
+    operand"; ``i4_operand_pack``): the fields of an I8Operand -- ``codes`` has half the bytes, ``scales`` is the same buffer --
+    and ``offsets``, the I8AffineOperand's buffer for an asymmetric parameter, else None.  ``i8_operand_decode``, ``i8_gemm`` and
+    ``i8_gemm_quantize`` take it as B and give, bit for bit, what they give on the same codes stored in bytes."""
+    codes: torch.Tensor
+    scales: torch.Tensor
+    lines: int
+    K: int
+    block: int
+    offsets: Optional[torch.Tensor] = None
+
+
+def _i8_offsets(operand) -> Optional[torch.Tensor]:
     """The offsets buffer of an operand, or None for a symmetric one."""
-    return getattr(operand, "offsets", None) if isinstance(operand, I8AffineOperand) else None
+    return getattr(operand, "offsets", None) if isinstance(operand, (I8AffineOperand, I4Operand)) else None
+
+
+def _check_i4_buffers(b: I4Operand) -> None:
+    """The kernels read whole tiles without a bounds check: the buffers of a packed operand must have lq_i4_operand_bytes' sizes."""
+    cb, sb = i4_operand_bytes(b.lines, b.K, b.block)
+    if b.codes.dtype != torch.uint8 or b.codes.numel() != cb or b.scales.dtype != torch.float32 or b.scales.numel() * 4 != sb:
+        raise ValueError(f"I4Operand ({b.lines}, {b.K}, block {b.block}): codes must be {cb} uint8 and scales {sb // 4} float32, got "
+                         f"{b.codes.numel()} {b.codes.dtype} and {b.scales.numel()} {b.scales.dtype}")
+    if b.offsets is not None and (b.offsets.dtype != torch.float32 or b.offsets.numel() * 4 != sb):
+        raise ValueError(f"I4Operand: offsets must be {sb // 4} float32, the layout of scales")
 
 
 def _check_i8_a_operand(a: I8Operand) -> None:
+    if isinstance(a, I4Operand):
+        raise ValueError("a packed 4-bit operand is a B operand only: the A side is an int8 operand (a 4-bit A operand is not built)")
     if _i8_offsets(a) is not None:
         raise ValueError("only the B operand carries offsets: activation offsets are not built")
 
@@ -718,17 +746,43 @@ def check_i8_conv_operand_layer(q_range, orientation, group_size=None, asymmetri
     return qmin, qmax
 
 
-def i8_operand_bytes(lines: int, K: int, block: int = 0) -> Tuple[int, int]:
-    """(code_bytes, scale_bytes) of an operand (include/lq_hip.h, lq_i8_operand_bytes).  Needs no device."""
+def check_i4_operand_layer(q_range, orientation, group_size=None, asymmetric=False, element_format=None, fan_in=None, *,
+                           offsets=False, conv=False, kernel_storage="oihw") -> Tuple[int, int]:
+    """What a quantizer must be to take the packed 4-bit operand -- (qmin, qmax) -- or ValueError naming the reason: everything
+    ``check_i8_operand_layer`` asks (``conv=True``: ``check_i8_conv_operand_layer``), and a range inside [-8, 7]."""
+    if conv:
+        qmin, qmax = check_i8_conv_operand_layer(q_range, orientation, group_size, asymmetric, element_format, fan_in, kernel_storage,
+                                                 offsets=offsets)
+    else:
+        qmin, qmax = check_i8_operand_layer(q_range, orientation, group_size, asymmetric, element_format, fan_in, offsets=offsets)
+    if (qmin, qmax) == (0, 15):
+        raise ValueError("q_range (0, 15): an unsigned 4-bit range is not built for the packed operand, whose nibbles are signed "
+                         f"codes in [{I4_RANGE[0]}, {I4_RANGE[1]}] (train.py: --bits 4 without --unsigned)")
+    if qmin < I4_RANGE[0] or qmax > I4_RANGE[1]:
+        raise ValueError(f"q_range ({qmin}, {qmax}) is not inside [{I4_RANGE[0]}, {I4_RANGE[1]}], the signed codes a nibble holds")
+    return qmin, qmax
+
+
+def _operand_bytes(lib_fn, what, lines, K, block) -> Tuple[int, int]:
     import ctypes
     cb, sb = ctypes.c_size_t(0), ctypes.c_size_t(0)
-    _hip.check(_hip.load().lq_i8_operand_bytes(int(lines), int(K), check_i8_block(block), ctypes.byref(cb), ctypes.byref(sb)),
-               "lq_i8_operand_bytes")
+    _hip.check(lib_fn(int(lines), int(K), check_i8_block(block), ctypes.byref(cb), ctypes.byref(sb)), what)
     return int(cb.value), int(sb.value)
 
 
-def _i8_operand_buffers(lines: int, K: int, block: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
-    cb, sb = i8_operand_bytes(lines, K, block)
+def i8_operand_bytes(lines: int, K: int, block: int = 0) -> Tuple[int, int]:
+    """(code_bytes, scale_bytes) of an operand (include/lq_hip.h, lq_i8_operand_bytes).  Needs no device."""
+    return _operand_bytes(_hip.load().lq_i8_operand_bytes, "lq_i8_operand_bytes", lines, K, block)
+
+
+def i4_operand_bytes(lines: int, K: int, block: int = 0) -> Tuple[int, int]:
+    """(code_bytes, scale_bytes) of a packed 4-bit operand (include/lq_hip.h, lq_i4_operand_bytes): half of ``i8_operand_bytes``'
+    code bytes, and its scale bytes.  Needs no device."""
+    return _operand_bytes(_hip.load().lq_i4_operand_bytes, "lq_i4_operand_bytes", lines, K, block)
+
+
+def _i8_operand_buffers(lines: int, K: int, block: int, device, bytes_of=i8_operand_bytes) -> Tuple[torch.Tensor, torch.Tensor]:
+    cb, sb = bytes_of(lines, K, block)
     return torch.empty(cb, dtype=torch.uint8, device=device), torch.empty(sb // 4, dtype=torch.float32, device=device)
 
 
@@ -740,10 +794,22 @@ def i8_operand_pack(parameter: torch.Tensor, scale: torch.Tensor, qmin: int, qma
     line length gives one scale per line; otherwise it must be a multiple of 64.  One launch.
     ``offset`` (the scale's shape): the operand of an asymmetric parameter, an I8AffineOperand (lq_i8_operand_pack_affine) whose
     codes are ``fq_forward_group_affine``'s and whose ``offsets`` are ``offset`` bit for bit."""
+    return _operand_pack(False, parameter, scale, qmin, qmax, group_size, rounding, offset)
+
+
+def i4_operand_pack(parameter: torch.Tensor, scale: torch.Tensor, qmin: int, qmax: int, group_size: int,
+                    rounding: str = "floor", offset: Optional[torch.Tensor] = None) -> I4Operand:
+    """``i8_operand_pack`` into the packed 4-bit operand (include/lq_hip.h, lq_i4_operand_pack / lq_i4_operand_pack_affine): the
+    same codes, two to a byte, the same scales (and ``offsets``) bit for bit.  The range must lie inside [-8, 7].  One launch."""
+    return _operand_pack(True, parameter, scale, qmin, qmax, group_size, rounding, offset)
+
+
+def _operand_pack(int4: bool, parameter, scale, qmin, qmax, group_size, rounding, offset):
     qmin, qmax = check_q_range(qmin, qmax)
-    if qmin < I8_RANGE[0] or qmax > I8_RANGE[1]:
-        raise ValueError(f"range ({qmin}, {qmax}) is not inside [{I8_RANGE[0]}, {I8_RANGE[1]}], the signed bytes the int8 matrix "
-                         "instruction multiplies")
+    lo, hi = I4_RANGE if int4 else I8_RANGE
+    if qmin < lo or qmax > hi:
+        raise ValueError(f"range ({qmin}, {qmax}) is not inside [{lo}, {hi}], " + ("the signed codes a nibble holds" if int4 else
+                         "the signed bytes the int8 matrix instruction multiplies"))
     rnd = check_rounding(rounding)
     p, s, (R, C, axis) = _group_param(parameter, scale, group_size)
     b = None if offset is None else _offset_like(offset, s)
@@ -753,18 +819,21 @@ def i8_operand_pack(parameter: torch.Tensor, scale: torch.Tensor, qmin: int, qma
         raise ValueError(f"group_size={gs}: a scale block of the int8 GEMM is the whole line ({K}) or a multiple of {I8_BLOCK_UNIT}")
     block = 0 if gs >= K else gs
     lib = _hip.load()
-    codes, scales = _i8_operand_buffers(lines, K, block, p.device)
+    name = "lq_i4_operand_pack" if int4 else "lq_i8_operand_pack"
+    codes, scales = _i8_operand_buffers(lines, K, block, p.device, i4_operand_bytes if int4 else i8_operand_bytes)
     if b is not None:
         offsets = torch.empty_like(scales)
-        _hip.check(lib.lq_i8_operand_pack_affine(_hip.ptr(p), _hip.ptr(s), _hip.ptr(b), qmin, qmax, rnd, R, C, axis, gs,
-                                                 _hip.ptr(codes), _hip.ptr(scales), _hip.ptr(offsets), _hip.stream_ptr(p.device)),
-                   "lq_i8_operand_pack_affine")
+        _hip.check(getattr(lib, name + "_affine")(_hip.ptr(p), _hip.ptr(s), _hip.ptr(b), qmin, qmax, rnd, R, C, axis, gs,
+                                                  _hip.ptr(codes), _hip.ptr(scales), _hip.ptr(offsets), _hip.stream_ptr(p.device)),
+                   name + "_affine")
+        if int4:
+            return I4Operand(codes, scales, lines, K, block, offsets)
         op = I8AffineOperand(codes, scales, lines, K, block)
         op.offsets = offsets
         return op
-    _hip.check(lib.lq_i8_operand_pack(_hip.ptr(p), _hip.ptr(s), qmin, qmax, rnd, R, C, axis, gs, _hip.ptr(codes), _hip.ptr(scales),
-                                      _hip.stream_ptr(p.device)), "lq_i8_operand_pack")
-    return I8Operand(codes, scales, lines, K, block)
+    _hip.check(getattr(lib, name)(_hip.ptr(p), _hip.ptr(s), qmin, qmax, rnd, R, C, axis, gs, _hip.ptr(codes), _hip.ptr(scales),
+                                  _hip.stream_ptr(p.device)), name)
+    return (I4Operand if int4 else I8Operand)(codes, scales, lines, K, block)
 
 
 def i8_operand_quantize(x: torch.Tensor, block: int = 0) -> I8Operand:
@@ -785,18 +854,22 @@ def i8_operand_quantize(x: torch.Tensor, block: int = 0) -> I8Operand:
 
 def i8_operand_decode(operand: I8Operand) -> torch.Tensor:
     """float32 ``(lines, K)``: code * scale of every element (include/lq_hip.h, lq_i8_operand_decode); of an I8AffineOperand
-    ``code * scale + offset``, two roundings (lq_i8_operand_decode_affine)."""
+    ``code * scale + offset``, two roundings (lq_i8_operand_decode_affine); of an I4Operand the same values from its nibbles
+    (lq_i4_operand_decode / lq_i4_operand_decode_affine)."""
     lib = _hip.load()
+    name = "lq_i8_operand_decode"
+    if isinstance(operand, I4Operand):
+        _check_i4_buffers(operand)
+        name = "lq_i4_operand_decode"
     out = torch.empty((operand.lines, operand.K), dtype=torch.float32, device=operand.codes.device)
     offsets = _i8_offsets(operand)
     if offsets is not None:
-        _hip.check(lib.lq_i8_operand_decode_affine(_hip.ptr(operand.codes), _hip.ptr(operand.scales), _hip.ptr(offsets),
-                                                   operand.lines, operand.K, check_i8_block(operand.block), _hip.ptr(out),
-                                                   _hip.stream_ptr(out.device)), "lq_i8_operand_decode_affine")
+        _hip.check(getattr(lib, name + "_affine")(_hip.ptr(operand.codes), _hip.ptr(operand.scales), _hip.ptr(offsets),
+                                                  operand.lines, operand.K, check_i8_block(operand.block), _hip.ptr(out),
+                                                  _hip.stream_ptr(out.device)), name + "_affine")
         return out
-    _hip.check(lib.lq_i8_operand_decode(_hip.ptr(operand.codes), _hip.ptr(operand.scales), operand.lines, operand.K,
-                                        check_i8_block(operand.block), _hip.ptr(out), _hip.stream_ptr(out.device)),
-               "lq_i8_operand_decode")
+    _hip.check(getattr(lib, name)(_hip.ptr(operand.codes), _hip.ptr(operand.scales), operand.lines, operand.K,
+                                  check_i8_block(operand.block), _hip.ptr(out), _hip.stream_ptr(out.device)), name)
     return out
 
 
@@ -817,23 +890,28 @@ def i8_period(a_block: int, b_block: int, K: int) -> int:
 def i8_gemm(a: I8Operand, b: I8Operand, bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``Y (a.lines, b.lines) = A B^T (+ bias)`` on v_mfma_i32_16x16x64_i8 (include/lq_hip.h, lq_i8_gemm): exact int32 sums per
     period, scaled into fp32 by the product of the two operands' scales, bit for bit the definition stated there.
-    ``out``: a float32 matrix to write into; its row stride is the leading dimension."""
+    ``out``: a float32 matrix to write into; its row stride is the leading dimension.
+    ``b`` may be an I4Operand (lq_i8_gemm_w4 / lq_i8_gemm_w4_affine): the same Y, bit for bit, from codes stored two to a byte."""
     if a.K != b.K:
         raise ValueError(f"the operands reduce over different K: {a.K} and {b.K}")
     _check_i8_a_operand(a)
     i8_period(a.block, b.block, a.K)
     lib = _hip.load()
+    name = "lq_i8_gemm"
+    if isinstance(b, I4Operand):
+        _check_i4_buffers(b)
+        name = "lq_i8_gemm_w4"
     M, N = a.lines, b.lines
     dev = a.codes.device
     bias, out, ldy = _gemm_output(a, b, bias, out)
     offsets = _i8_offsets(b)
     if offsets is not None:      # B = q s + b: the offset's row-sum term (lq_i8_gemm_affine)
-        _hip.check(lib.lq_i8_gemm_affine(_hip.ptr(a.codes), _hip.ptr(a.scales), a.block, _hip.ptr(b.codes), _hip.ptr(b.scales),
-                                         _hip.ptr(offsets), b.block, _hip.ptr(bias), _hip.ptr(out), ldy, M, N, a.K,
-                                         _hip.stream_ptr(dev)), "lq_i8_gemm_affine")
+        _hip.check(getattr(lib, name + "_affine")(_hip.ptr(a.codes), _hip.ptr(a.scales), a.block, _hip.ptr(b.codes), _hip.ptr(b.scales),
+                                                  _hip.ptr(offsets), b.block, _hip.ptr(bias), _hip.ptr(out), ldy, M, N, a.K,
+                                                  _hip.stream_ptr(dev)), name + "_affine")
         return out
-    _hip.check(lib.lq_i8_gemm(_hip.ptr(a.codes), _hip.ptr(a.scales), a.block, _hip.ptr(b.codes), _hip.ptr(b.scales), b.block,
-                              _hip.ptr(bias), _hip.ptr(out), ldy, M, N, a.K, _hip.stream_ptr(dev)), "lq_i8_gemm")
+    _hip.check(getattr(lib, name)(_hip.ptr(a.codes), _hip.ptr(a.scales), a.block, _hip.ptr(b.codes), _hip.ptr(b.scales), b.block,
+                                  _hip.ptr(bias), _hip.ptr(out), ldy, M, N, a.K, _hip.stream_ptr(dev)), name)
     return out
 
 
@@ -886,7 +964,8 @@ def i8_gemm_quantize(a: I8Operand, b: I8Operand, bias: Optional[torch.Tensor] = 
                      out_block: int = I8_OUT_BLOCK) -> I8Operand:
     """The int8 operand of ``activation(A B^T (+ bias))`` for the next product, ``a.lines`` lines over ``K = b.lines`` with scale
     blocks of ``out_block`` (64), written by the GEMM's own epilogue (include/lq_hip.h, lq_i8_gemm_quantize): byte for byte
-    ``i8_operand_quantize(act(i8_gemm(a, b, bias)), out_block)``, in one launch and without the fp32 matrix."""
+    ``i8_operand_quantize(act(i8_gemm(a, b, bias)), out_block)``, in one launch and without the fp32 matrix.  ``b`` may be an
+    I4Operand (lq_i8_gemm_quantize_w4 / lq_i8_gemm_quantize_w4_affine); the operand written is an int8 one either way."""
     out_block = check_i8_out_block(out_block)
     act = check_activation(activation)
     if a.K != b.K:
@@ -894,20 +973,24 @@ def i8_gemm_quantize(a: I8Operand, b: I8Operand, bias: Optional[torch.Tensor] = 
     _check_i8_a_operand(a)
     i8_period(a.block, b.block, a.K)
     lib = _hip.load()
+    name = "lq_i8_gemm_quantize"
+    if isinstance(b, I4Operand):
+        _check_i4_buffers(b)
+        name = "lq_i8_gemm_quantize_w4"
     M, N = a.lines, b.lines
     dev = a.codes.device
     bias = _gemm_output(a, b, bias, fp32_out=False)[0]
     codes, scales = _i8_operand_buffers(M, N, out_block, dev)
     offsets = _i8_offsets(b)
     if offsets is not None:
-        _hip.check(lib.lq_i8_gemm_quantize_affine(_hip.ptr(a.codes), _hip.ptr(a.scales), a.block, _hip.ptr(b.codes),
+        _hip.check(getattr(lib, name + "_affine")(_hip.ptr(a.codes), _hip.ptr(a.scales), a.block, _hip.ptr(b.codes),
                                                   _hip.ptr(b.scales), _hip.ptr(offsets), b.block, _hip.ptr(bias), act, out_block,
                                                   _hip.ptr(codes), _hip.ptr(scales), M, N, a.K, _hip.stream_ptr(dev)),
-                   "lq_i8_gemm_quantize_affine")
+                   name + "_affine")
         return I8Operand(codes, scales, M, N, out_block)
-    _hip.check(lib.lq_i8_gemm_quantize(_hip.ptr(a.codes), _hip.ptr(a.scales), a.block, _hip.ptr(b.codes), _hip.ptr(b.scales), b.block,
-                                       _hip.ptr(bias), act, out_block, _hip.ptr(codes), _hip.ptr(scales), M, N, a.K,
-                                       _hip.stream_ptr(dev)), "lq_i8_gemm_quantize")
+    _hip.check(getattr(lib, name)(_hip.ptr(a.codes), _hip.ptr(a.scales), a.block, _hip.ptr(b.codes), _hip.ptr(b.scales), b.block,
+                                  _hip.ptr(bias), act, out_block, _hip.ptr(codes), _hip.ptr(scales), M, N, a.K,
+                                  _hip.stream_ptr(dev)), name)
     return I8Operand(codes, scales, M, N, out_block)
 
 

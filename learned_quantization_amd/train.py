@@ -644,11 +644,16 @@ def build_parser():
                     help="with --i8-eval: asymmetric layers (--asymmetric) take the hardware path too (layers.i8_hardware(offsets=True): "
                          "their operand carries the offsets and the product adds the offset's row-sum term, at the price of more "
                          "matrix instructions per step); without it --i8-eval --asymmetric is refused")
+    ap.add_argument("--i8-eval-int4", action="store_true",
+                    help="with --i8-eval and --bits of at most 4: evaluate once more under layers.i8_hardware(int4=True) (the weights "
+                         "two 4-bit codes to a byte; with --i8-eval-convs the conv layers too) and add i8_eval_int4_layers, "
+                         "i8_eval_int4_accuracy and i8_eval_int4_max_logit_diff (the model's outputs against the byte operands'; "
+                         "0.0 is expected) to the result line")
     return ap
 
 
 @torch.no_grad()
-def i8_eval(model, x, y, act_block=0, convs=False, fused=False, offsets=False, direct=False):
+def i8_eval(model, x, y, act_block=0, convs=False, fused=False, offsets=False, direct=False, int4=False):
     """One evaluation of ``model`` on (x, y) under layers.i8_hardware, one under its ``emulate=True`` yardstick and one of the
     fake-quantised model as it stands: a dict of the three accuracies and the largest |difference| of the outputs of the last Dense
     layer that took the path (the logits of the MNIST model) between the hardware path and each of the other two.  ValueError for
@@ -659,7 +664,9 @@ def i8_eval(model, x, y, act_block=0, convs=False, fused=False, offsets=False, d
     ``i8_hardware(fused=True)``: the number of layers that fused, its accuracy and the largest |difference| of the model's ``logits``
     from the unfused hardware path's (the same bits are expected: 0.0).  ``direct=True`` (with ``convs=True``) adds an evaluation
     under ``i8_hardware(convs=True, direct=True)`` and one under its emulation: the conv layers on the direct int8 convolution, those
-    left on the im2col path, the accuracy, and the largest |difference| of the model's outputs between the two."""
+    left on the im2col path, the accuracy, and the largest |difference| of the model's outputs between the two.  ``int4=True``
+    adds an evaluation under ``i8_hardware(int4=True)`` (with ``convs`` as given): the number of layers that took the packed 4-bit
+    operand, the accuracy, and the largest |difference| of the model's outputs from the byte operands' (the same bits: 0.0)."""
     was_training = model.training
     model.eval()
     acc, logits = [], []
@@ -717,6 +724,18 @@ def i8_eval(model, x, y, act_block=0, convs=False, fused=False, offsets=False, d
             fields.update({"i8_eval_direct_layers": n_direct, "i8_eval_direct_im2col_layers": n_im2col,
                            "i8_eval_direct_accuracy": float((outs[0].argmax(1) == y).float().mean()),
                            "i8_eval_direct_max_logit_diff": float((outs[0] - outs[1]).abs().max())})
+        if int4:
+            outs = []
+            for i4 in (True, False):
+                with L.i8_hardware(model, probe.act_block, convs=convs, offsets=offsets, int4=i4) as hw4:
+                    if i4 and not hw4.int4_layers:
+                        raise ValueError("i8_eval: int4=True needs a layer on the hardware path whose range lies inside [-8, 7] "
+                                         "(--bits of at most 4, signed)")
+                    if i4:
+                        n_int4 = len(hw4.int4_layers)
+                    outs.append(model(x))
+            fields.update({"i8_eval_int4_layers": n_int4, "i8_eval_int4_accuracy": float((outs[0].argmax(1) == y).float().mean()),
+                           "i8_eval_int4_max_logit_diff": float((outs[0] - outs[1]).abs().max())})
     finally:
         model.train(was_training)
     return {"i8_eval_act_block": probe.act_block, "i8_eval_layers": n_layers, "i8_eval_accuracy": acc[0],
@@ -793,6 +812,8 @@ def main(argv=None):
         ap.error("--i8-eval needs --bits of at most 8, signed and symmetric (or --asymmetric with --i8-eval-offsets, which adds the "
                  "offset's row-sum term to the product), and no --element-format: it runs the Dense layers of an integer model on "
                  "the int8 matrix instruction")
+    if args.i8_eval_int4 and (not args.i8_eval or args.bits > 4):
+        ap.error("--i8-eval-int4 needs --i8-eval and --bits of at most 4: the packed operand holds signed codes in [-8, 7]")
     if args.i8_eval_act_block and not args.i8_eval:
         ap.error("--i8-eval-act-block needs --i8-eval")
     if args.i8_eval_convs and not args.i8_eval:
@@ -873,7 +894,7 @@ def main(argv=None):
     quant_stats = L.quant_stats(tr.model) if args.quant_stats and rank == 0 else None      # after the clock has stopped
     mx_stats = L.mx_quant_stats(tr.model) if args.mx_stats and rank == 0 else None
     mx_eval_fields = mx_eval(tr.model, *batches[0], act_format=args.mx_eval, fused=args.mx_eval_fused, convs=args.mx_eval_convs) if args.mx_eval is not None and rank == 0 else None
-    i8_eval_fields = i8_eval(tr.model, *batches[0], act_block=args.i8_eval_act_block, convs=args.i8_eval_convs, fused=args.i8_eval_fused, offsets=args.i8_eval_offsets, direct=args.i8_eval_direct) if args.i8_eval and rank == 0 else None
+    i8_eval_fields = i8_eval(tr.model, *batches[0], act_block=args.i8_eval_act_block, convs=args.i8_eval_convs, fused=args.i8_eval_fused, offsets=args.i8_eval_offsets, direct=args.i8_eval_direct, int4=args.i8_eval_int4) if args.i8_eval and rank == 0 else None
     if rank == 0:
         n_q = sum(p.numel() for l in tr.custom_layers for p in l._regularized())
         print(json.dumps({

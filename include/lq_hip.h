@@ -648,8 +648,22 @@ int lq_mx_operand_im2col(const float* X, const lq_conv_geom* g, int format, int 
  * C (ci) > 65536 (a tap's int32 sum must stay exact), M above 65535 * 64, ldy < co, a buffer of 2^31 bytes or more, a padded input
  * extent of 2^31 or more; for pack a range outside [-128, 127] and a bad rounding.  LQ_EALIGN: codes or scales off the 16-byte
  * grid; X, P, s, bias or Y off the 4-byte grid.
+ * lq_i8_conv2d_quantize: lq_i8_conv2d's arguments without Y and ldy, and an epilogue that writes the NEXT conv's pixel operand
+ * instead of Y.  DEFINITION (bit exact).  Let Y[m][n] be lq_i8_conv2d's Y, bias included, bit for bit, and
+ *       relu(v) = v > 0 ? v : (v != v ? v : +0)
+ *       aff(v)  = RN(RN(v * post_scale[n]) + post_shift[n])      the product and the sum round separately (no contraction)
+ *   affine_first = 0: v = aff(act(Y)) (conv, relu, BatchNorm);  affine_first = 1: v = act(aff(Y)) (conv, BatchNorm, relu); a
+ *   missing affine (post_scale and post_shift both NULL) or activation (LQ_ACT_NONE) is the identity.  out_codes and out_scales
+ *   are, byte for byte, what lq_i8_pixels_quantize writes for v seen as [B][co][OH][OW]: out_codes [M][CPo] int8, CPo = 32 *
+ *   ceil(co / 32), code 0 in channels co .. CPo - 1; out_scales [M]; line m = (b * OH + oh) * OW + ow is the output pixel.  A
+ *   pixel whose v are all zero gets scale 2^-126 and codes 0; a pixel holding a NaN or +-Inf gets a NaN scale and codes 0, and no
+ *   other pixel does.  ONE launch (capturable); no memset, workspace or atomics; reads no environment; writes exactly
+ *   lq_i8_pixels_bytes(B, co, OH, OW).  A pixel's scale is the absmax over all co channels, so a whole output row is resident in
+ *   one thread block before its first code: co <= 512.  LQ_EINVAL before any launch: everything lq_i8_conv2d refuses, co > 512, an
+ *   unknown activation, affine_first outside {0, 1}, exactly one of post_scale / post_shift NULL.  LQ_EALIGN: what lq_i8_conv2d
+ *   refuses, out_codes or out_scales off the 16-byte grid, post_scale or post_shift off the 4-byte grid.
  * Not built on this path: weight scales that vary along K (a group size below ci * kh * kw stays on the im2col path), offsets
- * (asymmetric layers), MX elements, an epilogue that writes the next layer's pixel operand, dilation and groups.
+ * (asymmetric layers), MX elements, an epilogue for co > 512 or with a residual input (the ResNet blocks), dilation and groups.
  *
  * PACKED 4-BIT B OPERAND (W4A8).  An operand of L lines by K whose codes lie in [-8, 7] stores them two to a byte, under the same
  * fp32 scales (and, for an asymmetric parameter, offsets) in exactly the layout above:
@@ -722,6 +736,10 @@ int lq_i8_conv_kernel_pack(const float* P, const float* s, int32_t qmin, int32_t
                            int64_t KW, void* codes, void* scales, void* stream);
 int lq_i8_conv2d(const void* pix_codes, const void* pix_scales, const void* k_codes, const void* k_scales,
                  const float* bias /* may be NULL */, float* Y, int64_t ldy, const lq_conv_geom* g, int64_t co, void* stream);
+int lq_i8_conv2d_quantize(const void* pix_codes, const void* pix_scales, const void* k_codes, const void* k_scales,
+                          const float* bias /* may be NULL */, const lq_conv_geom* g, int64_t co,
+                          const float* post_scale /* [co]; both or neither NULL */, const float* post_shift,
+                          int activation /* lq_mx_activation */, int affine_first, void* out_codes, void* out_scales, void* stream);
 
 /* ---- K4: forward and NQ backward of one tensor in a single pass (benchmark path) ---
  * Same results as lq_fq_forward followed by lq_fq_scale_grad (out, max|q| and the vote count bit for bit; on

@@ -24,6 +24,7 @@
 //   lq_mx_conv.hpp      the MX operand of that matrix, gathered from the input in one launch
 //   lq_i8_conv.hpp      the int8 operand of the same matrix: absmax scales per (line, scale block), two passes over the gather
 //   lq_i8_direct.hpp    the direct int8 convolution: NHWC pixel operand, per-tap kernel operand, the product that gathers its windows
+//   lq_i8_direct_quant.hpp  the direct int8 convolution with an epilogue that writes the next conv's pixel operand
 //   this file           host side: traversal plan, launchers, the extern "C" entry points
 //
 // The path is elementwise + per-group reductions: HBM-bound, no MFMA.  Design rules
@@ -78,6 +79,7 @@
 #include "lq_i8_conv.hpp"
 #include "lq_i8_gemm_quant.hpp"
 #include "lq_i8_direct.hpp"
+#include "lq_i8_direct_quant.hpp"
 
 namespace lq {
 
@@ -2610,6 +2612,79 @@ int lq_i8_conv2d(const void* pix_codes, const void* pix_scales, const void* k_co
     if (dk.step == 64) hipLaunchKernelGGL(k_i8_conv2d<64>, grid, dim3(kBlock), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(k_i8_conv2d<32>, grid, dim3(kBlock), 0, (hipStream_t)stream, p);
     return check_hip("direct int8 convolution");
+}
+
+// ---- the direct int8 convolution with a pixel-operand epilogue (lq_i8_direct_quant.hpp) ----
+constexpr int64_t kI8ConvQuantMaxCo = 512;      // 32 column tiles: four waves by eight, a whole output row resident in one block
+
+int lq_i8_conv2d_quantize(const void* pix_codes, const void* pix_scales, const void* k_codes, const void* k_scales, const float* bias,
+                          const lq_conv_geom* g, int64_t co, const float* post_scale, const float* post_shift, int activation,
+                          int affine_first, void* out_codes, void* out_scales, void* stream) {
+    const char* fn = __func__;
+    ConvDims cd;
+    int rc = conv_geom_dims(fn, g, cd);            // the xs_* fields are not read
+    if (rc) return rc;
+    I8DirectDims dp{}, dk{}, dout{};
+    if ((rc = i8_pixels_dims(fn, g->B, g->C, g->H, g->W, dp))) return rc;
+    if ((rc = i8_conv_kernel_dims(fn, co, g->C, g->KH, g->KW, dk))) return rc;
+    if (co > kI8ConvQuantMaxCo)
+        return fail(LQ_EINVAL, "%s: co = %lld is above %lld: a pixel's scale needs its whole output row, at most 32 column tiles, in one "
+                    "thread block before the first code", fn, (long long)co, (long long)kI8ConvQuantMaxCo);
+    if (activation != LQ_ACT_NONE && activation != LQ_ACT_RELU) return fail(LQ_EINVAL, "%s: bad activation %d", fn, activation);
+    if (affine_first != 0 && affine_first != 1) return fail(LQ_EINVAL, "%s: affine_first = %d is neither 0 nor 1", fn, affine_first);
+    if ((post_scale == nullptr) != (post_shift == nullptr))
+        return fail(LQ_EINVAL, "%s: post_scale and post_shift must both be given or both be NULL", fn);
+    if ((rc = i8_pixels_dims(fn, g->B, co, cd.OH, cd.OW, dout))) return rc;      // what is written: M * CPo < 2^31
+    if ((rc = check_operand_buffers(fn, pix_codes, pix_scales, kI8ScaleAlign))) return rc;
+    if ((rc = check_operand_buffers(fn, k_codes, k_scales, kI8ScaleAlign))) return rc;
+    if ((rc = check_operand_buffers(fn, out_codes, out_scales, kI8ScaleAlign))) return rc;
+    if ((rc = check_gemm_bias(fn, bias))) return rc;
+    if (post_scale && (!aligned(post_scale, 4) || !aligned(post_shift, 4)))
+        return fail(LQ_EALIGN, "%s: post_scale or post_shift is not 4-byte aligned", fn);
+    // the kernel forms a window's corner, oh * stride_h - pad_top, in 32 bits
+    if (g->H + g->pad_top + g->pad_bottom > 2147483647 || g->W + g->pad_left + g->pad_right > 2147483647)
+        return fail(LQ_EINVAL, "%s: the padded input (%lld x %lld) does not fit 32 bits", fn, (long long)(g->H + g->pad_top + g->pad_bottom),
+                    (long long)(g->W + g->pad_left + g->pad_right));
+    const int64_t MT = (cd.M + kI8TileLines - 1) / kI8TileLines;
+    dim3 unused;
+    if ((rc = gemm_grid(fn, 1, MT, cd.M, unused))) return rc;      // lq_i8_conv2d's limit on M, kept: the two calls take the same runs
+    I8ConvQuantParams q{};
+    I8Conv2dParams& p = q.c;
+    p.pix_codes = (const uint8_t*)pix_codes;
+    p.pix_scales = (const float*)pix_scales;
+    p.k_codes = (const uint8_t*)k_codes;
+    p.k_scales = (const float*)k_scales;
+    p.bias = bias;
+    p.ohow = make_fastdiv((uint32_t)(cd.OH * cd.OW));      // M <= 65535 * 64 bounds OH * OW and OW
+    p.ow = make_fastdiv((uint32_t)cd.OW);
+    p.M = (int32_t)cd.M;
+    p.N = (int32_t)co;
+    p.MT = (int32_t)MT;
+    p.NT = (int32_t)dk.NT;
+    p.CS = (int32_t)dk.CS;
+    p.CP = (int32_t)dk.CP;
+    p.H = (int32_t)g->H;
+    p.W = (int32_t)g->W;
+    p.KH = g->KH;
+    p.KW = g->KW;
+    p.stride_h = g->stride_h;
+    p.stride_w = g->stride_w;
+    p.pad_top = g->pad_top;
+    p.pad_left = g->pad_left;
+    q.gp.lo = q.ip.lo = -127.0f;
+    q.gp.hi = q.ip.hi = 127.0f;
+    q.ip.min_value = kOperandMinScale;
+    q.post_scale = post_scale;
+    q.post_shift = post_shift;
+    q.codes = (uint8_t*)out_codes;
+    q.scales = (float*)out_scales;
+    q.act = activation;
+    q.affine_first = affine_first;
+    q.CPo = (int32_t)dout.CP;
+    q.OT = (int32_t)(dout.CP / kI8TileLines);
+    if (dk.step == 64) i8_conv2d_quantize_launch<64>(q, (hipStream_t)stream);
+    else i8_conv2d_quantize_launch<32>(q, (hipStream_t)stream);
+    return check_hip("direct int8 convolution with pixel-operand epilogue");
 }
 
 static int i8_operand_decode(const char* fn, bool affine, bool w4, const void* codes, const void* scales, const void* offsets, int64_t L,

@@ -837,6 +837,7 @@ class _ConvBase(_HostLayer):
     _prefix = "custom_conv2d_layer"
     _has_bias = True
     _i8_direct_hw = None      # (operand, bias) parked by i8_hardware(convs=True, direct=True)
+    _i8_chain_hw = None       # (operand, bias) parked by i8_hardware(fused_convs=True) on the layers of a conv chain
 
     def __init__(self, seed=None, penalty_threshold=None, orientation="scalar", initializer=None, filters=None,
                  kernel_size=(3, 3), strides=(1, 1), padding="same", name=None, regularizer=None,
@@ -1119,21 +1120,66 @@ class _ConvBase(_HostLayer):
             y = y.view(B, OH, OW, self.filters)                   # [M][co] is NHWC: no transposition launch
             return y if self.data_format == "NHWC" else y.permute(0, 3, 1, 2)
 
-    def call_i8_direct(self, inputs, max_lines=None):
+    def _direct_step(self, x, operand, qb, max_lines=None, out_pixels=False, activation=None, affine=None, affine_first=False):
+        """One layer of a direct-conv chain: ``x`` a tensor in the layer's data format (quantised here, per run) or an ops.I8Pixels;
+        the result the fp32 view ``_direct_conv`` returns, or (``out_pixels``) the next conv's ops.I8Pixels from the product's own
+        epilogue (ops.i8_conv2d_quantize).  The batch is cut into runs of whole images by lines, as ``_direct_conv`` cuts it."""
+        if isinstance(x, ops.I8Pixels):
+            B, C, H, W = x.shape
+            def run(b0, b1):      # a cut: the codes of whole images stay on the 16-byte grid (CP % 32 == 0); the scales may not
+                scales = x.scales[b0:b1]
+                return ops.I8Pixels(x.codes[b0:b1], scales.clone() if scales.data_ptr() % 16 else scales, (b1 - b0, C, H, W))
+        else:
+            if x.dim() != 4:
+                raise ValueError(f"{self.name}: the input must have four axes, got shape {tuple(x.shape)}")
+            xt = x.permute(0, 3, 1, 2) if self.data_format == "NHWC" else x
+            B, C, H, W = xt.shape
+            run = lambda b0, b1: ops.i8_pixels_quantize(xt[b0:b1])                                      # noqa: E731
+        padding = self._mx_padding(H, W)
+        M, _, OH, OW = ops.mx_im2col_dims((B, C, H, W), self.kernel_size, self.strides, padding)
+        per = OH * OW
+        fit = 65535 * 64 if max_lines is None else min(65535 * 64, max_lines)
+        images = max(1, min(B, fit // per))
+        runs = [(b0, min(B, b0 + images)) for b0 in range(0, B, images)]
+        if out_pixels:
+            outs = [ops.i8_conv2d_quantize(run(b0, b1), operand, qb, self.strides, padding, activation, affine, affine_first)
+                    for b0, b1 in runs]
+            if len(outs) == 1:
+                return outs[0]
+            return ops.I8Pixels(torch.cat([o.codes for o in outs]), torch.cat([o.scales for o in outs]), (B, self.filters, OH, OW))
+        y = torch.empty((M, self.filters), dtype=torch.float32, device=operand.codes.device)
+        for b0, b1 in runs:
+            ops.i8_conv2d(run(b0, b1), operand, qb, self.strides, padding, out=y[b0 * per:b1 * per])
+        y = y.view(B, OH, OW, self.filters)
+        return y if self.data_format == "NHWC" else y.permute(0, 3, 1, 2)
+
+    def call_i8_direct(self, inputs, max_lines=None, out_pixels=False, activation=None, affine=None, affine_first=False):
         """The layer as a direct int8 convolution, under ``no_grad``: the inputs quantised ONCE per pixel to symmetric 8-bit integers
         (ops.i8_pixels_quantize: an int8 NHWC copy, one scale per pixel), convolved with ``i8_direct_operand()`` on the int8 matrix
         instruction by ops.i8_conv2d -- TensorFlow 'SAME' padding as ``call`` pads, or 'VALID' -- plus the fake-quantised bias where
         the layer has one.  No im2col matrix is written.  Inference only.  The result is the kind of view ``call_i8`` returns.  A
         batch of more than 65535 * 64 lines or more than ``max_lines`` lines is cut into runs of whole images; the result does not
         depend on the cut.  The activation scale is per PIXEL here and per im2col LINE in ``call_i8``: the two paths round the
-        activations differently and are not bit-identical."""
+        activations differently and are not bit-identical.
+        ``inputs`` may be an ops.I8Pixels (the pixel operand another conv's epilogue wrote): it is multiplied as it is.
+        ``out_pixels=True``: the result is the NEXT conv's ops.I8Pixels, written by the product's own epilogue
+        (ops.i8_conv2d_quantize) after ``activation`` (None or "relu") and ``affine = (g, h)`` (``bn_affine``), in the order
+        ``affine_first`` says; byte for byte ``ops.i8_pixels_quantize`` of that result.  Without it an epilogue is refused."""
         _check_max_lines(max_lines)
+        if not out_pixels and (activation is not None or affine is not None or affine_first):
+            raise ValueError(f"{self.name}: the fp32 result takes no epilogue (activation={activation!r}, affine, affine_first): apply "
+                             "it to the result, or ask for out_pixels=True")
+        direct = isinstance(inputs, ops.I8Pixels) or out_pixels
         if not self.built:
+            if isinstance(inputs, ops.I8Pixels):
+                raise ValueError(f"{self.name}: the layer is not built yet (no kernel to pack)")
             self.build(tuple(inputs.shape), device=inputs.device)
         with torch.no_grad():
             operand = self.i8_direct_operand()
             qb = self.nested_q_b_layer(self.b) if self._has_bias else None
-            return self._direct_conv(inputs, operand, qb, max_lines)
+            if not direct:
+                return self._direct_conv(inputs, operand, qb, max_lines)
+            return self._direct_step(inputs, operand, qb, max_lines, out_pixels, activation, affine, affine_first)
 
 
 class CustomConv2DLayer(_ConvBase):
@@ -1325,13 +1371,28 @@ class i8_hardware(_matrix_hardware):
     (``i8_operand(int4=True)``: half the weight bytes, the same bits) and is listed in ``int4_layers``; every other layer that
     switches keeps its byte operand.  It combines with ``convs``, ``fused``, ``offsets`` and ``emulate`` (which multiplies no
     operand and lists none); with ``direct`` the direct convs keep their own per-tap byte operand (a 4-bit one is not built).
-    Without ``int4`` (the default) nothing changes."""
+    Without ``int4`` (the default) nothing changes.
+    ``fused_convs=True`` (with ``convs=True, direct=True``; the model in eval mode on entry): a module of ``model`` that states conv
+    chains as ``i8_conv_chains()`` -- lists of (conv, activation, BatchNorm2d or None, affine_first), as models.CIFARCNN states its
+    three conv -> relu -> BN -> conv pairs -- evaluates each chain whose layers pass ``i8_direct_eligible`` through
+    ``i8_conv_chain`` in eval mode: every conv but the last writes the next conv's pixel operand from its own epilogue
+    (ops.i8_conv2d_quantize), the BatchNorm folded to ``bn_affine``'s ``(g, h)`` on entry, and no fp32 activation exists between
+    them.  ``fused_conv_layers`` lists the convs with such an epilogue.  The outputs differ from ``fused_convs=False`` by
+    roundings: ``aff`` is not torch's BatchNorm kernel bit for bit, and an ulp can move a code.  Refused without ``direct`` or with
+    ``emulate``.  Without it (the default) nothing changes."""
 
     _family, _dense_eligible = _I8, staticmethod(i8_hardware_eligible)
 
     def __init__(self, model: nn.Module, act_block=0, emulate=False, convs=False, fused=False, offsets=False, direct=False,
-                 int4=False):
+                 int4=False, fused_convs=False):
         self.direct, self.direct_layers = bool(direct), []
+        self.fused_convs, self.fused_conv_layers, self._fused_conv_modules = bool(fused_convs), [], []
+        if self.fused_convs and not (convs and direct):
+            raise ValueError("i8_hardware: fused_convs=True needs convs=True and direct=True: the epilogue writes the pixel operand of "
+                             "the direct int8 convolution")
+        if self.fused_convs and emulate:
+            raise ValueError("i8_hardware: emulate=True with fused_convs=True: the emulated path is the yardstick of the unfused path "
+                             "and has no pixel-operand epilogue")
         self.int4, self.int4_layers = bool(int4), []
         self.offsets = bool(offsets)
         self._opt_in = {"offsets": True} if self.offsets else {}
@@ -1368,9 +1429,39 @@ class i8_hardware(_matrix_hardware):
             dense = [m for m in self.layers if isinstance(m, CustomDenseLayer)]
             convs = [m for m in self.layers if not isinstance(m, CustomDenseLayer)] + direct
             self.layers = dense + sorted(convs, key=lambda m: order[id(m)])
+        if self.fused_convs:
+            self._enter_fused_convs()
         return self
 
+    def _enter_fused_convs(self):
+        """A module that states conv chains (``i8_conv_chains()``: lists of (conv, activation, BatchNorm2d or (g, h) or None,
+        affine_first)) gets, per chain whose layers all pass ``i8_direct_eligible``, the chain with its affines as ``(g, h)`` --
+        None for a chain that cannot fuse -- and the chain's layers their operands."""
+        self.fused_conv_layers, self._fused_conv_modules = [], []
+        with torch.no_grad():
+            for mod in self.model.modules():
+                stated = mod.i8_conv_chains() if callable(getattr(mod, "i8_conv_chains", None)) else []
+                parked = []
+                for chain in stated:
+                    ok = len(chain) > 1 and all(i8_direct_eligible(c) and act in ops.MX_ACTIVATIONS for c, act, _, _ in chain) \
+                        and all(c.filters <= ops.I8_CONV_QUANT_MAX_FILTERS for c, _, _, _ in chain[:-1])
+                    parked.append([(c, act, bn_affine(aff) if isinstance(aff, nn.BatchNorm2d) else aff, first)
+                                   for c, act, aff, first in chain] if ok else None)
+                if any(chain is not None for chain in parked):
+                    for chain in filter(None, parked):
+                        for c, _, _, _ in chain:
+                            c._i8_chain_hw = c._i8_direct_hw or (c.i8_direct_operand(), c.nested_q_b_layer(c.b).detach() if c._has_bias else None)
+                        self.fused_conv_layers += [c for c, _, _, _ in chain[:-1]]
+                    mod._i8_fused_convs = parked
+                    self._fused_conv_modules.append(mod)
+
     def __exit__(self, *exc):
+        for mod in self._fused_conv_modules:
+            mod._i8_fused_convs = None
+            for chain in filter(None, mod.i8_conv_chains()):
+                for c, _, _, _ in chain:
+                    c._i8_chain_hw = None
+        self._fused_conv_modules = []
         for m in self.direct_layers:
             m._i8_direct_hw = None
         return super().__exit__(*exc)
@@ -1443,6 +1534,62 @@ def i8_dense_chain(x, chain, act_block=64, offsets=False, int4=False):
         opt_in["int4"] = True
     return _dense_chain("i8_dense_chain", _I8, "int8", lambda layer: layer._check_i8(**opt_in),
                         lambda: ops.check_i8_block(act_block), x, chain, (act_block,), ops.I8_OUT_BLOCK, **opt_in)
+
+
+def bn_affine(bn: nn.BatchNorm2d):
+    """``(g, h)``, float32 ``(C,)`` each, of an eval-mode ``BatchNorm2d``: ``bn(v) = v g + h`` with ``g = gamma / sqrt(var + eps)`` and
+    ``h = beta - mean g``, computed in float64 and rounded once -- the affine of ops.i8_conv2d_quantize's epilogue.  (torch's own
+    eval-mode kernel rounds differently: the two agree to an ulp or so, not bit for bit.)"""
+    if not isinstance(bn, nn.BatchNorm2d) or bn.training or bn.running_mean is None or bn.running_var is None:
+        raise ValueError("bn_affine: needs a BatchNorm2d in eval mode with running statistics")
+    with torch.no_grad():
+        one = torch.ones_like(bn.running_var, dtype=torch.float64)
+        gamma = bn.weight.double() if bn.weight is not None else one
+        beta = bn.bias.double() if bn.bias is not None else 0.0 * one
+        g = gamma / torch.sqrt(bn.running_var.double() + bn.eps)
+        return g.float(), (beta - bn.running_mean.double() * g).float()
+
+
+def i8_conv_chain(x, chain, max_lines=None):
+    """``chain`` = [(conv, activation, affine, affine_first), ...]: conv layers applied one after the other as direct int8
+    convolutions, under ``no_grad``.  ``x`` is quantised once per pixel; every layer but the last goes through
+    ops.i8_conv2d_quantize, whose epilogue applies ``activation`` (None or "relu") and ``affine`` (None or ``(g, h)``, ``bn_affine``)
+    -- ``affine_first`` False: relu then affine, True: affine then relu -- and writes the next conv's pixel operand; the last goes
+    through ops.i8_conv2d to fp32 and takes no epilogue.  Bit for bit ``call_i8_direct`` -> relu -> ``.mul(g)`` -> ``.add(h)`` ->
+    ``call_i8_direct`` ..., without the fp32 activations and their launches.  A batch whose lines exceed the launch limit (or
+    ``max_lines``) is cut into runs of whole images; the result does not depend on the cut.  Inside ``i8_hardware(fused_convs=True)``
+    the operands parked on its entry are used, otherwise they are built here.  ValueError naming the reason for a layer that cannot
+    take the path (``i8_direct_eligible``), more than 512 filters on a layer with an epilogue, or an epilogue on the last layer."""
+    fn = "i8_conv_chain"
+    chain = [tuple(step) for step in chain]
+    _check_max_lines(max_lines)
+    if not chain:
+        raise ValueError(f"{fn}: the chain is empty")
+    for k, step in enumerate(chain):
+        if len(step) != 4:
+            raise ValueError(f"{fn}: step {k} must be (conv, activation, affine, affine_first), got {len(step)} entries")
+        layer, activation, affine, affine_first = step
+        if not isinstance(layer, _ConvBase):
+            raise ValueError(f"{fn}: layer {k} is a {type(layer).__name__}: only conv layers run as direct int8 convolutions")
+        try:
+            layer._check_i8_direct()
+            ops.check_mx_activation(activation)
+        except ValueError as e:
+            raise ValueError(f"{fn}: {layer.name}: {e}") from None
+        if k == len(chain) - 1:
+            if activation is not None or affine is not None or affine_first:
+                raise ValueError(f"{fn}: {layer.name}: the last layer writes fp32 and takes no epilogue (got activation={activation!r}, "
+                                 f"affine {'given' if affine is not None else 'None'}): apply it to the result")
+        elif layer.filters > ops.I8_CONV_QUANT_MAX_FILTERS:
+            raise ValueError(f"{fn}: {layer.name}: {layer.filters} filters: the epilogue holds a whole output row in one thread block, "
+                             f"at most {ops.I8_CONV_QUANT_MAX_FILTERS}")
+    with torch.no_grad():
+        a = x
+        for k, (layer, activation, affine, affine_first) in enumerate(chain):
+            hw = layer._i8_chain_hw
+            operand, qb = hw if hw is not None else (layer.i8_direct_operand(), layer.nested_q_b_layer(layer.b) if layer._has_bias else None)
+            a = layer._direct_step(a, operand, qb, max_lines, k < len(chain) - 1, activation, affine, affine_first)
+        return a
 
 
 def quantized_tensors(model: nn.Module):

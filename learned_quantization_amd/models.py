@@ -33,7 +33,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .layers import CustomConv2DLayer, CustomDenseLayer, RandomNormal, i8_dense_chain, l2, mx_dense_chain
+from .layers import CustomConv2DLayer, CustomDenseLayer, RandomNormal, i8_conv_chain, i8_dense_chain, l2, mx_dense_chain
 from .losses import softmax
 
 
@@ -129,11 +129,19 @@ class CIFARCNN(nn.Module):
         if device is not None:
             self.to(device)
 
+    def i8_conv_chains(self):
+        """The three conv -> relu -> BN -> conv pairs as layers.i8_conv_chain takes them (the BatchNorm stands for its affine)."""
+        return [[(self.convs[k], "relu", self.bns[k], False), (self.convs[k + 1], None, None, False)] for k in (0, 2, 4)]
+
     def forward(self, x):
+        fused = getattr(self, "_i8_fused_convs", None)             # inside layers.i8_hardware(..., fused_convs=True)
         for blk in range(3):
-            for j in range(2):
-                k = 2 * blk + j
-                x = self.bns[k](F.relu(self.convs[k](x)))      # conv -> relu -> BN (experiment.py:309-311)
+            if fused is not None and fused[blk] is not None and not self.training:
+                x = self.bns[2 * blk + 1](F.relu(i8_conv_chain(x, fused[blk])))
+            else:
+                for j in range(2):
+                    k = 2 * blk + j
+                    x = self.bns[k](F.relu(self.convs[k](x)))      # conv -> relu -> BN (experiment.py:309-311)
             x = self.drops[blk](F.max_pool2d(x, 2))
         x = torch.flatten(x.permute(0, 2, 3, 1), 1)           # Keras flattens NHWC
         x = self.drop_dense(self.bn_dense(F.relu(self.dense_1(x))))

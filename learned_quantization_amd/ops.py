@@ -1104,6 +1104,7 @@ def i8_operand_im2col(x: torch.Tensor, kernel_size, strides=(1, 1), padding=(0, 
 
 # --------------------------------------------------------------------------- the direct int8 convolution (no im2col matrix)
 I8_DIRECT_MAX_CHANNELS = 65536       # a tap's int32 sum over the channels stays exact (include/lq_hip.h)
+I8_CONV_QUANT_MAX_FILTERS = 512      # lq_i8_conv2d_quantize: a whole output row in one thread block (include/lq_hip.h)
 
 
 class I8Pixels(NamedTuple):
@@ -1198,14 +1199,8 @@ def i8_conv_kernel_pack(kernel: torch.Tensor, scale: torch.Tensor, qmin: int, qm
     return I8ConvKernel(codes, scales, co, ci, (kh, kw))
 
 
-def i8_conv2d(pixels: I8Pixels, kernel: I8ConvKernel, bias: Optional[torch.Tensor] = None, strides=(1, 1), padding=(0, 0, 0, 0),
-              out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """The convolution of a pixel operand with a packed kernel on the int8 matrix instruction, ``Y (B OH OW, co)`` in fp32 -- NHWC
-    once reshaped -- bit for bit the definition of include/lq_hip.h, lq_i8_conv2d: per tap an exact int32 sum over the channels
-    under that pixel's scale, the filter's scale after the last tap, then the bias.  The extents come from the operands;
-    ``padding`` is (top, bottom, left, right).  ``out``: a float32 matrix to write into; its row stride is the leading dimension.
-    One launch, no im2col matrix."""
-    import ctypes
+def _check_i8_conv_operands(pixels: I8Pixels, kernel: I8ConvKernel):
+    """The buffer checks of ``i8_conv2d`` and ``i8_conv2d_quantize``; the operands' device."""
     B, C, H, W = (int(d) for d in pixels.shape)
     if C != kernel.channels:
         raise ValueError(f"the input has {C} channels and the kernel {kernel.channels}")
@@ -1223,6 +1218,18 @@ def i8_conv2d(pixels: I8Pixels, kernel: I8ConvKernel, bias: Optional[torch.Tenso
     for name, t in (("pixels.codes", pixels.codes), ("pixels.scales", pixels.scales), ("kernel.codes", kernel.codes), ("kernel.scales", kernel.scales)):
         if not t.is_cuda or t.device != dev or (dev.index is not None and dev.index != torch.cuda.current_device()):
             raise RuntimeError(f"{name} is on {t.device}: both operands must be on the current HIP device; there is no CPU fallback")
+    return dev
+
+
+def i8_conv2d(pixels: I8Pixels, kernel: I8ConvKernel, bias: Optional[torch.Tensor] = None, strides=(1, 1), padding=(0, 0, 0, 0),
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The convolution of a pixel operand with a packed kernel on the int8 matrix instruction, ``Y (B OH OW, co)`` in fp32 -- NHWC
+    once reshaped -- bit for bit the definition of include/lq_hip.h, lq_i8_conv2d: per tap an exact int32 sum over the channels
+    under that pixel's scale, the filter's scale after the last tap, then the bias.  The extents come from the operands;
+    ``padding`` is (top, bottom, left, right).  ``out``: a float32 matrix to write into; its row stride is the leading dimension.
+    One launch, no im2col matrix."""
+    import ctypes
+    dev = _check_i8_conv_operands(pixels, kernel)
     lib = _hip.load()
     g = _conv_geom(pixels.shape, (0, 0, 0, 0), kernel.kernel_size, strides, padding)
     M = _geom_dims(lib, g)[0]
@@ -1231,6 +1238,40 @@ def i8_conv2d(pixels: I8Pixels, kernel: I8ConvKernel, bias: Optional[torch.Tenso
                                 _hip.ptr(bias), _hip.ptr(out), ldy, ctypes.byref(g), kernel.filters, _hip.stream_ptr(out.device)),
                "lq_i8_conv2d")
     return out
+
+
+def i8_conv2d_quantize(pixels: I8Pixels, kernel: I8ConvKernel, bias: Optional[torch.Tensor] = None, strides=(1, 1), padding=(0, 0, 0, 0),
+                       activation=None, affine=None, affine_first: bool = False) -> I8Pixels:
+    """The pixel operand of the NEXT conv, written by the convolution's own epilogue (include/lq_hip.h, lq_i8_conv2d_quantize): byte
+    for byte ``i8_pixels_quantize`` of ``v`` seen as ``(B, co, OH, OW)``, where ``v = aff(act(Y))`` (``affine_first=False``: conv,
+    relu, BatchNorm) or ``v = act(aff(Y))`` (``affine_first=True``), ``Y`` is ``i8_conv2d``'s result bit for bit and ``aff(v) = v *
+    g + h`` with ``affine = (g, h)``, float32 ``(co,)`` each, the product and the sum rounding separately.  One launch; no fp32
+    matrix.  ``co`` above 512 is refused."""
+    import ctypes
+    act = check_mx_activation(activation)
+    dev = _check_i8_conv_operands(pixels, kernel)
+    co = kernel.filters
+    g_, h_ = (None, None) if affine is None else affine
+    bias = _matrix_output(0, co, dev, bias, fp32_out=False)[0]
+    post = []
+    for name, t in (("affine[0]", g_), ("affine[1]", h_)):
+        if affine is not None:
+            t = _hip.require_device_f32(t, name)
+            if tuple(t.shape) != (co,):
+                raise ValueError(f"{name} must have shape ({co},), got {tuple(t.shape)}")
+        post.append(t)
+    lib = _hip.load()
+    g = _conv_geom(pixels.shape, (0, 0, 0, 0), kernel.kernel_size, strides, padding)
+    _, _, OH, OW = _geom_dims(lib, g)
+    B = int(pixels.shape[0])
+    cb, _ = i8_pixels_bytes(B, co, OH, OW)
+    codes = torch.empty((B, OH, OW, cb // (B * OH * OW)), dtype=torch.uint8, device=dev)
+    scales = torch.empty((B, OH, OW), dtype=torch.float32, device=dev)
+    _hip.check(lib.lq_i8_conv2d_quantize(_hip.ptr(pixels.codes), _hip.ptr(pixels.scales), _hip.ptr(kernel.codes), _hip.ptr(kernel.scales),
+                                         _hip.ptr(bias), ctypes.byref(g), co, _hip.ptr(post[0]), _hip.ptr(post[1]), act,
+                                         int(bool(affine_first)), _hip.ptr(codes), _hip.ptr(scales), _hip.stream_ptr(dev)),
+               "lq_i8_conv2d_quantize")
+    return I8Pixels(codes, scales, (B, co, OH, OW))
 
 
 STATS_MAX_BINS = 4096   # include/lq_hip.h, lq_group_stats: the widest range whose codes it bins

@@ -635,6 +635,12 @@ def build_parser():
                          "input quantised once per pixel, no im2col matrix) and add i8_eval_direct_layers, "
                          "i8_eval_direct_im2col_layers (the convs that stay on the im2col path), i8_eval_direct_accuracy and "
                          "i8_eval_direct_max_logit_diff (the model's outputs against the emulated path) to the result line")
+    ap.add_argument("--i8-eval-fused-convs", action="store_true",
+                    help="with --i8-eval --i8-eval-convs --i8-eval-direct: evaluate once more under layers.i8_hardware(convs=True, "
+                         "direct=True, fused_convs=True) (conv -> relu -> BatchNorm -> conv pairs through layers.i8_conv_chain: the "
+                         "first conv's epilogue writes the second's pixel operand) and add i8_eval_fused_conv_layers, "
+                         "i8_eval_fused_conv_accuracy and i8_eval_fused_conv_max_logit_diff (the model's outputs against the unfused "
+                         "direct path; not expected to be 0.0: the folded BatchNorm rounds differently from torch's) to the result line")
     ap.add_argument("--i8-eval-fused", action="store_true",
                     help="with --i8-eval --i8-eval-act-block 64: evaluate once more under layers.i8_hardware(fused=True) (the Dense "
                          "tail through layers.i8_dense_chain: relu and the next operand's quantisation, per row and block of 64, in "
@@ -653,7 +659,7 @@ def build_parser():
 
 
 @torch.no_grad()
-def i8_eval(model, x, y, act_block=0, convs=False, fused=False, offsets=False, direct=False, int4=False):
+def i8_eval(model, x, y, act_block=0, convs=False, fused=False, offsets=False, direct=False, int4=False, fused_convs=False):
     """One evaluation of ``model`` on (x, y) under layers.i8_hardware, one under its ``emulate=True`` yardstick and one of the
     fake-quantised model as it stands: a dict of the three accuracies and the largest |difference| of the outputs of the last Dense
     layer that took the path (the logits of the MNIST model) between the hardware path and each of the other two.  ValueError for
@@ -666,7 +672,10 @@ def i8_eval(model, x, y, act_block=0, convs=False, fused=False, offsets=False, d
     under ``i8_hardware(convs=True, direct=True)`` and one under its emulation: the conv layers on the direct int8 convolution, those
     left on the im2col path, the accuracy, and the largest |difference| of the model's outputs between the two.  ``int4=True``
     adds an evaluation under ``i8_hardware(int4=True)`` (with ``convs`` as given): the number of layers that took the packed 4-bit
-    operand, the accuracy, and the largest |difference| of the model's outputs from the byte operands' (the same bits: 0.0)."""
+    operand, the accuracy, and the largest |difference| of the model's outputs from the byte operands' (the same bits: 0.0).
+    ``fused_convs=True`` (with ``convs`` and ``direct``) adds an evaluation under ``i8_hardware(convs=True, direct=True,
+    fused_convs=True)``: the convs whose epilogue writes the next conv's pixel operand, the accuracy, and the largest |difference|
+    of the model's outputs from the unfused direct path's (reported, not expected to be 0.0)."""
     was_training = model.training
     model.eval()
     acc, logits = [], []
@@ -724,6 +733,18 @@ def i8_eval(model, x, y, act_block=0, convs=False, fused=False, offsets=False, d
             fields.update({"i8_eval_direct_layers": n_direct, "i8_eval_direct_im2col_layers": n_im2col,
                            "i8_eval_direct_accuracy": float((outs[0].argmax(1) == y).float().mean()),
                            "i8_eval_direct_max_logit_diff": float((outs[0] - outs[1]).abs().max())})
+        if convs and direct and fused_convs:
+            outs = []
+            for fc in (True, False):
+                with L.i8_hardware(model, probe.act_block, convs=True, offsets=offsets, direct=True, fused_convs=fc) as hwf:
+                    if fc and not hwf.fused_conv_layers:
+                        raise ValueError("i8_eval: fused_convs=True needs a model that states conv chains (i8_conv_chains(), as "
+                                         "models.CIFARCNN does) of convs that can run as direct int8 convolutions")
+                    if fc:
+                        n_fused_convs = len(hwf.fused_conv_layers)
+                    outs.append(model(x))
+            fields.update({"i8_eval_fused_conv_layers": n_fused_convs, "i8_eval_fused_conv_accuracy": float((outs[0].argmax(1) == y).float().mean()),
+                           "i8_eval_fused_conv_max_logit_diff": float((outs[0] - outs[1]).abs().max())})
         if int4:
             outs = []
             for i4 in (True, False):
@@ -821,6 +842,8 @@ def main(argv=None):
     if args.i8_eval_direct and not args.i8_eval_convs:
         ap.error("--i8-eval-direct needs --i8-eval --i8-eval-convs: it sends eligible conv layers of that evaluation down the direct "
                  "int8 convolution")
+    if args.i8_eval_fused_convs and not args.i8_eval_direct:
+        ap.error("--i8-eval-fused-convs needs --i8-eval --i8-eval-convs --i8-eval-direct: it fuses pairs of direct int8 convolutions")
     if args.i8_eval_fused and not args.i8_eval:
         ap.error("--i8-eval-fused needs --i8-eval: it compares the fused Dense tail with the unfused hardware path")
     if args.i8_eval_fused and args.i8_eval_act_block != 64:
@@ -894,7 +917,7 @@ def main(argv=None):
     quant_stats = L.quant_stats(tr.model) if args.quant_stats and rank == 0 else None      # after the clock has stopped
     mx_stats = L.mx_quant_stats(tr.model) if args.mx_stats and rank == 0 else None
     mx_eval_fields = mx_eval(tr.model, *batches[0], act_format=args.mx_eval, fused=args.mx_eval_fused, convs=args.mx_eval_convs) if args.mx_eval is not None and rank == 0 else None
-    i8_eval_fields = i8_eval(tr.model, *batches[0], act_block=args.i8_eval_act_block, convs=args.i8_eval_convs, fused=args.i8_eval_fused, offsets=args.i8_eval_offsets, direct=args.i8_eval_direct, int4=args.i8_eval_int4) if args.i8_eval and rank == 0 else None
+    i8_eval_fields = i8_eval(tr.model, *batches[0], act_block=args.i8_eval_act_block, convs=args.i8_eval_convs, fused=args.i8_eval_fused, offsets=args.i8_eval_offsets, direct=args.i8_eval_direct, int4=args.i8_eval_int4, fused_convs=args.i8_eval_fused_convs) if args.i8_eval and rank == 0 else None
     if rank == 0:
         n_q = sum(p.numel() for l in tr.custom_layers for p in l._regularized())
         print(json.dumps({

@@ -471,6 +471,47 @@ int lq_mx_gemm_quantize(const void* a_codes, const void* a_scales, int a_format,
                         const float* bias /* may be NULL */, int activation, int out_format, int method, void* out_codes,
                         void* out_scales, int64_t M, int64_t N, int64_t K, void* stream);
 
+/* ---- packed fp6 MX operands (LQ_ELEM_FP6_E2M3, LQ_ELEM_FP6_E3M2) ----
+ * The instruction takes 6-bit data too (format immediates 2 and 3), in fragments of 6 registers.  The entry points above keep
+ * refusing an fp6 format; these are the fp6 operand's own, and lq_mx6_gemm multiplies it with an operand of any of the five formats.
+ * An fp6 operand is cut into the same tiles (16 lines by 128 K; LT, KT, KG as above) and its SCALE buffer is the one above, bit for
+ * bit: [LT][KG][64][4], the same bytes, padding byte 127 and idle bytes.  Its codes:
+ *   codes   [LT][KT][1536]     fragment `lane` of tile (lt, kt) holds line 16 lt + (lane & 15) and, with g = lane >> 4, the 32
+ *                              consecutive k = 32 g + j of K step kt (one MX block, as fp4).  The fragment is 192 bits = 24 bytes:
+ *                              element j occupies bits 6 j .. 6 j + 5, bit b of the fragment being bit (b & 7) of its byte b >> 3
+ *                              (read as little-endian dwords the 24 bytes are operand registers 0 .. 5; registers 6, 7 are zero).
+ *                              The 1536 bytes of a tile are two planes, so that a wave's two loads are aligned and contiguous:
+ *                                bytes 0 .. 1023      [64 lanes][16]   bytes 0 .. 15 of each lane's fragment
+ *                                bytes 1024 .. 1535   [64 lanes][8]    bytes 16 .. 23 of each lane's fragment
+ *   code_bytes = LT * KT * 1536 (0.75 of an fp8 operand's), scale_bytes = LT * KG * 256.  Lines past L and elements past K hold code 0
+ *   under byte 127.
+ * The lane map -- lane l supplies line l & 15 and block l >> 4 of the step, the scale byte of lane l applies to block l >> 4, the
+ * bit order above -- is the one guessed from the fp4 map, held to the device by the one-term sweep and the exact products of
+ * tests/test_gpu_mx6.py ("fp6 operands", records what was guessed and what was found).
+ *
+ * lq_mx6_operand_bytes / _pack / _quantize / _decode: lq_mx_operand_*'s arguments, geometry, axes, scale rule and element step, for
+ * a format that is one of the two fp6 formats; the code of every element is bit for bit the code view of lq_fq_forward_mx.
+ * lq_mx6_gemm: lq_mx_gemm's arguments and definition (the products and the sum of a K step are the instruction's, the steps
+ * accumulate in ascending K, the bias is one fp32 addition) for the 16 format pairs with at least one fp6 side: an fp6 side is read
+ * in the layout above, any other side in lq_mx_operand's.
+ * lq_mx6_gemm_quantize: lq_mx_gemm_quantize for those 16 pairs; out_format is LQ_ELEM_FP8_E4M3, LQ_ELEM_FP8_E5M2 or
+ * LQ_ELEM_FP4_E2M1, written in lq_mx_operand's layout, byte for byte what lq_mx6_gemm -> act -> lq_mx_operand_quantize writes.
+ * LQ_EINVAL before any launch: everything the lq_mx_* counterpart refuses (NULL pointers, non-positive extents, L * K >= 2^31,
+ * gs != 32, fp32 scales, a bad method or activation, ldy < N); for the operand calls a format that is not fp6 (fp4 and fp8 operands
+ * are lq_mx_operand_*'s); for the products a pair without an fp6 side (that product is lq_mx_gemm's); out_format fp6 (not built: a
+ * row's block lies two elements to a lane across 16 lanes, and packing 6-bit fields across lanes is a piece of its own).  LQ_EALIGN
+ * as above.  Each call enqueues ONE launch (capturable), allocates nothing and writes exactly its stated bytes.  */
+int lq_mx6_operand_bytes(int format, int64_t L, int64_t K, size_t* code_bytes, size_t* scale_bytes);
+int lq_mx6_operand_pack(const float* P, const float* s, int format, int scale_format, int64_t R, int64_t C, int axis, int64_t gs,
+                        void* codes, void* scales, void* stream);
+int lq_mx6_operand_quantize(const float* X, int format, int method, int64_t M, int64_t K, void* codes, void* scales, void* stream);
+int lq_mx6_operand_decode(const void* codes, const void* scales, int format, int64_t L, int64_t K, float* out, void* stream);
+int lq_mx6_gemm(const void* a_codes, const void* a_scales, int a_format, const void* b_codes, const void* b_scales, int b_format,
+                const float* bias /* may be NULL */, float* Y, int64_t M, int64_t N, int64_t K, int64_t ldy, void* stream);
+int lq_mx6_gemm_quantize(const void* a_codes, const void* a_scales, int a_format, const void* b_codes, const void* b_scales, int b_format,
+                         const float* bias /* may be NULL */, int activation, int out_format, int method, void* out_codes,
+                         void* out_scales, int64_t M, int64_t N, int64_t K, void* stream);
+
 /* lq_mx_operand_im2col: the A operand of a convolution run as a GEMM, gathered from the input in one launch -- the im2col matrix
  * never exists in fp32.  With OH = (H + pad_top + pad_bottom - KH) / stride_h + 1 (rounded down; OW likewise from W, the left and
  * right pads, KW and stride_w), M = B * OH * OW lines and K = C * KH * KW:

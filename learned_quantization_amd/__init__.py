@@ -16,6 +16,7 @@ from .ops import (difference_term, fq_backward_clip, fq_backward_group, fq_forwa
                   fq_backward_group_affine, fq_forward_group_affine, scale_init_group_minmax, GroupStats, group_stats, summarize_stats,
                   ELEMENT_FORMATS, check_element_format, fq_backward_mx, fq_forward_mx, scale_init_mx, MxStats, mx_stats, summarize_mx_stats,
                   MxOperand, mx_gemm, mx_gemm_quantize, mx_im2col_dims, mx_operand_decode, mx_operand_im2col, mx_operand_pack, mx_operand_quantize,
+                  MX6_OPERAND_FORMATS, Mx6Operand, mx6_operand_bytes, mx6_operand_pack, mx6_operand_quantize,
                   I8AffineOperand, I8Operand, check_i8_conv_operand_layer, check_i8_operand_layer, i8_gemm, i8_gemm_quantize, i8_operand_bytes, i8_operand_decode, i8_operand_im2col, i8_operand_pack, i8_operand_quantize,
                   I4Operand, check_i4_operand_layer, i4_operand_bytes, i4_operand_pack,
                   I8ConvKernel, I8Pixels, check_i8_direct_layer, i8_conv2d, i8_conv2d_quantize, i8_conv_kernel_pack, i8_pixels_quantize,

@@ -81,6 +81,13 @@ SIGNATURES = {
     "lq_mx_gemm": (_c_int, [_c_p, _c_p, _c_int, _c_p, _c_p, _c_int, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p]),
     "lq_mx_gemm_quantize": (_c_int, [_c_p, _c_p, _c_int, _c_p, _c_p, _c_int, _c_p, _c_int, _c_int, _c_int, _c_p, _c_p, _c_i64, _c_i64,
                                      _c_i64, _c_p]),
+    "lq_mx6_operand_bytes": (_c_int, [_c_int, _c_i64, _c_i64, ctypes.POINTER(_c_sz), ctypes.POINTER(_c_sz)]),
+    "lq_mx6_operand_pack": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_i64, _c_i64, _c_int, _c_i64, _c_p, _c_p, _c_p]),
+    "lq_mx6_operand_quantize": (_c_int, [_c_p, _c_int, _c_int, _c_i64, _c_i64, _c_p, _c_p, _c_p]),
+    "lq_mx6_operand_decode": (_c_int, [_c_p, _c_p, _c_int, _c_i64, _c_i64, _c_p, _c_p]),
+    "lq_mx6_gemm": (_c_int, [_c_p, _c_p, _c_int, _c_p, _c_p, _c_int, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p]),
+    "lq_mx6_gemm_quantize": (_c_int, [_c_p, _c_p, _c_int, _c_p, _c_p, _c_int, _c_p, _c_int, _c_int, _c_int, _c_p, _c_p, _c_i64, _c_i64,
+                                      _c_i64, _c_p]),
     "lq_i8_operand_bytes": (_c_int, [_c_i64, _c_i64, _c_i64, ctypes.POINTER(_c_sz), ctypes.POINTER(_c_sz)]),
     "lq_i8_operand_pack": (_c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_int, _c_i64, _c_i64, _c_int, _c_i64, _c_p, _c_p, _c_p]),
     "lq_i8_operand_quantize": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p]),

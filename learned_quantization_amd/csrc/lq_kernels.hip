@@ -15,6 +15,7 @@
 //   lq_scale_init.hpp   scales and offsets from the weights: absmax / LSQ / MSE / min-max on the group-wise unit shapes
 //   lq_mx.hpp           OCP microscaling element formats: the group-wise traversal bodies with a minifloat element step
 //   lq_mx_operand.hpp   packed MX operands in the block-scaled matrix instruction's fragment order: pack, dynamic quantize, decode
+//   lq_mx6_operand.hpp  the same for the two fp6 formats: 24-byte fragments in two planes per tile
 //   lq_mx_gemm.hpp      the GEMM of two packed operands on v_mfma_scale_f32_16x16x128_f8f6f4
 //   lq_i8_operand.hpp   packed int8 operands with fp32 scales per line and scale block: pack, dynamic quantize, decode
 //   lq_i4_operand.hpp   4-bit codes two to a byte as the B operand of the int8 GEMM: pack, decode
@@ -71,6 +72,7 @@
 #include "lq_group_stats.hpp"
 #include "lq_mx_stats.hpp"
 #include "lq_mx_operand.hpp"
+#include "lq_mx6_operand.hpp"
 #include "lq_mx_gemm.hpp"
 #include "lq_mx_conv.hpp"
 #include "lq_i8_operand.hpp"
@@ -1844,39 +1846,66 @@ struct MxOperandDims {
     size_t code_bytes, scale_bytes;
 };
 
-static int mx_operand_dims(const char* fn, int format, int64_t L, int64_t K, MxOperandDims& d) {
-    int rc = check_mx_operand_format(fn, format);
-    if (rc) return rc;
+// the extents checked, the tiles and the scale buffer: what does not depend on the element width; fb bytes per fragment
+static int mx_extents(const char* fn, int64_t L, int64_t K, int64_t fb, MxOperandDims& d) {
     if (L <= 0 || K <= 0) return fail(LQ_EINVAL, "%s: extents must be positive (L=%lld K=%lld)", fn, (long long)L, (long long)K);
     if ((double)L * (double)K >= 2147483648.0) return fail(LQ_EINVAL, "%s: L * K = %lld * %lld is not below 2^31", fn, (long long)L, (long long)K);
     d.LT = (L + kMxTileLines - 1) / kMxTileLines;
     d.KT = (K + kMxTileK - 1) / kMxTileK;
     d.KG = (d.KT + 3) / 4;
-    d.fb = format == LQ_ELEM_FP4_E2M1 ? 16 : 32;
-    d.code_bytes = (size_t)(d.LT * d.KT * 64 * d.fb);
+    d.fb = fb;
+    d.code_bytes = (size_t)(d.LT * d.KT * 64 * fb);
     d.scale_bytes = (size_t)(d.LT * d.KG * 256);
     return LQ_OK;
 }
 
-int lq_mx_operand_bytes(int format, int64_t L, int64_t K, size_t* code_bytes, size_t* scale_bytes) {
-    const char* fn = __func__;
+static int mx_operand_dims(const char* fn, int format, int64_t L, int64_t K, MxOperandDims& d) {
+    int rc = check_mx_operand_format(fn, format);
+    return rc ? rc : mx_extents(fn, L, K, format == LQ_ELEM_FP4_E2M1 ? 16 : 32, d);
+}
+
+// the fp6 operand (lq_mx6_operand.hpp): the same tiles and scale buffer, 24-byte fragments.  `side`: an operand of lq_mx6_gemm,
+// which may have any of the five formats -- the other three in lq_mx_operand.hpp's layout
+// Three outcomes.  An fp6 format: the extents of 24-byte fragments.  fp4 / fp8 where the operand itself must be fp6 (side = false:
+// bytes, pack, quantize, decode): refused as "not an fp6 format".  Everything else is mx_operand_dims' answer: the existing
+// layout for the fp4 / fp8 side of a product (side = true), "bad element format" for a number outside the five, either way.
+static int mx6_operand_dims(const char* fn, int format, int64_t L, int64_t K, MxOperandDims& d, bool side = false) {
+    if (!mx_is_fp6(format)) {
+        if (side || format < LQ_ELEM_FP4_E2M1 || format > LQ_ELEM_FP8_E5M2) return mx_operand_dims(fn, format, L, K, d);
+        return fail(LQ_EINVAL, "%s: element format %d is not an fp6 format: fp4 and fp8 operands are lq_mx_operand_*'s", fn, format);
+    }
+    return mx_extents(fn, L, K, kMx6FragBytes, d);      // 64 fragments of 24 bytes: kMx6TileBytes per tile
+}
+
+static int mx_operand_bytes(const char* fn, bool fp6, int format, int64_t L, int64_t K, size_t* code_bytes, size_t* scale_bytes) {
     if (!code_bytes || !scale_bytes) return fail(LQ_EINVAL, "%s: code_bytes or scale_bytes is NULL", fn);
     MxOperandDims d;
-    int rc = mx_operand_dims(fn, format, L, K, d);
+    int rc = fp6 ? mx6_operand_dims(fn, format, L, K, d) : mx_operand_dims(fn, format, L, K, d);
     if (rc) return rc;
     *code_bytes = d.code_bytes;
     *scale_bytes = d.scale_bytes;
     return LQ_OK;
 }
 
+int lq_mx_operand_bytes(int format, int64_t L, int64_t K, size_t* code_bytes, size_t* scale_bytes) {
+    return mx_operand_bytes(__func__, false, format, L, K, code_bytes, scale_bytes);
+}
+
+int lq_mx6_operand_bytes(int format, int64_t L, int64_t K, size_t* code_bytes, size_t* scale_bytes) {
+    return mx_operand_bytes(__func__, true, format, L, K, code_bytes, scale_bytes);
+}
+
 extern "C++" {      // templates inside the C-linkage block
 template <bool DYN, int METHOD, bool LINE_FAST>
-static int launch_mx_operand(const MxOperandParams& op, bool fp4, bool vec, const char* what, void* stream) {
+static int launch_mx_operand(const MxOperandParams& op, bool vec, const char* what, void* stream) {
     const int64_t threads = (int64_t)op.LT * kMxTileLines * op.KT * 4;
     const dim3 grid((unsigned)((threads + kBlock - 1) / kBlock)), block(kBlock);
     hipStream_t st = (hipStream_t)stream;
     constexpr bool kVecForm = !LINE_FAST;      // float4 loads need the blocks along the contiguous axis: axis 1 and quantize
-    if (fp4) {
+    if (op.mp.bits == 6) {
+        if (kVecForm && vec) hipLaunchKernelGGL((k_mx6_operand<DYN, METHOD, kVecForm, LINE_FAST>), grid, block, 0, st, op);
+        else hipLaunchKernelGGL((k_mx6_operand<DYN, METHOD, false, LINE_FAST>), grid, block, 0, st, op);
+    } else if (op.mp.bits == 4) {
         if (kVecForm && vec) hipLaunchKernelGGL((k_mx_operand<DYN, METHOD, true, kVecForm, LINE_FAST>), grid, block, 0, st, op);
         else hipLaunchKernelGGL((k_mx_operand<DYN, METHOD, true, false, LINE_FAST>), grid, block, 0, st, op);
     } else {
@@ -1905,6 +1934,42 @@ static void launch_mx_gemm_quantize_b(const MxGemmQuantParams& p, int b_format, 
     else if (b_format == LQ_ELEM_FP8_E4M3) launch_mx_gemm_quantize_o<FA, LQ_ELEM_FP8_E4M3>(p, out_fp4, grid, st);
     else launch_mx_gemm_quantize_o<FA, LQ_ELEM_FP8_E5M2>(p, out_fp4, grid, st);
 }
+
+// The 16 pairs of lq_mx6_gemm / lq_mx6_gemm_quantize, those with an fp6 side: f.run<FA, FB>() of the pair.  The other nine are
+// lq_mx_gemm's and are not instantiated a second time
+template <int FA, class F>
+static void mx6_dispatch_b(int b_format, const F& f) {
+    if (b_format == LQ_ELEM_FP6_E2M3) f.template run<FA, LQ_ELEM_FP6_E2M3>();
+    else if (b_format == LQ_ELEM_FP6_E3M2) f.template run<FA, LQ_ELEM_FP6_E3M2>();
+    else if constexpr (mx_is_fp6(FA)) {
+        if (b_format == LQ_ELEM_FP4_E2M1) f.template run<FA, LQ_ELEM_FP4_E2M1>();
+        else if (b_format == LQ_ELEM_FP8_E4M3) f.template run<FA, LQ_ELEM_FP8_E4M3>();
+        else f.template run<FA, LQ_ELEM_FP8_E5M2>();
+    }
+}
+template <class F>
+static void mx6_dispatch(int a_format, int b_format, const F& f) {
+    if (a_format == LQ_ELEM_FP6_E2M3) mx6_dispatch_b<LQ_ELEM_FP6_E2M3>(b_format, f);
+    else if (a_format == LQ_ELEM_FP6_E3M2) mx6_dispatch_b<LQ_ELEM_FP6_E3M2>(b_format, f);
+    else if (a_format == LQ_ELEM_FP4_E2M1) mx6_dispatch_b<LQ_ELEM_FP4_E2M1>(b_format, f);
+    else if (a_format == LQ_ELEM_FP8_E4M3) mx6_dispatch_b<LQ_ELEM_FP8_E4M3>(b_format, f);
+    else mx6_dispatch_b<LQ_ELEM_FP8_E5M2>(b_format, f);
+}
+struct Mx6GemmLaunch {
+    const MxGemmParams& p;
+    dim3 grid;
+    hipStream_t st;
+    template <int FA, int FB>
+    void run() const { hipLaunchKernelGGL((k_mx_gemm<FA, FB>), grid, dim3(kBlock), 0, st, p); }
+};
+struct Mx6GemmQuantizeLaunch {
+    const MxGemmQuantParams& p;
+    bool out_fp4;
+    dim3 grid;
+    hipStream_t st;
+    template <int FA, int FB>
+    void run() const { launch_mx_gemm_quantize_o<FA, FB>(p, out_fp4, grid, st); }
+};
 }  // extern "C++"
 
 static void mx_operand_fill(MxOperandParams& op, const MxOperandDims& d, int format, int64_t L, int64_t K, void* codes, void* scales) {
@@ -1919,9 +1984,8 @@ static void mx_operand_fill(MxOperandParams& op, const MxOperandDims& d, int for
     op.KG = (int32_t)d.KG;
 }
 
-int lq_mx_operand_pack(const float* P, const float* s, int format, int scale_format, int64_t R, int64_t C, int axis, int64_t gs,
-                       void* codes, void* scales, void* stream) {
-    const char* fn = __func__;
+static int mx_operand_pack(const char* fn, bool fp6, const float* P, const float* s, int format, int scale_format, int64_t R, int64_t C,
+                           int axis, int64_t gs, void* codes, void* scales, void* stream) {
     int rc = check_group(fn, R, C, axis, gs);
     if (rc) return rc;
     LQ_REQUIRE_PTR_FN(fn, P);
@@ -1932,7 +1996,7 @@ int lq_mx_operand_pack(const float* P, const float* s, int format, int scale_for
     if (gs != kMxBlockLen) return fail(LQ_EINVAL, "%s: group size %lld: the instruction's block is %d", fn, (long long)gs, kMxBlockLen);
     const int64_t L = axis == 0 ? C : R, K = axis == 0 ? R : C;
     MxOperandDims d;
-    if ((rc = mx_operand_dims(fn, format, L, K, d))) return rc;
+    if ((rc = fp6 ? mx6_operand_dims(fn, format, L, K, d) : mx_operand_dims(fn, format, L, K, d))) return rc;
     if ((rc = check_operand_buffers(fn, codes, scales, kMxScaleAlign))) return rc;
     MxOperandParams op{};
     mx_operand_fill(op, d, format, L, K, codes, scales);
@@ -1942,17 +2006,26 @@ int lq_mx_operand_pack(const float* P, const float* s, int format, int scale_for
     op.k_stride = axis == 0 ? C : 1;
     op.s_line_stride = axis == 0 ? 1 : op.nbk;      // [nb][C] | [R][nb]
     op.s_blk_stride = axis == 0 ? C : 1;
-    const bool fp4 = format == LQ_ELEM_FP4_E2M1;
-    if (axis == 0) return launch_mx_operand<false, kInitMxOcp, true>(op, fp4, false, "microscaling operand pack", stream);
-    return launch_mx_operand<false, kInitMxOcp, false>(op, fp4, C % 4 == 0 && aligned(P, 16), "microscaling operand pack", stream);
+    if (axis == 0) return launch_mx_operand<false, kInitMxOcp, true>(op, false, "microscaling operand pack", stream);
+    return launch_mx_operand<false, kInitMxOcp, false>(op, C % 4 == 0 && aligned(P, 16), "microscaling operand pack", stream);
 }
 
-int lq_mx_operand_quantize(const float* X, int format, int method, int64_t M, int64_t K, void* codes, void* scales, void* stream) {
-    const char* fn = __func__;
+int lq_mx_operand_pack(const float* P, const float* s, int format, int scale_format, int64_t R, int64_t C, int axis, int64_t gs,
+                       void* codes, void* scales, void* stream) {
+    return mx_operand_pack(__func__, false, P, s, format, scale_format, R, C, axis, gs, codes, scales, stream);
+}
+
+int lq_mx6_operand_pack(const float* P, const float* s, int format, int scale_format, int64_t R, int64_t C, int axis, int64_t gs,
+                        void* codes, void* scales, void* stream) {
+    return mx_operand_pack(__func__, true, P, s, format, scale_format, R, C, axis, gs, codes, scales, stream);
+}
+
+static int mx_operand_quantize(const char* fn, bool fp6, const float* X, int format, int method, int64_t M, int64_t K, void* codes,
+                               void* scales, void* stream) {
     LQ_REQUIRE_PTR_FN(fn, X);
     if (method != LQ_MX_INIT_OCP && method != LQ_MX_INIT_COVER) return fail(LQ_EINVAL, "%s: bad method %d", fn, method);
     MxOperandDims d;
-    int rc = mx_operand_dims(fn, format, M, K, d);
+    int rc = fp6 ? mx6_operand_dims(fn, format, M, K, d) : mx_operand_dims(fn, format, M, K, d);
     if (rc) return rc;
     if ((rc = check_operand_buffers(fn, codes, scales, kMxScaleAlign))) return rc;
     MxOperandParams op{};
@@ -1963,16 +2036,23 @@ int lq_mx_operand_quantize(const float* X, int format, int method, int64_t M, in
     op.ip.emax = kMxFormats[format].emax;
     op.ip.mm_frac = kMxFormats[format].mm_frac;
     op.ip.min_value = kOperandMinScale;
-    const bool fp4 = format == LQ_ELEM_FP4_E2M1;
     const bool vec = K % 4 == 0 && aligned(X, 16);
-    if (method == LQ_MX_INIT_OCP) return launch_mx_operand<true, kInitMxOcp, false>(op, fp4, vec, "microscaling operand quantize", stream);
-    return launch_mx_operand<true, kInitMxCover, false>(op, fp4, vec, "microscaling operand quantize", stream);
+    if (method == LQ_MX_INIT_OCP) return launch_mx_operand<true, kInitMxOcp, false>(op, vec, "microscaling operand quantize", stream);
+    return launch_mx_operand<true, kInitMxCover, false>(op, vec, "microscaling operand quantize", stream);
 }
 
-int lq_mx_operand_decode(const void* codes, const void* scales, int format, int64_t L, int64_t K, float* out, void* stream) {
-    const char* fn = __func__;
+int lq_mx_operand_quantize(const float* X, int format, int method, int64_t M, int64_t K, void* codes, void* scales, void* stream) {
+    return mx_operand_quantize(__func__, false, X, format, method, M, K, codes, scales, stream);
+}
+
+int lq_mx6_operand_quantize(const float* X, int format, int method, int64_t M, int64_t K, void* codes, void* scales, void* stream) {
+    return mx_operand_quantize(__func__, true, X, format, method, M, K, codes, scales, stream);
+}
+
+static int mx_operand_decode(const char* fn, bool fp6, const void* codes, const void* scales, int format, int64_t L, int64_t K, float* out,
+                             void* stream) {
     MxOperandDims d;
-    int rc = mx_operand_dims(fn, format, L, K, d);
+    int rc = fp6 ? mx6_operand_dims(fn, format, L, K, d) : mx_operand_dims(fn, format, L, K, d);
     if (rc) return rc;
     if ((rc = check_operand_buffers(fn, codes, scales, kMxScaleAlign))) return rc;
     LQ_REQUIRE_PTR_FN(fn, out);
@@ -1988,16 +2068,40 @@ int lq_mx_operand_decode(const void* codes, const void* scales, int format, int6
     dp.emin = kMxFormats[format].emin;
     dp.bits = kMxFormats[format].bits;
     const int64_t n = L * K;
-    hipLaunchKernelGGL(k_mx_operand_decode, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream, dp);
+    const dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
+    if (fp6) hipLaunchKernelGGL(k_mx6_operand_decode, grid, dim3(kBlock), 0, (hipStream_t)stream, dp);
+    else hipLaunchKernelGGL(k_mx_operand_decode, grid, dim3(kBlock), 0, (hipStream_t)stream, dp);
     return check_hip("microscaling operand decode");
 }
 
-int lq_mx_gemm(const void* a_codes, const void* a_scales, int a_format, const void* b_codes, const void* b_scales, int b_format,
-               const float* bias, float* Y, int64_t M, int64_t N, int64_t K, int64_t ldy, void* stream) {
-    const char* fn = __func__;
+int lq_mx_operand_decode(const void* codes, const void* scales, int format, int64_t L, int64_t K, float* out, void* stream) {
+    return mx_operand_decode(__func__, false, codes, scales, format, L, K, out, stream);
+}
+
+int lq_mx6_operand_decode(const void* codes, const void* scales, int format, int64_t L, int64_t K, float* out, void* stream) {
+    return mx_operand_decode(__func__, true, codes, scales, format, L, K, out, stream);
+}
+
+// the pair of a product: fp6 = false lq_mx_gemm's nine, fp6 = true the sixteen with an fp6 side
+static int mx_gemm_pair_dims(const char* fn, bool fp6, int a_format, int b_format, int64_t M, int64_t N, int64_t K, MxOperandDims& da,
+                             MxOperandDims& db) {
+    if (!fp6) {
+        int rc = mx_operand_dims(fn, a_format, M, K, da);
+        return rc ? rc : mx_operand_dims(fn, b_format, N, K, db);
+    }
+    int rc = mx6_operand_dims(fn, a_format, M, K, da, true);
+    if (rc || (rc = mx6_operand_dims(fn, b_format, N, K, db, true))) return rc;
+    if (!mx_is_fp6(a_format) && !mx_is_fp6(b_format))
+        return fail(LQ_EINVAL, "%s: neither operand has an fp6 format (%d, %d): that product is lq_mx_gemm's", fn, a_format, b_format);
+    return LQ_OK;
+}
+
+static int mx_gemm(const char* fn, bool fp6, const void* a_codes, const void* a_scales, int a_format, const void* b_codes,
+                   const void* b_scales, int b_format, const float* bias, float* Y, int64_t M, int64_t N, int64_t K, int64_t ldy,
+                   void* stream) {
     MxOperandDims da, db;
-    int rc = mx_operand_dims(fn, a_format, M, K, da);
-    if (rc || (rc = mx_operand_dims(fn, b_format, N, K, db))) return rc;
+    int rc = mx_gemm_pair_dims(fn, fp6, a_format, b_format, M, N, K, da, db);
+    if (rc) return rc;
     if ((rc = check_operand_buffers(fn, a_codes, a_scales, kMxScaleAlign))) return rc;
     if ((rc = check_operand_buffers(fn, b_codes, b_scales, kMxScaleAlign))) return rc;
     if ((rc = check_gemm_output(fn, bias, Y, ldy, M, N))) return rc;
@@ -2018,19 +2122,33 @@ int lq_mx_gemm(const void* a_codes, const void* a_scales, int a_format, const vo
     dim3 grid;
     if ((rc = gemm_grid(fn, (db.LT + 3) / 4, da.LT, M, grid))) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (a_format == LQ_ELEM_FP4_E2M1) launch_mx_gemm_b<LQ_ELEM_FP4_E2M1>(p, b_format, grid, st);
+    if (fp6) mx6_dispatch(a_format, b_format, Mx6GemmLaunch{p, grid, st});
+    else if (a_format == LQ_ELEM_FP4_E2M1) launch_mx_gemm_b<LQ_ELEM_FP4_E2M1>(p, b_format, grid, st);
     else if (a_format == LQ_ELEM_FP8_E4M3) launch_mx_gemm_b<LQ_ELEM_FP8_E4M3>(p, b_format, grid, st);
     else launch_mx_gemm_b<LQ_ELEM_FP8_E5M2>(p, b_format, grid, st);
     return check_hip("microscaling GEMM");
 }
 
-int lq_mx_gemm_quantize(const void* a_codes, const void* a_scales, int a_format, const void* b_codes, const void* b_scales, int b_format,
-                        const float* bias, int activation, int out_format, int method, void* out_codes, void* out_scales, int64_t M,
-                        int64_t N, int64_t K, void* stream) {
-    const char* fn = __func__;
+int lq_mx_gemm(const void* a_codes, const void* a_scales, int a_format, const void* b_codes, const void* b_scales, int b_format,
+               const float* bias, float* Y, int64_t M, int64_t N, int64_t K, int64_t ldy, void* stream) {
+    return mx_gemm(__func__, false, a_codes, a_scales, a_format, b_codes, b_scales, b_format, bias, Y, M, N, K, ldy, stream);
+}
+
+int lq_mx6_gemm(const void* a_codes, const void* a_scales, int a_format, const void* b_codes, const void* b_scales, int b_format,
+                const float* bias, float* Y, int64_t M, int64_t N, int64_t K, int64_t ldy, void* stream) {
+    return mx_gemm(__func__, true, a_codes, a_scales, a_format, b_codes, b_scales, b_format, bias, Y, M, N, K, ldy, stream);
+}
+
+static int mx_gemm_quantize(const char* fn, bool fp6, const void* a_codes, const void* a_scales, int a_format, const void* b_codes,
+                            const void* b_scales, int b_format, const float* bias, int activation, int out_format, int method,
+                            void* out_codes, void* out_scales, int64_t M, int64_t N, int64_t K, void* stream) {
     MxOperandDims da, db, dout;
-    int rc = mx_operand_dims(fn, a_format, M, K, da);
-    if (rc || (rc = mx_operand_dims(fn, b_format, N, K, db)) || (rc = mx_operand_dims(fn, out_format, M, N, dout))) return rc;
+    int rc = mx_gemm_pair_dims(fn, fp6, a_format, b_format, M, N, K, da, db);
+    if (rc) return rc;
+    if (fp6 && mx_is_fp6(out_format))
+        return fail(LQ_EINVAL, "%s: out_format %d: an fp6 operand-out epilogue is not built (a row's block lies two elements to a lane "
+                               "across 16 lanes; packing 6-bit fields across lanes is a piece of its own)", fn, out_format);
+    if ((rc = mx_operand_dims(fn, out_format, M, N, dout))) return rc;
     if (method != LQ_MX_INIT_OCP && method != LQ_MX_INIT_COVER) return fail(LQ_EINVAL, "%s: bad method %d", fn, method);
     if (activation != LQ_ACT_NONE && activation != LQ_ACT_RELU) return fail(LQ_EINVAL, "%s: bad activation %d", fn, activation);
     if ((rc = check_operand_buffers(fn, a_codes, a_scales, kMxScaleAlign))) return rc;
@@ -2064,10 +2182,25 @@ int lq_mx_gemm_quantize(const void* a_codes, const void* a_scales, int a_format,
     if ((rc = gemm_grid(fn, 2 * dout.KT, da.LT, M, grid))) return rc;
     hipStream_t st = (hipStream_t)stream;
     const bool out_fp4 = out_format == LQ_ELEM_FP4_E2M1;
-    if (a_format == LQ_ELEM_FP4_E2M1) launch_mx_gemm_quantize_b<LQ_ELEM_FP4_E2M1>(p, b_format, out_fp4, grid, st);
+    if (fp6) mx6_dispatch(a_format, b_format, Mx6GemmQuantizeLaunch{p, out_fp4, grid, st});
+    else if (a_format == LQ_ELEM_FP4_E2M1) launch_mx_gemm_quantize_b<LQ_ELEM_FP4_E2M1>(p, b_format, out_fp4, grid, st);
     else if (a_format == LQ_ELEM_FP8_E4M3) launch_mx_gemm_quantize_b<LQ_ELEM_FP8_E4M3>(p, b_format, out_fp4, grid, st);
     else launch_mx_gemm_quantize_b<LQ_ELEM_FP8_E5M2>(p, b_format, out_fp4, grid, st);
     return check_hip("microscaling GEMM with operand-out epilogue");
+}
+
+int lq_mx_gemm_quantize(const void* a_codes, const void* a_scales, int a_format, const void* b_codes, const void* b_scales, int b_format,
+                        const float* bias, int activation, int out_format, int method, void* out_codes, void* out_scales, int64_t M,
+                        int64_t N, int64_t K, void* stream) {
+    return mx_gemm_quantize(__func__, false, a_codes, a_scales, a_format, b_codes, b_scales, b_format, bias, activation, out_format,
+                            method, out_codes, out_scales, M, N, K, stream);
+}
+
+int lq_mx6_gemm_quantize(const void* a_codes, const void* a_scales, int a_format, const void* b_codes, const void* b_scales, int b_format,
+                         const float* bias, int activation, int out_format, int method, void* out_codes, void* out_scales, int64_t M,
+                         int64_t N, int64_t K, void* stream) {
+    return mx_gemm_quantize(__func__, true, a_codes, a_scales, a_format, b_codes, b_scales, b_format, bias, activation, out_format,
+                            method, out_codes, out_scales, M, N, K, stream);
 }
 
 // ---- the operand of a convolution's im2col matrix (lq_mx_conv.hpp) ----

@@ -15,16 +15,18 @@
 #ifndef LQ_MX_GEMM_HPP_
 #define LQ_MX_GEMM_HPP_
 #include "lq_mx_operand.hpp"
+#include "lq_mx6_operand.hpp"
 
 namespace lq {
 
 typedef int mx_v8i __attribute__((ext_vector_type(8)));
 typedef float mx_v4f __attribute__((ext_vector_type(4)));
 
-// the instruction's format immediates (cbsz for A, blgp for B): 0 fp8 e4m3, 1 fp8 e5m2, 4 fp4 e2m1
+// the instruction's format immediates (cbsz for A, blgp for B): 0 fp8 e4m3, 1 fp8 e5m2, 2 fp6 e2m3, 3 fp6 e3m2, 4 fp4 e2m1
 __host__ __device__ constexpr int mx_hw_format(int format) {
-    return format == LQ_ELEM_FP8_E4M3 ? 0 : (format == LQ_ELEM_FP8_E5M2 ? 1 : 4);
+    return format == LQ_ELEM_FP8_E4M3 ? 0 : (format == LQ_ELEM_FP8_E5M2 ? 1 : (format == LQ_ELEM_FP6_E2M3 ? 2 : (format == LQ_ELEM_FP6_E3M2 ? 3 : 4)));
 }
+__host__ __device__ constexpr bool mx_is_fp6(int format) { return format == LQ_ELEM_FP6_E2M3 || format == LQ_ELEM_FP6_E3M2; }
 
 struct MxGemmParams {
     const uint8_t* a_codes;
@@ -38,9 +40,19 @@ struct MxGemmParams {
     int32_t MT, NT, KT, KG;   // tiles of 16 lines, K steps of 128, scale dwords per lane
 };
 
-// the fragment of `lane` in tile (lt, kt): an fp4 fragment fills the first four operand registers
+// the fragment of `lane` in tile (lt, kt): an fp4 fragment fills the first four operand registers, an fp6 fragment
+// (lq_mx6_operand.hpp: a 16-byte word of the tile's first plane, an 8-byte word of its second) the first six; the rest are zero
 template <int FORMAT>
 __device__ __forceinline__ mx_v8i mx_load_frag(const uint8_t* codes, int32_t KT, int32_t lt, int32_t kt, int lane) {
+    if constexpr (mx_is_fp6(FORMAT)) {
+        const uint8_t* tile = codes + ((int64_t)lt * KT + kt) * kMx6TileBytes;
+        const uint4 lo = reinterpret_cast<const uint4*>(tile)[lane];
+        const uint2 hi = reinterpret_cast<const uint2*>(tile + kMx6PlaneLo)[lane];
+        mx_v8i f;
+        f[0] = (int)lo.x; f[1] = (int)lo.y; f[2] = (int)lo.z; f[3] = (int)lo.w;
+        f[4] = (int)hi.x; f[5] = (int)hi.y; f[6] = 0; f[7] = 0;
+        return f;
+    }
     constexpr bool FP4 = FORMAT == LQ_ELEM_FP4_E2M1;
     const uint4* src = reinterpret_cast<const uint4*>(codes + (((int64_t)lt * KT + kt) * 64 + lane) * (FP4 ? 16 : 32));
     const uint4 lo = src[0];

@@ -745,15 +745,17 @@ class CustomDenseLayer(_HostLayer):
             return self._matrix_product(inputs, self.i8_operand(offsets, int4), self.nested_q_b_layer(self.b), _I8, (act_block,),
                                         out_block, activation)
 
-    def mx_operand(self) -> "ops.MxOperand":
+    def mx_operand(self, fp6=False) -> "ops.MxOperand":
         """The kernel under its current scales as an operand of the block-scaled matrix instruction (ops.mx_operand_pack): ``units``
         lines over K = in.  ValueError naming the reason for a layer without an element format, with ``scale_format="fp32"``, with
-        an fp6 format or with a group size other than 32."""
-        ops.check_mx_operand_layer(self.element_format, self.scale_format, self.group_size)
+        an fp6 format or with a group size other than 32.
+        ``fp6=True``: a layer with an fp6 element format is packed into an ops.Mx6Operand (ops.mx6_operand_pack) instead of being
+        refused; every other layer gets what it gets without it."""
+        ops.check_mx_operand_layer(self.element_format, self.scale_format, self.group_size, fp6=fp6)
         if not self.built:
             raise ValueError(f"{self.name}: the layer is not built yet (no kernel to pack)")
-        return ops.mx_operand_pack(self.W.detach(), self.nested_q_w_layer.scale.data, self.element_format, self.group_size,
-                                   self.scale_format)
+        return ops.mx_layer_pack(self.W.detach(), self.nested_q_w_layer.scale.data, self.element_format, self.group_size,
+                                 self.scale_format, fp6)
 
     def _check_operand_input(self, operand):
         if operand.K != self.W.shape[0]:
@@ -778,13 +780,15 @@ class CustomDenseLayer(_HostLayer):
                 raise ValueError(f"{self.name}: the emulated path has no operand-out epilogue ({family.out_name}={out!r})")
             return family.gemm_quantize(a, operand, qb, activation, out, act)
 
-    def call_mx(self, inputs, act_format="fp8_e4m3", act_scale="mx", out_format=None, activation=None):
+    def call_mx(self, inputs, act_format="fp8_e4m3", act_scale="mx", out_format=None, activation=None, fp6=False):
         """The layer on the block-scaled matrix instruction, under ``no_grad``: the inputs quantised per block of 32 along their last
         axis (``act_format`` elements under the ``act_scale`` rule, ops.mx_operand_quantize), multiplied with ``mx_operand()`` by
         ops.mx_gemm, plus the fake-quantised bias.  Inference only: there is no backward through this path.
         ``inputs`` may be an ops.MxOperand (``lines`` rows over ``K`` = in), which is multiplied as it is.  With ``out_format`` the
         result is not the fp32 matrix but the NEXT layer's operand, ``activation`` (None or "relu") applied and quantised under
-        ``act_scale`` by the product's own epilogue (ops.mx_gemm_quantize): one launch, no fp32 activation in memory."""
+        ``act_scale`` by the product's own epilogue (ops.mx_gemm_quantize): one launch, no fp32 activation in memory.
+        ``fp6=True`` lets a layer with an fp6 element format run (``mx_operand(fp6=True)``): the activations stay ``act_format``
+        (fp8 or fp4), so the layer runs as W6A8 or W6A4."""
         if not self.built:
             if isinstance(inputs, ops.MxOperand):
                 raise ValueError(f"{self.name}: the layer is not built yet (no kernel to pack)")
@@ -795,7 +799,7 @@ class CustomDenseLayer(_HostLayer):
             ops.check_mx_operand_format(out_format)
         ops.check_mx_activation(activation)
         with torch.no_grad():
-            return self._matrix_product(inputs, self.mx_operand(), self.nested_q_b_layer(self.b), _MX, (act_format, act_scale),
+            return self._matrix_product(inputs, self.mx_operand(fp6), self.nested_q_b_layer(self.b), _MX, (act_format, act_scale),
                                         out_format, activation)
 
 
@@ -965,19 +969,20 @@ class _ConvBase(_HostLayer):
 
     forward = call
 
-    def mx_operand(self) -> "ops.MxOperand":
+    def mx_operand(self, fp6=False) -> "ops.MxOperand":
         """The kernel under its current scales as an operand of the block-scaled matrix instruction (ops.mx_operand_pack, blocks
         along the contiguous axis): ``filters`` lines over K = ci kh kw, the reduction order of ops.mx_operand_im2col.  ValueError
         naming the reason for ``kernel_storage="hwio"``, for a layer without an element format, with ``scale_format="fp32"``, with an
-        fp6 format or with a group size other than 32, and for a layer that is not built."""
+        fp6 format or with a group size other than 32, and for a layer that is not built.
+        ``fp6=True``: a layer with an fp6 element format is packed into an ops.Mx6Operand instead of being refused."""
         if self.kernel_storage != "oihw":
             raise ValueError(f'{self.name}: kernel_storage="hwio": the block-scaled GEMM reduces over the (ci, kh, kw) memory run of a '
                              'kernel stored "oihw"')
-        ops.check_mx_operand_layer(self.element_format, self.scale_format, self.group_size)
+        ops.check_mx_operand_layer(self.element_format, self.scale_format, self.group_size, fp6=fp6)
         if not self.built:
             raise ValueError(f"{self.name}: the layer is not built yet (no kernel to pack)")
-        return ops.mx_operand_pack(self.kernel.detach(), self.nested_q_k_layer.scale.data, self.element_format, self.group_size,
-                                   self.scale_format)
+        return ops.mx_layer_pack(self.kernel.detach(), self.nested_q_k_layer.scale.data, self.element_format, self.group_size,
+                                 self.scale_format, fp6)
 
     def _mx_padding(self, h: int, w: int) -> Tuple[int, int, int, int]:
         """(top, bottom, left, right) of this layer on an h x w input: TensorFlow 'SAME' (asymmetric where it is) or none.  Both
@@ -1011,18 +1016,19 @@ class _ConvBase(_HostLayer):
             qb = self.nested_q_b_layer(self.b) if self._has_bias else None
             return self._matrix_conv(inputs, operand, qb, family, act, max_lines)
 
-    def call_mx(self, inputs, act_format="fp8_e4m3", act_scale="mx", max_lines=None):
+    def call_mx(self, inputs, act_format="fp8_e4m3", act_scale="mx", max_lines=None, fp6=False):
         """The layer on the block-scaled matrix instruction, under ``no_grad``: the im2col matrix of the inputs quantised per block
         of 32 along (ci, kh, kw) (``act_format`` elements under the ``act_scale`` rule) by ops.mx_operand_im2col -- TensorFlow 'SAME'
         padding as ``call`` pads, or 'VALID' -- multiplied with ``mx_operand()`` by ops.mx_gemm, plus the fake-quantised bias where
         the layer has one.  Inference only: there is no backward through this path.  The result is a view of the GEMM's (M, co)
         matrix: ``(B, co, OH, OW)`` with channels-last strides for ``data_format="NCHW"``, ``(B, OH, OW, co)`` for "NHWC".  A batch
         whose im2col matrix has 2^31 elements or more, more than 65535 * 64 lines or more than ``max_lines`` lines is cut into runs
-        of whole images that write their rows of the one result; the result does not depend on the cut."""
+        of whole images that write their rows of the one result; the result does not depend on the cut.
+        ``fp6=True`` lets a layer with an fp6 element format run (``mx_operand(fp6=True)``); the im2col operand stays ``act_format``."""
         _check_max_lines(max_lines)
         ops.check_mx_operand_format(act_format)
         ops.check_mx_scale_init(act_scale)
-        return self._call_matrix(inputs, _MX, (act_format, act_scale), max_lines)
+        return self._call_matrix(inputs, _MX, (act_format, act_scale), max_lines, fp6=fp6)
 
     def _check_i8(self, offsets=False, int4=False):
         """(qmin, qmax) of a conv layer that can run on the int8 matrix instruction, or ValueError naming the reason.
@@ -1197,17 +1203,23 @@ def custom_layers_of(model: nn.Module):
             if isinstance(m, (CustomDenseLayer, _ConvBase))]
 
 
-def mx_hardware_eligible(layer: nn.Module) -> bool:
+def _mx_layer_formats(fp6) -> Tuple[str, ...]:
+    return ops.MX_OPERAND_FORMATS + (ops.MX6_OPERAND_FORMATS if fp6 else ())
+
+
+def mx_hardware_eligible(layer: nn.Module, fp6=False) -> bool:
     """Whether ``layer`` takes the block-scaled GEMM under ``mx_hardware``: a built Dense layer with an fp4 / fp8 element format,
-    E8M0 scales and blocks of 32.  Conv layers keep the fake-quantised path (no implicit GEMM is built)."""
-    return (isinstance(layer, CustomDenseLayer) and layer.built and layer.element_format in ops.MX_OPERAND_FORMATS
+    E8M0 scales and blocks of 32.  Conv layers keep the fake-quantised path (no implicit GEMM is built).  ``fp6=True``: a layer
+    with an fp6 element format is eligible too."""
+    return (isinstance(layer, CustomDenseLayer) and layer.built and layer.element_format in _mx_layer_formats(fp6)
             and layer.scale_format == "e8m0" and layer.group_size == ops.MX_GROUP_SIZE)
 
 
-def mx_conv_eligible(layer: nn.Module) -> bool:
+def mx_conv_eligible(layer: nn.Module, fp6=False) -> bool:
     """Whether ``layer`` takes the block-scaled GEMM under ``mx_hardware(convs=True)``: a built conv layer with an fp4 / fp8 element
-    format, E8M0 scales, blocks of 32 and the kernel stored "oihw" (the blocks then run along the im2col operand's K)."""
-    return (isinstance(layer, _ConvBase) and layer.built and layer.element_format in ops.MX_OPERAND_FORMATS
+    format, E8M0 scales, blocks of 32 and the kernel stored "oihw" (the blocks then run along the im2col operand's K).  ``fp6=True``:
+    a layer with an fp6 element format is eligible too."""
+    return (isinstance(layer, _ConvBase) and layer.built and layer.element_format in _mx_layer_formats(fp6)
             and layer.scale_format == "e8m0" and layer.group_size == ops.MX_GROUP_SIZE and layer.kernel_storage == "oihw")
 
 
@@ -1274,11 +1286,17 @@ class mx_hardware(_matrix_hardware):
     operand, plus the fake-quantised bias; the result is a channels-last view for ``data_format="NCHW"``.  Operand and bias are
     built once, on entry, and the layer is listed in ``layers`` after the Dense layers.  Under ``emulate=True`` such a layer
     multiplies the decoded im2col operand with the fake-quantised kernel by ``torch.matmul`` instead.  Without ``convs`` (the
-    default) conv layers keep the fake-quantised path."""
+    default) conv layers keep the fake-quantised path.
+    ``fp6=True``: layers with an fp6 element format switch too -- their kernels packed into ops.Mx6Operand, the activations still
+    ``act_format`` (W6A8 / W6A4; an fp6 ``act_format`` stays refused) -- and are listed in ``layers``.  It combines with ``convs``,
+    ``fused`` and ``emulate``; fp4 / fp8 layers behave as they do without it, so a model without fp6 layers is bit-identical.
+    Without it (the default) fp6 layers keep the fake-quantised path."""
 
     _family, _dense_eligible, _conv_eligible = _MX, staticmethod(mx_hardware_eligible), staticmethod(mx_conv_eligible)
 
-    def __init__(self, model: nn.Module, act_format="fp8_e4m3", act_scale="mx", emulate=False, fused=False, convs=False):
+    def __init__(self, model: nn.Module, act_format="fp8_e4m3", act_scale="mx", emulate=False, fused=False, convs=False, fp6=False):
+        self.fp6 = bool(fp6)
+        self._opt_in = {"fp6": True} if self.fp6 else {}
         ops.check_mx_operand_format(act_format)
         ops.check_mx_scale_init(act_scale)
         if emulate and fused:
@@ -1501,20 +1519,22 @@ def _dense_chain(fn, family, gemm_name, check_layer, check_act, x, chain, act, o
         return a.reshape(*lead, a.shape[-1])
 
 
-def mx_dense_chain(x, chain, act_format="fp8_e4m3", act_scale="mx"):
+def mx_dense_chain(x, chain, act_format="fp8_e4m3", act_scale="mx", fp6=False):
     """``chain`` = [(layer, activation), ...]: Dense layers applied one after the other on the block-scaled matrix instruction, under
     ``no_grad``.  ``x`` is quantised once (ops.mx_operand_quantize); every layer but the last goes through ops.mx_gemm_quantize, which
     applies its activation (None or "relu") and writes the next layer's operand (``act_format`` under ``act_scale``) in the product's
     epilogue; the last goes through ops.mx_gemm to fp32 and takes no activation.  Bit for bit ``call_mx`` -> activation -> ``call_mx``
     ..., without the fp32 activations and their launches.  Inside ``mx_hardware`` the operands and biases built on its entry are
     used, otherwise they are built here.  ValueError naming the reason for a layer that cannot take the path
-    (``mx_hardware_eligible``) or an activation other than None / "relu"."""
+    (``mx_hardware_eligible``) or an activation other than None / "relu".  ``fp6=True`` lets layers with an fp6 element format take
+    the path (``mx_operand(fp6=True)``); the operands between the layers stay ``act_format``."""
     def check_act():
         ops.check_mx_operand_format(act_format)
         ops.check_mx_scale_init(act_scale)
+    opt_in = {"fp6": True} if fp6 else {}
     return _dense_chain("mx_dense_chain", _MX, "block-scaled",
-                        lambda layer: ops.check_mx_operand_layer(layer.element_format, layer.scale_format, layer.group_size), check_act,
-                        x, chain, (act_format, act_scale), act_format)
+                        lambda layer: ops.check_mx_operand_layer(layer.element_format, layer.scale_format, layer.group_size, **opt_in),
+                        check_act, x, chain, (act_format, act_scale), act_format, **opt_in)
 
 
 def i8_dense_chain(x, chain, act_block=64, offsets=False, int4=False):

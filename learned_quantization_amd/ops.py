@@ -498,6 +498,7 @@ def scale_init_mx(parameter: torch.Tensor, scale: torch.Tensor, element_format: 
 
 # --------------------------------------------------------------------------- packed MX operands and the block-scaled GEMM
 MX_OPERAND_FORMATS = ("fp4_e2m1", "fp8_e4m3", "fp8_e5m2")      # what the fragments are built for (include/lq_hip.h)
+MX6_OPERAND_FORMATS = ("fp6_e2m3", "fp6_e3m2")                 # the fp6 operand's: a layout and entry points of their own (lq_mx6_*)
 
 
 class MxOperand(NamedTuple):
@@ -519,30 +520,105 @@ def check_mx_operand_format(element_format) -> ElementFormat:
     return fmt
 
 
-def check_mx_operand_layer(element_format, scale_format, group_size) -> ElementFormat:
-    """What a quantizer must be to run on the block-scaled matrix instruction, or ValueError naming the reason."""
+def check_mx_operand_layer(element_format, scale_format, group_size, fp6=False) -> ElementFormat:
+    """What a quantizer must be to run on the block-scaled matrix instruction, or ValueError naming the reason.  ``fp6=True``
+    lets a layer with an fp6 element format pass too (``mx_layer_pack`` then gives it an Mx6Operand)."""
     if element_format is None:
         raise ValueError("the block-scaled GEMM needs a layer with an element_format (a microscaling layer)")
+    if fp6 and element_format in MX6_OPERAND_FORMATS:
+        return check_mx6_operand_layer(element_format, scale_format, group_size)
     fmt = check_mx_operand_format(element_format)
+    _check_mx_block(scale_format, group_size)
+    return fmt
+
+
+def _check_mx_block(scale_format, group_size) -> None:
     if scale_format != "e8m0":
         raise ValueError(f'scale_format={scale_format!r}: the block-scaled matrix instruction takes E8M0 (power-of-two) scales only')
     if group_size != MX_GROUP_SIZE:
         raise ValueError(f"group_size={group_size!r}: the block of the block-scaled matrix instruction is {MX_GROUP_SIZE}")
+
+
+class Mx6Operand(NamedTuple):
+    """An fp6 matrix of ``lines`` by ``K`` in the order the block-scaled matrix instruction consumes 6-bit data (include/lq_hip.h,
+    "packed fp6 MX operands"): the fields of MxOperand, ``codes`` 0.75 of an fp8 operand's bytes.  The TYPE selects the fp6 entry
+    points in ``mx_operand_decode``, ``mx_gemm`` and ``mx_gemm_quantize``; an MxOperand that names an fp6 format stays refused."""
+    codes: torch.Tensor
+    scales: torch.Tensor
+    format: str
+    lines: int
+    K: int
+
+
+def check_mx6_operand_format(element_format) -> ElementFormat:
+    """The table row of an fp6 operand's ``element_format``, or ValueError: one of MX6_OPERAND_FORMATS."""
+    fmt = check_element_format(element_format)
+    if element_format not in MX6_OPERAND_FORMATS:
+        raise ValueError(f"element_format={element_format!r}: an Mx6Operand holds one of {MX6_OPERAND_FORMATS}; the fp4 and fp8 "
+                         "formats have the MxOperand")
     return fmt
+
+
+def check_mx6_operand_layer(element_format, scale_format, group_size) -> ElementFormat:
+    """``check_mx_operand_layer`` for the fp6 operand: an fp6 element format, E8M0 scales, blocks of 32."""
+    if element_format is None:
+        raise ValueError("the block-scaled GEMM needs a layer with an element_format (a microscaling layer)")
+    fmt = check_mx6_operand_format(element_format)
+    _check_mx_block(scale_format, group_size)
+    return fmt
+
+
+class _OperandKind(NamedTuple):
+    """What differs between the MxOperand and the Mx6Operand for the functions below."""
+    cls: type
+    prefix: str               # of the C entry points
+    check_format: Callable
+    check_layer: Callable
+
+
+_MX8 = _OperandKind(MxOperand, "lq_mx_operand", check_mx_operand_format, check_mx_operand_layer)
+_MX6 = _OperandKind(Mx6Operand, "lq_mx6_operand", check_mx6_operand_format, check_mx6_operand_layer)
+
+
+def _mx_operand_format(operand) -> ElementFormat:
+    """The table row of an operand's format, checked against its type."""
+    return (_MX6 if isinstance(operand, Mx6Operand) else _MX8).check_format(operand.format)
+
+
+def _mx_operand_bytes(kind: _OperandKind, element_format: str, lines: int, K: int) -> Tuple[int, int]:
+    import ctypes
+    fmt = kind.check_format(element_format)
+    cb, sb = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    name = kind.prefix + "_bytes"
+    _hip.check(getattr(_hip.load(), name)(fmt.id, int(lines), int(K), ctypes.byref(cb), ctypes.byref(sb)), name)
+    return int(cb.value), int(sb.value)
 
 
 def mx_operand_bytes(element_format: str, lines: int, K: int) -> Tuple[int, int]:
     """(code_bytes, scale_bytes) of an operand (include/lq_hip.h, lq_mx_operand_bytes).  Needs no device."""
-    import ctypes
-    fmt = check_mx_operand_format(element_format)
-    cb, sb = ctypes.c_size_t(0), ctypes.c_size_t(0)
-    _hip.check(_hip.load().lq_mx_operand_bytes(fmt.id, int(lines), int(K), ctypes.byref(cb), ctypes.byref(sb)), "lq_mx_operand_bytes")
-    return int(cb.value), int(sb.value)
+    return _mx_operand_bytes(_MX8, element_format, lines, K)
 
 
-def _mx_operand_buffers(element_format: str, lines: int, K: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
-    cb, sb = mx_operand_bytes(element_format, lines, K)
+def mx6_operand_bytes(element_format: str, lines: int, K: int) -> Tuple[int, int]:
+    """(code_bytes, scale_bytes) of an fp6 operand (include/lq_hip.h, lq_mx6_operand_bytes).  Needs no device."""
+    return _mx_operand_bytes(_MX6, element_format, lines, K)
+
+
+def _mx_operand_buffers(element_format: str, lines: int, K: int, device, kind: _OperandKind = _MX8) -> Tuple[torch.Tensor, torch.Tensor]:
+    cb, sb = _mx_operand_bytes(kind, element_format, lines, K)
     return torch.empty(cb, dtype=torch.uint8, device=device), torch.empty(sb, dtype=torch.uint8, device=device)
+
+
+def _mx_operand_pack(kind: _OperandKind, parameter, scale, element_format, group_size, scale_format):
+    fmt = kind.check_layer(element_format, scale_format, group_size)
+    lib = _hip.load()
+    p, s, (R, C, axis) = _group_param(parameter, scale, group_size)
+    lines, K = (C, R) if axis == 0 else (R, C)
+    codes, scales = _mx_operand_buffers(element_format, lines, K, p.device, kind)
+    name = kind.prefix + "_pack"
+    _hip.check(getattr(lib, name)(_hip.ptr(p), _hip.ptr(s), fmt.id, check_scale_format(scale_format), R, C, axis, int(group_size),
+                                  _hip.ptr(codes), _hip.ptr(scales), _hip.stream_ptr(p.device)), name)
+    return kind.cls(codes, scales, element_format, lines, K)
 
 
 def mx_operand_pack(parameter: torch.Tensor, scale: torch.Tensor, element_format: str, group_size: int = MX_GROUP_SIZE,
@@ -550,40 +626,58 @@ def mx_operand_pack(parameter: torch.Tensor, scale: torch.Tensor, element_format
     """The operand of a stored parameter under its stored group-wise scales (include/lq_hip.h, lq_mx_operand_pack): the codes are
     those of ``fq_forward_mx``'s code view, the scale bytes the exponents of its effective scales.  The lines are the parameter's
     columns when the blocks run along its strided axis (a Dense kernel (in, out)), its rows otherwise.  One launch."""
-    fmt = check_mx_operand_layer(element_format, scale_format, group_size)
-    lib = _hip.load()
-    p, s, (R, C, axis) = _group_param(parameter, scale, group_size)
-    lines, K = (C, R) if axis == 0 else (R, C)
-    codes, scales = _mx_operand_buffers(element_format, lines, K, p.device)
-    _hip.check(lib.lq_mx_operand_pack(_hip.ptr(p), _hip.ptr(s), fmt.id, check_scale_format(scale_format), R, C, axis, int(group_size),
-                                      _hip.ptr(codes), _hip.ptr(scales), _hip.stream_ptr(p.device)), "lq_mx_operand_pack")
-    return MxOperand(codes, scales, element_format, lines, K)
+    return _mx_operand_pack(_MX8, parameter, scale, element_format, group_size, scale_format)
 
 
-def mx_operand_quantize(x: torch.Tensor, element_format: str = "fp8_e4m3", method: str = "mx") -> MxOperand:
-    """The operand of a row-major activation matrix ``x (M, K)`` under scales taken from ``x`` itself (include/lq_hip.h,
-    lq_mx_operand_quantize): per block of 32 along K what ``scale_init_mx(method, min_value=2^-126)`` writes, then the codes of
-    ``fq_forward_mx`` under it.  No learned state, no backward.  One launch, one read of ``x``."""
-    fmt = check_mx_operand_format(element_format)
+def mx6_operand_pack(parameter: torch.Tensor, scale: torch.Tensor, element_format: str, group_size: int = MX_GROUP_SIZE,
+                     scale_format: str = "e8m0") -> Mx6Operand:
+    """``mx_operand_pack`` for an fp6 ``element_format`` (include/lq_hip.h, lq_mx6_operand_pack): the same codes and scale bytes of
+    ``fq_forward_mx``, 6 bits to a code, in the fp6 operand's layout.  One launch."""
+    return _mx_operand_pack(_MX6, parameter, scale, element_format, group_size, scale_format)
+
+
+def mx_layer_pack(parameter: torch.Tensor, scale: torch.Tensor, element_format: str, group_size: int, scale_format: str, fp6=False):
+    """What a layer's ``mx_operand(fp6)`` packs: with ``fp6=True`` the Mx6Operand of a kernel with an fp6 element format; in every
+    other case ``mx_operand_pack``, which refuses an fp6 format."""
+    kind = _MX6 if fp6 and element_format in MX6_OPERAND_FORMATS else _MX8
+    return _mx_operand_pack(kind, parameter, scale, element_format, group_size, scale_format)
+
+
+def _mx_operand_quantize(kind: _OperandKind, x, element_format, method):
+    fmt = kind.check_format(element_format)
     m = check_mx_scale_init(method)
     if not isinstance(x, torch.Tensor) or x.dim() != 2:
         raise ValueError(f"x must be a matrix (M, K), got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
     lib = _hip.load()
     xc = _hip.require_device_f32(x, "x")
     M, K = (int(d) for d in xc.shape)
-    codes, scales = _mx_operand_buffers(element_format, M, K, xc.device)
-    _hip.check(lib.lq_mx_operand_quantize(_hip.ptr(xc), fmt.id, m, M, K, _hip.ptr(codes), _hip.ptr(scales),
-                                          _hip.stream_ptr(xc.device)), "lq_mx_operand_quantize")
-    return MxOperand(codes, scales, element_format, M, K)
+    codes, scales = _mx_operand_buffers(element_format, M, K, xc.device, kind)
+    name = kind.prefix + "_quantize"
+    _hip.check(getattr(lib, name)(_hip.ptr(xc), fmt.id, m, M, K, _hip.ptr(codes), _hip.ptr(scales), _hip.stream_ptr(xc.device)), name)
+    return kind.cls(codes, scales, element_format, M, K)
+
+
+def mx_operand_quantize(x: torch.Tensor, element_format: str = "fp8_e4m3", method: str = "mx") -> MxOperand:
+    """The operand of a row-major activation matrix ``x (M, K)`` under scales taken from ``x`` itself (include/lq_hip.h,
+    lq_mx_operand_quantize): per block of 32 along K what ``scale_init_mx(method, min_value=2^-126)`` writes, then the codes of
+    ``fq_forward_mx`` under it.  No learned state, no backward.  One launch, one read of ``x``."""
+    return _mx_operand_quantize(_MX8, x, element_format, method)
+
+
+def mx6_operand_quantize(x: torch.Tensor, element_format: str = "fp6_e2m3", method: str = "mx") -> Mx6Operand:
+    """``mx_operand_quantize`` for an fp6 ``element_format`` (include/lq_hip.h, lq_mx6_operand_quantize).  One launch."""
+    return _mx_operand_quantize(_MX6, x, element_format, method)
 
 
 def mx_operand_decode(operand: MxOperand) -> torch.Tensor:
-    """float32 ``(lines, K)``: value(code) * 2^(byte - 127) of every element (include/lq_hip.h, lq_mx_operand_decode)."""
-    fmt = check_mx_operand_format(operand.format)
+    """float32 ``(lines, K)``: value(code) * 2^(byte - 127) of every element (include/lq_hip.h, lq_mx_operand_decode; of an
+    Mx6Operand lq_mx6_operand_decode)."""
+    fmt = _mx_operand_format(operand)
     lib = _hip.load()
     out = torch.empty((operand.lines, operand.K), dtype=torch.float32, device=operand.codes.device)
-    _hip.check(lib.lq_mx_operand_decode(_hip.ptr(operand.codes), _hip.ptr(operand.scales), fmt.id, operand.lines, operand.K,
-                                        _hip.ptr(out), _hip.stream_ptr(out.device)), "lq_mx_operand_decode")
+    name = (_MX6 if isinstance(operand, Mx6Operand) else _MX8).prefix + "_decode"
+    _hip.check(getattr(lib, name)(_hip.ptr(operand.codes), _hip.ptr(operand.scales), fmt.id, operand.lines, operand.K,
+                                  _hip.ptr(out), _hip.stream_ptr(out.device)), name)
     return out
 
 
@@ -610,16 +704,18 @@ def _matrix_output(M: int, N: int, device, bias: Optional[torch.Tensor], out: Op
 
 def mx_gemm(a: MxOperand, b: MxOperand, bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``Y (a.lines, b.lines) = A B^T (+ bias)`` in fp32 on v_mfma_scale_f32_16x16x128_f8f6f4 (include/lq_hip.h, lq_mx_gemm).
-    ``out``: a float32 matrix to write into; its row stride is the leading dimension."""
-    fa, fb = check_mx_operand_format(a.format), check_mx_operand_format(b.format)
+    ``out``: a float32 matrix to write into; its row stride is the leading dimension.  With an Mx6Operand on either side the
+    product is lq_mx6_gemm's: the same definition for the 16 format pairs that have an fp6 side."""
+    fa, fb = _mx_operand_format(a), _mx_operand_format(b)
     if a.K != b.K:
         raise ValueError(f"the operands reduce over different K: {a.K} and {b.K}")
     lib = _hip.load()
     M, N = a.lines, b.lines
     dev = a.codes.device
     bias, out, ldy = _gemm_output(a, b, bias, out)
-    _hip.check(lib.lq_mx_gemm(_hip.ptr(a.codes), _hip.ptr(a.scales), fa.id, _hip.ptr(b.codes), _hip.ptr(b.scales), fb.id,
-                              _hip.ptr(bias), _hip.ptr(out), M, N, a.K, ldy, _hip.stream_ptr(dev)), "lq_mx_gemm")
+    name = "lq_mx6_gemm" if isinstance(a, Mx6Operand) or isinstance(b, Mx6Operand) else "lq_mx_gemm"
+    _hip.check(getattr(lib, name)(_hip.ptr(a.codes), _hip.ptr(a.scales), fa.id, _hip.ptr(b.codes), _hip.ptr(b.scales), fb.id,
+                                  _hip.ptr(bias), _hip.ptr(out), M, N, a.K, ldy, _hip.stream_ptr(dev)), name)
     return out
 
 
@@ -929,8 +1025,10 @@ def mx_gemm_quantize(a: MxOperand, b: MxOperand, bias: Optional[torch.Tensor] = 
                      method: str = "mx") -> MxOperand:
     """The operand of ``activation(A B^T (+ bias))`` for the next product, ``a.lines`` lines over ``K = b.lines``, written by the
     GEMM's own epilogue (include/lq_hip.h, lq_mx_gemm_quantize): byte for byte
-    ``mx_operand_quantize(act(mx_gemm(a, b, bias)), out_format, method)``, in one launch and without the fp32 matrix."""
-    fa, fb, fo = check_mx_operand_format(a.format), check_mx_operand_format(b.format), check_mx_operand_format(out_format)
+    ``mx_operand_quantize(act(mx_gemm(a, b, bias)), out_format, method)``, in one launch and without the fp32 matrix.  With an
+    Mx6Operand on either side it is lq_mx6_gemm_quantize; the operand written is an MxOperand either way (an fp6 ``out_format`` is
+    not built)."""
+    fa, fb, fo = _mx_operand_format(a), _mx_operand_format(b), check_mx_operand_format(out_format)
     m = check_mx_scale_init(method)
     act = check_mx_activation(activation)
     if a.K != b.K:
@@ -940,9 +1038,10 @@ def mx_gemm_quantize(a: MxOperand, b: MxOperand, bias: Optional[torch.Tensor] = 
     dev = a.codes.device
     bias = _gemm_output(a, b, bias, fp32_out=False)[0]
     codes, scales = _mx_operand_buffers(out_format, M, N, dev)
-    _hip.check(lib.lq_mx_gemm_quantize(_hip.ptr(a.codes), _hip.ptr(a.scales), fa.id, _hip.ptr(b.codes), _hip.ptr(b.scales), fb.id,
-                                       _hip.ptr(bias), act, fo.id, m, _hip.ptr(codes), _hip.ptr(scales), M, N, a.K,
-                                       _hip.stream_ptr(dev)), "lq_mx_gemm_quantize")
+    name = "lq_mx6_gemm_quantize" if isinstance(a, Mx6Operand) or isinstance(b, Mx6Operand) else "lq_mx_gemm_quantize"
+    _hip.check(getattr(lib, name)(_hip.ptr(a.codes), _hip.ptr(a.scales), fa.id, _hip.ptr(b.codes), _hip.ptr(b.scales), fb.id,
+                                  _hip.ptr(bias), act, fo.id, m, _hip.ptr(codes), _hip.ptr(scales), M, N, a.K,
+                                  _hip.stream_ptr(dev)), name)
     return MxOperand(codes, scales, out_format, M, N)
 
 

@@ -31,7 +31,7 @@ from . import _hip
 from .ddp import CaptureRefused, DataParallel, capture_with_agreement, control_group
 from .losses import LossLog, SCCEDifference, SCCEInverse, SCCEMaxBin, sparse_categorical_crossentropy
 from .models import INPUT_SHAPES, build_model, check_asymmetric_model, check_clip_mode, check_group_mode, check_mx_model
-from .ops import (ELEMENT_FORMATS, LAYER_SCALE_INITS, MX_OPERAND_FORMATS, MX_SCALE_INITS, ROUNDINGS, SCALE_FORMATS, check_element_format, check_minmax_range,
+from .ops import (ELEMENT_FORMATS, LAYER_SCALE_INITS, MX6_OPERAND_FORMATS, MX_OPERAND_FORMATS, MX_SCALE_INITS, ROUNDINGS, SCALE_FORMATS, check_element_format, check_minmax_range,
                   check_rounding, check_scale_format, q_range_of)
 from .optim import KerasAdam, ScaleAdam, non_scale_parameters, scale_parameters
 
@@ -616,6 +616,11 @@ def build_parser():
                          "matrix instruction, their im2col operand gathered by ops.mx_operand_im2col) and add mx_eval_conv_layers, "
                          "mx_eval_conv_accuracy and mx_eval_conv_max_logit_diff (the model's outputs against the emulated path with "
                          "convs=True) to the result line")
+    ap.add_argument("--mx-eval-fp6", action="store_true",
+                    help="with --mx-eval and an fp6 --element-format: run the layers under layers.mx_hardware(fp6=True) (their kernels "
+                         "packed 6 bits to a code into ops.Mx6Operand, the activations ACT_FORMAT: W6A8 / W6A4); the fields are "
+                         "--mx-eval's, against the emulated path.  Required for an fp6 model, which otherwise has no layer that "
+                         "takes the hardware path")
     ap.add_argument("--i8-eval", action="store_true",
                     help="with --bits (a signed range of at most 8 bits): evaluate the final model once more under layers.i8_hardware "
                          "(Dense layers on the int8 matrix instruction, activations quantised per row to 8-bit integers) and add "
@@ -766,22 +771,23 @@ def i8_eval(model, x, y, act_block=0, convs=False, fused=False, offsets=False, d
 
 
 @torch.no_grad()
-def mx_eval(model, x, y, act_format="fp8_e4m3", act_scale="mx", fused=False, convs=False):
+def mx_eval(model, x, y, act_format="fp8_e4m3", act_scale="mx", fused=False, convs=False, fp6=False):
     """One evaluation of ``model`` on (x, y) under layers.mx_hardware and one under its ``emulate=True`` yardstick: a dict of both
     accuracies and the largest |difference| of the outputs of the last Dense layer that took the path (the logits of the MNIST
     model).  ``fused=True`` adds a third evaluation under ``mx_hardware(fused=True)``: its accuracy and the largest |difference| of
     the model's ``logits`` from the unfused hardware path's (the same bits are expected: 0.0).  ``convs=True`` adds an evaluation under
     ``mx_hardware(convs=True)`` and one under its emulation: the number of conv layers that took the path, the accuracy, and the
-    largest |difference| of the model's outputs between the two; a model without Dense layers is then accepted."""
+    largest |difference| of the model's outputs between the two; a model without Dense layers is then accepted.  ``fp6=True``:
+    every evaluation runs under ``mx_hardware(fp6=True)``, so that layers with an fp6 element format take the path."""
     was_training = model.training
     model.eval()
     acc, logits = [], []
     try:
         for emulate in (False, True):
-            with L.mx_hardware(model, act_format, act_scale, emulate=emulate) as hw:
+            with L.mx_hardware(model, act_format, act_scale, emulate=emulate, fp6=fp6) as hw:
                 if not hw.layers and not convs:
                     raise ValueError("mx_eval: the model has no Dense layer that can run on the block-scaled matrix instruction "
-                                     "(fp4 / fp8 element format, E8M0 scales, blocks of 32)")
+                                     f"({'fp4 / fp6 / fp8' if fp6 else 'fp4 / fp8'} element format, E8M0 scales, blocks of 32)")
                 seen = []
                 # with convs=True a model without such a Dense layer is accepted: its Dense fields are those of the model's own output
                 hook = (hw.layers[-1] if hw.layers else model).register_forward_hook(lambda m, i, o: seen.append(o.detach()))
@@ -793,7 +799,7 @@ def mx_eval(model, x, y, act_format="fp8_e4m3", act_scale="mx", fused=False, con
                 logits.append(seen[-1])
         fields = {}
         if fused:
-            with L.mx_hardware(model, act_format, act_scale, fused=True) as hwf:
+            with L.mx_hardware(model, act_format, act_scale, fused=True, fp6=fp6) as hwf:
                 if not hwf.fused_layers or not callable(getattr(model, "logits", None)):
                     raise ValueError("mx_eval: fused=True needs a model whose Dense tail fuses (mx_chain() and logits(), as "
                                      "models.MNISTDense has): nothing but relu between eligible Dense layers")
@@ -803,11 +809,12 @@ def mx_eval(model, x, y, act_format="fp8_e4m3", act_scale="mx", fused=False, con
         if convs:
             outs = []
             for emulate in (False, True):
-                with L.mx_hardware(model, act_format, act_scale, emulate=emulate, convs=True) as hwc:
-                    n_convs = sum(L.mx_conv_eligible(m) for m in hwc.layers)
+                with L.mx_hardware(model, act_format, act_scale, emulate=emulate, convs=True, fp6=fp6) as hwc:
+                    n_convs = sum(L.mx_conv_eligible(m, fp6=fp6) for m in hwc.layers)
                     if not n_convs:
                         raise ValueError("mx_eval: convs=True needs a model with a conv layer that can run on the block-scaled matrix "
-                                         "instruction (fp4 / fp8 element format, E8M0 scales, blocks of 32, kernel stored oihw)")
+                                         f"instruction ({'fp4 / fp6 / fp8' if fp6 else 'fp4 / fp8'} element format, E8M0 scales, blocks of 32, "
+                                         "kernel stored oihw)")
                     outs.append(model(x))
             fields.update({"mx_eval_conv_layers": n_convs, "mx_eval_conv_accuracy": float((outs[0].argmax(1) == y).float().mean()),
                            "mx_eval_conv_max_logit_diff": float((outs[0] - outs[1]).abs().max())})
@@ -826,6 +833,11 @@ def main(argv=None):
         ap.error("--mx-eval-fused needs --mx-eval: it compares the fused Dense tail with the unfused hardware path")
     if args.mx_eval_convs and args.mx_eval is None:
         ap.error("--mx-eval-convs needs --mx-eval: it adds the conv layers to the hardware path that --mx-eval evaluates")
+    if args.mx_eval_fp6 and args.mx_eval is None:
+        ap.error("--mx-eval-fp6 needs --mx-eval: it lets the fp6 layers take the hardware path that --mx-eval evaluates")
+    if args.mx_eval is not None and args.element_format in MX6_OPERAND_FORMATS and not args.mx_eval_fp6:
+        ap.error(f"--mx-eval with --element-format {args.element_format} needs --mx-eval-fp6: an fp6 layer takes the block-scaled "
+                 "matrix instruction through the fp6 operand only (layers.mx_hardware(fp6=True))")
     if args.i8_eval_offsets and not args.i8_eval:
         ap.error("--i8-eval-offsets needs --i8-eval: it lets the asymmetric layers take the hardware path that --i8-eval evaluates")
     if args.i8_eval and (args.bits is None or args.bits > 8 or args.unsigned or (args.asymmetric and not args.i8_eval_offsets)
@@ -916,7 +928,7 @@ def main(argv=None):
     log_rows = tr.flush_loss_log() if args.loss_values and rank == 0 else None     # every rank holds the same rows: one writes
     quant_stats = L.quant_stats(tr.model) if args.quant_stats and rank == 0 else None      # after the clock has stopped
     mx_stats = L.mx_quant_stats(tr.model) if args.mx_stats and rank == 0 else None
-    mx_eval_fields = mx_eval(tr.model, *batches[0], act_format=args.mx_eval, fused=args.mx_eval_fused, convs=args.mx_eval_convs) if args.mx_eval is not None and rank == 0 else None
+    mx_eval_fields = mx_eval(tr.model, *batches[0], act_format=args.mx_eval, fused=args.mx_eval_fused, convs=args.mx_eval_convs, fp6=args.mx_eval_fp6) if args.mx_eval is not None and rank == 0 else None
     i8_eval_fields = i8_eval(tr.model, *batches[0], act_block=args.i8_eval_act_block, convs=args.i8_eval_convs, fused=args.i8_eval_fused, offsets=args.i8_eval_offsets, direct=args.i8_eval_direct, int4=args.i8_eval_int4, fused_convs=args.i8_eval_fused_convs) if args.i8_eval and rank == 0 else None
     if rank == 0:
         n_q = sum(p.numel() for l in tr.custom_layers for p in l._regularized())

@@ -703,8 +703,23 @@ int lq_mx_operand_im2col(const float* X, const lq_conv_geom* g, int format, int 
  *   one thread block before its first code: co <= 512.  LQ_EINVAL before any launch: everything lq_i8_conv2d refuses, co > 512, an
  *   unknown activation, affine_first outside {0, 1}, exactly one of post_scale / post_shift NULL.  LQ_EALIGN: what lq_i8_conv2d
  *   refuses, out_codes or out_scales off the 16-byte grid, post_scale or post_shift off the 4-byte grid.
+ * lq_i8_conv2d_quantize_residual: lq_i8_conv2d_quantize's arguments and, before out_codes, a RESIDUAL that is itself a pixel
+ * operand of the OUTPUT's shape (B, co, OH, OW) -- res_codes [M][CPo] int8, res_scales [M] fp32, what lq_i8_pixels_quantize or
+ * either epilogue writes -- added directly before the activation (the ResNet basic block: relu(bn2(conv2(y)) + shortcut)).
+ * DEFINITION (bit exact, independent of any tiling).  With Y, relu and aff as above:
+ *       r[m][n] = RN((float)res_codes[m][n] * res_scales[m])          one rounding
+ *       u = affine_first ? aff(Y) : Y
+ *       u = RN(u + r)                                                  the add rounds on its own (no contraction)
+ *       v = affine_first ? act(u) : aff(act(u))
+ *   out_codes / out_scales are, byte for byte, lq_i8_pixels_quantize of v seen as [B][co][OH][OW], padding included.  A NaN
+ *   residual scale makes exactly its own output pixel NaN-scaled with codes 0.  ONE launch (capturable); no workspace, memset or
+ *   atomics; reads no environment; writes exactly lq_i8_pixels_bytes(B, co, OH, OW).  LQ_EINVAL before any launch: everything
+ *   lq_i8_conv2d_quantize refuses, a NULL res_codes or res_scales (without a residual call lq_i8_conv2d_quantize), an output
+ *   buffer that overlaps a residual buffer (a row's scale is written by one lane and its residual read by others: not in place).
+ *   LQ_EALIGN: what lq_i8_conv2d_quantize refuses, res_codes or res_scales off the 16-byte grid.
  * Not built on this path: weight scales that vary along K (a group size below ci * kh * kw stays on the im2col path), offsets
- * (asymmetric layers), MX elements, an epilogue for co > 512 or with a residual input (the ResNet blocks), dilation and groups.
+ * (asymmetric layers), MX elements, an epilogue for co > 512 (the bottleneck blocks), an fp32 residual, an fp32 second output,
+ * dilation and groups.
  *
  * PACKED 4-BIT B OPERAND (W4A8).  An operand of L lines by K whose codes lie in [-8, 7] stores them two to a byte, under the same
  * fp32 scales (and, for an asymmetric parameter, offsets) in exactly the layout above:
@@ -781,6 +796,11 @@ int lq_i8_conv2d_quantize(const void* pix_codes, const void* pix_scales, const v
                           const float* bias /* may be NULL */, const lq_conv_geom* g, int64_t co,
                           const float* post_scale /* [co]; both or neither NULL */, const float* post_shift,
                           int activation /* lq_mx_activation */, int affine_first, void* out_codes, void* out_scales, void* stream);
+int lq_i8_conv2d_quantize_residual(const void* pix_codes, const void* pix_scales, const void* k_codes, const void* k_scales,
+                                   const float* bias /* may be NULL */, const lq_conv_geom* g, int64_t co,
+                                   const float* post_scale /* [co]; both or neither NULL */, const float* post_shift,
+                                   int activation /* lq_mx_activation */, int affine_first, const void* res_codes,
+                                   const void* res_scales, void* out_codes, void* out_scales, void* stream);
 
 /* ---- K4: forward and NQ backward of one tensor in a single pass (benchmark path) ---
  * Same results as lq_fq_forward followed by lq_fq_scale_grad (out, max|q| and the vote count bit for bit; on

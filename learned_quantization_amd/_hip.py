@@ -188,6 +188,8 @@ SIGNATURES.update({
     "lq_i8_conv2d": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, ctypes.POINTER(ConvGeom), _c_i64, _c_p]),
     "lq_i8_conv2d_quantize": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, ctypes.POINTER(ConvGeom), _c_i64, _c_p, _c_p, _c_int, _c_int, _c_p, _c_p,
                                        _c_p]),
+    "lq_i8_conv2d_quantize_residual": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, ctypes.POINTER(ConvGeom), _c_i64, _c_p, _c_p, _c_int, _c_int,
+                                                _c_p, _c_p, _c_p, _c_p, _c_p]),
 })
 
 

@@ -23,6 +23,13 @@
 // (i8_scalar); a row's absmax partials merge over its 16 lanes by the four DPP steps of i8_merge_dpp; the scale rule and the
 // element step are k_i8_pixels' own device functions; a quad's 4 x 4 bytes are transposed in registers (mx_quad_gather) so that a
 // lane stores one dword per tile into the NHWC row, and one lane per row stores the scale.
+//
+// RES = true (lq_i8_conv2d_quantize_residual): a residual pixel operand of the OUTPUT's shape is decoded, r = RN(code * scale), and
+// added directly before the activation.  Its NHWC row is laid out as this kernel stores its own codes, so after the tap loop a lane
+// reads one dword per owned tile at the very address it later stores to, and the same quad transpose (its own inverse) brings
+// byte r = row g4 + r of the lane's column; the four row scales come by one load per lane and the shuffle of the tap loop.  In the
+// BLOCK form every wave adds its own tiles' residual before its absmax partials go through LDS.  Two more VGPRs than RES = false,
+// the same waves per SIMD, no scratch, no LDS of its own (profiles/i8_conv_residual/kernel_resources.txt).
 #ifndef LQ_I8_DIRECT_QUANT_HPP_
 #define LQ_I8_DIRECT_QUANT_HPP_
 #include "lq_i8_direct.hpp"
@@ -42,11 +49,19 @@ struct I8ConvQuantParams {
     int32_t affine_first;     // 0: aff(act(Y)); 1: act(aff(Y))
     int32_t OT, CPo;          // column tiles of the padded row; its bytes
 };
+// lq_i8_conv2d_quantize_residual: the same, and a residual pixel operand of the OUTPUT's shape.  A derived struct, passed only to
+// the RES = true kernels, so that the kernel without a residual keeps its argument block and with it its instruction stream
+struct I8ConvQuantResParams : I8ConvQuantParams {
+    const uint8_t* res_codes;     // [M][CPo]
+    const float* res_scales;      // [M]
+};
+template <bool RES>
+using I8ConvQuantArgs = std::conditional_t<RES, I8ConvQuantResParams, I8ConvQuantParams>;
 
 __device__ __forceinline__ float i8_relu(float v) { return v > 0.f ? v : (v != v ? v : 0.f); }
 
-template <int STEP, int NTT, bool BLOCK>
-__global__ __launch_bounds__(kBlock) void k_i8_conv2d_quantize(const I8ConvQuantParams q) {
+template <int STEP, int NTT, bool BLOCK, bool RES>
+__global__ __launch_bounds__(kBlock) void k_i8_conv2d_quantize(const I8ConvQuantArgs<RES> q) {
     using Fr = I8Frag<STEP>;
     using FT = typename Fr::T;
     using Step = GroupStep<true, GroupParams>;
@@ -147,6 +162,27 @@ __global__ __launch_bounds__(kBlock) void k_i8_conv2d_quantize(const I8ConvQuant
     // result tile: column (lane & 15) on the lane, rows 4 (lane >> 4) + r in the registers.  The filter's scale, the bias, the
     // epilogue, and +0 for what lies past M, past co or in a tile the wave does not own (a clamped tile holds a copy of the last one)
     const int col = lane & 15, g4 = (lane >> 4) * 4, qd = lane & 3;
+    // RES: the residual, requested only now, after the tap loop (holding NTT dwords through it costs the widest forms registers
+    // they do not have).  Lane qd of a quad reads the dword it later STORES to -- row g4 + qd, the quad's four columns -- and the
+    // transpose that lays the codes out for the store is its own inverse, so it brings byte r = row g4 + r of column `col` here.
+    // A lane forms no address for a row past M or a tile the wave does not own.  The row scales: lane l < 16 of each sixteen
+    // reads row l's once; row g4 + r's comes across by the shuffle that brings the pixel scales in the tap loop
+    uint32_t rw[RES ? NTT : 1];
+    float rsc[4];
+    if constexpr (RES) {
+        const int32_t ms = mt * kI8TileLines + g4 + qd;
+        const uint8_t* src = q.res_codes + (int64_t)ms * q.CPo + (col & ~3);
+#pragma unroll
+        for (int j = 0; j < NTT; ++j) {
+            rw[j] = 0u;
+            if (j < own && ms < p.M) rw[j] = *reinterpret_cast<const uint32_t*>(src + (t0 + j) * kI8TileLines);
+        }
+        const int32_t mr = mt * kI8TileLines + col;
+        float rs = 0.f;
+        if (mr < p.M) rs = q.res_scales[mr];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) rsc[r] = __shfl(rs, g4 + r);
+    }
     bool live_n[NTT];
 #pragma unroll
     for (int j = 0; j < NTT; ++j) {
@@ -156,12 +192,18 @@ __global__ __launch_bounds__(kBlock) void k_i8_conv2d_quantize(const I8ConvQuant
         const float bv = (p.bias && live_n[j]) ? p.bias[n] : 0.f;
         const float ps = (q.post_scale && live_n[j]) ? q.post_scale[n] : 0.f;
         const float ph = (q.post_scale && live_n[j]) ? q.post_shift[n] : 0.f;
+        uint32_t rt = 0u;                              // RES: the residual codes of column `col`, row g4 + r in byte r
+        if constexpr (RES) rt = mx_quad_gather(rw[j], qd);        // every lane takes part in the transpose
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int32_t m = mt * kI8TileLines + g4 + r;
             float v = i8_scalar(__fmul_rn(y[j][r], sk));
             if (p.bias) v = i8_scalar(__fadd_rn(v, bv));
             if (q.post_scale && q.affine_first) v = i8_scalar(__fadd_rn(i8_scalar(__fmul_rn(v, ps)), ph));
+            if constexpr (RES) {                       // directly before the activation; the product and the sum round separately
+                const float rr = i8_scalar(__fmul_rn((float)(int8_t)(rt >> (8 * r)), rsc[r]));
+                v = i8_scalar(__fadd_rn(v, rr));
+            }
             if (q.act == LQ_ACT_RELU) v = i8_relu(v);
             if (q.post_scale && !q.affine_first) v = i8_scalar(__fadd_rn(i8_scalar(__fmul_rn(v, ps)), ph));
             y[j][r] = (live_n[j] && m < p.M) ? v : 0.f;
@@ -227,19 +269,20 @@ __global__ __launch_bounds__(kBlock) void k_i8_conv2d_quantize(const I8ConvQuant
     }
 }
 
-// the instantiation by the padded row's tiles: host side, called from lq_i8_conv2d_quantize
-template <int STEP>
-inline void i8_conv2d_quantize_launch(const I8ConvQuantParams& q, hipStream_t st) {
+// the instantiation by the padded row's tiles: host side, called from lq_i8_conv2d_quantize (RES = false) and
+// lq_i8_conv2d_quantize_residual (RES = true)
+template <int STEP, bool RES>
+inline void i8_conv2d_quantize_launch(const I8ConvQuantArgs<RES>& q, hipStream_t st) {
     const dim3 blk(kBlock);
     if (q.OT <= 8) {              // a row per wave, four A tiles per block
         const dim3 grid((unsigned)((q.c.MT + 3) / 4));
-        if (q.OT <= 2) hipLaunchKernelGGL((k_i8_conv2d_quantize<STEP, 2, false>), grid, blk, 0, st, q);
-        else if (q.OT <= 4) hipLaunchKernelGGL((k_i8_conv2d_quantize<STEP, 4, false>), grid, blk, 0, st, q);
-        else hipLaunchKernelGGL((k_i8_conv2d_quantize<STEP, 8, false>), grid, blk, 0, st, q);
+        if (q.OT <= 2) hipLaunchKernelGGL((k_i8_conv2d_quantize<STEP, 2, false, RES>), grid, blk, 0, st, q);
+        else if (q.OT <= 4) hipLaunchKernelGGL((k_i8_conv2d_quantize<STEP, 4, false, RES>), grid, blk, 0, st, q);
+        else hipLaunchKernelGGL((k_i8_conv2d_quantize<STEP, 8, false, RES>), grid, blk, 0, st, q);
     } else {                      // a row per block: ceil(OT / 4) tiles on the widest wave
         const dim3 grid((unsigned)q.c.MT);
-        if (q.OT <= 16) hipLaunchKernelGGL((k_i8_conv2d_quantize<STEP, 4, true>), grid, blk, 0, st, q);
-        else hipLaunchKernelGGL((k_i8_conv2d_quantize<STEP, 8, true>), grid, blk, 0, st, q);
+        if (q.OT <= 16) hipLaunchKernelGGL((k_i8_conv2d_quantize<STEP, 4, true, RES>), grid, blk, 0, st, q);
+        else hipLaunchKernelGGL((k_i8_conv2d_quantize<STEP, 8, true, RES>), grid, blk, 0, st, q);
     }
 }
 

@@ -2750,10 +2750,16 @@ int lq_i8_conv2d(const void* pix_codes, const void* pix_scales, const void* k_co
 // ---- the direct int8 convolution with a pixel-operand epilogue (lq_i8_direct_quant.hpp) ----
 constexpr int64_t kI8ConvQuantMaxCo = 512;      // 32 column tiles: four waves by eight, a whole output row resident in one block
 
-int lq_i8_conv2d_quantize(const void* pix_codes, const void* pix_scales, const void* k_codes, const void* k_scales, const float* bias,
-                          const lq_conv_geom* g, int64_t co, const float* post_scale, const float* post_shift, int activation,
-                          int affine_first, void* out_codes, void* out_scales, void* stream) {
-    const char* fn = __func__;
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + nb && b0 < a0 + na;
+}
+
+// the body of lq_i8_conv2d_quantize (residual = false; res_* are not read) and lq_i8_conv2d_quantize_residual
+static int i8_conv2d_quantize_entry(const char* fn, bool residual, const void* pix_codes, const void* pix_scales, const void* k_codes,
+                                    const void* k_scales, const float* bias, const lq_conv_geom* g, int64_t co, const float* post_scale,
+                                    const float* post_shift, int activation, int affine_first, const void* res_codes,
+                                    const void* res_scales, void* out_codes, void* out_scales, void* stream) {
     ConvDims cd;
     int rc = conv_geom_dims(fn, g, cd);            // the xs_* fields are not read
     if (rc) return rc;
@@ -2771,6 +2777,18 @@ int lq_i8_conv2d_quantize(const void* pix_codes, const void* pix_scales, const v
     if ((rc = check_operand_buffers(fn, pix_codes, pix_scales, kI8ScaleAlign))) return rc;
     if ((rc = check_operand_buffers(fn, k_codes, k_scales, kI8ScaleAlign))) return rc;
     if ((rc = check_operand_buffers(fn, out_codes, out_scales, kI8ScaleAlign))) return rc;
+    if (residual) {
+        if (!res_codes || !res_scales)
+            return fail(LQ_EINVAL, "%s: argument '%s' is NULL: the call without a residual is lq_i8_conv2d_quantize", fn,
+                        res_codes ? "res_scales" : "res_codes");
+        if (!aligned(res_codes, 16) || !aligned(res_scales, kI8ScaleAlign))
+            return fail(LQ_EALIGN, "%s: %s is not 16-byte aligned", fn, aligned(res_codes, 16) ? "res_scales" : "res_codes");
+        // a row's output scale is written by one lane while other lanes still read the row's residual: no in-place update
+        const size_t cb = (size_t)(cd.M * dout.CP), sb = (size_t)cd.M * sizeof(float);
+        if (ranges_overlap(out_codes, cb, res_codes, cb) || ranges_overlap(out_codes, cb, res_scales, sb) ||
+            ranges_overlap(out_scales, sb, res_codes, cb) || ranges_overlap(out_scales, sb, res_scales, sb))
+            return fail(LQ_EINVAL, "%s: an output buffer overlaps a residual buffer", fn);
+    }
     if ((rc = check_gemm_bias(fn, bias))) return rc;
     if (post_scale && (!aligned(post_scale, 4) || !aligned(post_shift, 4)))
         return fail(LQ_EALIGN, "%s: post_scale or post_shift is not 4-byte aligned", fn);
@@ -2781,7 +2799,8 @@ int lq_i8_conv2d_quantize(const void* pix_codes, const void* pix_scales, const v
     const int64_t MT = (cd.M + kI8TileLines - 1) / kI8TileLines;
     dim3 unused;
     if ((rc = gemm_grid(fn, 1, MT, cd.M, unused))) return rc;      // lq_i8_conv2d's limit on M, kept: the two calls take the same runs
-    I8ConvQuantParams q{};
+    I8ConvQuantResParams qr{};
+    I8ConvQuantParams& q = qr;          // the launch without a residual passes this part alone
     I8Conv2dParams& p = q.c;
     p.pix_codes = (const uint8_t*)pix_codes;
     p.pix_scales = (const float*)pix_scales;
@@ -2815,9 +2834,31 @@ int lq_i8_conv2d_quantize(const void* pix_codes, const void* pix_scales, const v
     q.affine_first = affine_first;
     q.CPo = (int32_t)dout.CP;
     q.OT = (int32_t)(dout.CP / kI8TileLines);
-    if (dk.step == 64) i8_conv2d_quantize_launch<64>(q, (hipStream_t)stream);
-    else i8_conv2d_quantize_launch<32>(q, (hipStream_t)stream);
+    if (residual) {
+        qr.res_codes = (const uint8_t*)res_codes;
+        qr.res_scales = (const float*)res_scales;
+        if (dk.step == 64) i8_conv2d_quantize_launch<64, true>(qr, (hipStream_t)stream);
+        else i8_conv2d_quantize_launch<32, true>(qr, (hipStream_t)stream);
+        return check_hip("direct int8 convolution with residual pixel-operand epilogue");
+    }
+    if (dk.step == 64) i8_conv2d_quantize_launch<64, false>(q, (hipStream_t)stream);
+    else i8_conv2d_quantize_launch<32, false>(q, (hipStream_t)stream);
     return check_hip("direct int8 convolution with pixel-operand epilogue");
+}
+
+int lq_i8_conv2d_quantize(const void* pix_codes, const void* pix_scales, const void* k_codes, const void* k_scales, const float* bias,
+                          const lq_conv_geom* g, int64_t co, const float* post_scale, const float* post_shift, int activation,
+                          int affine_first, void* out_codes, void* out_scales, void* stream) {
+    return i8_conv2d_quantize_entry(__func__, false, pix_codes, pix_scales, k_codes, k_scales, bias, g, co, post_scale, post_shift,
+                                    activation, affine_first, nullptr, nullptr, out_codes, out_scales, stream);
+}
+
+int lq_i8_conv2d_quantize_residual(const void* pix_codes, const void* pix_scales, const void* k_codes, const void* k_scales,
+                                   const float* bias, const lq_conv_geom* g, int64_t co, const float* post_scale,
+                                   const float* post_shift, int activation, int affine_first, const void* res_codes,
+                                   const void* res_scales, void* out_codes, void* out_scales, void* stream) {
+    return i8_conv2d_quantize_entry(__func__, true, pix_codes, pix_scales, k_codes, k_scales, bias, g, co, post_scale, post_shift,
+                                    activation, affine_first, res_codes, res_scales, out_codes, out_scales, stream);
 }
 
 static int i8_operand_decode(const char* fn, bool affine, bool w4, const void* codes, const void* scales, const void* offsets, int64_t L,

@@ -1126,15 +1126,20 @@ class _ConvBase(_HostLayer):
             y = y.view(B, OH, OW, self.filters)                   # [M][co] is NHWC: no transposition launch
             return y if self.data_format == "NHWC" else y.permute(0, 3, 1, 2)
 
-    def _direct_step(self, x, operand, qb, max_lines=None, out_pixels=False, activation=None, affine=None, affine_first=False):
+    def _direct_step(self, x, operand, qb, max_lines=None, out_pixels=False, activation=None, affine=None, affine_first=False,
+                     residual=None):
         """One layer of a direct-conv chain: ``x`` a tensor in the layer's data format (quantised here, per run) or an ops.I8Pixels;
         the result the fp32 view ``_direct_conv`` returns, or (``out_pixels``) the next conv's ops.I8Pixels from the product's own
-        epilogue (ops.i8_conv2d_quantize).  The batch is cut into runs of whole images by lines, as ``_direct_conv`` cuts it."""
+        epilogue (ops.i8_conv2d_quantize).  The batch is cut into runs of whole images by lines, as ``_direct_conv`` cuts it; a
+        ``residual`` (an ops.I8Pixels of the result's shape) is cut by the same images."""
+        def images_of(px):        # a cut: the codes of whole images stay on the 16-byte grid (CP % 32 == 0); the scales may not
+            def cut(b0, b1):
+                scales = px.scales[b0:b1]
+                return ops.I8Pixels(px.codes[b0:b1], scales.clone() if scales.data_ptr() % 16 else scales, (b1 - b0, *px.shape[1:]))
+            return cut
         if isinstance(x, ops.I8Pixels):
             B, C, H, W = x.shape
-            def run(b0, b1):      # a cut: the codes of whole images stay on the 16-byte grid (CP % 32 == 0); the scales may not
-                scales = x.scales[b0:b1]
-                return ops.I8Pixels(x.codes[b0:b1], scales.clone() if scales.data_ptr() % 16 else scales, (b1 - b0, C, H, W))
+            run = images_of(x)
         else:
             if x.dim() != 4:
                 raise ValueError(f"{self.name}: the input must have four axes, got shape {tuple(x.shape)}")
@@ -1148,7 +1153,11 @@ class _ConvBase(_HostLayer):
         images = max(1, min(B, fit // per))
         runs = [(b0, min(B, b0 + images)) for b0 in range(0, B, images)]
         if out_pixels:
-            outs = [ops.i8_conv2d_quantize(run(b0, b1), operand, qb, self.strides, padding, activation, affine, affine_first)
+            if residual is not None and (not isinstance(residual, ops.I8Pixels) or tuple(residual.shape) != (B, self.filters, OH, OW)):
+                raise ValueError(f"{self.name}: the residual must be an ops.I8Pixels of the result's shape {(B, self.filters, OH, OW)}, got "
+                                 f"{tuple(residual.shape) if isinstance(residual, ops.I8Pixels) else type(residual).__name__}")
+            res = images_of(residual) if residual is not None else (lambda b0, b1: None)
+            outs = [ops.i8_conv2d_quantize(run(b0, b1), operand, qb, self.strides, padding, activation, affine, affine_first, res(b0, b1))
                     for b0, b1 in runs]
             if len(outs) == 1:
                 return outs[0]
@@ -1159,7 +1168,8 @@ class _ConvBase(_HostLayer):
         y = y.view(B, OH, OW, self.filters)
         return y if self.data_format == "NHWC" else y.permute(0, 3, 1, 2)
 
-    def call_i8_direct(self, inputs, max_lines=None, out_pixels=False, activation=None, affine=None, affine_first=False):
+    def call_i8_direct(self, inputs, max_lines=None, out_pixels=False, activation=None, affine=None, affine_first=False,
+                       residual=None):
         """The layer as a direct int8 convolution, under ``no_grad``: the inputs quantised ONCE per pixel to symmetric 8-bit integers
         (ops.i8_pixels_quantize: an int8 NHWC copy, one scale per pixel), convolved with ``i8_direct_operand()`` on the int8 matrix
         instruction by ops.i8_conv2d -- TensorFlow 'SAME' padding as ``call`` pads, or 'VALID' -- plus the fake-quantised bias where
@@ -1170,11 +1180,13 @@ class _ConvBase(_HostLayer):
         ``inputs`` may be an ops.I8Pixels (the pixel operand another conv's epilogue wrote): it is multiplied as it is.
         ``out_pixels=True``: the result is the NEXT conv's ops.I8Pixels, written by the product's own epilogue
         (ops.i8_conv2d_quantize) after ``activation`` (None or "relu") and ``affine = (g, h)`` (``bn_affine``), in the order
-        ``affine_first`` says; byte for byte ``ops.i8_pixels_quantize`` of that result.  Without it an epilogue is refused."""
+        ``affine_first`` says; byte for byte ``ops.i8_pixels_quantize`` of that result.  Without it an epilogue is refused.
+        ``residual`` (with ``out_pixels=True``): an ops.I8Pixels of the result's shape, decoded and added directly before the
+        activation by the same epilogue (the basic ResNet block)."""
         _check_max_lines(max_lines)
-        if not out_pixels and (activation is not None or affine is not None or affine_first):
-            raise ValueError(f"{self.name}: the fp32 result takes no epilogue (activation={activation!r}, affine, affine_first): apply "
-                             "it to the result, or ask for out_pixels=True")
+        if not out_pixels and (activation is not None or affine is not None or affine_first or residual is not None):
+            raise ValueError(f"{self.name}: the fp32 result takes no epilogue (activation={activation!r}, affine, affine_first, "
+                             "residual): apply it to the result, or ask for out_pixels=True")
         direct = isinstance(inputs, ops.I8Pixels) or out_pixels
         if not self.built:
             if isinstance(inputs, ops.I8Pixels):
@@ -1185,7 +1197,7 @@ class _ConvBase(_HostLayer):
             qb = self.nested_q_b_layer(self.b) if self._has_bias else None
             if not direct:
                 return self._direct_conv(inputs, operand, qb, max_lines)
-            return self._direct_step(inputs, operand, qb, max_lines, out_pixels, activation, affine, affine_first)
+            return self._direct_step(inputs, operand, qb, max_lines, out_pixels, activation, affine, affine_first, residual)
 
 
 class CustomConv2DLayer(_ConvBase):
@@ -1395,7 +1407,12 @@ class i8_hardware(_matrix_hardware):
     three conv -> relu -> BN -> conv pairs -- evaluates each chain whose layers pass ``i8_direct_eligible`` through
     ``i8_conv_chain`` in eval mode: every conv but the last writes the next conv's pixel operand from its own epilogue
     (ops.i8_conv2d_quantize), the BatchNorm folded to ``bn_affine``'s ``(g, h)`` on entry, and no fp32 activation exists between
-    them.  ``fused_conv_layers`` lists the convs with such an epilogue.  The outputs differ from ``fused_convs=False`` by
+    them.  ``fused_conv_layers`` lists the convs with such an epilogue.  A module whose class sets ``i8_chains_out_pixels = True``
+    (models._ResidualBlock) runs its chains with ``out_pixels=True`` -- every conv through the epilogue, conv2 with the shortcut as
+    its residual, a chain of one conv allowed -- takes them all or none, and has every conv of them listed: models.ResNet18Like
+    then runs its eight basic blocks conv to conv in int8 (19 convs listed; the last block's conv2 reads conv1's pixel operand
+    but writes fp32 for the mean).  A model that states no chains, or reaches more than 512 filters (models.ResNet50Like), keeps
+    running unfused.  The outputs differ from ``fused_convs=False`` by
     roundings: ``aff`` is not torch's BatchNorm kernel bit for bit, and an ulp can move a code.  Refused without ``direct`` or with
     ``emulate``.  Without it (the default) nothing changes."""
 
@@ -1459,17 +1476,20 @@ class i8_hardware(_matrix_hardware):
         with torch.no_grad():
             for mod in self.model.modules():
                 stated = mod.i8_conv_chains() if callable(getattr(mod, "i8_conv_chains", None)) else []
+                every = bool(getattr(mod, "i8_chains_out_pixels", False))      # the module runs its chains with out_pixels=True
                 parked = []
                 for chain in stated:
-                    ok = len(chain) > 1 and all(i8_direct_eligible(c) and act in ops.MX_ACTIVATIONS for c, act, _, _ in chain) \
-                        and all(c.filters <= ops.I8_CONV_QUANT_MAX_FILTERS for c, _, _, _ in chain[:-1])
+                    ok = (len(chain) > 1 or every) and all(i8_direct_eligible(c) and act in ops.MX_ACTIVATIONS for c, act, _, _ in chain) \
+                        and all(c.filters <= ops.I8_CONV_QUANT_MAX_FILTERS for c, _, _, _ in (chain if every else chain[:-1]))
                     parked.append([(c, act, bn_affine(aff) if isinstance(aff, nn.BatchNorm2d) else aff, first)
                                    for c, act, aff, first in chain] if ok else None)
+                if every and any(chain is None for chain in parked):          # such a module's chains feed each other: all or none
+                    continue
                 if any(chain is not None for chain in parked):
                     for chain in filter(None, parked):
                         for c, _, _, _ in chain:
                             c._i8_chain_hw = c._i8_direct_hw or (c.i8_direct_operand(), c.nested_q_b_layer(c.b).detach() if c._has_bias else None)
-                        self.fused_conv_layers += [c for c, _, _, _ in chain[:-1]]
+                        self.fused_conv_layers += [c for c, _, _, _ in (chain if every else chain[:-1])]
                     mod._i8_fused_convs = parked
                     self._fused_conv_modules.append(mod)
 
@@ -1570,7 +1590,7 @@ def bn_affine(bn: nn.BatchNorm2d):
         return g.float(), (beta - bn.running_mean.double() * g).float()
 
 
-def i8_conv_chain(x, chain, max_lines=None):
+def i8_conv_chain(x, chain, max_lines=None, out_pixels=False):
     """``chain`` = [(conv, activation, affine, affine_first), ...]: conv layers applied one after the other as direct int8
     convolutions, under ``no_grad``.  ``x`` is quantised once per pixel; every layer but the last goes through
     ops.i8_conv2d_quantize, whose epilogue applies ``activation`` (None or "relu") and ``affine`` (None or ``(g, h)``, ``bn_affine``)
@@ -1579,16 +1599,25 @@ def i8_conv_chain(x, chain, max_lines=None):
     ``call_i8_direct`` ..., without the fp32 activations and their launches.  A batch whose lines exceed the launch limit (or
     ``max_lines``) is cut into runs of whole images; the result does not depend on the cut.  Inside ``i8_hardware(fused_convs=True)``
     the operands parked on its entry are used, otherwise they are built here.  ValueError naming the reason for a layer that cannot
-    take the path (``i8_direct_eligible``), more than 512 filters on a layer with an epilogue, or an epilogue on the last layer."""
+    take the path (``i8_direct_eligible``), more than 512 filters on a layer with an epilogue, or an epilogue on the last layer.
+    A step may carry a fifth entry, the RESIDUAL of its epilogue: an ops.I8Pixels of the step's output shape (or None), decoded and
+    added directly before the activation (ops.i8_conv2d_quantize, ``residual``).  ``out_pixels=True``: the LAST layer goes through
+    the epilogue too, with its activation, affine and residual, and the chain returns an ops.I8Pixels; ``x`` may itself be one.
+    So a basic ResNet block is ``[(conv1, "relu", bn1, True), (conv2, "relu", bn2, True, shortcut)]`` with ``out_pixels=True``.
+    A residual on a last layer that writes fp32 is refused: the fp32 result has no epilogue to add it in."""
     fn = "i8_conv_chain"
     chain = [tuple(step) for step in chain]
     _check_max_lines(max_lines)
     if not chain:
         raise ValueError(f"{fn}: the chain is empty")
     for k, step in enumerate(chain):
-        if len(step) != 4:
-            raise ValueError(f"{fn}: step {k} must be (conv, activation, affine, affine_first), got {len(step)} entries")
-        layer, activation, affine, affine_first = step
+        if len(step) not in (4, 5):
+            raise ValueError(f"{fn}: step {k} must be (conv, activation, affine, affine_first) or the same and a residual, got "
+                             f"{len(step)} entries")
+        layer, activation, affine, affine_first = step[:4]
+        residual = step[4] if len(step) == 5 else None
+        if residual is not None and not isinstance(residual, ops.I8Pixels):
+            raise ValueError(f"{fn}: step {k}: the residual must be an ops.I8Pixels or None, got {type(residual).__name__}")
         if not isinstance(layer, _ConvBase):
             raise ValueError(f"{fn}: layer {k} is a {type(layer).__name__}: only conv layers run as direct int8 convolutions")
         try:
@@ -1596,19 +1625,24 @@ def i8_conv_chain(x, chain, max_lines=None):
             ops.check_mx_activation(activation)
         except ValueError as e:
             raise ValueError(f"{fn}: {layer.name}: {e}") from None
-        if k == len(chain) - 1:
+        if k == len(chain) - 1 and not out_pixels:
             if activation is not None or affine is not None or affine_first:
                 raise ValueError(f"{fn}: {layer.name}: the last layer writes fp32 and takes no epilogue (got activation={activation!r}, "
                                  f"affine {'given' if affine is not None else 'None'}): apply it to the result")
+            if residual is not None:
+                raise ValueError(f"{fn}: {layer.name}: the last layer writes fp32 and has no epilogue to add a residual in: add it to "
+                                 "the result, or ask for out_pixels=True")
         elif layer.filters > ops.I8_CONV_QUANT_MAX_FILTERS:
             raise ValueError(f"{fn}: {layer.name}: {layer.filters} filters: the epilogue holds a whole output row in one thread block, "
                              f"at most {ops.I8_CONV_QUANT_MAX_FILTERS}")
     with torch.no_grad():
         a = x
-        for k, (layer, activation, affine, affine_first) in enumerate(chain):
+        for k, step in enumerate(chain):
+            layer, activation, affine, affine_first = step[:4]
             hw = layer._i8_chain_hw
             operand, qb = hw if hw is not None else (layer.i8_direct_operand(), layer.nested_q_b_layer(layer.b) if layer._has_bias else None)
-            a = layer._direct_step(a, operand, qb, max_lines, k < len(chain) - 1, activation, affine, affine_first)
+            a = layer._direct_step(a, operand, qb, max_lines, out_pixels or k < len(chain) - 1, activation, affine, affine_first,
+                                   step[4] if len(step) == 5 else None)
         return a
 
 

@@ -35,6 +35,7 @@ import torch.nn.functional as F
 
 from .layers import CustomConv2DLayer, CustomDenseLayer, RandomNormal, i8_conv_chain, i8_dense_chain, l2, mx_dense_chain
 from .losses import softmax
+from .ops import i8_pixels_quantize
 
 
 def _bn(c: int) -> nn.BatchNorm2d:
@@ -168,6 +169,34 @@ class _ResidualBlock(nn.Module):
             self.shortcut = mk(ci, (1, 1), stride, "custom_conv2d_layer_shortcut")
             self.bn_s = _bn(filters)
 
+    i8_chains_out_pixels = True        # layers.i8_hardware(fused_convs=True): every chain below ends in the epilogue
+
+    def i8_conv_chains(self):
+        """The block as layers.i8_conv_chain takes it with ``out_pixels=True`` (the BatchNorms stand for their affines): conv1 ->
+        BN -> relu -> conv2 -> BN, whose last step gets the shortcut as its residual when the block runs, and for a stride-2 block
+        the one-step chain of the shortcut."""
+        chains = [[(self.conv1, "relu", self.bn1, True), (self.conv2, "relu", self.bn2, True)]]
+        if self.shortcut is not None:
+            chains.append([(self.shortcut, None, self.bn_s, True)])
+        return chains
+
+    def i8_fused(self):
+        """The chains parked by layers.i8_hardware(..., fused_convs=True), in eval mode and when every one of them fuses; or None."""
+        fused = getattr(self, "_i8_fused_convs", None)
+        return fused if fused is not None and not self.training and all(c is not None for c in fused) else None
+
+    def forward_pixels(self, x, fused, fp32_out=False):
+        """The block from the pixel operand ``x`` (ops.I8Pixels) to the next block's: the shortcut is ``x`` itself or the shortcut
+        conv's epilogue, and conv2's epilogue adds it before the relu (ops.i8_conv2d_quantize, ``residual``).  ``fp32_out`` (the
+        model's last block): conv2 writes fp32 (ops.i8_conv2d) and its affine, the decoded shortcut, the add and the relu are torch's."""
+        sc = x if self.shortcut is None else i8_conv_chain(x, fused[1], out_pixels=True)
+        first, (conv2, act, aff, aff_first) = fused[0]
+        if not fp32_out:
+            return i8_conv_chain(x, [first, (conv2, act, aff, aff_first, sc)], out_pixels=True)
+        y = i8_conv_chain(x, [first, (conv2, None, None, False)])
+        r = sc.codes[..., :conv2.filters].view(torch.int8).float() * sc.scales.unsqueeze(-1)       # one rounding: the epilogue's r
+        return F.relu(y * aff[0].view(1, -1, 1, 1) + aff[1].view(1, -1, 1, 1) + r.permute(0, 3, 1, 2))
+
     def forward(self, x):
         sc = x
         y = F.relu(self.bn1(self.conv1(x)))
@@ -207,8 +236,15 @@ class ResNet18Like(nn.Module):
         pw = max((-(-w // 2) - 1) * 2 + 3 - w, 0)
         x = F.pad(x, (pw // 2, pw - pw // 2, ph // 2, ph - ph // 2), value=float("-inf"))
         x = self.drop0(F.max_pool2d(x, 3, 2))
-        for b in self.blocks:
-            x = b(x)
+        fused = [b.i8_fused() for b in self.blocks]               # inside layers.i8_hardware(..., fused_convs=True), eval mode
+        if not self.training and all(f is not None for f in fused):
+            a = i8_pixels_quantize(x)                             # the one quantisation: int8 pixel operands from here to the last conv
+            for b, f in zip(self.blocks[:-1], fused):
+                a = b.forward_pixels(a, f)
+            x = self.blocks[-1].forward_pixels(a, fused[-1], fp32_out=True)
+        else:
+            for b in self.blocks:
+                x = b(x)
         x = self.drop2(torch.mean(self.drop1(x), dim=(2, 3)))
         return softmax(self.out(x), dim=1)
 

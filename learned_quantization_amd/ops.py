@@ -1320,6 +1320,21 @@ def _check_i8_conv_operands(pixels: I8Pixels, kernel: I8ConvKernel):
     return dev
 
 
+def _check_i8_residual(residual: I8Pixels, shape, codes_shape, dev):
+    """The residual of ``i8_conv2d_quantize``: a pixel operand of the output's ``shape``, whole, contiguous and on ``dev`` -- the
+    rules of ``_check_i8_conv_operands``."""
+    if not isinstance(residual, I8Pixels):
+        raise ValueError(f"residual must be an I8Pixels (i8_pixels_quantize, or an epilogue's result), got {type(residual).__name__}")
+    if tuple(int(d) for d in residual.shape) != tuple(shape):
+        raise ValueError(f"residual has shape {tuple(residual.shape)}, not the output's (B, co, OH, OW) = {tuple(shape)}")
+    for name, t, dtype, want in (("residual.codes", residual.codes, torch.uint8, tuple(codes_shape)),
+                                 ("residual.scales", residual.scales, torch.float32, tuple(codes_shape[:3]))):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != want or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {want} for an output {tuple(shape)}")
+        if not t.is_cuda or t.device != dev:
+            raise RuntimeError(f"{name} is on {t.device}: the residual must be on the operands' HIP device; there is no CPU fallback")
+
+
 def i8_conv2d(pixels: I8Pixels, kernel: I8ConvKernel, bias: Optional[torch.Tensor] = None, strides=(1, 1), padding=(0, 0, 0, 0),
               out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The convolution of a pixel operand with a packed kernel on the int8 matrix instruction, ``Y (B OH OW, co)`` in fp32 -- NHWC
@@ -1340,12 +1355,16 @@ def i8_conv2d(pixels: I8Pixels, kernel: I8ConvKernel, bias: Optional[torch.Tenso
 
 
 def i8_conv2d_quantize(pixels: I8Pixels, kernel: I8ConvKernel, bias: Optional[torch.Tensor] = None, strides=(1, 1), padding=(0, 0, 0, 0),
-                       activation=None, affine=None, affine_first: bool = False) -> I8Pixels:
+                       activation=None, affine=None, affine_first: bool = False, residual: Optional[I8Pixels] = None) -> I8Pixels:
     """The pixel operand of the NEXT conv, written by the convolution's own epilogue (include/lq_hip.h, lq_i8_conv2d_quantize): byte
     for byte ``i8_pixels_quantize`` of ``v`` seen as ``(B, co, OH, OW)``, where ``v = aff(act(Y))`` (``affine_first=False``: conv,
     relu, BatchNorm) or ``v = act(aff(Y))`` (``affine_first=True``), ``Y`` is ``i8_conv2d``'s result bit for bit and ``aff(v) = v *
     g + h`` with ``affine = (g, h)``, float32 ``(co,)`` each, the product and the sum rounding separately.  One launch; no fp32
-    matrix.  ``co`` above 512 is refused."""
+    matrix.  ``co`` above 512 is refused.
+    ``residual``: an ``I8Pixels`` of the OUTPUT's shape ``(B, co, OH, OW)`` (lq_i8_conv2d_quantize_residual), decoded as ``r = codes *
+    scale`` (one rounding) and added directly before the activation: ``v = aff(act(Y + r))``, or ``v = act(aff(Y) + r)`` with
+    ``affine_first`` -- the basic ResNet block's ``relu(bn2(conv2(y)) + shortcut)``.  Still one launch.  ValueError when its shape
+    is not the output's."""
     import ctypes
     act = check_mx_activation(activation)
     dev = _check_i8_conv_operands(pixels, kernel)
@@ -1366,6 +1385,13 @@ def i8_conv2d_quantize(pixels: I8Pixels, kernel: I8ConvKernel, bias: Optional[to
     cb, _ = i8_pixels_bytes(B, co, OH, OW)
     codes = torch.empty((B, OH, OW, cb // (B * OH * OW)), dtype=torch.uint8, device=dev)
     scales = torch.empty((B, OH, OW), dtype=torch.float32, device=dev)
+    if residual is not None:
+        _check_i8_residual(residual, (B, co, OH, OW), tuple(codes.shape), dev)
+        _hip.check(lib.lq_i8_conv2d_quantize_residual(
+            _hip.ptr(pixels.codes), _hip.ptr(pixels.scales), _hip.ptr(kernel.codes), _hip.ptr(kernel.scales), _hip.ptr(bias), ctypes.byref(g),
+            co, _hip.ptr(post[0]), _hip.ptr(post[1]), act, int(bool(affine_first)), _hip.ptr(residual.codes), _hip.ptr(residual.scales),
+            _hip.ptr(codes), _hip.ptr(scales), _hip.stream_ptr(dev)), "lq_i8_conv2d_quantize_residual")
+        return I8Pixels(codes, scales, (B, co, OH, OW))
     _hip.check(lib.lq_i8_conv2d_quantize(_hip.ptr(pixels.codes), _hip.ptr(pixels.scales), _hip.ptr(kernel.codes), _hip.ptr(kernel.scales),
                                          _hip.ptr(bias), ctypes.byref(g), co, _hip.ptr(post[0]), _hip.ptr(post[1]), act,
                                          int(bool(affine_first)), _hip.ptr(codes), _hip.ptr(scales), _hip.stream_ptr(dev)),

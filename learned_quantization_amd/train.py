@@ -744,7 +744,7 @@ def i8_eval(model, x, y, act_block=0, convs=False, fused=False, offsets=False, d
                 with L.i8_hardware(model, probe.act_block, convs=True, offsets=offsets, direct=True, fused_convs=fc) as hwf:
                     if fc and not hwf.fused_conv_layers:
                         raise ValueError("i8_eval: fused_convs=True needs a model that states conv chains (i8_conv_chains(), as "
-                                         "models.CIFARCNN does) of convs that can run as direct int8 convolutions")
+                                         "models.CIFARCNN and the basic blocks of models.ResNet18Like do) of convs that can run as direct int8 convolutions")
                     if fc:
                         n_fused_convs = len(hwf.fused_conv_layers)
                     outs.append(model(x))

@@ -20,7 +20,7 @@
 // The tap walk is k_i8_conv2d's for one A tile: (i, j, cs) wave-uniform, each lane's pixel formed from its own line, the fragments
 // of the next step requested before this step's instructions, the exact int32 sum of a tap flushed under the pixel scale of the
 // result ROW, which comes across by a shuffle.  Then the filter's scale, the bias, and the epilogue in the one-wide fp32 forms
-// (i8_scalar); a row's absmax partials merge over its 16 lanes by the four DPP steps of i8_merge_dpp; the scale rule and the
+// (i8_scalar); a row's absmax partials merge over its 16 lanes by the four DPP steps of i8_row_absmax; the scale rule and the
 // element step are k_i8_pixels' own device functions; a quad's 4 x 4 bytes are transposed in registers (mx_quad_gather) so that a
 // lane stores one dword per tile into the NHWC row, and one lane per row stores the scale.
 //
@@ -57,8 +57,6 @@ struct I8ConvQuantResParams : I8ConvQuantParams {
 };
 template <bool RES>
 using I8ConvQuantArgs = std::conditional_t<RES, I8ConvQuantResParams, I8ConvQuantParams>;
-
-__device__ __forceinline__ float i8_relu(float v) { return v > 0.f ? v : (v != v ? v : 0.f); }
 
 template <int STEP, int NTT, bool BLOCK, bool RES>
 __global__ __launch_bounds__(kBlock) void k_i8_conv2d_quantize(const I8ConvQuantArgs<RES> q) {
@@ -217,10 +215,7 @@ __global__ __launch_bounds__(kBlock) void k_i8_conv2d_quantize(const I8ConvQuant
         ar[r] = InitAcc{0.f, 0.f, 0.0, 0u};
 #pragma unroll
         for (int j = 0; j < NTT; ++j) init_take<LQ_INIT_ABSMAX>(y[j][r], ar[r]);      // a masked +0 changes neither maximum
-        i8_merge_dpp<0xb1>(ar[r]);                     // lane ^ 1
-        i8_merge_dpp<0x4e>(ar[r]);                     // lane ^ 2
-        i8_merge_dpp<0x141>(ar[r]);                    // the other quad of the eight
-        i8_merge_dpp<0x140>(ar[r]);                    // the other eight of the sixteen
+        i8_row_absmax(ar[r]);
     }
     if constexpr (BLOCK) {
         __shared__ float sh_f[2][4][kI8TileLines];
@@ -249,7 +244,7 @@ __global__ __launch_bounds__(kBlock) void k_i8_conv2d_quantize(const I8ConvQuant
     for (int r = 0; r < 4; ++r) {
         const int32_t m = mt * kI8TileLines + g4 + r;
         const bool live_m = m < p.M;
-        const float s = live_m ? init_final(q.ip, init_raw<LQ_INIT_ABSMAX>(q.ip, ar[r], p.N), ar[r].bad) : 1.0f;
+        const float s = i8_row_scale(q.ip, ar[r], p.N, live_m);
         const Ctx c = Step::ctx(q.gp, s);
 #pragma unroll
         for (int j = 0; j < NTT; ++j) {

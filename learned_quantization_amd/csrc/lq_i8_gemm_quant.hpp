@@ -37,6 +37,21 @@ __device__ __forceinline__ void i8_merge_dpp(InitAcc& a) {
                                0.0, mx_dpp<CTRL>(a.bad));
 }
 
+// the row-operand epilogue, shared with lq_i8_direct_quant.hpp: a result row lies in the 16 lanes that share (lane >> 4)
+__device__ __forceinline__ float i8_relu(float v) { return v > 0.f ? v : (v != v ? v : 0.f); }
+
+// finishes a row's absmax over its 16 lanes: every lane of the sixteen ends with the row's merged partials
+__device__ __forceinline__ void i8_row_absmax(InitAcc& a) {
+    i8_merge_dpp<0xb1>(a);                             // lane ^ 1
+    i8_merge_dpp<0x4e>(a);                             // lane ^ 2
+    i8_merge_dpp<0x141>(a);                            // the other quad of the eight
+    i8_merge_dpp<0x140>(a);                            // the other eight of the sixteen
+}
+
+// the scale of a row of `count` elements from its merged absmax; a row past M gets 1
+__device__ __forceinline__ float i8_row_scale(const InitParams& ip, const InitAcc& a, int64_t count, bool live_m) {
+    return live_m ? init_final(ip, init_raw<LQ_INIT_ABSMAX>(ip, a, count), a.bad) : 1.0f;
+}
 struct I8GemmQuantAffineParams : I8GemmQuantParams {
     const float* b_offsets;   // [b_nbs][16 NT], the layout of b_scales
 };
@@ -152,7 +167,7 @@ __global__ __launch_bounds__(kBlock) void k_i8_gemm_quantize(const std::conditio
         for (int r = 0; r < 4; ++r) {
             const int32_t m = mt * kI8TileLines + g4 + r;
             float v = p.g.bias ? __fadd_rn(y[j][r], bv) : y[j][r];
-            if (p.act == LQ_ACT_RELU) v = v > 0.f ? v : (v != v ? v : 0.f);
+            if (p.act == LQ_ACT_RELU) v = i8_relu(v);
             y[j][r] = (live_n[j] && m < p.g.M) ? v : 0.f;
         }
     }
@@ -167,11 +182,8 @@ __global__ __launch_bounds__(kBlock) void k_i8_gemm_quantize(const std::conditio
         InitAcc a4{0.f, 0.f, 0.0, 0u};
 #pragma unroll
         for (int j = 0; j < 4; ++j) init_take<LQ_INIT_ABSMAX>(y[j][r], a4);      // a masked +0 changes neither maximum
-        i8_merge_dpp<0xb1>(a4);                        // lane ^ 1
-        i8_merge_dpp<0x4e>(a4);                        // lane ^ 2
-        i8_merge_dpp<0x141>(a4);                       // the other quad of the eight
-        i8_merge_dpp<0x140>(a4);                       // the other eight of the sixteen
-        const float s = live_m ? init_final(p.ip, init_raw<LQ_INIT_ABSMAX>(p.ip, a4, kI8TileK), a4.bad) : 1.0f;
+        i8_row_absmax(a4);
+        const float s = i8_row_scale(p.ip, a4, kI8TileK, live_m);
         const Ctx c = Step::ctx(p.gp, s);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {

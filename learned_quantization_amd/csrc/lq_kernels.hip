@@ -2340,15 +2340,31 @@ static int i8_operand_dims(const char* fn, int64_t L, int64_t K, int64_t block, 
     return LQ_OK;
 }
 
-int lq_i8_operand_bytes(int64_t L, int64_t K, int64_t block, size_t* code_bytes, size_t* scale_bytes) {
-    const char* fn = __func__;
+extern "C++" {      // a template inside the C-linkage block
+// the body of the four *_bytes calls of the int8 path: `dims(d)` is the operand's own *_dims call
+template <class Dims, class F>
+static int i8_bytes(const char* fn, size_t* code_bytes, size_t* scale_bytes, F dims) {
     if (!code_bytes || !scale_bytes) return fail(LQ_EINVAL, "%s: code_bytes or scale_bytes is NULL", fn);
-    I8OperandDims d;
-    int rc = i8_operand_dims(fn, L, K, block, d);
+    Dims d{};
+    int rc = dims(d);
     if (rc) return rc;
     *code_bytes = d.code_bytes;
     *scale_bytes = d.scale_bytes;
     return LQ_OK;
+}
+}  // extern "C++"
+
+int lq_i8_operand_bytes(int64_t L, int64_t K, int64_t block, size_t* code_bytes, size_t* scale_bytes) {
+    const char* fn = __func__;
+    return i8_bytes<I8OperandDims>(fn, code_bytes, scale_bytes, [&](I8OperandDims& d) { return i8_operand_dims(fn, L, K, block, d); });
+}
+
+// the activation quantizer of every int8 operand the device writes from fp32: symmetric codes in [-127, 127], an absmax scale that
+// is at least kOperandMinScale
+static void i8_act_quantizer(GroupParams& g, InitParams& ip) {
+    g.lo = ip.lo = -127.0f;
+    g.hi = ip.hi = 127.0f;
+    ip.min_value = kOperandMinScale;
 }
 
 // a 4-bit operand (lq_i4_operand.hpp): the tiles, scale blocks and refusals of the int8 operand, half the code bytes
@@ -2360,13 +2376,7 @@ static int i4_operand_dims(const char* fn, int64_t L, int64_t K, int64_t block, 
 
 int lq_i4_operand_bytes(int64_t L, int64_t K, int64_t block, size_t* code_bytes, size_t* scale_bytes) {
     const char* fn = __func__;
-    if (!code_bytes || !scale_bytes) return fail(LQ_EINVAL, "%s: code_bytes or scale_bytes is NULL", fn);
-    I8OperandDims d;
-    int rc = i4_operand_dims(fn, L, K, block, d);
-    if (rc) return rc;
-    *code_bytes = d.code_bytes;
-    *scale_bytes = d.scale_bytes;
-    return LQ_OK;
+    return i8_bytes<I8OperandDims>(fn, code_bytes, scale_bytes, [&](I8OperandDims& d) { return i4_operand_dims(fn, L, K, block, d); });
 }
 
 // an operand's offsets (the affine entry points): a buffer in the layout of its scales, on the same grid
@@ -2495,9 +2505,7 @@ int lq_i8_operand_quantize(const float* X, int64_t M, int64_t K, int64_t block, 
     if ((rc = check_operand_buffers(fn, codes, scales, kI8ScaleAlign))) return rc;
     I8QuantParams op{};
     op.g.P = X;
-    op.g.lo = op.ip.lo = -127.0f;
-    op.g.hi = op.ip.hi = 127.0f;
-    op.ip.min_value = kOperandMinScale;
+    i8_act_quantizer(op.g, op.ip);
     op.codes = (uint8_t*)codes;
     op.scales = (float*)scales;
     op.M = (int32_t)M;
@@ -2534,9 +2542,7 @@ int lq_i8_operand_im2col(const float* X, const lq_conv_geom* g, int64_t block, v
     if ((rc = check_operand_buffers(fn, codes, scales, kI8ScaleAlign))) return rc;
     I8Im2colParams op{};
     op.g.P = X;
-    op.g.lo = op.ip.lo = -127.0f;
-    op.g.hi = op.ip.hi = 127.0f;
-    op.ip.min_value = kOperandMinScale;
+    i8_act_quantizer(op.g, op.ip);
     op.codes = (uint8_t*)codes;
     op.scales = (float*)scales;
     fill_im2col_geom(op.geom, g, cd);
@@ -2607,24 +2613,13 @@ static int i8_conv_kernel_dims(const char* fn, int64_t co, int64_t ci, int64_t K
 
 int lq_i8_pixels_bytes(int64_t B, int64_t C, int64_t H, int64_t W, size_t* code_bytes, size_t* scale_bytes) {
     const char* fn = __func__;
-    if (!code_bytes || !scale_bytes) return fail(LQ_EINVAL, "%s: code_bytes or scale_bytes is NULL", fn);
-    I8DirectDims d{};
-    int rc = i8_pixels_dims(fn, B, C, H, W, d);
-    if (rc) return rc;
-    *code_bytes = d.code_bytes;
-    *scale_bytes = d.scale_bytes;
-    return LQ_OK;
+    return i8_bytes<I8DirectDims>(fn, code_bytes, scale_bytes, [&](I8DirectDims& d) { return i8_pixels_dims(fn, B, C, H, W, d); });
 }
 
 int lq_i8_conv_kernel_bytes(int64_t co, int64_t ci, int64_t KH, int64_t KW, size_t* code_bytes, size_t* scale_bytes) {
     const char* fn = __func__;
-    if (!code_bytes || !scale_bytes) return fail(LQ_EINVAL, "%s: code_bytes or scale_bytes is NULL", fn);
-    I8DirectDims d{};
-    int rc = i8_conv_kernel_dims(fn, co, ci, KH, KW, d);
-    if (rc) return rc;
-    *code_bytes = d.code_bytes;
-    *scale_bytes = d.scale_bytes;
-    return LQ_OK;
+    return i8_bytes<I8DirectDims>(fn, code_bytes, scale_bytes,
+                                  [&](I8DirectDims& d) { return i8_conv_kernel_dims(fn, co, ci, KH, KW, d); });
 }
 
 int lq_i8_pixels_quantize(const float* X, const lq_conv_geom* g, void* codes, void* scales, void* stream) {
@@ -2640,9 +2635,7 @@ int lq_i8_pixels_quantize(const float* X, const lq_conv_geom* g, void* codes, vo
     if ((rc = check_operand_buffers(fn, codes, scales, kI8ScaleAlign))) return rc;
     I8PixelsParams op{};
     op.g.P = X;
-    op.g.lo = op.ip.lo = -127.0f;
-    op.g.hi = op.ip.hi = 127.0f;
-    op.ip.min_value = kOperandMinScale;
+    i8_act_quantizer(op.g, op.ip);
     op.codes = (uint8_t*)codes;
     op.scales = (float*)scales;
     op.xs_b = g->xs_b;
@@ -2699,33 +2692,31 @@ int lq_i8_conv_kernel_pack(const float* P, const float* s, int32_t qmin, int32_t
     return check_hip("int8 conv kernel pack");
 }
 
-int lq_i8_conv2d(const void* pix_codes, const void* pix_scales, const void* k_codes, const void* k_scales, const float* bias, float* Y,
-                 int64_t ldy, const lq_conv_geom* g, int64_t co, void* stream) {
-    const char* fn = __func__;
-    ConvDims cd;
+// The direct convolution's rule, one for lq_i8_conv2d and the lq_i8_conv2d_quantize pair, so that the three take the same runs.
+// It stands in two parts, because each entry's own refusals stand between them and the order of refusals is part of the ABI.
+// First the extents: the geometry, and the pixel operand's and the kernel's own limits
+static int i8_conv2d_dims(const char* fn, const lq_conv_geom* g, int64_t co, ConvDims& cd, I8DirectDims& dk) {
     int rc = conv_geom_dims(fn, g, cd);            // the xs_* fields are not read
     if (rc) return rc;
-    I8DirectDims dp{}, dk{};
+    I8DirectDims dp{};
     if ((rc = i8_pixels_dims(fn, g->B, g->C, g->H, g->W, dp))) return rc;
-    if ((rc = i8_conv_kernel_dims(fn, co, g->C, g->KH, g->KW, dk))) return rc;
-    if ((rc = check_operand_buffers(fn, pix_codes, pix_scales, kI8ScaleAlign))) return rc;
-    if ((rc = check_operand_buffers(fn, k_codes, k_scales, kI8ScaleAlign))) return rc;
-    if ((rc = check_gemm_output(fn, bias, Y, ldy, cd.M, co))) return rc;
+    return i8_conv_kernel_dims(fn, co, g->C, g->KH, g->KW, dk);
+}
+
+// Then, once the entry has checked its buffers: the limits of the kernels' 32-bit arithmetic and of M, and all of I8Conv2dParams but
+// bias, Y and ldy.  `grid` is lq_i8_conv2d's; the epilogue kernels cut their own from MT (i8_conv2d_quantize_launch)
+static int i8_conv2d_rule(const char* fn, const void* pix_codes, const void* pix_scales, const void* k_codes, const void* k_scales,
+                          const lq_conv_geom* g, int64_t co, const ConvDims& cd, const I8DirectDims& dk, I8Conv2dParams& p, dim3& grid) {
     // the kernel forms a window's corner, oh * stride_h - pad_top, in 32 bits
     if (g->H + g->pad_top + g->pad_bottom > 2147483647 || g->W + g->pad_left + g->pad_right > 2147483647)
         return fail(LQ_EINVAL, "%s: the padded input (%lld x %lld) does not fit 32 bits", fn, (long long)(g->H + g->pad_top + g->pad_bottom),
                     (long long)(g->W + g->pad_left + g->pad_right));
     const int64_t MT = (cd.M + kI8TileLines - 1) / kI8TileLines;
-    dim3 grid;
-    if ((rc = gemm_grid(fn, (dk.NT + 3) / 4, MT, cd.M, grid))) return rc;
-    I8Conv2dParams p{};
+    if (int rc = gemm_grid(fn, (dk.NT + 3) / 4, MT, cd.M, grid)) return rc;
     p.pix_codes = (const uint8_t*)pix_codes;
     p.pix_scales = (const float*)pix_scales;
     p.k_codes = (const uint8_t*)k_codes;
     p.k_scales = (const float*)k_scales;
-    p.bias = bias;
-    p.Y = Y;
-    p.ldy = ldy;
     p.ohow = make_fastdiv((uint32_t)(cd.OH * cd.OW));      // M <= 65535 * 64 bounds OH * OW and OW
     p.ow = make_fastdiv((uint32_t)cd.OW);
     p.M = (int32_t)cd.M;
@@ -2742,6 +2733,25 @@ int lq_i8_conv2d(const void* pix_codes, const void* pix_scales, const void* k_co
     p.stride_w = g->stride_w;
     p.pad_top = g->pad_top;
     p.pad_left = g->pad_left;
+    return LQ_OK;
+}
+
+int lq_i8_conv2d(const void* pix_codes, const void* pix_scales, const void* k_codes, const void* k_scales, const float* bias, float* Y,
+                 int64_t ldy, const lq_conv_geom* g, int64_t co, void* stream) {
+    const char* fn = __func__;
+    ConvDims cd;
+    I8DirectDims dk{};
+    int rc = i8_conv2d_dims(fn, g, co, cd, dk);
+    if (rc) return rc;
+    if ((rc = check_operand_buffers(fn, pix_codes, pix_scales, kI8ScaleAlign))) return rc;
+    if ((rc = check_operand_buffers(fn, k_codes, k_scales, kI8ScaleAlign))) return rc;
+    if ((rc = check_gemm_output(fn, bias, Y, ldy, cd.M, co))) return rc;
+    I8Conv2dParams p{};
+    dim3 grid;
+    if ((rc = i8_conv2d_rule(fn, pix_codes, pix_scales, k_codes, k_scales, g, co, cd, dk, p, grid))) return rc;
+    p.bias = bias;
+    p.Y = Y;
+    p.ldy = ldy;
     if (dk.step == 64) hipLaunchKernelGGL(k_i8_conv2d<64>, grid, dim3(kBlock), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(k_i8_conv2d<32>, grid, dim3(kBlock), 0, (hipStream_t)stream, p);
     return check_hip("direct int8 convolution");
@@ -2761,11 +2771,9 @@ static int i8_conv2d_quantize_entry(const char* fn, bool residual, const void* p
                                     const float* post_shift, int activation, int affine_first, const void* res_codes,
                                     const void* res_scales, void* out_codes, void* out_scales, void* stream) {
     ConvDims cd;
-    int rc = conv_geom_dims(fn, g, cd);            // the xs_* fields are not read
+    I8DirectDims dk{}, dout{};
+    int rc = i8_conv2d_dims(fn, g, co, cd, dk);
     if (rc) return rc;
-    I8DirectDims dp{}, dk{}, dout{};
-    if ((rc = i8_pixels_dims(fn, g->B, g->C, g->H, g->W, dp))) return rc;
-    if ((rc = i8_conv_kernel_dims(fn, co, g->C, g->KH, g->KW, dk))) return rc;
     if (co > kI8ConvQuantMaxCo)
         return fail(LQ_EINVAL, "%s: co = %lld is above %lld: a pixel's scale needs its whole output row, at most 32 column tiles, in one "
                     "thread block before the first code", fn, (long long)co, (long long)kI8ConvQuantMaxCo);
@@ -2792,40 +2800,12 @@ static int i8_conv2d_quantize_entry(const char* fn, bool residual, const void* p
     if ((rc = check_gemm_bias(fn, bias))) return rc;
     if (post_scale && (!aligned(post_scale, 4) || !aligned(post_shift, 4)))
         return fail(LQ_EALIGN, "%s: post_scale or post_shift is not 4-byte aligned", fn);
-    // the kernel forms a window's corner, oh * stride_h - pad_top, in 32 bits
-    if (g->H + g->pad_top + g->pad_bottom > 2147483647 || g->W + g->pad_left + g->pad_right > 2147483647)
-        return fail(LQ_EINVAL, "%s: the padded input (%lld x %lld) does not fit 32 bits", fn, (long long)(g->H + g->pad_top + g->pad_bottom),
-                    (long long)(g->W + g->pad_left + g->pad_right));
-    const int64_t MT = (cd.M + kI8TileLines - 1) / kI8TileLines;
-    dim3 unused;
-    if ((rc = gemm_grid(fn, 1, MT, cd.M, unused))) return rc;      // lq_i8_conv2d's limit on M, kept: the two calls take the same runs
     I8ConvQuantResParams qr{};
     I8ConvQuantParams& q = qr;          // the launch without a residual passes this part alone
-    I8Conv2dParams& p = q.c;
-    p.pix_codes = (const uint8_t*)pix_codes;
-    p.pix_scales = (const float*)pix_scales;
-    p.k_codes = (const uint8_t*)k_codes;
-    p.k_scales = (const float*)k_scales;
-    p.bias = bias;
-    p.ohow = make_fastdiv((uint32_t)(cd.OH * cd.OW));      // M <= 65535 * 64 bounds OH * OW and OW
-    p.ow = make_fastdiv((uint32_t)cd.OW);
-    p.M = (int32_t)cd.M;
-    p.N = (int32_t)co;
-    p.MT = (int32_t)MT;
-    p.NT = (int32_t)dk.NT;
-    p.CS = (int32_t)dk.CS;
-    p.CP = (int32_t)dk.CP;
-    p.H = (int32_t)g->H;
-    p.W = (int32_t)g->W;
-    p.KH = g->KH;
-    p.KW = g->KW;
-    p.stride_h = g->stride_h;
-    p.stride_w = g->stride_w;
-    p.pad_top = g->pad_top;
-    p.pad_left = g->pad_left;
-    q.gp.lo = q.ip.lo = -127.0f;
-    q.gp.hi = q.ip.hi = 127.0f;
-    q.ip.min_value = kOperandMinScale;
+    dim3 unused;
+    if ((rc = i8_conv2d_rule(fn, pix_codes, pix_scales, k_codes, k_scales, g, co, cd, dk, q.c, unused))) return rc;
+    q.c.bias = bias;
+    i8_act_quantizer(q.gp, q.ip);
     q.post_scale = post_scale;
     q.post_shift = post_shift;
     q.codes = (uint8_t*)out_codes;
@@ -2911,12 +2891,11 @@ int lq_i4_operand_decode_affine(const void* codes, const void* scales, const voi
     return i8_operand_decode(__func__, true, true, codes, scales, offsets, L, K, block, out, stream);
 }
 
-// lq_i8_gemm (b_offsets == NULL, affine false) and lq_i8_gemm_affine: one set of refusals, one period rule, one grid;
-// w4: lq_i8_gemm_w4 and lq_i8_gemm_w4_affine, B a packed 4-bit operand (the same tiles and scales: nothing else differs)
-static int i8_gemm(const char* fn, bool affine, bool w4, const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes,
-                   const void* b_scales, const void* b_offsets, int64_t b_block, const float* bias, float* Y, int64_t ldy, int64_t M,
-                   int64_t N, int64_t K, void* stream) {
-    I8OperandDims da, db;
+// The int8 GEMM's rule, one for lq_i8_gemm and lq_i8_gemm_quantize and their w4 and affine forms (ops.i8_period states the period
+// in Python).  It stands in two parts, because lq_i8_gemm_quantize's own refusals stand between them and the order of refusals is
+// part of the ABI.  First the extents and the period, and what of I8GemmParams follows from them
+static int i8_gemm_rule(const char* fn, int64_t a_block, int64_t b_block, int64_t M, int64_t N, int64_t K, I8GemmParams& p,
+                        I8OperandDims& da, I8OperandDims& db) {
     int rc = i8_operand_dims(fn, M, K, a_block, da);
     if (rc || (rc = i8_operand_dims(fn, N, K, b_block, db))) return rc;
     const int64_t lo = std::min(a_block, b_block), hi = std::max(a_block, b_block);
@@ -2928,18 +2907,6 @@ static int i8_gemm(const char* fn, bool affine, bool w4, const void* a_codes, co
     if (period > 65536)
         return fail(LQ_EINVAL, "%s: a period of %lld k between two scale changes is above 65536: the int32 sum of that many products of "
                     "magnitude up to 2^14 could overflow", fn, (long long)period);
-    if ((rc = check_operand_buffers(fn, a_codes, a_scales, kI8ScaleAlign))) return rc;
-    if ((rc = check_operand_buffers(fn, b_codes, b_scales, kI8ScaleAlign))) return rc;
-    if (affine && (rc = check_operand_offsets(fn, b_offsets))) return rc;
-    if ((rc = check_gemm_output(fn, bias, Y, ldy, M, N))) return rc;
-    I8GemmParams p{};
-    p.a_codes = (const uint8_t*)a_codes;
-    p.a_scales = (const float*)a_scales;
-    p.b_codes = (const uint8_t*)b_codes;
-    p.b_scales = (const float*)b_scales;
-    p.bias = bias;
-    p.Y = Y;
-    p.ldy = ldy;
     p.M = (int32_t)M;
     p.N = (int32_t)N;
     p.MT = (int32_t)da.LT;
@@ -2948,6 +2915,35 @@ static int i8_gemm(const char* fn, bool affine, bool w4, const void* a_codes, co
     p.ps = (int32_t)(F > 0 ? std::min(F / kI8TileK, da.KT) : da.KT);
     p.a_every = a_block > 0 ? (int32_t)(a_block / F) : INT32_MAX;
     p.b_every = b_block > 0 ? (int32_t)(b_block / F) : INT32_MAX;
+    return LQ_OK;
+}
+
+// Then the operands' buffers, B's offsets where the entry is an affine one, and their four pointers
+static int i8_gemm_operands(const char* fn, bool affine, const void* a_codes, const void* a_scales, const void* b_codes,
+                            const void* b_scales, const void* b_offsets, I8GemmParams& p) {
+    int rc = check_operand_buffers(fn, a_codes, a_scales, kI8ScaleAlign);
+    if (rc || (rc = check_operand_buffers(fn, b_codes, b_scales, kI8ScaleAlign))) return rc;
+    if (affine && (rc = check_operand_offsets(fn, b_offsets))) return rc;
+    p.a_codes = (const uint8_t*)a_codes;
+    p.a_scales = (const float*)a_scales;
+    p.b_codes = (const uint8_t*)b_codes;
+    p.b_scales = (const float*)b_scales;
+    return LQ_OK;
+}
+
+// lq_i8_gemm (b_offsets == NULL, affine false) and lq_i8_gemm_affine: one set of refusals, one grid;
+// w4: lq_i8_gemm_w4 and lq_i8_gemm_w4_affine, B a packed 4-bit operand (the same tiles and scales: nothing else differs)
+static int i8_gemm(const char* fn, bool affine, bool w4, const void* a_codes, const void* a_scales, int64_t a_block, const void* b_codes,
+                   const void* b_scales, const void* b_offsets, int64_t b_block, const float* bias, float* Y, int64_t ldy, int64_t M,
+                   int64_t N, int64_t K, void* stream) {
+    I8OperandDims da, db;
+    I8GemmParams p{};
+    int rc = i8_gemm_rule(fn, a_block, b_block, M, N, K, p, da, db);
+    if (rc || (rc = i8_gemm_operands(fn, affine, a_codes, a_scales, b_codes, b_scales, b_offsets, p))) return rc;
+    if ((rc = check_gemm_output(fn, bias, Y, ldy, M, N))) return rc;
+    p.bias = bias;
+    p.Y = Y;
+    p.ldy = ldy;
     dim3 grid;
     if ((rc = gemm_grid(fn, (db.LT + 3) / 4, da.LT, M, grid))) return rc;
     if (affine) {
@@ -2990,45 +2986,20 @@ static int i8_gemm_quantize(const char* fn, bool affine, bool w4, const void* a_
                             int activation, int64_t out_block, void* out_codes, void* out_scales, int64_t M, int64_t N, int64_t K,
                             void* stream) {
     I8OperandDims da, db, dout;
-    int rc = i8_operand_dims(fn, M, K, a_block, da);
-    if (rc || (rc = i8_operand_dims(fn, N, K, b_block, db))) return rc;
-    const int64_t lo = std::min(a_block, b_block), hi = std::max(a_block, b_block);
-    if (lo > 0 && hi % lo != 0)
-        return fail(LQ_EINVAL, "%s: scale blocks %lld and %lld: the larger must be a multiple of the smaller", fn, (long long)a_block,
-                    (long long)b_block);
-    const int64_t F = lo > 0 ? lo : hi;            // the period, as lq_i8_gemm takes it
-    const int64_t period = F > 0 ? std::min(F, K) : K;
-    if (period > 65536)
-        return fail(LQ_EINVAL, "%s: a period of %lld k between two scale changes is above 65536: the int32 sum of that many products of "
-                    "magnitude up to 2^14 could overflow", fn, (long long)period);
+    I8GemmQuantParams p{};
+    int rc = i8_gemm_rule(fn, a_block, b_block, M, N, K, p.g, da, db);
+    if (rc) return rc;
     if (out_block != kI8TileK)
         return fail(LQ_EINVAL, "%s: out_block = %lld: the epilogue writes scale blocks of %d, the columns of one thread block; one "
                     "scale per row (0) or a larger block needs every column tile of the row before the first code", fn,
                     (long long)out_block, kI8TileK);
     if (activation != LQ_ACT_NONE && activation != LQ_ACT_RELU) return fail(LQ_EINVAL, "%s: bad activation %d", fn, activation);
     if ((rc = i8_operand_dims(fn, M, N, out_block, dout))) return rc;      // M * N < 2^31
-    if ((rc = check_operand_buffers(fn, a_codes, a_scales, kI8ScaleAlign))) return rc;
-    if ((rc = check_operand_buffers(fn, b_codes, b_scales, kI8ScaleAlign))) return rc;
-    if (affine && (rc = check_operand_offsets(fn, b_offsets))) return rc;
+    if ((rc = i8_gemm_operands(fn, affine, a_codes, a_scales, b_codes, b_scales, b_offsets, p.g))) return rc;
     if ((rc = check_operand_buffers(fn, out_codes, out_scales, kI8ScaleAlign))) return rc;
     if ((rc = check_gemm_bias(fn, bias))) return rc;
-    I8GemmQuantParams p{};
-    p.g.a_codes = (const uint8_t*)a_codes;
-    p.g.a_scales = (const float*)a_scales;
-    p.g.b_codes = (const uint8_t*)b_codes;
-    p.g.b_scales = (const float*)b_scales;
     p.g.bias = bias;
-    p.g.M = (int32_t)M;
-    p.g.N = (int32_t)N;
-    p.g.MT = (int32_t)da.LT;
-    p.g.NT = (int32_t)db.LT;
-    p.g.KT = (int32_t)da.KT;
-    p.g.ps = (int32_t)(F > 0 ? std::min(F / kI8TileK, da.KT) : da.KT);
-    p.g.a_every = a_block > 0 ? (int32_t)(a_block / F) : INT32_MAX;
-    p.g.b_every = b_block > 0 ? (int32_t)(b_block / F) : INT32_MAX;
-    p.gp.lo = p.ip.lo = -127.0f;
-    p.gp.hi = p.ip.hi = 127.0f;
-    p.ip.min_value = kOperandMinScale;
+    i8_act_quantizer(p.gp, p.ip);
     p.codes = (uint8_t*)out_codes;
     p.scales = (float*)out_scales;
     p.act = activation;

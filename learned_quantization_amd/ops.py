@@ -971,7 +971,8 @@ def i8_operand_decode(operand: I8Operand) -> torch.Tensor:
 
 def i8_period(a_block: int, b_block: int, K: int) -> int:
     """The length of a period of the int8 GEMM -- a maximal run of k on which neither operand's scale changes (the last may be
-    shorter) -- or ValueError: two non-zero blocks of which neither divides the other, or a period above 65536."""
+    shorter) -- or ValueError: two non-zero blocks of which neither divides the other, or a period above 65536.  The C statement
+    of the same rule is i8_gemm_rule (csrc/lq_kernels.hip)."""
     a_block, b_block = check_i8_block(a_block), check_i8_block(b_block)
     lo, hi = min(a_block, b_block), max(a_block, b_block)
     if lo > 0 and hi % lo:
@@ -981,6 +982,21 @@ def i8_period(a_block: int, b_block: int, K: int) -> int:
     if period > I8_MAX_PERIOD:
         raise ValueError(f"a period of {period} k between two scale changes is above {I8_MAX_PERIOD}: its int32 sum could overflow")
     return period
+
+
+def _i8_gemm_entry(stem: str, a: I8Operand, b: I8Operand) -> Tuple[str, tuple]:
+    """The entry point of a product with ``b`` -- ``stem``, ``_w4`` for an I4Operand (its buffers checked), ``_affine`` for a B
+    with offsets (B = q s + b: the offset's row-sum term) -- and the arguments all of them begin with: A, then B, its offsets
+    standing where the affine ABI takes them."""
+    name = stem
+    if isinstance(b, I4Operand):
+        _check_i4_buffers(b)
+        name += "_w4"
+    offsets = _i8_offsets(b)
+    if offsets is not None:
+        name += "_affine"
+    return name, (_hip.ptr(a.codes), _hip.ptr(a.scales), a.block, _hip.ptr(b.codes), _hip.ptr(b.scales),
+                  *(() if offsets is None else (_hip.ptr(offsets),)), b.block)
 
 
 def i8_gemm(a: I8Operand, b: I8Operand, bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -993,21 +1009,10 @@ def i8_gemm(a: I8Operand, b: I8Operand, bias: Optional[torch.Tensor] = None, out
     _check_i8_a_operand(a)
     i8_period(a.block, b.block, a.K)
     lib = _hip.load()
-    name = "lq_i8_gemm"
-    if isinstance(b, I4Operand):
-        _check_i4_buffers(b)
-        name = "lq_i8_gemm_w4"
-    M, N = a.lines, b.lines
-    dev = a.codes.device
+    name, operands = _i8_gemm_entry("lq_i8_gemm", a, b)
     bias, out, ldy = _gemm_output(a, b, bias, out)
-    offsets = _i8_offsets(b)
-    if offsets is not None:      # B = q s + b: the offset's row-sum term (lq_i8_gemm_affine)
-        _hip.check(getattr(lib, name + "_affine")(_hip.ptr(a.codes), _hip.ptr(a.scales), a.block, _hip.ptr(b.codes), _hip.ptr(b.scales),
-                                                  _hip.ptr(offsets), b.block, _hip.ptr(bias), _hip.ptr(out), ldy, M, N, a.K,
-                                                  _hip.stream_ptr(dev)), name + "_affine")
-        return out
-    _hip.check(getattr(lib, name)(_hip.ptr(a.codes), _hip.ptr(a.scales), a.block, _hip.ptr(b.codes), _hip.ptr(b.scales), b.block,
-                                  _hip.ptr(bias), _hip.ptr(out), ldy, M, N, a.K, _hip.stream_ptr(dev)), name)
+    _hip.check(getattr(lib, name)(*operands, _hip.ptr(bias), _hip.ptr(out), ldy, a.lines, b.lines, a.K,
+                                  _hip.stream_ptr(a.codes.device)), name)
     return out
 
 
@@ -1072,23 +1077,12 @@ def i8_gemm_quantize(a: I8Operand, b: I8Operand, bias: Optional[torch.Tensor] = 
     _check_i8_a_operand(a)
     i8_period(a.block, b.block, a.K)
     lib = _hip.load()
-    name = "lq_i8_gemm_quantize"
-    if isinstance(b, I4Operand):
-        _check_i4_buffers(b)
-        name = "lq_i8_gemm_quantize_w4"
+    name, operands = _i8_gemm_entry("lq_i8_gemm_quantize", a, b)
     M, N = a.lines, b.lines
     dev = a.codes.device
     bias = _gemm_output(a, b, bias, fp32_out=False)[0]
     codes, scales = _i8_operand_buffers(M, N, out_block, dev)
-    offsets = _i8_offsets(b)
-    if offsets is not None:
-        _hip.check(getattr(lib, name + "_affine")(_hip.ptr(a.codes), _hip.ptr(a.scales), a.block, _hip.ptr(b.codes),
-                                                  _hip.ptr(b.scales), _hip.ptr(offsets), b.block, _hip.ptr(bias), act, out_block,
-                                                  _hip.ptr(codes), _hip.ptr(scales), M, N, a.K, _hip.stream_ptr(dev)),
-                   name + "_affine")
-        return I8Operand(codes, scales, M, N, out_block)
-    _hip.check(getattr(lib, name)(_hip.ptr(a.codes), _hip.ptr(a.scales), a.block, _hip.ptr(b.codes), _hip.ptr(b.scales), b.block,
-                                  _hip.ptr(bias), act, out_block, _hip.ptr(codes), _hip.ptr(scales), M, N, a.K,
+    _hip.check(getattr(lib, name)(*operands, _hip.ptr(bias), act, out_block, _hip.ptr(codes), _hip.ptr(scales), M, N, a.K,
                                   _hip.stream_ptr(dev)), name)
     return I8Operand(codes, scales, M, N, out_block)
 
@@ -1385,17 +1379,13 @@ def i8_conv2d_quantize(pixels: I8Pixels, kernel: I8ConvKernel, bias: Optional[to
     cb, _ = i8_pixels_bytes(B, co, OH, OW)
     codes = torch.empty((B, OH, OW, cb // (B * OH * OW)), dtype=torch.uint8, device=dev)
     scales = torch.empty((B, OH, OW), dtype=torch.float32, device=dev)
+    name, res = "lq_i8_conv2d_quantize", ()
     if residual is not None:
         _check_i8_residual(residual, (B, co, OH, OW), tuple(codes.shape), dev)
-        _hip.check(lib.lq_i8_conv2d_quantize_residual(
-            _hip.ptr(pixels.codes), _hip.ptr(pixels.scales), _hip.ptr(kernel.codes), _hip.ptr(kernel.scales), _hip.ptr(bias), ctypes.byref(g),
-            co, _hip.ptr(post[0]), _hip.ptr(post[1]), act, int(bool(affine_first)), _hip.ptr(residual.codes), _hip.ptr(residual.scales),
-            _hip.ptr(codes), _hip.ptr(scales), _hip.stream_ptr(dev)), "lq_i8_conv2d_quantize_residual")
-        return I8Pixels(codes, scales, (B, co, OH, OW))
-    _hip.check(lib.lq_i8_conv2d_quantize(_hip.ptr(pixels.codes), _hip.ptr(pixels.scales), _hip.ptr(kernel.codes), _hip.ptr(kernel.scales),
-                                         _hip.ptr(bias), ctypes.byref(g), co, _hip.ptr(post[0]), _hip.ptr(post[1]), act,
-                                         int(bool(affine_first)), _hip.ptr(codes), _hip.ptr(scales), _hip.stream_ptr(dev)),
-               "lq_i8_conv2d_quantize")
+        name, res = name + "_residual", (_hip.ptr(residual.codes), _hip.ptr(residual.scales))
+    _hip.check(getattr(lib, name)(_hip.ptr(pixels.codes), _hip.ptr(pixels.scales), _hip.ptr(kernel.codes), _hip.ptr(kernel.scales),
+                                  _hip.ptr(bias), ctypes.byref(g), co, _hip.ptr(post[0]), _hip.ptr(post[1]), act,
+                                  int(bool(affine_first)), *res, _hip.ptr(codes), _hip.ptr(scales), _hip.stream_ptr(dev)), name)
     return I8Pixels(codes, scales, (B, co, OH, OW))
 
 

@@ -717,9 +717,18 @@ int lq_mx_operand_im2col(const float* X, const lq_conv_geom* g, int format, int 
  *   lq_i8_conv2d_quantize refuses, a NULL res_codes or res_scales (without a residual call lq_i8_conv2d_quantize), an output
  *   buffer that overlaps a residual buffer (a row's scale is written by one lane and its residual read by others: not in place).
  *   LQ_EALIGN: what lq_i8_conv2d_quantize refuses, res_codes or res_scales off the 16-byte grid.
+ * lq_i8_conv2d_quantize_wide: lq_i8_conv2d_quantize_residual's arguments; res_codes and res_scales may be NULL TOGETHER (no
+ * residual).  It accepts 1 <= co <= 2048 (the expanding 1 x 1 convs and projection shortcuts of a bottleneck block).  DEFINITION:
+ *   the definition of lq_i8_conv2d_quantize_residual (with a residual) or lq_i8_conv2d_quantize (without), with 2048 in the place
+ *   of 512; for any co both accept, out_codes and out_scales are byte for byte theirs.  A thread block parks its 16 output rows in
+ *   LDS as fp32 between the product and the codes: 32768 * ceil(CPo / 512) bytes of dynamic LDS (128 KB at co = 2048) beside 768
+ *   static bytes, which is above the 64 KB a kernel gets unasked, so the FIRST call that reaches each of the four kernel forms
+ *   raises that kernel's limit once (hipFuncSetAttribute; not a stream operation, nothing is recorded into a capture).  ONE launch
+ *   (capturable); no workspace, memset or atomics; reads no environment; writes exactly lq_i8_pixels_bytes(B, co, OH, OW).
+ *   LQ_EINVAL / LQ_EALIGN before any launch, in lq_i8_conv2d_quantize_residual's order: everything that refuses but co in 513 ..
+ *   2048; co > 2048; exactly one of res_codes / res_scales NULL.
  * Not built on this path: weight scales that vary along K (a group size below ci * kh * kw stays on the im2col path), offsets
- * (asymmetric layers), MX elements, an epilogue for co > 512 (the bottleneck blocks), an fp32 residual, an fp32 second output,
- * dilation and groups.
+ * (asymmetric layers), MX elements, an epilogue for co > 2048, an fp32 residual, an fp32 second output, dilation and groups.
  *
  * PACKED 4-BIT B OPERAND (W4A8).  An operand of L lines by K whose codes lie in [-8, 7] stores them two to a byte, under the same
  * fp32 scales (and, for an asymmetric parameter, offsets) in exactly the layout above:
@@ -801,6 +810,12 @@ int lq_i8_conv2d_quantize_residual(const void* pix_codes, const void* pix_scales
                                    const float* post_scale /* [co]; both or neither NULL */, const float* post_shift,
                                    int activation /* lq_mx_activation */, int affine_first, const void* res_codes,
                                    const void* res_scales, void* out_codes, void* out_scales, void* stream);
+int lq_i8_conv2d_quantize_wide(const void* pix_codes, const void* pix_scales, const void* k_codes, const void* k_scales,
+                               const float* bias /* may be NULL */, const lq_conv_geom* g, int64_t co,
+                               const float* post_scale /* [co]; both or neither NULL */, const float* post_shift,
+                               int activation /* lq_mx_activation */, int affine_first,
+                               const void* res_codes /* both or neither NULL */, const void* res_scales, void* out_codes,
+                               void* out_scales, void* stream);
 
 /* ---- K4: forward and NQ backward of one tensor in a single pass (benchmark path) ---
  * Same results as lq_fq_forward followed by lq_fq_scale_grad (out, max|q| and the vote count bit for bit; on

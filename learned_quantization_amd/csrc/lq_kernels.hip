@@ -26,6 +26,7 @@
 //   lq_i8_conv.hpp      the int8 operand of the same matrix: absmax scales per (line, scale block), two passes over the gather
 //   lq_i8_direct.hpp    the direct int8 convolution: NHWC pixel operand, per-tap kernel operand, the product that gathers its windows
 //   lq_i8_direct_quant.hpp  the direct int8 convolution with an epilogue that writes the next conv's pixel operand
+//   lq_i8_direct_quant_wide.hpp  that epilogue for rows of up to 2048 filters: the output row parked in LDS
 //   this file           host side: traversal plan, launchers, the extern "C" entry points
 //
 // The path is elementwise + per-group reductions: HBM-bound, no MFMA.  Design rules
@@ -82,6 +83,7 @@
 #include "lq_i8_gemm_quant.hpp"
 #include "lq_i8_direct.hpp"
 #include "lq_i8_direct_quant.hpp"
+#include "lq_i8_direct_quant_wide.hpp"
 
 namespace lq {
 
@@ -2765,16 +2767,34 @@ static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
     return a0 < b0 + nb && b0 < a0 + na;
 }
 
-// the body of lq_i8_conv2d_quantize (residual = false; res_* are not read) and lq_i8_conv2d_quantize_residual
+constexpr int64_t kI8ConvQuantWideMaxCo = kI8WideMaxTiles * kI8TileLines;      // 2048: four chunks of 32 column tiles, parked in 128 KB
+
+// the launch of lq_i8_conv2d_quantize_wide: the kernel form's dynamic-LDS limit (raised by the first call that reaches the form,
+// i8_conv_wide_lds_limit), then the one launch
+static int i8_conv2d_quantize_wide_run(const char* fn, bool residual, int64_t step, const I8ConvQuantResParams& qr, hipStream_t st) {
+    const I8ConvQuantParams& q = qr;
+    const hipError_t e = residual ? (step == 64 ? i8_conv2d_quantize_wide_launch<64, true>(qr, st) : i8_conv2d_quantize_wide_launch<32, true>(qr, st))
+                                  : (step == 64 ? i8_conv2d_quantize_wide_launch<64, false>(q, st) : i8_conv2d_quantize_wide_launch<32, false>(q, st));
+    if (e != hipSuccess)
+        return fail(LQ_EHIP, "%s: raising the kernel's dynamic LDS limit to %zu bytes: %s", fn, i8_conv_wide_lds(kI8WideMaxTiles),
+                    hipGetErrorString(e));
+    return check_hip("direct int8 convolution with wide pixel-operand epilogue");
+}
+
+// the body of lq_i8_conv2d_quantize (residual = false; res_* are not read), lq_i8_conv2d_quantize_residual and (wide: the residual
+// pair may be NULL together, the row is parked in LDS) lq_i8_conv2d_quantize_wide
 static int i8_conv2d_quantize_entry(const char* fn, bool residual, const void* pix_codes, const void* pix_scales, const void* k_codes,
                                     const void* k_scales, const float* bias, const lq_conv_geom* g, int64_t co, const float* post_scale,
                                     const float* post_shift, int activation, int affine_first, const void* res_codes,
-                                    const void* res_scales, void* out_codes, void* out_scales, void* stream) {
+                                    const void* res_scales, void* out_codes, void* out_scales, void* stream, bool wide = false) {
     ConvDims cd;
     I8DirectDims dk{}, dout{};
     int rc = i8_conv2d_dims(fn, g, co, cd, dk);
     if (rc) return rc;
-    if (co > kI8ConvQuantMaxCo)
+    if (wide && co > kI8ConvQuantWideMaxCo)
+        return fail(LQ_EINVAL, "%s: co = %lld is above %lld: a pixel's scale needs its whole output row, at most 128 column tiles parked "
+                    "in LDS, in one thread block before the first code", fn, (long long)co, (long long)kI8ConvQuantWideMaxCo);
+    if (!wide && co > kI8ConvQuantMaxCo)
         return fail(LQ_EINVAL, "%s: co = %lld is above %lld: a pixel's scale needs its whole output row, at most 32 column tiles, in one "
                     "thread block before the first code", fn, (long long)co, (long long)kI8ConvQuantMaxCo);
     if (activation != LQ_ACT_NONE && activation != LQ_ACT_RELU) return fail(LQ_EINVAL, "%s: bad activation %d", fn, activation);
@@ -2787,7 +2807,8 @@ static int i8_conv2d_quantize_entry(const char* fn, bool residual, const void* p
     if ((rc = check_operand_buffers(fn, out_codes, out_scales, kI8ScaleAlign))) return rc;
     if (residual) {
         if (!res_codes || !res_scales)
-            return fail(LQ_EINVAL, "%s: argument '%s' is NULL: the call without a residual is lq_i8_conv2d_quantize", fn,
+            return fail(LQ_EINVAL, wide ? "%s: argument '%s' is NULL: res_codes and res_scales are given together or not at all"
+                                        : "%s: argument '%s' is NULL: the call without a residual is lq_i8_conv2d_quantize", fn,
                         res_codes ? "res_scales" : "res_codes");
         if (!aligned(res_codes, 16) || !aligned(res_scales, kI8ScaleAlign))
             return fail(LQ_EALIGN, "%s: %s is not 16-byte aligned", fn, aligned(res_codes, 16) ? "res_scales" : "res_codes");
@@ -2814,6 +2835,11 @@ static int i8_conv2d_quantize_entry(const char* fn, bool residual, const void* p
     q.affine_first = affine_first;
     q.CPo = (int32_t)dout.CP;
     q.OT = (int32_t)(dout.CP / kI8TileLines);
+    if (wide) {
+        qr.res_codes = (const uint8_t*)res_codes;       // both NULL without a residual
+        qr.res_scales = (const float*)res_scales;
+        return i8_conv2d_quantize_wide_run(fn, residual, dk.step, qr, (hipStream_t)stream);
+    }
     if (residual) {
         qr.res_codes = (const uint8_t*)res_codes;
         qr.res_scales = (const float*)res_scales;
@@ -2839,6 +2865,14 @@ int lq_i8_conv2d_quantize_residual(const void* pix_codes, const void* pix_scales
                                    const void* res_scales, void* out_codes, void* out_scales, void* stream) {
     return i8_conv2d_quantize_entry(__func__, true, pix_codes, pix_scales, k_codes, k_scales, bias, g, co, post_scale, post_shift,
                                     activation, affine_first, res_codes, res_scales, out_codes, out_scales, stream);
+}
+
+int lq_i8_conv2d_quantize_wide(const void* pix_codes, const void* pix_scales, const void* k_codes, const void* k_scales,
+                               const float* bias, const lq_conv_geom* g, int64_t co, const float* post_scale, const float* post_shift,
+                               int activation, int affine_first, const void* res_codes, const void* res_scales, void* out_codes,
+                               void* out_scales, void* stream) {
+    return i8_conv2d_quantize_entry(__func__, res_codes || res_scales, pix_codes, pix_scales, k_codes, k_scales, bias, g, co, post_scale,
+                                    post_shift, activation, affine_first, res_codes, res_scales, out_codes, out_scales, stream, true);
 }
 
 static int i8_operand_decode(const char* fn, bool affine, bool w4, const void* codes, const void* scales, const void* offsets, int64_t L,

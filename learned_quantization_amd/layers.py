@@ -1127,11 +1127,11 @@ class _ConvBase(_HostLayer):
             return y if self.data_format == "NHWC" else y.permute(0, 3, 1, 2)
 
     def _direct_step(self, x, operand, qb, max_lines=None, out_pixels=False, activation=None, affine=None, affine_first=False,
-                     residual=None):
+                     residual=None, wide=False):
         """One layer of a direct-conv chain: ``x`` a tensor in the layer's data format (quantised here, per run) or an ops.I8Pixels;
         the result the fp32 view ``_direct_conv`` returns, or (``out_pixels``) the next conv's ops.I8Pixels from the product's own
         epilogue (ops.i8_conv2d_quantize).  The batch is cut into runs of whole images by lines, as ``_direct_conv`` cuts it; a
-        ``residual`` (an ops.I8Pixels of the result's shape) is cut by the same images."""
+        ``residual`` (an ops.I8Pixels of the result's shape) is cut by the same images.  ``wide``: ops.i8_conv2d_quantize's."""
         def images_of(px):        # a cut: the codes of whole images stay on the 16-byte grid (CP % 32 == 0); the scales may not
             def cut(b0, b1):
                 scales = px.scales[b0:b1]
@@ -1157,8 +1157,8 @@ class _ConvBase(_HostLayer):
                 raise ValueError(f"{self.name}: the residual must be an ops.I8Pixels of the result's shape {(B, self.filters, OH, OW)}, got "
                                  f"{tuple(residual.shape) if isinstance(residual, ops.I8Pixels) else type(residual).__name__}")
             res = images_of(residual) if residual is not None else (lambda b0, b1: None)
-            outs = [ops.i8_conv2d_quantize(run(b0, b1), operand, qb, self.strides, padding, activation, affine, affine_first, res(b0, b1))
-                    for b0, b1 in runs]
+            outs = [ops.i8_conv2d_quantize(run(b0, b1), operand, qb, self.strides, padding, activation, affine, affine_first, res(b0, b1),
+                                           wide) for b0, b1 in runs]
             if len(outs) == 1:
                 return outs[0]
             return ops.I8Pixels(torch.cat([o.codes for o in outs]), torch.cat([o.scales for o in outs]), (B, self.filters, OH, OW))
@@ -1169,7 +1169,7 @@ class _ConvBase(_HostLayer):
         return y if self.data_format == "NHWC" else y.permute(0, 3, 1, 2)
 
     def call_i8_direct(self, inputs, max_lines=None, out_pixels=False, activation=None, affine=None, affine_first=False,
-                       residual=None):
+                       residual=None, wide=False):
         """The layer as a direct int8 convolution, under ``no_grad``: the inputs quantised ONCE per pixel to symmetric 8-bit integers
         (ops.i8_pixels_quantize: an int8 NHWC copy, one scale per pixel), convolved with ``i8_direct_operand()`` on the int8 matrix
         instruction by ops.i8_conv2d -- TensorFlow 'SAME' padding as ``call`` pads, or 'VALID' -- plus the fake-quantised bias where
@@ -1182,7 +1182,9 @@ class _ConvBase(_HostLayer):
         (ops.i8_conv2d_quantize) after ``activation`` (None or "relu") and ``affine = (g, h)`` (``bn_affine``), in the order
         ``affine_first`` says; byte for byte ``ops.i8_pixels_quantize`` of that result.  Without it an epilogue is refused.
         ``residual`` (with ``out_pixels=True``): an ops.I8Pixels of the result's shape, decoded and added directly before the
-        activation by the same epilogue (the basic ResNet block)."""
+        activation by the same epilogue (the basic ResNet block).
+        ``wide=True`` (with ``out_pixels=True``): a layer of more than 512 filters, up to 2048, goes through the epilogue that parks
+        its output row in LDS (ops.i8_conv2d_quantize, ``wide``); a layer of at most 512 goes where it goes without it."""
         _check_max_lines(max_lines)
         if not out_pixels and (activation is not None or affine is not None or affine_first or residual is not None):
             raise ValueError(f"{self.name}: the fp32 result takes no epilogue (activation={activation!r}, affine, affine_first, "
@@ -1197,7 +1199,7 @@ class _ConvBase(_HostLayer):
             qb = self.nested_q_b_layer(self.b) if self._has_bias else None
             if not direct:
                 return self._direct_conv(inputs, operand, qb, max_lines)
-            return self._direct_step(inputs, operand, qb, max_lines, out_pixels, activation, affine, affine_first, residual)
+            return self._direct_step(inputs, operand, qb, max_lines, out_pixels, activation, affine, affine_first, residual, wide)
 
 
 class CustomConv2DLayer(_ConvBase):
@@ -1414,14 +1416,25 @@ class i8_hardware(_matrix_hardware):
     but writes fp32 for the mean).  A model that states no chains, or reaches more than 512 filters (models.ResNet50Like), keeps
     running unfused.  The outputs differ from ``fused_convs=False`` by
     roundings: ``aff`` is not torch's BatchNorm kernel bit for bit, and an ulp can move a code.  Refused without ``direct`` or with
-    ``emulate``.  Without it (the default) nothing changes."""
+    ``emulate``.  Without it (the default) nothing changes.
+    ``wide_convs=True`` (with ``fused_convs=True``): a module that states ``i8_wide_chains()`` (models._BottleneckBlock: conv1 ->
+    conv2 -> conv3 with the shortcut as conv3's residual, and the one-conv chain of a projection shortcut) gets them parked as
+    above, all or none, with up to 2048 filters on a conv: its chains run through ``i8_conv_chain(..., out_pixels=True,
+    wide=True)``, where a conv of more than 512 filters goes through the epilogue that parks its row in LDS
+    (ops.i8_conv2d_quantize, ``wide``).  models.ResNet50Like then runs its 16 bottleneck blocks from pixel operand to pixel
+    operand (52 convs listed; the last block's conv3 writes fp32 for the mean).  Without it (the default) ``i8_wide_chains`` is not
+    read and nothing changes."""
 
     _family, _dense_eligible = _I8, staticmethod(i8_hardware_eligible)
 
     def __init__(self, model: nn.Module, act_block=0, emulate=False, convs=False, fused=False, offsets=False, direct=False,
-                 int4=False, fused_convs=False):
+                 int4=False, fused_convs=False, wide_convs=False):
         self.direct, self.direct_layers = bool(direct), []
         self.fused_convs, self.fused_conv_layers, self._fused_conv_modules = bool(fused_convs), [], []
+        self.wide_convs = bool(wide_convs)
+        if self.wide_convs and not self.fused_convs:
+            raise ValueError("i8_hardware: wide_convs=True needs fused_convs=True: it widens the pixel-operand epilogue of the fused "
+                             "conv chains to 2048 filters")
         if self.fused_convs and not (convs and direct):
             raise ValueError("i8_hardware: fused_convs=True needs convs=True and direct=True: the epilogue writes the pixel operand of "
                              "the direct int8 convolution")
@@ -1468,6 +1481,16 @@ class i8_hardware(_matrix_hardware):
             self._enter_fused_convs()
         return self
 
+    def _stated_chains(self, mod):
+        """(chains, every, most) of a module: what it states as ``i8_conv_chains()``, whether it runs them with ``out_pixels=True``
+        (``i8_chains_out_pixels``), and the filters an epilogue of them takes.  Under ``wide_convs`` a module may state
+        ``i8_wide_chains()`` instead (models._BottleneckBlock): run with ``out_pixels=True, wide=True``, up to 2048 filters."""
+        if callable(getattr(mod, "i8_conv_chains", None)):
+            return mod.i8_conv_chains(), bool(getattr(mod, "i8_chains_out_pixels", False)), ops.I8_CONV_QUANT_MAX_FILTERS
+        if self.wide_convs and callable(getattr(mod, "i8_wide_chains", None)):
+            return mod.i8_wide_chains(), True, ops.I8_CONV_QUANT_WIDE_MAX_FILTERS
+        return [], False, 0
+
     def _enter_fused_convs(self):
         """A module that states conv chains (``i8_conv_chains()``: lists of (conv, activation, BatchNorm2d or (g, h) or None,
         affine_first)) gets, per chain whose layers all pass ``i8_direct_eligible``, the chain with its affines as ``(g, h)`` --
@@ -1475,12 +1498,11 @@ class i8_hardware(_matrix_hardware):
         self.fused_conv_layers, self._fused_conv_modules = [], []
         with torch.no_grad():
             for mod in self.model.modules():
-                stated = mod.i8_conv_chains() if callable(getattr(mod, "i8_conv_chains", None)) else []
-                every = bool(getattr(mod, "i8_chains_out_pixels", False))      # the module runs its chains with out_pixels=True
+                stated, every, most = self._stated_chains(mod)
                 parked = []
                 for chain in stated:
                     ok = (len(chain) > 1 or every) and all(i8_direct_eligible(c) and act in ops.MX_ACTIVATIONS for c, act, _, _ in chain) \
-                        and all(c.filters <= ops.I8_CONV_QUANT_MAX_FILTERS for c, _, _, _ in (chain if every else chain[:-1]))
+                        and all(c.filters <= most for c, _, _, _ in (chain if every else chain[:-1]))
                     parked.append([(c, act, bn_affine(aff) if isinstance(aff, nn.BatchNorm2d) else aff, first)
                                    for c, act, aff, first in chain] if ok else None)
                 if every and any(chain is None for chain in parked):          # such a module's chains feed each other: all or none
@@ -1496,7 +1518,7 @@ class i8_hardware(_matrix_hardware):
     def __exit__(self, *exc):
         for mod in self._fused_conv_modules:
             mod._i8_fused_convs = None
-            for chain in filter(None, mod.i8_conv_chains()):
+            for chain in filter(None, self._stated_chains(mod)[0]):
                 for c, _, _, _ in chain:
                     c._i8_chain_hw = None
         self._fused_conv_modules = []
@@ -1590,7 +1612,7 @@ def bn_affine(bn: nn.BatchNorm2d):
         return g.float(), (beta - bn.running_mean.double() * g).float()
 
 
-def i8_conv_chain(x, chain, max_lines=None, out_pixels=False):
+def i8_conv_chain(x, chain, max_lines=None, out_pixels=False, wide=False):
     """``chain`` = [(conv, activation, affine, affine_first), ...]: conv layers applied one after the other as direct int8
     convolutions, under ``no_grad``.  ``x`` is quantised once per pixel; every layer but the last goes through
     ops.i8_conv2d_quantize, whose epilogue applies ``activation`` (None or "relu") and ``affine`` (None or ``(g, h)``, ``bn_affine``)
@@ -1604,7 +1626,10 @@ def i8_conv_chain(x, chain, max_lines=None, out_pixels=False):
     added directly before the activation (ops.i8_conv2d_quantize, ``residual``).  ``out_pixels=True``: the LAST layer goes through
     the epilogue too, with its activation, affine and residual, and the chain returns an ops.I8Pixels; ``x`` may itself be one.
     So a basic ResNet block is ``[(conv1, "relu", bn1, True), (conv2, "relu", bn2, True, shortcut)]`` with ``out_pixels=True``.
-    A residual on a last layer that writes fp32 is refused: the fp32 result has no epilogue to add it in."""
+    A residual on a last layer that writes fp32 is refused: the fp32 result has no epilogue to add it in.
+    ``wide=True``: a layer with an epilogue may have up to 2048 filters (ops.I8_CONV_QUANT_WIDE_MAX_FILTERS); one of more than 512
+    goes through ops.i8_conv2d_quantize(..., wide=True), every other where it goes without the flag, so a chain can mix widths.
+    So a bottleneck block is ``[(conv1, "relu", bn1, True), (conv2, "relu", bn2, True), (conv3, "relu", bn3, True, shortcut)]``."""
     fn = "i8_conv_chain"
     chain = [tuple(step) for step in chain]
     _check_max_lines(max_lines)
@@ -1632,7 +1657,10 @@ def i8_conv_chain(x, chain, max_lines=None, out_pixels=False):
             if residual is not None:
                 raise ValueError(f"{fn}: {layer.name}: the last layer writes fp32 and has no epilogue to add a residual in: add it to "
                                  "the result, or ask for out_pixels=True")
-        elif layer.filters > ops.I8_CONV_QUANT_MAX_FILTERS:
+        elif wide and layer.filters > ops.I8_CONV_QUANT_WIDE_MAX_FILTERS:
+            raise ValueError(f"{fn}: {layer.name}: {layer.filters} filters: the wide epilogue parks a whole output row in LDS, at most "
+                             f"{ops.I8_CONV_QUANT_WIDE_MAX_FILTERS}")
+        elif not wide and layer.filters > ops.I8_CONV_QUANT_MAX_FILTERS:
             raise ValueError(f"{fn}: {layer.name}: {layer.filters} filters: the epilogue holds a whole output row in one thread block, "
                              f"at most {ops.I8_CONV_QUANT_MAX_FILTERS}")
     with torch.no_grad():
@@ -1642,7 +1670,7 @@ def i8_conv_chain(x, chain, max_lines=None, out_pixels=False):
             hw = layer._i8_chain_hw
             operand, qb = hw if hw is not None else (layer.i8_direct_operand(), layer.nested_q_b_layer(layer.b) if layer._has_bias else None)
             a = layer._direct_step(a, operand, qb, max_lines, out_pixels or k < len(chain) - 1, activation, affine, affine_first,
-                                   step[4] if len(step) == 5 else None)
+                                   step[4] if len(step) == 5 else None, wide)
         return a
 
 

@@ -273,6 +273,30 @@ class _BottleneckBlock(nn.Module):
             self.shortcut = mk(ci, co, (1, 1), stride, "custom_conv2d_layer_shortcut", values[3])
             self.bn_s = _bn(co)
 
+    def i8_wide_chains(self):
+        """The block as layers.i8_conv_chain takes it with ``out_pixels=True, wide=True`` (the BatchNorms stand for their affines):
+        conv1 -> BN -> relu -> conv2 -> BN -> relu -> conv3 -> BN, whose last step gets the shortcut as its residual when the block
+        runs, and for a projecting block the one-step chain of the shortcut.  Read by layers.i8_hardware under ``wide_convs=True``
+        only: conv3 and the shortcut have up to 2048 filters."""
+        chains = [[(self.conv1, "relu", self.bn1, True), (self.conv2, "relu", self.bn2, True), (self.conv3, "relu", self.bn3, True)]]
+        if self.shortcut is not None:
+            chains.append([(self.shortcut, None, self.bn_s, True)])
+        return chains
+
+    i8_fused = _ResidualBlock.i8_fused
+
+    def forward_pixels(self, x, fused, fp32_out=False):
+        """The block from the pixel operand ``x`` (ops.I8Pixels) to the next block's: the shortcut is ``x`` itself or the shortcut
+        conv's epilogue, and conv3's epilogue adds it before the relu.  ``fp32_out`` (the model's last block): conv3 writes fp32
+        (ops.i8_conv2d) and its affine, the decoded shortcut, the add and the relu are torch's."""
+        sc = x if self.shortcut is None else i8_conv_chain(x, fused[1], out_pixels=True, wide=True)
+        head, (conv3, act, aff, aff_first) = fused[0][:-1], fused[0][-1]
+        if not fp32_out:
+            return i8_conv_chain(x, [*head, (conv3, act, aff, aff_first, sc)], out_pixels=True, wide=True)
+        y = i8_conv_chain(x, [*head, (conv3, None, None, False)], wide=True)
+        r = sc.codes[..., :conv3.filters].view(torch.int8).float() * sc.scales.unsqueeze(-1)       # one rounding: the epilogue's r
+        return F.relu(y * aff[0].view(1, -1, 1, 1) + aff[1].view(1, -1, 1, 1) + r.permute(0, 3, 1, 2))
+
     def forward(self, x):
         sc = x
         y = F.relu(self.bn1(self.conv1(x)))
@@ -324,8 +348,15 @@ class ResNet50Like(nn.Module):
         pw = max((-(-w // 2) - 1) * 2 + 3 - w, 0)
         x = F.pad(x, (pw // 2, pw - pw // 2, ph // 2, ph - ph // 2), value=float("-inf"))
         x = F.max_pool2d(x, 3, 2)
-        for b in self.blocks:
-            x = b(x)
+        fused = [b.i8_fused() for b in self.blocks]       # inside layers.i8_hardware(..., fused_convs=True, wide_convs=True), eval mode
+        if not self.training and all(f is not None for f in fused):
+            a = i8_pixels_quantize(x)                     # the one quantisation: int8 pixel operands from here to the last conv
+            for b, f in zip(self.blocks[:-1], fused):
+                a = b.forward_pixels(a, f)
+            x = self.blocks[-1].forward_pixels(a, fused[-1], fp32_out=True)
+        else:
+            for b in self.blocks:
+                x = b(x)
         return softmax(self.out(torch.mean(x, dim=(2, 3))), dim=1)
 
 

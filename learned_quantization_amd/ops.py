@@ -1198,6 +1198,7 @@ def i8_operand_im2col(x: torch.Tensor, kernel_size, strides=(1, 1), padding=(0, 
 # --------------------------------------------------------------------------- the direct int8 convolution (no im2col matrix)
 I8_DIRECT_MAX_CHANNELS = 65536       # a tap's int32 sum over the channels stays exact (include/lq_hip.h)
 I8_CONV_QUANT_MAX_FILTERS = 512      # lq_i8_conv2d_quantize: a whole output row in one thread block (include/lq_hip.h)
+I8_CONV_QUANT_WIDE_MAX_FILTERS = 2048      # lq_i8_conv2d_quantize_wide (``wide=True``): the row parked in LDS
 
 
 class I8Pixels(NamedTuple):
@@ -1349,7 +1350,8 @@ def i8_conv2d(pixels: I8Pixels, kernel: I8ConvKernel, bias: Optional[torch.Tenso
 
 
 def i8_conv2d_quantize(pixels: I8Pixels, kernel: I8ConvKernel, bias: Optional[torch.Tensor] = None, strides=(1, 1), padding=(0, 0, 0, 0),
-                       activation=None, affine=None, affine_first: bool = False, residual: Optional[I8Pixels] = None) -> I8Pixels:
+                       activation=None, affine=None, affine_first: bool = False, residual: Optional[I8Pixels] = None,
+                       wide: bool = False) -> I8Pixels:
     """The pixel operand of the NEXT conv, written by the convolution's own epilogue (include/lq_hip.h, lq_i8_conv2d_quantize): byte
     for byte ``i8_pixels_quantize`` of ``v`` seen as ``(B, co, OH, OW)``, where ``v = aff(act(Y))`` (``affine_first=False``: conv,
     relu, BatchNorm) or ``v = act(aff(Y))`` (``affine_first=True``), ``Y`` is ``i8_conv2d``'s result bit for bit and ``aff(v) = v *
@@ -1358,7 +1360,11 @@ def i8_conv2d_quantize(pixels: I8Pixels, kernel: I8ConvKernel, bias: Optional[to
     ``residual``: an ``I8Pixels`` of the OUTPUT's shape ``(B, co, OH, OW)`` (lq_i8_conv2d_quantize_residual), decoded as ``r = codes *
     scale`` (one rounding) and added directly before the activation: ``v = aff(act(Y + r))``, or ``v = act(aff(Y) + r)`` with
     ``affine_first`` -- the basic ResNet block's ``relu(bn2(conv2(y)) + shortcut)``.  Still one launch.  ValueError when its shape
-    is not the output's."""
+    is not the output's.
+    ``wide=True``: ``co`` above 512, up to ``I8_CONV_QUANT_WIDE_MAX_FILTERS`` (2048: a bottleneck block's expanding conv and
+    projection shortcut), goes to lq_i8_conv2d_quantize_wide, which parks the output row in LDS -- the same definition, with or
+    without ``residual``, one launch.  A ``co`` of at most 512 goes where it goes without the flag, so the bytes there do not
+    depend on it.  Without it (the default) nothing changes."""
     import ctypes
     act = check_mx_activation(activation)
     dev = _check_i8_conv_operands(pixels, kernel)
@@ -1383,6 +1389,8 @@ def i8_conv2d_quantize(pixels: I8Pixels, kernel: I8ConvKernel, bias: Optional[to
     if residual is not None:
         _check_i8_residual(residual, (B, co, OH, OW), tuple(codes.shape), dev)
         name, res = name + "_residual", (_hip.ptr(residual.codes), _hip.ptr(residual.scales))
+    if wide and co > I8_CONV_QUANT_MAX_FILTERS:       # its residual pair may be NULL together
+        name, res = "lq_i8_conv2d_quantize_wide", res or (None, None)
     _hip.check(getattr(lib, name)(_hip.ptr(pixels.codes), _hip.ptr(pixels.scales), _hip.ptr(kernel.codes), _hip.ptr(kernel.scales),
                                   _hip.ptr(bias), ctypes.byref(g), co, _hip.ptr(post[0]), _hip.ptr(post[1]), act,
                                   int(bool(affine_first)), *res, _hip.ptr(codes), _hip.ptr(scales), _hip.stream_ptr(dev)), name)

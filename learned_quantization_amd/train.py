@@ -646,6 +646,10 @@ def build_parser():
                          "first conv's epilogue writes the second's pixel operand) and add i8_eval_fused_conv_layers, "
                          "i8_eval_fused_conv_accuracy and i8_eval_fused_conv_max_logit_diff (the model's outputs against the unfused "
                          "direct path; not expected to be 0.0: the folded BatchNorm rounds differently from torch's) to the result line")
+    ap.add_argument("--i8-eval-wide-convs", action="store_true",
+                    help="with --i8-eval-fused-convs: that evaluation runs under layers.i8_hardware(..., fused_convs=True, "
+                         "wide_convs=True): conv chains with up to 2048 filters (the bottleneck blocks of the ResNet-50 model) fuse "
+                         "too, through the epilogue that parks its output row in LDS")
     ap.add_argument("--i8-eval-fused", action="store_true",
                     help="with --i8-eval --i8-eval-act-block 64: evaluate once more under layers.i8_hardware(fused=True) (the Dense "
                          "tail through layers.i8_dense_chain: relu and the next operand's quantisation, per row and block of 64, in "
@@ -664,7 +668,8 @@ def build_parser():
 
 
 @torch.no_grad()
-def i8_eval(model, x, y, act_block=0, convs=False, fused=False, offsets=False, direct=False, int4=False, fused_convs=False):
+def i8_eval(model, x, y, act_block=0, convs=False, fused=False, offsets=False, direct=False, int4=False, fused_convs=False,
+            wide_convs=False):
     """One evaluation of ``model`` on (x, y) under layers.i8_hardware, one under its ``emulate=True`` yardstick and one of the
     fake-quantised model as it stands: a dict of the three accuracies and the largest |difference| of the outputs of the last Dense
     layer that took the path (the logits of the MNIST model) between the hardware path and each of the other two.  ValueError for
@@ -680,7 +685,9 @@ def i8_eval(model, x, y, act_block=0, convs=False, fused=False, offsets=False, d
     operand, the accuracy, and the largest |difference| of the model's outputs from the byte operands' (the same bits: 0.0).
     ``fused_convs=True`` (with ``convs`` and ``direct``) adds an evaluation under ``i8_hardware(convs=True, direct=True,
     fused_convs=True)``: the convs whose epilogue writes the next conv's pixel operand, the accuracy, and the largest |difference|
-    of the model's outputs from the unfused direct path's (reported, not expected to be 0.0)."""
+    of the model's outputs from the unfused direct path's (reported, not expected to be 0.0).  ``wide_convs=True`` (with
+    ``fused_convs``) makes that evaluation ``i8_hardware(..., fused_convs=True, wide_convs=True)``: chains with up to 2048 filters
+    (the bottleneck blocks of models.ResNet50Like) fuse too."""
     was_training = model.training
     model.eval()
     acc, logits = [], []
@@ -741,7 +748,8 @@ def i8_eval(model, x, y, act_block=0, convs=False, fused=False, offsets=False, d
         if convs and direct and fused_convs:
             outs = []
             for fc in (True, False):
-                with L.i8_hardware(model, probe.act_block, convs=True, offsets=offsets, direct=True, fused_convs=fc) as hwf:
+                with L.i8_hardware(model, probe.act_block, convs=True, offsets=offsets, direct=True, fused_convs=fc,
+                                   wide_convs=fc and wide_convs) as hwf:
                     if fc and not hwf.fused_conv_layers:
                         raise ValueError("i8_eval: fused_convs=True needs a model that states conv chains (i8_conv_chains(), as "
                                          "models.CIFARCNN and the basic blocks of models.ResNet18Like do) of convs that can run as direct int8 convolutions")
@@ -856,6 +864,8 @@ def main(argv=None):
                  "int8 convolution")
     if args.i8_eval_fused_convs and not args.i8_eval_direct:
         ap.error("--i8-eval-fused-convs needs --i8-eval --i8-eval-convs --i8-eval-direct: it fuses pairs of direct int8 convolutions")
+    if args.i8_eval_wide_convs and not args.i8_eval_fused_convs:
+        ap.error("--i8-eval-wide-convs needs --i8-eval-fused-convs: it widens the epilogue of the fused conv chains")
     if args.i8_eval_fused and not args.i8_eval:
         ap.error("--i8-eval-fused needs --i8-eval: it compares the fused Dense tail with the unfused hardware path")
     if args.i8_eval_fused and args.i8_eval_act_block != 64:
@@ -929,7 +939,7 @@ def main(argv=None):
     quant_stats = L.quant_stats(tr.model) if args.quant_stats and rank == 0 else None      # after the clock has stopped
     mx_stats = L.mx_quant_stats(tr.model) if args.mx_stats and rank == 0 else None
     mx_eval_fields = mx_eval(tr.model, *batches[0], act_format=args.mx_eval, fused=args.mx_eval_fused, convs=args.mx_eval_convs, fp6=args.mx_eval_fp6) if args.mx_eval is not None and rank == 0 else None
-    i8_eval_fields = i8_eval(tr.model, *batches[0], act_block=args.i8_eval_act_block, convs=args.i8_eval_convs, fused=args.i8_eval_fused, offsets=args.i8_eval_offsets, direct=args.i8_eval_direct, int4=args.i8_eval_int4, fused_convs=args.i8_eval_fused_convs) if args.i8_eval and rank == 0 else None
+    i8_eval_fields = i8_eval(tr.model, *batches[0], act_block=args.i8_eval_act_block, convs=args.i8_eval_convs, fused=args.i8_eval_fused, offsets=args.i8_eval_offsets, direct=args.i8_eval_direct, int4=args.i8_eval_int4, fused_convs=args.i8_eval_fused_convs, wide_convs=args.i8_eval_wide_convs) if args.i8_eval and rank == 0 else None
     if rank == 0:
         n_q = sum(p.numel() for l in tr.custom_layers for p in l._regularized())
         print(json.dumps({

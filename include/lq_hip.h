@@ -727,8 +727,22 @@ int lq_mx_operand_im2col(const float* X, const lq_conv_geom* g, int format, int 
  *   (capturable); no workspace, memset or atomics; reads no environment; writes exactly lq_i8_pixels_bytes(B, co, OH, OW).
  *   LQ_EINVAL / LQ_EALIGN before any launch, in lq_i8_conv2d_quantize_residual's order: everything that refuses but co in 513 ..
  *   2048; co > 2048; exactly one of res_codes / res_scales NULL.
+ * lq_i8_conv2d_quantize_pool: lq_i8_conv2d_quantize's arguments and, before out_codes, `pool`: the epilogue takes a
+ * non-overlapping pool x pool maximum (conv, relu, BatchNorm, MaxPool(2)) and writes the pixel operand of the POOLED image.
+ * DEFINITION (bit exact, independent of any tiling; tests/_i8_conv_pool_reference.py states it in NumPy).  Let v[b][oh][ow][n] be
+ * lq_i8_conv2d_quantize's v, bit for bit, POH = floor(OH / 2), POW = floor(OW / 2) (as torch's max_pool2d(x, 2) floors: a last odd
+ * row or column of the conv output belongs to no window), and with v_ij = v[b][2 ph + i][2 pw + j][n]
+ *       m = v_00; for u in (v_01, v_10, v_11): if (u > m || u != u) m = u;      p[b][n][ph][pw] = m
+ *   -- a NaN is sticky, and of equal members (+0 and -0 among them) the first stays, as in torch.  out_codes [PM][CPo], PM = B *
+ *   POH * POW, line pm = (b * POH + ph) * POW + pw, and out_scales [PM] are, byte for byte, what lq_i8_pixels_quantize writes for p
+ *   seen as [B][co][POH][POW], padding included.  ONE launch (capturable); no workspace, memset or atomics; reads no environment;
+ *   writes exactly lq_i8_pixels_bytes(B, co, POH, POW).  The maximum is taken over a lane's own four accumulator registers (the
+ *   four members of a window are four consecutive lines of a tile), so a quarter of lq_i8_conv2d_quantize's rows are quantised
+ *   and stored.  LQ_EINVAL before any launch: everything lq_i8_conv2d_quantize refuses (co > 512 among it), pool != 2, OH < 2 or
+ *   OW < 2.  LQ_EALIGN: what lq_i8_conv2d_quantize refuses.  A residual and the wide row are not part of this entry point.
  * Not built on this path: weight scales that vary along K (a group size below ci * kh * kw stays on the im2col path), offsets
- * (asymmetric layers), MX elements, an epilogue for co > 2048, an fp32 residual, an fp32 second output, dilation and groups.
+ * (asymmetric layers), MX elements, an epilogue for co > 2048, an fp32 residual, an fp32 second output, dilation and groups,
+ * overlapping or average pools, a pool with a residual or in the wide form, a pooled fp32 output.
  *
  * PACKED 4-BIT B OPERAND (W4A8).  An operand of L lines by K whose codes lie in [-8, 7] stores them two to a byte, under the same
  * fp32 scales (and, for an asymmetric parameter, offsets) in exactly the layout above:
@@ -815,6 +829,11 @@ int lq_i8_conv2d_quantize_wide(const void* pix_codes, const void* pix_scales, co
                                const float* post_scale /* [co]; both or neither NULL */, const float* post_shift,
                                int activation /* lq_mx_activation */, int affine_first,
                                const void* res_codes /* both or neither NULL */, const void* res_scales, void* out_codes,
+                               void* out_scales, void* stream);
+int lq_i8_conv2d_quantize_pool(const void* pix_codes, const void* pix_scales, const void* k_codes, const void* k_scales,
+                               const float* bias /* may be NULL */, const lq_conv_geom* g, int64_t co,
+                               const float* post_scale /* [co]; both or neither NULL */, const float* post_shift,
+                               int activation /* lq_mx_activation */, int affine_first, int32_t pool /* 2 */, void* out_codes,
                                void* out_scales, void* stream);
 
 /* ---- K4: forward and NQ backward of one tensor in a single pass (benchmark path) ---

@@ -192,6 +192,8 @@ SIGNATURES.update({
                                                 _c_p, _c_p, _c_p, _c_p, _c_p]),
     "lq_i8_conv2d_quantize_wide": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, ctypes.POINTER(ConvGeom), _c_i64, _c_p, _c_p, _c_int, _c_int,
                                             _c_p, _c_p, _c_p, _c_p, _c_p]),
+    "lq_i8_conv2d_quantize_pool": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, ctypes.POINTER(ConvGeom), _c_i64, _c_p, _c_p, _c_int, _c_int,
+                                            _c_i32, _c_p, _c_p, _c_p]),
 })
 
 

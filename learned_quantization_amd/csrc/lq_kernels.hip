@@ -27,6 +27,7 @@
 //   lq_i8_direct.hpp    the direct int8 convolution: NHWC pixel operand, per-tap kernel operand, the product that gathers its windows
 //   lq_i8_direct_quant.hpp  the direct int8 convolution with an epilogue that writes the next conv's pixel operand
 //   lq_i8_direct_quant_wide.hpp  that epilogue for rows of up to 2048 filters: the output row parked in LDS
+//   lq_i8_direct_quant_pool.hpp  that epilogue behind a 2 x 2 max-pool taken in the accumulator registers
 //   this file           host side: traversal plan, launchers, the extern "C" entry points
 //
 // The path is elementwise + per-group reductions: HBM-bound, no MFMA.  Design rules
@@ -84,6 +85,7 @@
 #include "lq_i8_direct.hpp"
 #include "lq_i8_direct_quant.hpp"
 #include "lq_i8_direct_quant_wide.hpp"
+#include "lq_i8_direct_quant_pool.hpp"
 
 namespace lq {
 
@@ -2781,12 +2783,14 @@ static int i8_conv2d_quantize_wide_run(const char* fn, bool residual, int64_t st
     return check_hip("direct int8 convolution with wide pixel-operand epilogue");
 }
 
-// the body of lq_i8_conv2d_quantize (residual = false; res_* are not read), lq_i8_conv2d_quantize_residual and (wide: the residual
-// pair may be NULL together, the row is parked in LDS) lq_i8_conv2d_quantize_wide
+// the body of lq_i8_conv2d_quantize (residual = false; res_* are not read), lq_i8_conv2d_quantize_residual, (wide: the residual
+// pair may be NULL together, the row is parked in LDS) lq_i8_conv2d_quantize_wide and (pooled: `pool` is the window, the lines
+// written are the pooled ones) lq_i8_conv2d_quantize_pool
 static int i8_conv2d_quantize_entry(const char* fn, bool residual, const void* pix_codes, const void* pix_scales, const void* k_codes,
                                     const void* k_scales, const float* bias, const lq_conv_geom* g, int64_t co, const float* post_scale,
                                     const float* post_shift, int activation, int affine_first, const void* res_codes,
-                                    const void* res_scales, void* out_codes, void* out_scales, void* stream, bool wide = false) {
+                                    const void* res_scales, void* out_codes, void* out_scales, void* stream, bool wide = false,
+                                    bool pooled = false, int32_t pool = 0) {
     ConvDims cd;
     I8DirectDims dk{}, dout{};
     int rc = i8_conv2d_dims(fn, g, co, cd, dk);
@@ -2802,6 +2806,13 @@ static int i8_conv2d_quantize_entry(const char* fn, bool residual, const void* p
     if ((post_scale == nullptr) != (post_shift == nullptr))
         return fail(LQ_EINVAL, "%s: post_scale and post_shift must both be given or both be NULL", fn);
     if ((rc = i8_pixels_dims(fn, g->B, co, cd.OH, cd.OW, dout))) return rc;      // what is written: M * CPo < 2^31
+    const int64_t POH = cd.OH / 2, POW = cd.OW / 2;       // pooled: floored, as F.max_pool2d(x, 2) floors
+    if (pooled) {
+        if (pool != 2) return fail(LQ_EINVAL, "%s: pool = %d: only the non-overlapping 2 x 2 maximum (pool = 2) is built", fn, (int)pool);
+        if (POH < 1 || POW < 1)
+            return fail(LQ_EINVAL, "%s: the conv output (%lld x %lld) holds no 2 x 2 window", fn, (long long)cd.OH, (long long)cd.OW);
+        if ((rc = i8_pixels_dims(fn, g->B, co, POH, POW, dout))) return rc;      // what is written: the pooled image's operand
+    }
     if ((rc = check_operand_buffers(fn, pix_codes, pix_scales, kI8ScaleAlign))) return rc;
     if ((rc = check_operand_buffers(fn, k_codes, k_scales, kI8ScaleAlign))) return rc;
     if ((rc = check_operand_buffers(fn, out_codes, out_scales, kI8ScaleAlign))) return rc;
@@ -2835,6 +2846,16 @@ static int i8_conv2d_quantize_entry(const char* fn, bool residual, const void* p
     q.affine_first = affine_first;
     q.CPo = (int32_t)dout.CP;
     q.OT = (int32_t)(dout.CP / kI8TileLines);
+    if (pooled) {                       // the kernel counts POOLED lines: four to an A tile (lq_i8_direct_quant_pool.hpp)
+        const int64_t PM = g->B * POH * POW;
+        q.c.M = (int32_t)PM;
+        q.c.MT = (int32_t)((PM + kI8PoolLines - 1) / kI8PoolLines);
+        q.c.ohow = make_fastdiv((uint32_t)(POH * POW));
+        q.c.ow = make_fastdiv((uint32_t)POW);
+        if (dk.step == 64) i8_conv2d_quantize_pool_launch<64>(q, (hipStream_t)stream);
+        else i8_conv2d_quantize_pool_launch<32>(q, (hipStream_t)stream);
+        return check_hip("direct int8 convolution with pooled pixel-operand epilogue");
+    }
     if (wide) {
         qr.res_codes = (const uint8_t*)res_codes;       // both NULL without a residual
         qr.res_scales = (const float*)res_scales;
@@ -2873,6 +2894,13 @@ int lq_i8_conv2d_quantize_wide(const void* pix_codes, const void* pix_scales, co
                                void* out_scales, void* stream) {
     return i8_conv2d_quantize_entry(__func__, res_codes || res_scales, pix_codes, pix_scales, k_codes, k_scales, bias, g, co, post_scale,
                                     post_shift, activation, affine_first, res_codes, res_scales, out_codes, out_scales, stream, true);
+}
+
+int lq_i8_conv2d_quantize_pool(const void* pix_codes, const void* pix_scales, const void* k_codes, const void* k_scales,
+                               const float* bias, const lq_conv_geom* g, int64_t co, const float* post_scale, const float* post_shift,
+                               int activation, int affine_first, int32_t pool, void* out_codes, void* out_scales, void* stream) {
+    return i8_conv2d_quantize_entry(__func__, false, pix_codes, pix_scales, k_codes, k_scales, bias, g, co, post_scale, post_shift,
+                                    activation, affine_first, nullptr, nullptr, out_codes, out_scales, stream, false, true, pool);
 }
 
 static int i8_operand_decode(const char* fn, bool affine, bool w4, const void* codes, const void* scales, const void* offsets, int64_t L,

@@ -1127,11 +1127,12 @@ class _ConvBase(_HostLayer):
             return y if self.data_format == "NHWC" else y.permute(0, 3, 1, 2)
 
     def _direct_step(self, x, operand, qb, max_lines=None, out_pixels=False, activation=None, affine=None, affine_first=False,
-                     residual=None, wide=False):
+                     residual=None, wide=False, pool=None):
         """One layer of a direct-conv chain: ``x`` a tensor in the layer's data format (quantised here, per run) or an ops.I8Pixels;
         the result the fp32 view ``_direct_conv`` returns, or (``out_pixels``) the next conv's ops.I8Pixels from the product's own
         epilogue (ops.i8_conv2d_quantize).  The batch is cut into runs of whole images by lines, as ``_direct_conv`` cuts it; a
-        ``residual`` (an ops.I8Pixels of the result's shape) is cut by the same images.  ``wide``: ops.i8_conv2d_quantize's."""
+        ``residual`` (an ops.I8Pixels of the result's shape) is cut by the same images.  ``wide`` and ``pool``:
+        ops.i8_conv2d_quantize's (a pool works inside an image, so the cut does not change it)."""
         def images_of(px):        # a cut: the codes of whole images stay on the 16-byte grid (CP % 32 == 0); the scales may not
             def cut(b0, b1):
                 scales = px.scales[b0:b1]
@@ -1158,10 +1159,10 @@ class _ConvBase(_HostLayer):
                                  f"{tuple(residual.shape) if isinstance(residual, ops.I8Pixels) else type(residual).__name__}")
             res = images_of(residual) if residual is not None else (lambda b0, b1: None)
             outs = [ops.i8_conv2d_quantize(run(b0, b1), operand, qb, self.strides, padding, activation, affine, affine_first, res(b0, b1),
-                                           wide) for b0, b1 in runs]
+                                           wide, pool) for b0, b1 in runs]
             if len(outs) == 1:
                 return outs[0]
-            return ops.I8Pixels(torch.cat([o.codes for o in outs]), torch.cat([o.scales for o in outs]), (B, self.filters, OH, OW))
+            return ops.I8Pixels(torch.cat([o.codes for o in outs]), torch.cat([o.scales for o in outs]), (B, *outs[0].shape[1:]))
         y = torch.empty((M, self.filters), dtype=torch.float32, device=operand.codes.device)
         for b0, b1 in runs:
             ops.i8_conv2d(run(b0, b1), operand, qb, self.strides, padding, out=y[b0 * per:b1 * per])
@@ -1169,7 +1170,7 @@ class _ConvBase(_HostLayer):
         return y if self.data_format == "NHWC" else y.permute(0, 3, 1, 2)
 
     def call_i8_direct(self, inputs, max_lines=None, out_pixels=False, activation=None, affine=None, affine_first=False,
-                       residual=None, wide=False):
+                       residual=None, wide=False, pool=None):
         """The layer as a direct int8 convolution, under ``no_grad``: the inputs quantised ONCE per pixel to symmetric 8-bit integers
         (ops.i8_pixels_quantize: an int8 NHWC copy, one scale per pixel), convolved with ``i8_direct_operand()`` on the int8 matrix
         instruction by ops.i8_conv2d -- TensorFlow 'SAME' padding as ``call`` pads, or 'VALID' -- plus the fake-quantised bias where
@@ -1184,8 +1185,13 @@ class _ConvBase(_HostLayer):
         ``residual`` (with ``out_pixels=True``): an ops.I8Pixels of the result's shape, decoded and added directly before the
         activation by the same epilogue (the basic ResNet block).
         ``wide=True`` (with ``out_pixels=True``): a layer of more than 512 filters, up to 2048, goes through the epilogue that parks
-        its output row in LDS (ops.i8_conv2d_quantize, ``wide``); a layer of at most 512 goes where it goes without it."""
+        its output row in LDS (ops.i8_conv2d_quantize, ``wide``); a layer of at most 512 goes where it goes without it.
+        ``pool=2`` (with ``out_pixels=True``): the epilogue takes the 2 x 2 maximum after the activation and the affine and writes
+        the pixel operand of the pooled image (ops.i8_conv2d_quantize, ``pool``); refused without ``out_pixels``."""
         _check_max_lines(max_lines)
+        if pool is not None and not out_pixels:
+            raise ValueError(f"{self.name}: pool={pool!r} without out_pixels=True: the fp32 result has no epilogue to pool in; apply "
+                             "F.max_pool2d to the result")
         if not out_pixels and (activation is not None or affine is not None or affine_first or residual is not None):
             raise ValueError(f"{self.name}: the fp32 result takes no epilogue (activation={activation!r}, affine, affine_first, "
                              "residual): apply it to the result, or ask for out_pixels=True")
@@ -1199,7 +1205,7 @@ class _ConvBase(_HostLayer):
             qb = self.nested_q_b_layer(self.b) if self._has_bias else None
             if not direct:
                 return self._direct_conv(inputs, operand, qb, max_lines)
-            return self._direct_step(inputs, operand, qb, max_lines, out_pixels, activation, affine, affine_first, residual, wide)
+            return self._direct_step(inputs, operand, qb, max_lines, out_pixels, activation, affine, affine_first, residual, wide, pool)
 
 
 class CustomConv2DLayer(_ConvBase):
@@ -1423,18 +1429,30 @@ class i8_hardware(_matrix_hardware):
     wide=True)``, where a conv of more than 512 filters goes through the epilogue that parks its row in LDS
     (ops.i8_conv2d_quantize, ``wide``).  models.ResNet50Like then runs its 16 bottleneck blocks from pixel operand to pixel
     operand (52 convs listed; the last block's conv3 writes fp32 for the mean).  Without it (the default) ``i8_wide_chains`` is not
-    read and nothing changes."""
+    read and nothing changes.
+    ``pooled_convs=True`` (with ``fused_convs=True``): a module that states ``i8_pooled_chain()`` -- ``(chain, pools)``, as
+    models.CIFARCNN states its six convs with the MaxPool(2) of blocks 1 and 2 -- and whose layers all pass ``i8_direct_eligible``
+    evaluates its conv stack in eval mode through ``i8_conv_chain(..., pools=pools)`` instead of its ``i8_conv_chains()``: a conv
+    before a pool takes the 2 x 2 maximum in its own epilogue (ops.i8_conv2d_quantize, ``pool``), so the model runs from its
+    first conv to its last from pixel operand to pixel operand, and ``fused_conv_layers`` lists five layers for it.  The pool is
+    exact, but the BatchNorm before it is now ``bn_affine``'s ``(g, h)`` in the epilogue where ``fused_convs`` alone runs torch's
+    kernel on the fp32 result, so the outputs differ from ``fused_convs`` alone by those roundings (an ulp can move a code); bit
+    for bit they are ``call_i8_direct`` -> relu -> ``.mul(g)`` -> ``.add(h)`` -> ``F.max_pool2d`` written out.  Without it (the default) ``i8_pooled_chain`` is not read and nothing changes."""
 
     _family, _dense_eligible = _I8, staticmethod(i8_hardware_eligible)
 
     def __init__(self, model: nn.Module, act_block=0, emulate=False, convs=False, fused=False, offsets=False, direct=False,
-                 int4=False, fused_convs=False, wide_convs=False):
+                 int4=False, fused_convs=False, wide_convs=False, pooled_convs=False):
         self.direct, self.direct_layers = bool(direct), []
         self.fused_convs, self.fused_conv_layers, self._fused_conv_modules = bool(fused_convs), [], []
         self.wide_convs = bool(wide_convs)
         if self.wide_convs and not self.fused_convs:
             raise ValueError("i8_hardware: wide_convs=True needs fused_convs=True: it widens the pixel-operand epilogue of the fused "
                              "conv chains to 2048 filters")
+        self.pooled_convs, self._pooled_conv_modules = bool(pooled_convs), []
+        if self.pooled_convs and not self.fused_convs:
+            raise ValueError("i8_hardware: pooled_convs=True needs fused_convs=True: it takes the max-pool between fused conv chains "
+                             "into the pixel-operand epilogue")
         if self.fused_convs and not (convs and direct):
             raise ValueError("i8_hardware: fused_convs=True needs convs=True and direct=True: the epilogue writes the pixel operand of "
                              "the direct int8 convolution")
@@ -1498,6 +1516,8 @@ class i8_hardware(_matrix_hardware):
         self.fused_conv_layers, self._fused_conv_modules = [], []
         with torch.no_grad():
             for mod in self.model.modules():
+                if self.pooled_convs and self._enter_pooled_convs(mod):
+                    continue
                 stated, every, most = self._stated_chains(mod)
                 parked = []
                 for chain in stated:
@@ -1515,7 +1535,30 @@ class i8_hardware(_matrix_hardware):
                     mod._i8_fused_convs = parked
                     self._fused_conv_modules.append(mod)
 
+    def _enter_pooled_convs(self, mod):
+        """A module that states ``i8_pooled_chain()`` -- (chain, pools) -- whose layers all pass ``i8_direct_eligible`` gets the
+        chain with its affines as ``(g, h)`` and the pools, and the layers their operands; True then.  Otherwise nothing changes
+        and its ``i8_conv_chains()`` are read as ever."""
+        if not callable(getattr(mod, "i8_pooled_chain", None)):
+            return False
+        chain, pools = mod.i8_pooled_chain()
+        if not (all(i8_direct_eligible(c) and act in ops.MX_ACTIVATIONS for c, act, _, _ in chain)
+                and all(c.filters <= ops.I8_CONV_QUANT_MAX_FILTERS for c, _, _, _ in chain[:-1])):
+            return False
+        for c, _, _, _ in chain:
+            c._i8_chain_hw = c._i8_direct_hw or (c.i8_direct_operand(), c.nested_q_b_layer(c.b).detach() if c._has_bias else None)
+        self.fused_conv_layers += [c for c, _, _, _ in chain[:-1]]
+        mod._i8_pooled_convs = ([(c, act, bn_affine(aff) if isinstance(aff, nn.BatchNorm2d) else aff, first)
+                                 for c, act, aff, first in chain], list(pools))
+        self._pooled_conv_modules.append(mod)
+        return True
+
     def __exit__(self, *exc):
+        for mod in self._pooled_conv_modules:
+            for c, _, _, _ in mod._i8_pooled_convs[0]:
+                c._i8_chain_hw = None
+            mod._i8_pooled_convs = None
+        self._pooled_conv_modules = []
         for mod in self._fused_conv_modules:
             mod._i8_fused_convs = None
             for chain in filter(None, self._stated_chains(mod)[0]):
@@ -1612,7 +1655,7 @@ def bn_affine(bn: nn.BatchNorm2d):
         return g.float(), (beta - bn.running_mean.double() * g).float()
 
 
-def i8_conv_chain(x, chain, max_lines=None, out_pixels=False, wide=False):
+def i8_conv_chain(x, chain, max_lines=None, out_pixels=False, wide=False, pools=None):
     """``chain`` = [(conv, activation, affine, affine_first), ...]: conv layers applied one after the other as direct int8
     convolutions, under ``no_grad``.  ``x`` is quantised once per pixel; every layer but the last goes through
     ops.i8_conv2d_quantize, whose epilogue applies ``activation`` (None or "relu") and ``affine`` (None or ``(g, h)``, ``bn_affine``)
@@ -1629,12 +1672,32 @@ def i8_conv_chain(x, chain, max_lines=None, out_pixels=False, wide=False):
     A residual on a last layer that writes fp32 is refused: the fp32 result has no epilogue to add it in.
     ``wide=True``: a layer with an epilogue may have up to 2048 filters (ops.I8_CONV_QUANT_WIDE_MAX_FILTERS); one of more than 512
     goes through ops.i8_conv2d_quantize(..., wide=True), every other where it goes without the flag, so a chain can mix widths.
-    So a bottleneck block is ``[(conv1, "relu", bn1, True), (conv2, "relu", bn2, True), (conv3, "relu", bn3, True, shortcut)]``."""
+    So a bottleneck block is ``[(conv1, "relu", bn1, True), (conv2, "relu", bn2, True), (conv3, "relu", bn3, True, shortcut)]``.
+    ``pools``: a sequence with one entry per step, None or 2.  A step with 2 takes the non-overlapping 2 x 2 maximum after its
+    activation and affine, in the same epilogue (ops.i8_conv2d_quantize, ``pool``), and writes the pixel operand of the pooled
+    image: conv -> relu -> BN -> MaxPool(2) -> conv without an fp32 activation.  It is refused on a step that writes fp32, has
+    a residual or has more than 512 filters.  So models.CIFARCNN's six convs are one chain (``i8_pooled_chain()``)."""
     fn = "i8_conv_chain"
     chain = [tuple(step) for step in chain]
     _check_max_lines(max_lines)
     if not chain:
         raise ValueError(f"{fn}: the chain is empty")
+    pools = [None] * len(chain) if pools is None else list(pools)
+    if len(pools) != len(chain):
+        raise ValueError(f"{fn}: pools has {len(pools)} entries for {len(chain)} steps: one per step, None or 2")
+    for k, pool in enumerate(pools):
+        if pool is None:
+            continue
+        if isinstance(pool, bool) or pool != 2:
+            raise ValueError(f"{fn}: step {k}: pool={pool!r}: only the non-overlapping 2 x 2 maximum (2) is built, or None")
+        if k == len(chain) - 1 and not out_pixels:
+            raise ValueError(f"{fn}: step {k}: a pool on the last layer, which writes fp32: apply F.max_pool2d to the result, or ask "
+                             "for out_pixels=True")
+        if len(chain[k]) == 5 and chain[k][4] is not None:
+            raise ValueError(f"{fn}: step {k}: a pool on a step with a residual is not built")
+        if len(chain[k]) in (4, 5) and getattr(chain[k][0], "filters", 0) > ops.I8_CONV_QUANT_MAX_FILTERS:
+            raise ValueError(f"{fn}: step {k}: a pool on a step with {chain[k][0].filters} filters: the pooled epilogue holds its row "
+                             f"in registers, at most {ops.I8_CONV_QUANT_MAX_FILTERS}")
     for k, step in enumerate(chain):
         if len(step) not in (4, 5):
             raise ValueError(f"{fn}: step {k} must be (conv, activation, affine, affine_first) or the same and a residual, got "
@@ -1670,7 +1733,7 @@ def i8_conv_chain(x, chain, max_lines=None, out_pixels=False, wide=False):
             hw = layer._i8_chain_hw
             operand, qb = hw if hw is not None else (layer.i8_direct_operand(), layer.nested_q_b_layer(layer.b) if layer._has_bias else None)
             a = layer._direct_step(a, operand, qb, max_lines, out_pixels or k < len(chain) - 1, activation, affine, affine_first,
-                                   step[4] if len(step) == 5 else None, wide)
+                                   step[4] if len(step) == 5 else None, wide and pools[k] is None, pools[k])
         return a
 
 

@@ -134,9 +134,18 @@ class CIFARCNN(nn.Module):
         """The three conv -> relu -> BN -> conv pairs as layers.i8_conv_chain takes them (the BatchNorm stands for its affine)."""
         return [[(self.convs[k], "relu", self.bns[k], False), (self.convs[k + 1], None, None, False)] for k in (0, 2, 4)]
 
+    def i8_pooled_chain(self):
+        """``(chain, pools)``: the six convs as ONE chain of layers.i8_conv_chain, the MaxPool(2) of blocks 1 and 2 taken in the
+        epilogue of their second conv (``pools``).  The last conv writes fp32: relu, BN and the last pool follow it."""
+        chain = [(self.convs[k], "relu", self.bns[k], False) for k in range(5)] + [(self.convs[5], None, None, False)]
+        return chain, [None, 2, None, 2, None, None]
+
     def forward(self, x):
+        pooled = None if self.training else getattr(self, "_i8_pooled_convs", None)      # layers.i8_hardware(..., pooled_convs=True)
+        if pooled is not None:                                     # all six convs as one chain; in eval mode a dropout is the identity
+            x = F.max_pool2d(self.bns[5](F.relu(i8_conv_chain(x, pooled[0], pools=pooled[1]))), 2)
         fused = getattr(self, "_i8_fused_convs", None)             # inside layers.i8_hardware(..., fused_convs=True)
-        for blk in range(3):
+        for blk in range(3) if pooled is None else ():
             if fused is not None and fused[blk] is not None and not self.training:
                 x = self.bns[2 * blk + 1](F.relu(i8_conv_chain(x, fused[blk])))
             else:

@@ -1351,7 +1351,7 @@ def i8_conv2d(pixels: I8Pixels, kernel: I8ConvKernel, bias: Optional[torch.Tenso
 
 def i8_conv2d_quantize(pixels: I8Pixels, kernel: I8ConvKernel, bias: Optional[torch.Tensor] = None, strides=(1, 1), padding=(0, 0, 0, 0),
                        activation=None, affine=None, affine_first: bool = False, residual: Optional[I8Pixels] = None,
-                       wide: bool = False) -> I8Pixels:
+                       wide: bool = False, pool: Optional[int] = None) -> I8Pixels:
     """The pixel operand of the NEXT conv, written by the convolution's own epilogue (include/lq_hip.h, lq_i8_conv2d_quantize): byte
     for byte ``i8_pixels_quantize`` of ``v`` seen as ``(B, co, OH, OW)``, where ``v = aff(act(Y))`` (``affine_first=False``: conv,
     relu, BatchNorm) or ``v = act(aff(Y))`` (``affine_first=True``), ``Y`` is ``i8_conv2d``'s result bit for bit and ``aff(v) = v *
@@ -1364,8 +1364,18 @@ def i8_conv2d_quantize(pixels: I8Pixels, kernel: I8ConvKernel, bias: Optional[to
     ``wide=True``: ``co`` above 512, up to ``I8_CONV_QUANT_WIDE_MAX_FILTERS`` (2048: a bottleneck block's expanding conv and
     projection shortcut), goes to lq_i8_conv2d_quantize_wide, which parks the output row in LDS -- the same definition, with or
     without ``residual``, one launch.  A ``co`` of at most 512 goes where it goes without the flag, so the bytes there do not
-    depend on it.  Without it (the default) nothing changes."""
+    depend on it.  Without it (the default) nothing changes.
+    ``pool=2``: the epilogue takes the non-overlapping 2 x 2 maximum of ``v`` -- conv, relu, BatchNorm, MaxPool(2) -- in the
+    accumulator registers and writes the pixel operand of the POOLED image (lq_i8_conv2d_quantize_pool): byte for byte
+    ``i8_pixels_quantize(F.max_pool2d(v, 2))``, shape ``(B, co, OH // 2, OW // 2)``, one launch.  Any other value is a ValueError;
+    with ``residual`` or ``wide=True`` it is not built.  Without it (the default) nothing changes."""
     import ctypes
+    if pool is not None:
+        if isinstance(pool, bool) or pool != 2:
+            raise ValueError(f"pool={pool!r}: only the non-overlapping 2 x 2 maximum (pool=2) is built, or None")
+        if residual is not None or wide:
+            raise ValueError("pool with residual or wide=True is not built: the pooled epilogue takes no residual and holds its "
+                             f"row in registers (at most {I8_CONV_QUANT_MAX_FILTERS} filters)")
     act = check_mx_activation(activation)
     dev = _check_i8_conv_operands(pixels, kernel)
     co = kernel.filters
@@ -1382,10 +1392,14 @@ def i8_conv2d_quantize(pixels: I8Pixels, kernel: I8ConvKernel, bias: Optional[to
     g = _conv_geom(pixels.shape, (0, 0, 0, 0), kernel.kernel_size, strides, padding)
     _, _, OH, OW = _geom_dims(lib, g)
     B = int(pixels.shape[0])
+    name, res = "lq_i8_conv2d_quantize", ()
+    if pool is not None:
+        if OH < 2 or OW < 2:
+            raise ValueError(f"pool=2: the conv output ({OH} x {OW}) holds no 2 x 2 window")
+        OH, OW, name, res = OH // 2, OW // 2, name + "_pool", (2,)
     cb, _ = i8_pixels_bytes(B, co, OH, OW)
     codes = torch.empty((B, OH, OW, cb // (B * OH * OW)), dtype=torch.uint8, device=dev)
     scales = torch.empty((B, OH, OW), dtype=torch.float32, device=dev)
-    name, res = "lq_i8_conv2d_quantize", ()
     if residual is not None:
         _check_i8_residual(residual, (B, co, OH, OW), tuple(codes.shape), dev)
         name, res = name + "_residual", (_hip.ptr(residual.codes), _hip.ptr(residual.scales))

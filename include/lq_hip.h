@@ -836,6 +836,56 @@ int lq_i8_conv2d_quantize_pool(const void* pix_codes, const void* pix_scales, co
                                int activation /* lq_mx_activation */, int affine_first, int32_t pool /* 2 */, void* out_codes,
                                void* out_scales, void* stream);
 
+/* ---- the direct int8 convolution of a FIRST layer (stem): an input of at most 4 channels under one scale per image row ----
+ * lq_i8_conv2d sums a tap exactly under one pixel scale, so at C = 3 each step of the matrix instruction carries 3 live bytes of
+ * 32.  With ONE SCALE PER IMAGE ROW a whole kernel row -- KW taps x 4 channel bytes <= 32 -- is one exact int32 step of
+ * v_mfma_i32_16x16x32_i8: a 7 x 7 stem is 7 instructions per 16 x 16 tile instead of 49, and the operand is 4 bytes per pixel.
+ * ROW OPERAND (lq_i8_rows_bytes, lq_i8_rows_quantize).  X is logically [B][C][H][W], 1 <= C <= 4, read through the xs_* element
+ * strides of `g` exactly as lq_i8_pixels_quantize reads it (B, C, H, W and xs_* are the only fields read; 4-byte loads of elements
+ * the row holds and of no others).  It writes
+ *   codes   [B][H][W][4] int8 (NHWC4): channel c in byte c, bytes C .. 3 hold code 0
+ *   scales  [B][H] fp32, one per image row
+ * and the scale and codes of row (b, h) are what lq_i8_operand_quantize gives row b * H + h of the matrix
+ * X.permute(0, 2, 3, 1).reshape(B * H, W * C) with block = 0: absmax over the row's W * C elements, qmin -127, qmax 127, min_value
+ * 2^-126, nearest even -- that kernel's own scale rule and element step.  A zero row gets scale 2^-126 and codes 0; a row holding
+ * a NaN or +-Inf gets a NaN scale and codes 0, and no other row does.  X is read once where W <= 256, the pixels past 256 a second
+ * time.  code_bytes = 4 * B * H * W, scale_bytes = 4 * B * H.
+ * STEM KERNEL OPERAND (lq_i8_stem_kernel_bytes, lq_i8_stem_kernel_pack).  An OIHW-stored kernel P[co][ci][KH][KW] with ci <= 4,
+ * KW <= 8 and KH <= 16 under ONE scale per filter, s[co]:
+ *   codes   [NT][KH][64 lanes][8], NT = ceil(co / 16): lane l, byte jj holds filter 16 nt + (l & 15), tap column
+ *           j = 2 (l >> 4) + (jj >> 2), channel jj & 3, of kernel row i; code 0 for j >= KW, c >= ci and filters past co
+ *   scales  [16 NT] fp32, s copied bit for bit, 1.0f past co
+ * The codes are lq_i8_conv_kernel_pack's for the same element (the same element step, `rounding` included).  code_bytes = 512 *
+ * NT * KH, scale_bytes = 64 * NT.
+ * PRODUCT (lq_i8_stem_conv2d).  lq_i8_conv2d's arguments with the row operand in the place of the pixel operand; Y, M, OH, OW and
+ * the line order are lq_i8_conv2d's.  DEFINITION (bit exact, independent of any tiling; tests/_i8_stem_reference.py states it in
+ * NumPy).  For output (m, n), from y = +0, over the kernel rows i ascending:
+ *       ih = oh * stride_h - pad_top + i; a row outside the image is skipped; otherwise, with iw = ow * stride_w - pad_left + j,
+ *       I = sum_{j, 0 <= iw < W} sum_c a[b][ih][iw][c] * q[n][c][i][j]      exact, int32
+ *       y = RN(y + RN((float)I * sr[b][ih]))                                 the product and the sum round separately
+ *   after the last row y = RN(y * sk[n]), and with a bias y = RN(y + bias[n]).  A NaN row scale makes NaN exactly the outputs
+ *   whose window covers the row; a NaN filter scale makes its column NaN.  No atomics: run-to-run bit-stable.
+ * EPILOGUE (lq_i8_stem_conv2d_quantize).  lq_i8_conv2d_quantize's arguments and definition with Y replaced by the stem product's
+ * Y: out_codes / out_scales are, byte for byte, lq_i8_pixels_quantize of v seen as [B][co][OH][OW] -- the NEXT conv's ordinary
+ * pixel operand.  co <= 128: one wave holds a whole output row.
+ * Each call only enqueues ONE launch (capturable), allocates nothing, uses no workspace, atomics or memset, reads no environment
+ * and writes exactly its code_bytes and scale_bytes, the M x co elements of Y, or lq_i8_pixels_bytes(B, co, OH, OW).  LQ_EINVAL /
+ * LQ_EALIGN before any launch, in the order of the twin entry: everything lq_i8_pixels_quantize, lq_i8_conv_kernel_pack,
+ * lq_i8_conv2d and lq_i8_conv2d_quantize refuse (with 4 * B * H * W < 2^31 for the row codes), and C (ci) > 4, KW > 8, KH > 16
+ * (the product stages up to 8 column tiles of 512 * KH bytes in 64 KB of LDS) and, for the epilogue, co > 128.
+ * Not built: a max-pool, a residual or MX elements in this epilogue, group-wise or asymmetric weight scales, C > 4, KW > 8.  */
+int lq_i8_rows_bytes(int64_t B, int64_t C, int64_t H, int64_t W, size_t* code_bytes, size_t* scale_bytes);
+int lq_i8_rows_quantize(const float* X, const lq_conv_geom* g, void* codes, void* scales, void* stream);
+int lq_i8_stem_kernel_bytes(int64_t co, int64_t ci, int64_t KH, int64_t KW, size_t* code_bytes, size_t* scale_bytes);
+int lq_i8_stem_kernel_pack(const float* P, const float* s, int32_t qmin, int32_t qmax, int rounding, int64_t co, int64_t ci, int64_t KH,
+                           int64_t KW, void* codes, void* scales, void* stream);
+int lq_i8_stem_conv2d(const void* row_codes, const void* row_scales, const void* k_codes, const void* k_scales,
+                      const float* bias /* may be NULL */, float* Y, int64_t ldy, const lq_conv_geom* g, int64_t co, void* stream);
+int lq_i8_stem_conv2d_quantize(const void* row_codes, const void* row_scales, const void* k_codes, const void* k_scales,
+                               const float* bias /* may be NULL */, const lq_conv_geom* g, int64_t co,
+                               const float* post_scale /* [co]; both or neither NULL */, const float* post_shift,
+                               int activation /* lq_mx_activation */, int affine_first, void* out_codes, void* out_scales, void* stream);
+
 /* ---- K4: forward and NQ backward of one tensor in a single pass (benchmark path) ---
  * Same results as lq_fq_forward followed by lq_fq_scale_grad (out, max|q| and the vote count bit for bit; on
  * streaming-size tensors the vote sum may differ by fp32 summation order, ~1e-7 relative); P is read once.  */

@@ -8,7 +8,7 @@ reference's own Python layer surface, executed by hand-written HIP kernels throu
 from .descriptor import (ORIENTATIONS, group_descriptor, group_geometry, groupwise_scale_shape, init_geometry, memory_descriptor, memory_order,
                          scale_shape)
 from .layers import (default_kernel_storage, CustomConv2DLayer, CustomConv2DLayerNoBias, CustomDenseLayer, CustomQuantizedScaleLayer,
-                     L2, MinValueConstraint, RandomNormal, SCALE_INIT, custom_layers_of, eps_float32, bn_affine, i8_conv_chain, i8_conv_eligible, i8_dense_chain, i8_direct_eligible, i8_hardware, i8_hardware_eligible, i8_int4_eligible, init_scales, l2,
+                     L2, MinValueConstraint, RandomNormal, SCALE_INIT, custom_layers_of, eps_float32, bn_affine, i8_conv_chain, i8_conv_eligible, i8_dense_chain, i8_direct_eligible, i8_hardware, i8_hardware_eligible, i8_int4_eligible, i8_stem_eligible, init_scales, l2,
                      mx_conv_eligible, mx_dense_chain, mx_hardware, mx_hardware_eligible, mx_quant_stats, quant_stats, quantized_tensors, reset_layer_names)
 from .losses import LossLog, SCCEDifference, SCCEInverse, SCCEMaxBin, sparse_categorical_crossentropy
 from .ops import (difference_term, fq_backward_clip, fq_backward_group, fq_forward, fq_forward_clip, fq_forward_group, fq_fwd_bwd_fused, fq_scale_grad, fq_scale_grad_ste,
@@ -20,6 +20,7 @@ from .ops import (difference_term, fq_backward_clip, fq_backward_group, fq_forwa
                   I8AffineOperand, I8Operand, check_i8_conv_operand_layer, check_i8_operand_layer, i8_gemm, i8_gemm_quantize, i8_operand_bytes, i8_operand_decode, i8_operand_im2col, i8_operand_pack, i8_operand_quantize,
                   I4Operand, check_i4_operand_layer, i4_operand_bytes, i4_operand_pack,
                   I8ConvKernel, I8Pixels, check_i8_direct_layer, i8_conv2d, i8_conv2d_quantize, i8_conv_kernel_pack, i8_pixels_quantize,
+                  I8Rows, I8StemKernel, i8_rows_quantize, i8_stem_conv2d, i8_stem_conv2d_quantize, i8_stem_kernel_pack,
                   my_custom_gradient, q_absmax_over_axis, q_minmax, q_pack, q_range_of, q_unique, q_unpack, quantized_integers, SCALE_INITS, scale_init_group)
 from .optim import KerasAdam, ScaleAdam, apply_constraints, non_scale_parameters, scale_parameters
 from .ddp import DataParallel, GradBucket

@@ -194,6 +194,13 @@ SIGNATURES.update({
                                             _c_p, _c_p, _c_p, _c_p, _c_p]),
     "lq_i8_conv2d_quantize_pool": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, ctypes.POINTER(ConvGeom), _c_i64, _c_p, _c_p, _c_int, _c_int,
                                             _c_i32, _c_p, _c_p, _c_p]),
+    "lq_i8_rows_bytes": (_c_int, [_c_i64, _c_i64, _c_i64, _c_i64, ctypes.POINTER(_c_sz), ctypes.POINTER(_c_sz)]),
+    "lq_i8_rows_quantize": (_c_int, [_c_p, ctypes.POINTER(ConvGeom), _c_p, _c_p, _c_p]),
+    "lq_i8_stem_kernel_bytes": (_c_int, [_c_i64, _c_i64, _c_i64, _c_i64, ctypes.POINTER(_c_sz), ctypes.POINTER(_c_sz)]),
+    "lq_i8_stem_kernel_pack": (_c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p]),
+    "lq_i8_stem_conv2d": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, ctypes.POINTER(ConvGeom), _c_i64, _c_p]),
+    "lq_i8_stem_conv2d_quantize": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, ctypes.POINTER(ConvGeom), _c_i64, _c_p, _c_p, _c_int, _c_int,
+                                            _c_p, _c_p, _c_p]),
 })
 
 

@@ -28,6 +28,7 @@
 //   lq_i8_direct_quant.hpp  the direct int8 convolution with an epilogue that writes the next conv's pixel operand
 //   lq_i8_direct_quant_wide.hpp  that epilogue for rows of up to 2048 filters: the output row parked in LDS
 //   lq_i8_direct_quant_pool.hpp  that epilogue behind a 2 x 2 max-pool taken in the accumulator registers
+//   lq_i8_stem.hpp      the direct int8 convolution of a first layer (C <= 4): row-scaled operand, a kernel row per step, B in LDS
 //   this file           host side: traversal plan, launchers, the extern "C" entry points
 //
 // The path is elementwise + per-group reductions: HBM-bound, no MFMA.  Design rules
@@ -86,6 +87,7 @@
 #include "lq_i8_direct_quant.hpp"
 #include "lq_i8_direct_quant_wide.hpp"
 #include "lq_i8_direct_quant_pool.hpp"
+#include "lq_i8_stem.hpp"
 
 namespace lq {
 
@@ -2901,6 +2903,195 @@ int lq_i8_conv2d_quantize_pool(const void* pix_codes, const void* pix_scales, co
                                int activation, int affine_first, int32_t pool, void* out_codes, void* out_scales, void* stream) {
     return i8_conv2d_quantize_entry(__func__, false, pix_codes, pix_scales, k_codes, k_scales, bias, g, co, post_scale, post_shift,
                                     activation, affine_first, nullptr, nullptr, out_codes, out_scales, stream, false, true, pool);
+}
+
+// ---- the direct int8 convolution of a first layer: row-scaled operand, a kernel row per step (lq_i8_stem.hpp) ----
+struct I8StemDims {
+    int64_t NT;
+    size_t code_bytes, scale_bytes;
+};
+
+static int i8_rows_dims(const char* fn, int64_t B, int64_t C, int64_t H, int64_t W, I8StemDims& d) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0)
+        return fail(LQ_EINVAL, "%s: extents must be positive (B=%lld C=%lld H=%lld W=%lld)", fn, (long long)B, (long long)C, (long long)H,
+                    (long long)W);
+    if (C > kI8StemChannels)
+        return fail(LQ_EINVAL, "%s: C = %lld channels is above %d: a pixel of the row operand is one dword; a wider input takes "
+                    "lq_i8_pixels_quantize", fn, (long long)C, kI8StemChannels);
+    const double bytes = (double)B * (double)H * (double)W * (double)kI8StemChannels;
+    if (bytes >= 2147483648.0)
+        return fail(LQ_EINVAL, "%s: the row codes, B * H * W * 4 = %lld * %lld * %lld * 4 bytes, are not below 2^31", fn, (long long)B,
+                    (long long)H, (long long)W);
+    d.code_bytes = (size_t)(B * H * W * kI8StemChannels);
+    d.scale_bytes = (size_t)(B * H * 4);
+    return LQ_OK;
+}
+
+static int i8_stem_kernel_dims(const char* fn, int64_t co, int64_t ci, int64_t KH, int64_t KW, I8StemDims& d) {
+    if (co <= 0 || ci <= 0) return fail(LQ_EINVAL, "%s: extents must be positive (co=%lld ci=%lld)", fn, (long long)co, (long long)ci);
+    if (KH <= 0 || KW <= 0) return fail(LQ_EINVAL, "%s: kernel size must be positive (KH=%lld KW=%lld)", fn, (long long)KH, (long long)KW);
+    if (ci > kI8StemChannels)
+        return fail(LQ_EINVAL, "%s: ci = %lld channels is above %d: a tap of the stem operand is one dword; a wider kernel takes "
+                    "lq_i8_conv_kernel_pack", fn, (long long)ci, kI8StemChannels);
+    if (KW > kI8StemMaxKW)
+        return fail(LQ_EINVAL, "%s: KW = %lld is above %d: a kernel row, KW taps of 4 bytes, must fit the 32 bytes of one step of the "
+                    "matrix instruction", fn, (long long)KW, kI8StemMaxKW);
+    if (KH > kI8StemMaxKH)
+        return fail(LQ_EINVAL, "%s: KH = %lld is above %d: the product stages up to 8 column tiles of KH * 512 bytes in 64 KB of LDS", fn,
+                    (long long)KH, kI8StemMaxKH);
+    if (co > 2147483647 - kI8TileLines) return fail(LQ_EINVAL, "%s: co = %lld is not below 2^31", fn, (long long)co);
+    d.NT = (co + kI8TileLines - 1) / kI8TileLines;
+    if ((double)d.NT * (double)KH * 512.0 >= 2147483648.0)
+        return fail(LQ_EINVAL, "%s: the kernel codes, NT * KH * 512 bytes (co=%lld KH=%lld), are not below 2^31", fn, (long long)co,
+                    (long long)KH);
+    d.code_bytes = (size_t)(d.NT * KH * 512);
+    d.scale_bytes = (size_t)(d.NT * kI8TileLines * 4);
+    return LQ_OK;
+}
+
+int lq_i8_rows_bytes(int64_t B, int64_t C, int64_t H, int64_t W, size_t* code_bytes, size_t* scale_bytes) {
+    const char* fn = __func__;
+    return i8_bytes<I8StemDims>(fn, code_bytes, scale_bytes, [&](I8StemDims& d) { return i8_rows_dims(fn, B, C, H, W, d); });
+}
+
+int lq_i8_stem_kernel_bytes(int64_t co, int64_t ci, int64_t KH, int64_t KW, size_t* code_bytes, size_t* scale_bytes) {
+    const char* fn = __func__;
+    return i8_bytes<I8StemDims>(fn, code_bytes, scale_bytes, [&](I8StemDims& d) { return i8_stem_kernel_dims(fn, co, ci, KH, KW, d); });
+}
+
+int lq_i8_rows_quantize(const float* X, const lq_conv_geom* g, void* codes, void* scales, void* stream) {
+    const char* fn = __func__;
+    LQ_REQUIRE_PTR_FN(fn, X);
+    if (!g) return fail(LQ_EINVAL, "%s: argument 'g' is NULL", fn);
+    I8StemDims d{};
+    int rc = i8_rows_dims(fn, g->B, g->C, g->H, g->W, d);
+    if (rc) return rc;
+    if (g->xs_b < 0 || g->xs_c < 0 || g->xs_h < 0 || g->xs_w < 0)
+        return fail(LQ_EINVAL, "%s: strides of X must not be negative (xs_b=%lld xs_c=%lld xs_h=%lld xs_w=%lld)", fn, (long long)g->xs_b,
+                    (long long)g->xs_c, (long long)g->xs_h, (long long)g->xs_w);
+    if ((rc = check_operand_buffers(fn, codes, scales, kI8ScaleAlign))) return rc;
+    I8RowsParams op{};
+    op.g.P = X;
+    i8_act_quantizer(op.g, op.ip);
+    op.codes = (uint32_t*)codes;
+    op.scales = (float*)scales;
+    op.xs_b = g->xs_b;
+    op.xs_c = g->xs_c;
+    op.xs_h = g->xs_h;
+    op.xs_w = g->xs_w;
+    op.h = make_fastdiv((uint32_t)g->H);           // 4 B H W < 2^31 bounds every product of the extents
+    op.NR = (int32_t)(g->B * g->H);
+    op.C = (int32_t)g->C;
+    op.W = (int32_t)g->W;
+    const int per = kBlock / 64;                   // a wave per row
+    const dim3 grid((unsigned)(((int64_t)op.NR + per - 1) / per)), blk(kBlock);
+    hipLaunchKernelGGL(k_i8_rows, grid, blk, 0, (hipStream_t)stream, op);
+    return check_hip("int8 row operand");
+}
+
+int lq_i8_stem_kernel_pack(const float* P, const float* s, int32_t qmin, int32_t qmax, int rounding, int64_t co, int64_t ci, int64_t KH,
+                           int64_t KW, void* codes, void* scales, void* stream) {
+    const char* fn = __func__;
+    LQ_REQUIRE_PTR_FN(fn, P);
+    LQ_REQUIRE_PTR_FN(fn, s);
+    int rc = check_clip_range(fn, qmin, qmax);
+    if (rc || (rc = check_rounding(fn, rounding))) return rc;
+    if (qmin < -128 || qmax > 127)
+        return fail(LQ_EINVAL, "%s: range [%d, %d] is not inside [-128, 127], the operands of the int8 matrix instruction", fn, (int)qmin,
+                    (int)qmax);
+    I8StemDims d{};
+    if ((rc = i8_stem_kernel_dims(fn, co, ci, KH, KW, d))) return rc;
+    if ((rc = check_operand_buffers(fn, codes, scales, kI8ScaleAlign))) return rc;
+    I8StemPackParams op{};
+    op.g.P = P;
+    op.g.s = s;
+    op.g.lo = (float)qmin;
+    op.g.hi = (float)qmax;
+    op.g.k = 1.0f;
+    op.codes = (uint8_t*)codes;
+    op.scales = (float*)scales;
+    op.co = (int32_t)co;
+    op.ci = (int32_t)ci;
+    op.KH = (int32_t)KH;
+    op.KW = (int32_t)KW;
+    op.NT = (int32_t)d.NT;
+    const int64_t threads = d.NT * KH * 64;
+    const dim3 grid((unsigned)((threads + kBlock - 1) / kBlock)), blk(kBlock);
+    if (rounding == LQ_ROUND_NEAREST_EVEN) hipLaunchKernelGGL(k_i8_stem_pack<true>, grid, blk, 0, (hipStream_t)stream, op);
+    else hipLaunchKernelGGL(k_i8_stem_pack<false>, grid, blk, 0, (hipStream_t)stream, op);
+    return check_hip("int8 stem kernel pack");
+}
+
+// the extents of the two stem products, in lq_i8_conv2d's order: the geometry, the row operand's limits, the kernel's
+static int i8_stem_conv2d_dims(const char* fn, const lq_conv_geom* g, int64_t co, ConvDims& cd, I8DirectDims& dk) {
+    int rc = conv_geom_dims(fn, g, cd);            // the xs_* fields are not read
+    if (rc) return rc;
+    I8StemDims dr{}, ds{};
+    if ((rc = i8_rows_dims(fn, g->B, g->C, g->H, g->W, dr))) return rc;
+    if ((rc = i8_stem_kernel_dims(fn, co, g->C, g->KH, g->KW, ds))) return rc;
+    dk.NT = ds.NT;                                 // what i8_conv2d_rule reads of the kernel; CS and CP are the direct path's, unused here
+    dk.CS = 1;
+    dk.CP = kI8StemChannels;
+    return LQ_OK;
+}
+
+int lq_i8_stem_conv2d(const void* row_codes, const void* row_scales, const void* k_codes, const void* k_scales, const float* bias,
+                      float* Y, int64_t ldy, const lq_conv_geom* g, int64_t co, void* stream) {
+    const char* fn = __func__;
+    ConvDims cd;
+    I8DirectDims dk{};
+    int rc = i8_stem_conv2d_dims(fn, g, co, cd, dk);
+    if (rc) return rc;
+    if ((rc = check_operand_buffers(fn, row_codes, row_scales, kI8ScaleAlign))) return rc;
+    if ((rc = check_operand_buffers(fn, k_codes, k_scales, kI8ScaleAlign))) return rc;
+    if ((rc = check_gemm_output(fn, bias, Y, ldy, cd.M, co))) return rc;
+    I8Conv2dParams p{};
+    dim3 unused;
+    if ((rc = i8_conv2d_rule(fn, row_codes, row_scales, k_codes, k_scales, g, co, cd, dk, p, unused))) return rc;
+    p.bias = bias;
+    p.Y = Y;
+    p.ldy = ldy;
+    i8_stem_conv2d_launch<false>(p, p.MT, p.KH, p.NT, (hipStream_t)stream);
+    return check_hip("int8 stem convolution");
+}
+
+int lq_i8_stem_conv2d_quantize(const void* row_codes, const void* row_scales, const void* k_codes, const void* k_scales,
+                               const float* bias, const lq_conv_geom* g, int64_t co, const float* post_scale, const float* post_shift,
+                               int activation, int affine_first, void* out_codes, void* out_scales, void* stream) {
+    const char* fn = __func__;
+    ConvDims cd;
+    I8DirectDims dk{}, dout{};
+    int rc = i8_stem_conv2d_dims(fn, g, co, cd, dk);
+    if (rc) return rc;
+    if (co > kI8StemMaxTiles * kI8TileLines)
+        return fail(LQ_EINVAL, "%s: co = %lld is above %d: a pixel's scale needs its whole output row, at most %d column tiles, in one "
+                    "wave before the first code", fn, (long long)co, kI8StemMaxTiles * kI8TileLines, kI8StemMaxTiles);
+    if (activation != LQ_ACT_NONE && activation != LQ_ACT_RELU) return fail(LQ_EINVAL, "%s: bad activation %d", fn, activation);
+    if (affine_first != 0 && affine_first != 1) return fail(LQ_EINVAL, "%s: affine_first = %d is neither 0 nor 1", fn, affine_first);
+    if ((post_scale == nullptr) != (post_shift == nullptr))
+        return fail(LQ_EINVAL, "%s: post_scale and post_shift must both be given or both be NULL", fn);
+    if ((rc = i8_pixels_dims(fn, g->B, co, cd.OH, cd.OW, dout))) return rc;      // what is written: M * CPo < 2^31
+    if ((rc = check_operand_buffers(fn, row_codes, row_scales, kI8ScaleAlign))) return rc;
+    if ((rc = check_operand_buffers(fn, k_codes, k_scales, kI8ScaleAlign))) return rc;
+    if ((rc = check_operand_buffers(fn, out_codes, out_scales, kI8ScaleAlign))) return rc;
+    if ((rc = check_gemm_bias(fn, bias))) return rc;
+    if (post_scale && (!aligned(post_scale, 4) || !aligned(post_shift, 4)))
+        return fail(LQ_EALIGN, "%s: post_scale or post_shift is not 4-byte aligned", fn);
+    I8ConvQuantParams q{};
+    dim3 unused;
+    if ((rc = i8_conv2d_rule(fn, row_codes, row_scales, k_codes, k_scales, g, co, cd, dk, q.c, unused))) return rc;
+    q.c.bias = bias;
+    i8_act_quantizer(q.gp, q.ip);
+    q.post_scale = post_scale;
+    q.post_shift = post_shift;
+    q.codes = (uint8_t*)out_codes;
+    q.scales = (float*)out_scales;
+    q.act = activation;
+    q.affine_first = affine_first;
+    q.CPo = (int32_t)dout.CP;
+    q.OT = (int32_t)(dout.CP / kI8TileLines);
+    i8_stem_conv2d_launch<true>(q, q.c.MT, q.c.KH, q.OT, (hipStream_t)stream);
+    return check_hip("int8 stem convolution with pixel-operand epilogue");
 }
 
 static int i8_operand_decode(const char* fn, bool affine, bool w4, const void* codes, const void* scales, const void* offsets, int64_t L,

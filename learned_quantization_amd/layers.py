@@ -842,6 +842,7 @@ class _ConvBase(_HostLayer):
     _has_bias = True
     _i8_direct_hw = None      # (operand, bias) parked by i8_hardware(convs=True, direct=True)
     _i8_chain_hw = None       # (operand, bias) parked by i8_hardware(fused_convs=True) on the layers of a conv chain
+    _i8_stem_hw = None        # (stem operand, bias) parked by i8_hardware(stem_convs=True) on a first conv of at most 4 channels
 
     def __init__(self, seed=None, penalty_threshold=None, orientation="scalar", initializer=None, filters=None,
                  kernel_size=(3, 3), strides=(1, 1), padding="same", name=None, regularizer=None,
@@ -947,6 +948,11 @@ class _ConvBase(_HostLayer):
         if direct is not None and not self.training:              # inside layers.i8_hardware(..., convs=True, direct=True), eval mode
             self._q_pre = None
             return self._direct_conv(inputs, direct[0], direct[1])
+        stem = self._i8_stem_hw
+        if stem is not None and not self.training:                # inside layers.i8_hardware(..., stem_convs=True), eval mode
+            self._q_pre = None
+            with torch.no_grad():
+                return self._direct_step(inputs, stem[0], stem[1])
         for family in (_MX, _I8):
             hw = getattr(self, family.hw, None)
             if hw is not None and not self.training:              # inside layers.mx_hardware / i8_hardware(..., convs=True), eval mode
@@ -1100,6 +1106,44 @@ class _ConvBase(_HostLayer):
         scale = self.nested_q_k_layer.scale.data.reshape(-1)      # one element ("scalar"), or one per filter ("groupwise", (co, 1))
         return ops.i8_conv_kernel_pack(self.kernel.detach().permute(3, 2, 0, 1), scale, qmin, qmax, self.rounding)
 
+    def _check_i8_stem(self):
+        """(qmin, qmax) of a conv layer that can run as a stem convolution, or ValueError naming the reason: what
+        ``_check_i8_direct`` asks, at most 4 input channels and a kernel of at most 16 x 8 (ops.check_i8_stem_shape)."""
+        q_range = self._check_i8_direct()
+        ops.check_i8_stem_shape(self.kernel.shape[2], self.kernel_size)
+        return q_range
+
+    def i8_stem_operand(self) -> "ops.I8StemKernel":
+        """The kernel under its current scales as the per-row operand of the stem convolution (ops.i8_stem_kernel_pack): the codes
+        of ``i8_direct_operand()``, a kernel row per step.  ValueError naming the reason for everything ``i8_direct_operand()``
+        refuses, for more than 4 input channels and for a kernel wider than 8 or higher than 16."""
+        qmin, qmax = self._check_i8_stem()
+        scale = self.nested_q_k_layer.scale.data.reshape(-1)
+        return ops.i8_stem_kernel_pack(self.kernel.detach().permute(3, 2, 0, 1), scale, qmin, qmax, self.rounding)
+
+    def call_i8_stem(self, inputs, max_lines=None, out_pixels=False, activation=None, affine=None, affine_first=False):
+        """The layer as a stem convolution, under ``no_grad``: the inputs (a tensor of at most 4 channels) quantised ONCE per image
+        row to symmetric 8-bit integers (ops.i8_rows_quantize: an int8 NHWC4 copy, one scale per row), convolved with
+        ``i8_stem_operand()`` by ops.i8_stem_conv2d -- a kernel row per step of the int8 matrix instruction, no padded channels, no
+        im2col matrix -- padded as ``call`` pads, plus the fake-quantised bias where the layer has one.  Inference only.  The result
+        is the kind of view ``call_i8_direct`` returns, and the batch is cut into runs of whole images as it cuts it.  The
+        activation scale is per image ROW here: the result is not bit-identical to ``call_i8`` or ``call_i8_direct``.
+        ``out_pixels=True``: the result is the NEXT conv's ops.I8Pixels from the product's own epilogue
+        (ops.i8_stem_conv2d_quantize) after ``activation`` and ``affine`` in the order ``affine_first`` says; at most 128 filters.
+        Without it an epilogue is refused."""
+        _check_max_lines(max_lines)
+        if not out_pixels and (activation is not None or affine is not None or affine_first):
+            raise ValueError(f"{self.name}: the fp32 result takes no epilogue (activation={activation!r}, affine, affine_first): "
+                             "apply it to the result, or ask for out_pixels=True")
+        if not isinstance(inputs, torch.Tensor):
+            raise ValueError(f"{self.name}: the stem convolution quantises a tensor itself, got {type(inputs).__name__}")
+        if not self.built:
+            self.build(tuple(inputs.shape), device=inputs.device)
+        with torch.no_grad():
+            operand = self.i8_stem_operand()
+            qb = self.nested_q_b_layer(self.b) if self._has_bias else None
+            return self._direct_step(inputs, operand, qb, max_lines, out_pixels, activation, affine, affine_first)
+
     def _direct_conv(self, inputs, operand, qb, max_lines=None):
         """The layer as a direct int8 convolution: per run of whole images (by lines) the pixel operand of the inputs, convolved
         with ``operand``, plus ``qb``, into its rows of the one result.  Where ``operand`` is a tensor (the fake-quantised OIHW
@@ -1132,7 +1176,14 @@ class _ConvBase(_HostLayer):
         the result the fp32 view ``_direct_conv`` returns, or (``out_pixels``) the next conv's ops.I8Pixels from the product's own
         epilogue (ops.i8_conv2d_quantize).  The batch is cut into runs of whole images by lines, as ``_direct_conv`` cuts it; a
         ``residual`` (an ops.I8Pixels of the result's shape) is cut by the same images.  ``wide`` and ``pool``:
-        ops.i8_conv2d_quantize's (a pool works inside an image, so the cut does not change it)."""
+        ops.i8_conv2d_quantize's (a pool works inside an image, so the cut does not change it).  Where ``operand`` is an
+        ops.I8StemKernel the step is the stem convolution: ``x`` a tensor, quantised per image row (ops.i8_rows_quantize), the
+        product ops.i8_stem_conv2d or its epilogue, which takes no residual, wide row or pool."""
+        stem = isinstance(operand, ops.I8StemKernel)
+        if stem and (isinstance(x, ops.I8Pixels) or residual is not None or wide or pool is not None):
+            raise ValueError(f"{self.name}: the stem convolution quantises a tensor itself and its epilogue takes no residual, wide "
+                             "row or pool")
+
         def images_of(px):        # a cut: the codes of whole images stay on the 16-byte grid (CP % 32 == 0); the scales may not
             def cut(b0, b1):
                 scales = px.scales[b0:b1]
@@ -1146,7 +1197,7 @@ class _ConvBase(_HostLayer):
                 raise ValueError(f"{self.name}: the input must have four axes, got shape {tuple(x.shape)}")
             xt = x.permute(0, 3, 1, 2) if self.data_format == "NHWC" else x
             B, C, H, W = xt.shape
-            run = lambda b0, b1: ops.i8_pixels_quantize(xt[b0:b1])                                      # noqa: E731
+            run = lambda b0, b1: (ops.i8_rows_quantize if stem else ops.i8_pixels_quantize)(xt[b0:b1])  # noqa: E731
         padding = self._mx_padding(H, W)
         M, _, OH, OW = ops.mx_im2col_dims((B, C, H, W), self.kernel_size, self.strides, padding)
         per = OH * OW
@@ -1158,14 +1209,18 @@ class _ConvBase(_HostLayer):
                 raise ValueError(f"{self.name}: the residual must be an ops.I8Pixels of the result's shape {(B, self.filters, OH, OW)}, got "
                                  f"{tuple(residual.shape) if isinstance(residual, ops.I8Pixels) else type(residual).__name__}")
             res = images_of(residual) if residual is not None else (lambda b0, b1: None)
-            outs = [ops.i8_conv2d_quantize(run(b0, b1), operand, qb, self.strides, padding, activation, affine, affine_first, res(b0, b1),
-                                           wide, pool) for b0, b1 in runs]
+            if stem:
+                outs = [ops.i8_stem_conv2d_quantize(run(b0, b1), operand, qb, self.strides, padding, activation, affine, affine_first)
+                        for b0, b1 in runs]
+            else:
+                outs = [ops.i8_conv2d_quantize(run(b0, b1), operand, qb, self.strides, padding, activation, affine, affine_first,
+                                               res(b0, b1), wide, pool) for b0, b1 in runs]
             if len(outs) == 1:
                 return outs[0]
             return ops.I8Pixels(torch.cat([o.codes for o in outs]), torch.cat([o.scales for o in outs]), (B, *outs[0].shape[1:]))
         y = torch.empty((M, self.filters), dtype=torch.float32, device=operand.codes.device)
         for b0, b1 in runs:
-            ops.i8_conv2d(run(b0, b1), operand, qb, self.strides, padding, out=y[b0 * per:b1 * per])
+            (ops.i8_stem_conv2d if stem else ops.i8_conv2d)(run(b0, b1), operand, qb, self.strides, padding, out=y[b0 * per:b1 * per])
         y = y.view(B, OH, OW, self.filters)
         return y if self.data_format == "NHWC" else y.permute(0, 3, 1, 2)
 
@@ -1377,6 +1432,23 @@ def _takes_direct(layer: nn.Module) -> bool:
     return i8_direct_eligible(layer) and layer.kernel.shape[2] % 32 == 0
 
 
+def i8_stem_eligible(layer: nn.Module) -> bool:
+    """Whether ``layer`` can run as a stem convolution (``call_i8_stem``): it passes ``i8_direct_eligible``, reads at most 4 input
+    channels and has a kernel of at most 16 x 8."""
+    if not isinstance(layer, _ConvBase):
+        return False
+    try:
+        layer._check_i8_stem()
+    except ValueError:
+        return False
+    return True
+
+
+def _takes_stem(layer: nn.Module) -> bool:
+    """What ``i8_hardware(stem_convs=True)`` sends down the stem path: a stem-eligible conv that ``_takes_direct`` rejects."""
+    return i8_stem_eligible(layer) and not _takes_direct(layer)
+
+
 class i8_hardware(_matrix_hardware):
     """Context manager beside ``mx_hardware``: inside it every eligible Dense layer of ``model`` (``i8_hardware_eligible``) computes
     its eval-mode ``call`` as ``call_i8`` does -- activations quantised per row and ``act_block`` inputs to symmetric 8-bit
@@ -1437,12 +1509,27 @@ class i8_hardware(_matrix_hardware):
     first conv to its last from pixel operand to pixel operand, and ``fused_conv_layers`` lists five layers for it.  The pool is
     exact, but the BatchNorm before it is now ``bn_affine``'s ``(g, h)`` in the epilogue where ``fused_convs`` alone runs torch's
     kernel on the fp32 result, so the outputs differ from ``fused_convs`` alone by those roundings (an ulp can move a code); bit
-    for bit they are ``call_i8_direct`` -> relu -> ``.mul(g)`` -> ``.add(h)`` -> ``F.max_pool2d`` written out.  Without it (the default) ``i8_pooled_chain`` is not read and nothing changes."""
+    for bit they are ``call_i8_direct`` -> relu -> ``.mul(g)`` -> ``.add(h)`` -> ``F.max_pool2d`` written out.  Without it (the default) ``i8_pooled_chain`` is not read and nothing changes.
+    ``stem_convs=True`` (with ``convs=True, direct=True``): a conv that can run as a stem convolution (``i8_stem_eligible``: at most
+    4 input channels, a kernel of at most 16 x 8) and that ``direct`` leaves on the im2col path -- the first conv of every model
+    here -- computes what its ``call_i8_stem`` does instead: its input quantised once per image ROW (ops.i8_rows_quantize), a kernel
+    row per step of the matrix instruction (ops.i8_stem_conv2d), no im2col matrix and no padded channels.  It is listed in
+    ``stem_layers`` as well as in ``layers``.  With ``fused_convs`` / ``pooled_convs`` a stated chain that BEGINS with such a conv
+    (of at most 128 filters) runs it through the stem entry and its pixel-operand epilogue (``i8_conv_chain(..., stem=True)``):
+    models.CIFARCNN then runs conv 1 to conv 6 with no padded-channel product.  The ResNets' stems write fp32 (their 3 x 3 / 2
+    max-pool is torch's).  The activation scale is per row there, so the outputs differ from ``stem_convs=False``; refused with
+    ``emulate``.  Without it (the default) nothing changes."""
 
     _family, _dense_eligible = _I8, staticmethod(i8_hardware_eligible)
 
     def __init__(self, model: nn.Module, act_block=0, emulate=False, convs=False, fused=False, offsets=False, direct=False,
-                 int4=False, fused_convs=False, wide_convs=False, pooled_convs=False):
+                 int4=False, fused_convs=False, wide_convs=False, pooled_convs=False, stem_convs=False):
+        self.stem_convs, self.stem_layers, self._stem_modules = bool(stem_convs), [], []
+        if self.stem_convs and not (convs and direct):
+            raise ValueError("i8_hardware: stem_convs=True needs convs=True and direct=True: it takes the first conv off the im2col "
+                             "path that direct=True leaves it on")
+        if self.stem_convs and emulate:
+            raise ValueError("i8_hardware: emulate=True with stem_convs=True: the emulated path has no row-scaled operand")
         self.direct, self.direct_layers = bool(direct), []
         self.fused_convs, self.fused_conv_layers, self._fused_conv_modules = bool(fused_convs), [], []
         self.wide_convs = bool(wide_convs)
@@ -1474,26 +1561,31 @@ class i8_hardware(_matrix_hardware):
 
     def _conv_eligible(self, layer, **opt_in):
         """The convs of the im2col path: with ``direct`` those that the direct path does not take."""
-        return i8_conv_eligible(layer, **opt_in) and not (self.direct and _takes_direct(layer))
+        return i8_conv_eligible(layer, **opt_in) and not (self.direct and _takes_direct(layer)) \
+            and not (self.stem_convs and _takes_stem(layer))
 
     def _operand_kwargs(self, layer):
         return {**self._opt_in, "int4": True} if self.int4 and i8_int4_eligible(layer, **self._opt_in) else self._opt_in
 
     def __enter__(self):
         direct = [m for m in custom_layers_of(self.model) if _takes_direct(m)] if self.direct and self.convs else []
+        stem = [m for m in custom_layers_of(self.model) if _takes_stem(m)] if self.stem_convs else []
         self.int4_layers = []
         with torch.no_grad():     # every operand before any layer switches: an exception here leaves the model as it was
             parked = [(m.nested_q_k_layer(m.kernel).detach().permute(3, 2, 0, 1) if self.emulate else m.i8_direct_operand(),
                        m.nested_q_b_layer(m.b).detach() if m._has_bias else None) for m in direct]
+            parked_stem = [(m.i8_stem_operand(), m.nested_q_b_layer(m.b).detach() if m._has_bias else None) for m in stem]
         super().__enter__()
         self.int4_layers = [m for m in self.layers if isinstance(getattr(m, _I8.hw)[0], ops.I4Operand)]
         for m, hw in zip(direct, parked):
             m._i8_direct_hw = hw
-        self.direct_layers = direct
-        if direct:                # ``layers``: the Dense layers, then the conv layers of either path in module order
+        for m, hw in zip(stem, parked_stem):
+            m._i8_stem_hw = hw
+        self.direct_layers, self.stem_layers = direct, stem
+        if direct or stem:        # ``layers``: the Dense layers, then the conv layers of every path in module order
             order = {id(m): k for k, m in enumerate(custom_layers_of(self.model))}
             dense = [m for m in self.layers if isinstance(m, CustomDenseLayer)]
-            convs = [m for m in self.layers if not isinstance(m, CustomDenseLayer)] + direct
+            convs = [m for m in self.layers if not isinstance(m, CustomDenseLayer)] + direct + stem
             self.layers = dense + sorted(convs, key=lambda m: order[id(m)])
         if self.fused_convs:
             self._enter_fused_convs()
@@ -1529,11 +1621,21 @@ class i8_hardware(_matrix_hardware):
                     continue
                 if any(chain is not None for chain in parked):
                     for chain in filter(None, parked):
-                        for c, _, _, _ in chain:
-                            c._i8_chain_hw = c._i8_direct_hw or (c.i8_direct_operand(), c.nested_q_b_layer(c.b).detach() if c._has_bias else None)
+                        for k, (c, _, _, _) in enumerate(chain):
+                            c._i8_chain_hw = self._chain_hw(mod, c, k == 0)
                         self.fused_conv_layers += [c for c, _, _, _ in (chain if every else chain[:-1])]
                     mod._i8_fused_convs = parked
                     self._fused_conv_modules.append(mod)
+
+    def _chain_hw(self, mod, c, first):
+        """(operand, bias) of a conv of a parked chain: what ``direct`` parked on it, or packed here.  The FIRST conv of a chain
+        keeps the stem operand ``stem_convs`` parked on it where the stem epilogue takes its filters; ``mod`` is then marked
+        (``_i8_stem_chain``) so that its forward asks ``i8_conv_chain`` for ``stem=True``."""
+        if first and c._i8_stem_hw is not None and c.filters <= ops.I8_STEM_QUANT_MAX_FILTERS:
+            mod._i8_stem_chain = True
+            self._stem_modules.append(mod)
+            return c._i8_stem_hw
+        return c._i8_direct_hw or (c.i8_direct_operand(), c.nested_q_b_layer(c.b).detach() if c._has_bias else None)
 
     def _enter_pooled_convs(self, mod):
         """A module that states ``i8_pooled_chain()`` -- (chain, pools) -- whose layers all pass ``i8_direct_eligible`` gets the
@@ -1545,8 +1647,8 @@ class i8_hardware(_matrix_hardware):
         if not (all(i8_direct_eligible(c) and act in ops.MX_ACTIVATIONS for c, act, _, _ in chain)
                 and all(c.filters <= ops.I8_CONV_QUANT_MAX_FILTERS for c, _, _, _ in chain[:-1])):
             return False
-        for c, _, _, _ in chain:
-            c._i8_chain_hw = c._i8_direct_hw or (c.i8_direct_operand(), c.nested_q_b_layer(c.b).detach() if c._has_bias else None)
+        for k, (c, _, _, _) in enumerate(chain):
+            c._i8_chain_hw = self._chain_hw(mod, c, k == 0)
         self.fused_conv_layers += [c for c, _, _, _ in chain[:-1]]
         mod._i8_pooled_convs = ([(c, act, bn_affine(aff) if isinstance(aff, nn.BatchNorm2d) else aff, first)
                                  for c, act, aff, first in chain], list(pools))
@@ -1567,6 +1669,11 @@ class i8_hardware(_matrix_hardware):
         self._fused_conv_modules = []
         for m in self.direct_layers:
             m._i8_direct_hw = None
+        for m in self.stem_layers:
+            m._i8_stem_hw = None
+        for mod in self._stem_modules:
+            mod._i8_stem_chain = False
+        self._stem_modules = []
         return super().__exit__(*exc)
 
 
@@ -1655,7 +1762,7 @@ def bn_affine(bn: nn.BatchNorm2d):
         return g.float(), (beta - bn.running_mean.double() * g).float()
 
 
-def i8_conv_chain(x, chain, max_lines=None, out_pixels=False, wide=False, pools=None):
+def i8_conv_chain(x, chain, max_lines=None, out_pixels=False, wide=False, pools=None, stem=False):
     """``chain`` = [(conv, activation, affine, affine_first), ...]: conv layers applied one after the other as direct int8
     convolutions, under ``no_grad``.  ``x`` is quantised once per pixel; every layer but the last goes through
     ops.i8_conv2d_quantize, whose epilogue applies ``activation`` (None or "relu") and ``affine`` (None or ``(g, h)``, ``bn_affine``)
@@ -1676,12 +1783,32 @@ def i8_conv_chain(x, chain, max_lines=None, out_pixels=False, wide=False, pools=
     ``pools``: a sequence with one entry per step, None or 2.  A step with 2 takes the non-overlapping 2 x 2 maximum after its
     activation and affine, in the same epilogue (ops.i8_conv2d_quantize, ``pool``), and writes the pixel operand of the pooled
     image: conv -> relu -> BN -> MaxPool(2) -> conv without an fp32 activation.  It is refused on a step that writes fp32, has
-    a residual or has more than 512 filters.  So models.CIFARCNN's six convs are one chain (``i8_pooled_chain()``)."""
+    a residual or has more than 512 filters.  So models.CIFARCNN's six convs are one chain (``i8_pooled_chain()``).
+    ``stem=True``: the FIRST conv runs as a stem convolution (``call_i8_stem``): ``x``, a tensor of at most 4 channels, is quantised
+    per image row and multiplied a kernel row per step, with no padded channels; where the step has an epilogue it is
+    ops.i8_stem_conv2d_quantize's (at most 128 filters, no residual, no pool).  The rest of the chain is unchanged.  Bit for bit
+    ``call_i8_stem`` -> relu -> ``.mul(g)`` -> ``.add(h)`` -> ``call_i8_direct`` ....  ValueError naming the reason for a first
+    conv that cannot take it (``i8_stem_eligible``).  Without it (the default) nothing changes."""
     fn = "i8_conv_chain"
     chain = [tuple(step) for step in chain]
     _check_max_lines(max_lines)
     if not chain:
         raise ValueError(f"{fn}: the chain is empty")
+    if stem:
+        first = chain[0][0]
+        if not isinstance(x, torch.Tensor):
+            raise ValueError(f"{fn}: stem=True: the stem convolution quantises a tensor itself, got {type(x).__name__}")
+        try:
+            if isinstance(first, _ConvBase):
+                first._check_i8_stem()
+        except ValueError as e:
+            raise ValueError(f"{fn}: stem=True: {first.name}: {e}") from None
+        epilogue = out_pixels or len(chain) > 1
+        if epilogue and getattr(first, "filters", 0) > ops.I8_STEM_QUANT_MAX_FILTERS:
+            raise ValueError(f"{fn}: stem=True: {first.name}: {first.filters} filters: the stem epilogue holds a whole output row in one "
+                             f"wave, at most {ops.I8_STEM_QUANT_MAX_FILTERS}")
+        if (pools is not None and list(pools)[:1] not in ([], [None])) or (len(chain[0]) == 5 and chain[0][4] is not None):
+            raise ValueError(f"{fn}: stem=True: the stem epilogue takes no pool and no residual")
     pools = [None] * len(chain) if pools is None else list(pools)
     if len(pools) != len(chain):
         raise ValueError(f"{fn}: pools has {len(pools)} entries for {len(chain)} steps: one per step, None or 2")
@@ -1732,8 +1859,11 @@ def i8_conv_chain(x, chain, max_lines=None, out_pixels=False, wide=False, pools=
             layer, activation, affine, affine_first = step[:4]
             hw = layer._i8_chain_hw
             operand, qb = hw if hw is not None else (layer.i8_direct_operand(), layer.nested_q_b_layer(layer.b) if layer._has_bias else None)
+            by_row = stem and k == 0
+            if by_row != isinstance(operand, ops.I8StemKernel):       # the parked operand is the other path's: pack this path's here
+                operand = layer.i8_stem_operand() if by_row else layer.i8_direct_operand()
             a = layer._direct_step(a, operand, qb, max_lines, out_pixels or k < len(chain) - 1, activation, affine, affine_first,
-                                   step[4] if len(step) == 5 else None, wide and pools[k] is None, pools[k])
+                                   step[4] if len(step) == 5 else None, wide and pools[k] is None and not by_row, pools[k])
         return a
 
 

@@ -142,12 +142,13 @@ class CIFARCNN(nn.Module):
 
     def forward(self, x):
         pooled = None if self.training else getattr(self, "_i8_pooled_convs", None)      # layers.i8_hardware(..., pooled_convs=True)
+        stem = bool(getattr(self, "_i8_stem_chain", False))        # layers.i8_hardware(..., stem_convs=True): conv 1 by image rows
         if pooled is not None:                                     # all six convs as one chain; in eval mode a dropout is the identity
-            x = F.max_pool2d(self.bns[5](F.relu(i8_conv_chain(x, pooled[0], pools=pooled[1]))), 2)
+            x = F.max_pool2d(self.bns[5](F.relu(i8_conv_chain(x, pooled[0], pools=pooled[1], stem=stem))), 2)
         fused = getattr(self, "_i8_fused_convs", None)             # inside layers.i8_hardware(..., fused_convs=True)
         for blk in range(3) if pooled is None else ():
             if fused is not None and fused[blk] is not None and not self.training:
-                x = self.bns[2 * blk + 1](F.relu(i8_conv_chain(x, fused[blk])))
+                x = self.bns[2 * blk + 1](F.relu(i8_conv_chain(x, fused[blk], stem=stem and blk == 0)))
             else:
                 for j in range(2):
                     k = 2 * blk + j

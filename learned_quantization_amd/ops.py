@@ -1271,6 +1271,11 @@ def i8_conv_kernel_pack(kernel: torch.Tensor, scale: torch.Tensor, qmin: int, qm
     """The operand of a conv kernel ``(co, ci, kh, kw)`` (OIHW; a non-contiguous tensor is copied) under ``scale``, one per filter
     (``co`` elements, or one element for all filters): the clamped integers of ``i8_operand_pack`` for the same elements, per tap in
     the fragment order the product reads (include/lq_hip.h, lq_i8_conv_kernel_pack).  One launch."""
+    return _conv_kernel_pack("lq_i8_conv_kernel_pack", i8_conv_kernel_bytes, I8ConvKernel, kernel, scale, qmin, qmax, rounding)
+
+
+def _conv_kernel_pack(name, bytes_of, kind, kernel, scale, qmin, qmax, rounding):
+    """The body of ``i8_conv_kernel_pack`` and ``i8_stem_kernel_pack``: one argument check, one launch of the C entry ``name``."""
     qmin, qmax = check_q_range(qmin, qmax)
     if qmin < I8_RANGE[0] or qmax > I8_RANGE[1]:
         raise ValueError(f"range ({qmin}, {qmax}) is not inside [{I8_RANGE[0]}, {I8_RANGE[1]}], the signed bytes the int8 matrix "
@@ -1285,12 +1290,12 @@ def i8_conv_kernel_pack(kernel: torch.Tensor, scale: torch.Tensor, qmin: int, qm
         raise ValueError(f"scale must hold one element or one per filter ({co}), got shape {tuple(scale.shape)}")
     s = s.expand(co).contiguous()
     lib = _hip.load()
-    cb, sb = i8_conv_kernel_bytes(co, ci, kh, kw)
+    cb, sb = bytes_of(co, ci, kh, kw)
     codes = torch.empty(cb, dtype=torch.uint8, device=p.device)
     scales = torch.empty(sb // 4, dtype=torch.float32, device=p.device)
-    _hip.check(lib.lq_i8_conv_kernel_pack(_hip.ptr(p), _hip.ptr(s), qmin, qmax, rnd, co, ci, kh, kw, _hip.ptr(codes), _hip.ptr(scales),
-                                          _hip.stream_ptr(p.device)), "lq_i8_conv_kernel_pack")
-    return I8ConvKernel(codes, scales, co, ci, (kh, kw))
+    _hip.check(getattr(lib, name)(_hip.ptr(p), _hip.ptr(s), qmin, qmax, rnd, co, ci, kh, kw, _hip.ptr(codes), _hip.ptr(scales),
+                                  _hip.stream_ptr(p.device)), name)
+    return kind(codes, scales, co, ci, (kh, kw))
 
 
 def _check_i8_conv_operands(pixels: I8Pixels, kernel: I8ConvKernel):
@@ -1328,6 +1333,19 @@ def _check_i8_residual(residual: I8Pixels, shape, codes_shape, dev):
             raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {want} for an output {tuple(shape)}")
         if not t.is_cuda or t.device != dev:
             raise RuntimeError(f"{name} is on {t.device}: the residual must be on the operands' HIP device; there is no CPU fallback")
+
+
+def _epilogue_affine(affine, co: int):
+    """``[g, h]`` of a pixel-operand epilogue's ``affine`` -- float32 ``(co,)`` each on the device -- or ``[None, None]``."""
+    g_, h_ = (None, None) if affine is None else affine
+    post = []
+    for name, t in (("affine[0]", g_), ("affine[1]", h_)):
+        if affine is not None:
+            t = _hip.require_device_f32(t, name)
+            if tuple(t.shape) != (co,):
+                raise ValueError(f"{name} must have shape ({co},), got {tuple(t.shape)}")
+        post.append(t)
+    return post
 
 
 def i8_conv2d(pixels: I8Pixels, kernel: I8ConvKernel, bias: Optional[torch.Tensor] = None, strides=(1, 1), padding=(0, 0, 0, 0),
@@ -1379,15 +1397,8 @@ def i8_conv2d_quantize(pixels: I8Pixels, kernel: I8ConvKernel, bias: Optional[to
     act = check_mx_activation(activation)
     dev = _check_i8_conv_operands(pixels, kernel)
     co = kernel.filters
-    g_, h_ = (None, None) if affine is None else affine
     bias = _matrix_output(0, co, dev, bias, fp32_out=False)[0]
-    post = []
-    for name, t in (("affine[0]", g_), ("affine[1]", h_)):
-        if affine is not None:
-            t = _hip.require_device_f32(t, name)
-            if tuple(t.shape) != (co,):
-                raise ValueError(f"{name} must have shape ({co},), got {tuple(t.shape)}")
-        post.append(t)
+    post = _epilogue_affine(affine, co)
     lib = _hip.load()
     g = _conv_geom(pixels.shape, (0, 0, 0, 0), kernel.kernel_size, strides, padding)
     _, _, OH, OW = _geom_dims(lib, g)
@@ -1408,6 +1419,142 @@ def i8_conv2d_quantize(pixels: I8Pixels, kernel: I8ConvKernel, bias: Optional[to
     _hip.check(getattr(lib, name)(_hip.ptr(pixels.codes), _hip.ptr(pixels.scales), _hip.ptr(kernel.codes), _hip.ptr(kernel.scales),
                                   _hip.ptr(bias), ctypes.byref(g), co, _hip.ptr(post[0]), _hip.ptr(post[1]), act,
                                   int(bool(affine_first)), *res, _hip.ptr(codes), _hip.ptr(scales), _hip.stream_ptr(dev)), name)
+    return I8Pixels(codes, scales, (B, co, OH, OW))
+
+
+# --------------------------------------------------------------------------- the direct int8 convolution of a first layer (stem)
+I8_STEM_MAX_CHANNELS = 4             # a pixel of the row operand is one dword (include/lq_hip.h)
+I8_STEM_MAX_KERNEL = (16, 8)         # (kh, kw): a kernel row is one step of the instruction; 8 column tiles of kh rows fit the LDS
+I8_STEM_QUANT_MAX_FILTERS = 128      # lq_i8_stem_conv2d_quantize: a whole output row in one wave
+
+
+class I8Rows(NamedTuple):
+    """An input ``(B, C, H, W)`` of at most 4 channels quantised once per image ROW (``i8_rows_quantize``; include/lq_hip.h, "stem"):
+    ``codes`` uint8 ``(B, H, W, 4)``, channel c in byte c and code 0 past C; ``scales`` float32 ``(B, H)``; ``shape`` the input's
+    logical ``(B, C, H, W)``."""
+    codes: torch.Tensor
+    scales: torch.Tensor
+    shape: Tuple[int, int, int, int]
+
+
+class I8StemKernel(NamedTuple):
+    """A conv kernel ``(co, ci, kh, kw)`` with ``ci <= 4`` and ``kw <= 8`` under one scale per filter, packed per kernel ROW in
+    fragment order (``i8_stem_kernel_pack``): ``codes`` (uint8) and ``scales`` (float32, ``16 ceil(co / 16)``) are opaque buffers of
+    lq_i8_stem_kernel_bytes' sizes."""
+    codes: torch.Tensor
+    scales: torch.Tensor
+    filters: int
+    channels: int
+    kernel_size: Tuple[int, int]
+
+
+def check_i8_stem_shape(channels: int, kernel_size) -> None:
+    """ValueError naming the reason for a conv that the stem product does not take: more than 4 input channels, a kernel wider than
+    8 or higher than 16."""
+    kh, kw = kernel_size
+    if channels > I8_STEM_MAX_CHANNELS:
+        raise ValueError(f"{channels} input channels: the stem convolution takes at most {I8_STEM_MAX_CHANNELS} (a pixel of its row "
+                         "operand is one dword); a wider input takes the direct convolution (call_i8_direct)")
+    if kh > I8_STEM_MAX_KERNEL[0] or kw > I8_STEM_MAX_KERNEL[1]:
+        raise ValueError(f"kernel_size ({kh}, {kw}): the stem convolution takes at most {I8_STEM_MAX_KERNEL}: a kernel row of kw taps "
+                         "by 4 channel bytes is one 32-byte step of the matrix instruction")
+
+
+def i8_rows_bytes(B: int, C: int, H: int, W: int) -> Tuple[int, int]:
+    """(code_bytes, scale_bytes) of the row operand of an input ``(B, C, H, W)`` (lq_i8_rows_bytes).  Needs no device."""
+    return _byte_pair(_hip.load().lq_i8_rows_bytes, "lq_i8_rows_bytes", B, C, H, W)
+
+
+def i8_stem_kernel_bytes(co: int, ci: int, kh: int, kw: int) -> Tuple[int, int]:
+    """(code_bytes, scale_bytes) of a packed stem kernel (lq_i8_stem_kernel_bytes).  Needs no device."""
+    return _byte_pair(_hip.load().lq_i8_stem_kernel_bytes, "lq_i8_stem_kernel_bytes", co, ci, kh, kw)
+
+
+def i8_rows_quantize(x: torch.Tensor) -> I8Rows:
+    """The row operand of ``x (B, C, H, W)``, ``C <= 4``: per image row the absmax scale of its ``W C`` elements and the
+    nearest-rounded symmetric 8-bit codes under it -- ``i8_operand_quantize`` of ``x.permute(0, 2, 3, 1).reshape(B H, W C)`` -- as an
+    int8 NHWC4 copy (include/lq_hip.h, lq_i8_rows_quantize).  ``x`` is read through its own strides: no copy.  One launch."""
+    import ctypes
+    _require_conv_input(x)
+    lib = _hip.load()
+    B, C, H, W = (int(d) for d in x.shape)
+    i8_rows_bytes(B, C, H, W)                          # the extents' refusals, before any allocation
+    g = _hip.ConvGeom(B, C, H, W, *(int(e) for e in x.stride()), 1, 1, 1, 1, 0, 0, 0, 0)
+    codes = torch.empty((B, H, W, 4), dtype=torch.uint8, device=x.device)
+    scales = torch.empty((B, H), dtype=torch.float32, device=x.device)
+    _hip.check(lib.lq_i8_rows_quantize(_hip.ptr(x), ctypes.byref(g), _hip.ptr(codes), _hip.ptr(scales), _hip.stream_ptr(x.device)),
+               "lq_i8_rows_quantize")
+    return I8Rows(codes, scales, (B, C, H, W))
+
+
+def i8_stem_kernel_pack(kernel: torch.Tensor, scale: torch.Tensor, qmin: int, qmax: int, rounding: str = "floor") -> I8StemKernel:
+    """The operand of a first-layer kernel ``(co, ci, kh, kw)`` (OIHW, ``ci <= 4``, ``kw <= 8``, ``kh <= 16``) under ``scale``, one per
+    filter: ``i8_conv_kernel_pack``'s codes for the same elements, a kernel row per 32-byte step in the fragment order the stem
+    product reads (include/lq_hip.h, lq_i8_stem_kernel_pack).  One launch."""
+    return _conv_kernel_pack("lq_i8_stem_kernel_pack", i8_stem_kernel_bytes, I8StemKernel, kernel, scale, qmin, qmax, rounding)
+
+
+def _check_i8_stem_operands(rows: I8Rows, kernel: I8StemKernel):
+    """The buffer checks of ``i8_stem_conv2d`` and ``i8_stem_conv2d_quantize`` (``_check_i8_conv_operands``' rules); the device."""
+    if not isinstance(rows, I8Rows) or not isinstance(kernel, I8StemKernel):
+        raise ValueError(f"the stem product takes an I8Rows and an I8StemKernel, got {type(rows).__name__} and {type(kernel).__name__}")
+    B, C, H, W = (int(d) for d in rows.shape)
+    if C != kernel.channels:
+        raise ValueError(f"the input has {C} channels and the kernel {kernel.channels}")
+    dev = rows.codes.device
+    rcb, rsb = i8_rows_bytes(B, C, H, W)
+    kcb, ksb = i8_stem_kernel_bytes(kernel.filters, kernel.channels, *kernel.kernel_size)
+    for name, t, dtype, numel in (("rows.codes", rows.codes, torch.uint8, rcb), ("rows.scales", rows.scales, torch.float32, rsb // 4),
+                                  ("kernel.codes", kernel.codes, torch.uint8, kcb), ("kernel.scales", kernel.scales, torch.float32, ksb // 4)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.numel() != numel or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dtype} tensor of {numel} elements for an input {(B, C, H, W)} and a kernel "
+                             f"({kernel.filters}, {kernel.channels}, {kernel.kernel_size[0]}, {kernel.kernel_size[1]})")
+        if not t.is_cuda or t.device != dev or (dev.index is not None and dev.index != torch.cuda.current_device()):
+            raise RuntimeError(f"{name} is on {t.device}: both operands must be on the current HIP device; there is no CPU fallback")
+    return dev
+
+
+def i8_stem_conv2d(rows: I8Rows, kernel: I8StemKernel, bias: Optional[torch.Tensor] = None, strides=(1, 1), padding=(0, 0, 0, 0),
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The convolution of a row operand with a packed stem kernel on the int8 matrix instruction, ``Y (B OH OW, co)`` in fp32 -- NHWC
+    once reshaped -- bit for bit the definition of include/lq_hip.h, lq_i8_stem_conv2d: per kernel ROW an exact int32 sum over its
+    taps and channels under that image row's scale, the filter's scale after the last row, then the bias.  ``padding`` is (top,
+    bottom, left, right).  ``out``: a float32 matrix to write into; its row stride is the leading dimension.  One launch."""
+    import ctypes
+    dev = _check_i8_stem_operands(rows, kernel)
+    lib = _hip.load()
+    g = _conv_geom(rows.shape, (0, 0, 0, 0), kernel.kernel_size, strides, padding)
+    M = _geom_dims(lib, g)[0]
+    bias, out, ldy = _matrix_output(M, kernel.filters, dev, bias, out)
+    _hip.check(lib.lq_i8_stem_conv2d(_hip.ptr(rows.codes), _hip.ptr(rows.scales), _hip.ptr(kernel.codes), _hip.ptr(kernel.scales),
+                                     _hip.ptr(bias), _hip.ptr(out), ldy, ctypes.byref(g), kernel.filters, _hip.stream_ptr(out.device)),
+               "lq_i8_stem_conv2d")
+    return out
+
+
+def i8_stem_conv2d_quantize(rows: I8Rows, kernel: I8StemKernel, bias: Optional[torch.Tensor] = None, strides=(1, 1),
+                            padding=(0, 0, 0, 0), activation=None, affine=None, affine_first: bool = False) -> I8Pixels:
+    """The pixel operand of the NEXT conv, written by the stem product's own epilogue (include/lq_hip.h,
+    lq_i8_stem_conv2d_quantize): byte for byte ``i8_pixels_quantize`` of ``v`` seen as ``(B, co, OH, OW)``, with ``v`` made from
+    ``i8_stem_conv2d``'s ``Y`` by ``activation``, ``affine = (g, h)`` and ``affine_first`` exactly as ``i8_conv2d_quantize`` makes it
+    from ``i8_conv2d``'s.  One launch; no fp32 matrix.  ``co`` above 128 is refused."""
+    import ctypes
+    act = check_mx_activation(activation)
+    dev = _check_i8_stem_operands(rows, kernel)
+    co = kernel.filters
+    bias = _matrix_output(0, co, dev, bias, fp32_out=False)[0]
+    post = _epilogue_affine(affine, co)
+    lib = _hip.load()
+    g = _conv_geom(rows.shape, (0, 0, 0, 0), kernel.kernel_size, strides, padding)
+    _, _, OH, OW = _geom_dims(lib, g)
+    B = int(rows.shape[0])
+    cb, _ = i8_pixels_bytes(B, co, OH, OW)
+    codes = torch.empty((B, OH, OW, cb // (B * OH * OW)), dtype=torch.uint8, device=dev)
+    scales = torch.empty((B, OH, OW), dtype=torch.float32, device=dev)
+    _hip.check(lib.lq_i8_stem_conv2d_quantize(_hip.ptr(rows.codes), _hip.ptr(rows.scales), _hip.ptr(kernel.codes), _hip.ptr(kernel.scales),
+                                              _hip.ptr(bias), ctypes.byref(g), co, _hip.ptr(post[0]), _hip.ptr(post[1]), act,
+                                              int(bool(affine_first)), _hip.ptr(codes), _hip.ptr(scales), _hip.stream_ptr(dev)),
+               "lq_i8_stem_conv2d_quantize")
     return I8Pixels(codes, scales, (B, co, OH, OW))
 
 

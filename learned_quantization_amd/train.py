@@ -655,6 +655,11 @@ def build_parser():
                          "pooled_convs=True) (a model that states i8_pooled_chain(), as the CIFAR CNN does, takes its MaxPool(2) in the "
                          "conv's epilogue: all six convs one chain) and add i8_eval_pooled_conv_layers, _accuracy and "
                          "_max_logit_diff (from --i8-eval-fused-convs alone) to the result")
+    ap.add_argument("--i8-eval-stem-convs", action="store_true",
+                    help="with --i8-eval-convs --i8-eval-direct: evaluate once more under layers.i8_hardware(..., stem_convs=True) (the "
+                         "first conv, of at most 4 input channels, quantised per image row and multiplied a kernel row per step of the "
+                         "matrix instruction instead of through im2col) and add i8_eval_stem_conv_layers, _accuracy and "
+                         "_max_logit_diff (from the same call without it) to the result")
     ap.add_argument("--i8-eval-fused", action="store_true",
                     help="with --i8-eval --i8-eval-act-block 64: evaluate once more under layers.i8_hardware(fused=True) (the Dense "
                          "tail through layers.i8_dense_chain: relu and the next operand's quantisation, per row and block of 64, in "
@@ -674,7 +679,7 @@ def build_parser():
 
 @torch.no_grad()
 def i8_eval(model, x, y, act_block=0, convs=False, fused=False, offsets=False, direct=False, int4=False, fused_convs=False,
-            wide_convs=False, pooled_convs=False):
+            wide_convs=False, pooled_convs=False, stem_convs=False):
     """One evaluation of ``model`` on (x, y) under layers.i8_hardware, one under its ``emulate=True`` yardstick and one of the
     fake-quantised model as it stands: a dict of the three accuracies and the largest |difference| of the outputs of the last Dense
     layer that took the path (the logits of the MNIST model) between the hardware path and each of the other two.  ValueError for
@@ -695,7 +700,10 @@ def i8_eval(model, x, y, act_block=0, convs=False, fused=False, offsets=False, d
     (the bottleneck blocks of models.ResNet50Like) fuse too.  ``pooled_convs=True`` (with ``fused_convs``) adds an evaluation under
     ``i8_hardware(..., fused_convs=True, pooled_convs=True)``: the convs with an epilogue (five of models.CIFARCNN's six), the
     accuracy, and the largest |difference| of the model's outputs from ``fused_convs`` alone (reported: the pool is exact, the
-    BatchNorm before it is ``bn_affine``'s in the epilogue instead of torch's kernel)."""
+    BatchNorm before it is ``bn_affine``'s in the epilogue instead of torch's kernel).  ``stem_convs=True`` (with ``convs`` and
+    ``direct``) adds an evaluation under ``i8_hardware(..., stem_convs=True)`` beside the conv flags as given: the convs on the stem
+    convolution (the first conv of each model here), the accuracy, and the largest |difference| of the model's outputs from the
+    same call without it (reported: the activation scale is per image row there)."""
     was_training = model.training
     model.eval()
     acc, logits = [], []
@@ -775,6 +783,19 @@ def i8_eval(model, x, y, act_block=0, convs=False, fused=False, offsets=False, d
                 n_pooled, p = len(hwp.fused_conv_layers), model(x)
             fields.update({"i8_eval_pooled_conv_layers": n_pooled, "i8_eval_pooled_conv_accuracy": float((p.argmax(1) == y).float().mean()),
                            "i8_eval_pooled_conv_max_logit_diff": float((p - outs[0]).abs().max())})
+        if convs and direct and stem_convs:
+            outs = []
+            for sc in (True, False):
+                with L.i8_hardware(model, probe.act_block, convs=True, offsets=offsets, direct=True, fused_convs=fused_convs,
+                                   wide_convs=wide_convs, pooled_convs=pooled_convs, stem_convs=sc) as hws:
+                    if sc and not hws.stem_layers:
+                        raise ValueError("i8_eval: stem_convs=True needs a first conv that can run as a stem convolution (at most 4 "
+                                         "input channels, a kernel of at most 16 x 8, one scale per filter, symmetric)")
+                    if sc:
+                        n_stem = len(hws.stem_layers)
+                    outs.append(model(x))
+            fields.update({"i8_eval_stem_conv_layers": n_stem, "i8_eval_stem_conv_accuracy": float((outs[0].argmax(1) == y).float().mean()),
+                           "i8_eval_stem_conv_max_logit_diff": float((outs[0] - outs[1]).abs().max())})
         if int4:
             outs = []
             for i4 in (True, False):
@@ -885,6 +906,9 @@ def main(argv=None):
         ap.error("--i8-eval-wide-convs needs --i8-eval-fused-convs: it widens the epilogue of the fused conv chains")
     if args.i8_eval_pooled_convs and not args.i8_eval_fused_convs:
         ap.error("--i8-eval-pooled-convs needs --i8-eval-fused-convs: it takes the max-pool between the fused conv chains into the epilogue")
+    if args.i8_eval_stem_convs and not (args.i8_eval_convs and args.i8_eval_direct):
+        ap.error("--i8-eval-stem-convs needs --i8-eval-convs --i8-eval-direct: it takes the first conv off the im2col path that the "
+                 "direct path leaves it on")
     if args.i8_eval_fused and not args.i8_eval:
         ap.error("--i8-eval-fused needs --i8-eval: it compares the fused Dense tail with the unfused hardware path")
     if args.i8_eval_fused and args.i8_eval_act_block != 64:
@@ -958,7 +982,7 @@ def main(argv=None):
     quant_stats = L.quant_stats(tr.model) if args.quant_stats and rank == 0 else None      # after the clock has stopped
     mx_stats = L.mx_quant_stats(tr.model) if args.mx_stats and rank == 0 else None
     mx_eval_fields = mx_eval(tr.model, *batches[0], act_format=args.mx_eval, fused=args.mx_eval_fused, convs=args.mx_eval_convs, fp6=args.mx_eval_fp6) if args.mx_eval is not None and rank == 0 else None
-    i8_eval_fields = i8_eval(tr.model, *batches[0], act_block=args.i8_eval_act_block, convs=args.i8_eval_convs, fused=args.i8_eval_fused, offsets=args.i8_eval_offsets, direct=args.i8_eval_direct, int4=args.i8_eval_int4, fused_convs=args.i8_eval_fused_convs, wide_convs=args.i8_eval_wide_convs, pooled_convs=args.i8_eval_pooled_convs) if args.i8_eval and rank == 0 else None
+    i8_eval_fields = i8_eval(tr.model, *batches[0], act_block=args.i8_eval_act_block, convs=args.i8_eval_convs, fused=args.i8_eval_fused, offsets=args.i8_eval_offsets, direct=args.i8_eval_direct, int4=args.i8_eval_int4, fused_convs=args.i8_eval_fused_convs, wide_convs=args.i8_eval_wide_convs, pooled_convs=args.i8_eval_pooled_convs, stem_convs=args.i8_eval_stem_convs) if args.i8_eval and rank == 0 else None
     if rank == 0:
         n_q = sum(p.numel() for l in tr.custom_layers for p in l._regularized())
         print(json.dumps({

@@ -873,7 +873,19 @@ int lq_i8_conv2d_quantize_pool(const void* pix_codes, const void* pix_scales, co
  * LQ_EALIGN before any launch, in the order of the twin entry: everything lq_i8_pixels_quantize, lq_i8_conv_kernel_pack,
  * lq_i8_conv2d and lq_i8_conv2d_quantize refuse (with 4 * B * H * W < 2^31 for the row codes), and C (ci) > 4, KW > 8, KH > 16
  * (the product stages up to 8 column tiles of 512 * KH bytes in 64 KB of LDS) and, for the epilogue, co > 128.
- * Not built: a max-pool, a residual or MX elements in this epilogue, group-wise or asymmetric weight scales, C > 4, KW > 8.  */
+ * POOLED EPILOGUE (lq_i8_stem_conv2d_quantize_pool).  lq_i8_stem_conv2d_quantize's arguments and, before out_codes, the four
+ * paddings (top, bottom, left, right), each 0 or 1, of a 3 x 3 maximum of stride 2 -- a ResNet's stem: conv, BatchNorm, relu,
+ * pad, MaxPool(3, 2).  PH = (OH + pool_top + pool_bottom - 3) / 2 + 1 and PW = (OW + pool_left + pool_right - 3) / 2 + 1, floored;
+ * pooled element (b, n, ph, pw) is the maximum of v over conv rows 2 ph - pool_top + {0, 1, 2} and conv columns 2 pw - pool_left +
+ * {0, 1, 2} inside the conv output (the padding is -inf and, with paddings <= 1, never alone in a window), with v the value
+ * lq_i8_stem_conv2d_quantize quantises, bit for bit.  The maximum is torch's max_pool2d: a NaN in a window makes that pooled
+ * element NaN, and no other; max(-0, +0) may be either zero (both give code 0 and the same scale).  out_codes / out_scales are,
+ * byte for byte, lq_i8_pixels_quantize of the pooled image seen as [B][co][PH][PW]: lq_i8_pixels_bytes(B, co, PH, PW), the padding
+ * of a ragged co included.  co <= 128.  LQ_EINVAL, after the refusals of lq_i8_stem_conv2d_quantize's extents and options and
+ * before its buffers': a padding outside {0, 1}; PH or PW below 1.  The unpooled extents are held to lq_i8_stem_conv2d_quantize's
+ * limits too (B * OH * OW * CPo < 2^31, B * OH * OW <= 65535 * 64), although that output is never written.
+ * Not built: a residual or MX elements in these epilogues, pools other than 3 x 3 / 2, an average pool, a pooled fp32 output, co
+ * above 128 with a pool, group-wise or asymmetric weight scales, C > 4, KW > 8.  */
 int lq_i8_rows_bytes(int64_t B, int64_t C, int64_t H, int64_t W, size_t* code_bytes, size_t* scale_bytes);
 int lq_i8_rows_quantize(const float* X, const lq_conv_geom* g, void* codes, void* scales, void* stream);
 int lq_i8_stem_kernel_bytes(int64_t co, int64_t ci, int64_t KH, int64_t KW, size_t* code_bytes, size_t* scale_bytes);
@@ -885,6 +897,12 @@ int lq_i8_stem_conv2d_quantize(const void* row_codes, const void* row_scales, co
                                const float* bias /* may be NULL */, const lq_conv_geom* g, int64_t co,
                                const float* post_scale /* [co]; both or neither NULL */, const float* post_shift,
                                int activation /* lq_mx_activation */, int affine_first, void* out_codes, void* out_scales, void* stream);
+int lq_i8_stem_conv2d_quantize_pool(const void* row_codes, const void* row_scales, const void* k_codes, const void* k_scales,
+                                    const float* bias /* may be NULL */, const lq_conv_geom* g, int64_t co,
+                                    const float* post_scale /* [co]; both or neither NULL */, const float* post_shift,
+                                    int activation /* lq_mx_activation */, int affine_first, int32_t pool_top /* 0 or 1 */,
+                                    int32_t pool_bottom, int32_t pool_left, int32_t pool_right, void* out_codes, void* out_scales,
+                                    void* stream);
 
 /* ---- K4: forward and NQ backward of one tensor in a single pass (benchmark path) ---
  * Same results as lq_fq_forward followed by lq_fq_scale_grad (out, max|q| and the vote count bit for bit; on

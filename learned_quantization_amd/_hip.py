@@ -201,6 +201,8 @@ SIGNATURES.update({
     "lq_i8_stem_conv2d": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, ctypes.POINTER(ConvGeom), _c_i64, _c_p]),
     "lq_i8_stem_conv2d_quantize": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, ctypes.POINTER(ConvGeom), _c_i64, _c_p, _c_p, _c_int, _c_int,
                                             _c_p, _c_p, _c_p]),
+    "lq_i8_stem_conv2d_quantize_pool": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, ctypes.POINTER(ConvGeom), _c_i64, _c_p, _c_p, _c_int, _c_int,
+                                                 _c_i32, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p]),
 })
 
 

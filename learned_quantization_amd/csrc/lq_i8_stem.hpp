@@ -164,6 +164,8 @@ __global__ __launch_bounds__(kBlock) void k_i8_stem_conv2d(const I8StemArgs<OUT>
         if constexpr (OUT) return q.c;
         else return q;
     }();
+    // The staging, the gather (`request`) and the epilogue value below are stated a second time in lq_i8_stem_pool.hpp (i8_stem_stage,
+    // i8_stem_gather, i8_stem_value): an edit to one is an edit to both
     extern __shared__ uint4 stem_lds[];               // [NTT][KH][64 lanes] fragments of 8 bytes
     const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
     const int32_t nt0 = (int32_t)blockIdx.y * NTT;    // OUT: grid.y = 1

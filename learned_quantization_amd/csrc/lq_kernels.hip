@@ -29,6 +29,7 @@
 //   lq_i8_direct_quant_wide.hpp  that epilogue for rows of up to 2048 filters: the output row parked in LDS
 //   lq_i8_direct_quant_pool.hpp  that epilogue behind a 2 x 2 max-pool taken in the accumulator registers
 //   lq_i8_stem.hpp      the direct int8 convolution of a first layer (C <= 4): row-scaled operand, a kernel row per step, B in LDS
+//   lq_i8_stem_pool.hpp the same with the 3 x 3 / 2 maximum in the pixel-operand epilogue: a strip of 16 conv columns per wave
 //   this file           host side: traversal plan, launchers, the extern "C" entry points
 //
 // The path is elementwise + per-group reductions: HBM-bound, no MFMA.  Design rules
@@ -88,6 +89,7 @@
 #include "lq_i8_direct_quant_wide.hpp"
 #include "lq_i8_direct_quant_pool.hpp"
 #include "lq_i8_stem.hpp"
+#include "lq_i8_stem_pool.hpp"
 
 namespace lq {
 
@@ -3055,10 +3057,12 @@ int lq_i8_stem_conv2d(const void* row_codes, const void* row_scales, const void*
     return check_hip("int8 stem convolution");
 }
 
-int lq_i8_stem_conv2d_quantize(const void* row_codes, const void* row_scales, const void* k_codes, const void* k_scales,
-                               const float* bias, const lq_conv_geom* g, int64_t co, const float* post_scale, const float* post_shift,
-                               int activation, int affine_first, void* out_codes, void* out_scales, void* stream) {
-    const char* fn = __func__;
+// the body of lq_i8_stem_conv2d_quantize and (pool_pads given: top, bottom, left, right of the 3 x 3 / 2 maximum; the lines written
+// are the pooled ones) lq_i8_stem_conv2d_quantize_pool
+static int i8_stem_conv2d_quantize_entry(const char* fn, const void* row_codes, const void* row_scales, const void* k_codes,
+                                         const void* k_scales, const float* bias, const lq_conv_geom* g, int64_t co,
+                                         const float* post_scale, const float* post_shift, int activation, int affine_first,
+                                         const int32_t* pool_pads, void* out_codes, void* out_scales, void* stream) {
     ConvDims cd;
     I8DirectDims dk{}, dout{};
     int rc = i8_stem_conv2d_dims(fn, g, co, cd, dk);
@@ -3071,13 +3075,29 @@ int lq_i8_stem_conv2d_quantize(const void* row_codes, const void* row_scales, co
     if ((post_scale == nullptr) != (post_shift == nullptr))
         return fail(LQ_EINVAL, "%s: post_scale and post_shift must both be given or both be NULL", fn);
     if ((rc = i8_pixels_dims(fn, g->B, co, cd.OH, cd.OW, dout))) return rc;      // what is written: M * CPo < 2^31
+    int64_t PH = 0, PW = 0;
+    if (pool_pads) {
+        for (int e = 0; e < 4; ++e)
+            if (pool_pads[e] != 0 && pool_pads[e] != 1)
+                return fail(LQ_EINVAL, "%s: pool padding (%d, %d, %d, %d): each of (top, bottom, left, right) is 0 or 1, so that every "
+                            "3 x 3 window holds an element of the conv output", fn, (int)pool_pads[0], (int)pool_pads[1], (int)pool_pads[2],
+                            (int)pool_pads[3]);
+        // floored, as F.max_pool2d(x, 3, 2) floors; a padded extent below 3 holds no window
+        PH = cd.OH + pool_pads[0] + pool_pads[1] >= 3 ? (cd.OH + pool_pads[0] + pool_pads[1] - 3) / 2 + 1 : 0;
+        PW = cd.OW + pool_pads[2] + pool_pads[3] >= 3 ? (cd.OW + pool_pads[2] + pool_pads[3] - 3) / 2 + 1 : 0;
+        if (PH < 1 || PW < 1)
+            return fail(LQ_EINVAL, "%s: the conv output (%lld x %lld) under pool padding (%d, %d, %d, %d) holds no 3 x 3 window", fn,
+                        (long long)cd.OH, (long long)cd.OW, (int)pool_pads[0], (int)pool_pads[1], (int)pool_pads[2], (int)pool_pads[3]);
+        if ((rc = i8_pixels_dims(fn, g->B, co, PH, PW, dout))) return rc;        // what is written: the pooled image's operand
+    }
     if ((rc = check_operand_buffers(fn, row_codes, row_scales, kI8ScaleAlign))) return rc;
     if ((rc = check_operand_buffers(fn, k_codes, k_scales, kI8ScaleAlign))) return rc;
     if ((rc = check_operand_buffers(fn, out_codes, out_scales, kI8ScaleAlign))) return rc;
     if ((rc = check_gemm_bias(fn, bias))) return rc;
     if (post_scale && (!aligned(post_scale, 4) || !aligned(post_shift, 4)))
         return fail(LQ_EALIGN, "%s: post_scale or post_shift is not 4-byte aligned", fn);
-    I8ConvQuantParams q{};
+    I8StemPoolParams qp{};
+    I8ConvQuantParams& q = qp;          // the launch without a pool passes this part alone
     dim3 unused;
     if ((rc = i8_conv2d_rule(fn, row_codes, row_scales, k_codes, k_scales, g, co, cd, dk, q.c, unused))) return rc;
     q.c.bias = bias;
@@ -3090,8 +3110,39 @@ int lq_i8_stem_conv2d_quantize(const void* row_codes, const void* row_scales, co
     q.affine_first = affine_first;
     q.CPo = (int32_t)dout.CP;
     q.OT = (int32_t)(dout.CP / kI8TileLines);
+    if (pool_pads) {                    // the kernel counts units: (image, block of R pooled rows, strip of 7 pooled columns)
+        const int64_t TS = (PW + kI8StemPoolWindows - 1) / kI8StemPoolWindows, RB = (PH + kI8StemPoolRows - 1) / kI8StemPoolRows;
+        qp.ts = make_fastdiv((uint32_t)TS);
+        qp.rb = make_fastdiv((uint32_t)RB);
+        qp.OH = (int32_t)cd.OH;
+        qp.OW = (int32_t)cd.OW;
+        qp.PH = (int32_t)PH;
+        qp.PW = (int32_t)PW;
+        qp.pool_top = pool_pads[0];
+        qp.pool_left = pool_pads[2];
+        qp.R = kI8StemPoolRows;
+        qp.units = (int32_t)(g->B * RB * TS);          // at most the pooled pixels, whose codes are below 2^31 bytes
+        i8_stem_conv2d_quantize_pool_launch(qp, (hipStream_t)stream);
+        return check_hip("int8 stem convolution with pooled pixel-operand epilogue");
+    }
     i8_stem_conv2d_launch<true>(q, q.c.MT, q.c.KH, q.OT, (hipStream_t)stream);
     return check_hip("int8 stem convolution with pixel-operand epilogue");
+}
+
+int lq_i8_stem_conv2d_quantize(const void* row_codes, const void* row_scales, const void* k_codes, const void* k_scales,
+                               const float* bias, const lq_conv_geom* g, int64_t co, const float* post_scale, const float* post_shift,
+                               int activation, int affine_first, void* out_codes, void* out_scales, void* stream) {
+    return i8_stem_conv2d_quantize_entry(__func__, row_codes, row_scales, k_codes, k_scales, bias, g, co, post_scale, post_shift,
+                                         activation, affine_first, nullptr, out_codes, out_scales, stream);
+}
+
+int lq_i8_stem_conv2d_quantize_pool(const void* row_codes, const void* row_scales, const void* k_codes, const void* k_scales,
+                                    const float* bias, const lq_conv_geom* g, int64_t co, const float* post_scale,
+                                    const float* post_shift, int activation, int affine_first, int32_t pool_top, int32_t pool_bottom,
+                                    int32_t pool_left, int32_t pool_right, void* out_codes, void* out_scales, void* stream) {
+    const int32_t pads[4] = {pool_top, pool_bottom, pool_left, pool_right};
+    return i8_stem_conv2d_quantize_entry(__func__, row_codes, row_scales, k_codes, k_scales, bias, g, co, post_scale, post_shift,
+                                         activation, affine_first, pads, out_codes, out_scales, stream);
 }
 
 static int i8_operand_decode(const char* fn, bool affine, bool w4, const void* codes, const void* scales, const void* offsets, int64_t L,

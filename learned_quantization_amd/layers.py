@@ -1121,7 +1121,7 @@ class _ConvBase(_HostLayer):
         scale = self.nested_q_k_layer.scale.data.reshape(-1)
         return ops.i8_stem_kernel_pack(self.kernel.detach().permute(3, 2, 0, 1), scale, qmin, qmax, self.rounding)
 
-    def call_i8_stem(self, inputs, max_lines=None, out_pixels=False, activation=None, affine=None, affine_first=False):
+    def call_i8_stem(self, inputs, max_lines=None, out_pixels=False, activation=None, affine=None, affine_first=False, pool=None):
         """The layer as a stem convolution, under ``no_grad``: the inputs (a tensor of at most 4 channels) quantised ONCE per image
         row to symmetric 8-bit integers (ops.i8_rows_quantize: an int8 NHWC4 copy, one scale per row), convolved with
         ``i8_stem_operand()`` by ops.i8_stem_conv2d -- a kernel row per step of the int8 matrix instruction, no padded channels, no
@@ -1130,8 +1130,14 @@ class _ConvBase(_HostLayer):
         activation scale is per image ROW here: the result is not bit-identical to ``call_i8`` or ``call_i8_direct``.
         ``out_pixels=True``: the result is the NEXT conv's ops.I8Pixels from the product's own epilogue
         (ops.i8_stem_conv2d_quantize) after ``activation`` and ``affine`` in the order ``affine_first`` says; at most 128 filters.
-        Without it an epilogue is refused."""
+        Without it an epilogue is refused.
+        ``pool=3`` (with ``out_pixels=True``): the epilogue takes the 3 x 3 maximum of stride 2 after the activation and the affine,
+        padded as TensorFlow pads a "same" pool of the conv's output extents ((0, 1) for an even extent, (1, 1) for an odd one), and
+        writes the pixel operand of the pooled image (ops.i8_stem_conv2d_quantize, ``pool``); refused without ``out_pixels``."""
         _check_max_lines(max_lines)
+        if pool is not None and not out_pixels:
+            raise ValueError(f"{self.name}: pool={pool!r} without out_pixels=True: the fp32 result has no epilogue to pool in; apply "
+                             "F.max_pool2d to the result")
         if not out_pixels and (activation is not None or affine is not None or affine_first):
             raise ValueError(f"{self.name}: the fp32 result takes no epilogue (activation={activation!r}, affine, affine_first): "
                              "apply it to the result, or ask for out_pixels=True")
@@ -1142,7 +1148,7 @@ class _ConvBase(_HostLayer):
         with torch.no_grad():
             operand = self.i8_stem_operand()
             qb = self.nested_q_b_layer(self.b) if self._has_bias else None
-            return self._direct_step(inputs, operand, qb, max_lines, out_pixels, activation, affine, affine_first)
+            return self._direct_step(inputs, operand, qb, max_lines, out_pixels, activation, affine, affine_first, pool=pool)
 
     def _direct_conv(self, inputs, operand, qb, max_lines=None):
         """The layer as a direct int8 convolution: per run of whole images (by lines) the pixel operand of the inputs, convolved
@@ -1178,11 +1184,12 @@ class _ConvBase(_HostLayer):
         ``residual`` (an ops.I8Pixels of the result's shape) is cut by the same images.  ``wide`` and ``pool``:
         ops.i8_conv2d_quantize's (a pool works inside an image, so the cut does not change it).  Where ``operand`` is an
         ops.I8StemKernel the step is the stem convolution: ``x`` a tensor, quantised per image row (ops.i8_rows_quantize), the
-        product ops.i8_stem_conv2d or its epilogue, which takes no residual, wide row or pool."""
+        product ops.i8_stem_conv2d or its epilogue, which takes no residual or wide row, and of the pools only 3: the 3 x 3 / 2
+        maximum under TensorFlow's "same" pool paddings of the conv's output extents (ops.i8_stem_conv2d_quantize, ``pool``)."""
         stem = isinstance(operand, ops.I8StemKernel)
-        if stem and (isinstance(x, ops.I8Pixels) or residual is not None or wide or pool is not None):
+        if stem and (isinstance(x, ops.I8Pixels) or residual is not None or wide or not (pool is None or (pool == 3 and not isinstance(pool, bool)))):
             raise ValueError(f"{self.name}: the stem convolution quantises a tensor itself and its epilogue takes no residual, wide "
-                             "row or pool")
+                             "row or pool other than 3")
 
         def images_of(px):        # a cut: the codes of whole images stay on the 16-byte grid (CP % 32 == 0); the scales may not
             def cut(b0, b1):
@@ -1210,8 +1217,10 @@ class _ConvBase(_HostLayer):
                                  f"{tuple(residual.shape) if isinstance(residual, ops.I8Pixels) else type(residual).__name__}")
             res = images_of(residual) if residual is not None else (lambda b0, b1: None)
             if stem:
-                outs = [ops.i8_stem_conv2d_quantize(run(b0, b1), operand, qb, self.strides, padding, activation, affine, affine_first)
-                        for b0, b1 in runs]
+                same = lambda n: (n % 2, 1)       # noqa: E731  a "same" 3 / 2 pool pads 1 in all (even) or 2 (odd), the lesser half first
+                pool_padding = (*same(OH), *same(OW)) if pool is not None else (0, 0, 0, 0)
+                outs = [ops.i8_stem_conv2d_quantize(run(b0, b1), operand, qb, self.strides, padding, activation, affine, affine_first,
+                                                    pool, pool_padding) for b0, b1 in runs]
             else:
                 outs = [ops.i8_conv2d_quantize(run(b0, b1), operand, qb, self.strides, padding, activation, affine, affine_first,
                                                res(b0, b1), wide, pool) for b0, b1 in runs]
@@ -1247,6 +1256,8 @@ class _ConvBase(_HostLayer):
         if pool is not None and not out_pixels:
             raise ValueError(f"{self.name}: pool={pool!r} without out_pixels=True: the fp32 result has no epilogue to pool in; apply "
                              "F.max_pool2d to the result")
+        if pool == 3 and not isinstance(pool, bool):
+            raise ValueError(f"{self.name}: pool=3: the 3 x 3 / 2 maximum is built in the stem convolution's epilogue only (call_i8_stem)")
         if not out_pixels and (activation is not None or affine is not None or affine_first or residual is not None):
             raise ValueError(f"{self.name}: the fp32 result takes no epilogue (activation={activation!r}, affine, affine_first, "
                              "residual): apply it to the result, or ask for out_pixels=True")
@@ -1516,15 +1527,31 @@ class i8_hardware(_matrix_hardware):
     row per step of the matrix instruction (ops.i8_stem_conv2d), no im2col matrix and no padded channels.  It is listed in
     ``stem_layers`` as well as in ``layers``.  With ``fused_convs`` / ``pooled_convs`` a stated chain that BEGINS with such a conv
     (of at most 128 filters) runs it through the stem entry and its pixel-operand epilogue (``i8_conv_chain(..., stem=True)``):
-    models.CIFARCNN then runs conv 1 to conv 6 with no padded-channel product.  The ResNets' stems write fp32 (their 3 x 3 / 2
-    max-pool is torch's).  The activation scale is per row there, so the outputs differ from ``stem_convs=False``; refused with
-    ``emulate``.  Without it (the default) nothing changes."""
+    models.CIFARCNN then runs conv 1 to conv 6 with no padded-channel product.  Without ``stem_pool`` the ResNets' stems write
+    fp32 and their 3 x 3 / 2 max-pool is torch's.  The activation scale is per row there, so the outputs differ from
+    ``stem_convs=False``; refused with ``emulate``.  Without it (the default) nothing changes.
+    ``stem_pool=True`` (with ``stem_convs=True`` and ``fused_convs=True``; ``wide_convs=True`` too for models.ResNet50Like): a model
+    that states ``i8_stem_chain()`` -- ``(chain, pools)``: its stem conv with activation and BatchNorm, and the 3 x 3 / 2 pool behind
+    it -- whose stem conv took the stem path (at most 128 filters) gets the chain parked with its affine as ``(g, h)``; where all its
+    blocks fuse, its eval forward runs ``i8_rows_quantize`` -> the pooled stem epilogue (ops.i8_stem_conv2d_quantize, ``pool=3``) ->
+    the blocks, int8 from the image rows to the last block, and the stem is listed in ``fused_conv_layers``.  The BatchNorm is then
+    ``bn_affine``'s product and sum, so the outputs differ from ``stem_pool=False`` in the last bits; bit for bit they are
+    ``call_i8_stem`` -> ``.mul(g)`` -> ``.add(h)`` -> relu -> ``F.pad(-inf)`` -> ``F.max_pool2d(3, 2)`` -> ``i8_pixels_quantize``
+    written out.  Refused without ``stem_convs`` and ``fused_convs``, or with ``emulate``.  Without it (the default)
+    ``i8_stem_chain`` is not read and nothing changes."""
 
     _family, _dense_eligible = _I8, staticmethod(i8_hardware_eligible)
 
     def __init__(self, model: nn.Module, act_block=0, emulate=False, convs=False, fused=False, offsets=False, direct=False,
-                 int4=False, fused_convs=False, wide_convs=False, pooled_convs=False, stem_convs=False):
+                 int4=False, fused_convs=False, wide_convs=False, pooled_convs=False, stem_convs=False, stem_pool=False):
         self.stem_convs, self.stem_layers, self._stem_modules = bool(stem_convs), [], []
+        self.stem_pool, self._stem_pool_modules = bool(stem_pool), []
+        if self.stem_pool and emulate:
+            raise ValueError("i8_hardware: emulate=True with stem_pool=True: the emulated path has no row-scaled operand and no "
+                             "pixel-operand epilogue")
+        if self.stem_pool and not (stem_convs and fused_convs):
+            raise ValueError("i8_hardware: stem_pool=True needs stem_convs=True and fused_convs=True: it takes the max-pool behind a "
+                             "stem convolution into its pixel-operand epilogue, which feeds the fused conv chains")
         if self.stem_convs and not (convs and direct):
             raise ValueError("i8_hardware: stem_convs=True needs convs=True and direct=True: it takes the first conv off the im2col "
                              "path that direct=True leaves it on")
@@ -1589,7 +1616,28 @@ class i8_hardware(_matrix_hardware):
             self.layers = dense + sorted(convs, key=lambda m: order[id(m)])
         if self.fused_convs:
             self._enter_fused_convs()
+        if self.stem_pool:
+            self._enter_stem_pool()
         return self
+
+    def _enter_stem_pool(self):
+        """A module that states ``i8_stem_chain()`` -- (chain, pools): one step, its stem conv -- whose conv ``stem_convs`` took
+        (at most 128 filters) and whose blocks ALL fused (its forward takes the pooled stem only then) gets the chain with its
+        affine as ``(g, h)`` and the pools; the conv is a fused layer then."""
+        for mod in self.model.modules():
+            if not callable(getattr(mod, "i8_stem_chain", None)):
+                continue
+            blocks = [b for b in mod.modules() if callable(getattr(b, "i8_fused", None))]
+            if not blocks or any(getattr(b, "_i8_fused_convs", None) is None or None in b._i8_fused_convs for b in blocks):
+                continue
+            chain, pools = mod.i8_stem_chain()
+            (c, act, aff, first), = chain
+            if c._i8_stem_hw is None or c.filters > ops.I8_STEM_QUANT_MAX_FILTERS or act not in ops.MX_ACTIVATIONS:
+                continue
+            c._i8_chain_hw = c._i8_stem_hw
+            mod._i8_stem_pool = ([(c, act, bn_affine(aff) if isinstance(aff, nn.BatchNorm2d) else aff, first)], list(pools))
+            self.fused_conv_layers.insert(0, c)
+            self._stem_pool_modules.append(mod)
 
     def _stated_chains(self, mod):
         """(chains, every, most) of a module: what it states as ``i8_conv_chains()``, whether it runs them with ``out_pixels=True``
@@ -1656,6 +1704,10 @@ class i8_hardware(_matrix_hardware):
         return True
 
     def __exit__(self, *exc):
+        for mod in self._stem_pool_modules:
+            mod._i8_stem_pool[0][0][0]._i8_chain_hw = None
+            mod._i8_stem_pool = None
+        self._stem_pool_modules = []
         for mod in self._pooled_conv_modules:
             for c, _, _, _ in mod._i8_pooled_convs[0]:
                 c._i8_chain_hw = None
@@ -1786,9 +1838,12 @@ def i8_conv_chain(x, chain, max_lines=None, out_pixels=False, wide=False, pools=
     a residual or has more than 512 filters.  So models.CIFARCNN's six convs are one chain (``i8_pooled_chain()``).
     ``stem=True``: the FIRST conv runs as a stem convolution (``call_i8_stem``): ``x``, a tensor of at most 4 channels, is quantised
     per image row and multiplied a kernel row per step, with no padded channels; where the step has an epilogue it is
-    ops.i8_stem_conv2d_quantize's (at most 128 filters, no residual, no pool).  The rest of the chain is unchanged.  Bit for bit
+    ops.i8_stem_conv2d_quantize's (at most 128 filters, no residual).  The rest of the chain is unchanged.  Bit for bit
     ``call_i8_stem`` -> relu -> ``.mul(g)`` -> ``.add(h)`` -> ``call_i8_direct`` ....  ValueError naming the reason for a first
-    conv that cannot take it (``i8_stem_eligible``).  Without it (the default) nothing changes."""
+    conv that cannot take it (``i8_stem_eligible``).  Without it (the default) nothing changes.
+    The stem step, and no other, takes 3 in ``pools``: the 3 x 3 maximum of stride 2 under TensorFlow's "same" pool paddings in the
+    stem epilogue (``call_i8_stem``, ``pool``), so a ResNet's stem is ``[(stem, "relu", bn0, True)]`` with ``pools=[3]``,
+    ``stem=True`` and ``out_pixels=True``: image rows in, the first block's pixel operand out."""
     fn = "i8_conv_chain"
     chain = [tuple(step) for step in chain]
     _check_max_lines(max_lines)
@@ -1807,16 +1862,18 @@ def i8_conv_chain(x, chain, max_lines=None, out_pixels=False, wide=False, pools=
         if epilogue and getattr(first, "filters", 0) > ops.I8_STEM_QUANT_MAX_FILTERS:
             raise ValueError(f"{fn}: stem=True: {first.name}: {first.filters} filters: the stem epilogue holds a whole output row in one "
                              f"wave, at most {ops.I8_STEM_QUANT_MAX_FILTERS}")
-        if (pools is not None and list(pools)[:1] not in ([], [None])) or (len(chain[0]) == 5 and chain[0][4] is not None):
-            raise ValueError(f"{fn}: stem=True: the stem epilogue takes no pool and no residual")
+        if (pools is not None and list(pools)[:1] not in ([], [None], [3])) or (len(chain[0]) == 5 and chain[0][4] is not None):
+            raise ValueError(f"{fn}: stem=True: the stem epilogue takes no pool but 3 (the 3 x 3 / 2 maximum) and no residual")
     pools = [None] * len(chain) if pools is None else list(pools)
     if len(pools) != len(chain):
         raise ValueError(f"{fn}: pools has {len(pools)} entries for {len(chain)} steps: one per step, None or 2")
     for k, pool in enumerate(pools):
         if pool is None:
             continue
-        if isinstance(pool, bool) or pool != 2:
-            raise ValueError(f"{fn}: step {k}: pool={pool!r}: only the non-overlapping 2 x 2 maximum (2) is built, or None")
+        on_stem = stem and k == 0 and pool == 3 and not isinstance(pool, bool)
+        if not on_stem and (isinstance(pool, bool) or pool != 2):
+            raise ValueError(f"{fn}: step {k}: pool={pool!r}: only the non-overlapping 2 x 2 maximum (2) is built, or None; the 3 x 3 "
+                             "/ 2 maximum (3) on the step of a stem convolution (stem=True, step 0) only")
         if k == len(chain) - 1 and not out_pixels:
             raise ValueError(f"{fn}: step {k}: a pool on the last layer, which writes fp32: apply F.max_pool2d to the result, or ask "
                              "for out_pixels=True")

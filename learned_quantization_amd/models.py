@@ -238,17 +238,26 @@ class ResNet18Like(nn.Module):
         if device is not None:
             self.to(device)
 
+    def i8_stem_chain(self):
+        """The stem as layers.i8_conv_chain takes it with ``stem=True, out_pixels=True``: (chain, pools) -- conv -> BN -> relu and the
+        3 x 3 / 2 "same" max-pool behind it.  Read by layers.i8_hardware under ``stem_pool=True`` only."""
+        return [(self.stem, "relu", self.bn0, True)], [3]
+
     def forward(self, x):
-        x = F.relu(self.bn0(self.stem(x)))
-        # MaxPooling2D(pool 3, stride 2, padding "same"): for even extents TF pads (0, 1); -inf padding
-        h, w = x.shape[-2:]
-        ph = max((-(-h // 2) - 1) * 2 + 3 - h, 0)
-        pw = max((-(-w // 2) - 1) * 2 + 3 - w, 0)
-        x = F.pad(x, (pw // 2, pw - pw // 2, ph // 2, ph - ph // 2), value=float("-inf"))
-        x = self.drop0(F.max_pool2d(x, 3, 2))
         fused = [b.i8_fused() for b in self.blocks]               # inside layers.i8_hardware(..., fused_convs=True), eval mode
-        if not self.training and all(f is not None for f in fused):
-            a = i8_pixels_quantize(x)                             # the one quantisation: int8 pixel operands from here to the last conv
+        int8 = not self.training and all(f is not None for f in fused)
+        pooled = getattr(self, "_i8_stem_pool", None) if int8 else None       # layers.i8_hardware(..., stem_pool=True)
+        if pooled is None:
+            x = F.relu(self.bn0(self.stem(x)))
+            # MaxPooling2D(pool 3, stride 2, padding "same"): for even extents TF pads (0, 1); -inf padding
+            h, w = x.shape[-2:]
+            ph = max((-(-h // 2) - 1) * 2 + 3 - h, 0)
+            pw = max((-(-w // 2) - 1) * 2 + 3 - w, 0)
+            x = F.pad(x, (pw // 2, pw - pw // 2, ph // 2, ph - ph // 2), value=float("-inf"))
+            x = self.drop0(F.max_pool2d(x, 3, 2))
+        if int8:
+            # the one quantisation: int8 pixel operands from here to the last conv; with the pooled stem, from the image rows on
+            a = i8_pixels_quantize(x) if pooled is None else i8_conv_chain(x, pooled[0], out_pixels=True, stem=True, pools=pooled[1])
             for b, f in zip(self.blocks[:-1], fused):
                 a = b.forward_pixels(a, f)
             x = self.blocks[-1].forward_pixels(a, fused[-1], fp32_out=True)
@@ -351,16 +360,22 @@ class ResNet50Like(nn.Module):
         if device is not None:
             self.to(device)
 
+    i8_stem_chain = ResNet18Like.i8_stem_chain
+
     def forward(self, x):
-        x = F.relu(self.bn0(self.stem(x)))
-        h, w = x.shape[-2:]
-        ph = max((-(-h // 2) - 1) * 2 + 3 - h, 0)
-        pw = max((-(-w // 2) - 1) * 2 + 3 - w, 0)
-        x = F.pad(x, (pw // 2, pw - pw // 2, ph // 2, ph - ph // 2), value=float("-inf"))
-        x = F.max_pool2d(x, 3, 2)
         fused = [b.i8_fused() for b in self.blocks]       # inside layers.i8_hardware(..., fused_convs=True, wide_convs=True), eval mode
-        if not self.training and all(f is not None for f in fused):
-            a = i8_pixels_quantize(x)                     # the one quantisation: int8 pixel operands from here to the last conv
+        int8 = not self.training and all(f is not None for f in fused)
+        pooled = getattr(self, "_i8_stem_pool", None) if int8 else None       # layers.i8_hardware(..., stem_pool=True)
+        if pooled is None:
+            x = F.relu(self.bn0(self.stem(x)))
+            h, w = x.shape[-2:]
+            ph = max((-(-h // 2) - 1) * 2 + 3 - h, 0)
+            pw = max((-(-w // 2) - 1) * 2 + 3 - w, 0)
+            x = F.pad(x, (pw // 2, pw - pw // 2, ph // 2, ph - ph // 2), value=float("-inf"))
+            x = F.max_pool2d(x, 3, 2)
+        if int8:
+            # the one quantisation: int8 pixel operands from here to the last conv; with the pooled stem, from the image rows on
+            a = i8_pixels_quantize(x) if pooled is None else i8_conv_chain(x, pooled[0], out_pixels=True, stem=True, pools=pooled[1])
             for b, f in zip(self.blocks[:-1], fused):
                 a = b.forward_pixels(a, f)
             x = self.blocks[-1].forward_pixels(a, fused[-1], fp32_out=True)

@@ -1532,13 +1532,36 @@ def i8_stem_conv2d(rows: I8Rows, kernel: I8StemKernel, bias: Optional[torch.Tens
     return out
 
 
+def _i8_stem_pool_dims(OH: int, OW: int, pool_padding=(0, 0, 0, 0)) -> Tuple[int, int]:
+    """``(PH, PW)`` of the 3 x 3 / 2 maximum of a conv output ``OH x OW`` under ``pool_padding`` (top, bottom, left, right), floored
+    as ``F.max_pool2d(x, 3, 2)`` floors; ValueError for a padding outside {0, 1} or an output that holds no window."""
+    pads = tuple(pool_padding)
+    if len(pads) != 4 or any(isinstance(e, bool) or e not in (0, 1) for e in pads):
+        raise ValueError(f"pool_padding={pool_padding!r}: (top, bottom, left, right), each 0 or 1, so that every 3 x 3 window holds an "
+                         "element of the conv output")
+    PH, PW = (OH + pads[0] + pads[1] - 3) // 2 + 1, (OW + pads[2] + pads[3] - 3) // 2 + 1
+    if OH + pads[0] + pads[1] < 3 or OW + pads[2] + pads[3] < 3:
+        raise ValueError(f"pool=3: the conv output ({OH} x {OW}) under pool_padding {pads} holds no 3 x 3 window")
+    return PH, PW
+
+
 def i8_stem_conv2d_quantize(rows: I8Rows, kernel: I8StemKernel, bias: Optional[torch.Tensor] = None, strides=(1, 1),
-                            padding=(0, 0, 0, 0), activation=None, affine=None, affine_first: bool = False) -> I8Pixels:
+                            padding=(0, 0, 0, 0), activation=None, affine=None, affine_first: bool = False,
+                            pool: Optional[int] = None, pool_padding=(0, 0, 0, 0)) -> I8Pixels:
     """The pixel operand of the NEXT conv, written by the stem product's own epilogue (include/lq_hip.h,
     lq_i8_stem_conv2d_quantize): byte for byte ``i8_pixels_quantize`` of ``v`` seen as ``(B, co, OH, OW)``, with ``v`` made from
     ``i8_stem_conv2d``'s ``Y`` by ``activation``, ``affine = (g, h)`` and ``affine_first`` exactly as ``i8_conv2d_quantize`` makes it
-    from ``i8_conv2d``'s.  One launch; no fp32 matrix.  ``co`` above 128 is refused."""
+    from ``i8_conv2d``'s.  One launch; no fp32 matrix.  ``co`` above 128 is refused.
+    ``pool=3``: the epilogue takes the overlapping 3 x 3 maximum of stride 2 of ``v`` under ``pool_padding`` (top, bottom, left,
+    right; each 0 or 1, padded with -inf) -- a ResNet's stem: conv, BatchNorm, relu, pad, MaxPool(3, 2) -- and writes the pixel
+    operand of the POOLED image (lq_i8_stem_conv2d_quantize_pool): byte for byte ``i8_pixels_quantize(F.max_pool2d(F.pad(v,
+    (left, right, top, bottom), value=-inf), 3, 2))``, shape ``(B, co, PH, PW)`` (``_i8_stem_pool_dims``), still one launch.  Any
+    other value is a ValueError, and so is a ``pool_padding`` without ``pool``.  Without it (the default) nothing changes."""
     import ctypes
+    if pool is not None and (isinstance(pool, bool) or pool != 3):
+        raise ValueError(f"pool={pool!r}: only the 3 x 3 maximum of stride 2 (pool=3) is built in the stem epilogue, or None")
+    if pool is None and tuple(pool_padding) != (0, 0, 0, 0):
+        raise ValueError(f"pool_padding={pool_padding!r} without pool=3")
     act = check_mx_activation(activation)
     dev = _check_i8_stem_operands(rows, kernel)
     co = kernel.filters
@@ -1548,13 +1571,16 @@ def i8_stem_conv2d_quantize(rows: I8Rows, kernel: I8StemKernel, bias: Optional[t
     g = _conv_geom(rows.shape, (0, 0, 0, 0), kernel.kernel_size, strides, padding)
     _, _, OH, OW = _geom_dims(lib, g)
     B = int(rows.shape[0])
+    name, pads = "lq_i8_stem_conv2d_quantize", ()
+    if pool is not None:
+        OH, OW = _i8_stem_pool_dims(OH, OW, pool_padding)
+        name, pads = name + "_pool", tuple(int(e) for e in pool_padding)
     cb, _ = i8_pixels_bytes(B, co, OH, OW)
     codes = torch.empty((B, OH, OW, cb // (B * OH * OW)), dtype=torch.uint8, device=dev)
     scales = torch.empty((B, OH, OW), dtype=torch.float32, device=dev)
-    _hip.check(lib.lq_i8_stem_conv2d_quantize(_hip.ptr(rows.codes), _hip.ptr(rows.scales), _hip.ptr(kernel.codes), _hip.ptr(kernel.scales),
-                                              _hip.ptr(bias), ctypes.byref(g), co, _hip.ptr(post[0]), _hip.ptr(post[1]), act,
-                                              int(bool(affine_first)), _hip.ptr(codes), _hip.ptr(scales), _hip.stream_ptr(dev)),
-               "lq_i8_stem_conv2d_quantize")
+    _hip.check(getattr(lib, name)(_hip.ptr(rows.codes), _hip.ptr(rows.scales), _hip.ptr(kernel.codes), _hip.ptr(kernel.scales),
+                                  _hip.ptr(bias), ctypes.byref(g), co, _hip.ptr(post[0]), _hip.ptr(post[1]), act,
+                                  int(bool(affine_first)), *pads, _hip.ptr(codes), _hip.ptr(scales), _hip.stream_ptr(dev)), name)
     return I8Pixels(codes, scales, (B, co, OH, OW))
 
 

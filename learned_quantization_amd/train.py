@@ -660,6 +660,11 @@ def build_parser():
                          "first conv, of at most 4 input channels, quantised per image row and multiplied a kernel row per step of the "
                          "matrix instruction instead of through im2col) and add i8_eval_stem_conv_layers, _accuracy and "
                          "_max_logit_diff (from the same call without it) to the result")
+    ap.add_argument("--i8-eval-stem-pool", action="store_true",
+                    help="with --i8-eval-stem-convs --i8-eval-fused-convs: evaluate once more under layers.i8_hardware(..., "
+                         "stem_convs=True, fused_convs=True, stem_pool=True) (a model that states i8_stem_chain(), as the ResNets do, "
+                         "takes the 3 x 3 / 2 max-pool behind its stem in the stem convolution's epilogue) and add "
+                         "i8_eval_stem_pool_layers, _accuracy and _max_logit_diff (from the same call without it) to the result")
     ap.add_argument("--i8-eval-fused", action="store_true",
                     help="with --i8-eval --i8-eval-act-block 64: evaluate once more under layers.i8_hardware(fused=True) (the Dense "
                          "tail through layers.i8_dense_chain: relu and the next operand's quantisation, per row and block of 64, in "
@@ -679,7 +684,7 @@ def build_parser():
 
 @torch.no_grad()
 def i8_eval(model, x, y, act_block=0, convs=False, fused=False, offsets=False, direct=False, int4=False, fused_convs=False,
-            wide_convs=False, pooled_convs=False, stem_convs=False):
+            wide_convs=False, pooled_convs=False, stem_convs=False, stem_pool=False):
     """One evaluation of ``model`` on (x, y) under layers.i8_hardware, one under its ``emulate=True`` yardstick and one of the
     fake-quantised model as it stands: a dict of the three accuracies and the largest |difference| of the outputs of the last Dense
     layer that took the path (the logits of the MNIST model) between the hardware path and each of the other two.  ValueError for
@@ -703,7 +708,10 @@ def i8_eval(model, x, y, act_block=0, convs=False, fused=False, offsets=False, d
     BatchNorm before it is ``bn_affine``'s in the epilogue instead of torch's kernel).  ``stem_convs=True`` (with ``convs`` and
     ``direct``) adds an evaluation under ``i8_hardware(..., stem_convs=True)`` beside the conv flags as given: the convs on the stem
     convolution (the first conv of each model here), the accuracy, and the largest |difference| of the model's outputs from the
-    same call without it (reported: the activation scale is per image row there)."""
+    same call without it (reported: the activation scale is per image row there).  ``stem_pool=True`` (with ``stem_convs`` and
+    ``fused_convs``) adds an evaluation under ``i8_hardware(..., stem_convs=True, fused_convs=True, stem_pool=True)``: the convs with
+    an epilogue, the stem among them, the accuracy, and the largest |difference| of the model's outputs from the same call without
+    it (reported, not expected to be 0.0: the pool is exact, the BatchNorm before it becomes ``bn_affine``'s)."""
     was_training = model.training
     model.eval()
     acc, logits = [], []
@@ -796,6 +804,19 @@ def i8_eval(model, x, y, act_block=0, convs=False, fused=False, offsets=False, d
                     outs.append(model(x))
             fields.update({"i8_eval_stem_conv_layers": n_stem, "i8_eval_stem_conv_accuracy": float((outs[0].argmax(1) == y).float().mean()),
                            "i8_eval_stem_conv_max_logit_diff": float((outs[0] - outs[1]).abs().max())})
+        if convs and direct and stem_convs and fused_convs and stem_pool:
+            outs = []
+            for sp in (True, False):
+                with L.i8_hardware(model, probe.act_block, convs=True, offsets=offsets, direct=True, fused_convs=True,
+                                   wide_convs=wide_convs, pooled_convs=pooled_convs, stem_convs=True, stem_pool=sp) as hwp:
+                    if sp and not hwp._stem_pool_modules:
+                        raise ValueError("i8_eval: stem_pool=True needs a model that states its stem as i8_stem_chain() (as the "
+                                         "ResNets of models do) with a conv that can run as a stem convolution of at most 128 filters")
+                    if sp:
+                        n_stem_pool = len(hwp.fused_conv_layers)
+                    outs.append(model(x))
+            fields.update({"i8_eval_stem_pool_layers": n_stem_pool, "i8_eval_stem_pool_accuracy": float((outs[0].argmax(1) == y).float().mean()),
+                           "i8_eval_stem_pool_max_logit_diff": float((outs[0] - outs[1]).abs().max())})
         if int4:
             outs = []
             for i4 in (True, False):
@@ -909,6 +930,9 @@ def main(argv=None):
     if args.i8_eval_stem_convs and not (args.i8_eval_convs and args.i8_eval_direct):
         ap.error("--i8-eval-stem-convs needs --i8-eval-convs --i8-eval-direct: it takes the first conv off the im2col path that the "
                  "direct path leaves it on")
+    if args.i8_eval_stem_pool and not (args.i8_eval_stem_convs and args.i8_eval_fused_convs):
+        ap.error("--i8-eval-stem-pool needs --i8-eval-stem-convs --i8-eval-fused-convs: it takes the max-pool behind the stem "
+                 "convolution into its epilogue, which feeds the fused conv chains")
     if args.i8_eval_fused and not args.i8_eval:
         ap.error("--i8-eval-fused needs --i8-eval: it compares the fused Dense tail with the unfused hardware path")
     if args.i8_eval_fused and args.i8_eval_act_block != 64:
@@ -982,7 +1006,7 @@ def main(argv=None):
     quant_stats = L.quant_stats(tr.model) if args.quant_stats and rank == 0 else None      # after the clock has stopped
     mx_stats = L.mx_quant_stats(tr.model) if args.mx_stats and rank == 0 else None
     mx_eval_fields = mx_eval(tr.model, *batches[0], act_format=args.mx_eval, fused=args.mx_eval_fused, convs=args.mx_eval_convs, fp6=args.mx_eval_fp6) if args.mx_eval is not None and rank == 0 else None
-    i8_eval_fields = i8_eval(tr.model, *batches[0], act_block=args.i8_eval_act_block, convs=args.i8_eval_convs, fused=args.i8_eval_fused, offsets=args.i8_eval_offsets, direct=args.i8_eval_direct, int4=args.i8_eval_int4, fused_convs=args.i8_eval_fused_convs, wide_convs=args.i8_eval_wide_convs, pooled_convs=args.i8_eval_pooled_convs, stem_convs=args.i8_eval_stem_convs) if args.i8_eval and rank == 0 else None
+    i8_eval_fields = i8_eval(tr.model, *batches[0], act_block=args.i8_eval_act_block, convs=args.i8_eval_convs, fused=args.i8_eval_fused, offsets=args.i8_eval_offsets, direct=args.i8_eval_direct, int4=args.i8_eval_int4, fused_convs=args.i8_eval_fused_convs, wide_convs=args.i8_eval_wide_convs, pooled_convs=args.i8_eval_pooled_convs, stem_convs=args.i8_eval_stem_convs, stem_pool=args.i8_eval_stem_pool) if args.i8_eval and rank == 0 else None
     if rank == 0:
         n_q = sum(p.numel() for l in tr.custom_layers for p in l._regularized())
         print(json.dumps({
